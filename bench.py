@@ -140,6 +140,21 @@ def make_inputs(cfgd, B, S, dev, seed):
     return init, ctx, gen
 
 
+DUMP_MAX_ELEMS = 15 << 20     # --dump-outputs: float32 elements written (60 MiB, under 64 MB with the .npy header)
+
+
+def dump_output(out_dir, name, t):
+    """--dump-outputs: one array the timed path returned, as float32 DIR/<name>.npy.  Above DUMP_MAX_ELEMS it is written as
+    DIR/<name>_sample.npy, a fixed sample of its flattened elements (seeded, sorted indices: the same for the same shape), so that
+    two builds run with the same arguments compare element for element."""
+    a = t.detach().float().cpu().numpy()
+    if a.size > DUMP_MAX_ELEMS:
+        idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+        a, name = a.reshape(-1)[idx], name + "_sample"
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def read_prof(L, h):
     """Per-class and per-op hipEvent tables of the handle (sampled DDIM iterations inside the timed region)."""
     classes = {}
@@ -444,12 +459,17 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the informational compressor / entropy coder legs (profiling runs)")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the timed decodes of BASELINE configs[2] and configs[4]")
     ap.add_argument("--dump-ops", default=None, help="write the launch program's op labels (program order) to this file (profiling tools)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the decoded images of the last timed step to DIR/reconstruction.npy (float32; a fixed seeded "
+                         "sample of at most 64 MB, DIR/reconstruction_sample.npy, when larger)")
     ap.add_argument("--prof-every", type=int, default=125,
                     help="hipEvent pairs around every launch of the DDIM iterations i %% N == 0 (inside the timed region: roofline.sampling)")
     ap.add_argument("--launch-check", action="store_true",
                     help="rendezvous only: every rank joins the process group, one all_reduce counts the ranks, rank 0 prints "
                          "{launch_check, ranks_seen, launcher}; no GPU work (CPU test of the self-launch path, gloo)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.sample_steps is None:
         a.sample_steps = 500 if a.param == "x" else 1000
 
@@ -529,6 +549,8 @@ def main():
     lo, hi = parallel.shard_bounds(B * world, world, rank)
     rec = full[lo:hi]
     ok = bool(torch.isfinite(full).all().item()) and tuple(full.shape) == (B * world, 3, S, S)
+    if rank == 0 and a.dump_outputs:
+        dump_output(a.dump_outputs, "reconstruction", full)      # the gathered batch: what a caller of the timed path receives
     arith = L.cdc_get_arith(h)
 
     classes, ops = read_prof(L, h)

@@ -1,13 +1,17 @@
 """Helper of tests/test_gpu_parity.py (separate processes: some switches are read once): one U-Net forward with the round-4 plane-operand
 forms and the round-5 few-pixel kernels on (default) against all of them off, on frame sizes whose tiles are ragged -- the two programs
 must agree to rounding."""
-import os, sys, subprocess
+import os, sys, subprocess, tempfile
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))     # (the repository root: this file lives in tests/)
 OFF = {"CDC_NO_PF_S2": "1", "CDC_NO_PF_TZ": "1", "CDC_NO_PF_17": "1", "CDC_NO_PF_UF": "1", "CDC_NO_RESID_PF": "1", "CDC_NO_PF_SKIP_PLANES": "1",
        "CDC_NO_RESID2": "1", "CDC_NO_CTX_ONE": "1", "CDC_WS_MIN_WGS": "100000000", "CDC_WS1_MIN_WGS": "100000000"}
 
+# the arrays pass through a directory private to this run (a fixed name under /tmp may belong to another user)
+TMP = tempfile.TemporaryDirectory(prefix="cdc_ab_forward_")
+
 def run(tag, B, H, W, off):
+    path = os.path.join(TMP.name, "ab_%s.npy" % tag)
     code = r'''
 import os, sys, numpy as np
 sys.path.insert(0, %r)
@@ -23,12 +27,12 @@ ctx = [synth.normal("ctx%%d" %% l, (B, c, H >> l, W >> l), 3, 0.5) for l, c in e
 y = un(x, t, ctx)
 np.save(%r, y)
 print(un.status())
-''' % (ROOT, B, H, W, "/tmp/ab_%s.npy" % tag)
+''' % (ROOT, B, H, W, path)
     env = dict(os.environ, CDC_DEV="1")
     if off:
         env.update(OFF)
     subprocess.run([sys.executable, "-c", code], env=env, check=True)
-    return np.load("/tmp/ab_%s.npy" % tag)
+    return np.load(path)
 
 worst = 0.0
 SHAPES = [(4, 160, 224), (2, 288, 352), (16, 64, 96), (8, 256, 256), (3, 320, 192)]

@@ -1402,7 +1402,8 @@ def test_bench_under_torchrun_one_rank_nccl(tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", "29611", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1",
-           "--warmup", "0", "--batch", "3", "--sample-steps", "6", "--size", "64", "--no-cpu-baseline", "--prof-every", "2"]
+           "--warmup", "0", "--batch", "3", "--sample-steps", "6", "--size", "64", "--no-cpu-baseline", "--prof-every", "2",
+           "--dump-outputs", str(tmp_path / "out")]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -1410,6 +1411,15 @@ def test_bench_under_torchrun_one_rank_nccl(tmp_path):
     assert d["n_gpus"] == 1 and d["config"]["rccl_ranks_seen"] == 1
     assert d["config"]["global_batch"] == 3 and d["config"]["finite"] is True
     assert d["value"] > 0 and d["roofline"]["achieved"] >= 0
+    # --dump-outputs: the decoded batch of the timed step = the same decode of the same seeded inputs run here
+    import bench
+    import torch
+    got = np.load(tmp_path / "out" / "reconstruction.npy")
+    assert got.dtype == np.float32 and got.shape == (3, 3, 64, 64)
+    un, diff, cfgd = bench.build_model("x", 0)
+    init, ctx, _ = bench.make_inputs(cfgd, 3, 64, torch.device("cuda", 0), 1000)
+    want = diff.decompress(ctx, (3, 3, 64, 64), sample_steps=6, init=init).cpu().numpy()
+    assert relerr(got, want) < 1e-5, relerr(got, want)
 
 
 def test_bench_multi_rank_branch_two_ranks_on_one_gpu():

@@ -206,3 +206,22 @@ def test_bench_roofline_object_leads_with_its_scalars():
     assert all(not isinstance(r[k], (dict, list)) for k in lead)
     assert abs(r["frac_of_measured_sustained"] - r["mfma_tflops_executed"] / 1500.0) < 1e-9
     assert r["kernel"] == "conv_pf3_kernel" and r["launches_per_iteration"] == 2
+
+
+def test_bench_dump_outputs_whole_or_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the timed path's output as float32 .npy, whole when small; above the cap a seeded sample of
+    its elements that is the same from run to run, so that two builds compare element for element."""
+    import torch
+    import bench
+    t = torch.randn(2, 3, 8, 8, generator=torch.Generator().manual_seed(0))
+    bench.dump_output(str(tmp_path / "a"), "reconstruction", t)
+    a = np.load(tmp_path / "a" / "reconstruction.npy")
+    assert a.dtype == np.float32 and a.shape == (2, 3, 8, 8)
+    np.testing.assert_array_equal(a, t.numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 100)
+    for d in ("b", "c"):
+        bench.dump_output(str(tmp_path / d), "reconstruction", t)
+    b, c = (np.load(tmp_path / d / "reconstruction_sample.npy") for d in ("b", "c"))
+    assert b.dtype == np.float32 and b.shape == (100,) and not os.path.exists(tmp_path / "b" / "reconstruction.npy")
+    np.testing.assert_array_equal(b, c)
+    assert np.isin(b, t.numpy().ravel()).all()
