@@ -161,7 +161,7 @@ struct Builder {
         emit(op);
         t->only = false;
         ++n_unpacked;
-        if (getenv("CDC_DEBUG_PLAN")) fprintf(stderr, "[plan] planes-only tensor %dx%dx%d unpacked for an fp32 reader\n", t->C, t->H, t->W);
+        if (debug_plan()) fprintf(stderr, "[plan] planes-only tensor %dx%dx%d unpacked for an fp32 reader\n", t->C, t->H, t->W);
         return true;
     }
     int n_unpacked = 0;
@@ -213,14 +213,80 @@ struct Builder {
         bool pf_only = false;                          // plan with conv_pf_kernel or return false
         bool no_f32 = false;                           // PF path only: nobody reads the fp32 copy of `out`
         int uf_c = 0, uf_pad = 0;                      // unfold on load (ConvArgs::uf_c): s0 is the uf_c-channel image, w a KH x 1 layer over KW*uf_c channels
+        // a linear epilogue: bias and residual at most (no LayerNorm, activation, shift, statistics, hoisted partial sums, res_conv)
+        bool linear_epilogue() const { return !ln_g && !relu && !shift && !stat_mean && !pre_add && !res3_w; }
     };
     int last_ksplit = 1;                               // slices the last conv() call really used
     bool last_pf_only = false;                         // the last conv() call wrote its result as planes only (no fp32 copy exists)
     const float *next_res3_w = nullptr, *next_res3_x = nullptr; long long next_res3_bs = 0;   // for the next block()
+    static bool debug_plan() { return getenv("CDC_DEBUG_PLAN") != nullptr; }   // (read per call: a caller may switch it)
+
+    // ---- the forms of the plane-operand kernels (conv_pf_kernel / conv_pf3_kernel / conv_pw_kernel): the weight and geometry
+    // conditions of one form and its PfShape, for an INPUT map of H x W (C0 > 0: two sources, C0 channels in the first).  The
+    // predictions (*_would_plan: will a reader take planes?  asked before the reader is planned) and the try_* that plan the launch
+    // call the same function; a try_* adds only the conditions of its operation.
+    PfShape pf_shape(const ConvW &w, int C0, int Ho, int Wo, bool need_all) const {
+        PfShape ps;
+        ps.Cin = w.Cin; ps.Cout = w.Cout; ps.C0 = C0; ps.KH = w.KH; ps.KW = w.KW; ps.nz = w.nz; ps.Ho = Ho; ps.Wo = Wo; ps.B = pb();
+        ps.need_all_cout = need_all; ps.cop = w.COP;
+        return ps;
+    }
+    // 3x3 / 1x1, stride 1, "same" padding
+    bool pf_form(const ConvW &w, int C0, int H, int W, bool need_all, PfShape *ps) const {
+        if (!w.wsh || w.stride != 1 || w.transposed || (w.Cin % 16) || !((w.KH == 3 && w.KW == 3) || (w.KH == 1 && w.KW == 1))) return false;
+        if (w.py() != w.KH / 2 || w.px() != w.KW / 2) return false;
+        *ps = pf_shape(w, C0, H, W, need_all);
+        return true;
+    }
+    // the Downsample: 3x3 / stride 2 / pad 1 on even extents, single source (STR = 2)
+    bool pf_s2_form(const ConvW &w, int C0, int H, int W, bool need_all, PfShape *ps) const {
+        if (!w.wsh || w.stride != 2 || w.transposed || w.KH != 3 || w.KW != 3 || C0 || (H & 1) || (W & 1) || (w.Cin % 16)) return false;
+        if (w.py() != 1 || w.px() != 1) return false;
+        *ps = pf_shape(w, 0, H / 2, W / 2, need_all);
+        ps->stride = 2;
+        return true;
+    }
+    // the Upsample: ConvTranspose2d 4x4 / stride 2 / pad 1, its four 2x2 phases fused in one workgroup (TZ = 4), single source
+    bool pf_tz_form(const ConvW &w, int C0, int H, int W, bool need_all, PfShape *ps) const {
+        if (!w.wsh || !w.transposed || w.tk != 4 || w.KH != 2 || w.KW != 2 || C0 || (w.Cin % 16)) return false;
+        *ps = pf_shape(w, 0, H, W, need_all);
+        ps->tz = 4;
+        return true;
+    }
+    // the row-folded final convolution: 1x7 / pad (0, 3), single source
+    bool pf_17_form(const ConvW &w, int C0, int H, int W, bool need_all, PfShape *ps) const {
+        if (!w.wsh || w.KH != 1 || w.KW != 7 || w.stride != 1 || w.transposed || C0 || (w.Cin % 16)) return false;
+        if (w.py() != 0 || w.px() != 3) return false;
+        *ps = pf_shape(w, 0, H, W, need_all);
+        return true;
+    }
+    // the first layer: 7x1 / pad (3, 0) over the kx-unfolded 3-channel image, patches built from the image in the kernel (UF)
+    bool pf_uf_form(const ConvW &w, int H, int W, bool need_all, PfShape *ps) const {
+        if (!w.wsh || w.KH != 7 || w.KW != 1 || w.stride != 1 || w.transposed || w.nz != 1 || w.py() != 3 || w.px() != 0) return false;
+        *ps = pf_shape(w, 0, H, W, need_all);
+        ps->uf = 3;
+        return true;
+    }
+    // pointwise: 1x1 / stride 1 / pad 0 (conv_pw_kernel; conv_ws1_kernel takes the same form)
+    bool pw_form(const ConvW &w, int C0, int H, int W, PfShape *ps) const {
+        if (!w.wsh || w.KH != 1 || w.KW != 1 || w.stride != 1 || w.transposed || w.nz != 1 || w.py() != 0 || w.px() != 0) return false;
+        *ps = pf_shape(w, C0, H, W, false);
+        return true;
+    }
+    static bool pf_plans(const PfShape &ps) { PfPlan plan; return pf_make_plan(ps, &plan); }
+
+    // Would a single-source 3x3 / 1x1 layer with fused LayerNorm run on conv_pf_kernel (given a PF input)?
+    bool pf_would_plan(const ConvW &w, int H, int W) { PfShape ps; return pf_on() && pf_form(w, 0, H, W, true, &ps) && pf_plans(ps); }
+    // ... a Downsample, given a PF input of H x W?
+    bool pf_s2_would_plan(const ConvW &w, int H, int W) { PfShape ps; return pf_on() && pf_s2_form(w, 0, H, W, false, &ps) && pf_plans(ps); }
+    // ... an Upsample?
+    bool pf_tz_would_plan(const ConvW &w, int H, int W) { PfShape ps; return pf_on() && pf_tz_form(w, 0, H, W, false, &ps) && pf_plans(ps); }
+    // ... the row-folded final convolution?
+    bool pf_17_would_plan(const ConvW &w, int H, int W) { PfShape ps; return pf_on() && pf_17_form(w, 0, H, W, false, &ps) && pf_plans(ps); }
 
     // Would BOTH readers of a decoder join cat[a0, a1] -- block1 (3x3, fused LayerNorm) and res_conv (1x1) of the ResnetBlock -- run
     // on the plane-operand kernels, given the twins of the two halves?  Then a0 (an Upsample output, read by nothing else) needs no
-    // fp32 copy at all.  Mirrors the conditions of try_pf.
+    // fp32 copy at all.
     bool join_reads_planes(const ResBlockW &rb, const float *p0, int C0, const float *p1, int H, int W) {
         PfTwin *t0 = twin(p0), *t1 = twin(p1);
         if (!t0 || !t1 || !t1->valid || t0->H != H || t0->W != W || t1->H != H || t1->W != W) return false;
@@ -231,83 +297,84 @@ struct Builder {
     bool join_would_read_planes(const ResBlockW &rb, int C0, int H, int W) {
         if (!pf_on() || !rb.has_res || rb.hoist_cx) return false;
         if (rb.cres.Cin != rb.c1.Cin || (C0 % 16) || C0 <= 0 || C0 >= rb.c1.Cin || !pf_site(SITE_JOIN, H, W)) return false;
-        for (const ConvW *w : {&rb.c1, &rb.cres}) {
-            const bool k3 = w->KH == 3 && w->KW == 3, k1 = w->KH == 1 && w->KW == 1;
-            if (!w->wsh || w->stride != 1 || w->transposed || (w->Cin % 16) || !(k3 || k1)) return false;
-            if ((w->pad_y >= 0 ? w->pad_y : w->pad) != w->KH / 2 || (w->pad_x >= 0 ? w->pad_x : w->pad) != w->KW / 2) return false;
-            PfShape ps;
-            ps.Cin = w->Cin; ps.Cout = w->Cout; ps.C0 = C0; ps.KH = w->KH; ps.KW = w->KW; ps.nz = 1; ps.Ho = H; ps.Wo = W; ps.B = pb();
-            ps.need_all_cout = k3;
-            PfPlan plan;
-            if (!pf_make_plan(ps, &plan)) return false;
+        PfShape p1, pr;
+        return pf_form(rb.c1, C0, H, W, rb.c1.KH == 3, &p1) && pf_plans(p1) && pf_form(rb.cres, C0, H, W, rb.cres.KH == 3, &pr) && pf_plans(pr);
+    }
+
+    // ---- argument blocks shared by the launch forms (PfArgs, ConvArgs)
+    // output addressing of a launch of Ho x Wo pixels (a transposed layer: per phase, the four phases interleaved)
+    template <class A> static void out_geometry(A &a, const ConvW &w, int Ho, int Wo) {
+        if (w.transposed) {
+            for (int z = 0; z < 4; ++z) {
+                const int py = z >> 1, px = z & 1;
+                a.pad_y[z] = w.tk == 5 ? 1 : 1 - py; a.pad_x[z] = w.tk == 5 ? 1 : 1 - px;
+                a.out_zoff[z] = py * 2 * Wo + px;
+            }
+            a.out_cs = (long long)4 * Ho * Wo; a.out_ys = 4 * Wo; a.out_xs = 2;
+        } else {
+            a.pad_y[0] = w.py(); a.pad_x[0] = w.px();
+            a.out_cs = (long long)Ho * Wo; a.out_ys = Wo; a.out_xs = 1;
         }
+        a.Ho = Ho; a.Wo = Wo;
+    }
+    // the twin of an output tensor of C x H x W (batch stride bs), or null when it has none of that shape
+    PfTwin *out_twin(const float *out, long long bs, int C, int H, int W) {
+        PfTwin *t = twin(out);
+        return t && t->C == C && t->H == H && t->W == W && bs == (long long)C * H * W ? t : nullptr;
+    }
+    // Binds the twin of `out` as the launch's planes output (Ho x Wo as for out_geometry) and marks it written; false when there is none.
+    template <class A> bool bind_out_pf(A &a, const ConvW &w, const float *out, long long out_bs, int Ho, int Wo) {
+        const int Wt = w.transposed ? 2 * Wo : Wo;
+        PfTwin *to = out_twin(out, out_bs, w.Cout, w.transposed ? 2 * Ho : Ho, Wt);
+        if (!to) return false;
+        a.out_pf = to->p; a.pf_bs = to->bs(); a.pf_ps = to->ps();
+        if (w.transposed) {
+            a.pf_ys = 2 * (Wt + 2); a.pf_xs = 2;
+            for (int z = 0; z < 4; ++z) a.pf_zoff[z] = ((z >> 1) + 1) * (Wt + 2) + (z & 1) + 1;
+        } else {
+            a.pf_ys = Wt + 2; a.pf_xs = 1; a.pf_zoff[0] = (Wt + 2) + 1;
+        }
+        to->valid = true;
+        return true;
+    }
+    int shift_stride(const ConvOpts &o) const { return o.shift_bs >= 0 ? o.shift_bs : h->shift_bs; }
+    // the epilogue as ConvOpts asks for it (a launch form that lacks a part is gated on it before)
+    template <class A> void epilogue(A &a, const ConvW &w, const ConvOpts &o) {
+        a.bias = o.no_bias ? nullptr : w.bias;
+        a.pre_add = o.pre_add;
+        a.ep_g = o.ln_g; a.ep_b = o.ln_b; a.eps = 1e-5f; a.relu = o.relu; a.relu_slope = o.relu_slope;
+        a.shift = o.shift; a.shift_bs = shift_stride(o);
+        a.resid = o.resid; a.resid_bs = o.resid_bs; a.resid_cs = o.resid_cs;
+        a.stat_mean = o.stat_mean; a.stat_rstd = o.stat_rstd;
+        a.res3_w = o.res3_w; a.res3_x = o.res3_x; a.res3_bs = o.res3_bs;
+        a.fault = fault_flag();
+    }
+    // the end of a single-launch convolution: its cost for the per-op table, what the caller reads back, the op
+    bool finish(Op &op, double flops, double bytes, bool pf_only) {
+        op.flops = flops; op.bytes = bytes;
+        last_ksplit = 1;
+        last_pf_only = pf_only;
+        emit(op);
         return true;
     }
 
-    // Would a Downsample convolution (3x3 / stride 2 / pad 1) run on conv_pf_kernel<..., STR = 2> given a PF input of H x W?
-    bool pf_s2_would_plan(const ConvW &w, int H, int W) {
-        if (!pf_on() || !w.wsh || w.stride != 2 || w.transposed || w.KH != 3 || w.KW != 3 || (H & 1) || (W & 1) || (w.Cin % 16)) return false;
-        if ((w.pad_y >= 0 ? w.pad_y : w.pad) != 1 || (w.pad_x >= 0 ? w.pad_x : w.pad) != 1) return false;
-        PfShape ps;
-        ps.Cin = w.Cin; ps.Cout = w.Cout; ps.KH = 3; ps.KW = 3; ps.Ho = H / 2; ps.Wo = W / 2; ps.B = pb(); ps.stride = 2;
-        PfPlan plan;
-        return pf_make_plan(ps, &plan);
-    }
-
-    // Would an Upsample (ConvTranspose2d 4x4 / stride 2 / pad 1) run on conv_pf_kernel<..., TZ = 4> given a PF input of H x W?
-    bool pf_tz_would_plan(const ConvW &w, int H, int W) {
-        if (!pf_on() || !w.wsh || !w.transposed || w.tk != 4 || w.KH != 2 || w.KW != 2 || (w.Cin % 16)) return false;
-        PfShape ps;
-        ps.Cin = w.Cin; ps.Cout = w.Cout; ps.KH = 2; ps.KW = 2; ps.nz = w.nz; ps.Ho = H; ps.Wo = W; ps.B = pb(); ps.tz = 4;
-        PfPlan plan;
-        return pf_make_plan(ps, &plan);
-    }
-
-    // Would the row-folded final convolution (1x7) run on conv_pf_kernel given a PF input of H x W?
-    bool pf_17_would_plan(const ConvW &w, int H, int W) {
-        if (!pf_on() || !w.wsh || w.KH != 1 || w.KW != 7 || w.stride != 1 || w.transposed || (w.Cin % 16)) return false;
-        if ((w.pad_y >= 0 ? w.pad_y : w.pad) != 0 || (w.pad_x >= 0 ? w.pad_x : w.pad) != 3) return false;
-        PfShape ps;
-        ps.Cin = w.Cin; ps.Cout = w.Cout; ps.KH = 1; ps.KW = 7; ps.Ho = H; ps.Wo = W; ps.B = pb(); ps.cop = w.COP;
-        PfPlan plan;
-        return pf_make_plan(ps, &plan);
-    }
-
-    // Would a single-source 3x3 / 1x1 layer with fused LayerNorm run on conv_pf_kernel (given a PF input)?
-    bool pf_would_plan(const ConvW &w, int H, int W) {
-        if (!pf_on() || !w.wsh || w.stride != 1 || w.transposed) return false;
-        if (!((w.KH == 3 && w.KW == 3) || (w.KH == 1 && w.KW == 1))) return false;
-        if ((w.pad_y >= 0 ? w.pad_y : w.pad) != w.KH / 2 || (w.pad_x >= 0 ? w.pad_x : w.pad) != w.KW / 2) return false;
-        PfShape ps;
-        ps.Cin = w.Cin; ps.Cout = w.Cout; ps.KH = w.KH; ps.KW = w.KW; ps.Ho = H; ps.Wo = W; ps.B = pb(); ps.need_all_cout = true;
-        PfPlan plan;
-        return (w.Cin % 16) == 0 && pf_make_plan(ps, &plan);
-    }
-
-    // Plans the convolution on conv_pf_kernel when every source has a valid PF twin and the layer is a stride-1
-    // k x k / 1x1 / phase-decomposed transposed convolution with "same" geometry.
+    // Plans the convolution on conv_pf_kernel when every source has a valid PF twin and the layer has one of its forms.
     bool try_pf(const ConvW &w, const float *s0, int C0, const float *s1, int H, int W, float *out, long long out_bs,
-                const ConvOpts &o, bool need_all, int prof, const ConvShape &s) {
-        if (!pf_on() || !w.wsh || (w.stride != 1 && w.stride != 2) || o.pre_mean || o.w_bs || o.wsp_bs || o.max_ksplit > 1) return false;
-        // stride 2: the 3x3 / pad 1 Downsample form on even extents, single source (conv_pf_kernel, STR = 2)
-        if (w.stride == 2 && (w.transposed || w.KH != 3 || w.KW != 3 || s1 || (H & 1) || (W & 1) || o.pre_add || o.res3_w)) return false;
+                const ConvOpts &o, bool need_all, int prof) {
+        if (!pf_on() || o.pre_mean || o.w_bs || o.wsp_bs || o.max_ksplit > 1) return false;
+        PfShape ps;
+        const int c0 = s1 ? C0 : 0;
+        if (!(pf_form(w, c0, H, W, need_all, &ps) || (pf_s2_form(w, c0, H, W, need_all, &ps) && !o.pre_add && !o.res3_w) ||
+              pf_tz_form(w, c0, H, W, need_all, &ps) || (pf_17_form(w, c0, H, W, need_all, &ps) && !o.ln_g && !o.emit_pf)))
+            return false;
         if (s1 && dev_env("CDC_TEST_JOIN_MISS")) return false;   // test hook: the joins miss the plane kernels AFTER their halves were made planes-only (ensure_f32)
         PfTwin *t0 = twin(s0), *t1 = s1 ? twin(s1) : nullptr;
         if (!t0 || !t0->valid || (s1 && (!t1 || !t1->valid))) return false;
         if (t0->H != H || t0->W != W || (t1 && (t1->H != H || t1->W != W))) return false;
         if (s1 ? (t0->C != C0 || t0->C + t1->C != w.Cin) : t0->C != w.Cin) return false;
-        // transposed 4x4: the four 2x2 phases fused in one workgroup (TZ = 4)
-        const bool k3 = w.KH == 3 && w.KW == 3 && !w.transposed, k1 = w.KH == 1 && w.KW == 1, k2 = w.transposed && w.tk == 4 && !s1;
-        const bool k17 = w.KH == 1 && w.KW == 7 && !w.transposed && w.stride == 1 && !s1 && !o.ln_g && !o.emit_pf;   // row-folded final convolution
-        if (!(k3 || k1 || k2 || k17)) return false;
-        if (!w.transposed && ((w.pad_y >= 0 ? w.pad_y : w.pad) != w.KH / 2 || (w.pad_x >= 0 ? w.pad_x : w.pad) != w.KW / 2)) return false;
-        PfShape ps;
-        ps.Cin = w.Cin; ps.Cout = w.Cout; ps.C0 = s1 ? C0 : 0; ps.KH = w.KH; ps.KW = w.KW; ps.nz = w.nz;
-        ps.Ho = s.Ho; ps.Wo = s.Wo; ps.B = pb(); ps.need_all_cout = need_all; ps.stride = w.stride;
-        ps.tz = k2 ? 4 : 1;
-        ps.cop = w.COP;
         PfPlan plan;
         if (!pf_make_plan(ps, &plan)) return false;
+        const int Ho = ps.Ho, Wo = ps.Wo;
         Op op;
         op.kind = Op::CONVPF; op.prof = prof; op.pfplan = plan; op.nz = w.nz;
         PfArgs &a = op.pf;
@@ -319,87 +386,48 @@ struct Builder {
         a.KH = w.KH; a.KW = w.KW; a.nz = w.nz; a.stride = w.stride; a.tz = ps.tz;
         a.nchunk = w.Cin / 16; a.COP = w.COP; a.Cout = w.Cout;
         a.acc_scale = w.wscale_inv;
-        a.out = o.no_f32 ? nullptr : out; a.out_bs = out_bs;
-        const int Ht = w.transposed ? 2 * H : s.Ho, Wt = w.transposed ? 2 * W : s.Wo;
-        if (w.transposed) {
-            for (int z = 0; z < 4; ++z) {
-                const int py = z >> 1, px = z & 1;
-                a.pad_y[z] = w.tk == 5 ? 1 : 1 - py; a.pad_x[z] = w.tk == 5 ? 1 : 1 - px;
-                a.out_zoff[z] = py * 2 * W + px;
-            }
-            a.out_cs = (long long)4 * H * W; a.out_ys = 4 * W; a.out_xs = 2;
-        } else {
-            a.pad_y[0] = w.KH / 2; a.pad_x[0] = w.KW / 2;
-            a.out_cs = (long long)s.Ho * s.Wo; a.out_ys = s.Wo; a.out_xs = 1;
-        }
-        a.Ho = s.Ho; a.Wo = s.Wo;
-        PfTwin *to = o.emit_pf ? twin(out) : nullptr;
-        if (to && to->C == w.Cout && to->H == Ht && to->W == Wt && out_bs == (long long)w.Cout * Ht * Wt) {
-            a.out_pf = to->p; a.pf_bs = to->bs(); a.pf_ps = to->ps();
-            if (w.transposed) {
-                a.pf_ys = 2 * (Wt + 2); a.pf_xs = 2;
-                for (int z = 0; z < 4; ++z) a.pf_zoff[z] = ((z >> 1) + 1) * (Wt + 2) + (z & 1) + 1;
-            } else {
-                a.pf_ys = Wt + 2; a.pf_xs = 1; a.pf_zoff[0] = (Wt + 2) + 1;
-            }
-            to->valid = true;
-        } else if (o.no_f32) {
-            a.out = out;                                // nothing else would hold the result
-        }
-        a.bias = o.no_bias ? nullptr : w.bias;
-        a.pre_add = o.pre_add;
-        a.ep_g = o.ln_g; a.ep_b = o.ln_b; a.eps = 1e-5f; a.relu = o.relu; a.relu_slope = o.relu_slope;
-        a.shift = o.shift; a.shift_bs = o.shift_bs >= 0 ? o.shift_bs : h->shift_bs;
-        a.resid = o.resid; a.resid_bs = o.resid_bs; a.resid_cs = o.resid_cs;
+        out_geometry(a, w, Ho, Wo);
+        a.out = out; a.out_bs = out_bs;
+        if (o.emit_pf && bind_out_pf(a, w, out, out_bs, Ho, Wo) && o.no_f32) a.out = nullptr;   // (no twin: the fp32 copy holds the result)
+        epilogue(a, w, o);
         if (o.resid1) {         // residual over a channel concatenation: every wave's channel part inside one source (64 / 96 / 128-channel parts)
             if (!o.resid || o.resid_c0 <= 0 || o.resid_c0 >= w.Cout || (o.resid_c0 % 64) || (o.resid_c0 % (plan.MB * 32))) return false;
             a.resid1 = o.resid1; a.resid1_bs = o.resid1_bs; a.resid_c0 = o.resid_c0;
         }
         if (PfTwin *tr = o.resid ? twin(o.resid) : nullptr)
             if (tr->only) {     // the residual exists as planes only (a ResnetBlock-chain output): read it from there
-                if (!tr->valid || tr->C != w.Cout || tr->H != s.Ho || tr->W != s.Wo || w.transposed || w.stride != 1 ||
-                    o.resid_bs != (long long)w.Cout * s.Ho * s.Wo || o.resid_cs != (long long)s.Ho * s.Wo) {
+                if (!tr->valid || tr->C != w.Cout || tr->H != Ho || tr->W != Wo || w.transposed || w.stride != 1 ||
+                    o.resid_bs != (long long)w.Cout * Ho * Wo || o.resid_cs != (long long)Ho * Wo) {
                     if (!ensure_f32(o.resid, o.resid_bs)) {
                         if (!rc) rc = fail(h, CDC_ERR_UNSUPPORTED, "planes-only residual of a shape the plane-operand kernels do not read");
                         return true;
                     }
                 } else {
                     a.resid = nullptr;
-                    a.resid_pf = tr->p; a.rpf_bs = tr->bs(); a.rpf_ps = tr->ps(); a.rpf_ys = s.Wo + 2; a.rpf_zoff = (s.Wo + 2) + 1;
+                    a.resid_pf = tr->p; a.rpf_bs = tr->bs(); a.rpf_ps = tr->ps(); a.rpf_ys = Wo + 2; a.rpf_zoff = (Wo + 2) + 1;
                 }
             }
-        a.stat_mean = o.stat_mean; a.stat_rstd = o.stat_rstd;
-        a.res3_w = o.res3_w; a.res3_x = o.res3_x; a.res3_bs = o.res3_bs;
-        a.fault = fault_flag();
         // large 3x3 layers: the persistent ping-ponged kernel.  Its chunk summation order depends on the launch geometry
         // (batch size, CU count), so a program planned "as for one image" (planB: the entropy coder's bit-exactness
         // contract between batch sizes) never uses it.
         if (planB == 0) pf3_make_plan(a, B, w.nz, &op.pfplan);
         // (hoisted partial sums in accumulator order, pre_add_c4: measured only on the first layer's form, try_pf_uf -- 0.364 -> 0.354 ms;
         //  the 192 / 256-channel layers did not move, their 1x1 res_convs lost 5 %)
-        if (getenv("CDC_DEBUG_PLAN"))
+        if (debug_plan())
             fprintf(stderr, "[plan] conv %dx%d %d->%d out %dx%d on conv_pf%s_kernel (epv %d, %d workgroups x %d tiles per group)\n", w.KH, w.KW, w.Cin, w.Cout,
-                    s.Ho, s.Wo, op.pfplan.pf3_epv ? "3" : "", op.pfplan.pf3_epv, op.pfplan.pf3_G, op.pfplan.pf3_iters);
-        const double px = (double)B * s.Ho * s.Wo * w.nz;
-        op.flops = 2.0 * px * w.Cout * w.Cin * w.KH * w.KW;
-        op.bytes = 4.0 * ((double)B * w.Cin * H * W + px * w.Cout);
-        last_ksplit = 1;
-        last_pf_only = a.out == nullptr;
-        emit(op);
-        return true;
+                    Ho, Wo, op.pfplan.pf3_epv ? "3" : "", op.pfplan.pf3_epv, op.pfplan.pf3_G, op.pfplan.pf3_iters);
+        const double px = (double)B * Ho * Wo * w.nz;
+        return finish(op, 2.0 * px * w.Cout * w.Cin * w.KH * w.KW, 4.0 * ((double)B * w.Cin * H * W + px * w.Cout), a.out == nullptr);
     }
 
     // The first layer (7x1 over the kx-unfolded 3-channel image, ConvOpts::uf_c) on conv_pf_kernel's UF form: the kernel builds its patch
     // buffers from the image itself, everything else (weight ring, tap loop, epilogue with hoisted partial sums, LayerNorm, planes out)
     // is the plane-operand kernel.
     bool try_pf_uf(const ConvW &w, const float *s0, long long bs0, int H, int W, float *out, long long out_bs, const ConvOpts &o,
-                   bool need_all, int prof, const ConvShape &s) {
-        if (!pf_on() || !w.wsh || o.uf_c != 3 || o.uf_pad != 3 || w.KH != 7 || w.KW != 1 || w.stride != 1 || w.transposed || w.nz != 1) return false;
-        if (o.pre_mean || o.w_bs || o.wsp_bs || o.max_ksplit > 1 || o.resid || o.res3_w || o.stat_mean) return false;
-        if ((w.pad_y >= 0 ? w.pad_y : w.pad) != 3 || (w.pad_x >= 0 ? w.pad_x : w.pad) != 0 || s.Ho != H || s.Wo != W) return false;
+                   bool need_all, int prof) {
         PfShape ps;
-        ps.Cin = w.Cin; ps.Cout = w.Cout; ps.KH = 7; ps.KW = 1; ps.Ho = H; ps.Wo = W; ps.B = pb(); ps.need_all_cout = need_all;
-        ps.uf = 3; ps.cop = w.COP;
+        if (!pf_on() || o.uf_c != 3 || o.uf_pad != 3 || !pf_uf_form(w, H, W, need_all, &ps)) return false;
+        if (o.pre_mean || o.w_bs || o.wsp_bs || o.max_ksplit > 1 || o.resid || o.res3_w || o.stat_mean) return false;
         PfPlan plan;
         if (!pf_make_plan(ps, &plan)) return false;
         Op op;
@@ -412,55 +440,33 @@ struct Builder {
         a.KH = 7; a.KW = 1; a.nz = 1;
         a.nchunk = 2; a.COP = w.COP; a.Cout = w.Cout;
         a.acc_scale = w.wscale_inv;
-        a.pad_y[0] = 3; a.pad_x[0] = 0;
-        a.out = o.no_f32 ? nullptr : out; a.out_bs = out_bs;
-        a.out_cs = (long long)H * W; a.out_ys = W; a.out_xs = 1;
-        a.Ho = H; a.Wo = W;
-        PfTwin *to = o.emit_pf ? twin(out) : nullptr;
-        if (to && to->C == w.Cout && to->H == H && to->W == W && out_bs == (long long)w.Cout * H * W) {
-            a.out_pf = to->p; a.pf_bs = to->bs(); a.pf_ps = to->ps();
-            a.pf_ys = W + 2; a.pf_xs = 1; a.pf_zoff[0] = (W + 2) + 1;
-            to->valid = true;
-        } else if (o.no_f32) {
-            a.out = out;
-        }
-        a.bias = o.no_bias ? nullptr : w.bias;
-        a.pre_add = o.pre_add;
-        if (a.pre_add && cur != &h->pre_ops)
-            if (const float *q = pre_add_c4(a.pre_add, w.Cout, H, W, out_bs)) { a.pre_add = q; a.pre_c4 = 1; }
-        a.ep_g = o.ln_g; a.ep_b = o.ln_b; a.eps = 1e-5f; a.relu = o.relu; a.relu_slope = o.relu_slope;
-        a.shift = o.shift; a.shift_bs = o.shift_bs >= 0 ? o.shift_bs : h->shift_bs;
-        a.fault = fault_flag();
+        out_geometry(a, w, H, W);
+        a.out = out; a.out_bs = out_bs;
+        if (o.emit_pf && bind_out_pf(a, w, out, out_bs, H, W) && o.no_f32) a.out = nullptr;
+        const float *c4 = o.pre_add && cur != &h->pre_ops ? pre_add_c4(o.pre_add, w.Cout, H, W, out_bs) : nullptr;
+        epilogue(a, w, o);
+        if (c4) { a.pre_add = c4; a.pre_c4 = 1; }
         const double px = (double)B * H * W;
-        op.flops = 2.0 * px * w.Cout * w.Cin * 7;
-        op.bytes = 4.0 * ((double)B * 3 * H * W + px * w.Cout);
-        last_ksplit = 1;
-        last_pf_only = a.out == nullptr;
-        emit(op);
-        return true;
+        return finish(op, 2.0 * px * w.Cout * w.Cin * 7, 4.0 * ((double)B * 3 * H * W + px * w.Cout), a.out == nullptr);
     }
 
     // Pointwise convolutions at the >= 32-pixel-wide levels on conv_pw_kernel (fp16 arithmetic): activations staged
     // per wave straight from the fp32 sources, PreNorm folded as (x - mean) on load / rstd in the epilogue.
     bool try_pw(const ConvW &w, const float *s0, int C0, long long bs0, const float *s1, long long bs1, int H, int W,
-                float *out, long long out_bs, const ConvOpts &o, bool need_all, int prof, const ConvShape &s) {
-        if (h->arith != 1 || !w.wsh || w.KH != 1 || w.KW != 1 || w.stride != 1 || w.transposed || w.nz != 1) return false;
-        if (dev_env("CDC_NO_PW")) return false;
-        if ((w.pad_y >= 0 ? w.pad_y : w.pad) != 0 || (w.pad_x >= 0 ? w.pad_x : w.pad) != 0) return false;
+                float *out, long long out_bs, const ConvOpts &o, bool need_all, int prof) {
+        PfShape ps;
+        if (h->arith != 1 || dev_env("CDC_NO_PW") || !pw_form(w, s1 ? C0 : 0, H, W, &ps)) return false;
         if (need_all || o.ln_g || o.stat_mean || o.res3_w || o.pf_only) return false;
         if (o.pre_mean && o.pre_mode != 2) return false;
         if (o.w_bs && !o.wsp_bs) return false;              // per-image weights without planes
-        PfShape ps;
-        ps.Cin = w.Cin; ps.Cout = w.Cout; ps.C0 = s1 ? C0 : 0; ps.KH = 1; ps.KW = 1; ps.nz = 1;
-        ps.Ho = s.Ho; ps.Wo = s.Wo; ps.B = pb(); ps.need_all_cout = false;
         PfPlan plan;
         if (!pw_make_plan(ps, &plan)) return false;
-        if (plan.lin && (o.shift || o.wsp_bs || (long long)w.Cout * s.Ho * s.Wo != out_bs)) return false;   // tiles span images
-        Op op;
-        if (getenv("CDC_DEBUG_PLAN"))
+        if (plan.lin && (o.shift || o.wsp_bs || (long long)w.Cout * H * W != out_bs)) return false;   // tiles span images
+        if (debug_plan())
             fprintf(stderr, "[plan] conv1x1 PW Cin=%4d Cout=%4d out=%3dx%-3d %s%s| MB=%d NPW=%d WM=%d WP=%d groups=%d R=%d wgs=%d lds=%zu\n", w.Cin, w.Cout,
-                    s.Ho, s.Wo, o.pre_mean ? "pre2 " : "", o.wsp_bs ? "per-image " : "", plan.MB, plan.NPW, plan.WM, plan.WP, plan.groups, plan.ring,
+                    H, W, o.pre_mean ? "pre2 " : "", o.wsp_bs ? "per-image " : "", plan.MB, plan.NPW, plan.WM, plan.WP, plan.groups, plan.ring,
                     plan.tiles_x * plan.tiles_y * B * plan.groups, plan.lds_bytes);
+        Op op;
         op.kind = Op::CONVPF; op.prof = prof; op.pfplan = plan; op.nz = 1; op.pw = true;
         PfArgs &a = op.pf;
         memset(&a, 0, sizeof a);
@@ -471,51 +477,33 @@ struct Builder {
         a.KH = 1; a.KW = 1; a.nz = 1;
         a.nchunk = w.Cin / 16; a.COP = w.COP; a.Cout = w.Cout;
         a.acc_scale = w.wscale_inv;
+        out_geometry(a, w, H, W);
         a.out = out; a.out_bs = out_bs;
-        a.out_cs = (long long)s.Ho * s.Wo; a.out_ys = s.Wo; a.out_xs = 1;
-        a.Ho = s.Ho; a.Wo = s.Wo;
-        if (PfTwin *to = (o.emit_pf && !plan.lin) ? twin(out) : nullptr)
-            if (to->C == w.Cout && to->H == s.Ho && to->W == s.Wo && out_bs == (long long)w.Cout * s.Ho * s.Wo && (w.Cout % 32) == 0) {
-                a.out_pf = to->p; a.pf_bs = to->bs(); a.pf_ps = to->ps();
-                a.pf_ys = s.Wo + 2; a.pf_xs = 1; a.pf_zoff[0] = (s.Wo + 2) + 1;
-                to->valid = true;
-                if (o.no_f32) a.out = nullptr;          // the planes are the only copy (their reader is a plane-operand kernel)
-            }
-        a.bias = o.no_bias ? nullptr : w.bias;
-        a.pre_add = o.pre_add;
-        a.relu = o.relu; a.relu_slope = o.relu_slope; a.eps = 1e-5f;
-        a.shift = o.shift; a.shift_bs = o.shift_bs >= 0 ? o.shift_bs : h->shift_bs;
-        a.resid = o.resid; a.resid_bs = o.resid_bs; a.resid_cs = o.resid_cs;
-        a.fault = fault_flag();
-        const double px = (double)B * s.Ho * s.Wo;
-        op.flops = 2.0 * px * w.Cout * w.Cin;
-        op.bytes = 4.0 * ((double)B * w.Cin * H * W + px * w.Cout);
-        last_ksplit = 1;
-        last_pf_only = a.out == nullptr;
-        emit(op);
-        return true;
+        // (no_f32: the planes are the only copy, their reader is a plane-operand kernel)
+        if (o.emit_pf && !plan.lin && (w.Cout % 32) == 0 && bind_out_pf(a, w, out, out_bs, H, W) && o.no_f32) a.out = nullptr;
+        epilogue(a, w, o);
+        const double px = (double)B * H * W;
+        return finish(op, 2.0 * px * w.Cout * w.Cin, 4.0 * ((double)B * w.Cin * H * W + px * w.Cout), a.out == nullptr);
     }
 
     // 3x3 / stride-1 / pad-1 layer of a few-pixel level on conv_ws_kernel (conv_ws_kernel.h): the RAW result (bias added, no LayerNorm)
     // goes to `raw`; a Block's LayerNorm / ReLU / shift / residual is the in-place pass its caller emits behind it.
     // (H, W: the INPUT map; the stride-2 form is the Downsample, 3x3 / pad 1 on even extents)
-    bool ws_would_plan(const ConvW &w, int C0, bool two_src, int H, int W) {
+    bool ws_would_plan(const ConvW &w, int C0, bool two_src, int H, int W, WsPlan *plan) {
         if (h->arith != 1 || !w.wsh || planB > 0 || w.KH != 3 || w.KW != 3 || (w.stride != 1 && w.stride != 2) || w.transposed || w.nz != 1) return false;
-        if ((w.pad_y >= 0 ? w.pad_y : w.pad) != 1 || (w.pad_x >= 0 ? w.pad_x : w.pad) != 1) return false;
+        if (w.py() != 1 || w.px() != 1) return false;
         if (w.COP != w.Cout || w.Cin_pad != w.Cin) return false;
         if (w.stride == 2 && ((H & 1) || (W & 1) || two_src)) return false;
-        WsPlan plan;
-        return ws_make_plan(w.Cin, two_src ? C0 : w.Cin, w.Cout, H / w.stride, W / w.stride, pb(), w.stride, &plan);
+        return ws_make_plan(w.Cin, two_src ? C0 : w.Cin, w.Cout, H / w.stride, W / w.stride, pb(), w.stride, plan);
     }
     bool try_ws(const ConvW &w, const float *s0, int C0, long long bs0, const float *s1, long long bs1, int H, int W, float *raw,
                 long long raw_bs, int prof, const float *pre_add = nullptr) {
-        if (rc || !ws_would_plan(w, C0, s1 != nullptr, H, W)) return false;
+        Op op;
+        op.kind = Op::CONVWS; op.prof = prof;
+        if (rc || !ws_would_plan(w, C0, s1 != nullptr, H, W, &op.wsplan)) return false;
         if (!ensure_f32(s0, bs0) || (s1 && !ensure_f32(s1, bs1))) return false;
         const int Ho = H / w.stride, Wo = W / w.stride;
         if (raw_bs != (long long)w.Cout * Ho * Wo) return false;
-        Op op;
-        op.kind = Op::CONVWS; op.prof = prof;
-        if (!ws_make_plan(w.Cin, s1 ? C0 : w.Cin, w.Cout, Ho, Wo, pb(), w.stride, &op.wsplan)) return false;
         WsArgs &a = op.ws;
         memset(&a, 0, sizeof a);
         a.x0 = s0; a.x0_bs = bs0; a.x1 = s1; a.x1_bs = bs1;
@@ -525,16 +513,11 @@ struct Builder {
         a.pre_add = pre_add;
         a.out = raw; a.out_bs = raw_bs;
         a.fault = fault_flag();
-        const double px = (double)B * Ho * Wo;
-        op.flops = 2.0 * px * w.Cout * w.Cin * 9;
-        op.bytes = 4.0 * ((double)B * H * W * w.Cin + px * w.Cout);
-        if (getenv("CDC_DEBUG_PLAN"))
+        if (debug_plan())
             fprintf(stderr, "[plan] conv 3x3 s%d %d->%d out %dx%d on conv_ws_kernel: %d tiles of %d pixels x %d groups, %d waves, %zu bytes of LDS\n", w.stride, w.Cin, w.Cout, Ho, Wo,
                     op.wsplan.tiles, op.wsplan.NPB * 32, op.wsplan.groups, op.wsplan.waves, op.wsplan.lds_bytes);
-        last_ksplit = 1;
-        last_pf_only = false;
-        emit(op);
-        return true;
+        const double px = (double)B * Ho * Wo;
+        return finish(op, 2.0 * px * w.Cout * w.Cin * 9, 4.0 * ((double)B * H * W * w.Cin + px * w.Cout), false);
     }
 
     // 1x1 layer of a few-pixel launch (at most 128 pixel blocks, or per-image weights) on conv_ws1_kernel (conv_ws1_kernel.h): all of K inside the
@@ -542,8 +525,8 @@ struct Builder {
     // residual; shared or per-image weight planes.
     bool try_ws1(const ConvW &w, const float *s0, int C0, long long bs0, const float *s1, long long bs1, int H, int W, float *out, long long out_bs,
                  const ConvOpts &o, bool need_all, int prof) {
-        if (rc || h->arith != 1 || !w.wsh || planB > 0 || w.KH != 1 || w.KW != 1 || w.stride != 1 || w.transposed || w.nz != 1) return false;
-        if ((w.pad_y >= 0 ? w.pad_y : w.pad) != 0 || (w.pad_x >= 0 ? w.pad_x : w.pad) != 0) return false;
+        PfShape ps;     // (unused: the form is conv_pw_kernel's)
+        if (rc || h->arith != 1 || planB > 0 || !pw_form(w, 0, H, W, &ps)) return false;
         if (need_all || o.ln_g || o.stat_mean || o.res3_w || o.pf_only || (o.pre_add && o.resid) || o.relu || o.resid1 || o.uf_c) return false;
         if (o.pre_mean && o.pre_mode != 2) return false;
         if (o.w_bs && !o.wsp_bs) return false;               // per-image weights without planes
@@ -571,23 +554,18 @@ struct Builder {
         a.w = w.wsh; a.w_bs = o.wsp_bs / 8;                 // units of 8 halfs
         a.nchunk = w.Cin / 16; a.COP = w.COP; a.Cout = w.Cout; a.acc_scale = w.wscale_inv;
         a.bias = o.no_bias ? nullptr : w.bias;
-        a.shift = o.shift; a.shift_bs = o.shift_bs >= 0 ? o.shift_bs : h->shift_bs;
+        a.shift = o.shift; a.shift_bs = shift_stride(o);
         a.resid = o.resid; a.resid_bs = o.resid_bs;
         // (a hoisted partial sum -- the step-invariant context half of a concatenated input, layout of `out` -- is one more addend of this linear epilogue)
         if (o.pre_add) { a.resid = o.pre_add; a.resid_bs = out_bs; a.resid_is_pre = 1; }
         a.out = out; a.out_bs = out_bs;
         a.fault = fault_flag();
-        const double px = (double)B * H * W;
-        op.flops = 2.0 * px * w.Cout * w.Cin;
-        op.bytes = 4.0 * px * (w.Cin + w.Cout);
-        if (getenv("CDC_DEBUG_PLAN"))
+        if (debug_plan())
             fprintf(stderr, "[plan] conv 1x1 %d->%d out %dx%d on conv_ws1_kernel: %d tiles of %d pixels x %d groups, %d waves%s%s\n", w.Cin, w.Cout, H, W,
                     op.ws1plan.tiles, op.ws1plan.NPB * 32, op.ws1plan.groups, op.ws1plan.waves, o.pre_mean ? ", folded PreNorm" : "", o.wsp_bs ? ", per-image weights" : "");
-        last_ksplit = 1;
-        last_pf_only = false;
         ws1_h = H;
-        emit(op);
-        return true;
+        const double px = (double)B * H * W;
+        return finish(op, 2.0 * px * w.Cout * w.Cin, 4.0 * px * (w.Cin + w.Cout), false);
     }
 
     // Emits one convolution.  s1 (optional) is the second concat source.  Returns false when
@@ -596,7 +574,6 @@ struct Builder {
               long long bs1, int H, int W, float *out, long long out_bs, const ConvOpts &o,
               bool need_all, int prof) {
         if (rc) return true;
-        const int pad_y = w.pad_y >= 0 ? w.pad_y : w.pad, pad_x = w.pad_x >= 0 ? w.pad_x : w.pad;
         if (s1 && (C0 % 4)) {
             // the kernel wants every K-chunk inside one concat source: materialise odd seams
             const long long n0 = (long long)C0 * H * W, n1 = (long long)(w.Cin - C0) * H * W;
@@ -612,15 +589,15 @@ struct Builder {
         s.allow_split = w.wsp != nullptr;
         s.arith = (h->arith == 1 && w.wsh) ? 1 : 0;
         s.per_image_w = o.wsp_bs != 0;
-        for (int z = 0; z < 4; ++z) s.pad_x[z] = w.transposed ? (w.tk == 5 ? 1 : 1 - (z & 1)) : pad_x;
+        for (int z = 0; z < 4; ++z) s.pad_x[z] = w.transposed ? (w.tk == 5 ? 1 : 1 - (z & 1)) : w.px();
         if (w.transposed) { s.Ho = H; s.Wo = W; }
         else {
-            s.Ho = (H + 2 * pad_y - w.KH) / w.stride + 1;
-            s.Wo = (W + 2 * pad_x - w.KW) / w.stride + 1;
+            s.Ho = (H + 2 * w.py() - w.KH) / w.stride + 1;
+            s.Wo = (W + 2 * w.px() - w.KW) / w.stride + 1;
         }
         s.B = pb(); s.need_all_cout = need_all; s.lnmode = o.pre_mean ? o.pre_mode : 0;
-        if (!o.uf_c && try_pf(w, s0, C0, s1, H, W, out, out_bs, o, need_all, prof, s)) return true;
-        if (o.uf_c && !s1 && try_pf_uf(w, s0, bs0, H, W, out, out_bs, o, need_all, prof, s)) return true;
+        if (!o.uf_c && try_pf(w, s0, C0, s1, H, W, out, out_bs, o, need_all, prof)) return true;
+        if (o.uf_c && !s1 && try_pf_uf(w, s0, bs0, H, W, out, out_bs, o, need_all, prof)) return true;
         if (o.pf_only) return false;
         if (o.resid1 && !rc) { rc = fail(h, CDC_ERR_UNSUPPORTED, "a two-source residual reached a kernel without it"); return true; }
         {   // a planes-only source / residual and a reader of fp32: unpack it once (ensure_f32)
@@ -632,13 +609,12 @@ struct Builder {
                 }
         }
         // Downsample of a few-pixel level at small batch: all of K inside the workgroup (no split-K, no sum pass)
-        if (w.stride == 2 && !need_all && !o.ln_g && !o.relu && !o.shift && !o.stat_mean && !o.pre_add && !o.res3_w && !o.resid && !o.pre_mean &&
-            !o.w_bs && !o.uf_c && !(o.emit_pf && twin(out)) && try_ws(w, s0, C0, bs0, s1, bs1, H, W, out, out_bs, prof))
+        if (w.stride == 2 && !need_all && o.linear_epilogue() && !o.resid && !o.pre_mean && !o.w_bs && !o.uf_c && !(o.emit_pf && twin(out)) &&
+            try_ws(w, s0, C0, bs0, s1, bs1, H, W, out, out_bs, prof))
             return true;
         if (!o.uf_c && try_ws1(w, s0, C0, bs0, s1, bs1, H, W, out, out_bs, o, need_all, prof)) return true;
-        if (!o.uf_c && try_pw(w, s0, C0, bs0, s1, bs1, H, W, out, out_bs, o, need_all, prof, s)) return true;
-        const bool linear_ep = !need_all && !o.ln_g && !o.relu && !o.shift && !o.stat_mean && !o.pre_add && !o.res3_w &&
-                               w.nz == 1 && !w.transposed;
+        if (!o.uf_c && try_pw(w, s0, C0, bs0, s1, bs1, H, W, out, out_bs, o, need_all, prof)) return true;
+        const bool linear_ep = !need_all && o.linear_epilogue() && w.nz == 1 && !w.transposed;
         s.max_ksplit = o.max_ksplit > 1 ? o.max_ksplit : (linear_ep ? 4 : 1);
         if (need_all && (w.Cout % 32)) return false;
         ConvPlan plan;
@@ -664,8 +640,7 @@ struct Builder {
         // at 8x8 / 16x16: slice K as well, slice 0 carries bias + residual, a sum pass follows.
         float *ks_scratch = nullptr;
         const long long dense_bs = (long long)w.Cout * s.Ho * s.Wo;
-        if (o.max_ksplit <= 1 && plan.split == 2 && !need_all && !o.ln_g && !o.relu && !o.shift && !o.stat_mean &&
-            !o.pre_add && !o.res3_w && w.nz == 1 && !w.transposed) {
+        if (o.max_ksplit <= 1 && plan.split == 2 && linear_ep) {
             const long long wgs = (long long)(plan.ipw > 1 ? ceil_div(pb(), plan.ipw) : plan.tiles_x * plan.tiles_y * pb()) *
                                   plan.groups;
             const int ks = (int)std::min<long long>(ceil_div(kKsTarget, wgs), std::min(4, plan.nchunk / 4));
@@ -674,7 +649,7 @@ struct Builder {
                 ks_scratch = dalloc((size_t)ks * B * dense_bs);
             }
         }
-        if (getenv("CDC_DEBUG_PLAN"))
+        if (debug_plan())
             fprintf(stderr, "[plan] %-10s Cin=%4d Cout=%4d k=%dx%d s=%d in=%3dx%-3d out=%3dx%-3d %s%s%s| MB=%2d NPW=%d "
                     "WN=%d groups=%2d KC=%2d nchunk=%3d tiles=%dx%d wgs=%6d lds=%6zu\n", kProfNames[prof], w.Cin,
                     w.Cout, w.KH, w.KW, w.stride, H, W, s.Ho, s.Wo, need_all ? "LN " : "   ",
@@ -694,48 +669,17 @@ struct Builder {
         if (plan.split == 2 && plan.arith == 1) { a.wsp = w.wsh; a.acc_scale = w.wscale_inv; }
         a.KH = w.KH; a.KW = w.KW; a.stride = w.stride;
         a.Cin_pad = w.Cin_pad; a.COP = w.COP; a.Cout = w.Cout;
-        a.out = out; a.out_bs = out_bs;
-        if (w.transposed) {
-            for (int z = 0; z < 4; ++z) {
-                const int py = z >> 1, px = z & 1;
-                a.pad_y[z] = w.tk == 5 ? 1 : 1 - py; a.pad_x[z] = w.tk == 5 ? 1 : 1 - px;
-                a.out_zoff[z] = py * 2 * W + px;
-            }
-            a.out_cs = (long long)4 * H * W; a.out_ys = 4 * W; a.out_xs = 2;
-        } else {
-            a.pad_y[0] = pad_y; a.pad_x[0] = pad_x;
-            a.out_cs = (long long)s.Ho * s.Wo; a.out_ys = s.Wo; a.out_xs = 1;
-        }
-        a.Ho = s.Ho; a.Wo = s.Wo;
-        a.bias = o.no_bias ? nullptr : w.bias;
-        a.pre_add = o.pre_add;
-        a.ep_g = o.ln_g; a.ep_b = o.ln_b; a.eps = 1e-5f; a.relu = o.relu; a.relu_slope = o.relu_slope;
-        a.shift = o.shift; a.shift_bs = o.shift_bs >= 0 ? o.shift_bs : h->shift_bs;
-        a.resid = o.resid; a.resid_bs = o.resid_bs; a.resid_cs = o.resid_cs;
-        a.stat_mean = o.stat_mean; a.stat_rstd = o.stat_rstd;
-        a.out_ks = (long long)B * out_bs;
-        a.res3_w = o.res3_w; a.res3_x = o.res3_x; a.res3_bs = o.res3_bs;
-        a.fault = fault_flag();
+        a.out = out; a.out_bs = out_bs; a.out_ks = (long long)B * out_bs;
+        out_geometry(a, w, s.Ho, s.Wo);
+        epilogue(a, w, o);
         if (o.uf_c) {
             a.uf_c = o.uf_c; a.uf_pad = o.uf_pad;
             a.uf_magic = o.uf_c > 1 ? (unsigned)(((1ull << 32) + o.uf_c - 1) / o.uf_c) : 0u;
         }
-        if (o.emit_pf && !ks_scratch && plan.ksplit <= 1 && (w.Cout % 32) == 0)
-            if (PfTwin *to = twin(out)) {
-                const int Ht = w.transposed ? 2 * H : s.Ho, Wt = w.transposed ? 2 * W : s.Wo;
-                if (to->C == w.Cout && to->H == Ht && to->W == Wt && out_bs == (long long)w.Cout * Ht * Wt) {
-                    a.out_pf = to->p; a.pf_bs = to->bs(); a.pf_ps = to->ps();
-                    if (w.transposed) {
-                        a.pf_ys = 2 * (Wt + 2); a.pf_xs = 2;
-                        for (int z = 0; z < 4; ++z) a.pf_zoff[z] = ((z >> 1) + 1) * (Wt + 2) + (z & 1) + 1;
-                    } else {
-                        a.pf_ys = Wt + 2; a.pf_xs = 1; a.pf_zoff[0] = (Wt + 2) + 1;
-                    }
-                    a.pf_only = o.no_f32 ? 1 : 0;
-                    last_pf_only = a.pf_only != 0;
-                    to->valid = true;
-                }
-            }
+        if (o.emit_pf && !ks_scratch && plan.ksplit <= 1 && (w.Cout % 32) == 0 && bind_out_pf(a, w, out, out_bs, s.Ho, s.Wo)) {
+            a.pf_only = o.no_f32 ? 1 : 0;
+            last_pf_only = o.no_f32;
+        }
         const double px = (double)B * s.Ho * s.Wo * w.nz;
         op.flops = 2.0 * px * w.Cout * w.Cin * w.KH * w.KW;
         op.bytes = 4.0 * ((double)B * w.Cin * H * W + px * w.Cout);
@@ -750,9 +694,7 @@ struct Builder {
             c.bytes = 4.0 * B * dense_bs * (plan.ksplit + 1);
             emit(c);
             // split-K epilogues cannot emit planes (partial sums): pack the reduced tensor where a reader wants them
-            if (o.emit_pf && !w.transposed)
-                if (PfTwin *to = twin(out))
-                    if (to->C == w.Cout && to->H == s.Ho && to->W == s.Wo && out_bs == (long long)w.Cout * s.Ho * s.Wo) pack(out, out_bs);
+            if (o.emit_pf && !w.transposed && out_twin(out, out_bs, w.Cout, s.Ho, s.Wo)) pack(out, out_bs);
         }
         return true;
     }

@@ -45,6 +45,8 @@ struct Param {                    // one state_dict entry
 struct ConvW {                    // packed convolution weights (device)
     int Cin = 0, Cout = 0, KH = 1, KW = 1, stride = 1, pad = 0;
     int pad_y = -1, pad_x = -1;   // override `pad` per axis when >= 0 (row-folded convolutions)
+    int py() const { return pad_y >= 0 ? pad_y : pad; }
+    int px() const { return pad_x >= 0 ? pad_x : pad; }
     int tk = 4;                   // transposed: kernel size of the reference layer (4: (4,2,1); 5: (5,2,2,op 1))
     bool transposed = false;      // ConvTranspose2d 4x4 s2 p1 as four 2x2 phase convolutions
     int Cin_pad = 0, COP = 0, nz = 1;
