@@ -112,6 +112,9 @@ def lib():
     L.cdc_entropy_peek.argtypes = [_vp, ctypes.c_size_t, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]
     L.cdc_entropy_set_limit.argtypes = [H, _i]
     L.cdc_entropy_decode.argtypes = [H, _vp, ctypes.POINTER(ctypes.c_size_t), _vp, _i, _vp, _vp, _i, _vp]
+    L.cdc_enable_vbr.argtypes = [H]
+    L.cdc_set_bitrate_scale.argtypes = [H, _vp, _i]
+    L.cdc_entropy_peek_bitrate_scale.argtypes = [_vp, ctypes.c_size_t, ctypes.POINTER(_i), ctypes.POINTER(ctypes.c_float)]
     L.cdc_dequantize.argtypes = [H, _vp, _vp, _vp, ctypes.c_longlong, _i, _vp]
     L.cdc_bpp.argtypes = [H, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]
     L.cdc_set_schedule.argtypes = [H, _i, _vp, _vp, _vp, _vp, _vp, _vp]
@@ -151,7 +154,7 @@ EXPORTS = ["cdc_create", "cdc_destroy", "cdc_last_error", "cdc_version", "cdc_nu
            "cdc_encoder_encode", "cdc_set_arith", "cdc_get_arith", "cdc_unet_tap", "cdc_prof_num_ops", "cdc_prof_op",
            "cdc_entropy_encode", "cdc_entropy_peek", "cdc_entropy_set_limit", "cdc_entropy_decode", "cdc_get_range_faults",
            "cdc_get_nonfinite_results", "cdc_set_schedule_v", "cdc_probe_mfma_f16", "cdc_probe_hbm_copy",
-           "cdc_op_stress", "cdc_op_stress_result"]
+           "cdc_op_stress", "cdc_op_stress_result", "cdc_enable_vbr", "cdc_set_bitrate_scale", "cdc_entropy_peek_bitrate_scale"]
 
 
 def handle_status(handle):

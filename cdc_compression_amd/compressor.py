@@ -12,6 +12,11 @@ are taken when present (each enables the corresponding entry points: `hyper_deco
 Decode side of the hyperprior: `hyper_decode(q_hyper_latent)` runs
 `hyper_dec` (compress_modules.py:54-59) and returns `(mean, scale.clamp(min=0.1))`; `dequantize(x, offset)`
 is `quantize(x, "dequantize", offset)` (utils.py:72-85).
+
+Variable bitrate (`BigCompressor(vbr=True)`, epsilonparam compress_modules.py:125-184): every entry point that runs a
+VBRCondition site takes the rate as `cond` / `bitrate_scale` -- a numpy array or torch tensor of 1 (broadcast) or B
+elements, as the reference's `cond.reshape(-1, 1, 1, 1)` accepts -- and the streams of `compress_to_bytes` carry each
+image's rate (container version 4), so `decompress_from_bytes` needs none.
 """
 import ctypes
 
@@ -35,7 +40,8 @@ class NormalDistribution:
 class _ContextDecoder:
     _up_index = 1
 
-    def __init__(self, dim, rev_mults, out_channels, device=0):
+    def __init__(self, dim, rev_mults, out_channels, device=0, vbr=False):
+        self.vbr = bool(vbr)
         self.dim = dim
         self.rev_mults = tuple(rev_mults)
         self.out_channels = out_channels
@@ -75,10 +81,39 @@ class _ContextDecoder:
             rc = L.cdc_ctxdec_create(ctypes.byref(cfg), self.device_index, ctypes.byref(h))
             if rc != 0:
                 raise _lib.CdcError(f"cdc_ctxdec_create failed ({rc}): {L.cdc_last_error(None).decode()}")
-            self._h = h
+            self._h = self._vbr_handle(h)
             for k, v in self._sd.items():
                 self._load_one(k, v)
         return self._h
+
+    # ---- variable bitrate ---------------------------------------------------------------------
+    def _vbr_handle(self, h):
+        """A freshly created handle, switched to the VBR model (manifest with the VBRCondition sites) when this is one."""
+        if self.vbr:
+            rc = _lib.lib().cdc_enable_vbr(h)
+            if rc != 0:
+                msg = _lib.lib().cdc_last_error(h).decode()
+                _lib.lib().cdc_destroy(h)
+                raise _lib.CdcError(f"cdc_enable_vbr failed ({rc}): {msg}")
+        return h
+
+    def _rates(self, cond, B):
+        """cond / bitrate_scale -> float32 host vector of 1 or B rates (VBR model), None (fixed-rate model)."""
+        if not self.vbr:
+            if cond is not None:
+                raise NotImplementedError(f"{type(self).__name__}(vbr=False) takes no bitrate conditioning (cond / bitrate_scale)")
+            return None
+        if cond is None:
+            raise ValueError(f"{type(self).__name__}(vbr=True) needs a bitrate_scale (cond): 1 or B values, e.g. in [0, 1]")
+        r = np.ascontiguousarray(_as_host_f32(cond).reshape(-1))
+        if r.size not in (1, B):
+            raise ValueError(f"bitrate_scale has {r.size} values for a batch of {B} (1 or {B} expected)")
+        return r
+
+    def _set_rate(self, h, cond, B):
+        r = self._rates(cond, B)
+        if r is not None:
+            _lib.check(h, _lib.lib().cdc_set_bitrate_scale(h, r.ctypes.data, int(r.size)))
 
     def __del__(self):
         try:
@@ -165,14 +200,15 @@ class _ContextDecoder:
 
     # ---- Compressor.decode ------------------------------------------------------------------
     def decode(self, input, cond=None):
-        """q_latent [B, reversed_dims[0], h, w] -> [ctx@16h, ctx@8h, ctx@4h, ctx@2h] (finest first)."""
-        if cond is not None:
-            raise NotImplementedError("vbr conditioning (VBRCondition) is not on the decode path (vbr=False)")
+        """q_latent [B, reversed_dims[0], h, w] -> [ctx@16h, ctx@8h, ctx@4h, ctx@2h] (finest first).  cond: the bitrate_scale
+        of a VBR model (1 or B values)."""
+        aq = _Arg(input, self.device_index)
+        B, C, hl, wl = aq.shape
+        self._rates(cond, B)
         L, h = _lib.lib(), self._handle()
         if not self._finalized:
             raise _lib.CdcError("load_state_dict() has not been called")
-        aq = _Arg(input, self.device_index)
-        B, C, hl, wl = aq.shape
+        self._set_rate(h, cond, B)
         if C != self.reversed_dims[0]:
             raise _lib.CdcError(f"q_latent has {C} channels, the decoder expects {self.reversed_dims[0]}")
         n = len(self.rev_mults)
@@ -199,7 +235,7 @@ class _ContextDecoder:
             rc = L.cdc_hyperdec_create(ctypes.byref(cfg), self.device_index, ctypes.byref(h))
             if rc != 0:
                 raise _lib.CdcError(f"cdc_hyperdec_create failed ({rc}): {L.cdc_last_error(None).decode()}")
-            self._hh = h
+            self._hh = self._vbr_handle(h)
         return self._hh
 
     def hyper_manifest(self):
@@ -246,13 +282,14 @@ class _ContextDecoder:
         self._hyper_finalized = True
         return self
 
-    def hyper_decode(self, q_hyper_latent, scale_min=0.1):
-        """compress_modules.py:54-59: (mean, scale) of the latent distribution from q_hyper_latent."""
+    def hyper_decode(self, q_hyper_latent, scale_min=0.1, cond=None):
+        """compress_modules.py:54-59: (mean, scale) of the latent distribution from q_hyper_latent (cond: VBR rate)."""
         L, h = _lib.lib(), self._hyper_handle()
         if not self._hyper_finalized:
             raise _lib.CdcError("load_hyper_state_dict() has not been called")
         aq = _Arg(q_hyper_latent, self.device_index)
         B, C, hh, wh = aq.shape
+        self._set_rate(h, cond, B)
         if C != self.reversed_hyper_dims[0]:
             raise _lib.CdcError(f"q_hyper_latent has {C} channels, hyper_dec expects {self.reversed_hyper_dims[0]}")
         up = 2 ** (len(self.reversed_hyper_dims) - 2)       # one stride-2 ConvTranspose2d per hyper_dec layer but the last
@@ -321,7 +358,7 @@ class _ContextDecoder:
             rc = L.cdc_encoder_create(ctypes.byref(cfg), self.device_index, ctypes.byref(h))
             if rc != 0:
                 raise _lib.CdcError(f"cdc_encoder_create failed ({rc}): {L.cdc_last_error(None).decode()}")
-            self._eh = h
+            self._eh = self._vbr_handle(h)
         return self._eh
 
     def encoder_manifest(self):
@@ -352,13 +389,14 @@ class _ContextDecoder:
         self._enc_finalized = True
         return self
 
-    def analysis(self, images):
-        """The unquantised (latent, hyper_latent) of Compressor.encode (compress_modules.py:43-51)."""
+    def analysis(self, images, cond=None):
+        """The unquantised (latent, hyper_latent) of Compressor.encode (compress_modules.py:43-51); cond: VBR rate."""
         L, h = _lib.lib(), self._enc_handle()
         if not self._enc_finalized:
             raise _lib.CdcError("load_encoder_state_dict() has not been called")
         ax = _Arg(images, self.device_index)
         B, C, H, W = ax.shape
+        self._set_rate(h, cond, B)
         n, nh = len(self.dim_mults), len(self.hyper_dims_mults)
         lat, pl, _ = _result_like(images, (B, self.dim * self.dim_mults[-1], H >> n, W >> n), self.device_index)
         hyp, ph, _ = _result_like(images, (B, self.dim * self.hyper_dims_mults[-1], H >> (n + nh - 1), W >> (n + nh - 1)),
@@ -376,12 +414,11 @@ class _ContextDecoder:
         return med
 
     def encode(self, input, cond=None):
-        """Compressor.encode (compress_modules.py:43-66): (q_latent, q_hyper_latent, state4bpp)."""
-        if cond is not None:
-            raise NotImplementedError("vbr conditioning is not implemented (vbr=False)")
-        latent, hyper_latent = self.analysis(input)
+        """Compressor.encode (compress_modules.py:43-66): (q_latent, q_hyper_latent, state4bpp); cond: VBR rate."""
+        self._rates(cond, _Arg(input, self.device_index).shape[0])
+        latent, hyper_latent = self.analysis(input, cond)
         q_hyper_latent = self.dequantize(hyper_latent, self._medians_like(hyper_latent))
-        mean, scale = self.hyper_decode(q_hyper_latent)
+        mean, scale = self.hyper_decode(q_hyper_latent, cond=cond)
         q_latent = self.dequantize(latent, mean)
         state4bpp = {"latent": latent, "hyper_latent": hyper_latent,
                      "latent_distribution": NormalDistribution(mean, scale)}
@@ -393,13 +430,15 @@ class _ContextDecoder:
         med = self._medians.reshape(-1) if self._medians is not None else np.zeros(C, np.float32)
         return np.ascontiguousarray(med, dtype=np.float32)
 
-    def compress_to_bytes(self, images):
+    def compress_to_bytes(self, images, bitrate_scale=None):
         """images [B, 3, H, W] -> list of B bitstreams (bytes): analysis transform + hyper encoder on the GPU, then the
-        range-ANS coder of include/cdc_hip.h (cdc_entropy_encode) over exactly the symbols `bpp()` prices."""
-        latent, hyper = self.analysis(images)
-        return self.latents_to_bytes(latent, hyper)
+        range-ANS coder of include/cdc_hip.h (cdc_entropy_encode) over exactly the symbols `bpp()` prices.  A VBR model
+        takes bitrate_scale (1 or B values) and records each image's rate in its stream."""
+        self._rates(bitrate_scale, _Arg(images, self.device_index).shape[0])
+        latent, hyper = self.analysis(images, bitrate_scale)
+        return self.latents_to_bytes(latent, hyper, bitrate_scale)
 
-    def latents_to_bytes(self, latent, hyper):
+    def latents_to_bytes(self, latent, hyper, bitrate_scale=None):
         """The UNquantised outputs of `analysis()` -> list of B bitstreams.  The coder's determinism contract starts here: the
         same (latent, hyper) rows give the same bytes whatever the batch they are coded in (the analysis transform itself is
         an ordinary batched forward: its last bits may depend on the batch size, like any other entry point's)."""
@@ -408,6 +447,7 @@ class _ContextDecoder:
             raise _lib.CdcError("the prior.* tensors have not been loaded (load_state_dict with the full state_dict)")
         al, ah = _Arg(latent, self.device_index), _Arg(hyper, self.device_index)
         B, _, hh, wh = ah.shape
+        self._set_rate(h, bitrate_scale, B)
         nsym = int(np.prod(al.shape[1:])) + int(np.prod(ah.shape[1:]))
         cap = B * (64 + 2 * 320 + 6 * nsym)              # <= 2 renormalisation bytes + a 4-byte escape payload per symbol
         buf = np.empty(cap, dtype=np.uint8)
@@ -418,10 +458,12 @@ class _ContextDecoder:
         raw = buf[: offs[B]].tobytes()
         return [raw[offs[b]: offs[b + 1]] for b in range(B)]
 
-    def decompress_from_bytes(self, streams, like=None, return_hyper=False, max_image_hw=None):
+    def decompress_from_bytes(self, streams, like=None, return_hyper=False, max_image_hw=None, return_bitrate_scale=False):
         """list of B bitstreams -> q_latent [B, C, h, w] exactly as the encoder dequantised it (numpy, or a tensor on
         `like`'s device); all streams must have the same latent size.  max_image_hw=(H, W): refuse streams whose header
-        describes a larger image before anything is allocated (untrusted input; default: the library's 2^22-position bound)."""
+        describes a larger image before anything is allocated (untrusted input; default: the library's 2^22-position bound).
+        return_bitrate_scale: also return the float32 [B] rates the streams of a VBR model carry (None for a fixed-rate model);
+        `decode(q_latent, rates)` then gives the context pyramid."""
         L, h = _lib.lib(), self._hyper_handle()
         # the limit is handle state in the library: set it on EVERY call (None -> the library's default bound), so that one
         # restricted call does not restrict the next; the product is clamped before it is handed over as a C int
@@ -457,13 +499,31 @@ class _ContextDecoder:
         offs[B] = pos
         med = self._median_vector()
         _lib.check(h, L.cdc_entropy_decode(h, blob, offs, med.ctypes.data, B, pq, ph, mem, _current_stream(mem)))
-        return (q, qh) if return_hyper else q
+        out = (q, qh) if return_hyper else (q,)
+        if return_bitrate_scale:
+            out = out + (self.bitrate_scale_of(streams) if self.vbr else None,)
+        return out if len(out) > 1 else out[0]
+
+    @staticmethod
+    def bitrate_scale_of(streams):
+        """float32 [B]: the bitrate_scale each (version-4, variable-bitrate) stream carries; a fixed-rate stream has none."""
+        L = _lib.lib()
+        has, r = ctypes.c_int(), ctypes.c_float()
+        out = np.empty(len(streams), np.float32)
+        for b, s in enumerate(streams):
+            s = bytes(s)
+            if L.cdc_entropy_peek_bitrate_scale(s, len(s), ctypes.byref(has), ctypes.byref(r)) != 0:
+                raise _lib.CdcError("not a CDC bitstream")
+            if not has.value:
+                raise _lib.CdcError(f"stream {b} is a fixed-rate (version 3) stream: it carries no bitrate_scale")
+            out[b] = r.value
+        return out
 
     def forward(self, input, cond=None):
         """Compressor.forward (compress_modules.py:92-103)."""
         q_latent, q_hyper_latent, state4bpp = self.encode(input, cond)
         shape = tuple(_Arg(input, self.device_index).shape)
-        return {"output": self.decode(q_latent), "bpp": self.bpp(shape, state4bpp), "q_latent": q_latent,
+        return {"output": self.decode(q_latent, cond), "bpp": self.bpp(shape, state4bpp), "q_latent": q_latent,
                 "q_hyper_latent": q_hyper_latent}
 
     __call__ = forward
@@ -484,13 +544,11 @@ class ResnetCompressor(_ContextDecoder):
 
 
 class BigCompressor(_ContextDecoder):
-    """epsilonparam/modules/compress_modules.py:112-185 (decoder half, vbr=False)."""
+    """epsilonparam/modules/compress_modules.py:112-185; vbr=True adds the VBRCondition sites (variable bitrate)."""
     _up_index = 2
 
     def __init__(self, dim=64, dim_mults=(1, 3, 3, 3), hyper_dims_mults=(3, 3, 3), channels=3,
                  out_channels=3, vbr=False, device=0):
-        if vbr:
-            raise NotImplementedError("vbr=True (VBRCondition scalers) is not on the decode path")
-        super().__init__(dim, tuple(reversed(dim_mults)), out_channels, device)
+        super().__init__(dim, tuple(reversed(dim_mults)), out_channels, device, vbr=vbr)
         self.dim_mults, self.hyper_dims_mults, self.channels = tuple(dim_mults), tuple(hyper_dims_mults), channels
         self.reversed_hyper_dims = list(reversed([dim * dim_mults[-1] * 2] + [dim * m for m in hyper_dims_mults]))

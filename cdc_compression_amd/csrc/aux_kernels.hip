@@ -1662,6 +1662,39 @@ hipError_t dequantize_launch(const float *x, const float *loc, float *out, long 
     return hipGetLastError();
 }
 
+// VBRCondition (epsilonparam network_components.py:304-314) at one site, in place: one (image, channel) plane per blockIdx (y, z), so
+// the scale s and shift t are two multiply-adds of the plane's own rate and channel parameters (no separate launch, no table), and
+// image b's result depends on rate[b] alone (the entropy coder's batch = batch-1 contract).  The products and sums are rounded
+// one by one as the reference's `input * scale + shift` (a 1x1 convolution of a 1-channel input is w r + b); LeakyReLU(0.2) of
+// the hyper layers follows.  V = float4: 16-byte accesses (HW % 4 == 0, 16-byte aligned planes).
+template <class V>
+__global__ void __launch_bounds__(256) vbr_affine_kernel(float *x, long long bs, int C, int HW, const float *rate, const float *p, int leaky) {
+    const int c = blockIdx.y, b = blockIdx.z;
+    const float r = rate[b];
+    const float s = __fadd_rn(__fmul_rn(p[c], r), p[C + c]), t = __fadd_rn(__fmul_rn(p[2 * C + c], r), p[3 * C + c]);
+    auto f = [&](float v) { const float y = __fadd_rn(__fmul_rn(v, s), t); return (leaky && !(y > 0.f)) ? __fmul_rn(y, 0.2f) : y; };
+    V *q = reinterpret_cast<V *>(x + (size_t)b * bs + (size_t)c * HW);
+    const int n = HW / (int)(sizeof(V) / sizeof(float));
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        if constexpr (sizeof(V) == 16) {
+            float4 v = q[i];
+            v.x = f(v.x); v.y = f(v.y); v.z = f(v.z); v.w = f(v.w);
+            q[i] = v;
+        } else {
+            q[i] = f(q[i]);
+        }
+    }
+}
+
+hipError_t vbr_affine_launch(float *x, long long bs, int C, int HW, const float *rate, const float *p, int leaky, int B, hipStream_t st) {
+    const bool v4 = ((HW | bs) & 3) == 0 && (reinterpret_cast<size_t>(x) & 15) == 0;
+    const int n = v4 ? HW / 4 : HW;
+    const dim3 grid((unsigned)std::max(1, std::min((n + 1023) / 1024, 64)), (unsigned)C, (unsigned)B);   // <= 4 accesses per thread
+    if (v4) hipLaunchKernelGGL(vbr_affine_kernel<float4>, grid, dim3(256), 0, st, x, bs, C, HW, rate, p, leaky);
+    else hipLaunchKernelGGL(vbr_affine_kernel<float>, grid, dim3(256), 0, st, x, bs, C, HW, rate, p, leaky);
+    return hipGetLastError();
+}
+
 hipError_t copy_channels_launch(const float *src, long long src_bs, float *dst, long long dst_bs,
                                 long long n, int B, hipStream_t st, int parts, long long part_stride,
                                 const int *step_ptr, long long step_stride) {

@@ -108,6 +108,9 @@ int run_op(cdc_handle *h, const Op &op, int B, hipStream_t st) {
             HIP_TRY(h, copy_channels_launch(op.cp.src, op.cp.src_bs, op.cp.dst, op.cp.dst_bs, op.cp.n,
                                             B, st, op.cp_parts, op.cp_part_stride, op.cp_step, op.cp_step_stride));
             break;
+        case Op::VBR:
+            HIP_TRY(h, vbr_affine_launch(op.vb.x, op.vb.bs, op.vb.C, op.vb.HW, op.vb.rate, op.vb.p, op.vb.leaky, B, st));
+            break;
     }
     if (prof) {
         HIP_TRY(h, hipEventRecord(eb, st));
@@ -206,6 +209,23 @@ int check_ready(cdc_handle *h) {
     if (!h) return CDC_ERR_INVALID;
     if (!h->finalized) return fail(h, CDC_ERR_STATE, "weights not finalized (cdc_finalize_weights)");
     HIP_TRY(h, hipSetDevice(h->device));
+    return CDC_OK;
+}
+
+// The per-image rates of one call of a VBR program into its d_rate buffer: `rates` (B values, the entropy decoder's from the stream
+// headers) or the handle's cdc_set_bitrate_scale values (1, broadcast, or B).  There is no default rate.  No-op on a non-VBR handle.
+int stage_rate(cdc_handle *h, const float *rates, int B, hipStream_t st) {
+    if (!h->vbr) return CDC_OK;
+    if (!h->d_rate) return fail(h, CDC_ERR_STATE, "variable-bitrate program without a rate buffer");
+    if (!rates) {
+        const size_t n = h->vbr_rate.size();
+        if (n == 0) return fail(h, CDC_ERR_STATE, "variable-bitrate model: no bitrate_scale set (cdc_set_bitrate_scale)");
+        if (n != 1 && n != (size_t)B)
+            return fail(h, CDC_ERR_INVALID, "bitrate_scale has %zu values for a batch of %d (1 or %d expected)", n, B, B);
+    }
+    h->vbr_stage.resize((size_t)B);
+    for (int b = 0; b < B; ++b) h->vbr_stage[b] = rates ? rates[b] : h->vbr_rate[h->vbr_rate.size() == 1 ? 0 : b];
+    HIP_TRY(h, hipMemcpyAsync(h->d_rate, h->vbr_stage.data(), sizeof(float) * B, hipMemcpyHostToDevice, st));
     return CDC_OK;
 }
 
@@ -317,6 +337,32 @@ int cdc_get_arith(const cdc_handle *h) { return h ? h->arith : CDC_ERR_INVALID; 
 int cdc_get_range_faults(const cdc_handle *h) { return h ? h->range_faults : CDC_ERR_INVALID; }
 int cdc_get_nonfinite_results(const cdc_handle *h) { return h ? h->nonfinite_results : CDC_ERR_INVALID; }
 
+int cdc_enable_vbr(cdc_handle *h) {
+    if (!h) return CDC_ERR_INVALID;
+    if (h->kind < 1 || h->kind > 3) return fail(h, CDC_ERR_INVALID, "variable bitrate needs a context-decoder, encoder or hyper-decoder handle");
+    if ((h->kind == 1 && h->up_index != 2) || (h->kind == 3 && h->down_index != 2))
+        return fail(h, CDC_ERR_INVALID, "variable bitrate: the VBRCondition sits at index 1 of each level, so the resampling layer must be at index 2");
+    for (const Param &p : h->params)
+        if (p.loaded) return fail(h, CDC_ERR_STATE, "cdc_enable_vbr must come before any cdc_load_tensor");
+    if (h->vbr) return CDC_OK;
+    return no_throw(h, [&] {
+        h->vbr = true;
+        h->params.clear();
+        h->pindex.clear();
+        build_compressor_manifest(h);
+        return CDC_OK;
+    });
+}
+
+int cdc_set_bitrate_scale(cdc_handle *h, const float *cond, int n) {
+    if (!h) return CDC_ERR_INVALID;
+    if (!h->vbr) return fail(h, CDC_ERR_STATE, "not a variable-bitrate handle (cdc_enable_vbr)");
+    if (!cond || n < 1) return fail(h, CDC_ERR_INVALID, "null/invalid argument");
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(cond[i])) return fail(h, CDC_ERR_INVALID, "bitrate_scale[%d] is not finite", i);
+    return no_throw(h, [&] { h->vbr_rate.assign(cond, cond + n); return CDC_OK; });
+}
+
 int cdc_num_tensors(const cdc_handle *h) {
     if (!h) return CDC_ERR_INVALID;
     int n = 0;
@@ -371,19 +417,7 @@ int cdc_encoder_create(const cdc_encoder_config *cfg, int device, cdc_handle **o
     for (int i = 0; i < cfg->n_dim_mults; ++i) h->enc_dims.push_back(cfg->dim * cfg->dim_mults[i]);
     h->henc_dims.push_back(h->enc_dims.back());
     for (int i = 0; i < cfg->n_hyper_mults; ++i) h->henc_dims.push_back(cfg->dim * cfg->hyper_mults[i]);
-    for (int i = 0; i < cfg->n_dim_mults; ++i) {          // registration order of Compressor.enc (:131-141)
-        const std::string p = "enc." + std::to_string(i);
-        add_resblock_params(h.get(), p + ".0", h->enc_dims[i], h->enc_dims[i + 1], i == 0 ? 7 : 3, false);
-        const std::string d = p + "." + std::to_string(cfg->down_index) + ".conv";
-        add_param(h.get(), d + ".weight", {h->enc_dims[i + 1], h->enc_dims[i + 1], 3, 3});
-        add_param(h.get(), d + ".bias", {h->enc_dims[i + 1]});
-    }
-    for (int i = 0; i < cfg->n_hyper_mults; ++i) {        // Compressor.hyper_enc (:155-165)
-        const std::string p = "hyper_enc." + std::to_string(i) + ".0";
-        const int k = i == 0 ? 3 : 5;
-        add_param(h.get(), p + ".weight", {h->henc_dims[i + 1], h->henc_dims[i], k, k});
-        add_param(h.get(), p + ".bias", {h->henc_dims[i + 1]});
-    }
+    build_compressor_manifest(h.get());
     *out = h.release();
     return CDC_OK;
 }
@@ -396,6 +430,7 @@ int cdc_encoder_encode(cdc_handle *h, const float *images, float *latent, float 
     if (!images || !latent || !hyper_latent || B < 1) return fail(h, CDC_ERR_INVALID, "null/invalid argument");
     if ((rc = build_encoder_program(h, B, H, W))) return rc;
     hipStream_t st = pick_stream(h, stream, mem);
+    if ((rc = stage_rate(h, nullptr, B, st))) return rc;
     if ((rc = copy_in(h, h->in_x, images, (size_t)B * h->enc_dims[0] * H * W, mem, st))) return rc;
     const bool guard = guard_enabled(h);
     if (guard) { if ((rc = ensure_fault_flag(h))) return rc; HIP_TRY(h, hipMemsetAsync(h->d_fault, 0, sizeof(int), st)); }
@@ -428,21 +463,7 @@ int cdc_hyperdec_create(const cdc_hyperdec_config *cfg, int device, cdc_handle *
         h->hyper_dims.push_back(cfg->dims[i]);
     }
     if (h->hyper_dims.back() % 2) return fail(nullptr, CDC_ERR_INVALID, "the last layer must produce mean and scale");
-    for (int i = 0; i < cfg->n_layers; ++i) {
-        const std::string p = "hyper_dec." + std::to_string(i) + ".0";
-        const int din = h->hyper_dims[i], dout = h->hyper_dims[i + 1];
-        if (i == cfg->n_layers - 1) add_param(h.get(), p + ".weight", {dout, din, 3, 3});      // Conv2d
-        else add_param(h.get(), p + ".weight", {din, dout, 5, 5});                          // ConvTranspose2d
-        add_param(h.get(), p + ".bias", {dout});
-    }
-    // FlexiblePrior(channels = dims[0], dims = [3, 3, 3]) (network_components.py:316-336), squeezed shapes;
-    // optional: only cdc_bpp needs it
-    const int pc = h->hyper_dims[0], pd[5] = {1, 3, 3, 3, 1};
-    for (int i = 0; i < 4; ++i) {
-        add_param(h.get(), "prior.affine." + std::to_string(i) + ".weight", {pc, pd[i], pd[i + 1]}, true);
-        add_param(h.get(), "prior.affine." + std::to_string(i) + ".bias", {pc, pd[i + 1]}, true);
-        if (i < 3) add_param(h.get(), "prior.a." + std::to_string(i), {pc, pd[i + 1]}, true);
-    }
+    build_compressor_manifest(h.get());
     *out = h.release();
     return CDC_OK;
 }
@@ -497,6 +518,7 @@ int cdc_hyperdec_decode(cdc_handle *h, const float *q_hyper_latent, float *mean,
         return fail(h, CDC_ERR_INVALID, "null/invalid argument");
     if ((rc = build_hyperdec_program(h, B, hh, wh))) return rc;
     hipStream_t st = pick_stream(h, stream, mem);
+    if ((rc = stage_rate(h, nullptr, B, st))) return rc;
     if ((rc = copy_in(h, h->in_x, q_hyper_latent, (size_t)B * h->hyper_dims[0] * hh * wh, mem, st))) return rc;
     const bool guard = guard_enabled(h);
     if (guard) { if ((rc = ensure_fault_flag(h))) return rc; HIP_TRY(h, hipMemsetAsync(h->d_fault, 0, sizeof(int), st)); }
@@ -562,15 +584,7 @@ int cdc_ctxdec_create(const cdc_ctxdec_config *cfg, int device, cdc_handle **out
         h->rev_dims.push_back(cfg->dim * cfg->rev_mults[i]);
     }
     h->rev_dims.push_back(cfg->out_channels);
-    const int n = cfg->n_rev_mults;
-    for (int i = 0; i < n; ++i) {       // registration order of Compressor.dec (compress_modules.py:147-156)
-        const std::string p = "dec." + std::to_string(i);
-        const int din = h->rev_dims[i], dout = h->rev_dims[i + 1], dmid = i == n - 1 ? din : dout;
-        add_resblock_params(h.get(), p + ".0", din, dmid, 3, false);
-        const std::string u = p + "." + std::to_string(cfg->up_index);
-        add_param(h.get(), u + ".conv.weight", {dmid, dout, 4, 4});     // ConvTranspose2d: [Cin][Cout][4][4]
-        add_param(h.get(), u + ".conv.bias", {dout});
-    }
+    build_compressor_manifest(h.get());
     *out = h.release();
     return CDC_OK;
 }
@@ -587,6 +601,7 @@ int cdc_ctxdec_decode(cdc_handle *h, const float *q_latent, float *const *outs, 
         if (!outs[i]) return fail(h, CDC_ERR_INVALID, "null output %d", i);
     if ((rc = build_ctxdec_program(h, B, hl, wl))) return rc;
     hipStream_t st = pick_stream(h, stream, mem);
+    if ((rc = stage_rate(h, nullptr, B, st))) return rc;
     if ((rc = copy_in(h, h->in_x, q_latent, (size_t)B * h->rev_dims[0] * hl * wl, mem, st))) return rc;
     const bool guard = guard_enabled(h);
     if (guard) { if ((rc = ensure_fault_flag(h))) return rc; HIP_TRY(h, hipMemsetAsync(h->d_fault, 0, sizeof(int), st)); }

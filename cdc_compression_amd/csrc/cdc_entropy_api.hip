@@ -5,6 +5,10 @@ namespace {
 constexpr int kStreamVersion = 3;
 // 'C' 'D' 'C' 3 | arith | 0 | hh u16 | wh u16 | n_hyper u32 | n_latent u32 | model hash u32 | symbol checksum u32 | hyper escapes u32 | latent escapes u32
 constexpr int kStreamHeader = 34;
+// variable-bitrate model: the same header with version byte 4, then bitrate_scale f32 (hyper_dec and the synthesis transform need it)
+constexpr int kStreamVersionVbr = 4;
+constexpr int kStreamHeaderVbr = 38;
+inline int stream_header(const unsigned char *s) { return s[3] == kStreamVersionVbr ? kStreamHeaderVbr : kStreamHeader; }
 
 int ensure_entropy(cdc_handle *h, const float *medians) {
     if (h->kind != 2) return fail(h, CDC_ERR_STATE, "handle is not a hyper decoder");
@@ -80,7 +84,7 @@ int entropy_encode_impl(cdc_handle *h, const float *latent, const float *hyper_l
     cdc::RansMeta *meta;
     long long *d_off;
     const long long cap_h = section_cap(nh), cap_l = section_cap(nl);
-    const long long pack_cap = (long long)B * (kStreamHeader + cap_h + 4 * nh + cap_l + 4 * nl);
+    const long long pack_cap = (long long)B * ((h->vbr ? kStreamHeaderVbr : kStreamHeader) + cap_h + 4 * nh + cap_l + 4 * nl);
     HIP_TRY(h, d.get(&symh, (size_t)B * nh)); HIP_TRY(h, d.get(&syml, (size_t)B * nl)); HIP_TRY(h, d.get(&bin, (size_t)B * nl));
     HIP_TRY(h, d.get(&sf, (size_t)B * std::max(nh, nl))); HIP_TRY(h, d.get(&ew, (size_t)B * std::max(nh, nl)));
     HIP_TRY(h, d.get(&sec_h, (size_t)B * cap_h)); HIP_TRY(h, d.get(&sec_l, (size_t)B * cap_l));
@@ -93,6 +97,7 @@ int entropy_encode_impl(cdc_handle *h, const float *latent, const float *hyper_l
     HIP_TRY(h, hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipStreamSynchronize(st));
     if (hbad) return fail(h, CDC_ERR_INVALID, "non-finite or out-of-range hyper-latent (nothing to code)");
+    if ((rc = stage_rate(h, nullptr, B, st))) return rc;      // variable bitrate: the handle's rates, recorded in the streams below
     int fault = 0;
     if ((rc = hyperdec_batch(h, B, st, guard_enabled(h) && !h->in_retry, &fault))) return rc;
     if (fault) {
@@ -107,7 +112,8 @@ int entropy_encode_impl(cdc_handle *h, const float *latent, const float *hyper_l
     HIP_TRY(h, cdc::rans_encode_launch(T, syml, nl, bin, nl, 0, Ch, (int)nl, 1u, B, sf, ew, sec_l, cap_l, esc_l, nl, meta + B, st));
     const long long dev_cap = (long long)std::min<unsigned long long>((unsigned long long)cap, (unsigned long long)pack_cap);
     HIP_TRY(h, d.get(&packed, (size_t)dev_cap));
-    cdc::RansPack P{sec_h, sec_l, esc_h, esc_l, meta, meta + B, cap_h, cap_l, nh, nl, dev_cap, packed, d_off, h->ent_model_hash, h->arith, hh, wh};
+    cdc::RansPack P{sec_h, sec_l, esc_h, esc_l, meta, meta + B, cap_h, cap_l, nh, nl, dev_cap, packed, d_off, h->ent_model_hash, h->arith, hh, wh,
+                    h->vbr ? h->d_rate : nullptr};
     HIP_TRY(h, cdc::rans_pack_launch(P, B, st));
     std::vector<long long> hoff((size_t)B + 1);
     HIP_TRY(h, hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -139,20 +145,28 @@ int entropy_decode_impl(cdc_handle *h, const unsigned char *in, const size_t *of
     // the decoder runs hyper_dec in the encoder's arithmetic (see the contract in entropy.hip); the handle's own mode comes back
     struct Restore { cdc_handle *h; int a; ~Restore() { if (h->arith != a) (void)cdc_set_arith(h, a); } } restore{h, h->arith};
     // ---- headers: everything that sizes an allocation is validated here ----
-    struct Hdr { int hh, wh, ar; uint32_t nbh, nbl, sum, eh, el; };
+    struct Hdr { int hh, wh, ar, hdr; uint32_t nbh, nbl, sum, eh, el; float rate; };
     std::vector<Hdr> hd((size_t)B);
     for (int b = 0; b < B; ++b) {
         if (offsets[b + 1] < offsets[b]) return fail(h, CDC_ERR_INVALID, "image %d: offsets decrease", b);
         const unsigned char *s = in + offsets[b];
         const size_t n = offsets[b + 1] - offsets[b];
         Hdr &q = hd[b];
-        if (cdc_entropy_peek(s, n, &q.hh, &q.wh, &q.ar)) return fail(h, CDC_ERR_INVALID, "image %d: not a CDC bitstream (version %d container)", b, kStreamVersion);
+        if (cdc_entropy_peek(s, n, &q.hh, &q.wh, &q.ar)) return fail(h, CDC_ERR_INVALID, "image %d: not a CDC bitstream (version %d / %d container)", b, kStreamVersion, kStreamVersionVbr);
+        int has_rate = 0;
+        q.rate = 0.f;
+        (void)cdc_entropy_peek_bitrate_scale(s, n, &has_rate, &q.rate);
+        if (has_rate != (h->vbr ? 1 : 0))
+            return fail(h, CDC_ERR_INVALID, h->vbr ? "image %d: a fixed-rate stream (version 3) given to a variable-bitrate model"
+                                                   : "image %d: a variable-bitrate stream (version 4) given to a fixed-rate model", b);
+        if (has_rate && !std::isfinite(q.rate)) return fail(h, CDC_ERR_INVALID, "image %d: non-finite bitrate_scale in the header", b);
+        q.hdr = stream_header(s);
         if (q.hh < 1 || q.wh < 1 || (long long)q.hh * q.wh > std::min(kMaxHyperPositions, h->ent_max_positions))
             return fail(h, CDC_ERR_INVALID, "image %d: hyper-latent size %d x %d in the stream header exceeds the decoder's limit of %d positions "
                         "(cdc_entropy_set_limit)", b, q.hh, q.wh, std::min(kMaxHyperPositions, h->ent_max_positions));
         if (q.ar != CDC_ARITH_BF16X3 && q.ar != CDC_ARITH_F16X2) return fail(h, CDC_ERR_INVALID, "image %d: unknown arithmetic %d", b, q.ar);
         q.nbh = get_u32(s + 10); q.nbl = get_u32(s + 14); q.sum = get_u32(s + 22); q.eh = get_u32(s + 26); q.el = get_u32(s + 30);
-        if ((unsigned long long)kStreamHeader + q.nbh + q.nbl != n) return fail(h, CDC_ERR_INVALID, "image %d: truncated bitstream", b);
+        if ((unsigned long long)q.hdr + q.nbh + q.nbl != n) return fail(h, CDC_ERR_INVALID, "image %d: truncated bitstream", b);
         if (get_u32(s + 18) != h->ent_model_hash)
             return fail(h, CDC_ERR_INVALID, "image %d: the stream was coded with other probability tables (prior parameters, medians, library build or libm differ)", b);
         if (4ull * q.eh + 256 > q.nbh || 4ull * q.el + 256 > q.nbl) return fail(h, CDC_ERR_INVALID, "image %d: corrupt section sizes", b);
@@ -180,7 +194,7 @@ int entropy_decode_impl(cdc_handle *h, const unsigned char *in, const size_t *of
         std::vector<long long> off(2 * (size_t)nb);
         std::vector<int> len(2 * (size_t)nb), esc(2 * (size_t)nb);
         for (int b = b0; b < b1; ++b) {
-            const long long base = (long long)(offsets[b] - offsets[0]) + kStreamHeader;
+            const long long base = (long long)(offsets[b] - offsets[0]) + hd[b].hdr;
             off[b - b0] = base; len[b - b0] = (int)hd[b].nbh; esc[b - b0] = (int)hd[b].eh;
             off[nb + b - b0] = base + hd[b].nbh; len[nb + b - b0] = (int)hd[b].nbl; esc[nb + b - b0] = (int)hd[b].el;
         }
@@ -200,6 +214,11 @@ int entropy_decode_impl(cdc_handle *h, const unsigned char *in, const size_t *of
         const cdc::EntropyDev T = h->ent->dev();
         HIP_TRY(h, cdc::rans_decode_launch(T, d_in, d_off, d_len, d_esc, nullptr, 0, per, 0, (int)nh, 0u, nb, symh, nh, meta, st));
         HIP_TRY(h, cdc::symbols_to_hyper_launch(symh, h->ent->d_medians, Ch, per, nb, h->in_x, st));
+        if (h->vbr) {                     // each image's own rate; the handle's cdc_set_bitrate_scale values stay as they are
+            std::vector<float> rates((size_t)nb);
+            for (int b = b0; b < b1; ++b) rates[b - b0] = hd[b].rate;
+            if ((rc = stage_rate(h, rates.data(), nb, st))) return rc;
+        }
         int fault = 0;
         if ((rc = hyperdec_batch(h, nb, st, false, &fault))) return rc;
         HIP_TRY(h, cdc::latent_symbols_launch(nullptr, 0, o.p, o.p + nl, o.bs(), h->ent->d_edges, nl, nb, nullptr, bin, nullptr, st));
@@ -246,10 +265,19 @@ int cdc_entropy_set_limit(cdc_handle *h, int max_hyper_positions) {
 }
 
 int cdc_entropy_peek(const unsigned char *in, size_t n, int *hh, int *wh, int *arith) {
-    if (!in || n < (size_t)kStreamHeader || in[0] != 'C' || in[1] != 'D' || in[2] != 'C' || in[3] != kStreamVersion) return CDC_ERR_INVALID;
+    if (!in || n < (size_t)kStreamHeader || in[0] != 'C' || in[1] != 'D' || in[2] != 'C' ||
+        (in[3] != kStreamVersion && in[3] != kStreamVersionVbr) || n < (size_t)stream_header(in)) return CDC_ERR_INVALID;
     if (arith) *arith = in[4];
     if (hh) *hh = in[6] | (in[7] << 8);
     if (wh) *wh = in[8] | (in[9] << 8);
+    return CDC_OK;
+}
+
+int cdc_entropy_peek_bitrate_scale(const unsigned char *in, size_t n, int *has_scale, float *scale) {
+    if (cdc_entropy_peek(in, n, nullptr, nullptr, nullptr)) return CDC_ERR_INVALID;
+    const bool v4 = in[3] == kStreamVersionVbr;
+    if (has_scale) *has_scale = v4 ? 1 : 0;
+    if (v4 && scale) { const uint32_t u = get_u32(in + kStreamHeader); memcpy(scale, &u, 4); }
     return CDC_OK;
 }
 

@@ -250,6 +250,9 @@ hipError_t nonfinite_launch(const float *x, long long bs, long long n, int B, in
 // cdc_op_stress: counters[0] += 1, counters[1] += (a[0..n) differs bitwise from b[0..n)); counters[2] is scratch
 hipError_t bits_differ_launch(const float *a, const float *b, long long n, long long *counters, hipStream_t st);
 hipError_t dequantize_launch(const float *x, const float *loc, float *out, long long n, hipStream_t st);
+// VBRCondition (variable-bitrate compressors) in place over x [B][C][HW] (batch stride bs): with r = rate[b],
+// x = x * (p[c] r + p[C + c]) + (p[2C + c] r + p[3C + c]), then LeakyReLU(0.2) when `leaky`
+hipError_t vbr_affine_launch(float *x, long long bs, int C, int HW, const float *rate, const float *p, int leaky, int B, hipStream_t st);
 hipError_t unfold_x_launch(const float *src, long long src_bs, float *dst, long long dst_bs, int C, int KW,
                            int pad, int H, int W, int B, hipStream_t st);
 

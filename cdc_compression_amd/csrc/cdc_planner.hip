@@ -24,7 +24,7 @@ struct Builder {
         op.id = (int)h->op_ms.size();
         h->op_ms.push_back(0); h->op_n.push_back(0); h->op_flops.push_back(op.flops);
         char buf[160];
-        const char *kinds[] = {"conv", "ln", "temb", "kstats", "ctxp", "ctxr", "ctxf", "combine", "ddim", "copy", "unfold", "kvctx", "lnconv", "convpf", "pfpack", "convws", "convws1"};
+        const char *kinds[] = {"conv", "ln", "temb", "kstats", "ctxp", "ctxr", "ctxf", "combine", "ddim", "copy", "unfold", "kvctx", "lnconv", "convpf", "pfpack", "convws", "convws1", "vbr"};
         if (op.kind == Op::PFPACK && op.pk.c4 == 2) kinds[Op::PFPACK] = "pfunpack";
         if (op.kind == Op::CONV)
             snprintf(buf, sizeof buf, "conv %dx%d s%d %4d->%-4d out %3dx%-3d MB%d NPW%d WN%d g%d tg%d ipw%d ks%d%s%s%s%s%s", op.conv.KH,
@@ -50,6 +50,8 @@ struct Builder {
             snprintf(buf, sizeof buf, "kvctx C=%d N=%d nsplit=%d", op.kvc.C, op.kvc.N, op.kvc.nsplit);
         else if (op.kind == Op::LNCONV)
             snprintf(buf, sizeof buf, "lnconv C=%d N=%d nsplit=%d", op.lnc.C, op.lnc.N, op.lnc.nsplit);
+        else if (op.kind == Op::VBR)
+            snprintf(buf, sizeof buf, "vbr C=%d HW=%d%s", op.vb.C, op.vb.HW, op.vb.leaky ? " leaky" : "");
         else if (op.kind == Op::KSTATS || op.kind == Op::CTXP || op.kind == Op::CTXR || op.kind == Op::CTXF)
             snprintf(buf, sizeof buf, "%s C=%d N=%d nsplit=%d", op.at_one ? "ctx1" : kinds[op.kind], op.at.C, op.at.N, op.at_one ? 1 : op.at.nsplit);
         else
@@ -901,6 +903,16 @@ struct Builder {
         mark_planes_only(out);
         return out;
     }
+    // VBRCondition at one site of a variable-bitrate compressor (in place on the fp32 tensor; + LeakyReLU(0.2) at the hyper sites).
+    // `a` must have no PF twin: a plane reader would skip the affine (the VBR programs allocate these tensors without one).
+    void vbr(const Act &a, const VbrW &w, bool leaky) {
+        if (rc) return;
+        if (twin(a.p) || w.C != a.C || !h->d_rate) { rc = fail(h, CDC_ERR_INVALID, "VBR site %dx%dx%d: bad program", a.C, a.H, a.W); return; }
+        Op op; op.kind = Op::VBR; op.prof = PC_SMALL;
+        op.vb = {a.p, a.bs(), a.C, a.H * a.W, h->d_rate, w.p, leaky ? 1 : 0};
+        op.bytes = 8.0 * B * a.C * a.H * a.W;
+        emit(op);
+    }
     // after the block() call that produced `a`: if it wrote planes only, say so on the twin (its readers must take planes) and on the Act
     void mark_planes_only(Act &a) {
         if (!last_pf_only) return;
@@ -1049,6 +1061,7 @@ void free_program(cdc_handle *h) {
     h->pB = h->pH = h->pW = 0;
     h->p_batch1_plan = false;
     h->time_steps_B = 0;
+    h->d_rate = nullptr;           // (it lived in act_allocs)
 }
 
 // Builds the launch program of Unet.forward for batch B at H x W (unet.py:106-135).
@@ -1235,8 +1248,12 @@ int build_encoder_program(cdc_handle *h, int B, int H, int W) {
     h->in_x = bd.dalloc((size_t)B * h->enc_dims[0] * H * W);
     if (bd.rc) return bd.rc;
     Act x; x.p = h->in_x; x.C = h->enc_dims[0]; x.H = H; x.W = W;
+    // variable bitrate: the ResnetBlock outputs get no PF twin (the affine rewrites the fp32 copy; the Downsample then reads that)
+    const bool vbr = h->vbr;
+    if (vbr) h->d_rate = bd.dalloc((size_t)B);
     for (int i = 0; i < n; ++i) {
-        x = bd.resblock(h->rbs[i], x, nullptr, false, nullptr, nullptr);
+        x = bd.resblock(h->rbs[i], x, nullptr, false, nullptr, nullptr, vbr ? Builder::SITE_NONE : Builder::SITE_ALWAYS);
+        if (vbr) bd.vbr(x, h->vbrs[i], false);
         const ConvW &dw = h->downs[i];
         Act y = bd.new_act(dw.Cout, x.H / 2, x.W / 2);
         Builder::ConvOpts od; od.emit_pf = true;
@@ -1249,10 +1266,12 @@ int build_encoder_program(cdc_handle *h, int B, int H, int W) {
     for (int i = 0; i < nh; ++i) {
         const ConvW &cw = h->hconvs[i];
         const int s = i == 0 ? 1 : 2;
-        Act y = bd.new_act(cw.Cout, x.H / s, x.W / s);
+        const bool site = vbr && i < nh - 1;        // conv + bias, VBRCondition, LeakyReLU(0.2)
+        Act y = bd.new_act(cw.Cout, x.H / s, x.W / s, !site);
         Builder::ConvOpts o;
-        if (i < nh - 1) { o.relu = 1; o.relu_slope = 0.2f; }
+        if (i < nh - 1 && !site) { o.relu = 1; o.relu_slope = 0.2f; }
         bd.conv(cw, x.p, x.C, x.bs(), nullptr, 0, x.H, x.W, y.p, y.bs(), o, false, i == 0 ? PC_CONV3 : PC_DOWN);
+        if (site) bd.vbr(y, h->vbrs[n + i], true);
         x = y;
         if (bd.rc) return bd.rc;
     }
@@ -1272,13 +1291,16 @@ int build_hyperdec_program(cdc_handle *h, int B, int hh, int wh, bool batch1_pla
     if (bd.rc) return bd.rc;
     Act x; x.p = h->in_x; x.C = h->hyper_dims[0]; x.H = hh; x.W = wh;
     const int n = (int)h->hconvs.size();
+    const bool vbr = h->vbr;
+    if (vbr) h->d_rate = bd.dalloc((size_t)B);
     for (int i = 0; i < n; ++i) {
         const ConvW &cw = h->hconvs[i];
-        const bool last = i == n - 1;
-        Act y = bd.new_act(cw.Cout, last ? x.H : x.H * 2, last ? x.W : x.W * 2);
+        const bool last = i == n - 1, site = vbr && !last;   // variable bitrate: conv + bias, VBRCondition, LeakyReLU(0.2)
+        Act y = bd.new_act(cw.Cout, last ? x.H : x.H * 2, last ? x.W : x.W * 2, !site);
         Builder::ConvOpts o;
-        if (!last) { o.relu = 1; o.relu_slope = 0.2f; }           // nn.LeakyReLU(0.2)
+        if (!last && !site) { o.relu = 1; o.relu_slope = 0.2f; }           // nn.LeakyReLU(0.2)
         bd.conv(cw, x.p, x.C, x.bs(), nullptr, 0, x.H, x.W, y.p, y.bs(), o, false, last ? PC_CONV3 : PC_UP);
+        if (site) bd.vbr(y, h->vbrs[i], true);
         x = y;
         if (bd.rc) return bd.rc;
     }
@@ -1299,8 +1321,12 @@ int build_ctxdec_program(cdc_handle *h, int B, int hl, int wl) {
     if (bd.rc) return bd.rc;
     Act x; x.p = h->in_x; x.C = h->rev_dims[0]; x.H = hl; x.W = wl;
     const int n = (int)h->rev_dims.size() - 1;
+    // variable bitrate: as in the encoder, the ResnetBlock outputs get no PF twin, so the Upsample reads the affine's fp32 result
+    const bool vbr = h->vbr;
+    if (vbr) h->d_rate = bd.dalloc((size_t)B);
     for (int i = 0; i < n; ++i) {
-        x = bd.resblock(h->rbs[i], x, nullptr, false, nullptr, nullptr);
+        x = bd.resblock(h->rbs[i], x, nullptr, false, nullptr, nullptr, vbr ? Builder::SITE_NONE : Builder::SITE_ALWAYS);
+        if (vbr) bd.vbr(x, h->vbrs[i], false);
         const ConvW &uw = h->ups[i];
         Act y = bd.new_act(uw.Cout, x.H * 2, x.W * 2);
         Builder::ConvOpts ouu; ouu.emit_pf = true;

@@ -75,7 +75,7 @@ struct AttnW { std::string prefix; int C; ConvW qkv, out; float *ng, *nb;
                unsigned short *kvWh = nullptr; float kv_scale_inv = 1.f; };   // fp16 planes {WH, WL, WH2} of W' 2^s   // fused front half: (W_kv diag(g))^T [C][2C], W_kv b_ln [2C]   // folded output; uq = Wq b_ln
 
 struct Op {
-    enum Kind { CONV, LN, TEMB, KSTATS, CTXP, CTXR, CTXF, COMBINE, DDIM, COPY, UNFOLD, KVCTX, LNCONV, CONVPF, PFPACK, CONVWS, CONVWS1 } kind;
+    enum Kind { CONV, LN, TEMB, KSTATS, CTXP, CTXR, CTXF, COMBINE, DDIM, COPY, UNFOLD, KVCTX, LNCONV, CONVPF, PFPACK, CONVWS, CONVWS1, VBR } kind;
     int prof = PC_SMALL;
     int id = -1;                  // index into cdc_handle::op_ms (per-op timing table, debug aid)
     char label[96] = {0};
@@ -104,7 +104,10 @@ struct Op {
     int at_one = 0;                    // CTXP: row maxima, partial context and reduction in this ONE launch (ctx_one_launch)
     struct { const float *src; long long src_bs; float *dst; long long dst_bs; int C, KW, pad, H, W; } uf;
     struct { const float *src; long long src_bs; void *dst; long long dst_bs; int C, H, W; int c4; } pk;   // PFPACK (c4: fp32 -> accumulator order)
+    struct { float *x; long long bs; int C, HW; const float *rate, *p; int leaky; } vb;   // VBR: in-place VBRCondition (+ LeakyReLU 0.2)
 };
+
+struct VbrW { int C = 0; float *p = nullptr; };   // one VBRCondition site: [scale.weight | scale.bias | shift.weight | shift.bias], C each
 
 
 }  // namespace cdcapi
@@ -131,6 +134,13 @@ struct cdc_handle {
     std::vector<int> rev_dims;    // kind 1: [dim*m for m in rev_mults] + [out_channels]
     int up_index = 1;
     std::vector<Act> dec_outs;    // kind 1: outputs of the program, coarsest first
+    // variable bitrate (cdc_enable_vbr, kinds 1-3): a VBRCondition after every ResnetBlock (dec / enc) and after every hyper layer
+    // but the last (hyper_enc / hyper_dec), in forward order; the rate of each image lives in d_rate (program buffer, pB floats)
+    bool vbr = false;
+    std::vector<VbrW> vbrs;
+    std::vector<float> vbr_rate;  // cdc_set_bitrate_scale: 1 value (broadcast) or one per image; empty until set
+    std::vector<float> vbr_stage; // host staging of the per-image rates of the current call
+    float *d_rate = nullptr;
     int device = 0;
     int arith = default_arith();  // k x k / wide 1x1 convolutions: 1 two fp16 planes (3 MFMA products), 0 three bf16 planes (6)
     std::string err;
@@ -248,6 +258,9 @@ int build_program(cdc_handle *h, int B, int H, int W);
 int build_encoder_program(cdc_handle *h, int B, int H, int W);
 int build_hyperdec_program(cdc_handle *h, int B, int hh, int wh, bool batch1_plan = false);
 int build_ctxdec_program(cdc_handle *h, int B, int hl, int wl);
+// ---- variable bitrate: the manifest of a compressor handle (cdc_weights.hip), the rates of one call (cdc_api.hip)
+void build_compressor_manifest(cdc_handle *h);
+int stage_rate(cdc_handle *h, const float *rates, int B, hipStream_t st);
 // ---- cdc_api.hip: running a launch program
 hipEvent_t get_event(cdc_handle *h);
 int resolve_pending(cdc_handle *h);

@@ -91,6 +91,66 @@ void build_manifest(cdc_handle *h) {
     add_param(h, "final_conv.1.bias", {h->out_dim});
 }
 
+// The compressor handles (kinds 1-3), in the registration order of Compressor.enc / .hyper_enc / .hyper_dec / .dec
+// (epsilonparam compress_modules.py:125-184).  With h->vbr a VBRCondition(1, C) -- `.scale` / `.shift` Conv2d(1, C, 1) -- sits at index
+// 1 of every enc / dec level and of every hyper layer but the last.
+static void add_vbr_params(cdc_handle *h, const std::string &p, int c) {
+    add_param(h, p + ".scale.weight", {c, 1, 1, 1});
+    add_param(h, p + ".scale.bias", {c});
+    add_param(h, p + ".shift.weight", {c, 1, 1, 1});
+    add_param(h, p + ".shift.bias", {c});
+}
+
+void build_compressor_manifest(cdc_handle *h) {
+    if (h->kind == 3) {
+        const int n = (int)h->enc_dims.size() - 1, nh = (int)h->henc_dims.size() - 1;
+        for (int i = 0; i < n; ++i) {          // Compressor.enc (:131-141)
+            const std::string p = "enc." + std::to_string(i);
+            add_resblock_params(h, p + ".0", h->enc_dims[i], h->enc_dims[i + 1], i == 0 ? 7 : 3, false);
+            if (h->vbr) add_vbr_params(h, p + ".1", h->enc_dims[i + 1]);
+            const std::string d = p + "." + std::to_string(h->down_index) + ".conv";
+            add_param(h, d + ".weight", {h->enc_dims[i + 1], h->enc_dims[i + 1], 3, 3});
+            add_param(h, d + ".bias", {h->enc_dims[i + 1]});
+        }
+        for (int i = 0; i < nh; ++i) {         // Compressor.hyper_enc (:155-165)
+            const std::string p = "hyper_enc." + std::to_string(i);
+            const int k = i == 0 ? 3 : 5;
+            add_param(h, p + ".0.weight", {h->henc_dims[i + 1], h->henc_dims[i], k, k});
+            add_param(h, p + ".0.bias", {h->henc_dims[i + 1]});
+            if (h->vbr && i < nh - 1) add_vbr_params(h, p + ".1", h->henc_dims[i + 1]);
+        }
+    } else if (h->kind == 2) {
+        const int n = (int)h->hyper_dims.size() - 1;
+        for (int i = 0; i < n; ++i) {
+            const std::string p = "hyper_dec." + std::to_string(i);
+            const int din = h->hyper_dims[i], dout = h->hyper_dims[i + 1];
+            if (i == n - 1) add_param(h, p + ".0.weight", {dout, din, 3, 3});      // Conv2d
+            else add_param(h, p + ".0.weight", {din, dout, 5, 5});                 // ConvTranspose2d
+            add_param(h, p + ".0.bias", {dout});
+            if (h->vbr && i < n - 1) add_vbr_params(h, p + ".1", dout);
+        }
+        // FlexiblePrior(channels = dims[0], dims = [3, 3, 3]) (network_components.py:316-336), squeezed shapes;
+        // optional: only cdc_bpp needs it
+        const int pc = h->hyper_dims[0], pd[5] = {1, 3, 3, 3, 1};
+        for (int i = 0; i < 4; ++i) {
+            add_param(h, "prior.affine." + std::to_string(i) + ".weight", {pc, pd[i], pd[i + 1]}, true);
+            add_param(h, "prior.affine." + std::to_string(i) + ".bias", {pc, pd[i + 1]}, true);
+            if (i < 3) add_param(h, "prior.a." + std::to_string(i), {pc, pd[i + 1]}, true);
+        }
+    } else if (h->kind == 1) {
+        const int n = (int)h->rev_dims.size() - 1;
+        for (int i = 0; i < n; ++i) {          // Compressor.dec (compress_modules.py:147-156)
+            const std::string p = "dec." + std::to_string(i);
+            const int din = h->rev_dims[i], dout = h->rev_dims[i + 1], dmid = i == n - 1 ? din : dout;
+            add_resblock_params(h, p + ".0", din, dmid, 3, false);
+            if (h->vbr) add_vbr_params(h, p + ".1", dmid);
+            const std::string u = p + "." + std::to_string(h->up_index);
+            add_param(h, u + ".conv.weight", {dmid, dout, 4, 4});     // ConvTranspose2d: [Cin][Cout][4][4]
+            add_param(h, u + ".conv.bias", {dout});
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // weight upload / repacking
 // ------------------------------------------------------------------------------------------------
@@ -426,6 +486,21 @@ int pack_attn(cdc_handle *h, const std::string &p, int c) {
     return CDC_OK;
 }
 
+// one VBRCondition site -> [scale.weight | scale.bias | shift.weight | shift.bias] on the device (vbr_affine_kernel's operand)
+static int pack_vbr(cdc_handle *h, const std::string &p, int c) {
+    std::vector<float> v;
+    for (const char *suf : {".scale.weight", ".scale.bias", ".shift.weight", ".shift.bias"}) {
+        const auto &t = hostp(h, p + suf);
+        v.insert(v.end(), t.begin(), t.end());
+    }
+    VbrW w;
+    w.C = c;
+    int rc = upload(h, v.data(), v.size(), &w.p, &h->weight_allocs);
+    if (rc) return rc;
+    h->vbrs.push_back(w);
+    return CDC_OK;
+}
+
 void free_pool(std::vector<void *> *pool) {
     for (void *p : *pool) (void)hipFree(p);
     pool->clear();
@@ -446,7 +521,7 @@ int cdc_finalize_weights(cdc_handle *h) {
     free_program(h);
     free_pool(&h->weight_allocs);
     h->d_fault = nullptr; h->d_step = nullptr;          // (they lived in that pool)
-    h->rbs.clear(); h->attns.clear(); h->downs.clear(); h->ups.clear();
+    h->rbs.clear(); h->attns.clear(); h->downs.clear(); h->ups.clear(); h->vbrs.clear();
     if (h->kind == 3) {
         const int n = (int)h->enc_dims.size() - 1;
         int shift_off = 0;
@@ -458,6 +533,7 @@ int cdc_finalize_weights(cdc_handle *h) {
             const std::string d = p + "." + std::to_string(h->down_index) + ".conv";
             if ((rc = pack_named_conv(h, d + ".weight", d + ".bias", 2, 1, false, &dw))) return rc;
             h->downs.push_back(dw);
+            if (h->vbr && (rc = pack_vbr(h, p + ".1", h->enc_dims[i + 1]))) return rc;
         }
         h->hconvs.clear();
         const int nh = (int)h->henc_dims.size() - 1;
@@ -466,6 +542,7 @@ int cdc_finalize_weights(cdc_handle *h) {
             ConvW cw;
             if ((rc = pack_named_conv(h, p + ".weight", p + ".bias", i == 0 ? 1 : 2, i == 0 ? 1 : 2, false, &cw))) return rc;
             h->hconvs.push_back(cw);
+            if (h->vbr && i < nh - 1 && (rc = pack_vbr(h, "hyper_enc." + std::to_string(i) + ".1", h->henc_dims[i + 1]))) return rc;
         }
         h->shift_bs = 0;
         h->finalized = true;
@@ -480,6 +557,7 @@ int cdc_finalize_weights(cdc_handle *h) {
             const bool last = i == n - 1;
             if ((rc = pack_named_conv(h, p + ".weight", p + ".bias", last ? 1 : 2, last ? 1 : 2, !last, &cw))) return rc;
             h->hconvs.push_back(cw);
+            if (h->vbr && !last && (rc = pack_vbr(h, "hyper_dec." + std::to_string(i) + ".1", h->hyper_dims[i + 1]))) return rc;
         }
         h->d_prior = nullptr;
         if (h->params[h->pindex.at("prior.affine.0.weight")].loaded) {
@@ -530,6 +608,7 @@ int cdc_finalize_weights(cdc_handle *h) {
             const std::string u = p + "." + std::to_string(h->up_index);
             if ((rc = pack_named_conv(h, u + ".conv.weight", u + ".conv.bias", 2, 1, true, &uw))) return rc;
             h->ups.push_back(uw);
+            if (h->vbr && (rc = pack_vbr(h, p + ".1", dmid))) return rc;
         }
         h->shift_bs = 0;
         h->finalized = true;

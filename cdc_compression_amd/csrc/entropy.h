@@ -73,6 +73,7 @@ struct RansPack {
     long long *offsets;
     uint32_t model;
     int arith, hh, wh;
+    const float *rates = nullptr;   // variable-bitrate streams (version 4): each image's bitrate_scale after the header; null: version 3
 };
 hipError_t rans_pack_launch(const RansPack &P, int B, hipStream_t st);
 

@@ -132,29 +132,36 @@ class _GaussianDiffusionBase:
                 img = out.copy()
         return img
 
-    def decompress(self, context, shape, sample_steps=None, init=None, eta=0, clip_denoised=None):
+    def decompress(self, context, shape, sample_steps=None, init=None, eta=0, clip_denoised=None, bitrate_scale=None):
         """Decode half of compress(): context pyramid (= context_fn(...)["output"]) -> image.  `context`
         may also be the transmitted q_latent tensor [B, C, H/16, W/16]: it then goes through
-        `context_fn.decode` first (compress_modules.py:68-74; cdc_compression_amd.compressor on the GPU)."""
+        `context_fn.decode` first (compress_modules.py:68-74; cdc_compression_amd.compressor on the GPU) -- with
+        `bitrate_scale` (1 or B values) for a variable-bitrate context model -- or the entropy-coded streams, whose
+        variable-bitrate form carries each image's rate itself."""
         if isinstance(context, (bytes, bytearray)):
             context = [context]
         if isinstance(context, (list, tuple)) and context and isinstance(context[0], (bytes, bytearray)):
-            # entropy-coded bitstreams (compress_to_bytes): range-ANS decode -> q_latent
-            context = self.context_fn.decompress_from_bytes(context, like=init)
+            # entropy-coded bitstreams (compress_to_bytes): range-ANS decode -> q_latent (+ the rates of a VBR model)
+            if bitrate_scale is not None:
+                raise ValueError("the streams carry their own bitrate_scale")
+            context, bitrate_scale = self.context_fn.decompress_from_bytes(context, like=init, return_bitrate_scale=True)
         if not isinstance(context, (list, tuple)):
             if self.context_fn is None or not hasattr(self.context_fn, "decode"):
                 raise RuntimeError("decompress(q_latent, ...) needs a context_fn with decode()")
-            context = self.context_fn.decode(context)
+            context = self.context_fn.decode(context) if bitrate_scale is None else self.context_fn.decode(context, bitrate_scale)
         self.set_sample_schedule(self.num_timesteps if sample_steps is None else sample_steps)
         if clip_denoised is None:
             clip_denoised = True if self._param == "x" else getattr(self, "clip_noise", "none")
         return self._loop(tuple(shape), context, clip_denoised, init, eta)
 
 
-    def compress_to_bytes(self, images):
+    def compress_to_bytes(self, images, bitrate_scale=None):
         """The transmitted half of compress(): images -> one entropy-coded bitstream per image.
-        `decompress(streams, shape, sample_steps, init)` reconstructs from them."""
-        return self.context_fn.compress_to_bytes(images)
+        `decompress(streams, shape, sample_steps, init)` reconstructs from them.  bitrate_scale: the rate of a
+        variable-bitrate context model (1 or B values), recorded in each stream."""
+        if bitrate_scale is None:
+            return self.context_fn.compress_to_bytes(images)
+        return self.context_fn.compress_to_bytes(images, bitrate_scale)
 
 
 class GaussianDiffusionX(_GaussianDiffusionBase):

@@ -81,3 +81,29 @@ def context_pyramid(cfg_context_channels, B, H, W, seed=3, std=0.5):
     """N(0, std^2) stand-in for `context_fn.decode(q_latent)`: list of [B, C_l, H/2^l, W/2^l]."""
     return [normal(f"ctx{l}", (B, c, H >> l, W >> l), seed, std)
             for l, c in enumerate(cfg_context_channels)]
+
+
+def is_vbr_key(name):
+    """A VBRCondition parameter (epsilonparam network_components.py:304-314): `<site>.scale.*` / `<site>.shift.*`."""
+    parts = name.split(".")
+    return len(parts) >= 2 and parts[-2] in ("scale", "shift") and parts[-1] in ("weight", "bias")
+
+
+def compressor_state_dict(manifest, seed=0):
+    """Synthetic parameters for a compressor manifest: `unet_state_dict` for every entry but the VBRCondition scalers,
+    which keep the affine O(1) -- scale = 1 + N(0, 0.05^2) + N(0, 0.2^2) r, shift = N(0, 0.05^2) + N(0, 0.05^2) r -- instead of
+    the N(0, 0.1^2) bias / N(0, 1) weight draws that would make the activations vanish.  The scale still changes sign in some
+    channels at an extrapolated rate r (|r| of a few), which the golden generator pins."""
+    sd = unet_state_dict([(n, s) for n, s in manifest if not is_vbr_key(n)], seed=seed)
+    for name, shape in manifest:
+        if not is_vbr_key(name):
+            continue
+        shape = tuple(shape)
+        if name.endswith(".scale.weight"):
+            t = normal(name, shape, seed, 0.2)
+        elif name.endswith(".scale.bias"):
+            t = normal(name, shape, seed, 0.05, 1.0)
+        else:
+            t = normal(name, shape, seed, 0.05)
+        sd[name] = t
+    return {n: sd[n] for n, _ in manifest}

@@ -251,6 +251,7 @@ int cdc_bpp(cdc_handle *h, const float *q_hyper_latent, const float *q_latent, c
  * out receives B concatenated streams, image b at [offsets[b], offsets[b+1]) (offsets has B+1 entries).  Each stream:
  *   'C' 'D' 'C' 3 | arith u8 | 0 | h_hyper u16 | w_hyper u16 | n_hyper u32 | n_latent u32 | model u32 | symbols u32 |
  *   esc_hyper u32 | esc_latent u32 | hyper section | latent section                   (version 3, 34-byte header, little endian)
+ * (version 4, variable-bitrate models: see cdc_enable_vbr below -- the same header, then bitrate_scale f32 at bytes 34-37)
  * section = 64 x u32 final lane states | renormalisation bytes | escape payloads (u32 each, symbol order); n_* = section bytes.
  * model   = FNV-1a over every integer of the probability tables (per table K, then its 2K+2 frequencies; the per-channel
  *           hyper tables, then the 128 scale tables): a decoder whose tables differ (other prior.* parameters or medians,
@@ -272,6 +273,7 @@ int cdc_bpp(cdc_handle *h, const float *q_hyper_latent, const float *q_latent, c
  * Synchronous; latent / hyper_latent / q_latent / q_hyper_latent follow `mem`, in / out / offsets / medians are host. */
 int cdc_entropy_encode(cdc_handle *h, const float *latent, const float *hyper_latent, const float *medians, int B,
                        int h_hyper, int w_hyper, unsigned char *out, size_t cap, size_t *offsets, int mem_kind, void *stream);
+/* Header fields of a version-3 or version-4 stream (CDC_ERR_INVALID for anything else). */
 int cdc_entropy_peek(const unsigned char *in, size_t n, int *h_hyper, int *w_hyper, int *arith);
 /* A stream header sizes the decoder's allocations and its hyper_dec launch program (up to 2^22 positions = a 131072 x 131072
  * image: tens of GB on a 288 GB part).  A caller that knows what it expects bounds that BEFORE decoding untrusted bytes: streams whose
@@ -280,6 +282,32 @@ int cdc_entropy_set_limit(cdc_handle *h, int max_hyper_positions);
 /* -> q_latent [B][dims[n]/2][up*h][up*w] (exactly the encoder's dequantised latent) and, optionally, q_hyper_latent. */
 int cdc_entropy_decode(cdc_handle *h, const unsigned char *in, const size_t *offsets, const float *medians, int B,
                        float *q_latent, float *q_hyper_latent, int mem_kind, void *stream);
+
+/* ---- variable bitrate (epsilonparam BigCompressor(vbr=True), compress_modules.py:125-184) --------------------------------------
+ * A VBR model carries a VBRCondition(1, C) (network_components.py:304-314) at index 1 of every `enc` / `dec` level (after the
+ * ResnetBlock, before the Downsample / Upsample) and of every `hyper_enc` / `hyper_dec` layer but the last (after conv + bias,
+ * before the LeakyReLU): y[b][c] = x[b][c] * (scale.weight[c] r_b + scale.bias[c]) + (shift.weight[c] r_b + shift.bias[c]), r_b the
+ * image's bitrate_scale (in [0, 1] for a trained model; any finite value is taken).
+ *
+ * cdc_enable_vbr: switches a context-decoder, encoder or hyper-decoder handle to the VBR model.  Its manifest then also lists
+ *   "<site>.scale.weight" [C][1][1][1], ".scale.bias" [C], ".shift.weight" [C][1][1][1], ".shift.bias" [C] of its own sites, in the
+ *   reference's state_dict order, and cdc_finalize_weights requires them.  Only before the first cdc_load_tensor (CDC_ERR_STATE);
+ *   other handle kinds, or a resampling layer not at index 2 (up_index / down_index, as BigCompressor has it), get CDC_ERR_INVALID.
+ * cdc_set_bitrate_scale: the rates of every later compute call on the handle (cdc_ctxdec_decode, cdc_encoder_encode,
+ *   cdc_hyperdec_decode, cdc_entropy_encode) until set again: n = 1 (one rate for the whole batch) or n = B (one per image).  `cond`
+ *   is a host array, copied before return.  Non-finite values (CDC_ERR_INVALID) and non-VBR handles (CDC_ERR_STATE) are refused.
+ *   A compute call on a VBR handle with no rate set (CDC_ERR_STATE), or with n neither 1 nor B (CDC_ERR_INVALID), fails: there is
+ *   no default rate.  Image b's result depends on its own rate only, whatever the batch.
+ * Streams of a VBR hyper-decoder handle are container version 4: the version-3 header with version byte 4, then the image's
+ *   bitrate_scale (f32, little endian) at bytes 34-37; the sections start at byte 38.  cdc_entropy_encode records each image's rate
+ *   bit for bit; cdc_entropy_decode runs hyper_dec with each image's rate from its own stream (one call may mix rates) and leaves the
+ *   handle's cdc_set_bitrate_scale values as they were.  A version-4 stream on a non-VBR handle, or a version-3 stream on a VBR
+ *   handle, is refused (CDC_ERR_INVALID).  A non-VBR handle writes exactly the version-3 streams it always did.
+ * cdc_entropy_peek_bitrate_scale: a stream's rate without a handle: *has_scale = 1 and *scale = the rate for version 4,
+ *   *has_scale = 0 for version 3; CDC_ERR_INVALID for anything else.  (cdc_entropy_peek reads both versions.) */
+int cdc_enable_vbr(cdc_handle *h);
+int cdc_set_bitrate_scale(cdc_handle *h, const float *cond, int n);
+int cdc_entropy_peek_bitrate_scale(const unsigned char *in, size_t n, int *has_scale, float *scale);
 
 /* quantize(x, "dequantize", offset) = round(x - offset) + offset, round = half-to-even (utils.py:72-85). */
 int cdc_dequantize(cdc_handle *h, const float *x, const float *offset, float *out, long long n, int mem_kind,
