@@ -121,6 +121,15 @@ int run_op(cdc_handle *h, const Op &op, int B, hipStream_t st) {
     return CDC_OK;
 }
 
+// The launch program h->ops over B images (the compressor programs, the single operators).
+int run_ops(cdc_handle *h, int B, hipStream_t st) {
+    for (const Op &op : h->ops) {
+        int rc = run_op(h, op, B, st);
+        if (rc) return rc;
+    }
+    return CDC_OK;
+}
+
 // Context-only part of the program (hoisted context halves): once per decode / forward.
 int run_pre(cdc_handle *h, hipStream_t st) {
     for (const Op &op : h->pre_ops) {
@@ -212,6 +221,13 @@ int check_ready(cdc_handle *h) {
     return CDC_OK;
 }
 
+// CDC_ERR_STATE for a handle of another kind; a null handle is left to the entry point's own check
+int require_kind(cdc_handle *h, HandleKind kind) {
+    if (!h || h->kind == kind) return CDC_OK;
+    static const char *const what[] = {"a U-Net", "a context decoder", "a hyper decoder", "an encoder"};
+    return fail(h, CDC_ERR_STATE, "handle is not %s", what[(int)kind]);
+}
+
 // The per-image rates of one call of a VBR program into its d_rate buffer: `rates` (B values, the entropy decoder's from the stream
 // headers) or the handle's cdc_set_bitrate_scale values (1, broadcast, or B).  There is no default rate.  No-op on a non-VBR handle.
 int stage_rate(cdc_handle *h, const float *rates, int B, hipStream_t st) {
@@ -234,27 +250,26 @@ bool guard_enabled(const cdc_handle *h) {
     static const bool no_guard = getenv("CDC_NO_RANGE_GUARD") != nullptr;
     return !no_guard && (h->arith == CDC_ARITH_F16X2 || h->in_retry);
 }
-int ensure_fault_flag(cdc_handle *h) {
+int arm_range_guard(cdc_handle *h, hipStream_t st, bool always) {
+    if (!always && !guard_enabled(h)) return CDC_OK;
     if (!h->d_fault) { void *p = nullptr; HIP_TRY(h, hipMalloc(&p, sizeof(int))); h->d_fault = (int *)p; h->weight_allocs.push_back(p); }
+    HIP_TRY(h, hipMemsetAsync(h->d_fault, 0, sizeof(int), st));
     return CDC_OK;
 }
-// OR of "not finite" over device tensors (and of whatever a kernel already left in d_fault) -> *fault
-int guard_check(cdc_handle *h, std::initializer_list<GuardBuf> bufs, int B, hipStream_t st, int *fault) {
+int range_check(cdc_handle *h, const std::vector<GuardBuf> &bufs, int B, hipStream_t st) {
+    if (!guard_enabled(h)) return CDC_OK;
     for (const GuardBuf &g : bufs)
         if (g.p && g.n > 0) HIP_TRY(h, cdc::nonfinite_launch(g.p, g.bs, g.n, B, h->d_fault, st));
-    *fault = 0;
-    HIP_TRY(h, hipMemcpyAsync(fault, h->d_fault, sizeof(int), hipMemcpyDeviceToHost, st));
+    int fault = 0;
+    HIP_TRY(h, hipMemcpyAsync(&fault, h->d_fault, sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipStreamSynchronize(st));
-    return CDC_OK;
-}
-// a fault in F16X2: switch to the full-range arithmetic (returns true: repeat the call); a fault in the repetition: count it
-bool guard_escalate(cdc_handle *h, int *rc) {
-    *rc = CDC_OK;
+    if (!fault) return CDC_OK;
     if (h->in_retry || h->arith != CDC_ARITH_F16X2) {
         ++h->nonfinite_results;
         if (h->in_retry) h->retry_futile = true;            // non-finite in the full-range arithmetic too: it was not the fp16 range
-        return false;
+        return CDC_OK;
     }
+    // a fault in F16X2: switch to the full-range arithmetic and repeat the call
     ++h->range_faults;
     static bool warned = false;
     if (!warned) {
@@ -262,8 +277,22 @@ bool guard_escalate(cdc_handle *h, int *rc) {
         fprintf(stderr, "cdc_hip: a value left the fp16 range of CDC_ARITH_F16X2; the call is repeated in CDC_ARITH_BF16X3 and the handle stays "
                         "in that (slower, full-range) arithmetic -- see cdc_get_range_faults()\n");
     }
-    *rc = cdc_set_arith(h, CDC_ARITH_BF16X3);
-    return *rc == CDC_OK;
+    int rc = cdc_set_arith(h, CDC_ARITH_BF16X3);
+    return rc ? rc : kRangeRetry;
+}
+
+// The sequence of the compressor programs (encoder, hyper decoder, context decoder), built for B images: the per-image rates,
+// the input `x` (n floats), the launches and the range check of every output (h->dec_outs).
+static int run_compressor(cdc_handle *h, const float *x, size_t n, int B, int mem, hipStream_t st) {
+    int rc;
+    if ((rc = stage_rate(h, nullptr, B, st))) return rc;
+    if ((rc = copy_in(h, h->in_x, x, n, mem, st))) return rc;
+    if ((rc = arm_range_guard(h, st, false))) return rc;
+    h->prof_now = true;
+    if ((rc = run_ops(h, h->pB, st))) return rc;
+    std::vector<GuardBuf> outs;
+    for (const Act &a : h->dec_outs) outs.push_back({a.p, a.bs(), (long long)a.C * a.H * a.W});
+    return range_check(h, outs, B, st);
 }
 
 }  // namespace cdcapi
@@ -339,8 +368,8 @@ int cdc_get_nonfinite_results(const cdc_handle *h) { return h ? h->nonfinite_res
 
 int cdc_enable_vbr(cdc_handle *h) {
     if (!h) return CDC_ERR_INVALID;
-    if (h->kind < 1 || h->kind > 3) return fail(h, CDC_ERR_INVALID, "variable bitrate needs a context-decoder, encoder or hyper-decoder handle");
-    if ((h->kind == 1 && h->up_index != 2) || (h->kind == 3 && h->down_index != 2))
+    if (h->kind == HandleKind::Unet) return fail(h, CDC_ERR_INVALID, "variable bitrate needs a context-decoder, encoder or hyper-decoder handle");
+    if ((h->kind == HandleKind::ContextDecoder && h->up_index != 2) || (h->kind == HandleKind::Encoder && h->down_index != 2))
         return fail(h, CDC_ERR_INVALID, "variable bitrate: the VBRCondition sits at index 1 of each level, so the resampling layer must be at index 2");
     for (const Param &p : h->params)
         if (p.loaded) return fail(h, CDC_ERR_STATE, "cdc_enable_vbr must come before any cdc_load_tensor");
@@ -410,7 +439,7 @@ int cdc_encoder_create(const cdc_encoder_config *cfg, int device, cdc_handle **o
     std::unique_ptr<cdc_handle> h(new cdc_handle);
     memset(&h->cfg, 0, sizeof h->cfg);
     h->cfg.dim = cfg->dim;
-    h->kind = 3;
+    h->kind = HandleKind::Encoder;
     h->device = device;
     h->down_index = cfg->down_index;
     h->enc_dims.push_back(cfg->channels);
@@ -424,30 +453,18 @@ int cdc_encoder_create(const cdc_encoder_config *cfg, int device, cdc_handle **o
 
 int cdc_encoder_encode(cdc_handle *h, const float *images, float *latent, float *hyper_latent, int B, int H, int W,
                        int mem, void *stream) {
-    int rc = check_ready(h);
-    if (rc) return rc;
-    if (h->kind != 3) return fail(h, CDC_ERR_STATE, "handle is not an encoder");
-    if (!images || !latent || !hyper_latent || B < 1) return fail(h, CDC_ERR_INVALID, "null/invalid argument");
-    if ((rc = build_encoder_program(h, B, H, W))) return rc;
-    hipStream_t st = pick_stream(h, stream, mem);
-    if ((rc = stage_rate(h, nullptr, B, st))) return rc;
-    if ((rc = copy_in(h, h->in_x, images, (size_t)B * h->enc_dims[0] * H * W, mem, st))) return rc;
-    const bool guard = guard_enabled(h);
-    if (guard) { if ((rc = ensure_fault_flag(h))) return rc; HIP_TRY(h, hipMemsetAsync(h->d_fault, 0, sizeof(int), st)); }
-    h->prof_now = true;
-    for (const Op &op : h->ops)
-        if ((rc = run_op(h, op, h->pB, st))) return rc;
-    const Act &l = h->dec_outs[0], &hl = h->dec_outs[1];
-    if (guard) {
-        int fault = 0;
-        if ((rc = guard_check(h, {{l.p, l.bs(), (long long)l.C * l.H * l.W}, {hl.p, hl.bs(), (long long)hl.C * hl.H * hl.W}}, B, st, &fault))) return rc;
-        if (fault) {
-            if (guard_escalate(h, &rc)) { RetryScope r(h); return cdc_encoder_encode(h, images, latent, hyper_latent, B, H, W, mem, stream); }
-            if (rc) return rc;
-        }
-    }
-    if ((rc = copy_out(h, latent, l.p, (size_t)B * l.C * l.H * l.W, mem, st))) return rc;
-    return copy_out(h, hyper_latent, hl.p, (size_t)B * hl.C * hl.H * hl.W, mem, st);
+    return with_range_guard(h, [&]() -> int {
+        int rc = check_ready(h);
+        if (rc) return rc;
+        if ((rc = require_kind(h, HandleKind::Encoder))) return rc;
+        if (!images || !latent || !hyper_latent || B < 1) return fail(h, CDC_ERR_INVALID, "null/invalid argument");
+        if ((rc = build_encoder_program(h, B, H, W))) return rc;
+        hipStream_t st = pick_stream(h, stream, mem);
+        if ((rc = run_compressor(h, images, (size_t)B * h->enc_dims[0] * H * W, B, mem, st))) return rc;
+        const Act &l = h->dec_outs[0], &hl = h->dec_outs[1];
+        if ((rc = copy_out(h, latent, l.p, (size_t)B * l.C * l.H * l.W, mem, st))) return rc;
+        return copy_out(h, hyper_latent, hl.p, (size_t)B * hl.C * hl.H * hl.W, mem, st);
+    });
 }
 
 int cdc_hyperdec_create(const cdc_hyperdec_config *cfg, int device, cdc_handle **out) {
@@ -456,7 +473,7 @@ int cdc_hyperdec_create(const cdc_hyperdec_config *cfg, int device, cdc_handle *
     if (device < 0) return fail(nullptr, CDC_ERR_INVALID, "device %d out of range", device);
     std::unique_ptr<cdc_handle> h(new cdc_handle);
     memset(&h->cfg, 0, sizeof h->cfg);
-    h->kind = 2;
+    h->kind = HandleKind::HyperDecoder;
     h->device = device;
     for (int i = 0; i <= cfg->n_layers; ++i) {
         if (cfg->dims[i] < 1) return fail(nullptr, CDC_ERR_INVALID, "bad cdc_hyperdec_config");
@@ -472,7 +489,7 @@ int cdc_bpp(cdc_handle *h, const float *q_hyper_latent, const float *q_latent, c
             float *bpp, int B, int hh, int wh, int H_img, int W_img, int mem, void *stream) {
     int rc = check_ready(h);
     if (rc) return rc;
-    if (h->kind != 2) return fail(h, CDC_ERR_STATE, "handle is not a hyper decoder");
+    if ((rc = require_kind(h, HandleKind::HyperDecoder))) return rc;
     if (!h->d_prior) return fail(h, CDC_ERR_STATE, "the prior.* tensors were not loaded");
     if (!q_hyper_latent || !q_latent || !mean || !scale || !bpp || B < 1 || hh < 1 || wh < 1 || H_img < 1 || W_img < 1)
         return fail(h, CDC_ERR_INVALID, "null/invalid argument");
@@ -480,14 +497,13 @@ int cdc_bpp(cdc_handle *h, const float *q_hyper_latent, const float *q_latent, c
     const long long nh = (long long)Ch * hh * wh, up = 1LL << ((int)h->hyper_dims.size() - 2),
                     nl = (long long)Cl * up * up * hh * wh;   // hyper_dec upsamples by 2 per layer but the last
     hipStream_t st = pick_stream(h, stream, mem);
-    std::vector<void *> tmp;
+    DevPool tmp;                                      // host pointers: device copies of the operands and of the result
     auto dev = [&](const float *p, long long n) -> const float * {
         if (mem == CDC_MEM_DEVICE) return p;
-        void *d = nullptr;
-        if (hipMalloc(&d, sizeof(float) * n) != hipSuccess) return nullptr;
-        tmp.push_back(d);
+        float *d = nullptr;
+        if (tmp.get(&d, (size_t)n) != hipSuccess) return nullptr;
         (void)hipMemcpyAsync(d, p, sizeof(float) * n, hipMemcpyHostToDevice, st);
-        return (const float *)d;
+        return d;
     };
     const float *dqh = dev(q_hyper_latent, B * nh), *dql = dev(q_latent, B * nl), *dm = dev(mean, B * nl),
                 *ds = dev(scale, B * nl);
@@ -496,7 +512,7 @@ int cdc_bpp(cdc_handle *h, const float *q_hyper_latent, const float *q_latent, c
     if (!dqh || !dql || !dm || !ds) e = hipErrorOutOfMemory;
     if (e == hipSuccess) {
         if (mem == CDC_MEM_DEVICE) dout = bpp;
-        else { e = hipMalloc(&dout, sizeof(float) * B); if (e == hipSuccess) tmp.push_back(dout); }
+        else e = tmp.get(&dout, (size_t)B);
     }
     if (e == hipSuccess)
         e = bpp_launch(dqh, nh, hh * wh, h->d_prior, dql, dm, ds, nl, 1.0f / ((float)H_img * (float)W_img), dout, B, st);
@@ -504,44 +520,31 @@ int cdc_bpp(cdc_handle *h, const float *q_hyper_latent, const float *q_latent, c
         e = hipMemcpyAsync(bpp, dout, sizeof(float) * B, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
     }
-    if (mem != CDC_MEM_DEVICE) { (void)hipStreamSynchronize(st); for (void *d : tmp) (void)hipFree(d); }
+    if (mem != CDC_MEM_DEVICE) (void)hipStreamSynchronize(st);   // nothing queued may still use what tmp frees
     if (e != hipSuccess) return fail(h, CDC_ERR_HIP, "cdc_bpp: %s", hipGetErrorString(e));
     return CDC_OK;
 }
 
 int cdc_hyperdec_decode(cdc_handle *h, const float *q_hyper_latent, float *mean, float *scale, int B, int hh,
                         int wh, float scale_min, int mem, void *stream) {
-    int rc = check_ready(h);
-    if (rc) return rc;
-    if (h->kind != 2) return fail(h, CDC_ERR_STATE, "handle is not a hyper decoder");
-    if (!q_hyper_latent || !mean || !scale || B < 1 || hh < 1 || wh < 1)
-        return fail(h, CDC_ERR_INVALID, "null/invalid argument");
-    if ((rc = build_hyperdec_program(h, B, hh, wh))) return rc;
-    hipStream_t st = pick_stream(h, stream, mem);
-    if ((rc = stage_rate(h, nullptr, B, st))) return rc;
-    if ((rc = copy_in(h, h->in_x, q_hyper_latent, (size_t)B * h->hyper_dims[0] * hh * wh, mem, st))) return rc;
-    const bool guard = guard_enabled(h);
-    if (guard) { if ((rc = ensure_fault_flag(h))) return rc; HIP_TRY(h, hipMemsetAsync(h->d_fault, 0, sizeof(int), st)); }
-    h->prof_now = true;
-    for (const Op &op : h->ops)
-        if ((rc = run_op(h, op, h->pB, st))) return rc;
-    const Act &o = h->dec_outs[0];                  // [B][2C][4hh][4wh]: mean = channels [0, C), scale = [C, 2C)
-    const int C = o.C / 2;
-    const long long half = (long long)C * o.H * o.W;
-    if (guard) {
-        int fault = 0;
-        if ((rc = guard_check(h, {{o.p, o.bs(), 2 * half}}, B, st, &fault))) return rc;
-        if (fault) {
-            if (guard_escalate(h, &rc)) { RetryScope r(h); return cdc_hyperdec_decode(h, q_hyper_latent, mean, scale, B, hh, wh, scale_min, mem, stream); }
-            if (rc) return rc;
+    return with_range_guard(h, [&]() -> int {
+        int rc = check_ready(h);
+        if (rc) return rc;
+        if ((rc = require_kind(h, HandleKind::HyperDecoder))) return rc;
+        if (!q_hyper_latent || !mean || !scale || B < 1 || hh < 1 || wh < 1)
+            return fail(h, CDC_ERR_INVALID, "null/invalid argument");
+        if ((rc = build_hyperdec_program(h, B, hh, wh))) return rc;
+        hipStream_t st = pick_stream(h, stream, mem);
+        if ((rc = run_compressor(h, q_hyper_latent, (size_t)B * h->hyper_dims[0] * hh * wh, B, mem, st))) return rc;
+        const Act &o = h->dec_outs[0];                  // [B][2C][4hh][4wh]: mean = channels [0, C), scale = [C, 2C)
+        const long long half = (long long)(o.C / 2) * o.H * o.W;
+        HIP_TRY(h, clamp_min_launch(o.p + half, o.bs(), half, scale_min, B, st));
+        for (int b = 0; b < B; ++b) {
+            if ((rc = copy_out(h, mean + (size_t)b * half, o.p + (size_t)b * o.bs(), (size_t)half, mem, st))) return rc;
+            if ((rc = copy_out(h, scale + (size_t)b * half, o.p + (size_t)b * o.bs() + half, (size_t)half, mem, st))) return rc;
         }
-    }
-    HIP_TRY(h, clamp_min_launch(o.p + half, o.bs(), half, scale_min, B, st));
-    for (int b = 0; b < B; ++b) {
-        if ((rc = copy_out(h, mean + (size_t)b * half, o.p + (size_t)b * o.bs(), (size_t)half, mem, st))) return rc;
-        if ((rc = copy_out(h, scale + (size_t)b * half, o.p + (size_t)b * o.bs() + half, (size_t)half, mem, st))) return rc;
-    }
-    return CDC_OK;
+        return CDC_OK;
+    });
 }
 
 int cdc_dequantize(cdc_handle *h, const float *x, const float *offset, float *out, long long n, int mem, void *stream) {
@@ -554,15 +557,16 @@ int cdc_dequantize(cdc_handle *h, const float *x, const float *offset, float *ou
         HIP_TRY(h, dequantize_launch(x, offset, out, n, st));
         return CDC_OK;
     }
-    float *dx = nullptr, *dl = nullptr;
-    HIP_TRY(h, hipMalloc(&dx, sizeof(float) * n));
-    if (hipMalloc(&dl, sizeof(float) * n) != hipSuccess) { (void)hipFree(dx); return fail(h, CDC_ERR_NOMEM, "hipMalloc failed"); }
+    DevPool d;
+    float *dx, *dl;
+    HIP_TRY(h, d.get(&dx, (size_t)n));
+    if (d.get(&dl, (size_t)n) != hipSuccess) return fail(h, CDC_ERR_NOMEM, "hipMalloc failed");
     hipError_t e = hipMemcpyAsync(dx, x, sizeof(float) * n, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(dl, offset, sizeof(float) * n, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = dequantize_launch(dx, dl, dx, n, st);
     if (e == hipSuccess) e = hipMemcpyAsync(out, dx, sizeof(float) * n, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(dx); (void)hipFree(dl);
+    const hipError_t es = hipStreamSynchronize(st);   // (after an error too: nothing queued may still use what d frees)
+    if (e == hipSuccess) e = es;
     if (e != hipSuccess) return fail(h, CDC_ERR_HIP, "dequantize: %s", hipGetErrorString(e));
     return CDC_OK;
 }
@@ -576,7 +580,7 @@ int cdc_ctxdec_create(const cdc_ctxdec_config *cfg, int device, cdc_handle **out
     std::unique_ptr<cdc_handle> h(new cdc_handle);
     memset(&h->cfg, 0, sizeof h->cfg);
     h->cfg.dim = cfg->dim;
-    h->kind = 1;
+    h->kind = HandleKind::ContextDecoder;
     h->device = device;
     h->up_index = cfg->up_index;
     for (int i = 0; i < cfg->n_rev_mults; ++i) {
@@ -591,67 +595,45 @@ int cdc_ctxdec_create(const cdc_ctxdec_config *cfg, int device, cdc_handle **out
 
 int cdc_ctxdec_decode(cdc_handle *h, const float *q_latent, float *const *outs, int n_outs, int B,
                       int hl, int wl, int mem, void *stream) {
-    int rc = check_ready(h);
-    if (rc) return rc;
-    if (h->kind != 1) return fail(h, CDC_ERR_STATE, "handle is not a context decoder");
-    const int n = (int)h->rev_dims.size() - 1;
-    if (!q_latent || !outs || n_outs != n || B < 1 || hl < 1 || wl < 1)
-        return fail(h, CDC_ERR_INVALID, "null/invalid argument (the decoder has %d outputs)", n);
-    for (int i = 0; i < n; ++i)
-        if (!outs[i]) return fail(h, CDC_ERR_INVALID, "null output %d", i);
-    if ((rc = build_ctxdec_program(h, B, hl, wl))) return rc;
-    hipStream_t st = pick_stream(h, stream, mem);
-    if ((rc = stage_rate(h, nullptr, B, st))) return rc;
-    if ((rc = copy_in(h, h->in_x, q_latent, (size_t)B * h->rev_dims[0] * hl * wl, mem, st))) return rc;
-    const bool guard = guard_enabled(h);
-    if (guard) { if ((rc = ensure_fault_flag(h))) return rc; HIP_TRY(h, hipMemsetAsync(h->d_fault, 0, sizeof(int), st)); }
-    h->prof_now = true;
-    for (const Op &op : h->ops)
-        if ((rc = run_op(h, op, h->pB, st))) return rc;
-    if (guard) {
-        for (int i = 0; i < n; ++i) {
-            const Act &a = h->dec_outs[i];
-            HIP_TRY(h, cdc::nonfinite_launch(a.p, a.bs(), (long long)a.C * a.H * a.W, B, h->d_fault, st));
+    return with_range_guard(h, [&]() -> int {
+        int rc = check_ready(h);
+        if (rc) return rc;
+        if ((rc = require_kind(h, HandleKind::ContextDecoder))) return rc;
+        const int n = (int)h->rev_dims.size() - 1;
+        if (!q_latent || !outs || n_outs != n || B < 1 || hl < 1 || wl < 1)
+            return fail(h, CDC_ERR_INVALID, "null/invalid argument (the decoder has %d outputs)", n);
+        for (int i = 0; i < n; ++i)
+            if (!outs[i]) return fail(h, CDC_ERR_INVALID, "null output %d", i);
+        if ((rc = build_ctxdec_program(h, B, hl, wl))) return rc;
+        hipStream_t st = pick_stream(h, stream, mem);
+        if ((rc = run_compressor(h, q_latent, (size_t)B * h->rev_dims[0] * hl * wl, B, mem, st))) return rc;
+        for (int i = 0; i < n; ++i) {       // outs[0] = finest = the last level's output (output[::-1])
+            const Act &a = h->dec_outs[n - 1 - i];
+            if ((rc = copy_out(h, outs[i], a.p, (size_t)B * a.C * a.H * a.W, mem, st))) return rc;
         }
-        int fault = 0;
-        if ((rc = guard_check(h, {}, B, st, &fault))) return rc;
-        if (fault) {
-            if (guard_escalate(h, &rc)) { RetryScope r(h); return cdc_ctxdec_decode(h, q_latent, outs, n_outs, B, hl, wl, mem, stream); }
-            if (rc) return rc;
-        }
-    }
-    for (int i = 0; i < n; ++i) {       // outs[0] = finest = the last level's output (output[::-1])
-        const Act &a = h->dec_outs[n - 1 - i];
-        if ((rc = copy_out(h, outs[i], a.p, (size_t)B * a.C * a.H * a.W, mem, st))) return rc;
-    }
-    return CDC_OK;
+        return CDC_OK;
+    });
 }
 
 int cdc_unet_forward(cdc_handle *h, const float *x, const float *time, const float *const *ctx,
                      int n_ctx, float *out, int B, int H, int W, int mem, void *stream) {
-    int rc = check_ready(h);
-    if (rc) return rc;
-    if (h->kind != 0) return fail(h, CDC_ERR_STATE, "handle is not a U-Net");
-    if (!x || !time || !out || B < 1) return fail(h, CDC_ERR_INVALID, "null/invalid argument");
-    if ((rc = build_program(h, B, H, W))) return rc;
-    hipStream_t st = pick_stream(h, stream, mem);
-    if ((rc = copy_in(h, h->in_x, x, (size_t)B * h->cfg.channels * H * W, mem, st))) return rc;
-    if ((rc = copy_in(h, h->in_time, time, B, mem, st))) return rc;
-    if ((rc = stage_ctx(h, ctx, n_ctx, B, mem, st))) return rc;
-    const bool guard = guard_enabled(h);
-    if (guard) { if ((rc = ensure_fault_flag(h))) return rc; HIP_TRY(h, hipMemsetAsync(h->d_fault, 0, sizeof(int), st)); }
-    h->prof_now = true;
-    if ((rc = run_pre(h, st))) return rc;
-    if ((rc = run_unet(h, st, -1))) return rc;
-    if (guard) {
-        int fault = 0;
-        if ((rc = guard_check(h, {{h->out_fx, 0, (long long)B * h->out_dim * H * W}}, 1, st, &fault))) return rc;
-        if (fault) {
-            if (guard_escalate(h, &rc)) { RetryScope r(h); return cdc_unet_forward(h, x, time, ctx, n_ctx, out, B, H, W, mem, stream); }
-            if (rc) return rc;
-        }
-    }
-    return copy_out(h, out, h->out_fx, (size_t)B * h->out_dim * H * W, mem, st);
+    return with_range_guard(h, [&]() -> int {
+        int rc = check_ready(h);
+        if (rc) return rc;
+        if ((rc = require_kind(h, HandleKind::Unet))) return rc;
+        if (!x || !time || !out || B < 1) return fail(h, CDC_ERR_INVALID, "null/invalid argument");
+        if ((rc = build_program(h, B, H, W))) return rc;
+        hipStream_t st = pick_stream(h, stream, mem);
+        if ((rc = copy_in(h, h->in_x, x, (size_t)B * h->cfg.channels * H * W, mem, st))) return rc;
+        if ((rc = copy_in(h, h->in_time, time, B, mem, st))) return rc;
+        if ((rc = stage_ctx(h, ctx, n_ctx, B, mem, st))) return rc;
+        if ((rc = arm_range_guard(h, st, false))) return rc;
+        h->prof_now = true;
+        if ((rc = run_pre(h, st))) return rc;
+        if ((rc = run_unet(h, st, -1))) return rc;
+        if ((rc = range_check(h, {{h->out_fx, 0, (long long)B * h->out_dim * H * W}}, 1, st))) return rc;
+        return copy_out(h, out, h->out_fx, (size_t)B * h->out_dim * H * W, mem, st);
+    });
 }
 
 int cdc_unet_tap(cdc_handle *h, const char *name, float *out, int64_t shape[4]) {
@@ -676,12 +658,12 @@ int cdc_unet_tap(cdc_handle *h, const char *name, float *out, int64_t shape[4]) 
 int cdc_set_schedule(cdc_handle *h, int steps, const float *time_in, const float *sqrt_recip,
                      const float *sqrt_recipm1, const float *sqrt_ac_prev,
                      const float *one_minus_ac_prev, const float *sigma) {
-    if (h && h->kind != 0) return fail(h, CDC_ERR_STATE, "handle is not a U-Net");
+    int rc0 = require_kind(h, HandleKind::Unet);
+    if (rc0) return rc0;
     if (!h || steps < 1 || !time_in || !sqrt_recip || !sqrt_recipm1 || !sqrt_ac_prev ||
         !one_minus_ac_prev || !sigma)
         return fail(h, CDC_ERR_INVALID, "null/invalid argument");
-    int rc0 = ensure_device(h);
-    if (rc0) return rc0;
+    if ((rc0 = ensure_device(h))) return rc0;
     std::vector<float> tab((size_t)5 * steps);
     const float *srcs[5] = {sqrt_recip, sqrt_recipm1, sqrt_ac_prev, one_minus_ac_prev, sigma};
     for (int k = 0; k < 5; ++k) memcpy(&tab[(size_t)k * steps], srcs[k], sizeof(float) * steps);
@@ -736,11 +718,11 @@ static int ensure_time_rows(cdc_handle *h, int B) {
 }
 
 int cdc_set_schedule_v(cdc_handle *h, int steps, const float *sqrt_ac, const float *sqrt_one_minus_ac) {
-    if (h && h->kind != 0) return fail(h, CDC_ERR_STATE, "handle is not a U-Net");
+    int rc0 = require_kind(h, HandleKind::Unet);
+    if (rc0) return rc0;
     if (!h || !sqrt_ac || !sqrt_one_minus_ac) return fail(h, CDC_ERR_INVALID, "null argument");
     if (!h->steps || steps != h->steps) return fail(h, CDC_ERR_STATE, "cdc_set_schedule_v follows cdc_set_schedule with the same number of steps");
-    int rc0 = ensure_device(h);
-    if (rc0) return rc0;
+    if ((rc0 = ensure_device(h))) return rc0;
     std::vector<float> tab((size_t)2 * steps);
     memcpy(&tab[0], sqrt_ac, sizeof(float) * steps);
     memcpy(&tab[steps], sqrt_one_minus_ac, sizeof(float) * steps);
@@ -784,136 +766,123 @@ static int ddim_on_device(cdc_handle *h, const float *x_in, int i, const float *
 int cdc_ddim_step(cdc_handle *h, const float *x_in, int i, const float *const *ctx, int n_ctx,
                   const float *noise, float eta, float *x_out, int B, int H, int W, int pred_mode,
                   int clip, int mem, void *stream) {
-    if (h && h->kind != 0) return fail(h, CDC_ERR_STATE, "handle is not a U-Net");
-    int rc = check_ready(h);
-    if (rc) return rc;
-    if (!h->steps) return fail(h, CDC_ERR_STATE, "cdc_set_schedule has not been called");
-    if (i < 0 || i >= h->steps) return fail(h, CDC_ERR_INVALID, "step index %d out of [0,%d)", i, h->steps);
-    if (h->out_dim != h->cfg.channels)
-        return fail(h, CDC_ERR_UNSUPPORTED, "sampler needs out_dim == channels");
-    if (eta != 0.f && !noise) return fail(h, CDC_ERR_INVALID, "eta != 0 needs the noise draw");
-    if (pred_mode < 0 || pred_mode > 3 || clip < 0 || clip > 2) return fail(h, CDC_ERR_INVALID, "pred_mode %d / clip %d out of range", pred_mode, clip);
-    if (pred_mode == CDC_PRED_V && (!h->d_tab_v || h->tab_v_gen != h->sched_gen))
-        return fail(h, CDC_ERR_STATE, "pred_mode \"v\" needs cdc_set_schedule_v after cdc_set_schedule");
-    if ((rc = build_program(h, B, H, W))) return rc;
-    if ((rc = ensure_time_rows(h, B))) return rc;
-    hipStream_t st = pick_stream(h, stream, mem);
-    const size_t n = (size_t)B * h->cfg.channels * H * W;
-    if ((rc = copy_in(h, h->in_x, x_in, n, mem, st))) return rc;
-    // the flag is cleared BEFORE the hoisted context convolutions run: they report range faults into it too (as in cdc_decode)
-    if ((rc = ensure_fault_flag(h))) return rc;              // (the sampler kernel writes the flag)
-    const bool guard = guard_enabled(h);
-    HIP_TRY(h, hipMemsetAsync(h->d_fault, 0, sizeof(int), st));
-    if (ctx) {
-        if ((rc = stage_ctx(h, ctx, n_ctx, B, mem, st))) return rc;
-        h->prof_now = true;
-        if ((rc = run_pre(h, st))) return rc;
-    }
-    if (eta != 0.f && (rc = copy_in(h, h->noise_buf, noise, n, mem, st))) return rc;
-    if ((rc = ddim_on_device(h, h->in_x, i, h->noise_buf, eta, h->xa, B, H, W, pred_mode, clip, st)))
-        return rc;
-    if (guard) {
-        int fault = 0;
-        if ((rc = guard_check(h, {{h->xa, 0, (long long)n}}, 1, st, &fault))) return rc;
-        if (fault) {
-            const bool esc = guard_escalate(h, &rc);
-            if (esc && !ctx)            // the staged context went with the old launch program: the caller has to hand it over again
-                return fail(h, CDC_ERR_STATE, "fp16 range overflow in step %d; the handle is now in CDC_ARITH_BF16X3 -- repeat the step WITH the context", i);
-            if (esc) { RetryScope r(h); return cdc_ddim_step(h, x_in, i, ctx, n_ctx, noise, eta, x_out, B, H, W, pred_mode, clip, mem, stream); }
-            if (rc) return rc;
+    return with_range_guard(h, [&]() -> int {
+        int rc = require_kind(h, HandleKind::Unet);
+        if (rc) return rc;
+        if ((rc = check_ready(h))) return rc;
+        if (!h->steps) return fail(h, CDC_ERR_STATE, "cdc_set_schedule has not been called");
+        if (i < 0 || i >= h->steps) return fail(h, CDC_ERR_INVALID, "step index %d out of [0,%d)", i, h->steps);
+        if (h->out_dim != h->cfg.channels)
+            return fail(h, CDC_ERR_UNSUPPORTED, "sampler needs out_dim == channels");
+        if (eta != 0.f && !noise) return fail(h, CDC_ERR_INVALID, "eta != 0 needs the noise draw");
+        if (pred_mode < 0 || pred_mode > 3 || clip < 0 || clip > 2) return fail(h, CDC_ERR_INVALID, "pred_mode %d / clip %d out of range", pred_mode, clip);
+        if (pred_mode == CDC_PRED_V && (!h->d_tab_v || h->tab_v_gen != h->sched_gen))
+            return fail(h, CDC_ERR_STATE, "pred_mode \"v\" needs cdc_set_schedule_v after cdc_set_schedule");
+        if ((rc = build_program(h, B, H, W))) return rc;
+        if ((rc = ensure_time_rows(h, B))) return rc;
+        hipStream_t st = pick_stream(h, stream, mem);
+        const size_t n = (size_t)B * h->cfg.channels * H * W;
+        if ((rc = copy_in(h, h->in_x, x_in, n, mem, st))) return rc;
+        // the flag is cleared BEFORE the hoisted context convolutions run: they report range faults into it too (as in cdc_decode)
+        if ((rc = arm_range_guard(h, st, true))) return rc;
+        if (ctx) {
+            if ((rc = stage_ctx(h, ctx, n_ctx, B, mem, st))) return rc;
+            h->prof_now = true;
+            if ((rc = run_pre(h, st))) return rc;
         }
-    }
-    return copy_out(h, x_out, h->xa, n, mem, st);
+        if (eta != 0.f && (rc = copy_in(h, h->noise_buf, noise, n, mem, st))) return rc;
+        if ((rc = ddim_on_device(h, h->in_x, i, h->noise_buf, eta, h->xa, B, H, W, pred_mode, clip, st)))
+            return rc;
+        rc = range_check(h, {{h->xa, 0, (long long)n}}, 1, st);
+        if (rc == kRangeRetry && !ctx)      // the staged context went with the old launch program: the caller has to hand it over again
+            return fail(h, CDC_ERR_STATE, "fp16 range overflow in step %d; the handle is now in CDC_ARITH_BF16X3 -- repeat the step WITH the context", i);
+        if (rc) return rc;
+        return copy_out(h, x_out, h->xa, n, mem, st);
+    });
 }
 
 int cdc_decode(cdc_handle *h, const float *init, const float *const *ctx, int n_ctx, float *out, int B,
                int H, int W, int pred_mode, int clip, int mem, void *stream) {
-    if (h && h->kind != 0) return fail(h, CDC_ERR_STATE, "handle is not a U-Net");
-    int rc = check_ready(h);
-    if (rc) return rc;
-    if (!h->steps) return fail(h, CDC_ERR_STATE, "cdc_set_schedule has not been called");
-    if (h->out_dim != h->cfg.channels)
-        return fail(h, CDC_ERR_UNSUPPORTED, "sampler needs out_dim == channels");
-    if (!out || !ctx) return fail(h, CDC_ERR_INVALID, "null argument");
-    if (pred_mode < 0 || pred_mode > 3 || clip < 0 || clip > 2)
-        return fail(h, CDC_ERR_INVALID, "pred_mode %d / clip %d out of range", pred_mode, clip);
-    if (pred_mode == CDC_PRED_V && (!h->d_tab_v || h->tab_v_gen != h->sched_gen))
-        return fail(h, CDC_ERR_STATE, "pred_mode \"v\" needs cdc_set_schedule_v after cdc_set_schedule");
-    if ((rc = build_program(h, B, H, W))) return rc;
-    if ((rc = ensure_time_rows(h, B))) return rc;
-    hipStream_t st = pick_stream(h, stream, mem);
-    const size_t n = (size_t)B * h->cfg.channels * H * W;
-    if ((rc = ensure_fault_flag(h))) return rc;
-    HIP_TRY(h, hipMemsetAsync(h->d_fault, 0, sizeof(int), st));
-    if (init) { if ((rc = copy_in(h, h->in_x, init, n, mem, st))) return rc; }
-    else HIP_TRY(h, hipMemsetAsync(h->in_x, 0, n * sizeof(float), st));
-    if ((rc = stage_ctx(h, ctx, n_ctx, B, mem, st))) return rc;
-    h->prof_now = false;
-    if ((rc = run_pre(h, st))) return rc;       // hoisted context halves: once per decode
-    // for i in reversed(range(steps)): img = ddim(img, i)      (x: :188-200 ; eps: :174-190)
-    // Optional (CDC_GRAPH=1): replay one captured DDIM iteration as a hipGraph; the step index lives in device memory
-    // and is decremented by the graph's last node.  Measured (tools/gpu_graph_latency.py): bit-identical, and NO
-    // faster -- 5.8 ms / iteration at batch 1 either way: the ~170 kernels of an iteration are bound by their own
-    // serial latency (tiny grids), not by host launches -- so the eager loop stays the default.
-    const char *genv = getenv("CDC_GRAPH");           // 0 / 1 overrides the batch-size rule
-    const bool use_graph = !h->prof && h->steps > 2 && genv && atoi(genv) != 0;
-    int i = h->steps - 1;
-    if (use_graph) {
-        // the legacy default stream cannot be captured: iterate on the library's own stream, fenced by events
-        hipStream_t cs = st;
-        if (!h->gev_in) { HIP_TRY(h, hipEventCreateWithFlags(&h->gev_in, hipEventDisableTiming));
-                          HIP_TRY(h, hipEventCreateWithFlags(&h->gev_out, hipEventDisableTiming)); }
-        if (st != h->own_stream) {
-            HIP_TRY(h, hipEventRecord(h->gev_in, cs));
-            st = h->own_stream;
-            HIP_TRY(h, hipStreamWaitEvent(st, h->gev_in, 0));
+    return with_range_guard(h, [&]() -> int {
+        int rc = require_kind(h, HandleKind::Unet);
+        if (rc) return rc;
+        if ((rc = check_ready(h))) return rc;
+        if (!h->steps) return fail(h, CDC_ERR_STATE, "cdc_set_schedule has not been called");
+        if (h->out_dim != h->cfg.channels)
+            return fail(h, CDC_ERR_UNSUPPORTED, "sampler needs out_dim == channels");
+        if (!out || !ctx) return fail(h, CDC_ERR_INVALID, "null argument");
+        if (pred_mode < 0 || pred_mode > 3 || clip < 0 || clip > 2)
+            return fail(h, CDC_ERR_INVALID, "pred_mode %d / clip %d out of range", pred_mode, clip);
+        if (pred_mode == CDC_PRED_V && (!h->d_tab_v || h->tab_v_gen != h->sched_gen))
+            return fail(h, CDC_ERR_STATE, "pred_mode \"v\" needs cdc_set_schedule_v after cdc_set_schedule");
+        if ((rc = build_program(h, B, H, W))) return rc;
+        if ((rc = ensure_time_rows(h, B))) return rc;
+        hipStream_t st = pick_stream(h, stream, mem);
+        const size_t n = (size_t)B * h->cfg.channels * H * W;
+        if ((rc = arm_range_guard(h, st, true))) return rc;
+        if (init) { if ((rc = copy_in(h, h->in_x, init, n, mem, st))) return rc; }
+        else HIP_TRY(h, hipMemsetAsync(h->in_x, 0, n * sizeof(float), st));
+        if ((rc = stage_ctx(h, ctx, n_ctx, B, mem, st))) return rc;
+        h->prof_now = false;
+        if ((rc = run_pre(h, st))) return rc;       // hoisted context halves: once per decode
+        // for i in reversed(range(steps)): img = ddim(img, i)      (x: :188-200 ; eps: :174-190)
+        // Optional (CDC_GRAPH=1): replay one captured DDIM iteration as a hipGraph; the step index lives in device memory
+        // and is decremented by the graph's last node.  Measured (tools/gpu_graph_latency.py): bit-identical, and NO
+        // faster -- 5.8 ms / iteration at batch 1 either way: the ~170 kernels of an iteration are bound by their own
+        // serial latency (tiny grids), not by host launches -- so the eager loop stays the default.
+        const char *genv = getenv("CDC_GRAPH");           // 0 / 1 overrides the batch-size rule
+        const bool use_graph = !h->prof && h->steps > 2 && genv && atoi(genv) != 0;
+        int i = h->steps - 1;
+        if (use_graph) {
+            // the legacy default stream cannot be captured: iterate on the library's own stream, fenced by events
+            hipStream_t cs = st;
+            if (!h->gev_in) { HIP_TRY(h, hipEventCreateWithFlags(&h->gev_in, hipEventDisableTiming));
+                              HIP_TRY(h, hipEventCreateWithFlags(&h->gev_out, hipEventDisableTiming)); }
+            if (st != h->own_stream) {
+                HIP_TRY(h, hipEventRecord(h->gev_in, cs));
+                st = h->own_stream;
+                HIP_TRY(h, hipStreamWaitEvent(st, h->gev_in, 0));
+            }
+            if (!h->d_step) { void *p = nullptr; HIP_TRY(h, hipMalloc(&p, sizeof(int))); h->d_step = (int *)p; h->weight_allocs.push_back(p); }
+            // first iteration eagerly (kernel attributes, code pages), then capture the second and replay it
+            if ((rc = ddim_on_device(h, h->in_x, i, nullptr, 0.f, h->in_x, B, H, W, pred_mode, clip, st))) return rc;
+            --i;
+            const int key[4] = {h->steps, pred_mode, clip, h->sched_gen};
+            if (!h->graph_exec || memcmp(key, h->graph_key, sizeof key)) {
+                if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
+                hipGraph_t g = nullptr;
+                HIP_TRY(h, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+                rc = ddim_on_device(h, h->in_x, -2, nullptr, 0.f, h->in_x, B, H, W, pred_mode, clip, st);
+                hipError_t e = rc ? hipSuccess : step_dec_launch(h->d_step, st);
+                hipError_t e2 = hipStreamEndCapture(st, &g);
+                if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
+                if (e != hipSuccess || e2 != hipSuccess || !g)
+                    return fail(h, CDC_ERR_HIP, "graph capture failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+                e = hipGraphInstantiate(&h->graph_exec, g, nullptr, nullptr, 0);
+                (void)hipGraphDestroy(g);
+                if (e != hipSuccess) { h->graph_exec = nullptr; return fail(h, CDC_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e)); }
+                memcpy(h->graph_key, key, sizeof key);
+            }
+            HIP_TRY(h, hipMemcpyAsync(h->d_step, &i, sizeof(int), hipMemcpyHostToDevice, st));
+            HIP_TRY(h, hipStreamSynchronize(st));      // `i` is a stack variable
+            for (; i >= 0; --i) HIP_TRY(h, hipGraphLaunch(h->graph_exec, st));
+            if (st != cs) {
+                HIP_TRY(h, hipEventRecord(h->gev_out, st));
+                HIP_TRY(h, hipStreamWaitEvent(cs, h->gev_out, 0));
+                st = cs;
+            }
         }
-        if (!h->d_step) { void *p = nullptr; HIP_TRY(h, hipMalloc(&p, sizeof(int))); h->d_step = (int *)p; h->weight_allocs.push_back(p); }
-        // first iteration eagerly (kernel attributes, code pages), then capture the second and replay it
-        if ((rc = ddim_on_device(h, h->in_x, i, nullptr, 0.f, h->in_x, B, H, W, pred_mode, clip, st))) return rc;
-        --i;
-        const int key[4] = {h->steps, pred_mode, clip, h->sched_gen};
-        if (!h->graph_exec || memcmp(key, h->graph_key, sizeof key)) {
-            if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
-            hipGraph_t g = nullptr;
-            HIP_TRY(h, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            rc = ddim_on_device(h, h->in_x, -2, nullptr, 0.f, h->in_x, B, H, W, pred_mode, clip, st);
-            hipError_t e = rc ? hipSuccess : step_dec_launch(h->d_step, st);
-            hipError_t e2 = hipStreamEndCapture(st, &g);
-            if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-            if (e != hipSuccess || e2 != hipSuccess || !g)
-                return fail(h, CDC_ERR_HIP, "graph capture failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-            e = hipGraphInstantiate(&h->graph_exec, g, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(g);
-            if (e != hipSuccess) { h->graph_exec = nullptr; return fail(h, CDC_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e)); }
-            memcpy(h->graph_key, key, sizeof key);
+        for (; i >= 0; --i) {
+            h->prof_now = (i % h->prof_every) == 0;
+            if ((rc = ddim_on_device(h, h->in_x, i, nullptr, 0.f, h->in_x, B, H, W, pred_mode, clip, st)))
+                return rc;
         }
-        HIP_TRY(h, hipMemcpyAsync(h->d_step, &i, sizeof(int), hipMemcpyHostToDevice, st));
-        HIP_TRY(h, hipStreamSynchronize(st));      // `i` is a stack variable
-        for (; i >= 0; --i) HIP_TRY(h, hipGraphLaunch(h->graph_exec, st));
-        if (st != cs) {
-            HIP_TRY(h, hipEventRecord(h->gev_out, st));
-            HIP_TRY(h, hipStreamWaitEvent(cs, h->gev_out, 0));
-            st = cs;
-        }
-    }
-    for (; i >= 0; --i) {
-        h->prof_now = (i % h->prof_every) == 0;
-        if ((rc = ddim_on_device(h, h->in_x, i, nullptr, 0.f, h->in_x, B, H, W, pred_mode, clip, st)))
-            return rc;
-    }
-    h->prof_now = true;
-    // Range guard (see guard_enabled above): a non-finite U-Net output is flagged by the sampler kernel of the iteration it
-    // occurs in; the final image is checked as well.  One 4-byte read-back per decode.
-    if (guard_enabled(h)) {
-        int fault = 0;
-        if ((rc = guard_check(h, {{h->in_x, 0, (long long)n}}, 1, st, &fault))) return rc;
-        if (fault) {
-            if (guard_escalate(h, &rc)) { RetryScope r(h); return cdc_decode(h, init, ctx, n_ctx, out, B, H, W, pred_mode, clip, mem, stream); }
-            if (rc) return rc;
-        }
-    }
-    return copy_out(h, out, h->in_x, n, mem, st);
+        h->prof_now = true;
+        // Range guard: a non-finite U-Net output is flagged by the sampler kernel of the iteration it occurs in; the final image
+        // is checked as well.  One 4-byte read-back per decode.
+        if ((rc = range_check(h, {{h->in_x, 0, (long long)n}}, 1, st))) return rc;
+        return copy_out(h, out, h->in_x, n, mem, st);
+    });
 }
 
 int cdc_prof_enable(cdc_handle *h, int on) {

@@ -11,7 +11,8 @@ constexpr int kStreamHeaderVbr = 38;
 inline int stream_header(const unsigned char *s) { return s[3] == kStreamVersionVbr ? kStreamHeaderVbr : kStreamHeader; }
 
 int ensure_entropy(cdc_handle *h, const float *medians) {
-    if (h->kind != 2) return fail(h, CDC_ERR_STATE, "handle is not a hyper decoder");
+    int rc = require_kind(h, HandleKind::HyperDecoder);
+    if (rc) return rc;
     if (h->h_prior.empty()) return fail(h, CDC_ERR_STATE, "the prior.* tensors were not loaded");
     const int C = h->hyper_dims[0];
     if (!h->ent) h->ent.reset(new cdc::EntropyModel);
@@ -21,7 +22,7 @@ int ensure_entropy(cdc_handle *h, const float *medians) {
         h->ent->dev_stale = true;
     }
     if (!h->ent->d_edges) {
-        int rc = upload(h, h->ent->edges, cdc::kEntropyBins, &h->ent->d_edges, &h->weight_allocs);
+        rc = upload(h, h->ent->edges, cdc::kEntropyBins, &h->ent->d_edges, &h->weight_allocs);
         if (rc) return rc;
     }
     if (h->ent->dev_stale) {
@@ -37,18 +38,16 @@ constexpr int kMaxHyperPositions = 1 << 22;       // hh * wh of a 131072 x 13107
 inline long long section_cap(long long n) { return (2 * n + 256 + 15) & ~15ll; }   // <= 2 renormalisation bytes per symbol + 64 states
 
 // hyper_dec over the batch through the batch-1 launch plan: h->in_x (filled by the caller) -> dec_outs[0] = (mean | scale).
-// *fault: results left the F16X2 range (checked only when `guard`).
-int hyperdec_batch(cdc_handle *h, int B, hipStream_t st, bool guard, int *fault) {
+// `check`: the results are range-checked (kRangeRetry when they left the F16X2 range).
+int hyperdec_batch(cdc_handle *h, int B, hipStream_t st, bool check) {
     int rc;
-    if (guard) { if ((rc = ensure_fault_flag(h))) return rc; HIP_TRY(h, hipMemsetAsync(h->d_fault, 0, sizeof(int), st)); }
+    if (check && (rc = arm_range_guard(h, st, false))) return rc;
     h->prof_now = false;
-    for (const Op &op : h->ops)
-        if ((rc = run_op(h, op, B, st))) return rc;
+    if ((rc = run_ops(h, B, st))) return rc;
     const Act &o = h->dec_outs[0];
     const long long half = (long long)(o.C / 2) * o.H * o.W;
-    *fault = 0;
-    if (guard && (rc = guard_check(h, {{o.p, o.bs(), 2 * half}}, B, st, fault))) return rc;
-    if (!*fault) HIP_TRY(h, clamp_min_launch(o.p + half, o.bs(), half, 0.1f, B, st));   // scale.clamp(min=0.1), compress_modules.py:59
+    if (check && (rc = range_check(h, {{o.p, o.bs(), 2 * half}}, B, st))) return rc;
+    HIP_TRY(h, clamp_min_launch(o.p + half, o.bs(), half, 0.1f, B, st));   // scale.clamp(min=0.1), compress_modules.py:59
     return CDC_OK;
 }
 
@@ -98,14 +97,9 @@ int entropy_encode_impl(cdc_handle *h, const float *latent, const float *hyper_l
     HIP_TRY(h, hipStreamSynchronize(st));
     if (hbad) return fail(h, CDC_ERR_INVALID, "non-finite or out-of-range hyper-latent (nothing to code)");
     if ((rc = stage_rate(h, nullptr, B, st))) return rc;      // variable bitrate: the handle's rates, recorded in the streams below
-    int fault = 0;
-    if ((rc = hyperdec_batch(h, B, st, guard_enabled(h) && !h->in_retry, &fault))) return rc;
-    if (fault) {
-        // the encoder may leave CDC_ARITH_F16X2 when hyper_dec overflows its range: the stream header records the arithmetic
-        // that was finally used and the decoder runs what the header says
-        if (guard_escalate(h, &rc)) { RetryScope r(h); return entropy_encode_impl(h, latent, hyper_latent, medians, B, hh, wh, out, cap, offsets, mem, stream); }
-        if (rc) return rc;
-    }
+    // the encoder may leave CDC_ARITH_F16X2 when hyper_dec overflows its range (checked outside the repetition only): the stream
+    // header records the arithmetic that was finally used and the decoder runs what the header says
+    if ((rc = hyperdec_batch(h, B, st, !h->in_retry))) return rc;
     HIP_TRY(h, cdc::latent_symbols_launch(d_lat, nl, o.p, o.p + nl, o.bs(), h->ent->d_edges, nl, B, syml, bin, bad, st));
     const cdc::EntropyDev T = h->ent->dev();
     HIP_TRY(h, cdc::rans_encode_launch(T, symh, nh, nullptr, 0, per, 0, (int)nh, 0u, B, sf, ew, sec_h, cap_h, esc_h, nh, meta, st));
@@ -120,8 +114,8 @@ int entropy_encode_impl(cdc_handle *h, const float *latent, const float *hyper_l
     HIP_TRY(h, hipMemcpyAsync(hoff.data(), d_off, sizeof(long long) * ((size_t)B + 1), hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipStreamSynchronize(st));
     if (hbad) {
-        // (in the BF16X3 repetition of a range fault: the range was not the cause -- RetryScope puts the handle back into F16X2
-        // and takes the fault off the count, as include/cdc_hip.h promises for every entry point)
+        // (in the BF16X3 repetition of a range fault: the range was not the cause -- with_range_guard puts the handle back into
+        // F16X2 and takes the fault off the count, as include/cdc_hip.h promises for every entry point)
         if (h->in_retry) h->retry_futile = true;
         return fail(h, CDC_ERR_INVALID, "non-finite or out-of-range latent, mean or scale (nothing to code)");
     }
@@ -219,8 +213,7 @@ int entropy_decode_impl(cdc_handle *h, const unsigned char *in, const size_t *of
             for (int b = b0; b < b1; ++b) rates[b - b0] = hd[b].rate;
             if ((rc = stage_rate(h, rates.data(), nb, st))) return rc;
         }
-        int fault = 0;
-        if ((rc = hyperdec_batch(h, nb, st, false, &fault))) return rc;
+        if ((rc = hyperdec_batch(h, nb, st, false))) return rc;
         HIP_TRY(h, cdc::latent_symbols_launch(nullptr, 0, o.p, o.p + nl, o.bs(), h->ent->d_edges, nl, nb, nullptr, bin, nullptr, st));
         HIP_TRY(h, cdc::rans_decode_launch(T, d_in, d_off + nb, d_len + nb, d_esc + nb, bin, nl, 0, Ch, (int)nl, 1u, nb, syml, nl, meta + nb, st));
         std::vector<cdc::RansMeta> hm(2 * (size_t)nb);
@@ -254,11 +247,14 @@ extern "C" {
 
 int cdc_entropy_encode(cdc_handle *h, const float *latent, const float *hyper_latent, const float *medians, int B,
                        int hh, int wh, unsigned char *out, size_t cap, size_t *offsets, int mem, void *stream) {
-    return no_throw(h, [&] { return entropy_encode_impl(h, latent, hyper_latent, medians, B, hh, wh, out, cap, offsets, mem, stream); });
+    return no_throw(h, [&] {
+        return with_range_guard(h, [&] { return entropy_encode_impl(h, latent, hyper_latent, medians, B, hh, wh, out, cap, offsets, mem, stream); });
+    });
 }
 
 int cdc_entropy_set_limit(cdc_handle *h, int max_hyper_positions) {
-    if (!h || h->kind != 2) return h ? fail(h, CDC_ERR_STATE, "handle is not a hyper decoder") : CDC_ERR_INVALID;
+    if (!h) return CDC_ERR_INVALID;
+    if (int rc = require_kind(h, HandleKind::HyperDecoder)) return rc;
     if (max_hyper_positions < 1) return fail(h, CDC_ERR_INVALID, "limit %d", max_hyper_positions);
     h->ent_max_positions = std::min(max_hyper_positions, kMaxHyperPositions);
     return CDC_OK;

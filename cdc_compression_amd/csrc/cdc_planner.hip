@@ -63,7 +63,7 @@ struct Builder {
     }
 
     // Range-guard flag of the handle (conv_args.h: ConvArgs::fault): every convolution / LayerNorm launch of a program reports
-    // non-finite accumulators there; the entry points clear it before a call and read it back after (guard_check).
+    // non-finite accumulators there; the entry points clear it before a call and read it back after (range_check).
     int *fault_flag() {
         if (!h->d_fault && !rc) {
             void *p = nullptr;
@@ -1345,13 +1345,6 @@ int build_ctxdec_program(cdc_handle *h, int B, int hl, int wl) {
 // ---- single operators ----------------------------------------------------------------------------
 namespace {
 
-constexpr int kOpRetry = -10000;  // internal: repeat the operator in CDC_ARITH_BF16X3 (never returned to the caller)
-template <class F> int op_with_guard(cdc_handle *h, F &&f) {
-    int rc = f();
-    if (rc == kOpRetry) { RetryScope r(h); rc = f(); if (rc == kOpRetry) rc = CDC_ERR_STATE; }
-    return rc;
-}
-
 struct OpScope {                 // temporary device pool + op list for the cdc_op_* entry points
     cdc_handle *h;
     std::vector<void *> pool;
@@ -1370,24 +1363,13 @@ struct OpScope {                 // temporary device pool + op list for the cdc_
     }
     int up(const float *src, size_t n, float **dst) { return upload(h, src, n, dst, &pool); }
     // Range guard of the single-operator entry points: the launches report non-finite accumulators (ConvArgs::fault) and the
-    // result is checked; a faulting F16X2 call returns kOpRetry and its entry point repeats it in BF16X3.
+    // result is checked; a faulting F16X2 call returns kRangeRetry and its entry point repeats it in BF16X3.
     int run(int B, float *host_out, const float *dev_out, size_t n) {
         hipStream_t st = h->own_stream;
-        const bool guard = guard_enabled(h);
         int rc;
-        if (guard) { if ((rc = ensure_fault_flag(h))) return rc; HIP_TRY(h, hipMemsetAsync(h->d_fault, 0, sizeof(int), st)); }
-        for (const Op &op : h->ops) {
-            rc = run_op(h, op, B, st);
-            if (rc) return rc;
-        }
-        if (guard) {
-            int fault = 0;
-            if ((rc = guard_check(h, {{dev_out, 0, (long long)n}}, 1, st, &fault))) return rc;
-            if (fault) {
-                if (guard_escalate(h, &rc)) return kOpRetry;
-                if (rc) return rc;
-            }
-        }
+        if ((rc = arm_range_guard(h, st, false))) return rc;
+        if ((rc = run_ops(h, B, st))) return rc;
+        if ((rc = range_check(h, {{dev_out, 0, (long long)n}}, 1, st))) return rc;
         if (h->op_stress_n > 0) {      // cdc_op_stress: the program again and again, every result against the first, on the device
             void *first = nullptr, *cnt = nullptr;
             HIP_TRY(h, hipMalloc(&first, n * sizeof(float))); pool.push_back(first);
@@ -1395,7 +1377,7 @@ struct OpScope {                 // temporary device pool + op list for the cdc_
             HIP_TRY(h, hipMemsetAsync(cnt, 0, 3 * sizeof(long long), st));
             HIP_TRY(h, hipMemcpyAsync(first, dev_out, n * sizeof(float), hipMemcpyDeviceToDevice, st));
             for (int k = 0; k < h->op_stress_n; ++k) {
-                for (const Op &op : h->ops) { rc = run_op(h, op, B, st); if (rc) return rc; }
+                if ((rc = run_ops(h, B, st))) return rc;
                 HIP_TRY(h, bits_differ_launch(dev_out, (const float *)first, (long long)n, (long long *)cnt, st));
             }
             long long c[3] = {0, 0, 0};
@@ -1570,23 +1552,23 @@ int cdc_op_conv2d(cdc_handle *h, const float *x, const float *w, const float *bi
                   int Cin, int H, int W, int Cout, int KH, int KW, int stride, int pad,
                   const float *ln_g, const float *ln_b, int relu, const float *shift,
                   const float *resid) {
-    return op_with_guard(h, [&] { return op_conv2d_impl(h, x, w, bias, y, B, Cin, H, W, Cout, KH, KW, stride, pad, ln_g, ln_b, relu, shift, resid); });
+    return with_range_guard(h, [&] { return op_conv2d_impl(h, x, w, bias, y, B, Cin, H, W, Cout, KH, KW, stride, pad, ln_g, ln_b, relu, shift, resid); });
 }
 
 int cdc_op_conv_transpose2d(cdc_handle *h, const float *x, const float *w, const float *bias, float *y,
                             int B, int Cin, int H, int W, int Cout) {
-    return op_with_guard(h, [&] { return op_conv_transpose2d_impl(h, x, w, bias, y, B, Cin, H, W, Cout); });
+    return with_range_guard(h, [&] { return op_conv_transpose2d_impl(h, x, w, bias, y, B, Cin, H, W, Cout); });
 }
 
 int cdc_op_chan_layernorm(cdc_handle *h, const float *x, const float *g, const float *b, float *y, int B,
                           int C, int HW) {
-    return op_with_guard(h, [&] { return op_chan_layernorm_impl(h, x, g, b, y, B, C, HW); });
+    return with_range_guard(h, [&] { return op_chan_layernorm_impl(h, x, g, b, y, B, C, HW); });
 }
 
 int cdc_op_linear_attention(cdc_handle *h, const float *x, const float *norm_g, const float *norm_b,
                             const float *w_qkv, const float *w_out, const float *b_out, float *y, int B,
                             int C, int H, int W) {
-    return op_with_guard(h, [&] { return op_linear_attention_impl(h, x, norm_g, norm_b, w_qkv, w_out, b_out, y, B, C, H, W); });
+    return with_range_guard(h, [&] { return op_linear_attention_impl(h, x, norm_g, norm_b, w_qkv, w_out, b_out, y, B, C, H, W); });
 }
 
 int cdc_op_stress(cdc_handle *h, int repeats) {

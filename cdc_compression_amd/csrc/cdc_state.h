@@ -118,23 +118,25 @@ static int default_arith() {      // CDC_ARITH=0 selects the three-plane bf16 ar
     return e ? (atoi(e) ? 1 : 0) : 1;
 }
 
+// ContextDecoder: Compressor.decode; HyperDecoder: hyper_dec (+ the rate estimate and the entropy coder); Encoder: enc + hyper_enc
+enum class HandleKind { Unet, ContextDecoder, HyperDecoder, Encoder };
+
 struct cdc_handle {
     cdc_unet_config cfg;
-    int kind = 0;                 // 0: denoising U-Net, 1: context decoder (Compressor.decode), 2: hyper decoder,
-                                  // 3: encoder (enc + hyper_enc)
-    std::vector<int> enc_dims, henc_dims;     // kind 3
+    HandleKind kind = HandleKind::Unet;
+    std::vector<int> enc_dims, henc_dims;     // Encoder
     int down_index = 1;
-    std::vector<int> hyper_dims;  // kind 2: reversed_hyper_dims
-    std::vector<ConvW> hconvs;    // kind 2: packed layers
-    float *d_prior = nullptr;     // kind 2: FlexiblePrior per channel, 44 floats (softplus / tanh applied), or null
-    std::vector<double> h_prior;  // kind 2: the same in float64 (probability tables of the entropy coder)
-    std::unique_ptr<cdc::EntropyModel> ent;   // kind 2: entropy coder tables (built on first use)
+    std::vector<int> hyper_dims;  // HyperDecoder: reversed_hyper_dims
+    std::vector<ConvW> hconvs;    // HyperDecoder: packed layers
+    float *d_prior = nullptr;     // HyperDecoder: FlexiblePrior per channel, 44 floats (softplus / tanh applied), or null
+    std::vector<double> h_prior;  // HyperDecoder: the same in float64 (probability tables of the entropy coder)
+    std::unique_ptr<cdc::EntropyModel> ent;   // HyperDecoder: entropy coder tables (built on first use)
     uint32_t ent_model_hash = 0;
-    int ent_max_positions = 1 << 22;          // kind 2: largest hh * wh cdc_entropy_decode accepts from a stream header (cdc_entropy_set_limit)
-    std::vector<int> rev_dims;    // kind 1: [dim*m for m in rev_mults] + [out_channels]
+    int ent_max_positions = 1 << 22;          // HyperDecoder: largest hh * wh cdc_entropy_decode accepts from a stream header (cdc_entropy_set_limit)
+    std::vector<int> rev_dims;    // ContextDecoder: [dim*m for m in rev_mults] + [out_channels]
     int up_index = 1;
-    std::vector<Act> dec_outs;    // kind 1: outputs of the program, coarsest first
-    // variable bitrate (cdc_enable_vbr, kinds 1-3): a VBRCondition after every ResnetBlock (dec / enc) and after every hyper layer
+    std::vector<Act> dec_outs;    // ContextDecoder: outputs of the program, coarsest first
+    // variable bitrate (cdc_enable_vbr, the compressor kinds): a VBRCondition after every ResnetBlock (dec / enc) and after every hyper layer
     // but the last (hyper_enc / hyper_dec), in forward order; the rate of each image lives in d_rate (program buffer, pB floats)
     bool vbr = false;
     std::vector<VbrW> vbrs;
@@ -265,6 +267,7 @@ int stage_rate(cdc_handle *h, const float *rates, int B, hipStream_t st);
 hipEvent_t get_event(cdc_handle *h);
 int resolve_pending(cdc_handle *h);
 int run_op(cdc_handle *h, const Op &op, int B, hipStream_t st);
+int run_ops(cdc_handle *h, int B, hipStream_t st);
 int run_pre(cdc_handle *h, hipStream_t st);
 int run_unet(cdc_handle *h, hipStream_t st, int step, bool skip_combine = false);
 int copy_in(cdc_handle *h, float *dst, const float *src, size_t n, int mem, hipStream_t st);
@@ -273,6 +276,7 @@ int stage_ctx(cdc_handle *h, const float *const *ctx, int n_ctx, int B, int mem,
 int ensure_device(cdc_handle *h);
 hipStream_t pick_stream(cdc_handle *h, void *stream, int mem);
 int check_ready(cdc_handle *h);
+int require_kind(cdc_handle *h, HandleKind kind);
 
 // ---- range guard of the two-plane fp16 arithmetic ------------------------------------------------------------------
 // |activation| >= 65504 becomes inf / NaN in CDC_ARITH_F16X2 and propagates to the results of the call.  Every entry point
@@ -280,11 +284,15 @@ int check_ready(cdc_handle *h);
 // a call whose results are not finite is repeated ONCE in the full-range three-plane bf16 arithmetic, and the handle stays
 // in that mode (cdc_get_arith / cdc_get_range_faults tell).  Results that are non-finite there too -- a non-finite input,
 // parameters that overflow fp32 -- are returned as they are, as the reference would (cdc_get_nonfinite_results counts them).
+// An entry point arms the flag before its launches, checks after them and runs inside with_range_guard.
 bool guard_enabled(const cdc_handle *h);
-int ensure_fault_flag(cdc_handle *h);
+// clears the fault flag; `always`: even with the guard off (cdc_decode / cdc_ddim_step: the sampler kernel writes the flag)
+int arm_range_guard(cdc_handle *h, hipStream_t st, bool always);
 struct GuardBuf { const float *p; long long bs, n; };
-int guard_check(cdc_handle *h, std::initializer_list<GuardBuf> bufs, int B, hipStream_t st, int *fault);
-bool guard_escalate(cdc_handle *h, int *rc);
+constexpr int kRangeRetry = -10000;   // internal: the handle is now in BF16X3, repeat the call (never returned to a caller)
+// With the guard on: "not finite" over `bufs` (and whatever a kernel of the call left in the flag).  CDC_OK: no fault, or a
+// fault in the repetition, counted and returned as it is; kRangeRetry: a fault in F16X2; or an error.
+int range_check(cdc_handle *h, const std::vector<GuardBuf> &bufs, int B, hipStream_t st);
 // The repetition of a call in BF16X3.  When that result is non-finite as well (a NaN / inf in the inputs or the parameters), the
 // range was not the cause: the handle goes back to F16X2 and the fault is counted in nonfinite_results only.
 struct RetryScope {
@@ -299,8 +307,16 @@ struct RetryScope {
         }
     }
 };
+// body() once, and once more in BF16X3 when it asks for that (kRangeRetry)
+template <class F> int with_range_guard(cdc_handle *h, F &&body) {
+    int rc = body();
+    if (rc != kRangeRetry) return rc;
+    RetryScope r(h);
+    rc = body();
+    return rc == kRangeRetry ? CDC_ERR_STATE : rc;
+}
 
-// device scratch of one entropy call, released on every exit path
+// device scratch of one call, released on every exit path
 struct DevPool {
     std::vector<void *> v;
     ~DevPool() { for (void *p : v) (void)hipFree(p); }

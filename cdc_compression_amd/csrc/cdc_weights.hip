@@ -91,7 +91,7 @@ void build_manifest(cdc_handle *h) {
     add_param(h, "final_conv.1.bias", {h->out_dim});
 }
 
-// The compressor handles (kinds 1-3), in the registration order of Compressor.enc / .hyper_enc / .hyper_dec / .dec
+// The compressor handles (encoder, hyper decoder, context decoder), in the registration order of Compressor.enc / .hyper_enc / .hyper_dec / .dec
 // (epsilonparam compress_modules.py:125-184).  With h->vbr a VBRCondition(1, C) -- `.scale` / `.shift` Conv2d(1, C, 1) -- sits at index
 // 1 of every enc / dec level and of every hyper layer but the last.
 static void add_vbr_params(cdc_handle *h, const std::string &p, int c) {
@@ -102,7 +102,7 @@ static void add_vbr_params(cdc_handle *h, const std::string &p, int c) {
 }
 
 void build_compressor_manifest(cdc_handle *h) {
-    if (h->kind == 3) {
+    if (h->kind == HandleKind::Encoder) {
         const int n = (int)h->enc_dims.size() - 1, nh = (int)h->henc_dims.size() - 1;
         for (int i = 0; i < n; ++i) {          // Compressor.enc (:131-141)
             const std::string p = "enc." + std::to_string(i);
@@ -119,7 +119,7 @@ void build_compressor_manifest(cdc_handle *h) {
             add_param(h, p + ".0.bias", {h->henc_dims[i + 1]});
             if (h->vbr && i < nh - 1) add_vbr_params(h, p + ".1", h->henc_dims[i + 1]);
         }
-    } else if (h->kind == 2) {
+    } else if (h->kind == HandleKind::HyperDecoder) {
         const int n = (int)h->hyper_dims.size() - 1;
         for (int i = 0; i < n; ++i) {
             const std::string p = "hyper_dec." + std::to_string(i);
@@ -137,7 +137,7 @@ void build_compressor_manifest(cdc_handle *h) {
             add_param(h, "prior.affine." + std::to_string(i) + ".bias", {pc, pd[i + 1]}, true);
             if (i < 3) add_param(h, "prior.a." + std::to_string(i), {pc, pd[i + 1]}, true);
         }
-    } else if (h->kind == 1) {
+    } else if (h->kind == HandleKind::ContextDecoder) {
         const int n = (int)h->rev_dims.size() - 1;
         for (int i = 0; i < n; ++i) {          // Compressor.dec (compress_modules.py:147-156)
             const std::string p = "dec." + std::to_string(i);
@@ -522,7 +522,7 @@ int cdc_finalize_weights(cdc_handle *h) {
     free_pool(&h->weight_allocs);
     h->d_fault = nullptr; h->d_step = nullptr;          // (they lived in that pool)
     h->rbs.clear(); h->attns.clear(); h->downs.clear(); h->ups.clear(); h->vbrs.clear();
-    if (h->kind == 3) {
+    if (h->kind == HandleKind::Encoder) {
         const int n = (int)h->enc_dims.size() - 1;
         int shift_off = 0;
         for (int i = 0; i < n; ++i) {
@@ -548,7 +548,7 @@ int cdc_finalize_weights(cdc_handle *h) {
         h->finalized = true;
         return CDC_OK;
     }
-    if (h->kind == 2) {
+    if (h->kind == HandleKind::HyperDecoder) {
         const int n = (int)h->hyper_dims.size() - 1;
         h->hconvs.clear();
         for (int i = 0; i < n; ++i) {
@@ -596,7 +596,7 @@ int cdc_finalize_weights(cdc_handle *h) {
         h->finalized = true;
         return CDC_OK;
     }
-    if (h->kind == 1) {
+    if (h->kind == HandleKind::ContextDecoder) {
         // Compressor.dec: ResnetBlock(rev[i] -> rev[i+1] | rev[i] on the last level) + Upsample(-> rev[i+1])
         const int n = (int)h->rev_dims.size() - 1;
         int shift_off = 0;

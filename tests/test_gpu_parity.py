@@ -1270,6 +1270,19 @@ def test_block_conv_reports_fp16_overflow_where_layernorm_relu_would_hide_it(O, 
     assert relerr(got2, ref2) < 1e-5 and G.status()["range_faults"] == 1
 
 
+def test_operator_with_a_non_finite_input_returns_it_and_keeps_f16x2():
+    """A NaN in the input of a cdc_op_* call is non-finite in BF16X3 too: the result comes back as it is, counted in
+    nonfinite_results and not as a range fault, and the handle keeps its fast arithmetic."""
+    x = synth.normal("cx", (1, 8, 9, 11), 22)
+    x[0, 3, 4, 5] = np.nan
+    w = synth.normal("cw", (6, 8, 3, 3), 22, 1.0 / np.sqrt(8 * 9))
+    b = synth.normal("cb", (6,), 22, 0.1)
+    G = Ops(0)
+    y = G.conv2d(x, w, b, 1, 1)
+    assert not np.isfinite(y).all()
+    assert G.status() == {"arith": 1, "range_faults": 0, "nonfinite_results": 1}, G.status()
+
+
 def test_overflow_of_a_block_input_only_is_detected_inside_the_network(O):
     """The in-network form of the case above: a time-embedding bias of 2e5 on one channel makes h1 = Block1(x) + mlp(t) leave
     the fp16 range; h1 feeds block2 and nothing else (network_components.py:107-114), so the overflow sits ONLY in the
@@ -1327,6 +1340,45 @@ def test_range_guard_in_unet_forward_and_ddim_step():
     np.random.seed(3)
     rec = diff.decompress(big, x.shape, sample_steps=2, init=init, eta=0.5)
     assert np.isfinite(rec).all() and un4.status()["arith"] == 0 and un4.range_faults == 1
+    # cdc_ddim_step WITHOUT the context (ctx == NULL reuses the hoisted context halves of the previous step): a range fault
+    # switches the handle to BF16X3, but the staged context went with the old launch program -- the step is not repeated, the
+    # caller is told to hand the context over again
+    B, C, H, W = x.shape
+    ctx_c = [np.ascontiguousarray(c, np.float32) for c in ctx]
+    cptr = (ctypes.c_void_p * len(ctx_c))(*[c.ctypes.data for c in ctx_c])
+
+    def step(u, x_in, with_ctx):
+        out = np.empty_like(x_in)
+        rc = L.cdc_ddim_step(u._handle(), x_in.ctypes.data, 1, cptr if with_ctx else None, len(ctx) if with_ctx else 0, None,
+                             0.0, out.ctypes.data, B, H, W, _lib.CDC_PRED_X, _lib.CDC_CLIP_ALL, _lib.CDC_MEM_HOST, None)
+        return rc, out
+
+    un5, *_ = make_unet("small_x")
+    cdc.GaussianDiffusionX(un5, None, None, num_timesteps=8193, pred_mode="x", var_schedule="cosine").set_sample_schedule(2)
+    assert step(un5, init, True)[0] == 0 and un5.status() == {"arith": 1, "range_faults": 0, "nonfinite_results": 0}
+    rc, _ = step(un5, init * np.float32(3.0e5), False)                   # -2: CDC_ERR_STATE
+    assert rc == -2 and "WITH the context" in L.cdc_last_error(un5._handle()).decode()
+    assert un5.status() == {"arith": 0, "range_faults": 1, "nonfinite_results": 0}
+    rc, y5 = step(un5, init, True)
+    assert rc == 0 and np.isfinite(y5).all() and un5.status() == {"arith": 0, "range_faults": 1, "nonfinite_results": 0}
+    un6, *_ = make_unet("small_x")
+    _lib.check(un6._handle(), L.cdc_set_arith(un6._handle(), 0))
+    cdc.GaussianDiffusionX(un6, None, None, num_timesteps=8193, pred_mode="x", var_schedule="cosine").set_sample_schedule(2)
+    rc, y6 = step(un6, init, True)
+    assert rc == 0
+    np.testing.assert_array_equal(y5, y6)
+    # cdc_decode with a NaN in `init` (eps tree without clamps, which could turn the NaN into a finite value): the result is
+    # non-finite in BF16X3 too -- returned as it is and counted, and the handle keeps F16X2
+    un7, _, _, x_e, _, ctx_e, _ = make_unet("small_eps")
+    diff7 = cdc.GaussianDiffusionEps(un7, None, num_timesteps=20000, clip_noise="none", pred_mode="noise", var_schedule="linear")
+    init_e = synth.normal("init", x_e.shape, seed=1, std=0.8)
+    init_nan = init_e.copy()
+    init_nan[0, 0, 0, 0] = np.nan
+    rec7 = diff7.decompress(ctx_e, x_e.shape, sample_steps=2, init=init_nan)
+    assert not np.isfinite(rec7).all()
+    assert un7.status() == {"arith": 1, "range_faults": 0, "nonfinite_results": 1}
+    rec7b = diff7.decompress(ctx_e, x_e.shape, sample_steps=2, init=init_e)
+    assert np.isfinite(rec7b).all() and un7.status() == {"arith": 1, "range_faults": 0, "nonfinite_results": 1}
 
 
 def test_range_guard_in_the_compressor_entry_points():
@@ -1360,6 +1412,13 @@ def test_range_guard_in_the_compressor_entry_points():
     for a, b in zip(outs, ref.decode(ql)):
         np.testing.assert_array_equal(a, b)
     assert ref.range_faults == 0
+    # a NaN in q_latent is non-finite in BF16X3 too: returned as it is and counted, and the context decoder keeps F16X2
+    comp3 = _small_compressor()
+    ql_nan = np.rint(lat_r)
+    ql_nan[0, 0, 0, 0] = np.nan
+    outs3 = comp3.decode(ql_nan)
+    assert not all(np.isfinite(o).all() for o in outs3)
+    assert comp3.status()["dec"] == {"arith": 1, "range_faults": 0, "nonfinite_results": 1}
     # the entropy encoder refuses what it cannot code instead of converting NaN to an integer
     comp2 = _small_compressor()
     with pytest.raises(_lib.CdcError, match="non-finite"):
