@@ -8,7 +8,11 @@ x-param, batch 32, 256x256, 500 steps, 1 MI355X.  Multi-GPU: one process per GPU
 batch is sharded (weak scaling: `batch` images per GPU) through cdc_compression_amd.parallel.sharded_decode;
 the only collective is its final all_gather of the decoded images over RCCL.
 
-    python bench.py                      # N=1, 1 timed decode + verification + CPU baseline sample
+A plain run sets up, warms up, times its steps, writes --dump-outputs and prints the JSON line; every other measurement and
+check is part of --full.
+
+    python bench.py                      # N=1, 1 timed decode, the headline line alone
+    python bench.py --full               # + verification, bf16x3 decode, other configs, compressor legs, ceilings, CPU baseline
     python bench.py --gpus 8             # starts its 8 ranks itself (one per GPU, RCCL; self_launch below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 1 --warmup 0      # the same under an external launcher
@@ -267,7 +271,7 @@ def roofline_block(classes, ops, B, S, arith, value, sample_steps, steps, dt, cf
                       "frac_of_8tb_s": alg_bytes / (dom_ms * 1e-3) / 8e12} if alg_bytes and dom_ms > 0 else None),
         "peak_basis": f"2500 TFLOP/s dense 16-bit MFMA / {products} products per algorithmic fp32 product",
         "mfma_tflops_executed": ach * products,
-        # what THIS box sustains, measured by this run right after the timed region (csrc/probe.hip through the C-ABI): a register-only
+        # what THIS box sustains, measured by a --full run right after the timed region (csrc/probe.hip through the C-ABI): a register-only
         # loop of v_mfma_f32_32x32x16_f16 on constant / on pseudo-random operands, and a 1 GiB float4 copy.  `peak` / `frac` stay on the
         # guide's nominal 2500 TFLOP/s; these say how far the part itself is from it under load.
         "mfma_sustained_measured": ({**ceilings["mfma"], "frac_of_random_operand_loop": (ach * products / ceilings["mfma"]["tflops_random_operands"]
@@ -453,11 +457,16 @@ def main():
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="process-group backend: nccl = RCCL over xGMI (one rank per GPU); gloo lets several ranks share one GPU "
                          "(dry run of the multi-rank path on a 1-GPU box: rank r uses cuda:(LOCAL_RANK mod device count))")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify", action="store_true", help="skip the B=1 re-decode of two output rows")
-    ap.add_argument("--no-alt-arith", action="store_true", help="skip the extra decode in the exact bf16x3 arithmetic")
-    ap.add_argument("--no-extras", action="store_true", help="skip the informational compressor / entropy coder legs (profiling runs)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the timed decodes of BASELINE configs[2] and configs[4]")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run what it does not need: the B=1 re-decode of two output rows, the decode in "
+                         "bf16x3, the sampling cost, the compressor / entropy coder legs, BASELINE configs[2] and configs[4], the "
+                         "part's measured ceilings and the CPU baseline (the --no-* options below skip single legs of it)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the B=1 re-decode of two output rows")
+    ap.add_argument("--no-alt-arith", action="store_true", help="--full: skip the extra decode in the exact bf16x3 arithmetic")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="--full: skip the sampling cost and the informational compressor / entropy coder legs (profiling runs)")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: skip the timed decodes of BASELINE configs[2] and configs[4]")
     ap.add_argument("--dump-ops", default=None, help="write the launch program's op labels (program order) to this file (profiling tools)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="write the decoded images of the last timed step to DIR/reconstruction.npy (float32; a fixed seeded "
@@ -472,6 +481,9 @@ def main():
         ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.sample_steps is None:
         a.sample_steps = 500 if a.param == "x" else 1000
+    if not a.full:
+        # a plain run does only what the headline needs: every leg behind the timed region is off
+        a.no_cpu_baseline = a.no_verify = a.no_alt_arith = a.no_extras = a.no_other_configs = True
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         # bare `python bench.py --gpus N`: this process is only the launcher of its N ranks (one per GPU)
@@ -596,7 +608,7 @@ def main():
                        "backend": (a.backend if use_dist else None), "launcher": launcher,
                        "arith": arith_name(arith)},
             "roofline": roofline_block(classes, ops, B, S, arith, value, a.sample_steps, a.steps, dt, cfgd, a.prof_every,
-                                       ceilings=measure_ceilings(L, local) if world == 1 else None),
+                                       ceilings=measure_ceilings(L, local) if world == 1 and a.full else None),
         }
         if world > 1 and not a.no_verify:
             out["verify"] = {"every_rank_checked_rows_0_and_last_of_its_shard_against_batch1_decodes": True,

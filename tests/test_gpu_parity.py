@@ -1481,6 +1481,36 @@ def test_bench_under_torchrun_one_rank_nccl(tmp_path):
     assert relerr(got, want) < 1e-5, relerr(got, want)
 
 
+def test_bench_plain_run_is_the_headline_alone():
+    """A plain `python bench.py --gpus 1` sets up, warms up, times its steps and prints the line.  What the headline does not need
+    (batch-1 verification, the bf16x3 decode, the sampling cost, the compressor legs, the measured ceilings) runs with --full only,
+    beside the same headline fields."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--batch", "3",
+           "--sample-steps", "6", "--size", "64", "--prof-every", "2"]
+    runs = []
+    for extra in ([], ["--full", "--no-cpu-baseline"]):
+        r = subprocess.run(cmd + extra, capture_output=True, text=True, timeout=600, env=env, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        runs.append(json.loads(lines[0]))
+    plain, full = runs
+    moved = {"verify", "batch1", "alt_arith", "context_decode", "compressor_forward", "entropy_coder", "other_configs", "cpu_baseline"}
+    assert not moved & set(plain), moved & set(plain)
+    assert {"verify", "batch1", "context_decode", "compressor_forward", "entropy_coder"} <= set(full)
+    assert "sampling" not in plain["roofline"] and plain["roofline"]["mfma_sustained_measured"] is None
+    assert "sampling" in full["roofline"] and full["roofline"]["mfma_sustained_measured"] is not None
+    for k in ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "steps", "warmup"):
+        assert plain[k] == full[k], k
+    assert abs(plain["value"] - 3 / (plain["ms_per_step"] * 1e-3)) < 1e-6 * plain["value"]
+    assert plain["config"]["finite"] is True and plain["config"]["range_faults"] == 0 and plain["roofline"]["achieved"] > 0
+    assert full["config"]["finite"] is True and full["verify"]["ok"] is True
+
+
 def test_bench_multi_rank_branch_two_ranks_on_one_gpu():
     """the world > 1 branch of bench.py (per-rank seeds, shard of a global batch, all_gather of the decoded
     images, MAX-over-ranks timing, rank count, per-rank verification) on the one GPU of a test box: torchrun starts TWO ranks
@@ -1492,7 +1522,7 @@ def test_bench_multi_rank_branch_two_ranks_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k != "HSA_ENABLE_IPC_MODE_LEGACY"}    # bench.py sets it itself
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", "29613", os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2",
-           "--warmup", "1", "--batch", "3", "--sample-steps", "6", "--size", "64", "--no-cpu-baseline", "--prof-every", "2"]
+           "--warmup", "1", "--batch", "3", "--sample-steps", "6", "--size", "64", "--full", "--no-cpu-baseline", "--prof-every", "2"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -1529,7 +1559,7 @@ def test_bench_self_launch_two_ranks_on_one_gpu():
     env = {k: v for k, v in os.environ.items()
            if k not in ("HSA_ENABLE_IPC_MODE_LEGACY", "RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1",
-           "--batch", "3", "--sample-steps", "6", "--size", "64", "--no-cpu-baseline", "--prof-every", "2"]
+           "--batch", "3", "--sample-steps", "6", "--size", "64", "--full", "--no-cpu-baseline", "--prof-every", "2"]
     assert "torch.distributed.run" not in " ".join(cmd)
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -3,7 +3,7 @@
 #   pmc_r06_path.{txt,json}       counters over the WHOLE decode path (tools/gpu_pmc_path.sh: separate --pmc passes)
 #   pmc_r06_traffic.json          HBM bytes per op label of the launch program + the kernel_source_hash of the build they were collected on
 #                                 (bench.py's roofline.traffic quotes it for exactly these kernel sources only)
-#   bench_r06.json                the default bench line (headline + other_configs + verify + alt_arith + cpu_baseline + measured ceilings)
+#   bench_r06.json                the --full bench line (headline + other_configs + verify + alt_arith + cpu_baseline + measured ceilings)
 #   per_op_r06.txt                per-op / per-level times of one DDIM iteration from a kernel trace (tools/trace_by_op.py), batch 32
 #   per_op_r06_batch1.txt         the same at one image per call
 #   rocprof_r06_kernel_stats.csv  rocprofv3 --kernel-trace --stats of `python bench.py` without the extra legs
@@ -15,7 +15,7 @@ timeout 1500 bash tools/gpu_pmc_path.sh 3 r06 > $OUT/pmc_path_log.txt 2>&1
 cp $R/gpurun_out/pmc_r06/pmc_r06_path.txt $R/gpurun_out/pmc_r06/pmc_r06_path.json $R/gpurun_out/pmc_r06/pmc_r06_traffic.json $R/gpurun_out/pmc_r06/ops.txt $OUT/ 2>/dev/null
 cp $R/gpurun_out/pmc_r06/pmc_r06_traffic.json $R/profiles/pmc_r06_traffic.json 2>/dev/null     # bench.py reads it (roofline.traffic)
 tail -6 $OUT/pmc_path_log.txt
-timeout 1200 python bench.py > $OUT/bench_r06.json 2> $OUT/bench_stderr.txt
+timeout 1200 python bench.py --full > $OUT/bench_r06.json 2> $OUT/bench_stderr.txt
 tail -1 $OUT/bench_r06.json | cut -c1-300
 bash tools/gpu_by_op.sh > $OUT/by_op_log.txt 2>&1
 cp $R/gpurun_out/by_op/by_op_batch32.txt $OUT/per_op_r06.txt; cp $R/gpurun_out/by_op/by_op_batch1.txt $OUT/per_op_r06_batch1.txt

@@ -4,7 +4,7 @@ set -u
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/suite_bench; mkdir -p $OUT; cd $R
 timeout 1500 python -m pytest tests -m gpu -q -p no:cacheprovider > $OUT/pytest.log 2>&1
 tail -4 $OUT/pytest.log
-CDC_BENCH_OPS=400 timeout 900 python bench.py --no-other-configs --no-alt-arith --no-extras > $OUT/bench.json 2> $OUT/bench_stderr.txt
+CDC_BENCH_OPS=400 timeout 900 python bench.py --full --no-other-configs --no-alt-arith --no-extras > $OUT/bench.json 2> $OUT/bench_stderr.txt
 grep "^\[op\]" $OUT/bench_stderr.txt > $OUT/per_op.txt
 python - <<'PY'
 import json,os
