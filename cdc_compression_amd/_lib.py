@@ -12,6 +12,8 @@ CDC_MEM_HOST, CDC_MEM_DEVICE = 0, 1
 CDC_PRED_X, CDC_PRED_NOISE, CDC_PRED_NOISE_XTREE, CDC_PRED_V = 0, 1, 2, 3
 CDC_CLIP_NONE, CDC_CLIP_ALL, CDC_CLIP_HALF = 0, 1, 2
 CDC_MAX_LEVELS = 8
+CDC_ELEM_F32, CDC_ELEM_U8 = 0, 1
+CDC_FILL_EDGE, CDC_FILL_ZERO = 0, 1
 
 _f = ctypes.POINTER(ctypes.c_float)
 _i = ctypes.c_int
@@ -115,6 +117,12 @@ def lib():
     L.cdc_enable_vbr.argtypes = [H]
     L.cdc_set_bitrate_scale.argtypes = [H, _vp, _i]
     L.cdc_entropy_peek_bitrate_scale.argtypes = [_vp, ctypes.c_size_t, ctypes.POINTER(_i), ctypes.POINTER(ctypes.c_float)]
+    L.cdc_padded_size.argtypes = [H, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]
+    L.cdc_frame_pad.argtypes = [H, _vp, _vp] + [_i] * 8 + [_vp]
+    L.cdc_frame_crop.argtypes = [H, _vp, _vp] + [_i] * 7 + [_vp]
+    L.cdc_entropy_set_image_scale.argtypes = [H, _i]
+    L.cdc_entropy_encode_image.argtypes = [H, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), _i, _vp]
+    L.cdc_entropy_peek_image_size.argtypes = [_vp, ctypes.c_size_t, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]
     L.cdc_dequantize.argtypes = [H, _vp, _vp, _vp, ctypes.c_longlong, _i, _vp]
     L.cdc_bpp.argtypes = [H, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]
     L.cdc_set_schedule.argtypes = [H, _i, _vp, _vp, _vp, _vp, _vp, _vp]
@@ -154,7 +162,9 @@ EXPORTS = ["cdc_create", "cdc_destroy", "cdc_last_error", "cdc_version", "cdc_nu
            "cdc_encoder_encode", "cdc_set_arith", "cdc_get_arith", "cdc_unet_tap", "cdc_prof_num_ops", "cdc_prof_op",
            "cdc_entropy_encode", "cdc_entropy_peek", "cdc_entropy_set_limit", "cdc_entropy_decode", "cdc_get_range_faults",
            "cdc_get_nonfinite_results", "cdc_set_schedule_v", "cdc_probe_mfma_f16", "cdc_probe_hbm_copy",
-           "cdc_op_stress", "cdc_op_stress_result", "cdc_enable_vbr", "cdc_set_bitrate_scale", "cdc_entropy_peek_bitrate_scale"]
+           "cdc_op_stress", "cdc_op_stress_result", "cdc_enable_vbr", "cdc_set_bitrate_scale", "cdc_entropy_peek_bitrate_scale",
+           "cdc_padded_size", "cdc_frame_pad", "cdc_frame_crop", "cdc_entropy_set_image_scale", "cdc_entropy_encode_image",
+           "cdc_entropy_peek_image_size"]
 
 
 def handle_status(handle):
@@ -170,4 +180,7 @@ def handle_status(handle):
 def check(handle, rc):
     if rc != 0:
         msg = lib().cdc_last_error(handle)
-        raise CdcError(f"libcdc_hip error {rc}: {msg.decode() if msg else ''}")
+        msg = msg.decode() if msg else ""
+        if "must be multiples of" in msg:
+            msg += " -- padded_size(H, W) gives the frame; compress() / decompress() / the compressor's forward() pad any size themselves"
+        raise CdcError(f"libcdc_hip error {rc}: {msg}")

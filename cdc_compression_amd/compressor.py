@@ -17,12 +17,19 @@ Variable bitrate (`BigCompressor(vbr=True)`, epsilonparam compress_modules.py:12
 VBRCondition site takes the rate as `cond` / `bitrate_scale` -- a numpy array or torch tensor of 1 (broadcast) or B
 elements, as the reference's `cond.reshape(-1, 1, 1, 1)` accepts -- and the streams of `compress_to_bytes` carry each
 image's rate (container version 4), so `decompress_from_bytes` needs none.
+
+Images of any size (cdc_compression_amd.frame states the rule): `forward`, `encode` and `compress_to_bytes` take `[B, 3, H, W]` of
+any `H, W >= 1`, float32 in [-1, 1] or uint8, and run on the frame padded at the bottom / right by edge replication to this model's
+multiple (`padded_size`).  Every latent and `forward()["output"]` -- the context pyramid the denoising U-Net consumes -- belong to
+that PADDED frame; `bpp` counts bits over the original `H * W`; the streams record `H x W` (container version 5 / 6) unless the
+image already is its own frame, in which case they are the version-3 / -4 streams they always were.  `analysis`, `decode`,
+`hyper_decode` mirror the reference's modules one to one and keep requiring frame sizes.
 """
 import ctypes
 
 import numpy as np
 
-from . import _lib
+from . import _lib, frame
 from .unet import _Arg, _as_host_f32, _current_stream, _result_like
 
 
@@ -236,6 +243,8 @@ class _ContextDecoder:
             if rc != 0:
                 raise _lib.CdcError(f"cdc_hyperdec_create failed ({rc}): {L.cdc_last_error(None).decode()}")
             self._hh = self._vbr_handle(h)
+            # image pixels per hyper-latent position (the streams of images that are not their own frame need it)
+            _lib.check(self._hh, L.cdc_entropy_set_image_scale(self._hh, self.frame_multiple))
         return self._hh
 
     def hyper_manifest(self):
@@ -343,6 +352,29 @@ class _ContextDecoder:
         q_latent = self.dequantize(state4bpp["latent"], mean)
         return self.rate(q_hyper, q_latent, mean, scale, (H, W))
 
+    # ---- images of any size ------------------------------------------------------------------
+    @property
+    def frame_multiple(self):
+        """Image pixels per hyper-latent position and side: what H and W of a frame must be multiples of (64 as published)."""
+        return 2 ** (len(self.rev_mults) + len(self.reversed_hyper_dims) - 2)
+
+    def padded_size(self, H, W):
+        """(Hp, Wp) of the frame an H x W image is coded on (cdc_padded_size of the encoder handle: no hard-coded 64)."""
+        return frame.padded_size([self._enc_handle()], H, W)
+
+    def _framed(self, input, padded_hw=None):
+        """images [B, 3, H, W] (float32 / uint8, any size) -> (float32 frame, (H, W)).  An image that is its own frame and float32
+        passes through untouched.  padded_hw: a larger frame another part of the model asks for (GaussianDiffusion: the U-Net's)."""
+        _, _, H, W = frame.image_shape(input)
+        Hp, Wp = self.padded_size(H, W)
+        if padded_hw is not None:
+            if tuple(padded_hw) != self.padded_size(*padded_hw) or padded_hw[0] < Hp or padded_hw[1] < Wp:
+                raise _lib.CdcError(f"padded_hw {tuple(padded_hw)} is no frame of a {H} x {W} image for this model (multiple {self.frame_multiple})")
+            Hp, Wp = padded_hw
+        if (Hp, Wp) == (H, W) and not frame.is_uint8(input):
+            return input, (H, W)
+        return frame.pad(self._enc_handle(), input, Hp, Wp, self.device_index), (H, W)
+
     # ---- encoder (SURVEY section 8f row 3) ---------------------------------------------------
     def _enc_handle(self):
         if self._eh is None:
@@ -413,9 +445,11 @@ class _ContextDecoder:
             med = torch.from_numpy(med).to(t.device)
         return med
 
-    def encode(self, input, cond=None):
-        """Compressor.encode (compress_modules.py:43-66): (q_latent, q_hyper_latent, state4bpp); cond: VBR rate."""
-        self._rates(cond, _Arg(input, self.device_index).shape[0])
+    def encode(self, input, cond=None, padded_hw=None):
+        """Compressor.encode (compress_modules.py:43-66): (q_latent, q_hyper_latent, state4bpp); cond: VBR rate.  Images of any
+        size (float32 / uint8): the results are those of the padded frame."""
+        self._rates(cond, frame.image_shape(input)[0])
+        input, _ = self._framed(input, padded_hw)
         latent, hyper_latent = self.analysis(input, cond)
         q_hyper_latent = self.dequantize(hyper_latent, self._medians_like(hyper_latent))
         mean, scale = self.hyper_decode(q_hyper_latent, cond=cond)
@@ -434,14 +468,17 @@ class _ContextDecoder:
         """images [B, 3, H, W] -> list of B bitstreams (bytes): analysis transform + hyper encoder on the GPU, then the
         range-ANS coder of include/cdc_hip.h (cdc_entropy_encode) over exactly the symbols `bpp()` prices.  A VBR model
         takes bitrate_scale (1 or B values) and records each image's rate in its stream."""
-        self._rates(bitrate_scale, _Arg(images, self.device_index).shape[0])
+        self._rates(bitrate_scale, frame.image_shape(images)[0])
+        images, hw = self._framed(images)
         latent, hyper = self.analysis(images, bitrate_scale)
-        return self.latents_to_bytes(latent, hyper, bitrate_scale)
+        return self.latents_to_bytes(latent, hyper, bitrate_scale, image_hw=hw)
 
-    def latents_to_bytes(self, latent, hyper, bitrate_scale=None):
+    def latents_to_bytes(self, latent, hyper, bitrate_scale=None, image_hw=None):
         """The UNquantised outputs of `analysis()` -> list of B bitstreams.  The coder's determinism contract starts here: the
         same (latent, hyper) rows give the same bytes whatever the batch they are coded in (the analysis transform itself is
-        an ordinary batched forward: its last bits may depend on the batch size, like any other entry point's)."""
+        an ordinary batched forward: its last bits may depend on the batch size, like any other entry point's).
+        image_hw=(H, W): the size of the original image when the latents are those of its padded frame; the streams then record it
+        (container version 5 / 6) unless it equals the frame's, and are today's version 3 / 4 otherwise."""
         L, h = _lib.lib(), self._hyper_handle()
         if not (self._hyper_finalized and self._prior_loaded):
             raise _lib.CdcError("the prior.* tensors have not been loaded (load_state_dict with the full state_dict)")
@@ -453,17 +490,23 @@ class _ContextDecoder:
         buf = np.empty(cap, dtype=np.uint8)
         offs = (ctypes.c_size_t * (B + 1))()
         med = self._median_vector()
-        _lib.check(h, L.cdc_entropy_encode(h, al.ptr, ah.ptr, med.ctypes.data, B, hh, wh, buf.ctypes.data, cap, offs, al.mem,
-                                           _current_stream(al.mem)))
+        if image_hw is None:
+            _lib.check(h, L.cdc_entropy_encode(h, al.ptr, ah.ptr, med.ctypes.data, B, hh, wh, buf.ctypes.data, cap, offs, al.mem,
+                                               _current_stream(al.mem)))
+        else:
+            _lib.check(h, L.cdc_entropy_encode_image(h, al.ptr, ah.ptr, med.ctypes.data, B, hh, wh, int(image_hw[0]), int(image_hw[1]),
+                                                     buf.ctypes.data, cap, offs, al.mem, _current_stream(al.mem)))
         raw = buf[: offs[B]].tobytes()
         return [raw[offs[b]: offs[b + 1]] for b in range(B)]
 
-    def decompress_from_bytes(self, streams, like=None, return_hyper=False, max_image_hw=None, return_bitrate_scale=False):
+    def decompress_from_bytes(self, streams, like=None, return_hyper=False, max_image_hw=None, return_bitrate_scale=False,
+                              return_image_size=False):
         """list of B bitstreams -> q_latent [B, C, h, w] exactly as the encoder dequantised it (numpy, or a tensor on
         `like`'s device); all streams must have the same latent size.  max_image_hw=(H, W): refuse streams whose header
         describes a larger image before anything is allocated (untrusted input; default: the library's 2^22-position bound).
         return_bitrate_scale: also return the float32 [B] rates the streams of a VBR model carry (None for a fixed-rate model);
-        `decode(q_latent, rates)` then gives the context pyramid."""
+        `decode(q_latent, rates)` then gives the context pyramid.  return_image_size: also return (H, W), the size the streams
+        record (version 5 / 6) or, for version 3 / 4, the coded extent; q_latent is that of the padded frame either way."""
         L, h = _lib.lib(), self._hyper_handle()
         # the limit is handle state in the library: set it on EVERY call (None -> the library's default bound), so that one
         # restricted call does not restrict the next; the product is clamped before it is handed over as a C int
@@ -502,7 +545,27 @@ class _ContextDecoder:
         out = (q, qh) if return_hyper else (q,)
         if return_bitrate_scale:
             out = out + (self.bitrate_scale_of(streams) if self.vbr else None,)
+        if return_image_size:
+            sizes = set(self.image_size_of(streams, self.frame_multiple))
+            if len(sizes) != 1:
+                raise _lib.CdcError("the streams of one call must share the image size")
+            out = out + (sizes.pop(),)
         return out if len(out) > 1 else out[0]
+
+    @staticmethod
+    def image_size_of(streams, frame_multiple=64):
+        """[(H, W)] of the images the streams hold: the recorded size (version 5 / 6) or the coded extent (version 3 / 4:
+        frame_multiple pixels per hyper-latent position)."""
+        L = _lib.lib()
+        has, H, W, hh, wh = (ctypes.c_int() for _ in range(5))
+        out = []
+        for s in streams:
+            s = bytes(s)
+            if L.cdc_entropy_peek_image_size(s, len(s), ctypes.byref(has), ctypes.byref(H), ctypes.byref(W)) != 0 or \
+                    L.cdc_entropy_peek(s, len(s), ctypes.byref(hh), ctypes.byref(wh), None) != 0:
+                raise _lib.CdcError("not a CDC bitstream")
+            out.append((H.value, W.value) if has.value else (hh.value * frame_multiple, wh.value * frame_multiple))
+        return out
 
     @staticmethod
     def bitrate_scale_of(streams):
@@ -519,10 +582,11 @@ class _ContextDecoder:
             out[b] = r.value
         return out
 
-    def forward(self, input, cond=None):
-        """Compressor.forward (compress_modules.py:92-103)."""
-        q_latent, q_hyper_latent, state4bpp = self.encode(input, cond)
-        shape = tuple(_Arg(input, self.device_index).shape)
+    def forward(self, input, cond=None, padded_hw=None):
+        """Compressor.forward (compress_modules.py:92-103).  Images of any size (float32 / uint8): "output" (the context pyramid the
+        U-Net consumes), "q_latent" and "q_hyper_latent" are those of the PADDED frame, "bpp" counts bits over the original H * W."""
+        shape = frame.image_shape(input)
+        q_latent, q_hyper_latent, state4bpp = self.encode(input, cond, padded_hw)
         return {"output": self.decode(q_latent, cond), "bpp": self.bpp(shape, state4bpp), "q_latent": q_latent,
                 "q_hyper_latent": q_hyper_latent}
 

@@ -571,6 +571,99 @@ int cdc_dequantize(cdc_handle *h, const float *x, const float *offset, float *ou
     return CDC_OK;
 }
 
+// ---- images of any size: the padded frame (frame_kernels.hip) ------------------------------------------------------------------
+namespace {
+int frame_args(cdc_handle *h, const void *src, const void *dst, int B, int H, int W, int Hp, int Wp, int elem, int mem) {
+    if (!src || !dst || B < 1 || H < 1 || W < 1 || Hp < H || Wp < W) return fail(h, CDC_ERR_INVALID, "frame: null pointer or sizes B=%d %dx%d -> %dx%d (need 1 <= H <= Hp, 1 <= W <= Wp)", B, H, W, Hp, Wp);
+    if (elem != CDC_ELEM_F32 && elem != CDC_ELEM_U8) return fail(h, CDC_ERR_INVALID, "frame: element kind %d", elem);
+    if (mem != CDC_MEM_HOST && mem != CDC_MEM_DEVICE) return fail(h, CDC_ERR_INVALID, "frame: mem_kind %d", mem);
+    if ((long long)B * 3 * Hp * Wp > (1ll << 40)) return fail(h, CDC_ERR_INVALID, "frame: %d x 3 x %d x %d elements", B, Hp, Wp);
+    return CDC_OK;
+}
+}  // namespace
+
+int cdc_frame_pad(cdc_handle *h, const void *src, float *dst, int B, int H, int W, int Hp, int Wp, int elem, int fill, int mem, void *stream) {
+    if (!h) return CDC_ERR_INVALID;
+    return no_throw(h, [&] {
+        return with_range_guard(h, [&]() -> int {
+            int rc = ensure_device(h);
+            if (rc) return rc;
+            if ((rc = frame_args(h, src, dst, B, H, W, Hp, Wp, elem, mem))) return rc;
+            if (fill != CDC_FILL_EDGE && fill != CDC_FILL_ZERO) return fail(h, CDC_ERR_INVALID, "frame: fill mode %d", fill);
+            const int P = 3 * B, u8 = elem == CDC_ELEM_U8;
+            hipStream_t st = pick_stream(h, stream, mem);
+            if (mem == CDC_MEM_DEVICE) {
+                HIP_TRY(h, frame_in_launch(src, u8, dst, P, H, W, Hp, Wp, fill, st));
+                return CDC_OK;
+            }
+            const size_t nin = (size_t)P * H * W * (u8 ? 1 : 4), nout = (size_t)P * Hp * Wp;
+            DevPool d;
+            uint8_t *ds;
+            float *dd;
+            HIP_TRY(h, d.get(&ds, nin));
+            HIP_TRY(h, d.get(&dd, nout));
+            hipError_t e = hipMemcpyAsync(ds, src, nin, hipMemcpyHostToDevice, st);
+            if (e == hipSuccess) e = frame_in_launch(ds, u8, dd, P, H, W, Hp, Wp, fill, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(dst, dd, nout * sizeof(float), hipMemcpyDeviceToHost, st);
+            const hipError_t es = hipStreamSynchronize(st);   // (after an error too: nothing queued may still use what d frees)
+            if (e == hipSuccess) e = es;
+            if (e != hipSuccess) return fail(h, CDC_ERR_HIP, "frame_pad: %s", hipGetErrorString(e));
+            return CDC_OK;
+        });
+    });
+}
+
+int cdc_frame_crop(cdc_handle *h, const float *src, void *dst, int B, int H, int W, int Hp, int Wp, int elem, int mem, void *stream) {
+    if (!h) return CDC_ERR_INVALID;
+    return no_throw(h, [&] {
+        return with_range_guard(h, [&]() -> int {
+            int rc = ensure_device(h);
+            if (rc) return rc;
+            if ((rc = frame_args(h, src, dst, B, H, W, Hp, Wp, elem, mem))) return rc;
+            const int P = 3 * B, u8 = elem == CDC_ELEM_U8;
+            hipStream_t st = pick_stream(h, stream, mem);
+            if (mem == CDC_MEM_DEVICE) {
+                HIP_TRY(h, frame_out_launch(src, dst, u8, P, H, W, Hp, Wp, st));
+                return CDC_OK;
+            }
+            const size_t nin = (size_t)P * Hp * Wp, nout = (size_t)P * H * W * (u8 ? 1 : 4);
+            DevPool d;
+            float *ds;
+            uint8_t *dd;
+            HIP_TRY(h, d.get(&ds, nin));
+            HIP_TRY(h, d.get(&dd, nout));
+            hipError_t e = hipMemcpyAsync(ds, src, nin * sizeof(float), hipMemcpyHostToDevice, st);
+            if (e == hipSuccess) e = frame_out_launch(ds, dd, u8, P, H, W, Hp, Wp, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(dst, dd, nout, hipMemcpyDeviceToHost, st);
+            const hipError_t es = hipStreamSynchronize(st);
+            if (e == hipSuccess) e = es;
+            if (e != hipSuccess) return fail(h, CDC_ERR_HIP, "frame_crop: %s", hipGetErrorString(e));
+            return CDC_OK;
+        });
+    });
+}
+
+int cdc_padded_size(cdc_handle *h, int H, int W, int *Hp, int *Wp) {
+    if (!h) return CDC_ERR_INVALID;
+    if (H < 1 || W < 1 || !Hp || !Wp) return fail(h, CDC_ERR_INVALID, "padded_size: H=%d W=%d", H, W);
+    int shift = 0;
+    long long M = 0;
+    switch (h->kind) {
+        case HandleKind::Unet: shift = h->cfg.n_dim_mults - 1; break;                              // one Downsample per level but the last
+        case HandleKind::Encoder: shift = (int)h->enc_dims.size() - 1 + (int)h->henc_dims.size() - 2; break;   // enc levels + stride-2 hyper_enc layers
+        case HandleKind::ContextDecoder: shift = (int)h->rev_dims.size() - 1; break;               // one Upsample per level
+        case HandleKind::HyperDecoder:
+            if (h->ent_pixels < 1) return fail(h, CDC_ERR_STATE, "padded_size: cdc_entropy_set_image_scale has not been called on this hyper-decoder handle");
+            M = h->ent_pixels;
+            break;
+    }
+    if (!M) M = 1ll << shift;
+    const long long hp = ((long long)H + M - 1) / M * M, wp = ((long long)W + M - 1) / M * M;
+    if (hp > INT32_MAX || wp > INT32_MAX) return fail(h, CDC_ERR_INVALID, "padded_size: %d x %d exceeds the int range at multiple %lld", H, W, M);
+    *Hp = (int)hp; *Wp = (int)wp;
+    return CDC_OK;
+}
+
 int cdc_ctxdec_create(const cdc_ctxdec_config *cfg, int device, cdc_handle **out) {
     if (!cfg || !out) return fail(nullptr, CDC_ERR_INVALID, "null argument");
     if (cfg->dim <= 0 || cfg->n_rev_mults < 1 || cfg->n_rev_mults > CDC_MAX_LEVELS || cfg->out_channels < 1 ||

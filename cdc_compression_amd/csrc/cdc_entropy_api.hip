@@ -8,7 +8,16 @@ constexpr int kStreamHeader = 34;
 // variable-bitrate model: the same header with version byte 4, then bitrate_scale f32 (hyper_dec and the synthesis transform need it)
 constexpr int kStreamVersionVbr = 4;
 constexpr int kStreamHeaderVbr = 38;
-inline int stream_header(const unsigned char *s) { return s[3] == kStreamVersionVbr ? kStreamHeaderVbr : kStreamHeader; }
+// an image that is not its own padded size: the version-3 (4) header with version byte 5 (6), then -- after the bitrate_scale of
+// version 6 -- img_h u32 | img_w u32: the size the decoder crops to (the coded extent is the image padded at the bottom / right)
+constexpr int kStreamVersionSized = 5, kStreamVersionVbrSized = 6;
+constexpr int kStreamSizeField = 8;
+inline bool version_known(int v) { return v == kStreamVersion || v == kStreamVersionVbr || v == kStreamVersionSized || v == kStreamVersionVbrSized; }
+inline bool version_vbr(int v) { return v == kStreamVersionVbr || v == kStreamVersionVbrSized; }
+inline bool version_sized(int v) { return v == kStreamVersionSized || v == kStreamVersionVbrSized; }
+inline int stream_header(const unsigned char *s) { return (version_vbr(s[3]) ? kStreamHeaderVbr : kStreamHeader) + (version_sized(s[3]) ? kStreamSizeField : 0); }
+// the recorded size must pad to exactly the coded extent: D (n - 1) < size <= D n, D image pixels per hyper-latent position
+inline bool size_fits(long long size, int n, int D) { return size > (long long)D * (n - 1) && size <= (long long)D * n; }
 
 int ensure_entropy(cdc_handle *h, const float *medians) {
     int rc = require_kind(h, HandleKind::HyperDecoder);
@@ -51,13 +60,22 @@ int hyperdec_batch(cdc_handle *h, int B, hipStream_t st, bool check) {
     return CDC_OK;
 }
 
+// img_h = img_w = 0: the image is the coded extent (version 3 / 4), as is an image size equal to it
 int entropy_encode_impl(cdc_handle *h, const float *latent, const float *hyper_latent, const float *medians, int B,
-                        int hh, int wh, unsigned char *out, size_t cap, size_t *offsets, int mem, void *stream) {
+                        int hh, int wh, int img_h, int img_w, unsigned char *out, size_t cap, size_t *offsets, int mem, void *stream) {
     int rc = check_ready(h);
     if (rc) return rc;
     if (!latent || !hyper_latent || !medians || !out || !offsets || B < 1 || hh < 1 || wh < 1 || hh > 65535 || wh > 65535 ||
         (long long)hh * wh > kMaxHyperPositions)
         return fail(h, CDC_ERR_INVALID, "null/invalid argument");
+    if (img_h || img_w) {
+        const int D = h->ent_pixels;
+        if (D < 1) return fail(h, CDC_ERR_STATE, "cdc_entropy_set_image_scale has not been called on this handle");
+        if (!size_fits(img_h, hh, D) || !size_fits(img_w, wh, D))
+            return fail(h, CDC_ERR_INVALID, "a %d x %d image does not pad to the coded extent %lld x %lld (%d x %d hyper-latent positions of %d pixels)",
+                        img_h, img_w, (long long)D * hh, (long long)D * wh, hh, wh, D);
+        if ((long long)D * hh == img_h && (long long)D * wh == img_w) img_h = img_w = 0;      // nothing to crop: today's stream, byte for byte
+    }
     if ((rc = ensure_entropy(h, medians))) return rc;
     hipStream_t st = h->own_stream;                       // synchronous entry point
     if (mem == CDC_MEM_DEVICE) HIP_TRY(h, hipStreamSynchronize((hipStream_t)stream));
@@ -83,7 +101,7 @@ int entropy_encode_impl(cdc_handle *h, const float *latent, const float *hyper_l
     cdc::RansMeta *meta;
     long long *d_off;
     const long long cap_h = section_cap(nh), cap_l = section_cap(nl);
-    const long long pack_cap = (long long)B * ((h->vbr ? kStreamHeaderVbr : kStreamHeader) + cap_h + 4 * nh + cap_l + 4 * nl);
+    const long long pack_cap = (long long)B * ((h->vbr ? kStreamHeaderVbr : kStreamHeader) + kStreamSizeField + cap_h + 4 * nh + cap_l + 4 * nl);
     HIP_TRY(h, d.get(&symh, (size_t)B * nh)); HIP_TRY(h, d.get(&syml, (size_t)B * nl)); HIP_TRY(h, d.get(&bin, (size_t)B * nl));
     HIP_TRY(h, d.get(&sf, (size_t)B * std::max(nh, nl))); HIP_TRY(h, d.get(&ew, (size_t)B * std::max(nh, nl)));
     HIP_TRY(h, d.get(&sec_h, (size_t)B * cap_h)); HIP_TRY(h, d.get(&sec_l, (size_t)B * cap_l));
@@ -107,7 +125,7 @@ int entropy_encode_impl(cdc_handle *h, const float *latent, const float *hyper_l
     const long long dev_cap = (long long)std::min<unsigned long long>((unsigned long long)cap, (unsigned long long)pack_cap);
     HIP_TRY(h, d.get(&packed, (size_t)dev_cap));
     cdc::RansPack P{sec_h, sec_l, esc_h, esc_l, meta, meta + B, cap_h, cap_l, nh, nl, dev_cap, packed, d_off, h->ent_model_hash, h->arith, hh, wh,
-                    h->vbr ? h->d_rate : nullptr};
+                    h->vbr ? h->d_rate : nullptr, img_h, img_w};
     HIP_TRY(h, cdc::rans_pack_launch(P, B, st));
     std::vector<long long> hoff((size_t)B + 1);
     HIP_TRY(h, hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -140,24 +158,36 @@ int entropy_decode_impl(cdc_handle *h, const unsigned char *in, const size_t *of
     struct Restore { cdc_handle *h; int a; ~Restore() { if (h->arith != a) (void)cdc_set_arith(h, a); } } restore{h, h->arith};
     // ---- headers: everything that sizes an allocation is validated here ----
     struct Hdr { int hh, wh, ar, hdr; uint32_t nbh, nbl, sum, eh, el; float rate; };
+    int img0_h = -1, img0_w = -1;                        // the size every image of the call shares (0: the coded extent)
     std::vector<Hdr> hd((size_t)B);
     for (int b = 0; b < B; ++b) {
         if (offsets[b + 1] < offsets[b]) return fail(h, CDC_ERR_INVALID, "image %d: offsets decrease", b);
         const unsigned char *s = in + offsets[b];
         const size_t n = offsets[b + 1] - offsets[b];
         Hdr &q = hd[b];
-        if (cdc_entropy_peek(s, n, &q.hh, &q.wh, &q.ar)) return fail(h, CDC_ERR_INVALID, "image %d: not a CDC bitstream (version %d / %d container)", b, kStreamVersion, kStreamVersionVbr);
+        if (cdc_entropy_peek(s, n, &q.hh, &q.wh, &q.ar)) return fail(h, CDC_ERR_INVALID, "image %d: not a CDC bitstream (version %d / %d / %d / %d container)", b, kStreamVersion, kStreamVersionVbr, kStreamVersionSized, kStreamVersionVbrSized);
         int has_rate = 0;
         q.rate = 0.f;
         (void)cdc_entropy_peek_bitrate_scale(s, n, &has_rate, &q.rate);
         if (has_rate != (h->vbr ? 1 : 0))
-            return fail(h, CDC_ERR_INVALID, h->vbr ? "image %d: a fixed-rate stream (version 3) given to a variable-bitrate model"
-                                                   : "image %d: a variable-bitrate stream (version 4) given to a fixed-rate model", b);
+            return fail(h, CDC_ERR_INVALID, h->vbr ? "image %d: a fixed-rate stream (version 3 / 5) given to a variable-bitrate model"
+                                                   : "image %d: a variable-bitrate stream (version 4 / 6) given to a fixed-rate model", b);
         if (has_rate && !std::isfinite(q.rate)) return fail(h, CDC_ERR_INVALID, "image %d: non-finite bitrate_scale in the header", b);
         q.hdr = stream_header(s);
         if (q.hh < 1 || q.wh < 1 || (long long)q.hh * q.wh > std::min(kMaxHyperPositions, h->ent_max_positions))
             return fail(h, CDC_ERR_INVALID, "image %d: hyper-latent size %d x %d in the stream header exceeds the decoder's limit of %d positions "
                         "(cdc_entropy_set_limit)", b, q.hh, q.wh, std::min(kMaxHyperPositions, h->ent_max_positions));
+        int has_size = 0, ih = 0, iw = 0;
+        (void)cdc_entropy_peek_image_size(s, n, &has_size, &ih, &iw);
+        if (has_size) {
+            const int D = h->ent_pixels;
+            if (D < 1) return fail(h, CDC_ERR_STATE, "image %d: the stream records an image size; cdc_entropy_set_image_scale has not been called on this handle", b);
+            if (!size_fits(ih, q.hh, D) || !size_fits(iw, q.wh, D))
+                return fail(h, CDC_ERR_INVALID, "image %d: the recorded size %u x %u does not pad to the coded extent %lld x %lld", b, (unsigned)ih, (unsigned)iw,
+                            (long long)D * q.hh, (long long)D * q.wh);
+        }
+        if (b == 0) { img0_h = ih; img0_w = iw; }
+        else if (ih != img0_h || iw != img0_w) return fail(h, CDC_ERR_INVALID, "image %d: its recorded size differs from image 0's (one call decodes one image size)", b);
         if (q.ar != CDC_ARITH_BF16X3 && q.ar != CDC_ARITH_F16X2) return fail(h, CDC_ERR_INVALID, "image %d: unknown arithmetic %d", b, q.ar);
         q.nbh = get_u32(s + 10); q.nbl = get_u32(s + 14); q.sum = get_u32(s + 22); q.eh = get_u32(s + 26); q.el = get_u32(s + 30);
         if ((unsigned long long)q.hdr + q.nbh + q.nbl != n) return fail(h, CDC_ERR_INVALID, "image %d: truncated bitstream", b);
@@ -248,8 +278,24 @@ extern "C" {
 int cdc_entropy_encode(cdc_handle *h, const float *latent, const float *hyper_latent, const float *medians, int B,
                        int hh, int wh, unsigned char *out, size_t cap, size_t *offsets, int mem, void *stream) {
     return no_throw(h, [&] {
-        return with_range_guard(h, [&] { return entropy_encode_impl(h, latent, hyper_latent, medians, B, hh, wh, out, cap, offsets, mem, stream); });
+        return with_range_guard(h, [&] { return entropy_encode_impl(h, latent, hyper_latent, medians, B, hh, wh, 0, 0, out, cap, offsets, mem, stream); });
     });
+}
+
+int cdc_entropy_encode_image(cdc_handle *h, const float *latent, const float *hyper_latent, const float *medians, int B,
+                             int hh, int wh, int img_h, int img_w, unsigned char *out, size_t cap, size_t *offsets, int mem, void *stream) {
+    return no_throw(h, [&]() -> int {
+        if (h && (img_h < 1 || img_w < 1)) return fail(h, CDC_ERR_INVALID, "image size %d x %d", img_h, img_w);
+        return with_range_guard(h, [&] { return entropy_encode_impl(h, latent, hyper_latent, medians, B, hh, wh, img_h, img_w, out, cap, offsets, mem, stream); });
+    });
+}
+
+int cdc_entropy_set_image_scale(cdc_handle *h, int pixels_per_position) {
+    if (!h) return CDC_ERR_INVALID;
+    if (int rc = require_kind(h, HandleKind::HyperDecoder)) return rc;
+    if (pixels_per_position < 1 || pixels_per_position > 65536) return fail(h, CDC_ERR_INVALID, "pixels per hyper-latent position: %d", pixels_per_position);
+    h->ent_pixels = pixels_per_position;
+    return CDC_OK;
 }
 
 int cdc_entropy_set_limit(cdc_handle *h, int max_hyper_positions) {
@@ -262,7 +308,12 @@ int cdc_entropy_set_limit(cdc_handle *h, int max_hyper_positions) {
 
 int cdc_entropy_peek(const unsigned char *in, size_t n, int *hh, int *wh, int *arith) {
     if (!in || n < (size_t)kStreamHeader || in[0] != 'C' || in[1] != 'D' || in[2] != 'C' ||
-        (in[3] != kStreamVersion && in[3] != kStreamVersionVbr) || n < (size_t)stream_header(in)) return CDC_ERR_INVALID;
+        !version_known(in[3]) || n < (size_t)stream_header(in)) return CDC_ERR_INVALID;
+    if (version_sized(in[3])) {                           // a recorded size is 1 .. 2^31 - 1 on both sides: anything else is no stream
+        const unsigned char *f = in + stream_header(in) - kStreamSizeField;
+        const uint32_t uh = get_u32(f), uw = get_u32(f + 4);
+        if (uh < 1 || uw < 1 || uh > (uint32_t)INT32_MAX || uw > (uint32_t)INT32_MAX) return CDC_ERR_INVALID;
+    }
     if (arith) *arith = in[4];
     if (hh) *hh = in[6] | (in[7] << 8);
     if (wh) *wh = in[8] | (in[9] << 8);
@@ -271,9 +322,19 @@ int cdc_entropy_peek(const unsigned char *in, size_t n, int *hh, int *wh, int *a
 
 int cdc_entropy_peek_bitrate_scale(const unsigned char *in, size_t n, int *has_scale, float *scale) {
     if (cdc_entropy_peek(in, n, nullptr, nullptr, nullptr)) return CDC_ERR_INVALID;
-    const bool v4 = in[3] == kStreamVersionVbr;
+    const bool v4 = version_vbr(in[3]);
     if (has_scale) *has_scale = v4 ? 1 : 0;
     if (v4 && scale) { const uint32_t u = get_u32(in + kStreamHeader); memcpy(scale, &u, 4); }
+    return CDC_OK;
+}
+
+int cdc_entropy_peek_image_size(const unsigned char *in, size_t n, int *has_size, int *img_h, int *img_w) {
+    if (cdc_entropy_peek(in, n, nullptr, nullptr, nullptr)) return CDC_ERR_INVALID;
+    const bool sized = version_sized(in[3]);
+    const unsigned char *f = in + stream_header(in) - kStreamSizeField;
+    if (has_size) *has_size = sized ? 1 : 0;                // (cdc_entropy_peek has checked the range of a recorded size)
+    if (sized && img_h) *img_h = (int)get_u32(f);
+    if (sized && img_w) *img_w = (int)get_u32(f + 4);
     return CDC_OK;
 }
 

@@ -253,6 +253,10 @@ hipError_t dequantize_launch(const float *x, const float *loc, float *out, long 
 // VBRCondition (variable-bitrate compressors) in place over x [B][C][HW] (batch stride bs): with r = rate[b],
 // x = x * (p[c] r + p[C + c]) + (p[2C + c] r + p[3C + c]), then LeakyReLU(0.2) when `leaky`
 hipError_t vbr_affine_launch(float *x, long long bs, int C, int HW, const float *rate, const float *p, int leaky, int B, hipStream_t st);
+// frame_kernels.hip: P planes [H][W] (float32, or uint8 -> v / 255 * 2 - 1) -> [Hp][Wp] float32, extended at the bottom / right by edge
+// replication (zero = 1: by zeros), and the top-left [H][W] window back (float32 copy, or the uint8 of save_image)
+hipError_t frame_in_launch(const void *src, int u8, float *dst, int P, int H, int W, int Hp, int Wp, int zero, hipStream_t st);
+hipError_t frame_out_launch(const float *src, void *dst, int u8, int P, int H, int W, int Hp, int Wp, hipStream_t st);
 hipError_t unfold_x_launch(const float *src, long long src_bs, float *dst, long long dst_bs, int C, int KW,
                            int pad, int H, int W, int B, hipStream_t st);
 

@@ -74,6 +74,7 @@ struct RansPack {
     uint32_t model;
     int arith, hh, wh;
     const float *rates = nullptr;   // variable-bitrate streams (version 4): each image's bitrate_scale after the header; null: version 3
+    int img_h = 0, img_w = 0;       // an image smaller than the coded extent (version 5 / 6): its size after the header (and the rate); 0: version 3 / 4
 };
 hipError_t rans_pack_launch(const RansPack &P, int B, hipStream_t st);
 

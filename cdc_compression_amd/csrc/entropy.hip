@@ -454,7 +454,8 @@ hipError_t rans_decode_launch(EntropyDev T, const uint8_t *in, const long long *
 // the 34 header bytes), packed back to back: one workgroup per image
 __global__ void __launch_bounds__(256) rans_pack_kernel(RansPack P) {
     const int b = blockIdx.x;
-    const int hdr = P.rates ? 38 : 34;
+    const bool sized = P.img_h > 0;
+    const int hdr = (P.rates ? 38 : 34) + (sized ? 8 : 0);
     auto sizes = [&](int i, uint32_t *nh, uint32_t *nl, uint32_t *eh, uint32_t *el) {
         *eh = (uint32_t)(P.esc_bs_h - P.meta_h[i].esc_start); *el = (uint32_t)(P.esc_bs_l - P.meta_l[i].esc_start);
         *nh = (uint32_t)(P.out_bs_h - P.meta_h[i].start) + 4u * *eh; *nl = (uint32_t)(P.out_bs_l - P.meta_l[i].start) + 4u * *el;
@@ -471,10 +472,11 @@ __global__ void __launch_bounds__(256) rans_pack_kernel(RansPack P) {
     uint8_t *o = P.out + off;
     if (threadIdx.x == 0) {
         const uint32_t w[6] = {nh, nl, P.model, P.meta_h[b].checksum + P.meta_l[b].checksum, eh, el};
-        o[0] = 'C'; o[1] = 'D'; o[2] = 'C'; o[3] = P.rates ? 4 : 3; o[4] = (uint8_t)P.arith; o[5] = 0;
+        o[0] = 'C'; o[1] = 'D'; o[2] = 'C'; o[3] = (P.rates ? 4 : 3) + (sized ? 2 : 0); o[4] = (uint8_t)P.arith; o[5] = 0;
         o[6] = (uint8_t)(P.hh & 255); o[7] = (uint8_t)(P.hh >> 8); o[8] = (uint8_t)(P.wh & 255); o[9] = (uint8_t)(P.wh >> 8);
         for (int k = 0; k < 6; ++k) for (int q = 0; q < 4; ++q) o[10 + 4 * k + q] = (uint8_t)(w[k] >> (8 * q));
         if (P.rates) { const uint32_t r = __float_as_uint(P.rates[b]); for (int q = 0; q < 4; ++q) o[34 + q] = (uint8_t)(r >> (8 * q)); }
+        if (sized) for (int q = 0; q < 4; ++q) { o[hdr - 8 + q] = (uint8_t)((uint32_t)P.img_h >> (8 * q)); o[hdr - 4 + q] = (uint8_t)((uint32_t)P.img_w >> (8 * q)); }
     }
     o += hdr;
     const uint8_t *sh = P.sec_h + (long long)b * P.out_bs_h + P.meta_h[b].start, *sl = P.sec_l + (long long)b * P.out_bs_l + P.meta_l[b].start;

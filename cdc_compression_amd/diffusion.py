@@ -8,12 +8,16 @@
 `decompress()` is the decode half alone (context pyramid in, reconstruction out).  The N-step
 loop runs inside libcdc_hip.so (cdc_decode); eta != 0 falls back to per-step cdc_ddim_step
 calls because the reference draws torch.randn_like on the host RNG every step.
+
+Images of any size (cdc_compression_amd.frame states the rule): `compress`, `compress_to_bytes` and `decompress` pad on the device to
+the model's multiple, run on the padded frame and return the top-left `[B, 3, H, W]` window, bpp over `H * W`.  `p_sample_loop`
+mirrors the reference's method and keeps requiring frame sizes (`padded_size(H, W)` tells them).
 """
 import ctypes
 
 import numpy as np
 
-from . import _lib
+from . import _lib, frame
 from .schedule import SampleSchedule
 from .unet import _Arg, _current_stream, _is_torch, _result_like
 
@@ -53,6 +57,33 @@ class _GaussianDiffusionBase:
         if cf and hasattr(self.context_fn, "load_state_dict"):
             self.context_fn.load_state_dict(cf, strict=strict)
         return self
+
+    # ---- images of any size -------------------------------------------------------------------
+    def padded_size(self, H, W):
+        """(Hp, Wp) of the frame an H x W image runs on: rounded up to the least common multiple of what the U-Net and the
+        context model need (cdc_padded_size of their handles; 64 for both published configurations)."""
+        hs = [self.denoise_fn._handle()]
+        if hasattr(self.context_fn, "_enc_handle"):
+            hs.append(self.context_fn._enc_handle())
+        return frame.padded_size(hs, H, W)
+
+    def _compress(self, images, sample_steps, init, eta, loop, *ctx_args):
+        """compress() of both trees: context model and sampler on the padded frame, the window of the image back."""
+        B, _, H, W = frame.image_shape(images)
+        Hp, Wp = self.padded_size(H, W)
+        h, dev = self.denoise_fn._handle(), self.denoise_fn.device_index
+        if hasattr(self.context_fn, "_framed"):              # this package's compressor: pads itself, bpp over H * W
+            context_dict = self.context_fn(images, *ctx_args, padded_hw=(Hp, Wp))        # x :216, eps :205
+        elif (Hp, Wp) == (H, W) and not frame.is_uint8(images):
+            context_dict = self.context_fn(images, *ctx_args)
+        else:                                                # any other context_fn sees the frame; its bpp counts the frame's pixels
+            context_dict = dict(self.context_fn(frame.pad(h, images, Hp, Wp, dev), *ctx_args))
+            context_dict["bpp"] = context_dict["bpp"] * ((Hp * Wp) / (H * W))
+        self.set_sample_schedule(self.num_timesteps if sample_steps is None else sample_steps)
+        rec = loop((B, 3, Hp, Wp), context_dict["output"], frame.extend_init(h, init, B, H, W, Hp, Wp, dev))
+        if (Hp, Wp) != (H, W):
+            rec = frame.crop(h, rec, H, W, dev)
+        return rec, context_dict["bpp"]
 
     # ---- schedule ---------------------------------------------------------------------------
     def set_sample_schedule(self, sample_steps, device=None):
@@ -132,19 +163,26 @@ class _GaussianDiffusionBase:
                 img = out.copy()
         return img
 
-    def decompress(self, context, shape, sample_steps=None, init=None, eta=0, clip_denoised=None, bitrate_scale=None):
+    def decompress(self, context, shape=None, sample_steps=None, init=None, eta=0, clip_denoised=None, bitrate_scale=None,
+                   as_uint8=False):
         """Decode half of compress(): context pyramid (= context_fn(...)["output"]) -> image.  `context`
         may also be the transmitted q_latent tensor [B, C, H/16, W/16]: it then goes through
         `context_fn.decode` first (compress_modules.py:68-74; cdc_compression_amd.compressor on the GPU) -- with
         `bitrate_scale` (1 or B values) for a variable-bitrate context model -- or the entropy-coded streams, whose
-        variable-bitrate form carries each image's rate itself."""
+        variable-bitrate form carries each image's rate itself.
+        shape: [B, 3, H, W] of the images.  None: what the streams record (container version 5 / 6), else the coded extent (the
+        finest context level).  A shape the context cannot belong to -- larger than the coded extent, or a whole multiple or
+        more smaller -- or one that contradicts the size the streams record is an error.  The reconstruction is the frame's top-left H x W window.
+        as_uint8: the uint8 image the reference's script saves (clamp(-1, 1) / 2 + 0.5, then save_image's rounding), made on the device."""
+        recorded = None
         if isinstance(context, (bytes, bytearray)):
             context = [context]
         if isinstance(context, (list, tuple)) and context and isinstance(context[0], (bytes, bytearray)):
             # entropy-coded bitstreams (compress_to_bytes): range-ANS decode -> q_latent (+ the rates of a VBR model)
             if bitrate_scale is not None:
                 raise ValueError("the streams carry their own bitrate_scale")
-            context, bitrate_scale = self.context_fn.decompress_from_bytes(context, like=init, return_bitrate_scale=True)
+            context, bitrate_scale, recorded = self.context_fn.decompress_from_bytes(context, like=init, return_bitrate_scale=True,
+                                                                                     return_image_size=True)
         if not isinstance(context, (list, tuple)):
             if self.context_fn is None or not hasattr(self.context_fn, "decode"):
                 raise RuntimeError("decompress(q_latent, ...) needs a context_fn with decode()")
@@ -152,13 +190,29 @@ class _GaussianDiffusionBase:
         self.set_sample_schedule(self.num_timesteps if sample_steps is None else sample_steps)
         if clip_denoised is None:
             clip_denoised = True if self._param == "x" else getattr(self, "clip_noise", "none")
-        return self._loop(tuple(shape), context, clip_denoised, init, eta)
+        B, _, Hp, Wp = (int(d) for d in context[0].shape)          # the coded extent: the finest context level
+        H, W = recorded if recorded is not None else ((Hp, Wp) if shape is None else (int(shape[2]), int(shape[3])))
+        if shape is not None and tuple(int(d) for d in shape) != (B, 3, H, W):
+            raise _lib.CdcError(f"shape {tuple(shape)} contradicts the context, which holds {B} image(s) of {H} x {W}")
+        M = self.padded_size(1, 1)[0]                               # the frame of an image is less than one multiple larger than it
+        if not (0 <= Hp - H < M and 0 <= Wp - W < M):
+            raise _lib.CdcError(f"a {H} x {W} image does not pad to the {Hp} x {Wp} frame of the context (multiple {M})")
+        h, dev = self.denoise_fn._handle(), self.denoise_fn.device_index
+        rec = self._loop((B, 3, Hp, Wp), context, clip_denoised, frame.extend_init(h, init, B, H, W, Hp, Wp, dev), eta)
+        if (Hp, Wp) != (H, W) or as_uint8:
+            rec = frame.crop(h, rec, H, W, dev, as_uint8=as_uint8)
+        return rec
 
 
     def compress_to_bytes(self, images, bitrate_scale=None):
         """The transmitted half of compress(): images -> one entropy-coded bitstream per image.
         `decompress(streams, shape, sample_steps, init)` reconstructs from them.  bitrate_scale: the rate of a
-        variable-bitrate context model (1 or B values), recorded in each stream."""
+        variable-bitrate context model (1 or B values), recorded in each stream.  Images of any size: a stream records H x W
+        unless the image is its own padded frame."""
+        _, _, H, W = frame.image_shape(images)
+        if self.padded_size(H, W) != self.context_fn.padded_size(H, W):
+            raise NotImplementedError("the stream records the image size against the context model's own multiple: a U-Net that needs a "
+                                      f"larger one ({self.padded_size(H, W)} against {self.context_fn.padded_size(H, W)}) cannot share it")
         if bitrate_scale is None:
             return self.context_fn.compress_to_bytes(images)
         return self.context_fn.compress_to_bytes(images, bitrate_scale)
@@ -183,11 +237,8 @@ class GaussianDiffusionX(_GaussianDiffusionBase):
         return self._loop(tuple(shape), context, clip_denoised, init, eta)
 
     def compress(self, images, sample_steps=None, bpp_return_mean=True, init=None, eta=0):
-        context_dict = self.context_fn(images)                                      # :216
-        self.set_sample_schedule(self.num_timesteps if sample_steps is None else sample_steps)
-        rec = self.p_sample_loop(tuple(images.shape), context_dict["output"], clip_denoised=True,
-                                 init=init, eta=eta)                                  # :223
-        bpp = context_dict["bpp"]
+        rec, bpp = self._compress(images, sample_steps, init, eta,
+                                  lambda shape, ctx, i: self.p_sample_loop(shape, ctx, clip_denoised=True, init=i, eta=eta))   # :223
         return rec, (bpp.mean() if bpp_return_mean else bpp)
 
 
@@ -213,9 +264,6 @@ class GaussianDiffusionEps(_GaussianDiffusionBase):
 
     def compress(self, images, sample_steps=None, bitrate_scale=None, sample_mode="ddpm",
                  bpp_return_mean=True, init=None, eta=0):
-        context_dict = self.context_fn(images, bitrate_scale)                        # :205
-        self.set_sample_schedule(self.num_timesteps if sample_steps is None else sample_steps)
-        rec = self.p_sample_loop(tuple(images.shape), context_dict["output"], sample_mode, init=init,
-                                 eta=eta)
-        bpp = context_dict["bpp"]
+        rec, bpp = self._compress(images, sample_steps, init, eta,
+                                  lambda shape, ctx, i: self.p_sample_loop(shape, ctx, sample_mode, init=i, eta=eta), bitrate_scale)
         return rec, (bpp.mean() if bpp_return_mean else bpp)

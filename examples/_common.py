@@ -12,18 +12,18 @@ if ROOT not in sys.path:
 
 
 def read_image(path, device):
-    """torchvision.io.read_image(path).unsqueeze(0).float() / 255  ->  [1, 3, H, W] in [0, 1]."""
+    """torchvision.io.read_image(path).unsqueeze(0)  ->  uint8 [1, 3, H, W] on `device`, any H and W (the library converts it,
+    `/ 255 * 2 - 1` as the reference's script, and pads it on the device)."""
     import torch
     from PIL import Image
     a = np.asarray(Image.open(path).convert("RGB"), dtype=np.uint8)
-    return torch.from_numpy(a.transpose(2, 0, 1).copy()).unsqueeze(0).float().to(device) / 255.0
+    return torch.from_numpy(a.transpose(2, 0, 1).copy()).unsqueeze(0).to(device)
 
 
-def save_image(t, path):
-    """torchvision.utils.save_image for one [1, 3, H, W] tensor in [0, 1]: x*255 + 0.5, clamp, uint8."""
+def save_image(u8, path):
+    """One uint8 [1, 3, H, W] image (what torchvision.utils.save_image writes: the library's uint8 form does its rounding)."""
     from PIL import Image
-    a = (t[0].detach().float().cpu() * 255.0 + 0.5).clamp(0, 255).to(dtype=__import__("torch").uint8).numpy()
-    Image.fromarray(a.transpose(1, 2, 0)).save(path)
+    Image.fromarray(u8[0].detach().cpu().numpy().transpose(1, 2, 0)).save(path)
 
 
 def ema_model_state(ema_state):
@@ -50,14 +50,15 @@ def synthetic_state(diffusion, seed_unet=0, seed_ctx=15, eps=False):
         sd["denoise_fn." + k] = v
     comp = diffusion.context_fn
     man = comp.manifest() + comp.hyper_manifest() + comp.encoder_manifest()
-    csd = synth.unet_state_dict(man, seed=seed_ctx)
+    # FlexiblePrior entries in the reference's shapes (network_components.py:316-336; dims 1-3-3-3-1): with them the state is the one
+    # the parity fixtures were made with (tests/golden: synth.unet_state_dict over the reference compressor's state_dict names)
     C0 = comp.reversed_hyper_dims[0]
     pd = (1, 3, 3, 3, 1)
     for i in range(4):
-        csd[f"prior.affine.{i}.weight"] = synth.normal(f"pw{i}", (C0, 1, 1, pd[i], pd[i + 1]), seed_ctx, 1.0)
-        csd[f"prior.affine.{i}.bias"] = synth.normal(f"pb{i}", (C0, 1, 1, 1, pd[i + 1]), seed_ctx, 0.1)
+        man += [(f"prior.affine.{i}.weight", (C0, 1, 1, pd[i], pd[i + 1])), (f"prior.affine.{i}.bias", (C0, 1, 1, 1, pd[i + 1]))]
         if i < 3:
-            csd[f"prior.a.{i}"] = synth.normal(f"pa{i}", (C0, 1, 1, 1, pd[i + 1]), seed_ctx, 0.5)
+            man.append((f"prior.a.{i}", (C0, 1, 1, 1, pd[i + 1])))
+    csd = synth.unet_state_dict(man, seed=seed_ctx)
     csd["prior._medians"] = np.zeros((1, C0, 1, 1), np.float32)
     for k, v in csd.items():
         sd["context_fn." + k] = v
@@ -65,21 +66,31 @@ def synthetic_state(diffusion, seed_unet=0, seed_ctx=15, eps=False):
 
 
 def run_folder(diffusion, config, rank, compress_kwargs):
-    """The per-image loop of both reference scripts (test_xparam.py:72-84 / test_epsilonparam.py:67-80)."""
+    """The per-image loop of both reference scripts (test_xparam.py:72-84 / test_epsilonparam.py:67-80), for images of any size:
+    the uint8 image goes straight to compress(), which pads it on the device and returns the H x W reconstruction; the saved
+    image is that reconstruction in the library's uint8 form (clamp(-1, 1) / 2 + 0.5, then save_image's rounding)."""
     import torch
+    from cdc_compression_amd import frame, synth
     if getattr(config, "seed", None) is not None:
         torch.manual_seed(config.seed)
     for img in sorted(os.listdir(config.img_dir)):
         if img.endswith(".png") or img.endswith(".jpg"):
             to_be_compressed = read_image(os.path.join(config.img_dir, img), rank)
+            shape = tuple(to_be_compressed.shape)
+            if os.environ.get("CDC_SYNTHETIC_INIT"):        # seed of a device-independent start noise (the parity fixtures' generator)
+                init = torch.from_numpy(synth.normal("init", shape, seed=int(os.environ["CDC_SYNTHETIC_INIT"]),
+                                                     std=config.gamma)).to(to_be_compressed.device)
+            else:
+                init = torch.randn(shape, device=to_be_compressed.device) * config.gamma
             compressed, bpp = diffusion.compress(
-                to_be_compressed * 2.0 - 1.0,
+                to_be_compressed,
                 sample_steps=config.n_denoise_step,
-                init=torch.randn_like(to_be_compressed) * config.gamma,
+                init=init,
                 **compress_kwargs,
             )
-            compressed = compressed.clamp(-1, 1) / 2.0 + 0.5
+            un = diffusion.denoise_fn
+            compressed = frame.crop(un._handle(), compressed, shape[2], shape[3], un.device_index, as_uint8=True)
             pathlib.Path(config.out_dir).mkdir(parents=True, exist_ok=True)
-            save_image(compressed.cpu(), os.path.join(config.out_dir, img))
+            save_image(compressed, os.path.join(config.out_dir, img))
             print("image:", img)
             print("bpp:", bpp)

@@ -273,7 +273,8 @@ int cdc_bpp(cdc_handle *h, const float *q_hyper_latent, const float *q_latent, c
  * Synchronous; latent / hyper_latent / q_latent / q_hyper_latent follow `mem`, in / out / offsets / medians are host. */
 int cdc_entropy_encode(cdc_handle *h, const float *latent, const float *hyper_latent, const float *medians, int B,
                        int h_hyper, int w_hyper, unsigned char *out, size_t cap, size_t *offsets, int mem_kind, void *stream);
-/* Header fields of a version-3 or version-4 stream (CDC_ERR_INVALID for anything else). */
+/* Header fields of a version-3, -4, -5 or -6 stream (CDC_ERR_INVALID for anything else, a version-5 / -6 header whose recorded
+ * image size is 0 or beyond 2^31 - 1 on either side included: every peek below refuses what this one refuses). */
 int cdc_entropy_peek(const unsigned char *in, size_t n, int *h_hyper, int *w_hyper, int *arith);
 /* A stream header sizes the decoder's allocations and its hyper_dec launch program (up to 2^22 positions = a 131072 x 131072
  * image: tens of GB on a 288 GB part).  A caller that knows what it expects bounds that BEFORE decoding untrusted bytes: streams whose
@@ -308,6 +309,58 @@ int cdc_entropy_decode(cdc_handle *h, const unsigned char *in, const size_t *off
 int cdc_enable_vbr(cdc_handle *h);
 int cdc_set_bitrate_scale(cdc_handle *h, const float *cond, int n);
 int cdc_entropy_peek_bitrate_scale(const unsigned char *in, size_t n, int *has_scale, float *scale);
+
+/* ---- images of any size (no reference counterpart: the reference's torch.cat sites fail unless H and W are multiples of 64) ------
+ * THE RULE, fixed so that encoder and decoder agree: with M the least common multiple of what the model's parts need (2^(levels-1)
+ * of the U-Net, 2^(n_dim_mults + n_hyper_mults - 1) of the compressor; 64 for both published configurations), the model runs on the
+ * frame Hp x Wp = ceil(H / M) M x ceil(W / M) M whose pixel (y, x) is pixel (min(y, H-1), min(x, W-1)) of the image -- padding at the
+ * bottom and the right by edge replication, torch.nn.functional.pad(mode="replicate"); reflection is undefined once the margin
+ * exceeds the side -- and the result is the frame's top-left H x W window.  Start noise given at H x W is extended with zeros; bpp
+ * counts bits over H * W (cdc_bpp with H_img = H, W_img = W); eta != 0 draws its noise at the padded shape.
+ *
+ * cdc_padded_size: (Hp, Wp) of an H x W image for the handle's own part of the model: a U-Net handle rounds up to 2^(n_dim_mults-1),
+ *   an encoder handle to 2^(n_dim_mults + n_hyper_mults - 1), a context-decoder handle to 2^n_rev_mults, a hyper-decoder handle to
+ *   the value of cdc_entropy_set_image_scale (CDC_ERR_STATE before it).  A model's M is the largest of its handles' (all are
+ *   powers of two), so no caller hard-codes 64.
+ * cdc_frame_pad: src [B][3][H][W] -> dst [B][3][Hp][Wp] float32 in one pass (csrc/frame_kernels.hip).  elem_kind of src:
+ *   CDC_ELEM_F32 (already in [-1, 1]; copied bit for bit) or CDC_ELEM_U8 (torchvision.io.read_image layout), converted as
+ *   float(v) / 255.0 * 2.0 - 1.0 in that operation order (xparam/test_xparam.py:74,76; epsilonparam/test_epsilonparam.py:69):
+ *   bit for bit what torch computes.  fill_mode CDC_FILL_EDGE is the rule above; CDC_FILL_ZERO writes 0 outside the image (the
+ *   extension of the start noise).  Hp = H and Wp = W is allowed (a plain copy / conversion).
+ * cdc_frame_crop: src [B][3][Hp][Wp] float32 -> dst [B][3][H][W], the top-left window: CDC_ELEM_F32 bit for bit, or CDC_ELEM_U8 as
+ *   the reference script saves it: clamp(x, -1, 1) / 2.0 + 0.5 (xparam/test_xparam.py:81; epsilonparam/test_epsilonparam.py:77), then
+ *   torchvision.utils.save_image's * 255 + 0.5, clamp to [0, 255], truncation (:83) -- each operation rounded on its own, as torch's.
+ * Both take any handle kind (they use its device, stream and error state only) and run through the same guard / error runner as
+ * every entry point; B, H, W < 1, Hp < H or Wp < W -> CDC_ERR_INVALID.  mem_kind / stream as for cdc_unet_forward (both pointers
+ * follow mem_kind; CDC_MEM_HOST stages through device buffers and synchronises).
+ *
+ * STREAMS of an image that is not its own padded size are container version 5 (fixed rate) / 6 (variable bitrate): the version-3 /
+ * version-4 header byte for byte with version byte 5 / 6, followed -- after the bitrate_scale of version 6 -- by
+ * img_h u32 | img_w u32 (little endian; bytes 34-41 of version 5, 38-45 of version 6); the sections start 8 bytes later.
+ * cdc_entropy_set_image_scale: D = image pixels per hyper-latent position and side (2^(n_dim_mults + n_hyper_mults - 1) of the
+ *   model the hyper decoder belongs to, which the handle's own configuration does not tell); needed by the two calls below.
+ * cdc_entropy_encode_image: cdc_entropy_encode with the size of the original image.  D (h_hyper - 1) < img_h <= D h_hyper and
+ *   likewise the width are required (CDC_ERR_INVALID).  An image that is its own padded size gets exactly the version-3 / -4
+ *   bytes of cdc_entropy_encode; any other the version-5 / -6 stream.  cdc_entropy_encode itself is unchanged.
+ * cdc_entropy_decode accepts versions 3 and 5 on a fixed-rate handle and 4 and 6 on a variable-bitrate handle; the streams of one
+ *   call share latent size and recorded size.  Before anything is allocated a version-5 / -6 header must satisfy the same
+ *   inequalities (the recorded size pads to exactly the coded extent; img_h = 0, one row beyond or one block short are refused),
+ *   and cdc_entropy_set_limit applies as before.  The latents it returns are those of the padded frame: the caller decodes
+ *   D h_hyper x D w_hyper pixels and crops (cdc_frame_crop) to the recorded size.
+ * cdc_entropy_peek_image_size: handle-free; *has_size = 1 and the recorded size for versions 5 / 6, *has_size = 0 for 3 / 4
+ *   (the image is the coded extent); CDC_ERR_INVALID for anything else. */
+enum { CDC_ELEM_F32 = 0, CDC_ELEM_U8 = 1 };
+enum { CDC_FILL_EDGE = 0, CDC_FILL_ZERO = 1 };
+int cdc_padded_size(cdc_handle *h, int H, int W, int *Hp, int *Wp);
+int cdc_frame_pad(cdc_handle *h, const void *src, float *dst, int B, int H, int W, int Hp, int Wp, int elem_kind, int fill_mode,
+                  int mem_kind, void *stream);
+int cdc_frame_crop(cdc_handle *h, const float *src, void *dst, int B, int H, int W, int Hp, int Wp, int elem_kind, int mem_kind,
+                   void *stream);
+int cdc_entropy_set_image_scale(cdc_handle *h, int pixels_per_position);
+int cdc_entropy_encode_image(cdc_handle *h, const float *latent, const float *hyper_latent, const float *medians, int B,
+                             int h_hyper, int w_hyper, int img_h, int img_w, unsigned char *out, size_t cap, size_t *offsets,
+                             int mem_kind, void *stream);
+int cdc_entropy_peek_image_size(const unsigned char *in, size_t n, int *has_size, int *img_h, int *img_w);
 
 /* quantize(x, "dequantize", offset) = round(x - offset) + offset, round = half-to-even (utils.py:72-85). */
 int cdc_dequantize(cdc_handle *h, const float *x, const float *offset, float *out, long long n, int mem_kind,
