@@ -130,6 +130,11 @@ def lib():
     L.cdc_ddim_step.argtypes = [H, _vp, _i, pp, _i, _vp, ctypes.c_float, _vp, _i, _i, _i, _i, _i,
                                 _i, _vp]
     L.cdc_decode.argtypes = [H, _vp, pp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp]
+    u64p = ctypes.POINTER(ctypes.c_uint64)
+    L.cdc_decode_seeded.argtypes = [H, _vp, ctypes.c_float, u64p, ctypes.c_float, pp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp]
+    L.cdc_randn.argtypes = [H, u64p, _i, ctypes.c_int64, ctypes.c_uint32, ctypes.c_float, _vp, _i, _vp]
+    L.cdc_randn_host.argtypes = [u64p, _i, ctypes.c_int64, ctypes.c_uint32, ctypes.c_float, _vp]
+    L.cdc_philox4x32_10.argtypes = [ctypes.POINTER(ctypes.c_uint32)] * 3
     L.cdc_prof_enable.argtypes = [H, _i]
     L.cdc_prof_name.argtypes = [_i]
     L.cdc_prof_name.restype = ctypes.c_char_p
@@ -164,7 +169,7 @@ EXPORTS = ["cdc_create", "cdc_destroy", "cdc_last_error", "cdc_version", "cdc_nu
            "cdc_get_nonfinite_results", "cdc_set_schedule_v", "cdc_probe_mfma_f16", "cdc_probe_hbm_copy",
            "cdc_op_stress", "cdc_op_stress_result", "cdc_enable_vbr", "cdc_set_bitrate_scale", "cdc_entropy_peek_bitrate_scale",
            "cdc_padded_size", "cdc_frame_pad", "cdc_frame_crop", "cdc_entropy_set_image_scale", "cdc_entropy_encode_image",
-           "cdc_entropy_peek_image_size"]
+           "cdc_entropy_peek_image_size", "cdc_decode_seeded", "cdc_randn", "cdc_randn_host", "cdc_philox4x32_10"]
 
 
 def handle_status(handle):

@@ -6,6 +6,7 @@
 #include <stdlib.h>
 
 #include "cdc_internal.h"
+#include "rng.h"
 
 namespace cdc {
 
@@ -1401,6 +1402,9 @@ __device__ __forceinline__ float ddim_update(const DdimConsts &k, float fx, floa
     return xn;
 }
 
+// SEEDED: the step's noise comes from the generator of rng.h (DdimArgs::seeds), draw number = step index + 1, instead of a tensor.  A
+// compile-time instance of its own, so that the eta = 0 / noise-tensor kernels keep the code they had.
+template <bool SEEDED>
 __global__ void __launch_bounds__(256) ddim_kernel(const DdimArgs a) {
     const int si = a.step_ptr ? *a.step_ptr : a.i;
     const float c_recip = a.tab[0 * a.steps + si];
@@ -1436,6 +1440,15 @@ __global__ void __launch_bounds__(256) ddim_kernel(const DdimArgs a) {
         }
         const float x = a.x[idx];
         bad |= !(fabsf(fx) <= 3.0e38f);                    // inf / NaN from the U-Net (fp16-plane range overflow)
+        if constexpr (SEEDED) {
+            // the quad of this element, then its lane (frames whose width is no multiple of 4: ddim_rows4_kernel's draws, one by one)
+            const long long b = idx / a.per_image, e = idx - b * a.per_image;
+            float z[4];
+            cdcrng::normal4(a.seeds[b], (uint32_t)(e >> 2), (uint32_t)si + 1u, z);
+            const int lane = (int)(e & 3);
+            const float nz = lane == 0 ? z[0] : lane == 1 ? z[1] : lane == 2 ? z[2] : z[3];
+            a.x_next[idx] = ddim_update(kc, fx, x, nz, idx < clip_n, true);
+        } else
         a.x_next[idx] = ddim_update(kc, fx, x, a.noise ? a.noise[idx] : 0.f, idx < clip_n, a.noise != nullptr);
     }
     if (bad && a.fault) *a.fault = 1;                      // sticky, read by the host after the decode
@@ -1445,6 +1458,7 @@ __global__ void __launch_bounds__(256) ddim_kernel(const DdimArgs a) {
 // 16-byte loads / stores, the (image, channel) index is blockIdx.y.  ddim_kernel's element loop derives (plane, pixel) from a 64-bit
 // element index -- two 64-bit divisions per element made it VALU-bound (90 us per launch at batch 32 for 0.23 GB of traffic).
 // Same sums in the same order, same expressions per component: same bits.
+template <bool SEEDED>
 __global__ void __launch_bounds__(256) ddim_rows4_kernel(const DdimArgs a) {
     const int si = a.step_ptr ? *a.step_ptr : a.i;
     const float c_recip = a.tab[0 * a.steps + si];
@@ -1475,6 +1489,12 @@ __global__ void __launch_bounds__(256) ddim_rows4_kernel(const DdimArgs a) {
     const float4 x4 = *reinterpret_cast<const float4 *>(a.x + idx);
     const float xs[4] = {x4.x, x4.y, x4.z, x4.w};
     float nz[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (SEEDED) {
+        // one Philox call: the four normals of these four pixels (plane % 4 == 0, so they are one quad of the image's own tensor)
+        const int b = img_co / a.pC;
+        const long long e = (long long)(img_co - b * a.pC) * plane + pix;
+        cdcrng::normal4(a.seeds[b], (uint32_t)(e >> 2), (uint32_t)si + 1u, nz);
+    } else
     if (a.noise) { const float4 n4 = *reinterpret_cast<const float4 *>(a.noise + idx); nz[0] = n4.x; nz[1] = n4.y; nz[2] = n4.z; nz[3] = n4.w; }
     const bool clip = idx < clip_n;                       // (clip_n is a whole number of images)
     const DdimConsts kc{c_recip, c_recipm1, c_acp, c_eps, c_sac, c_s1mac, sig, a.pred_mode};
@@ -1483,7 +1503,7 @@ __global__ void __launch_bounds__(256) ddim_rows4_kernel(const DdimArgs a) {
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         bad |= !(fabsf(fx[c]) <= 3.0e38f);
-        out[c] = ddim_update(kc, fx[c], xs[c], nz[c], clip, a.noise != nullptr);
+        out[c] = ddim_update(kc, fx[c], xs[c], nz[c], clip, SEEDED || a.noise != nullptr);
     }
     *reinterpret_cast<float4 *>(a.x_next + idx) = make_float4(out[0], out[1], out[2], out[3]);
     if (bad && a.fault) *a.fault = 1;
@@ -1501,11 +1521,46 @@ hipError_t ddim_launch(const DdimArgs &a, hipStream_t st) {
     const long long plane = (long long)a.pH * a.pW;
     if (a.P && plane > 0 && (a.pW & 3) == 0 && plane < (1ll << 30) && a.n % plane == 0 && a.n / plane <= 65535 &&
         (((uintptr_t)a.P | (uintptr_t)a.x | (uintptr_t)a.x_next | (uintptr_t)a.noise) & 15) == 0) {
-        hipLaunchKernelGGL(ddim_rows4_kernel, dim3((unsigned)ceil_div(plane / 4, 256), (unsigned)(a.n / plane)), dim3(256), 0, st, a);
+        const dim3 g((unsigned)ceil_div(plane / 4, 256), (unsigned)(a.n / plane));
+        if (a.seeds) hipLaunchKernelGGL(ddim_rows4_kernel<true>, g, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(ddim_rows4_kernel<false>, g, dim3(256), 0, st, a);
         return hipGetLastError();
     }
     const int grid = (int)std::min<long long>((a.n + 255) / 256, 4096);
-    hipLaunchKernelGGL(ddim_kernel, dim3(grid), dim3(256), 0, st, a);
+    if (a.seeds) hipLaunchKernelGGL(ddim_kernel<true>, dim3(grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(ddim_kernel<false>, dim3(grid), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+// out[b][e] = scale * z(seeds[b], draw, e): the start image of a seeded decode and cdc_randn.  One quad of rng.h per thread; a
+// 16-byte store where every image starts on a 16-byte boundary (per_image % 4 == 0), element stores with a bound otherwise.
+template <bool VEC>
+__global__ void __launch_bounds__(256) randn_fill_kernel(const unsigned long long *seeds, long long per_image, unsigned draw,
+                                                         float scale, float *out) {
+    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (4 * q >= per_image) return;
+    const int b = blockIdx.y;
+    float z[4];
+    cdcrng::normal4(seeds[b], (uint32_t)q, draw, z);
+    float *o = out + (size_t)b * per_image + 4 * q;
+    if constexpr (VEC) {
+        *reinterpret_cast<float4 *>(o) = make_float4(scale * z[0], scale * z[1], scale * z[2], scale * z[3]);
+    } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (4 * q + c < per_image) o[c] = scale * z[c];
+    }
+}
+
+hipError_t randn_fill_launch(const unsigned long long *seeds, int B, long long per_image, unsigned draw, float scale, float *out,
+                             hipStream_t st) {
+    const long long nq = (per_image + 3) / 4;
+    if (B < 1 || B > 65535 || per_image < 1 || nq > (1ll << 32)) return hipErrorInvalidValue;
+    const dim3 g((unsigned)((nq + 255) / 256), (unsigned)B);
+    if ((per_image & 3) == 0 && ((uintptr_t)out & 15) == 0)
+        hipLaunchKernelGGL(randn_fill_kernel<true>, g, dim3(256), 0, st, seeds, per_image, draw, scale, out);
+    else
+        hipLaunchKernelGGL(randn_fill_kernel<false>, g, dim3(256), 0, st, seeds, per_image, draw, scale, out);
     return hipGetLastError();
 }
 

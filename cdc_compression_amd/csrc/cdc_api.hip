@@ -3,6 +3,7 @@
 // programs and the profiling tables.  Parameter repacking: cdc_weights.hip; the launch-program builder: cdc_planner.hip; the entropy
 // coder's entry points: cdc_entropy_api.hip; shared types: cdc_state.h.
 #include "cdc_state.h"
+#include "rng.h"
 
 namespace cdcapi {
 
@@ -340,6 +341,7 @@ void cdc_destroy(cdc_handle *h) {
     if (h->d_tab_v) (void)hipFree(h->d_tab_v);
     if (h->d_time_steps) (void)hipFree(h->d_time_steps);
     if (h->d_shift_tab) (void)hipFree(h->d_shift_tab);
+    if (h->d_seeds) (void)hipFree(h->d_seeds);
     (void)resolve_pending(h);
     for (hipEvent_t e : h->ev_free) (void)hipEventDestroy(e);
     if (h->gev_in) (void)hipEventDestroy(h->gev_in);
@@ -833,7 +835,7 @@ int cdc_set_schedule_v(cdc_handle *h, int steps, const float *sqrt_ac, const flo
 
 static int ddim_on_device(cdc_handle *h, const float *x_in, int i, const float *noise, float eta,
                           float *x_out, int B, int H, int W, int pred_mode, int clip,
-                          hipStream_t st) {
+                          hipStream_t st, const unsigned long long *seeds = nullptr) {
     int rc;
     const size_t n = (size_t)B * h->cfg.channels * H * W;
     if (x_in != h->in_x)
@@ -852,6 +854,7 @@ static int ddim_on_device(cdc_handle *h, const float *x_in, int i, const float *
         op.ddim.P = cb->cb.P; op.ddim.P_bias = cb->cb.bias; op.ddim.pC = cb->cb.Cout; op.ddim.pKH = cb->cb.KH; op.ddim.pPad = cb->cb.pad;
         op.ddim.pH = cb->cb.H; op.ddim.pW = cb->cb.W;
     }
+    if (eta != 0.f && seeds) { op.ddim.noise = nullptr; op.ddim.seeds = seeds; op.ddim.per_image = (long long)(n / B); }
     op.bytes = 16.0 * n;
     return run_op(h, op, B, st);
 }
@@ -894,8 +897,26 @@ int cdc_ddim_step(cdc_handle *h, const float *x_in, int i, const float *const *c
     });
 }
 
-int cdc_decode(cdc_handle *h, const float *init, const float *const *ctx, int n_ctx, float *out, int B,
-               int H, int W, int pred_mode, int clip, int mem, void *stream) {
+// The per-image seeds of a call into the handle's device array (grow only: a captured graph holds its address).
+static int stage_seeds(cdc_handle *h, const uint64_t *seeds, int B, hipStream_t st) {
+    if (B > h->seeds_cap) {
+        HIP_TRY(h, hipDeviceSynchronize());
+        if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }   // it baked the old address
+        if (h->d_seeds) { (void)hipFree(h->d_seeds); h->d_seeds = nullptr; h->seeds_cap = 0; }
+        void *p = nullptr;
+        HIP_TRY(h, hipMalloc(&p, sizeof(unsigned long long) * (size_t)B));
+        h->d_seeds = (unsigned long long *)p;
+        h->seeds_cap = B;
+    }
+    HIP_TRY(h, hipStreamSynchronize(st));     // an earlier call's copy out of h_seeds may still be queued
+    h->h_seeds.assign(seeds, seeds + B);
+    HIP_TRY(h, hipMemcpyAsync(h->d_seeds, h->h_seeds.data(), sizeof(unsigned long long) * (size_t)B, hipMemcpyHostToDevice, st));
+    return CDC_OK;
+}
+
+// cdc_decode (seeds null: eta = 0, no generator) and cdc_decode_seeded: one loop.
+static int decode_impl(cdc_handle *h, const float *init, float gamma, const uint64_t *seeds, float eta, const float *const *ctx,
+                       int n_ctx, float *out, int B, int H, int W, int pred_mode, int clip, int mem, void *stream) {
     return with_range_guard(h, [&]() -> int {
         int rc = require_kind(h, HandleKind::Unet);
         if (rc) return rc;
@@ -913,7 +934,16 @@ int cdc_decode(cdc_handle *h, const float *init, const float *const *ctx, int n_
         hipStream_t st = pick_stream(h, stream, mem);
         const size_t n = (size_t)B * h->cfg.channels * H * W;
         if ((rc = arm_range_guard(h, st, true))) return rc;
+        // the generator is needed for the start image (no init, gamma != 0) and for the steps (eta != 0); the BF16X3 repetition of
+        // a range fault comes through here again and regenerates both from the seeds
+        const bool gen_init = seeds && !init && gamma != 0.f;
+        const unsigned long long *dseeds = nullptr;
+        if (seeds && (gen_init || eta != 0.f)) {
+            if ((rc = stage_seeds(h, seeds, B, st))) return rc;
+            dseeds = h->d_seeds;
+        }
         if (init) { if ((rc = copy_in(h, h->in_x, init, n, mem, st))) return rc; }
+        else if (gen_init) HIP_TRY(h, randn_fill_launch(dseeds, B, (long long)(n / B), 0u, gamma, h->in_x, st));
         else HIP_TRY(h, hipMemsetAsync(h->in_x, 0, n * sizeof(float), st));
         if ((rc = stage_ctx(h, ctx, n_ctx, B, mem, st))) return rc;
         h->prof_now = false;
@@ -938,14 +968,16 @@ int cdc_decode(cdc_handle *h, const float *init, const float *const *ctx, int n_
             }
             if (!h->d_step) { void *p = nullptr; HIP_TRY(h, hipMalloc(&p, sizeof(int))); h->d_step = (int *)p; h->weight_allocs.push_back(p); }
             // first iteration eagerly (kernel attributes, code pages), then capture the second and replay it
-            if ((rc = ddim_on_device(h, h->in_x, i, nullptr, 0.f, h->in_x, B, H, W, pred_mode, clip, st))) return rc;
+            if ((rc = ddim_on_device(h, h->in_x, i, nullptr, eta, h->in_x, B, H, W, pred_mode, clip, st, dseeds))) return rc;
             --i;
-            const int key[4] = {h->steps, pred_mode, clip, h->sched_gen};
+            int eta_bits;
+            memcpy(&eta_bits, &eta, sizeof eta_bits);
+            const int key[6] = {h->steps, pred_mode, clip, h->sched_gen, eta_bits, dseeds != nullptr};
             if (!h->graph_exec || memcmp(key, h->graph_key, sizeof key)) {
                 if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
                 hipGraph_t g = nullptr;
                 HIP_TRY(h, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-                rc = ddim_on_device(h, h->in_x, -2, nullptr, 0.f, h->in_x, B, H, W, pred_mode, clip, st);
+                rc = ddim_on_device(h, h->in_x, -2, nullptr, eta, h->in_x, B, H, W, pred_mode, clip, st, dseeds);
                 hipError_t e = rc ? hipSuccess : step_dec_launch(h->d_step, st);
                 hipError_t e2 = hipStreamEndCapture(st, &g);
                 if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
@@ -967,7 +999,7 @@ int cdc_decode(cdc_handle *h, const float *init, const float *const *ctx, int n_
         }
         for (; i >= 0; --i) {
             h->prof_now = (i % h->prof_every) == 0;
-            if ((rc = ddim_on_device(h, h->in_x, i, nullptr, 0.f, h->in_x, B, H, W, pred_mode, clip, st)))
+            if ((rc = ddim_on_device(h, h->in_x, i, nullptr, eta, h->in_x, B, H, W, pred_mode, clip, st, dseeds)))
                 return rc;
         }
         h->prof_now = true;
@@ -976,6 +1008,77 @@ int cdc_decode(cdc_handle *h, const float *init, const float *const *ctx, int n_
         if ((rc = range_check(h, {{h->in_x, 0, (long long)n}}, 1, st))) return rc;
         return copy_out(h, out, h->in_x, n, mem, st);
     });
+}
+
+int cdc_decode(cdc_handle *h, const float *init, const float *const *ctx, int n_ctx, float *out, int B,
+               int H, int W, int pred_mode, int clip, int mem, void *stream) {
+    return decode_impl(h, init, 0.f, nullptr, 0.f, ctx, n_ctx, out, B, H, W, pred_mode, clip, mem, stream);
+}
+
+int cdc_decode_seeded(cdc_handle *h, const float *init, float gamma, const uint64_t *seeds, float eta, const float *const *ctx,
+                      int n_ctx, float *out, int B, int H, int W, int pred_mode, int clip, int mem, void *stream) {
+    if (!h) return CDC_ERR_INVALID;
+    if (!seeds) return fail(h, CDC_ERR_INVALID, "cdc_decode_seeded: null seeds");
+    if (!(fabsf(eta) <= 3.0e38f) || !(fabsf(gamma) <= 3.0e38f)) return fail(h, CDC_ERR_INVALID, "cdc_decode_seeded: eta / gamma not finite");
+    if (B < 1 || B > 65535) return fail(h, CDC_ERR_INVALID, "cdc_decode_seeded: batch %d", B);
+    return no_throw(h, [&] { return decode_impl(h, init, gamma, seeds, eta, ctx, n_ctx, out, B, H, W, pred_mode, clip, mem, stream); });
+}
+
+// ---- the generator behind entry points of its own (rng.h) ---------------------------------------------------------------------
+static int randn_args(cdc_handle *h, const uint64_t *seeds, int B, int64_t per_image, const float *out) {
+    const char *bad = (!seeds || !out) ? "null argument" : (B < 1 || B > 65535) ? "batch outside [1, 65535]"
+                      : (per_image < 1 || per_image > (1ll << 34)) ? "per_image outside [1, 2^34]" : nullptr;
+    if (!bad) return CDC_OK;
+    return h ? fail(h, CDC_ERR_INVALID, "randn: %s", bad) : CDC_ERR_INVALID;
+}
+
+int cdc_randn(cdc_handle *h, const uint64_t *seeds, int B, int64_t per_image, uint32_t draw, float scale, float *out, int mem,
+              void *stream) {
+    if (!h) return CDC_ERR_INVALID;
+    return no_throw(h, [&] {
+        return with_range_guard(h, [&]() -> int {
+            int rc = ensure_device(h);
+            if (rc) return rc;
+            if ((rc = randn_args(h, seeds, B, per_image, out))) return rc;
+            if (mem != CDC_MEM_HOST && mem != CDC_MEM_DEVICE) return fail(h, CDC_ERR_INVALID, "randn: mem_kind %d", mem);
+            hipStream_t st = pick_stream(h, stream, mem);
+            if ((rc = stage_seeds(h, seeds, B, st))) return rc;
+            if (mem == CDC_MEM_DEVICE) {
+                HIP_TRY(h, randn_fill_launch(h->d_seeds, B, per_image, draw, scale, out, st));
+                return CDC_OK;
+            }
+            const size_t n = (size_t)B * (size_t)per_image;
+            DevPool d;
+            float *dd;
+            if (d.get(&dd, n) != hipSuccess) return fail(h, CDC_ERR_NOMEM, "hipMalloc failed");
+            hipError_t e = randn_fill_launch(h->d_seeds, B, per_image, draw, scale, dd, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(out, dd, n * sizeof(float), hipMemcpyDeviceToHost, st);
+            const hipError_t es = hipStreamSynchronize(st);   // (after an error too: nothing queued may still use what d frees)
+            if (e == hipSuccess) e = es;
+            if (e != hipSuccess) return fail(h, CDC_ERR_HIP, "randn: %s", hipGetErrorString(e));
+            return CDC_OK;
+        });
+    });
+}
+
+int cdc_randn_host(const uint64_t *seeds, int B, int64_t per_image, uint32_t draw, float scale, float *out) {
+    int rc = randn_args(nullptr, seeds, B, per_image, out);
+    if (rc) return rc;
+    for (int b = 0; b < B; ++b) {
+        float *o = out + (size_t)b * (size_t)per_image;
+        for (int64_t q = 0; 4 * q < per_image; ++q) {
+            float z[4];
+            cdcrng::normal4(seeds[b], (uint32_t)q, draw, z);
+            for (int c = 0; c < 4 && 4 * q + c < per_image; ++c) o[4 * q + c] = scale * z[c];
+        }
+    }
+    return CDC_OK;
+}
+
+int cdc_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
+    if (!ctr || !key || !out) return CDC_ERR_INVALID;
+    cdcrng::philox4x32_10(ctr[0], ctr[1], ctr[2], ctr[3], key[0], key[1], out);
+    return CDC_OK;
 }
 
 int cdc_prof_enable(cdc_handle *h, int on) {

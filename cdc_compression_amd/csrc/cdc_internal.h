@@ -237,8 +237,16 @@ struct DdimArgs {
     // evaluated inside the sampler kernel (same sum, same order as fold_combine_kernel) instead of being read from `fx`
     const float *P = nullptr, *P_bias = nullptr;
     int pC = 0, pKH = 0, pPad = 0, pH = 0, pW = 0;
+    // The noise of the step: none (noise and seeds null: eta = 0), a tensor (`noise`: cdc_ddim_step), or generated in the kernel
+    // (`seeds` non-null, rng.h): image b draws z(seeds[b], draw = step index + 1, element index inside its own per_image elements);
+    // `noise` is then neither read nor written.
+    const unsigned long long *seeds = nullptr;
+    long long per_image = 0;
 };
 hipError_t ddim_launch(const DdimArgs &a, hipStream_t st);
+// out[b][e] = scale * z(seeds[b], draw, e) for e < per_image (rng.h; seeds on the device); 16-byte stores when the layout allows
+hipError_t randn_fill_launch(const unsigned long long *seeds, int B, long long per_image, unsigned draw, float scale, float *out,
+                             hipStream_t st);
 hipError_t copy_channels_launch(const float *src, long long src_bs, float *dst, long long dst_bs,
                                 long long n, int B, hipStream_t st, int parts = 1, long long part_stride = 0,
                                 const int *step_ptr = nullptr, long long step_stride = 0);

@@ -197,7 +197,11 @@ struct cdc_handle {
     int *d_fault = nullptr;              // sticky "non-finite U-Net output" flag written by the sampler kernel
     hipGraphExec_t graph_exec = nullptr;
     hipEvent_t gev_in = nullptr, gev_out = nullptr;   // order the caller's stream around the graph stream
-    int graph_key[4] = {0, 0, 0, 0};      // steps, pred_mode, clip, stream-independent program generation
+    int graph_key[6] = {0, 0, 0, 0, 0, 0};   // steps, pred_mode, clip, stream-independent program generation, eta's bits, seeded
+    // seeded stochastic decode (cdc_decode_seeded / cdc_randn): the per-image seeds of the running call on the device
+    unsigned long long *d_seeds = nullptr;
+    int seeds_cap = 0;
+    std::vector<unsigned long long> h_seeds;   // staging copy: the caller's array may go away before the copy has run
     int time_steps_B = 0;
     int op_stress_n = 0;                 // cdc_op_stress: extra executions of every cdc_op_* program, results compared on the device
     long long op_stress_launches = 0, op_stress_differing = 0;

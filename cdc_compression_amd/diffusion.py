@@ -9,6 +9,11 @@
 loop runs inside libcdc_hip.so (cdc_decode); eta != 0 falls back to per-step cdc_ddim_step
 calls because the reference draws torch.randn_like on the host RNG every step.
 
+Seeded stochastic decode (no reference counterpart): with `seed=` every draw -- the per-step noise of eta != 0 and, with `gamma=`,
+the start image gamma * randn -- comes from the counter-based generator inside the sampler kernels (cdc_decode_seeded;
+include/cdc_hip.h states the format): same context + same seed => same picture on every host, whatever the batch or the rank.
+seed: an int s (image b takes (s + b) mod 2^64) or B ints in [0, 2^64).  No torch / NumPy generator is touched.
+
 Images of any size (cdc_compression_amd.frame states the rule): `compress`, `compress_to_bytes` and `decompress` pad on the device to
 the model's multiple, run on the padded frame and return the top-left `[B, 3, H, W]` window, bpp over `H * W`.  `p_sample_loop`
 mirrors the reference's method and keeps requiring frame sizes (`padded_size(H, W)` tells them).
@@ -18,6 +23,7 @@ import ctypes
 import numpy as np
 
 from . import _lib, frame
+from .parallel import expand_seeds
 from .schedule import SampleSchedule
 from .unet import _Arg, _current_stream, _is_torch, _result_like
 
@@ -67,6 +73,29 @@ class _GaussianDiffusionBase:
             hs.append(self.context_fn._enc_handle())
         return frame.padded_size(hs, H, W)
 
+    @staticmethod
+    def _seed_args(seed, gamma, init, B=None):
+        """The argument rules of a seeded decode, checked before anything runs: -> the B seeds (None without a seed)."""
+        if gamma is not None and seed is None:
+            raise ValueError("gamma (a start image made on the device) needs a seed")
+        if gamma is not None and init is not None:
+            raise ValueError("gamma and init exclude each other: the start image is either made from the seed or given")
+        if seed is None or B is None:
+            return None
+        return expand_seeds(seed, B)
+
+    def randn(self, seed, shape, draw=0, scale=1.0, like=None):
+        """scale * z(seed_b, draw) of shape [B, ...], made on the device by the generator of the seeded decode (cdc_randn): draw 0 is the
+        start image of `gamma=`, draw i + 1 the noise of sample index i.  A NumPy array, or a torch tensor like `like`."""
+        B = int(shape[0])
+        seeds = np.asarray(expand_seeds(seed, B), dtype=np.uint64)
+        per = int(np.prod([int(d) for d in shape[1:]]))
+        h, dev = self.denoise_fn._handle(), self.denoise_fn.device_index
+        out, optr, omem = _result_like(like if like is not None else np.empty(0, np.float32), tuple(int(d) for d in shape), dev)
+        _lib.check(h, _lib.lib().cdc_randn(h, seeds.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), B, per, int(draw), float(scale),
+                                           optr, omem, _current_stream(omem)))
+        return out
+
     def _compress(self, images, sample_steps, init, eta, loop, *ctx_args):
         """compress() of both trees: context model and sampler on the padded frame, the window of the image back."""
         B, _, H, W = frame.image_shape(images)
@@ -115,10 +144,11 @@ class _GaussianDiffusionBase:
             return {"x": _lib.CDC_PRED_X, "noise": _lib.CDC_PRED_NOISE_XTREE, "v": _lib.CDC_PRED_V}[self.pred_mode]
         return _lib.CDC_PRED_NOISE                        # (the eps tree's ddim ignores pred_mode: eps :137-139)
 
-    def _loop(self, shape, context, clip_denoised, init, eta):
+    def _loop(self, shape, context, clip_denoised, init, eta, seed=None, gamma=None):
+        B, C, H, W = shape
+        seeds = self._seed_args(seed, gamma, init, B)
         L, un = _lib.lib(), self.denoise_fn
         h = un._handle()
-        B, C, H, W = shape
         proto = init if init is not None else context[0]
         dev = un.device_index
         actx = [_Arg(c, dev) for c in context]
@@ -132,10 +162,16 @@ class _GaussianDiffusionBase:
         if omem != mem:
             raise _lib.CdcError("init and context must live in the same memory space")
         stream = _current_stream(mem)
-        if eta == 0:
+        if eta == 0 or seeds is not None:
             ai = _Arg(init, dev) if init is not None else None
             if ai is not None and ai.mem != mem:
                 raise _lib.CdcError("init and context must live in the same memory space")
+            if seeds is not None:      # every draw from the generator in the sampler kernels: any eta stays in the device loop
+                sd = np.asarray(seeds, dtype=np.uint64)
+                _lib.check(h, L.cdc_decode_seeded(h, ai.ptr if ai else None, 0.0 if gamma is None else float(gamma),
+                                                  sd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), float(eta), ptrs, len(actx), optr,
+                                                  B, H, W, pred, clip, mem, stream))
+                return out
             _lib.check(h, L.cdc_decode(h, ai.ptr if ai else None, ptrs, len(actx), optr, B, H, W, pred,
                                        clip, mem, stream))
             return out
@@ -164,7 +200,7 @@ class _GaussianDiffusionBase:
         return img
 
     def decompress(self, context, shape=None, sample_steps=None, init=None, eta=0, clip_denoised=None, bitrate_scale=None,
-                   as_uint8=False):
+                   as_uint8=False, seed=None, gamma=None):
         """Decode half of compress(): context pyramid (= context_fn(...)["output"]) -> image.  `context`
         may also be the transmitted q_latent tensor [B, C, H/16, W/16]: it then goes through
         `context_fn.decode` first (compress_modules.py:68-74; cdc_compression_amd.compressor on the GPU) -- with
@@ -173,7 +209,10 @@ class _GaussianDiffusionBase:
         shape: [B, 3, H, W] of the images.  None: what the streams record (container version 5 / 6), else the coded extent (the
         finest context level).  A shape the context cannot belong to -- larger than the coded extent, or a whole multiple or
         more smaller -- or one that contradicts the size the streams record is an error.  The reconstruction is the frame's top-left H x W window.
-        as_uint8: the uint8 image the reference's script saves (clamp(-1, 1) / 2 + 0.5, then save_image's rounding), made on the device."""
+        as_uint8: the uint8 image the reference's script saves (clamp(-1, 1) / 2 + 0.5, then save_image's rounding), made on the device.
+        seed / gamma: the seeded stochastic decode (module docstring): with a seed, any eta runs in the device loop with generated
+        noise; gamma (needs a seed, excludes init) starts from gamma * randn made on the device.  The draws are indexed on the padded frame."""
+        self._seed_args(seed, gamma, init)
         recorded = None
         if isinstance(context, (bytes, bytearray)):
             context = [context]
@@ -187,6 +226,7 @@ class _GaussianDiffusionBase:
             if self.context_fn is None or not hasattr(self.context_fn, "decode"):
                 raise RuntimeError("decompress(q_latent, ...) needs a context_fn with decode()")
             context = self.context_fn.decode(context) if bitrate_scale is None else self.context_fn.decode(context, bitrate_scale)
+        self._seed_args(seed, gamma, init, int(context[0].shape[0]))
         self.set_sample_schedule(self.num_timesteps if sample_steps is None else sample_steps)
         if clip_denoised is None:
             clip_denoised = True if self._param == "x" else getattr(self, "clip_noise", "none")
@@ -198,7 +238,8 @@ class _GaussianDiffusionBase:
         if not (0 <= Hp - H < M and 0 <= Wp - W < M):
             raise _lib.CdcError(f"a {H} x {W} image does not pad to the {Hp} x {Wp} frame of the context (multiple {M})")
         h, dev = self.denoise_fn._handle(), self.denoise_fn.device_index
-        rec = self._loop((B, 3, Hp, Wp), context, clip_denoised, frame.extend_init(h, init, B, H, W, Hp, Wp, dev), eta)
+        rec = self._loop((B, 3, Hp, Wp), context, clip_denoised, frame.extend_init(h, init, B, H, W, Hp, Wp, dev), eta,
+                         seed, gamma)
         if (Hp, Wp) != (H, W) or as_uint8:
             rec = frame.crop(h, rec, H, W, dev, as_uint8=as_uint8)
         return rec
@@ -233,12 +274,14 @@ class GaussianDiffusionX(_GaussianDiffusionBase):
         self.loss_type = loss_type
         self.lagrangian_beta = lagrangian
 
-    def p_sample_loop(self, shape, context, clip_denoised=False, init=None, eta=0):
-        return self._loop(tuple(shape), context, clip_denoised, init, eta)
+    def p_sample_loop(self, shape, context, clip_denoised=False, init=None, eta=0, seed=None, gamma=None):
+        return self._loop(tuple(shape), context, clip_denoised, init, eta, seed, gamma)
 
-    def compress(self, images, sample_steps=None, bpp_return_mean=True, init=None, eta=0):
+    def compress(self, images, sample_steps=None, bpp_return_mean=True, init=None, eta=0, seed=None, gamma=None):
+        self._seed_args(seed, gamma, init, frame.image_shape(images)[0])
         rec, bpp = self._compress(images, sample_steps, init, eta,
-                                  lambda shape, ctx, i: self.p_sample_loop(shape, ctx, clip_denoised=True, init=i, eta=eta))   # :223
+                                  lambda shape, ctx, i: self.p_sample_loop(shape, ctx, clip_denoised=True, init=i, eta=eta,
+                                                                           seed=seed, gamma=gamma))   # :223
         return rec, (bpp.mean() if bpp_return_mean else bpp)
 
 
@@ -256,14 +299,16 @@ class GaussianDiffusionEps(_GaussianDiffusionBase):
         self.clip_noise = clip_noise
         self.vbr = vbr
 
-    def p_sample_loop(self, shape, context, sample_mode, init=None, eta=0):
+    def p_sample_loop(self, shape, context, sample_mode, init=None, eta=0, seed=None, gamma=None):
         if sample_mode != "ddim":
             raise NotImplementedError('sample_mode "ddpm" raises AttributeError in the reference '
                                       "(posterior_mean_coef1 undefined); only \"ddim\" is implemented")
-        return self._loop(tuple(shape), context, self.clip_noise, init, eta)
+        return self._loop(tuple(shape), context, self.clip_noise, init, eta, seed, gamma)
 
     def compress(self, images, sample_steps=None, bitrate_scale=None, sample_mode="ddpm",
-                 bpp_return_mean=True, init=None, eta=0):
+                 bpp_return_mean=True, init=None, eta=0, seed=None, gamma=None):
+        self._seed_args(seed, gamma, init, frame.image_shape(images)[0])
         rec, bpp = self._compress(images, sample_steps, init, eta,
-                                  lambda shape, ctx, i: self.p_sample_loop(shape, ctx, sample_mode, init=i, eta=eta), bitrate_scale)
+                                  lambda shape, ctx, i: self.p_sample_loop(shape, ctx, sample_mode, init=i, eta=eta, seed=seed,
+                                                                           gamma=gamma), bitrate_scale)
         return rec, (bpp.mean() if bpp_return_mean else bpp)

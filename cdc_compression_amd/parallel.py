@@ -16,6 +16,38 @@ def shard_bounds(batch, world_size, rank):
     return lo, lo + base + (1 if rank < extra else 0)
 
 
+def expand_seeds(seed, batch):
+    """The per-image 64-bit seeds of a seeded decode (`seed=` of decompress / compress; include/cdc_hip.h: cdc_decode_seeded):
+    an int s gives image b the seed (s + b) mod 2^64; a sequence of `batch` ints is taken as it is.  Every value must lie in
+    [0, 2^64); anything else is a ValueError."""
+    if isinstance(seed, bool) or (not hasattr(seed, "__index__") and not hasattr(seed, "__len__")):
+        raise ValueError(f"seed must be an int or a sequence of {batch} ints, not {type(seed).__name__}")
+    if hasattr(seed, "__index__") and not hasattr(seed, "__len__"):
+        s = int(seed)
+        if not 0 <= s < 2 ** 64:
+            raise ValueError(f"seed {s} outside [0, 2^64)")
+        return [(s + b) % 2 ** 64 for b in range(batch)]
+    seeds = list(seed)
+    if len(seeds) != batch:
+        raise ValueError(f"{len(seeds)} seeds for a batch of {batch}")
+    out = []
+    for v in seeds:
+        if isinstance(v, bool) or not hasattr(v, "__index__"):
+            raise ValueError(f"seed {v!r} is not an int")
+        v = int(v)
+        if not 0 <= v < 2 ** 64:
+            raise ValueError(f"seed {v} outside [0, 2^64)")
+        out.append(v)
+    return out
+
+
+def shard_seeds(seed, batch, world_size, rank):
+    """The seeds of this rank's shard_bounds slice of a `batch`-image job: a sharded seeded decode then equals the unsharded one
+    image for image (an image's draws depend on its own seed only)."""
+    lo, hi = shard_bounds(batch, world_size, rank)
+    return expand_seeds(seed, batch)[lo:hi]
+
+
 def sharded_decode(decode_fn, init, context, world_size=1, rank=0, dist=None, global_batch=None):
     """Run `decode_fn(init_shard, context_shard) -> reconstruction shard` on this rank's slice of the
     batch and gather the full batch on every rank.

@@ -1,5 +1,5 @@
 """Shared pieces of the two inference scripts (counterparts of the reference's test_xparam.py / test_epsilonparam.py):
-image IO without torchvision, checkpoint unwrapping, the per-image loop."""
+image IO without torchvision, checkpoint unwrapping, the options both scripts share (--device_seed), the per-image loop."""
 import os
 import pathlib
 import sys
@@ -9,6 +9,21 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+
+
+def _shared_options():
+    """Options both scripts share, taken off the command line here, before the scripts' own parsers (which mirror the reference's
+    argument lists) see it:
+      --device_seed N   init is made on the device from N and --gamma by the library's counter-based generator (the k-th image of the
+                        folder takes seed N + k): the same picture on every host.  Without it init = torch.randn * gamma, as before."""
+    import argparse
+    p = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    p.add_argument("--device_seed", type=int, default=None)
+    opts, sys.argv[1:] = p.parse_known_args(sys.argv[1:])
+    return opts
+
+
+SHARED = _shared_options()
 
 
 def read_image(path, device):
@@ -73,11 +88,18 @@ def run_folder(diffusion, config, rank, compress_kwargs):
     from cdc_compression_amd import frame, synth
     if getattr(config, "seed", None) is not None:
         torch.manual_seed(config.seed)
+    device_seed, k = SHARED.device_seed, 0
     for img in sorted(os.listdir(config.img_dir)):
         if img.endswith(".png") or img.endswith(".jpg"):
             to_be_compressed = read_image(os.path.join(config.img_dir, img), rank)
             shape = tuple(to_be_compressed.shape)
-            if os.environ.get("CDC_SYNTHETIC_INIT"):        # seed of a device-independent start noise (the parity fixtures' generator)
+            if device_seed is not None:
+                # --device_seed N: init = gamma * randn made on the device from seed N + k for the k-th image of the folder (the
+                # library's counter-based generator: the same picture on every host; no torch generator is involved)
+                init = None
+                compress_kwargs = dict(compress_kwargs, seed=(device_seed + k) % 2 ** 64, gamma=config.gamma)
+                k += 1
+            elif os.environ.get("CDC_SYNTHETIC_INIT"):        # seed of a device-independent start noise (the parity fixtures' generator)
                 init = torch.from_numpy(synth.normal("init", shape, seed=int(os.environ["CDC_SYNTHETIC_INIT"]),
                                                      std=config.gamma)).to(to_be_compressed.device)
             else:

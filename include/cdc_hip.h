@@ -83,7 +83,7 @@ const char *cdc_version(void);
  *                              bits for 6e-5 <= |a| < 65504.  RANGE GUARD: |a| >= 65504 makes the accumulators of its
  *                              convolution inf / NaN.  Every convolution / LayerNorm launch reports that itself, BEFORE a
  *                              fused LayerNorm + ReLU can turn it into a finite wrong value (round 4), and EVERY entry point
- *                              that runs the arithmetic (cdc_unet_forward, cdc_ddim_step, cdc_decode, cdc_ctxdec_decode,
+ *                              that runs the arithmetic (cdc_unet_forward, cdc_ddim_step, cdc_decode, cdc_decode_seeded, cdc_ctxdec_decode,
  *                              cdc_hyperdec_decode, cdc_encoder_encode, cdc_entropy_encode, the cdc_op_* operators) also
  *                              checks its results (one small kernel + a 4-byte read-back: the call synchronises its
  *                              stream) and repeats a faulting call ONCE in CDC_ARITH_BF16X3.  The handle then STAYS in that mode (a warning is printed once;
@@ -158,6 +158,41 @@ int cdc_ddim_step(cdc_handle *h, const float *x_in, int i, const float *const *c
  * init may be NULL (zeros, :183).  This is the timed hot path of bench.py. */
 int cdc_decode(cdc_handle *h, const float *init, const float *const *ctx, int n_ctx, float *out,
                int B, int H, int W, int pred_mode, int clip, int mem, void *stream);
+
+/* ---- seeded stochastic decode (no reference counterpart: the reference draws torch.randn on the host's global generator) -------
+ * The decoder is a sampler: scripts start from init = randn * gamma, and eta != 0 adds a normal draw per DDIM step.  Here the
+ * draws come from a counter-based generator evaluated INSIDE the sampler kernels: same context + same seed => same picture, on
+ * every host, in every batch, on every rank.
+ *
+ * THE FORMAT of the draws (fixed; a decoder elsewhere must be able to reproduce it; csrc/rng.h is its one implementation):
+ *   generator  Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11) with the Random123 constants: multipliers 0xD2511F53 (on counter
+ *              word 0) and 0xCD9E8D57 (on word 2), key increments 0x9E3779B9 / 0xBB67AE85 per round, ten rounds;
+ *   key        (seed & 0xffffffff, seed >> 32) of the IMAGE's 64-bit seed -- one seed per image of the batch;
+ *   counter    (q, draw, 0, 0).  q = element index inside the image's own [C][H][W] float tensor (the frame the sampler runs on,
+ *              i.e. the padded one for images of any size), divided by 4; the four output words belong to elements 4q .. 4q+3.
+ *              draw = 0 is the start image; draw = i + 1 is the noise of sample index i (the reference's `t`).  Counter words 2
+ *              and 3 are 0 and reserved;
+ *   uniform    u = ((word >> 9) + 0.5) * 2^-23: exact in float32, inside [2^-24, 1 - 2^-24];
+ *   normal     Box-Muller in float32 on (u0, u1) -> elements 0, 1 and (u2, u3) -> elements 2, 3:
+ *              r = sqrtf(-2 logf(ua)),  z = r cosf(2 pi ub),  r sinf(2 pi ub);  |z| <= 5.77.
+ * An image's draws depend on (its seed, draw, element index) and on nothing else.  Device kernels agree with one another bit for
+ * bit; host (cdc_randn_host) and device differ by their libm only (<= 1e-5).
+ *
+ * cdc_decode_seeded: the loop of cdc_decode (context staged once, hoisted context convolutions once, eager or CDC_GRAPH=1, range
+ *   guard; the BF16X3 repetition regenerates the start image and every draw from the seeds).  `seeds`: host array of B uint64_t.
+ *   init != NULL is used as it is; init == NULL starts from gamma * z(seed_b, draw 0), or from zeros when gamma == 0.  Per step
+ *   x += eta * sigma[i] * z(seed_b, draw i + 1), generated in the sampler kernel: no noise tensor is written or read.
+ *   eta == 0 && gamma == 0 is cdc_decode bit for bit.
+ * cdc_randn: out[b][e] = scale * z(seeds[b], draw, e) for e < per_image, made on the device (out follows `mem`): the start image for
+ *   a caller that wants to keep it, and the very draws of the fused loop for a caller that drives cdc_ddim_step itself.  Any handle
+ *   kind (device, stream and error state only).  B in [1, 65535], per_image in [1, 2^34].
+ * cdc_randn_host / cdc_philox4x32_10: the same header evaluated on the host; no handle, no GPU. */
+int cdc_decode_seeded(cdc_handle *h, const float *init, float gamma, const uint64_t *seeds, float eta, const float *const *ctx,
+                      int n_ctx, float *out, int B, int H, int W, int pred_mode, int clip, int mem, void *stream);
+int cdc_randn(cdc_handle *h, const uint64_t *seeds, int B, int64_t per_image, uint32_t draw, float scale, float *out, int mem,
+              void *stream);
+int cdc_randn_host(const uint64_t *seeds, int B, int64_t per_image, uint32_t draw, float scale, float *out);
+int cdc_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
 /* ---- measurement --------------------------------------------------------------------------- */
 
