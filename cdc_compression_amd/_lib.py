@@ -14,6 +14,7 @@ CDC_CLIP_NONE, CDC_CLIP_ALL, CDC_CLIP_HALF = 0, 1, 2
 CDC_MAX_LEVELS = 8
 CDC_ELEM_F32, CDC_ELEM_U8 = 0, 1
 CDC_FILL_EDGE, CDC_FILL_ZERO = 0, 1
+CDC_METRIC_PSNR, CDC_METRIC_MSSSIM = 1, 2
 
 _f = ctypes.POINTER(ctypes.c_float)
 _i = ctypes.c_int
@@ -42,6 +43,11 @@ class EncoderConfig(ctypes.Structure):
     _fields_ = [("dim", ctypes.c_int32), ("channels", ctypes.c_int32), ("n_dim_mults", ctypes.c_int32),
                 ("dim_mults", ctypes.c_int32 * CDC_MAX_LEVELS), ("n_hyper_mults", ctypes.c_int32),
                 ("hyper_mults", ctypes.c_int32 * CDC_MAX_LEVELS), ("down_index", ctypes.c_int32)]
+
+
+class ImageView(ctypes.Structure):
+    _fields_ = [("data", ctypes.c_void_p), ("elem_kind", ctypes.c_int), ("Hf", ctypes.c_int), ("Wf", ctypes.c_int),
+                ("as_saved", ctypes.c_int)]
 
 
 class CdcError(RuntimeError):
@@ -123,6 +129,8 @@ def lib():
     L.cdc_entropy_set_image_scale.argtypes = [H, _i]
     L.cdc_entropy_encode_image.argtypes = [H, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), _i, _vp]
     L.cdc_entropy_peek_image_size.argtypes = [_vp, ctypes.c_size_t, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]
+    f64p = ctypes.POINTER(ctypes.c_double)
+    L.cdc_distortion.argtypes = [H, ctypes.POINTER(ImageView), ctypes.POINTER(ImageView), _i, _i, _i, _i, f64p, f64p, f64p, _i, _vp]
     L.cdc_dequantize.argtypes = [H, _vp, _vp, _vp, ctypes.c_longlong, _i, _vp]
     L.cdc_bpp.argtypes = [H, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]
     L.cdc_set_schedule.argtypes = [H, _i, _vp, _vp, _vp, _vp, _vp, _vp]
@@ -169,7 +177,8 @@ EXPORTS = ["cdc_create", "cdc_destroy", "cdc_last_error", "cdc_version", "cdc_nu
            "cdc_get_nonfinite_results", "cdc_set_schedule_v", "cdc_probe_mfma_f16", "cdc_probe_hbm_copy",
            "cdc_op_stress", "cdc_op_stress_result", "cdc_enable_vbr", "cdc_set_bitrate_scale", "cdc_entropy_peek_bitrate_scale",
            "cdc_padded_size", "cdc_frame_pad", "cdc_frame_crop", "cdc_entropy_set_image_scale", "cdc_entropy_encode_image",
-           "cdc_entropy_peek_image_size", "cdc_decode_seeded", "cdc_randn", "cdc_randn_host", "cdc_philox4x32_10"]
+           "cdc_entropy_peek_image_size", "cdc_decode_seeded", "cdc_randn", "cdc_randn_host", "cdc_philox4x32_10",
+           "cdc_distortion"]
 
 
 def handle_status(handle):

@@ -342,6 +342,7 @@ void cdc_destroy(cdc_handle *h) {
     if (h->d_time_steps) (void)hipFree(h->d_time_steps);
     if (h->d_shift_tab) (void)hipFree(h->d_shift_tab);
     if (h->d_seeds) (void)hipFree(h->d_seeds);
+    if (h->metric_work) (void)hipFree(h->metric_work);
     (void)resolve_pending(h);
     for (hipEvent_t e : h->ev_free) (void)hipEventDestroy(e);
     if (h->gev_in) (void)hipEventDestroy(h->gev_in);
@@ -640,6 +641,72 @@ int cdc_frame_crop(cdc_handle *h, const float *src, void *dst, int B, int H, int
             const hipError_t es = hipStreamSynchronize(st);
             if (e == hipSuccess) e = es;
             if (e != hipSuccess) return fail(h, CDC_ERR_HIP, "frame_crop: %s", hipGetErrorString(e));
+            return CDC_OK;
+        });
+    });
+}
+
+// ---- distortion of decoded images (metric_kernels.hip) ---------------------------------------------------------------------------------
+int cdc_distortion(cdc_handle *h, const cdc_image_view *a, const cdc_image_view *b, int B, int H, int W, int what, double *psnr,
+                   double *msssim, double *components, int mem, void *stream) {
+    if (!h) return CDC_ERR_INVALID;
+    return no_throw(h, [&] {
+        return with_range_guard(h, [&]() -> int {
+            int rc = ensure_device(h);
+            if (rc) return rc;
+            if (!a || !b || !a->data || !b->data) return fail(h, CDC_ERR_INVALID, "distortion: null operand");
+            if (B < 1 || H < 1 || W < 1) return fail(h, CDC_ERR_INVALID, "distortion: B=%d H=%d W=%d (all must be >= 1)", B, H, W);
+            if (mem != CDC_MEM_HOST && mem != CDC_MEM_DEVICE) return fail(h, CDC_ERR_INVALID, "distortion: mem_kind %d", mem);
+            const bool want_psnr = what & CDC_METRIC_PSNR, want_ms = what & CDC_METRIC_MSSSIM;
+            if (what == 0 || (what & ~(CDC_METRIC_PSNR | CDC_METRIC_MSSSIM))) return fail(h, CDC_ERR_INVALID, "distortion: what = %d names no metric (CDC_METRIC_PSNR | CDC_METRIC_MSSSIM)", what);
+            if (want_psnr && !psnr) return fail(h, CDC_ERR_INVALID, "distortion: PSNR requested without a psnr array");
+            if (want_ms && !msssim) return fail(h, CDC_ERR_INVALID, "distortion: MS-SSIM requested without an msssim array");
+            MetricView mv[2];
+            size_t bytes[2];
+            const cdc_image_view *src[2] = {a, b};
+            for (int i = 0; i < 2; ++i) {
+                const cdc_image_view &v = *src[i];
+                const char n = "ab"[i];
+                if (v.elem_kind != CDC_ELEM_F32 && v.elem_kind != CDC_ELEM_U8) return fail(h, CDC_ERR_INVALID, "distortion: operand %c has element kind %d", n, v.elem_kind);
+                if (v.Hf < H || v.Wf < W) return fail(h, CDC_ERR_INVALID, "distortion: operand %c is a %d x %d frame, smaller than the %d x %d window", n, v.Hf, v.Wf, H, W);
+                if (v.as_saved && v.elem_kind == CDC_ELEM_U8) return fail(h, CDC_ERR_INVALID, "distortion: as_saved on operand %c, which is uint8 already", n);
+                if ((long long)B * 3 * v.Hf * v.Wf > (1ll << 40)) return fail(h, CDC_ERR_INVALID, "distortion: %d x 3 x %d x %d elements", B, v.Hf, v.Wf);
+                mv[i] = {v.data, v.elem_kind == CDC_ELEM_U8 ? METRIC_U8 : (v.as_saved ? METRIC_F32_SAVED : METRIC_F32), v.Hf, v.Wf};
+                bytes[i] = (size_t)B * 3 * v.Hf * v.Wf * (v.elem_kind == CDC_ELEM_U8 ? 1 : 4);
+            }
+            if (want_ms && std::min(H, W) <= 160) return fail(h, CDC_ERR_INVALID, "distortion: MS-SSIM needs min(H, W) > 160 (five scales of an 11-tap window), got %d x %d", H, W);
+            MetricLayout L;
+            if (!metric_layout(B, H, W, want_psnr, want_ms, &L)) return fail(h, CDC_ERR_INVALID, "distortion: B=%d %d x %d is beyond the launch limits", B, H, W);
+            hipStream_t st = pick_stream(h, stream, mem);
+            if (L.bytes > h->metric_cap) {                         // (an earlier call has synchronised its stream before it returned)
+                if (h->metric_work) { (void)hipFree(h->metric_work); h->metric_work = nullptr; h->metric_cap = 0; }
+                if (hipMalloc(&h->metric_work, L.bytes) != hipSuccess) { h->metric_work = nullptr; return fail(h, CDC_ERR_NOMEM, "distortion: hipMalloc of %zu bytes failed", L.bytes); }
+                h->metric_cap = L.bytes;
+            }
+            DevPool d;
+            hipError_t e = hipSuccess;
+            if (mem == CDC_MEM_HOST) {
+                for (int i = 0; i < 2 && e == hipSuccess; ++i) {
+                    uint8_t *p;
+                    if (d.get(&p, bytes[i]) != hipSuccess) return fail(h, CDC_ERR_NOMEM, "distortion: hipMalloc failed");
+                    e = hipMemcpyAsync(p, mv[i].data, bytes[i], hipMemcpyHostToDevice, st);
+                    mv[i].data = p;
+                }
+            }
+            if (e == hipSuccess && want_psnr) e = metric_psnr_launch(mv[0], mv[1], B, H, W, L, h->metric_work, st);
+            if (e == hipSuccess && want_ms) e = metric_msssim_launch(mv[0], mv[1], B, L, h->metric_work, st);
+            const int per = 2 + METRIC_SCALES * 3;
+            std::vector<double> res((size_t)B * per);
+            if (e == hipSuccess) e = hipMemcpyAsync(res.data(), (char *)h->metric_work + L.result_off, sizeof(double) * res.size(), hipMemcpyDeviceToHost, st);
+            const hipError_t es = hipStreamSynchronize(st);   // (after an error too: nothing queued may still use what d frees)
+            if (e == hipSuccess) e = es;
+            if (e != hipSuccess) return fail(h, CDC_ERR_HIP, "distortion: %s", hipGetErrorString(e));
+            if (want_psnr)
+                for (int i = 0; i < B; ++i) psnr[i] = res[i] == 0.0 ? INFINITY : 10.0 * log10(1.0 / res[i]);
+            if (want_ms) {
+                memcpy(msssim, res.data() + B, sizeof(double) * B);
+                if (components) memcpy(components, res.data() + 2 * (size_t)B, sizeof(double) * B * METRIC_SCALES * 3);
+            }
             return CDC_OK;
         });
     });

@@ -265,6 +265,20 @@ hipError_t vbr_affine_launch(float *x, long long bs, int C, int HW, const float 
 // replication (zero = 1: by zeros), and the top-left [H][W] window back (float32 copy, or the uint8 of save_image)
 hipError_t frame_in_launch(const void *src, int u8, float *dst, int P, int H, int W, int Hp, int Wp, int zero, hipStream_t st);
 hipError_t frame_out_launch(const float *src, void *dst, int u8, int P, int H, int W, int Hp, int Wp, hipStream_t st);
+// metric_kernels.hip (cdc_distortion): PSNR and MS-SSIM of the top-left H x W window of two image batches [B][3][Hf][Wf]
+enum { METRIC_F32 = 0, METRIC_U8 = 1, METRIC_F32_SAVED = 2 };      // float32 in [-1, 1]; uint8; float32 through the byte cdc_frame_crop writes
+constexpr int METRIC_SCALES = 5, METRIC_TILE_H = 16, METRIC_TILE_W = 32;   // a workgroup's tile of the valid SSIM map
+struct MetricView { const void *data; int kind, Hf, Wf; };         // device pointer
+struct MetricLayout {                                              // the device work area of one call (byte offsets, 16-byte aligned)
+    size_t bytes = 0, result_off = 0, psnr_off = 0;                // results: doubles mse [B] | msssim [B] | components [B][5][3]
+    int psnr_blocks = 0;
+    int Hs[METRIC_SCALES] = {}, Ws[METRIC_SCALES] = {}, tiles_y[METRIC_SCALES] = {}, tiles_x[METRIC_SCALES] = {};
+    size_t partial_off[METRIC_SCALES] = {}, plane_off[METRIC_SCALES][2] = {};   // planes of scale l >= 1 of the two operands
+};
+int metric_next_side(int s);                                       // side of the next scale: (s + 2 (s mod 2) - 2) / 2 + 1
+bool metric_layout(int B, int H, int W, bool psnr, bool msssim, MetricLayout *L);   // false: too small for five scales, or too many tiles
+hipError_t metric_psnr_launch(const MetricView &a, const MetricView &b, int B, int H, int W, const MetricLayout &L, void *work, hipStream_t st);
+hipError_t metric_msssim_launch(const MetricView &a, const MetricView &b, int B, const MetricLayout &L, void *work, hipStream_t st);
 hipError_t unfold_x_launch(const float *src, long long src_bs, float *dst, long long dst_bs, int C, int KW,
                            int pad, int H, int W, int B, hipStream_t st);
 

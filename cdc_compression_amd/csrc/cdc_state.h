@@ -203,6 +203,8 @@ struct cdc_handle {
     int seeds_cap = 0;
     std::vector<unsigned long long> h_seeds;   // staging copy: the caller's array may go away before the copy has run
     int time_steps_B = 0;
+    void *metric_work = nullptr;         // cdc_distortion: partial sums and the pooled MS-SSIM pyramids of both operands, grown on demand
+    size_t metric_cap = 0;
     int op_stress_n = 0;                 // cdc_op_stress: extra executions of every cdc_op_* program, results compared on the device
     long long op_stress_launches = 0, op_stress_differing = 0;
     // profiling

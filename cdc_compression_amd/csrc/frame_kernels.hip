@@ -7,31 +7,16 @@
 // accesses otherwise.  Both variants are chosen per launch (template flag), the only per-thread decision is "is my quad cut by
 // the image's right edge", and coordinates are clamped with min(), not branched on.  A general element-wise variant (VEC = false)
 // covers a padded width that is not a multiple of 4 or an unaligned padded base, which only direct C-ABI callers can produce.
-// Arithmetic of the uint8 forms: exactly torch's operation sequence, every operation rounded on its own (this file is compiled
-// with -ffp-contract=off, and the two-rounding sites use the _rn intrinsics so that the intent survives a change of flags):
-//   in   float(v) / 255.0 * 2.0 - 1.0                          (xparam/test_xparam.py:74,76: read_image().float() / 255.0, * 2.0 - 1.0)
-//   out  clamp(x, -1, 1) / 2.0 + 0.5, then * 255 + 0.5, clamp(0, 255), truncate
-//                                                              (xparam/test_xparam.py:81 and torchvision.utils.save_image)
+// Arithmetic of the uint8 forms: frame_pixel.h (torch's operation sequence, every operation rounded on its own).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "cdc_internal.h"
+#include "frame_pixel.h"
 
 namespace cdc {
 
 namespace {
-
-__device__ __forceinline__ float u8_to_unit(uint32_t v) {
-    return __fsub_rn(__fmul_rn(__fdiv_rn((float)v, 255.0f), 2.0f), 1.0f);
-}
-
-__device__ __forceinline__ uint32_t unit_to_u8(float x) {
-    float t = fminf(fmaxf(x, -1.0f), 1.0f);
-    t = __fadd_rn(__fmul_rn(t, 0.5f), 0.5f);                       // / 2.0 is exact as * 0.5
-    t = __fadd_rn(__fmul_rn(t, 255.0f), 0.5f);                     // mul, then add_: two roundings
-    t = fminf(fmaxf(t, 0.0f), 255.0f);
-    return (uint32_t)t;                                            // truncation (a NaN becomes 0)
-}
 
 template <class T> __device__ __forceinline__ float load_elem(const T *p);
 template <> __device__ __forceinline__ float load_elem<float>(const float *p) { return *p; }

@@ -96,8 +96,8 @@ class _GaussianDiffusionBase:
                                            optr, omem, _current_stream(omem)))
         return out
 
-    def _compress(self, images, sample_steps, init, eta, loop, *ctx_args):
-        """compress() of both trees: context model and sampler on the padded frame, the window of the image back."""
+    def _compress_frame(self, images, sample_steps, init, eta, loop, *ctx_args):
+        """compress() of both trees up to the crop: context model and sampler on the padded frame -> (frame, bpp [B], H, W)."""
         B, _, H, W = frame.image_shape(images)
         Hp, Wp = self.padded_size(H, W)
         h, dev = self.denoise_fn._handle(), self.denoise_fn.device_index
@@ -110,9 +110,27 @@ class _GaussianDiffusionBase:
             context_dict["bpp"] = context_dict["bpp"] * ((Hp * Wp) / (H * W))
         self.set_sample_schedule(self.num_timesteps if sample_steps is None else sample_steps)
         rec = loop((B, 3, Hp, Wp), context_dict["output"], frame.extend_init(h, init, B, H, W, Hp, Wp, dev))
-        if (Hp, Wp) != (H, W):
-            rec = frame.crop(h, rec, H, W, dev)
-        return rec, context_dict["bpp"]
+        return rec, context_dict["bpp"], H, W
+
+    def _window(self, rec, H, W):
+        """The reconstruction compress() returns: the frame's top-left H x W window (the frame itself when it is the image)."""
+        if tuple(rec.shape[2:]) != (H, W):
+            rec = frame.crop(self.denoise_fn._handle(), rec, H, W, self.denoise_fn.device_index)
+        return rec
+
+    def evaluate(self, images, *args, as_saved=True, **kwargs):
+        """compress() with the other axis of the rate-distortion plot: takes compress()'s arguments, runs its path once and returns
+        {"reconstruction": what compress() returns, "bpp": [B], "psnr": float64 [B], "ms_ssim": float64 [B], or None when
+        min(H, W) <= 160}.  The distortion is measured on the device (cdc_compression_amd.metrics), on the padded frame's H x W window
+        against `images` as given (float32 or uint8); as_saved: float32 operands through the uint8 image the reference's script would
+        save (metrics.psnr(model, reconstruction, images, as_saved=True) gives the same figures)."""
+        from . import metrics
+        import inspect
+        bound = dict(inspect.signature(self.compress).bind(images, *args, **kwargs).arguments)
+        bound.pop("bpp_return_mean", None)                    # bpp comes per image
+        rec, bpp, H, W = self._frame_of(**bound)
+        ps, ms = metrics.distortion(self.denoise_fn, rec, images, size=(H, W), as_saved=as_saved)
+        return {"reconstruction": self._window(rec, H, W), "bpp": bpp, "psnr": ps, "ms_ssim": ms}
 
     # ---- schedule ---------------------------------------------------------------------------
     def set_sample_schedule(self, sample_steps, device=None):
@@ -277,12 +295,15 @@ class GaussianDiffusionX(_GaussianDiffusionBase):
     def p_sample_loop(self, shape, context, clip_denoised=False, init=None, eta=0, seed=None, gamma=None):
         return self._loop(tuple(shape), context, clip_denoised, init, eta, seed, gamma)
 
-    def compress(self, images, sample_steps=None, bpp_return_mean=True, init=None, eta=0, seed=None, gamma=None):
+    def _frame_of(self, images, sample_steps=None, init=None, eta=0, seed=None, gamma=None):
         self._seed_args(seed, gamma, init, frame.image_shape(images)[0])
-        rec, bpp = self._compress(images, sample_steps, init, eta,
-                                  lambda shape, ctx, i: self.p_sample_loop(shape, ctx, clip_denoised=True, init=i, eta=eta,
-                                                                           seed=seed, gamma=gamma))   # :223
-        return rec, (bpp.mean() if bpp_return_mean else bpp)
+        return self._compress_frame(images, sample_steps, init, eta,
+                                    lambda shape, ctx, i: self.p_sample_loop(shape, ctx, clip_denoised=True, init=i, eta=eta,
+                                                                             seed=seed, gamma=gamma))   # :223
+
+    def compress(self, images, sample_steps=None, bpp_return_mean=True, init=None, eta=0, seed=None, gamma=None):
+        rec, bpp, H, W = self._frame_of(images, sample_steps, init, eta, seed, gamma)
+        return self._window(rec, H, W), (bpp.mean() if bpp_return_mean else bpp)
 
 
 class GaussianDiffusionEps(_GaussianDiffusionBase):
@@ -305,10 +326,13 @@ class GaussianDiffusionEps(_GaussianDiffusionBase):
                                       "(posterior_mean_coef1 undefined); only \"ddim\" is implemented")
         return self._loop(tuple(shape), context, self.clip_noise, init, eta, seed, gamma)
 
+    def _frame_of(self, images, sample_steps=None, bitrate_scale=None, sample_mode="ddpm", init=None, eta=0, seed=None, gamma=None):
+        self._seed_args(seed, gamma, init, frame.image_shape(images)[0])
+        return self._compress_frame(images, sample_steps, init, eta,
+                                    lambda shape, ctx, i: self.p_sample_loop(shape, ctx, sample_mode, init=i, eta=eta, seed=seed,
+                                                                             gamma=gamma), bitrate_scale)
+
     def compress(self, images, sample_steps=None, bitrate_scale=None, sample_mode="ddpm",
                  bpp_return_mean=True, init=None, eta=0, seed=None, gamma=None):
-        self._seed_args(seed, gamma, init, frame.image_shape(images)[0])
-        rec, bpp = self._compress(images, sample_steps, init, eta,
-                                  lambda shape, ctx, i: self.p_sample_loop(shape, ctx, sample_mode, init=i, eta=eta, seed=seed,
-                                                                           gamma=gamma), bitrate_scale)
-        return rec, (bpp.mean() if bpp_return_mean else bpp)
+        rec, bpp, H, W = self._frame_of(images, sample_steps, bitrate_scale, sample_mode, init, eta, seed, gamma)
+        return self._window(rec, H, W), (bpp.mean() if bpp_return_mean else bpp)

@@ -15,10 +15,13 @@ def _shared_options():
     """Options both scripts share, taken off the command line here, before the scripts' own parsers (which mirror the reference's
     argument lists) see it:
       --device_seed N   init is made on the device from N and --gamma by the library's counter-based generator (the k-th image of the
-                        folder takes seed N + k): the same picture on every host.  Without it init = torch.randn * gamma, as before."""
+                        folder takes seed N + k): the same picture on every host.  Without it init = torch.randn * gamma, as before.
+      --metrics         print PSNR and MS-SSIM of the saved image against the input beside bpp (computed on the device from the
+                        reconstruction that is already there: cdc_compression_amd.metrics).  Without it the output is unchanged."""
     import argparse
     p = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
     p.add_argument("--device_seed", type=int, default=None)
+    p.add_argument("--metrics", action="store_true")
     opts, sys.argv[1:] = p.parse_known_args(sys.argv[1:])
     return opts
 
@@ -111,8 +114,14 @@ def run_folder(diffusion, config, rank, compress_kwargs):
                 **compress_kwargs,
             )
             un = diffusion.denoise_fn
+            if SHARED.metrics:                                # the float reconstruction as it is saved, against the uint8 input
+                from cdc_compression_amd import metrics
+                ps, ms = metrics.distortion(un, compressed, to_be_compressed, as_saved=True)
             compressed = frame.crop(un._handle(), compressed, shape[2], shape[3], un.device_index, as_uint8=True)
             pathlib.Path(config.out_dir).mkdir(parents=True, exist_ok=True)
             save_image(compressed, os.path.join(config.out_dir, img))
             print("image:", img)
             print("bpp:", bpp)
+            if SHARED.metrics:
+                print("psnr:", float(ps[0]))
+                print("ms_ssim:", "n/a (needs min(H, W) > 160)" if ms is None else float(ms[0]))

@@ -397,6 +397,41 @@ int cdc_entropy_encode_image(cdc_handle *h, const float *latent, const float *hy
                              int mem_kind, void *stream);
 int cdc_entropy_peek_image_size(const unsigned char *in, size_t n, int *has_size, int *img_h, int *img_w);
 
+/* ---- distortion of decoded images: PSNR and MS-SSIM on the device (csrc/metric_kernels.hip) --------------------------------------
+ * THE DEFINITION.  Operands: two image batches a, b, each [B][3][Hf][Wf] with Hf >= H, Wf >= W and its own element kind, frame size
+ * and as_saved flag (a cdc_image_view each).  Only the top-left H x W window is evaluated -- a padded decoder frame is measured
+ * without a crop -- and nothing outside it influences a result, NaN or Inf there included.
+ * Mapping to [0, 1]:  CDC_ELEM_U8: v / 255.   CDC_ELEM_F32: clamp(x, -1, 1) * 0.5 + 0.5 (what the reference scripts do before
+ *   saving).   CDC_ELEM_F32 with as_saved = 1: the byte that cdc_frame_crop(..., CDC_ELEM_U8) would write, then v / 255.
+ * PSNR of image i: 10 log10(1 / mean((a - b)^2)) over its 3 H W elements (the reference's batch_psnr before the batch mean,
+ *   xparam/modules/trainer.py:12-16); +inf for identical operands.  Two byte operands (uint8, or float32 with as_saved): the
+ *   differences are integers and the sum of squares an exact integer, so the MSE is exact.  Otherwise the difference is fp32 and every
+ *   squared term is accumulated in fp64.
+ * MS-SSIM of image i, with the conventions of pytorch-msssim 0.2.1 ms_ssim(X, Y, data_range=1, size_average=False):
+ *   window   11-tap Gaussian g[i] ~ exp(-(i - 5)^2 / (2 * 1.5^2)), normalised, applied separably as a VALID filter per channel;
+ *   per scale  mu1 = g*x, mu2 = g*y, s1 = g*x^2 - mu1^2, s2 = g*y^2 - mu2^2, s12 = g*xy - mu1 mu2,
+ *              cs = (2 s12 + C2) / (s1 + s2 + C2), ssim = (2 mu1 mu2 + C1) / (mu1^2 + mu2^2 + C1) * cs, C1 = 0.01^2, C2 = 0.03^2,
+ *              per channel the spatial mean of each map;
+ *   scales 0-3 contribute relu(mean cs); both images then go through avg_pool2d(kernel 2, stride 2, padding = (H mod 2, W mod 2))
+ *              with the pad counted: an odd side gets one zero row / column at the top / left, the divisor is always 4, the next
+ *              side is (s + 2 (s mod 2) - 2) / 2 + 1;   scale 4 contributes relu(mean ssim);
+ *   result   prod_l value_l ^ w_l with w = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333), then the mean over the three channels.
+ *   components[i][l][c] is value_l of channel c (after the relu).  min(H, W) > 160 is required; PSNR has no lower limit.
+ *   The planes are fp32, every product, filter sum and moment difference fp64 (parity with a float64 evaluation: 1e-5 absolute).
+ * A result depends neither on the batch the image sits in nor on the run (no atomics, fixed summation orders).
+ *
+ * cdc_distortion: what = CDC_METRIC_PSNR | CDC_METRIC_MSSSIM selects; psnr [B], msssim [B] and components [B][5][3] (may be NULL) are
+ *   ALWAYS HOST arrays, and the call SYNCHRONISES the stream before it returns.  The image pointers follow mem_kind (CDC_MEM_HOST
+ *   images are staged through device buffers); stream as for cdc_unet_forward.  Any handle kind (its device, stream and error state
+ *   only; the pooled pyramids, 2 B 3 (~H W / 3) floats, live in handle-owned device memory grown on demand), the same guard / error
+ *   runner as every entry point.  CDC_ERR_INVALID, with a message: B, H, W < 1; Hf < H or Wf < W; an unknown element kind; as_saved
+ *   on a uint8 operand; what == 0 or an output pointer missing for a requested metric; MS-SSIM with min(H, W) <= 160. */
+typedef struct { const void *data; int elem_kind; int Hf, Wf; int as_saved; } cdc_image_view;
+enum { CDC_METRIC_PSNR = 1, CDC_METRIC_MSSSIM = 2 };
+int cdc_distortion(cdc_handle *h, const cdc_image_view *a, const cdc_image_view *b, int B, int H, int W, int what,
+                   double *psnr /*[B]*/, double *msssim /*[B]*/, double *components /*[B][5][3] or NULL*/,
+                   int mem_kind, void *stream);
+
 /* quantize(x, "dequantize", offset) = round(x - offset) + offset, round = half-to-even (utils.py:72-85). */
 int cdc_dequantize(cdc_handle *h, const float *x, const float *offset, float *out, long long n, int mem_kind,
                    void *stream);
