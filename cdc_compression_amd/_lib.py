@@ -131,6 +131,8 @@ def lib():
     L.cdc_entropy_peek_image_size.argtypes = [_vp, ctypes.c_size_t, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]
     f64p = ctypes.POINTER(ctypes.c_double)
     L.cdc_distortion.argtypes = [H, ctypes.POINTER(ImageView), ctypes.POINTER(ImageView), _i, _i, _i, _i, f64p, f64p, f64p, _i, _vp]
+    L.cdc_lpips_create.argtypes = [_i, ctypes.POINTER(H)]
+    L.cdc_lpips.argtypes = [H, ctypes.POINTER(ImageView), ctypes.POINTER(ImageView), _i, _i, _i, f64p, f64p, _i, _vp]
     L.cdc_dequantize.argtypes = [H, _vp, _vp, _vp, ctypes.c_longlong, _i, _vp]
     L.cdc_bpp.argtypes = [H, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]
     L.cdc_set_schedule.argtypes = [H, _i, _vp, _vp, _vp, _vp, _vp, _vp]
@@ -178,7 +180,7 @@ EXPORTS = ["cdc_create", "cdc_destroy", "cdc_last_error", "cdc_version", "cdc_nu
            "cdc_op_stress", "cdc_op_stress_result", "cdc_enable_vbr", "cdc_set_bitrate_scale", "cdc_entropy_peek_bitrate_scale",
            "cdc_padded_size", "cdc_frame_pad", "cdc_frame_crop", "cdc_entropy_set_image_scale", "cdc_entropy_encode_image",
            "cdc_entropy_peek_image_size", "cdc_decode_seeded", "cdc_randn", "cdc_randn_host", "cdc_philox4x32_10",
-           "cdc_distortion"]
+           "cdc_distortion", "cdc_lpips_create", "cdc_lpips"]
 
 
 def handle_status(handle):

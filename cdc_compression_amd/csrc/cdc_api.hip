@@ -112,6 +112,10 @@ int run_op(cdc_handle *h, const Op &op, int B, hipStream_t st) {
         case Op::VBR:
             HIP_TRY(h, vbr_affine_launch(op.vb.x, op.vb.bs, op.vb.C, op.vb.HW, op.vb.rate, op.vb.p, op.vb.leaky, B, st));
             break;
+        case Op::MAXPOOL: HIP_TRY(h, maxpool2_launch(op.mp.src, op.mp.dst, (long long)B * op.mp.C, op.mp.H, op.mp.W, st)); break;
+        case Op::LPHEAD:            // B rows = B / 2 pairs
+            HIP_TRY(h, lpips_head_launch(op.lh.f, op.lh.bs, op.lh.C, op.lh.HW, op.lh.w, B / 2, op.lh.partials, op.lh.res, op.lh.layer, op.lh.fault, st));
+            break;
     }
     if (prof) {
         HIP_TRY(h, hipEventRecord(eb, st));
@@ -225,7 +229,7 @@ int check_ready(cdc_handle *h) {
 // CDC_ERR_STATE for a handle of another kind; a null handle is left to the entry point's own check
 int require_kind(cdc_handle *h, HandleKind kind) {
     if (!h || h->kind == kind) return CDC_OK;
-    static const char *const what[] = {"a U-Net", "a context decoder", "a hyper decoder", "an encoder"};
+    static const char *const what[] = {"a U-Net", "a context decoder", "a hyper decoder", "an encoder", "an LPIPS-VGG network"};
     return fail(h, CDC_ERR_STATE, "handle is not %s", what[(int)kind]);
 }
 
@@ -712,6 +716,99 @@ int cdc_distortion(cdc_handle *h, const cdc_image_view *a, const cdc_image_view 
     });
 }
 
+// ---- LPIPS-VGG of decoded images (lpips_kernels.hip, build_lpips_program) ------------------------------------------------------------
+int cdc_lpips_create(int device, cdc_handle **out) {
+    if (!out) return fail(nullptr, CDC_ERR_INVALID, "null argument");
+    if (device < 0) return fail(nullptr, CDC_ERR_INVALID, "device %d out of range", device);
+    std::unique_ptr<cdc_handle> h(new cdc_handle);
+    memset(&h->cfg, 0, sizeof h->cfg);
+    h->kind = HandleKind::Lpips;
+    h->device = device;
+    build_lpips_manifest(h.get());
+    *out = h.release();
+    return CDC_OK;
+}
+
+int cdc_lpips(cdc_handle *h, const cdc_image_view *a, const cdc_image_view *b, int B, int H, int W, double *lpips, double *layers,
+              int mem, void *stream) {
+    if (!h) return CDC_ERR_INVALID;
+    return no_throw(h, [&] {
+        return with_range_guard(h, [&]() -> int {
+            if (h->kind != HandleKind::Lpips) return fail(h, CDC_ERR_INVALID, "lpips: handle is not an LPIPS-VGG network (cdc_lpips_create)");
+            if (!h->finalized) return fail(h, CDC_ERR_INVALID, "lpips: weights not finalized (cdc_finalize_weights)");
+            if (!a || !b || !a->data || !b->data) return fail(h, CDC_ERR_INVALID, "lpips: null operand");
+            if (!lpips) return fail(h, CDC_ERR_INVALID, "lpips: no result array");
+            if (B < 1) return fail(h, CDC_ERR_INVALID, "lpips: B=%d (must be >= 1)", B);
+            if (H < 16 || W < 16) return fail(h, CDC_ERR_INVALID, "lpips: the window is %d x %d, H, W >= 16 is required (four poolings)", H, W);
+            if (mem != CDC_MEM_HOST && mem != CDC_MEM_DEVICE) return fail(h, CDC_ERR_INVALID, "lpips: mem_kind %d", mem);
+            MetricView mv[2];
+            size_t bytes[2], img_bytes[2];
+            const cdc_image_view *src[2] = {a, b};
+            for (int i = 0; i < 2; ++i) {
+                const cdc_image_view &v = *src[i];
+                const char n = "ab"[i];
+                if (v.elem_kind != CDC_ELEM_F32 && v.elem_kind != CDC_ELEM_U8) return fail(h, CDC_ERR_INVALID, "lpips: operand %c has element kind %d", n, v.elem_kind);
+                if (v.Hf < H || v.Wf < W) return fail(h, CDC_ERR_INVALID, "lpips: operand %c is a %d x %d frame, smaller than the %d x %d window", n, v.Hf, v.Wf, H, W);
+                if (v.as_saved && v.elem_kind == CDC_ELEM_U8) return fail(h, CDC_ERR_INVALID, "lpips: as_saved on operand %c, which is uint8 already", n);
+                if ((long long)B * 3 * v.Hf * v.Wf > (1ll << 40)) return fail(h, CDC_ERR_INVALID, "lpips: %d x 3 x %d x %d elements", B, v.Hf, v.Wf);
+                mv[i] = {v.data, v.elem_kind == CDC_ELEM_U8 ? METRIC_U8 : (v.as_saved ? METRIC_F32_SAVED : METRIC_F32), v.Hf, v.Wf};
+                img_bytes[i] = (size_t)3 * v.Hf * v.Wf * (v.elem_kind == CDC_ELEM_U8 ? 1 : 4);
+                bytes[i] = (size_t)B * img_bytes[i];
+            }
+            if ((long long)H * W > (1ll << 28)) return fail(h, CDC_ERR_INVALID, "lpips: a %d x %d window is beyond the launch limits", H, W);
+            int rc = check_ready(h);
+            if (rc) return rc;
+            // A batch runs in equal chunks of `pairs`: as few chunks as keep the program's activations under the budget (one pair at
+            // least).  CDC_LPIPS_BUDGET_MB (development switch): another budget, to force a split.
+            size_t budget = (size_t)4096 << 20;
+            if (const char *e = dev_env("CDC_LPIPS_BUDGET_MB")) budget = (size_t)std::max(1, atoi(e)) << 20;
+            const int max_pairs = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, budget / lpips_pair_bytes(H, W)));
+            const int pairs = ceil_div(B, ceil_div(B, max_pairs));
+            if ((rc = build_lpips_program(h, pairs, H, W))) return rc;
+            const int cap = pairs;                                  // (a program kept from a larger call may hold more: its rows are not used)
+            hipStream_t st = pick_stream(h, stream, mem);
+            DevPool d;
+            double *dres = nullptr;
+            if (d.get(&dres, (size_t)B * LPIPS_TAPS) != hipSuccess) return fail(h, CDC_ERR_NOMEM, "lpips: hipMalloc failed");
+            hipError_t e = hipSuccess;
+            if (mem == CDC_MEM_HOST) {
+                for (int i = 0; i < 2 && e == hipSuccess; ++i) {
+                    uint8_t *p;
+                    if (d.get(&p, bytes[i]) != hipSuccess) return fail(h, CDC_ERR_NOMEM, "lpips: hipMalloc failed");
+                    e = hipMemcpyAsync(p, mv[i].data, bytes[i], hipMemcpyHostToDevice, st);
+                    mv[i].data = p;
+                }
+            }
+            if (e == hipSuccess && (rc = arm_range_guard(h, st, false))) e = hipErrorUnknown;
+            h->prof_now = true;
+            for (int c0 = 0; c0 < B && e == hipSuccess && !rc; c0 += cap) {
+                const int n = std::min(cap, B - c0);
+                MetricView ca = mv[0], cb = mv[1];
+                ca.data = (const char *)mv[0].data + (size_t)c0 * img_bytes[0];
+                cb.data = (const char *)mv[1].data + (size_t)c0 * img_bytes[1];
+                e = lpips_in_launch(ca, cb, n, H, W, h->lp_shift, h->lp_scale, h->in_x, st);
+                if (e == hipSuccess) rc = run_ops(h, 2 * n, st);
+                if (e == hipSuccess && !rc)
+                    e = hipMemcpyAsync(dres + (size_t)c0 * LPIPS_TAPS, h->lp_res, sizeof(double) * n * LPIPS_TAPS, hipMemcpyDeviceToDevice, st);
+            }
+            std::vector<double> res((size_t)B * LPIPS_TAPS);
+            if (e == hipSuccess && !rc) e = hipMemcpyAsync(res.data(), dres, sizeof(double) * res.size(), hipMemcpyDeviceToHost, st);
+            const hipError_t es = hipStreamSynchronize(st);       // (after an error too: nothing queued may still use what d frees)
+            if (rc) return rc;
+            if (e == hipSuccess) e = es;
+            if (e != hipSuccess) return fail(h, CDC_ERR_HIP, "lpips: %s", hipGetErrorString(e));
+            if ((rc = range_check(h, {}, B, st))) return rc;       // the flag: a non-finite accumulator or layer value
+            for (int i = 0; i < B; ++i) {
+                double s = 0.0;
+                for (int l = 0; l < LPIPS_TAPS; ++l) s += res[(size_t)i * LPIPS_TAPS + l];
+                lpips[i] = s;
+            }
+            if (layers) memcpy(layers, res.data(), sizeof(double) * res.size());
+            return CDC_OK;
+        });
+    });
+}
+
 int cdc_padded_size(cdc_handle *h, int H, int W, int *Hp, int *Wp) {
     if (!h) return CDC_ERR_INVALID;
     if (H < 1 || W < 1 || !Hp || !Wp) return fail(h, CDC_ERR_INVALID, "padded_size: H=%d W=%d", H, W);
@@ -721,6 +818,7 @@ int cdc_padded_size(cdc_handle *h, int H, int W, int *Hp, int *Wp) {
         case HandleKind::Unet: shift = h->cfg.n_dim_mults - 1; break;                              // one Downsample per level but the last
         case HandleKind::Encoder: shift = (int)h->enc_dims.size() - 1 + (int)h->henc_dims.size() - 2; break;   // enc levels + stride-2 hyper_enc layers
         case HandleKind::ContextDecoder: shift = (int)h->rev_dims.size() - 1; break;               // one Upsample per level
+        case HandleKind::Lpips: break;                                                             // any size (floor-mode pooling)
         case HandleKind::HyperDecoder:
             if (h->ent_pixels < 1) return fail(h, CDC_ERR_STATE, "padded_size: cdc_entropy_set_image_scale has not been called on this hyper-decoder handle");
             M = h->ent_pixels;

@@ -279,6 +279,19 @@ int metric_next_side(int s);                                       // side of th
 bool metric_layout(int B, int H, int W, bool psnr, bool msssim, MetricLayout *L);   // false: too small for five scales, or too many tiles
 hipError_t metric_psnr_launch(const MetricView &a, const MetricView &b, int B, int H, int W, const MetricLayout &L, void *work, hipStream_t st);
 hipError_t metric_msssim_launch(const MetricView &a, const MetricView &b, int B, const MetricLayout &L, void *work, hipStream_t st);
+// lpips_kernels.hip (cdc_lpips): what LPIPS-VGG needs beside the planner's convolutions.  Operands as MetricView (device pointers).
+constexpr int LPIPS_TAPS = 5;
+// both operands' H x W windows -> out [2 n][3][H][W]: (2 u - 1 - shift[c]) / scale[c], operand a in rows 0 .. n-1, b in rows n .. 2n-1
+hipError_t lpips_in_launch(const MetricView &a, const MetricView &b, int n, int H, int W, const float shift[3], const float scale[3], float *out,
+                           hipStream_t st);
+// max_pool2d(2, 2), floor mode, over `planes` contiguous fp32 planes [H][W] -> [H / 2][W / 2]
+hipError_t maxpool2_launch(const float *in, float *out, long long planes, int H, int W, hipStream_t st);
+// The head of one tap: f [2 n][C][HW] (batch stride bs; operand 0 of pair i in row i, operand 1 in row n + i), w [C] ->
+// res[i][layer] = mean over the map of sum_c w_c (f0_c / (|f0| + 1e-10) - f1_c / (|f1| + 1e-10))^2, float64.  partials: n *
+// lpips_head_blocks(HW) doubles.  A non-finite result sets *fault (may be null).
+int lpips_head_blocks(int HW);
+hipError_t lpips_head_launch(const float *f, long long bs, int C, int HW, const float *w, int n, double *partials, double *res, int layer,
+                             int *fault, hipStream_t st);
 hipError_t unfold_x_launch(const float *src, long long src_bs, float *dst, long long dst_bs, int C, int KW,
                            int pad, int H, int W, int B, hipStream_t st);
 

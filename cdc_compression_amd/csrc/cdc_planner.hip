@@ -24,7 +24,7 @@ struct Builder {
         op.id = (int)h->op_ms.size();
         h->op_ms.push_back(0); h->op_n.push_back(0); h->op_flops.push_back(op.flops);
         char buf[160];
-        const char *kinds[] = {"conv", "ln", "temb", "kstats", "ctxp", "ctxr", "ctxf", "combine", "ddim", "copy", "unfold", "kvctx", "lnconv", "convpf", "pfpack", "convws", "convws1", "vbr"};
+        const char *kinds[] = {"conv", "ln", "temb", "kstats", "ctxp", "ctxr", "ctxf", "combine", "ddim", "copy", "unfold", "kvctx", "lnconv", "convpf", "pfpack", "convws", "convws1", "vbr", "maxpool", "lpips_head"};
         if (op.kind == Op::PFPACK && op.pk.c4 == 2) kinds[Op::PFPACK] = "pfunpack";
         if (op.kind == Op::CONV)
             snprintf(buf, sizeof buf, "conv %dx%d s%d %4d->%-4d out %3dx%-3d MB%d NPW%d WN%d g%d tg%d ipw%d ks%d%s%s%s%s%s", op.conv.KH,
@@ -52,6 +52,10 @@ struct Builder {
             snprintf(buf, sizeof buf, "lnconv C=%d N=%d nsplit=%d", op.lnc.C, op.lnc.N, op.lnc.nsplit);
         else if (op.kind == Op::VBR)
             snprintf(buf, sizeof buf, "vbr C=%d HW=%d%s", op.vb.C, op.vb.HW, op.vb.leaky ? " leaky" : "");
+        else if (op.kind == Op::MAXPOOL)
+            snprintf(buf, sizeof buf, "maxpool2 C=%d in %dx%d", op.mp.C, op.mp.H, op.mp.W);
+        else if (op.kind == Op::LPHEAD)
+            snprintf(buf, sizeof buf, "lpips_head tap %d C=%d HW=%d", op.lh.layer, op.lh.C, op.lh.HW);
         else if (op.kind == Op::KSTATS || op.kind == Op::CTXP || op.kind == Op::CTXR || op.kind == Op::CTXF)
             snprintf(buf, sizeof buf, "%s C=%d N=%d nsplit=%d", op.at_one ? "ctx1" : kinds[op.kind], op.at.C, op.at.N, op.at_one ? 1 : op.at.nsplit);
         else
@@ -214,6 +218,7 @@ struct Builder {
         bool emit_pf = false;                          // `out` holds final values: also write its PF twin (if it has one)
         bool pf_only = false;                          // plan with conv_pf_kernel or return false
         bool no_f32 = false;                           // PF path only: nobody reads the fp32 copy of `out`
+        bool no_ksplit = false;                        // a linear epilogue that must stay ONE launch: no split-K scratch + sum pass
         int uf_c = 0, uf_pad = 0;                      // unfold on load (ConvArgs::uf_c): s0 is the uf_c-channel image, w a KH x 1 layer over KW*uf_c channels
         // a linear epilogue: bias and residual at most (no LayerNorm, activation, shift, statistics, hoisted partial sums, res_conv)
         bool linear_epilogue() const { return !ln_g && !relu && !shift && !stat_mean && !pre_add && !res3_w; }
@@ -616,7 +621,7 @@ struct Builder {
             return true;
         if (!o.uf_c && try_ws1(w, s0, C0, bs0, s1, bs1, H, W, out, out_bs, o, need_all, prof)) return true;
         if (!o.uf_c && try_pw(w, s0, C0, bs0, s1, bs1, H, W, out, out_bs, o, need_all, prof)) return true;
-        const bool linear_ep = !need_all && o.linear_epilogue() && w.nz == 1 && !w.transposed;
+        const bool linear_ep = !need_all && o.linear_epilogue() && w.nz == 1 && !w.transposed && !o.no_ksplit;
         s.max_ksplit = o.max_ksplit > 1 ? o.max_ksplit : (linear_ep ? 4 : 1);
         if (need_all && (w.Cout % 32)) return false;
         ConvPlan plan;
@@ -1062,6 +1067,7 @@ void free_program(cdc_handle *h) {
     h->p_batch1_plan = false;
     h->time_steps_B = 0;
     h->d_rate = nullptr;           // (it lived in act_allocs)
+    h->lp_res = nullptr;
 }
 
 // Builds the launch program of Unet.forward for batch B at H x W (unet.py:106-135).
@@ -1336,6 +1342,91 @@ int build_ctxdec_program(cdc_handle *h, int B, int hl, int wl) {
         if (bd.rc) return bd.rc;
     }
     h->pB = B; h->pH = hl; h->pW = wl;
+    return CDC_OK;
+}
+
+// ---- LPIPS-VGG (cdc_lpips) ---------------------------------------------------------------------------------------------------------
+// VGG16's features up to relu5_3: widths per level, `|` = max_pool2d(2, 2) in floor mode; the tap of a level is its last ReLU.
+static const int kVggLevelConvs[LPIPS_TAPS] = {2, 2, 3, 3, 3};
+static const int kVggLevelWidth[LPIPS_TAPS] = {64, 128, 256, 512, 512};
+
+// fp32 activations of one pair (both operands): the scaled input, every convolution output and every pooled map
+size_t lpips_pair_bytes(int H, int W) {
+    size_t px = (size_t)3 * H * W;
+    int hh = H, ww = W;
+    for (int l = 0; l < LPIPS_TAPS; ++l) {
+        if (l) { hh /= 2; ww /= 2; px += (size_t)kVggLevelWidth[l - 1] * hh * ww; }
+        px += (size_t)kVggLevelConvs[l] * kVggLevelWidth[l] * hh * ww;
+    }
+    px += (size_t)2 * kVggLevelWidth[2] * (H / 4) * (W / 4);       // the two partial-sum buffers of the sliced layers
+    return 2 * px * sizeof(float);
+}
+
+// One program over 2 * pairs images: rows 0 .. pairs-1 the first operands, rows pairs .. 2 pairs-1 the second (a call with n < pairs
+// pairs runs it over 2 n rows, second operands from row n: the batch strides do not depend on the row count).  Every convolution is a
+// Builder::conv with bias + ReLU on the existing kernels, planned as for ONE image (planB = 1, like the entropy coder's hyper decoder):
+// an image's features depend neither on the pairs of its chunk nor on the chunking.  The activations are fp32 NCHW without plane
+// twins (the pooling kernel writes fp32 only), so every layer takes the register-staged kernels of Builder::conv's generic path.
+// Accuracy: the head subtracts two normalised feature vectors that differ by a few per cent, so a relative error of the features
+// reaches the result ~50 times larger.  The kernels add a layer's K = 9 Cin products into one fp32 accumulator, and at K = 4608 (the
+// 512-channel layers) the rounding of that chain, ~sqrt(K) ulp, is most of the features' error.  A layer of 256 / 512 input
+// channels therefore runs as 2 / 4 convolutions over 128 input channels each (K = 1152, the chain of the 128-channel layers): slice 0
+// adds the bias, every further slice adds the partial sums of the one before in its epilogue (ConvOpts::pre_add), the last applies
+// the ReLU.  Same flops; the partial planes of these small maps are the only extra traffic.
+int build_lpips_program(cdc_handle *h, int pairs, int H, int W) {
+    if (h->pB >= 2 * pairs && h->pH == H && h->pW == W) return CDC_OK;
+    free_program(h);
+    const int B = 2 * pairs;
+    Builder bd{h, B, &h->act_allocs};
+    bd.planB = 1;
+    h->in_x = bd.dalloc((size_t)B * 3 * H * W);
+    h->lp_res = reinterpret_cast<double *>(bd.dalloc((size_t)pairs * LPIPS_TAPS * 2));
+    int max_blocks = 1;                 // one partial per workgroup of the widest head launch
+    for (int l = 0; l < LPIPS_TAPS; ++l) max_blocks = std::max(max_blocks, lpips_head_blocks((H >> l) * (W >> l)));
+    double *partials = reinterpret_cast<double *>(bd.dalloc((size_t)pairs * max_blocks * 2));
+    if (bd.rc) return bd.rc;
+    Act x; x.p = h->in_x; x.C = 3; x.H = H; x.W = W;
+    size_t ci = 0;
+    int layer = 0;
+    float *part[2] = {nullptr, nullptr};    // ping-pong partial sums of the sliced layers
+    for (int l = 0; l < LPIPS_TAPS; ++l) {
+        if (l) {
+            Act y = bd.new_act(x.C, x.H / 2, x.W / 2, false);
+            if (bd.rc) return bd.rc;
+            Op op; op.kind = Op::MAXPOOL; op.prof = PC_SMALL;
+            op.mp = {x.p, y.p, x.C, x.H, x.W};
+            op.bytes = 4.0 * B * x.C * ((double)x.H * x.W + (double)y.H * y.W);
+            bd.emit(op);
+            x = y;
+        }
+        for (int k = 0; k < kVggLevelConvs[l]; ++k, ++layer) {
+            const int parts = h->lp_parts[layer];
+            Act y = bd.new_act(kVggLevelWidth[l], x.H, x.W, false);
+            if (parts > 1 && !part[0]) {        // (the first sliced layer has the largest output of all of them)
+                part[0] = bd.dalloc((size_t)B * y.bs());
+                part[1] = bd.dalloc((size_t)B * y.bs());
+            }
+            for (int p = 0; p < parts; ++p) {
+                const ConvW &cw = h->hconvs[ci++];
+                const bool last = p == parts - 1;
+                Builder::ConvOpts o;
+                o.relu = last ? 1 : 0;
+                o.no_ksplit = true;             // (slice 0 has a plain bias epilogue: keep it one launch, its memory is budgeted)
+                if (p) { o.pre_add = part[(p - 1) & 1]; o.no_bias = true; }
+                bd.conv(cw, x.p + (size_t)p * cw.Cin * x.H * x.W, cw.Cin, x.bs(), nullptr, 0, x.H, x.W, last ? y.p : part[p & 1], y.bs(), o, false,
+                        PC_CONV3);
+                if (bd.rc) return bd.rc;
+            }
+            x = y;
+        }
+        h->taps["relu" + std::to_string(l + 1) + "_" + std::to_string(kVggLevelConvs[l])] = x;
+        Op op; op.kind = Op::LPHEAD; op.prof = PC_SMALL;
+        op.lh = {x.p, x.bs(), x.C, x.H * x.W, h->lp_lin[l], partials, h->lp_res, l, bd.fault_flag()};
+        op.bytes = 2.0 * 4.0 * B * x.C * x.H * x.W;
+        bd.emit(op);
+        if (bd.rc) return bd.rc;
+    }
+    h->pB = B; h->pH = H; h->pW = W;
     return CDC_OK;
 }
 

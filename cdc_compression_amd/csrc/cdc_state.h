@@ -75,7 +75,7 @@ struct AttnW { std::string prefix; int C; ConvW qkv, out; float *ng, *nb;
                unsigned short *kvWh = nullptr; float kv_scale_inv = 1.f; };   // fp16 planes {WH, WL, WH2} of W' 2^s   // fused front half: (W_kv diag(g))^T [C][2C], W_kv b_ln [2C]   // folded output; uq = Wq b_ln
 
 struct Op {
-    enum Kind { CONV, LN, TEMB, KSTATS, CTXP, CTXR, CTXF, COMBINE, DDIM, COPY, UNFOLD, KVCTX, LNCONV, CONVPF, PFPACK, CONVWS, CONVWS1, VBR } kind;
+    enum Kind { CONV, LN, TEMB, KSTATS, CTXP, CTXR, CTXF, COMBINE, DDIM, COPY, UNFOLD, KVCTX, LNCONV, CONVPF, PFPACK, CONVWS, CONVWS1, VBR, MAXPOOL, LPHEAD } kind;
     int prof = PC_SMALL;
     int id = -1;                  // index into cdc_handle::op_ms (per-op timing table, debug aid)
     char label[96] = {0};
@@ -105,6 +105,8 @@ struct Op {
     struct { const float *src; long long src_bs; float *dst; long long dst_bs; int C, KW, pad, H, W; } uf;
     struct { const float *src; long long src_bs; void *dst; long long dst_bs; int C, H, W; int c4; } pk;   // PFPACK (c4: fp32 -> accumulator order)
     struct { float *x; long long bs; int C, HW; const float *rate, *p; int leaky; } vb;   // VBR: in-place VBRCondition (+ LeakyReLU 0.2)
+    struct { const float *src; float *dst; int C, H, W; } mp;                               // MAXPOOL: max_pool2d(2, 2), floor mode (lpips_kernels.hip)
+    struct { const float *f; long long bs; int C, HW; const float *w; double *partials, *res; int layer; int *fault; } lh;   // LPHEAD: one LPIPS tap, run over B / 2 pairs
 };
 
 struct VbrW { int C = 0; float *p = nullptr; };   // one VBRCondition site: [scale.weight | scale.bias | shift.weight | shift.bias], C each
@@ -118,8 +120,9 @@ static int default_arith() {      // CDC_ARITH=0 selects the three-plane bf16 ar
     return e ? (atoi(e) ? 1 : 0) : 1;
 }
 
-// ContextDecoder: Compressor.decode; HyperDecoder: hyper_dec (+ the rate estimate and the entropy coder); Encoder: enc + hyper_enc
-enum class HandleKind { Unet, ContextDecoder, HyperDecoder, Encoder };
+// ContextDecoder: Compressor.decode; HyperDecoder: hyper_dec (+ the rate estimate and the entropy coder); Encoder: enc + hyper_enc;
+// Lpips: the LPIPS-VGG network of cdc_lpips
+enum class HandleKind { Unet, ContextDecoder, HyperDecoder, Encoder, Lpips };
 
 struct cdc_handle {
     cdc_unet_config cfg;
@@ -203,6 +206,12 @@ struct cdc_handle {
     int seeds_cap = 0;
     std::vector<unsigned long long> h_seeds;   // staging copy: the caller's array may go away before the copy has run
     int time_steps_B = 0;
+    // Lpips: the thirteen VGG16 layers live in hconvs; the five `lin` weight vectors, the scaling layer, and the program's result area
+    // (a layer of >= 256 input channels is packed as lp_parts[layer] slices of 128 input channels, consecutive in hconvs)
+    std::vector<int> lp_parts;
+    float *lp_lin[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    float lp_shift[3] = {-.030f, -.088f, -.188f}, lp_scale[3] = {.458f, .448f, .450f};
+    double *lp_res = nullptr;            // [pairs of the program][5] layer values of the running chunk (program buffer)
     void *metric_work = nullptr;         // cdc_distortion: partial sums and the pooled MS-SSIM pyramids of both operands, grown on demand
     size_t metric_cap = 0;
     int op_stress_n = 0;                 // cdc_op_stress: extra executions of every cdc_op_* program, results compared on the device
@@ -267,6 +276,11 @@ int build_program(cdc_handle *h, int B, int H, int W);
 int build_encoder_program(cdc_handle *h, int B, int H, int W);
 int build_hyperdec_program(cdc_handle *h, int B, int hh, int wh, bool batch1_plan = false);
 int build_ctxdec_program(cdc_handle *h, int B, int hl, int wl);
+// LPIPS-VGG over up to `pairs` image pairs of H x W (2 pairs rows: first operands, then second operands); every kernel variant is
+// planned as for one image, so a pair's result does not depend on the pairs beside it.  h->pB = 2 pairs is the program's capacity.
+int build_lpips_program(cdc_handle *h, int pairs, int H, int W);
+size_t lpips_pair_bytes(int H, int W);   // activation bytes of one pair
+void build_lpips_manifest(cdc_handle *h);
 // ---- variable bitrate: the manifest of a compressor handle (cdc_weights.hip), the rates of one call (cdc_api.hip)
 void build_compressor_manifest(cdc_handle *h);
 int stage_rate(cdc_handle *h, const float *rates, int B, hipStream_t st);

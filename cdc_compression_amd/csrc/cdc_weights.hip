@@ -151,6 +151,30 @@ void build_compressor_manifest(cdc_handle *h) {
     }
 }
 
+// LPIPS-VGG (include/cdc_hip.h: cdc_lpips): the names of lpips 0.1.4's LPIPS(net="vgg").state_dict() below its prefix, written
+// from that source as remembered -- a name that does not load from a real checkpoint is corrected in this table alone.
+// net.slice{k}.{i}: torchvision's vgg16().features[i] (the Conv2d modules; ReLU and MaxPool2d hold no parameters).
+static const struct { int slice, index, cin, cout; } kLpipsConvs[13] = {
+    {1, 0, 3, 64}, {1, 2, 64, 64}, {2, 5, 64, 128}, {2, 7, 128, 128}, {3, 10, 128, 256}, {3, 12, 256, 256}, {3, 14, 256, 256},
+    {4, 17, 256, 512}, {4, 19, 512, 512}, {4, 21, 512, 512}, {5, 24, 512, 512}, {5, 26, 512, 512}, {5, 28, 512, 512}};
+static const int kLpipsLinC[LPIPS_TAPS] = {64, 128, 256, 512, 512};
+static const int kLpipsSlice = 128;     // input channels per slice of a wide layer
+static std::string lpips_conv_name(int i) {
+    return "net.slice" + std::to_string(kLpipsConvs[i].slice) + "." + std::to_string(kLpipsConvs[i].index);
+}
+
+void build_lpips_manifest(cdc_handle *h) {
+    for (int i = 0; i < 13; ++i) {
+        add_param(h, lpips_conv_name(i) + ".weight", {kLpipsConvs[i].cout, kLpipsConvs[i].cin, 3, 3});
+        add_param(h, lpips_conv_name(i) + ".bias", {kLpipsConvs[i].cout});
+    }
+    for (int k = 0; k < LPIPS_TAPS; ++k) add_param(h, "lin" + std::to_string(k) + ".model.1.weight", {1, kLpipsLinC[k], 1, 1});
+    // optional: the copies the package's ModuleList registers (they must equal lin{k}), and the scaling layer's buffers
+    for (int k = 0; k < LPIPS_TAPS; ++k) add_param(h, "lins." + std::to_string(k) + ".model.1.weight", {1, kLpipsLinC[k], 1, 1}, true);
+    add_param(h, "scaling_layer.shift", {1, 3, 1, 1}, true);
+    add_param(h, "scaling_layer.scale", {1, 3, 1, 1}, true);
+}
+
 // ------------------------------------------------------------------------------------------------
 // weight upload / repacking
 // ------------------------------------------------------------------------------------------------
@@ -591,6 +615,37 @@ int cdc_finalize_weights(cdc_handle *h) {
                 }
             }
             if ((rc = upload(h, pk.data(), pk.size(), &h->d_prior, &h->weight_allocs))) return rc;
+        }
+        h->shift_bs = 0;
+        h->finalized = true;
+        return CDC_OK;
+    }
+    if (h->kind == HandleKind::Lpips) {
+        // A layer of 256 / 512 input channels is packed as 2 / 4 slices of kLpipsSlice input channels: the program runs them as a chain
+        // of convolutions, each adding the partial sums of the one before (build_lpips_program says why).
+        h->hconvs.clear();
+        h->lp_parts.clear();
+        for (int i = 0; i < 13; ++i) {
+            const int cin = kLpipsConvs[i].cin, parts = cin > kLpipsSlice ? cin / kLpipsSlice : 1;
+            h->lp_parts.push_back(parts);
+            for (int p = 0; p < parts; ++p) {
+                ConvW cw;
+                if ((rc = pack_named_conv(h, lpips_conv_name(i) + ".weight", lpips_conv_name(i) + ".bias", 1, 1, false, &cw,
+                                          parts > 1 ? p * kLpipsSlice : 0, parts > 1 ? kLpipsSlice : 0))) return rc;
+                h->hconvs.push_back(cw);
+            }
+        }
+        for (int k = 0; k < LPIPS_TAPS; ++k) {
+            const std::string lin = "lin" + std::to_string(k) + ".model.1.weight", dup = "lins." + std::to_string(k) + ".model.1.weight";
+            if (h->params[h->pindex.at(dup)].loaded && hostp(h, dup) != hostp(h, lin))
+                return fail(h, CDC_ERR_INVALID, "\"%s\" differs from \"%s\"", dup.c_str(), lin.c_str());
+            if ((rc = upload_param(h, lin, &h->lp_lin[k]))) return rc;
+        }
+        const float shift0[3] = {-.030f, -.088f, -.188f}, scale0[3] = {.458f, .448f, .450f};
+        const bool has_shift = h->params[h->pindex.at("scaling_layer.shift")].loaded, has_scale = h->params[h->pindex.at("scaling_layer.scale")].loaded;
+        for (int c = 0; c < 3; ++c) {
+            h->lp_shift[c] = has_shift ? hostp(h, "scaling_layer.shift")[c] : shift0[c];
+            h->lp_scale[c] = has_scale ? hostp(h, "scaling_layer.scale")[c] : scale0[c];
         }
         h->shift_bs = 0;
         h->finalized = true;

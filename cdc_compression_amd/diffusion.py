@@ -22,7 +22,7 @@ import ctypes
 
 import numpy as np
 
-from . import _lib, frame
+from . import _lib, frame, lpips
 from .parallel import expand_seeds
 from .schedule import SampleSchedule
 from .unet import _Arg, _current_stream, _is_torch, _result_like
@@ -41,6 +41,7 @@ class _GaussianDiffusionBase:
         self.sample_steps = None
         self.training = False
         self._sched = None
+        self.loss_fn_vgg = None      # LpipsVGG, when load_state_dict() found the reference's LPIPS-VGG weights
 
     def eval(self):
         self.training = False
@@ -51,17 +52,23 @@ class _GaussianDiffusionBase:
         self.denoise_fn.to(device)
         if hasattr(self.context_fn, "to"):
             self.context_fn.to(device)
+        if self.loss_fn_vgg is not None:
+            self.loss_fn_vgg.to(device)
         return self
 
     def load_state_dict(self, state_dict, strict=True):
         """Accepts the reference GaussianDiffusion.state_dict(): keys "denoise_fn.*" feed the HIP
-        U-Net; "context_fn.*" are forwarded to context_fn if it has load_state_dict; train_* buffers
-        are derived constants and ignored."""
+        U-Net; "context_fn.*" are forwarded to context_fn if it has load_state_dict; "loss_fn_vgg.*" (the LPIPS-VGG
+        network of a checkpoint trained with an LPIPS weight) become `self.loss_fn_vgg`, an LpipsVGG whose library handle
+        is created on first use, and evaluate() then reports "lpips"; train_* buffers are derived constants and ignored."""
         un = {k[len("denoise_fn."):]: v for k, v in state_dict.items() if k.startswith("denoise_fn.")}
         self.denoise_fn.load_state_dict(un, strict=strict)
         cf = {k[len("context_fn."):]: v for k, v in state_dict.items() if k.startswith("context_fn.")}
         if cf and hasattr(self.context_fn, "load_state_dict"):
             self.context_fn.load_state_dict(cf, strict=strict)
+        if any(k.startswith(lpips.PREFIX) for k in state_dict):
+            self.loss_fn_vgg = lpips.LpipsVGG(device=getattr(self.denoise_fn, "device_index", 0))
+            self.loss_fn_vgg.load_state_dict(state_dict, prefix=lpips.PREFIX, strict=strict)
         return self
 
     # ---- images of any size -------------------------------------------------------------------
@@ -121,7 +128,8 @@ class _GaussianDiffusionBase:
     def evaluate(self, images, *args, as_saved=True, **kwargs):
         """compress() with the other axis of the rate-distortion plot: takes compress()'s arguments, runs its path once and returns
         {"reconstruction": what compress() returns, "bpp": [B], "psnr": float64 [B], "ms_ssim": float64 [B], or None when
-        min(H, W) <= 160}.  The distortion is measured on the device (cdc_compression_amd.metrics), on the padded frame's H x W window
+        min(H, W) <= 160}, and "lpips": float64 [B] when the loaded state dict carried the LPIPS-VGG weights (self.loss_fn_vgg).
+        The distortion is measured on the device (cdc_compression_amd.metrics), on the padded frame's H x W window
         against `images` as given (float32 or uint8); as_saved: float32 operands through the uint8 image the reference's script would
         save (metrics.psnr(model, reconstruction, images, as_saved=True) gives the same figures)."""
         from . import metrics
@@ -130,7 +138,10 @@ class _GaussianDiffusionBase:
         bound.pop("bpp_return_mean", None)                    # bpp comes per image
         rec, bpp, H, W = self._frame_of(**bound)
         ps, ms = metrics.distortion(self.denoise_fn, rec, images, size=(H, W), as_saved=as_saved)
-        return {"reconstruction": self._window(rec, H, W), "bpp": bpp, "psnr": ps, "ms_ssim": ms}
+        out = {"reconstruction": self._window(rec, H, W), "bpp": bpp, "psnr": ps, "ms_ssim": ms}
+        if self.loss_fn_vgg is not None:
+            out["lpips"] = metrics.lpips(self.loss_fn_vgg, rec, images, size=(H, W), as_saved=as_saved)
+        return out
 
     # ---- schedule ---------------------------------------------------------------------------
     def set_sample_schedule(self, sample_steps, device=None):
@@ -290,6 +301,7 @@ class GaussianDiffusionX(_GaussianDiffusionBase):
         self._init_common(denoise_fn, context_fn, num_timesteps, pred_mode, var_schedule)
         self.ae_fn = None
         self.loss_type = loss_type
+        self.aux_loss_weight = aux_loss_weight      # (the reference builds its LPIPS-VGG network when this is > 0)
         self.lagrangian_beta = lagrangian
 
     def p_sample_loop(self, shape, context, clip_denoised=False, init=None, eta=0, seed=None, gamma=None):
@@ -318,6 +330,7 @@ class GaussianDiffusionEps(_GaussianDiffusionBase):
             raise NotImplementedError('eps-param tree: only pred_mode="noise" reaches ddim()')
         self.channels = channels
         self.clip_noise = clip_noise
+        self.aux_loss_weight = aux_loss_weight      # (the reference builds its LPIPS-VGG network when this is > 0)
         self.vbr = vbr
 
     def p_sample_loop(self, shape, context, sample_mode, init=None, eta=0, seed=None, gamma=None):

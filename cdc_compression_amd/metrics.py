@@ -5,7 +5,8 @@ operands' common shape), so a padded decoder frame is measured beside the image 
 are numpy, torch-cpu or torch-cuda tensors, float32 (in [-1, 1], mapped as `clamp(-1, 1) / 2 + 0.5`) or uint8 (`v / 255`);
 `as_saved=True` measures a float32 operand through the uint8 image the reference's script would save.  The header states the
 definition (PSNR: the reference's per-image `batch_psnr`; MS-SSIM: the conventions of pytorch-msssim 0.2.1, `data_range=1`).
-Results are float64 NumPy arrays of `B` values."""
+`lpips` is the third axis: LPIPS-VGG of lpips 0.1.4 on the same operands (cdc_lpips; the model is an `lpips.LpipsVGG`, which holds
+the network's weights).  Results are float64 NumPy arrays of `B` values."""
 import ctypes
 import math
 
@@ -15,6 +16,7 @@ from . import _lib, frame
 from .unet import _Arg, _current_stream, _is_torch
 
 MS_SSIM_MIN_SIDE = 161      # min(H, W) > 160: five scales of an 11-tap window
+LPIPS_MIN_SIDE = 16         # four floor-mode poolings leave at least one pixel
 
 
 def _is_f32(t):
@@ -55,11 +57,8 @@ def _check_args(a, b, size, as_saved):
     return shapes[0][0], H, W, saved
 
 
-def _distortion(model, a, b, size, as_saved, what, components=False):
-    B, H, W, saved = _check_args(a, b, size, as_saved)
-    if what & _lib.CDC_METRIC_MSSSIM and min(H, W) < MS_SSIM_MIN_SIDE:
-        raise ValueError(f"MS-SSIM needs min(H, W) > 160, got {H} x {W}")
-    h, dev = model._handle(), model.device_index
+def _views(a, b, saved, dev):
+    """The two operands as (pointer holders, cdc_image_view structures) in one memory space."""
     args = [frame._ArgU8(t, dev) if frame.is_uint8(t) else _Arg(t, dev) for t in (a, b)]
     if args[0].mem != args[1].mem:       # one mem_kind per call: a host operand joins the other on the device
         import torch
@@ -67,6 +66,15 @@ def _distortion(model, a, b, size, as_saved, what, components=False):
                 (frame._ArgU8 if x.keep.dtype == np.uint8 else _Arg)(torch.from_numpy(x.keep).to(f"cuda:{dev}"), dev) for x in args]
     views = [_lib.ImageView(x.ptr, _lib.CDC_ELEM_U8 if frame.is_uint8(t) else _lib.CDC_ELEM_F32, x.shape[2], x.shape[3], int(s))
              for x, t, s in zip(args, (a, b), saved)]
+    return args, views
+
+
+def _distortion(model, a, b, size, as_saved, what, components=False):
+    B, H, W, saved = _check_args(a, b, size, as_saved)
+    if what & _lib.CDC_METRIC_MSSSIM and min(H, W) < MS_SSIM_MIN_SIDE:
+        raise ValueError(f"MS-SSIM needs min(H, W) > 160, got {H} x {W}")
+    h, dev = model._handle(), model.device_index
+    args, views = _views(a, b, saved, dev)
     ps, ms, comp = np.empty(B, np.float64), np.empty(B, np.float64), np.empty((B, 5, 3), np.float64)
     p = lambda v: v.ctypes.data_as(ctypes.POINTER(ctypes.c_double))     # noqa: E731
     mem = args[0].mem
@@ -95,6 +103,21 @@ def distortion(model, a, b, size=None, as_saved=False):
         return psnr(model, a, b, size, as_saved), None
     ps, ms, _ = _distortion(model, a, b, size, as_saved, _lib.CDC_METRIC_PSNR | _lib.CDC_METRIC_MSSSIM)
     return ps, ms
+
+
+def lpips(model, a, b, size=None, as_saved=False, return_layers=False):
+    """LPIPS-VGG per image over the window, float64 [B] (H, W >= 16).  `model`: an `LpipsVGG` with loaded weights.
+    return_layers: also [B, 5], the values of the taps relu1_2 ... relu5_3 whose sum the distance is."""
+    B, H, W, saved = _check_args(a, b, size, as_saved)
+    if min(H, W) < LPIPS_MIN_SIDE:
+        raise ValueError(f"LPIPS-VGG needs H, W >= 16 (four poolings), got {H} x {W}")
+    h, dev = model._ready(), model.device_index
+    args, views = _views(a, b, saved, dev)
+    out, layers = np.empty(B, np.float64), np.empty((B, 5), np.float64)
+    p = lambda v: v.ctypes.data_as(ctypes.POINTER(ctypes.c_double))     # noqa: E731
+    mem = args[0].mem
+    _lib.check(h, _lib.lib().cdc_lpips(h, ctypes.byref(views[0]), ctypes.byref(views[1]), B, H, W, p(out), p(layers), mem, _current_stream(mem)))
+    return (out, layers) if return_layers else out
 
 
 def ms_ssim_db(m):

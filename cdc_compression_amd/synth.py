@@ -107,3 +107,37 @@ def compressor_state_dict(manifest, seed=0):
             t = normal(name, shape, seed, 0.05)
         sd[name] = t
     return {n: sd[n] for n, _ in manifest}
+
+
+# VGG16's convolutions inside lpips 0.1.4's LPIPS(net="vgg"): (slice, index in torchvision's vgg16().features, Cin, Cout)
+LPIPS_VGG_CONVS = ((1, 0, 3, 64), (1, 2, 64, 64), (2, 5, 64, 128), (2, 7, 128, 128), (3, 10, 128, 256), (3, 12, 256, 256),
+                   (3, 14, 256, 256), (4, 17, 256, 512), (4, 19, 512, 512), (4, 21, 512, 512), (5, 24, 512, 512), (5, 26, 512, 512),
+                   (5, 28, 512, 512))
+LPIPS_VGG_TAP_CHANNELS = (64, 128, 256, 512, 512)
+
+
+def lpips_vgg_manifest():
+    """[(name, shape)] of the LPIPS-VGG parameters below their prefix (include/cdc_hip.h: cdc_lpips), in the library's order."""
+    man = []
+    for sl, idx, cin, cout in LPIPS_VGG_CONVS:
+        man += [(f"net.slice{sl}.{idx}.weight", (cout, cin, 3, 3)), (f"net.slice{sl}.{idx}.bias", (cout,))]
+    return man + [(f"lin{k}.model.1.weight", (1, c, 1, 1)) for k, c in enumerate(LPIPS_VGG_TAP_CHANNELS)]
+
+
+def lpips_vgg_state_dict(seed=0, prefix="", with_duplicates=False):
+    """Synthetic LPIPS-VGG parameters: He-scaled convolutions N(0, 2 / fan_in), biases 0.05 + N(0, 0.01^2), non-negative `lin`
+    weights |N(0, 1 / 32^2)| -- activations stay O(1) through the thirteen layers (below 20 on smoothed random images) and a copy of
+    such an image with Gaussian noise of sigma 0.02 ... 0.3 scores 6e-4 ... 3e-2.
+    with_duplicates: also the `lins.{k}` copies that the package's ModuleList registers."""
+    sd = {}
+    for name, shape in lpips_vgg_manifest():
+        if name.endswith(".bias"):
+            t = normal(name, shape, seed, 0.01, 0.05)
+        elif name.startswith("lin"):
+            t = np.abs(normal(name, shape, seed, 1.0 / 32.0))
+        else:
+            t = normal(name, shape, seed, float(np.sqrt(2.0 / (shape[1] * 9))))
+        sd[prefix + name] = t
+        if with_duplicates and name.startswith("lin"):
+            sd[prefix + "lins." + name[3:]] = t.copy()
+    return sd

@@ -58,11 +58,15 @@ def load_checkpoint(path):
     return torch.load(path, map_location="cpu", weights_only=False)
 
 
-def synthetic_state(diffusion, seed_unet=0, seed_ctx=15, eps=False):
+def synthetic_state(diffusion, seed_unet=0, seed_ctx=15, eps=False, lpips=None):
     """Deterministic stand-in parameters (there is no network for the published checkpoints): the generator the
-    parity fixtures use (cdc_compression_amd.synth)."""
+    parity fixtures use (cdc_compression_amd.synth).  lpips: with the "loss_fn_vgg.*" entries of a checkpoint trained with an
+    LPIPS weight (stand-in LPIPS-VGG weights); None: when the model was built with one, as the reference's is (--lpips_weight
+    other than 0 goes to the diffusion's aux_loss_weight)."""
     from cdc_compression_amd import synth
-    sd = {}
+    if lpips is None:
+        lpips = getattr(diffusion, "aux_loss_weight", 0) != 0
+    sd = synth.lpips_vgg_state_dict(seed=seed_unet, prefix="loss_fn_vgg.", with_duplicates=True) if lpips else {}
     for k, v in synth.unet_state_dict(diffusion.denoise_fn.manifest(), seed=seed_unet,
                                       final_gain=0.2 if eps else 1.0).items():
         sd["denoise_fn." + k] = v
@@ -114,6 +118,9 @@ def run_folder(diffusion, config, rank, compress_kwargs):
                 **compress_kwargs,
             )
             un = diffusion.denoise_fn
+            lp = None
+            if diffusion.loss_fn_vgg is not None and min(shape[2:]) >= 16:   # the checkpoint carried the LPIPS-VGG weights
+                lp = diffusion.loss_fn_vgg(compressed, to_be_compressed, as_saved=True)
             if SHARED.metrics:                                # the float reconstruction as it is saved, against the uint8 input
                 from cdc_compression_amd import metrics
                 ps, ms = metrics.distortion(un, compressed, to_be_compressed, as_saved=True)
@@ -125,3 +132,5 @@ def run_folder(diffusion, config, rank, compress_kwargs):
             if SHARED.metrics:
                 print("psnr:", float(ps[0]))
                 print("ms_ssim:", "n/a (needs min(H, W) > 160)" if ms is None else float(ms[0]))
+            if lp is not None:
+                print("lpips:", float(lp[0]))

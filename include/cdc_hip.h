@@ -84,7 +84,7 @@ const char *cdc_version(void);
  *                              convolution inf / NaN.  Every convolution / LayerNorm launch reports that itself, BEFORE a
  *                              fused LayerNorm + ReLU can turn it into a finite wrong value (round 4), and EVERY entry point
  *                              that runs the arithmetic (cdc_unet_forward, cdc_ddim_step, cdc_decode, cdc_decode_seeded, cdc_ctxdec_decode,
- *                              cdc_hyperdec_decode, cdc_encoder_encode, cdc_entropy_encode, the cdc_op_* operators) also
+ *                              cdc_hyperdec_decode, cdc_encoder_encode, cdc_entropy_encode, cdc_lpips, the cdc_op_* operators) also
  *                              checks its results (one small kernel + a 4-byte read-back: the call synchronises its
  *                              stream) and repeats a faulting call ONCE in CDC_ARITH_BF16X3.  The handle then STAYS in that mode (a warning is printed once;
  *                              cdc_get_arith / cdc_get_range_faults tell).  Results that are non-finite in the full-range
@@ -431,6 +431,40 @@ enum { CDC_METRIC_PSNR = 1, CDC_METRIC_MSSSIM = 2 };
 int cdc_distortion(cdc_handle *h, const cdc_image_view *a, const cdc_image_view *b, int B, int H, int W, int what,
                    double *psnr /*[B]*/, double *msssim /*[B]*/, double *components /*[B][5][3] or NULL*/,
                    int mem_kind, void *stream);
+
+/* ---- LPIPS-VGG of decoded images on the device: the perceptual axis (csrc/lpips_kernels.hip, build_lpips_program) ----------------
+ * THE DEFINITION.  LPIPS of the lpips package, version 0.1.4: LPIPS(net="vgg", lpips=True, spatial=False).forward(in0, in1,
+ * normalize=False), per image.  The reference trains with it (xparam/modules/denoising_diffusion.py:47,331-336) and its checkpoints
+ * carry the network under "loss_fn_vgg.".  The package is not installed where this library was written: the state-dict names and
+ * the place of the 1e-10 below are written from its 0.1.4 source as remembered; a name that does not load from a real checkpoint is
+ * corrected in the manifest table of csrc/cdc_weights.hip alone, not in a kernel.
+ * Operands: two cdc_image_view batches over the top-left H x W window, mapped to [0, 1] exactly as for cdc_distortion (uint8,
+ *   float32 clamped, float32 as_saved); the network input is 2 u - 1.  Nothing outside the window influences a result.
+ * Scaling layer: (x - shift[c]) / scale[c], shift = (-.030, -.088, -.188), scale = (.458, .448, .450) unless the state dict holds
+ *   "scaling_layer.shift" / "scaling_layer.scale" [1][3][1][1].
+ * Features: VGG16's thirteen 3x3 / pad 1 / stride 1 convolutions with bias and ReLU, widths
+ *   3->64->64 | 128, 128 | 256, 256, 256 | 512, 512, 512 | 512, 512, 512, where | is max_pool2d(2, 2) in floor mode (an odd side loses
+ *   its last row or column).  The taps are relu1_2, relu2_2, relu3_3, relu4_3, relu5_3.  H, W >= 16 is required.
+ * Head, per tap and pixel, in the direct form: n = f / (sqrt(sum_c f_c^2) + 1e-10) for both operands, d = sum_c w_c (n0_c - n1_c)^2
+ *   (never the three-sum expansion, which cancels to a relative 1e-4 in fp32 at LPIPS ~ 1e-3); the layer value is the mean of d over
+ *   the tap's map, the result the sum of the five layer values.  fp32 per element, fp64 sums of the per-pixel values.
+ * State-dict names (below the prefix): "net.slice1.{0,2}", "net.slice2.{5,7}", "net.slice3.{10,12,14}", "net.slice4.{17,19,21}",
+ *   "net.slice5.{24,26,28}", each ".weight" [Cout][Cin][3][3] and ".bias" [Cout]; "lin{k}.model.1.weight" [1][C][1][1], k = 0..4.
+ *   Optional (loadable, not enumerated by cdc_num_tensors): the copies "lins.{k}.model.1.weight" that the package's ModuleList
+ *   registers -- cdc_finalize_weights refuses one that differs from lin{k} -- and the two scaling_layer buffers.
+ * A result depends neither on the batch the pair sits in, nor on how the batch is split into chunks, nor on the run: every
+ * convolution is planned as for one image, there are no atomics and every sum has a fixed order.
+ *
+ * cdc_lpips_create: a handle of the LPIPS kind on `device`; parameters through cdc_load_tensor / cdc_finalize_weights.
+ * cdc_lpips: lpips [B] and layers [B][5] (may be NULL) are ALWAYS HOST float64 arrays and the call SYNCHRONISES the stream before it
+ *   returns; the image pointers follow mem_kind (CDC_MEM_HOST images are staged through device buffers); stream as for
+ *   cdc_unet_forward.  The batch runs in equal chunks whose fp32 activations (about 0.18 GB per pair at 256 x 256) stay under 4 GiB.  The
+ *   range guard applies as to every entry point: activations beyond the fp16 range repeat the call in CDC_ARITH_BF16X3.
+ *   CDC_ERR_INVALID, with a message: a handle of another kind; weights not finalized; B < 1; H or W < 16; Hf < H or Wf < W; an
+ *   unknown element kind; as_saved on a uint8 operand; a missing operand or result pointer. */
+int cdc_lpips_create(int device, cdc_handle **out);
+int cdc_lpips(cdc_handle *h, const cdc_image_view *a, const cdc_image_view *b, int B, int H, int W, double *lpips /*[B]*/,
+              double *layers /*[B][5] or NULL*/, int mem_kind, void *stream);
 
 /* quantize(x, "dequantize", offset) = round(x - offset) + offset, round = half-to-even (utils.py:72-85). */
 int cdc_dequantize(cdc_handle *h, const float *x, const float *offset, float *out, long long n, int mem_kind,

@@ -8,6 +8,9 @@ labels (bench.py --dump-ops), and an op costs  end(op) - end(previous op)  -- it
 what the iteration pays for it.  Output: per-op table, per-class and per-level sums (mean over the matched iterations).
 
 usage: trace_by_op.py <kernel_trace.csv> <ops.txt> [--batch B]
+
+--start-kernel NAME: a program that is not a DDIM iteration (cdc_lpips: NAME = lpips_in_kernel, op labels from tools/lpips_time.py
+--dump-ops): a segment runs from one dispatch of NAME to the next, NAME's own time is the first row, the labels follow it.
 """
 import argparse
 import collections
@@ -33,7 +36,8 @@ def expect(label):
     return {"ln": (("ln_kernel",), 1), "temb": (("copy_kernel", "temb_kernel"), 1), "copy": (("copy_kernel",), 1), "kvctx": (("kvctx",), 1),
             "ctxf": (("ctx_r", "fold_"), 0), "ctxp": (("ctx_partial",), 1), "ctx1": (("ctx_partial",), 1), "kstats": (("kmax_kernel",), 1),
             "pfpack": (("pf_pack_kernel", "c4_pack_kernel"), 1), "pfunpack": (("pf_unpack_kernel",), 1), "unfold": (("unfold_x_kernel",), 1),
-            "ctxr": (("ctx_reduce_kernel",), 1), "lnconv": (("lnconv_kernel",), 1)}.get(k, ((k,), 1))
+            "ctxr": (("ctx_reduce_kernel",), 1), "lnconv": (("lnconv_kernel",), 1),
+            "lpips_head": (("lpips_head_kernel", "lpips_final_kernel"), 0)}.get(k, ((k,), 1))
 
 
 def level_of(label):
@@ -62,11 +66,47 @@ def cls_of(label):
     return "first/last"
 
 
+def by_segment(a, rows, labels):
+    """Segments that START at a dispatch of a.start_kernel (the last one ends with the trace): per-op means over the matched segments."""
+    starts = [i for i, r in enumerate(rows) if r[2].startswith(a.start_kernel)]
+    per_op = collections.defaultdict(list)
+    n_ok, bad_at = 0, None
+    for s0, s1 in zip(starts, starts[1:] + [len(rows)]):
+        seq = rows[s0 + 1:s1]
+        out, i, prev_end = [(a.start_kernel, (rows[s0][1] - rows[s0][0]) * 1e-3, 1)], 0, rows[s0][1]
+        for lab in labels:
+            pref, cnt = expect(lab)
+            if i >= len(seq) or not seq[i][2].startswith(pref):
+                bad_at = (lab, seq[i][2] if i < len(seq) else "<end of segment>")
+                break
+            j = i + 1
+            if cnt == 0:
+                while j < len(seq) and seq[j][2].startswith(pref):
+                    j += 1
+            out.append((lab, (seq[j - 1][1] - prev_end) * 1e-3, j - i))
+            prev_end = seq[j - 1][1]
+            i = j
+        else:
+            n_ok += 1
+            for k, (lab, us, nk) in enumerate(out):
+                per_op[(k, lab, nk)].append(us)
+    print(f"# {a.csv}: {len(rows)} dispatches, {len(starts)} segments from {a.start_kernel}, {n_ok} matched to {len(labels)} op labels")
+    if not n_ok:
+        print(f"# first mismatch: op label '{bad_at[0]}' against dispatch '{bad_at[1][:100]}'" if bad_at else "# no segment in the trace")
+        return 1
+    tot = sum(sum(v) / len(v) for v in per_op.values())
+    print(f"# one segment, batch {a.batch}: {tot / 1e3:.3f} ms = sum of (end of the op's last kernel - end of the previous op)")
+    for (k, lab, nk), v in sorted(per_op.items()):
+        print(f"{sum(v) / len(v):9.2f} us  {nk} kernel{'s' if nk > 1 else ' '}  {lab}")
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("csv")
     ap.add_argument("ops")
     ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--start-kernel", default=None)
     a = ap.parse_args()
     rows = []
     with open(a.csv) as f:
@@ -74,6 +114,8 @@ def main():
             rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), short(r["Kernel_Name"])))
     rows.sort()
     labels = [l.rstrip("\n") for l in open(a.ops) if l.strip() and " HOIST" not in l and not l.startswith("combine")]
+    if a.start_kernel:
+        return by_segment(a, rows, labels)
     ends = [i for i, r in enumerate(rows) if r[2].startswith("ddim_")]
     per_op = collections.defaultdict(list)
     n_ok = n_bad = 0
