@@ -113,6 +113,9 @@ def lib():
     L.cdc_ctxdec_create.argtypes = [ctypes.POINTER(CtxdecConfig), _i, ctypes.POINTER(H)]
     L.cdc_ctxdec_decode.argtypes = [H, _vp, pp, _i, _i, _i, _i, _i, _vp]
     L.cdc_encoder_create.argtypes = [ctypes.POINTER(EncoderConfig), _i, ctypes.POINTER(H)]
+    L.cdc_simple_ctxdec_create.argtypes = [ctypes.POINTER(CtxdecConfig), _i, ctypes.POINTER(H)]
+    L.cdc_simple_encoder_create.argtypes = [ctypes.POINTER(EncoderConfig), _i, ctypes.POINTER(H)]
+    L.cdc_op_gdn.argtypes = [H, _vp, _vp, _vp, _vp, _i, _i, _i, _i]
     L.cdc_encoder_encode.argtypes = [H, _vp, _vp, _vp, _i, _i, _i, _i, _vp]
     L.cdc_hyperdec_create.argtypes = [ctypes.POINTER(HyperdecConfig), _i, ctypes.POINTER(H)]
     L.cdc_hyperdec_decode.argtypes = [H, _vp, _vp, _vp, _i, _i, _i, ctypes.c_float, _i, _vp]
@@ -180,7 +183,7 @@ EXPORTS = ["cdc_create", "cdc_destroy", "cdc_last_error", "cdc_version", "cdc_nu
            "cdc_op_stress", "cdc_op_stress_result", "cdc_enable_vbr", "cdc_set_bitrate_scale", "cdc_entropy_peek_bitrate_scale",
            "cdc_padded_size", "cdc_frame_pad", "cdc_frame_crop", "cdc_entropy_set_image_scale", "cdc_entropy_encode_image",
            "cdc_entropy_peek_image_size", "cdc_decode_seeded", "cdc_randn", "cdc_randn_host", "cdc_philox4x32_10",
-           "cdc_distortion", "cdc_lpips_create", "cdc_lpips"]
+           "cdc_distortion", "cdc_lpips_create", "cdc_lpips", "cdc_simple_encoder_create", "cdc_simple_ctxdec_create", "cdc_op_gdn"]
 
 
 def handle_status(handle):

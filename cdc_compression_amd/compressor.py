@@ -46,6 +46,8 @@ class NormalDistribution:
 
 class _ContextDecoder:
     _up_index = 1
+    _ctxdec_create = "cdc_ctxdec_create"        # the library's constructors of this model's context-decoder / encoder handles
+    _encoder_create = "cdc_encoder_create"
 
     def __init__(self, dim, rev_mults, out_channels, device=0, vbr=False):
         self.vbr = bool(vbr)
@@ -85,9 +87,9 @@ class _ContextDecoder:
             for i, m in enumerate(self.rev_mults):
                 cfg.rev_mults[i] = m
             h = ctypes.c_void_p()
-            rc = L.cdc_ctxdec_create(ctypes.byref(cfg), self.device_index, ctypes.byref(h))
+            rc = getattr(L, self._ctxdec_create)(ctypes.byref(cfg), self.device_index, ctypes.byref(h))
             if rc != 0:
-                raise _lib.CdcError(f"cdc_ctxdec_create failed ({rc}): {L.cdc_last_error(None).decode()}")
+                raise _lib.CdcError(f"{self._ctxdec_create} failed ({rc}): {L.cdc_last_error(None).decode()}")
             self._h = self._vbr_handle(h)
             for k, v in self._sd.items():
                 self._load_one(k, v)
@@ -387,9 +389,9 @@ class _ContextDecoder:
             for i, m in enumerate(self.hyper_dims_mults):
                 cfg.hyper_mults[i] = m
             h = ctypes.c_void_p()
-            rc = L.cdc_encoder_create(ctypes.byref(cfg), self.device_index, ctypes.byref(h))
+            rc = getattr(L, self._encoder_create)(ctypes.byref(cfg), self.device_index, ctypes.byref(h))
             if rc != 0:
-                raise _lib.CdcError(f"cdc_encoder_create failed ({rc}): {L.cdc_last_error(None).decode()}")
+                raise _lib.CdcError(f"{self._encoder_create} failed ({rc}): {L.cdc_last_error(None).decode()}")
             self._eh = self._vbr_handle(h)
         return self._eh
 
@@ -614,5 +616,24 @@ class BigCompressor(_ContextDecoder):
     def __init__(self, dim=64, dim_mults=(1, 3, 3, 3), hyper_dims_mults=(3, 3, 3), channels=3,
                  out_channels=3, vbr=False, device=0):
         super().__init__(dim, tuple(reversed(dim_mults)), out_channels, device, vbr=vbr)
+        self.dim_mults, self.hyper_dims_mults, self.channels = tuple(dim_mults), tuple(hyper_dims_mults), channels
+        self.reversed_hyper_dims = list(reversed([dim * dim_mults[-1] * 2] + [dim * m for m in hyper_dims_mults]))
+
+
+class SimpleCompressor(_ContextDecoder):
+    """epsilonparam/modules/compress_modules.py:187-257, the GDN context model: Conv2d(5, 2, 2) + GDN1 per `enc` level,
+    ConvTranspose2d(5, 2, 2, 1) + inverse GDN1 per `dec` level (no GDN on the last level of either), hyperprior and entropy coder as
+    `BigCompressor(vbr=False)`.  For the same arguments it gives a context pyramid of the same shapes, so it pairs with the same U-Net.
+    vbr=True is not available: the reference raises on its first forward."""
+    _ctxdec_create = "cdc_simple_ctxdec_create"
+    _encoder_create = "cdc_simple_encoder_create"
+
+    def __init__(self, dim=64, dim_mults=(1, 2, 3, 3), hyper_dims_mults=(3, 3, 3), channels=3,
+                 out_channels=3, vbr=False, device=0):
+        if vbr:
+            # compress_modules.py:213: the last `enc` level holds an nn.Identity where Compressor.encode (:46-47) calls vbrscaler(input, cond)
+            raise NotImplementedError("SimpleCompressor(vbr=True) does not run in the reference: its first forward raises "
+                                      "\"TypeError: Identity.forward() takes 2 positional arguments but 3 were given\"")
+        super().__init__(dim, tuple(reversed(dim_mults)), out_channels, device, vbr=False)
         self.dim_mults, self.hyper_dims_mults, self.channels = tuple(dim_mults), tuple(hyper_dims_mults), channels
         self.reversed_hyper_dims = list(reversed([dim * dim_mults[-1] * 2] + [dim * m for m in hyper_dims_mults]))

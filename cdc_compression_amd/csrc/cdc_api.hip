@@ -112,6 +112,7 @@ int run_op(cdc_handle *h, const Op &op, int B, hipStream_t st) {
         case Op::VBR:
             HIP_TRY(h, vbr_affine_launch(op.vb.x, op.vb.bs, op.vb.C, op.vb.HW, op.vb.rate, op.vb.p, op.vb.leaky, B, st));
             break;
+        case Op::GDN: HIP_TRY(h, gdn_launch(op.gdn, B, st)); break;
         case Op::MAXPOOL: HIP_TRY(h, maxpool2_launch(op.mp.src, op.mp.dst, (long long)B * op.mp.C, op.mp.H, op.mp.W, st)); break;
         case Op::LPHEAD:            // B rows = B / 2 pairs
             HIP_TRY(h, lpips_head_launch(op.lh.f, op.lh.bs, op.lh.C, op.lh.HW, op.lh.w, B / 2, op.lh.partials, op.lh.res, op.lh.layer, op.lh.fault, st));
@@ -376,6 +377,8 @@ int cdc_get_nonfinite_results(const cdc_handle *h) { return h ? h->nonfinite_res
 int cdc_enable_vbr(cdc_handle *h) {
     if (!h) return CDC_ERR_INVALID;
     if (h->kind == HandleKind::Unet) return fail(h, CDC_ERR_INVALID, "variable bitrate needs a context-decoder, encoder or hyper-decoder handle");
+    if (h->simple)      // (the reference's SimpleCompressor(vbr=True) raises on its first forward: an nn.Identity called with (input, cond))
+        return fail(h, CDC_ERR_INVALID, "variable bitrate: SimpleCompressor has no working VBR form in the reference");
     if ((h->kind == HandleKind::ContextDecoder && h->up_index != 2) || (h->kind == HandleKind::Encoder && h->down_index != 2))
         return fail(h, CDC_ERR_INVALID, "variable bitrate: the VBRCondition sits at index 1 of each level, so the resampling layer must be at index 2");
     for (const Param &p : h->params)
@@ -456,6 +459,25 @@ int cdc_encoder_create(const cdc_encoder_config *cfg, int device, cdc_handle **o
     build_compressor_manifest(h.get());
     *out = h.release();
     return CDC_OK;
+}
+
+int cdc_simple_encoder_create(const cdc_encoder_config *cfg, int device, cdc_handle **out) {
+    if (!cfg || !out) return fail(nullptr, CDC_ERR_INVALID, "null argument");
+    cdc_encoder_config c = *cfg;
+    c.down_index = 1;           // (ignored: the level's layers sit at fixed indices 0 and 2)
+    *out = nullptr;
+    int rc = cdc_encoder_create(&c, device, out);
+    if (rc) return rc;
+    cdc_handle *h = *out;
+    rc = no_throw(nullptr, [&] {
+        h->simple = true;
+        h->params.clear();
+        h->pindex.clear();
+        build_compressor_manifest(h);
+        return CDC_OK;
+    });
+    if (rc) { cdc_destroy(h); *out = nullptr; }
+    return rc;
 }
 
 int cdc_encoder_encode(cdc_handle *h, const float *images, float *latent, float *hyper_latent, int B, int H, int W,
@@ -851,6 +873,25 @@ int cdc_ctxdec_create(const cdc_ctxdec_config *cfg, int device, cdc_handle **out
     build_compressor_manifest(h.get());
     *out = h.release();
     return CDC_OK;
+}
+
+int cdc_simple_ctxdec_create(const cdc_ctxdec_config *cfg, int device, cdc_handle **out) {
+    if (!cfg || !out) return fail(nullptr, CDC_ERR_INVALID, "null argument");
+    cdc_ctxdec_config c = *cfg;
+    c.up_index = 1;             // (ignored)
+    *out = nullptr;
+    int rc = cdc_ctxdec_create(&c, device, out);
+    if (rc) return rc;
+    cdc_handle *h = *out;
+    rc = no_throw(nullptr, [&] {
+        h->simple = true;
+        h->params.clear();
+        h->pindex.clear();
+        build_compressor_manifest(h);
+        return CDC_OK;
+    });
+    if (rc) { cdc_destroy(h); *out = nullptr; }
+    return rc;
 }
 
 int cdc_ctxdec_decode(cdc_handle *h, const float *q_latent, float *const *outs, int n_outs, int B,

@@ -292,6 +292,18 @@ hipError_t maxpool2_launch(const float *in, float *out, long long planes, int H,
 int lpips_head_blocks(int HW);
 hipError_t lpips_head_launch(const float *f, long long bs, int C, int HW, const float *w, int n, double *partials, double *res, int layer,
                              int *fault, hipStream_t st);
+// gdn_kernels.hip: GDN1 / inverse GDN1 (epsilon-tree SimpleCompressor) over x [B][C][HW] as one fused pass; beta [C] and gamma [C][C]
+// are the REPARAMETRISED parameters (gdn_reparam, host, float32 operation by operation as torch).  C % 16 == 0, 16 <= C <= 256.
+struct GdnArgs {
+    const float *x; long long x_bs;
+    float *y; long long y_bs;         // must not alias x (a workgroup's tiles are read by all of its waves)
+    const float *beta, *gamma;
+    int C, HW, inverse;
+    int *fault;                       // range guard (ConvArgs::fault): set to 1 on a non-finite output (may be null)
+};
+bool gdn_supported(int C);
+hipError_t gdn_launch(const GdnArgs &a, int B, hipStream_t st);
+void gdn_reparam(const float *beta, const float *gamma, int C, float *beta_r, float *gamma_r);
 hipError_t unfold_x_launch(const float *src, long long src_bs, float *dst, long long dst_bs, int C, int KW,
                            int pad, int H, int W, int B, hipStream_t st);
 

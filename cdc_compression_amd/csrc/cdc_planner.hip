@@ -24,7 +24,7 @@ struct Builder {
         op.id = (int)h->op_ms.size();
         h->op_ms.push_back(0); h->op_n.push_back(0); h->op_flops.push_back(op.flops);
         char buf[160];
-        const char *kinds[] = {"conv", "ln", "temb", "kstats", "ctxp", "ctxr", "ctxf", "combine", "ddim", "copy", "unfold", "kvctx", "lnconv", "convpf", "pfpack", "convws", "convws1", "vbr", "maxpool", "lpips_head"};
+        const char *kinds[] = {"conv", "ln", "temb", "kstats", "ctxp", "ctxr", "ctxf", "combine", "ddim", "copy", "unfold", "kvctx", "lnconv", "convpf", "pfpack", "convws", "convws1", "vbr", "maxpool", "lpips_head", "gdn"};
         if (op.kind == Op::PFPACK && op.pk.c4 == 2) kinds[Op::PFPACK] = "pfunpack";
         if (op.kind == Op::CONV)
             snprintf(buf, sizeof buf, "conv %dx%d s%d %4d->%-4d out %3dx%-3d MB%d NPW%d WN%d g%d tg%d ipw%d ks%d%s%s%s%s%s", op.conv.KH,
@@ -52,6 +52,8 @@ struct Builder {
             snprintf(buf, sizeof buf, "lnconv C=%d N=%d nsplit=%d", op.lnc.C, op.lnc.N, op.lnc.nsplit);
         else if (op.kind == Op::VBR)
             snprintf(buf, sizeof buf, "vbr C=%d HW=%d%s", op.vb.C, op.vb.HW, op.vb.leaky ? " leaky" : "");
+        else if (op.kind == Op::GDN)
+            snprintf(buf, sizeof buf, "gdn C=%d HW=%d%s", op.gdn.C, op.gdn.HW, op.gdn.inverse ? " inv" : "");
         else if (op.kind == Op::MAXPOOL)
             snprintf(buf, sizeof buf, "maxpool2 C=%d in %dx%d", op.mp.C, op.mp.H, op.mp.W);
         else if (op.kind == Op::LPHEAD)
@@ -918,6 +920,20 @@ struct Builder {
         op.bytes = 8.0 * B * a.C * a.H * a.W;
         emit(op);
     }
+    // GDN1 / inverse GDN1 (network_components.py:381-412) over x -> y, one fused pass (gdn_kernels.hip); beta / gamma reparametrised
+    void gdn(const GdnW &w, const float *x, long long x_bs, float *y, long long y_bs, int HW) {
+        if (rc) return;
+        if (!gdn_supported(w.C)) {
+            rc = fail(h, CDC_ERR_UNSUPPORTED, "GDN over %d channels: the kernel takes multiples of 16 from 16 to 256", w.C);
+            return;
+        }
+        if (x == y || HW < 1) { rc = fail(h, CDC_ERR_INVALID, "GDN C=%d HW=%d: bad program", w.C, HW); return; }
+        Op op; op.kind = Op::GDN; op.prof = PC_GDN;
+        op.gdn = {x, x_bs, y, y_bs, w.beta, w.gamma, w.C, HW, w.inverse ? 1 : 0, fault_flag()};
+        op.flops = 2.0 * B * HW * w.C * w.C;
+        op.bytes = 8.0 * B * w.C * HW;
+        emit(op);
+    }
     // after the block() call that produced `a`: if it wrote planes only, say so on the twin (its readers must take planes) and on the Act
     void mark_planes_only(Act &a) {
         if (!last_pf_only) return;
@@ -1242,8 +1258,32 @@ int build_program(cdc_handle *h, int B, int H, int W) {
     return CDC_OK;
 }
 
+// The tail both encoder programs share: `latent` is the first output; hyper_enc (compress_modules.py:50-55: Conv2d 3x3, then 5x5 /
+// stride 2, LeakyReLU(0.2) between; variable bitrate: VBRCondition sites vbr_base + i) gives hyper_latent, the second.
+static int emit_hyper_enc(cdc_handle *h, Builder &bd, Act x, int vbr_base) {
+    const int nh = (int)h->henc_dims.size() - 1;
+    const bool vbr = h->vbr;
+    h->dec_outs.clear();
+    h->dec_outs.push_back(x);                       // latent
+    for (int i = 0; i < nh; ++i) {
+        const ConvW &cw = h->hconvs[i];
+        const int s = i == 0 ? 1 : 2;
+        const bool site = vbr && i < nh - 1;        // conv + bias, VBRCondition, LeakyReLU(0.2)
+        Act y = bd.new_act(cw.Cout, x.H / s, x.W / s, !site);
+        Builder::ConvOpts o;
+        if (i < nh - 1 && !site) { o.relu = 1; o.relu_slope = 0.2f; }
+        bd.conv(cw, x.p, x.C, x.bs(), nullptr, 0, x.H, x.W, y.p, y.bs(), o, false, i == 0 ? PC_CONV3 : PC_DOWN);
+        if (site) bd.vbr(y, h->vbrs[vbr_base + i], true);
+        x = y;
+        if (bd.rc) return bd.rc;
+    }
+    h->dec_outs.push_back(x);                       // hyper_latent
+    return CDC_OK;
+}
+
 // Launch program of Compressor.encode up to the quantisers (compress_modules.py:43-51) for images [B][C][H][W].
 int build_encoder_program(cdc_handle *h, int B, int H, int W) {
+    if (h->simple) return build_simple_encoder_program(h, B, H, W);
     if (h->pB == B && h->pH == H && h->pW == W) return CDC_OK;
     free_program(h);
     const int n = (int)h->enc_dims.size() - 1, nh = (int)h->henc_dims.size() - 1;
@@ -1267,21 +1307,37 @@ int build_encoder_program(cdc_handle *h, int B, int H, int W) {
         x = y;
         if (bd.rc) return bd.rc;
     }
-    h->dec_outs.clear();
-    h->dec_outs.push_back(x);                       // latent
-    for (int i = 0; i < nh; ++i) {
-        const ConvW &cw = h->hconvs[i];
-        const int s = i == 0 ? 1 : 2;
-        const bool site = vbr && i < nh - 1;        // conv + bias, VBRCondition, LeakyReLU(0.2)
-        Act y = bd.new_act(cw.Cout, x.H / s, x.W / s, !site);
-        Builder::ConvOpts o;
-        if (i < nh - 1 && !site) { o.relu = 1; o.relu_slope = 0.2f; }
-        bd.conv(cw, x.p, x.C, x.bs(), nullptr, 0, x.H, x.W, y.p, y.bs(), o, false, i == 0 ? PC_CONV3 : PC_DOWN);
-        if (site) bd.vbr(y, h->vbrs[n + i], true);
+    if (int rc = emit_hyper_enc(h, bd, x, n)) return rc;
+    h->pB = B; h->pH = H; h->pW = W;
+    return CDC_OK;
+}
+
+// Launch program of SimpleCompressor.encode up to the quantisers (epsilonparam compress_modules.py:207-217, 43-55): per level
+// Conv2d(5, stride 2, padding 2) and GDN1 (none on the last level), then hyper_enc as in build_encoder_program.
+int build_simple_encoder_program(cdc_handle *h, int B, int H, int W) {
+    if (h->pB == B && h->pH == H && h->pW == W) return CDC_OK;
+    free_program(h);
+    const int n = (int)h->enc_dims.size() - 1, nh = (int)h->henc_dims.size() - 1;
+    const int down = 1 << (n + nh - 1);
+    if (H % down || W % down)
+        return fail(h, CDC_ERR_INVALID, "H=%d, W=%d must be multiples of %d", H, W, down);
+    Builder bd{h, B, &h->act_allocs};
+    h->in_x = bd.dalloc((size_t)B * h->enc_dims[0] * H * W);
+    if (bd.rc) return bd.rc;
+    Act x; x.p = h->in_x; x.C = h->enc_dims[0]; x.H = H; x.W = W;
+    for (int i = 0; i < n; ++i) {                   // (fp32 tensors only: the GDN kernel reads and writes no planes)
+        const ConvW &dw = h->downs[i];
+        Act y = bd.new_act(dw.Cout, x.H / 2, x.W / 2, false);
+        bd.conv(dw, x.p, x.C, x.bs(), nullptr, 0, x.H, x.W, y.p, y.bs(), Builder::ConvOpts(), false, PC_DOWN);
+        if (i < n - 1) {
+            Act g = bd.new_act(y.C, y.H, y.W, false);
+            bd.gdn(h->gdns[i], y.p, y.bs(), g.p, g.bs(), y.H * y.W);
+            y = g;
+        }
         x = y;
         if (bd.rc) return bd.rc;
     }
-    h->dec_outs.push_back(x);                       // hyper_latent
+    if (int rc = emit_hyper_enc(h, bd, x, n)) return rc;
     h->pB = B; h->pH = H; h->pW = W;
     return CDC_OK;
 }
@@ -1319,6 +1375,7 @@ int build_hyperdec_program(cdc_handle *h, int B, int hh, int wh, bool batch1_pla
 
 // Launch program of Compressor.decode (compress_modules.py:68-74) for q_latent [B][rev[0]][hl][wl].
 int build_ctxdec_program(cdc_handle *h, int B, int hl, int wl) {
+    if (h->simple) return build_simple_ctxdec_program(h, B, hl, wl);
     if (h->pB == B && h->pH == hl && h->pW == wl) return CDC_OK;
     free_program(h);
     h->dec_outs.clear();
@@ -1337,6 +1394,35 @@ int build_ctxdec_program(cdc_handle *h, int B, int hl, int wl) {
         Act y = bd.new_act(uw.Cout, x.H * 2, x.W * 2);
         Builder::ConvOpts ouu; ouu.emit_pf = true;
         bd.conv(uw, x.p, x.C, x.bs(), nullptr, 0, x.H, x.W, y.p, y.bs(), ouu, false, PC_UP);
+        x = y;
+        h->dec_outs.push_back(y);
+        if (bd.rc) return bd.rc;
+    }
+    h->pB = B; h->pH = hl; h->pW = wl;
+    return CDC_OK;
+}
+
+// Launch program of SimpleCompressor.decode (epsilonparam compress_modules.py:219-229, 74-82) for q_latent [B][rev[0]][hl][wl]: per
+// level ConvTranspose2d(5, stride 2, padding 2, output_padding 1), packed as the hyper decoder's, and inverse GDN1 (none on the last
+// level); every level's result is an output.
+int build_simple_ctxdec_program(cdc_handle *h, int B, int hl, int wl) {
+    if (h->pB == B && h->pH == hl && h->pW == wl) return CDC_OK;
+    free_program(h);
+    h->dec_outs.clear();
+    Builder bd{h, B, &h->act_allocs};
+    h->in_x = bd.dalloc((size_t)B * h->rev_dims[0] * hl * wl);
+    if (bd.rc) return bd.rc;
+    Act x; x.p = h->in_x; x.C = h->rev_dims[0]; x.H = hl; x.W = wl;
+    const int n = (int)h->rev_dims.size() - 1;
+    for (int i = 0; i < n; ++i) {
+        const ConvW &uw = h->ups[i];
+        Act y = bd.new_act(uw.Cout, x.H * 2, x.W * 2, false);
+        bd.conv(uw, x.p, x.C, x.bs(), nullptr, 0, x.H, x.W, y.p, y.bs(), Builder::ConvOpts(), false, PC_UP);
+        if (i < n - 1) {
+            Act g = bd.new_act(y.C, y.H, y.W, false);
+            bd.gdn(h->gdns[i], y.p, y.bs(), g.p, g.bs(), y.H * y.W);
+            y = g;
+        }
         x = y;
         h->dec_outs.push_back(y);
         if (bd.rc) return bd.rc;
@@ -1660,6 +1746,33 @@ int cdc_op_linear_attention(cdc_handle *h, const float *x, const float *norm_g, 
                             const float *w_qkv, const float *w_out, const float *b_out, float *y, int B,
                             int C, int H, int W) {
     return with_range_guard(h, [&] { return op_linear_attention_impl(h, x, norm_g, norm_b, w_qkv, w_out, b_out, y, B, C, H, W); });
+}
+
+// Single GDN1 layer over RAW parameters: reparametrised on the host as cdc_finalize_weights does, then the program's own kernel.
+static int op_gdn_impl(cdc_handle *h, const float *x, const float *beta, const float *gamma, float *y, int B, int C, int HW, int inverse) {
+    int rc = op_ready(h);
+    if (rc) return rc;
+    if (!x || !beta || !gamma || !y || B < 1 || HW < 1) return fail(h, CDC_ERR_INVALID, "null/invalid argument");
+    if (!gdn_supported(C)) return fail(h, CDC_ERR_UNSUPPORTED, "GDN over %d channels: the kernel takes multiples of 16 from 16 to 256", C);
+    OpScope sc(h);
+    Builder bd{h, B, &sc.pool};
+    std::vector<float> br((size_t)C), gr((size_t)C * C);
+    gdn_reparam(beta, gamma, C, br.data(), gr.data());
+    GdnW w;
+    w.C = C; w.inverse = inverse != 0;
+    float *dx;
+    if ((rc = sc.up(br.data(), br.size(), &w.beta))) return rc;
+    if ((rc = sc.up(gr.data(), gr.size(), &w.gamma))) return rc;
+    if ((rc = sc.up(x, (size_t)B * C * HW, &dx))) return rc;
+    float *dy = bd.dalloc((size_t)B * C * HW);
+    if (bd.rc) return bd.rc;
+    bd.gdn(w, dx, (long long)C * HW, dy, (long long)C * HW, HW);
+    if (bd.rc) return bd.rc;
+    return sc.run(B, y, dy, (size_t)B * C * HW);
+}
+
+int cdc_op_gdn(cdc_handle *h, const float *x, const float *beta, const float *gamma, float *y, int B, int C, int HW, int inverse) {
+    return with_range_guard(h, [&] { return no_throw(h, [&] { return op_gdn_impl(h, x, beta, gamma, y, B, C, HW, inverse); }); });
 }
 
 int cdc_op_stress(cdc_handle *h, int repeats) {

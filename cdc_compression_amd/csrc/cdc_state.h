@@ -28,10 +28,10 @@ using namespace cdc;
 namespace cdcapi {
 
 
-enum ProfClass { PC_CONV3 = 0, PC_CONV7, PC_CONV1, PC_DOWN, PC_UP, PC_ATTN_CTX, PC_LN, PC_SMALL,
+enum ProfClass { PC_CONV3 = 0, PC_CONV7, PC_CONV1, PC_DOWN, PC_UP, PC_ATTN_CTX, PC_LN, PC_SMALL, PC_GDN,
                  PC_COUNT };
 static const char *const kProfNames[PC_COUNT] = {"conv3x3", "conv7x7", "conv1x1", "downsample", "upsample",
-                                    "attn_ctx", "layernorm", "small"};
+                                    "attn_ctx", "layernorm", "small", "gdn"};
 
 struct Param {                    // one state_dict entry
     std::string name;
@@ -75,7 +75,7 @@ struct AttnW { std::string prefix; int C; ConvW qkv, out; float *ng, *nb;
                unsigned short *kvWh = nullptr; float kv_scale_inv = 1.f; };   // fp16 planes {WH, WL, WH2} of W' 2^s   // fused front half: (W_kv diag(g))^T [C][2C], W_kv b_ln [2C]   // folded output; uq = Wq b_ln
 
 struct Op {
-    enum Kind { CONV, LN, TEMB, KSTATS, CTXP, CTXR, CTXF, COMBINE, DDIM, COPY, UNFOLD, KVCTX, LNCONV, CONVPF, PFPACK, CONVWS, CONVWS1, VBR, MAXPOOL, LPHEAD } kind;
+    enum Kind { CONV, LN, TEMB, KSTATS, CTXP, CTXR, CTXF, COMBINE, DDIM, COPY, UNFOLD, KVCTX, LNCONV, CONVPF, PFPACK, CONVWS, CONVWS1, VBR, MAXPOOL, LPHEAD, GDN } kind;
     int prof = PC_SMALL;
     int id = -1;                  // index into cdc_handle::op_ms (per-op timing table, debug aid)
     char label[96] = {0};
@@ -106,9 +106,11 @@ struct Op {
     struct { const float *src; long long src_bs; void *dst; long long dst_bs; int C, H, W; int c4; } pk;   // PFPACK (c4: fp32 -> accumulator order)
     struct { float *x; long long bs; int C, HW; const float *rate, *p; int leaky; } vb;   // VBR: in-place VBRCondition (+ LeakyReLU 0.2)
     struct { const float *src; float *dst; int C, H, W; } mp;                               // MAXPOOL: max_pool2d(2, 2), floor mode (lpips_kernels.hip)
+    GdnArgs gdn;                                                                            // GDN: GDN1 / inverse GDN1 (gdn_kernels.hip)
     struct { const float *f; long long bs; int C, HW; const float *w; double *partials, *res; int layer; int *fault; } lh;   // LPHEAD: one LPIPS tap, run over B / 2 pairs
 };
 
+struct GdnW { int C = 0; bool inverse = false; float *beta = nullptr, *gamma = nullptr; };   // one GDN1 layer: reparametrised beta' [C], gamma' [C][C] (device)
 struct VbrW { int C = 0; float *p = nullptr; };   // one VBRCondition site: [scale.weight | scale.bias | shift.weight | shift.bias], C each
 
 
@@ -129,6 +131,10 @@ struct cdc_handle {
     HandleKind kind = HandleKind::Unet;
     std::vector<int> enc_dims, henc_dims;     // Encoder
     int down_index = 1;
+    // SimpleCompressor (cdc_simple_encoder_create / cdc_simple_ctxdec_create): the kinds Encoder / ContextDecoder with 5x5 stride-2
+    // (transposed) convolutions in downs / ups and a GDN1 (inverse GDN1) after every level but the last, in place of the ResnetBlocks
+    bool simple = false;
+    std::vector<GdnW> gdns;
     std::vector<int> hyper_dims;  // HyperDecoder: reversed_hyper_dims
     std::vector<ConvW> hconvs;    // HyperDecoder: packed layers
     float *d_prior = nullptr;     // HyperDecoder: FlexiblePrior per channel, 44 floats (softplus / tanh applied), or null
@@ -273,9 +279,11 @@ void free_pool(std::vector<void *> *pool);
 // ---- cdc_planner.hip
 void free_program(cdc_handle *h);
 int build_program(cdc_handle *h, int B, int H, int W);
-int build_encoder_program(cdc_handle *h, int B, int H, int W);
+int build_encoder_program(cdc_handle *h, int B, int H, int W);          // (a SimpleCompressor handle: build_simple_encoder_program)
+int build_simple_encoder_program(cdc_handle *h, int B, int H, int W);
 int build_hyperdec_program(cdc_handle *h, int B, int hh, int wh, bool batch1_plan = false);
-int build_ctxdec_program(cdc_handle *h, int B, int hl, int wl);
+int build_ctxdec_program(cdc_handle *h, int B, int hl, int wl);         // (a SimpleCompressor handle: build_simple_ctxdec_program)
+int build_simple_ctxdec_program(cdc_handle *h, int B, int hl, int wl);
 // LPIPS-VGG over up to `pairs` image pairs of H x W (2 pairs rows: first operands, then second operands); every kernel variant is
 // planned as for one image, so a pair's result does not depend on the pairs beside it.  h->pB = 2 pairs is the program's capacity.
 int build_lpips_program(cdc_handle *h, int pairs, int H, int W);

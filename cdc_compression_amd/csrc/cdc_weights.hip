@@ -101,10 +101,22 @@ static void add_vbr_params(cdc_handle *h, const std::string &p, int c) {
     add_param(h, p + ".shift.bias", {c});
 }
 
+// GDN1(ch) at index 2 of a SimpleCompressor level (epsilonparam network_components.py:330-345): raw (unreparametrised) parameters
+static void add_gdn_params(cdc_handle *h, const std::string &p, int c) {
+    add_param(h, p + ".beta", {c});
+    add_param(h, p + ".gamma", {c, c});
+}
+
 void build_compressor_manifest(cdc_handle *h) {
     if (h->kind == HandleKind::Encoder) {
         const int n = (int)h->enc_dims.size() - 1, nh = (int)h->henc_dims.size() - 1;
-        for (int i = 0; i < n; ++i) {          // Compressor.enc (:131-141)
+        for (int i = 0; h->simple && i < n; ++i) {   // SimpleCompressor.enc (:207-217): Conv2d(5, 2, 2), Identity, GDN1 | Identity
+            const std::string p = "enc." + std::to_string(i);
+            add_param(h, p + ".0.weight", {h->enc_dims[i + 1], h->enc_dims[i], 5, 5});
+            add_param(h, p + ".0.bias", {h->enc_dims[i + 1]});
+            if (i < n - 1) add_gdn_params(h, p + ".2", h->enc_dims[i + 1]);
+        }
+        for (int i = 0; !h->simple && i < n; ++i) {  // Compressor.enc (:131-141)
             const std::string p = "enc." + std::to_string(i);
             add_resblock_params(h, p + ".0", h->enc_dims[i], h->enc_dims[i + 1], i == 0 ? 7 : 3, false);
             if (h->vbr) add_vbr_params(h, p + ".1", h->enc_dims[i + 1]);
@@ -139,7 +151,13 @@ void build_compressor_manifest(cdc_handle *h) {
         }
     } else if (h->kind == HandleKind::ContextDecoder) {
         const int n = (int)h->rev_dims.size() - 1;
-        for (int i = 0; i < n; ++i) {          // Compressor.dec (compress_modules.py:147-156)
+        for (int i = 0; h->simple && i < n; ++i) {   // SimpleCompressor.dec (:219-229): ConvTranspose2d(5, 2, 2, 1), Identity, GDN1(inverse) | Identity
+            const std::string p = "dec." + std::to_string(i);
+            add_param(h, p + ".0.weight", {h->rev_dims[i], h->rev_dims[i + 1], 5, 5});      // [Cin][Cout][5][5]
+            add_param(h, p + ".0.bias", {h->rev_dims[i + 1]});
+            if (i < n - 1) add_gdn_params(h, p + ".2", h->rev_dims[i + 1]);
+        }
+        for (int i = 0; !h->simple && i < n; ++i) {  // Compressor.dec (compress_modules.py:147-156)
             const std::string p = "dec." + std::to_string(i);
             const int din = h->rev_dims[i], dout = h->rev_dims[i + 1], dmid = i == n - 1 ? din : dout;
             add_resblock_params(h, p + ".0", din, dmid, 3, false);
@@ -525,6 +543,21 @@ static int pack_vbr(cdc_handle *h, const std::string &p, int c) {
     return CDC_OK;
 }
 
+// one GDN1 layer: beta' / gamma' (gdn_reparam: float32, operation by operation as the reference's forward) on the device
+static int pack_gdn(cdc_handle *h, const std::string &p, int c, bool inverse) {
+    const auto &beta = hostp(h, p + ".beta");
+    const auto &gamma = hostp(h, p + ".gamma");
+    std::vector<float> br((size_t)c), gr((size_t)c * c);
+    gdn_reparam(beta.data(), gamma.data(), c, br.data(), gr.data());
+    GdnW w;
+    w.C = c; w.inverse = inverse;
+    int rc;
+    if ((rc = upload(h, br.data(), br.size(), &w.beta, &h->weight_allocs))) return rc;
+    if ((rc = upload(h, gr.data(), gr.size(), &w.gamma, &h->weight_allocs))) return rc;
+    h->gdns.push_back(w);
+    return CDC_OK;
+}
+
 void free_pool(std::vector<void *> *pool) {
     for (void *p : *pool) (void)hipFree(p);
     pool->clear();
@@ -545,11 +578,20 @@ int cdc_finalize_weights(cdc_handle *h) {
     free_program(h);
     free_pool(&h->weight_allocs);
     h->d_fault = nullptr; h->d_step = nullptr;          // (they lived in that pool)
-    h->rbs.clear(); h->attns.clear(); h->downs.clear(); h->ups.clear(); h->vbrs.clear();
+    h->rbs.clear(); h->attns.clear(); h->downs.clear(); h->ups.clear(); h->vbrs.clear(); h->gdns.clear();
     if (h->kind == HandleKind::Encoder) {
         const int n = (int)h->enc_dims.size() - 1;
         int shift_off = 0;
-        for (int i = 0; i < n; ++i) {
+        for (int i = 0; h->simple && i < n; ++i) {
+            const std::string p = "enc." + std::to_string(i);
+            if (i < n - 1 && !gdn_supported(h->enc_dims[i + 1]))
+                return fail(h, CDC_ERR_UNSUPPORTED, "GDN over %d channels: the kernel takes multiples of 16 from 16 to 256", h->enc_dims[i + 1]);
+            ConvW dw;
+            if ((rc = pack_named_conv(h, p + ".0.weight", p + ".0.bias", 2, 2, false, &dw))) return rc;
+            h->downs.push_back(dw);
+            if (i < n - 1 && (rc = pack_gdn(h, p + ".2", h->enc_dims[i + 1], false))) return rc;
+        }
+        for (int i = 0; !h->simple && i < n; ++i) {
             const std::string p = "enc." + std::to_string(i);
             if ((rc = pack_resblock(h, p + ".0", h->enc_dims[i], h->enc_dims[i + 1], i == 0 ? 7 : 3, &shift_off, 0, false)))
                 return rc;
@@ -655,7 +697,16 @@ int cdc_finalize_weights(cdc_handle *h) {
         // Compressor.dec: ResnetBlock(rev[i] -> rev[i+1] | rev[i] on the last level) + Upsample(-> rev[i+1])
         const int n = (int)h->rev_dims.size() - 1;
         int shift_off = 0;
-        for (int i = 0; i < n; ++i) {
+        for (int i = 0; h->simple && i < n; ++i) {
+            const std::string p = "dec." + std::to_string(i);
+            if (i < n - 1 && !gdn_supported(h->rev_dims[i + 1]))
+                return fail(h, CDC_ERR_UNSUPPORTED, "GDN over %d channels: the kernel takes multiples of 16 from 16 to 256", h->rev_dims[i + 1]);
+            ConvW uw;
+            if ((rc = pack_named_conv(h, p + ".0.weight", p + ".0.bias", 2, 2, true, &uw))) return rc;
+            h->ups.push_back(uw);
+            if (i < n - 1 && (rc = pack_gdn(h, p + ".2", h->rev_dims[i + 1], true))) return rc;
+        }
+        for (int i = 0; !h->simple && i < n; ++i) {
             const std::string p = "dec." + std::to_string(i);
             const int din = h->rev_dims[i], dout = h->rev_dims[i + 1], dmid = i == n - 1 ? din : dout;
             if ((rc = pack_resblock(h, p + ".0", din, dmid, 3, &shift_off, 0, false))) return rc;

@@ -105,3 +105,14 @@ class Ops:
             self._h, _p(x), _p(norm_g.reshape(-1)), _p(norm_b.reshape(-1)), _p(w_qkv), _p(w_out),
             _p(b_out), _p(y), B, C, H, W))
         return y
+
+    def gdn(self, x, beta, gamma, inverse=False):
+        """GDN1.forward (epsilonparam network_components.py:381-412) with the raw parameters beta [C], gamma [C, C]:
+        y = x / (beta' + gamma' |x|), or x * (...) when inverse."""
+        x, beta, gamma = _c(x), _c(beta).reshape(-1), _c(gamma)
+        B, C, H, W = x.shape
+        if beta.shape != (C,) or gamma.shape != (C, C):
+            raise ValueError(f"beta {beta.shape} / gamma {gamma.shape} do not belong to {C} channels")
+        y = np.empty_like(x)
+        _lib.check(self._h, _lib.lib().cdc_op_gdn(self._h, _p(x), _p(beta), _p(gamma), _p(y), B, C, H * W, int(bool(inverse))))
+        return y

@@ -109,6 +109,47 @@ def compressor_state_dict(manifest, seed=0):
     return {n: sd[n] for n, _ in manifest}
 
 
+def is_gdn_key(name):
+    """A GDN1 parameter (epsilonparam network_components.py:330-345): `<layer>.beta` / `<layer>.gamma`."""
+    return name.endswith(".beta") or name.endswith(".gamma")
+
+
+def simple_compressor_state_dict(manifest, seed=0):
+    """Synthetic parameters for a SimpleCompressor manifest: `unet_state_dict` for the convolutions and biases; per GDN1 layer
+    beta = 1 + N(0, 0.1^2) with beta[0] = 0 (below the reparametrisation's bound: the clamp acts) and
+    gamma = sqrt(0.1) I + N(0, 0.05^2) (about half of the off-diagonal entries are negative and clamp to the bound).  The
+    normalisation pool stays near 1, so the activations stay O(1) through the levels."""
+    sd = unet_state_dict([(n, s) for n, s in manifest if not is_gdn_key(n)], seed=seed)
+    for name, shape in manifest:
+        shape = tuple(shape)
+        if name.endswith(".beta"):
+            t = normal(name, shape, seed, 0.1, 1.0)
+            t[0] = 0.0
+        elif name.endswith(".gamma"):
+            t = (normal(name, shape, seed, 0.05).astype(np.float64) + np.sqrt(0.1) * np.eye(shape[0])).astype(np.float32)
+        else:
+            continue
+        sd[name] = t
+    return {n: sd[n] for n, _ in manifest}
+
+
+def gdn_layer_params(C, seed=0, name="gdn"):
+    """(beta [C], gamma [C, C]) of one GDN1 layer, drawn as `simple_compressor_state_dict` draws them."""
+    sd = simple_compressor_state_dict([(f"{name}.beta", (C,)), (f"{name}.gamma", (C, C))], seed=seed)
+    return sd[f"{name}.beta"], sd[f"{name}.gamma"]
+
+
+def gdn_input(shape, seed=0, name="gdn_x"):
+    """N(0, 1) activations [B, C, H, W] for a GDN1 layer with a few special entries: flat indices 0, 7, 14, ... (every 7th of the
+    first 35) are exact zeros, flat index 3 is +1e4 and the last element is -1e4."""
+    x = normal(name, shape, seed, 1.0)
+    flat = x.reshape(-1)
+    flat[0:35:7] = 0.0
+    flat[3] = 1e4
+    flat[-1] = -1e4
+    return x
+
+
 # VGG16's convolutions inside lpips 0.1.4's LPIPS(net="vgg"): (slice, index in torchvision's vgg16().features, Cin, Cout)
 LPIPS_VGG_CONVS = ((1, 0, 3, 64), (1, 2, 64, 64), (2, 5, 64, 128), (2, 7, 128, 128), (3, 10, 128, 256), (3, 12, 256, 256),
                    (3, 14, 256, 256), (4, 17, 256, 512), (4, 19, 512, 512), (4, 21, 512, 512), (5, 24, 512, 512), (5, 26, 512, 512),

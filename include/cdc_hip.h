@@ -222,6 +222,15 @@ int cdc_ctxdec_create(const cdc_ctxdec_config *cfg, int device, cdc_handle **out
 int cdc_ctxdec_decode(cdc_handle *h, const float *q_latent, float *const *outs, int n_outs, int B,
                       int h_latent, int w_latent, int mem_kind, void *stream);
 
+/* SimpleCompressor.decode (epsilonparam/modules/compress_modules.py:219-229, 74-82), the GDN context model: level i =
+ * ConvTranspose2d(rev[i] -> rev[i+1], 5, stride 2, padding 2, output_padding 1) + inverse GDN1(rev[i+1]); the last level has no
+ * GDN.  Outputs are collected after the GDN.  Keys: "dec.<i>.0.weight" [Cin][Cout][5][5], "dec.<i>.0.bias", "dec.<i>.2.beta" [C],
+ * "dec.<i>.2.gamma" [C][C] (raw parameters; cdc_finalize_weights reparametrises them in float32 as GDN.forward does,
+ * network_components.py:357-363).  up_index is ignored.  The handle is a context decoder: cdc_ctxdec_decode runs it, the frame
+ * multiple of cdc_padded_size is 2^n_rev_mults.  cdc_enable_vbr is refused (CDC_ERR_INVALID): SimpleCompressor(vbr=True) raises in
+ * the reference.  Every rev[i+1] but the last must be a multiple of 16 in 16 .. 256 (CDC_ERR_UNSUPPORTED at cdc_finalize_weights). */
+int cdc_simple_ctxdec_create(const cdc_ctxdec_config *cfg, int device, cdc_handle **out);
+
 /* ---- encoder: analysis transform + hyper encoder --------------------- */
 
 /* Compressor.encode up to the quantisers (compress_modules.py:43-51,131-165): `enc` = n_dim_mults x
@@ -246,6 +255,13 @@ int cdc_encoder_create(const cdc_encoder_config *cfg, int device, cdc_handle **o
  * (`latent`, `hyper_latent` of state4bpp); quantisation is cdc_dequantize with the prior medians / the mean. */
 int cdc_encoder_encode(cdc_handle *h, const float *images, float *latent, float *hyper_latent, int B, int H,
                        int W, int mem_kind, void *stream);
+
+/* SimpleCompressor.encode up to the quantisers (epsilonparam/modules/compress_modules.py:207-217, 43-55): `enc` = n_dim_mults x
+ * [Conv2d(dims[i] -> dims[i+1], 5, stride 2, padding 2), GDN1(dims[i+1])] with no GDN on the last level, then `hyper_enc` as above.
+ * Keys: "enc.<i>.0.weight" [Cout][Cin][5][5], "enc.<i>.0.bias", "enc.<i>.2.beta" [C], "enc.<i>.2.gamma" [C][C], "hyper_enc.*".
+ * down_index is ignored.  The handle is an encoder: cdc_encoder_encode runs it, with the same frame multiple
+ * 2^(n_dim_mults + n_hyper_mults - 1).  cdc_enable_vbr is refused (CDC_ERR_INVALID); channel limits as for cdc_simple_ctxdec_create. */
+int cdc_simple_encoder_create(const cdc_encoder_config *cfg, int device, cdc_handle **out);
 
 /* ---- hyperprior decoder (decode side) ------------------------------------ */
 
@@ -514,6 +530,12 @@ int cdc_op_conv_transpose2d(cdc_handle *h, const float *x, const float *w, const
 /* LayerNorm.forward (:56-66). */
 int cdc_op_chan_layernorm(cdc_handle *h, const float *x, const float *g, const float *b, float *y,
                           int B, int C, int HW);
+/* GDN1.forward (epsilonparam/modules/network_components.py:381-412) over x [B][C][HW] with the RAW parameters beta [C], gamma [C][C]:
+ *   beta' = max(beta, (1e-6 + 2^-36)^0.5)^2 - 2^-36,  gamma' = max(gamma, 2^-18)^2 - 2^-36          (float32, one rounding per operation)
+ *   norm[b][i][p] = beta'[i] + sum_j gamma'[i][j] |x[b][j][p]|;   y = x / norm, or x * norm when `inverse`   (no square, no root)
+ * as one fused pass on the fp32 matrix instructions.  C % 16 == 0 and 16 <= C <= 256, else CDC_ERR_UNSUPPORTED (nothing is launched).
+ * Host pointers; honours cdc_op_stress. */
+int cdc_op_gdn(cdc_handle *h, const float *x, const float *beta, const float *gamma, float *y, int B, int C, int HW, int inverse);
 /* Residual(PreNorm(LinearAttention)) (:10-16,69-77,117-139): y = to_out(attn(to_qkv(LN(x)))) + x. */
 int cdc_op_linear_attention(cdc_handle *h, const float *x, const float *norm_g,
                             const float *norm_b, const float *w_qkv, const float *w_out,
