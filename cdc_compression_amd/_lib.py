@@ -4,6 +4,8 @@ import ctypes
 import os
 import subprocess
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # CDC_HIP_LIB selects another build of the same HIP library (A/B kernel experiments, tools/build_variant.sh)
 LIB_PATH = os.environ.get("CDC_HIP_LIB") or os.path.join(_HERE, "libcdc_hip.so")
@@ -203,3 +205,101 @@ def check(handle, rc):
         if "must be multiples of" in msg:
             msg += " -- padded_size(H, W) gives the frame; compress() / decompress() / the compressor's forward() pad any size themselves"
         raise CdcError(f"libcdc_hip error {rc}: {msg}")
+
+
+def device_index_of(device):
+    """The device index a model's `device=` / `.to()` argument names: an int, "cuda", "cuda:3", torch.device("cuda", 2); 0 when it
+    names none (None, "cuda", an object whose .index is None)."""
+    if device is None:
+        return 0
+    if isinstance(device, str):
+        return int(device.split(":")[1]) if ":" in device else 0
+    if hasattr(device, "index"):
+        return int(device.index or 0)
+    return int(device)
+
+
+class Handle:
+    """The one owner of a library handle (cdc_handle*) of the Python mirror: created on first use, destroyed with this object, and
+    re-created on another device with everything it was given.
+
+    create: the constructor's name ("cdc_create", "cdc_ctxdec_create", ...); config: a callable returning its filled config structure
+    (None: the constructor takes none, cdc_lpips_create); setup(ptr): runs after every creation (cdc_enable_vbr, ...) -- when it raises,
+    the fresh handle is destroyed and the next use tries again."""
+
+    def __init__(self, create, config, device_index, setup=None):
+        self.create, self.config, self.device_index, self.setup = create, config, int(device_index), setup
+        self.raw = None            # the c_void_p while a handle exists
+        self.tensors = {}          # name -> a float32 copy of the array load() was given, in its shape (what a move replays)
+        self.finalized = False     # finalize() has run since the last load()
+
+    @property
+    def ptr(self):
+        """The handle; a new one gets setup(), every remembered tensor, and final weights again if they were final."""
+        if self.raw is None:
+            L = lib()
+            h = _vp()
+            args = () if self.config is None else (ctypes.byref(self.config()),)
+            rc = getattr(L, self.create)(*args, self.device_index, ctypes.byref(h))
+            if rc != 0:
+                raise CdcError(f"{self.create} failed ({rc}): {L.cdc_last_error(None).decode()}")
+            self.raw = h
+            try:
+                if self.setup is not None:
+                    self.setup(h)
+                for name, a in self.tensors.items():
+                    self._load(h, name, a)
+                if self.finalized:
+                    check(h, L.cdc_finalize_weights(h))
+            except BaseException:
+                self.close()
+                raise
+        return self.raw
+
+    def manifest(self):
+        """[(name, shape)] of the required tensors, in the library's (= the reference state_dict's) order."""
+        L, h = lib(), self.ptr
+        out = []
+        for i in range(L.cdc_num_tensors(h)):
+            name = ctypes.c_char_p()
+            shape = (ctypes.c_int64 * 4)()
+            nd = ctypes.c_int()
+            check(h, L.cdc_tensor_info(h, i, ctypes.byref(name), shape, ctypes.byref(nd)))
+            out.append((name.value.decode(), tuple(shape[j] for j in range(nd.value))))
+        return out
+
+    @staticmethod
+    def _load(h, name, a):
+        shape = (ctypes.c_int64 * max(a.ndim, 1))(*a.shape)
+        check(h, lib().cdc_load_tensor(h, name.encode(), a.ctypes.data, shape, a.ndim))
+
+    def load(self, name, array):
+        a = np.array(array, dtype=np.float32, order="C")       # a copy: what a move replays is what was loaded, whatever the caller does next
+        self._load(self.ptr, name, a)
+        self.tensors[name] = a
+        self.finalized = False
+
+    def finalize(self):
+        h = self.ptr
+        check(h, lib().cdc_finalize_weights(h))
+        self.finalized = True
+
+    def status(self):
+        return handle_status(self.raw)
+
+    def close(self):
+        if self.raw is not None:
+            h, self.raw = self.raw, None
+            lib().cdc_destroy(h)
+
+    def move(self, device_index):
+        """Bind to another device: the handle goes, what was loaded stays; the next `ptr` creates it there.  Touches no device."""
+        if int(device_index) != self.device_index:
+            self.close()
+            self.device_index = int(device_index)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

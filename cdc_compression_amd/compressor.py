@@ -44,68 +44,95 @@ class NormalDistribution:
         return self.loc
 
 
+def _enable_vbr(h):
+    """setup of a compressor handle of a VBR model: the manifest with the VBRCondition sites."""
+    rc = _lib.lib().cdc_enable_vbr(h)
+    if rc != 0:
+        raise _lib.CdcError(f"cdc_enable_vbr failed ({rc}): {_lib.lib().cdc_last_error(h).decode()}")
+
+
 class _ContextDecoder:
     _up_index = 1
     _ctxdec_create = "cdc_ctxdec_create"        # the library's constructors of this model's context-decoder / encoder handles
     _encoder_create = "cdc_encoder_create"
 
-    def __init__(self, dim, rev_mults, out_channels, device=0, vbr=False):
+    def __init__(self, dim, dim_mults, rev_mults, hyper_dims_mults, channels, out_channels, device=0, vbr=False):
         self.vbr = bool(vbr)
         self.dim = dim
+        self.dim_mults, self.hyper_dims_mults, self.channels = tuple(dim_mults), tuple(hyper_dims_mults), channels
         self.rev_mults = tuple(rev_mults)
         self.out_channels = out_channels
         self.reversed_dims = [dim * m for m in self.rev_mults] + [out_channels]
+        # compress_modules.py:26-31
+        self.reversed_hyper_dims = list(reversed([dim * self.dim_mults[-1] * 2] + [dim * m for m in self.hyper_dims_mults]))
         self.training = False
-        self.device_index = int(device) if not hasattr(device, "index") else (device.index or 0)
-        self._h = None
-        self._sd = {}
-        self._finalized = False
-        self._hh = None
         self._hyper_finalized = False
         self._prior_loaded = False
         self._medians = None
-        self._eh = None
         self._enc_finalized = False
-        self.reversed_hyper_dims = None
-        self._full_sd = None          # host copy of every entry load_state_dict() used (replayed by .to())
+        # the three library handles (_lib.Handle); their closures hold values, not self: no reference cycle delays cdc_destroy
+        index, rev, dm, hm, hyper_dims = self._up_index, self.rev_mults, self.dim_mults, self.hyper_dims_mults, self.reversed_hyper_dims
+        multiple, vbr_setup = self.frame_multiple, _enable_vbr if self.vbr else None
+
+        def dec_config():
+            cfg = _lib.CtxdecConfig()
+            cfg.dim, cfg.out_channels, cfg.up_index = dim, out_channels, index
+            cfg.n_rev_mults = len(rev)
+            for i, m in enumerate(rev):
+                cfg.rev_mults[i] = m
+            return cfg
+
+        def hyper_config():
+            cfg = _lib.HyperdecConfig()
+            cfg.n_layers = len(hyper_dims) - 1
+            for i, d in enumerate(hyper_dims):
+                cfg.dims[i] = d
+            return cfg
+
+        def hyper_setup(h):
+            if vbr_setup:
+                vbr_setup(h)
+            # image pixels per hyper-latent position (the streams of images that are not their own frame need it)
+            _lib.check(h, _lib.lib().cdc_entropy_set_image_scale(h, multiple))
+
+        def enc_config():
+            cfg = _lib.EncoderConfig()
+            cfg.dim, cfg.channels, cfg.down_index = dim, channels, index
+            cfg.n_dim_mults, cfg.n_hyper_mults = len(dm), len(hm)
+            for i, m in enumerate(dm):
+                cfg.dim_mults[i] = m
+            for i, m in enumerate(hm):
+                cfg.hyper_mults[i] = m
+            return cfg
+        dev = _lib.device_index_of(device)
+        self._dec = _lib.Handle(self._ctxdec_create, dec_config, dev, vbr_setup)
+        self._hyper = _lib.Handle("cdc_hyperdec_create", hyper_config, dev, hyper_setup)
+        self._enc = _lib.Handle(self._encoder_create, enc_config, dev, vbr_setup)
+
+    def _handle(self):
+        return self._dec.ptr
+
+    def _hyper_handle(self):
+        return self._hyper.ptr
+
+    def _enc_handle(self):
+        return self._enc.ptr
+
+    _h = property(lambda self: self._dec.raw)
+    _hh = property(lambda self: self._hyper.raw)
+    _eh = property(lambda self: self._enc.raw)
+    _finalized = property(lambda self: self._dec.finalized)
+    device_index = property(lambda self: self._dec.device_index)
 
     def status(self):
         """Per library handle (context decoder, hyper decoder, encoder): arithmetic mode and range-guard counters."""
-        return {name: _lib.handle_status(getattr(self, attr, None)) for name, attr in (("dec", "_h"), ("hyper_dec", "_hh"), ("enc", "_eh"))}
+        return {"dec": self._dec.status(), "hyper_dec": self._hyper.status(), "enc": self._enc.status()}
 
     @property
     def range_faults(self):
         return sum(v["range_faults"] for v in self.status().values())
 
-    # ---- handle management ----------------------------------------------------------------
-    def _handle(self):
-        if self._h is None:
-            L = _lib.lib()
-            cfg = _lib.CtxdecConfig()
-            cfg.dim, cfg.out_channels, cfg.up_index = self.dim, self.out_channels, self._up_index
-            cfg.n_rev_mults = len(self.rev_mults)
-            for i, m in enumerate(self.rev_mults):
-                cfg.rev_mults[i] = m
-            h = ctypes.c_void_p()
-            rc = getattr(L, self._ctxdec_create)(ctypes.byref(cfg), self.device_index, ctypes.byref(h))
-            if rc != 0:
-                raise _lib.CdcError(f"{self._ctxdec_create} failed ({rc}): {L.cdc_last_error(None).decode()}")
-            self._h = self._vbr_handle(h)
-            for k, v in self._sd.items():
-                self._load_one(k, v)
-        return self._h
-
     # ---- variable bitrate ---------------------------------------------------------------------
-    def _vbr_handle(self, h):
-        """A freshly created handle, switched to the VBR model (manifest with the VBRCondition sites) when this is one."""
-        if self.vbr:
-            rc = _lib.lib().cdc_enable_vbr(h)
-            if rc != 0:
-                msg = _lib.lib().cdc_last_error(h).decode()
-                _lib.lib().cdc_destroy(h)
-                raise _lib.CdcError(f"cdc_enable_vbr failed ({rc}): {msg}")
-        return h
-
     def _rates(self, cond, B):
         """cond / bitrate_scale -> float32 host vector of 1 or B rates (VBR model), None (fixed-rate model)."""
         if not self.vbr:
@@ -124,37 +151,12 @@ class _ContextDecoder:
         if r is not None:
             _lib.check(h, _lib.lib().cdc_set_bitrate_scale(h, r.ctypes.data, int(r.size)))
 
-    def __del__(self):
-        try:
-            if self._h is not None:
-                _lib.lib().cdc_destroy(self._h)
-                self._h = None
-            if self._hh is not None:
-                _lib.lib().cdc_destroy(self._hh)
-                self._hh = None
-            if self._eh is not None:
-                _lib.lib().cdc_destroy(self._eh)
-                self._eh = None
-        except Exception:
-            pass
-
     def to(self, device):
-        idx = device if isinstance(device, int) else getattr(device, "index", None)
-        if isinstance(device, str):
-            idx = int(device.split(":")[1]) if ":" in device else 0
-        idx = 0 if idx is None else int(idx)
-        if idx != self.device_index:
-            # the handles are bound to a device: drop them and replay the parameters on the new one
-            for attr in ("_h", "_hh", "_eh"):
-                if getattr(self, attr) is not None:
-                    _lib.lib().cdc_destroy(getattr(self, attr))
-                    setattr(self, attr, None)
-            self._finalized = self._hyper_finalized = self._enc_finalized = self._prior_loaded = False
-            self.device_index = idx
-            if self._full_sd:
-                full, self._sd = self._full_sd, {}
-                self.load_state_dict(full, strict=False)
-        self.device_index = idx
+        """Another device: the three handles go now, and nothing else happens here.  The next use of each creates it on the new device
+        with its parameters loaded and final as they were, so an error of that device (no such device, out of memory) surfaces at
+        that use, not in .to()."""
+        for lh in (self._dec, self._hyper, self._enc):
+            lh.move(_lib.device_index_of(device))
         return self
 
     def eval(self):
@@ -164,28 +166,11 @@ class _ContextDecoder:
     # ---- parameters -----------------------------------------------------------------------
     def manifest(self):
         """[(name, shape)] of the `dec.*` entries, in the reference's registration order."""
-        L, h = _lib.lib(), self._handle()
-        out = []
-        for i in range(L.cdc_num_tensors(h)):
-            name = ctypes.c_char_p()
-            shape = (ctypes.c_int64 * 4)()
-            nd = ctypes.c_int()
-            _lib.check(h, L.cdc_tensor_info(h, i, ctypes.byref(name), shape, ctypes.byref(nd)))
-            out.append((name.value.decode(), tuple(shape[j] for j in range(nd.value))))
-        return out
-
-    def _load_one(self, name, value):
-        L, h = _lib.lib(), self._h
-        a = _as_host_f32(value)
-        shape = (ctypes.c_int64 * max(a.ndim, 1))(*a.shape)
-        _lib.check(h, L.cdc_load_tensor(h, name.encode(), a.ctypes.data, shape, a.ndim))
+        return self._dec.manifest()
 
     def load_state_dict(self, state_dict, strict=True):
         """Takes the `dec.*` entries; the encoder / hyperprior entries of a full reference state_dict are
         not this module's.  strict: every `dec.*` key must match the manifest."""
-        h = self._handle()
-        self._full_sd = {k: _as_host_f32(v).copy() for k, v in state_dict.items()
-                         if k.split(".")[0] in ("dec", "hyper_dec", "enc", "hyper_enc", "prior")}
         names = [n for n, _ in self.manifest()]
         missing = [n for n in names if n not in state_dict]
         unexpected = [k for k in state_dict if k.startswith("dec.") and k not in names]
@@ -194,10 +179,8 @@ class _ContextDecoder:
                                f"{missing[:3]}{'...' if len(missing) > 3 else ''}, unexpected {unexpected[:3]}")
         for n in names:
             if n in state_dict:
-                self._sd[n] = _as_host_f32(state_dict[n])
-                self._load_one(n, self._sd[n])
-        _lib.check(h, _lib.lib().cdc_finalize_weights(h))
-        self._finalized = True
+                self._dec.load(n, _as_host_f32(state_dict[n]))
+        self._dec.finalize()
         if any(k.startswith("hyper_dec.") for k in state_dict):
             self.load_hyper_state_dict(state_dict)      # also takes prior.* when present
         if any(k.startswith("enc.") for k in state_dict):
@@ -205,7 +188,7 @@ class _ContextDecoder:
         return self
 
     def state_dict(self):
-        return dict(self._sd)
+        return dict(self._dec.tensors)
 
     # ---- Compressor.decode ------------------------------------------------------------------
     def decode(self, input, cond=None):
@@ -233,36 +216,11 @@ class _ContextDecoder:
         return outs
 
     # ---- hyperprior, decode side -----------------------------------------------------------
-    def _hyper_handle(self):
-        if self._hh is None:
-            L = _lib.lib()
-            cfg = _lib.HyperdecConfig()
-            cfg.n_layers = len(self.reversed_hyper_dims) - 1
-            for i, d in enumerate(self.reversed_hyper_dims):
-                cfg.dims[i] = d
-            h = ctypes.c_void_p()
-            rc = L.cdc_hyperdec_create(ctypes.byref(cfg), self.device_index, ctypes.byref(h))
-            if rc != 0:
-                raise _lib.CdcError(f"cdc_hyperdec_create failed ({rc}): {L.cdc_last_error(None).decode()}")
-            self._hh = self._vbr_handle(h)
-            # image pixels per hyper-latent position (the streams of images that are not their own frame need it)
-            _lib.check(self._hh, L.cdc_entropy_set_image_scale(self._hh, self.frame_multiple))
-        return self._hh
-
     def hyper_manifest(self):
-        L, h = _lib.lib(), self._hyper_handle()
-        out = []
-        for i in range(L.cdc_num_tensors(h)):
-            name = ctypes.c_char_p()
-            shape = (ctypes.c_int64 * 4)()
-            nd = ctypes.c_int()
-            _lib.check(h, L.cdc_tensor_info(h, i, ctypes.byref(name), shape, ctypes.byref(nd)))
-            out.append((name.value.decode(), tuple(shape[j] for j in range(nd.value))))
-        return out
+        return self._hyper.manifest()
 
     def load_hyper_state_dict(self, state_dict):
         """`hyper_dec.*` entries of the reference compressor's state_dict."""
-        L, h = _lib.lib(), self._hyper_handle()
         names = [n for n, _ in self.hyper_manifest()]
         missing = [n for n in names if n not in state_dict]
         unexpected = [k for k in state_dict if k.startswith("hyper_dec.") and k not in names]
@@ -270,9 +228,7 @@ class _ContextDecoder:
             raise RuntimeError(f"Error(s) in loading state_dict for {type(self).__name__}.hyper_dec: missing "
                                f"{missing[:3]}, unexpected {unexpected[:3]}")
         for n in names:
-            a = _as_host_f32(state_dict[n])
-            shape = (ctypes.c_int64 * max(a.ndim, 1))(*a.shape)
-            _lib.check(h, L.cdc_load_tensor(h, n.encode(), a.ctypes.data, shape, a.ndim))
+            self._hyper.load(n, _as_host_f32(state_dict[n]))
         # FlexiblePrior (rate estimate only): reference shapes [C,1,1,in,out] / [C,1,1,1,out], singleton axes squeezed
         self._prior_loaded = False
         pk = [k for k in state_dict if k.startswith("prior.affine.") or k.startswith("prior.a.")]
@@ -284,12 +240,11 @@ class _ContextDecoder:
                                          if a.ndim == 5 else a)
                 if a.ndim == 3 and not k.endswith(".weight"):
                     a = np.ascontiguousarray(a.reshape(C, -1))
-                shape = (ctypes.c_int64 * a.ndim)(*a.shape)
-                _lib.check(h, L.cdc_load_tensor(h, k.encode(), a.ctypes.data, shape, a.ndim))
+                self._hyper.load(k, a)
             self._prior_loaded = True
         if "prior._medians" in state_dict:
             self._medians = _as_host_f32(state_dict["prior._medians"]).reshape(1, -1, 1, 1)
-        _lib.check(h, L.cdc_finalize_weights(h))
+        self._hyper.finalize()
         self._hyper_finalized = True
         return self
 
@@ -378,37 +333,11 @@ class _ContextDecoder:
         return frame.pad(self._enc_handle(), input, Hp, Wp, self.device_index), (H, W)
 
     # ---- encoder ---------------------------------------------------
-    def _enc_handle(self):
-        if self._eh is None:
-            L = _lib.lib()
-            cfg = _lib.EncoderConfig()
-            cfg.dim, cfg.channels, cfg.down_index = self.dim, self.channels, self._up_index
-            cfg.n_dim_mults, cfg.n_hyper_mults = len(self.dim_mults), len(self.hyper_dims_mults)
-            for i, m in enumerate(self.dim_mults):
-                cfg.dim_mults[i] = m
-            for i, m in enumerate(self.hyper_dims_mults):
-                cfg.hyper_mults[i] = m
-            h = ctypes.c_void_p()
-            rc = getattr(L, self._encoder_create)(ctypes.byref(cfg), self.device_index, ctypes.byref(h))
-            if rc != 0:
-                raise _lib.CdcError(f"{self._encoder_create} failed ({rc}): {L.cdc_last_error(None).decode()}")
-            self._eh = self._vbr_handle(h)
-        return self._eh
-
     def encoder_manifest(self):
-        L, h = _lib.lib(), self._enc_handle()
-        out = []
-        for i in range(L.cdc_num_tensors(h)):
-            name = ctypes.c_char_p()
-            shape = (ctypes.c_int64 * 4)()
-            nd = ctypes.c_int()
-            _lib.check(h, L.cdc_tensor_info(h, i, ctypes.byref(name), shape, ctypes.byref(nd)))
-            out.append((name.value.decode(), tuple(shape[j] for j in range(nd.value))))
-        return out
+        return self._enc.manifest()
 
     def load_encoder_state_dict(self, state_dict):
         """`enc.*` and `hyper_enc.*` entries of the reference compressor's state_dict."""
-        L, h = _lib.lib(), self._enc_handle()
         names = [n for n, _ in self.encoder_manifest()]
         missing = [n for n in names if n not in state_dict]
         unexpected = [k for k in state_dict if (k.startswith("enc.") or k.startswith("hyper_enc.")) and k not in names]
@@ -416,10 +345,8 @@ class _ContextDecoder:
             raise RuntimeError(f"Error(s) in loading state_dict for {type(self).__name__}.enc: missing "
                                f"{missing[:3]}, unexpected {unexpected[:3]}")
         for n in names:
-            a = _as_host_f32(state_dict[n])
-            shape = (ctypes.c_int64 * max(a.ndim, 1))(*a.shape)
-            _lib.check(h, L.cdc_load_tensor(h, n.encode(), a.ctypes.data, shape, a.ndim))
-        _lib.check(h, L.cdc_finalize_weights(h))
+            self._enc.load(n, _as_host_f32(state_dict[n]))
+        self._enc.finalize()
         self._enc_finalized = True
         return self
 
@@ -603,10 +530,7 @@ class ResnetCompressor(_ContextDecoder):
                  hyper_dims_mults=(4, 4, 4), channels=3, out_channels=3, device=0):
         if dim * dim_mults[-1] != dim * reverse_dim_mults[0]:
             raise AssertionError("dims[-1] == reversed_dims[0]")       # compress_modules.py:23
-        super().__init__(dim, reverse_dim_mults, out_channels, device)
-        self.dim_mults, self.hyper_dims_mults, self.channels = tuple(dim_mults), tuple(hyper_dims_mults), channels
-        # compress_modules.py:26-31
-        self.reversed_hyper_dims = list(reversed([dim * dim_mults[-1] * 2] + [dim * m for m in hyper_dims_mults]))
+        super().__init__(dim, dim_mults, reverse_dim_mults, hyper_dims_mults, channels, out_channels, device)
 
 
 class BigCompressor(_ContextDecoder):
@@ -615,9 +539,7 @@ class BigCompressor(_ContextDecoder):
 
     def __init__(self, dim=64, dim_mults=(1, 3, 3, 3), hyper_dims_mults=(3, 3, 3), channels=3,
                  out_channels=3, vbr=False, device=0):
-        super().__init__(dim, tuple(reversed(dim_mults)), out_channels, device, vbr=vbr)
-        self.dim_mults, self.hyper_dims_mults, self.channels = tuple(dim_mults), tuple(hyper_dims_mults), channels
-        self.reversed_hyper_dims = list(reversed([dim * dim_mults[-1] * 2] + [dim * m for m in hyper_dims_mults]))
+        super().__init__(dim, dim_mults, tuple(reversed(dim_mults)), hyper_dims_mults, channels, out_channels, device, vbr=vbr)
 
 
 class SimpleCompressor(_ContextDecoder):
@@ -634,6 +556,4 @@ class SimpleCompressor(_ContextDecoder):
             # compress_modules.py:213: the last `enc` level holds an nn.Identity where Compressor.encode (:46-47) calls vbrscaler(input, cond)
             raise NotImplementedError("SimpleCompressor(vbr=True) does not run in the reference: its first forward raises "
                                       "\"TypeError: Identity.forward() takes 2 positional arguments but 3 were given\"")
-        super().__init__(dim, tuple(reversed(dim_mults)), out_channels, device, vbr=False)
-        self.dim_mults, self.hyper_dims_mults, self.channels = tuple(dim_mults), tuple(hyper_dims_mults), channels
-        self.reversed_hyper_dims = list(reversed([dim * dim_mults[-1] * 2] + [dim * m for m in hyper_dims_mults]))
+        super().__init__(dim, dim_mults, tuple(reversed(dim_mults)), hyper_dims_mults, channels, out_channels, device, vbr=False)

@@ -440,45 +440,36 @@ int cdc_load_tensor(cdc_handle *h, const char *name, const float *data, const in
     return CDC_OK;
 }
 
-int cdc_encoder_create(const cdc_encoder_config *cfg, int device, cdc_handle **out) {
+namespace {
+// cdc_encoder_create / cdc_simple_encoder_create (simple: the GDN model, whose levels hold their layers at fixed indices: no down_index)
+int encoder_create(const cdc_encoder_config *cfg, int device, bool simple, cdc_handle **out) {
     if (!cfg || !out) return fail(nullptr, CDC_ERR_INVALID, "null argument");
+    const int down_index = simple ? 1 : cfg->down_index;
     if (cfg->dim <= 0 || cfg->channels < 1 || cfg->n_dim_mults < 1 || cfg->n_dim_mults > CDC_MAX_LEVELS ||
-        cfg->n_hyper_mults < 1 || cfg->n_hyper_mults > CDC_MAX_LEVELS || cfg->down_index < 1 || cfg->down_index > 2)
+        cfg->n_hyper_mults < 1 || cfg->n_hyper_mults > CDC_MAX_LEVELS || down_index < 1 || down_index > 2)
         return fail(nullptr, CDC_ERR_INVALID, "bad cdc_encoder_config");
     if (device < 0) return fail(nullptr, CDC_ERR_INVALID, "device %d out of range", device);
-    std::unique_ptr<cdc_handle> h(new cdc_handle);
-    memset(&h->cfg, 0, sizeof h->cfg);
-    h->cfg.dim = cfg->dim;
-    h->kind = HandleKind::Encoder;
-    h->device = device;
-    h->down_index = cfg->down_index;
-    h->enc_dims.push_back(cfg->channels);
-    for (int i = 0; i < cfg->n_dim_mults; ++i) h->enc_dims.push_back(cfg->dim * cfg->dim_mults[i]);
-    h->henc_dims.push_back(h->enc_dims.back());
-    for (int i = 0; i < cfg->n_hyper_mults; ++i) h->henc_dims.push_back(cfg->dim * cfg->hyper_mults[i]);
-    build_compressor_manifest(h.get());
-    *out = h.release();
-    return CDC_OK;
-}
-
-int cdc_simple_encoder_create(const cdc_encoder_config *cfg, int device, cdc_handle **out) {
-    if (!cfg || !out) return fail(nullptr, CDC_ERR_INVALID, "null argument");
-    cdc_encoder_config c = *cfg;
-    c.down_index = 1;           // (ignored: the level's layers sit at fixed indices 0 and 2)
-    *out = nullptr;
-    int rc = cdc_encoder_create(&c, device, out);
-    if (rc) return rc;
-    cdc_handle *h = *out;
-    rc = no_throw(nullptr, [&] {
-        h->simple = true;
-        h->params.clear();
-        h->pindex.clear();
-        build_compressor_manifest(h);
+    return no_throw(nullptr, [&] {
+        std::unique_ptr<cdc_handle> h(new cdc_handle);
+        memset(&h->cfg, 0, sizeof h->cfg);
+        h->cfg.dim = cfg->dim;
+        h->kind = HandleKind::Encoder;
+        h->simple = simple;
+        h->device = device;
+        h->down_index = down_index;
+        h->enc_dims.push_back(cfg->channels);
+        for (int i = 0; i < cfg->n_dim_mults; ++i) h->enc_dims.push_back(cfg->dim * cfg->dim_mults[i]);
+        h->henc_dims.push_back(h->enc_dims.back());
+        for (int i = 0; i < cfg->n_hyper_mults; ++i) h->henc_dims.push_back(cfg->dim * cfg->hyper_mults[i]);
+        build_compressor_manifest(h.get());
+        *out = h.release();
         return CDC_OK;
     });
-    if (rc) { cdc_destroy(h); *out = nullptr; }
-    return rc;
 }
+}  // namespace
+
+int cdc_encoder_create(const cdc_encoder_config *cfg, int device, cdc_handle **out) { return encoder_create(cfg, device, false, out); }
+int cdc_simple_encoder_create(const cdc_encoder_config *cfg, int device, cdc_handle **out) { return encoder_create(cfg, device, true, out); }
 
 int cdc_encoder_encode(cdc_handle *h, const float *images, float *latent, float *hyper_latent, int B, int H, int W,
                        int mem, void *stream) {
@@ -526,32 +517,12 @@ int cdc_bpp(cdc_handle *h, const float *q_hyper_latent, const float *q_latent, c
     const long long nh = (long long)Ch * hh * wh, up = 1LL << ((int)h->hyper_dims.size() - 2),
                     nl = (long long)Cl * up * up * hh * wh;   // hyper_dec upsamples by 2 per layer but the last
     hipStream_t st = pick_stream(h, stream, mem);
-    DevPool tmp;                                      // host pointers: device copies of the operands and of the result
-    auto dev = [&](const float *p, long long n) -> const float * {
-        if (mem == CDC_MEM_DEVICE) return p;
-        float *d = nullptr;
-        if (tmp.get(&d, (size_t)n) != hipSuccess) return nullptr;
-        (void)hipMemcpyAsync(d, p, sizeof(float) * n, hipMemcpyHostToDevice, st);
-        return d;
-    };
-    const float *dqh = dev(q_hyper_latent, B * nh), *dql = dev(q_latent, B * nl), *dm = dev(mean, B * nl),
-                *ds = dev(scale, B * nl);
-    float *dout = nullptr;
-    hipError_t e = hipSuccess;
-    if (!dqh || !dql || !dm || !ds) e = hipErrorOutOfMemory;
-    if (e == hipSuccess) {
-        if (mem == CDC_MEM_DEVICE) dout = bpp;
-        else e = tmp.get(&dout, (size_t)B);
-    }
-    if (e == hipSuccess)
-        e = bpp_launch(dqh, nh, hh * wh, h->d_prior, dql, dm, ds, nl, 1.0f / ((float)H_img * (float)W_img), dout, B, st);
-    if (e == hipSuccess && mem != CDC_MEM_DEVICE) {
-        e = hipMemcpyAsync(bpp, dout, sizeof(float) * B, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-    }
-    if (mem != CDC_MEM_DEVICE) (void)hipStreamSynchronize(st);   // nothing queued may still use what tmp frees
-    if (e != hipSuccess) return fail(h, CDC_ERR_HIP, "cdc_bpp: %s", hipGetErrorString(e));
-    return CDC_OK;
+    Staging s(h, mem, st);
+    const float *dqh = s.in(q_hyper_latent, sizeof(float) * B * nh), *dql = s.in(q_latent, sizeof(float) * B * nl),
+                *dm = s.in(mean, sizeof(float) * B * nl), *ds = s.in(scale, sizeof(float) * B * nl);
+    float *dout = s.out(bpp, sizeof(float) * B);
+    if (s.ok()) s.e = bpp_launch(dqh, nh, hh * wh, h->d_prior, dql, dm, ds, nl, 1.0f / ((float)H_img * (float)W_img), dout, B, st);
+    return s.finish("cdc_bpp");
 }
 
 int cdc_hyperdec_decode(cdc_handle *h, const float *q_hyper_latent, float *mean, float *scale, int B, int hh,
@@ -582,22 +553,11 @@ int cdc_dequantize(cdc_handle *h, const float *x, const float *offset, float *ou
     if (rc) return rc;
     if (!x || !offset || !out || n < 1) return fail(h, CDC_ERR_INVALID, "null/invalid argument");
     hipStream_t st = pick_stream(h, stream, mem);
-    if (mem == CDC_MEM_DEVICE) {
-        HIP_TRY(h, dequantize_launch(x, offset, out, n, st));
-        return CDC_OK;
-    }
-    DevPool d;
-    float *dx, *dl;
-    HIP_TRY(h, d.get(&dx, (size_t)n));
-    if (d.get(&dl, (size_t)n) != hipSuccess) return fail(h, CDC_ERR_NOMEM, "hipMalloc failed");
-    hipError_t e = hipMemcpyAsync(dx, x, sizeof(float) * n, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dl, offset, sizeof(float) * n, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = dequantize_launch(dx, dl, dx, n, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dx, sizeof(float) * n, hipMemcpyDeviceToHost, st);
-    const hipError_t es = hipStreamSynchronize(st);   // (after an error too: nothing queued may still use what d frees)
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return fail(h, CDC_ERR_HIP, "dequantize: %s", hipGetErrorString(e));
-    return CDC_OK;
+    Staging s(h, mem, st);
+    const float *dx = s.in(x, sizeof(float) * n), *dl = s.in(offset, sizeof(float) * n);
+    float *dout = s.out(out, sizeof(float) * n, (void *)dx);      // host memory: in place over the staged x
+    if (s.ok()) s.e = dequantize_launch(dx, dl, dout, n, st);
+    return s.finish("dequantize");
 }
 
 // ---- images of any size: the padded frame (frame_kernels.hip) ------------------------------------------------------------------
@@ -621,23 +581,11 @@ int cdc_frame_pad(cdc_handle *h, const void *src, float *dst, int B, int H, int 
             if (fill != CDC_FILL_EDGE && fill != CDC_FILL_ZERO) return fail(h, CDC_ERR_INVALID, "frame: fill mode %d", fill);
             const int P = 3 * B, u8 = elem == CDC_ELEM_U8;
             hipStream_t st = pick_stream(h, stream, mem);
-            if (mem == CDC_MEM_DEVICE) {
-                HIP_TRY(h, frame_in_launch(src, u8, dst, P, H, W, Hp, Wp, fill, st));
-                return CDC_OK;
-            }
-            const size_t nin = (size_t)P * H * W * (u8 ? 1 : 4), nout = (size_t)P * Hp * Wp;
-            DevPool d;
-            uint8_t *ds;
-            float *dd;
-            HIP_TRY(h, d.get(&ds, nin));
-            HIP_TRY(h, d.get(&dd, nout));
-            hipError_t e = hipMemcpyAsync(ds, src, nin, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) e = frame_in_launch(ds, u8, dd, P, H, W, Hp, Wp, fill, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(dst, dd, nout * sizeof(float), hipMemcpyDeviceToHost, st);
-            const hipError_t es = hipStreamSynchronize(st);   // (after an error too: nothing queued may still use what d frees)
-            if (e == hipSuccess) e = es;
-            if (e != hipSuccess) return fail(h, CDC_ERR_HIP, "frame_pad: %s", hipGetErrorString(e));
-            return CDC_OK;
+            Staging s(h, mem, st);
+            const void *ds = s.in(src, (size_t)P * H * W * (u8 ? 1 : 4));
+            float *dd = s.out(dst, (size_t)P * Hp * Wp * sizeof(float));
+            if (s.ok()) s.e = frame_in_launch(ds, u8, dd, P, H, W, Hp, Wp, fill, st);
+            return s.finish("frame_pad");
         });
     });
 }
@@ -651,28 +599,31 @@ int cdc_frame_crop(cdc_handle *h, const float *src, void *dst, int B, int H, int
             if ((rc = frame_args(h, src, dst, B, H, W, Hp, Wp, elem, mem))) return rc;
             const int P = 3 * B, u8 = elem == CDC_ELEM_U8;
             hipStream_t st = pick_stream(h, stream, mem);
-            if (mem == CDC_MEM_DEVICE) {
-                HIP_TRY(h, frame_out_launch(src, dst, u8, P, H, W, Hp, Wp, st));
-                return CDC_OK;
-            }
-            const size_t nin = (size_t)P * Hp * Wp, nout = (size_t)P * H * W * (u8 ? 1 : 4);
-            DevPool d;
-            float *ds;
-            uint8_t *dd;
-            HIP_TRY(h, d.get(&ds, nin));
-            HIP_TRY(h, d.get(&dd, nout));
-            hipError_t e = hipMemcpyAsync(ds, src, nin * sizeof(float), hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) e = frame_out_launch(ds, dd, u8, P, H, W, Hp, Wp, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(dst, dd, nout, hipMemcpyDeviceToHost, st);
-            const hipError_t es = hipStreamSynchronize(st);
-            if (e == hipSuccess) e = es;
-            if (e != hipSuccess) return fail(h, CDC_ERR_HIP, "frame_crop: %s", hipGetErrorString(e));
-            return CDC_OK;
+            Staging s(h, mem, st);
+            const float *ds = s.in(src, (size_t)P * Hp * Wp * sizeof(float));
+            void *dd = s.out(dst, (size_t)P * H * W * (u8 ? 1 : 4));
+            if (s.ok()) s.e = frame_out_launch(ds, dd, u8, P, H, W, Hp, Wp, st);
+            return s.finish("frame_crop");
         });
     });
 }
 
 // ---- distortion of decoded images (metric_kernels.hip) ---------------------------------------------------------------------------------
+namespace {
+// One cdc_image_view operand (`name`: 'a' / 'b') of cdc_distortion / cdc_lpips (`what`), checked against the B x H x W window: the view
+// the kernels take and the operand's size in bytes.
+int image_operand(cdc_handle *h, const char *what, const cdc_image_view &v, char name, int B, int H, int W, MetricView *mv, size_t *bytes) {
+    const bool u8 = v.elem_kind == CDC_ELEM_U8;
+    if (v.elem_kind != CDC_ELEM_F32 && !u8) return fail(h, CDC_ERR_INVALID, "%s: operand %c has element kind %d", what, name, v.elem_kind);
+    if (v.Hf < H || v.Wf < W) return fail(h, CDC_ERR_INVALID, "%s: operand %c is a %d x %d frame, smaller than the %d x %d window", what, name, v.Hf, v.Wf, H, W);
+    if (v.as_saved && u8) return fail(h, CDC_ERR_INVALID, "%s: as_saved on operand %c, which is uint8 already", what, name);
+    if ((long long)B * 3 * v.Hf * v.Wf > (1ll << 40)) return fail(h, CDC_ERR_INVALID, "%s: %d x 3 x %d x %d elements", what, B, v.Hf, v.Wf);
+    *mv = {v.data, u8 ? METRIC_U8 : (v.as_saved ? METRIC_F32_SAVED : METRIC_F32), v.Hf, v.Wf};
+    *bytes = (size_t)B * 3 * v.Hf * v.Wf * (u8 ? 1 : 4);
+    return CDC_OK;
+}
+}  // namespace
+
 int cdc_distortion(cdc_handle *h, const cdc_image_view *a, const cdc_image_view *b, int B, int H, int W, int what, double *psnr,
                    double *msssim, double *components, int mem, void *stream) {
     if (!h) return CDC_ERR_INVALID;
@@ -689,17 +640,8 @@ int cdc_distortion(cdc_handle *h, const cdc_image_view *a, const cdc_image_view 
             if (want_ms && !msssim) return fail(h, CDC_ERR_INVALID, "distortion: MS-SSIM requested without an msssim array");
             MetricView mv[2];
             size_t bytes[2];
-            const cdc_image_view *src[2] = {a, b};
-            for (int i = 0; i < 2; ++i) {
-                const cdc_image_view &v = *src[i];
-                const char n = "ab"[i];
-                if (v.elem_kind != CDC_ELEM_F32 && v.elem_kind != CDC_ELEM_U8) return fail(h, CDC_ERR_INVALID, "distortion: operand %c has element kind %d", n, v.elem_kind);
-                if (v.Hf < H || v.Wf < W) return fail(h, CDC_ERR_INVALID, "distortion: operand %c is a %d x %d frame, smaller than the %d x %d window", n, v.Hf, v.Wf, H, W);
-                if (v.as_saved && v.elem_kind == CDC_ELEM_U8) return fail(h, CDC_ERR_INVALID, "distortion: as_saved on operand %c, which is uint8 already", n);
-                if ((long long)B * 3 * v.Hf * v.Wf > (1ll << 40)) return fail(h, CDC_ERR_INVALID, "distortion: %d x 3 x %d x %d elements", B, v.Hf, v.Wf);
-                mv[i] = {v.data, v.elem_kind == CDC_ELEM_U8 ? METRIC_U8 : (v.as_saved ? METRIC_F32_SAVED : METRIC_F32), v.Hf, v.Wf};
-                bytes[i] = (size_t)B * 3 * v.Hf * v.Wf * (v.elem_kind == CDC_ELEM_U8 ? 1 : 4);
-            }
+            if ((rc = image_operand(h, "distortion", *a, 'a', B, H, W, &mv[0], &bytes[0]))) return rc;
+            if ((rc = image_operand(h, "distortion", *b, 'b', B, H, W, &mv[1], &bytes[1]))) return rc;
             if (want_ms && std::min(H, W) <= 160) return fail(h, CDC_ERR_INVALID, "distortion: MS-SSIM needs min(H, W) > 160 (five scales of an 11-tap window), got %d x %d", H, W);
             MetricLayout L;
             if (!metric_layout(B, H, W, want_psnr, want_ms, &L)) return fail(h, CDC_ERR_INVALID, "distortion: B=%d %d x %d is beyond the launch limits", B, H, W);
@@ -709,24 +651,14 @@ int cdc_distortion(cdc_handle *h, const cdc_image_view *a, const cdc_image_view 
                 if (hipMalloc(&h->metric_work, L.bytes) != hipSuccess) { h->metric_work = nullptr; return fail(h, CDC_ERR_NOMEM, "distortion: hipMalloc of %zu bytes failed", L.bytes); }
                 h->metric_cap = L.bytes;
             }
-            DevPool d;
-            hipError_t e = hipSuccess;
-            if (mem == CDC_MEM_HOST) {
-                for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-                    uint8_t *p;
-                    if (d.get(&p, bytes[i]) != hipSuccess) return fail(h, CDC_ERR_NOMEM, "distortion: hipMalloc failed");
-                    e = hipMemcpyAsync(p, mv[i].data, bytes[i], hipMemcpyHostToDevice, st);
-                    mv[i].data = p;
-                }
-            }
-            if (e == hipSuccess && want_psnr) e = metric_psnr_launch(mv[0], mv[1], B, H, W, L, h->metric_work, st);
-            if (e == hipSuccess && want_ms) e = metric_msssim_launch(mv[0], mv[1], B, L, h->metric_work, st);
+            Staging s(h, mem, st);
+            for (int i = 0; i < 2; ++i) mv[i].data = s.in(mv[i].data, bytes[i]);
+            if (s.ok() && want_psnr) s.e = metric_psnr_launch(mv[0], mv[1], B, H, W, L, h->metric_work, st);
+            if (s.ok() && want_ms) s.e = metric_msssim_launch(mv[0], mv[1], B, L, h->metric_work, st);
             const int per = 2 + METRIC_SCALES * 3;
             std::vector<double> res((size_t)B * per);
-            if (e == hipSuccess) e = hipMemcpyAsync(res.data(), (char *)h->metric_work + L.result_off, sizeof(double) * res.size(), hipMemcpyDeviceToHost, st);
-            const hipError_t es = hipStreamSynchronize(st);   // (after an error too: nothing queued may still use what d frees)
-            if (e == hipSuccess) e = es;
-            if (e != hipSuccess) return fail(h, CDC_ERR_HIP, "distortion: %s", hipGetErrorString(e));
+            s.fetch(res.data(), (char *)h->metric_work + L.result_off, sizeof(double) * res.size());
+            if ((rc = s.finish("distortion"))) return rc;
             if (want_psnr)
                 for (int i = 0; i < B; ++i) psnr[i] = res[i] == 0.0 ? INFINITY : 10.0 * log10(1.0 / res[i]);
             if (want_ms) {
@@ -764,22 +696,13 @@ int cdc_lpips(cdc_handle *h, const cdc_image_view *a, const cdc_image_view *b, i
             if (H < 16 || W < 16) return fail(h, CDC_ERR_INVALID, "lpips: the window is %d x %d, H, W >= 16 is required (four poolings)", H, W);
             if (mem != CDC_MEM_HOST && mem != CDC_MEM_DEVICE) return fail(h, CDC_ERR_INVALID, "lpips: mem_kind %d", mem);
             MetricView mv[2];
-            size_t bytes[2], img_bytes[2];
-            const cdc_image_view *src[2] = {a, b};
-            for (int i = 0; i < 2; ++i) {
-                const cdc_image_view &v = *src[i];
-                const char n = "ab"[i];
-                if (v.elem_kind != CDC_ELEM_F32 && v.elem_kind != CDC_ELEM_U8) return fail(h, CDC_ERR_INVALID, "lpips: operand %c has element kind %d", n, v.elem_kind);
-                if (v.Hf < H || v.Wf < W) return fail(h, CDC_ERR_INVALID, "lpips: operand %c is a %d x %d frame, smaller than the %d x %d window", n, v.Hf, v.Wf, H, W);
-                if (v.as_saved && v.elem_kind == CDC_ELEM_U8) return fail(h, CDC_ERR_INVALID, "lpips: as_saved on operand %c, which is uint8 already", n);
-                if ((long long)B * 3 * v.Hf * v.Wf > (1ll << 40)) return fail(h, CDC_ERR_INVALID, "lpips: %d x 3 x %d x %d elements", B, v.Hf, v.Wf);
-                mv[i] = {v.data, v.elem_kind == CDC_ELEM_U8 ? METRIC_U8 : (v.as_saved ? METRIC_F32_SAVED : METRIC_F32), v.Hf, v.Wf};
-                img_bytes[i] = (size_t)3 * v.Hf * v.Wf * (v.elem_kind == CDC_ELEM_U8 ? 1 : 4);
-                bytes[i] = (size_t)B * img_bytes[i];
-            }
+            size_t bytes[2];
+            int rc;
+            if ((rc = image_operand(h, "lpips", *a, 'a', B, H, W, &mv[0], &bytes[0]))) return rc;
+            if ((rc = image_operand(h, "lpips", *b, 'b', B, H, W, &mv[1], &bytes[1]))) return rc;
+            const size_t img_bytes[2] = {bytes[0] / B, bytes[1] / B};
             if ((long long)H * W > (1ll << 28)) return fail(h, CDC_ERR_INVALID, "lpips: a %d x %d window is beyond the launch limits", H, W);
-            int rc = check_ready(h);
-            if (rc) return rc;
+            if ((rc = check_ready(h))) return rc;
             // A batch runs in equal chunks of `pairs`: as few chunks as keep the program's activations under the budget (one pair at
             // least).  CDC_LPIPS_BUDGET_MB (development switch): another budget, to force a split.
             size_t budget = (size_t)4096 << 20;
@@ -789,41 +712,32 @@ int cdc_lpips(cdc_handle *h, const cdc_image_view *a, const cdc_image_view *b, i
             if ((rc = build_lpips_program(h, pairs, H, W))) return rc;
             const int cap = pairs;                                  // (a program kept from a larger call may hold more: its rows are not used)
             hipStream_t st = pick_stream(h, stream, mem);
-            DevPool d;
-            double *dres = nullptr;
-            if (d.get(&dres, (size_t)B * LPIPS_TAPS) != hipSuccess) return fail(h, CDC_ERR_NOMEM, "lpips: hipMalloc failed");
-            hipError_t e = hipSuccess;
-            if (mem == CDC_MEM_HOST) {
-                for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-                    uint8_t *p;
-                    if (d.get(&p, bytes[i]) != hipSuccess) return fail(h, CDC_ERR_NOMEM, "lpips: hipMalloc failed");
-                    e = hipMemcpyAsync(p, mv[i].data, bytes[i], hipMemcpyHostToDevice, st);
-                    mv[i].data = p;
-                }
-            }
-            if (e == hipSuccess && (rc = arm_range_guard(h, st, false))) e = hipErrorUnknown;
+            Staging s(h, mem, st);
+            std::vector<double> res((size_t)B * LPIPS_TAPS);
+            double *dres = (double *)s.scratch(sizeof(double) * res.size());
+            s.fetch(res.data(), dres, sizeof(double) * res.size());
+            for (int i = 0; i < 2; ++i) mv[i].data = s.in(mv[i].data, bytes[i]);
+            if (s.ok()) rc = arm_range_guard(h, st, false);
             h->prof_now = true;
-            for (int c0 = 0; c0 < B && e == hipSuccess && !rc; c0 += cap) {
+            for (int c0 = 0; c0 < B && s.ok() && !rc; c0 += cap) {
                 const int n = std::min(cap, B - c0);
                 MetricView ca = mv[0], cb = mv[1];
                 ca.data = (const char *)mv[0].data + (size_t)c0 * img_bytes[0];
                 cb.data = (const char *)mv[1].data + (size_t)c0 * img_bytes[1];
-                e = lpips_in_launch(ca, cb, n, H, W, h->lp_shift, h->lp_scale, h->in_x, st);
-                if (e == hipSuccess) rc = run_ops(h, 2 * n, st);
-                if (e == hipSuccess && !rc)
-                    e = hipMemcpyAsync(dres + (size_t)c0 * LPIPS_TAPS, h->lp_res, sizeof(double) * n * LPIPS_TAPS, hipMemcpyDeviceToDevice, st);
+                s.e = lpips_in_launch(ca, cb, n, H, W, h->lp_shift, h->lp_scale, h->in_x, st);
+                if (s.ok()) rc = run_ops(h, 2 * n, st);
+                if (s.ok() && !rc)
+                    s.e = hipMemcpyAsync(dres + (size_t)c0 * LPIPS_TAPS, h->lp_res, sizeof(double) * n * LPIPS_TAPS, hipMemcpyDeviceToDevice, st);
             }
-            std::vector<double> res((size_t)B * LPIPS_TAPS);
-            if (e == hipSuccess && !rc) e = hipMemcpyAsync(res.data(), dres, sizeof(double) * res.size(), hipMemcpyDeviceToHost, st);
-            const hipError_t es = hipStreamSynchronize(st);       // (after an error too: nothing queued may still use what d frees)
+            if (rc) s.drop_results();
+            const int frc = s.finish("lpips");      // (synchronises: the range check below reads the flag)
             if (rc) return rc;
-            if (e == hipSuccess) e = es;
-            if (e != hipSuccess) return fail(h, CDC_ERR_HIP, "lpips: %s", hipGetErrorString(e));
+            if (frc) return frc;
             if ((rc = range_check(h, {}, B, st))) return rc;       // the flag: a non-finite accumulator or layer value
             for (int i = 0; i < B; ++i) {
-                double s = 0.0;
-                for (int l = 0; l < LPIPS_TAPS; ++l) s += res[(size_t)i * LPIPS_TAPS + l];
-                lpips[i] = s;
+                double sum = 0.0;
+                for (int l = 0; l < LPIPS_TAPS; ++l) sum += res[(size_t)i * LPIPS_TAPS + l];
+                lpips[i] = sum;
             }
             if (layers) memcpy(layers, res.data(), sizeof(double) * res.size());
             return CDC_OK;
@@ -853,46 +767,37 @@ int cdc_padded_size(cdc_handle *h, int H, int W, int *Hp, int *Wp) {
     return CDC_OK;
 }
 
-int cdc_ctxdec_create(const cdc_ctxdec_config *cfg, int device, cdc_handle **out) {
+namespace {
+// cdc_ctxdec_create / cdc_simple_ctxdec_create (simple: the GDN model; no up_index)
+int ctxdec_create(const cdc_ctxdec_config *cfg, int device, bool simple, cdc_handle **out) {
     if (!cfg || !out) return fail(nullptr, CDC_ERR_INVALID, "null argument");
+    const int up_index = simple ? 1 : cfg->up_index;
     if (cfg->dim <= 0 || cfg->n_rev_mults < 1 || cfg->n_rev_mults > CDC_MAX_LEVELS || cfg->out_channels < 1 ||
-        cfg->up_index < 1 || cfg->up_index > 2)
+        up_index < 1 || up_index > 2)
         return fail(nullptr, CDC_ERR_INVALID, "bad cdc_ctxdec_config");
     if (device < 0) return fail(nullptr, CDC_ERR_INVALID, "device %d out of range", device);
-    std::unique_ptr<cdc_handle> h(new cdc_handle);
-    memset(&h->cfg, 0, sizeof h->cfg);
-    h->cfg.dim = cfg->dim;
-    h->kind = HandleKind::ContextDecoder;
-    h->device = device;
-    h->up_index = cfg->up_index;
-    for (int i = 0; i < cfg->n_rev_mults; ++i) {
-        if (cfg->rev_mults[i] < 1) return fail(nullptr, CDC_ERR_INVALID, "bad cdc_ctxdec_config");
-        h->rev_dims.push_back(cfg->dim * cfg->rev_mults[i]);
-    }
-    h->rev_dims.push_back(cfg->out_channels);
-    build_compressor_manifest(h.get());
-    *out = h.release();
-    return CDC_OK;
-}
-
-int cdc_simple_ctxdec_create(const cdc_ctxdec_config *cfg, int device, cdc_handle **out) {
-    if (!cfg || !out) return fail(nullptr, CDC_ERR_INVALID, "null argument");
-    cdc_ctxdec_config c = *cfg;
-    c.up_index = 1;             // (ignored)
-    *out = nullptr;
-    int rc = cdc_ctxdec_create(&c, device, out);
-    if (rc) return rc;
-    cdc_handle *h = *out;
-    rc = no_throw(nullptr, [&] {
-        h->simple = true;
-        h->params.clear();
-        h->pindex.clear();
-        build_compressor_manifest(h);
+    return no_throw(nullptr, [&]() -> int {
+        std::unique_ptr<cdc_handle> h(new cdc_handle);
+        memset(&h->cfg, 0, sizeof h->cfg);
+        h->cfg.dim = cfg->dim;
+        h->kind = HandleKind::ContextDecoder;
+        h->simple = simple;
+        h->device = device;
+        h->up_index = up_index;
+        for (int i = 0; i < cfg->n_rev_mults; ++i) {
+            if (cfg->rev_mults[i] < 1) return fail(nullptr, CDC_ERR_INVALID, "bad cdc_ctxdec_config");
+            h->rev_dims.push_back(cfg->dim * cfg->rev_mults[i]);
+        }
+        h->rev_dims.push_back(cfg->out_channels);
+        build_compressor_manifest(h.get());
+        *out = h.release();
         return CDC_OK;
     });
-    if (rc) { cdc_destroy(h); *out = nullptr; }
-    return rc;
 }
+}  // namespace
+
+int cdc_ctxdec_create(const cdc_ctxdec_config *cfg, int device, cdc_handle **out) { return ctxdec_create(cfg, device, false, out); }
+int cdc_simple_ctxdec_create(const cdc_ctxdec_config *cfg, int device, cdc_handle **out) { return ctxdec_create(cfg, device, true, out); }
 
 int cdc_ctxdec_decode(cdc_handle *h, const float *q_latent, float *const *outs, int n_outs, int B,
                       int hl, int wl, int mem, void *stream) {

@@ -357,4 +357,57 @@ struct DevPool {
     }
 };
 
+// Operands and results of one call that may live in host memory (`mem`): a device pointer passes through; a host pointer is staged
+// through device scratch of the call, by copies on the call's stream.  After the first error the later steps are skipped (ok()).
+struct Staging {
+    cdc_handle *h;
+    int mem;
+    hipStream_t st;
+    DevPool pool;
+    hipError_t e = hipSuccess;    // the first HIP error: the caller stores its launches' here (`if (s.ok()) s.e = ..._launch(...)`)
+    bool nomem = false;           // a scratch allocation failed
+    struct Back { void *host; const void *dev; size_t bytes; } backs[4];   // results to copy to the host in finish()
+    int n_backs = 0;
+    bool host_results = false;    // finish() synchronises for a device-memory call too
+    Staging(cdc_handle *h_, int mem_, hipStream_t st_) : h(h_), mem(mem_), st(st_) {}
+    bool ok() const { return e == hipSuccess && !nomem; }
+    void *scratch(size_t bytes) {
+        uint8_t *p = nullptr;
+        if (ok() && pool.get(&p, bytes) != hipSuccess) nomem = true;
+        return p;
+    }
+    template <class T> const T *in(const T *p, size_t bytes) {
+        if (mem == CDC_MEM_DEVICE) return p;
+        void *d = scratch(bytes);
+        if (d) e = hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, st);
+        return (const T *)d;
+    }
+    // a result that lives in host memory whatever `mem` says (the float64 arrays of the metrics)
+    void fetch(void *host, const void *dev, size_t bytes) {
+        host_results = true;
+        if (n_backs < (int)(sizeof backs / sizeof backs[0])) backs[n_backs++] = {host, dev, bytes};
+        else if (e == hipSuccess) e = hipErrorInvalidValue;
+    }
+    void drop_results() { n_backs = 0; }   // a call that failed otherwise: no copies back, finish() still synchronises
+    // dev: device memory the result is produced in when `p` is host memory (default: new scratch)
+    template <class T> T *out(T *p, size_t bytes, void *dev = nullptr) {
+        if (mem == CDC_MEM_DEVICE) return p;
+        if (!dev) dev = scratch(bytes);
+        fetch(p, dev, bytes);
+        return (T *)dev;
+    }
+    // the copies back, then -- when host memory was involved -- one synchronisation, after an error too: nothing queued may still use
+    // what the pool frees
+    int finish(const char *what) {
+        for (int i = 0; i < n_backs && ok(); ++i) e = hipMemcpyAsync(backs[i].host, backs[i].dev, backs[i].bytes, hipMemcpyDeviceToHost, st);
+        if (mem != CDC_MEM_DEVICE || host_results) {
+            const hipError_t es = hipStreamSynchronize(st);
+            if (e == hipSuccess) e = es;
+        }
+        if (nomem) return fail(h, CDC_ERR_NOMEM, "%s: hipMalloc failed", what);
+        if (e != hipSuccess) return fail(h, CDC_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+        return CDC_OK;
+    }
+};
+
 }  // namespace cdcapi

@@ -6,8 +6,6 @@ cdc_lpips states the definition; kernels in csrc/lpips_kernels.hip, the network 
 below a prefix, `model(a, b)` returns the distance per image as float64.  The state-dict names are written from that package's source
 as remembered (it is not installed here); the library's manifest is the one place that holds them.  This is the metric, not the
 training loss: there are no gradients."""
-import ctypes
-
 import numpy as np
 
 from . import _lib
@@ -21,56 +19,31 @@ MIN_SIDE = 16
 
 class LpipsVGG:
     def __init__(self, device=None):
-        self.device_index = 0 if device is None else (int(device) if not hasattr(device, "index") else (device.index or 0))
         self.training = False
-        self._h = None
-        self._sd = {}
-        self._finalized = False
+        self._lh = _lib.Handle("cdc_lpips_create", None, _lib.device_index_of(device))
 
-    # ---- handle management: created on first use; the parameters become final (on the GPU) with the first computation
+    # ---- handle management (_lib.Handle): created on first use; the parameters become final (on the GPU) with the first computation
     def _handle(self):
-        if self._h is None:
-            L = _lib.lib()
-            h = ctypes.c_void_p()
-            rc = L.cdc_lpips_create(self.device_index, ctypes.byref(h))
-            if rc != 0:
-                raise _lib.CdcError(f"cdc_lpips_create failed ({rc}): {L.cdc_last_error(None).decode()}")
-            self._h = h
-            for k, v in self._sd.items():
-                self._load_one(k, v)
-        return self._h
+        return self._lh.ptr
+
+    _h = property(lambda self: self._lh.raw)
+    _finalized = property(lambda self: self._lh.finalized)
+    device_index = property(lambda self: self._lh.device_index)
 
     def _ready(self):
         """The handle with final weights (what a computation needs: this is where a host without a GPU fails)."""
         h = self._handle()
         if not self._finalized:
-            if not self._sd:
+            if not self._lh.tensors:
                 raise _lib.CdcError("load_state_dict() has not been called")
-            _lib.check(h, _lib.lib().cdc_finalize_weights(h))
-            self._finalized = True
+            self._lh.finalize()
         return h
 
     def status(self):
-        return _lib.handle_status(self._h)
-
-    def __del__(self):
-        try:
-            if self._h is not None:
-                _lib.lib().cdc_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+        return self._lh.status()
 
     def to(self, device):
-        idx = device if isinstance(device, int) else getattr(device, "index", None)
-        if isinstance(device, str):
-            idx = int(device.split(":")[1]) if ":" in device else 0
-        idx = 0 if idx is None else int(idx)
-        if idx != self.device_index and self._h is not None:
-            _lib.lib().cdc_destroy(self._h)
-            self._h = None
-            self._finalized = False
-        self.device_index = idx
+        self._lh.move(_lib.device_index_of(device))
         return self
 
     def eval(self):
@@ -80,20 +53,7 @@ class LpipsVGG:
     # ---- parameters
     def manifest(self):
         """[(name, shape)] of the required entries, below the prefix."""
-        L, h = _lib.lib(), self._handle()
-        out = []
-        for i in range(L.cdc_num_tensors(h)):
-            name = ctypes.c_char_p()
-            shape = (ctypes.c_int64 * 4)()
-            nd = ctypes.c_int()
-            _lib.check(h, L.cdc_tensor_info(h, i, ctypes.byref(name), shape, ctypes.byref(nd)))
-            out.append((name.value.decode(), tuple(shape[j] for j in range(nd.value))))
-        return out
-
-    def _load_one(self, name, value):
-        a = _as_host_f32(value)
-        shape = (ctypes.c_int64 * max(a.ndim, 1))(*a.shape)
-        _lib.check(self._h, _lib.lib().cdc_load_tensor(self._h, name.encode(), a.ctypes.data, shape, a.ndim))
+        return self._lh.manifest()
 
     def load_state_dict(self, state_dict, prefix=None, strict=True):
         """The entries below `prefix`; None: "loss_fn_vgg." when keys carry it (a whole reference checkpoint), else none.
@@ -115,16 +75,13 @@ class LpipsVGG:
             lin, dup = f"lin{k}.model.1.weight", f"lins.{k}.model.1.weight"
             if dup in sd and lin in sd and not np.array_equal(_as_host_f32(sd[dup]), _as_host_f32(sd[lin])):
                 raise RuntimeError(f"{prefix}{dup} differs from {prefix}{lin}: the two names hold one parameter")
-        self._handle()
         for n in names + list(OPTIONAL):
             if n in sd:
-                self._sd[n] = _as_host_f32(sd[n])
-                self._load_one(n, self._sd[n])
-        self._finalized = False
+                self._lh.load(n, _as_host_f32(sd[n]))
         return self
 
     def state_dict(self):
-        return dict(self._sd)
+        return dict(self._lh.tensors)
 
     # ---- the distance
     def forward(self, a, b, size=None, as_saved=False, return_layers=False):

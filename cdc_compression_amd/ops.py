@@ -17,27 +17,20 @@ def _p(a):
 
 class Ops:
     def __init__(self, device=0):
-        L = _lib.lib()
-        cfg = _lib.UnetConfig()
-        cfg.dim, cfg.channels, cfg.context_channels, cfg.out_dim = 32, 3, 3, 3
-        cfg.n_dim_mults = 1
-        cfg.dim_mults[0] = 1
-        cfg.n_context_dim_mults = 1
-        cfg.context_dim_mults[0] = 1
-        self._h = ctypes.c_void_p()
-        rc = L.cdc_create(ctypes.byref(cfg), device, ctypes.byref(self._h))
-        if rc != 0:
-            raise _lib.CdcError(f"cdc_create failed ({rc}): {L.cdc_last_error(None).decode()}")
-
-    def __del__(self):
-        try:
-            _lib.lib().cdc_destroy(self._h)
-        except Exception:
-            pass
+        def config():
+            cfg = _lib.UnetConfig()
+            cfg.dim, cfg.channels, cfg.context_channels, cfg.out_dim = 32, 3, 3, 3
+            cfg.n_dim_mults = 1
+            cfg.dim_mults[0] = 1
+            cfg.n_context_dim_mults = 1
+            cfg.context_dim_mults[0] = 1
+            return cfg
+        self._lh = _lib.Handle("cdc_create", config, _lib.device_index_of(device))
+        self._h = self._lh.ptr
 
     def status(self):
         """{"arith", "range_faults", "nonfinite_results"} of this handle (range guard of the fp16 arithmetic)."""
-        return _lib.handle_status(self._h)
+        return self._lh.status()
 
     def stress(self, repeats):
         """Every following operator call launches its program `repeats` more times and counts the executions whose result is not

@@ -82,64 +82,44 @@ class Unet:
         self.context_dim_mults = tuple(context_dim_mults)
         self.embd_type = embd_type
         self.training = False
-        self.device_index = int(device) if not hasattr(device, "index") else (device.index or 0)
-        self._h = None
-        self._sd = {}
-        self._finalized = False
-        self._want_final = False     # load_state_dict() completed once: re-finalize after a device change
+        dim_mults, context_dim_mults, out_dim = self.dim_mults, self.context_dim_mults, self.out_dim
 
-    # ---- handle management ----------------------------------------------------------------
-    def _handle(self):
-        if self._h is None:
-            L = _lib.lib()
+        def config():
             cfg = _lib.UnetConfig()
-            cfg.dim, cfg.channels, cfg.context_channels = self.dim, self.channels, self.context_channels
-            cfg.out_dim = self.out_dim
-            cfg.n_dim_mults = len(self.dim_mults)
-            cfg.n_context_dim_mults = len(self.context_dim_mults)
-            for i, m in enumerate(self.dim_mults):
+            cfg.dim, cfg.channels, cfg.context_channels, cfg.out_dim = dim, channels, context_channels, out_dim
+            cfg.n_dim_mults, cfg.n_context_dim_mults = len(dim_mults), len(context_dim_mults)
+            for i, m in enumerate(dim_mults):
                 cfg.dim_mults[i] = m
-            for i, m in enumerate(self.context_dim_mults):
+            for i, m in enumerate(context_dim_mults):
                 cfg.context_dim_mults[i] = m
-            h = ctypes.c_void_p()
-            rc = L.cdc_create(ctypes.byref(cfg), self.device_index, ctypes.byref(h))
-            if rc != 0:
-                raise _lib.CdcError(f"cdc_create failed ({rc}): {L.cdc_last_error(None).decode()}")
-            self._h = h
-            for k, v in self._sd.items():
-                self._load_one(k, v)
-            if self._sd and self._want_final:
-                # a handle re-created after .to(other device): the replayed parameters are final again
-                _lib.check(h, L.cdc_finalize_weights(h))
-                self._finalized = True
-        return self._h
+            return cfg
+        self._lh = _lib.Handle("cdc_create", config, _lib.device_index_of(device))
+
+    # ---- handle management (_lib.Handle) --------------------------------------------------
+    def _handle(self):
+        return self._lh.ptr
+
+    _h = property(lambda self: self._lh.raw)
+
+    @_h.setter
+    def _h(self, h):
+        """For a caller that has destroyed the handle itself (cdc_destroy(un._h); un._h = None): it must not be destroyed twice."""
+        self._lh.raw = h
+
+    _finalized = property(lambda self: self._lh.finalized)
+    device_index = property(lambda self: self._lh.device_index)
 
     def status(self):
         """Arithmetic mode and range-guard counters of the library handle (see _lib.handle_status)."""
-        return _lib.handle_status(self._h)
+        return self._lh.status()
 
     @property
     def range_faults(self):
         return self.status()["range_faults"]
 
-    def __del__(self):
-        try:
-            if self._h is not None:
-                _lib.lib().cdc_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
     def to(self, device):
-        idx = device if isinstance(device, int) else getattr(device, "index", None)
-        if isinstance(device, str):
-            idx = int(device.split(":")[1]) if ":" in device else 0
-        idx = 0 if idx is None else int(idx)
-        if idx != self.device_index and self._h is not None:
-            _lib.lib().cdc_destroy(self._h)
-            self._h = None
-            self._finalized = False
-        self.device_index = idx
+        """Another device: the handle goes now; the next use creates it there, with the parameters loaded and final as they were."""
+        self._lh.move(_lib.device_index_of(device))
         return self
 
     def eval(self):
@@ -149,24 +129,9 @@ class Unet:
     # ---- parameters -----------------------------------------------------------------------
     def manifest(self):
         """[(name, shape)] in the order of the reference Unet.state_dict()."""
-        L, h = _lib.lib(), self._handle()
-        out = []
-        for i in range(L.cdc_num_tensors(h)):
-            name = ctypes.c_char_p()
-            shape = (ctypes.c_int64 * 4)()
-            nd = ctypes.c_int()
-            _lib.check(h, L.cdc_tensor_info(h, i, ctypes.byref(name), shape, ctypes.byref(nd)))
-            out.append((name.value.decode(), tuple(shape[j] for j in range(nd.value))))
-        return out
-
-    def _load_one(self, name, value):
-        L, h = _lib.lib(), self._h
-        a = _as_host_f32(value)
-        shape = (ctypes.c_int64 * max(a.ndim, 1))(*a.shape)
-        _lib.check(h, L.cdc_load_tensor(h, name.encode(), a.ctypes.data, shape, a.ndim))
+        return self._lh.manifest()
 
     def load_state_dict(self, state_dict, strict=True):
-        h = self._handle()
         names = [n for n, _ in self.manifest()]
         missing = [n for n in names if n not in state_dict]
         unexpected = [k for k in state_dict if k not in names]
@@ -175,15 +140,12 @@ class Unet:
                                f"{'...' if len(missing) > 3 else ''}, unexpected {unexpected[:3]}")
         for n in names:
             if n in state_dict:
-                self._sd[n] = _as_host_f32(state_dict[n])
-                self._load_one(n, self._sd[n])
-        _lib.check(h, _lib.lib().cdc_finalize_weights(h))
-        self._finalized = True
-        self._want_final = True
+                self._lh.load(n, _as_host_f32(state_dict[n]))
+        self._lh.finalize()
         return self
 
     def state_dict(self):
-        return dict(self._sd)
+        return dict(self._lh.tensors)
 
     # ---- forward --------------------------------------------------------------------------
     def forward(self, x, time=None, context=None):

@@ -116,6 +116,28 @@ def test_frame_kernels_match_torch_bit_for_bit(W, where):
     del keep
 
 
+@pytest.mark.parametrize("H,W", [(37, 50), (40, 48)])      # W % 4 != 0: the element path; W % 4 == 0: the 16-byte path
+def test_frame_entry_points_give_the_same_bits_from_host_and_device_memory(H, W):
+    """The host-staging path of cdc_frame_pad / cdc_frame_crop (operands copied through call scratch) against device operands."""
+    torch = pytest.importorskip("torch")
+    keep, h = _handle()
+    rng = np.random.default_rng(H * 100 + W)
+    f32 = (rng.standard_normal((2, 3, H, W)) * 0.8).astype(np.float32)
+    u8 = rng.integers(0, 256, (2, 3, H, W), dtype=np.uint8)
+    fr = (rng.standard_normal((2, 3, 64, 64)) * 0.8).astype(np.float32)
+    dev = lambda a: torch.from_numpy(a).cuda()      # noqa: E731
+    for img in (f32, u8):
+        for zero in (False, True):
+            host = frame.pad(h, img, 64, 64, 0, zero=zero)
+            assert host.shape == (2, 3, 64, 64) and np.array_equal(_bits(host), _bits(frame.pad(h, dev(img), 64, 64, 0, zero=zero).cpu().numpy()))
+        assert np.array_equal(_bits(host[:, :, :H, :W]), _bits(f32 if img is f32 else (img.astype(np.float32) / 255.0 * 2.0 - 1.0).astype(np.float32)))
+    host = frame.crop(h, fr, H, W, 0)
+    assert np.array_equal(_bits(host), _bits(fr[:, :, :H, :W])) and np.array_equal(_bits(host), _bits(frame.crop(h, dev(fr), H, W, 0).cpu().numpy()))
+    host = frame.crop(h, fr, H, W, 0, as_uint8=True)
+    assert host.dtype == np.uint8 and np.array_equal(host, frame.crop(h, dev(fr), H, W, 0, as_uint8=True).cpu().numpy())
+    del keep
+
+
 def test_frame_entry_points_refuse_bad_sizes():
     keep, h = _handle()
     L = _lib.lib()

@@ -82,6 +82,18 @@ def test_psnr_of_bytes_is_exact(H, W, where):
     assert np.all(np.isposinf(metrics.psnr(m, to(f), to(R.saved_u8(f)), as_saved=True)))
 
 
+def test_psnr_gives_the_same_bits_from_host_and_device_memory():
+    """The host-staging path of cdc_distortion against device operands: 37 x 50 windows of 64 x 64 frames, every operand kind."""
+    m, dev = _model(), _to("device")
+    a, b, f, _, _ = _byte_case(37, 50)
+    g = np.random.default_rng(5).uniform(-1.3, 1.3, f.shape).astype(np.float32)
+    for x, y, saved in ((a, b, False), (f, b, True), (f, g, False), (a, g, (False, True))):
+        fx, fy = _in_frame(x, 255 if x.dtype == np.uint8 else 1e30), _in_frame(y, 7 if y.dtype == np.uint8 else -1e30)
+        host = metrics.psnr(m, fx, fy, size=(37, 50), as_saved=saved)
+        assert np.all(np.isfinite(host)) and np.array_equal(_bits(host), _bits(metrics.psnr(m, dev(fx), dev(fy), size=(37, 50), as_saved=saved)))
+        assert np.array_equal(_bits(host), _bits(metrics.psnr(m, x, y, as_saved=saved)))
+
+
 # ---- 2. PSNR with a float operand -----------------------------------------------------------------------------------------------------
 
 @functools.lru_cache(maxsize=None)

@@ -778,6 +778,31 @@ def test_rate_estimate_matches_reference_bpp(name):
     assert np.abs(b - g["bpp"]).max() <= 1e-4 * max(1.0, float(np.abs(g["bpp"]).max())), (b, g["bpp"])
 
 
+def test_dequantize_and_rate_give_the_same_bits_from_host_and_device_memory():
+    """The host-staging path of cdc_dequantize and cdc_bpp (operands copied through call scratch) against device operands: 1027 elements
+    (no multiple of 4) and the hyperdec_small_x model on a 1 x 1 hyper latent."""
+    import torch
+    meta = json.load(open(os.path.join(GOLDEN, "manifest_hyperdec_small_x.json")))
+    man = [(k, tuple(v)) for k, v in meta["manifest"]]
+    pman = [(k, tuple(v)) for k, v in meta["prior_manifest"]]
+    m = getattr(cdc, meta["class"])(**meta["kwargs"])
+    m.load_hyper_state_dict({**synth.unet_state_dict(man, seed=7), **synth.unet_state_dict(pman, seed=11)})
+    dev = lambda a: torch.from_numpy(a).cuda()      # noqa: E731
+    x = synth.normal("deq_x", (1, 1027, 1, 1), seed=3, std=4.0)
+    off = synth.normal("deq_off", (1, 1027, 1, 1), seed=4, std=1.0)
+    host = m.dequantize(x, off)
+    assert host.shape == x.shape and np.isfinite(host).all() and np.abs((host - off) - np.round(host - off)).max() < 1e-5
+    np.testing.assert_array_equal(host, m.dequantize(dev(x), dev(off)).cpu().numpy())
+    B, Ch, Cl = 2, m.reversed_hyper_dims[0], m.reversed_hyper_dims[-1] // 2
+    qh = np.round(synth.normal("bpp_qh", (B, Ch, 1, 1), seed=5, std=2.0))
+    mean = synth.normal("bpp_mean", (B, Cl, 4, 4), seed=6, std=2.0)
+    scale = np.abs(synth.normal("bpp_scale", (B, Cl, 4, 4), seed=7, std=1.0)) + np.float32(0.1)
+    ql = m.dequantize(synth.normal("bpp_lat", (B, Cl, 4, 4), seed=8, std=3.0), mean)
+    host = m.rate(qh, ql, mean, scale, (64, 64))
+    assert host.shape == (B,) and np.all(np.isfinite(host)) and np.all(host > 0)
+    np.testing.assert_array_equal(host, m.rate(dev(qh), dev(ql), dev(mean), dev(scale), (64, 64)).cpu().numpy())
+
+
 # ---- encoder (SURVEY section 8f row 3) and the whole compressor forward ---------------------------------
 
 def _symbols_close(a, ref, max_flip_frac=1e-4):
@@ -1429,14 +1454,19 @@ def test_range_guard_in_the_compressor_entry_points():
 
 def test_model_follows_device_change_after_load():
     """load_state_dict() followed by .to(device) must leave a usable model (both reference test
-    scripts use that order): the handle is re-created, the parameters replayed AND finalized again."""
+    scripts use that order): the handle is re-created, the parameters replayed AND finalized again.  .to(1) then .to(0) with nothing
+    run in between: device 1 is never touched, and the handle of device 0 is a new one."""
     un, kw, sd, x, time, ctx, g = make_unet("small_x")
     y0 = un(x, time, ctx)
+    first = un._h.value
     un.to(0)                          # same device: nothing happens
-    un._h and _lib.lib().cdc_destroy(un._h)
-    un._h, un._finalized = None, False          # what .to(other device) does
-    y1 = un(x, time, ctx) if (un._handle() and un._finalized) else None
-    assert y1 is not None
+    assert un._h.value == first
+    un.to(1)
+    assert un._h is None and un.device_index == 1
+    un.to(0)
+    assert un._h is None and un._finalized and set(un.state_dict()) == set(sd)
+    y1 = un(x, time, ctx)
+    assert un._h is not None
     np.testing.assert_array_equal(y0, y1)
     meta = json.load(open(os.path.join(GOLDEN, "manifest_encoder_small_x.json")))
     comp = cdc.ResnetCompressor(**meta["kwargs"])
@@ -1444,11 +1474,28 @@ def test_model_follows_device_change_after_load():
     comp.load_state_dict(csd)
     img = synth.normal("img", (1, 3, 64, 64), seed=9, std=0.5)
     a = comp(img)
-    comp.device_index = -1            # force the "device changed" branch of .to()
-    comp.to(0)
+    live = {"arith": 1, "range_faults": 0, "nonfinite_results": 0}
+    assert comp.status() == {"dec": live, "hyper_dec": live, "enc": live}
+    comp.to(1).to(0)
+    assert (comp._h, comp._hh, comp._eh) == (None, None, None) and comp.status()["dec"]["arith"] is None
     b = comp(img)
     np.testing.assert_array_equal(a["q_latent"], b["q_latent"])
+    np.testing.assert_array_equal(a["q_hyper_latent"], b["q_hyper_latent"])
     np.testing.assert_array_equal(a["bpp"], b["bpp"])
+    assert len(a["output"]) == len(b["output"]) == 4
+    for oa, ob in zip(a["output"], b["output"]):
+        np.testing.assert_array_equal(oa, ob)
+    assert comp.status() == {"dec": live, "hyper_dec": live, "enc": live}       # three live handles again
+    assert set(comp.state_dict()) == {k for k in csd if k.startswith("dec.")}
+    from cdc_compression_amd import metrics
+    lp = cdc.LpipsVGG().load_state_dict(synth.lpips_vgg_state_dict(seed=3))
+    pa, pb = synth.normal("lp_a", (1, 3, 16, 16), seed=1, std=0.5), synth.normal("lp_b", (1, 3, 16, 16), seed=2, std=0.5)
+    d0 = metrics.lpips(lp, pa, pb)
+    assert lp._finalized and np.isfinite(d0).all() and d0[0] > 0
+    lp.to(1).to(0)
+    assert lp._h is None
+    d1 = metrics.lpips(lp, pa, pb)
+    assert lp._h is not None and np.array_equal(d0.view(np.int64), d1.view(np.int64))
 
 
 def test_bench_under_torchrun_one_rank_nccl(tmp_path):
