@@ -25,6 +25,8 @@ namespace cdc {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
+constexpr float kPScale = 8192.0f;       // 2^13: the softmax weight of the fp16 paths is carried as p 2^13 (see kvctx_kernel)
+
 // exact three-way bf16 split of an fp32 value (truncation; see conv_split_kernel.h)
 __device__ __forceinline__ void split3(float a, unsigned &h, unsigned &m, unsigned &l) {
     h = __float_as_uint(a) & 0xFFFF0000u;
@@ -35,9 +37,21 @@ __device__ __forceinline__ void split3(float a, unsigned &h, unsigned &m, unsign
 
 // F16 = true (CDC_ARITH_F16X2): both contractions on the fp16 matrix cores with two-plane operands (three products):
 //   projection:  W' 2^s as {WH, WL, WH2} (static planes), x - mean as (h, l') -- as in conv_split_kernel.h AR = 1;
-//   sum_n p v:   p = exp(k - max) in (0, 1] as {PH, PL = fp16(p - PH), PH2 = PH 2^-11} (absolute error <= 3e-8, i.e. fp32
-//                resolution of the largest weight p = 1), v as (h, l'); K = 16 pixels per instruction: 6 fp16 MFMAs per
+//   sum_n p v:   p = exp(k - max) in (0, 1] is carried as p' = p 2^13 (kPScale; exact) in (0, 8192], split as
+//                {PH, PL = fp16(p' - PH), PH2 = PH 2^-11}; v as (h, l'); K = 16 pixels per instruction: 6 fp16 MFMAs per
 //                32-pixel tile and S block instead of 16 v_mfma_f32_32x32x2_f32 (32 vs 64 cycles each).
+//                Error of a carried weight: RELATIVE <= 2^-21 p for p >= 2^-16 (PH + PL hold 22 bits while PL is a normal
+//                fp16), absolute <= 3.6e-12 below that; PH itself stays normal down to p = 2^-27 = 7.5e-9.  Unscaled, PH is
+//                an fp16 subnormal below p = 6.1e-5 (the matrix cores keep those) and PL rounds to nothing: an absolute error
+//                of 3e-8, 0.5 % of a weight of 6e-6, while Z is summed from the fp32 p.  Where thousands of pixels share one
+//                such weight and nearly one v (one feature on a flat background) the errors add up.  `max` is the RUNNING
+//                maximum of this workgroup's split: N / nsplit pixels, 32 at one image of 32 x 64 and 2048 at the 256 x 256
+//                level of a batch of 32 (nsplit = min(128, 1024 / B), cdc_planner.hip), and every pixel after the feature is
+//                weighed against it.  Measured on an MI355X (profiles/attention_edges.md): splits of 32 - 128 pixels are too
+//                short to show it either way; at 512 pixels per split with the feature first in its split see that file.
+//                Z carries the same 2^13 (it is summed from the fp32 p'), so the factor cancels in ctx_r0_kernel's S / Z;
+//                M stays the true row maximum and the splits of a row share the factor.
+//                Range: Z <= 2^13 N <= 2^29 at N = 65536, |S| <= Z max |v|: far inside fp32.
 template <int CB, int NW, bool F16 = false>      // C = 32 * CB channels, NW waves per workgroup
 __global__ void __launch_bounds__(64 * NW, CB == 2 ? 3 : 1) kvctx_kernel(const KvCtxArgs a) {
     constexpr int C = 32 * CB, NBLK = 2 * CB;        // kv row blocks of 32 channels
@@ -219,7 +233,7 @@ __global__ void __launch_bounds__(64 * NW, CB == 2 ? 3 : 1) kvctx_kernel(const K
         }
         float pv[16];
 #pragma unroll
-        for (int s = 0; s < 16; ++s) { pv[s] = expf(kk[s] - m_run); zsum += pv[s]; }
+        for (int s = 0; s < 16; ++s) { pv[s] = expf(kk[s] - m_run) * (F16 ? kPScale : 1.0f); zsum += pv[s]; }
         if constexpr (F16) {
             f16x8 ph[2], pl[2], ph2[2];
 #pragma unroll
@@ -444,13 +458,13 @@ __global__ void __launch_bounds__(64 * NW, CB == 2 ? (VP ? 2 : 3) : 1) kvctx16_k
                 }
             }
         }
-        // p in (0, 1] as {PH, PL = fp16(p - PH), PH2 = PH 2^-11} (absolute error <= 3e-8)
+        // p' = p 2^13 in (0, 8192] as {PH, PL = fp16(p' - PH), PH2 = PH 2^-11} (relative error <= 2^-21 down to p = 2^-16: kvctx_kernel)
         f16x8 ph[2], pl[2], ph2[2];
 #pragma unroll
         for (int st = 0; st < 2; ++st)
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                const float p = __builtin_amdgcn_exp2f(kk[8 * st + i] - m_run);
+                const float p = __builtin_amdgcn_exp2f(kk[8 * st + i] - m_run) * kPScale;
                 zsum += p;
                 const _Float16 h = (_Float16)p;
                 ph[st][i] = h;

@@ -591,7 +591,12 @@ __global__ void __launch_bounds__(256) ctx_partial_kernel(const float *k, const 
         const int nb = wave * 16;
         if constexpr (F16) {
             // one K = 16 step per wave and chunk: lane (row jj, half) holds pixels nb + 8 half .. + 7 of its row -- two
-            // swizzled 4-pixel groups.  p = exp(k - max) in (0, 1] as {PH, PL, PH2 = PH 2^-11}, v as (h, l'): three products.
+            // swizzled 4-pixel groups.  p' = exp(k - max) 2^13 in (0, 8192] as {PH, PL = fp16(p' - PH), PH2 = PH 2^-11}, v as (h, l'):
+            // three products.  The factor keeps the planes of a small weight normal fp16 numbers (attn_kernels.hip, kvctx_kernel); `max`
+            // is the maximum of the whole row here, so a row with one feature on a flat background has all its other pixels at one small
+            // weight (measured: profiles/attention_edges.md).  S and the row sums of this loop both carry the factor (a power of two:
+            // exact) and every reader divides one by the other (ctx_r0_kernel, ctx_reduce_kernel, the ONE epilogue).
+            // Range: sums <= 2^13 N max |v|, far inside fp32 at any pixel count.
             typedef _Float16 h8 __attribute__((ext_vector_type(8)));
             const int g0 = (nb + 8 * half) >> 2;
             const int o0 = 4 * (g0 ^ (jj & 15)), o1 = 4 * ((g0 + 1) ^ (jj & 15));
@@ -605,7 +610,7 @@ __global__ void __launch_bounds__(256) ctx_partial_kernel(const float *k, const 
                 for (int t = 0; t < 8; ++t) {
                     const bool pv = n0 + nb + 8 * half + t < n_end;
                     // v_exp_f32 (exp2(x log2 e)), as kvctx16_kernel: <= 2 ulp on a weight in (0, 1]
-                    const float pp = pv ? __builtin_amdgcn_exp2f((kk[t] - mrow[i]) * 1.44269504088896341f) : 0.f;
+                    const float pp = pv ? __builtin_amdgcn_exp2f((kk[t] - mrow[i]) * 1.44269504088896341f) * 8192.0f : 0.f;
                     zrow[i] += pp;
                     const _Float16 hq = (_Float16)pp;
                     ph[i][t] = hq;

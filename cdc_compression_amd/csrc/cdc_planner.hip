@@ -971,7 +971,8 @@ struct Builder {
         }
         float *kmaxs = fused ? dalloc((size_t)B * nsplit * C) : nullptr;   // per-split row maxima
         float *S = dalloc((size_t)B * nsplit * C * C);
-        float *ksum = dalloc((size_t)B * nsplit * C);      // per-split partial sums of exp(k - max)
+        float *ksum = dalloc((size_t)B * nsplit * C);      // per-split partial sums of exp(k - max); x 2^13, as S, from the fp16 kernels (kvctx16_kernel,
+                                                           // kvctx_kernel<F16>, ctx_partial_kernel<F16>), plain from the f32 and generic ones: only S / Z means anything
         const int Cin_pad = round_up(C, 16), COP = round_up(C, 32);
         float *ctxw = dalloc((size_t)B * Cin_pad * COP);
         float *T1 = fold ? dalloc((size_t)B * C * C) : nullptr;
@@ -1011,6 +1012,7 @@ struct Builder {
         unsigned short *Ws = (stream_out || split_out || split_ctxq) ? reinterpret_cast<unsigned short *>(dalloc((size_t)B * C * C * 3 / 2 + 8)) : nullptr;
         // (debugging taps of the level's intermediates: the staged projection, the partial context sums, the per-image matrix)
         if (!fused) h->taps[at.prefix + ".kv"] = qkv;
+        // (.S and .Z carry a common factor 2^13 where an fp16 kernel wrote them, see ksum above)
         { Act ts; ts.p = S; ts.C = nsplit; ts.H = C; ts.W = C; h->taps[at.prefix + ".S"] = ts; }
         { Act ts; ts.p = ksum; ts.C = nsplit; ts.H = 1; ts.W = C; h->taps[at.prefix + ".Z"] = ts; }
         { Act ts; ts.p = kmax; ts.C = 1; ts.H = 1; ts.W = C; h->taps[at.prefix + ".kmax"] = ts; }
@@ -1692,6 +1694,7 @@ static int op_linear_attention_impl(cdc_handle *h, const float *x, const float *
     at.C = C;
     if ((rc = pack_qkv_folded(h, w_qkv, norm_g, norm_b, C, 0, 3 * C, &at.qkv, &sc.pool))) return rc;
     if ((rc = pack_qkv_folded(h, w_qkv, norm_g, norm_b, C, C, 2 * C, &at.kv, &sc.pool))) return rc;
+    if ((rc = pack_kvctx(h, w_qkv, norm_g, norm_b, C, &at, &sc.pool))) return rc;     // the fused front half, as the model's levels have it
     if ((rc = pack_conv(h, w_out, b_out, C, C, 1, 1, 1, 0, false, &at.out, &sc.pool))) return rc;
     if ((rc = sc.up(norm_g, C, &at.ng))) return rc;
     if ((rc = sc.up(norm_b, C, &at.nb))) return rc;

@@ -275,6 +275,7 @@ int pack_conv(cdc_handle *h, const float *w, const float *bias, int CoutF, int C
 int pack_named_conv(cdc_handle *h, const std::string &wname, const std::string &bname, int stride, int pad, bool transposed, ConvW *cw,
                     int ci0 = 0, int ncin = 0, int co0 = 0, int ncout = 0);
 int pack_qkv_folded(cdc_handle *h, const float *wq, const float *g, const float *bln, int C, int co0, int nco, ConvW *cw, std::vector<void *> *pool);
+int pack_kvctx(cdc_handle *h, const float *wq, const float *g, const float *bn, int c, AttnW *a, std::vector<void *> *pool);
 void free_pool(std::vector<void *> *pool);
 // ---- cdc_planner.hip
 void free_program(cdc_handle *h);

@@ -429,6 +429,69 @@ int pack_qkv_folded(cdc_handle *h, const float *wq, const float *g, const float 
     return pack_conv(h, w.data(), bias.data(), nco, C, 1, 1, 1, 0, false, cw, pool);
 }
 
+// Operands of the fused kv-projection + context kernels (attn_kernels.hip) from the raw to_qkv weight [3c][c] and the PreNorm affine:
+// AttnW::kvWt / kvb / kvWs / kvWh / kv_scale_inv.  Shared by the model's weights (pack_attn) and the single-operator entry point
+// (cdc_op_linear_attention), so that both plan the same kernels.
+int pack_kvctx(cdc_handle *h, const float *wq, const float *g, const float *bn, int c, AttnW *a, std::vector<void *> *pool) {
+    int rc;
+    // W' = W_kv diag(g) transposed, bias' = W_kv b_ln
+    std::vector<float> wt((size_t)c * 2 * c), kb(2 * c);
+    for (int co = 0; co < 2 * c; ++co) {
+        double acc = 0;
+        for (int ci = 0; ci < c; ++ci) {
+            const float v = wq[(size_t)(c + co) * c + ci];          // k rows then v rows of to_qkv
+            wt[(size_t)ci * 2 * c + co] = v * g[ci];
+            acc += (double)v * bn[ci];
+        }
+        kb[co] = (float)acc;
+    }
+    if ((rc = upload(h, wt.data(), wt.size(), &a->kvWt, pool))) return rc;
+    if (c % 16 == 0) {      // three bf16 planes of W' in A-operand order (kvctx_kernel, C = 64)
+        std::vector<unsigned short> sp((size_t)(c / 16) * 3 * 2 * 2 * c * 8);
+        for (int co = 0; co < 2 * c; ++co)
+            for (int ci = 0; ci < c; ++ci) {
+                const float v = wt[(size_t)ci * 2 * c + co];
+                uint32_t u; memcpy(&u, &v, 4);
+                const uint32_t h1 = u & 0xFFFF0000u; float f1; memcpy(&f1, &h1, 4);
+                const float r = v - f1; uint32_t ur; memcpy(&ur, &r, 4);
+                const uint32_t h2 = ur & 0xFFFF0000u; float f2; memcpy(&f2, &h2, 4);
+                const float r2 = r - f2; uint32_t h3; memcpy(&h3, &r2, 4);
+                const uint32_t parts[3] = {h1, h2, h3};
+                const int q = ci >> 4, kh = (ci >> 3) & 1, i = ci & 7;
+                for (int pl = 0; pl < 3; ++pl)
+                    sp[((size_t)((q * 3 + pl) * 2 + kh) * 2 * c + co) * 8 + i] = (unsigned short)(parts[pl] >> 16);
+            }
+        float *dsp = nullptr;
+        if ((rc = upload(h, reinterpret_cast<const float *>(sp.data()), (sp.size() + 1) / 2, &dsp, pool)))
+            return rc;
+        a->kvWs = reinterpret_cast<unsigned short *>(dsp);
+        // the same in two-plane fp16 arithmetic: {WH, WL, WH2 = WH 2^-11} of W' 2^s (see conv_split_kernel.h AR = 1)
+        float wmax = 0.f;
+        for (float v : wt) wmax = std::max(wmax, fabsf(v));
+        int sexp = 0;
+        if (wmax > 0.f && std::isfinite(wmax)) { int e; frexpf(wmax, &e); sexp = 14 - e; }
+        sexp = std::max(-100, std::min(100, sexp));
+        const float scl = ldexpf(1.f, sexp);
+        auto f16bits = [](float f) { const _Float16 hf = (_Float16)f; unsigned short u; memcpy(&u, &hf, 2); return u; };
+        std::vector<unsigned short> sh(sp.size(), 0);
+        for (int co = 0; co < 2 * c; ++co)
+            for (int ci = 0; ci < c; ++ci) {
+                const float v = wt[(size_t)ci * 2 * c + co] * scl;
+                const _Float16 wh = (_Float16)v;
+                const unsigned short parts[3] = {f16bits((float)wh), f16bits(v - (float)wh), f16bits((float)wh * (1.0f / 2048.0f))};
+                const int q = ci >> 4, kh = (ci >> 3) & 1, i = ci & 7;
+                for (int pl = 0; pl < 3; ++pl) sh[((size_t)((q * 3 + pl) * 2 + kh) * 2 * c + co) * 8 + i] = parts[pl];
+            }
+        float *dsh = nullptr;
+        if ((rc = upload(h, reinterpret_cast<const float *>(sh.data()), (sh.size() + 1) / 2, &dsh, pool)))
+            return rc;
+        a->kvWh = reinterpret_cast<unsigned short *>(dsh);
+        a->kv_scale_inv = ldexpf(1.f, -sexp);
+    }
+    if ((rc = upload(h, kb.data(), kb.size(), &a->kvb, pool))) return rc;
+    return CDC_OK;
+}
+
 int pack_attn(cdc_handle *h, const std::string &p, int c) {
     AttnW a;
     a.prefix = p; a.C = c;
@@ -467,62 +530,7 @@ int pack_attn(cdc_handle *h, const std::string &p, int c) {
             uq[d] = (float)acc;
         }
         if ((rc = upload(h, uq.data(), uq.size(), &a.uq, &h->weight_allocs))) return rc;
-        // fused kv-projection + context kernel (attn_kernels.hip): W' = W_kv diag(g) transposed, bias' = W_kv b_ln
-        const auto &g = hostp(h, p + ".fn.norm.g");
-        std::vector<float> wt((size_t)c * 2 * c), kb(2 * c);
-        for (int co = 0; co < 2 * c; ++co) {
-            double acc = 0;
-            for (int ci = 0; ci < c; ++ci) {
-                const float v = wq[(size_t)(c + co) * c + ci];          // k rows then v rows of to_qkv
-                wt[(size_t)ci * 2 * c + co] = v * g[ci];
-                acc += (double)v * bn[ci];
-            }
-            kb[co] = (float)acc;
-        }
-        if ((rc = upload(h, wt.data(), wt.size(), &a.kvWt, &h->weight_allocs))) return rc;
-        if (c % 16 == 0) {      // three bf16 planes of W' in A-operand order (kvctx_kernel, C = 64)
-            std::vector<unsigned short> sp((size_t)(c / 16) * 3 * 2 * 2 * c * 8);
-            for (int co = 0; co < 2 * c; ++co)
-                for (int ci = 0; ci < c; ++ci) {
-                    const float v = wt[(size_t)ci * 2 * c + co];
-                    uint32_t u; memcpy(&u, &v, 4);
-                    const uint32_t h1 = u & 0xFFFF0000u; float f1; memcpy(&f1, &h1, 4);
-                    const float r = v - f1; uint32_t ur; memcpy(&ur, &r, 4);
-                    const uint32_t h2 = ur & 0xFFFF0000u; float f2; memcpy(&f2, &h2, 4);
-                    const float r2 = r - f2; uint32_t h3; memcpy(&h3, &r2, 4);
-                    const uint32_t parts[3] = {h1, h2, h3};
-                    const int q = ci >> 4, kh = (ci >> 3) & 1, i = ci & 7;
-                    for (int pl = 0; pl < 3; ++pl)
-                        sp[((size_t)((q * 3 + pl) * 2 + kh) * 2 * c + co) * 8 + i] = (unsigned short)(parts[pl] >> 16);
-                }
-            float *dsp = nullptr;
-            if ((rc = upload(h, reinterpret_cast<const float *>(sp.data()), (sp.size() + 1) / 2, &dsp, &h->weight_allocs)))
-                return rc;
-            a.kvWs = reinterpret_cast<unsigned short *>(dsp);
-            // the same in two-plane fp16 arithmetic: {WH, WL, WH2 = WH 2^-11} of W' 2^s (see conv_split_kernel.h AR = 1)
-            float wmax = 0.f;
-            for (float v : wt) wmax = std::max(wmax, fabsf(v));
-            int sexp = 0;
-            if (wmax > 0.f && std::isfinite(wmax)) { int e; frexpf(wmax, &e); sexp = 14 - e; }
-            sexp = std::max(-100, std::min(100, sexp));
-            const float scl = ldexpf(1.f, sexp);
-            auto f16bits = [](float f) { const _Float16 hf = (_Float16)f; unsigned short u; memcpy(&u, &hf, 2); return u; };
-            std::vector<unsigned short> sh(sp.size(), 0);
-            for (int co = 0; co < 2 * c; ++co)
-                for (int ci = 0; ci < c; ++ci) {
-                    const float v = wt[(size_t)ci * 2 * c + co] * scl;
-                    const _Float16 wh = (_Float16)v;
-                    const unsigned short parts[3] = {f16bits((float)wh), f16bits(v - (float)wh), f16bits((float)wh * (1.0f / 2048.0f))};
-                    const int q = ci >> 4, kh = (ci >> 3) & 1, i = ci & 7;
-                    for (int pl = 0; pl < 3; ++pl) sh[((size_t)((q * 3 + pl) * 2 + kh) * 2 * c + co) * 8 + i] = parts[pl];
-                }
-            float *dsh = nullptr;
-            if ((rc = upload(h, reinterpret_cast<const float *>(sh.data()), (sh.size() + 1) / 2, &dsh, &h->weight_allocs)))
-                return rc;
-            a.kvWh = reinterpret_cast<unsigned short *>(dsh);
-            a.kv_scale_inv = ldexpf(1.f, -sexp);
-        }
-        if ((rc = upload(h, kb.data(), kb.size(), &a.kvb, &h->weight_allocs))) return rc;
+        if ((rc = pack_kvctx(h, wq.data(), hostp(h, p + ".fn.norm.g").data(), bn.data(), c, &a, &h->weight_allocs))) return rc;
     }
     h->attns.push_back(a);
     return CDC_OK;

@@ -15,6 +15,7 @@ from cdc_compression_amd import _lib, synth
 from cdc_compression_amd.ops import Ops
 from oracle import model as om
 from oracle import ops as oops
+import attention_ref
 from helpers import GOLDEN, digest_idx, load_case, oracle_cfg
 
 pytestmark = pytest.mark.gpu
@@ -389,16 +390,17 @@ def test_layernorm_on_16_byte_accesses(O, shape, env, monkeypatch):
     assert relerr(Ops(0).chan_layernorm(x, g, b), O.chan_layernorm(x, g, b)) < 1e-6
 
 
+def _attention_inputs(B, C, H, W):
+    """(x, state dict of "a" = Residual(PreNorm(LinearAttention))): the `normal` case of tests/attention_ref.py at the seed of these tests."""
+    x, g, b, wq, wo, bo = attention_ref.case_normal(24, (B, C, H, W))
+    return x, {"a.fn.norm.g": g, "a.fn.norm.b": b, "a.fn.fn.to_qkv.weight": wq, "a.fn.fn.to_out.weight": wo, "a.fn.fn.to_out.bias": bo}
+
+
 @pytest.mark.parametrize("case", [(2, 16, 8, 8), (1, 64, 32, 32), (2, 64, 64, 64), (1, 128, 64, 64), (2, 128, 16, 16), (1, 384, 8, 8),
                                   (1, 24, 12, 20), (1, 64, 64, 64)])
 def test_linear_attention_matches_oracle(O, G, case):
     B, C, H, W = case
-    x = synth.normal("ax", (B, C, H, W), 24)
-    sd = {"a.fn.norm.g": synth.normal("ag", (1, C, 1, 1), 24, 0.2, 1.0),
-          "a.fn.norm.b": synth.normal("ab", (1, C, 1, 1), 24, 0.2),
-          "a.fn.fn.to_qkv.weight": synth.normal("aq", (3 * C, C, 1, 1), 24, 2.0 / np.sqrt(C)),
-          "a.fn.fn.to_out.weight": synth.normal("ao", (C, C, 1, 1), 24, 1.0 / np.sqrt(C)),
-          "a.fn.fn.to_out.bias": synth.normal("aob", (C,), 24, 0.1)}
+    x, sd = _attention_inputs(B, C, H, W)
     ref = om.attention(O, sd, "a", x)
     got = G.linear_attention(x, sd["a.fn.norm.g"], sd["a.fn.norm.b"], sd["a.fn.fn.to_qkv.weight"],
                              sd["a.fn.fn.to_out.weight"], sd["a.fn.fn.to_out.bias"])
@@ -419,12 +421,7 @@ def test_linear_attention_alternate_kernels(O, case, env, monkeypatch):
     from cdc_compression_amd.ops import Ops
     G2 = Ops(0)                               # (the arithmetic is read when the handle is created)
     B, C, H, W = case
-    x = synth.normal("ax", (B, C, H, W), 24)
-    sd = {"a.fn.norm.g": synth.normal("ag", (1, C, 1, 1), 24, 0.2, 1.0),
-          "a.fn.norm.b": synth.normal("ab", (1, C, 1, 1), 24, 0.2),
-          "a.fn.fn.to_qkv.weight": synth.normal("aq", (3 * C, C, 1, 1), 24, 2.0 / np.sqrt(C)),
-          "a.fn.fn.to_out.weight": synth.normal("ao", (C, C, 1, 1), 24, 1.0 / np.sqrt(C)),
-          "a.fn.fn.to_out.bias": synth.normal("aob", (C,), 24, 0.1)}
+    x, sd = _attention_inputs(B, C, H, W)
     ref = om.attention(O, sd, "a", x)
     got = G2.linear_attention(x, sd["a.fn.norm.g"], sd["a.fn.norm.b"], sd["a.fn.fn.to_qkv.weight"],
                               sd["a.fn.fn.to_out.weight"], sd["a.fn.fn.to_out.bias"])
@@ -437,12 +434,7 @@ def test_attention_fold_in_one_launch_equals_the_two_launch_fold(O, case, monkey
     T1 slab of a column block stays in LDS) against the oracle, and bit-identical to the two launches of round 4 (same products, same order)."""
     from cdc_compression_amd.ops import Ops
     B, C, H, W = case
-    x = synth.normal("ax", (B, C, H, W), 24)
-    sd = {"a.fn.norm.g": synth.normal("ag", (1, C, 1, 1), 24, 0.2, 1.0),
-          "a.fn.norm.b": synth.normal("ab", (1, C, 1, 1), 24, 0.2),
-          "a.fn.fn.to_qkv.weight": synth.normal("aq", (3 * C, C, 1, 1), 24, 2.0 / np.sqrt(C)),
-          "a.fn.fn.to_out.weight": synth.normal("ao", (C, C, 1, 1), 24, 1.0 / np.sqrt(C)),
-          "a.fn.fn.to_out.bias": synth.normal("aob", (C,), 24, 0.1)}
+    x, sd = _attention_inputs(B, C, H, W)
     args = (x, sd["a.fn.norm.g"], sd["a.fn.norm.b"], sd["a.fn.fn.to_qkv.weight"], sd["a.fn.fn.to_out.weight"], sd["a.fn.fn.to_out.bias"])
     ref = om.attention(O, sd, "a", x)
     one = Ops(0).linear_attention(*args)
