@@ -466,10 +466,9 @@ __global__ void __launch_bounds__(256) kmax_kernel(const float *k, long long k_b
     }
 }
 
-hipError_t kstats_launch(const float *k, long long k_bs, int C, int N, float *kmax, int B,
-                         hipStream_t st) {
-    const int block = N >= 2048 ? 256 : 64;
-    hipLaunchKernelGGL(kmax_kernel, dim3(C, B), dim3(block), 0, st, k, k_bs, C, N, kmax);
+hipError_t kstats_launch(const AttnCtxArgs &a, int B, hipStream_t st) {
+    const int block = a.N >= 2048 ? 256 : 64;
+    hipLaunchKernelGGL(kmax_kernel, dim3(a.C, B), dim3(block), 0, st, a.k, a.bs, a.C, a.N, a.kmax);
     return hipGetLastError();
 }
 
@@ -758,8 +757,12 @@ __global__ void __launch_bounds__(256) ctx_partial_generic_kernel(const float *k
 }
 
 // ONE launch for kstats + partial + reduce (see ctx_partial_kernel, ONE): N % 4 == 0, C % 64 == 0, Cin_pad == COP == C
-hipError_t ctx_one_launch(const float *k, const float *v, long long kv_bs, int C, int N, float scale, float *ctxw, int Cin_pad, int COP,
-                          unsigned short *Ws, int B, hipStream_t st, int f16) {
+hipError_t ctx_one_launch(const AttnCtxArgs &a, int B, hipStream_t st) {
+    const float *k = a.k, *v = a.v, scale = a.scale;
+    float *ctxw = a.ctxw;
+    const long long kv_bs = a.bs;
+    const int C = a.C, N = a.N, Cin_pad = a.Cin_pad, COP = a.COP;
+    unsigned short *Ws = a.ws_f16 ? a.Ws : nullptr;      // (the kernel emits fp16 planes only)
     if ((N & 3) || (C % 64) || Cin_pad != C || COP != C) return hipErrorInvalidValue;
     const int tiles = C / 64;
     const size_t lds = sizeof(float) * 4 * 64 * 64;
@@ -772,7 +775,7 @@ hipError_t ctx_one_launch(const float *k, const float *v, long long kv_bs, int C
     }
     const int img_major = (tiles > 1 && B % 8 == 0 && !dev_env("CDC_CTX_NO_IMG_MAJOR")) ? 1 : 0;      // (round 6; the switch: A/B)
     const dim3 grid = img_major ? dim3((unsigned)B, 1, (unsigned)(tiles * tiles)) : dim3((unsigned)(tiles * tiles), 1, (unsigned)B);
-    if (f16)
+    if (a.f16)
         hipLaunchKernelGGL((ctx_partial_kernel<true, true>), grid, dim3(256), lds, st, k, v, kv_bs, C, N, nullptr, nullptr, nullptr, 1, tiles, scale,
                            ctxw, Cin_pad, COP, Ws, img_major);
     else
@@ -781,9 +784,11 @@ hipError_t ctx_one_launch(const float *k, const float *v, long long kv_bs, int C
     return hipGetLastError();
 }
 
-hipError_t ctx_partial_launch(const float *k, const float *v, long long kv_bs, int C, int N,
-                              const float *kmax, float *S, float *Zp, int nsplit, int B,
-                              hipStream_t st, int f16) {
+hipError_t ctx_partial_launch(const AttnCtxArgs &a, int B, hipStream_t st) {
+    const float *k = a.k, *v = a.v, *kmax = a.kmax;
+    float *S = a.S, *Zp = a.ksum;
+    const long long kv_bs = a.bs;
+    const int C = a.C, N = a.N, nsplit = a.nsplit;
     if (N & 3) {                                 // 16-byte DMA pieces need N % 4 == 0
         hipLaunchKernelGGL(ctx_partial_generic_kernel, dim3(C, nsplit, B), dim3(C >= 256 ? 256 : 64), 0, st,
                            k, v, kv_bs, C, N, kmax, S, Zp, nsplit);
@@ -803,7 +808,7 @@ hipError_t ctx_partial_launch(const float *k, const float *v, long long kv_bs, i
     // (image-major as in ctx_one_launch: the tiles of an image and split share its k / v row blocks)
     const int img_major = (tiles > 1 && B % 8 == 0 && !dev_env("CDC_CTX_NO_IMG_MAJOR")) ? 1 : 0;
     const dim3 grid = img_major ? dim3((unsigned)B, (unsigned)nsplit, (unsigned)(tiles * tiles)) : dim3((unsigned)(tiles * tiles), (unsigned)nsplit, (unsigned)B);
-    if (f16)
+    if (a.f16)
         hipLaunchKernelGGL(ctx_partial_kernel<true>, grid, dim3(256), lds, st, k, v,
                            kv_bs, C, N, kmax, S, Zp, nsplit, tiles, 0.f, nullptr, 0, 0, nullptr, img_major);
     else
@@ -860,10 +865,9 @@ __global__ void __launch_bounds__(256) ctx_reduce_kernel(const float *S, const f
     }
 }
 
-hipError_t ctx_reduce_launch(const float *S, const float *ksum, int C, int nsplit, float scale,
-                             float *ctxw, int Cin_pad, int COP, int B, hipStream_t st, unsigned short *Ws) {
-    hipLaunchKernelGGL(ctx_reduce_kernel, dim3(ceil_div(Cin_pad, 8), B), dim3(COP >= 256 ? 256 : 64), 0, st, S,
-                       ksum, C, nsplit, scale, ctxw, Cin_pad, COP, Ws);
+hipError_t ctx_reduce_launch(const AttnCtxArgs &a, int B, hipStream_t st) {
+    hipLaunchKernelGGL(ctx_reduce_kernel, dim3(ceil_div(a.Cin_pad, 8), B), dim3(a.COP >= 256 ? 256 : 64), 0, st, (const float *)a.S,
+                       (const float *)a.ksum, a.C, a.nsplit, a.scale, a.ctxw, a.Cin_pad, a.COP, a.ws_f16 ? a.Ws : nullptr);   // (fp16 planes only)
     return hipGetLastError();
 }
 
@@ -1302,10 +1306,12 @@ __global__ void __launch_bounds__(64 * (CT / 32)) fold_r12_mfma_kernel(const flo
     }
 }
 
-hipError_t ctx_fold_launch(const float *S, const float *ksum, int C, int nsplit, float scale,
-                           const float *WoT, const float *WqT, float *T1, float *Mt, int Cin_pad,
-                           int COP, const float *ln_g, const float *u, const float *b_out,
-                           float *biasB, int B, hipStream_t st, const float *M, unsigned short *Ws, int ws_f16, const float *Wq) {
+hipError_t ctx_fold_launch(const AttnCtxArgs &a, int B, hipStream_t st) {
+    const float *S = a.S, *ksum = a.ksum, *WoT = a.WoT, *WqT = a.WqT, *ln_g = a.ln_g, *u = a.uq, *b_out = a.b_out, *M = a.M, *Wq = a.Wq;
+    float *T1 = a.T1, *Mt = a.ctxw, *biasB = a.biasB;
+    const float scale = a.scale;
+    const int C = a.C, nsplit = a.nsplit, Cin_pad = a.Cin_pad, COP = a.COP, ws_f16 = a.ws_f16;
+    unsigned short *Ws = a.Ws;
     const int blk = C >= 256 ? 256 : (C >= 128 ? 128 : 64);
     // Mt doubles as scratch for the normalised context (C*C <= Cin_pad*COP) until R2 overwrites it
     int spf = 1;
@@ -1373,11 +1379,10 @@ __global__ void __launch_bounds__(256) fold_combine_kernel(const float *P, const
     }
 }
 
-hipError_t fold_combine_launch(const float *P, const float *bias, float *out, int Cout, int KH,
-                               int pad, int H, int W, int B, hipStream_t st) {
-    const int gx = (int)std::min<size_t>(((size_t)H * W + 255) / 256, 1024);
-    hipLaunchKernelGGL(fold_combine_kernel, dim3(gx, Cout, B), dim3(256), 0, st, P, bias, out, Cout, KH,
-                       pad, H, W);
+hipError_t fold_combine_launch(const CombineArgs &a, int B, hipStream_t st) {
+    const int gx = (int)std::min<size_t>(((size_t)a.H * a.W + 255) / 256, 1024);
+    hipLaunchKernelGGL(fold_combine_kernel, dim3(gx, a.Cout, B), dim3(256), 0, st, a.P, a.bias, a.out, a.Cout, a.KH,
+                       a.pad, a.H, a.W);
     return hipGetLastError();
 }
 
@@ -1746,18 +1751,20 @@ __global__ void __launch_bounds__(256) vbr_affine_kernel(float *x, long long bs,
     }
 }
 
-hipError_t vbr_affine_launch(float *x, long long bs, int C, int HW, const float *rate, const float *p, int leaky, int B, hipStream_t st) {
-    const bool v4 = ((HW | bs) & 3) == 0 && (reinterpret_cast<size_t>(x) & 15) == 0;
-    const int n = v4 ? HW / 4 : HW;
-    const dim3 grid((unsigned)std::max(1, std::min((n + 1023) / 1024, 64)), (unsigned)C, (unsigned)B);   // <= 4 accesses per thread
-    if (v4) hipLaunchKernelGGL(vbr_affine_kernel<float4>, grid, dim3(256), 0, st, x, bs, C, HW, rate, p, leaky);
-    else hipLaunchKernelGGL(vbr_affine_kernel<float>, grid, dim3(256), 0, st, x, bs, C, HW, rate, p, leaky);
+hipError_t vbr_affine_launch(const VbrArgs &a, int B, hipStream_t st) {
+    const bool v4 = ((a.HW | a.bs) & 3) == 0 && (reinterpret_cast<size_t>(a.x) & 15) == 0;
+    const int n = v4 ? a.HW / 4 : a.HW;
+    const dim3 grid((unsigned)std::max(1, std::min((n + 1023) / 1024, 64)), (unsigned)a.C, (unsigned)B);   // <= 4 accesses per thread
+    if (v4) hipLaunchKernelGGL(vbr_affine_kernel<float4>, grid, dim3(256), 0, st, a.x, a.bs, a.C, a.HW, a.rate, a.p, a.leaky);
+    else hipLaunchKernelGGL(vbr_affine_kernel<float>, grid, dim3(256), 0, st, a.x, a.bs, a.C, a.HW, a.rate, a.p, a.leaky);
     return hipGetLastError();
 }
 
-hipError_t copy_channels_launch(const float *src, long long src_bs, float *dst, long long dst_bs,
-                                long long n, int B, hipStream_t st, int parts, long long part_stride,
-                                const int *step_ptr, long long step_stride) {
+hipError_t copy_channels_launch(const CopyArgs &a, int B, hipStream_t st) {
+    const float *src = a.src;
+    float *dst = a.dst;
+    const long long src_bs = a.src_bs, dst_bs = a.dst_bs, n = a.n, part_stride = a.part_stride, step_stride = a.step_stride;
+    const int parts = a.parts, *step_ptr = a.step;
     const bool v4 = ((n | src_bs | dst_bs | part_stride | step_stride) & 3) == 0 &&
                     ((reinterpret_cast<size_t>(src) | reinterpret_cast<size_t>(dst)) & 15) == 0;
     const long long nv = v4 ? n / 4 : n;
@@ -1798,11 +1805,10 @@ __global__ void __launch_bounds__(256) unfold_x_kernel(const float *src, long lo
     }
 }
 
-hipError_t unfold_x_launch(const float *src, long long src_bs, float *dst, long long dst_bs, int C, int KW,
-                           int pad, int H, int W, int B, hipStream_t st) {
-    const int gx = std::min((H * (W >> 2) + 255) / 256, 256);
-    hipLaunchKernelGGL(unfold_x_kernel, dim3(gx, C * KW, B), dim3(256), 0, st, src, src_bs, dst, dst_bs, C, KW,
-                       pad, H, W);
+hipError_t unfold_x_launch(const UnfoldArgs &a, int B, hipStream_t st) {
+    const int gx = std::min((a.H * (a.W >> 2) + 255) / 256, 256);
+    hipLaunchKernelGGL(unfold_x_kernel, dim3(gx, a.C * a.KW, B), dim3(256), 0, st, a.src, a.src_bs, a.dst, a.dst_bs, a.C, a.KW,
+                       a.pad, a.H, a.W);
     return hipGetLastError();
 }
 

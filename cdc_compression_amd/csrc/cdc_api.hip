@@ -54,70 +54,7 @@ int run_op(cdc_handle *h, const Op &op, int B, hipStream_t st) {
     // kernel cold (first launch: code, operands and argument block as the program leaves them) beside itself hot.
     static const int nrep = [] { const char *e = dev_env("CDC_DEV_REPEAT"); return e ? std::max(1, atoi(e)) : 1; }();
     for (int rep = 0; rep < nrep; ++rep)
-    switch (op.kind) {
-        case Op::CONV: HIP_TRY(h, conv_launch(op.conv, op.plan, B, op.nz, st)); break;
-        case Op::CONVPF:
-            if (op.pw) HIP_TRY(h, pw_launch(op.pf, op.pfplan, B, st));
-            else HIP_TRY(h, pf_launch(op.pf, op.pfplan, B, op.nz, st));
-            break;
-        case Op::CONVWS: HIP_TRY(h, ws_launch(op.ws, op.wsplan, st)); break;
-        case Op::CONVWS1: HIP_TRY(h, ws1_launch(op.ws1, op.ws1plan, st)); break;
-        case Op::PFPACK:
-            if (op.pk.c4 == 2) {       // unpack: planes (pk.dst) -> the tensor's fp32 buffer (pk.src)
-                HIP_TRY(h, pf_unpack_launch(op.pk.dst, op.pk.dst_bs, const_cast<float *>(op.pk.src), op.pk.src_bs, op.pk.C, op.pk.H, op.pk.W, B, st));
-                break;
-            }
-            if (op.pk.c4) { HIP_TRY(h, c4_pack_launch(op.pk.src, op.pk.src_bs, (float *)op.pk.dst, op.pk.C, (long long)op.pk.H * op.pk.W, B, st)); break; }
-            HIP_TRY(h, pf_pack_launch(op.pk.src, op.pk.src_bs, op.pk.dst, op.pk.dst_bs, op.pk.C, op.pk.H, op.pk.W, B, st));
-            break;
-        case Op::LN: HIP_TRY(h, ln_launch(op.ln, B, st)); break;
-        case Op::TEMB: HIP_TRY(h, temb_launch(op.temb, B, st)); break;
-        case Op::KSTATS:
-            HIP_TRY(h, kstats_launch(op.at.k, op.at.bs, op.at.C, op.at.N, op.at.kmax, B, st));
-            break;
-        case Op::CTXP: {
-            if (op.at_one) {
-                HIP_TRY(h, ctx_one_launch(op.at.k, op.at.v, op.at.bs, op.at.C, op.at.N, op.at.scale, op.at.ctxw, op.at.Cin_pad, op.at.COP,
-                                          op.at_ws_f16 ? op.at_Ws : nullptr, B, st, h->arith == 1));
-                break;
-            }
-            HIP_TRY(h, ctx_partial_launch(op.at.k, op.at.v, op.at.bs, op.at.C, op.at.N, op.at.kmax,
-                                          op.at.S, op.at.ksum, op.at.nsplit, B, st, h->arith == 1));
-            break;
-        }
-        case Op::CTXR:
-            HIP_TRY(h, ctx_reduce_launch(op.at.S, op.at.ksum, op.at.C, op.at.nsplit, op.at.scale,
-                                         op.at.ctxw, op.at.Cin_pad, op.at.COP, B, st, op.at_ws_f16 ? op.at_Ws : nullptr));
-            break;
-        case Op::KVCTX: HIP_TRY(h, kvctx_launch(op.kvc, B, st)); break;
-        case Op::LNCONV: HIP_TRY(h, lnconv_launch(op.lnc, B, st)); break;
-        case Op::CTXF:
-            HIP_TRY(h, ctx_fold_launch(op.at.S, op.at.ksum, op.at.C, op.at.nsplit, op.at.scale, op.at.WoT,
-                                       op.at.WqT, op.at.T1, op.at.ctxw, op.at.Cin_pad, op.at.COP, op.at.ln_g,
-                                       op.at.ln_b, op.at.b_out, op.at.biasB, B, st, op.at_M, op.at_Ws, op.at_ws_f16, op.at_Wq));
-            break;
-        case Op::COMBINE:
-            HIP_TRY(h, fold_combine_launch(op.cb.P, op.cb.bias, op.cb.out, op.cb.Cout, op.cb.KH, op.cb.pad,
-                                           op.cb.H, op.cb.W, B, st));
-            break;
-        case Op::DDIM: HIP_TRY(h, ddim_launch(op.ddim, st)); break;
-        case Op::UNFOLD:
-            HIP_TRY(h, unfold_x_launch(op.uf.src, op.uf.src_bs, op.uf.dst, op.uf.dst_bs, op.uf.C, op.uf.KW,
-                                       op.uf.pad, op.uf.H, op.uf.W, B, st));
-            break;
-        case Op::COPY:
-            HIP_TRY(h, copy_channels_launch(op.cp.src, op.cp.src_bs, op.cp.dst, op.cp.dst_bs, op.cp.n,
-                                            B, st, op.cp_parts, op.cp_part_stride, op.cp_step, op.cp_step_stride));
-            break;
-        case Op::VBR:
-            HIP_TRY(h, vbr_affine_launch(op.vb.x, op.vb.bs, op.vb.C, op.vb.HW, op.vb.rate, op.vb.p, op.vb.leaky, B, st));
-            break;
-        case Op::GDN: HIP_TRY(h, gdn_launch(op.gdn, B, st)); break;
-        case Op::MAXPOOL: HIP_TRY(h, maxpool2_launch(op.mp.src, op.mp.dst, (long long)B * op.mp.C, op.mp.H, op.mp.W, st)); break;
-        case Op::LPHEAD:            // B rows = B / 2 pairs
-            HIP_TRY(h, lpips_head_launch(op.lh.f, op.lh.bs, op.lh.C, op.lh.HW, op.lh.w, B / 2, op.lh.partials, op.lh.res, op.lh.layer, op.lh.fault, st));
-            break;
-    }
+        HIP_TRY(h, std::visit([&](const auto &payload) { return op_launch(payload, B, st); }, op.p));
     if (prof) {
         HIP_TRY(h, hipEventRecord(eb, st));
         h->pending.push_back({ea, eb, op.prof, op.flops, op.bytes, op.id});
@@ -149,17 +86,17 @@ int run_pre(cdc_handle *h, hipStream_t st) {
 // step < 0: plain Unet.forward with the caller's per-image time values.
 int run_unet(cdc_handle *h, hipStream_t st, int step, bool skip_combine) {
     for (const Op &op : h->ops) {
-        if (skip_combine && op.kind == Op::COMBINE) continue;      // (the sampler kernel evaluates it: ddim_on_device)
-        if (op.kind == Op::TEMB && (step >= 0 || step == -2)) {
-            Op c = op;
-            c.kind = Op::COPY;
-            c.cp = {h->d_shift_tab + (step >= 0 ? (size_t)step * h->shift_bs : 0), 0, h->shift, h->shift_bs, h->shift_bs};
-            if (step == -2) { c.cp_step = h->d_step; c.cp_step_stride = h->shift_bs; }
-            int rc = run_op(h, c, h->pB, st);
-            if (rc) return rc;
-            continue;
+        if (skip_combine && op.get<CombineArgs>()) continue;      // (the sampler kernel evaluates it: ddim_on_device)
+        int rc;
+        if (op.get<TembArgs>() && (step >= 0 || step == -2)) {      // the shifts of the step: a row of the per-decode table, under TEMB's id
+            CopyArgs c = {h->d_shift_tab + (step >= 0 ? (size_t)step * h->shift_bs : 0), 0, h->shift, h->shift_bs, h->shift_bs};
+            if (step == -2) { c.step = h->d_step; c.step_stride = h->shift_bs; }
+            Op cop(op.prof, c, op.flops, op.bytes);
+            cop.id = op.id;
+            rc = run_op(h, cop, h->pB, st);
+        } else {
+            rc = run_op(h, op, h->pB, st);
         }
-        int rc = run_op(h, op, h->pB, st);
         if (rc) return rc;
     }
     return CDC_OK;
@@ -953,20 +890,15 @@ static int ddim_on_device(cdc_handle *h, const float *x_in, int i, const float *
         HIP_TRY(h, hipMemcpyAsync(h->in_x, x_in, n * sizeof(float), hipMemcpyDeviceToDevice, st));
     // the 7-row combine of the final convolution rides in the sampler kernel (one launch and a 3-channel tensor less per iteration)
     static const bool fuse_combine = getenv("CDC_NO_COMBINE_FUSE") == nullptr;
-    const Op *cb = nullptr;
-    if (fuse_combine && !h->ops.empty() && h->ops.back().kind == Op::COMBINE && h->ops.back().cb.out == h->out_fx) cb = &h->ops.back();
+    const CombineArgs *cb = (fuse_combine && !h->ops.empty()) ? h->ops.back().get<CombineArgs>() : nullptr;
+    if (cb && cb->out != h->out_fx) cb = nullptr;
     if ((rc = run_unet(h, st, i, cb != nullptr))) return rc;
-    Op op;
-    op.kind = Op::DDIM; op.prof = PC_SMALL;
-    op.ddim = {h->out_fx, h->in_x, (eta != 0.f) ? noise : nullptr, x_out, h->d_tab, h->steps, i < 0 ? 0 : i,
-               i == -2 ? h->d_step : nullptr, pred_mode, clip, eta, (long long)n,
-               (long long)(B / 2) * h->cfg.channels * H * W, h->d_fault, pred_mode == CDC_PRED_V ? h->d_tab_v : nullptr};
-    if (cb) {
-        op.ddim.P = cb->cb.P; op.ddim.P_bias = cb->cb.bias; op.ddim.pC = cb->cb.Cout; op.ddim.pKH = cb->cb.KH; op.ddim.pPad = cb->cb.pad;
-        op.ddim.pH = cb->cb.H; op.ddim.pW = cb->cb.W;
-    }
-    if (eta != 0.f && seeds) { op.ddim.noise = nullptr; op.ddim.seeds = seeds; op.ddim.per_image = (long long)(n / B); }
-    op.bytes = 16.0 * n;
+    DdimArgs d = {h->out_fx, h->in_x, (eta != 0.f) ? noise : nullptr, x_out, h->d_tab, h->steps, i < 0 ? 0 : i,
+                  i == -2 ? h->d_step : nullptr, pred_mode, clip, eta, (long long)n,
+                  (long long)(B / 2) * h->cfg.channels * H * W, h->d_fault, pred_mode == CDC_PRED_V ? h->d_tab_v : nullptr};
+    if (cb) { d.P = cb->P; d.P_bias = cb->bias; d.pC = cb->Cout; d.pKH = cb->KH; d.pPad = cb->pad; d.pH = cb->H; d.pW = cb->W; }
+    if (eta != 0.f && seeds) { d.noise = nullptr; d.seeds = seeds; d.per_image = (long long)(n / B); }
+    const Op op(PC_SMALL, d, 0, 16.0 * n);
     return run_op(h, op, B, st);
 }
 

@@ -170,7 +170,6 @@ struct TembArgs {
 };
 hipError_t temb_launch(const TembArgs &a, int B, hipStream_t st);
 
-// k-softmax statistics over the spatial axis (network_components.py:134): per (b, channel) row
 // Fused k/v projection + softmax_N(k) v^T of the folded attention levels (attn_kernels.hip).
 struct KvCtxArgs {
     const float *x; long long x_bs;     // PreNorm input [B][C][N]
@@ -199,26 +198,41 @@ struct LnConvArgs {
 };
 hipError_t lnconv_launch(const LnConvArgs &a, int B, hipStream_t st);
 
-hipError_t kstats_launch(const float *k, long long k_bs, int C, int N, float *kmax, int B,
-                         hipStream_t st);
+// The attention context chain of one level (network_components.py:134-137): k-softmax row maxima, the unnormalised partial context
+// S[b][split][d][e] = sum_{n in split} exp(k[d,n] - kmax[d]) v[e,n], its reduction to per-image 1x1 weights, and -- the folded levels --
+// the fold of to_out and to_q into them.  One block for the whole chain: every launcher reads the fields of its kernel.
+struct AttnCtxArgs {
+    const float *k, *v;             // staged k / v projections [B][C][N] (null where kvctx_kernel made S / ksum from x)
+    long long bs;                   // ... their batch stride
+    int C, N;
+    float *kmax;                    // [B][C] row maxima of k (kstats -> partial)
+    float *ksum;                    // [B][nsplit][C] partial sums of exp(k - max)
+    float *S;                       // [B][nsplit][C][C] partial context
+    float *ctxw;                    // [B][Cin_pad][COP] packed per-image 1x1 weights: the context (reduce / one), M' (fold)
+    int nsplit, Cin_pad, COP;
+    float scale;                    // C^-1/2 (q * scale folded in)
+    const float *WoT, *WqT;         // fold: to_out / to_q weights, transposed [C][C]
+    float *T1;                      // fold: [B][C][C] scratch
+    const float *ln_g, *uq, *b_out; // fold: PreNorm gain, Wq b_ln, to_out bias
+    float *biasB;                   // fold: [B][C] per-image bias M' b_ln + b_out
+    const float *M;                 // fold after kvctx: per-split row maxima [B][nsplit][C] (or null)
+    unsigned short *Ws;             // weight planes of ctxw for the split convolution / lnconv_kernel (or null)
+    int ws_f16;                     // the planes are fp16 {WH, WL, WH2} of ctxw 2^8 instead of bf16 (reduce / one emit only these)
+    const float *Wq;                // fold: Wq [d][ci], the A operand of fold_r2_mfma_kernel
+    int f16;                        // partial / one: the two-plane fp16 arithmetic (the handle's arith == 1 when planned)
+};
+hipError_t kstats_launch(const AttnCtxArgs &a, int B, hipStream_t st);
 // S[b][split][d][e] = sum_{n in split} exp(k[d,n]-kmax[d]) * v[e,n]      (:135, unnormalised)
-hipError_t ctx_partial_launch(const float *k, const float *v, long long kv_bs, int C, int N,
-                              const float *kmax, float *S, float *Zp, int nsplit, int B,
-                              hipStream_t st, int f16 = 0);
-hipError_t ctx_one_launch(const float *k, const float *v, long long kv_bs, int C, int N, float scale, float *ctxw, int Cin_pad, int COP,
-                          unsigned short *Ws, int B, hipStream_t st, int f16);
+hipError_t ctx_partial_launch(const AttnCtxArgs &a, int B, hipStream_t st);
+// kstats + partial + reduce as ONE launch (one split)
+hipError_t ctx_one_launch(const AttnCtxArgs &a, int B, hipStream_t st);
 // ctxw[b][d][e] = scale * sum_split S / ksum[d], written as per-image packed 1x1 weights
 // [Cin_pad][COP] (rows d >= C and cols e >= C zeroed)
-hipError_t ctx_reduce_launch(const float *S, const float *ksum, int C, int nsplit, float scale,
-                             float *ctxw, int Cin_pad, int COP, int B, hipStream_t st, unsigned short *Ws = nullptr);
-
-hipError_t ctx_fold_launch(const float *S, const float *ksum, int C, int nsplit, float scale,
-                           const float *WoT, const float *WqT, float *T1, float *Mt, int Cin_pad,
-                           int COP, const float *ln_g, const float *u, const float *b_out,
-                           float *biasB, int B, hipStream_t st, const float *M = nullptr,
-                           unsigned short *Ws = nullptr, int ws_f16 = 0, const float *Wq = nullptr);
-hipError_t fold_combine_launch(const float *P, const float *bias, float *out, int Cout, int KH,
-                               int pad, int H, int W, int B, hipStream_t st);
+hipError_t ctx_reduce_launch(const AttnCtxArgs &a, int B, hipStream_t st);
+hipError_t ctx_fold_launch(const AttnCtxArgs &a, int B, hipStream_t st);
+// 7-row combine of the row-folded final convolution: out[co][y][x] = bias[co] + sum_ky P[(co, ky)][y + ky - pad][x]
+struct CombineArgs { const float *P, *bias; float *out; int Cout, KH, pad, H, W; };
+hipError_t fold_combine_launch(const CombineArgs &a, int B, hipStream_t st);
 
 struct DdimArgs {
     const float *fx, *x, *noise;
@@ -247,9 +261,10 @@ hipError_t ddim_launch(const DdimArgs &a, hipStream_t st);
 // out[b][e] = scale * z(seeds[b], draw, e) for e < per_image (rng.h; seeds on the device); 16-byte stores when the layout allows
 hipError_t randn_fill_launch(const unsigned long long *seeds, int B, long long per_image, unsigned draw, float scale, float *out,
                              hipStream_t st);
-hipError_t copy_channels_launch(const float *src, long long src_bs, float *dst, long long dst_bs,
-                                long long n, int B, hipStream_t st, int parts = 1, long long part_stride = 0,
-                                const int *step_ptr = nullptr, long long step_stride = 0);
+// dst[b] = sum of `parts` planes of src[b] (plane p at + p * part_stride); step != null: the source row is selected by a device step index
+struct CopyArgs { const float *src; long long src_bs; float *dst; long long dst_bs, n; int parts = 1; long long part_stride = 0;
+                  const int *step = nullptr; long long step_stride = 0; };
+hipError_t copy_channels_launch(const CopyArgs &a, int B, hipStream_t st);
 hipError_t step_dec_launch(int *step, hipStream_t st);
 hipError_t bpp_launch(const float *qh, long long nh, int hw_h, const float *prior, const float *ql, const float *mean,
                       const float *scale, long long nl, float inv_hw, float *bpp, int B, hipStream_t st);
@@ -260,7 +275,8 @@ hipError_t bits_differ_launch(const float *a, const float *b, long long n, long 
 hipError_t dequantize_launch(const float *x, const float *loc, float *out, long long n, hipStream_t st);
 // VBRCondition (variable-bitrate compressors) in place over x [B][C][HW] (batch stride bs): with r = rate[b],
 // x = x * (p[c] r + p[C + c]) + (p[2C + c] r + p[3C + c]), then LeakyReLU(0.2) when `leaky`
-hipError_t vbr_affine_launch(float *x, long long bs, int C, int HW, const float *rate, const float *p, int leaky, int B, hipStream_t st);
+struct VbrArgs { float *x; long long bs; int C, HW; const float *rate, *p; int leaky; };
+hipError_t vbr_affine_launch(const VbrArgs &a, int B, hipStream_t st);
 // frame_kernels.hip: P planes [H][W] (float32, or uint8 -> v / 255 * 2 - 1) -> [Hp][Wp] float32, extended at the bottom / right by edge
 // replication (zero = 1: by zeros), and the top-left [H][W] window back (float32 copy, or the uint8 of save_image)
 hipError_t frame_in_launch(const void *src, int u8, float *dst, int P, int H, int W, int Hp, int Wp, int zero, hipStream_t st);
@@ -284,14 +300,15 @@ constexpr int LPIPS_TAPS = 5;
 // both operands' H x W windows -> out [2 n][3][H][W]: (2 u - 1 - shift[c]) / scale[c], operand a in rows 0 .. n-1, b in rows n .. 2n-1
 hipError_t lpips_in_launch(const MetricView &a, const MetricView &b, int n, int H, int W, const float shift[3], const float scale[3], float *out,
                            hipStream_t st);
-// max_pool2d(2, 2), floor mode, over `planes` contiguous fp32 planes [H][W] -> [H / 2][W / 2]
-hipError_t maxpool2_launch(const float *in, float *out, long long planes, int H, int W, hipStream_t st);
+// max_pool2d(2, 2), floor mode, over B * C contiguous fp32 planes [H][W] -> [H / 2][W / 2]
+struct MaxpoolArgs { const float *src; float *dst; int C, H, W; };
+hipError_t maxpool2_launch(const MaxpoolArgs &a, int B, hipStream_t st);
 // The head of one tap: f [2 n][C][HW] (batch stride bs; operand 0 of pair i in row i, operand 1 in row n + i), w [C] ->
 // res[i][layer] = mean over the map of sum_c w_c (f0_c / (|f0| + 1e-10) - f1_c / (|f1| + 1e-10))^2, float64.  partials: n *
 // lpips_head_blocks(HW) doubles.  A non-finite result sets *fault (may be null).
 int lpips_head_blocks(int HW);
-hipError_t lpips_head_launch(const float *f, long long bs, int C, int HW, const float *w, int n, double *partials, double *res, int layer,
-                             int *fault, hipStream_t st);
+struct LpipsHeadArgs { const float *f; long long bs; int C, HW; const float *w; double *partials, *res; int layer; int *fault; };
+hipError_t lpips_head_launch(const LpipsHeadArgs &a, int n, hipStream_t st);
 // gdn_kernels.hip: GDN1 / inverse GDN1 (epsilon-tree SimpleCompressor) over x [B][C][HW] as one fused pass; beta [C] and gamma [C][C]
 // are the REPARAMETRISED parameters (gdn_reparam, host, float32 operation by operation as torch).  C % 16 == 0, 16 <= C <= 256.
 struct GdnArgs {
@@ -304,7 +321,8 @@ struct GdnArgs {
 bool gdn_supported(int C);
 hipError_t gdn_launch(const GdnArgs &a, int B, hipStream_t st);
 void gdn_reparam(const float *beta, const float *gamma, int C, float *beta_r, float *gamma_r);
-hipError_t unfold_x_launch(const float *src, long long src_bs, float *dst, long long dst_bs, int C, int KW,
-                           int pad, int H, int W, int B, hipStream_t st);
+// column unfold for few-channel k x k convolutions: dst[kx * C + c][y][x] = src[c][y][x + kx - pad]
+struct UnfoldArgs { const float *src; long long src_bs; float *dst; long long dst_bs; int C, KW, pad, H, W; };
+hipError_t unfold_x_launch(const UnfoldArgs &a, int B, hipStream_t st);
 
 }  // namespace cdc

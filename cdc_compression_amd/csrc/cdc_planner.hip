@@ -19,51 +19,14 @@ struct Builder {
     int pb() const { return planB > 0 ? planB : B; }
     std::vector<Op> *cur = nullptr; // op list being emitted to (h->ops unless set)
 
-    int ws1_h = 0;                  // (label only: rows of the map of the CONVWS1 op being emitted)
     void emit(Op op) {
         op.id = (int)h->op_ms.size();
         h->op_ms.push_back(0); h->op_n.push_back(0); h->op_flops.push_back(op.flops);
+        const bool hoisted = cur == &h->pre_ops;
         char buf[160];
-        const char *kinds[] = {"conv", "ln", "temb", "kstats", "ctxp", "ctxr", "ctxf", "combine", "ddim", "copy", "unfold", "kvctx", "lnconv", "convpf", "pfpack", "convws", "convws1", "vbr", "maxpool", "lpips_head", "gdn"};
-        if (op.kind == Op::PFPACK && op.pk.c4 == 2) kinds[Op::PFPACK] = "pfunpack";
-        if (op.kind == Op::CONV)
-            snprintf(buf, sizeof buf, "conv %dx%d s%d %4d->%-4d out %3dx%-3d MB%d NPW%d WN%d g%d tg%d ipw%d ks%d%s%s%s%s%s", op.conv.KH,
-                     op.conv.KW, op.conv.stride, op.conv.Cin, op.conv.Cout, op.conv.Ho, op.conv.Wo, op.plan.MB,
-                     op.plan.NPW, op.plan.WN, op.plan.groups, op.plan.tg, op.plan.ipw, op.plan.ksplit, op.plan.split == 2 ? (op.plan.arith ? " SPLIT2H" : " SPLIT2") : (op.plan.split ? " SPLIT" : ""),
-                     op.conv.ep_g ? " LN" : "",
-                     op.conv.ln_mean ? " pre" : "", cur == &h->pre_ops ? " HOIST" : "", op.conv.resid ? " +res" : "");
-        else if (op.kind == Op::CONVPF)
-            snprintf(buf, sizeof buf, "conv %dx%d s%d %4d->%-4d out %3dx%-3d MB%d NPW%d WM%d WP%d g%d R%d %s%s%s%s%s%s", op.pf.KH, op.pf.KW,
-                     op.pf.stride == 2 ? 2 : 1, op.pf.Cin, op.pf.Cout, op.pf.Ho, op.pf.Wo, op.pfplan.MB, op.pfplan.NPW, op.pfplan.WM, op.pfplan.WP,
-                     op.pfplan.groups, op.pfplan.ring, op.pw ? (op.pf.pre_mean ? "PW pre" : "PW") : (op.pfplan.pf3_epv ? (op.pf.ep_g ? "PF3 LN" : "PF3") : (op.pf.ep_g ? "PF LN" : "PF")), op.pf.out ? "" : " nof32", op.pf.out_pf ? " +pf" : "",
-                     op.pf.resid ? " +res" : (op.pf.resid_pf ? " +resP" : ""), cur == &h->pre_ops ? " HOIST" : "", op.pf.tz == 4 ? " TZ4" : "");
-        else if (op.kind == Op::CONVWS)
-            snprintf(buf, sizeof buf, "conv 3x3 s%d %4d->%-4d out %3dx%-3d NPB%d waves%d tiles%d g%d WS%s", op.wsplan.stride, op.ws.Cin, op.ws.Cout, op.ws.H, op.wsplan.W,
-                     op.wsplan.NPB, op.wsplan.waves, op.wsplan.tiles, op.wsplan.groups, op.ws.pre_add ? " pre_add" : "");
-        else if (op.kind == Op::CONVWS1)
-            snprintf(buf, sizeof buf, "conv 1x1 s1 %4d->%-4d out %3dx%-3d NPB%d waves%d tiles%d g%d WS1%s%s%s", op.ws1.Cin, op.ws1.Cout, ws1_h, op.ws1.HW / std::max(ws1_h, 1),
-                     op.ws1plan.NPB, op.ws1plan.waves, op.ws1plan.tiles, op.ws1plan.groups, op.ws1.pre_mean ? " pre" : "", op.ws1.w_bs ? " perimg" : "",
-                     op.ws1.resid ? (op.ws1.resid_is_pre ? " pre_add" : " +res") : "");
-        else if (op.kind == Op::LN)
-            snprintf(buf, sizeof buf, "ln C=%d HW=%d%s", op.ln.C, op.ln.HW, op.ln.out ? "" : " stats");
-        else if (op.kind == Op::KVCTX)
-            snprintf(buf, sizeof buf, "kvctx C=%d N=%d nsplit=%d", op.kvc.C, op.kvc.N, op.kvc.nsplit);
-        else if (op.kind == Op::LNCONV)
-            snprintf(buf, sizeof buf, "lnconv C=%d N=%d nsplit=%d", op.lnc.C, op.lnc.N, op.lnc.nsplit);
-        else if (op.kind == Op::VBR)
-            snprintf(buf, sizeof buf, "vbr C=%d HW=%d%s", op.vb.C, op.vb.HW, op.vb.leaky ? " leaky" : "");
-        else if (op.kind == Op::GDN)
-            snprintf(buf, sizeof buf, "gdn C=%d HW=%d%s", op.gdn.C, op.gdn.HW, op.gdn.inverse ? " inv" : "");
-        else if (op.kind == Op::MAXPOOL)
-            snprintf(buf, sizeof buf, "maxpool2 C=%d in %dx%d", op.mp.C, op.mp.H, op.mp.W);
-        else if (op.kind == Op::LPHEAD)
-            snprintf(buf, sizeof buf, "lpips_head tap %d C=%d HW=%d", op.lh.layer, op.lh.C, op.lh.HW);
-        else if (op.kind == Op::KSTATS || op.kind == Op::CTXP || op.kind == Op::CTXR || op.kind == Op::CTXF)
-            snprintf(buf, sizeof buf, "%s C=%d N=%d nsplit=%d", op.at_one ? "ctx1" : kinds[op.kind], op.at.C, op.at.N, op.at_one ? 1 : op.at.nsplit);
-        else
-            snprintf(buf, sizeof buf, "%s", kinds[op.kind]);
-        // every op of the context-only part of the program says so (the convolutions' formats above already do)
-        if (cur == &h->pre_ops && !strstr(buf, " HOIST") && strlen(buf) + 7 < sizeof buf) strcat(buf, " HOIST");
+        std::visit([&](const auto &payload) { op_label(payload, buf, sizeof buf, hoisted); }, op.p);
+        // every op of the context-only part of the program says so (the convolutions' formats already do)
+        if (hoisted && !strstr(buf, " HOIST") && strlen(buf) + 7 < sizeof buf) strcat(buf, " HOIST");
         h->op_label.push_back(buf);
         (cur ? cur : &h->ops)->push_back(op);
     }
@@ -97,7 +60,8 @@ struct Builder {
     }
     // ---- PF twins: a second copy of an activation as two fp16 planes with a zero halo (conv_pf_kernel.h),
     // keyed by the fp32 tensor's address; `valid` once a producer of this program has emitted it.
-    struct PfTwin { void *p = nullptr; int C = 0, H = 0, W = 0; bool valid = false;
+    struct PfTwin { void *p = nullptr; float *f32 = nullptr;    // the planes; the fp32 tensor they twin (ensure_f32 unpacks into it)
+                    int C = 0, H = 0, W = 0; bool valid = false;
                     bool only = false;          // the planes are the ONLY copy: the producer wrote no fp32 (readers must take planes)
                     long long ps() const { return (long long)(H + 2) * (W + 2); }
                     long long bs() const { return (long long)(C / 8) * 2 * ps(); } };
@@ -131,9 +95,9 @@ struct Builder {
     static long long pf_maxpix() { const char *e = dev_env("CDC_PF_MAXPIX"); const long long v = e ? atoll(e) : 0; return v > 0 ? v : (1LL << 40); }
     PfTwin *twin(const float *p) { auto it = pfmap.find(p); return it == pfmap.end() ? nullptr : &it->second; }
     bool still_planes_only(const float *p) { PfTwin *t = twin(p); return t && t->only; }    // (false once ensure_f32 unpacked it)
-    void add_twin(const float *p, int C, int H, int W) {
+    void add_twin(float *p, int C, int H, int W) {
         if (rc || !p || !pf_on() || (C % 16) || W < 32 || H < 2 || (long long)H * W > pf_maxpix()) return;
-        PfTwin t; t.C = C; t.H = H; t.W = W;
+        PfTwin t; t.f32 = p; t.C = C; t.H = H; t.W = W;
         const size_t bytes = (size_t)B * t.bs() * 16;
         void *q = nullptr;
         hipError_t e = hipMalloc(&q, bytes);
@@ -148,10 +112,7 @@ struct Builder {
     void pack(const float *p, long long bs) {
         PfTwin *t = twin(p);
         if (rc || !t) return;
-        Op op; op.kind = Op::PFPACK; op.prof = PC_SMALL;
-        op.pk = {p, bs, t->p, t->bs(), t->C, t->H, t->W, 0};
-        op.bytes = 8.0 * B * t->C * t->H * t->W;
-        emit(op);
+        emit(Op(PC_SMALL, PfPackOp{p, bs, t->p, t->bs(), t->C, t->H, t->W}, 0, 8.0 * B * t->C * t->H * t->W));
         t->valid = true;
     }
     // PF -> fp32 for a planes-only tensor that reaches a reader of fp32 after all (the planes-only decision is taken by shape
@@ -163,10 +124,7 @@ struct Builder {
         PfTwin *t = q ? twin(q) : nullptr;
         if (!t || !t->only) return true;
         if (rc || !t->valid || bs != (long long)t->C * t->H * t->W) return false;
-        Op op; op.kind = Op::PFPACK; op.prof = PC_SMALL;
-        op.pk = {q, bs, t->p, t->bs(), t->C, t->H, t->W, 2};      // c4 == 2: unpack (dst = the planes, src = the fp32 buffer to fill)
-        op.bytes = 8.0 * B * t->C * t->H * t->W;
-        emit(op);
+        emit(Op(PC_SMALL, PfUnpackOp{t->p, t->bs(), t->f32, bs, t->C, t->H, t->W}, 0, 8.0 * B * t->C * t->H * t->W));
         t->only = false;
         ++n_unpacked;
         if (debug_plan()) fprintf(stderr, "[plan] planes-only tensor %dx%dx%d unpacked for an fp32 reader\n", t->C, t->H, t->W);
@@ -185,10 +143,7 @@ struct Builder {
         if (rc) return nullptr;
         std::vector<Op> *saved = cur;
         cur = &h->pre_ops;
-        Op op; op.kind = Op::PFPACK; op.prof = PC_SMALL;
-        op.pk = {p, bs, q, 0, C, H, W, 1};
-        op.bytes = 8.0 * B * C * H * W;
-        emit(op);
+        emit(Op(PC_SMALL, C4PackOp{p, bs, q, C, H, W}, 0, 8.0 * B * C * H * W));
         cur = saved;
         c4map[p] = q;
         return q;
@@ -359,11 +314,10 @@ struct Builder {
         a.fault = fault_flag();
     }
     // the end of a single-launch convolution: its cost for the per-op table, what the caller reads back, the op
-    bool finish(Op &op, double flops, double bytes, bool pf_only) {
-        op.flops = flops; op.bytes = bytes;
+    template <class T> bool finish(int prof, const T &payload, double flops, double bytes, bool pf_only) {
         last_ksplit = 1;
         last_pf_only = pf_only;
-        emit(op);
+        emit(Op(prof, payload, flops, bytes));
         return true;
     }
 
@@ -384,9 +338,9 @@ struct Builder {
         PfPlan plan;
         if (!pf_make_plan(ps, &plan)) return false;
         const int Ho = ps.Ho, Wo = ps.Wo;
-        Op op;
-        op.kind = Op::CONVPF; op.prof = prof; op.pfplan = plan; op.nz = w.nz;
-        PfArgs &a = op.pf;
+        PfConvOp op;
+        op.plan = plan; op.nz = w.nz;
+        PfArgs &a = op.a;
         memset(&a, 0, sizeof a);
         a.src0 = t0->p; a.src0_bs = t0->bs();
         if (t1) { a.src1 = t1->p; a.src1_bs = t1->bs(); }
@@ -419,14 +373,14 @@ struct Builder {
         // large 3x3 layers: the persistent ping-ponged kernel.  Its chunk summation order depends on the launch geometry
         // (batch size, CU count), so a program planned "as for one image" (planB: the entropy coder's bit-exactness
         // contract between batch sizes) never uses it.
-        if (planB == 0) pf3_make_plan(a, B, w.nz, &op.pfplan);
+        if (planB == 0) pf3_make_plan(a, B, w.nz, &op.plan);
         // (hoisted partial sums in accumulator order, pre_add_c4: measured only on the first layer's form, try_pf_uf -- 0.364 -> 0.354 ms;
         //  the 192 / 256-channel layers did not move, their 1x1 res_convs lost 5 %)
         if (debug_plan())
             fprintf(stderr, "[plan] conv %dx%d %d->%d out %dx%d on conv_pf%s_kernel (epv %d, %d workgroups x %d tiles per group)\n", w.KH, w.KW, w.Cin, w.Cout,
-                    Ho, Wo, op.pfplan.pf3_epv ? "3" : "", op.pfplan.pf3_epv, op.pfplan.pf3_G, op.pfplan.pf3_iters);
+                    Ho, Wo, op.plan.pf3_epv ? "3" : "", op.plan.pf3_epv, op.plan.pf3_G, op.plan.pf3_iters);
         const double px = (double)B * Ho * Wo * w.nz;
-        return finish(op, 2.0 * px * w.Cout * w.Cin * w.KH * w.KW, 4.0 * ((double)B * w.Cin * H * W + px * w.Cout), a.out == nullptr);
+        return finish(prof, op, 2.0 * px * w.Cout * w.Cin * w.KH * w.KW, 4.0 * ((double)B * w.Cin * H * W + px * w.Cout), a.out == nullptr);
     }
 
     // The first layer (7x1 over the kx-unfolded 3-channel image, ConvOpts::uf_c) on conv_pf_kernel's UF form: the kernel builds its patch
@@ -439,9 +393,9 @@ struct Builder {
         if (o.pre_mean || o.w_bs || o.wsp_bs || o.max_ksplit > 1 || o.resid || o.res3_w || o.stat_mean) return false;
         PfPlan plan;
         if (!pf_make_plan(ps, &plan)) return false;
-        Op op;
-        op.kind = Op::CONVPF; op.prof = prof; op.pfplan = plan; op.nz = 1;
-        PfArgs &a = op.pf;
+        PfConvOp op;
+        op.plan = plan; op.nz = 1;
+        PfArgs &a = op.a;
         memset(&a, 0, sizeof a);
         a.x0 = s0; a.x0_bs = bs0;
         a.C0 = a.Cin = 32; a.H = H; a.W = W;
@@ -456,7 +410,7 @@ struct Builder {
         epilogue(a, w, o);
         if (c4) { a.pre_add = c4; a.pre_c4 = 1; }
         const double px = (double)B * H * W;
-        return finish(op, 2.0 * px * w.Cout * w.Cin * 7, 4.0 * ((double)B * 3 * H * W + px * w.Cout), a.out == nullptr);
+        return finish(prof, op, 2.0 * px * w.Cout * w.Cin * 7, 4.0 * ((double)B * 3 * H * W + px * w.Cout), a.out == nullptr);
     }
 
     // Pointwise convolutions at the >= 32-pixel-wide levels on conv_pw_kernel (fp16 arithmetic): activations staged
@@ -475,9 +429,9 @@ struct Builder {
             fprintf(stderr, "[plan] conv1x1 PW Cin=%4d Cout=%4d out=%3dx%-3d %s%s| MB=%d NPW=%d WM=%d WP=%d groups=%d R=%d wgs=%d lds=%zu\n", w.Cin, w.Cout,
                     H, W, o.pre_mean ? "pre2 " : "", o.wsp_bs ? "per-image " : "", plan.MB, plan.NPW, plan.WM, plan.WP, plan.groups, plan.ring,
                     plan.tiles_x * plan.tiles_y * B * plan.groups, plan.lds_bytes);
-        Op op;
-        op.kind = Op::CONVPF; op.prof = prof; op.pfplan = plan; op.nz = 1; op.pw = true;
-        PfArgs &a = op.pf;
+        PwConvOp op;
+        op.plan = plan;
+        PfArgs &a = op.a;
         memset(&a, 0, sizeof a);
         a.x0 = s0; a.x0_bs = bs0; a.x1 = s1; a.x1_bs = bs1;
         a.C0 = s1 ? C0 : w.Cin; a.Cin = w.Cin; a.H = H; a.W = W;
@@ -492,7 +446,7 @@ struct Builder {
         if (o.emit_pf && !plan.lin && (w.Cout % 32) == 0 && bind_out_pf(a, w, out, out_bs, H, W) && o.no_f32) a.out = nullptr;
         epilogue(a, w, o);
         const double px = (double)B * H * W;
-        return finish(op, 2.0 * px * w.Cout * w.Cin, 4.0 * ((double)B * w.Cin * H * W + px * w.Cout), a.out == nullptr);
+        return finish(prof, op, 2.0 * px * w.Cout * w.Cin, 4.0 * ((double)B * w.Cin * H * W + px * w.Cout), a.out == nullptr);
     }
 
     // 3x3 / stride-1 / pad-1 layer of a few-pixel level on conv_ws_kernel (conv_ws_kernel.h): the RAW result (bias added, no LayerNorm)
@@ -507,13 +461,12 @@ struct Builder {
     }
     bool try_ws(const ConvW &w, const float *s0, int C0, long long bs0, const float *s1, long long bs1, int H, int W, float *raw,
                 long long raw_bs, int prof, const float *pre_add = nullptr) {
-        Op op;
-        op.kind = Op::CONVWS; op.prof = prof;
-        if (rc || !ws_would_plan(w, C0, s1 != nullptr, H, W, &op.wsplan)) return false;
+        WsConvOp op;
+        if (rc || !ws_would_plan(w, C0, s1 != nullptr, H, W, &op.plan)) return false;
         if (!ensure_f32(s0, bs0) || (s1 && !ensure_f32(s1, bs1))) return false;
         const int Ho = H / w.stride, Wo = W / w.stride;
         if (raw_bs != (long long)w.Cout * Ho * Wo) return false;
-        WsArgs &a = op.ws;
+        WsArgs &a = op.a;
         memset(&a, 0, sizeof a);
         a.x0 = s0; a.x0_bs = bs0; a.x1 = s1; a.x1_bs = bs1;
         a.C0 = s1 ? C0 : w.Cin; a.Cin = w.Cin; a.H = Ho; a.B = B;
@@ -524,9 +477,9 @@ struct Builder {
         a.fault = fault_flag();
         if (debug_plan())
             fprintf(stderr, "[plan] conv 3x3 s%d %d->%d out %dx%d on conv_ws_kernel: %d tiles of %d pixels x %d groups, %d waves, %zu bytes of LDS\n", w.stride, w.Cin, w.Cout, Ho, Wo,
-                    op.wsplan.tiles, op.wsplan.NPB * 32, op.wsplan.groups, op.wsplan.waves, op.wsplan.lds_bytes);
+                    op.plan.tiles, op.plan.NPB * 32, op.plan.groups, op.plan.waves, op.plan.lds_bytes);
         const double px = (double)B * Ho * Wo;
-        return finish(op, 2.0 * px * w.Cout * w.Cin * 9, 4.0 * ((double)B * H * W * w.Cin + px * w.Cout), false);
+        return finish(prof, op, 2.0 * px * w.Cout * w.Cin * 9, 4.0 * ((double)B * H * W * w.Cin + px * w.Cout), false);
     }
 
     // 1x1 layer of a few-pixel launch (at most 128 pixel blocks, or per-image weights) on conv_ws1_kernel (conv_ws1_kernel.h): all of K inside the
@@ -551,11 +504,11 @@ struct Builder {
         const int max_groups_wide = dev_env("CDC_WS1_MAX_GROUPS") ? atoi(dev_env("CDC_WS1_MAX_GROUPS")) : 0;
         const bool wide_ok = blocks <= max_blocks || (max_groups_wide > 0 && blocks <= 256 && w.Cout / 32 <= max_groups_wide);
         if (!wide_ok && !(o.wsp_bs && W < 32)) return false;     // (per-image products of the few-pixel levels at any batch)
-        Op op;
-        op.kind = Op::CONVWS1; op.prof = prof;
-        if (!ws1_make_plan(w.Cin, s1 ? C0 : w.Cin, w.Cout, H * W, pb(), o.wsp_bs != 0, &op.ws1plan)) return false;
+        Ws1ConvOp op;
+        op.H = H;
+        if (!ws1_make_plan(w.Cin, s1 ? C0 : w.Cin, w.Cout, H * W, pb(), o.wsp_bs != 0, &op.plan)) return false;
         if (!ensure_f32(s0, bs0) || (s1 && !ensure_f32(s1, bs1)) || (o.resid && !ensure_f32(o.resid, o.resid_bs))) return false;
-        Ws1Args &a = op.ws1;
+        Ws1Args &a = op.a;
         memset(&a, 0, sizeof a);
         a.x0 = s0; a.x0_bs = bs0; a.x1 = s1; a.x1_bs = bs1;
         a.C0 = s1 ? C0 : w.Cin; a.Cin = w.Cin; a.HW = H * W; a.B = B;
@@ -571,10 +524,9 @@ struct Builder {
         a.fault = fault_flag();
         if (debug_plan())
             fprintf(stderr, "[plan] conv 1x1 %d->%d out %dx%d on conv_ws1_kernel: %d tiles of %d pixels x %d groups, %d waves%s%s\n", w.Cin, w.Cout, H, W,
-                    op.ws1plan.tiles, op.ws1plan.NPB * 32, op.ws1plan.groups, op.ws1plan.waves, o.pre_mean ? ", folded PreNorm" : "", o.wsp_bs ? ", per-image weights" : "");
-        ws1_h = H;
+                    op.plan.tiles, op.plan.NPB * 32, op.plan.groups, op.plan.waves, o.pre_mean ? ", folded PreNorm" : "", o.wsp_bs ? ", per-image weights" : "");
         const double px = (double)B * H * W;
-        return finish(op, 2.0 * px * w.Cout * w.Cin, 4.0 * px * (w.Cin + w.Cout), false);
+        return finish(prof, op, 2.0 * px * w.Cout * w.Cin, 4.0 * px * (w.Cin + w.Cout), false);
     }
 
     // Emits one convolution.  s1 (optional) is the second concat source.  Returns false when
@@ -665,9 +617,9 @@ struct Builder {
                     s.lnmode ? (s.lnmode == 2 ? "pre2 " : "pre1 ") : "     ", cur == &h->pre_ops ? "HOIST " : "", plan.MB, plan.NPW, plan.WN,
                     plan.groups, plan.KC, plan.nchunk, plan.tiles_x, plan.tiles_y,
                     plan.tiles_x * plan.tiles_y * B * plan.groups * w.nz, plan.lds_bytes);
-        Op op;
-        op.kind = Op::CONV; op.prof = prof; op.plan = plan; op.nz = w.nz;
-        ConvArgs &a = op.conv;
+        ConvOp op;
+        op.plan = plan; op.nz = w.nz;
+        ConvArgs &a = op.a;
         memset(&a, 0, sizeof a);
         a.src0 = s0; a.src1 = s1; a.src0_bs = bs0; a.src1_bs = bs1;
         a.C0 = s1 ? C0 : w.Cin; a.Cin = w.Cin; a.H = H; a.W = W;
@@ -690,18 +642,13 @@ struct Builder {
             last_pf_only = o.no_f32;
         }
         const double px = (double)B * s.Ho * s.Wo * w.nz;
-        op.flops = 2.0 * px * w.Cout * w.Cin * w.KH * w.KW;
-        op.bytes = 4.0 * ((double)B * w.Cin * H * W + px * w.Cout);
         if (ks_scratch) {
             a.out = ks_scratch; a.out_bs = dense_bs; a.out_ks = (long long)B * dense_bs;
         }
-        emit(op);
+        emit(Op(prof, op, 2.0 * px * w.Cout * w.Cin * w.KH * w.KW, 4.0 * ((double)B * w.Cin * H * W + px * w.Cout)));
         if (ks_scratch) {
-            Op c; c.kind = Op::COPY; c.prof = prof;
-            c.cp = {ks_scratch, dense_bs, out, out_bs, dense_bs};
-            c.cp_parts = plan.ksplit; c.cp_part_stride = (long long)B * dense_bs;
-            c.bytes = 4.0 * B * dense_bs * (plan.ksplit + 1);
-            emit(c);
+            emit(Op(prof, CopyArgs{ks_scratch, dense_bs, out, out_bs, dense_bs, plan.ksplit, (long long)B * dense_bs}, 0,
+                    4.0 * B * dense_bs * (plan.ksplit + 1)));
             // split-K epilogues cannot emit planes (partial sums): pack the reduced tensor where a reader wants them
             if (o.emit_pf && !w.transposed && out_twin(out, out_bs, w.Cout, s.Ho, s.Wo)) pack(out, out_bs);
         }
@@ -711,22 +658,16 @@ struct Builder {
     void ln(const float *in, float *out, int C, int HW, const float *g, const float *b, int relu,
             const float *shift, const float *resid, float *sm, float *sr, int nparts = 1) {
         if (rc) return;
-        Op op;
-        op.kind = Op::LN; op.prof = PC_LN;
-        LnArgs &a = op.ln;
+        LnArgs a = {};
         a.nparts = nparts; a.part_stride = (long long)B * C * HW;
         a.in = in; a.out = out; a.C = C; a.HW = HW; a.g = g; a.b = b; a.eps = 1e-5f; a.relu = relu;
         a.shift = shift; a.shift_bs = h->shift_bs; a.resid = resid; a.stat_mean = sm; a.stat_rstd = sr;
         a.fault = fault_flag();
-        op.bytes = 4.0 * B * C * HW * (out ? 2 : 1);
-        emit(op);
+        emit(Op(PC_LN, a, 0, 4.0 * B * C * HW * (out ? 2 : 1)));
     }
 
     void copy(const float *src, long long src_bs, float *dst, long long dst_bs, long long n) {
-        Op c; c.kind = Op::COPY; c.prof = PC_SMALL;
-        c.cp = {src, src_bs, dst, dst_bs, n};
-        c.bytes = 8.0 * B * n;
-        emit(c);
+        emit(Op(PC_SMALL, CopyArgs{src, src_bs, dst, dst_bs, n}, 0, 8.0 * B * n));
     }
 
     // Fused LayerNorm epilogue needs every output channel in one workgroup; at few-pixel levels that
@@ -857,10 +798,7 @@ struct Builder {
                       nullptr, nullptr, prof1, h1_pf_only, a0.C, rb.k / 2)) {
             } else if (rb.has_unfold && (W & 3) == 0) {
                 Act u = new_act(a0.C * rb.k, H, W, false);
-                Op uo; uo.kind = Op::UNFOLD; uo.prof = prof1;
-                uo.uf = {a0.p, a0.bs(), u.p, u.bs(), a0.C, rb.k, rb.k / 2, H, W};
-                uo.bytes = 4.0 * B * (a0.C + u.C) * HW;
-                emit(uo);
+                emit(Op(prof1, UnfoldArgs{a0.p, a0.bs(), u.p, u.bs(), a0.C, rb.k, rb.k / 2, H, W}, 0, 4.0 * B * (a0.C + u.C) * HW));
                 block(rb.c1u, u.p, u.C, u.bs(), nullptr, 0, H, W, h1, rb.g1, rb.b1, shift, p1.p, nullptr, 0,
                       nullptr, nullptr, prof1, h1_pf_only);
             } else
@@ -915,10 +853,7 @@ struct Builder {
     void vbr(const Act &a, const VbrW &w, bool leaky) {
         if (rc) return;
         if (twin(a.p) || w.C != a.C || !h->d_rate) { rc = fail(h, CDC_ERR_INVALID, "VBR site %dx%dx%d: bad program", a.C, a.H, a.W); return; }
-        Op op; op.kind = Op::VBR; op.prof = PC_SMALL;
-        op.vb = {a.p, a.bs(), a.C, a.H * a.W, h->d_rate, w.p, leaky ? 1 : 0};
-        op.bytes = 8.0 * B * a.C * a.H * a.W;
-        emit(op);
+        emit(Op(PC_SMALL, VbrArgs{a.p, a.bs(), a.C, a.H * a.W, h->d_rate, w.p, leaky ? 1 : 0}, 0, 8.0 * B * a.C * a.H * a.W));
     }
     // GDN1 / inverse GDN1 (network_components.py:381-412) over x -> y, one fused pass (gdn_kernels.hip); beta / gamma reparametrised
     void gdn(const GdnW &w, const float *x, long long x_bs, float *y, long long y_bs, int HW) {
@@ -928,11 +863,8 @@ struct Builder {
             return;
         }
         if (x == y || HW < 1) { rc = fail(h, CDC_ERR_INVALID, "GDN C=%d HW=%d: bad program", w.C, HW); return; }
-        Op op; op.kind = Op::GDN; op.prof = PC_GDN;
-        op.gdn = {x, x_bs, y, y_bs, w.beta, w.gamma, w.C, HW, w.inverse ? 1 : 0, fault_flag()};
-        op.flops = 2.0 * B * HW * w.C * w.C;
-        op.bytes = 8.0 * B * w.C * HW;
-        emit(op);
+        emit(Op(PC_GDN, GdnArgs{x, x_bs, y, y_bs, w.beta, w.gamma, w.C, HW, w.inverse ? 1 : 0, fault_flag()}, 2.0 * B * HW * w.C * w.C,
+                8.0 * B * w.C * HW));
     }
     // after the block() call that produced `a`: if it wrote planes only, say so on the twin (its readers must take planes) and on the Act
     void mark_planes_only(Act &a) {
@@ -978,25 +910,13 @@ struct Builder {
         float *T1 = fold ? dalloc((size_t)B * C * C) : nullptr;
         float *biasB = fold ? dalloc((size_t)B * C) : nullptr;
         if (rc) return Act();
-        Op k; k.kind = Op::KSTATS; k.prof = PC_SMALL;
-        k.at = {kp, vp, fused ? 0 : qkv.bs(), C, N, kmax, ksum, S, ctxw, nsplit, Cin_pad, COP,
-                1.0f / sqrtf((float)C), at.WoT, at.WqT, T1, at.ng, at.uq, at.out.bias, biasB};
-        k.bytes = 8.0 * B * C * N;
         if (fused) {
-            Op f; f.kind = Op::KVCTX; f.prof = PC_ATTN_CTX;
-            f.kvc = {x.p, x.bs(), sm, sr, at.kvWt, at.kvb, at.kvWs, C, N, nsplit, S, ksum, kmaxs};
-            if (h->arith == 1 && at.kvWh) { f.kvc.Ws = at.kvWh; f.kvc.f16 = 1; f.kvc.wscale_inv = at.kv_scale_inv; }
-            f.flops = 6.0 * B * (double)C * C * N; f.bytes = 4.0 * B * C * N;
-            emit(f);
+            KvCtxArgs f = {x.p, x.bs(), sm, sr, at.kvWt, at.kvb, at.kvWs, C, N, nsplit, S, ksum, kmaxs};
+            if (h->arith == 1 && at.kvWh) { f.Ws = at.kvWh; f.f16 = 1; f.wscale_inv = at.kv_scale_inv; }
+            emit(Op(PC_ATTN_CTX, f, 6.0 * B * (double)C * C * N, 4.0 * B * C * N));
         }
         // few-pixel levels (not folded): kstats + partial context + reduction as ONE launch (round 4; the chain is latency-bound)
         const bool ctx_one = !fused && !fold && (N & 3) == 0 && N <= 1024 && (C % 64) == 0 && Cin_pad == C && COP == C && !dev_env("CDC_NO_CTX_ONE");
-        if (!fused && !ctx_one) {
-            emit(k);
-            Op p = k; p.kind = Op::CTXP; p.prof = PC_ATTN_CTX;
-            p.flops = 2.0 * B * (double)C * C * N; p.bytes = 8.0 * B * C * N;
-            emit(p);
-        }
         // folded output as one streaming pass (lnconv_kernel) where the level is wide enough to be bandwidth-bound
         const bool stream_out = fold && (C == 64 || C == 192) && N >= 4096 && N % 1024 == 0;
         // folded output as a 1x1 split convolution with per-image planes (C % 16 == 0, planes layout = the A-operand
@@ -1017,15 +937,20 @@ struct Builder {
         { Act ts; ts.p = ksum; ts.C = nsplit; ts.H = 1; ts.W = C; h->taps[at.prefix + ".Z"] = ts; }
         { Act ts; ts.p = kmax; ts.C = 1; ts.H = 1; ts.W = C; h->taps[at.prefix + ".kmax"] = ts; }
         { Act ts; ts.p = ctxw; ts.C = 1; ts.H = Cin_pad; ts.W = COP; h->taps[at.prefix + ".M"] = ts; }
-        Op r = k; r.kind = fold ? Op::CTXF : Op::CTXR; r.prof = PC_SMALL;
-        r.at_M = kmaxs; r.at_Ws = Ws; r.at_ws_f16 = planes_f16 ? 1 : 0; r.at_Wq = at.Wq;
-        r.bytes = 4.0 * B * nsplit * C * C;
-        r.flops = fold ? 4.0 * B * (double)C * C * C : 0.0;
+        // the context chain of the level, from one argument block
+        const AttnCtxArgs ca = {kp, vp, fused ? 0 : qkv.bs(), C, N, kmax, ksum, S, ctxw, nsplit, Cin_pad, COP, 1.0f / sqrtf((float)C),
+                                at.WoT, at.WqT, T1, at.ng, at.uq, at.out.bias, biasB, kmaxs, Ws, planes_f16 ? 1 : 0, at.Wq, h->arith == 1};
+        const double ctx_flops = 2.0 * B * (double)C * C * N, ctx_bytes = 8.0 * B * C * N;
         if (ctx_one) {
-            r.kind = Op::CTXP; r.prof = PC_ATTN_CTX; r.at_one = 1;
-            r.flops = 2.0 * B * (double)C * C * N; r.bytes = 8.0 * B * C * N;
+            emit(Op(PC_ATTN_CTX, CtxOneOp{ca}, ctx_flops, ctx_bytes));
+        } else {
+            if (!fused) {
+                emit(Op(PC_SMALL, KstatsOp{ca}, 0, ctx_bytes));
+                emit(Op(PC_ATTN_CTX, CtxPartialOp{ca}, ctx_flops, ctx_bytes));
+            }
+            if (fold) emit(Op(PC_SMALL, CtxFoldOp{ca}, 4.0 * B * (double)C * C * C, 4.0 * B * nsplit * C * C));
+            else emit(Op(PC_SMALL, CtxReduceOp{ca}, 0, 4.0 * B * nsplit * C * C));
         }
-        emit(r);
         ConvW cw;    // per-image weights produced above
         cw.Cin = C; cw.Cout = C; cw.KH = cw.KW = 1; cw.stride = 1; cw.pad = 0;
         cw.Cin_pad = Cin_pad; cw.COP = COP; cw.wp = ctxw; cw.nz = 1; cw.bias = nullptr;
@@ -1035,14 +960,12 @@ struct Builder {
             if (planes_f16) { cw.wsh = Ws; cw.wscale_inv = 1.0f / 256.0f; }
         }
         if (stream_out && !split_out) {
-            Op f; f.kind = Op::LNCONV; f.prof = PC_CONV1;
             int ns = std::max(1, ceil_div(2048, B));
             while (ns > 1 && N % (32 * ns)) --ns;
-            f.lnc = {x.p, x.bs(), sm, sr, Ws, biasB, y.p, y.bs(), C, N, ns};
+            LnConvArgs f = {x.p, x.bs(), sm, sr, Ws, biasB, y.p, y.bs(), C, N, ns};
             if (PfTwin *ty = twin(y.p))
-                if ((W % 32) == 0) { f.lnc.y_pf = ty->p; f.lnc.pf_bs = ty->bs(); f.lnc.pf_ps = ty->ps(); f.lnc.W = W; ty->valid = true; }
-            f.flops = 2.0 * B * (double)C * C * N; f.bytes = 12.0 * B * C * N;
-            emit(f);
+                if ((W % 32) == 0) { f.y_pf = ty->p; f.pf_bs = ty->bs(); f.pf_ps = ty->ps(); f.W = W; ty->valid = true; }
+            emit(Op(PC_CONV1, f, 2.0 * B * (double)C * C * N, 12.0 * B * C * N));
             return y;
         }
         if (fold) {
@@ -1108,11 +1031,8 @@ int build_program(cdc_handle *h, int B, int H, int W) {
     for (int l = 0; l < n_ctx; ++l) h->in_ctx.push_back(bd.new_act(h->context_dims[l], H >> l, W >> l, false));
     if (bd.rc) return bd.rc;
 
-    Op t; t.kind = Op::TEMB; t.prof = PC_SMALL;
-    t.temb.time = h->in_time; t.temb.w0 = h->tm_w0; t.temb.b0 = h->tm_b0; t.temb.w2 = h->tm_w2;
-    t.temb.b2 = h->tm_b2; t.temb.dim = h->cfg.dim; t.temb.layers = h->d_temb_layers;
-    t.temb.n_layers = (int)h->rbs.size(); t.temb.shift = h->shift; t.temb.shift_bs = h->shift_bs;
-    bd.emit(t);
+    bd.emit(Op(PC_SMALL, TembArgs{h->in_time, h->tm_w0, h->tm_b0, h->tm_w2, h->tm_b2, h->cfg.dim, h->d_temb_layers, (int)h->rbs.size(),
+                                  h->shift, h->shift_bs}));
 
     Act x; x.p = h->in_x; x.C = h->cfg.channels; x.H = H; x.W = W;
     std::vector<Act> skips;
@@ -1152,7 +1072,7 @@ int build_program(cdc_handle *h, int B, int H, int W) {
             const ResBlockW &nrb = h->rbs[rbi];
             Builder::ConvOpts od; od.emit_pf = bd.pf_would_plan(nrb.hoist_cx ? nrb.c1x : nrb.c1, y.H, y.W);
             bd.conv(dw, x.p, x.C, x.bs(), nullptr, 0, x.H, x.W, y.p, y.bs(), od, false, PC_DOWN);
-            if (x.pf && bd.still_planes_only(x.p) && (h->ops.empty() || h->ops.back().kind != Op::CONVPF || h->ops.back().pw))
+            if (x.pf && bd.still_planes_only(x.p) && (h->ops.empty() || !h->ops.back().on_conv_pf_kernel()))
                 return fail(h, CDC_ERR_UNSUPPORTED, "planes-only Downsample input without a plane-operand kernel");
             x = y;
             h->taps[dn + ".3"] = x;
@@ -1227,7 +1147,7 @@ int build_program(cdc_handle *h, int B, int H, int W) {
         }
         if (x_planes_only && bd.still_planes_only(x.p)) {
             bool on_pf = false;
-            for (size_t q = ops_before; q < h->ops.size(); ++q) on_pf = on_pf || (h->ops[q].kind == Op::CONVPF && !h->ops[q].pw);
+            for (size_t q = ops_before; q < h->ops.size(); ++q) on_pf = on_pf || h->ops[q].on_conv_pf_kernel();
             if (!on_pf) return fail(h, CDC_ERR_UNSUPPORTED, "planes-only Upsample input without a plane-operand kernel");
         }
         x = y;
@@ -1249,12 +1169,9 @@ int build_program(cdc_handle *h, int B, int H, int W) {
     of.no_bias = true;
     bd.conv(h->fin_conv, x.p, x.C, x.bs(), nullptr, 0, H, W, h->fin_P, (long long)h->out_dim * KHf * H * W,
             of, false, PC_CONV7);
-    if (x.pf && !bd.rc && bd.still_planes_only(x.p) && (h->ops.empty() || h->ops.back().kind != Op::CONVPF || h->ops.back().pw))
+    if (x.pf && !bd.rc && bd.still_planes_only(x.p) && (h->ops.empty() || !h->ops.back().on_conv_pf_kernel()))
         return fail(h, CDC_ERR_UNSUPPORTED, "planes-only final-convolution input without a plane-operand kernel");
-    Op cb; cb.kind = Op::COMBINE; cb.prof = PC_SMALL;
-    cb.cb = {h->fin_P, h->fin_bias, h->out_fx, h->out_dim, KHf, 3, H, W};
-    cb.bytes = 4.0 * B * h->out_dim * (KHf + 1) * H * W;
-    bd.emit(cb);
+    bd.emit(Op(PC_SMALL, CombineArgs{h->fin_P, h->fin_bias, h->out_fx, h->out_dim, KHf, 3, H, W}, 0, 4.0 * B * h->out_dim * (KHf + 1) * H * W));
     if (bd.rc) return bd.rc;
     h->pB = B; h->pH = H; h->pW = W;
     return CDC_OK;
@@ -1481,10 +1398,7 @@ int build_lpips_program(cdc_handle *h, int pairs, int H, int W) {
         if (l) {
             Act y = bd.new_act(x.C, x.H / 2, x.W / 2, false);
             if (bd.rc) return bd.rc;
-            Op op; op.kind = Op::MAXPOOL; op.prof = PC_SMALL;
-            op.mp = {x.p, y.p, x.C, x.H, x.W};
-            op.bytes = 4.0 * B * x.C * ((double)x.H * x.W + (double)y.H * y.W);
-            bd.emit(op);
+            bd.emit(Op(PC_SMALL, MaxpoolArgs{x.p, y.p, x.C, x.H, x.W}, 0, 4.0 * B * x.C * ((double)x.H * x.W + (double)y.H * y.W)));
             x = y;
         }
         for (int k = 0; k < kVggLevelConvs[l]; ++k, ++layer) {
@@ -1508,10 +1422,8 @@ int build_lpips_program(cdc_handle *h, int pairs, int H, int W) {
             x = y;
         }
         h->taps["relu" + std::to_string(l + 1) + "_" + std::to_string(kVggLevelConvs[l])] = x;
-        Op op; op.kind = Op::LPHEAD; op.prof = PC_SMALL;
-        op.lh = {x.p, x.bs(), x.C, x.H * x.W, h->lp_lin[l], partials, h->lp_res, l, bd.fault_flag()};
-        op.bytes = 2.0 * 4.0 * B * x.C * x.H * x.W;
-        bd.emit(op);
+        bd.emit(Op(PC_SMALL, LpipsHeadArgs{x.p, x.bs(), x.C, x.H * x.W, h->lp_lin[l], partials, h->lp_res, l, bd.fault_flag()}, 0,
+                   2.0 * 4.0 * B * x.C * x.H * x.W));
         if (bd.rc) return bd.rc;
     }
     h->pB = B; h->pH = H; h->pW = W;
@@ -1624,12 +1536,12 @@ static int op_conv2d_impl(cdc_handle *h, const float *x, const float *w, const f
     // test aid: the layer must have been planned on the plane-operand kernel (a silent fallback would test nothing)
     if (dev_env("CDC_OP_REQUIRE_PF")) {
         bool on_pf = false;
-        for (const Op &q : h->ops) on_pf = on_pf || (q.kind == Op::CONVPF && !q.pw);
+        for (const Op &q : h->ops) on_pf = on_pf || q.on_conv_pf_kernel();
         if (!on_pf) return fail(h, CDC_ERR_UNSUPPORTED, "CDC_OP_REQUIRE_PF: the convolution was not planned on conv_pf_kernel");
     }
     if (dev_env("CDC_OP_REQUIRE_WS")) {       // ... or on the weight-stationary kernel of the few-pixel levels
         bool on_ws = false;
-        for (const Op &q : h->ops) on_ws = on_ws || q.kind == Op::CONVWS;
+        for (const Op &q : h->ops) on_ws = on_ws || q.get<WsConvOp>();
         if (!on_ws) return fail(h, CDC_ERR_UNSUPPORTED, "CDC_OP_REQUIRE_WS: the convolution was not planned on conv_ws_kernel");
     }
     return sc.run(B, y, dy, (size_t)B * Cout * Ho * Wo);
@@ -1658,7 +1570,7 @@ static int op_conv_transpose2d_impl(cdc_handle *h, const float *x, const float *
     if (bd.rc) return bd.rc;
     if (dev_env("CDC_OP_REQUIRE_PF")) {       // test aid, see op_conv2d_impl
         bool on_pf = false;
-        for (const Op &q : h->ops) on_pf = on_pf || (q.kind == Op::CONVPF && !q.pw);
+        for (const Op &q : h->ops) on_pf = on_pf || q.on_conv_pf_kernel();
         if (!on_pf) return fail(h, CDC_ERR_UNSUPPORTED, "CDC_OP_REQUIRE_PF: the convolution was not planned on conv_pf_kernel");
     }
     return sc.run(B, y, dy, ny);

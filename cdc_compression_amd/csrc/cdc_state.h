@@ -15,6 +15,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <variant>
 #include <vector>
 
 #include "../../include/cdc_hip.h"
@@ -74,41 +75,110 @@ struct AttnW { std::string prefix; int C; ConvW qkv, out; float *ng, *nb;
                float *kvWt = nullptr, *kvb = nullptr; unsigned short *kvWs = nullptr;
                unsigned short *kvWh = nullptr; float kv_scale_inv = 1.f; };   // fp16 planes {WH, WL, WH2} of W' 2^s   // fused front half: (W_kv diag(g))^T [C][2C], W_kv b_ln [2C]   // folded output; uq = Wq b_ln
 
+// ---- launch program: an Op is a common header and exactly ONE payload (the argument block of one kernel entry, with its launch plan
+// where it has one).  Every payload type has two overloads, op_launch and op_label; run_op and Builder::emit visit them, so a new op
+// kind is one payload type and its two overloads -- leaving one out does not compile.
+struct ConvOp { ConvArgs a; ConvPlan plan; int nz; };          // register-staged convolution (conv_kernel.h, conv_split_kernel.h)
+struct PfConvOp { PfArgs a; PfPlan plan; int nz; };            // plane-operand convolution on conv_pf_kernel / conv_pf3_kernel
+struct PwConvOp { PfArgs a; PfPlan plan; };                    // pointwise convolution on conv_pw_kernel (activations from the fp32 tensor)
+struct WsConvOp { WsArgs a; WsPlan plan; };                    // weight-stationary 3x3 convolution of the few-pixel levels
+struct Ws1ConvOp { Ws1Args a; Ws1Plan plan; int H; };          // ... its 1x1 sibling (H: rows of the map, for the label)
+struct PfPackOp { const float *src; long long src_bs; void *dst; long long dst_bs; int C, H, W; };      // fp32 -> planes
+struct C4PackOp { const float *src; long long src_bs; float *dst; int C, H, W; };                       // fp32 -> accumulator order (PfArgs::pre_c4)
+struct PfUnpackOp { const void *planes; long long planes_bs; float *dst; long long dst_bs; int C, H, W; };   // planes -> fp32
+struct KstatsOp { AttnCtxArgs a; };                            // the attention context chain: one AttnCtxArgs, one type per launcher
+struct CtxPartialOp { AttnCtxArgs a; };
+struct CtxOneOp { AttnCtxArgs a; };
+struct CtxReduceOp { AttnCtxArgs a; };
+struct CtxFoldOp { AttnCtxArgs a; };
+using OpPayload = std::variant<ConvOp, PfConvOp, PwConvOp, WsConvOp, Ws1ConvOp, PfPackOp, C4PackOp, PfUnpackOp, LnArgs, TembArgs, KstatsOp,
+                               CtxPartialOp, CtxOneOp, CtxReduceOp, CtxFoldOp, KvCtxArgs, LnConvArgs, CombineArgs, DdimArgs, CopyArgs,
+                               UnfoldArgs, VbrArgs, MaxpoolArgs, LpipsHeadArgs, GdnArgs>;
+
 struct Op {
-    enum Kind { CONV, LN, TEMB, KSTATS, CTXP, CTXR, CTXF, COMBINE, DDIM, COPY, UNFOLD, KVCTX, LNCONV, CONVPF, PFPACK, CONVWS, CONVWS1, VBR, MAXPOOL, LPHEAD, GDN } kind;
-    int prof = PC_SMALL;
+    int prof;
     int id = -1;                  // index into cdc_handle::op_ms (per-op timing table, debug aid)
-    char label[96] = {0};
-    double flops = 0, bytes = 0;
-    ConvArgs conv; ConvPlan plan; int nz = 1;
-    PfArgs pf; PfPlan pfplan;     // CONVPF: pre-split fp16 operands by LDS-DMA (conv_pf_kernel.h)
-    WsArgs ws; WsPlan wsplan;     // CONVWS: weight-stationary 3x3 convolution of the few-pixel levels (conv_ws_kernel.h)
-    Ws1Args ws1; Ws1Plan ws1plan; // CONVWS1: its 1x1 sibling (conv_ws1_kernel.h)
-    bool pw = false;              // CONVPF on conv_pw_kernel (pointwise, activations from the fp32 tensor)
-    LnArgs ln;
-    TembArgs temb;
-    struct { const float *k, *v; long long bs; int C, N; float *kmax, *ksum, *S, *ctxw;
-             int nsplit, Cin_pad, COP; float scale; const float *WoT, *WqT; float *T1;
-             const float *ln_g, *ln_b, *b_out; float *biasB; } at;
-    struct { const float *P, *bias; float *out; int Cout, KH, pad, H, W; } cb;
-    DdimArgs ddim;
-    struct { const float *src; long long src_bs; float *dst; long long dst_bs, n; } cp;
-    int cp_parts = 1; long long cp_part_stride = 0;
-    const int *cp_step = nullptr; long long cp_step_stride = 0;   // COPY: source row selected by a device step index
-    KvCtxArgs kvc;
-    LnConvArgs lnc;
-    int at_ws_f16 = 0;                 // CTXF: the planes are fp16 {WH, WL, WH2} of M' 2^8 (split convolution) instead of bf16
-    unsigned short *at_Ws = nullptr;   // CTXF: also emit M' as bf16 planes for lnconv_kernel
-    const float *at_Wq = nullptr;      // CTXF: Wq [d][ci] (fold_r2_mfma_kernel)
-    const float *at_M = nullptr;  // CTXF after KVCTX: per-split row maxima   // COPY: dst = sum of cp_parts planes of src
-    int at_one = 0;                    // CTXP: row maxima, partial context and reduction in this ONE launch (ctx_one_launch)
-    struct { const float *src; long long src_bs; float *dst; long long dst_bs; int C, KW, pad, H, W; } uf;
-    struct { const float *src; long long src_bs; void *dst; long long dst_bs; int C, H, W; int c4; } pk;   // PFPACK (c4: fp32 -> accumulator order)
-    struct { float *x; long long bs; int C, HW; const float *rate, *p; int leaky; } vb;   // VBR: in-place VBRCondition (+ LeakyReLU 0.2)
-    struct { const float *src; float *dst; int C, H, W; } mp;                               // MAXPOOL: max_pool2d(2, 2), floor mode (lpips_kernels.hip)
-    GdnArgs gdn;                                                                            // GDN: GDN1 / inverse GDN1 (gdn_kernels.hip)
-    struct { const float *f; long long bs; int C, HW; const float *w; double *partials, *res; int layer; int *fault; } lh;   // LPHEAD: one LPIPS tap, run over B / 2 pairs
+    double flops, bytes;
+    OpPayload p;
+    template <class T> Op(int prof_, const T &payload, double flops_ = 0, double bytes_ = 0) : prof(prof_), flops(flops_), bytes(bytes_), p(payload) {}
+    template <class T> const T *get() const { return std::get_if<T>(&p); }      // the payload if the op is of that kind, else null
+    bool on_conv_pf_kernel() const { return get<PfConvOp>() != nullptr; }       // a plane-operand convolution on conv_pf_kernel
 };
+
+// B: the images of the call (LpipsHeadArgs: B rows = B / 2 pairs)
+inline hipError_t op_launch(const ConvOp &o, int B, hipStream_t st) { return conv_launch(o.a, o.plan, B, o.nz, st); }
+inline hipError_t op_launch(const PfConvOp &o, int B, hipStream_t st) { return pf_launch(o.a, o.plan, B, o.nz, st); }
+inline hipError_t op_launch(const PwConvOp &o, int B, hipStream_t st) { return pw_launch(o.a, o.plan, B, st); }
+inline hipError_t op_launch(const WsConvOp &o, int, hipStream_t st) { return ws_launch(o.a, o.plan, st); }
+inline hipError_t op_launch(const Ws1ConvOp &o, int, hipStream_t st) { return ws1_launch(o.a, o.plan, st); }
+inline hipError_t op_launch(const PfPackOp &o, int B, hipStream_t st) { return pf_pack_launch(o.src, o.src_bs, o.dst, o.dst_bs, o.C, o.H, o.W, B, st); }
+inline hipError_t op_launch(const C4PackOp &o, int B, hipStream_t st) { return c4_pack_launch(o.src, o.src_bs, o.dst, o.C, (long long)o.H * o.W, B, st); }
+inline hipError_t op_launch(const PfUnpackOp &o, int B, hipStream_t st) { return pf_unpack_launch(o.planes, o.planes_bs, o.dst, o.dst_bs, o.C, o.H, o.W, B, st); }
+inline hipError_t op_launch(const LnArgs &a, int B, hipStream_t st) { return ln_launch(a, B, st); }
+inline hipError_t op_launch(const TembArgs &a, int B, hipStream_t st) { return temb_launch(a, B, st); }
+inline hipError_t op_launch(const KstatsOp &o, int B, hipStream_t st) { return kstats_launch(o.a, B, st); }
+inline hipError_t op_launch(const CtxPartialOp &o, int B, hipStream_t st) { return ctx_partial_launch(o.a, B, st); }
+inline hipError_t op_launch(const CtxOneOp &o, int B, hipStream_t st) { return ctx_one_launch(o.a, B, st); }
+inline hipError_t op_launch(const CtxReduceOp &o, int B, hipStream_t st) { return ctx_reduce_launch(o.a, B, st); }
+inline hipError_t op_launch(const CtxFoldOp &o, int B, hipStream_t st) { return ctx_fold_launch(o.a, B, st); }
+inline hipError_t op_launch(const KvCtxArgs &a, int B, hipStream_t st) { return kvctx_launch(a, B, st); }
+inline hipError_t op_launch(const LnConvArgs &a, int B, hipStream_t st) { return lnconv_launch(a, B, st); }
+inline hipError_t op_launch(const CombineArgs &a, int B, hipStream_t st) { return fold_combine_launch(a, B, st); }
+inline hipError_t op_launch(const DdimArgs &a, int, hipStream_t st) { return ddim_launch(a, st); }
+inline hipError_t op_launch(const CopyArgs &a, int B, hipStream_t st) { return copy_channels_launch(a, B, st); }
+inline hipError_t op_launch(const UnfoldArgs &a, int B, hipStream_t st) { return unfold_x_launch(a, B, st); }
+inline hipError_t op_launch(const VbrArgs &a, int B, hipStream_t st) { return vbr_affine_launch(a, B, st); }
+inline hipError_t op_launch(const MaxpoolArgs &a, int B, hipStream_t st) { return maxpool2_launch(a, B, st); }
+inline hipError_t op_launch(const LpipsHeadArgs &a, int B, hipStream_t st) { return lpips_head_launch(a, B / 2, st); }
+inline hipError_t op_launch(const GdnArgs &a, int B, hipStream_t st) { return gdn_launch(a, B, st); }
+
+// The op's line of the per-op profile table (cdc_prof_op).  hoisted: the op belongs to the context-only part of the program; the
+// convolutions say so in the middle of their line, Builder::emit appends " HOIST" to every other hoisted op.
+inline void op_label(const ConvOp &o, char *buf, size_t n, bool hoisted) {
+    const ConvArgs &a = o.a; const ConvPlan &p = o.plan;
+    snprintf(buf, n, "conv %dx%d s%d %4d->%-4d out %3dx%-3d MB%d NPW%d WN%d g%d tg%d ipw%d ks%d%s%s%s%s%s", a.KH, a.KW, a.stride, a.Cin, a.Cout, a.Ho,
+             a.Wo, p.MB, p.NPW, p.WN, p.groups, p.tg, p.ipw, p.ksplit, p.split == 2 ? (p.arith ? " SPLIT2H" : " SPLIT2") : (p.split ? " SPLIT" : ""),
+             a.ep_g ? " LN" : "", a.ln_mean ? " pre" : "", hoisted ? " HOIST" : "", a.resid ? " +res" : "");
+}
+inline void pf_label(const PfArgs &a, const PfPlan &p, const char *kernel, char *buf, size_t n, bool hoisted) {
+    snprintf(buf, n, "conv %dx%d s%d %4d->%-4d out %3dx%-3d MB%d NPW%d WM%d WP%d g%d R%d %s%s%s%s%s%s", a.KH, a.KW, a.stride == 2 ? 2 : 1, a.Cin, a.Cout,
+             a.Ho, a.Wo, p.MB, p.NPW, p.WM, p.WP, p.groups, p.ring, kernel, a.out ? "" : " nof32", a.out_pf ? " +pf" : "",
+             a.resid ? " +res" : (a.resid_pf ? " +resP" : ""), hoisted ? " HOIST" : "", a.tz == 4 ? " TZ4" : "");
+}
+inline void op_label(const PfConvOp &o, char *buf, size_t n, bool hoisted) {
+    pf_label(o.a, o.plan, o.plan.pf3_epv ? (o.a.ep_g ? "PF3 LN" : "PF3") : (o.a.ep_g ? "PF LN" : "PF"), buf, n, hoisted);
+}
+inline void op_label(const PwConvOp &o, char *buf, size_t n, bool hoisted) { pf_label(o.a, o.plan, o.a.pre_mean ? "PW pre" : "PW", buf, n, hoisted); }
+inline void op_label(const WsConvOp &o, char *buf, size_t n, bool) {
+    snprintf(buf, n, "conv 3x3 s%d %4d->%-4d out %3dx%-3d NPB%d waves%d tiles%d g%d WS%s", o.plan.stride, o.a.Cin, o.a.Cout, o.a.H, o.plan.W, o.plan.NPB,
+             o.plan.waves, o.plan.tiles, o.plan.groups, o.a.pre_add ? " pre_add" : "");
+}
+inline void op_label(const Ws1ConvOp &o, char *buf, size_t n, bool) {
+    snprintf(buf, n, "conv 1x1 s1 %4d->%-4d out %3dx%-3d NPB%d waves%d tiles%d g%d WS1%s%s%s", o.a.Cin, o.a.Cout, o.H, o.a.HW / std::max(o.H, 1), o.plan.NPB,
+             o.plan.waves, o.plan.tiles, o.plan.groups, o.a.pre_mean ? " pre" : "", o.a.w_bs ? " perimg" : "",
+             o.a.resid ? (o.a.resid_is_pre ? " pre_add" : " +res") : "");
+}
+inline void op_label(const PfPackOp &, char *buf, size_t n, bool) { snprintf(buf, n, "pfpack"); }
+inline void op_label(const C4PackOp &, char *buf, size_t n, bool) { snprintf(buf, n, "pfpack"); }
+inline void op_label(const PfUnpackOp &, char *buf, size_t n, bool) { snprintf(buf, n, "pfunpack"); }
+inline void op_label(const LnArgs &a, char *buf, size_t n, bool) { snprintf(buf, n, "ln C=%d HW=%d%s", a.C, a.HW, a.out ? "" : " stats"); }
+inline void op_label(const TembArgs &, char *buf, size_t n, bool) { snprintf(buf, n, "temb"); }
+inline void ctx_label(const char *kind, const AttnCtxArgs &a, int nsplit, char *buf, size_t n) { snprintf(buf, n, "%s C=%d N=%d nsplit=%d", kind, a.C, a.N, nsplit); }
+inline void op_label(const KstatsOp &o, char *buf, size_t n, bool) { ctx_label("kstats", o.a, o.a.nsplit, buf, n); }
+inline void op_label(const CtxPartialOp &o, char *buf, size_t n, bool) { ctx_label("ctxp", o.a, o.a.nsplit, buf, n); }
+inline void op_label(const CtxOneOp &o, char *buf, size_t n, bool) { ctx_label("ctx1", o.a, 1, buf, n); }
+inline void op_label(const CtxReduceOp &o, char *buf, size_t n, bool) { ctx_label("ctxr", o.a, o.a.nsplit, buf, n); }
+inline void op_label(const CtxFoldOp &o, char *buf, size_t n, bool) { ctx_label("ctxf", o.a, o.a.nsplit, buf, n); }
+inline void op_label(const KvCtxArgs &a, char *buf, size_t n, bool) { snprintf(buf, n, "kvctx C=%d N=%d nsplit=%d", a.C, a.N, a.nsplit); }
+inline void op_label(const LnConvArgs &a, char *buf, size_t n, bool) { snprintf(buf, n, "lnconv C=%d N=%d nsplit=%d", a.C, a.N, a.nsplit); }
+inline void op_label(const CombineArgs &, char *buf, size_t n, bool) { snprintf(buf, n, "combine"); }
+inline void op_label(const DdimArgs &, char *buf, size_t n, bool) { snprintf(buf, n, "ddim"); }
+inline void op_label(const CopyArgs &, char *buf, size_t n, bool) { snprintf(buf, n, "copy"); }
+inline void op_label(const UnfoldArgs &, char *buf, size_t n, bool) { snprintf(buf, n, "unfold"); }
+inline void op_label(const VbrArgs &a, char *buf, size_t n, bool) { snprintf(buf, n, "vbr C=%d HW=%d%s", a.C, a.HW, a.leaky ? " leaky" : ""); }
+inline void op_label(const MaxpoolArgs &a, char *buf, size_t n, bool) { snprintf(buf, n, "maxpool2 C=%d in %dx%d", a.C, a.H, a.W); }
+inline void op_label(const LpipsHeadArgs &a, char *buf, size_t n, bool) { snprintf(buf, n, "lpips_head tap %d C=%d HW=%d", a.layer, a.C, a.HW); }
+inline void op_label(const GdnArgs &a, char *buf, size_t n, bool) { snprintf(buf, n, "gdn C=%d HW=%d%s", a.C, a.HW, a.inverse ? " inv" : ""); }
 
 struct GdnW { int C = 0; bool inverse = false; float *beta = nullptr, *gamma = nullptr; };   // one GDN1 layer: reparametrised beta' [C], gamma' [C][C] (device)
 struct VbrW { int C = 0; float *p = nullptr; };   // one VBRCondition site: [scale.weight | scale.bias | shift.weight | shift.bias], C each

@@ -209,7 +209,11 @@ hipError_t lpips_in_launch(const MetricView &a, const MetricView &b, int n, int 
     return hipGetLastError();
 }
 
-hipError_t maxpool2_launch(const float *in, float *out, long long planes, int H, int W, hipStream_t st) {
+hipError_t maxpool2_launch(const MaxpoolArgs &a, int B, hipStream_t st) {
+    const float *in = a.src;
+    float *out = a.dst;
+    const long long planes = (long long)B * a.C;
+    const int H = a.H, W = a.W;
     const int Ho = H / 2, Wo = W / 2;
     if (Ho < 1 || Wo < 1) return hipErrorInvalidValue;
     const bool vec = W % 8 == 0 && aligned(in, 16) && aligned(out, 16) && ((long long)H * W) % 4 == 0;
@@ -226,15 +230,14 @@ hipError_t maxpool2_launch(const float *in, float *out, long long planes, int H,
 static bool head_quads(int HW) { return HW % 4 == 0 && HW >= 32768; }
 int lpips_head_blocks(int HW) { return ceil_div(HW, 256 * (head_quads(HW) ? 4 : 1)); }
 
-hipError_t lpips_head_launch(const float *f, long long bs, int C, int HW, const float *w, int n, double *partials, double *res, int layer,
-                             int *fault, hipStream_t st) {
-    const bool vec = head_quads(HW);
-    if (vec && (bs % 4 != 0 || !aligned(f, 16))) return hipErrorInvalidValue;   // (the program's activations are dense and hipMalloc-aligned)
-    const int nblk = lpips_head_blocks(HW);
+hipError_t lpips_head_launch(const LpipsHeadArgs &a, int n, hipStream_t st) {
+    const bool vec = head_quads(a.HW);
+    if (vec && (a.bs % 4 != 0 || !aligned(a.f, 16))) return hipErrorInvalidValue;   // (the program's activations are dense and hipMalloc-aligned)
+    const int nblk = lpips_head_blocks(a.HW);
     const dim3 g((unsigned)nblk, (unsigned)n), blk(256);
-    if (vec) hipLaunchKernelGGL((lpips_head_kernel<4>), g, blk, 0, st, f, bs, C, HW, w, n, partials);
-    else hipLaunchKernelGGL((lpips_head_kernel<1>), g, blk, 0, st, f, bs, C, HW, w, n, partials);
-    hipLaunchKernelGGL(lpips_final_kernel, dim3((unsigned)ceil_div(n, 64)), dim3(64), 0, st, partials, nblk, n, (double)HW, res, layer, fault);
+    if (vec) hipLaunchKernelGGL((lpips_head_kernel<4>), g, blk, 0, st, a.f, a.bs, a.C, a.HW, a.w, n, a.partials);
+    else hipLaunchKernelGGL((lpips_head_kernel<1>), g, blk, 0, st, a.f, a.bs, a.C, a.HW, a.w, n, a.partials);
+    hipLaunchKernelGGL(lpips_final_kernel, dim3((unsigned)ceil_div(n, 64)), dim3(64), 0, st, a.partials, nblk, n, (double)a.HW, a.res, a.layer, a.fault);
     return hipGetLastError();
 }
 

@@ -1087,14 +1087,42 @@ def test_configs4_full_length_512_batch16_rows_match_batch1_decodes():
 TAPS = ["downs.0.0", "downs.0.2", "downs.1.3", "mid_block1", "ups.0"]
 
 
-def _op_labels(un):
+def _op_table(un):
+    """(labels, launches) of the per-op profile table of `un`'s launch program."""
     L, h = _lib.lib(), un._handle()
-    labels = []
+    labels, launches = [], []
     for i in range(L.cdc_prof_num_ops(h)):
         lab, ms, n, fl = ctypes.c_char_p(), ctypes.c_double(), ctypes.c_int64(), ctypes.c_double()
-        L.cdc_prof_op(h, i, ctypes.byref(lab), ctypes.byref(ms), ctypes.byref(n), ctypes.byref(fl))
+        assert L.cdc_prof_op(h, i, ctypes.byref(lab), ctypes.byref(ms), ctypes.byref(n), ctypes.byref(fl)) == 0
         labels.append(lab.value.decode())
-    return labels
+        launches.append(n.value)
+    return labels, launches
+
+
+def _op_labels(un):
+    return _op_table(un)[0]
+
+
+def test_every_op_of_the_program_is_launched_once_and_labelled():
+    """The launch program has one dispatch (run_op visits the op's payload) and one labelling (Builder::emit visits the same payload): one
+    profiled forward of the small x-param U-Net at its golden shape (batch 2, 32 x 32) must leave exactly one launch on every op the
+    planner registered, the hoisted context-only ones included, and every op must carry a label.  An op that was registered but skipped or
+    dispatched twice, or an id that no longer lines up with its label, shows here; no reference values are involved."""
+    kw, man, sd, x, t, ctx, _ = load_case("small_x")
+    un = cdc.Unet(**kw)
+    un.load_state_dict(sd)
+    L, h = _lib.lib(), un._handle()
+    L.cdc_prof_reset(h)
+    L.cdc_prof_enable(h, 1)
+    y = un(x, t, ctx)
+    n_ops = L.cdc_prof_num_ops(h)
+    labels, launches = _op_table(un)
+    L.cdc_prof_enable(h, 0)
+    assert np.isfinite(y).all()
+    assert n_ops == len(labels) and n_ops > 0
+    assert all(labels), labels
+    assert any(" HOIST" in l for l in labels), labels                  # the program has a context-only part, and it is in the table
+    assert launches == [1] * n_ops, [(l, n) for l, n in zip(labels, launches) if n != 1]
 
 
 def test_planes_only_tensor_reaching_an_fp32_reader_is_unpacked_not_a_build_error(monkeypatch):
