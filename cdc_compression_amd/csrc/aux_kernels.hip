@@ -1542,6 +1542,119 @@ hipError_t ddim_launch(const DdimArgs &a, hipStream_t st) {
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------
+// Second-order multistep update (DPM-Solver++ 2M in data-prediction form; SolverArgs, include/cdc_hip.h).  Kernels of their own
+// beside the DDIM pair, which keeps its code: the same prediction x0 (ddim_update's expressions, clip included), then
+// x_next = ((a x) + (b x0)) + (c x0_prev) with every product and sum rounded on its own (fp contract off, so the scalar and the
+// four-pixel form hold the same bits), and x0 written over x0_prev by the thread that read it.  20 bytes per element where fx
+// is a tensor; bound by memory.
+// ---------------------------------------------------------------------------------------------
+struct SolverConsts { float c_recip, c_recipm1, c_sac, c_s1mac, a, b, c; int pred_mode; };
+__device__ __forceinline__ SolverConsts solver_consts(const SolverArgs &a) {
+    const int si = a.step_ptr ? *a.step_ptr : a.i;
+    return {a.tab[0 * a.steps + si], a.tab[1 * a.steps + si], a.tab_v ? a.tab_v[si] : 0.f, a.tab_v ? a.tab_v[a.steps + si] : 0.f,
+            a.stab[0 * a.steps + si], a.stab[1 * a.steps + si], a.stab[2 * a.steps + si], a.pred_mode};
+}
+__device__ __forceinline__ float solver_x0(const SolverConsts &k, float fx, float x, bool clip) {
+#pragma clang fp contract(off)
+    float x0;
+    if (k.pred_mode == 0) x0 = fx;
+    else if (k.pred_mode == 3) x0 = k.c_sac * x - k.c_s1mac * fx;
+    else x0 = k.c_recip * x - k.c_recipm1 * fx;
+    if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    return x0;
+}
+__device__ __forceinline__ float solver_next(const SolverConsts &k, float x, float x0, float x0_prev) {
+#pragma clang fp contract(off)
+    const float t0 = k.a * x, t1 = k.b * x0, t2 = k.c * x0_prev;
+    return (t0 + t1) + t2;
+}
+
+__global__ void __launch_bounds__(256) solver_kernel(const SolverArgs a) {
+    const SolverConsts kc = solver_consts(a);
+    const long long clip_n = a.clip == 1 ? a.n : (a.clip == 2 ? a.clip_half_n : 0);
+    bool bad = false;
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < a.n;
+         idx += (long long)gridDim.x * blockDim.x) {
+        float fx;
+        if (a.P) {
+            const long long plane = (long long)a.pH * a.pW, img_co = idx / plane;      // = b * Cout + co
+            const int pix = (int)(idx - img_co * plane), y = pix / a.pW;
+            const float *p = a.P + (size_t)img_co * a.pKH * plane + pix;
+            fx = a.P_bias ? a.P_bias[(int)(img_co % a.pC)] : 0.f;
+            for (int ky = 0; ky < a.pKH; ++ky) {
+                const int r = y + ky - a.pPad;
+                if (r >= 0 && r < a.pH) fx += p[(size_t)ky * plane + (long long)(ky - a.pPad) * a.pW];
+            }
+        } else {
+            fx = a.fx[idx];
+        }
+        bad |= !(fabsf(fx) <= 3.0e38f);
+        const float x = a.x[idx];
+        const float x0 = solver_x0(kc, fx, x, idx < clip_n);
+        a.x_next[idx] = solver_next(kc, x, x0, a.hist[idx]);
+        a.hist[idx] = x0;
+    }
+    if (bad && a.fault) *a.fault = 1;
+}
+
+// Four consecutive pixels of one (image, channel) plane per thread (pW % 4 == 0), 16-byte accesses, blockIdx.y = the plane.
+__global__ void __launch_bounds__(256) solver_rows4_kernel(const SolverArgs a) {
+    const SolverConsts kc = solver_consts(a);
+    const long long clip_n = a.clip == 1 ? a.n : (a.clip == 2 ? a.clip_half_n : 0);
+    const int plane = a.pH * a.pW;
+    const int pix = 4 * (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (pix >= plane) return;
+    const int img_co = blockIdx.y, y = pix / a.pW;
+    const long long idx = (long long)img_co * plane + pix;
+    float fx[4];
+    if (a.P) {
+        const float *p = a.P + (size_t)img_co * a.pKH * plane + pix;
+        const float b0 = a.P_bias ? a.P_bias[img_co % a.pC] : 0.f;
+        fx[0] = fx[1] = fx[2] = fx[3] = b0;
+        for (int ky = 0; ky < a.pKH; ++ky) {
+            const int r = y + ky - a.pPad;
+            if (r >= 0 && r < a.pH) {
+                const float4 q = *reinterpret_cast<const float4 *>(p + (size_t)ky * plane + (long long)(ky - a.pPad) * a.pW);
+                fx[0] += q.x; fx[1] += q.y; fx[2] += q.z; fx[3] += q.w;
+            }
+        }
+    } else {
+        const float4 q = *reinterpret_cast<const float4 *>(a.fx + idx);
+        fx[0] = q.x; fx[1] = q.y; fx[2] = q.z; fx[3] = q.w;
+    }
+    const float4 x4 = *reinterpret_cast<const float4 *>(a.x + idx);
+    const float4 h4 = *reinterpret_cast<const float4 *>(a.hist + idx);
+    const float xs[4] = {x4.x, x4.y, x4.z, x4.w}, hs[4] = {h4.x, h4.y, h4.z, h4.w};
+    const bool clip = idx < clip_n;                       // (clip_n is a whole number of images)
+    bool bad = false;
+    float out[4], x0[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        bad |= !(fabsf(fx[c]) <= 3.0e38f);
+        x0[c] = solver_x0(kc, fx[c], xs[c], clip);
+        out[c] = solver_next(kc, xs[c], x0[c], hs[c]);
+    }
+    *reinterpret_cast<float4 *>(a.x_next + idx) = make_float4(out[0], out[1], out[2], out[3]);
+    *reinterpret_cast<float4 *>(a.hist + idx) = make_float4(x0[0], x0[1], x0[2], x0[3]);
+    if (bad && a.fault) *a.fault = 1;
+}
+
+// ddim_launch's rule (a given fx tensor takes the four-pixel form too, read 16 bytes at a time)
+hipError_t solver_launch(const SolverArgs &a, hipStream_t st) {
+    const long long plane = (long long)a.pH * a.pW;
+    if (a.n <= 0) return hipErrorInvalidValue;
+    if (plane > 0 && (a.pW & 3) == 0 && plane < (1ll << 30) && a.n % plane == 0 && a.n / plane <= 65535 &&
+        (((uintptr_t)a.P | (uintptr_t)a.fx | (uintptr_t)a.x | (uintptr_t)a.x_next | (uintptr_t)a.hist) & 15) == 0) {
+        const dim3 g((unsigned)ceil_div(plane / 4, 256), (unsigned)(a.n / plane));
+        hipLaunchKernelGGL(solver_rows4_kernel, g, dim3(256), 0, st, a);
+        return hipGetLastError();
+    }
+    const int grid = (int)std::min<long long>((a.n + 255) / 256, 4096);
+    hipLaunchKernelGGL(solver_kernel, dim3(grid), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
 // out[b][e] = scale * z(seeds[b], draw, e): the start image of a seeded decode and cdc_randn.  One quad of rng.h per thread; a
 // 16-byte store where every image starts on a 16-byte boundary (per_image % 4 == 0), element stores with a bound otherwise.
 template <bool VEC>

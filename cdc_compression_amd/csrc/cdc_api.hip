@@ -284,6 +284,8 @@ void cdc_destroy(cdc_handle *h) {
     if (h->d_time_steps) (void)hipFree(h->d_time_steps);
     if (h->d_shift_tab) (void)hipFree(h->d_shift_tab);
     if (h->d_seeds) (void)hipFree(h->d_seeds);
+    if (h->d_stab) (void)hipFree(h->d_stab);
+    if (h->d_hist) (void)hipFree(h->d_hist);
     if (h->metric_work) (void)hipFree(h->metric_work);
     (void)resolve_pending(h);
     for (hipEvent_t e : h->ev_free) (void)hipEventDestroy(e);
@@ -881,6 +883,75 @@ int cdc_set_schedule_v(cdc_handle *h, int steps, const float *sqrt_ac, const flo
     return CDC_OK;
 }
 
+int cdc_set_solver(cdc_handle *h, int steps, const float *a, const float *b, const float *c) {
+    int rc0 = require_kind(h, HandleKind::Unet);
+    if (rc0) return rc0;
+    if (!h || !a || !b || !c) return fail(h, CDC_ERR_INVALID, "null argument");
+    if (!h->steps || steps != h->steps) return fail(h, CDC_ERR_STATE, "cdc_set_solver follows cdc_set_schedule with the same number of steps");
+    if ((rc0 = ensure_device(h))) return rc0;
+    return no_throw(h, [&]() -> int {
+        std::vector<float> tab((size_t)3 * steps);
+        const float *srcs[3] = {a, b, c};
+        for (int k = 0; k < 3; ++k) memcpy(&tab[(size_t)k * steps], srcs[k], sizeof(float) * steps);
+        for (float v : tab)
+            if (!(fabsf(v) <= 3.0e38f)) return fail(h, CDC_ERR_INVALID, "cdc_set_solver: a table value is not finite");
+        if (h->d_stab && h->stab_sched_gen == h->sched_gen && tab == h->h_stab) return CDC_OK;    // the same tables again change nothing
+        HIP_TRY(h, hipDeviceSynchronize());
+        if (tab.size() > h->stab_cap) {       // grow only; the buffer keeps its address otherwise
+            if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }   // it baked the old address
+            if (h->d_stab) { (void)hipFree(h->d_stab); h->d_stab = nullptr; h->stab_cap = 0; }
+            HIP_TRY(h, hipMalloc((void **)&h->d_stab, tab.size() * sizeof(float)));
+            h->stab_cap = tab.size();
+        }
+        HIP_TRY(h, hipMemcpy(h->d_stab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+        h->h_stab.swap(tab);
+        h->stab_sched_gen = h->sched_gen;
+        ++h->solver_gen;
+        return CDC_OK;
+    });
+}
+
+// What every solver entry point needs beyond the DDIM ones' checks: tables of the current schedule, and pred_mode "v"'s.
+static int solver_ready(cdc_handle *h, int pred_mode, int clip) {
+    if (!h->steps) return fail(h, CDC_ERR_STATE, "cdc_set_schedule has not been called");
+    if (pred_mode < 0 || pred_mode > 3 || clip < 0 || clip > 2) return fail(h, CDC_ERR_INVALID, "pred_mode %d / clip %d out of range", pred_mode, clip);
+    if (!h->d_stab || h->stab_sched_gen != h->sched_gen)
+        return fail(h, CDC_ERR_STATE, "the solver needs cdc_set_solver after cdc_set_schedule");
+    if (pred_mode == CDC_PRED_V && (!h->d_tab_v || h->tab_v_gen != h->sched_gen))
+        return fail(h, CDC_ERR_STATE, "pred_mode \"v\" needs cdc_set_schedule_v after cdc_set_schedule");
+    return CDC_OK;
+}
+
+// The history buffer of the solver: n floats, grow only (a captured graph holds its address).
+static int ensure_hist(cdc_handle *h, size_t n) {
+    if (n <= h->hist_cap) return CDC_OK;
+    HIP_TRY(h, hipDeviceSynchronize());
+    if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
+    if (h->d_hist) { (void)hipFree(h->d_hist); h->d_hist = nullptr; h->hist_cap = 0; }
+    void *p = nullptr;
+    HIP_TRY(h, hipMalloc(&p, n * sizeof(float)));
+    h->d_hist = (float *)p;
+    h->hist_cap = n;
+    return CDC_OK;
+}
+
+// One iteration of the multistep sampler: the U-Net on h->in_x, then x_out = a x + b x0 + c hist, hist <- x0 (h->d_hist, in place).
+static int solver_on_device(cdc_handle *h, int i, float *x_out, int B, int H, int W, int pred_mode, int clip, hipStream_t st) {
+    int rc;
+    const size_t n = (size_t)B * h->cfg.channels * H * W;
+    static const bool fuse_combine = getenv("CDC_NO_COMBINE_FUSE") == nullptr;
+    const CombineArgs *cb = (fuse_combine && !h->ops.empty()) ? h->ops.back().get<CombineArgs>() : nullptr;
+    if (cb && cb->out != h->out_fx) cb = nullptr;
+    if ((rc = run_unet(h, st, i, cb != nullptr))) return rc;
+    SolverArgs d = {h->out_fx, h->in_x, x_out, h->d_hist, h->d_tab, h->d_stab, pred_mode == CDC_PRED_V ? h->d_tab_v : nullptr,
+                    h->steps, i < 0 ? 0 : i, i == -2 ? h->d_step : nullptr, pred_mode, clip, (long long)n,
+                    (long long)(B / 2) * h->cfg.channels * H * W, h->d_fault};
+    d.pC = h->cfg.channels; d.pH = H; d.pW = W;
+    if (cb) { d.P = cb->P; d.P_bias = cb->bias; d.pC = cb->Cout; d.pKH = cb->KH; d.pPad = cb->pad; d.pH = cb->H; d.pW = cb->W; }
+    const Op op(PC_SMALL, d, 0, 20.0 * n);
+    return run_op(h, op, B, st);
+}
+
 static int ddim_on_device(cdc_handle *h, const float *x_in, int i, const float *noise, float eta,
                           float *x_out, int B, int H, int W, int pred_mode, int clip,
                           hipStream_t st, const unsigned long long *seeds = nullptr) {
@@ -957,9 +1028,10 @@ static int stage_seeds(cdc_handle *h, const uint64_t *seeds, int B, hipStream_t 
     return CDC_OK;
 }
 
-// cdc_decode (seeds null: eta = 0, no generator) and cdc_decode_seeded: one loop.
+// cdc_decode (seeds null: eta = 0, no generator), cdc_decode_seeded and cdc_decode_solver (solver: the multistep update in place of
+// the DDIM one, eta = 0): one loop.
 static int decode_impl(cdc_handle *h, const float *init, float gamma, const uint64_t *seeds, float eta, const float *const *ctx,
-                       int n_ctx, float *out, int B, int H, int W, int pred_mode, int clip, int mem, void *stream) {
+                       int n_ctx, float *out, int B, int H, int W, int pred_mode, int clip, int mem, void *stream, bool solver = false) {
     return with_range_guard(h, [&]() -> int {
         int rc = require_kind(h, HandleKind::Unet);
         if (rc) return rc;
@@ -972,11 +1044,15 @@ static int decode_impl(cdc_handle *h, const float *init, float gamma, const uint
             return fail(h, CDC_ERR_INVALID, "pred_mode %d / clip %d out of range", pred_mode, clip);
         if (pred_mode == CDC_PRED_V && (!h->d_tab_v || h->tab_v_gen != h->sched_gen))
             return fail(h, CDC_ERR_STATE, "pred_mode \"v\" needs cdc_set_schedule_v after cdc_set_schedule");
+        if (solver && (rc = solver_ready(h, pred_mode, clip))) return rc;
         if ((rc = build_program(h, B, H, W))) return rc;
         if ((rc = ensure_time_rows(h, B))) return rc;
         hipStream_t st = pick_stream(h, stream, mem);
         const size_t n = (size_t)B * h->cfg.channels * H * W;
+        if (solver && (rc = ensure_hist(h, n))) return rc;
         if ((rc = arm_range_guard(h, st, true))) return rc;
+        // the history starts as zeros in every decode, the BF16X3 repetition included: c = 0 on the first step multiplies them
+        if (solver) HIP_TRY(h, hipMemsetAsync(h->d_hist, 0, n * sizeof(float), st));
         // the generator is needed for the start image (no init, gamma != 0) and for the steps (eta != 0); the BF16X3 repetition of
         // a range fault comes through here again and regenerates both from the seeds
         const bool gen_init = seeds && !init && gamma != 0.f;
@@ -985,6 +1061,11 @@ static int decode_impl(cdc_handle *h, const float *init, float gamma, const uint
             if ((rc = stage_seeds(h, seeds, B, st))) return rc;
             dseeds = h->d_seeds;
         }
+        // one iteration, in place on h->in_x; i = -2: the step index comes from h->d_step (graph capture)
+        auto iterate = [&](int i, hipStream_t s) {
+            return solver ? solver_on_device(h, i, h->in_x, B, H, W, pred_mode, clip, s)
+                          : ddim_on_device(h, h->in_x, i, nullptr, eta, h->in_x, B, H, W, pred_mode, clip, s, dseeds);
+        };
         if (init) { if ((rc = copy_in(h, h->in_x, init, n, mem, st))) return rc; }
         else if (gen_init) HIP_TRY(h, randn_fill_launch(dseeds, B, (long long)(n / B), 0u, gamma, h->in_x, st));
         else HIP_TRY(h, hipMemsetAsync(h->in_x, 0, n * sizeof(float), st));
@@ -1011,16 +1092,16 @@ static int decode_impl(cdc_handle *h, const float *init, float gamma, const uint
             }
             if (!h->d_step) { void *p = nullptr; HIP_TRY(h, hipMalloc(&p, sizeof(int))); h->d_step = (int *)p; h->weight_allocs.push_back(p); }
             // first iteration eagerly (kernel attributes, code pages), then capture the second and replay it
-            if ((rc = ddim_on_device(h, h->in_x, i, nullptr, eta, h->in_x, B, H, W, pred_mode, clip, st, dseeds))) return rc;
+            if ((rc = iterate(i, st))) return rc;
             --i;
             int eta_bits;
             memcpy(&eta_bits, &eta, sizeof eta_bits);
-            const int key[6] = {h->steps, pred_mode, clip, h->sched_gen, eta_bits, dseeds != nullptr};
+            const int key[8] = {h->steps, pred_mode, clip, h->sched_gen, eta_bits, dseeds != nullptr, solver ? 1 : 0, solver ? h->solver_gen : 0};
             if (!h->graph_exec || memcmp(key, h->graph_key, sizeof key)) {
                 if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
                 hipGraph_t g = nullptr;
                 HIP_TRY(h, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-                rc = ddim_on_device(h, h->in_x, -2, nullptr, eta, h->in_x, B, H, W, pred_mode, clip, st, dseeds);
+                rc = iterate(-2, st);
                 hipError_t e = rc ? hipSuccess : step_dec_launch(h->d_step, st);
                 hipError_t e2 = hipStreamEndCapture(st, &g);
                 if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
@@ -1042,8 +1123,7 @@ static int decode_impl(cdc_handle *h, const float *init, float gamma, const uint
         }
         for (; i >= 0; --i) {
             h->prof_now = (i % h->prof_every) == 0;
-            if ((rc = ddim_on_device(h, h->in_x, i, nullptr, eta, h->in_x, B, H, W, pred_mode, clip, st, dseeds)))
-                return rc;
+            if ((rc = iterate(i, st))) return rc;
         }
         h->prof_now = true;
         // Range guard: a non-finite U-Net output is flagged by the sampler kernel of the iteration it occurs in; the final image
@@ -1065,6 +1145,85 @@ int cdc_decode_seeded(cdc_handle *h, const float *init, float gamma, const uint6
     if (!(fabsf(eta) <= 3.0e38f) || !(fabsf(gamma) <= 3.0e38f)) return fail(h, CDC_ERR_INVALID, "cdc_decode_seeded: eta / gamma not finite");
     if (B < 1 || B > 65535) return fail(h, CDC_ERR_INVALID, "cdc_decode_seeded: batch %d", B);
     return no_throw(h, [&] { return decode_impl(h, init, gamma, seeds, eta, ctx, n_ctx, out, B, H, W, pred_mode, clip, mem, stream); });
+}
+
+int cdc_decode_solver(cdc_handle *h, const float *init, float gamma, const uint64_t *seeds, const float *const *ctx, int n_ctx, float *out,
+                      int B, int H, int W, int pred_mode, int clip, int mem, void *stream) {
+    if (!h) return CDC_ERR_INVALID;
+    if (!(fabsf(gamma) <= 3.0e38f)) return fail(h, CDC_ERR_INVALID, "cdc_decode_solver: gamma not finite");
+    if (B < 1 || B > 65535) return fail(h, CDC_ERR_INVALID, "cdc_decode_solver: batch %d", B);
+    return no_throw(h, [&] { return decode_impl(h, init, gamma, seeds, 0.f, ctx, n_ctx, out, B, H, W, pred_mode, clip, mem, stream, true); });
+}
+
+int cdc_solver_step(cdc_handle *h, const float *x_in, const float *x0_prev_in, int i, const float *const *ctx, int n_ctx, float *x_out,
+                    float *x0_out, int B, int H, int W, int pred_mode, int clip, int mem, void *stream) {
+    if (!h) return CDC_ERR_INVALID;
+    return no_throw(h, [&] {
+        return with_range_guard(h, [&]() -> int {
+            int rc = require_kind(h, HandleKind::Unet);
+            if (rc) return rc;
+            if ((rc = check_ready(h))) return rc;
+            if ((rc = solver_ready(h, pred_mode, clip))) return rc;
+            if (!x_in || !x_out || !x0_out || B < 1) return fail(h, CDC_ERR_INVALID, "null/invalid argument");
+            if (i < 0 || i >= h->steps) return fail(h, CDC_ERR_INVALID, "step index %d out of [0,%d)", i, h->steps);
+            if (!x0_prev_in && h->h_stab[(size_t)2 * h->steps + i] != 0.f)
+                return fail(h, CDC_ERR_INVALID, "step %d is second order (c != 0): it needs the previous step's x0", i);
+            if (h->out_dim != h->cfg.channels) return fail(h, CDC_ERR_UNSUPPORTED, "sampler needs out_dim == channels");
+            if ((rc = build_program(h, B, H, W))) return rc;
+            if ((rc = ensure_time_rows(h, B))) return rc;
+            hipStream_t st = pick_stream(h, stream, mem);
+            const size_t n = (size_t)B * h->cfg.channels * H * W;
+            if ((rc = ensure_hist(h, n))) return rc;
+            if ((rc = copy_in(h, h->in_x, x_in, n, mem, st))) return rc;
+            if (x0_prev_in) { if ((rc = copy_in(h, h->d_hist, x0_prev_in, n, mem, st))) return rc; }
+            else HIP_TRY(h, hipMemsetAsync(h->d_hist, 0, n * sizeof(float), st));
+            if ((rc = arm_range_guard(h, st, true))) return rc;
+            if (ctx) {
+                if ((rc = stage_ctx(h, ctx, n_ctx, B, mem, st))) return rc;
+                h->prof_now = true;
+                if ((rc = run_pre(h, st))) return rc;
+            }
+            if ((rc = solver_on_device(h, i, h->xa, B, H, W, pred_mode, clip, st))) return rc;
+            rc = range_check(h, {{h->xa, 0, (long long)n}}, 1, st);
+            if (rc == kRangeRetry && !ctx)
+                return fail(h, CDC_ERR_STATE, "fp16 range overflow in step %d; the handle is now in CDC_ARITH_BF16X3 -- repeat the step WITH the context", i);
+            if (rc) return rc;
+            if ((rc = copy_out(h, x0_out, h->d_hist, n, mem, st))) return rc;
+            return copy_out(h, x_out, h->xa, n, mem, st);
+        });
+    });
+}
+
+int cdc_op_solver_update(cdc_handle *h, const float *fx, const float *x, const float *x0_prev, int i, float *x_next, float *x0_out, int B,
+                         int C, int H, int W, int pred_mode, int clip, int mem, void *stream) {
+    if (!h) return CDC_ERR_INVALID;
+    return no_throw(h, [&] {
+        return with_range_guard(h, [&]() -> int {
+            int rc = require_kind(h, HandleKind::Unet);
+            if (rc) return rc;
+            if ((rc = ensure_device(h))) return rc;
+            if ((rc = solver_ready(h, pred_mode, clip))) return rc;
+            if (!fx || !x || !x0_prev || !x_next || !x0_out) return fail(h, CDC_ERR_INVALID, "null argument");
+            if (B < 1 || C < 1 || H < 1 || W < 1 || (long long)B * C * H * W > (1ll << 40))
+                return fail(h, CDC_ERR_INVALID, "solver_update: %d x %d x %d x %d elements", B, C, H, W);
+            if (i < 0 || i >= h->steps) return fail(h, CDC_ERR_INVALID, "step index %d out of [0,%d)", i, h->steps);
+            if (mem != CDC_MEM_HOST && mem != CDC_MEM_DEVICE) return fail(h, CDC_ERR_INVALID, "solver_update: mem_kind %d", mem);
+            hipStream_t st = pick_stream(h, stream, mem);
+            const size_t n = (size_t)B * C * H * W, bytes = n * sizeof(float);
+            Staging s(h, mem, st);
+            const float *dfx = s.in(fx, bytes), *dx = s.in(x, bytes);
+            float *dn = s.out(x_next, bytes), *dh = s.out(x0_out, bytes);      // the history lives in x0_out's memory: updated in place
+            if (s.ok() && dh != x0_prev)
+                s.e = hipMemcpyAsync(dh, x0_prev, bytes, mem == CDC_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st);
+            if (s.ok()) {
+                SolverArgs d = {dfx, dx, dn, dh, h->d_tab, h->d_stab, pred_mode == CDC_PRED_V ? h->d_tab_v : nullptr, h->steps, i, nullptr,
+                                pred_mode, clip, (long long)n, (long long)(B / 2) * C * H * W, nullptr};
+                d.pC = C; d.pH = H; d.pW = W;
+                s.e = solver_launch(d, st);
+            }
+            return s.finish("solver_update");
+        });
+    });
 }
 
 // ---- the generator behind entry points of its own (rng.h) ---------------------------------------------------------------------

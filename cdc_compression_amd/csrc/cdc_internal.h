@@ -258,6 +258,26 @@ struct DdimArgs {
     long long per_image = 0;
 };
 hipError_t ddim_launch(const DdimArgs &a, hipStream_t st);
+// Second-order multistep update in data-prediction form (DPM-Solver++ 2M; include/cdc_hip.h states it):
+//   x0 = the prediction ddim_update forms for pred_mode / clip;  x_next = ((a_i x) + (b_i x0)) + (c_i hist);  hist <- x0
+// hist, of the image's shape, is read and overwritten in place by the thread that owns the element.
+struct SolverArgs {
+    const float *fx, *x;
+    float *x_next, *hist;
+    const float *tab;      // the schedule's device table [5][steps] (rows 0, 1: sqrt_recip, sqrt_recipm1 of pred_mode 1 / 2)
+    const float *stab;     // device table [3][steps]: a, b, c (cdc_set_solver)
+    const float *tab_v;    // pred_mode 3, as in DdimArgs
+    int steps, i;
+    const int *step_ptr;   // non-null: the step index is read from device memory (hipGraph replay)
+    int pred_mode, clip;   // as in DdimArgs
+    long long n, clip_half_n;
+    int *fault;            // set to 1 when the U-Net output holds inf / NaN (may be null)
+    // P non-null: fx is the 7-row combine of the final convolution's partial planes, as in DdimArgs; pC / pH / pW are always the
+    // image's channels and frame
+    const float *P = nullptr, *P_bias = nullptr;
+    int pC = 0, pKH = 0, pPad = 0, pH = 0, pW = 0;
+};
+hipError_t solver_launch(const SolverArgs &a, hipStream_t st);
 // out[b][e] = scale * z(seeds[b], draw, e) for e < per_image (rng.h; seeds on the device); 16-byte stores when the layout allows
 hipError_t randn_fill_launch(const unsigned long long *seeds, int B, long long per_image, unsigned draw, float scale, float *out,
                              hipStream_t st);

@@ -92,7 +92,7 @@ struct CtxOneOp { AttnCtxArgs a; };
 struct CtxReduceOp { AttnCtxArgs a; };
 struct CtxFoldOp { AttnCtxArgs a; };
 using OpPayload = std::variant<ConvOp, PfConvOp, PwConvOp, WsConvOp, Ws1ConvOp, PfPackOp, C4PackOp, PfUnpackOp, LnArgs, TembArgs, KstatsOp,
-                               CtxPartialOp, CtxOneOp, CtxReduceOp, CtxFoldOp, KvCtxArgs, LnConvArgs, CombineArgs, DdimArgs, CopyArgs,
+                               CtxPartialOp, CtxOneOp, CtxReduceOp, CtxFoldOp, KvCtxArgs, LnConvArgs, CombineArgs, DdimArgs, SolverArgs, CopyArgs,
                                UnfoldArgs, VbrArgs, MaxpoolArgs, LpipsHeadArgs, GdnArgs>;
 
 struct Op {
@@ -125,6 +125,7 @@ inline hipError_t op_launch(const KvCtxArgs &a, int B, hipStream_t st) { return 
 inline hipError_t op_launch(const LnConvArgs &a, int B, hipStream_t st) { return lnconv_launch(a, B, st); }
 inline hipError_t op_launch(const CombineArgs &a, int B, hipStream_t st) { return fold_combine_launch(a, B, st); }
 inline hipError_t op_launch(const DdimArgs &a, int, hipStream_t st) { return ddim_launch(a, st); }
+inline hipError_t op_launch(const SolverArgs &a, int, hipStream_t st) { return solver_launch(a, st); }
 inline hipError_t op_launch(const CopyArgs &a, int B, hipStream_t st) { return copy_channels_launch(a, B, st); }
 inline hipError_t op_launch(const UnfoldArgs &a, int B, hipStream_t st) { return unfold_x_launch(a, B, st); }
 inline hipError_t op_launch(const VbrArgs &a, int B, hipStream_t st) { return vbr_affine_launch(a, B, st); }
@@ -173,6 +174,7 @@ inline void op_label(const KvCtxArgs &a, char *buf, size_t n, bool) { snprintf(b
 inline void op_label(const LnConvArgs &a, char *buf, size_t n, bool) { snprintf(buf, n, "lnconv C=%d N=%d nsplit=%d", a.C, a.N, a.nsplit); }
 inline void op_label(const CombineArgs &, char *buf, size_t n, bool) { snprintf(buf, n, "combine"); }
 inline void op_label(const DdimArgs &, char *buf, size_t n, bool) { snprintf(buf, n, "ddim"); }
+inline void op_label(const SolverArgs &, char *buf, size_t n, bool) { snprintf(buf, n, "solver"); }
 inline void op_label(const CopyArgs &, char *buf, size_t n, bool) { snprintf(buf, n, "copy"); }
 inline void op_label(const UnfoldArgs &, char *buf, size_t n, bool) { snprintf(buf, n, "unfold"); }
 inline void op_label(const VbrArgs &a, char *buf, size_t n, bool) { snprintf(buf, n, "vbr C=%d HW=%d%s", a.C, a.HW, a.leaky ? " leaky" : ""); }
@@ -276,7 +278,15 @@ struct cdc_handle {
     int *d_fault = nullptr;              // sticky "non-finite U-Net output" flag written by the sampler kernel
     hipGraphExec_t graph_exec = nullptr;
     hipEvent_t gev_in = nullptr, gev_out = nullptr;   // order the caller's stream around the graph stream
-    int graph_key[6] = {0, 0, 0, 0, 0, 0};   // steps, pred_mode, clip, stream-independent program generation, eta's bits, seeded
+    int graph_key[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // steps, pred_mode, clip, stream-independent program generation, eta's bits, seeded, sampler, solver-table generation
+    // second-order multistep sampler (cdc_set_solver / cdc_decode_solver): a / b / c [3][steps], valid for schedule generation
+    // stab_sched_gen; the history x0 of the previous step, of the image's shape.  Both grow only: a captured graph holds their address.
+    float *d_stab = nullptr;
+    size_t stab_cap = 0;
+    std::vector<float> h_stab;
+    int stab_sched_gen = -1, solver_gen = 0;
+    float *d_hist = nullptr;
+    size_t hist_cap = 0;
     // seeded stochastic decode (cdc_decode_seeded / cdc_randn): the per-image seeds of the running call on the device
     unsigned long long *d_seeds = nullptr;
     int seeds_cap = 0;

@@ -14,6 +14,13 @@ the start image gamma * randn -- comes from the counter-based generator inside t
 include/cdc_hip.h states the format): same context + same seed => same picture on every host, whatever the batch or the rank.
 seed: an int s (image b takes (s + b) mod 2^64) or B ints in [0, 2^64).  No torch / NumPy generator is touched.
 
+Sampler and step grid (no reference counterpart; both opt-in, the defaults are the reference's): `sampler="dpmpp_2m"` replaces the
+first-order DDIM update by the second-order multistep solver in data-prediction form (DPM-Solver++ 2M; include/cdc_hip.h states the
+update and its tables; eta must be 0, `seed` / `gamma` still make the start image), `spacing="logsnr"` -- or a strictly increasing
+array of train indices, whose length is then sample_steps -- replaces the reference's linspace over train indices by a grid uniform in
+logSNR (cdc_compression_amd.schedule).  The two are orthogonal; the solver pays off on the logSNR grid.  `diffusion.index` and
+`diffusion.sample_steps` report the grid in use.
+
 Images of any size (cdc_compression_amd.frame states the rule): `compress`, `compress_to_bytes` and `decompress` pad on the device to
 the model's multiple, run on the padded frame and return the top-left `[B, 3, H, W]` window, bpp over `H * W`.  `p_sample_loop`
 mirrors the reference's method and keeps requiring frame sizes (`padded_size(H, W)` tells them).
@@ -24,7 +31,7 @@ import numpy as np
 
 from . import _lib, frame, lpips
 from .parallel import expand_seeds
-from .schedule import SampleSchedule
+from .schedule import SAMPLERS, SampleSchedule
 from .unet import _Arg, _current_stream, _is_torch, _result_like
 
 
@@ -39,6 +46,7 @@ class _GaussianDiffusionBase:
         self.pred_mode = pred_mode
         self.var_schedule = var_schedule
         self.sample_steps = None
+        self.sampler = "ddim"
         self.training = False
         self._sched = None
         self.loss_fn_vgg = None      # LpipsVGG, when load_state_dict() found the reference's LPIPS-VGG weights
@@ -91,6 +99,20 @@ class _GaussianDiffusionBase:
             return None
         return expand_seeds(seed, B)
 
+    @staticmethod
+    def _sampler_args(sampler, eta):
+        """The argument rules of the sampler choice, checked before anything runs."""
+        if sampler not in SAMPLERS:
+            raise ValueError(f"sampler {sampler!r}: one of {SAMPLERS}")
+        if sampler != "ddim" and eta != 0:
+            raise ValueError(f'sampler "{sampler}" is deterministic: eta must be 0 (seed / gamma still make the start image)')
+
+    def _steps(self, sample_steps, spacing):
+        """sample_steps of a call: as given, else the length of an explicit grid, else the train steps."""
+        if sample_steps is not None:
+            return sample_steps
+        return self.num_timesteps if isinstance(spacing, str) else len(spacing)
+
     def randn(self, seed, shape, draw=0, scale=1.0, like=None):
         """scale * z(seed_b, draw) of shape [B, ...], made on the device by the generator of the seeded decode (cdc_randn): draw 0 is the
         start image of `gamma=`, draw i + 1 the noise of sample index i.  A NumPy array, or a torch tensor like `like`."""
@@ -103,8 +125,9 @@ class _GaussianDiffusionBase:
                                            optr, omem, _current_stream(omem)))
         return out
 
-    def _compress_frame(self, images, sample_steps, init, eta, loop, *ctx_args):
+    def _compress_frame(self, images, sample_steps, init, eta, loop, *ctx_args, sampler="ddim", spacing="index"):
         """compress() of both trees up to the crop: context model and sampler on the padded frame -> (frame, bpp [B], H, W)."""
+        self._sampler_args(sampler, eta)
         B, _, H, W = frame.image_shape(images)
         Hp, Wp = self.padded_size(H, W)
         h, dev = self.denoise_fn._handle(), self.denoise_fn.device_index
@@ -115,7 +138,7 @@ class _GaussianDiffusionBase:
         else:                                                # any other context_fn sees the frame; its bpp counts the frame's pixels
             context_dict = dict(self.context_fn(frame.pad(h, images, Hp, Wp, dev), *ctx_args))
             context_dict["bpp"] = context_dict["bpp"] * ((Hp * Wp) / (H * W))
-        self.set_sample_schedule(self.num_timesteps if sample_steps is None else sample_steps)
+        self.set_sample_schedule(self._steps(sample_steps, spacing), sampler=sampler, spacing=spacing)
         rec = loop((B, 3, Hp, Wp), context_dict["output"], frame.extend_init(h, init, B, H, W, Hp, Wp, dev))
         return rec, context_dict["bpp"], H, W
 
@@ -144,10 +167,16 @@ class _GaussianDiffusionBase:
         return out
 
     # ---- schedule ---------------------------------------------------------------------------
-    def set_sample_schedule(self, sample_steps, device=None):
+    def set_sample_schedule(self, sample_steps, device=None, sampler="ddim", spacing="index"):
+        """The step grid (`spacing`: "index", "logsnr" or an array of train indices) and the tables of `sampler` ("ddim", "dpmpp_2m")
+        for the next p_sample_loop; the defaults are the reference's schedule."""
+        if sampler not in SAMPLERS:
+            raise ValueError(f"sampler {sampler!r}: one of {SAMPLERS}")
         # the schedule flavour (index / time rule, sigma formula) belongs to the TREE, not to pred_mode
-        s = SampleSchedule(self.num_timesteps, self.var_schedule, self._param, sample_steps)
+        s = SampleSchedule(self.num_timesteps, self.var_schedule, self._param, sample_steps, spacing=spacing)
         self.sample_steps = sample_steps
+        self.sampler = sampler
+        self._spacing_arg = spacing
         self._sched = s
         self.index = s.index
         self.alphas_cumprod = s.alphas_cumprod
@@ -159,6 +188,26 @@ class _GaussianDiffusionBase:
                                          p(s.sqrt_ac_prev), p(s.one_minus_ac_prev), p(s.sigma)))
         if self._param == "x" and self.pred_mode == "v":             # predict_start_from_v reads two more tables (x :128-139)
             _lib.check(h, L.cdc_set_schedule_v(h, s.steps, p(s.sqrt_ac), p(s.sqrt_one_minus_ac)))
+        if sampler == "dpmpp_2m":
+            self._set_solver_tables(*s.solver())
+
+    def _set_solver_tables(self, a, b, c):
+        """The a / b / c tables of the multistep update for the schedule in force (cdc_set_solver)."""
+        h = self.denoise_fn._handle()
+        a, b, c = (np.ascontiguousarray(t, dtype=np.float32) for t in (a, b, c))
+        if not a.shape == b.shape == c.shape == (self._sched.steps,):
+            raise ValueError(f"solver tables must hold {self._sched.steps} values each")
+        _lib.check(h, _lib.lib().cdc_set_solver(h, self._sched.steps, a.ctypes.data, b.ctypes.data, c.ctypes.data))
+        self.solver_tables = (a, b, c)
+
+    def _reschedule(self, sampler, spacing):
+        """p_sample_loop's keywords: None keeps what set_sample_schedule was given; a value sets the schedule again, at its steps."""
+        if sampler is None and spacing is None:
+            return
+        if self.sample_steps is None:
+            raise ValueError("p_sample_loop(sampler= / spacing=) follows set_sample_schedule, which gives the number of steps")
+        self.set_sample_schedule(self.sample_steps, sampler=self.sampler if sampler is None else sampler,
+                                 spacing=self._spacing_arg if spacing is None else spacing)
 
     # ---- sampler ----------------------------------------------------------------------------
     def _clip_flag(self, clip_denoised):
@@ -173,8 +222,13 @@ class _GaussianDiffusionBase:
             return {"x": _lib.CDC_PRED_X, "noise": _lib.CDC_PRED_NOISE_XTREE, "v": _lib.CDC_PRED_V}[self.pred_mode]
         return _lib.CDC_PRED_NOISE                        # (the eps tree's ddim ignores pred_mode: eps :137-139)
 
-    def _loop(self, shape, context, clip_denoised, init, eta, seed=None, gamma=None):
+    def _loop(self, shape, context, clip_denoised, init, eta, seed=None, gamma=None, sampler=None):
+        """sampler: None runs what set_sample_schedule was given."""
         B, C, H, W = shape
+        sampler = self.sampler if sampler is None else sampler
+        self._sampler_args(sampler, eta)
+        if sampler != self.sampler:
+            raise ValueError(f'the schedule in force was set for sampler "{self.sampler}": set_sample_schedule(..., sampler="{sampler}") first')
         seeds = self._seed_args(seed, gamma, init, B)
         L, un = _lib.lib(), self.denoise_fn
         h = un._handle()
@@ -195,6 +249,12 @@ class _GaussianDiffusionBase:
             ai = _Arg(init, dev) if init is not None else None
             if ai is not None and ai.mem != mem:
                 raise _lib.CdcError("init and context must live in the same memory space")
+            if sampler == "dpmpp_2m":      # the multistep update in the device loop; the seeds serve the start image only
+                sd = None if seeds is None else np.asarray(seeds, dtype=np.uint64)
+                _lib.check(h, L.cdc_decode_solver(h, ai.ptr if ai else None, 0.0 if gamma is None else float(gamma),
+                                                  None if sd is None else sd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ptrs, len(actx),
+                                                  optr, B, H, W, pred, clip, mem, stream))
+                return out
             if seeds is not None:      # every draw from the generator in the sampler kernels: any eta stays in the device loop
                 sd = np.asarray(seeds, dtype=np.uint64)
                 _lib.check(h, L.cdc_decode_seeded(h, ai.ptr if ai else None, 0.0 if gamma is None else float(gamma),
@@ -229,7 +289,7 @@ class _GaussianDiffusionBase:
         return img
 
     def decompress(self, context, shape=None, sample_steps=None, init=None, eta=0, clip_denoised=None, bitrate_scale=None,
-                   as_uint8=False, seed=None, gamma=None):
+                   as_uint8=False, seed=None, gamma=None, sampler="ddim", spacing="index"):
         """Decode half of compress(): context pyramid (= context_fn(...)["output"]) -> image.  `context`
         may also be the transmitted q_latent tensor [B, C, H/16, W/16]: it then goes through
         `context_fn.decode` first (compress_modules.py:68-74; cdc_compression_amd.compressor on the GPU) -- with
@@ -240,8 +300,10 @@ class _GaussianDiffusionBase:
         more smaller -- or one that contradicts the size the streams record is an error.  The reconstruction is the frame's top-left H x W window.
         as_uint8: the uint8 image the reference's script saves (clamp(-1, 1) / 2 + 0.5, then save_image's rounding), made on the device.
         seed / gamma: the seeded stochastic decode (module docstring): with a seed, any eta runs in the device loop with generated
-        noise; gamma (needs a seed, excludes init) starts from gamma * randn made on the device.  The draws are indexed on the padded frame."""
+        noise; gamma (needs a seed, excludes init) starts from gamma * randn made on the device.  The draws are indexed on the padded frame.
+        sampler / spacing: the update rule and the step grid (module docstring); an explicit grid's length is sample_steps."""
         self._seed_args(seed, gamma, init)
+        self._sampler_args(sampler, eta)
         recorded = None
         if isinstance(context, (bytes, bytearray)):
             context = [context]
@@ -256,7 +318,7 @@ class _GaussianDiffusionBase:
                 raise RuntimeError("decompress(q_latent, ...) needs a context_fn with decode()")
             context = self.context_fn.decode(context) if bitrate_scale is None else self.context_fn.decode(context, bitrate_scale)
         self._seed_args(seed, gamma, init, int(context[0].shape[0]))
-        self.set_sample_schedule(self.num_timesteps if sample_steps is None else sample_steps)
+        self.set_sample_schedule(self._steps(sample_steps, spacing), sampler=sampler, spacing=spacing)
         if clip_denoised is None:
             clip_denoised = True if self._param == "x" else getattr(self, "clip_noise", "none")
         B, _, Hp, Wp = (int(d) for d in context[0].shape)          # the coded extent: the finest context level
@@ -268,7 +330,7 @@ class _GaussianDiffusionBase:
             raise _lib.CdcError(f"a {H} x {W} image does not pad to the {Hp} x {Wp} frame of the context (multiple {M})")
         h, dev = self.denoise_fn._handle(), self.denoise_fn.device_index
         rec = self._loop((B, 3, Hp, Wp), context, clip_denoised, frame.extend_init(h, init, B, H, W, Hp, Wp, dev), eta,
-                         seed, gamma)
+                         seed, gamma, sampler)
         if (Hp, Wp) != (H, W) or as_uint8:
             rec = frame.crop(h, rec, H, W, dev, as_uint8=as_uint8)
         return rec
@@ -304,17 +366,20 @@ class GaussianDiffusionX(_GaussianDiffusionBase):
         self.aux_loss_weight = aux_loss_weight      # (the reference builds its LPIPS-VGG network when this is > 0)
         self.lagrangian_beta = lagrangian
 
-    def p_sample_loop(self, shape, context, clip_denoised=False, init=None, eta=0, seed=None, gamma=None):
-        return self._loop(tuple(shape), context, clip_denoised, init, eta, seed, gamma)
+    def p_sample_loop(self, shape, context, clip_denoised=False, init=None, eta=0, seed=None, gamma=None, sampler=None, spacing=None):
+        self._reschedule(sampler, spacing)
+        return self._loop(tuple(shape), context, clip_denoised, init, eta, seed, gamma, sampler)
 
-    def _frame_of(self, images, sample_steps=None, init=None, eta=0, seed=None, gamma=None):
+    def _frame_of(self, images, sample_steps=None, init=None, eta=0, seed=None, gamma=None, sampler="ddim", spacing="index"):
         self._seed_args(seed, gamma, init, frame.image_shape(images)[0])
         return self._compress_frame(images, sample_steps, init, eta,
                                     lambda shape, ctx, i: self.p_sample_loop(shape, ctx, clip_denoised=True, init=i, eta=eta,
-                                                                             seed=seed, gamma=gamma))   # :223
+                                                                             seed=seed, gamma=gamma),   # :223
+                                    sampler=sampler, spacing=spacing)
 
-    def compress(self, images, sample_steps=None, bpp_return_mean=True, init=None, eta=0, seed=None, gamma=None):
-        rec, bpp, H, W = self._frame_of(images, sample_steps, init, eta, seed, gamma)
+    def compress(self, images, sample_steps=None, bpp_return_mean=True, init=None, eta=0, seed=None, gamma=None, sampler="ddim",
+                 spacing="index"):
+        rec, bpp, H, W = self._frame_of(images, sample_steps, init, eta, seed, gamma, sampler, spacing)
         return self._window(rec, H, W), (bpp.mean() if bpp_return_mean else bpp)
 
 
@@ -333,19 +398,21 @@ class GaussianDiffusionEps(_GaussianDiffusionBase):
         self.aux_loss_weight = aux_loss_weight      # (the reference builds its LPIPS-VGG network when this is > 0)
         self.vbr = vbr
 
-    def p_sample_loop(self, shape, context, sample_mode, init=None, eta=0, seed=None, gamma=None):
+    def p_sample_loop(self, shape, context, sample_mode, init=None, eta=0, seed=None, gamma=None, sampler=None, spacing=None):
         if sample_mode != "ddim":
             raise NotImplementedError('sample_mode "ddpm" raises AttributeError in the reference '
                                       "(posterior_mean_coef1 undefined); only \"ddim\" is implemented")
-        return self._loop(tuple(shape), context, self.clip_noise, init, eta, seed, gamma)
+        self._reschedule(sampler, spacing)
+        return self._loop(tuple(shape), context, self.clip_noise, init, eta, seed, gamma, sampler)
 
-    def _frame_of(self, images, sample_steps=None, bitrate_scale=None, sample_mode="ddpm", init=None, eta=0, seed=None, gamma=None):
+    def _frame_of(self, images, sample_steps=None, bitrate_scale=None, sample_mode="ddpm", init=None, eta=0, seed=None, gamma=None,
+                  sampler="ddim", spacing="index"):
         self._seed_args(seed, gamma, init, frame.image_shape(images)[0])
         return self._compress_frame(images, sample_steps, init, eta,
                                     lambda shape, ctx, i: self.p_sample_loop(shape, ctx, sample_mode, init=i, eta=eta, seed=seed,
-                                                                             gamma=gamma), bitrate_scale)
+                                                                             gamma=gamma), bitrate_scale, sampler=sampler, spacing=spacing)
 
     def compress(self, images, sample_steps=None, bitrate_scale=None, sample_mode="ddpm",
-                 bpp_return_mean=True, init=None, eta=0, seed=None, gamma=None):
-        rec, bpp, H, W = self._frame_of(images, sample_steps, bitrate_scale, sample_mode, init, eta, seed, gamma)
+                 bpp_return_mean=True, init=None, eta=0, seed=None, gamma=None, sampler="ddim", spacing="index"):
+        rec, bpp, H, W = self._frame_of(images, sample_steps, bitrate_scale, sample_mode, init, eta, seed, gamma, sampler, spacing)
         return self._window(rec, H, W), (bpp.mean() if bpp_return_mean else bpp)

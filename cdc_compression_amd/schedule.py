@@ -33,19 +33,104 @@ def linspace_index(T, steps):
     return np.where(i < steps // 2, lo, hi).astype(np.int64)
 
 
-class SampleSchedule:
-    """Per-sample-step tables handed to cdc_set_schedule."""
+def half_logsnr(ac):
+    """lambda = 1/2 log(ac / (1 - ac)) = log(alpha / sigma), in float64 over the float32 values given."""
+    ac = np.asarray(ac, np.float32).astype(np.float64)
+    return 0.5 * (np.log(ac) - np.log1p(-ac))
 
-    def __init__(self, num_timesteps, var_schedule, tree, sample_steps):
+
+def logsnr_index(train_ac, steps):
+    """`steps` train indices whose lambda is as uniform as the train grid allows, strictly increasing from 0 to T - 1 (2 <= steps <= T):
+    the index nearest in lambda to each of `steps` uniform targets (ties to the lower index), then one forward and one backward pass
+    that separate the collisions -- the cosine schedule's last twelve indices span lambda from -6 to -12, and at many steps the
+    clean end collides too."""
+    T = int(train_ac.shape[0])
+    if not 2 <= steps <= T:
+        raise ValueError(f"a logSNR grid needs 2 <= sample_steps <= {T}, got {steps}")
+    lam = half_logsnr(train_ac)
+    assert np.all(np.diff(lam) < 0), "lambda is not strictly decreasing over the train schedule"
+    w = lam[0] + (lam[-1] - lam[0]) * (np.arange(steps, dtype=np.float64) / (steps - 1))
+    hi = np.clip(np.searchsorted(-lam, -w, side="left"), 1, T - 1)      # the first index whose lambda is <= the target
+    lo = hi - 1
+    idx = np.where(np.abs(lam[lo] - w) <= np.abs(lam[hi] - w), lo, hi).astype(np.int64)
+    idx[0] = 0
+    for j in range(1, steps):
+        idx[j] = max(idx[j], idx[j - 1] + 1)
+    idx[-1] = T - 1
+    for j in range(steps - 2, -1, -1):
+        idx[j] = min(idx[j], idx[j + 1] - 1)
+    return idx
+
+
+def solver_tables(ac, ac_prev, order=2, dtype=np.float32):
+    """a, b, c [steps] of the multistep update  x_next = a_i x + b_i x0 + c_i x0_prev  (DPM-Solver++ 2M in data-prediction form;
+    include/cdc_hip.h states it), in float64 from the grid's float32 ac / ac_prev.  With alpha = sqrt(ac), sigma = sqrt(1 - ac),
+    lambda = log(alpha / sigma):  h_i = lambda(ac_prev_i) - lambda(ac_i),  a_i = sigma_prev / sigma,  b1_i = -alpha_prev expm1(-h_i)
+    (i = 0: ac_prev = 1, so a = 0, b1 = 1);  0 < i < steps - 1:  r_i = (lambda_i - lambda_{i+1}) / h_i,  b_i = b1_i (1 + 1 / (2 r_i)),
+    c_i = -b1_i / (2 r_i);  the first executed step (i = steps - 1) and the last (i = 0) are first order: b = b1, c = 0.
+    order=1: every step first order, which is the DDIM step at eta = 0."""
+    if order not in (1, 2):
+        raise ValueError(f"order {order}: 1 or 2")
+    ac = np.asarray(ac, np.float32).astype(np.float64)
+    acp = np.asarray(ac_prev, np.float32).astype(np.float64)
+    n = int(ac.shape[0])
+    lam = half_logsnr(ac)
+    a, b1 = np.zeros(n), np.ones(n)
+    if n > 1:
+        h = half_logsnr(acp[1:]) - lam[1:]
+        a[1:] = np.sqrt(1.0 - acp[1:]) / np.sqrt(1.0 - ac[1:])
+        b1[1:] = -np.sqrt(acp[1:]) * np.expm1(-h)
+    if acp[0] != 1.0:                                       # (a grid whose first ac_prev is not the clean image)
+        a[0] = np.sqrt(1.0 - acp[0]) / np.sqrt(1.0 - ac[0])
+        b1[0] = -np.sqrt(acp[0]) * np.expm1(-(half_logsnr(acp[:1])[0] - lam[0]))
+    b, c = b1.copy(), np.zeros(n)
+    if order == 2 and n > 2:
+        i = np.arange(1, n - 1)
+        r = (lam[i] - lam[i + 1]) / h[i - 1]
+        b[i] = b1[i] * (1.0 + 1.0 / (2.0 * r))
+        c[i] = -b1[i] / (2.0 * r)
+    return a.astype(dtype), b.astype(dtype), c.astype(dtype)
+
+
+SPACINGS = ("index", "logsnr")
+SAMPLERS = ("ddim", "dpmpp_2m")
+
+
+class SampleSchedule:
+    """Per-sample-step tables handed to cdc_set_schedule (and, for sampler "dpmpp_2m", cdc_set_solver)."""
+
+    def __init__(self, num_timesteps, var_schedule, tree, sample_steps, spacing="index"):
         """tree: "x" (xparam/modules/denoising_diffusion.py) or "eps" (epsilonparam/...): the two trees differ in
-        the U-Net time input, the sample_steps == 1 special case and the order of operations of sigma."""
+        the U-Net time input, the sample_steps == 1 special case and the order of operations of sigma.
+        spacing: "index" (the reference's linspace over train indices), "logsnr" (logsnr_index) or a strictly increasing 1-D integer
+        array of train indices whose length is sample_steps.  Under any spacing but "index" the U-Net time input is
+        index / num_timesteps in both trees -- what both train with; the eps tree's t / sample_steps is its approximation on the
+        linspace grid.  sample_steps == 1 keeps the "index" behaviour under either named spacing."""
         pred_mode = tree
         betas = cosine_beta_schedule(num_timesteps) if var_schedule == "cosine" \
             else linear_beta_schedule(num_timesteps)
         T = int(betas.shape[0])
         train_ac = np.cumprod(1.0 - betas, axis=0).astype(np.float32)
         f = np.float32
-        if sample_steps == 1 and pred_mode == "x":
+        explicit = not isinstance(spacing, str)
+        if explicit:
+            given = np.asarray(spacing)
+            if given.ndim != 1 or given.size < 1 or not np.issubdtype(given.dtype, np.integer):
+                raise ValueError("spacing: \"index\", \"logsnr\" or a 1-D integer array of train indices")
+            if given.size != sample_steps:
+                raise ValueError(f"spacing holds {given.size} indices for sample_steps = {sample_steps}")
+            given = given.astype(np.int64)
+            if given[0] < 0 or given[-1] > T - 1 or np.any(np.diff(given) <= 0):
+                raise ValueError(f"spacing must be strictly increasing within [0, {T - 1}]")
+        elif spacing not in SPACINGS:
+            raise ValueError(f"spacing {spacing!r}: one of {SPACINGS} or an array of train indices")
+        by_index = not explicit and (spacing == "index" or sample_steps == 1)
+        self.spacing = "index" if by_index else ("explicit" if explicit else spacing)
+        if explicit:
+            indice = given
+        elif not by_index:
+            indice = logsnr_index(train_ac, sample_steps)
+        elif sample_steps == 1 and pred_mode == "x":
             indice = np.array([T - 1], np.int64)          # x-param special case (:91-94)
         else:
             indice = linspace_index(T, sample_steps)
@@ -67,4 +152,11 @@ class SampleSchedule:
             self.time_in = (indice.astype(f) / f(T)).astype(f)                       # :154
         else:
             self.sigma = (np.sqrt((f(1) - acp) / (f(1) - ac)) * np.sqrt(f(1) - ac / acp)).astype(f)
-            self.time_in = (np.arange(sample_steps).astype(f) / f(sample_steps)).astype(f)  # eps :138
+            if by_index:
+                self.time_in = (np.arange(sample_steps).astype(f) / f(sample_steps)).astype(f)  # eps :138
+            else:
+                self.time_in = (indice.astype(f) / f(num_timesteps)).astype(f)
+
+    def solver(self, order=2):
+        """The float32 a / b / c tables of solver_tables over this grid."""
+        return solver_tables(self.alphas_cumprod, self.alphas_cumprod_prev, order)

@@ -17,11 +17,16 @@ def _shared_options():
       --device_seed N   init is made on the device from N and --gamma by the library's counter-based generator (the k-th image of the
                         folder takes seed N + k): the same picture on every host.  Without it init = torch.randn * gamma, as before.
       --metrics         print PSNR and MS-SSIM of the saved image against the input beside bpp (computed on the device from the
-                        reconstruction that is already there: cdc_compression_amd.metrics).  Without it the output is unchanged."""
+                        reconstruction that is already there: cdc_compression_amd.metrics).  Without it the output is unchanged.
+      --sampler S       "ddim" (default, the reference's update) or "dpmpp_2m", the second-order multistep solver (eta = 0 only).
+      --spacing G       "index" (default, the reference's linspace over train indices) or "logsnr", the grid uniform in logSNR on
+                        which the second-order solver pays off.  Without the two the output is unchanged."""
     import argparse
     p = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
     p.add_argument("--device_seed", type=int, default=None)
     p.add_argument("--metrics", action="store_true")
+    p.add_argument("--sampler", choices=("ddim", "dpmpp_2m"), default=None)
+    p.add_argument("--spacing", choices=("index", "logsnr"), default=None)
     opts, sys.argv[1:] = p.parse_known_args(sys.argv[1:])
     return opts
 
@@ -96,6 +101,10 @@ def run_folder(diffusion, config, rank, compress_kwargs):
     if getattr(config, "seed", None) is not None:
         torch.manual_seed(config.seed)
     device_seed, k = SHARED.device_seed, 0
+    if SHARED.sampler is not None:
+        compress_kwargs = dict(compress_kwargs, sampler=SHARED.sampler)
+    if SHARED.spacing is not None:
+        compress_kwargs = dict(compress_kwargs, spacing=SHARED.spacing)
     for img in sorted(os.listdir(config.img_dir)):
         if img.endswith(".png") or img.endswith(".jpg"):
             to_be_compressed = read_image(os.path.join(config.img_dir, img), rank)

@@ -194,6 +194,45 @@ int cdc_randn(cdc_handle *h, const uint64_t *seeds, int B, int64_t per_image, ui
 int cdc_randn_host(const uint64_t *seeds, int B, int64_t per_image, uint32_t draw, float scale, float *out);
 int cdc_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
+/* ---- second-order multistep sampler (no reference counterpart: the reference's only update rule is the first-order DDIM step) ----
+ * DPM-Solver++ 2M (Lu et al. 2022) in data-prediction form.  It works on the prediction x0 the DDIM step forms (clip included), needs
+ * no extra U-Net evaluation, and keeps one tensor of the image's shape: the x0 of the previous executed step.  eta = 0 by construction.
+ *
+ * THE UPDATE at sample index i (steps run i = steps-1 .. 0):
+ *   x0      = what the DDIM update predicts for pred_mode / clip:  CDC_PRED_X: fx;  CDC_PRED_V: sqrt_ac[i] x - sqrt_one_minus_ac[i] fx;
+ *             CDC_PRED_NOISE / CDC_PRED_NOISE_XTREE: sqrt_recip[i] x - sqrt_recipm1[i] fx;  then the clamp to [-1, 1] where clip says so;
+ *   x_next  = ((a[i] x) + (b[i] x0)) + (c[i] x0_prev)      every product and sum rounded to float32 on its own, in this order;
+ *   x0_prev <- x0                                          (zeros before the first executed step).
+ * THE TABLES, computed by the host in float64 from the grid's float32 ac[i] / ac_prev[i] (ac_prev[0] = 1) and handed over as float32.
+ * With alpha = sqrt(ac), sigma = sqrt(1 - ac), lambda = log(alpha / sigma):
+ *   h[i]  = lambda(ac_prev[i]) - lambda(ac[i]),   a[i] = sigma_prev / sigma,   b1[i] = -alpha_prev expm1(-h[i])
+ *           (i = 0: ac_prev = 1, hence a = 0 and b1 = 1: the last step returns x0);
+ *   0 < i < steps-1:   r[i] = (lambda(ac[i]) - lambda(ac[i+1])) / h[i],   b[i] = b1[i] (1 + 1 / (2 r[i])),   c[i] = -b1[i] / (2 r[i]);
+ *   the first executed step (i = steps-1) and the last (i = 0) are first order: b = b1, c = 0.
+ * With c = 0 and b = b1 everywhere the update is, algebraically, the DDIM step at eta = 0 (b1 = sqrt(ac_prev) - sqrt(ac) a).
+ * The second-order step pays off on a grid that is uniform in lambda; on the reference's index-uniform grid r runs from 0.15 to 14.
+ *
+ * cdc_set_solver: the tables of the schedule in force: follows cdc_set_schedule with the same number of steps (CDC_ERR_STATE
+ *   otherwise), and goes stale with the next cdc_set_schedule that changes the tables, as cdc_set_schedule_v does.  Host arrays, copied
+ *   before return; non-finite values are refused.
+ * cdc_decode_solver: the loop of cdc_decode with this update (context staged once, hoisted context convolutions once, eager or
+ *   CDC_GRAPH=1, range guard).  The history lives in handle-owned device memory, zero-filled at the start of every decode, the
+ *   BF16X3 repetition included.  `seeds` (B uint64_t on the host, may be NULL) serve only the start image: init == NULL starts from
+ *   gamma * z(seed_b, draw 0) of the seeded decode's generator when seeds != NULL and gamma != 0, from zeros otherwise.
+ * cdc_solver_step: one update at sample index i, the counterpart of cdc_ddim_step: x0_prev_in is the x0_out of the previous call
+ *   (NULL where c[i] == 0: zeros), x0_out receives this step's x0.  A chain of these equals cdc_decode_solver bit for bit.
+ * cdc_op_solver_update: the sampler kernel alone on given tensors [B][C][H][W] -- fx is the network output -- with the handle's
+ *   tables; no weights are needed.  x0_out may be x0_prev (in place).  W a multiple of 4 and 16-byte aligned tensors take the four-pixel
+ *   kernel, anything else the scalar one; both give the same bits.
+ * All follow `mem` / `stream` as cdc_decode does and need a U-Net handle. */
+int cdc_set_solver(cdc_handle *h, int steps, const float *a, const float *b, const float *c);
+int cdc_decode_solver(cdc_handle *h, const float *init, float gamma, const uint64_t *seeds /* nullable */, const float *const *ctx,
+                      int n_ctx, float *out, int B, int H, int W, int pred_mode, int clip, int mem, void *stream);
+int cdc_solver_step(cdc_handle *h, const float *x_in, const float *x0_prev_in, int i, const float *const *ctx, int n_ctx,
+                    float *x_out, float *x0_out, int B, int H, int W, int pred_mode, int clip, int mem, void *stream);
+int cdc_op_solver_update(cdc_handle *h, const float *fx, const float *x, const float *x0_prev, int i, float *x_next, float *x0_out,
+                         int B, int C, int H, int W, int pred_mode, int clip, int mem, void *stream);
+
 /* ---- measurement --------------------------------------------------------------------------- */
 
 /* ---- context decoder: Compressor.decode ---------------------------- */
