@@ -131,6 +131,37 @@ int stage_ctx(cdc_handle *h, const float *const *ctx, int n_ctx, int B, int mem,
     return CDC_OK;
 }
 
+// stage_ctx for K samples per image (cdc_decode_samples): ctx[l] holds B images, h->in_ctx[l] receives each of them K times in a row.
+// Device pointers: the repeat kernel reads the caller's tensor.  Host pointers: the B images go through a handle-owned, grow-only buffer
+// first (one level at a time: copy and kernel are ordered on the stream).
+int stage_ctx_repeated(cdc_handle *h, const float *const *ctx, int n_ctx, int B, int K, int mem, hipStream_t st) {
+    if (n_ctx != (int)h->in_ctx.size())
+        return fail(h, CDC_ERR_INVALID, "expected %d context tensors, got %d", (int)h->in_ctx.size(), n_ctx);
+    size_t need = 0;
+    for (int l = 0; l < n_ctx; ++l) {
+        if (!ctx[l]) return fail(h, CDC_ERR_INVALID, "null context tensor %d", l);
+        need = std::max(need, (size_t)B * (size_t)h->in_ctx[l].bs());
+    }
+    if (mem == CDC_MEM_HOST && need > h->rep_stage_cap) {
+        HIP_TRY(h, hipDeviceSynchronize());
+        if (h->d_rep_stage) { (void)hipFree(h->d_rep_stage); h->d_rep_stage = nullptr; h->rep_stage_cap = 0; }
+        void *p = nullptr;
+        HIP_TRY(h, hipMalloc(&p, need * sizeof(float)));
+        h->d_rep_stage = (float *)p;
+        h->rep_stage_cap = need;
+    }
+    for (int l = 0; l < n_ctx; ++l) {
+        const long long per = h->in_ctx[l].bs();
+        const float *src = ctx[l];
+        if (mem == CDC_MEM_HOST) {
+            HIP_TRY(h, hipMemcpyAsync(h->d_rep_stage, ctx[l], (size_t)B * per * sizeof(float), hipMemcpyHostToDevice, st));
+            src = h->d_rep_stage;
+        }
+        HIP_TRY(h, repeat_images_launch({src, h->in_ctx[l].p, per, K, 4}, B, st));
+    }
+    return CDC_OK;
+}
+
 int ensure_device(cdc_handle *h) {
     if (!h) return CDC_ERR_INVALID;
     if (!h->own_stream) {
@@ -286,6 +317,8 @@ void cdc_destroy(cdc_handle *h) {
     if (h->d_seeds) (void)hipFree(h->d_seeds);
     if (h->d_stab) (void)hipFree(h->d_stab);
     if (h->d_hist) (void)hipFree(h->d_hist);
+    if (h->d_rep_stage) (void)hipFree(h->d_rep_stage);
+    if (h->d_pick) (void)hipFree(h->d_pick);
     if (h->metric_work) (void)hipFree(h->metric_work);
     (void)resolve_pending(h);
     for (hipEvent_t e : h->ev_free) (void)hipEventDestroy(e);
@@ -1029,9 +1062,10 @@ static int stage_seeds(cdc_handle *h, const uint64_t *seeds, int B, hipStream_t 
 }
 
 // cdc_decode (seeds null: eta = 0, no generator), cdc_decode_seeded and cdc_decode_solver (solver: the multistep update in place of
-// the DDIM one, eta = 0): one loop.
+// the DDIM one, eta = 0): one loop.  rep > 0 (cdc_decode_samples): ctx holds B / rep images, each staged rep times in a row.
 static int decode_impl(cdc_handle *h, const float *init, float gamma, const uint64_t *seeds, float eta, const float *const *ctx,
-                       int n_ctx, float *out, int B, int H, int W, int pred_mode, int clip, int mem, void *stream, bool solver = false) {
+                       int n_ctx, float *out, int B, int H, int W, int pred_mode, int clip, int mem, void *stream, bool solver = false,
+                       int rep = 0) {
     return with_range_guard(h, [&]() -> int {
         int rc = require_kind(h, HandleKind::Unet);
         if (rc) return rc;
@@ -1069,7 +1103,7 @@ static int decode_impl(cdc_handle *h, const float *init, float gamma, const uint
         if (init) { if ((rc = copy_in(h, h->in_x, init, n, mem, st))) return rc; }
         else if (gen_init) HIP_TRY(h, randn_fill_launch(dseeds, B, (long long)(n / B), 0u, gamma, h->in_x, st));
         else HIP_TRY(h, hipMemsetAsync(h->in_x, 0, n * sizeof(float), st));
-        if ((rc = stage_ctx(h, ctx, n_ctx, B, mem, st))) return rc;
+        if ((rc = rep ? stage_ctx_repeated(h, ctx, n_ctx, B / rep, rep, mem, st) : stage_ctx(h, ctx, n_ctx, B, mem, st))) return rc;
         h->prof_now = false;
         if ((rc = run_pre(h, st))) return rc;       // hoisted context halves: once per decode
         // for i in reversed(range(steps)): img = ddim(img, i)      (x: :188-200 ; eps: :174-190)
@@ -1153,6 +1187,114 @@ int cdc_decode_solver(cdc_handle *h, const float *init, float gamma, const uint6
     if (!(fabsf(gamma) <= 3.0e38f)) return fail(h, CDC_ERR_INVALID, "cdc_decode_solver: gamma not finite");
     if (B < 1 || B > 65535) return fail(h, CDC_ERR_INVALID, "cdc_decode_solver: batch %d", B);
     return no_throw(h, [&] { return decode_impl(h, init, gamma, seeds, 0.f, ctx, n_ctx, out, B, H, W, pred_mode, clip, mem, stream, true); });
+}
+
+// ---- K seeded samples per image (sample_kernels.hip) ----------------------------------------------------------------------------------
+int cdc_decode_samples(cdc_handle *h, float gamma, const uint64_t *seeds, float eta, const float *const *ctx, int n_ctx, float *out, int B,
+                       int K, int H, int W, int pred_mode, int clip, int solver, int mem, void *stream) {
+    if (!h) return CDC_ERR_INVALID;
+    if (!seeds) return fail(h, CDC_ERR_INVALID, "cdc_decode_samples: null seeds");
+    if (!(fabsf(eta) <= 3.0e38f) || !(fabsf(gamma) <= 3.0e38f)) return fail(h, CDC_ERR_INVALID, "cdc_decode_samples: eta / gamma not finite");
+    if (B < 1 || K < 1) return fail(h, CDC_ERR_INVALID, "cdc_decode_samples: B=%d K=%d (both must be >= 1)", B, K);
+    if ((long long)B * K > 65535) return fail(h, CDC_ERR_INVALID, "cdc_decode_samples: B * K = %lld rows, beyond the generator's 65535", (long long)B * K);
+    if (solver != 0 && solver != 1) return fail(h, CDC_ERR_INVALID, "cdc_decode_samples: solver %d (0 ddim, 1 the multistep update)", solver);
+    if (solver && eta != 0.f) return fail(h, CDC_ERR_INVALID, "cdc_decode_samples: the multistep update is deterministic, eta must be 0");
+    if (mem != CDC_MEM_HOST && mem != CDC_MEM_DEVICE) return fail(h, CDC_ERR_INVALID, "cdc_decode_samples: mem_kind %d", mem);
+    return no_throw(h, [&] { return decode_impl(h, nullptr, gamma, seeds, eta, ctx, n_ctx, out, B * K, H, W, pred_mode, clip, mem, stream, solver != 0, K); });
+}
+
+namespace {
+// what cdc_repeat_images / cdc_sample_moments / cdc_sample_select share: B images (rows of K) of per_image elements
+int sample_args(cdc_handle *h, const char *what, int B, int K, int64_t per_image, int mem) {
+    if (B < 1 || K < 1 || per_image < 1) return fail(h, CDC_ERR_INVALID, "%s: B=%d K=%d per_image=%lld (all must be >= 1)", what, B, K, (long long)per_image);
+    if (per_image > (1ll << 40) || (long long)B * K > (1ll << 40) / per_image) return fail(h, CDC_ERR_INVALID, "%s: %d x %d x %lld elements", what, B, K, (long long)per_image);
+    if (mem != CDC_MEM_HOST && mem != CDC_MEM_DEVICE) return fail(h, CDC_ERR_INVALID, "%s: mem_kind %d", what, mem);
+    return CDC_OK;
+}
+}  // namespace
+
+int cdc_repeat_images(cdc_handle *h, const void *src, void *dst, int B, int K, int64_t per_image, int elem_bytes, int mem, void *stream) {
+    if (!h) return CDC_ERR_INVALID;
+    return no_throw(h, [&] {
+        return with_range_guard(h, [&]() -> int {
+            int rc = ensure_device(h);
+            if (rc) return rc;
+            if (!src || !dst) return fail(h, CDC_ERR_INVALID, "repeat_images: null pointer");
+            if (elem_bytes != 1 && elem_bytes != 4) return fail(h, CDC_ERR_INVALID, "repeat_images: elem_bytes %d (1 or 4)", elem_bytes);
+            if ((rc = sample_args(h, "repeat_images", B, K, per_image, mem))) return rc;
+            hipStream_t st = pick_stream(h, stream, mem);
+            const size_t bytes = (size_t)B * (size_t)per_image * elem_bytes;
+            Staging s(h, mem, st);
+            const void *ds = s.in((const uint8_t *)src, bytes);
+            void *dd = s.out((uint8_t *)dst, bytes * K);
+            if (s.ok()) s.e = repeat_images_launch({ds, dd, (long long)per_image, K, elem_bytes}, B, st);
+            return s.finish("repeat_images");
+        });
+    });
+}
+
+int cdc_sample_moments(cdc_handle *h, const float *samples, int B, int Kc, int64_t per_image, int count_before, float *mean, float *m2,
+                       int finish, int mem, void *stream) {
+    if (!h) return CDC_ERR_INVALID;
+    return no_throw(h, [&] {
+        return with_range_guard(h, [&]() -> int {
+            int rc = ensure_device(h);
+            if (rc) return rc;
+            if (!samples || !mean) return fail(h, CDC_ERR_INVALID, "sample_moments: null pointer");
+            if ((rc = sample_args(h, "sample_moments", B, Kc, per_image, mem))) return rc;
+            if (count_before < 0 || count_before > INT32_MAX - Kc) return fail(h, CDC_ERR_INVALID, "sample_moments: count_before %d", count_before);
+            if (finish && count_before + Kc < 2) return fail(h, CDC_ERR_INVALID, "sample_moments: finish needs a final count >= 2, got %d", count_before + Kc);
+            hipStream_t st = pick_stream(h, stream, mem);
+            const size_t bytes = (size_t)B * (size_t)per_image * sizeof(float);
+            Staging s(h, mem, st);
+            const float *ds = s.in(samples, bytes * Kc);
+            // host memory: the accumulators are updated in device scratch, filled from the caller's arrays when the count continues
+            float *acc[2] = {mean, m2};
+            for (float *&a : acc) {
+                if (!a || mem == CDC_MEM_DEVICE) continue;
+                float *host = a;
+                void *d = count_before > 0 ? (void *)s.in(host, bytes) : s.scratch(bytes);
+                a = s.out(host, bytes, d);
+            }
+            if (s.ok()) s.e = sample_moments_launch({ds, acc[0], acc[1], (long long)per_image, Kc, count_before, finish != 0}, B, st);
+            return s.finish("sample_moments");
+        });
+    });
+}
+
+int cdc_sample_select(cdc_handle *h, const float *samples, const int *pick, float *best, int B, int Kc, int64_t per_image, int mem,
+                      void *stream) {
+    if (!h) return CDC_ERR_INVALID;
+    return no_throw(h, [&] {
+        return with_range_guard(h, [&]() -> int {
+            int rc = ensure_device(h);
+            if (rc) return rc;
+            if (!samples || !pick || !best) return fail(h, CDC_ERR_INVALID, "sample_select: null pointer");
+            if ((rc = sample_args(h, "sample_select", B, Kc, per_image, mem))) return rc;
+            for (int b = 0; b < B; ++b)
+                if (pick[b] >= Kc) return fail(h, CDC_ERR_INVALID, "sample_select: pick[%d] = %d, the chunk holds %d samples per image", b, pick[b], Kc);
+            hipStream_t st = pick_stream(h, stream, mem);
+            // the picks into the handle's device array, as stage_seeds stages the seeds
+            if (B > h->pick_cap) {
+                HIP_TRY(h, hipDeviceSynchronize());
+                if (h->d_pick) { (void)hipFree(h->d_pick); h->d_pick = nullptr; h->pick_cap = 0; }
+                void *p = nullptr;
+                HIP_TRY(h, hipMalloc(&p, sizeof(int) * (size_t)B));
+                h->d_pick = (int *)p;
+                h->pick_cap = B;
+            }
+            HIP_TRY(h, hipStreamSynchronize(st));     // an earlier call's copy out of h_pick may still be queued
+            h->h_pick.assign(pick, pick + B);
+            HIP_TRY(h, hipMemcpyAsync(h->d_pick, h->h_pick.data(), sizeof(int) * (size_t)B, hipMemcpyHostToDevice, st));
+            const size_t bytes = (size_t)B * (size_t)per_image * sizeof(float);
+            Staging s(h, mem, st);
+            const float *ds = s.in(samples, bytes * Kc);
+            // host memory: best goes in as well -- the images that are not picked keep their content
+            float *db = mem == CDC_MEM_DEVICE ? best : s.out(best, bytes, (void *)s.in(best, bytes));
+            if (s.ok()) s.e = sample_select_launch({ds, h->d_pick, db, (long long)per_image, Kc}, B, st);
+            return s.finish("sample_select");
+        });
+    });
 }
 
 int cdc_solver_step(cdc_handle *h, const float *x_in, const float *x0_prev_in, int i, const float *const *ctx, int n_ctx, float *x_out,

@@ -301,6 +301,17 @@ hipError_t vbr_affine_launch(const VbrArgs &a, int B, hipStream_t st);
 // replication (zero = 1: by zeros), and the top-left [H][W] window back (float32 copy, or the uint8 of save_image)
 hipError_t frame_in_launch(const void *src, int u8, float *dst, int P, int H, int W, int Hp, int Wp, int zero, hipStream_t st);
 hipError_t frame_out_launch(const float *src, void *dst, int u8, int P, int H, int W, int Hp, int Wp, hipStream_t st);
+// sample_kernels.hip (K seeded samples per image).  B images of per_image elements each; 16-byte accesses where the layout allows.
+// dst[b * K + k] = src[b], elements of elem_bytes (4 or 1)
+struct RepeatArgs { const void *src; void *dst; long long per_image; int K, elem_bytes; };
+hipError_t repeat_images_launch(const RepeatArgs &a, int B, hipStream_t st);
+// the Welford update of mean / m2 [B][per_image] over samples [B][Kc][per_image], k = 0 .. Kc-1, the count continuing from count_before
+// (0: the accumulators are not read); m2 may be null; finish: m2 /= count - 1 after the last sample
+struct MomentsArgs { const float *samples; float *mean, *m2; long long per_image; int Kc, count_before, finish; };
+hipError_t sample_moments_launch(const MomentsArgs &a, int B, hipStream_t st);
+// best[b] = samples[b][pick[b]] where pick[b] >= 0 (pick: device array of B ints, each < Kc)
+struct SelectArgs { const float *samples; const int *pick; float *best; long long per_image; int Kc; };
+hipError_t sample_select_launch(const SelectArgs &a, int B, hipStream_t st);
 // metric_kernels.hip (cdc_distortion): PSNR and MS-SSIM of the top-left H x W window of two image batches [B][3][Hf][Wf]
 enum { METRIC_F32 = 0, METRIC_U8 = 1, METRIC_F32_SAVED = 2 };      // float32 in [-1, 1]; uint8; float32 through the byte cdc_frame_crop writes
 constexpr int METRIC_SCALES = 5, METRIC_TILE_H = 16, METRIC_TILE_W = 32;   // a workgroup's tile of the valid SSIM map

@@ -292,6 +292,13 @@ struct cdc_handle {
     int seeds_cap = 0;
     std::vector<unsigned long long> h_seeds;   // staging copy: the caller's array may go away before the copy has run
     int time_steps_B = 0;
+    // K samples per image (cdc_decode_samples / cdc_sample_select): the B host images of one context level on their way to the repeat
+    // kernel, and the picks of the running call with their staging copy.  Both grow only.
+    float *d_rep_stage = nullptr;
+    size_t rep_stage_cap = 0;
+    int *d_pick = nullptr;
+    int pick_cap = 0;
+    std::vector<int> h_pick;
     // Lpips: the thirteen VGG16 layers live in hconvs; the five `lin` weight vectors, the scaling layer, and the program's result area
     // (a layer of >= 256 input channels is packed as lp_parts[layer] slices of 128 input channels, consecutive in hconvs)
     std::vector<int> lp_parts;
@@ -383,6 +390,7 @@ int run_unet(cdc_handle *h, hipStream_t st, int step, bool skip_combine = false)
 int copy_in(cdc_handle *h, float *dst, const float *src, size_t n, int mem, hipStream_t st);
 int copy_out(cdc_handle *h, float *dst, const float *src, size_t n, int mem, hipStream_t st);
 int stage_ctx(cdc_handle *h, const float *const *ctx, int n_ctx, int B, int mem, hipStream_t st);
+int stage_ctx_repeated(cdc_handle *h, const float *const *ctx, int n_ctx, int B, int K, int mem, hipStream_t st);
 int ensure_device(cdc_handle *h);
 hipStream_t pick_stream(cdc_handle *h, void *stream, int mem);
 int check_ready(cdc_handle *h);

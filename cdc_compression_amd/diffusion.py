@@ -21,6 +21,12 @@ array of train indices, whose length is then sample_steps -- replaces the refere
 logSNR (cdc_compression_amd.schedule).  The two are orthogonal; the solver pays off on the logSNR grid.  `diffusion.index` and
 `diffusion.sample_steps` report the grid in use.
 
+K samples per image (no reference counterpart; cdc_compression_amd.samples): `decompress(..., samples=K)` decodes K seeded samples of
+every image through the batch programs -- sample k of image b has the seed `parallel.sample_seeds(seed, B, K)[b][k]`, sample 0 being the
+plain seeded decode -- and returns them, their pixel-wise mean, or mean and unbiased variance (folded on the device in a fixed order:
+the result does not depend on `sample_chunk`).  `compress_best_of` is the encoder's closed loop: it scores K candidate seeds against the
+original on the device and returns the winner with its seed, which `decompress(..., seed=)` reproduces.
+
 Images of any size (cdc_compression_amd.frame states the rule): `compress`, `compress_to_bytes` and `decompress` pad on the device to
 the model's multiple, run on the padded frame and return the top-left `[B, 3, H, W]` window, bpp over `H * W`.  `p_sample_loop`
 mirrors the reference's method and keeps requiring frame sizes (`padded_size(H, W)` tells them).
@@ -29,8 +35,8 @@ import ctypes
 
 import numpy as np
 
-from . import _lib, frame, lpips
-from .parallel import expand_seeds
+from . import _lib, frame, lpips, samples as _samples
+from .parallel import expand_seeds, sample_seeds
 from .schedule import SAMPLERS, SampleSchedule
 from .unet import _Arg, _current_stream, _is_torch, _result_like
 
@@ -125,9 +131,8 @@ class _GaussianDiffusionBase:
                                            optr, omem, _current_stream(omem)))
         return out
 
-    def _compress_frame(self, images, sample_steps, init, eta, loop, *ctx_args, sampler="ddim", spacing="index"):
-        """compress() of both trees up to the crop: context model and sampler on the padded frame -> (frame, bpp [B], H, W)."""
-        self._sampler_args(sampler, eta)
+    def _context_of(self, images, *ctx_args):
+        """The context model on the padded frame of `images` -> (context_dict with bpp over H * W, B, H, W, Hp, Wp)."""
         B, _, H, W = frame.image_shape(images)
         Hp, Wp = self.padded_size(H, W)
         h, dev = self.denoise_fn._handle(), self.denoise_fn.device_index
@@ -138,6 +143,13 @@ class _GaussianDiffusionBase:
         else:                                                # any other context_fn sees the frame; its bpp counts the frame's pixels
             context_dict = dict(self.context_fn(frame.pad(h, images, Hp, Wp, dev), *ctx_args))
             context_dict["bpp"] = context_dict["bpp"] * ((Hp * Wp) / (H * W))
+        return context_dict, B, H, W, Hp, Wp
+
+    def _compress_frame(self, images, sample_steps, init, eta, loop, *ctx_args, sampler="ddim", spacing="index"):
+        """compress() of both trees up to the crop: context model and sampler on the padded frame -> (frame, bpp [B], H, W)."""
+        self._sampler_args(sampler, eta)
+        context_dict, B, H, W, Hp, Wp = self._context_of(images, *ctx_args)
+        h, dev = self.denoise_fn._handle(), self.denoise_fn.device_index
         self.set_sample_schedule(self._steps(sample_steps, spacing), sampler=sampler, spacing=spacing)
         rec = loop((B, 3, Hp, Wp), context_dict["output"], frame.extend_init(h, init, B, H, W, Hp, Wp, dev))
         return rec, context_dict["bpp"], H, W
@@ -289,7 +301,7 @@ class _GaussianDiffusionBase:
         return img
 
     def decompress(self, context, shape=None, sample_steps=None, init=None, eta=0, clip_denoised=None, bitrate_scale=None,
-                   as_uint8=False, seed=None, gamma=None, sampler="ddim", spacing="index"):
+                   as_uint8=False, seed=None, gamma=None, sampler="ddim", spacing="index", samples=None, reduce=None, sample_chunk=None):
         """Decode half of compress(): context pyramid (= context_fn(...)["output"]) -> image.  `context`
         may also be the transmitted q_latent tensor [B, C, H/16, W/16]: it then goes through
         `context_fn.decode` first (compress_modules.py:68-74; cdc_compression_amd.compressor on the GPU) -- with
@@ -301,9 +313,16 @@ class _GaussianDiffusionBase:
         as_uint8: the uint8 image the reference's script saves (clamp(-1, 1) / 2 + 0.5, then save_image's rounding), made on the device.
         seed / gamma: the seeded stochastic decode (module docstring): with a seed, any eta runs in the device loop with generated
         noise; gamma (needs a seed, excludes init) starts from gamma * randn made on the device.  The draws are indexed on the padded frame.
-        sampler / spacing: the update rule and the step grid (module docstring); an explicit grid's length is sample_steps."""
+        sampler / spacing: the update rule and the step grid (module docstring); an explicit grid's length is sample_steps.
+        samples: K seeded samples per image (needs a seed and gamma or eta != 0, excludes init); None is the single decode.
+        reduce: None returns [B, K, 3, H, W] (uint8 with as_uint8); "mean" their pixel-wise mean [B, 3, H, W] (with as_uint8: its uint8
+        form); "mean_var" (K >= 2, no as_uint8) the pair (mean, unbiased variance).  The moments are folded on the padded frame and
+        cropped once.  sample_chunk: samples per image per library call (default: the largest divisor of K with B * Kc <= 32)."""
         self._seed_args(seed, gamma, init)
         self._sampler_args(sampler, eta)
+        if samples is None and (reduce is not None or sample_chunk is not None):
+            raise ValueError("reduce / sample_chunk belong to samples=K")
+        K = None if samples is None else _samples.check_args(samples, seed, gamma, eta, init, reduce, as_uint8, sample_chunk)
         recorded = None
         if isinstance(context, (bytes, bytearray)):
             context = [context]
@@ -317,7 +336,10 @@ class _GaussianDiffusionBase:
             if self.context_fn is None or not hasattr(self.context_fn, "decode"):
                 raise RuntimeError("decompress(q_latent, ...) needs a context_fn with decode()")
             context = self.context_fn.decode(context) if bitrate_scale is None else self.context_fn.decode(context, bitrate_scale)
-        self._seed_args(seed, gamma, init, int(context[0].shape[0]))
+        if K is None:
+            self._seed_args(seed, gamma, init, int(context[0].shape[0]))
+        else:
+            all_seeds = sample_seeds(seed, int(context[0].shape[0]), K)
         self.set_sample_schedule(self._steps(sample_steps, spacing), sampler=sampler, spacing=spacing)
         if clip_denoised is None:
             clip_denoised = True if self._param == "x" else getattr(self, "clip_noise", "none")
@@ -329,11 +351,88 @@ class _GaussianDiffusionBase:
         if not (0 <= Hp - H < M and 0 <= Wp - W < M):
             raise _lib.CdcError(f"a {H} x {W} image does not pad to the {Hp} x {Wp} frame of the context (multiple {M})")
         h, dev = self.denoise_fn._handle(), self.denoise_fn.device_index
+        if K is not None:
+            return self._decompress_samples(context, all_seeds, K, (H, W), clip_denoised, eta, gamma, sampler, reduce, sample_chunk, as_uint8)
         rec = self._loop((B, 3, Hp, Wp), context, clip_denoised, frame.extend_init(h, init, B, H, W, Hp, Wp, dev), eta,
                          seed, gamma, sampler)
         if (Hp, Wp) != (H, W) or as_uint8:
             rec = frame.crop(h, rec, H, W, dev, as_uint8=as_uint8)
         return rec
+
+    # ---- K samples per image (cdc_compression_amd.samples) --------------------------------------------------------------
+    def _sample_chunk(self, context, seeds, k0, Kc, clip_denoised, eta, gamma, sampler):
+        """Samples k0 .. k0 + Kc - 1 of every image on the padded frame: [B * Kc, 3, Hp, Wp], row b * Kc + kk (cdc_decode_samples)."""
+        B, _, Hp, Wp = (int(d) for d in context[0].shape)
+        return _samples.decode_samples(self.denoise_fn, context, _samples.chunk_seeds(seeds, k0, Kc), B, Kc, Hp, Wp, gamma, eta,
+                                       self._pred_flag(), self._clip_flag(clip_denoised), sampler == "dpmpp_2m")
+
+    def _decompress_samples(self, context, seeds, K, size, clip_denoised, eta, gamma, sampler, reduce, sample_chunk, as_uint8):
+        un = self.denoise_fn
+        h, dev = un._handle(), un.device_index
+        B, _, Hp, Wp = (int(d) for d in context[0].shape)
+        H, W = size
+        window = lambda t, u8=False: (frame.crop(h, t, H, W, dev, as_uint8=u8) if (Hp, Wp) != (H, W) or u8 else t)   # noqa: E731
+        plan = _samples.chunks(B, K, sample_chunk)
+        if reduce is None:
+            out = None
+            for k0, Kc in plan:
+                part = window(self._sample_chunk(context, seeds, k0, Kc, clip_denoised, eta, gamma, sampler), as_uint8)
+                part = part.reshape((B, Kc, 3, H, W))
+                if Kc == K:
+                    return part
+                if out is None:
+                    out = frame._empty_like(part, (B, K, 3, H, W), as_uint8)[0]
+                out[:, k0:k0 + Kc] = part
+            return out
+        mean = frame._empty_like(context[0], (B, 3, Hp, Wp), False)[0]
+        m2 = frame._empty_like(context[0], (B, 3, Hp, Wp), False)[0] if reduce == "mean_var" else None
+        for k0, Kc in plan:
+            chunk = self._sample_chunk(context, seeds, k0, Kc, clip_denoised, eta, gamma, sampler)
+            _samples.fold_moments(un, chunk, B, Kc, k0, mean, m2, finish=m2 is not None and k0 + Kc == K)
+        if m2 is None:
+            return window(mean, as_uint8)
+        return window(mean), window(m2)
+
+    def _best_of(self, images, samples, metric, seed, gamma, eta, sample_steps, sampler, spacing, sample_chunk, as_saved, clip_denoised,
+                 *ctx_args):
+        """compress_best_of of both trees."""
+        from . import metrics
+        K = _samples.check_args(samples, seed, gamma, eta, sample_chunk=sample_chunk, metric=metric)
+        self._sampler_args(sampler, eta)
+        B, _, H, W = frame.image_shape(images)
+        if metric == "lpips" and self.loss_fn_vgg is None:
+            raise ValueError('metric "lpips" needs the LPIPS-VGG weights (self.loss_fn_vgg: a state dict with "loss_fn_vgg." keys)')
+        if metric == "ms_ssim" and min(H, W) < metrics.MS_SSIM_MIN_SIDE:
+            raise ValueError(f"MS-SSIM needs min(H, W) > 160, got {H} x {W}")
+        higher = _samples.METRICS[metric]
+        all_seeds = sample_seeds(seed, B, K)
+        context_dict, B, H, W, Hp, Wp = self._context_of(images, *ctx_args)
+        context = context_dict["output"]
+        self.set_sample_schedule(self._steps(sample_steps, spacing), sampler=sampler, spacing=spacing)
+        un = self.denoise_fn
+        scores = np.full((B, K), np.nan, np.float64)
+        best_k = [0] * B
+        best = frame._empty_like(context[0], (B, 3, Hp, Wp), False)[0]
+        originals = None
+        for k0, Kc in _samples.chunks(B, K, sample_chunk):
+            chunk = self._sample_chunk(context, all_seeds, k0, Kc, clip_denoised, eta, gamma, sampler)
+            if originals is None or originals.shape[0] != B * Kc:
+                originals = _samples.repeat_images(un, images, Kc)
+            if metric == "lpips":
+                row = metrics.lpips(self.loss_fn_vgg, chunk, originals, size=(H, W), as_saved=as_saved)
+            else:
+                row = getattr(metrics, metric)(un, chunk, originals, size=(H, W), as_saved=as_saved)
+            scores[:, k0:k0 + Kc] = np.asarray(row, np.float64).reshape(B, Kc)
+            pick = []
+            for b in range(B):
+                for k in range(k0, k0 + Kc):
+                    if _samples.better(float(scores[b, k]), float(scores[b, best_k[b]]), higher):
+                        best_k[b] = k
+                pick.append(best_k[b] - k0 if best_k[b] >= k0 else -1)     # (the first chunk always picks: sample 0 when nothing beats it)
+            _samples.select(un, chunk, pick, best, B, Kc)
+        return {"reconstruction": self._window(best, H, W), "bpp": context_dict["bpp"],
+                "seed": np.asarray([all_seeds[b][best_k[b]] for b in range(B)], dtype=np.uint64), "sample": np.asarray(best_k, dtype=np.int64),
+                "score": scores[np.arange(B), best_k], "scores": scores}
 
 
     def compress_to_bytes(self, images, bitrate_scale=None):
@@ -383,6 +482,16 @@ class GaussianDiffusionX(_GaussianDiffusionBase):
         return self._window(rec, H, W), (bpp.mean() if bpp_return_mean else bpp)
 
 
+    def compress_best_of(self, images, samples, metric="psnr", seed=None, gamma=None, eta=0, sample_steps=None, sampler="ddim",
+                         spacing="index", sample_chunk=None, as_saved=True):
+        """The encoder's closed loop: the context model once, then `samples` seeded decodes per image (seeds
+        parallel.sample_seeds(seed, B, samples)), each scored on the device against `images` on the frame's H x W window
+        (metric "psnr" / "ms_ssim": higher is better; "lpips": lower, needs self.loss_fn_vgg; ties go to the lowest k, a NaN never
+        beats a number) -> {"reconstruction": the winner's window, "bpp": [B], "seed": uint64 [B], ready for decompress(..., seed=),
+        "sample": int [B], "score": [B], "scores": [B, samples]}."""
+        return self._best_of(images, samples, metric, seed, gamma, eta, sample_steps, sampler, spacing, sample_chunk, as_saved, True)
+
+
 class GaussianDiffusionEps(_GaussianDiffusionBase):
     """epsilonparam/modules/denoising_diffusion.py:12-215."""
     _param = "eps"
@@ -416,3 +525,9 @@ class GaussianDiffusionEps(_GaussianDiffusionBase):
                  bpp_return_mean=True, init=None, eta=0, seed=None, gamma=None, sampler="ddim", spacing="index"):
         rec, bpp, H, W = self._frame_of(images, sample_steps, bitrate_scale, sample_mode, init, eta, seed, gamma, sampler, spacing)
         return self._window(rec, H, W), (bpp.mean() if bpp_return_mean else bpp)
+
+    def compress_best_of(self, images, samples, metric="psnr", seed=None, gamma=None, eta=0, sample_steps=None, sampler="ddim",
+                         spacing="index", sample_chunk=None, as_saved=True, bitrate_scale=None):
+        """GaussianDiffusionX.compress_best_of with this tree's context argument (bitrate_scale of a variable-bitrate model)."""
+        return self._best_of(images, samples, metric, seed, gamma, eta, sample_steps, sampler, spacing, sample_chunk, as_saved,
+                             self.clip_noise, bitrate_scale)

@@ -41,6 +41,22 @@ def expand_seeds(seed, batch):
     return out
 
 
+def sample_seeds(seed, batch, samples):
+    """The seeds of `samples` seeded decodes per image (`samples=` of decompress, compress_best_of; include/cdc_hip.h states the rule):
+    [batch][samples] ints.  With s_b = expand_seeds(seed, batch)[b], sample k of image b has the seed (s_b + k * 2^32) mod 2^64: sample 0
+    is the seeded decode of the same `seed`, and an int seed never gives two rows the same key (images differ by +1, samples by
+    +2^32).  A 2-D [batch][samples] array of ints in [0, 2^64) is taken as it is."""
+    if isinstance(samples, bool) or not hasattr(samples, "__index__") or int(samples) < 1:
+        raise ValueError(f"samples must be an int >= 1, not {samples!r}")
+    K = int(samples)
+    rows = list(seed) if hasattr(seed, "__len__") else None
+    if rows and all(hasattr(r, "__len__") for r in rows):
+        if len(rows) != batch:
+            raise ValueError(f"{len(rows)} rows of seeds for a batch of {batch}")
+        return [expand_seeds(r, K) for r in rows]
+    return [[(s + (k << 32)) % 2 ** 64 for k in range(K)] for s in expand_seeds(seed, batch)]
+
+
 def shard_seeds(seed, batch, world_size, rank):
     """The seeds of this rank's shard_bounds slice of a `batch`-image job: a sharded seeded decode then equals the unsharded one
     image for image (an image's draws depend on its own seed only)."""

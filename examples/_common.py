@@ -20,14 +20,23 @@ def _shared_options():
                         reconstruction that is already there: cdc_compression_amd.metrics).  Without it the output is unchanged.
       --sampler S       "ddim" (default, the reference's update) or "dpmpp_2m", the second-order multistep solver (eta = 0 only).
       --spacing G       "index" (default, the reference's linspace over train indices) or "logsnr", the grid uniform in logSNR on
-                        which the second-order solver pays off.  Without the two the output is unchanged."""
+                        which the second-order solver pays off.  Without the two the output is unchanged.
+      --samples K       the encoder's closed loop (compress_best_of): K seeded decodes per image, seeds
+                        parallel.sample_seeds(N + k, 1, K) with N = --device_seed (0 without it), each scored against the input on the
+                        device; the best one is saved, and its scores, sample index and seed are printed -- decompress(..., seed=)
+                        with that seed reproduces the saved picture.
+      --select METRIC   the score of --samples: "psnr" (default), "ms_ssim" or "lpips".  Without the two the output is unchanged."""
     import argparse
     p = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
     p.add_argument("--device_seed", type=int, default=None)
     p.add_argument("--metrics", action="store_true")
     p.add_argument("--sampler", choices=("ddim", "dpmpp_2m"), default=None)
     p.add_argument("--spacing", choices=("index", "logsnr"), default=None)
+    p.add_argument("--samples", type=int, default=None)
+    p.add_argument("--select", choices=("psnr", "ms_ssim", "lpips"), default=None)
     opts, sys.argv[1:] = p.parse_known_args(sys.argv[1:])
+    if opts.select is not None and opts.samples is None:
+        p.error("--select METRIC scores the candidates of --samples K")
     return opts
 
 
@@ -109,7 +118,17 @@ def run_folder(diffusion, config, rank, compress_kwargs):
         if img.endswith(".png") or img.endswith(".jpg"):
             to_be_compressed = read_image(os.path.join(config.img_dir, img), rank)
             shape = tuple(to_be_compressed.shape)
-            if device_seed is not None:
+            best = None
+            if SHARED.samples is not None:
+                # --samples K: K candidate seeds per image, the best by --select is kept (bpp is the context model's, as compress()'s)
+                kw = {n: compress_kwargs[n] for n in ("sampler", "spacing", "bitrate_scale", "eta") if n in compress_kwargs}
+                best = diffusion.compress_best_of(to_be_compressed, SHARED.samples, metric=SHARED.select or "psnr",
+                                                  seed=((device_seed or 0) + k) % 2 ** 64, gamma=config.gamma,
+                                                  sample_steps=config.n_denoise_step, **kw)
+                k += 1
+                compressed = best["reconstruction"]
+                bpp = best["bpp"].mean() if compress_kwargs.get("bpp_return_mean", True) else best["bpp"]
+            elif device_seed is not None:
                 # --device_seed N: init = gamma * randn made on the device from seed N + k for the k-th image of the folder (the
                 # library's counter-based generator: the same picture on every host; no torch generator is involved)
                 init = None
@@ -120,12 +139,13 @@ def run_folder(diffusion, config, rank, compress_kwargs):
                                                      std=config.gamma)).to(to_be_compressed.device)
             else:
                 init = torch.randn(shape, device=to_be_compressed.device) * config.gamma
-            compressed, bpp = diffusion.compress(
-                to_be_compressed,
-                sample_steps=config.n_denoise_step,
-                init=init,
-                **compress_kwargs,
-            )
+            if best is None:
+                compressed, bpp = diffusion.compress(
+                    to_be_compressed,
+                    sample_steps=config.n_denoise_step,
+                    init=init,
+                    **compress_kwargs,
+                )
             un = diffusion.denoise_fn
             lp = None
             if diffusion.loss_fn_vgg is not None and min(shape[2:]) >= 16:   # the checkpoint carried the LPIPS-VGG weights
@@ -143,3 +163,7 @@ def run_folder(diffusion, config, rank, compress_kwargs):
                 print("ms_ssim:", "n/a (needs min(H, W) > 160)" if ms is None else float(ms[0]))
             if lp is not None:
                 print("lpips:", float(lp[0]))
+            if best is not None:
+                print("scores:", " ".join(repr(float(v)) for v in best["scores"][0]))
+                print("sample:", int(best["sample"][0]))
+                print("chosen seed:", int(best["seed"][0]))

@@ -233,6 +233,48 @@ int cdc_solver_step(cdc_handle *h, const float *x_in, const float *x0_prev_in, i
 int cdc_op_solver_update(cdc_handle *h, const float *fx, const float *x, const float *x0_prev, int i, float *x_next, float *x0_out,
                          int B, int C, int H, int W, int pred_mode, int clip, int mem, void *stream);
 
+/* ---- K seeded samples per image (no reference counterpart: the reference cannot ask for "sample k") -------------------------------
+ * A seeded decode is a pure function of (stream, seed, gamma, eta, steps), so one stream has as many reconstructions as there are
+ * seeds.  These entry points decode K of them per image through the batch programs and fold or select them on the device
+ * (csrc/sample_kernels.hip).  Everywhere below an array of samples is [B][K][per_image]: row b * K + k is sample k of image b.
+ *
+ * THE SEED RULE (the Python mirror's parallel.sample_seeds; the C entry points take whatever seeds they are given): with s_b the seed
+ *   of image b (an int seed s: s_b = (s + b) mod 2^64), sample k of image b has the seed (s_b + k * 2^32) mod 2^64.  Sample 0 is the
+ *   seeded decode of s_b; images differ in the low key word, samples in the high one.
+ * THE WELFORD ORDER (cdc_sample_moments; a decoder elsewhere that wants the same bits needs it): per element, the samples one after the
+ *   other in the order k = 0 .. K-1, float32 state (mean, m2), starting from zeros:
+ *       cnt = float(count_before + k + 1);   d = x - mean;   mean = mean + d / cnt;   m2 = m2 + d * (x - mean)
+ *   every operation rounded to float32 on its own (no fused multiply-add), the division IEEE-rounded.  The unbiased variance is
+ *   m2 / float(n - 1), one more IEEE division.  The state is two words and the order is fixed, so the result does not depend on how the
+ *   K samples are cut into chunks, bit for bit.
+ *
+ * cdc_repeat_images: dst[b * K + k][e] = src[b][e] for e < per_image; elements of elem_bytes = 4 (float32) or 1 (uint8 images).  16-byte
+ *   accesses when an image is a whole number of 16-byte units and both pointers are 16-byte aligned, element accesses otherwise.
+ * cdc_decode_samples: the loop of cdc_decode_seeded (solver = 0) or cdc_decode_solver (solver = 1: eta must be 0 and cdc_set_solver's
+ *   tables valid) at batch B * K.  ctx[l] holds B images; the library stages each K times in a row (device pointers: the repeat kernel
+ *   reads the caller's tensors; host pointers: through a handle-owned buffer), inside the range-guarded part of the call, so the BF16X3
+ *   repetition restages the context and regenerates every draw from the seeds.  `seeds`: host array of B * K uint64_t, row b * K + k.
+ *   There is no init: the start image is gamma * z(seed, draw 0), or zeros when gamma == 0.  out [B * K][C][H][W].  K = 1 is
+ *   cdc_decode_seeded / cdc_decode_solver without init.  B * K <= 65535 (cdc_randn's limit).  Needs a U-Net handle.
+ * cdc_sample_moments: folds the chunk samples [B][Kc][per_image] into mean [B][per_image] and m2 [B][per_image] (m2 may be NULL: the
+ *   mean only) by the update above, the count continuing from count_before.  count_before == 0: the accumulators are not read.
+ *   finish != 0: m2 <- m2 / float(n - 1) after the last sample, n = count_before + Kc >= 2 the final count.
+ * cdc_sample_select: for every image b with pick[b] >= 0, best[b] <- samples[b][pick[b]] bit for bit (NaN payloads included);
+ *   pick[b] < 0 leaves best[b] as it is.  `pick`: host array of B ints, staged through the handle.
+ * CDC_ERR_INVALID, with a message: B, K (Kc) or per_image < 1; B * K > 65535 for cdc_decode_samples; elem_bytes not 1 or 4;
+ *   count_before < 0; finish with a final count < 2; pick[b] >= Kc; null pointers.
+ * cdc_repeat_images, cdc_sample_moments and cdc_sample_select take any handle kind (its device, stream and error state only).  All four
+ * run through the same guard / error runner as every entry point and follow `mem` / `stream` as cdc_decode does. */
+int cdc_repeat_images(cdc_handle *h, const void *src, void *dst, int B, int K, int64_t per_image, int elem_bytes /* 1 | 4 */, int mem,
+                      void *stream);
+int cdc_decode_samples(cdc_handle *h, float gamma, const uint64_t *seeds /* [B * K], host */, float eta, const float *const *ctx /* B images */,
+                       int n_ctx, float *out /* [B * K][C][H][W] */, int B, int K, int H, int W, int pred_mode, int clip,
+                       int solver /* 0 ddim, 1 the multistep update */, int mem, void *stream);
+int cdc_sample_moments(cdc_handle *h, const float *samples, int B, int Kc, int64_t per_image, int count_before, float *mean,
+                       float *m2 /* nullable */, int finish, int mem, void *stream);
+int cdc_sample_select(cdc_handle *h, const float *samples, const int *pick /* [B], host */, float *best, int B, int Kc, int64_t per_image,
+                      int mem, void *stream);
+
 /* ---- measurement --------------------------------------------------------------------------- */
 
 /* ---- context decoder: Compressor.decode ---------------------------- */
