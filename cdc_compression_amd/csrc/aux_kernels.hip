@@ -1,12 +1,11 @@
 // aux_kernels.hip -- the non-GEMM kernels of the decode path: standalone channel LayerNorm,
-// time-embedding MLPs, k-softmax statistics, linear-attention context (k.v^T on MFMA), DDIM update.
+// time-embedding MLPs, k-softmax statistics, linear-attention context (k.v^T on MFMA).
 #include <math.h>
 
 #include <algorithm>
 #include <stdlib.h>
 
 #include "cdc_internal.h"
-#include "rng.h"
 
 namespace cdc {
 
@@ -1383,307 +1382,6 @@ hipError_t fold_combine_launch(const CombineArgs &a, int B, hipStream_t st) {
     const int gx = (int)std::min<size_t>(((size_t)a.H * a.W + 255) / 256, 1024);
     hipLaunchKernelGGL(fold_combine_kernel, dim3(gx, a.Cout, B), dim3(256), 0, st, a.P, a.bias, a.out, a.Cout, a.KH,
                        a.pad, a.H, a.W);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------
-// DDIM update.  x-param: xparam/modules/denoising_diffusion.py:152-174 ; eps-param:
-// epsilonparam/modules/denoising_diffusion.py:137-152.  Same operation order as the reference.
-// ---------------------------------------------------------------------------------------------
-// One element of the update (denoising_diffusion.py ddim(), both trees); shared by the two kernels below.  No fused multiply-adds
-// (fp contract off): every product and sum is rounded on its own, as the reference's element-wise tensor operations round them -- and the
-// scalar and the four-pixel kernel then hold the same bits whatever hipcc packs (left to the contraction heuristics the two differed in
-// the last bit, which a 30-step eps-param chain amplifies to 7e-4).
-struct DdimConsts { float c_recip, c_recipm1, c_acp, c_eps, c_sac, c_s1mac, sig; int pred_mode; };
-__device__ __forceinline__ float ddim_update(const DdimConsts &k, float fx, float x, float noise, bool clip, bool has_noise) {
-#pragma clang fp contract(off)
-    float x0, eps;
-    if (k.pred_mode == 0 || k.pred_mode == 3) {
-        x0 = k.pred_mode == 0 ? fx : k.c_sac * x - k.c_s1mac * fx;
-        if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-        eps = (k.c_recip * x - x0) / k.c_recipm1;
-    } else {
-        eps = fx;
-        x0 = k.c_recip * x - k.c_recipm1 * eps;
-        if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-    }
-    float xn = k.c_acp * x0 + k.c_eps * eps;
-    if (has_noise) xn += k.sig * noise;
-    return xn;
-}
-
-// SEEDED: the step's noise comes from the generator of rng.h (DdimArgs::seeds), draw number = step index + 1, instead of a tensor.  A
-// compile-time instance of its own, so that the eta = 0 / noise-tensor kernels keep the code they had.
-template <bool SEEDED>
-__global__ void __launch_bounds__(256) ddim_kernel(const DdimArgs a) {
-    const int si = a.step_ptr ? *a.step_ptr : a.i;
-    const float c_recip = a.tab[0 * a.steps + si];
-    const float c_recipm1 = a.tab[1 * a.steps + si];
-    const float c_acp = a.tab[2 * a.steps + si];
-    const float c_1macp = a.tab[3 * a.steps + si];
-    const float sig = a.eta * a.tab[4 * a.steps + si];
-    // pred_mode 3 ("v", xparam :128-139,161-162): x0 = sqrt(ac) x - sqrt(1 - ac) v
-    const float c_sac = a.tab_v ? a.tab_v[si] : 0.f, c_s1mac = a.tab_v ? a.tab_v[a.steps + si] : 0.f;
-    float var = c_1macp - sig * sig;
-    // x-tree (pred_mode 0 "x", 2 "noise", 3 "v"): .clamp(min=0) under the square root (xparam :169); eps-tree: none
-    if (a.pred_mode != 1) var = fmaxf(var, 0.f);
-    const float c_eps = sqrtf(var);
-    // clip: 0 none, 1 every image, 2 the first B/2 images only (eps-tree clip_noise "half", eps :142-143)
-    const long long clip_n = a.clip == 1 ? a.n : (a.clip == 2 ? a.clip_half_n : 0);
-    const DdimConsts kc{c_recip, c_recipm1, c_acp, c_eps, c_sac, c_s1mac, sig, a.pred_mode};
-    bool bad = false;
-    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < a.n;
-         idx += (long long)gridDim.x * blockDim.x) {
-        float fx;
-        if (a.P) {
-            // the 7-row combine of the row-folded final convolution (fold_combine_kernel) evaluated here: out_fx is never written
-            const long long plane = (long long)a.pH * a.pW, img_co = idx / plane;      // = b * Cout + co
-            const int pix = (int)(idx - img_co * plane), y = pix / a.pW;
-            const float *p = a.P + (size_t)img_co * a.pKH * plane + pix;
-            fx = a.P_bias ? a.P_bias[(int)(img_co % a.pC)] : 0.f;
-            for (int ky = 0; ky < a.pKH; ++ky) {
-                const int r = y + ky - a.pPad;
-                if (r >= 0 && r < a.pH) fx += p[(size_t)ky * plane + (long long)(ky - a.pPad) * a.pW];
-            }
-        } else {
-            fx = a.fx[idx];
-        }
-        const float x = a.x[idx];
-        bad |= !(fabsf(fx) <= 3.0e38f);                    // inf / NaN from the U-Net (fp16-plane range overflow)
-        if constexpr (SEEDED) {
-            // the quad of this element, then its lane (frames whose width is no multiple of 4: ddim_rows4_kernel's draws, one by one)
-            const long long b = idx / a.per_image, e = idx - b * a.per_image;
-            float z[4];
-            cdcrng::normal4(a.seeds[b], (uint32_t)(e >> 2), (uint32_t)si + 1u, z);
-            const int lane = (int)(e & 3);
-            const float nz = lane == 0 ? z[0] : lane == 1 ? z[1] : lane == 2 ? z[2] : z[3];
-            a.x_next[idx] = ddim_update(kc, fx, x, nz, idx < clip_n, true);
-        } else
-        a.x_next[idx] = ddim_update(kc, fx, x, a.noise ? a.noise[idx] : 0.f, idx < clip_n, a.noise != nullptr);
-    }
-    if (bad && a.fault) *a.fault = 1;                      // sticky, read by the host after the decode
-}
-
-// The same update with the 7-row combine, four consecutive pixels of one (image, channel) plane per thread (pW % 4 == 0; round 4):
-// 16-byte loads / stores, the (image, channel) index is blockIdx.y.  ddim_kernel's element loop derives (plane, pixel) from a 64-bit
-// element index -- two 64-bit divisions per element made it VALU-bound (90 us per launch at batch 32 for 0.23 GB of traffic).
-// Same sums in the same order, same expressions per component: same bits.
-template <bool SEEDED>
-__global__ void __launch_bounds__(256) ddim_rows4_kernel(const DdimArgs a) {
-    const int si = a.step_ptr ? *a.step_ptr : a.i;
-    const float c_recip = a.tab[0 * a.steps + si];
-    const float c_recipm1 = a.tab[1 * a.steps + si];
-    const float c_acp = a.tab[2 * a.steps + si];
-    const float c_1macp = a.tab[3 * a.steps + si];
-    const float sig = a.eta * a.tab[4 * a.steps + si];
-    const float c_sac = a.tab_v ? a.tab_v[si] : 0.f, c_s1mac = a.tab_v ? a.tab_v[a.steps + si] : 0.f;
-    float var = c_1macp - sig * sig;
-    if (a.pred_mode != 1) var = fmaxf(var, 0.f);
-    const float c_eps = sqrtf(var);
-    const long long clip_n = a.clip == 1 ? a.n : (a.clip == 2 ? a.clip_half_n : 0);
-    const int plane = a.pH * a.pW;
-    const int pix = 4 * (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (pix >= plane) return;
-    const int img_co = blockIdx.y, y = pix / a.pW;
-    const long long idx = (long long)img_co * plane + pix;
-    const float *p = a.P + (size_t)img_co * a.pKH * plane + pix;
-    const float b0 = a.P_bias ? a.P_bias[img_co % a.pC] : 0.f;
-    float fx[4] = {b0, b0, b0, b0};
-    for (int ky = 0; ky < a.pKH; ++ky) {
-        const int r = y + ky - a.pPad;
-        if (r >= 0 && r < a.pH) {
-            const float4 q = *reinterpret_cast<const float4 *>(p + (size_t)ky * plane + (long long)(ky - a.pPad) * a.pW);
-            fx[0] += q.x; fx[1] += q.y; fx[2] += q.z; fx[3] += q.w;
-        }
-    }
-    const float4 x4 = *reinterpret_cast<const float4 *>(a.x + idx);
-    const float xs[4] = {x4.x, x4.y, x4.z, x4.w};
-    float nz[4] = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (SEEDED) {
-        // one Philox call: the four normals of these four pixels (plane % 4 == 0, so they are one quad of the image's own tensor)
-        const int b = img_co / a.pC;
-        const long long e = (long long)(img_co - b * a.pC) * plane + pix;
-        cdcrng::normal4(a.seeds[b], (uint32_t)(e >> 2), (uint32_t)si + 1u, nz);
-    } else
-    if (a.noise) { const float4 n4 = *reinterpret_cast<const float4 *>(a.noise + idx); nz[0] = n4.x; nz[1] = n4.y; nz[2] = n4.z; nz[3] = n4.w; }
-    const bool clip = idx < clip_n;                       // (clip_n is a whole number of images)
-    const DdimConsts kc{c_recip, c_recipm1, c_acp, c_eps, c_sac, c_s1mac, sig, a.pred_mode};
-    bool bad = false;
-    float out[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        bad |= !(fabsf(fx[c]) <= 3.0e38f);
-        out[c] = ddim_update(kc, fx[c], xs[c], nz[c], clip, SEEDED || a.noise != nullptr);
-    }
-    *reinterpret_cast<float4 *>(a.x_next + idx) = make_float4(out[0], out[1], out[2], out[3]);
-    if (bad && a.fault) *a.fault = 1;
-}
-
-// end of a graph-replayed DDIM iteration: the next replay works on step - 1
-__global__ void step_dec_kernel(int *step) { *step -= 1; }
-
-hipError_t step_dec_launch(int *step, hipStream_t st) {
-    hipLaunchKernelGGL(step_dec_kernel, dim3(1), dim3(1), 0, st, step);
-    return hipGetLastError();
-}
-
-hipError_t ddim_launch(const DdimArgs &a, hipStream_t st) {
-    const long long plane = (long long)a.pH * a.pW;
-    if (a.P && plane > 0 && (a.pW & 3) == 0 && plane < (1ll << 30) && a.n % plane == 0 && a.n / plane <= 65535 &&
-        (((uintptr_t)a.P | (uintptr_t)a.x | (uintptr_t)a.x_next | (uintptr_t)a.noise) & 15) == 0) {
-        const dim3 g((unsigned)ceil_div(plane / 4, 256), (unsigned)(a.n / plane));
-        if (a.seeds) hipLaunchKernelGGL(ddim_rows4_kernel<true>, g, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(ddim_rows4_kernel<false>, g, dim3(256), 0, st, a);
-        return hipGetLastError();
-    }
-    const int grid = (int)std::min<long long>((a.n + 255) / 256, 4096);
-    if (a.seeds) hipLaunchKernelGGL(ddim_kernel<true>, dim3(grid), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(ddim_kernel<false>, dim3(grid), dim3(256), 0, st, a);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------
-// Second-order multistep update (DPM-Solver++ 2M in data-prediction form; SolverArgs, include/cdc_hip.h).  Kernels of their own
-// beside the DDIM pair, which keeps its code: the same prediction x0 (ddim_update's expressions, clip included), then
-// x_next = ((a x) + (b x0)) + (c x0_prev) with every product and sum rounded on its own (fp contract off, so the scalar and the
-// four-pixel form hold the same bits), and x0 written over x0_prev by the thread that read it.  20 bytes per element where fx
-// is a tensor; bound by memory.
-// ---------------------------------------------------------------------------------------------
-struct SolverConsts { float c_recip, c_recipm1, c_sac, c_s1mac, a, b, c; int pred_mode; };
-__device__ __forceinline__ SolverConsts solver_consts(const SolverArgs &a) {
-    const int si = a.step_ptr ? *a.step_ptr : a.i;
-    return {a.tab[0 * a.steps + si], a.tab[1 * a.steps + si], a.tab_v ? a.tab_v[si] : 0.f, a.tab_v ? a.tab_v[a.steps + si] : 0.f,
-            a.stab[0 * a.steps + si], a.stab[1 * a.steps + si], a.stab[2 * a.steps + si], a.pred_mode};
-}
-__device__ __forceinline__ float solver_x0(const SolverConsts &k, float fx, float x, bool clip) {
-#pragma clang fp contract(off)
-    float x0;
-    if (k.pred_mode == 0) x0 = fx;
-    else if (k.pred_mode == 3) x0 = k.c_sac * x - k.c_s1mac * fx;
-    else x0 = k.c_recip * x - k.c_recipm1 * fx;
-    if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-    return x0;
-}
-__device__ __forceinline__ float solver_next(const SolverConsts &k, float x, float x0, float x0_prev) {
-#pragma clang fp contract(off)
-    const float t0 = k.a * x, t1 = k.b * x0, t2 = k.c * x0_prev;
-    return (t0 + t1) + t2;
-}
-
-__global__ void __launch_bounds__(256) solver_kernel(const SolverArgs a) {
-    const SolverConsts kc = solver_consts(a);
-    const long long clip_n = a.clip == 1 ? a.n : (a.clip == 2 ? a.clip_half_n : 0);
-    bool bad = false;
-    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < a.n;
-         idx += (long long)gridDim.x * blockDim.x) {
-        float fx;
-        if (a.P) {
-            const long long plane = (long long)a.pH * a.pW, img_co = idx / plane;      // = b * Cout + co
-            const int pix = (int)(idx - img_co * plane), y = pix / a.pW;
-            const float *p = a.P + (size_t)img_co * a.pKH * plane + pix;
-            fx = a.P_bias ? a.P_bias[(int)(img_co % a.pC)] : 0.f;
-            for (int ky = 0; ky < a.pKH; ++ky) {
-                const int r = y + ky - a.pPad;
-                if (r >= 0 && r < a.pH) fx += p[(size_t)ky * plane + (long long)(ky - a.pPad) * a.pW];
-            }
-        } else {
-            fx = a.fx[idx];
-        }
-        bad |= !(fabsf(fx) <= 3.0e38f);
-        const float x = a.x[idx];
-        const float x0 = solver_x0(kc, fx, x, idx < clip_n);
-        a.x_next[idx] = solver_next(kc, x, x0, a.hist[idx]);
-        a.hist[idx] = x0;
-    }
-    if (bad && a.fault) *a.fault = 1;
-}
-
-// Four consecutive pixels of one (image, channel) plane per thread (pW % 4 == 0), 16-byte accesses, blockIdx.y = the plane.
-__global__ void __launch_bounds__(256) solver_rows4_kernel(const SolverArgs a) {
-    const SolverConsts kc = solver_consts(a);
-    const long long clip_n = a.clip == 1 ? a.n : (a.clip == 2 ? a.clip_half_n : 0);
-    const int plane = a.pH * a.pW;
-    const int pix = 4 * (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (pix >= plane) return;
-    const int img_co = blockIdx.y, y = pix / a.pW;
-    const long long idx = (long long)img_co * plane + pix;
-    float fx[4];
-    if (a.P) {
-        const float *p = a.P + (size_t)img_co * a.pKH * plane + pix;
-        const float b0 = a.P_bias ? a.P_bias[img_co % a.pC] : 0.f;
-        fx[0] = fx[1] = fx[2] = fx[3] = b0;
-        for (int ky = 0; ky < a.pKH; ++ky) {
-            const int r = y + ky - a.pPad;
-            if (r >= 0 && r < a.pH) {
-                const float4 q = *reinterpret_cast<const float4 *>(p + (size_t)ky * plane + (long long)(ky - a.pPad) * a.pW);
-                fx[0] += q.x; fx[1] += q.y; fx[2] += q.z; fx[3] += q.w;
-            }
-        }
-    } else {
-        const float4 q = *reinterpret_cast<const float4 *>(a.fx + idx);
-        fx[0] = q.x; fx[1] = q.y; fx[2] = q.z; fx[3] = q.w;
-    }
-    const float4 x4 = *reinterpret_cast<const float4 *>(a.x + idx);
-    const float4 h4 = *reinterpret_cast<const float4 *>(a.hist + idx);
-    const float xs[4] = {x4.x, x4.y, x4.z, x4.w}, hs[4] = {h4.x, h4.y, h4.z, h4.w};
-    const bool clip = idx < clip_n;                       // (clip_n is a whole number of images)
-    bool bad = false;
-    float out[4], x0[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        bad |= !(fabsf(fx[c]) <= 3.0e38f);
-        x0[c] = solver_x0(kc, fx[c], xs[c], clip);
-        out[c] = solver_next(kc, xs[c], x0[c], hs[c]);
-    }
-    *reinterpret_cast<float4 *>(a.x_next + idx) = make_float4(out[0], out[1], out[2], out[3]);
-    *reinterpret_cast<float4 *>(a.hist + idx) = make_float4(x0[0], x0[1], x0[2], x0[3]);
-    if (bad && a.fault) *a.fault = 1;
-}
-
-// ddim_launch's rule (a given fx tensor takes the four-pixel form too, read 16 bytes at a time)
-hipError_t solver_launch(const SolverArgs &a, hipStream_t st) {
-    const long long plane = (long long)a.pH * a.pW;
-    if (a.n <= 0) return hipErrorInvalidValue;
-    if (plane > 0 && (a.pW & 3) == 0 && plane < (1ll << 30) && a.n % plane == 0 && a.n / plane <= 65535 &&
-        (((uintptr_t)a.P | (uintptr_t)a.fx | (uintptr_t)a.x | (uintptr_t)a.x_next | (uintptr_t)a.hist) & 15) == 0) {
-        const dim3 g((unsigned)ceil_div(plane / 4, 256), (unsigned)(a.n / plane));
-        hipLaunchKernelGGL(solver_rows4_kernel, g, dim3(256), 0, st, a);
-        return hipGetLastError();
-    }
-    const int grid = (int)std::min<long long>((a.n + 255) / 256, 4096);
-    hipLaunchKernelGGL(solver_kernel, dim3(grid), dim3(256), 0, st, a);
-    return hipGetLastError();
-}
-
-// out[b][e] = scale * z(seeds[b], draw, e): the start image of a seeded decode and cdc_randn.  One quad of rng.h per thread; a
-// 16-byte store where every image starts on a 16-byte boundary (per_image % 4 == 0), element stores with a bound otherwise.
-template <bool VEC>
-__global__ void __launch_bounds__(256) randn_fill_kernel(const unsigned long long *seeds, long long per_image, unsigned draw,
-                                                         float scale, float *out) {
-    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (4 * q >= per_image) return;
-    const int b = blockIdx.y;
-    float z[4];
-    cdcrng::normal4(seeds[b], (uint32_t)q, draw, z);
-    float *o = out + (size_t)b * per_image + 4 * q;
-    if constexpr (VEC) {
-        *reinterpret_cast<float4 *>(o) = make_float4(scale * z[0], scale * z[1], scale * z[2], scale * z[3]);
-    } else {
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-            if (4 * q + c < per_image) o[c] = scale * z[c];
-    }
-}
-
-hipError_t randn_fill_launch(const unsigned long long *seeds, int B, long long per_image, unsigned draw, float scale, float *out,
-                             hipStream_t st) {
-    const long long nq = (per_image + 3) / 4;
-    if (B < 1 || B > 65535 || per_image < 1 || nq > (1ll << 32)) return hipErrorInvalidValue;
-    const dim3 g((unsigned)((nq + 255) / 256), (unsigned)B);
-    if ((per_image & 3) == 0 && ((uintptr_t)out & 15) == 0)
-        hipLaunchKernelGGL(randn_fill_kernel<true>, g, dim3(256), 0, st, seeds, per_image, draw, scale, out);
-    else
-        hipLaunchKernelGGL(randn_fill_kernel<false>, g, dim3(256), 0, st, seeds, per_image, draw, scale, out);
     return hipGetLastError();
 }
 

@@ -86,10 +86,10 @@ int run_pre(cdc_handle *h, hipStream_t st) {
 // step < 0: plain Unet.forward with the caller's per-image time values.
 int run_unet(cdc_handle *h, hipStream_t st, int step, bool skip_combine) {
     for (const Op &op : h->ops) {
-        if (skip_combine && op.get<CombineArgs>()) continue;      // (the sampler kernel evaluates it: ddim_on_device)
+        if (skip_combine && op.get<CombineArgs>()) continue;      // (the sampler kernel evaluates it: sampler_on_device)
         int rc;
         if (op.get<TembArgs>() && (step >= 0 || step == -2)) {      // the shifts of the step: a row of the per-decode table, under TEMB's id
-            CopyArgs c = {h->d_shift_tab + (step >= 0 ? (size_t)step * h->shift_bs : 0), 0, h->shift, h->shift_bs, h->shift_bs};
+            CopyArgs c = {h->d_shift_tab.p + (step >= 0 ? (size_t)step * h->shift_bs : 0), 0, h->shift, h->shift_bs, h->shift_bs};
             if (step == -2) { c.step = h->d_step; c.step_stride = h->shift_bs; }
             Op cop(op.prof, c, op.flops, op.bytes);
             cop.id = op.id;
@@ -142,20 +142,14 @@ int stage_ctx_repeated(cdc_handle *h, const float *const *ctx, int n_ctx, int B,
         if (!ctx[l]) return fail(h, CDC_ERR_INVALID, "null context tensor %d", l);
         need = std::max(need, (size_t)B * (size_t)h->in_ctx[l].bs());
     }
-    if (mem == CDC_MEM_HOST && need > h->rep_stage_cap) {
-        HIP_TRY(h, hipDeviceSynchronize());
-        if (h->d_rep_stage) { (void)hipFree(h->d_rep_stage); h->d_rep_stage = nullptr; h->rep_stage_cap = 0; }
-        void *p = nullptr;
-        HIP_TRY(h, hipMalloc(&p, need * sizeof(float)));
-        h->d_rep_stage = (float *)p;
-        h->rep_stage_cap = need;
-    }
+    int rc = mem == CDC_MEM_HOST ? h->d_rep_stage.grow(h, need) : CDC_OK;
+    if (rc) return rc;
     for (int l = 0; l < n_ctx; ++l) {
         const long long per = h->in_ctx[l].bs();
         const float *src = ctx[l];
         if (mem == CDC_MEM_HOST) {
-            HIP_TRY(h, hipMemcpyAsync(h->d_rep_stage, ctx[l], (size_t)B * per * sizeof(float), hipMemcpyHostToDevice, st));
-            src = h->d_rep_stage;
+            HIP_TRY(h, hipMemcpyAsync(h->d_rep_stage.p, ctx[l], (size_t)B * per * sizeof(float), hipMemcpyHostToDevice, st));
+            src = h->d_rep_stage.p;
         }
         HIP_TRY(h, repeat_images_launch({src, h->in_ctx[l].p, per, K, 4}, B, st));
     }
@@ -310,15 +304,15 @@ void cdc_destroy(cdc_handle *h) {
     (void)hipDeviceSynchronize();
     free_program(h);
     free_pool(&h->weight_allocs);
-    if (h->d_tab) (void)hipFree(h->d_tab);
-    if (h->d_tab_v) (void)hipFree(h->d_tab_v);
-    if (h->d_time_steps) (void)hipFree(h->d_time_steps);
-    if (h->d_shift_tab) (void)hipFree(h->d_shift_tab);
-    if (h->d_seeds) (void)hipFree(h->d_seeds);
-    if (h->d_stab) (void)hipFree(h->d_stab);
-    if (h->d_hist) (void)hipFree(h->d_hist);
-    if (h->d_rep_stage) (void)hipFree(h->d_rep_stage);
-    if (h->d_pick) (void)hipFree(h->d_pick);
+    h->d_tab.release();
+    h->d_tab_v.release();
+    h->d_time_steps.release();
+    h->d_shift_tab.release();
+    h->seeds.dev.release();
+    h->d_stab.release();
+    h->d_hist.release();
+    h->d_rep_stage.release();
+    h->picks.dev.release();
     if (h->metric_work) (void)hipFree(h->metric_work);
     (void)resolve_pending(h);
     for (hipEvent_t e : h->ev_free) (void)hipEventDestroy(e);
@@ -846,16 +840,12 @@ int cdc_set_schedule(cdc_handle *h, int steps, const float *time_in, const float
     const float *srcs[5] = {sqrt_recip, sqrt_recipm1, sqrt_ac_prev, one_minus_ac_prev, sigma};
     for (int k = 0; k < 5; ++k) memcpy(&tab[(size_t)k * steps], srcs[k], sizeof(float) * steps);
     // compress() / decompress() set the schedule on every call: the same tables again change nothing
-    if (h->d_tab && h->steps == steps && tab == h->h_tab && (int)h->h_time_in.size() == steps &&
+    if (h->d_tab.p && h->steps == steps && tab == h->h_tab && (int)h->h_time_in.size() == steps &&
         memcmp(h->h_time_in.data(), time_in, sizeof(float) * steps) == 0)
         return CDC_OK;
     HIP_TRY(h, hipDeviceSynchronize());
-    if (tab.size() > h->tab_cap) {       // grow only; the buffer keeps its address otherwise
-        if (h->d_tab) { (void)hipFree(h->d_tab); h->d_tab = nullptr; }
-        HIP_TRY(h, hipMalloc((void **)&h->d_tab, tab.size() * sizeof(float)));
-        h->tab_cap = tab.size();
-    }
-    HIP_TRY(h, hipMemcpy(h->d_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+    if ((rc0 = h->d_tab.grow(h, tab.size()))) return rc0;
+    HIP_TRY(h, hipMemcpy(h->d_tab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
     h->h_tab.swap(tab);
     h->h_time_in.assign(time_in, time_in + steps);
     h->steps = steps;
@@ -869,27 +859,16 @@ int cdc_set_schedule(cdc_handle *h, int steps, const float *time_in, const float
 // network_components.py:96-100) depend on nothing else: evaluate them for every sample step in one
 // launch (one workgroup per step) and broadcast row i at iteration i.
 static int ensure_time_rows(cdc_handle *h, int B) {
-    if (h->d_shift_tab && h->time_steps_B == B) return CDC_OK;
-    const size_t need = (size_t)h->steps * (h->shift_bs + 1);
-    if (need > h->trows_cap) {           // owned by the handle (not by the launch program): reused across schedules
-        if (h->d_time_steps) (void)hipFree(h->d_time_steps);
-        if (h->d_shift_tab) (void)hipFree(h->d_shift_tab);
-        h->d_time_steps = h->d_shift_tab = nullptr;
-        h->trows_cap = 0;
-        if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }   // it baked the old addresses
-        void *p = nullptr, *q = nullptr;
-        HIP_TRY(h, hipMalloc(&p, (size_t)h->steps * sizeof(float)));
-        h->d_time_steps = (float *)p;
-        HIP_TRY(h, hipMalloc(&q, (size_t)h->steps * h->shift_bs * sizeof(float)));
-        h->d_shift_tab = (float *)q;
-        h->trows_cap = need;
-    }
-    HIP_TRY(h, hipMemcpy(h->d_time_steps, h->h_time_in.data(), (size_t)h->steps * sizeof(float), hipMemcpyHostToDevice));
+    if (h->d_shift_tab.p && h->time_steps_B == B) return CDC_OK;
+    int rc = h->d_time_steps.grow(h, (size_t)h->steps);
+    if (!rc) rc = h->d_shift_tab.grow(h, (size_t)h->steps * h->shift_bs);
+    if (rc) return rc;
+    HIP_TRY(h, hipMemcpy(h->d_time_steps.p, h->h_time_in.data(), (size_t)h->steps * sizeof(float), hipMemcpyHostToDevice));
     h->time_steps_B = B;
     TembArgs t;
-    t.time = h->d_time_steps; t.w0 = h->tm_w0; t.b0 = h->tm_b0; t.w2 = h->tm_w2; t.b2 = h->tm_b2;
+    t.time = h->d_time_steps.p; t.w0 = h->tm_w0; t.b0 = h->tm_b0; t.w2 = h->tm_w2; t.b2 = h->tm_b2;
     t.dim = h->cfg.dim; t.layers = h->d_temb_layers; t.n_layers = (int)h->rbs.size();
-    t.shift = h->d_shift_tab; t.shift_bs = h->shift_bs;
+    t.shift = h->d_shift_tab.p; t.shift_bs = h->shift_bs;
     HIP_TRY(h, temb_launch(t, h->steps, h->own_stream));
     HIP_TRY(h, hipStreamSynchronize(h->own_stream));
     return CDC_OK;
@@ -905,13 +884,8 @@ int cdc_set_schedule_v(cdc_handle *h, int steps, const float *sqrt_ac, const flo
     memcpy(&tab[0], sqrt_ac, sizeof(float) * steps);
     memcpy(&tab[steps], sqrt_one_minus_ac, sizeof(float) * steps);
     HIP_TRY(h, hipDeviceSynchronize());
-    if (steps > h->tab_v_steps) {
-        if (h->d_tab_v) { (void)hipFree(h->d_tab_v); h->d_tab_v = nullptr; }
-        HIP_TRY(h, hipMalloc((void **)&h->d_tab_v, tab.size() * sizeof(float)));
-        h->tab_v_steps = steps;
-    }
-    HIP_TRY(h, hipMemcpy(h->d_tab_v, tab.data(), sizeof(float) * steps, hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(h->d_tab_v + h->steps, tab.data() + steps, sizeof(float) * steps, hipMemcpyHostToDevice));
+    if ((rc0 = h->d_tab_v.grow(h, tab.size()))) return rc0;
+    HIP_TRY(h, hipMemcpy(h->d_tab_v.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
     h->tab_v_gen = h->sched_gen;
     return CDC_OK;
 }
@@ -928,15 +902,11 @@ int cdc_set_solver(cdc_handle *h, int steps, const float *a, const float *b, con
         for (int k = 0; k < 3; ++k) memcpy(&tab[(size_t)k * steps], srcs[k], sizeof(float) * steps);
         for (float v : tab)
             if (!(fabsf(v) <= 3.0e38f)) return fail(h, CDC_ERR_INVALID, "cdc_set_solver: a table value is not finite");
-        if (h->d_stab && h->stab_sched_gen == h->sched_gen && tab == h->h_stab) return CDC_OK;    // the same tables again change nothing
+        if (h->d_stab.p && h->stab_sched_gen == h->sched_gen && tab == h->h_stab) return CDC_OK;    // the same tables again change nothing
         HIP_TRY(h, hipDeviceSynchronize());
-        if (tab.size() > h->stab_cap) {       // grow only; the buffer keeps its address otherwise
-            if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }   // it baked the old address
-            if (h->d_stab) { (void)hipFree(h->d_stab); h->d_stab = nullptr; h->stab_cap = 0; }
-            HIP_TRY(h, hipMalloc((void **)&h->d_stab, tab.size() * sizeof(float)));
-            h->stab_cap = tab.size();
-        }
-        HIP_TRY(h, hipMemcpy(h->d_stab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+        int rc = h->d_stab.grow(h, tab.size());
+        if (rc) return rc;
+        HIP_TRY(h, hipMemcpy(h->d_stab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
         h->h_stab.swap(tab);
         h->stab_sched_gen = h->sched_gen;
         ++h->solver_gen;
@@ -944,121 +914,101 @@ int cdc_set_solver(cdc_handle *h, int steps, const float *a, const float *b, con
     });
 }
 
-// What every solver entry point needs beyond the DDIM ones' checks: tables of the current schedule, and pred_mode "v"'s.
-static int solver_ready(cdc_handle *h, int pred_mode, int clip) {
+// What every sampler entry point needs: a schedule, a model whose output has the image's shape, pred_mode / clip in range, the tables
+// of pred_mode "v" and -- solver -- those of the multistep update, both of the current schedule.
+static int sampler_ready(cdc_handle *h, int pred_mode, int clip, bool solver) {
     if (!h->steps) return fail(h, CDC_ERR_STATE, "cdc_set_schedule has not been called");
+    if (h->out_dim != h->cfg.channels) return fail(h, CDC_ERR_UNSUPPORTED, "sampler needs out_dim == channels");
     if (pred_mode < 0 || pred_mode > 3 || clip < 0 || clip > 2) return fail(h, CDC_ERR_INVALID, "pred_mode %d / clip %d out of range", pred_mode, clip);
-    if (!h->d_stab || h->stab_sched_gen != h->sched_gen)
+    if (solver && (!h->d_stab.p || h->stab_sched_gen != h->sched_gen))
         return fail(h, CDC_ERR_STATE, "the solver needs cdc_set_solver after cdc_set_schedule");
-    if (pred_mode == CDC_PRED_V && (!h->d_tab_v || h->tab_v_gen != h->sched_gen))
+    if (pred_mode == CDC_PRED_V && (!h->d_tab_v.p || h->tab_v_gen != h->sched_gen))
         return fail(h, CDC_ERR_STATE, "pred_mode \"v\" needs cdc_set_schedule_v after cdc_set_schedule");
     return CDC_OK;
 }
 
-// The history buffer of the solver: n floats, grow only (a captured graph holds its address).
-static int ensure_hist(cdc_handle *h, size_t n) {
-    if (n <= h->hist_cap) return CDC_OK;
-    HIP_TRY(h, hipDeviceSynchronize());
-    if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
-    if (h->d_hist) { (void)hipFree(h->d_hist); h->d_hist = nullptr; h->hist_cap = 0; }
-    void *p = nullptr;
-    HIP_TRY(h, hipMalloc(&p, n * sizeof(float)));
-    h->d_hist = (float *)p;
-    h->hist_cap = n;
-    return CDC_OK;
+// What the two update rules share, for B x C x H x W elements at step i (i = -2: the step index comes from h->d_step, graph capture)
+static SamplerArgs sampler_args(cdc_handle *h, const float *fx, const float *x, float *x_next, int i, int B, int C, int H, int W, int pred_mode,
+                                int clip, int *fault) {
+    SamplerArgs s = {fx, x, x_next, h->d_tab.p, pred_mode == CDC_PRED_V ? h->d_tab_v.p : nullptr, h->steps, i < 0 ? 0 : i,
+                     i == -2 ? h->d_step : nullptr, pred_mode, clip, (long long)B * C * H * W, (long long)(B / 2) * C * H * W, fault};
+    s.pC = C; s.pH = H; s.pW = W;
+    return s;
 }
 
-// One iteration of the multistep sampler: the U-Net on h->in_x, then x_out = a x + b x0 + c hist, hist <- x0 (h->d_hist, in place).
-static int solver_on_device(cdc_handle *h, int i, float *x_out, int B, int H, int W, int pred_mode, int clip, hipStream_t st) {
+// The noise of a DDIM step (eta != 0): a tensor, or the per-image seeds of the generator on the device
+struct StepNoise { const float *tensor = nullptr; const unsigned long long *seeds = nullptr; };
+
+// One iteration: the U-Net on h->in_x, then the update h->in_x -> x_out.  solver: x_out = a x + b x0 + c hist, hist <- x0 (h->d_hist, in
+// place); else the DDIM update with `noise`.  The 7-row combine of the final convolution rides in the sampler kernel (one launch and a
+// 3-channel tensor less per iteration).
+static int sampler_on_device(cdc_handle *h, bool solver, int i, StepNoise noise, float eta, float *x_out, int B, int H, int W, int pred_mode,
+                             int clip, hipStream_t st) {
     int rc;
-    const size_t n = (size_t)B * h->cfg.channels * H * W;
     static const bool fuse_combine = getenv("CDC_NO_COMBINE_FUSE") == nullptr;
     const CombineArgs *cb = (fuse_combine && !h->ops.empty()) ? h->ops.back().get<CombineArgs>() : nullptr;
     if (cb && cb->out != h->out_fx) cb = nullptr;
     if ((rc = run_unet(h, st, i, cb != nullptr))) return rc;
-    SolverArgs d = {h->out_fx, h->in_x, x_out, h->d_hist, h->d_tab, h->d_stab, pred_mode == CDC_PRED_V ? h->d_tab_v : nullptr,
-                    h->steps, i < 0 ? 0 : i, i == -2 ? h->d_step : nullptr, pred_mode, clip, (long long)n,
-                    (long long)(B / 2) * h->cfg.channels * H * W, h->d_fault};
-    d.pC = h->cfg.channels; d.pH = H; d.pW = W;
-    if (cb) { d.P = cb->P; d.P_bias = cb->bias; d.pC = cb->Cout; d.pKH = cb->KH; d.pPad = cb->pad; d.pH = cb->H; d.pW = cb->W; }
-    const Op op(PC_SMALL, d, 0, 20.0 * n);
-    return run_op(h, op, B, st);
+    SamplerArgs s = sampler_args(h, h->out_fx, h->in_x, x_out, i, B, h->cfg.channels, H, W, pred_mode, clip, h->d_fault);
+    if (cb) { s.P = cb->P; s.P_bias = cb->bias; s.pC = cb->Cout; s.pKH = cb->KH; s.pPad = cb->pad; s.pH = cb->H; s.pW = cb->W; }
+    if (solver) return run_op(h, Op(PC_SMALL, SolverArgs{s, h->d_hist.p, h->d_stab.p}, 0, 20.0 * s.n), B, st);
+    DdimArgs d = {s};
+    d.eta = eta;
+    if (eta != 0.f && noise.seeds) { d.seeds = noise.seeds; d.per_image = s.n / B; }
+    else if (eta != 0.f) d.noise = noise.tensor;
+    return run_op(h, Op(PC_SMALL, d, 0, 16.0 * s.n), B, st);
 }
 
-static int ddim_on_device(cdc_handle *h, const float *x_in, int i, const float *noise, float eta,
-                          float *x_out, int B, int H, int W, int pred_mode, int clip,
-                          hipStream_t st, const unsigned long long *seeds = nullptr) {
-    int rc;
-    const size_t n = (size_t)B * h->cfg.channels * H * W;
-    if (x_in != h->in_x)
-        HIP_TRY(h, hipMemcpyAsync(h->in_x, x_in, n * sizeof(float), hipMemcpyDeviceToDevice, st));
-    // the 7-row combine of the final convolution rides in the sampler kernel (one launch and a 3-channel tensor less per iteration)
-    static const bool fuse_combine = getenv("CDC_NO_COMBINE_FUSE") == nullptr;
-    const CombineArgs *cb = (fuse_combine && !h->ops.empty()) ? h->ops.back().get<CombineArgs>() : nullptr;
-    if (cb && cb->out != h->out_fx) cb = nullptr;
-    if ((rc = run_unet(h, st, i, cb != nullptr))) return rc;
-    DdimArgs d = {h->out_fx, h->in_x, (eta != 0.f) ? noise : nullptr, x_out, h->d_tab, h->steps, i < 0 ? 0 : i,
-                  i == -2 ? h->d_step : nullptr, pred_mode, clip, eta, (long long)n,
-                  (long long)(B / 2) * h->cfg.channels * H * W, h->d_fault, pred_mode == CDC_PRED_V ? h->d_tab_v : nullptr};
-    if (cb) { d.P = cb->P; d.P_bias = cb->bias; d.pC = cb->Cout; d.pKH = cb->KH; d.pPad = cb->pad; d.pH = cb->H; d.pW = cb->W; }
-    if (eta != 0.f && seeds) { d.noise = nullptr; d.seeds = seeds; d.per_image = (long long)(n / B); }
-    const Op op(PC_SMALL, d, 0, 16.0 * n);
-    return run_op(h, op, B, st);
-}
-
-int cdc_ddim_step(cdc_handle *h, const float *x_in, int i, const float *const *ctx, int n_ctx,
-                  const float *noise, float eta, float *x_out, int B, int H, int W, int pred_mode,
-                  int clip, int mem, void *stream) {
+// cdc_ddim_step and cdc_solver_step: one iteration from and to the caller's memory.  They differ in the extra input (`extra_in`: the
+// noise draw / the previous step's x0, either may be null) and the solver's extra output x0_out.
+static int sampler_step(cdc_handle *h, bool solver, const float *x_in, const float *extra_in, float eta, int i, const float *const *ctx,
+                        int n_ctx, float *x_out, float *x0_out, int B, int H, int W, int pred_mode, int clip, int mem, void *stream) {
     return with_range_guard(h, [&]() -> int {
         int rc = require_kind(h, HandleKind::Unet);
         if (rc) return rc;
         if ((rc = check_ready(h))) return rc;
-        if (!h->steps) return fail(h, CDC_ERR_STATE, "cdc_set_schedule has not been called");
+        if ((rc = sampler_ready(h, pred_mode, clip, solver))) return rc;
+        if (!x_in || !x_out || (solver && !x0_out) || B < 1) return fail(h, CDC_ERR_INVALID, "null/invalid argument");
         if (i < 0 || i >= h->steps) return fail(h, CDC_ERR_INVALID, "step index %d out of [0,%d)", i, h->steps);
-        if (h->out_dim != h->cfg.channels)
-            return fail(h, CDC_ERR_UNSUPPORTED, "sampler needs out_dim == channels");
-        if (eta != 0.f && !noise) return fail(h, CDC_ERR_INVALID, "eta != 0 needs the noise draw");
-        if (pred_mode < 0 || pred_mode > 3 || clip < 0 || clip > 2) return fail(h, CDC_ERR_INVALID, "pred_mode %d / clip %d out of range", pred_mode, clip);
-        if (pred_mode == CDC_PRED_V && (!h->d_tab_v || h->tab_v_gen != h->sched_gen))
-            return fail(h, CDC_ERR_STATE, "pred_mode \"v\" needs cdc_set_schedule_v after cdc_set_schedule");
+        if (solver && !extra_in && h->h_stab[(size_t)2 * h->steps + i] != 0.f)
+            return fail(h, CDC_ERR_INVALID, "step %d is second order (c != 0): it needs the previous step's x0", i);
+        if (!solver && eta != 0.f && !extra_in) return fail(h, CDC_ERR_INVALID, "eta != 0 needs the noise draw");
         if ((rc = build_program(h, B, H, W))) return rc;
         if ((rc = ensure_time_rows(h, B))) return rc;
         hipStream_t st = pick_stream(h, stream, mem);
         const size_t n = (size_t)B * h->cfg.channels * H * W;
+        if (solver && (rc = h->d_hist.grow(h, n))) return rc;
         if ((rc = copy_in(h, h->in_x, x_in, n, mem, st))) return rc;
-        // the flag is cleared BEFORE the hoisted context convolutions run: they report range faults into it too (as in cdc_decode)
+        if (extra_in && (solver || eta != 0.f)) { if ((rc = copy_in(h, solver ? h->d_hist.p : h->noise_buf, extra_in, n, mem, st))) return rc; }
+        else if (solver) HIP_TRY(h, hipMemsetAsync(h->d_hist.p, 0, n * sizeof(float), st));      // a first-order step: c = 0 multiplies zeros
+        // the flag is cleared BEFORE the hoisted context convolutions run: they report range faults into it too (as in the decode loop)
         if ((rc = arm_range_guard(h, st, true))) return rc;
         if (ctx) {
             if ((rc = stage_ctx(h, ctx, n_ctx, B, mem, st))) return rc;
             h->prof_now = true;
             if ((rc = run_pre(h, st))) return rc;
         }
-        if (eta != 0.f && (rc = copy_in(h, h->noise_buf, noise, n, mem, st))) return rc;
-        if ((rc = ddim_on_device(h, h->in_x, i, h->noise_buf, eta, h->xa, B, H, W, pred_mode, clip, st)))
-            return rc;
+        if ((rc = sampler_on_device(h, solver, i, {h->noise_buf, nullptr}, eta, h->xa, B, H, W, pred_mode, clip, st))) return rc;
         rc = range_check(h, {{h->xa, 0, (long long)n}}, 1, st);
         if (rc == kRangeRetry && !ctx)      // the staged context went with the old launch program: the caller has to hand it over again
             return fail(h, CDC_ERR_STATE, "fp16 range overflow in step %d; the handle is now in CDC_ARITH_BF16X3 -- repeat the step WITH the context", i);
         if (rc) return rc;
+        if (solver && (rc = copy_out(h, x0_out, h->d_hist.p, n, mem, st))) return rc;
         return copy_out(h, x_out, h->xa, n, mem, st);
     });
 }
 
-// The per-image seeds of a call into the handle's device array (grow only: a captured graph holds its address).
-static int stage_seeds(cdc_handle *h, const uint64_t *seeds, int B, hipStream_t st) {
-    if (B > h->seeds_cap) {
-        HIP_TRY(h, hipDeviceSynchronize());
-        if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }   // it baked the old address
-        if (h->d_seeds) { (void)hipFree(h->d_seeds); h->d_seeds = nullptr; h->seeds_cap = 0; }
-        void *p = nullptr;
-        HIP_TRY(h, hipMalloc(&p, sizeof(unsigned long long) * (size_t)B));
-        h->d_seeds = (unsigned long long *)p;
-        h->seeds_cap = B;
-    }
-    HIP_TRY(h, hipStreamSynchronize(st));     // an earlier call's copy out of h_seeds may still be queued
-    h->h_seeds.assign(seeds, seeds + B);
-    HIP_TRY(h, hipMemcpyAsync(h->d_seeds, h->h_seeds.data(), sizeof(unsigned long long) * (size_t)B, hipMemcpyHostToDevice, st));
-    return CDC_OK;
+int cdc_ddim_step(cdc_handle *h, const float *x_in, int i, const float *const *ctx, int n_ctx,
+                  const float *noise, float eta, float *x_out, int B, int H, int W, int pred_mode,
+                  int clip, int mem, void *stream) {
+    if (!h) return CDC_ERR_INVALID;
+    return no_throw(h, [&] { return sampler_step(h, false, x_in, noise, eta, i, ctx, n_ctx, x_out, nullptr, B, H, W, pred_mode, clip, mem, stream); });
+}
+
+int cdc_solver_step(cdc_handle *h, const float *x_in, const float *x0_prev_in, int i, const float *const *ctx, int n_ctx, float *x_out,
+                    float *x0_out, int B, int H, int W, int pred_mode, int clip, int mem, void *stream) {
+    if (!h) return CDC_ERR_INVALID;
+    return no_throw(h, [&] { return sampler_step(h, true, x_in, x0_prev_in, 0.f, i, ctx, n_ctx, x_out, x0_out, B, H, W, pred_mode, clip, mem, stream); });
 }
 
 // cdc_decode (seeds null: eta = 0, no generator), cdc_decode_seeded and cdc_decode_solver (solver: the multistep update in place of
@@ -1070,36 +1020,26 @@ static int decode_impl(cdc_handle *h, const float *init, float gamma, const uint
         int rc = require_kind(h, HandleKind::Unet);
         if (rc) return rc;
         if ((rc = check_ready(h))) return rc;
-        if (!h->steps) return fail(h, CDC_ERR_STATE, "cdc_set_schedule has not been called");
-        if (h->out_dim != h->cfg.channels)
-            return fail(h, CDC_ERR_UNSUPPORTED, "sampler needs out_dim == channels");
+        if ((rc = sampler_ready(h, pred_mode, clip, solver))) return rc;
         if (!out || !ctx) return fail(h, CDC_ERR_INVALID, "null argument");
-        if (pred_mode < 0 || pred_mode > 3 || clip < 0 || clip > 2)
-            return fail(h, CDC_ERR_INVALID, "pred_mode %d / clip %d out of range", pred_mode, clip);
-        if (pred_mode == CDC_PRED_V && (!h->d_tab_v || h->tab_v_gen != h->sched_gen))
-            return fail(h, CDC_ERR_STATE, "pred_mode \"v\" needs cdc_set_schedule_v after cdc_set_schedule");
-        if (solver && (rc = solver_ready(h, pred_mode, clip))) return rc;
         if ((rc = build_program(h, B, H, W))) return rc;
         if ((rc = ensure_time_rows(h, B))) return rc;
         hipStream_t st = pick_stream(h, stream, mem);
         const size_t n = (size_t)B * h->cfg.channels * H * W;
-        if (solver && (rc = ensure_hist(h, n))) return rc;
+        if (solver && (rc = h->d_hist.grow(h, n))) return rc;
         if ((rc = arm_range_guard(h, st, true))) return rc;
         // the history starts as zeros in every decode, the BF16X3 repetition included: c = 0 on the first step multiplies them
-        if (solver) HIP_TRY(h, hipMemsetAsync(h->d_hist, 0, n * sizeof(float), st));
+        if (solver) HIP_TRY(h, hipMemsetAsync(h->d_hist.p, 0, n * sizeof(float), st));
         // the generator is needed for the start image (no init, gamma != 0) and for the steps (eta != 0); the BF16X3 repetition of
         // a range fault comes through here again and regenerates both from the seeds
         const bool gen_init = seeds && !init && gamma != 0.f;
         const unsigned long long *dseeds = nullptr;
         if (seeds && (gen_init || eta != 0.f)) {
-            if ((rc = stage_seeds(h, seeds, B, st))) return rc;
-            dseeds = h->d_seeds;
+            if ((rc = h->seeds.stage(h, seeds, (size_t)B, st))) return rc;
+            dseeds = h->seeds.dev.p;
         }
         // one iteration, in place on h->in_x; i = -2: the step index comes from h->d_step (graph capture)
-        auto iterate = [&](int i, hipStream_t s) {
-            return solver ? solver_on_device(h, i, h->in_x, B, H, W, pred_mode, clip, s)
-                          : ddim_on_device(h, h->in_x, i, nullptr, eta, h->in_x, B, H, W, pred_mode, clip, s, dseeds);
-        };
+        auto iterate = [&](int i, hipStream_t s) { return sampler_on_device(h, solver, i, {nullptr, dseeds}, eta, h->in_x, B, H, W, pred_mode, clip, s); };
         if (init) { if ((rc = copy_in(h, h->in_x, init, n, mem, st))) return rc; }
         else if (gen_init) HIP_TRY(h, randn_fill_launch(dseeds, B, (long long)(n / B), 0u, gamma, h->in_x, st));
         else HIP_TRY(h, hipMemsetAsync(h->in_x, 0, n * sizeof(float), st));
@@ -1169,7 +1109,8 @@ static int decode_impl(cdc_handle *h, const float *init, float gamma, const uint
 
 int cdc_decode(cdc_handle *h, const float *init, const float *const *ctx, int n_ctx, float *out, int B,
                int H, int W, int pred_mode, int clip, int mem, void *stream) {
-    return decode_impl(h, init, 0.f, nullptr, 0.f, ctx, n_ctx, out, B, H, W, pred_mode, clip, mem, stream);
+    if (!h) return CDC_ERR_INVALID;
+    return no_throw(h, [&] { return decode_impl(h, init, 0.f, nullptr, 0.f, ctx, n_ctx, out, B, H, W, pred_mode, clip, mem, stream); });
 }
 
 int cdc_decode_seeded(cdc_handle *h, const float *init, float gamma, const uint64_t *seeds, float eta, const float *const *ctx,
@@ -1274,64 +1215,14 @@ int cdc_sample_select(cdc_handle *h, const float *samples, const int *pick, floa
             for (int b = 0; b < B; ++b)
                 if (pick[b] >= Kc) return fail(h, CDC_ERR_INVALID, "sample_select: pick[%d] = %d, the chunk holds %d samples per image", b, pick[b], Kc);
             hipStream_t st = pick_stream(h, stream, mem);
-            // the picks into the handle's device array, as stage_seeds stages the seeds
-            if (B > h->pick_cap) {
-                HIP_TRY(h, hipDeviceSynchronize());
-                if (h->d_pick) { (void)hipFree(h->d_pick); h->d_pick = nullptr; h->pick_cap = 0; }
-                void *p = nullptr;
-                HIP_TRY(h, hipMalloc(&p, sizeof(int) * (size_t)B));
-                h->d_pick = (int *)p;
-                h->pick_cap = B;
-            }
-            HIP_TRY(h, hipStreamSynchronize(st));     // an earlier call's copy out of h_pick may still be queued
-            h->h_pick.assign(pick, pick + B);
-            HIP_TRY(h, hipMemcpyAsync(h->d_pick, h->h_pick.data(), sizeof(int) * (size_t)B, hipMemcpyHostToDevice, st));
+            if ((rc = h->picks.stage(h, pick, (size_t)B, st))) return rc;
             const size_t bytes = (size_t)B * (size_t)per_image * sizeof(float);
             Staging s(h, mem, st);
             const float *ds = s.in(samples, bytes * Kc);
             // host memory: best goes in as well -- the images that are not picked keep their content
             float *db = mem == CDC_MEM_DEVICE ? best : s.out(best, bytes, (void *)s.in(best, bytes));
-            if (s.ok()) s.e = sample_select_launch({ds, h->d_pick, db, (long long)per_image, Kc}, B, st);
+            if (s.ok()) s.e = sample_select_launch({ds, h->picks.dev.p, db, (long long)per_image, Kc}, B, st);
             return s.finish("sample_select");
-        });
-    });
-}
-
-int cdc_solver_step(cdc_handle *h, const float *x_in, const float *x0_prev_in, int i, const float *const *ctx, int n_ctx, float *x_out,
-                    float *x0_out, int B, int H, int W, int pred_mode, int clip, int mem, void *stream) {
-    if (!h) return CDC_ERR_INVALID;
-    return no_throw(h, [&] {
-        return with_range_guard(h, [&]() -> int {
-            int rc = require_kind(h, HandleKind::Unet);
-            if (rc) return rc;
-            if ((rc = check_ready(h))) return rc;
-            if ((rc = solver_ready(h, pred_mode, clip))) return rc;
-            if (!x_in || !x_out || !x0_out || B < 1) return fail(h, CDC_ERR_INVALID, "null/invalid argument");
-            if (i < 0 || i >= h->steps) return fail(h, CDC_ERR_INVALID, "step index %d out of [0,%d)", i, h->steps);
-            if (!x0_prev_in && h->h_stab[(size_t)2 * h->steps + i] != 0.f)
-                return fail(h, CDC_ERR_INVALID, "step %d is second order (c != 0): it needs the previous step's x0", i);
-            if (h->out_dim != h->cfg.channels) return fail(h, CDC_ERR_UNSUPPORTED, "sampler needs out_dim == channels");
-            if ((rc = build_program(h, B, H, W))) return rc;
-            if ((rc = ensure_time_rows(h, B))) return rc;
-            hipStream_t st = pick_stream(h, stream, mem);
-            const size_t n = (size_t)B * h->cfg.channels * H * W;
-            if ((rc = ensure_hist(h, n))) return rc;
-            if ((rc = copy_in(h, h->in_x, x_in, n, mem, st))) return rc;
-            if (x0_prev_in) { if ((rc = copy_in(h, h->d_hist, x0_prev_in, n, mem, st))) return rc; }
-            else HIP_TRY(h, hipMemsetAsync(h->d_hist, 0, n * sizeof(float), st));
-            if ((rc = arm_range_guard(h, st, true))) return rc;
-            if (ctx) {
-                if ((rc = stage_ctx(h, ctx, n_ctx, B, mem, st))) return rc;
-                h->prof_now = true;
-                if ((rc = run_pre(h, st))) return rc;
-            }
-            if ((rc = solver_on_device(h, i, h->xa, B, H, W, pred_mode, clip, st))) return rc;
-            rc = range_check(h, {{h->xa, 0, (long long)n}}, 1, st);
-            if (rc == kRangeRetry && !ctx)
-                return fail(h, CDC_ERR_STATE, "fp16 range overflow in step %d; the handle is now in CDC_ARITH_BF16X3 -- repeat the step WITH the context", i);
-            if (rc) return rc;
-            if ((rc = copy_out(h, x0_out, h->d_hist, n, mem, st))) return rc;
-            return copy_out(h, x_out, h->xa, n, mem, st);
         });
     });
 }
@@ -1344,7 +1235,7 @@ int cdc_op_solver_update(cdc_handle *h, const float *fx, const float *x, const f
             int rc = require_kind(h, HandleKind::Unet);
             if (rc) return rc;
             if ((rc = ensure_device(h))) return rc;
-            if ((rc = solver_ready(h, pred_mode, clip))) return rc;
+            if ((rc = sampler_ready(h, pred_mode, clip, true))) return rc;
             if (!fx || !x || !x0_prev || !x_next || !x0_out) return fail(h, CDC_ERR_INVALID, "null argument");
             if (B < 1 || C < 1 || H < 1 || W < 1 || (long long)B * C * H * W > (1ll << 40))
                 return fail(h, CDC_ERR_INVALID, "solver_update: %d x %d x %d x %d elements", B, C, H, W);
@@ -1358,10 +1249,7 @@ int cdc_op_solver_update(cdc_handle *h, const float *fx, const float *x, const f
             if (s.ok() && dh != x0_prev)
                 s.e = hipMemcpyAsync(dh, x0_prev, bytes, mem == CDC_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st);
             if (s.ok()) {
-                SolverArgs d = {dfx, dx, dn, dh, h->d_tab, h->d_stab, pred_mode == CDC_PRED_V ? h->d_tab_v : nullptr, h->steps, i, nullptr,
-                                pred_mode, clip, (long long)n, (long long)(B / 2) * C * H * W, nullptr};
-                d.pC = C; d.pH = H; d.pW = W;
-                s.e = solver_launch(d, st);
+                s.e = solver_launch({sampler_args(h, dfx, dx, dn, i, B, C, H, W, pred_mode, clip, nullptr), dh, h->d_stab.p}, st);
             }
             return s.finish("solver_update");
         });
@@ -1386,16 +1274,16 @@ int cdc_randn(cdc_handle *h, const uint64_t *seeds, int B, int64_t per_image, ui
             if ((rc = randn_args(h, seeds, B, per_image, out))) return rc;
             if (mem != CDC_MEM_HOST && mem != CDC_MEM_DEVICE) return fail(h, CDC_ERR_INVALID, "randn: mem_kind %d", mem);
             hipStream_t st = pick_stream(h, stream, mem);
-            if ((rc = stage_seeds(h, seeds, B, st))) return rc;
+            if ((rc = h->seeds.stage(h, seeds, (size_t)B, st))) return rc;
             if (mem == CDC_MEM_DEVICE) {
-                HIP_TRY(h, randn_fill_launch(h->d_seeds, B, per_image, draw, scale, out, st));
+                HIP_TRY(h, randn_fill_launch(h->seeds.dev.p, B, per_image, draw, scale, out, st));
                 return CDC_OK;
             }
             const size_t n = (size_t)B * (size_t)per_image;
             DevPool d;
             float *dd;
             if (d.get(&dd, n) != hipSuccess) return fail(h, CDC_ERR_NOMEM, "hipMalloc failed");
-            hipError_t e = randn_fill_launch(h->d_seeds, B, per_image, draw, scale, dd, st);
+            hipError_t e = randn_fill_launch(h->seeds.dev.p, B, per_image, draw, scale, dd, st);
             if (e == hipSuccess) e = hipMemcpyAsync(out, dd, n * sizeof(float), hipMemcpyDeviceToHost, st);
             const hipError_t es = hipStreamSynchronize(st);   // (after an error too: nothing queued may still use what d frees)
             if (e == hipSuccess) e = es;

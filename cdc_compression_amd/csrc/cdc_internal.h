@@ -234,48 +234,42 @@ hipError_t ctx_fold_launch(const AttnCtxArgs &a, int B, hipStream_t st);
 struct CombineArgs { const float *P, *bias; float *out; int Cout, KH, pad, H, W; };
 hipError_t fold_combine_launch(const CombineArgs &a, int B, hipStream_t st);
 
-struct DdimArgs {
-    const float *fx, *x, *noise;
+// sampler_kernels.hip: one sampler step.  SamplerArgs is what the two update rules share, DdimArgs / SolverArgs what each adds.
+struct SamplerArgs {
+    const float *fx, *x;   // the model output (read when P is null) and the current image
     float *x_next;
-    const float *tab;   // device table [5][steps]: sqrt_recip, sqrt_recipm1, sqrt_ac_prev,
-                        //                          one_minus_ac_prev, sigma
+    const float *tab;      // device table [5][steps]: sqrt_recip, sqrt_recipm1, sqrt_ac_prev, one_minus_ac_prev, sigma
+    const float *tab_v;    // pred_mode 3: device table [2][steps]: sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod (else null)
     int steps, i;
     const int *step_ptr;   // non-null: the step index is read from device memory (hipGraph replay)
     int pred_mode, clip;   // pred_mode: 0 x-tree "x", 1 eps-tree "noise", 2 x-tree "noise", 3 x-tree "v"; clip: 0 none, 1 all, 2 first half
-    float eta;
     long long n;
     long long clip_half_n; // elements of the first B/2 images
-    int *fault;            // set to 1 when the U-Net output holds inf / NaN (may be null)
-    const float *tab_v;    // pred_mode 3: device table [2][steps]: sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod
-    // non-null: fx is the 7-row combine of the row-folded final convolution's partial planes P [B][pC][pKH][pH][pW] (+ P_bias[pC]),
-    // evaluated inside the sampler kernel (same sum, same order as fold_combine_kernel) instead of being read from `fx`
+    int *fault;            // set to 1 when the model output holds inf / NaN (may be null)
+    // P non-null: fx is the 7-row combine of the row-folded final convolution's partial planes P [B][pC][pKH][pH][pW] (+ P_bias[pC]),
+    // evaluated inside the sampler kernel (same sum, same order as fold_combine_kernel) instead of being read from `fx`.  pC / pH / pW
+    // are always the image's channels and frame: the launch picks the traversal by them.
     const float *P = nullptr, *P_bias = nullptr;
     int pC = 0, pKH = 0, pPad = 0, pH = 0, pW = 0;
-    // The noise of the step: none (noise and seeds null: eta = 0), a tensor (`noise`: cdc_ddim_step), or generated in the kernel
-    // (`seeds` non-null, rng.h): image b draws z(seeds[b], draw = step index + 1, element index inside its own per_image elements);
-    // `noise` is then neither read nor written.
+};
+// DDIM: the noise of the step is none (noise and seeds null: eta = 0), a tensor (`noise`: cdc_ddim_step),
+// or generated in the kernel (`seeds` non-null, rng.h): image b draws z(seeds[b], draw = step index + 1, element index inside its own
+// per_image elements); `noise` is then neither read nor written.
+struct DdimArgs {
+    SamplerArgs s;
+    const float *noise = nullptr;
+    float eta = 0.f;
     const unsigned long long *seeds = nullptr;
     long long per_image = 0;
 };
 hipError_t ddim_launch(const DdimArgs &a, hipStream_t st);
 // Second-order multistep update in data-prediction form (DPM-Solver++ 2M; include/cdc_hip.h states it):
-//   x0 = the prediction ddim_update forms for pred_mode / clip;  x_next = ((a_i x) + (b_i x0)) + (c_i hist);  hist <- x0
+//   x0 = the prediction of pred_mode / clip;  x_next = ((a_i x) + (b_i x0)) + (c_i hist);  hist <- x0
 // hist, of the image's shape, is read and overwritten in place by the thread that owns the element.
 struct SolverArgs {
-    const float *fx, *x;
-    float *x_next, *hist;
-    const float *tab;      // the schedule's device table [5][steps] (rows 0, 1: sqrt_recip, sqrt_recipm1 of pred_mode 1 / 2)
+    SamplerArgs s;
+    float *hist;
     const float *stab;     // device table [3][steps]: a, b, c (cdc_set_solver)
-    const float *tab_v;    // pred_mode 3, as in DdimArgs
-    int steps, i;
-    const int *step_ptr;   // non-null: the step index is read from device memory (hipGraph replay)
-    int pred_mode, clip;   // as in DdimArgs
-    long long n, clip_half_n;
-    int *fault;            // set to 1 when the U-Net output holds inf / NaN (may be null)
-    // P non-null: fx is the 7-row combine of the final convolution's partial planes, as in DdimArgs; pC / pH / pW are always the
-    // image's channels and frame
-    const float *P = nullptr, *P_bias = nullptr;
-    int pC = 0, pKH = 0, pPad = 0, pH = 0, pW = 0;
 };
 hipError_t solver_launch(const SolverArgs &a, hipStream_t st);
 // out[b][e] = scale * z(seeds[b], draw, e) for e < per_image (rng.h; seeds on the device); 16-byte stores when the layout allows

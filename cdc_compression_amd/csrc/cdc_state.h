@@ -194,6 +194,22 @@ static int default_arith() {      // CDC_ARITH=0 selects the three-plane bf16 ar
     return e ? (atoi(e) ? 1 : 0) : 1;
 }
 
+// A device buffer of the handle that only grows: a captured graph (graph_exec) has baked its address, so it moves only when it has
+// to, and the graph goes with it.  grow() is the one place that does this: synchronise the device, drop the graph, free, allocate,
+// record the capacity.  (Dropping the graph is harmless for a buffer no graph reads: the next graph decode captures again.)
+template <class T> struct GrowBuf {
+    T *p = nullptr;
+    size_t cap = 0;                        // elements
+    int grow(cdc_handle *h, size_t n);     // CDC_OK with cap >= n (the content is lost when the buffer moved), or the HIP error
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
+// ... filled from a caller's host array through a copy the handle owns (the caller's array may go away before the copy has run)
+template <class T> struct StagedBuf {
+    GrowBuf<T> dev;
+    std::vector<T> host;
+    template <class S> int stage(cdc_handle *h, const S *src, size_t n, hipStream_t st);
+};
+
 // ContextDecoder: Compressor.decode; HyperDecoder: hyper_dec (+ the rate estimate and the entropy coder); Encoder: enc + hyper_enc;
 // Lpips: the LPIPS-VGG network of cdc_lpips
 enum class HandleKind { Unet, ContextDecoder, HyperDecoder, Encoder, Lpips };
@@ -261,15 +277,14 @@ struct cdc_handle {
     float *xa = nullptr, *xb = nullptr, *noise_buf = nullptr;     // decode ping-pong
     // schedule
     int steps = 0;
-    float *d_tab = nullptr;              // [5][steps]
-    float *d_tab_v = nullptr;            // [2][steps] (cdc_set_schedule_v), valid for schedule generation tab_v_gen
-    int tab_v_gen = -1, tab_v_steps = 0;
+    GrowBuf<float> d_tab;                // [5][steps]
+    GrowBuf<float> d_tab_v;              // [2][steps] (cdc_set_schedule_v), valid for schedule generation tab_v_gen
+    int tab_v_gen = -1;
     std::vector<float> h_tab;            // host copy of d_tab: an unchanged schedule is not uploaded again
-    size_t tab_cap = 0, trows_cap = 0;   // capacities (floats) of d_tab / d_shift_tab: buffers are reused, not leaked
     int sched_gen = 0;                   // bumped whenever the device tables change (invalidates the captured graph)
     std::vector<float> h_time_in;
-    float *d_time_steps = nullptr;       // [steps] U-Net time input per sample step
-    float *d_shift_tab = nullptr;        // [steps][shift_bs]: time-embedding shifts of every step
+    GrowBuf<float> d_time_steps;         // [steps] U-Net time input per sample step
+    GrowBuf<float> d_shift_tab;          // [steps][shift_bs]: time-embedding shifts of every step (owned by the handle, not by the launch program)
     // hipGraph replay of one DDIM iteration (launch-bound small batches): the step index lives on the device
     int *d_step = nullptr;
     int range_faults = 0;                // calls repeated in bf16x3 arithmetic after an fp16 range overflow
@@ -280,32 +295,27 @@ struct cdc_handle {
     hipEvent_t gev_in = nullptr, gev_out = nullptr;   // order the caller's stream around the graph stream
     int graph_key[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // steps, pred_mode, clip, stream-independent program generation, eta's bits, seeded, sampler, solver-table generation
     // second-order multistep sampler (cdc_set_solver / cdc_decode_solver): a / b / c [3][steps], valid for schedule generation
-    // stab_sched_gen; the history x0 of the previous step, of the image's shape.  Both grow only: a captured graph holds their address.
-    float *d_stab = nullptr;
-    size_t stab_cap = 0;
+    // stab_sched_gen; the history x0 of the previous step, of the image's shape.
+    GrowBuf<float> d_stab;
     std::vector<float> h_stab;
     int stab_sched_gen = -1, solver_gen = 0;
-    float *d_hist = nullptr;
-    size_t hist_cap = 0;
+    GrowBuf<float> d_hist;
     // seeded stochastic decode (cdc_decode_seeded / cdc_randn): the per-image seeds of the running call on the device
-    unsigned long long *d_seeds = nullptr;
-    int seeds_cap = 0;
-    std::vector<unsigned long long> h_seeds;   // staging copy: the caller's array may go away before the copy has run
+    StagedBuf<unsigned long long> seeds;
     int time_steps_B = 0;
     // K samples per image (cdc_decode_samples / cdc_sample_select): the B host images of one context level on their way to the repeat
-    // kernel, and the picks of the running call with their staging copy.  Both grow only.
-    float *d_rep_stage = nullptr;
-    size_t rep_stage_cap = 0;
-    int *d_pick = nullptr;
-    int pick_cap = 0;
-    std::vector<int> h_pick;
+    // kernel, and the picks of the running call.
+    GrowBuf<float> d_rep_stage;
+    StagedBuf<int> picks;
     // Lpips: the thirteen VGG16 layers live in hconvs; the five `lin` weight vectors, the scaling layer, and the program's result area
     // (a layer of >= 256 input channels is packed as lp_parts[layer] slices of 128 input channels, consecutive in hconvs)
     std::vector<int> lp_parts;
     float *lp_lin[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     float lp_shift[3] = {-.030f, -.088f, -.188f}, lp_scale[3] = {.458f, .448f, .450f};
     double *lp_res = nullptr;            // [pairs of the program][5] layer values of the running chunk (program buffer)
-    void *metric_work = nullptr;         // cdc_distortion: partial sums and the pooled MS-SSIM pyramids of both operands, grown on demand
+    // cdc_distortion: partial sums and the pooled MS-SSIM pyramids of both operands, grown on demand (no GrowBuf: its failure is
+    // CDC_ERR_NOMEM with a text of its own, and no graph or queued work holds it)
+    void *metric_work = nullptr;
     size_t metric_cap = 0;
     int op_stress_n = 0;                 // cdc_op_stress: extra executions of every cdc_op_* program, results compared on the device
     long long op_stress_launches = 0, op_stress_differing = 0;
@@ -500,3 +510,22 @@ struct Staging {
 };
 
 }  // namespace cdcapi
+
+// (down here: they need the complete handle and HIP_TRY)
+template <class T> int GrowBuf<T>::grow(cdc_handle *h, size_t n) {
+    if (n <= cap) return CDC_OK;
+    HIP_TRY(h, hipDeviceSynchronize());
+    if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
+    release();
+    HIP_TRY(h, hipMalloc((void **)&p, n * sizeof(T)));
+    cap = n;
+    return CDC_OK;
+}
+template <class T> template <class S> int StagedBuf<T>::stage(cdc_handle *h, const S *src, size_t n, hipStream_t st) {
+    int rc = dev.grow(h, n);
+    if (rc) return rc;
+    HIP_TRY(h, hipStreamSynchronize(st));     // an earlier call's copy out of `host` may still be queued
+    host.assign(src, src + n);
+    HIP_TRY(h, hipMemcpyAsync(dev.p, host.data(), sizeof(T) * n, hipMemcpyHostToDevice, st));
+    return CDC_OK;
+}

@@ -1,0 +1,270 @@
+// sampler_kernels.hip -- one sampler step: the model output (a tensor, or the 7-row combine of the final convolution's partial planes),
+// the prediction x0, and one of two update rules -- DDIM (xparam/modules/denoising_diffusion.py:152-174, epsilonparam :137-152; same
+// operation order as the reference) or the second-order multistep update (SolverArgs) -- in one of two traversals.  Beside them the
+// step counter of a graph-replayed iteration and the fill kernel of the generator (rng.h).
+#include <math.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "cdc_internal.h"
+#include "rng.h"
+
+namespace cdc {
+
+// ---- what every form of the step shares ----------------------------------------------------------------------------------------
+struct StepConsts {
+    int si, pred_mode;                            // the step index (from device memory under graph replay)
+    float c_recip, c_recipm1, c_sac, c_s1mac;     // rows 0, 1 of `tab`; rows 0, 1 of `tab_v` (pred_mode 3) or 0
+    long long clip_n;                             // the elements before this index are clipped: always a whole number of images
+};
+__device__ __forceinline__ StepConsts step_consts(const SamplerArgs &s) {
+    const int si = s.step_ptr ? *s.step_ptr : s.i;
+    // clip: 0 none, 1 every image, 2 the first B/2 images only (eps-tree clip_noise "half", eps :142-143)
+    return {si, s.pred_mode, s.tab[0 * s.steps + si], s.tab[1 * s.steps + si], s.tab_v ? s.tab_v[si] : 0.f,
+            s.tab_v ? s.tab_v[s.steps + si] : 0.f, s.clip == 1 ? s.n : (s.clip == 2 ? s.clip_half_n : 0)};
+}
+
+// The model output of element idx.  With P: the 7-row combine of the row-folded final convolution evaluated here (fold_combine_kernel's
+// sum in its order: the bias, then ky ascending over the rows inside the image); out_fx is never written.
+__device__ __forceinline__ float model_out(const SamplerArgs &s, long long idx) {
+    if (!s.P) return s.fx[idx];
+    const long long plane = (long long)s.pH * s.pW, img_co = idx / plane;      // = b * Cout + co
+    const int pix = (int)(idx - img_co * plane), y = pix / s.pW;
+    const float *p = s.P + (size_t)img_co * s.pKH * plane + pix;
+    float fx = s.P_bias ? s.P_bias[(int)(img_co % s.pC)] : 0.f;
+    for (int ky = 0; ky < s.pKH; ++ky) {
+        const int r = y + ky - s.pPad;
+        if (r >= 0 && r < s.pH) fx += p[(size_t)ky * plane + (long long)(ky - s.pPad) * s.pW];
+    }
+    return fx;
+}
+// ... of the four pixels pix .. pix + 3 of plane img_co (one row: pW % 4 == 0), 16 bytes per access
+__device__ __forceinline__ void model_out4(const SamplerArgs &s, int img_co, int pix, int plane, float fx[4]) {
+    if (!s.P) {
+        const float4 q = *reinterpret_cast<const float4 *>(s.fx + (long long)img_co * plane + pix);
+        fx[0] = q.x; fx[1] = q.y; fx[2] = q.z; fx[3] = q.w;
+        return;
+    }
+    const int y = pix / s.pW;
+    const float *p = s.P + (size_t)img_co * s.pKH * plane + pix;
+    fx[0] = fx[1] = fx[2] = fx[3] = s.P_bias ? s.P_bias[img_co % s.pC] : 0.f;
+    for (int ky = 0; ky < s.pKH; ++ky) {
+        const int r = y + ky - s.pPad;
+        if (r >= 0 && r < s.pH) {
+            const float4 q = *reinterpret_cast<const float4 *>(p + (size_t)ky * plane + (long long)(ky - s.pPad) * s.pW);
+            fx[0] += q.x; fx[1] += q.y; fx[2] += q.z; fx[3] += q.w;
+        }
+    }
+}
+
+// inf / NaN from the U-Net (fp16-plane range overflow)
+__device__ __forceinline__ bool nonfinite(float v) { return !(fabsf(v) <= 3.0e38f); }
+
+// The prediction x0 of both rules.  pred_mode 3 ("v", xparam :128-139,161-162): x0 = sqrt(ac) x - sqrt(1 - ac) v.  No fused multiply-adds
+// here or in the rules (fp contract off): every product and sum is rounded on its own, as the reference's element-wise tensor operations
+// round them -- and the two traversals then hold the same bits whatever hipcc packs (left to the contraction heuristics they differed in
+// the last bit, which a 30-step eps-param chain amplifies to 7e-4).
+__device__ __forceinline__ float predict_x0(const StepConsts &k, float fx, float x, bool clip) {
+#pragma clang fp contract(off)
+    float x0;
+    if (k.pred_mode == 0) x0 = fx;
+    else if (k.pred_mode == 3) x0 = k.c_sac * x - k.c_s1mac * fx;
+    else x0 = k.c_recip * x - k.c_recipm1 * fx;
+    if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    return x0;
+}
+
+// ---- the two rules.  A rule is built once per thread from its arguments and the step's constants; one() updates element idx, four()
+// the four elements from idx on (pixels pix .. pix + 3 of plane img_co), given their model outputs and x. --------------------------
+// DDIM (denoising_diffusion.py ddim(), both trees).  The noise of the step: none (eta = 0), a tensor (`noise`), or -- SEEDED, an instance
+// of its own so that the others carry no generator code -- made here: image b draws z(seeds[b], step index + 1, element inside the image).
+template <bool SEEDED>
+struct DdimRule {
+    using Args = DdimArgs;
+    const DdimArgs &a;
+    const StepConsts &k;
+    float c_acp, c_eps, sig;
+    __device__ __forceinline__ DdimRule(const DdimArgs &a_, const StepConsts &k_) : a(a_), k(k_) {
+        const SamplerArgs &s = a.s;      // (the step's scalars, not pixel values: their contraction is the compiler's, as it always was)
+        c_acp = s.tab[2 * s.steps + k.si];
+        const float c_1macp = s.tab[3 * s.steps + k.si];
+        sig = a.eta * s.tab[4 * s.steps + k.si];
+        float var = c_1macp - sig * sig;
+        // x-tree (pred_mode 0 "x", 2 "noise", 3 "v"): .clamp(min=0) under the square root (xparam :169); eps-tree: none
+        if (s.pred_mode != 1) var = fmaxf(var, 0.f);
+        c_eps = sqrtf(var);
+    }
+    __device__ __forceinline__ float next(float fx, float x, float noise, bool clip, bool has_noise) const {
+#pragma clang fp contract(off)
+        const float x0 = predict_x0(k, fx, x, clip);
+        const float eps = (k.pred_mode == 0 || k.pred_mode == 3) ? (k.c_recip * x - x0) / k.c_recipm1 : fx;
+        float xn = c_acp * x0 + c_eps * eps;
+        if (has_noise) xn += sig * noise;
+        return xn;
+    }
+    __device__ __forceinline__ void one(long long idx, float fx, float x, bool clip) const {
+        if constexpr (SEEDED) {
+            // the quad of this element, then its lane (frames whose width is no multiple of 4: four()'s draws, one by one)
+            const long long b = idx / a.per_image, e = idx - b * a.per_image;
+            float z[4];
+            cdcrng::normal4(a.seeds[b], (uint32_t)(e >> 2), (uint32_t)k.si + 1u, z);
+            const int lane = (int)(e & 3);
+            a.s.x_next[idx] = next(fx, x, lane == 0 ? z[0] : lane == 1 ? z[1] : lane == 2 ? z[2] : z[3], clip, true);
+        } else {
+            a.s.x_next[idx] = next(fx, x, a.noise ? a.noise[idx] : 0.f, clip, a.noise != nullptr);
+        }
+    }
+    __device__ __forceinline__ void four(long long idx, int img_co, int pix, int plane, const float fx[4], const float x[4], bool clip) const {
+        float nz[4] = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (SEEDED) {
+            // one Philox call: the four normals of these four pixels (plane % 4 == 0, so they are one quad of the image's own tensor)
+            const int b = img_co / a.s.pC;
+            const long long e = (long long)(img_co - b * a.s.pC) * plane + pix;
+            cdcrng::normal4(a.seeds[b], (uint32_t)(e >> 2), (uint32_t)k.si + 1u, nz);
+        } else if (a.noise) {
+            const float4 n4 = *reinterpret_cast<const float4 *>(a.noise + idx);
+            nz[0] = n4.x; nz[1] = n4.y; nz[2] = n4.z; nz[3] = n4.w;
+        }
+        float out[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) out[c] = next(fx[c], x[c], nz[c], clip, SEEDED || a.noise != nullptr);
+        *reinterpret_cast<float4 *>(a.s.x_next + idx) = make_float4(out[0], out[1], out[2], out[3]);
+    }
+};
+
+// The multistep update (DPM-Solver++ 2M in data-prediction form; include/cdc_hip.h states it):
+// x_next = ((a x) + (b x0)) + (c x0_prev), and x0 written over x0_prev by the thread that read it.
+struct SolverRule {
+    using Args = SolverArgs;
+    const SolverArgs &a;
+    const StepConsts &k;
+    float ca, cb, cc;
+    __device__ __forceinline__ SolverRule(const SolverArgs &a_, const StepConsts &k_) : a(a_), k(k_) {
+        ca = a.stab[0 * a.s.steps + k.si]; cb = a.stab[1 * a.s.steps + k.si]; cc = a.stab[2 * a.s.steps + k.si];
+    }
+    __device__ __forceinline__ float next(float x, float x0, float x0_prev) const {
+#pragma clang fp contract(off)
+        const float t0 = ca * x, t1 = cb * x0, t2 = cc * x0_prev;
+        return (t0 + t1) + t2;
+    }
+    __device__ __forceinline__ void one(long long idx, float fx, float x, bool clip) const {
+        const float x0 = predict_x0(k, fx, x, clip);
+        a.s.x_next[idx] = next(x, x0, a.hist[idx]);
+        a.hist[idx] = x0;
+    }
+    __device__ __forceinline__ void four(long long idx, int, int, int, const float fx[4], const float x[4], bool clip) const {
+        const float4 h4 = *reinterpret_cast<const float4 *>(a.hist + idx);
+        const float hs[4] = {h4.x, h4.y, h4.z, h4.w};
+        float out[4], x0[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            x0[c] = predict_x0(k, fx[c], x[c], clip);
+            out[c] = next(x[c], x0[c], hs[c]);
+        }
+        *reinterpret_cast<float4 *>(a.s.x_next + idx) = make_float4(out[0], out[1], out[2], out[3]);
+        *reinterpret_cast<float4 *>(a.hist + idx) = make_float4(x0[0], x0[1], x0[2], x0[3]);
+    }
+};
+
+// ---- the two traversals ----------------------------------------------------------------------------------------------------------
+// Any frame: a grid-stride loop over the elements; with the fused combine, (plane, pixel) come from two 64-bit divisions per element.
+template <class Rule>
+__global__ void __launch_bounds__(256) sampler_kernel(const typename Rule::Args a) {
+    const SamplerArgs &s = a.s;
+    const StepConsts k = step_consts(s);
+    const Rule rule(a, k);
+    bool bad = false;
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < s.n; idx += (long long)gridDim.x * blockDim.x) {
+        const float fx = model_out(s, idx);
+        bad |= nonfinite(fx);
+        rule.one(idx, fx, s.x[idx], idx < k.clip_n);
+    }
+    if (bad && s.fault) *s.fault = 1;                      // sticky, read by the host after the decode
+}
+
+// pW % 4 == 0: four consecutive pixels of one (image, channel) plane per thread, 16-byte loads / stores, the plane is blockIdx.y (the
+// divisions made the element loop VALU-bound: 90 us per launch at batch 32 for 0.23 GB of traffic).  Same sums in the same order, same
+// expressions per component: same bits.
+template <class Rule>
+__global__ void __launch_bounds__(256) sampler_rows4_kernel(const typename Rule::Args a) {
+    const SamplerArgs &s = a.s;
+    const StepConsts k = step_consts(s);
+    const Rule rule(a, k);
+    const int plane = s.pH * s.pW;
+    const int pix = 4 * (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (pix >= plane) return;
+    const int img_co = blockIdx.y;
+    const long long idx = (long long)img_co * plane + pix;
+    float fx[4];
+    model_out4(s, img_co, pix, plane, fx);
+    const float4 x4 = *reinterpret_cast<const float4 *>(s.x + idx);
+    const float xs[4] = {x4.x, x4.y, x4.z, x4.w};
+    const bool bad = nonfinite(fx[0]) | nonfinite(fx[1]) | nonfinite(fx[2]) | nonfinite(fx[3]);
+    rule.four(idx, img_co, pix, plane, fx, xs, idx < k.clip_n);
+    if (bad && s.fault) *s.fault = 1;
+}
+
+// The four-pixel form where the frame and every pointer the instance dereferences allow it (`rule_ptrs`: the rule's own, or-ed).
+template <class Rule>
+static hipError_t sampler_launch(const typename Rule::Args &a, uintptr_t rule_ptrs, hipStream_t st) {
+    const SamplerArgs &s = a.s;
+    const long long plane = (long long)s.pH * s.pW;
+    if (s.n <= 0) return hipErrorInvalidValue;
+    if (plane > 0 && (s.pW & 3) == 0 && plane < (1ll << 30) && s.n % plane == 0 && s.n / plane <= 65535 &&
+        (((uintptr_t)s.P | (uintptr_t)s.fx | (uintptr_t)s.x | (uintptr_t)s.x_next | rule_ptrs) & 15) == 0) {
+        const dim3 g((unsigned)ceil_div((int)(plane / 4), 256), (unsigned)(s.n / plane));
+        hipLaunchKernelGGL(sampler_rows4_kernel<Rule>, g, dim3(256), 0, st, a);
+    } else {
+        const int grid = (int)std::min<long long>((s.n + 255) / 256, 4096);
+        hipLaunchKernelGGL(sampler_kernel<Rule>, dim3(grid), dim3(256), 0, st, a);
+    }
+    return hipGetLastError();
+}
+
+hipError_t ddim_launch(const DdimArgs &a, hipStream_t st) {
+    return a.seeds ? sampler_launch<DdimRule<true>>(a, 0, st) : sampler_launch<DdimRule<false>>(a, (uintptr_t)a.noise, st);
+}
+hipError_t solver_launch(const SolverArgs &a, hipStream_t st) { return sampler_launch<SolverRule>(a, (uintptr_t)a.hist, st); }
+
+// end of a graph-replayed iteration: the next replay works on step - 1
+__global__ void step_dec_kernel(int *step) { *step -= 1; }
+
+hipError_t step_dec_launch(int *step, hipStream_t st) {
+    hipLaunchKernelGGL(step_dec_kernel, dim3(1), dim3(1), 0, st, step);
+    return hipGetLastError();
+}
+
+// out[b][e] = scale * z(seeds[b], draw, e): the start image of a seeded decode and cdc_randn.  One quad of rng.h per thread; a
+// 16-byte store where every image starts on a 16-byte boundary (per_image % 4 == 0), element stores with a bound otherwise.
+template <bool VEC>
+__global__ void __launch_bounds__(256) randn_fill_kernel(const unsigned long long *seeds, long long per_image, unsigned draw,
+                                                         float scale, float *out) {
+    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (4 * q >= per_image) return;
+    const int b = blockIdx.y;
+    float z[4];
+    cdcrng::normal4(seeds[b], (uint32_t)q, draw, z);
+    float *o = out + (size_t)b * per_image + 4 * q;
+    if constexpr (VEC) {
+        *reinterpret_cast<float4 *>(o) = make_float4(scale * z[0], scale * z[1], scale * z[2], scale * z[3]);
+    } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (4 * q + c < per_image) o[c] = scale * z[c];
+    }
+}
+
+hipError_t randn_fill_launch(const unsigned long long *seeds, int B, long long per_image, unsigned draw, float scale, float *out,
+                             hipStream_t st) {
+    const long long nq = (per_image + 3) / 4;
+    if (B < 1 || B > 65535 || per_image < 1 || nq > (1ll << 32)) return hipErrorInvalidValue;
+    const dim3 g((unsigned)((nq + 255) / 256), (unsigned)B);
+    if ((per_image & 3) == 0 && ((uintptr_t)out & 15) == 0)
+        hipLaunchKernelGGL(randn_fill_kernel<true>, g, dim3(256), 0, st, seeds, per_image, draw, scale, out);
+    else
+        hipLaunchKernelGGL(randn_fill_kernel<false>, g, dim3(256), 0, st, seeds, per_image, draw, scale, out);
+    return hipGetLastError();
+}
+
+}  // namespace cdc

@@ -84,7 +84,7 @@ def test_fused_loop_is_the_stepped_chain_bit_for_bit(name, tree, kw):
 
 
 def test_fused_loop_is_the_stepped_chain_on_a_width_that_is_no_multiple_of_4():
-    """odd_x's model on a 24 x 42 frame: the scalar ddim_kernel, which evaluates the quad of its element and picks its lane, against the
+    """odd_x's model on a 24 x 42 frame: the scalar sampler kernel, which evaluates the quad of its element and picks its lane, against the
     16-byte fill kernel's draws (the golden odd_x frame is 40 wide and takes the four-pixel kernel)."""
     kw, man, sd, *_ = load_case("odd_x")
     un = cdc.Unet(**kw)

@@ -96,7 +96,7 @@ def dispatches(d, counter):
 
 
 def last_iteration(seq):
-    ends = [i for i, (k, _) in enumerate(seq) if k.startswith("ddim_")]          # ddim_kernel / ddim_rows4_kernel
+    ends = [i for i, (k, _) in enumerate(seq) if k.startswith(("sampler_", "ddim_"))]     # sampler_kernel / sampler_rows4_kernel (ddim_*: traces from before the one sampler family)
     if len(ends) < 2:
         return []
     return seq[ends[-2] + 1: ends[-1] + 1]

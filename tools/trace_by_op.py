@@ -116,7 +116,7 @@ def main():
     labels = [l.rstrip("\n") for l in open(a.ops) if l.strip() and " HOIST" not in l and not l.startswith("combine")]
     if a.start_kernel:
         return by_segment(a, rows, labels)
-    ends = [i for i, r in enumerate(rows) if r[2].startswith("ddim_")]
+    ends = [i for i, r in enumerate(rows) if r[2].startswith(("sampler_", "ddim_"))]
     per_op = collections.defaultdict(list)
     n_ok = n_bad = 0
     bad_at = None
