@@ -151,7 +151,8 @@ def lib():
     L.cdc_decode_solver.argtypes = [H, _vp, ctypes.c_float, u64p, pp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp]
     L.cdc_solver_step.argtypes = [H, _vp, _vp, _i, pp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]
     L.cdc_op_solver_update.argtypes = [H, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]
-    L.cdc_repeat_images.argtypes = [H, _vp, _vp, _i, _i, ctypes.c_int64, _i, _i, _vp]
+    L.cdc_op_ddim_update.argtypes = [H, _vp, _vp, _vp, u64p, ctypes.c_float, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp]
+    L.cdc_repeat_images.argtypes =[H, _vp, _vp, _i, _i, ctypes.c_int64, _i, _i, _vp]
     L.cdc_decode_samples.argtypes = [H, ctypes.c_float, u64p, ctypes.c_float, pp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]
     L.cdc_sample_moments.argtypes = [H, _vp, _i, _i, ctypes.c_int64, _i, _vp, _vp, _i, _i, _vp]
     L.cdc_sample_select.argtypes = [H, _vp, ctypes.POINTER(_i), _vp, _i, _i, ctypes.c_int64, _i, _vp]
@@ -194,7 +195,7 @@ EXPORTS = ["cdc_create", "cdc_destroy", "cdc_last_error", "cdc_version", "cdc_nu
            "cdc_padded_size", "cdc_frame_pad", "cdc_frame_crop", "cdc_entropy_set_image_scale", "cdc_entropy_encode_image",
            "cdc_entropy_peek_image_size", "cdc_decode_seeded", "cdc_randn", "cdc_randn_host", "cdc_philox4x32_10",
            "cdc_distortion", "cdc_lpips_create", "cdc_lpips", "cdc_simple_encoder_create", "cdc_simple_ctxdec_create", "cdc_op_gdn",
-           "cdc_set_solver", "cdc_decode_solver", "cdc_solver_step", "cdc_op_solver_update",
+           "cdc_set_solver", "cdc_decode_solver", "cdc_solver_step", "cdc_op_solver_update", "cdc_op_ddim_update",
            "cdc_repeat_images", "cdc_decode_samples", "cdc_sample_moments", "cdc_sample_select"]
 
 

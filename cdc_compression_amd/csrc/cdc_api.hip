@@ -1256,6 +1256,50 @@ int cdc_op_solver_update(cdc_handle *h, const float *fx, const float *x, const f
     });
 }
 
+int cdc_op_ddim_update(cdc_handle *h, const float *fx, const float *x, const float *noise, const uint64_t *seeds, float eta, int i,
+                       float *x_next, int B, int C, int H, int W, int pred_mode, int clip, const float *planes, const float *plane_bias,
+                       int KH, int pad, int mem, void *stream) {
+    if (!h) return CDC_ERR_INVALID;
+    return no_throw(h, [&] {
+        return with_range_guard(h, [&]() -> int {
+            int rc = require_kind(h, HandleKind::Unet);
+            if (rc) return rc;
+            if ((rc = ensure_device(h))) return rc;
+            if ((rc = sampler_ready(h, pred_mode, clip, false))) return rc;
+            if (!x || !x_next) return fail(h, CDC_ERR_INVALID, "null argument");
+            if (!fx == !planes) return fail(h, CDC_ERR_INVALID, "ddim_update: the model output is either fx or planes");
+            if (planes && (KH < 1 || pad < 0 || pad >= KH)) return fail(h, CDC_ERR_INVALID, "ddim_update: KH %d / pad %d", KH, pad);
+            if (B < 1 || C < 1 || H < 1 || W < 1 || (long long)B * C * H * W > (1ll << 40) ||
+                (planes && (long long)B * C * H * W > (1ll << 40) / KH))
+                return fail(h, CDC_ERR_INVALID, "ddim_update: %d x %d x %d x %d elements", B, C, H, W);
+            if (i < 0 || i >= h->steps) return fail(h, CDC_ERR_INVALID, "step index %d out of [0,%d)", i, h->steps);
+            if (mem != CDC_MEM_HOST && mem != CDC_MEM_DEVICE) return fail(h, CDC_ERR_INVALID, "ddim_update: mem_kind %d", mem);
+            if (!(fabsf(eta) <= 3.0e38f)) return fail(h, CDC_ERR_INVALID, "ddim_update: eta is not finite");
+            if (noise && seeds) return fail(h, CDC_ERR_INVALID, "ddim_update: the noise is either a tensor or seeds");
+            if (eta != 0.f && !noise && !seeds) return fail(h, CDC_ERR_INVALID, "eta != 0 needs the noise draw or the seeds");
+            if (seeds && B > 65535) return fail(h, CDC_ERR_INVALID, "ddim_update: seeds serve a batch of at most 65535");
+            hipStream_t st = pick_stream(h, stream, mem);
+            const size_t n = (size_t)B * C * H * W, bytes = n * sizeof(float);
+            if (eta != 0.f && seeds && (rc = h->seeds.stage(h, seeds, (size_t)B, st))) return rc;
+            Staging s(h, mem, st);
+            const float *dfx = fx ? s.in(fx, bytes) : nullptr, *dx = s.in(x, bytes);
+            const float *dP = planes ? s.in(planes, bytes * KH) : nullptr;
+            const float *dPb = planes && plane_bias ? s.in(plane_bias, (size_t)C * sizeof(float)) : nullptr;
+            const float *dz = eta != 0.f && noise ? s.in(noise, bytes) : nullptr;
+            float *dn = s.out(x_next, bytes);
+            if (s.ok()) {
+                DdimArgs d = {sampler_args(h, dfx, dx, dn, i, B, C, H, W, pred_mode, clip, nullptr)};
+                if (dP) { d.s.P = dP; d.s.P_bias = dPb; d.s.pKH = KH; d.s.pPad = pad; }
+                d.eta = eta;
+                if (eta != 0.f && seeds) { d.seeds = h->seeds.dev.p; d.per_image = (long long)(n / B); }
+                else d.noise = dz;
+                s.e = ddim_launch(d, st);
+            }
+            return s.finish("ddim_update");
+        });
+    });
+}
+
 // ---- the generator behind entry points of its own (rng.h) ---------------------------------------------------------------------
 static int randn_args(cdc_handle *h, const uint64_t *seeds, int B, int64_t per_image, const float *out) {
     const char *bad = (!seeds || !out) ? "null argument" : (B < 1 || B > 65535) ? "batch outside [1, 65535]"

@@ -224,6 +224,15 @@ int cdc_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out
  * cdc_op_solver_update: the sampler kernel alone on given tensors [B][C][H][W] -- fx is the network output -- with the handle's
  *   tables; no weights are needed.  x0_out may be x0_prev (in place).  W a multiple of 4 and 16-byte aligned tensors take the four-pixel
  *   kernel, anything else the scalar one; both give the same bits.
+ * cdc_op_ddim_update: its counterpart for the DDIM update (the rule every decode runs by default; cdc_ddim_step states it), with the
+ *   tables of cdc_set_schedule (and cdc_set_schedule_v for CDC_PRED_V); no solver tables and no weights are needed.  The noise of the
+ *   step: eta == 0: none (noise and seeds are not looked at);  seeds != NULL: B uint64_t on the host, image b draws
+ *   z(seeds[b], draw i + 1, element inside its own C * H * W elements) inside the kernel, B <= 65535;  else `noise` is the tensor
+ *   [B][C][H][W].  eta != 0 with neither, both at once, and a non-finite eta are refused.  The model output is `fx`, or -- planes !=
+ *   NULL, fx == NULL -- the row combine of the final convolution's partial planes evaluated inside the kernel:
+ *   fx[b][c][y][x] = plane_bias[c] (0 when NULL) + sum over ky = 0 .. KH-1 with 0 <= y + ky - pad < H, ascending, of
+ *   planes[b][c][ky][y + ky - pad][x];  planes is [B][C][KH][H][W], plane_bias [C], 1 <= KH, 0 <= pad < KH.  x_next may be x (in
+ *   place).  The traversal is chosen as for cdc_op_solver_update (a batch * channels above 65535 takes the scalar kernel too).
  * All follow `mem` / `stream` as cdc_decode does and need a U-Net handle. */
 int cdc_set_solver(cdc_handle *h, int steps, const float *a, const float *b, const float *c);
 int cdc_decode_solver(cdc_handle *h, const float *init, float gamma, const uint64_t *seeds /* nullable */, const float *const *ctx,
@@ -232,6 +241,10 @@ int cdc_solver_step(cdc_handle *h, const float *x_in, const float *x0_prev_in, i
                     float *x_out, float *x0_out, int B, int H, int W, int pred_mode, int clip, int mem, void *stream);
 int cdc_op_solver_update(cdc_handle *h, const float *fx, const float *x, const float *x0_prev, int i, float *x_next, float *x0_out,
                          int B, int C, int H, int W, int pred_mode, int clip, int mem, void *stream);
+int cdc_op_ddim_update(cdc_handle *h, const float *fx, const float *x, const float *noise /* nullable */,
+                       const uint64_t *seeds /* nullable, host, [B] */, float eta, int i, float *x_next, int B, int C, int H, int W,
+                       int pred_mode, int clip, const float *planes /* nullable */, const float *plane_bias /* nullable */, int KH,
+                       int pad, int mem, void *stream);
 
 /* ---- K seeded samples per image (no reference counterpart: the reference cannot ask for "sample k") -------------------------------
  * A seeded decode is a pure function of (stream, seed, gamma, eta, steps), so one stream has as many reconstructions as there are

@@ -14,6 +14,7 @@ import cdc_compression_amd as cdc
 from cdc_compression_amd import _lib, synth
 from cdc_compression_amd.schedule import SampleSchedule
 from helpers import GOLDEN, load_case
+from sampler_ref import predict_x0_f64
 from test_gpu_parity import TOL_DEC, make_unet, relerr
 
 pytestmark = pytest.mark.gpu
@@ -53,17 +54,7 @@ def tabled():
 def _update_f64(s, a, b, c, i, fx, x, prev, pred, clip):
     """-> x0, its rounding bound where the kernel computes it, and the three terms of the update, all float64."""
     fx, x, prev = (t.astype(np.float64) for t in (fx, x, prev))
-    d = lambda t: np.float64(t[i])                                   # noqa: E731
-    if pred == _lib.CDC_PRED_X:
-        x0, e0 = fx, np.zeros_like(fx)
-    else:
-        p, q = (d(s.sqrt_ac), d(s.sqrt_one_minus_ac)) if pred == _lib.CDC_PRED_V else (d(s.sqrt_recip), d(s.sqrt_recipm1))
-        x0 = p * x - q * fx
-        e0 = U * (np.abs(p * x) + np.abs(q * fx) + np.abs(x0))       # two products and one difference, each rounded once
-    B = x.shape[0]
-    nclip = {_lib.CDC_CLIP_NONE: 0, _lib.CDC_CLIP_ALL: B, _lib.CDC_CLIP_HALF: B // 2}[clip]
-    x0 = x0.copy()
-    x0[:nclip] = np.clip(x0[:nclip], -1.0, 1.0)                       # (the clamp is exact and does not enlarge an error)
+    x0, e0 = predict_x0_f64(s, i, fx, x, pred, clip)                 # (shared with the DDIM update's statement)
     return x0, e0, (a[i] * x, b[i] * x0, c[i] * prev)
 
 

@@ -152,5 +152,5 @@ def test_keywords_are_on_every_public_entry_and_checked_before_anything_runs():
             diff.decompress([np.zeros((1, 3, 64, 64), np.float32)], sample_steps=4, sampler="order1")
         with pytest.raises(ValueError, match="eta must be 0"):
             diff.compress(np.zeros((1, 3, 64, 64), np.float32), sample_steps=4, eta=0.5, seed=1, sampler="dpmpp_2m")
-    for name in ("cdc_set_solver", "cdc_decode_solver", "cdc_solver_step", "cdc_op_solver_update"):
+    for name in ("cdc_set_solver", "cdc_decode_solver", "cdc_solver_step", "cdc_op_solver_update", "cdc_op_ddim_update"):
         assert name in _lib.EXPORTS and hasattr(_lib.lib(), name)
