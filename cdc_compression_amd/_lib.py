@@ -17,6 +17,7 @@ CDC_MAX_LEVELS = 8
 CDC_ELEM_F32, CDC_ELEM_U8 = 0, 1
 CDC_FILL_EDGE, CDC_FILL_ZERO = 0, 1
 CDC_METRIC_PSNR, CDC_METRIC_MSSSIM = 1, 2
+CDC_TRACE_X0, CDC_TRACE_XT, CDC_TRACE_U8 = 1, 2, 4
 
 _f = ctypes.POINTER(ctypes.c_float)
 _i = ctypes.c_int
@@ -152,6 +153,11 @@ def lib():
     L.cdc_solver_step.argtypes = [H, _vp, _vp, _i, pp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]
     L.cdc_op_solver_update.argtypes = [H, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]
     L.cdc_op_ddim_update.argtypes = [H, _vp, _vp, _vp, u64p, ctypes.c_float, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp]
+    ip = ctypes.POINTER(_i)
+    L.cdc_set_trace.argtypes = [H, ip, _i, _i, _i, _i]
+    L.cdc_trace_info.argtypes = [H, ip, ip, ip, ip, ip, ip]
+    L.cdc_trace_read.argtypes = [H, _i, _i, _i, _vp, _i, _vp]
+    L.cdc_op_trace_tap.argtypes = [H, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp]
     L.cdc_repeat_images.argtypes =[H, _vp, _vp, _i, _i, ctypes.c_int64, _i, _i, _vp]
     L.cdc_decode_samples.argtypes = [H, ctypes.c_float, u64p, ctypes.c_float, pp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]
     L.cdc_sample_moments.argtypes = [H, _vp, _i, _i, ctypes.c_int64, _i, _vp, _vp, _i, _i, _vp]
@@ -196,7 +202,8 @@ EXPORTS = ["cdc_create", "cdc_destroy", "cdc_last_error", "cdc_version", "cdc_nu
            "cdc_entropy_peek_image_size", "cdc_decode_seeded", "cdc_randn", "cdc_randn_host", "cdc_philox4x32_10",
            "cdc_distortion", "cdc_lpips_create", "cdc_lpips", "cdc_simple_encoder_create", "cdc_simple_ctxdec_create", "cdc_op_gdn",
            "cdc_set_solver", "cdc_decode_solver", "cdc_solver_step", "cdc_op_solver_update", "cdc_op_ddim_update",
-           "cdc_repeat_images", "cdc_decode_samples", "cdc_sample_moments", "cdc_sample_select"]
+           "cdc_repeat_images", "cdc_decode_samples", "cdc_sample_moments", "cdc_sample_select",
+           "cdc_set_trace", "cdc_trace_info", "cdc_trace_read", "cdc_op_trace_tap"]
 
 
 def handle_status(handle):

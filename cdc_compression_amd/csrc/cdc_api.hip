@@ -314,6 +314,7 @@ void cdc_destroy(cdc_handle *h) {
     h->d_rep_stage.release();
     h->picks.dev.release();
     if (h->metric_work) (void)hipFree(h->metric_work);
+    if (h->trace_buf) (void)hipFree(h->trace_buf);
     (void)resolve_pending(h);
     for (hipEvent_t e : h->ev_free) (void)hipEventDestroy(e);
     if (h->gev_in) (void)hipEventDestroy(h->gev_in);
@@ -942,8 +943,11 @@ struct StepNoise { const float *tensor = nullptr; const unsigned long long *seed
 // One iteration: the U-Net on h->in_x, then the update h->in_x -> x_out.  solver: x_out = a x + b x0 + c hist, hist <- x0 (h->d_hist, in
 // place); else the DDIM update with `noise`.  The 7-row combine of the final convolution rides in the sampler kernel (one launch and a
 // 3-channel tensor less per iteration).
+// `trace` (a traced decode, at a step that is recorded): the tap of x0 runs before the update -- x_out may be h->in_x -- from the
+// very SamplerArgs the update gets; x_t is captured after it: a device-to-device copy (float32 slots) or the crop kernel (uint8).
+struct TraceStep { void *x0 = nullptr, *xt = nullptr; int u8 = 0, win_h = 0, win_w = 0; };
 static int sampler_on_device(cdc_handle *h, bool solver, int i, StepNoise noise, float eta, float *x_out, int B, int H, int W, int pred_mode,
-                             int clip, hipStream_t st) {
+                             int clip, hipStream_t st, const TraceStep *trace = nullptr) {
     int rc;
     static const bool fuse_combine = getenv("CDC_NO_COMBINE_FUSE") == nullptr;
     const CombineArgs *cb = (fuse_combine && !h->ops.empty()) ? h->ops.back().get<CombineArgs>() : nullptr;
@@ -951,12 +955,64 @@ static int sampler_on_device(cdc_handle *h, bool solver, int i, StepNoise noise,
     if ((rc = run_unet(h, st, i, cb != nullptr))) return rc;
     SamplerArgs s = sampler_args(h, h->out_fx, h->in_x, x_out, i, B, h->cfg.channels, H, W, pred_mode, clip, h->d_fault);
     if (cb) { s.P = cb->P; s.P_bias = cb->bias; s.pC = cb->Cout; s.pKH = cb->KH; s.pPad = cb->pad; s.pH = cb->H; s.pW = cb->W; }
-    if (solver) return run_op(h, Op(PC_SMALL, SolverArgs{s, h->d_hist.p, h->d_stab.p}, 0, 20.0 * s.n), B, st);
-    DdimArgs d = {s};
-    d.eta = eta;
-    if (eta != 0.f && noise.seeds) { d.seeds = noise.seeds; d.per_image = s.n / B; }
-    else if (eta != 0.f) d.noise = noise.tensor;
-    return run_op(h, Op(PC_SMALL, d, 0, 16.0 * s.n), B, st);
+    if (trace && trace->x0) {
+        TraceArgs t = {s, trace->x0, trace->u8, trace->win_h, trace->win_w};
+        t.s.x_next = nullptr; t.s.fault = nullptr;
+        const double per = (cb ? 4.0 * cb->KH : 4.0) + 4.0;      // bytes read per element; written: 4 (float32) or 1 per window element
+        const double wr = trace->u8 ? (double)B * s.pC * trace->win_h * trace->win_w : 4.0 * s.n;
+        if ((rc = run_op(h, Op(PC_SMALL, t, 0, per * s.n + wr), B, st))) return rc;
+    }
+    if (solver) rc = run_op(h, Op(PC_SMALL, SolverArgs{s, h->d_hist.p, h->d_stab.p}, 0, 20.0 * s.n), B, st);
+    else {
+        DdimArgs d = {s};
+        d.eta = eta;
+        if (eta != 0.f && noise.seeds) { d.seeds = noise.seeds; d.per_image = s.n / B; }
+        else if (eta != 0.f) d.noise = noise.tensor;
+        rc = run_op(h, Op(PC_SMALL, d, 0, 16.0 * s.n), B, st);
+    }
+    if (rc || !trace || !trace->xt) return rc;
+    if (!trace->u8) {
+        HIP_TRY(h, hipMemcpyAsync(trace->xt, x_out, (size_t)s.n * sizeof(float), hipMemcpyDeviceToDevice, st));
+        return CDC_OK;
+    }
+    const int P = B * h->cfg.channels;
+    return run_op(h, Op(PC_SMALL, FrameOutOp{x_out, trace->xt, 1, P, trace->win_h, trace->win_w, H, W}, 0, 5.0 * P * trace->win_h * trace->win_w), B, st);
+}
+
+// The slots of a traced decode (cdc_set_trace) for B images of H x W at the schedule in force: the request checked, the buffer sized
+// in 64 bits and allocated, before anything is launched.  slot_of[i]: the slot of sample index i in execution order, or -1.
+static int trace_plan(cdc_handle *h, int B, int H, int W, std::vector<int> *slot_of) {
+    h->tr_slots = 0;
+    if (B < 1 || H < 1 || W < 1) return fail(h, CDC_ERR_INVALID, "trace: B=%d %dx%d", B, H, W);
+    slot_of->assign((size_t)h->steps, -1);
+    for (int i : h->trace_steps) {
+        if (i < 0 || i >= h->steps) return fail(h, CDC_ERR_INVALID, "trace: sample index %d out of [0,%d)", i, h->steps);
+        if ((*slot_of)[i] != -1) return fail(h, CDC_ERR_INVALID, "trace: sample index %d is given twice", i);
+        (*slot_of)[i] = 0;
+    }
+    int S = 0;
+    for (int i = h->steps - 1; i >= 0; --i)
+        if ((*slot_of)[i] == 0) (*slot_of)[i] = S++;
+    const int u8 = (h->trace_what & CDC_TRACE_U8) != 0, C = h->cfg.channels;
+    const int wh = u8 ? (h->trace_win_h ? h->trace_win_h : H) : H, ww = u8 ? (h->trace_win_w ? h->trace_win_w : W) : W;
+    if (wh < 1 || wh > H || ww < 1 || ww > W) return fail(h, CDC_ERR_INVALID, "trace: window %d x %d outside the %d x %d frame", wh, ww, H, W);
+    const int kinds = ((h->trace_what & CDC_TRACE_X0) ? 1 : 0) + ((h->trace_what & CDC_TRACE_XT) ? 1 : 0);
+    const double slot_d = (double)B * C * wh * ww * (u8 ? 1 : 4), total_d = slot_d * S * kinds;
+    if (total_d > (double)(1ull << 40))
+        return fail(h, CDC_ERR_NOMEM, "trace: %d slots x %d kind(s) of %.0f bytes (%d x %d x %d x %d, %d byte(s) each) = %.0f bytes, beyond 2^40", S,
+                    kinds, slot_d, B, C, wh, ww, u8 ? 1 : 4, total_d);
+    const size_t slot = (size_t)B * C * wh * ww * (u8 ? 1 : 4), total = slot * S * kinds;
+    if (total > h->trace_cap) {
+        if (h->trace_buf) { (void)hipFree(h->trace_buf); h->trace_buf = nullptr; h->trace_cap = 0; }     // (hipFree waits for queued reads of it)
+        if (hipMalloc(&h->trace_buf, total) != hipSuccess) {
+            (void)hipGetLastError();
+            h->trace_buf = nullptr;
+            return fail(h, CDC_ERR_NOMEM, "trace: hipMalloc of %zu bytes failed (%d slots x %d kind(s) of %zu bytes)", total, S, kinds, slot);
+        }
+        h->trace_cap = total;
+    }
+    h->tr_slot_bytes = slot; h->tr_what = h->trace_what; h->tr_B = B; h->tr_C = C; h->tr_H = wh; h->tr_W = ww;
+    return S;
 }
 
 // cdc_ddim_step and cdc_solver_step: one iteration from and to the caller's memory.  They differ in the extra input (`extra_in`: the
@@ -1022,6 +1078,15 @@ static int decode_impl(cdc_handle *h, const float *init, float gamma, const uint
         if ((rc = check_ready(h))) return rc;
         if ((rc = sampler_ready(h, pred_mode, clip, solver))) return rc;
         if (!out || !ctx) return fail(h, CDC_ERR_INVALID, "null argument");
+        // a trace (cdc_set_trace): checked and its buffer allocated before anything is launched; the BF16X3 repetition comes through
+        // here again and records from the start
+        const bool traced = !h->trace_steps.empty();
+        std::vector<int> slot_of;
+        int n_slots = 0;
+        if (traced) {
+            if (rep) return fail(h, CDC_ERR_INVALID, "cdc_decode_samples: a trace is set (cdc_set_trace); a trajectory belongs to a single decode");
+            if ((n_slots = trace_plan(h, B, H, W, &slot_of)) < 0) return n_slots;
+        }
         if ((rc = build_program(h, B, H, W))) return rc;
         if ((rc = ensure_time_rows(h, B))) return rc;
         hipStream_t st = pick_stream(h, stream, mem);
@@ -1039,7 +1104,15 @@ static int decode_impl(cdc_handle *h, const float *init, float gamma, const uint
             dseeds = h->seeds.dev.p;
         }
         // one iteration, in place on h->in_x; i = -2: the step index comes from h->d_step (graph capture)
-        auto iterate = [&](int i, hipStream_t s) { return sampler_on_device(h, solver, i, {nullptr, dseeds}, eta, h->in_x, B, H, W, pred_mode, clip, s); };
+        const bool tr_u8 = traced && (h->tr_what & CDC_TRACE_U8);
+        uint8_t *const tr_x0 = traced && (h->tr_what & CDC_TRACE_X0) ? (uint8_t *)h->trace_buf : nullptr;
+        uint8_t *const tr_xt = !traced || !(h->tr_what & CDC_TRACE_XT) ? nullptr : (uint8_t *)h->trace_buf + (tr_x0 ? (size_t)n_slots * h->tr_slot_bytes : 0);
+        auto iterate = [&](int i, hipStream_t s) {
+            if (!traced || i < 0 || slot_of[i] < 0) return sampler_on_device(h, solver, i, {nullptr, dseeds}, eta, h->in_x, B, H, W, pred_mode, clip, s);
+            const size_t off = (size_t)slot_of[i] * h->tr_slot_bytes;
+            const TraceStep t = {tr_x0 ? tr_x0 + off : nullptr, tr_xt ? tr_xt + off : nullptr, tr_u8 ? 1 : 0, h->tr_H, h->tr_W};
+            return sampler_on_device(h, solver, i, {nullptr, dseeds}, eta, h->in_x, B, H, W, pred_mode, clip, s, &t);
+        };
         if (init) { if ((rc = copy_in(h, h->in_x, init, n, mem, st))) return rc; }
         else if (gen_init) HIP_TRY(h, randn_fill_launch(dseeds, B, (long long)(n / B), 0u, gamma, h->in_x, st));
         else HIP_TRY(h, hipMemsetAsync(h->in_x, 0, n * sizeof(float), st));
@@ -1052,7 +1125,7 @@ static int decode_impl(cdc_handle *h, const float *init, float gamma, const uint
         // faster -- 5.8 ms / iteration at batch 1 either way: the ~170 kernels of an iteration are bound by their own
         // serial latency (tiny grids), not by host launches -- so the eager loop stays the default.
         const char *genv = getenv("CDC_GRAPH");           // 0 / 1 overrides the batch-size rule
-        const bool use_graph = !h->prof && h->steps > 2 && genv && atoi(genv) != 0;
+        const bool use_graph = !traced && !h->prof && h->steps > 2 && genv && atoi(genv) != 0;      // (a traced decode runs the eager loop)
         int i = h->steps - 1;
         if (use_graph) {
             // the legacy default stream cannot be captured: iterate on the library's own stream, fenced by events
@@ -1103,6 +1176,7 @@ static int decode_impl(cdc_handle *h, const float *init, float gamma, const uint
         // Range guard: a non-finite U-Net output is flagged by the sampler kernel of the iteration it occurs in; the final image
         // is checked as well.  One 4-byte read-back per decode.
         if ((rc = range_check(h, {{h->in_x, 0, (long long)n}}, 1, st))) return rc;
+        if (traced) h->tr_slots = n_slots;
         return copy_out(h, out, h->in_x, n, mem, st);
     });
 }
@@ -1296,6 +1370,98 @@ int cdc_op_ddim_update(cdc_handle *h, const float *fx, const float *x, const flo
                 s.e = ddim_launch(d, st);
             }
             return s.finish("ddim_update");
+        });
+    });
+}
+
+// ---- decode trajectory (the tap kernel of sampler_kernels.hip; the recording itself is decode_impl's) --------------------------------
+int cdc_set_trace(cdc_handle *h, const int *steps, int n, int what, int win_h, int win_w) {
+    if (!h) return CDC_ERR_INVALID;
+    return no_throw(h, [&]() -> int {
+        int rc = require_kind(h, HandleKind::Unet);
+        if (rc) return rc;
+        if (n < 0 || (n > 0 && !steps)) return fail(h, CDC_ERR_INVALID, "set_trace: n = %d%s", n, n > 0 ? " with null steps" : "");
+        if (n == 0) { h->trace_steps.clear(); h->trace_what = 0; h->trace_win_h = h->trace_win_w = 0; return CDC_OK; }
+        if ((what & ~(CDC_TRACE_X0 | CDC_TRACE_XT | CDC_TRACE_U8)) || !(what & (CDC_TRACE_X0 | CDC_TRACE_XT)))
+            return fail(h, CDC_ERR_INVALID, "set_trace: what = %d (CDC_TRACE_X0 | CDC_TRACE_XT, at least one, and CDC_TRACE_U8)", what);
+        if (win_h < 0 || win_w < 0) return fail(h, CDC_ERR_INVALID, "set_trace: window %d x %d", win_h, win_w);
+        h->trace_steps.assign(steps, steps + n);
+        h->trace_what = what; h->trace_win_h = win_h; h->trace_win_w = win_w;
+        return CDC_OK;
+    });
+}
+
+int cdc_trace_info(cdc_handle *h, int *n_slots, int *B, int *C, int *H, int *W, int *what) {
+    if (!h) return CDC_ERR_INVALID;
+    const bool any = h->tr_slots > 0;
+    if (n_slots) *n_slots = h->tr_slots;
+    if (B) *B = any ? h->tr_B : 0;
+    if (C) *C = any ? h->tr_C : 0;
+    if (H) *H = any ? h->tr_H : 0;
+    if (W) *W = any ? h->tr_W : 0;
+    if (what) *what = any ? h->tr_what : 0;
+    return CDC_OK;
+}
+
+int cdc_trace_read(cdc_handle *h, int kind, int slot0, int n_slots, void *out, int mem, void *stream) {
+    if (!h) return CDC_ERR_INVALID;
+    return no_throw(h, [&]() -> int {
+        int rc = ensure_device(h);
+        if (rc) return rc;
+        if (h->tr_slots < 1 || !h->trace_buf) return fail(h, CDC_ERR_STATE, "trace_read: no traced decode has run on this handle");
+        if ((kind != CDC_TRACE_X0 && kind != CDC_TRACE_XT) || !(h->tr_what & kind))
+            return fail(h, CDC_ERR_INVALID, "trace_read: kind %d was not recorded (what = %d)", kind, h->tr_what);
+        if (!out || slot0 < 0 || n_slots < 1 || slot0 > h->tr_slots - n_slots)
+            return fail(h, CDC_ERR_INVALID, "trace_read: slots %d .. +%d of %d, or a null pointer", slot0, n_slots, h->tr_slots);
+        if (mem != CDC_MEM_HOST && mem != CDC_MEM_DEVICE) return fail(h, CDC_ERR_INVALID, "trace_read: mem_kind %d", mem);
+        hipStream_t st = pick_stream(h, stream, mem);
+        const size_t first = (kind == CDC_TRACE_XT && (h->tr_what & CDC_TRACE_X0)) ? (size_t)h->tr_slots : 0;
+        const uint8_t *src = (const uint8_t *)h->trace_buf + (first + (size_t)slot0) * h->tr_slot_bytes;
+        const size_t bytes = (size_t)n_slots * h->tr_slot_bytes;
+        if (mem == CDC_MEM_HOST) {
+            HIP_TRY(h, hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, st));
+            HIP_TRY(h, hipStreamSynchronize(st));
+        } else {
+            HIP_TRY(h, hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToDevice, st));
+        }
+        return CDC_OK;
+    });
+}
+
+int cdc_op_trace_tap(cdc_handle *h, const float *fx, const float *x, int i, void *out, int B, int C, int H, int W, int pred_mode, int clip,
+                     int elem, int win_h, int win_w, const float *planes, const float *plane_bias, int KH, int pad, int mem, void *stream) {
+    if (!h) return CDC_ERR_INVALID;
+    return no_throw(h, [&] {
+        return with_range_guard(h, [&]() -> int {
+            int rc = require_kind(h, HandleKind::Unet);
+            if (rc) return rc;
+            if ((rc = ensure_device(h))) return rc;
+            if ((rc = sampler_ready(h, pred_mode, clip, false))) return rc;
+            if (!x || !out) return fail(h, CDC_ERR_INVALID, "null argument");
+            if (!fx == !planes) return fail(h, CDC_ERR_INVALID, "trace_tap: the model output is either fx or planes");
+            if (planes && (KH < 1 || pad < 0 || pad >= KH)) return fail(h, CDC_ERR_INVALID, "trace_tap: KH %d / pad %d", KH, pad);
+            if (B < 1 || C < 1 || H < 1 || W < 1 || (long long)B * C * H * W > (1ll << 40) ||
+                (planes && (long long)B * C * H * W > (1ll << 40) / KH))
+                return fail(h, CDC_ERR_INVALID, "trace_tap: %d x %d x %d x %d elements", B, C, H, W);
+            if (i < 0 || i >= h->steps) return fail(h, CDC_ERR_INVALID, "step index %d out of [0,%d)", i, h->steps);
+            if (elem != CDC_ELEM_F32 && elem != CDC_ELEM_U8) return fail(h, CDC_ERR_INVALID, "trace_tap: element kind %d", elem);
+            const int u8 = elem == CDC_ELEM_U8;
+            if (u8 && (win_h < 1 || win_h > H || win_w < 1 || win_w > W))
+                return fail(h, CDC_ERR_INVALID, "trace_tap: window %d x %d outside the %d x %d frame", win_h, win_w, H, W);
+            if (mem != CDC_MEM_HOST && mem != CDC_MEM_DEVICE) return fail(h, CDC_ERR_INVALID, "trace_tap: mem_kind %d", mem);
+            hipStream_t st = pick_stream(h, stream, mem);
+            const size_t n = (size_t)B * C * H * W, bytes = n * sizeof(float);
+            Staging s(h, mem, st);
+            const float *dfx = fx ? s.in(fx, bytes) : nullptr, *dx = s.in(x, bytes);
+            const float *dP = planes ? s.in(planes, bytes * KH) : nullptr;
+            const float *dPb = planes && plane_bias ? s.in(plane_bias, (size_t)C * sizeof(float)) : nullptr;
+            void *dout = s.out((uint8_t *)out, u8 ? (size_t)B * C * win_h * win_w : bytes);
+            if (s.ok()) {
+                TraceArgs t = {sampler_args(h, dfx, dx, nullptr, i, B, C, H, W, pred_mode, clip, nullptr), dout, u8, win_h, win_w};
+                if (dP) { t.s.P = dP; t.s.P_bias = dPb; t.s.pKH = KH; t.s.pPad = pad; }
+                s.e = trace_tap_launch(t, st);
+            }
+            return s.finish("trace_tap");
         });
     });
 }

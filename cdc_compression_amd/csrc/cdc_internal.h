@@ -272,6 +272,16 @@ struct SolverArgs {
     const float *stab;     // device table [3][steps]: a, b, c (cdc_set_solver)
 };
 hipError_t solver_launch(const SolverArgs &a, hipStream_t st);
+// The tap of a decode trajectory (cdc_set_trace, cdc_op_trace_tap): the prediction x0 the update of this step is about to use -- the
+// same model output, predict_x0 and clip as the sampler kernel launched after it -- written to `out`: float32 of the frame's shape
+// (u8 = 0), or the as-saved bytes (frame_pixel.h) of the top-left win_h x win_w window of every plane, [planes][win_h][win_w] (u8 = 1).
+// s.x_next, s.fault and s.step_ptr are not used.  The traversal is chosen as sampler_launch chooses it.
+struct TraceArgs {
+    SamplerArgs s;
+    void *out;
+    int u8, win_h, win_w;
+};
+hipError_t trace_tap_launch(const TraceArgs &a, hipStream_t st);
 // out[b][e] = scale * z(seeds[b], draw, e) for e < per_image (rng.h; seeds on the device); 16-byte stores when the layout allows
 hipError_t randn_fill_launch(const unsigned long long *seeds, int B, long long per_image, unsigned draw, float scale, float *out,
                              hipStream_t st);

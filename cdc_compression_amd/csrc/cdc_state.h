@@ -91,9 +91,10 @@ struct CtxPartialOp { AttnCtxArgs a; };
 struct CtxOneOp { AttnCtxArgs a; };
 struct CtxReduceOp { AttnCtxArgs a; };
 struct CtxFoldOp { AttnCtxArgs a; };
+struct FrameOutOp { const float *src; void *dst; int u8, P, H, W, Hp, Wp; };    // the crop kernel (frame_kernels.hip): a trajectory's x_t bytes
 using OpPayload = std::variant<ConvOp, PfConvOp, PwConvOp, WsConvOp, Ws1ConvOp, PfPackOp, C4PackOp, PfUnpackOp, LnArgs, TembArgs, KstatsOp,
                                CtxPartialOp, CtxOneOp, CtxReduceOp, CtxFoldOp, KvCtxArgs, LnConvArgs, CombineArgs, DdimArgs, SolverArgs, CopyArgs,
-                               UnfoldArgs, VbrArgs, MaxpoolArgs, LpipsHeadArgs, GdnArgs>;
+                               UnfoldArgs, VbrArgs, MaxpoolArgs, LpipsHeadArgs, GdnArgs, TraceArgs, FrameOutOp>;
 
 struct Op {
     int prof;
@@ -132,6 +133,8 @@ inline hipError_t op_launch(const VbrArgs &a, int B, hipStream_t st) { return vb
 inline hipError_t op_launch(const MaxpoolArgs &a, int B, hipStream_t st) { return maxpool2_launch(a, B, st); }
 inline hipError_t op_launch(const LpipsHeadArgs &a, int B, hipStream_t st) { return lpips_head_launch(a, B / 2, st); }
 inline hipError_t op_launch(const GdnArgs &a, int B, hipStream_t st) { return gdn_launch(a, B, st); }
+inline hipError_t op_launch(const TraceArgs &a, int, hipStream_t st) { return trace_tap_launch(a, st); }
+inline hipError_t op_launch(const FrameOutOp &o, int, hipStream_t st) { return frame_out_launch(o.src, o.dst, o.u8, o.P, o.H, o.W, o.Hp, o.Wp, st); }
 
 // The op's line of the per-op profile table (cdc_prof_op).  hoisted: the op belongs to the context-only part of the program; the
 // convolutions say so in the middle of their line, Builder::emit appends " HOIST" to every other hoisted op.
@@ -181,6 +184,8 @@ inline void op_label(const VbrArgs &a, char *buf, size_t n, bool) { snprintf(buf
 inline void op_label(const MaxpoolArgs &a, char *buf, size_t n, bool) { snprintf(buf, n, "maxpool2 C=%d in %dx%d", a.C, a.H, a.W); }
 inline void op_label(const LpipsHeadArgs &a, char *buf, size_t n, bool) { snprintf(buf, n, "lpips_head tap %d C=%d HW=%d", a.layer, a.C, a.HW); }
 inline void op_label(const GdnArgs &a, char *buf, size_t n, bool) { snprintf(buf, n, "gdn C=%d HW=%d%s", a.C, a.HW, a.inverse ? " inv" : ""); }
+inline void op_label(const TraceArgs &a, char *buf, size_t n, bool) { snprintf(buf, n, "trace x0%s", a.u8 ? " u8" : ""); }
+inline void op_label(const FrameOutOp &o, char *buf, size_t n, bool) { snprintf(buf, n, "trace x_t%s", o.u8 ? " u8" : ""); }
 
 struct GdnW { int C = 0; bool inverse = false; float *beta = nullptr, *gamma = nullptr; };   // one GDN1 layer: reparametrised beta' [C], gamma' [C][C] (device)
 struct VbrW { int C = 0; float *p = nullptr; };   // one VBRCondition site: [scale.weight | scale.bias | shift.weight | shift.bias], C each
@@ -317,6 +322,14 @@ struct cdc_handle {
     // CDC_ERR_NOMEM with a text of its own, and no graph or queued work holds it)
     void *metric_work = nullptr;
     size_t metric_cap = 0;
+    // decode trajectory (cdc_set_trace): the request, and the recording of the last traced decode.  trace_buf holds the x0 slots, then
+    // the x_t slots, tr_slots of tr_slot_bytes each, in execution order (no GrowBuf: its failure is CDC_ERR_NOMEM with the sizes in the
+    // text, and no graph reads it -- a traced decode runs the eager loop).
+    std::vector<int> trace_steps;        // the sample indices asked for, as given
+    int trace_what = 0, trace_win_h = 0, trace_win_w = 0;
+    void *trace_buf = nullptr;
+    size_t trace_cap = 0, tr_slot_bytes = 0;
+    int tr_slots = 0, tr_what = 0, tr_B = 0, tr_C = 0, tr_H = 0, tr_W = 0;
     int op_stress_n = 0;                 // cdc_op_stress: extra executions of every cdc_op_* program, results compared on the device
     long long op_stress_launches = 0, op_stress_differing = 0;
     // profiling

@@ -1,13 +1,15 @@
 // sampler_kernels.hip -- one sampler step: the model output (a tensor, or the 7-row combine of the final convolution's partial planes),
 // the prediction x0, and one of two update rules -- DDIM (xparam/modules/denoising_diffusion.py:152-174, epsilonparam :137-152; same
 // operation order as the reference) or the second-order multistep update (SolverArgs) -- in one of two traversals.  Beside them the
-// step counter of a graph-replayed iteration and the fill kernel of the generator (rng.h).
+// tap of a decode trajectory (the x0 of a step, written to a slot), the step counter of a graph-replayed iteration and the fill kernel
+// of the generator (rng.h).
 #include <math.h>
 #include <stdint.h>
 
 #include <algorithm>
 
 #include "cdc_internal.h"
+#include "frame_pixel.h"
 #include "rng.h"
 
 namespace cdc {
@@ -226,6 +228,87 @@ hipError_t ddim_launch(const DdimArgs &a, hipStream_t st) {
     return a.seeds ? sampler_launch<DdimRule<true>>(a, 0, st) : sampler_launch<DdimRule<false>>(a, (uintptr_t)a.noise, st);
 }
 hipError_t solver_launch(const SolverArgs &a, hipStream_t st) { return sampler_launch<SolverRule>(a, (uintptr_t)a.hist, st); }
+
+// ---- the tap of a decode trajectory (TraceArgs): the x0 the update of this step is about to use, from step_consts / model_out(4) /
+// predict_x0 above -- the device functions of the update, so the bits are those it sees -- in the same two traversals.  It runs before
+// the sampler kernel of its step (the decode loop updates x in place) and writes nothing but its slot.  Per element: the model output
+// (4 bytes, or the pKH planes of the fused combine: 4 pKH) + x (4) read, 4 bytes (float32 slot) or 1 byte (uint8 slot) written; for a
+// uint8 slot the threads outside the window return before they load anything.
+template <bool U8>
+__global__ void __launch_bounds__(256) trace_tap_kernel(const TraceArgs a) {
+    const SamplerArgs &s = a.s;
+    const StepConsts k = step_consts(s);
+    const long long plane = (long long)s.pH * s.pW;
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < s.n; idx += (long long)gridDim.x * blockDim.x) {
+        long long o = idx;
+        if constexpr (U8) {
+            const long long img_co = idx / plane;
+            const int pix = (int)(idx - img_co * plane), y = pix / s.pW, xx = pix - y * s.pW;
+            if (y >= a.win_h || xx >= a.win_w) continue;
+            o = (img_co * a.win_h + y) * a.win_w + xx;
+        }
+        const float x0 = predict_x0(k, model_out(s, idx), s.x[idx], idx < k.clip_n);
+        if constexpr (U8) ((uint8_t *)a.out)[o] = (uint8_t)unit_to_u8(x0);
+        else ((float *)a.out)[o] = x0;
+    }
+}
+
+// pW % 4 == 0: four pixels of one plane per thread, as sampler_rows4_kernel.  U8: the quad lies in one row; it is written as one
+// 32-bit word where the window's rows are whole quads and the slot is 4-byte aligned (OUT_VEC), byte by byte up to the window's edge
+// otherwise.
+template <bool U8, bool OUT_VEC>
+__global__ void __launch_bounds__(256) trace_tap_rows4_kernel(const TraceArgs a) {
+    const SamplerArgs &s = a.s;
+    const int plane = s.pH * s.pW;
+    const int pix = 4 * (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (pix >= plane) return;
+    const int y = pix / s.pW, xx = pix - y * s.pW;
+    if (U8 && (y >= a.win_h || xx >= a.win_w)) return;
+    const StepConsts k = step_consts(s);
+    const int img_co = blockIdx.y;
+    const long long idx = (long long)img_co * plane + pix;
+    float fx[4], x0[4];
+    model_out4(s, img_co, pix, plane, fx);
+    const float4 x4 = *reinterpret_cast<const float4 *>(s.x + idx);
+    const float xs[4] = {x4.x, x4.y, x4.z, x4.w};
+#pragma unroll
+    for (int c = 0; c < 4; ++c) x0[c] = predict_x0(k, fx[c], xs[c], idx < k.clip_n);
+    if constexpr (U8) {
+        uint8_t *d = (uint8_t *)a.out + ((long long)img_co * a.win_h + y) * a.win_w + xx;
+        uint32_t b[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) b[c] = unit_to_u8(x0[c]);
+        if constexpr (OUT_VEC) {
+            *reinterpret_cast<uint32_t *>(d) = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
+        } else {
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (xx + c < a.win_w) d[c] = (uint8_t)b[c];
+        }
+    } else {
+        *reinterpret_cast<float4 *>((float *)a.out + idx) = make_float4(x0[0], x0[1], x0[2], x0[3]);
+    }
+}
+
+// The traversal by sampler_launch's rule (a float32 slot is a pointer the four-pixel form stores 16 bytes to; a uint8 slot is not).
+hipError_t trace_tap_launch(const TraceArgs &a, hipStream_t st) {
+    const SamplerArgs &s = a.s;
+    const long long plane = (long long)s.pH * s.pW;
+    if (s.n <= 0 || !a.out || plane <= 0 || s.n % plane != 0) return hipErrorInvalidValue;
+    if (a.u8 && (a.win_h < 1 || a.win_h > s.pH || a.win_w < 1 || a.win_w > s.pW)) return hipErrorInvalidValue;
+    if ((s.pW & 3) == 0 && plane < (1ll << 30) && s.n / plane <= 65535 &&
+        (((uintptr_t)s.P | (uintptr_t)s.fx | (uintptr_t)s.x | (a.u8 ? 0 : (uintptr_t)a.out)) & 15) == 0) {
+        const dim3 g((unsigned)ceil_div((int)(plane / 4), 256), (unsigned)(s.n / plane));
+        if (!a.u8) hipLaunchKernelGGL((trace_tap_rows4_kernel<false, true>), g, dim3(256), 0, st, a);
+        else if ((a.win_w & 3) == 0 && ((uintptr_t)a.out & 3) == 0) hipLaunchKernelGGL((trace_tap_rows4_kernel<true, true>), g, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((trace_tap_rows4_kernel<true, false>), g, dim3(256), 0, st, a);
+    } else {
+        const int grid = (int)std::min<long long>((s.n + 255) / 256, 4096);
+        if (a.u8) hipLaunchKernelGGL(trace_tap_kernel<true>, dim3(grid), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(trace_tap_kernel<false>, dim3(grid), dim3(256), 0, st, a);
+    }
+    return hipGetLastError();
+}
 
 // end of a graph-replayed iteration: the next replay works on step - 1
 __global__ void step_dec_kernel(int *step) { *step -= 1; }

@@ -27,6 +27,11 @@ plain seeded decode -- and returns them, their pixel-wise mean, or mean and unbi
 the result does not depend on `sample_chunk`).  `compress_best_of` is the encoder's closed loop: it scores K candidate seeds against the
 original on the device and returns the winner with its seed, which `decompress(..., seed=)` reproduces.
 
+Decode trajectory (no reference counterpart beyond a commented-out buffer.append in its p_sample_loop; cdc_compression_amd.trajectory):
+`trajectory=` on p_sample_loop / decompress / compress / evaluate records the prediction x0 and / or the state x_t of chosen steps
+inside the device loop (cdc_set_trace) and returns a `Trajectory` beside the usual result; the trace is set for the one call and
+cleared again, also on error.
+
 Images of any size (cdc_compression_amd.frame states the rule): `compress`, `compress_to_bytes` and `decompress` pad on the device to
 the model's multiple, run on the padded frame and return the top-left `[B, 3, H, W]` window, bpp over `H * W`.  `p_sample_loop`
 mirrors the reference's method and keeps requiring frame sizes (`padded_size(H, W)` tells them).
@@ -35,7 +40,7 @@ import ctypes
 
 import numpy as np
 
-from . import _lib, frame, lpips, samples as _samples
+from . import _lib, frame, lpips, samples as _samples, trajectory as _trajectory
 from .parallel import expand_seeds, sample_seeds
 from .schedule import SAMPLERS, SampleSchedule
 from .unet import _Arg, _current_stream, _is_torch, _result_like
@@ -145,14 +150,17 @@ class _GaussianDiffusionBase:
             context_dict["bpp"] = context_dict["bpp"] * ((Hp * Wp) / (H * W))
         return context_dict, B, H, W, Hp, Wp
 
-    def _compress_frame(self, images, sample_steps, init, eta, loop, *ctx_args, sampler="ddim", spacing="index"):
-        """compress() of both trees up to the crop: context model and sampler on the padded frame -> (frame, bpp [B], H, W)."""
+    def _compress_frame(self, images, sample_steps, init, eta, loop, *ctx_args, sampler="ddim", spacing="index", trace=None):
+        """compress() of both trees up to the crop: context model and sampler on the padded frame -> (frame, bpp [B], H, W, Trajectory
+        or None).  trace: (trajectory, trajectory_of, trajectory_dtype, seed) of the call; loop(shape, context, init, spec, window)."""
         self._sampler_args(sampler, eta)
+        spec = None if trace is None else self._trace_spec(*trace[:3], self._steps(sample_steps, spacing), eta, trace[3])
         context_dict, B, H, W, Hp, Wp = self._context_of(images, *ctx_args)
         h, dev = self.denoise_fn._handle(), self.denoise_fn.device_index
         self.set_sample_schedule(self._steps(sample_steps, spacing), sampler=sampler, spacing=spacing)
-        rec = loop((B, 3, Hp, Wp), context_dict["output"], frame.extend_init(h, init, B, H, W, Hp, Wp, dev))
-        return rec, context_dict["bpp"], H, W
+        rec = loop((B, 3, Hp, Wp), context_dict["output"], frame.extend_init(h, init, B, H, W, Hp, Wp, dev), spec, (H, W))
+        rec, traj = rec if spec is not None else (rec, None)
+        return rec, context_dict["bpp"], H, W, traj
 
     def _window(self, rec, H, W):
         """The reconstruction compress() returns: the frame's top-left H x W window (the frame itself when it is the image)."""
@@ -171,12 +179,34 @@ class _GaussianDiffusionBase:
         import inspect
         bound = dict(inspect.signature(self.compress).bind(images, *args, **kwargs).arguments)
         bound.pop("bpp_return_mean", None)                    # bpp comes per image
-        rec, bpp, H, W = self._frame_of(**bound)
+        rec, bpp, H, W, traj = self._frame_of(**bound)
         ps, ms = metrics.distortion(self.denoise_fn, rec, images, size=(H, W), as_saved=as_saved)
         out = {"reconstruction": self._window(rec, H, W), "bpp": bpp, "psnr": ps, "ms_ssim": ms}
         if self.loss_fn_vgg is not None:
             out["lpips"] = metrics.lpips(self.loss_fn_vgg, rec, images, size=(H, W), as_saved=as_saved)
+        if traj is not None:
+            out["trajectory"] = self._score_trajectory(traj, images, as_saved)
         return out
+
+    def _score_trajectory(self, traj, images, as_saved):
+        """evaluate()'s "trajectory": the Trajectory with per-slot figures of x0 (of x_t when x0 was not recorded) against `images`,
+        through the metric calls evaluate() itself uses: {"trajectory", "steps", "of", "psnr": [S][B], "ms_ssim": [S][B] or None,
+        "lpips": [S][B] when the LPIPS-VGG weights are loaded}."""
+        from . import metrics
+        of = "x0" if traj.x0 is not None else "x_t"
+        slots = traj.x0 if traj.x0 is not None else traj.x_t
+        res = {"trajectory": traj, "steps": list(traj.steps), "of": of, "psnr": [], "ms_ssim": []}
+        if self.loss_fn_vgg is not None:
+            res["lpips"] = []
+        for k in range(len(traj)):
+            ps, ms = metrics.distortion(self.denoise_fn, slots[k], images, as_saved=as_saved)
+            res["psnr"].append(ps)
+            res["ms_ssim"].append(ms)
+            if self.loss_fn_vgg is not None:
+                res["lpips"].append(metrics.lpips(self.loss_fn_vgg, slots[k], images, as_saved=as_saved))
+        if all(m is None for m in res["ms_ssim"]):
+            res["ms_ssim"] = None
+        return res
 
     # ---- schedule ---------------------------------------------------------------------------
     def set_sample_schedule(self, sample_steps, device=None, sampler="ddim", spacing="index"):
@@ -234,8 +264,28 @@ class _GaussianDiffusionBase:
             return {"x": _lib.CDC_PRED_X, "noise": _lib.CDC_PRED_NOISE_XTREE, "v": _lib.CDC_PRED_V}[self.pred_mode]
         return _lib.CDC_PRED_NOISE                        # (the eps tree's ddim ignores pred_mode: eps :137-139)
 
-    def _loop(self, shape, context, clip_denoised, init, eta, seed=None, gamma=None, sampler=None):
-        """sampler: None runs what set_sample_schedule was given."""
+    def _trace_spec(self, trajectory, trajectory_of, trajectory_dtype, steps, eta, seed, samples=None):
+        """The trajectory keywords of a call, checked before anything runs -> trajectory.Spec or None (a Spec passes through)."""
+        if isinstance(trajectory, _trajectory.Spec):
+            return trajectory
+        if trajectory is not None and steps is None:
+            raise ValueError("p_sample_loop(trajectory=) follows set_sample_schedule, which gives the number of steps")
+        return _trajectory.check_args(trajectory, trajectory_of, trajectory_dtype, steps, samples, eta, seed)
+
+    def _trajectory_result(self, slots, spec, H, W):
+        """The slots as read from the library -> Trajectory, every kind cropped to the H x W window as the reconstruction is."""
+        h, dev = self.denoise_fn._handle(), self.denoise_fn.device_index
+        kinds = {}
+        for name, t in slots.items():
+            if t is not None and tuple(t.shape[3:]) != (H, W):
+                S, B = int(t.shape[0]), int(t.shape[1])
+                t = frame.crop(h, t.reshape((S * B,) + tuple(t.shape[2:])), H, W, dev).reshape((S, B, 3, H, W))
+            kinds[name] = t
+        return _trajectory.Trajectory(spec.indices, np.asarray(self.index)[spec.indices], kinds["x0"], kinds["x_t"])
+
+    def _loop(self, shape, context, clip_denoised, init, eta, seed=None, gamma=None, sampler=None, trace=None, window=None):
+        """sampler: None runs what set_sample_schedule was given.  trace: a trajectory.Spec -> (result, Trajectory) cropped to `window`
+        ((H, W) inside the frame; None: the frame)."""
         B, C, H, W = shape
         sampler = self.sampler if sampler is None else sampler
         self._sampler_args(sampler, eta)
@@ -261,21 +311,30 @@ class _GaussianDiffusionBase:
             ai = _Arg(init, dev) if init is not None else None
             if ai is not None and ai.mem != mem:
                 raise _lib.CdcError("init and context must live in the same memory space")
-            if sampler == "dpmpp_2m":      # the multistep update in the device loop; the seeds serve the start image only
-                sd = None if seeds is None else np.asarray(seeds, dtype=np.uint64)
-                _lib.check(h, L.cdc_decode_solver(h, ai.ptr if ai else None, 0.0 if gamma is None else float(gamma),
-                                                  None if sd is None else sd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ptrs, len(actx),
-                                                  optr, B, H, W, pred, clip, mem, stream))
+
+            def device_loop():
+                if sampler == "dpmpp_2m":      # the multistep update in the device loop; the seeds serve the start image only
+                    sd = None if seeds is None else np.asarray(seeds, dtype=np.uint64)
+                    _lib.check(h, L.cdc_decode_solver(h, ai.ptr if ai else None, 0.0 if gamma is None else float(gamma),
+                                                      None if sd is None else sd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ptrs,
+                                                      len(actx), optr, B, H, W, pred, clip, mem, stream))
+                elif seeds is not None:      # every draw from the generator in the sampler kernels: any eta stays in the device loop
+                    sd = np.asarray(seeds, dtype=np.uint64)
+                    _lib.check(h, L.cdc_decode_seeded(h, ai.ptr if ai else None, 0.0 if gamma is None else float(gamma),
+                                                      sd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), float(eta), ptrs, len(actx), optr,
+                                                      B, H, W, pred, clip, mem, stream))
+                else:
+                    _lib.check(h, L.cdc_decode(h, ai.ptr if ai else None, ptrs, len(actx), optr, B, H, W, pred,
+                                               clip, mem, stream))
+            if trace is None:
+                device_loop()
                 return out
-            if seeds is not None:      # every draw from the generator in the sampler kernels: any eta stays in the device loop
-                sd = np.asarray(seeds, dtype=np.uint64)
-                _lib.check(h, L.cdc_decode_seeded(h, ai.ptr if ai else None, 0.0 if gamma is None else float(gamma),
-                                                  sd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), float(eta), ptrs, len(actx), optr,
-                                                  B, H, W, pred, clip, mem, stream))
-                return out
-            _lib.check(h, L.cdc_decode(h, ai.ptr if ai else None, ptrs, len(actx), optr, B, H, W, pred,
-                                       clip, mem, stream))
-            return out
+            wh, ww = (H, W) if window is None else window
+            with _trajectory.active(h, trace, wh, ww):       # the trace is set for this call only, and cleared on error too
+                device_loop()
+            return out, self._trajectory_result(_trajectory.read(h, trace, out, dev), trace, wh, ww)
+        if trace is not None:
+            raise ValueError("trajectory with eta != 0 needs a seed: without one the decode runs in the host loop, which has no x0")
         # eta != 0: the reference draws torch.randn_like(noise) per step (x :172, eps :150)
         if init is None:
             img = out
@@ -301,7 +360,8 @@ class _GaussianDiffusionBase:
         return img
 
     def decompress(self, context, shape=None, sample_steps=None, init=None, eta=0, clip_denoised=None, bitrate_scale=None,
-                   as_uint8=False, seed=None, gamma=None, sampler="ddim", spacing="index", samples=None, reduce=None, sample_chunk=None):
+                   as_uint8=False, seed=None, gamma=None, sampler="ddim", spacing="index", samples=None, reduce=None, sample_chunk=None,
+                   trajectory=None, trajectory_of="x0", trajectory_dtype="float32"):
         """Decode half of compress(): context pyramid (= context_fn(...)["output"]) -> image.  `context`
         may also be the transmitted q_latent tensor [B, C, H/16, W/16]: it then goes through
         `context_fn.decode` first (compress_modules.py:68-74; cdc_compression_amd.compressor on the GPU) -- with
@@ -317,9 +377,13 @@ class _GaussianDiffusionBase:
         samples: K seeded samples per image (needs a seed and gamma or eta != 0, excludes init); None is the single decode.
         reduce: None returns [B, K, 3, H, W] (uint8 with as_uint8); "mean" their pixel-wise mean [B, 3, H, W] (with as_uint8: its uint8
         form); "mean_var" (K >= 2, no as_uint8) the pair (mean, unbiased variance).  The moments are folded on the padded frame and
-        cropped once.  sample_chunk: samples per image per library call (default: the largest divisor of K with B * Kc <= 32)."""
+        cropped once.  sample_chunk: samples per image per library call (default: the largest divisor of K with B * Kc <= 32).
+        trajectory / trajectory_of / trajectory_dtype (cdc_compression_amd.trajectory): x0 and / or x_t of chosen steps, recorded in the
+        device loop -> (reconstruction, Trajectory), the slots [S, B, 3, H, W] cropped to the window as the reconstruction is; excludes
+        samples=, and eta != 0 needs a seed."""
         self._seed_args(seed, gamma, init)
         self._sampler_args(sampler, eta)
+        spec = self._trace_spec(trajectory, trajectory_of, trajectory_dtype, self._steps(sample_steps, spacing), eta, seed, samples)
         if samples is None and (reduce is not None or sample_chunk is not None):
             raise ValueError("reduce / sample_chunk belong to samples=K")
         K = None if samples is None else _samples.check_args(samples, seed, gamma, eta, init, reduce, as_uint8, sample_chunk)
@@ -354,10 +418,11 @@ class _GaussianDiffusionBase:
         if K is not None:
             return self._decompress_samples(context, all_seeds, K, (H, W), clip_denoised, eta, gamma, sampler, reduce, sample_chunk, as_uint8)
         rec = self._loop((B, 3, Hp, Wp), context, clip_denoised, frame.extend_init(h, init, B, H, W, Hp, Wp, dev), eta,
-                         seed, gamma, sampler)
+                         seed, gamma, sampler, spec, (H, W))
+        rec, traj = rec if spec is not None else (rec, None)
         if (Hp, Wp) != (H, W) or as_uint8:
             rec = frame.crop(h, rec, H, W, dev, as_uint8=as_uint8)
-        return rec
+        return rec if traj is None else (rec, traj)
 
     # ---- K samples per image (cdc_compression_amd.samples) --------------------------------------------------------------
     def _sample_chunk(self, context, seeds, k0, Kc, clip_denoised, eta, gamma, sampler):
@@ -465,21 +530,30 @@ class GaussianDiffusionX(_GaussianDiffusionBase):
         self.aux_loss_weight = aux_loss_weight      # (the reference builds its LPIPS-VGG network when this is > 0)
         self.lagrangian_beta = lagrangian
 
-    def p_sample_loop(self, shape, context, clip_denoised=False, init=None, eta=0, seed=None, gamma=None, sampler=None, spacing=None):
+    def p_sample_loop(self, shape, context, clip_denoised=False, init=None, eta=0, seed=None, gamma=None, sampler=None, spacing=None,
+                      trajectory=None, trajectory_of="x0", trajectory_dtype="float32", window=None):
+        """trajectory / trajectory_of / trajectory_dtype (cdc_compression_amd.trajectory): -> (image, Trajectory), the slots cropped
+        to `window` ((H, W) of the image inside the frame `shape`; None: the frame)."""
+        spec = self._trace_spec(trajectory, trajectory_of, trajectory_dtype, self.sample_steps, eta, seed)
         self._reschedule(sampler, spacing)
-        return self._loop(tuple(shape), context, clip_denoised, init, eta, seed, gamma, sampler)
+        return self._loop(tuple(shape), context, clip_denoised, init, eta, seed, gamma, sampler, spec, window)
 
-    def _frame_of(self, images, sample_steps=None, init=None, eta=0, seed=None, gamma=None, sampler="ddim", spacing="index"):
+    def _frame_of(self, images, sample_steps=None, init=None, eta=0, seed=None, gamma=None, sampler="ddim", spacing="index",
+                  trajectory=None, trajectory_of="x0", trajectory_dtype="float32"):
         self._seed_args(seed, gamma, init, frame.image_shape(images)[0])
         return self._compress_frame(images, sample_steps, init, eta,
-                                    lambda shape, ctx, i: self.p_sample_loop(shape, ctx, clip_denoised=True, init=i, eta=eta,
-                                                                             seed=seed, gamma=gamma),   # :223
-                                    sampler=sampler, spacing=spacing)
+                                    lambda shape, ctx, i, spec, win: self.p_sample_loop(shape, ctx, clip_denoised=True, init=i, eta=eta,
+                                                                                        seed=seed, gamma=gamma, trajectory=spec,
+                                                                                        window=win),   # :223
+                                    sampler=sampler, spacing=spacing, trace=(trajectory, trajectory_of, trajectory_dtype, seed))
 
     def compress(self, images, sample_steps=None, bpp_return_mean=True, init=None, eta=0, seed=None, gamma=None, sampler="ddim",
-                 spacing="index"):
-        rec, bpp, H, W = self._frame_of(images, sample_steps, init, eta, seed, gamma, sampler, spacing)
-        return self._window(rec, H, W), (bpp.mean() if bpp_return_mean else bpp)
+                 spacing="index", trajectory=None, trajectory_of="x0", trajectory_dtype="float32"):
+        """trajectory=: -> (reconstruction, bpp, Trajectory) (cdc_compression_amd.trajectory)."""
+        rec, bpp, H, W, traj = self._frame_of(images, sample_steps, init, eta, seed, gamma, sampler, spacing, trajectory, trajectory_of,
+                                              trajectory_dtype)
+        res = (self._window(rec, H, W), (bpp.mean() if bpp_return_mean else bpp))
+        return res if traj is None else res + (traj,)
 
 
     def compress_best_of(self, images, samples, metric="psnr", seed=None, gamma=None, eta=0, sample_steps=None, sampler="ddim",
@@ -507,24 +581,33 @@ class GaussianDiffusionEps(_GaussianDiffusionBase):
         self.aux_loss_weight = aux_loss_weight      # (the reference builds its LPIPS-VGG network when this is > 0)
         self.vbr = vbr
 
-    def p_sample_loop(self, shape, context, sample_mode, init=None, eta=0, seed=None, gamma=None, sampler=None, spacing=None):
+    def p_sample_loop(self, shape, context, sample_mode, init=None, eta=0, seed=None, gamma=None, sampler=None, spacing=None,
+                      trajectory=None, trajectory_of="x0", trajectory_dtype="float32", window=None):
+        """trajectory / trajectory_of / trajectory_dtype / window: as GaussianDiffusionX.p_sample_loop."""
+        spec = self._trace_spec(trajectory, trajectory_of, trajectory_dtype, self.sample_steps, eta, seed)
         if sample_mode != "ddim":
             raise NotImplementedError('sample_mode "ddpm" raises AttributeError in the reference '
                                       "(posterior_mean_coef1 undefined); only \"ddim\" is implemented")
         self._reschedule(sampler, spacing)
-        return self._loop(tuple(shape), context, self.clip_noise, init, eta, seed, gamma, sampler)
+        return self._loop(tuple(shape), context, self.clip_noise, init, eta, seed, gamma, sampler, spec, window)
 
     def _frame_of(self, images, sample_steps=None, bitrate_scale=None, sample_mode="ddpm", init=None, eta=0, seed=None, gamma=None,
-                  sampler="ddim", spacing="index"):
+                  sampler="ddim", spacing="index", trajectory=None, trajectory_of="x0", trajectory_dtype="float32"):
         self._seed_args(seed, gamma, init, frame.image_shape(images)[0])
         return self._compress_frame(images, sample_steps, init, eta,
-                                    lambda shape, ctx, i: self.p_sample_loop(shape, ctx, sample_mode, init=i, eta=eta, seed=seed,
-                                                                             gamma=gamma), bitrate_scale, sampler=sampler, spacing=spacing)
+                                    lambda shape, ctx, i, spec, win: self.p_sample_loop(shape, ctx, sample_mode, init=i, eta=eta, seed=seed,
+                                                                                        gamma=gamma, trajectory=spec, window=win),
+                                    bitrate_scale, sampler=sampler, spacing=spacing,
+                                    trace=(trajectory, trajectory_of, trajectory_dtype, seed))
 
     def compress(self, images, sample_steps=None, bitrate_scale=None, sample_mode="ddpm",
-                 bpp_return_mean=True, init=None, eta=0, seed=None, gamma=None, sampler="ddim", spacing="index"):
-        rec, bpp, H, W = self._frame_of(images, sample_steps, bitrate_scale, sample_mode, init, eta, seed, gamma, sampler, spacing)
-        return self._window(rec, H, W), (bpp.mean() if bpp_return_mean else bpp)
+                 bpp_return_mean=True, init=None, eta=0, seed=None, gamma=None, sampler="ddim", spacing="index",
+                 trajectory=None, trajectory_of="x0", trajectory_dtype="float32"):
+        """trajectory=: -> (reconstruction, bpp, Trajectory) (cdc_compression_amd.trajectory)."""
+        rec, bpp, H, W, traj = self._frame_of(images, sample_steps, bitrate_scale, sample_mode, init, eta, seed, gamma, sampler, spacing,
+                                              trajectory, trajectory_of, trajectory_dtype)
+        res = (self._window(rec, H, W), (bpp.mean() if bpp_return_mean else bpp))
+        return res if traj is None else res + (traj,)
 
     def compress_best_of(self, images, samples, metric="psnr", seed=None, gamma=None, eta=0, sample_steps=None, sampler="ddim",
                          spacing="index", sample_chunk=None, as_saved=True, bitrate_scale=None):

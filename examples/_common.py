@@ -25,7 +25,10 @@ def _shared_options():
                         parallel.sample_seeds(N + k, 1, K) with N = --device_seed (0 without it), each scored against the input on the
                         device; the best one is saved, and its scores, sample index and seed are printed -- decompress(..., seed=)
                         with that seed reproduces the saved picture.
-      --select METRIC   the score of --samples: "psnr" (default), "ms_ssim" or "lpips".  Without the two the output is unchanged."""
+      --select METRIC   the score of --samples: "psnr" (default), "ms_ssim" or "lpips".  Without the two the output is unchanged.
+      --trajectory N    progressive previews: the prediction x0 of every N-th executed step (and of the last), recorded inside the
+                        device loop as uint8 (compress(..., trajectory=N, trajectory_dtype="uint8")) and saved beside the image as
+                        name.stepNNNN.png, NNNN the sample index.  Not with --samples.  Without it the output is unchanged."""
     import argparse
     p = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
     p.add_argument("--device_seed", type=int, default=None)
@@ -34,9 +37,12 @@ def _shared_options():
     p.add_argument("--spacing", choices=("index", "logsnr"), default=None)
     p.add_argument("--samples", type=int, default=None)
     p.add_argument("--select", choices=("psnr", "ms_ssim", "lpips"), default=None)
+    p.add_argument("--trajectory", type=int, default=None)
     opts, sys.argv[1:] = p.parse_known_args(sys.argv[1:])
     if opts.select is not None and opts.samples is None:
         p.error("--select METRIC scores the candidates of --samples K")
+    if opts.trajectory is not None and (opts.trajectory < 1 or opts.samples is not None):
+        p.error("--trajectory N needs N >= 1 and excludes --samples")
     return opts
 
 
@@ -139,7 +145,11 @@ def run_folder(diffusion, config, rank, compress_kwargs):
                                                      std=config.gamma)).to(to_be_compressed.device)
             else:
                 init = torch.randn(shape, device=to_be_compressed.device) * config.gamma
-            if best is None:
+            traj = None
+            if best is None and SHARED.trajectory is not None:
+                compressed, bpp, traj = diffusion.compress(to_be_compressed, sample_steps=config.n_denoise_step, init=init,
+                                                           trajectory=SHARED.trajectory, trajectory_dtype="uint8", **compress_kwargs)
+            elif best is None:
                 compressed, bpp = diffusion.compress(
                     to_be_compressed,
                     sample_steps=config.n_denoise_step,
@@ -156,6 +166,10 @@ def run_folder(diffusion, config, rank, compress_kwargs):
             compressed = frame.crop(un._handle(), compressed, shape[2], shape[3], un.device_index, as_uint8=True)
             pathlib.Path(config.out_dir).mkdir(parents=True, exist_ok=True)
             save_image(compressed, os.path.join(config.out_dir, img))
+            if traj is not None:                              # name.stepNNNN.png: the x0 the update of sample index NNNN used
+                stem = os.path.splitext(img)[0]
+                for slot, i in enumerate(traj.steps):
+                    save_image(traj.x0[slot], os.path.join(config.out_dir, f"{stem}.step{i:04d}.png"))
             print("image:", img)
             print("bpp:", bpp)
             if SHARED.metrics:

@@ -246,6 +246,43 @@ int cdc_op_ddim_update(cdc_handle *h, const float *fx, const float *x, const flo
                        int pred_mode, int clip, const float *planes /* nullable */, const float *plane_bias /* nullable */, int KH,
                        int pad, int mem, void *stream);
 
+/* ---- decode trajectory: x0 and x_t of chosen steps, recorded inside the device loop (no reference counterpart: the reference's
+ * p_sample_loop carries a commented-out buffer.append every 50 steps) ----------------------------------------------------------------
+ * For sample index i (a decode runs i = steps-1 .. 0):
+ *   x0_i   the prediction the update of step i used: the sampler kernel's own x0 of that step's model output and input, after the clip
+ *          that applies to the image (CDC_CLIP_ALL / _NONE / _HALF).  In pred_mode "x" at i = steps-1 it is the network's direct estimate.
+ *   x_t_i  the state that update produced; x_t_0 is the decode's result.
+ * x0_i is evaluated by a tap kernel launched BEFORE the sampler kernel of its step (the loop updates x in place), from the same device
+ * functions, with fp contraction off: the very bits the update saw.  x_t_i is captured after the update.
+ *
+ * cdc_set_trace: the request, kept on the handle until changed; n = 0 (steps may be NULL) turns it off.  `steps`: n sample indices, host
+ *   array, copied.  `what`: a bit set of CDC_TRACE_X0, CDC_TRACE_XT (at least one) and CDC_TRACE_U8.  Without CDC_TRACE_U8 a slot is
+ *   float32 [B][C][H][W], the frame; with it a slot holds the as-saved bytes (what cdc_frame_crop writes as CDC_ELEM_U8) of the top-left
+ *   win_h x win_w window only, [B][C][win_h][win_w] -- the crop is fused into the tap -- where win_h = 0 / win_w = 0 stand for the frame's
+ *   H / W.  The indices are checked at the decode, against the schedule in force there: each inside [0, steps) and no index twice, the
+ *   window inside the frame; CDC_ERR_INVALID names the index.  Needs a U-Net handle.
+ * With a trace set, cdc_decode, cdc_decode_seeded and cdc_decode_solver record into a handle-owned buffer, slots in execution order
+ *   (descending index), and always run the eager loop: CDC_GRAPH is ignored.  The buffer's size is computed in 64 bits; more than 2^40
+ *   bytes, or a failed allocation, is CDC_ERR_NOMEM with the sizes in the message, before any launch.  The BF16X3 repetition of a range
+ *   fault records again from the start: the trace is that of the returned image.  cdc_decode_samples with a trace set is
+ *   CDC_ERR_INVALID.  Without a trace a decode launches exactly what it launched before.
+ * cdc_trace_info: of the last traced decode: the slot count (0: none yet), B, the slot's C / H / W (the window for uint8 slots) and
+ *   `what`.  Any pointer may be NULL.
+ * cdc_trace_read: slots slot0 .. slot0 + n_slots - 1 of `kind` (CDC_TRACE_X0 or CDC_TRACE_XT, one that was recorded) to out, n_slots
+ *   times B * C * H * W elements of 4 bytes or 1; follows `mem` / `stream` as cdc_decode does.  A decode on device pointers is queued on
+ *   its stream: read on that stream, or synchronise it first.
+ * cdc_op_trace_tap: the tap kernel alone on given tensors, in the style of cdc_op_ddim_update: the model output is fx or planes (+
+ *   plane_bias, KH, pad), x the step's input, i the sample index, with the handle's tables; no weights are needed.  elem_kind
+ *   CDC_ELEM_F32: out is [B][C][H][W] and may be x (in place); CDC_ELEM_U8: out is [B][C][win_h][win_w] bytes, 1 <= win_h <= H,
+ *   1 <= win_w <= W.  The traversal is chosen as for cdc_op_ddim_update; both give the same bits. */
+enum { CDC_TRACE_X0 = 1, CDC_TRACE_XT = 2, CDC_TRACE_U8 = 4 };
+int cdc_set_trace(cdc_handle *h, const int *steps /* nullable when n == 0 */, int n, int what, int win_h, int win_w);
+int cdc_trace_info(cdc_handle *h, int *n_slots, int *B, int *C, int *H, int *W, int *what);
+int cdc_trace_read(cdc_handle *h, int kind, int slot0, int n_slots, void *out, int mem, void *stream);
+int cdc_op_trace_tap(cdc_handle *h, const float *fx, const float *x, int i, void *out, int B, int C, int H, int W, int pred_mode,
+                     int clip, int elem_kind, int win_h, int win_w, const float *planes /* nullable */,
+                     const float *plane_bias /* nullable */, int KH, int pad, int mem, void *stream);
+
 /* ---- K seeded samples per image (no reference counterpart: the reference cannot ask for "sample k") -------------------------------
  * A seeded decode is a pure function of (stream, seed, gamma, eta, steps), so one stream has as many reconstructions as there are
  * seeds.  These entry points decode K of them per image through the batch programs and fold or select them on the device
