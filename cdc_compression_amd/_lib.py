@@ -119,6 +119,7 @@ def lib():
     L.cdc_simple_ctxdec_create.argtypes = [ctypes.POINTER(CtxdecConfig), _i, ctypes.POINTER(H)]
     L.cdc_simple_encoder_create.argtypes = [ctypes.POINTER(EncoderConfig), _i, ctypes.POINTER(H)]
     L.cdc_op_gdn.argtypes = [H, _vp, _vp, _vp, _vp, _i, _i, _i, _i]
+    L.cdc_op_gdn_workgroups.argtypes = [H, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]
     L.cdc_encoder_encode.argtypes = [H, _vp, _vp, _vp, _i, _i, _i, _i, _vp]
     L.cdc_hyperdec_create.argtypes = [ctypes.POINTER(HyperdecConfig), _i, ctypes.POINTER(H)]
     L.cdc_hyperdec_decode.argtypes = [H, _vp, _vp, _vp, _i, _i, _i, ctypes.c_float, _i, _vp]
@@ -201,6 +202,7 @@ EXPORTS = ["cdc_create", "cdc_destroy", "cdc_last_error", "cdc_version", "cdc_nu
            "cdc_padded_size", "cdc_frame_pad", "cdc_frame_crop", "cdc_entropy_set_image_scale", "cdc_entropy_encode_image",
            "cdc_entropy_peek_image_size", "cdc_decode_seeded", "cdc_randn", "cdc_randn_host", "cdc_philox4x32_10",
            "cdc_distortion", "cdc_lpips_create", "cdc_lpips", "cdc_simple_encoder_create", "cdc_simple_ctxdec_create", "cdc_op_gdn",
+           "cdc_op_gdn_workgroups",
            "cdc_set_solver", "cdc_decode_solver", "cdc_solver_step", "cdc_op_solver_update", "cdc_op_ddim_update",
            "cdc_repeat_images", "cdc_decode_samples", "cdc_sample_moments", "cdc_sample_select",
            "cdc_set_trace", "cdc_trace_info", "cdc_trace_read", "cdc_op_trace_tap"]

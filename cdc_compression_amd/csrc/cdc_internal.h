@@ -354,6 +354,8 @@ struct GdnArgs {
     int *fault;                       // range guard (ConvArgs::fault): set to 1 on a non-finite output (may be null)
 };
 bool gdn_supported(int C);
+int gdn_tiles(int HW);                   // 64-pixel tiles of an image
+int gdn_workgroups(int HW, int B);       // workgroups per image of gdn_launch's grid (each walks its tiles with that stride)
 hipError_t gdn_launch(const GdnArgs &a, int B, hipStream_t st);
 void gdn_reparam(const float *beta, const float *gamma, int C, float *beta_r, float *gamma_r);
 // column unfold for few-channel k x k convolutions: dst[kx * C + c][y][x] = src[c][y][x + kx - pad]

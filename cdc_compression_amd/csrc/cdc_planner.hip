@@ -1690,6 +1690,19 @@ int cdc_op_gdn(cdc_handle *h, const float *x, const float *beta, const float *ga
     return with_range_guard(h, [&] { return no_throw(h, [&] { return op_gdn_impl(h, x, beta, gamma, y, B, C, HW, inverse); }); });
 }
 
+int cdc_op_gdn_workgroups(cdc_handle *h, int B, int HW, int *per_image, int *tiles) {
+    if (!h) return CDC_ERR_INVALID;
+    int ndev = 0;                               // the rule reads the CU count of the handle's device; a host without one gets
+    if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) {     // device_cus()'s stand-in, so the rule is testable there
+        const int rc = op_ready(h);
+        if (rc) return rc;
+    }
+    if (B < 1 || HW < 1) return fail(h, CDC_ERR_INVALID, "cdc_op_gdn_workgroups: B = %d, HW = %d", B, HW);
+    if (per_image) *per_image = gdn_workgroups(HW, B);
+    if (tiles) *tiles = gdn_tiles(HW);
+    return CDC_OK;
+}
+
 int cdc_op_stress(cdc_handle *h, int repeats) {
     if (!h) return CDC_ERR_INVALID;
     if (repeats < 0) return fail(h, CDC_ERR_INVALID, "cdc_op_stress: repeats < 0");

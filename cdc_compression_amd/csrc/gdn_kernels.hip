@@ -87,12 +87,19 @@ __global__ void __launch_bounds__(64 * CB) gdn_kernel(const GdnArgs a) {
 
 bool gdn_supported(int C) { return C >= 16 && C <= 256 && (C % 16) == 0; }
 
+int gdn_tiles(int HW) { return ceil_div(HW, kGdnTile); }
+
+// The workgroups of one image.  gamma' is fetched once per workgroup: a few workgroups per CU, each walking its tiles with stride
+// gridDim.x.  CDC_GDN_WGS=n (development switch, read per launch: the tests switch it) forces min(tiles, n).
+int gdn_workgroups(int HW, int B) {
+    const int ntiles = gdn_tiles(HW);
+    if (const char *e = dev_env("CDC_GDN_WGS")) { const int n = atoi(e); if (n >= 1) return std::min(ntiles, n); }
+    return std::max(1, std::min(ntiles, ceil_div(4 * device_cus(), B)));
+}
+
 hipError_t gdn_launch(const GdnArgs &a, int B, hipStream_t st) {
     if (!gdn_supported(a.C) || B < 1 || a.HW < 1) return hipErrorInvalidValue;
-    const int ntiles = ceil_div(a.HW, kGdnTile);
-    // gamma' is fetched once per workgroup: a few workgroups per CU, each walking its tiles with stride gridDim.x
-    const int per_image = std::max(1, std::min(ntiles, ceil_div(4 * device_cus(), B)));
-    const dim3 grid((unsigned)per_image, (unsigned)B), block((unsigned)(4 * a.C));
+    const dim3 grid((unsigned)gdn_workgroups(a.HW, B), (unsigned)B), block((unsigned)(4 * a.C));
     const size_t lds = sizeof(float) * (size_t)a.C * kGdnLd;
 #define CDC_GDN_LAUNCH(CB)                                                                               \
     case CB: {                                                                                           \

@@ -109,3 +109,10 @@ class Ops:
         y = np.empty_like(x)
         _lib.check(self._h, _lib.lib().cdc_op_gdn(self._h, _p(x), _p(beta), _p(gamma), _p(y), B, C, H * W, int(bool(inverse))))
         return y
+
+    def gdn_workgroups(self, B, HW):
+        """(workgroups per image, 64-pixel tiles per image) of the grid `gdn` launches for B images of HW pixels: each workgroup walks
+        the tiles w, w + per_image, ...  Launches nothing (include/cdc_hip.h: cdc_op_gdn_workgroups)."""
+        per_image, tiles = ctypes.c_int(), ctypes.c_int()
+        _lib.check(self._h, _lib.lib().cdc_op_gdn_workgroups(self._h, int(B), int(HW), ctypes.byref(per_image), ctypes.byref(tiles)))
+        return per_image.value, tiles.value

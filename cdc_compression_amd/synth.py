@@ -46,6 +46,17 @@ def normal(name, shape, seed=0, std=1.0, mean=0.0):
     return z.astype(np.float32).reshape(shape)
 
 
+def uniform(name, shape, seed=0, lo=0.0, hi=1.0):
+    """U[lo, hi) float64 tensor, a pure function of (name, seed, element index): the top 53 bits of the same counter hash, times
+    2^-53 (exact), then one multiply and one add.  The caller casts."""
+    n = int(np.prod(shape)) if len(shape) else 1
+    base = np.uint64((_fnv1a(name) ^ (seed * 0xD6E8FEB86659FD93)) & _MASK)
+    with np.errstate(over="ignore"):
+        ctr = base + np.arange(n, dtype=np.uint64) * _GOLD
+    u = (_splitmix64(ctr) >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+    return (u * (float(hi) - float(lo)) + float(lo)).reshape(shape)
+
+
 def unet_state_dict(manifest, seed=0, final_gain=1.0):
     """Synthetic parameters for a Unet manifest [(name, shape), ...].
 

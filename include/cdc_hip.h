@@ -667,6 +667,11 @@ int cdc_op_chan_layernorm(cdc_handle *h, const float *x, const float *g, const f
  * as one fused pass on the fp32 matrix instructions.  C % 16 == 0 and 16 <= C <= 256, else CDC_ERR_UNSUPPORTED (nothing is launched).
  * Host pointers; honours cdc_op_stress. */
 int cdc_op_gdn(cdc_handle *h, const float *x, const float *beta, const float *gamma, float *y, int B, int C, int HW, int inverse);
+/* The grid cdc_op_gdn (and a GDN op of the compressor programs) launches for B images of HW pixels on the handle's device:
+ * *tiles = 64-pixel tiles of one image, *per_image = workgroups per image; each workgroup walks tiles w, w + per_image, ...  (the
+ * rule does not depend on C).  Test infrastructure: a test of the tile walk asserts per_image < tiles for the launch it checks.
+ * Either pointer may be NULL.  Launches nothing; on a host without a device it answers for 256 CUs. */
+int cdc_op_gdn_workgroups(cdc_handle *h, int B, int HW, int *per_image, int *tiles);
 /* Residual(PreNorm(LinearAttention)) (:10-16,69-77,117-139): y = to_out(attn(to_qkv(LN(x)))) + x. */
 int cdc_op_linear_attention(cdc_handle *h, const float *x, const float *norm_g,
                             const float *norm_b, const float *w_qkv, const float *w_out,
