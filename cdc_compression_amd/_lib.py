@@ -179,6 +179,9 @@ def lib():
     L.cdc_op_conv2d.argtypes = [H, _vp, _vp, _vp, _vp] + [_i] * 9 + [_vp, _vp, _i, _vp, _vp]
     L.cdc_op_conv_transpose2d.argtypes = [H, _vp, _vp, _vp, _vp] + [_i] * 5
     L.cdc_op_chan_layernorm.argtypes = [H, _vp, _vp, _vp, _vp, _i, _i, _i]
+    L.cdc_op_chan_layernorm_ex.argtypes = [H, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i]
+    L.cdc_op_ln_form.argtypes = [H, _i, _i, _i, _i, _i] + [ctypes.POINTER(_i)] * 4
+    L.cdc_op_sum_slices.argtypes = [H, _vp, _i, _vp, _i, ctypes.c_longlong]
     L.cdc_op_linear_attention.argtypes = [H] + [_vp] * 7 + [_i] * 4
     L.cdc_op_stress.argtypes = [H, _i]
     L.cdc_op_stress_result.argtypes = [H, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
@@ -202,7 +205,7 @@ EXPORTS = ["cdc_create", "cdc_destroy", "cdc_last_error", "cdc_version", "cdc_nu
            "cdc_padded_size", "cdc_frame_pad", "cdc_frame_crop", "cdc_entropy_set_image_scale", "cdc_entropy_encode_image",
            "cdc_entropy_peek_image_size", "cdc_decode_seeded", "cdc_randn", "cdc_randn_host", "cdc_philox4x32_10",
            "cdc_distortion", "cdc_lpips_create", "cdc_lpips", "cdc_simple_encoder_create", "cdc_simple_ctxdec_create", "cdc_op_gdn",
-           "cdc_op_gdn_workgroups",
+           "cdc_op_gdn_workgroups", "cdc_op_chan_layernorm_ex", "cdc_op_ln_form", "cdc_op_sum_slices",
            "cdc_set_solver", "cdc_decode_solver", "cdc_solver_step", "cdc_op_solver_update", "cdc_op_ddim_update",
            "cdc_repeat_images", "cdc_decode_samples", "cdc_sample_moments", "cdc_sample_select",
            "cdc_set_trace", "cdc_trace_info", "cdc_trace_read", "cdc_op_trace_tap"]

@@ -202,6 +202,11 @@ __global__ void __launch_bounds__(256) ln_kernel_sliced(const LnArgs a) {
 // an in-wave butterfly + 4 LDS values instead of CS LDS reads per thread.
 template <int COLS, int NP>
 __global__ void __launch_bounds__(256) ln_kernel_vec(const LnArgs a) {
+    // No multiply is fused with a following add here.  Left to the compiler, the instantiations fused different pairs (x - tot * inv_c
+    // with and without the rounded mean; some float4 components and not others): the pass behind a split-K convolution differed in
+    // its last bits from the same pass over the summed tensor, and a pixel's result depended on the float4 lane it sat in
+    // (tests/test_gpu_ln_edges.py: slices against their float32 sum, the pixel permutation).
+#pragma clang fp contract(off)
     constexpr int CS = 256 / COLS, NV = 8 * kLnCache / CS;
     __shared__ float4 red[2][4][COLS];
     const int b = a.img_major ? blockIdx.x : blockIdx.y, bx = a.img_major ? blockIdx.y : blockIdx.x, tid = threadIdx.x;
@@ -337,12 +342,8 @@ template <int COLS> static void ln_vec_launch(const LnArgs &a, dim3 grid, hipStr
 }
 constexpr int kLnVecMaxParts2 = 6;      // most slices ln_kernel_vec<2, NP> is instantiated for (other widths: 4)
 
-// The workgroup shape (pixel columns per workgroup, hence the order of the cross-slice channel reduction) is chosen from the RUN-TIME
-// batch B, so the last bits of a LayerNorm output may differ between batch sizes (the parity tests bound rows of a batch against
-// batch-1 calls at 5e-6).  Nothing with a bit-exactness contract across batch sizes contains a LayerNorm: hyper_dec -- the entropy
-// coder's model, include/cdc_hip.h -- is convolutions + LeakyReLU only.
-hipError_t ln_launch(const LnArgs &a, int B, hipStream_t st) {
-    if (a.nparts > 1 && a.C > 8 * kLnCache) return hipErrorInvalidValue;
+LnForm ln_form(const LnArgs &a, int B) {
+    LnForm f = {};
     if (a.C <= 8 * kLnCache && a.nparts >= 1 && a.nparts <= kLnVecMaxParts2 && (a.HW & 3) == 0 && (a.part_stride & 3) == 0 &&
         ((((uintptr_t)a.in) | ((uintptr_t)a.out) | ((uintptr_t)a.resid) | ((uintptr_t)a.stat_mean) | ((uintptr_t)a.stat_rstd)) & 15) == 0 &&
         !dev_env("CDC_NO_LN_VEC")) {
@@ -354,24 +355,48 @@ hipError_t ln_launch(const LnArgs &a, int B, hipStream_t st) {
         // same image.  Workgroups go to the XCDs round robin by linear id, and the eight L2s share nothing: with the image as the FAST grid
         // dimension (and B a multiple of 8) all column blocks of an image run on ONE XCD, so a line is fetched from the memory side once
         // instead of once per neighbour (round 6; CDC_LN_NO_IMG_MAJOR=1 brings the old order back for A/B).
-        LnArgs la = a;
-        la.img_major = (cols < 8 && B % 8 == 0 && a.HW > 4 * cols && !dev_env("CDC_LN_NO_IMG_MAJOR")) ? 1 : 0;
+        f.kind = 2; f.width = cols; f.np = a.nparts;
+        f.img_major = (cols < 8 && B % 8 == 0 && a.HW > 4 * cols && !dev_env("CDC_LN_NO_IMG_MAJOR")) ? 1 : 0;
         const unsigned nbx = (unsigned)ceil_div(a.HW, 4 * cols);
-        const dim3 grid = la.img_major ? dim3((unsigned)B, nbx) : dim3(nbx, (unsigned)B);
-        if (cols == 8) ln_vec_launch<8>(la, grid, st);
-        else if (cols == 4) ln_vec_launch<4>(la, grid, st);
-        else ln_vec_launch<2>(la, grid, st);
-        return hipGetLastError();
+        f.grid = f.img_major ? dim3((unsigned)B, nbx) : dim3(nbx, (unsigned)B);
+        return f;
     }
     if (a.C <= 8 * kLnCache) {
         static const int pl8_max = 64;
         // 8-pixel workgroups also wherever 32-pixel ones would leave most of the chip idle (small batches)
         static const int min_wgs = 256;    // (measured at batch 32: 16x16 maps are faster on 32-pixel workgroups, 128-byte rows)
         const bool pl8 = a.HW <= pl8_max || (long long)ceil_div(a.HW, 32) * B < min_wgs;
-        const dim3 grid((unsigned)ceil_div(a.HW, pl8 ? 8 : 32), (unsigned)B);
+        f.kind = 1; f.width = pl8 ? 8 : 32;
+        f.np = (a.nparts >= 1 && a.nparts <= 4) ? a.nparts : 0;     // 0: the run-time slice loop
+        f.grid = dim3((unsigned)ceil_div(a.HW, f.width), (unsigned)B);
+        return f;
+    }
+    f.kind = 0; f.width = a.HW >= 256 ? 256 : 64; f.np = 1;
+    f.grid = dim3((unsigned)ceil_div(a.HW, f.width), (unsigned)B);
+    return f;
+}
+
+// The workgroup shape (pixel columns per workgroup, hence the order of the cross-slice channel reduction) is chosen from the RUN-TIME
+// batch B, so the last bits of a LayerNorm output may differ between batch sizes (the parity tests bound rows of a batch against
+// batch-1 calls at 5e-6).  Nothing with a bit-exactness contract across batch sizes contains a LayerNorm: hyper_dec -- the entropy
+// coder's model, include/cdc_hip.h -- is convolutions + LeakyReLU only.
+// ln_form owns the choice (kernel, width, slice count, grid order, grid); ln_launch launches what it returns.
+hipError_t ln_launch(const LnArgs &a, int B, hipStream_t st) {
+    if (a.nparts > 1 && a.C > 8 * kLnCache) return hipErrorInvalidValue;
+    const LnForm f = ln_form(a, B);
+    const dim3 grid = f.grid;
+    if (f.kind == 2) {
+        LnArgs la = a;
+        la.img_major = f.img_major;
+        if (f.width == 8) ln_vec_launch<8>(la, grid, st);
+        else if (f.width == 4) ln_vec_launch<4>(la, grid, st);
+        else ln_vec_launch<2>(la, grid, st);
+        return hipGetLastError();
+    }
+    if (f.kind == 1) {
 #define CDC_LN_LAUNCH(PLV, NPV) hipLaunchKernelGGL((ln_kernel_sliced<PLV, NPV>), grid, dim3(256), 0, st, a)
-        if (pl8) {
-            switch (a.nparts) {
+        if (f.width == 8) {
+            switch (f.np) {
                 case 1: CDC_LN_LAUNCH(8, 1); break;
                 case 2: CDC_LN_LAUNCH(8, 2); break;
                 case 3: CDC_LN_LAUNCH(8, 3); break;
@@ -379,7 +404,7 @@ hipError_t ln_launch(const LnArgs &a, int B, hipStream_t st) {
                 default: CDC_LN_LAUNCH(8, 0); break;
             }
         } else {
-            switch (a.nparts) {                       // (48 cached values per thread and slice)
+            switch (f.np) {                           // (48 cached values per thread and slice)
                 case 1: CDC_LN_LAUNCH(32, 1); break;
                 case 2: CDC_LN_LAUNCH(32, 2); break;
                 case 3: CDC_LN_LAUNCH(32, 3); break;
@@ -390,9 +415,7 @@ hipError_t ln_launch(const LnArgs &a, int B, hipStream_t st) {
 #undef CDC_LN_LAUNCH
         return hipGetLastError();
     }
-    const int block = a.HW >= 256 ? 256 : 64;
-    dim3 grid((unsigned)ceil_div(a.HW, block), (unsigned)B);
-    hipLaunchKernelGGL(ln_kernel, grid, dim3(block), 0, st, a);
+    hipLaunchKernelGGL(ln_kernel, grid, dim3(f.width), 0, st, a);
     return hipGetLastError();
 }
 

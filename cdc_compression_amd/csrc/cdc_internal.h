@@ -151,6 +151,16 @@ struct LnArgs {
     int *fault;               // range guard (ConvArgs::fault): set to 1 when a pixel's statistics are not finite (may be null)
     int img_major;            // set by ln_launch: blockIdx.x = image, blockIdx.y = pixel-column block (see there)
 };
+// Which of the 25 LayerNorm instantiations a launch over B images runs (host; reads the pointers' alignment and the development
+// switches CDC_NO_LN_VEC, CDC_LN_VEC_COLS, CDC_LN_NO_IMG_MAJOR): ln_launch launches exactly this, cdc_op_ln_form reports it.
+struct LnForm {
+    int kind;                 // 0 ln_kernel, 1 ln_kernel_sliced, 2 ln_kernel_vec
+    int width;                // kind 0: threads per workgroup (64 / 256); 1: PL (8 / 32); 2: COLS (2 / 4 / 8)
+    int np;                   // template slice count (kind 1: 0 = the run-time loop)
+    int img_major;            // kind 2: blockIdx.x = image
+    dim3 grid;
+};
+LnForm ln_form(const LnArgs &a, int B);
 hipError_t ln_launch(const LnArgs &a, int B, hipStream_t st);
 
 struct TembLayer {            // one ResnetBlock.mlp (network_components.py:96-100)

@@ -1576,21 +1576,75 @@ static int op_conv_transpose2d_impl(cdc_handle *h, const float *x, const float *
     return sc.run(B, y, dy, ny);
 }
 
-static int op_chan_layernorm_impl(cdc_handle *h, const float *x, const float *g, const float *b, float *y, int B,
-                          int C, int HW) {
+// Everything Builder::ln can ask of the stand-alone LayerNorm (cdc_op_chan_layernorm_ex; cdc_op_chan_layernorm is the plain call of it).
+// One device buffer holds [y | stat_mean | stat_rstd] (what of them the call has), so the range guard and cdc_op_stress see all of it.
+// in_place: that buffer's y part is the kernel's input as well; a copy of x into it leads the program, so every repetition under
+// cdc_op_stress starts from x again.
+static const char *ln_ex_refusal(const float *x, const float *g, const float *b, int in_place, const float *y, const float *sm, const float *sr,
+                                 int B, int C, int HW, int nparts) {
+    if (!x) return "x is null";
+    if (B < 1 || C < 1 || HW < 1 || nparts < 1) return "B, C, HW and nparts start at 1";
+    if (!y && !sm && !sr) return "no output: y, stat_mean and stat_rstd are all null";
+    if (y && (!g || !b)) return "g and b are needed for y";
+    if (in_place && nparts > 1) return "in_place with split-K slices";
+    if (in_place && !y) return "in_place without y";
+    if (nparts > 1 && C > 384) return "split-K slices over more than 384 channels";
+    return nullptr;
+}
+
+static int op_chan_layernorm_impl(cdc_handle *h, const float *x, int nparts, const float *g, const float *b, int relu, const float *shift,
+                                  const float *resid, int in_place, float *y, float *stat_mean, float *stat_rstd, int B, int C, int HW) {
+    if (!h) return CDC_ERR_INVALID;
+    if (const char *why = ln_ex_refusal(x, g, b, in_place, y, stat_mean, stat_rstd, B, C, HW, nparts))
+        return fail(h, CDC_ERR_INVALID, "channel LayerNorm: %s", why);
     int rc = op_ready(h);
     if (rc) return rc;
-    if (!x || !g || !b || !y) return fail(h, CDC_ERR_INVALID, "null argument");
     OpScope sc(h);
     Builder bd{h, B, &sc.pool};
-    float *dx, *dg, *db;
-    if ((rc = sc.up(x, (size_t)B * C * HW, &dx))) return rc;
-    if ((rc = sc.up(g, C, &dg))) return rc;
-    if ((rc = sc.up(b, C, &db))) return rc;
-    float *dy = bd.dalloc((size_t)B * C * HW);
+    const size_t n = (size_t)B * C * HW, ns = (size_t)B * HW;
+    const bool stats = stat_mean || stat_rstd;
+    float *dx, *dg = nullptr, *db = nullptr, *ds = nullptr, *dr = nullptr;
+    if ((rc = sc.up(x, n * nparts, &dx))) return rc;
+    if (y && (rc = sc.up(g, C, &dg))) return rc;
+    if (y && (rc = sc.up(b, C, &db))) return rc;
+    if (y && shift && (rc = sc.up(shift, (size_t)B * C, &ds))) return rc;
+    if (y && resid && (rc = sc.up(resid, n, &dr))) return rc;
+    h->shift_bs = C;
+    const size_t ny = y ? n : 0, total = ny + (stats ? 2 * ns : 0);
+    float *dout = bd.dalloc(total);
     if (bd.rc) return bd.rc;
-    bd.ln(dx, dy, C, HW, dg, db, 0, nullptr, nullptr, nullptr, nullptr);
-    return sc.run(B, y, dy, (size_t)B * C * HW);
+    float *dy = y ? dout : nullptr, *dsm = stats ? dout + ny : nullptr, *dsr = stats ? dout + ny + ns : nullptr;
+    if (in_place) {
+        bd.copy(dx, (long long)C * HW, dy, (long long)C * HW, (long long)C * HW);
+        bd.ln(dy, dy, C, HW, dg, db, relu, ds, dr, dsm, dsr);
+    } else {
+        bd.ln(dx, dy, C, HW, dg, db, relu, ds, dr, dsm, dsr, nparts);
+    }
+    if (bd.rc) return bd.rc;
+    if (!stats) return sc.run(B, y, dout, total);
+    std::vector<float> host(total);
+    if ((rc = sc.run(B, host.data(), dout, total))) return rc;
+    if (y) memcpy(y, host.data(), ny * sizeof(float));
+    if (stat_mean) memcpy(stat_mean, host.data() + ny, ns * sizeof(float));
+    if (stat_rstd) memcpy(stat_rstd, host.data() + ny + ns, ns * sizeof(float));
+    return CDC_OK;
+}
+
+// The split-K sum pass alone: the CopyArgs op Builder::conv emits behind a sliced convolution with a linear epilogue.
+static int op_sum_slices_impl(cdc_handle *h, const float *x, int parts, float *y, int B, long long n) {
+    if (!h) return CDC_ERR_INVALID;
+    if (!x || !y || parts < 1 || B < 1 || n < 1) return fail(h, CDC_ERR_INVALID, "cdc_op_sum_slices: null/invalid argument");
+    int rc = op_ready(h);
+    if (rc) return rc;
+    OpScope sc(h);
+    Builder bd{h, B, &sc.pool};
+    float *dx;
+    if ((rc = sc.up(x, (size_t)parts * B * n, &dx))) return rc;
+    float *dy = bd.dalloc((size_t)B * n);
+    if (bd.rc) return bd.rc;
+    bd.emit(Op(PC_SMALL, CopyArgs{dx, n, dy, n, n, parts, (long long)B * n}, 0, 4.0 * B * n * (parts + 1)));
+    if (bd.rc) return bd.rc;
+    return sc.run(B, y, dy, (size_t)B * n);
 }
 
 static int op_linear_attention_impl(cdc_handle *h, const float *x, const float *norm_g, const float *norm_b,
@@ -1654,7 +1708,33 @@ int cdc_op_conv_transpose2d(cdc_handle *h, const float *x, const float *w, const
 
 int cdc_op_chan_layernorm(cdc_handle *h, const float *x, const float *g, const float *b, float *y, int B,
                           int C, int HW) {
-    return with_range_guard(h, [&] { return op_chan_layernorm_impl(h, x, g, b, y, B, C, HW); });
+    return with_range_guard(h, [&] { return op_chan_layernorm_impl(h, x, 1, g, b, 0, nullptr, nullptr, 0, y, nullptr, nullptr, B, C, HW); });
+}
+
+int cdc_op_chan_layernorm_ex(cdc_handle *h, const float *x, int nparts, const float *g, const float *b, int relu, const float *shift,
+                             const float *resid, int in_place, float *y, float *stat_mean, float *stat_rstd, int B, int C, int HW) {
+    return with_range_guard(h, [&] {
+        return no_throw(h, [&] { return op_chan_layernorm_impl(h, x, nparts, g, b, relu, shift, resid, in_place, y, stat_mean, stat_rstd, B, C, HW); });
+    });
+}
+
+int cdc_op_sum_slices(cdc_handle *h, const float *x, int parts, float *y, int B, long long n) {
+    return with_range_guard(h, [&] { return no_throw(h, [&] { return op_sum_slices_impl(h, x, parts, y, B, n); }); });
+}
+
+int cdc_op_ln_form(cdc_handle *h, int B, int C, int HW, int nparts, int aligned16, int *kind, int *width, int *np, int *img_major) {
+    if (!h) return CDC_ERR_INVALID;
+    if (B < 1 || C < 1 || HW < 1 || nparts < 1) return fail(h, CDC_ERR_INVALID, "cdc_op_ln_form: B = %d, C = %d, HW = %d, nparts = %d", B, C, HW, nparts);
+    if (nparts > 1 && C > 384) return fail(h, CDC_ERR_INVALID, "cdc_op_ln_form: %d split-K slices over %d > 384 channels", nparts, C);
+    LnArgs a = {};
+    a.C = C; a.HW = HW; a.nparts = nparts; a.part_stride = (long long)B * C * HW;
+    a.in = reinterpret_cast<const float *>((uintptr_t)(aligned16 ? 16 : 4));      // (only the address bits are read)
+    const LnForm f = ln_form(a, B);
+    if (kind) *kind = f.kind;
+    if (width) *width = f.width;
+    if (np) *np = f.np;
+    if (img_major) *img_major = f.img_major;
+    return CDC_OK;
 }
 
 int cdc_op_linear_attention(cdc_handle *h, const float *x, const float *norm_g, const float *norm_b,

@@ -90,6 +90,40 @@ class Ops:
                                                              H * W))
         return y
 
+    def chan_layernorm_ex(self, x, g=None, b=None, relu=False, shift=None, resid=None, in_place=False, want_y=True, want_stats=False):
+        """The stand-alone LayerNorm with everything a program asks of it (include/cdc_hip.h: cdc_op_chan_layernorm_ex).
+        x [B, C, H, W], or [K, B, C, H, W]: K split-K slices summed on load.  -> y, (mean, rstd) [B, H, W] or (y, mean, rstd):
+        want_y=False is the statistics-only pass over x; with y the statistics are those of the final values."""
+        x = _c(x)
+        K = x.shape[0] if x.ndim == 5 else 1
+        B, C, H, W = x.shape[-4:]
+        g, b, shift, resid = (None if a is None else _c(a).reshape(-1) for a in (g, b, shift, resid))
+        y = np.empty((B, C, H, W), np.float32) if want_y else None
+        want_stats = want_stats or not want_y
+        sm, sr = (np.empty((B, H, W), np.float32), np.empty((B, H, W), np.float32)) if want_stats else (None, None)
+        _lib.check(self._h, _lib.lib().cdc_op_chan_layernorm_ex(self._h, _p(x), K, _p(g), _p(b), int(bool(relu)), _p(shift), _p(resid),
+                                                                int(bool(in_place)), _p(y), _p(sm), _p(sr), B, C, H * W))
+        if not want_y:
+            return sm, sr
+        return (y, sm, sr) if want_stats else y
+
+    def ln_form(self, B, C, HW, nparts=1, aligned16=True):
+        """(kind, width, np, img_major) of the LayerNorm launch over B images of C channels and HW pixels with `nparts` slices: kind 0
+        ln_kernel (width = threads per workgroup), 1 ln_kernel_sliced (width = PL), 2 ln_kernel_vec (width = COLS); np 0 = the
+        run-time slice loop.  Launches nothing (include/cdc_hip.h: cdc_op_ln_form)."""
+        v = [ctypes.c_int() for _ in range(4)]
+        _lib.check(self._h, _lib.lib().cdc_op_ln_form(self._h, int(B), int(C), int(HW), int(nparts), int(bool(aligned16)),
+                                                      *[ctypes.byref(a) for a in v]))
+        return tuple(a.value for a in v)
+
+    def sum_slices(self, x):
+        """x [parts, B, n] -> [B, n]: the split-K sum pass (slice order), alone (include/cdc_hip.h: cdc_op_sum_slices)."""
+        x = _c(x)
+        parts, B, n = x.shape
+        y = np.empty((B, n), np.float32)
+        _lib.check(self._h, _lib.lib().cdc_op_sum_slices(self._h, _p(x), parts, _p(y), B, n))
+        return y
+
     def linear_attention(self, x, norm_g, norm_b, w_qkv, w_out, b_out):
         x, norm_g, norm_b, w_qkv, w_out, b_out = map(_c, (x, norm_g, norm_b, w_qkv, w_out, b_out))
         B, C, H, W = x.shape

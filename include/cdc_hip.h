@@ -661,6 +661,26 @@ int cdc_op_conv_transpose2d(cdc_handle *h, const float *x, const float *w, const
 /* LayerNorm.forward (:56-66). */
 int cdc_op_chan_layernorm(cdc_handle *h, const float *x, const float *g, const float *b, float *y,
                           int B, int C, int HW);
+/* The same pass with everything a program asks of it (test infrastructure of the few-pixel levels):
+ *   x [nparts][B][C][HW]: nparts split-K partial sums, summed on load in slice order (nparts = 1: the tensor itself);
+ *   v = (x - mean) / sqrt(var + 1e-5) * g[c] + b[c]  (biased variance over the channels of a pixel), relu: max(v, 0),
+ *   + shift[b][c] (nullable), + resid[b][c][p] (nullable);
+ *   y [B][C][HW], or NULL: statistics only -- stat_mean / stat_rstd [B][HW] then hold the mean and 1 / sqrt(var + 1e-5) of x;
+ *   with y they hold those of the FINAL values (either may be NULL);  in_place: the kernel's output buffer is its input buffer.
+ * Refused with CDC_ERR_INVALID before anything is launched: x NULL; y and both statistics NULL; g or b NULL with y; in_place with
+ * nparts > 1 or without y; C > 384 with nparts > 1; B, C, HW or nparts < 1.  Host pointers; honours cdc_op_stress and the range
+ * guard over every output of the call (stat_mean and stat_rstd when y is NULL). */
+int cdc_op_chan_layernorm_ex(cdc_handle *h, const float *x, int nparts, const float *g, const float *b, int relu, const float *shift,
+                             const float *resid, int in_place, float *y, float *stat_mean, float *stat_rstd, int B, int C, int HW);
+/* Which LayerNorm kernel a launch over B images of C channels and HW pixels with nparts slices runs, on buffers that are 16-byte
+ * aligned (aligned16) or not: *kind 0 ln_kernel, 1 ln_kernel_sliced, 2 ln_kernel_vec; *width its threads per workgroup (64 / 256),
+ * pixels per workgroup PL (8 / 32) or float4 columns COLS (2 / 4 / 8); *np the compiled slice count (0: the run-time loop);
+ * *img_major whether the image is the fast grid dimension.  Any pointer may be NULL.  Launches nothing and needs no device.
+ * Test infrastructure: a test asserts the form it names before it runs it. */
+int cdc_op_ln_form(cdc_handle *h, int B, int C, int HW, int nparts, int aligned16, int *kind, int *width, int *np, int *img_major);
+/* y [B][n] = x[0] + x[1] + ... over x [parts][B][n] in slice order: the sum pass behind a split-K convolution with a linear
+ * epilogue, alone.  Host pointers; honours cdc_op_stress. */
+int cdc_op_sum_slices(cdc_handle *h, const float *x, int parts, float *y, int B, long long n);
 /* GDN1.forward (epsilonparam/modules/network_components.py:381-412) over x [B][C][HW] with the RAW parameters beta [C], gamma [C][C]:
  *   beta' = max(beta, (1e-6 + 2^-36)^0.5)^2 - 2^-36,  gamma' = max(gamma, 2^-18)^2 - 2^-36          (float32, one rounding per operation)
  *   norm[b][i][p] = beta'[i] + sum_j gamma'[i][j] |x[b][j][p]|;   y = x / norm, or x * norm when `inverse`   (no square, no root)
