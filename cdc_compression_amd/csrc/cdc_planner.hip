@@ -154,6 +154,12 @@ struct Builder {
         if (want_twin && pf_site(site, H, W)) add_twin(a.p, C, H, W);
         return a;
     }
+    // the program's input tensor (h->in_x: what the entry points copy the caller's images / latents into)
+    Act input(int C, int H, int W) {
+        Act x = new_act(C, H, W, false);
+        h->in_x = x.p;
+        return x;
+    }
 
     struct ConvOpts {
         const float *ln_g = nullptr, *ln_b = nullptr;  // fused LN after bias
@@ -180,9 +186,28 @@ struct Builder {
         // a linear epilogue: bias and residual at most (no LayerNorm, activation, shift, statistics, hoisted partial sums, res_conv)
         bool linear_epilogue() const { return !ln_g && !relu && !shift && !stat_mean && !pre_add && !res3_w; }
     };
-    int last_ksplit = 1;                               // slices the last conv() call really used
-    bool last_pf_only = false;                         // the last conv() call wrote its result as planes only (no fp32 copy exists)
-    const float *next_res3_w = nullptr, *next_res3_x = nullptr; long long next_res3_bs = 0;   // for the next block()
+    // ---- tensor views: what a layer reads and writes.  From an Act, two Acts (a channel concat) or raw (a channel slice, scratch, an upload)
+    struct In {
+        const float *p0 = nullptr, *p1 = nullptr;      // fp32 sources; p1: the second half of a concat, or null
+        int C0 = 0, H = 0, W = 0;                      // C0: channels of p0 (read only where there is a p1)
+        long long bs0 = 0, bs1 = 0;
+        In(const float *p, int C, long long bs, int H_, int W_) : p0(p), C0(C), H(H_), W(W_), bs0(bs) {}
+        In(const Act &a) : In(a.p, a.C, a.bs(), a.H, a.W) {}
+        In(const Act &a, const Act &b) : In(a) { p1 = b.p; bs1 = b.bs(); }
+        int c0() const { return p1 ? C0 : 0; }         // the seam of a concat (0: one source), as the plans ask for it
+        int c0(const ConvW &w) const { return p1 ? C0 : w.Cin; }   // ... as the argument blocks do
+    };
+    struct Out {
+        float *p = nullptr; long long bs = 0;
+        Out(const Act &a) : p(a.p), bs(a.bs()) {}
+        Out(float *p_, long long bs_) : p(p_), bs(bs_) {}
+    };
+    // what conv() / block() did; false in a boolean context: nothing was emitted, the caller takes its other form
+    struct Planned {
+        bool planned; int ksplit; bool planes_only;    // K slices really used; the result exists as planes only (no fp32 copy)
+        Planned(bool planned_ = false, int ksplit_ = 1, bool planes_only_ = false) : planned(planned_), ksplit(ksplit_), planes_only(planes_only_) {}
+        explicit operator bool() const { return planned; }
+    };
     static bool debug_plan() { return getenv("CDC_DEBUG_PLAN") != nullptr; }   // (read per call: a caller may switch it)
 
     // ---- the forms of the plane-operand kernels (conv_pf_kernel / conv_pf3_kernel / conv_pw_kernel): the weight and geometry
@@ -313,28 +338,34 @@ struct Builder {
         a.res3_w = o.res3_w; a.res3_x = o.res3_x; a.res3_bs = o.res3_bs;
         a.fault = fault_flag();
     }
-    // the end of a single-launch convolution: its cost for the per-op table, what the caller reads back, the op
-    template <class T> bool finish(int prof, const T &payload, double flops, double bytes, bool pf_only) {
-        last_ksplit = 1;
-        last_pf_only = pf_only;
+    // the end of a single-launch convolution: its cost for the per-op table, the op, what the caller gets back
+    template <class T> Planned finish(int prof, const T &payload, double flops, double bytes, bool planes_only) {
         emit(Op(prof, payload, flops, bytes));
-        return true;
+        return Planned(true, 1, planes_only);
+    }
+    // What conv_pf_kernel's forms and conv_pw_kernel fill alike: weights and scale, channel counts, output addressing and, where the form
+    // can write planes (`can_emit`), the output's twin -- INSTEAD of the fp32 copy with no_f32 (no twin: the fp32 copy holds the result).
+    void pf_common(PfArgs &a, const ConvW &w, Out out, int Ho, int Wo, const ConvOpts &o, bool can_emit = true) {
+        a.w = w.wsh; a.acc_scale = w.wscale_inv;
+        a.nchunk = w.Cin / 16; a.COP = w.COP; a.Cout = w.Cout;
+        out_geometry(a, w, Ho, Wo);
+        a.out = out.p; a.out_bs = out.bs;
+        if (o.emit_pf && can_emit && bind_out_pf(a, w, out.p, out.bs, Ho, Wo) && o.no_f32) a.out = nullptr;
     }
 
     // Plans the convolution on conv_pf_kernel when every source has a valid PF twin and the layer has one of its forms.
-    bool try_pf(const ConvW &w, const float *s0, int C0, const float *s1, int H, int W, float *out, long long out_bs,
-                const ConvOpts &o, bool need_all, int prof) {
-        if (!pf_on() || o.pre_mean || o.w_bs || o.wsp_bs || o.max_ksplit > 1) return false;
+    Planned try_pf(const ConvW &w, In in, Out out, const ConvOpts &o, bool need_all, int prof) {
+        if (!pf_on() || o.uf_c || o.pre_mean || o.w_bs || o.wsp_bs || o.max_ksplit > 1) return false;
         PfShape ps;
-        const int c0 = s1 ? C0 : 0;
+        const int c0 = in.c0(), H = in.H, W = in.W;
         if (!(pf_form(w, c0, H, W, need_all, &ps) || (pf_s2_form(w, c0, H, W, need_all, &ps) && !o.pre_add && !o.res3_w) ||
               pf_tz_form(w, c0, H, W, need_all, &ps) || (pf_17_form(w, c0, H, W, need_all, &ps) && !o.ln_g && !o.emit_pf)))
             return false;
-        if (s1 && dev_env("CDC_TEST_JOIN_MISS")) return false;   // test hook: the joins miss the plane kernels AFTER their halves were made planes-only (ensure_f32)
-        PfTwin *t0 = twin(s0), *t1 = s1 ? twin(s1) : nullptr;
-        if (!t0 || !t0->valid || (s1 && (!t1 || !t1->valid))) return false;
+        if (in.p1 && dev_env("CDC_TEST_JOIN_MISS")) return false;   // test hook: the joins miss the plane kernels AFTER their halves were made planes-only (ensure_f32)
+        PfTwin *t0 = twin(in.p0), *t1 = in.p1 ? twin(in.p1) : nullptr;
+        if (!t0 || !t0->valid || (in.p1 && (!t1 || !t1->valid))) return false;
         if (t0->H != H || t0->W != W || (t1 && (t1->H != H || t1->W != W))) return false;
-        if (s1 ? (t0->C != C0 || t0->C + t1->C != w.Cin) : t0->C != w.Cin) return false;
+        if (in.p1 ? (t0->C != in.C0 || t0->C + t1->C != w.Cin) : t0->C != w.Cin) return false;
         PfPlan plan;
         if (!pf_make_plan(ps, &plan)) return false;
         const int Ho = ps.Ho, Wo = ps.Wo;
@@ -344,14 +375,10 @@ struct Builder {
         memset(&a, 0, sizeof a);
         a.src0 = t0->p; a.src0_bs = t0->bs();
         if (t1) { a.src1 = t1->p; a.src1_bs = t1->bs(); }
-        a.C0 = s1 ? C0 : w.Cin; a.Cin = w.Cin; a.H = H; a.W = W;
-        a.w = w.wsh; a.w_zs = w.wsp_zs / 8;            // planes of 8 halfs = one unit
+        a.C0 = in.c0(w); a.Cin = w.Cin; a.H = H; a.W = W;
+        a.w_zs = w.wsp_zs / 8;                         // planes of 8 halfs = one unit
         a.KH = w.KH; a.KW = w.KW; a.nz = w.nz; a.stride = w.stride; a.tz = ps.tz;
-        a.nchunk = w.Cin / 16; a.COP = w.COP; a.Cout = w.Cout;
-        a.acc_scale = w.wscale_inv;
-        out_geometry(a, w, Ho, Wo);
-        a.out = out; a.out_bs = out_bs;
-        if (o.emit_pf && bind_out_pf(a, w, out, out_bs, Ho, Wo) && o.no_f32) a.out = nullptr;   // (no twin: the fp32 copy holds the result)
+        pf_common(a, w, out, Ho, Wo, o);
         epilogue(a, w, o);
         if (o.resid1) {         // residual over a channel concatenation: every wave's channel part inside one source (64 / 96 / 128-channel parts)
             if (!o.resid || o.resid_c0 <= 0 || o.resid_c0 >= w.Cout || (o.resid_c0 % 64) || (o.resid_c0 % (plan.MB * 32))) return false;
@@ -386,10 +413,10 @@ struct Builder {
     // The first layer (7x1 over the kx-unfolded 3-channel image, ConvOpts::uf_c) on conv_pf_kernel's UF form: the kernel builds its patch
     // buffers from the image itself, everything else (weight ring, tap loop, epilogue with hoisted partial sums, LayerNorm, planes out)
     // is the plane-operand kernel.
-    bool try_pf_uf(const ConvW &w, const float *s0, long long bs0, int H, int W, float *out, long long out_bs, const ConvOpts &o,
-                   bool need_all, int prof) {
+    Planned try_pf_uf(const ConvW &w, In in, Out out, const ConvOpts &o, bool need_all, int prof) {
         PfShape ps;
-        if (!pf_on() || o.uf_c != 3 || o.uf_pad != 3 || !pf_uf_form(w, H, W, need_all, &ps)) return false;
+        const int H = in.H, W = in.W;
+        if (!pf_on() || in.p1 || o.uf_c != 3 || o.uf_pad != 3 || !pf_uf_form(w, H, W, need_all, &ps)) return false;
         if (o.pre_mean || o.w_bs || o.wsp_bs || o.max_ksplit > 1 || o.resid || o.res3_w || o.stat_mean) return false;
         PfPlan plan;
         if (!pf_make_plan(ps, &plan)) return false;
@@ -397,16 +424,13 @@ struct Builder {
         op.plan = plan; op.nz = 1;
         PfArgs &a = op.a;
         memset(&a, 0, sizeof a);
-        a.x0 = s0; a.x0_bs = bs0;
+        a.x0 = in.p0; a.x0_bs = in.bs0;
         a.C0 = a.Cin = 32; a.H = H; a.W = W;
-        a.w = w.wsh; a.w_zs = w.wsp_zs / 8;
+        a.w_zs = w.wsp_zs / 8;
         a.KH = 7; a.KW = 1; a.nz = 1;
-        a.nchunk = 2; a.COP = w.COP; a.Cout = w.Cout;
-        a.acc_scale = w.wscale_inv;
-        out_geometry(a, w, H, W);
-        a.out = out; a.out_bs = out_bs;
-        if (o.emit_pf && bind_out_pf(a, w, out, out_bs, H, W) && o.no_f32) a.out = nullptr;
-        const float *c4 = o.pre_add && cur != &h->pre_ops ? pre_add_c4(o.pre_add, w.Cout, H, W, out_bs) : nullptr;
+        pf_common(a, w, out, H, W, o);
+        a.nchunk = 2;                                   // (the unfolded channels padded to 32, not w.Cin / 16)
+        const float *c4 = o.pre_add && cur != &h->pre_ops ? pre_add_c4(o.pre_add, w.Cout, H, W, out.bs) : nullptr;
         epilogue(a, w, o);
         if (c4) { a.pre_add = c4; a.pre_c4 = 1; }
         const double px = (double)B * H * W;
@@ -415,16 +439,16 @@ struct Builder {
 
     // Pointwise convolutions at the >= 32-pixel-wide levels on conv_pw_kernel (fp16 arithmetic): activations staged
     // per wave straight from the fp32 sources, PreNorm folded as (x - mean) on load / rstd in the epilogue.
-    bool try_pw(const ConvW &w, const float *s0, int C0, long long bs0, const float *s1, long long bs1, int H, int W,
-                float *out, long long out_bs, const ConvOpts &o, bool need_all, int prof) {
+    Planned try_pw(const ConvW &w, In in, Out out, const ConvOpts &o, bool need_all, int prof) {
         PfShape ps;
-        if (h->arith != 1 || dev_env("CDC_NO_PW") || !pw_form(w, s1 ? C0 : 0, H, W, &ps)) return false;
-        if (need_all || o.ln_g || o.stat_mean || o.res3_w || o.pf_only) return false;
+        const int H = in.H, W = in.W;
+        if (h->arith != 1 || dev_env("CDC_NO_PW") || !pw_form(w, in.c0(), H, W, &ps)) return false;
+        if (need_all || o.ln_g || o.stat_mean || o.res3_w || o.pf_only || o.uf_c) return false;
         if (o.pre_mean && o.pre_mode != 2) return false;
         if (o.w_bs && !o.wsp_bs) return false;              // per-image weights without planes
         PfPlan plan;
         if (!pw_make_plan(ps, &plan)) return false;
-        if (plan.lin && (o.shift || o.wsp_bs || (long long)w.Cout * H * W != out_bs)) return false;   // tiles span images
+        if (plan.lin && (o.shift || o.wsp_bs || (long long)w.Cout * H * W != out.bs)) return false;   // tiles span images
         if (debug_plan())
             fprintf(stderr, "[plan] conv1x1 PW Cin=%4d Cout=%4d out=%3dx%-3d %s%s| MB=%d NPW=%d WM=%d WP=%d groups=%d R=%d wgs=%d lds=%zu\n", w.Cin, w.Cout,
                     H, W, o.pre_mean ? "pre2 " : "", o.wsp_bs ? "per-image " : "", plan.MB, plan.NPW, plan.WM, plan.WP, plan.groups, plan.ring,
@@ -433,17 +457,12 @@ struct Builder {
         op.plan = plan;
         PfArgs &a = op.a;
         memset(&a, 0, sizeof a);
-        a.x0 = s0; a.x0_bs = bs0; a.x1 = s1; a.x1_bs = bs1;
-        a.C0 = s1 ? C0 : w.Cin; a.Cin = w.Cin; a.H = H; a.W = W;
+        a.x0 = in.p0; a.x0_bs = in.bs0; a.x1 = in.p1; a.x1_bs = in.bs1;
+        a.C0 = in.c0(w); a.Cin = w.Cin; a.H = H; a.W = W;
         a.pre_mean = o.pre_mean; a.pre_rstd = o.pre_mean ? o.pre_rstd : nullptr;
-        a.w = w.wsh; a.w_bs = o.wsp_bs / 8;             // units of 8 halfs
+        a.w_bs = o.wsp_bs / 8;                          // units of 8 halfs
         a.KH = 1; a.KW = 1; a.nz = 1;
-        a.nchunk = w.Cin / 16; a.COP = w.COP; a.Cout = w.Cout;
-        a.acc_scale = w.wscale_inv;
-        out_geometry(a, w, H, W);
-        a.out = out; a.out_bs = out_bs;
-        // (no_f32: the planes are the only copy, their reader is a plane-operand kernel)
-        if (o.emit_pf && !plan.lin && (w.Cout % 32) == 0 && bind_out_pf(a, w, out, out_bs, H, W) && o.no_f32) a.out = nullptr;
+        pf_common(a, w, out, H, W, o, !plan.lin && (w.Cout % 32) == 0);
         epilogue(a, w, o);
         const double px = (double)B * H * W;
         return finish(prof, op, 2.0 * px * w.Cout * w.Cin, 4.0 * ((double)B * w.Cin * H * W + px * w.Cout), a.out == nullptr);
@@ -459,21 +478,21 @@ struct Builder {
         if (w.stride == 2 && ((H & 1) || (W & 1) || two_src)) return false;
         return ws_make_plan(w.Cin, two_src ? C0 : w.Cin, w.Cout, H / w.stride, W / w.stride, pb(), w.stride, plan);
     }
-    bool try_ws(const ConvW &w, const float *s0, int C0, long long bs0, const float *s1, long long bs1, int H, int W, float *raw,
-                long long raw_bs, int prof, const float *pre_add = nullptr) {
+    Planned try_ws(const ConvW &w, In in, Out raw, int prof, const float *pre_add = nullptr) {
         WsConvOp op;
-        if (rc || !ws_would_plan(w, C0, s1 != nullptr, H, W, &op.plan)) return false;
-        if (!ensure_f32(s0, bs0) || (s1 && !ensure_f32(s1, bs1))) return false;
+        const int H = in.H, W = in.W;
+        if (rc || !ws_would_plan(w, in.C0, in.p1 != nullptr, H, W, &op.plan)) return false;
+        if (!ensure_f32(in.p0, in.bs0) || (in.p1 && !ensure_f32(in.p1, in.bs1))) return false;
         const int Ho = H / w.stride, Wo = W / w.stride;
-        if (raw_bs != (long long)w.Cout * Ho * Wo) return false;
+        if (raw.bs != (long long)w.Cout * Ho * Wo) return false;
         WsArgs &a = op.a;
         memset(&a, 0, sizeof a);
-        a.x0 = s0; a.x0_bs = bs0; a.x1 = s1; a.x1_bs = bs1;
-        a.C0 = s1 ? C0 : w.Cin; a.Cin = w.Cin; a.H = Ho; a.B = B;
+        a.x0 = in.p0; a.x0_bs = in.bs0; a.x1 = in.p1; a.x1_bs = in.bs1;
+        a.C0 = in.c0(w); a.Cin = w.Cin; a.H = Ho; a.B = B;
         a.w = w.wsh; a.nchunk = w.Cin / 16; a.COP = w.COP; a.Cout = w.Cout; a.acc_scale = w.wscale_inv;
         a.bias = pre_add ? nullptr : w.bias;            // (a hoisted partial sum already carries the bias)
         a.pre_add = pre_add;
-        a.out = raw; a.out_bs = raw_bs;
+        a.out = raw.p; a.out_bs = raw.bs;
         a.fault = fault_flag();
         if (debug_plan())
             fprintf(stderr, "[plan] conv 3x3 s%d %d->%d out %dx%d on conv_ws_kernel: %d tiles of %d pixels x %d groups, %d waves, %zu bytes of LDS\n", w.stride, w.Cin, w.Cout, Ho, Wo,
@@ -485,14 +504,14 @@ struct Builder {
     // 1x1 layer of a few-pixel launch (at most 128 pixel blocks, or per-image weights) on conv_ws1_kernel (conv_ws1_kernel.h): all of K inside the
     // workgroup -- no partial-sum tensors, no sum pass.  Epilogue: bias, folded PreNorm (mean on load, rstd after), per-image shift,
     // residual; shared or per-image weight planes.
-    bool try_ws1(const ConvW &w, const float *s0, int C0, long long bs0, const float *s1, long long bs1, int H, int W, float *out, long long out_bs,
-                 const ConvOpts &o, bool need_all, int prof) {
+    Planned try_ws1(const ConvW &w, In in, Out out, const ConvOpts &o, bool need_all, int prof) {
         PfShape ps;     // (unused: the form is conv_pw_kernel's)
+        const int H = in.H, W = in.W;
         if (rc || h->arith != 1 || planB > 0 || !pw_form(w, 0, H, W, &ps)) return false;
         if (need_all || o.ln_g || o.stat_mean || o.res3_w || o.pf_only || (o.pre_add && o.resid) || o.relu || o.resid1 || o.uf_c) return false;
         if (o.pre_mean && o.pre_mode != 2) return false;
         if (o.w_bs && !o.wsp_bs) return false;               // per-image weights without planes
-        if (w.COP != w.Cout || w.Cin_pad != w.Cin || out_bs != (long long)w.Cout * H * W) return false;
+        if (w.COP != w.Cout || w.Cin_pad != w.Cin || out.bs != (long long)w.Cout * H * W) return false;
         if (o.resid && (o.resid_cs != (long long)H * W)) return false;
         // Measured (batch 32, profiles/per_op_r05*.txt): it wins wherever the alternative is a split-K launch + sum pass (the 8x8 level, the
         // per-image attention products everywhere); at 16x16 and batch 32 the wide folded-PreNorm projections (24 - 36 channel groups, each
@@ -506,12 +525,12 @@ struct Builder {
         if (!wide_ok && !(o.wsp_bs && W < 32)) return false;     // (per-image products of the few-pixel levels at any batch)
         Ws1ConvOp op;
         op.H = H;
-        if (!ws1_make_plan(w.Cin, s1 ? C0 : w.Cin, w.Cout, H * W, pb(), o.wsp_bs != 0, &op.plan)) return false;
-        if (!ensure_f32(s0, bs0) || (s1 && !ensure_f32(s1, bs1)) || (o.resid && !ensure_f32(o.resid, o.resid_bs))) return false;
+        if (!ws1_make_plan(w.Cin, in.c0(w), w.Cout, H * W, pb(), o.wsp_bs != 0, &op.plan)) return false;
+        if (!ensure_f32(in.p0, in.bs0) || (in.p1 && !ensure_f32(in.p1, in.bs1)) || (o.resid && !ensure_f32(o.resid, o.resid_bs))) return false;
         Ws1Args &a = op.a;
         memset(&a, 0, sizeof a);
-        a.x0 = s0; a.x0_bs = bs0; a.x1 = s1; a.x1_bs = bs1;
-        a.C0 = s1 ? C0 : w.Cin; a.Cin = w.Cin; a.HW = H * W; a.B = B;
+        a.x0 = in.p0; a.x0_bs = in.bs0; a.x1 = in.p1; a.x1_bs = in.bs1;
+        a.C0 = in.c0(w); a.Cin = w.Cin; a.HW = H * W; a.B = B;
         a.pre_mean = o.pre_mean; a.pre_rstd = o.pre_mean ? o.pre_rstd : nullptr;
         a.w = w.wsh; a.w_bs = o.wsp_bs / 8;                 // units of 8 halfs
         a.nchunk = w.Cin / 16; a.COP = w.COP; a.Cout = w.Cout; a.acc_scale = w.wscale_inv;
@@ -519,8 +538,8 @@ struct Builder {
         a.shift = o.shift; a.shift_bs = shift_stride(o);
         a.resid = o.resid; a.resid_bs = o.resid_bs;
         // (a hoisted partial sum -- the step-invariant context half of a concatenated input, layout of `out` -- is one more addend of this linear epilogue)
-        if (o.pre_add) { a.resid = o.pre_add; a.resid_bs = out_bs; a.resid_is_pre = 1; }
-        a.out = out; a.out_bs = out_bs;
+        if (o.pre_add) { a.resid = o.pre_add; a.resid_bs = out.bs; a.resid_is_pre = 1; }
+        a.out = out.p; a.out_bs = out.bs;
         a.fault = fault_flag();
         if (debug_plan())
             fprintf(stderr, "[plan] conv 1x1 %d->%d out %dx%d on conv_ws1_kernel: %d tiles of %d pixels x %d groups, %d waves%s%s\n", w.Cin, w.Cout, H, W,
@@ -529,23 +548,27 @@ struct Builder {
         return finish(prof, op, 2.0 * px * w.Cout * w.Cin, 4.0 * px * (w.Cin + w.Cout), false);
     }
 
-    // Emits one convolution.  s1 (optional) is the second concat source.  Returns false when
-    // `need_all` (fused LN / statistics) cannot be planned; the caller then emits the unfused form.
-    bool conv(const ConvW &w, const float *s0, int C0, long long bs0, const float *s1,
-              long long bs1, int H, int W, float *out, long long out_bs, const ConvOpts &o,
-              bool need_all, int prof) {
+    // workgroups of a register-staged plan at the planning batch, per phase: what the split-K rules fill the chip from
+    long long plan_wgs(const ConvPlan &plan) const {
+        return (long long)(plan.ipw > 1 ? ceil_div(pb(), plan.ipw) : plan.tiles_x * plan.tiles_y * pb()) * plan.groups;
+    }
+
+    // Emits one convolution.  Returns false when `need_all` (fused LN / statistics) cannot be planned; the caller then emits the
+    // unfused form.
+    Planned conv(const ConvW &w, In in, Out out, const ConvOpts &o, bool need_all, int prof) {
         if (rc) return true;
-        if (s1 && (C0 % 4)) {
+        const int H = in.H, W = in.W;
+        if (in.p1 && (in.C0 % 4)) {
             // the kernel wants every K-chunk inside one concat source: materialise odd seams
-            const long long n0 = (long long)C0 * H * W, n1 = (long long)(w.Cin - C0) * H * W;
+            const long long n0 = (long long)in.C0 * H * W, n1 = (long long)(w.Cin - in.C0) * H * W;
             float *cat = dalloc((size_t)B * (n0 + n1));
-            copy(s0, bs0, cat, n0 + n1, n0);
-            copy(s1, bs1, cat + n0, n0 + n1, n1);
-            s0 = cat; bs0 = n0 + n1; s1 = nullptr; bs1 = 0;
+            copy(in.p0, in.bs0, cat, n0 + n1, n0);
+            copy(in.p1, in.bs1, cat + n0, n0 + n1, n1);
+            in = In(cat, w.Cin, n0 + n1, H, W);
         }
         ConvShape s;
         s.Cin = w.Cin; s.Cout = w.Cout; s.KH = w.KH; s.KW = w.KW; s.stride = w.stride;
-        s.C0 = s1 ? C0 : 0;
+        s.C0 = in.c0();
         s.Win = W; s.nz = w.nz;
         s.allow_split = w.wsp != nullptr;
         s.arith = (h->arith == 1 && w.wsh) ? 1 : 0;
@@ -557,12 +580,12 @@ struct Builder {
             s.Wo = (W + 2 * w.px() - w.KW) / w.stride + 1;
         }
         s.B = pb(); s.need_all_cout = need_all; s.lnmode = o.pre_mean ? o.pre_mode : 0;
-        if (!o.uf_c && try_pf(w, s0, C0, s1, H, W, out, out_bs, o, need_all, prof)) return true;
-        if (o.uf_c && !s1 && try_pf_uf(w, s0, bs0, H, W, out, out_bs, o, need_all, prof)) return true;
+        if (Planned r = try_pf(w, in, out, o, need_all, prof)) return r;
+        if (Planned r = try_pf_uf(w, in, out, o, need_all, prof)) return r;
         if (o.pf_only) return false;
         if (o.resid1 && !rc) { rc = fail(h, CDC_ERR_UNSUPPORTED, "a two-source residual reached a kernel without it"); return true; }
         {   // a planes-only source / residual and a reader of fp32: unpack it once (ensure_f32)
-            const std::pair<const float *, long long> rd[3] = {{s0, bs0}, {s1, bs1}, {o.resid, o.resid_bs}};
+            const std::pair<const float *, long long> rd[3] = {{in.p0, in.bs0}, {in.p1, in.bs1}, {o.resid, o.resid_bs}};
             for (const auto &q : rd)
                 if (!ensure_f32(q.first, q.second) && !rc) {
                     rc = fail(h, CDC_ERR_UNSUPPORTED, "a planes-only tensor reached a kernel that reads fp32 and cannot be unpacked");
@@ -570,11 +593,10 @@ struct Builder {
                 }
         }
         // Downsample of a few-pixel level at small batch: all of K inside the workgroup (no split-K, no sum pass)
-        if (w.stride == 2 && !need_all && o.linear_epilogue() && !o.resid && !o.pre_mean && !o.w_bs && !o.uf_c && !(o.emit_pf && twin(out)) &&
-            try_ws(w, s0, C0, bs0, s1, bs1, H, W, out, out_bs, prof))
-            return true;
-        if (!o.uf_c && try_ws1(w, s0, C0, bs0, s1, bs1, H, W, out, out_bs, o, need_all, prof)) return true;
-        if (!o.uf_c && try_pw(w, s0, C0, bs0, s1, bs1, H, W, out, out_bs, o, need_all, prof)) return true;
+        if (w.stride == 2 && !need_all && o.linear_epilogue() && !o.resid && !o.pre_mean && !o.w_bs && !o.uf_c && !(o.emit_pf && twin(out.p)))
+            if (Planned r = try_ws(w, in, out, prof)) return r;
+        if (Planned r = try_ws1(w, in, out, o, need_all, prof)) return r;
+        if (Planned r = try_pw(w, in, out, o, need_all, prof)) return r;
         const bool linear_ep = !need_all && o.linear_epilogue() && w.nz == 1 && !w.transposed && !o.no_ksplit;
         s.max_ksplit = o.max_ksplit > 1 ? o.max_ksplit : (linear_ep ? 4 : 1);
         if (need_all && (w.Cout % 32)) return false;
@@ -587,23 +609,20 @@ struct Builder {
         }
         if (o.uf_c && !(plan.split == 2 && plan.arith == 1 && plan.xu == 1 && plan.lnmode == 0 &&
                         conv_lookup_split2hu(plan.MB, plan.NPW))) return false;                       // only that kernel unfolds on load
-        last_ksplit = 1;
-        last_pf_only = false;
+        Planned did(true);
         if (o.max_ksplit > 1 && plan.split == 2 && !need_all) {
             // few workgroups and a long K loop (low-resolution levels): slice K so that the chip holds
             // >= 4 workgroups per CU; the LayerNorm kernel that follows adds the slices
-            const long long wgs = (long long)(plan.ipw > 1 ? ceil_div(pb(), plan.ipw) : plan.tiles_x * plan.tiles_y * pb()) *
-                                  plan.groups * w.nz;
+            const long long wgs = plan_wgs(plan) * w.nz;
             int ks = (int)std::min<long long>(ceil_div(kKsTarget, wgs), std::min(o.max_ksplit, plan.nchunk / 4));
-            if (ks > 1) { plan.ksplit = ks; last_ksplit = ks; }
+            if (ks > 1) { plan.ksplit = ks; did.ksplit = ks; }
         }
         // Plain (linear) epilogues at the few-workgroup levels -- the attention projections and res_convs
         // at 8x8 / 16x16: slice K as well, slice 0 carries bias + residual, a sum pass follows.
         float *ks_scratch = nullptr;
         const long long dense_bs = (long long)w.Cout * s.Ho * s.Wo;
         if (o.max_ksplit <= 1 && plan.split == 2 && linear_ep) {
-            const long long wgs = (long long)(plan.ipw > 1 ? ceil_div(pb(), plan.ipw) : plan.tiles_x * plan.tiles_y * pb()) *
-                                  plan.groups;
+            const long long wgs = plan_wgs(plan);      // (no `* w.nz` as above: a linear epilogue is sliced only where nz == 1, linear_ep)
             const int ks = (int)std::min<long long>(ceil_div(kKsTarget, wgs), std::min(4, plan.nchunk / 4));
             if (ks > 1 && (planB > 0 || (size_t)B * dense_bs * 4 * ks <= (64u << 20))) {
                 plan.ksplit = ks;
@@ -621,8 +640,8 @@ struct Builder {
         op.plan = plan; op.nz = w.nz;
         ConvArgs &a = op.a;
         memset(&a, 0, sizeof a);
-        a.src0 = s0; a.src1 = s1; a.src0_bs = bs0; a.src1_bs = bs1;
-        a.C0 = s1 ? C0 : w.Cin; a.Cin = w.Cin; a.H = H; a.W = W;
+        a.src0 = in.p0; a.src1 = in.p1; a.src0_bs = in.bs0; a.src1_bs = in.bs1;
+        a.C0 = in.c0(w); a.Cin = w.Cin; a.H = H; a.W = W;
         a.ln_mean = o.pre_mean; a.ln_rstd = o.pre_rstd; a.ln_g = o.pre_g; a.ln_b = o.pre_b;
         a.wp = w.wp; a.w_bs = o.w_bs; a.w_zs = w.w_zs;
         a.wsp = w.wsp; a.wsp_zs = w.wsp_zs; a.wsp_bs = o.wsp_bs;
@@ -630,16 +649,16 @@ struct Builder {
         if (plan.split == 2 && plan.arith == 1) { a.wsp = w.wsh; a.acc_scale = w.wscale_inv; }
         a.KH = w.KH; a.KW = w.KW; a.stride = w.stride;
         a.Cin_pad = w.Cin_pad; a.COP = w.COP; a.Cout = w.Cout;
-        a.out = out; a.out_bs = out_bs; a.out_ks = (long long)B * out_bs;
+        a.out = out.p; a.out_bs = out.bs; a.out_ks = (long long)B * out.bs;
         out_geometry(a, w, s.Ho, s.Wo);
         epilogue(a, w, o);
         if (o.uf_c) {
             a.uf_c = o.uf_c; a.uf_pad = o.uf_pad;
             a.uf_magic = o.uf_c > 1 ? (unsigned)(((1ull << 32) + o.uf_c - 1) / o.uf_c) : 0u;
         }
-        if (o.emit_pf && !ks_scratch && plan.ksplit <= 1 && (w.Cout % 32) == 0 && bind_out_pf(a, w, out, out_bs, s.Ho, s.Wo)) {
+        if (o.emit_pf && !ks_scratch && plan.ksplit <= 1 && (w.Cout % 32) == 0 && bind_out_pf(a, w, out.p, out.bs, s.Ho, s.Wo)) {
             a.pf_only = o.no_f32 ? 1 : 0;
-            last_pf_only = o.no_f32;
+            did.planes_only = o.no_f32;
         }
         const double px = (double)B * s.Ho * s.Wo * w.nz;
         if (ks_scratch) {
@@ -647,23 +666,29 @@ struct Builder {
         }
         emit(Op(prof, op, 2.0 * px * w.Cout * w.Cin * w.KH * w.KW, 4.0 * ((double)B * w.Cin * H * W + px * w.Cout)));
         if (ks_scratch) {
-            emit(Op(prof, CopyArgs{ks_scratch, dense_bs, out, out_bs, dense_bs, plan.ksplit, (long long)B * dense_bs}, 0,
+            emit(Op(prof, CopyArgs{ks_scratch, dense_bs, out.p, out.bs, dense_bs, plan.ksplit, (long long)B * dense_bs}, 0,
                     4.0 * B * dense_bs * (plan.ksplit + 1)));
             // split-K epilogues cannot emit planes (partial sums): pack the reduced tensor where a reader wants them
-            if (o.emit_pf && !w.transposed && out_twin(out, out_bs, w.Cout, s.Ho, s.Wo)) pack(out, out_bs);
+            if (o.emit_pf && !w.transposed && out_twin(out.p, out.bs, w.Cout, s.Ho, s.Wo)) pack(out.p, out.bs);
         }
-        return true;
+        return did;
     }
 
-    void ln(const float *in, float *out, int C, int HW, const float *g, const float *b, int relu,
-            const float *shift, const float *resid, float *sm, float *sr, int nparts = 1) {
+    // The stand-alone channel LayerNorm over the sum of `nparts` split-K slices of `in`, with the parts of a convolution's epilogue
+    // it has: o.ln_g / ln_b, relu, shift (the U-Net's table), a dense resid, stat_mean / stat_rstd.  out == null: statistics only.
+    void ln(const float *in, float *out, int C, int HW, const ConvOpts &o, int nparts = 1) {
         if (rc) return;
         LnArgs a = {};
         a.nparts = nparts; a.part_stride = (long long)B * C * HW;
-        a.in = in; a.out = out; a.C = C; a.HW = HW; a.g = g; a.b = b; a.eps = 1e-5f; a.relu = relu;
-        a.shift = shift; a.shift_bs = h->shift_bs; a.resid = resid; a.stat_mean = sm; a.stat_rstd = sr;
+        a.in = in; a.out = out; a.C = C; a.HW = HW; a.g = o.ln_g; a.b = o.ln_b; a.eps = 1e-5f; a.relu = o.relu;
+        a.shift = o.shift; a.shift_bs = h->shift_bs; a.resid = o.resid; a.stat_mean = o.stat_mean; a.stat_rstd = o.stat_rstd;
         a.fault = fault_flag();
         emit(Op(PC_LN, a, 0, 4.0 * B * C * HW * (out ? 2 : 1)));
+    }
+    void ln_stats(const float *x, int C, int HW, float *sm, float *sr) {
+        ConvOpts o;
+        o.stat_mean = sm; o.stat_rstd = sr;
+        ln(x, nullptr, C, HW, o);
     }
 
     void copy(const float *src, long long src_bs, float *dst, long long dst_bs, long long n) {
@@ -696,44 +721,33 @@ struct Builder {
 
     // conv -> channel LN -> ReLU (+shift) (+resid) (+stats), fused when possible (Block.forward,
     // network_components.py:83-91, plus the adds of ResnetBlock.forward :107-114)
-    // uf_c > 0 (unfold on load, ConvArgs::uf_c): s0 is the uf_c-channel image and w the KH x 1 layer over its kx-unfolded channels; only
-    // the fused register-staged plan can do that -- returns false, with nothing emitted, when it is not available.
-    bool block(const ConvW &w, const float *s0, int C0, long long bs0, const float *s1, long long bs1,
-               int H, int W, Act out, const float *g, const float *b, const float *shift,
-               const float *pre_add, const float *resid, long long resid_bs, float *sm, float *sr,
-               int prof, bool pf_only_out = false, int uf_c = 0, int uf_pad = 0, const float *resid1 = nullptr, long long resid1_bs = 0,
-               int resid_c0 = 0) {
-        ConvOpts o;
-        o.resid1 = resid1; o.resid1_bs = resid1_bs; o.resid_c0 = resid_c0;
-        o.uf_c = uf_c; o.uf_pad = uf_pad;
-        o.no_f32 = pf_only_out;
-        o.ln_g = g; o.ln_b = b; o.relu = 1; o.shift = shift; o.pre_add = pre_add;
-        o.no_bias = pre_add != nullptr;          // the hoisted partial already carries the bias
-        o.resid = resid; o.resid_bs = resid_bs; o.resid_cs = (long long)H * W;
-        o.stat_mean = sm; o.stat_rstd = sr;
-        o.res3_w = next_res3_w; o.res3_x = next_res3_x; o.res3_bs = next_res3_bs;
-        const bool want_res3 = next_res3_w != nullptr;
-        next_res3_w = next_res3_x = nullptr;
+    // `o` names the parts (ln_g / ln_b, shift, pre_add, resid*, resid1*, stat_*, no_f32, uf_*, res3_*); relu, emit_pf, resid_cs and no_bias are set here.
+    // o.uf_c > 0 (unfold on load, ConvArgs::uf_c): `in` is the uf_c-channel image and w the KH x 1 layer over its kx-unfolded channels;
+    // only the fused register-staged plan can do that -- returns false, with nothing emitted, when it is not available.
+    Planned block(const ConvW &w, In in, Out out, ConvOpts o, int prof) {
+        const int H = in.H, W = in.W;
+        o.relu = 1;
         o.emit_pf = true;
+        o.no_bias = o.pre_add != nullptr;        // the hoisted partial already carries the bias
+        o.resid_cs = (long long)H * W;
         {   // pre-split operands first: there the fused LayerNorm reduces across waves (up to 256 channels)
             ConvOpts op = o;
             op.pf_only = true;
-            if (conv(w, s0, C0, bs0, s1, bs1, H, W, out.p, out.bs(), op, true, prof)) return true;
+            if (Planned r = conv(w, in, out, op, true, prof)) return r;
         }
         // few-pixel levels: the weight-stationary kernel (all of K in one workgroup, no partial-sum tensors) + an in-place LayerNorm pass
-        if (!want_res3 && !uf_c && !resid1 && w.stride == 1 && out.bs() == (long long)w.Cout * H * W &&
-            try_ws(w, s0, C0, bs0, s1, bs1, H, W, out.p, out.bs(), prof, pre_add)) {
-            ln(out.p, out.p, w.Cout, H * W, g, b, 1, shift, resid, sm, sr);
+        if (!o.res3_w && !o.uf_c && !o.resid1 && w.stride == 1 && out.bs == (long long)w.Cout * H * W && try_ws(w, in, out, prof, o.pre_add)) {
+            ln(out.p, out.p, w.Cout, H * W, o);
             return true;
         }
-        if (prefer_fused(w, H, W) && conv(w, s0, C0, bs0, s1, bs1, H, W, out.p, out.bs(), o, true, prof))
-            return true;
-        if (uf_c) return false;
-        if (want_res3) { rc = fail(h, CDC_ERR_UNSUPPORTED, "epilogue res_conv needs the fused LayerNorm plan"); return true; }
+        if (prefer_fused(w, H, W))
+            if (Planned r = conv(w, in, out, o, true, prof)) return r;
+        if (o.uf_c) return false;
+        if (o.res3_w) { rc = fail(h, CDC_ERR_UNSUPPORTED, "epilogue res_conv needs the fused LayerNorm plan"); return true; }
         ConvOpts u;
-        u.pre_add = pre_add; u.no_bias = o.no_bias;
+        u.pre_add = o.pre_add; u.no_bias = o.no_bias;
         const size_t plane_f = (size_t)B * w.Cout * H * W;
-        if (!pre_add && w.wsp && w.Cout <= 8 * 48 && plane_f * 4 * 4 <= (160u << 20)) {
+        if (!o.pre_add && w.wsp && w.Cout <= 8 * 48 && plane_f * 4 * 4 <= (160u << 20)) {
             // low-resolution levels: split-K partial sums into scratch, summed by the LayerNorm kernel
             // small batches: up to six slices (the 8 x 8 level: 24 chunks -> 6 slices of 4; measured at batch 1: its 3 x 3 layers
             // 0.53 -> 0.46 ms per iteration, LayerNorm passes unchanged with ln_kernel_vec<2, 6>; whole model -1.4 % at batch 1 - 4,
@@ -741,18 +755,16 @@ struct Builder {
             const int kmax = (pb() <= 8 ? 6 : 4);
             float *part = dalloc(plane_f * kmax);
             u.max_ksplit = kmax;
-            conv(w, s0, C0, bs0, s1, bs1, H, W, part, out.bs(), u, false, prof);
-            ln(part, out.p, w.Cout, H * W, g, b, 1, shift, resid, sm, sr, last_ksplit);
+            // (the slices lie B * out.bs apart: `out`'s dense stride, not a stride of the scratch)
+            const Planned sliced = conv(w, in, Out(part, out.bs), u, false, prof);
+            ln(part, out.p, w.Cout, H * W, o, sliced.ksplit);
             return true;
         }
-        conv(w, s0, C0, bs0, s1, bs1, H, W, out.p, out.bs(), u, false, prof);
-        ln(out.p, out.p, w.Cout, H * W, g, b, 1, shift, resid, sm, sr);
+        conv(w, in, out, u, false, prof);
+        ln(out.p, out.p, w.Cout, H * W, o);
         return true;
     }
 
-    // ResnetBlock.forward (network_components.py:107-114).  a1 = second concat source.  If
-    // `a1_is_context` the block was packed with split weights: the context halves are evaluated into
-    // h->pre_ops (once per decode) and enter the per-step convolutions as `pre_add`.
     // Would a ResnetBlock read its input x ONLY as planes -- block1 on a plane-operand kernel, identity residual read from planes in
     // block2's epilogue (round 4: PfArgs::resid_pf)?  Then the block that produces x writes no fp32 copy (out_planes_only below).
     bool rb_reads_planes_only(const ResBlockW &rb, int C, int H, int W) {
@@ -760,31 +772,52 @@ struct Builder {
         return pf_would_plan(rb.c1, H, W) && pf_would_plan(rb.c2, H, W);
     }
 
-    Act resblock(const ResBlockW &rb, Act a0, const Act *a1, bool a1_is_context, float *sm, float *sr,
-                 Site out_site = SITE_ALWAYS, bool out_planes_only = false) {
+    // after the conv() / block() call `did` that produced `a`: if it wrote planes only, say so on the twin (its readers must take
+    // planes) and on the Act
+    void mark_planes_only(Act &a, const Planned &did) {
+        if (!did.planes_only) return;
+        PfTwin *t = twin(a.p);
+        t->only = true;
+        a.pf = t->p; a.pf_bs = t->bs();
+    }
+    // A planes-only input `x` of the layer (`what`) whose ops start at index `first` of the program must have been read there by a
+    // plane-operand kernel (an fp32 reader would have unpacked it: ensure_f32): anything else read a buffer nobody wrote.
+    void require_planes_reader(const Act &x, size_t first, const char *what) {
+        if (rc || !x.pf || !still_planes_only(x.p)) return;
+        for (size_t q = first; q < h->ops.size(); ++q)
+            if (h->ops[q].on_conv_pf_kernel()) return;
+        rc = fail(h, CDC_ERR_UNSUPPORTED, "planes-only %s input without a plane-operand kernel", what);
+    }
+
+    // ResnetBlock.forward (network_components.py:107-114).  a1 = second concat source.  Where the block was packed with split
+    // weights for it (hoist_cx: the first block of a level with context, cdc_weights.hip) a1 is the context: its halves are
+    // evaluated into h->pre_ops (once per decode) and enter the per-step convolutions as `pre_add`.
+    Act resblock(const ResBlockW &rb, Act a0, const Act *a1, float *sm, float *sr, Site out_site = SITE_ALWAYS, bool out_planes_only = false) {
         if (rc) return Act();
         const int H = a0.H, W = a0.W, HW = H * W;
         const int prof1 = rb.k == 7 ? PC_CONV7 : PC_CONV3;
-        const float *shift = rb.has_mlp ? h->shift + rb.shift_off : nullptr;   // Compressor blocks: no time embedding
         Act h1 = new_act(rb.cout, H, W), out = new_act(rb.cout, H, W, true, out_site);
         if (pf_mode() >= 2 && pf_would_plan(rb.c2, H, W)) add_twin(h1.p, rb.cout, H, W);
+        ConvOpts o1, o2;                        // block1: + time embedding; block2: + residual, the statistics the level's attention reads
+        o1.ln_g = rb.g1; o1.ln_b = rb.b1;
+        o1.shift = rb.has_mlp ? h->shift + rb.shift_off : nullptr;             // Compressor blocks: no time embedding
         // h1 feeds block2 only: when block2 runs on the pre-split operand kernel the fp32 copy is never read
-        const bool h1_pf_only = twin(h1.p) && pf_would_plan(rb.c2, H, W);
-        if (a1 && a1_is_context && rb.hoist_cx == a0.C) {
+        o1.no_f32 = twin(h1.p) && pf_would_plan(rb.c2, H, W);
+        o2.ln_g = rb.g2; o2.ln_b = rb.b2; o2.stat_mean = sm; o2.stat_rstd = sr;
+        o2.no_f32 = out_planes_only && twin(out.p);
+        auto residual = [&](const Act &r) { o2.resid = r.p; o2.resid_bs = r.bs(); };
+        if (a1 && rb.hoist_cx == a0.C) {
             // identity residual over cat[x, context] (downs.1.0): read from its two sources in block2's epilogue where that runs on a
             // plane-operand kernel (PfArgs::resid1) instead of materialising the concatenation every iteration
             const bool res2 = !rb.has_res && (a0.C % 64) == 0 && a0.C + a1->C == rb.cout && pf_would_plan(rb.c2, H, W) && !dev_env("CDC_NO_RESID2");
             std::vector<Op> *saved = cur;
             Act p1 = new_act(rb.cout, H, W, false);
             cur = &h->pre_ops;
-            conv(rb.c1c, a1->p, a1->C, a1->bs(), nullptr, 0, H, W, p1.p, p1.bs(), ConvOpts(), false, prof1);
-            const float *res = nullptr;
-            long long res_bs = 0;
+            conv(rb.c1c, *a1, p1, ConvOpts(), false, prof1);
             Act pr, cat;
             if (rb.has_res) {
                 pr = new_act(rb.cout, H, W, false);
-                conv(rb.cresc, a1->p, a1->C, a1->bs(), nullptr, 0, H, W, pr.p, pr.bs(), ConvOpts(), false,
-                     PC_CONV1);
+                conv(rb.cresc, *a1, pr, ConvOpts(), false, PC_CONV1);
             } else if (!res2) {
                 // identity residual over the concatenation (downs.1.0): context half copied once
                 cat = new_act(a0.C + a1->C, H, W, false);
@@ -793,59 +826,52 @@ struct Builder {
             cur = saved;
             // first 7x7 layer = 7x1 convolution over the kx-unfolded image: the unfolding happens while the patch is loaded
             // (round 4); the explicit unfold pass + its 21-channel tensor remain the fall-back
-            if (rb.has_unfold && (W & 3) == 0 &&
-                block(rb.c1u, a0.p, a0.C * rb.k, a0.bs(), nullptr, 0, H, W, h1, rb.g1, rb.b1, shift, p1.p, nullptr, 0,
-                      nullptr, nullptr, prof1, h1_pf_only, a0.C, rb.k / 2)) {
+            o1.pre_add = p1.p;
+            ConvOpts o1u = o1;
+            o1u.uf_c = a0.C; o1u.uf_pad = rb.k / 2;
+            if (rb.has_unfold && (W & 3) == 0 && block(rb.c1u, a0, h1, o1u, prof1)) {
             } else if (rb.has_unfold && (W & 3) == 0) {
                 Act u = new_act(a0.C * rb.k, H, W, false);
                 emit(Op(prof1, UnfoldArgs{a0.p, a0.bs(), u.p, u.bs(), a0.C, rb.k, rb.k / 2, H, W}, 0, 4.0 * B * (a0.C + u.C) * HW));
-                block(rb.c1u, u.p, u.C, u.bs(), nullptr, 0, H, W, h1, rb.g1, rb.b1, shift, p1.p, nullptr, 0,
-                      nullptr, nullptr, prof1, h1_pf_only);
+                block(rb.c1u, u, h1, o1, prof1);
             } else
-            block(rb.c1x, a0.p, a0.C, a0.bs(), nullptr, 0, H, W, h1, rb.g1, rb.b1, shift, p1.p, nullptr, 0,
-                  nullptr, nullptr, prof1, h1_pf_only);
+                block(rb.c1x, a0, h1, o1, prof1);
             if (rb.has_res && a0.C == 3 && rb.cresx.COP == round_up(rb.cout, 32) && prefer_fused(rb.c2, H, W)) {
                 // res_conv over the 3 image channels rides in block2's epilogue; its context half (with
                 // the bias) is the hoisted tensor
-                res = pr.p; res_bs = pr.bs();
-                next_res3_w = rb.cresx.wp; next_res3_x = a0.p; next_res3_bs = a0.bs();
+                residual(pr);
+                o2.res3_w = rb.cresx.wp; o2.res3_x = a0.p; o2.res3_bs = a0.bs();
             } else if (rb.has_res) {
                 Act r = new_act(rb.cout, H, W, false);
                 ConvOpts orr; orr.pre_add = pr.p; orr.no_bias = true;
-                conv(rb.cresx, a0.p, a0.C, a0.bs(), nullptr, 0, H, W, r.p, r.bs(), orr, false, PC_CONV1);
-                res = r.p; res_bs = r.bs();
+                conv(rb.cresx, a0, r, orr, false, PC_CONV1);
+                residual(r);
             } else if (res2) {
-                res = a0.p; res_bs = a0.bs();
+                residual(a0);
+                o2.resid1 = a1->p; o2.resid1_bs = a1->bs(); o2.resid_c0 = a0.C;
             } else {
                 copy(a0.p, a0.bs(), cat.p, cat.bs(), a0.bs());
-                res = cat.p; res_bs = cat.bs();
+                residual(cat);
             }
-            block(rb.c2, h1.p, rb.cout, h1.bs(), nullptr, 0, H, W, out, rb.g2, rb.b2, nullptr, nullptr, res,
-                  res_bs, sm, sr, PC_CONV3, out_planes_only && twin(out.p), 0, 0, res2 ? a1->p : nullptr, res2 ? a1->bs() : 0, res2 ? a0.C : 0);
-            mark_planes_only(out);
+            mark_planes_only(out, block(rb.c2, h1, out, o2, PC_CONV3));
             return out;
         }
-        const float *s0 = a0.p, *s1 = a1 ? a1->p : nullptr;
-        int C0 = a0.C;
-        long long bs0 = a0.bs(), bs1 = a1 ? a1->bs() : 0;
+        // identity residual over a concat: materialised, it is the block's one input
+        In in = a1 ? In(a0, *a1) : In(a0);
         if (!rb.has_res && a1) {
             Act cat = new_act(a0.C + a1->C, H, W, false);
             copy(a0.p, a0.bs(), cat.p, cat.bs(), a0.bs());
             copy(a1->p, a1->bs(), cat.p + a0.bs(), cat.bs(), a1->bs());
-            s0 = cat.p; s1 = nullptr; C0 = cat.C; bs0 = cat.bs(); bs1 = 0;
+            in = cat;
         }
-        block(rb.c1, s0, C0, bs0, s1, bs1, H, W, h1, rb.g1, rb.b1, shift, nullptr, nullptr, 0, nullptr,
-              nullptr, prof1, h1_pf_only);
-        const float *res = s0;
-        long long res_bs = bs0;
+        block(rb.c1, in, h1, o1, prof1);
+        o2.resid = in.p0; o2.resid_bs = in.bs0;
         if (rb.has_res) {
             Act r = new_act(rb.cout, H, W, false);
-            conv(rb.cres, s0, C0, bs0, s1, bs1, H, W, r.p, r.bs(), ConvOpts(), false, PC_CONV1);
-            res = r.p; res_bs = r.bs();
+            conv(rb.cres, in, r, ConvOpts(), false, PC_CONV1);
+            residual(r);
         }
-        block(rb.c2, h1.p, rb.cout, h1.bs(), nullptr, 0, H, W, out, rb.g2, rb.b2, nullptr, nullptr, res,
-              res_bs, sm, sr, PC_CONV3, out_planes_only && twin(out.p));
-        mark_planes_only(out);
+        mark_planes_only(out, block(rb.c2, h1, out, o2, PC_CONV3));
         return out;
     }
     // VBRCondition at one site of a variable-bitrate compressor (in place on the fp32 tensor; + LeakyReLU(0.2) at the hyper sites).
@@ -866,12 +892,10 @@ struct Builder {
         emit(Op(PC_GDN, GdnArgs{x, x_bs, y, y_bs, w.beta, w.gamma, w.C, HW, w.inverse ? 1 : 0, fault_flag()}, 2.0 * B * HW * w.C * w.C,
                 8.0 * B * w.C * HW));
     }
-    // after the block() call that produced `a`: if it wrote planes only, say so on the twin (its readers must take planes) and on the Act
-    void mark_planes_only(Act &a) {
-        if (!last_pf_only) return;
-        PfTwin *t = twin(a.p);
-        t->only = true;
-        a.pf = t->p; a.pf_bs = t->bs();
+    // a debugging tap on a buffer that is no activation of the program
+    void tap(const std::string &name, float *p, int C, int H, int W) {
+        Act t; t.p = p; t.C = C; t.H = H; t.W = W;
+        h->taps[name] = t;
     }
 
     // Residual(PreNorm(LinearAttention)) (network_components.py:10-16,69-77,117-139)
@@ -889,7 +913,7 @@ struct Builder {
         ConvOpts oq;                                   // LN(x) folded into the projection (LNMODE 2)
         oq.pre_mean = sm; oq.pre_rstd = sr; oq.pre_mode = 2;
         if (!fused)
-            conv(fold ? at.kv : at.qkv, x.p, C, x.bs(), nullptr, 0, H, W, qkv.p, qkv.bs(), oq, false, PC_CONV1);
+            conv(fold ? at.kv : at.qkv, x, qkv, oq, false, PC_CONV1);
         const float *kp = fused ? nullptr : qkv.p + (size_t)(fold ? 0 : C) * N, *vp = fused ? nullptr : kp + (size_t)C * N;
         float *kmax = dalloc((size_t)B * C);
         const int tiles = ceil_div(C, 64);
@@ -933,10 +957,10 @@ struct Builder {
         // (debugging taps of the level's intermediates: the staged projection, the partial context sums, the per-image matrix)
         if (!fused) h->taps[at.prefix + ".kv"] = qkv;
         // (.S and .Z carry a common factor 2^13 where an fp16 kernel wrote them, see ksum above)
-        { Act ts; ts.p = S; ts.C = nsplit; ts.H = C; ts.W = C; h->taps[at.prefix + ".S"] = ts; }
-        { Act ts; ts.p = ksum; ts.C = nsplit; ts.H = 1; ts.W = C; h->taps[at.prefix + ".Z"] = ts; }
-        { Act ts; ts.p = kmax; ts.C = 1; ts.H = 1; ts.W = C; h->taps[at.prefix + ".kmax"] = ts; }
-        { Act ts; ts.p = ctxw; ts.C = 1; ts.H = Cin_pad; ts.W = COP; h->taps[at.prefix + ".M"] = ts; }
+        tap(at.prefix + ".S", S, nsplit, C, C);
+        tap(at.prefix + ".Z", ksum, nsplit, 1, C);
+        tap(at.prefix + ".kmax", kmax, 1, 1, C);
+        tap(at.prefix + ".M", ctxw, 1, Cin_pad, COP);
         // the context chain of the level, from one argument block
         const AttnCtxArgs ca = {kp, vp, fused ? 0 : qkv.bs(), C, N, kmax, ksum, S, ctxw, nsplit, Cin_pad, COP, 1.0f / sqrtf((float)C),
                                 at.WoT, at.WqT, T1, at.ng, at.uq, at.out.bias, biasB, kmaxs, Ws, planes_f16 ? 1 : 0, at.Wq, h->arith == 1};
@@ -978,18 +1002,17 @@ struct Builder {
             oy.resid = x.p; oy.resid_bs = x.bs(); oy.resid_cs = N;
             oy.emit_pf = true;
             oy.no_f32 = out_planes_only && split_out && twin(y.p) != nullptr;
-            conv(cw, x.p, C, x.bs(), nullptr, 0, H, W, y.p, y.bs(), oy, false, PC_CONV1);
-            if (last_pf_only) { PfTwin *ty = twin(y.p); ty->only = true; y.pf = ty->p; y.pf_bs = ty->bs(); }
+            mark_planes_only(y, conv(cw, x, y, oy, false, PC_CONV1));
             return y;
         }
         // out[e,n] = sum_d ctx[d,e] q[d,n]  as a 1x1 convolution with per-image weights (:137)
         Act o = new_act(C, H, W, false);
         ConvOpts oo; oo.w_bs = (long long)Cin_pad * COP; oo.no_bias = true;
         if (split_ctxq) oo.wsp_bs = (long long)(C / 16) * 6 * C * 8;
-        conv(cw, qkv.p, C, qkv.bs(), nullptr, 0, H, W, o.p, o.bs(), oo, false, PC_CONV1);
+        conv(cw, In(qkv.p, C, qkv.bs(), H, W), o, oo, false, PC_CONV1);        // (q: the first C channels of the projection)
         ConvOpts oy; oy.resid = x.p; oy.resid_bs = x.bs(); oy.resid_cs = N;
         oy.emit_pf = true;
-        conv(at.out, o.p, C, o.bs(), nullptr, 0, H, W, y.p, y.bs(), oy, false, PC_CONV1);
+        conv(at.out, o, y, oy, false, PC_CONV1);
         return y;
     }
 };
@@ -1011,9 +1034,21 @@ void free_program(cdc_handle *h) {
     h->lp_res = nullptr;
 }
 
+// The frame of every program builder: nothing to do when the handle holds the program of this shape (and kind of plan) already;
+// the shape is committed only once the whole program was built.
+static bool program_built(const cdc_handle *h, int B, int H, int W, bool batch1_plan = false) {
+    return h->pB == B && h->pH == H && h->pW == W && h->p_batch1_plan == batch1_plan;
+}
+static int commit_program(cdc_handle *h, const Builder &bd, int H, int W, bool batch1_plan = false) {
+    if (bd.rc) return bd.rc;
+    h->pB = bd.B; h->pH = H; h->pW = W;
+    h->p_batch1_plan = batch1_plan;
+    return CDC_OK;
+}
+
 // Builds the launch program of Unet.forward for batch B at H x W (unet.py:106-135).
 int build_program(cdc_handle *h, int B, int H, int W) {
-    if (h->pB == B && h->pH == H && h->pW == W) return CDC_OK;
+    if (program_built(h, B, H, W)) return CDC_OK;
     free_program(h);
     const int n = h->n_res;
     const int down = 1 << (n - 1);
@@ -1021,7 +1056,7 @@ int build_program(cdc_handle *h, int B, int H, int W) {
         return fail(h, CDC_ERR_INVALID, "H=%d, W=%d must be multiples of %d (%d downsamples)", H, W,
                     down, n - 1);
     Builder bd{h, B, &h->act_allocs};
-    h->in_x = bd.dalloc((size_t)B * h->cfg.channels * H * W);
+    Act x = bd.input(h->cfg.channels, H, W);
     h->in_time = bd.dalloc(B);
     h->shift = bd.dalloc((size_t)B * h->shift_bs);
     h->xa = bd.dalloc((size_t)B * h->cfg.channels * H * W);
@@ -1034,7 +1069,6 @@ int build_program(cdc_handle *h, int B, int H, int W) {
     bd.emit(Op(PC_SMALL, TembArgs{h->in_time, h->tm_w0, h->tm_b0, h->tm_w2, h->tm_b2, h->cfg.dim, h->d_temb_layers, (int)h->rbs.size(),
                                   h->shift, h->shift_bs}));
 
-    Act x; x.p = h->in_x; x.C = h->cfg.channels; x.H = H; x.W = W;
     std::vector<Act> skips;
     size_t rbi = 0, ati = 0;
     for (int i = 0; i < n; ++i) {
@@ -1043,13 +1077,14 @@ int build_program(cdc_handle *h, int B, int H, int W) {
         const bool has_ctx = i < n_ctx;
         const std::string dn = "downs." + std::to_string(i);
         // (its output goes to the second ResnetBlock only: planes INSTEAD of fp32 where that block reads nothing else)
-        x = bd.resblock(h->rbs[rbi], x, has_ctx ? &h->in_ctx[i] : nullptr, true, nullptr, nullptr, Builder::SITE_RB_CHAIN,
+        x = bd.resblock(h->rbs[rbi], x, has_ctx ? &h->in_ctx[i] : nullptr, nullptr, nullptr, Builder::SITE_RB_CHAIN,
                         bd.rb_reads_planes_only(h->rbs[rbi + 1], h->rbs[rbi].cout, x.H, x.W));
         ++rbi;
         h->taps[dn + ".0"] = x;
-        x = bd.resblock(h->rbs[rbi++], x, nullptr, false, sm, sr);
+        x = bd.resblock(h->rbs[rbi++], x, nullptr, sm, sr);
         h->taps[dn + ".1"] = x;
-        { Act ts; ts.p = sm; ts.C = 1; ts.H = x.H; ts.W = x.W; h->taps[dn + ".1.stat_mean"] = ts; ts.p = sr; h->taps[dn + ".1.stat_rstd"] = ts; }   // (the PreNorm statistics the attention reads)
+        bd.tap(dn + ".1.stat_mean", sm, 1, x.H, x.W);       // (the PreNorm statistics the attention reads)
+        bd.tap(dn + ".1.stat_rstd", sr, 1, x.H, x.W);
         // (the level-0 skip is never popped -- unet.py:113 pushes six, :123 pops five: its only reader is the Downsample)
         // Its output goes to the Downsample as planes INSTEAD of fp32 where that convolution runs on the plane-operand kernel.
         const bool l0_planes = i == 0 && n > 1 && bd.pf_s2_would_plan(h->downs[0], x.H, x.W);
@@ -1071,9 +1106,9 @@ int build_program(cdc_handle *h, int B, int H, int W) {
             // batches: it does not, and a split-K Downsample would need a pack launch to make them)
             const ResBlockW &nrb = h->rbs[rbi];
             Builder::ConvOpts od; od.emit_pf = bd.pf_would_plan(nrb.hoist_cx ? nrb.c1x : nrb.c1, y.H, y.W);
-            bd.conv(dw, x.p, x.C, x.bs(), nullptr, 0, x.H, x.W, y.p, y.bs(), od, false, PC_DOWN);
-            if (x.pf && bd.still_planes_only(x.p) && (h->ops.empty() || !h->ops.back().on_conv_pf_kernel()))
-                return fail(h, CDC_ERR_UNSUPPORTED, "planes-only Downsample input without a plane-operand kernel");
+            const size_t first = h->ops.size();
+            bd.conv(dw, x, y, od, false, PC_DOWN);
+            bd.require_planes_reader(x, first, "Downsample");
             x = y;
             h->taps[dn + ".3"] = x;
         }
@@ -1082,11 +1117,11 @@ int build_program(cdc_handle *h, int B, int H, int W) {
     {
         const int HWl = x.H * x.W;
         float *sm = bd.dalloc((size_t)B * HWl), *sr = bd.dalloc((size_t)B * HWl);
-        x = bd.resblock(h->rbs[rbi++], x, nullptr, false, sm, sr);          // mid_block1
+        x = bd.resblock(h->rbs[rbi++], x, nullptr, sm, sr);          // mid_block1
         h->taps["mid_block1"] = x;
         x = bd.attention(h->attns[ati++], x, sm, sr);                       // mid_attn
         h->taps["mid_attn"] = x;
-        x = bd.resblock(h->rbs[rbi++], x, nullptr, false, nullptr, nullptr, Builder::SITE_JOIN); // mid_block2 (decoder concat half)
+        x = bd.resblock(h->rbs[rbi++], x, nullptr, nullptr, nullptr, Builder::SITE_JOIN); // mid_block2 (decoder concat half)
         h->taps["mid_block2"] = x;
     }
     float *fsm = nullptr, *fsr = nullptr;       // LN statistics of the last Upsample output
@@ -1096,16 +1131,15 @@ int build_program(cdc_handle *h, int B, int H, int W) {
         skips.pop_back();
         const int HWl = x.H * x.W;
         float *sm = bd.dalloc((size_t)B * HWl), *sr = bd.dalloc((size_t)B * HWl);
-        x = bd.resblock(h->rbs[rbi], x, &skip, false, nullptr, nullptr, Builder::SITE_RB_CHAIN,
+        x = bd.resblock(h->rbs[rbi], x, &skip, nullptr, nullptr, Builder::SITE_RB_CHAIN,
                         bd.rb_reads_planes_only(h->rbs[rbi + 1], h->rbs[rbi].cout, x.H, x.W));
         ++rbi;
-        x = bd.resblock(h->rbs[rbi++], x, nullptr, false, sm, sr);
+        x = bd.resblock(h->rbs[rbi++], x, nullptr, sm, sr);
         // (an Upsample reads fp32: planes of its input only with the development switch that runs it on conv_pf_kernel)
         // ... or, where the fused-phase plane-operand kernel takes it, planes INSTEAD of fp32 (the Upsample is the only reader)
         const bool up_planes = bd.pf_tz_would_plan(h->ups[i], x.H, x.W);
         x = bd.attention(h->attns[ati++], x, sm, sr, up_planes ? Builder::SITE_ALWAYS_PLANES : Builder::SITE_NONE, up_planes);
-        const bool x_planes_only = x.pf != nullptr;
-        const size_t ops_before = h->ops.size();
+        const size_t first = h->ops.size();
         const ConvW &uw = h->ups[i];
         // the last Upsample feeds the final convolution only: planes INSTEAD of fp32 when that runs on the plane-operand kernel
         // (which needs the final LayerNorm applied here, in this epilogue)
@@ -1116,8 +1150,7 @@ int build_program(cdc_handle *h, int B, int H, int W) {
         // the next level's join is this tensor's only reader: planes INSTEAD of fp32 when block1 and res_conv both take planes
         if (i < n - 2 && !skips.empty())
             ou.no_f32 = bd.join_reads_planes(h->rbs[rbi], y.p, y.C, skips.back().p, y.H, y.W);
-        bool up_pf_only = false;
-        bool done = false;
+        Builder::Planned done;
         if (i == n - 2) {
             // the final LayerNorm (unet.py:104) needs per-pixel statistics of this output: emit them
             // from the epilogue when one workgroup owns all channels
@@ -1126,37 +1159,31 @@ int build_program(cdc_handle *h, int B, int H, int W) {
             Builder::ConvOpts ol;
             ol.ln_g = h->fin_g; ol.ln_b = h->fin_b;
             ol.emit_pf = ol.no_f32 = fin_planes;
-            done = bd.conv(uw, x.p, x.C, x.bs(), nullptr, 0, x.H, x.W, y.p, y.bs(), ol, true, PC_UP);
-            final_ln_done = done;
-            if (done && bd.last_pf_only) { Builder::PfTwin *ty = bd.twin(y.p); y.pf = ty->p; y.pf_bs = ty->bs(); }
+            done = bd.conv(uw, x, y, ol, true, PC_UP);
+            final_ln_done = done.planned;
             if (!done) {
                 fsm = bd.dalloc((size_t)B * 4 * HWl); fsr = bd.dalloc((size_t)B * 4 * HWl);
                 ou.stat_mean = fsm; ou.stat_rstd = fsr;
-                done = bd.conv(uw, x.p, x.C, x.bs(), nullptr, 0, x.H, x.W, y.p, y.bs(), ou, true, PC_UP);
+                done = bd.conv(uw, x, y, ou, true, PC_UP);
                 if (!done) { ou.stat_mean = ou.stat_rstd = nullptr; }
             }
         }
         if (!done) {
-            bd.conv(uw, x.p, x.C, x.bs(), nullptr, 0, x.H, x.W, y.p, y.bs(), ou, false, PC_UP);
-            up_pf_only = bd.last_pf_only;
-            if (up_pf_only) { Builder::PfTwin *ty = bd.twin(y.p); ty->only = true; y.pf = ty->p; y.pf_bs = ty->bs(); }
+            done = bd.conv(uw, x, y, ou, false, PC_UP);
             if (i == n - 2) {
                 if (!fsm) { fsm = bd.dalloc((size_t)B * 4 * HWl); fsr = bd.dalloc((size_t)B * 4 * HWl); }
-                bd.ln(y.p, nullptr, y.C, y.H * y.W, nullptr, nullptr, 0, nullptr, nullptr, fsm, fsr);
+                bd.ln_stats(y.p, y.C, y.H * y.W, fsm, fsr);
             }
         }
-        if (x_planes_only && bd.still_planes_only(x.p)) {
-            bool on_pf = false;
-            for (size_t q = ops_before; q < h->ops.size(); ++q) on_pf = on_pf || h->ops[q].on_conv_pf_kernel();
-            if (!on_pf) return fail(h, CDC_ERR_UNSUPPORTED, "planes-only Upsample input without a plane-operand kernel");
-        }
+        bd.mark_planes_only(y, done);
+        bd.require_planes_reader(x, first, "Upsample");
         x = y;
         if (!final_ln_done) h->taps["ups." + std::to_string(i)] = x;   // (the last one may hold LN(up(x)) instead; a planes-only tensor is unpacked on demand: Act::pf)
         if (bd.rc) return bd.rc;
     }
     if (n == 1) {       // no Upsample stage: statistics of the last attention output
         fsm = bd.dalloc((size_t)B * H * W); fsr = bd.dalloc((size_t)B * H * W);
-        bd.ln(x.p, nullptr, x.C, x.H * x.W, nullptr, nullptr, 0, nullptr, nullptr, fsm, fsr);
+        bd.ln_stats(x.p, x.C, x.H * x.W, fsm, fsr);
     }
     // final_conv = Sequential(LayerNorm(dim), Conv2d(dim, out_dim, 7, padding=3))  (unet.py:104):
     // LN applied while staging; the 7x7 conv runs row-folded (1x7 taps, out_dim*7 virtual channels)
@@ -1167,14 +1194,11 @@ int build_program(cdc_handle *h, int B, int H, int W) {
     Builder::ConvOpts of;
     if (!final_ln_done) { of.pre_mean = fsm; of.pre_rstd = fsr; of.pre_g = h->fin_g; of.pre_b = h->fin_b; }
     of.no_bias = true;
-    bd.conv(h->fin_conv, x.p, x.C, x.bs(), nullptr, 0, H, W, h->fin_P, (long long)h->out_dim * KHf * H * W,
-            of, false, PC_CONV7);
-    if (x.pf && !bd.rc && bd.still_planes_only(x.p) && (h->ops.empty() || !h->ops.back().on_conv_pf_kernel()))
-        return fail(h, CDC_ERR_UNSUPPORTED, "planes-only final-convolution input without a plane-operand kernel");
+    const size_t first = h->ops.size();
+    bd.conv(h->fin_conv, x, Builder::Out(h->fin_P, (long long)h->out_dim * KHf * H * W), of, false, PC_CONV7);
+    bd.require_planes_reader(x, first, "final-convolution");
     bd.emit(Op(PC_SMALL, CombineArgs{h->fin_P, h->fin_bias, h->out_fx, h->out_dim, KHf, 3, H, W}, 0, 4.0 * B * h->out_dim * (KHf + 1) * H * W));
-    if (bd.rc) return bd.rc;
-    h->pB = B; h->pH = H; h->pW = W;
-    return CDC_OK;
+    return commit_program(h, bd, H, W);
 }
 
 // The tail both encoder programs share: `latent` is the first output; hyper_enc (compress_modules.py:50-55: Conv2d 3x3, then 5x5 /
@@ -1191,7 +1215,7 @@ static int emit_hyper_enc(cdc_handle *h, Builder &bd, Act x, int vbr_base) {
         Act y = bd.new_act(cw.Cout, x.H / s, x.W / s, !site);
         Builder::ConvOpts o;
         if (i < nh - 1 && !site) { o.relu = 1; o.relu_slope = 0.2f; }
-        bd.conv(cw, x.p, x.C, x.bs(), nullptr, 0, x.H, x.W, y.p, y.bs(), o, false, i == 0 ? PC_CONV3 : PC_DOWN);
+        bd.conv(cw, x, y, o, false, i == 0 ? PC_CONV3 : PC_DOWN);
         if (site) bd.vbr(y, h->vbrs[vbr_base + i], true);
         x = y;
         if (bd.rc) return bd.rc;
@@ -1203,51 +1227,48 @@ static int emit_hyper_enc(cdc_handle *h, Builder &bd, Act x, int vbr_base) {
 // Launch program of Compressor.encode up to the quantisers (compress_modules.py:43-51) for images [B][C][H][W].
 int build_encoder_program(cdc_handle *h, int B, int H, int W) {
     if (h->simple) return build_simple_encoder_program(h, B, H, W);
-    if (h->pB == B && h->pH == H && h->pW == W) return CDC_OK;
+    if (program_built(h, B, H, W)) return CDC_OK;
     free_program(h);
     const int n = (int)h->enc_dims.size() - 1, nh = (int)h->henc_dims.size() - 1;
     const int down = 1 << (n + nh - 1);
     if (H % down || W % down)
         return fail(h, CDC_ERR_INVALID, "H=%d, W=%d must be multiples of %d", H, W, down);
     Builder bd{h, B, &h->act_allocs};
-    h->in_x = bd.dalloc((size_t)B * h->enc_dims[0] * H * W);
+    Act x = bd.input(h->enc_dims[0], H, W);
     if (bd.rc) return bd.rc;
-    Act x; x.p = h->in_x; x.C = h->enc_dims[0]; x.H = H; x.W = W;
     // variable bitrate: the ResnetBlock outputs get no PF twin (the affine rewrites the fp32 copy; the Downsample then reads that)
     const bool vbr = h->vbr;
     if (vbr) h->d_rate = bd.dalloc((size_t)B);
     for (int i = 0; i < n; ++i) {
-        x = bd.resblock(h->rbs[i], x, nullptr, false, nullptr, nullptr, vbr ? Builder::SITE_NONE : Builder::SITE_ALWAYS);
+        x = bd.resblock(h->rbs[i], x, nullptr, nullptr, nullptr, vbr ? Builder::SITE_NONE : Builder::SITE_ALWAYS);
         if (vbr) bd.vbr(x, h->vbrs[i], false);
         const ConvW &dw = h->downs[i];
         Act y = bd.new_act(dw.Cout, x.H / 2, x.W / 2);
         Builder::ConvOpts od; od.emit_pf = true;
-        bd.conv(dw, x.p, x.C, x.bs(), nullptr, 0, x.H, x.W, y.p, y.bs(), od, false, PC_DOWN);
+        bd.conv(dw, x, y, od, false, PC_DOWN);
         x = y;
         if (bd.rc) return bd.rc;
     }
     if (int rc = emit_hyper_enc(h, bd, x, n)) return rc;
-    h->pB = B; h->pH = H; h->pW = W;
-    return CDC_OK;
+    return commit_program(h, bd, H, W);
 }
 
 // Launch program of SimpleCompressor.encode up to the quantisers (epsilonparam compress_modules.py:207-217, 43-55): per level
 // Conv2d(5, stride 2, padding 2) and GDN1 (none on the last level), then hyper_enc as in build_encoder_program.
 int build_simple_encoder_program(cdc_handle *h, int B, int H, int W) {
-    if (h->pB == B && h->pH == H && h->pW == W) return CDC_OK;
+    if (program_built(h, B, H, W)) return CDC_OK;
     free_program(h);
     const int n = (int)h->enc_dims.size() - 1, nh = (int)h->henc_dims.size() - 1;
     const int down = 1 << (n + nh - 1);
     if (H % down || W % down)
         return fail(h, CDC_ERR_INVALID, "H=%d, W=%d must be multiples of %d", H, W, down);
     Builder bd{h, B, &h->act_allocs};
-    h->in_x = bd.dalloc((size_t)B * h->enc_dims[0] * H * W);
+    Act x = bd.input(h->enc_dims[0], H, W);
     if (bd.rc) return bd.rc;
-    Act x; x.p = h->in_x; x.C = h->enc_dims[0]; x.H = H; x.W = W;
     for (int i = 0; i < n; ++i) {                   // (fp32 tensors only: the GDN kernel reads and writes no planes)
         const ConvW &dw = h->downs[i];
         Act y = bd.new_act(dw.Cout, x.H / 2, x.W / 2, false);
-        bd.conv(dw, x.p, x.C, x.bs(), nullptr, 0, x.H, x.W, y.p, y.bs(), Builder::ConvOpts(), false, PC_DOWN);
+        bd.conv(dw, x, y, Builder::ConvOpts(), false, PC_DOWN);
         if (i < n - 1) {
             Act g = bd.new_act(y.C, y.H, y.W, false);
             bd.gdn(h->gdns[i], y.p, y.bs(), g.p, g.bs(), y.H * y.W);
@@ -1257,20 +1278,18 @@ int build_simple_encoder_program(cdc_handle *h, int B, int H, int W) {
         if (bd.rc) return bd.rc;
     }
     if (int rc = emit_hyper_enc(h, bd, x, n)) return rc;
-    h->pB = B; h->pH = H; h->pW = W;
-    return CDC_OK;
+    return commit_program(h, bd, H, W);
 }
 
 // Launch program of Compressor.hyper_dec (compress_modules.py:54-60) for q_hyper_latent [B][dims[0]][hh][wh].
 // batch1_plan: every image runs the kernels a batch-1 call would run (the entropy coder's contract, entropy.hip)
 int build_hyperdec_program(cdc_handle *h, int B, int hh, int wh, bool batch1_plan) {
-    if (h->pB == B && h->pH == hh && h->pW == wh && h->p_batch1_plan == batch1_plan) return CDC_OK;
+    if (program_built(h, B, hh, wh, batch1_plan)) return CDC_OK;
     free_program(h);
     Builder bd{h, B, &h->act_allocs};
     if (batch1_plan) bd.planB = 1;
-    h->in_x = bd.dalloc((size_t)B * h->hyper_dims[0] * hh * wh);
+    Act x = bd.input(h->hyper_dims[0], hh, wh);
     if (bd.rc) return bd.rc;
-    Act x; x.p = h->in_x; x.C = h->hyper_dims[0]; x.H = hh; x.W = wh;
     const int n = (int)h->hconvs.size();
     const bool vbr = h->vbr;
     if (vbr) h->d_rate = bd.dalloc((size_t)B);
@@ -1280,63 +1299,58 @@ int build_hyperdec_program(cdc_handle *h, int B, int hh, int wh, bool batch1_pla
         Act y = bd.new_act(cw.Cout, last ? x.H : x.H * 2, last ? x.W : x.W * 2, !site);
         Builder::ConvOpts o;
         if (!last && !site) { o.relu = 1; o.relu_slope = 0.2f; }           // nn.LeakyReLU(0.2)
-        bd.conv(cw, x.p, x.C, x.bs(), nullptr, 0, x.H, x.W, y.p, y.bs(), o, false, last ? PC_CONV3 : PC_UP);
+        bd.conv(cw, x, y, o, false, last ? PC_CONV3 : PC_UP);
         if (site) bd.vbr(y, h->vbrs[i], true);
         x = y;
         if (bd.rc) return bd.rc;
     }
     h->dec_outs.clear();
     h->dec_outs.push_back(x);
-    h->pB = B; h->pH = hh; h->pW = wh;
-    h->p_batch1_plan = batch1_plan;
-    return CDC_OK;
+    return commit_program(h, bd, hh, wh, batch1_plan);
 }
 
 // Launch program of Compressor.decode (compress_modules.py:68-74) for q_latent [B][rev[0]][hl][wl].
 int build_ctxdec_program(cdc_handle *h, int B, int hl, int wl) {
     if (h->simple) return build_simple_ctxdec_program(h, B, hl, wl);
-    if (h->pB == B && h->pH == hl && h->pW == wl) return CDC_OK;
+    if (program_built(h, B, hl, wl)) return CDC_OK;
     free_program(h);
     h->dec_outs.clear();
     Builder bd{h, B, &h->act_allocs};
-    h->in_x = bd.dalloc((size_t)B * h->rev_dims[0] * hl * wl);
+    Act x = bd.input(h->rev_dims[0], hl, wl);
     if (bd.rc) return bd.rc;
-    Act x; x.p = h->in_x; x.C = h->rev_dims[0]; x.H = hl; x.W = wl;
     const int n = (int)h->rev_dims.size() - 1;
     // variable bitrate: as in the encoder, the ResnetBlock outputs get no PF twin, so the Upsample reads the affine's fp32 result
     const bool vbr = h->vbr;
     if (vbr) h->d_rate = bd.dalloc((size_t)B);
     for (int i = 0; i < n; ++i) {
-        x = bd.resblock(h->rbs[i], x, nullptr, false, nullptr, nullptr, vbr ? Builder::SITE_NONE : Builder::SITE_ALWAYS);
+        x = bd.resblock(h->rbs[i], x, nullptr, nullptr, nullptr, vbr ? Builder::SITE_NONE : Builder::SITE_ALWAYS);
         if (vbr) bd.vbr(x, h->vbrs[i], false);
         const ConvW &uw = h->ups[i];
         Act y = bd.new_act(uw.Cout, x.H * 2, x.W * 2);
         Builder::ConvOpts ouu; ouu.emit_pf = true;
-        bd.conv(uw, x.p, x.C, x.bs(), nullptr, 0, x.H, x.W, y.p, y.bs(), ouu, false, PC_UP);
+        bd.conv(uw, x, y, ouu, false, PC_UP);
         x = y;
         h->dec_outs.push_back(y);
         if (bd.rc) return bd.rc;
     }
-    h->pB = B; h->pH = hl; h->pW = wl;
-    return CDC_OK;
+    return commit_program(h, bd, hl, wl);
 }
 
 // Launch program of SimpleCompressor.decode (epsilonparam compress_modules.py:219-229, 74-82) for q_latent [B][rev[0]][hl][wl]: per
 // level ConvTranspose2d(5, stride 2, padding 2, output_padding 1), packed as the hyper decoder's, and inverse GDN1 (none on the last
 // level); every level's result is an output.
 int build_simple_ctxdec_program(cdc_handle *h, int B, int hl, int wl) {
-    if (h->pB == B && h->pH == hl && h->pW == wl) return CDC_OK;
+    if (program_built(h, B, hl, wl)) return CDC_OK;
     free_program(h);
     h->dec_outs.clear();
     Builder bd{h, B, &h->act_allocs};
-    h->in_x = bd.dalloc((size_t)B * h->rev_dims[0] * hl * wl);
+    Act x = bd.input(h->rev_dims[0], hl, wl);
     if (bd.rc) return bd.rc;
-    Act x; x.p = h->in_x; x.C = h->rev_dims[0]; x.H = hl; x.W = wl;
     const int n = (int)h->rev_dims.size() - 1;
     for (int i = 0; i < n; ++i) {
         const ConvW &uw = h->ups[i];
         Act y = bd.new_act(uw.Cout, x.H * 2, x.W * 2, false);
-        bd.conv(uw, x.p, x.C, x.bs(), nullptr, 0, x.H, x.W, y.p, y.bs(), Builder::ConvOpts(), false, PC_UP);
+        bd.conv(uw, x, y, Builder::ConvOpts(), false, PC_UP);
         if (i < n - 1) {
             Act g = bd.new_act(y.C, y.H, y.W, false);
             bd.gdn(h->gdns[i], y.p, y.bs(), g.p, g.bs(), y.H * y.W);
@@ -1346,8 +1360,7 @@ int build_simple_ctxdec_program(cdc_handle *h, int B, int hl, int wl) {
         h->dec_outs.push_back(y);
         if (bd.rc) return bd.rc;
     }
-    h->pB = B; h->pH = hl; h->pW = wl;
-    return CDC_OK;
+    return commit_program(h, bd, hl, wl);
 }
 
 // ---- LPIPS-VGG (cdc_lpips) ---------------------------------------------------------------------------------------------------------
@@ -1379,18 +1392,17 @@ size_t lpips_pair_bytes(int H, int W) {
 // adds the bias, every further slice adds the partial sums of the one before in its epilogue (ConvOpts::pre_add), the last applies
 // the ReLU.  Same flops; the partial planes of these small maps are the only extra traffic.
 int build_lpips_program(cdc_handle *h, int pairs, int H, int W) {
-    if (h->pB >= 2 * pairs && h->pH == H && h->pW == W) return CDC_OK;
+    if (h->pB >= 2 * pairs && h->pH == H && h->pW == W) return CDC_OK;    // (not program_built: a program of more pairs serves)
     free_program(h);
     const int B = 2 * pairs;
     Builder bd{h, B, &h->act_allocs};
     bd.planB = 1;
-    h->in_x = bd.dalloc((size_t)B * 3 * H * W);
+    Act x = bd.input(3, H, W);
     h->lp_res = reinterpret_cast<double *>(bd.dalloc((size_t)pairs * LPIPS_TAPS * 2));
     int max_blocks = 1;                 // one partial per workgroup of the widest head launch
     for (int l = 0; l < LPIPS_TAPS; ++l) max_blocks = std::max(max_blocks, lpips_head_blocks((H >> l) * (W >> l)));
     double *partials = reinterpret_cast<double *>(bd.dalloc((size_t)pairs * max_blocks * 2));
     if (bd.rc) return bd.rc;
-    Act x; x.p = h->in_x; x.C = 3; x.H = H; x.W = W;
     size_t ci = 0;
     int layer = 0;
     float *part[2] = {nullptr, nullptr};    // ping-pong partial sums of the sliced layers
@@ -1415,8 +1427,9 @@ int build_lpips_program(cdc_handle *h, int pairs, int H, int W) {
                 o.relu = last ? 1 : 0;
                 o.no_ksplit = true;             // (slice 0 has a plain bias epilogue: keep it one launch, its memory is budgeted)
                 if (p) { o.pre_add = part[(p - 1) & 1]; o.no_bias = true; }
-                bd.conv(cw, x.p + (size_t)p * cw.Cin * x.H * x.W, cw.Cin, x.bs(), nullptr, 0, x.H, x.W, last ? y.p : part[p & 1], y.bs(), o, false,
-                        PC_CONV3);
+                // (slice p of the input's channels, at the whole tensor's batch stride)
+                const Builder::In slice(x.p + (size_t)p * cw.Cin * x.H * x.W, cw.Cin, x.bs(), x.H, x.W);
+                bd.conv(cw, slice, Builder::Out(last ? y.p : part[p & 1], y.bs()), o, false, PC_CONV3);
                 if (bd.rc) return bd.rc;
             }
             x = y;
@@ -1426,8 +1439,7 @@ int build_lpips_program(cdc_handle *h, int pairs, int H, int W) {
                    2.0 * 4.0 * B * x.C * x.H * x.W));
         if (bd.rc) return bd.rc;
     }
-    h->pB = B; h->pH = H; h->pW = W;
-    return CDC_OK;
+    return commit_program(h, bd, H, W);
 }
 
 
@@ -1485,6 +1497,18 @@ struct OpScope {                 // temporary device pool + op list for the cdc_
 
 int op_ready(cdc_handle *h) { return ensure_device(h); }
 
+// Test aid of the convolution entry points (a silent fallback would test nothing): under CDC_OP_REQUIRE_PF the layer must have been planned
+// on the plane-operand kernel, under CDC_OP_REQUIRE_WS (`ws`: the entry point has that form) on the weight-stationary one of the few-pixel levels.
+int require_kernel(cdc_handle *h, bool ws) {
+    bool on_pf = false, on_ws = false;
+    for (const Op &q : h->ops) { on_pf = on_pf || q.on_conv_pf_kernel(); on_ws = on_ws || q.get<WsConvOp>(); }
+    if (dev_env("CDC_OP_REQUIRE_PF") && !on_pf)
+        return fail(h, CDC_ERR_UNSUPPORTED, "CDC_OP_REQUIRE_PF: the convolution was not planned on conv_pf_kernel");
+    if (ws && dev_env("CDC_OP_REQUIRE_WS") && !on_ws)
+        return fail(h, CDC_ERR_UNSUPPORTED, "CDC_OP_REQUIRE_WS: the convolution was not planned on conv_ws_kernel");
+    return CDC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1517,33 +1541,23 @@ static int op_conv2d_impl(cdc_handle *h, const float *x, const float *w, const f
     Builder::ConvOpts o;
     o.ln_g = dg; o.ln_b = db; o.relu = relu; o.shift = ds;
     o.resid = dr; o.resid_bs = (long long)Cout * Ho * Wo; o.resid_cs = (long long)Ho * Wo;
-    const long long obs = (long long)Cout * Ho * Wo;
+    const Builder::In in(dx, Cin, (long long)Cin * H * W, H, W);
+    const Builder::Out out(dy, (long long)Cout * Ho * Wo);
     const int prof = KH == 7 ? PC_CONV7 : (KH == 1 ? PC_CONV1 : PC_CONV3);
     // few-pixel maps: the weight-stationary kernel (its raw result + the in-place LayerNorm pass; a bias-only call is the raw result)
-    if (dg && relu && stride == 1 && bd.try_ws(cw, dx, Cin, (long long)Cin * H * W, nullptr, 0, H, W, dy, obs, prof)) {
-        bd.ln(dy, dy, Cout, Ho * Wo, dg, db, relu, ds, dr, nullptr, nullptr);
-    } else if (!dg && !relu && !ds && !dr && stride == 1 && bd.try_ws(cw, dx, Cin, (long long)Cin * H * W, nullptr, 0, H, W, dy, obs, prof)) {
+    if (dg && relu && stride == 1 && bd.try_ws(cw, in, out, prof)) {
+        bd.ln(dy, dy, Cout, Ho * Wo, o);
+    } else if (!dg && !relu && !ds && !dr && stride == 1 && bd.try_ws(cw, in, out, prof)) {
     } else if (dg) {
-        if (!bd.conv(cw, dx, Cin, (long long)Cin * H * W, nullptr, 0, H, W, dy, obs, o, true, prof)) {
-            bd.conv(cw, dx, Cin, (long long)Cin * H * W, nullptr, 0, H, W, dy, obs, Builder::ConvOpts(),
-                    false, prof);
-            bd.ln(dy, dy, Cout, Ho * Wo, dg, db, relu, ds, dr, nullptr, nullptr);
+        if (!bd.conv(cw, in, out, o, true, prof)) {
+            bd.conv(cw, in, out, Builder::ConvOpts(), false, prof);
+            bd.ln(dy, dy, Cout, Ho * Wo, o);
         }
     } else {
-        bd.conv(cw, dx, Cin, (long long)Cin * H * W, nullptr, 0, H, W, dy, obs, o, false, prof);
+        bd.conv(cw, in, out, o, false, prof);
     }
     if (bd.rc) return bd.rc;
-    // test aid: the layer must have been planned on the plane-operand kernel (a silent fallback would test nothing)
-    if (dev_env("CDC_OP_REQUIRE_PF")) {
-        bool on_pf = false;
-        for (const Op &q : h->ops) on_pf = on_pf || q.on_conv_pf_kernel();
-        if (!on_pf) return fail(h, CDC_ERR_UNSUPPORTED, "CDC_OP_REQUIRE_PF: the convolution was not planned on conv_pf_kernel");
-    }
-    if (dev_env("CDC_OP_REQUIRE_WS")) {       // ... or on the weight-stationary kernel of the few-pixel levels
-        bool on_ws = false;
-        for (const Op &q : h->ops) on_ws = on_ws || q.get<WsConvOp>();
-        if (!on_ws) return fail(h, CDC_ERR_UNSUPPORTED, "CDC_OP_REQUIRE_WS: the convolution was not planned on conv_ws_kernel");
-    }
+    if ((rc = require_kernel(h, true))) return rc;
     return sc.run(B, y, dy, (size_t)B * Cout * Ho * Wo);
 }
 
@@ -1565,14 +1579,9 @@ static int op_conv_transpose2d_impl(cdc_handle *h, const float *x, const float *
         bd.pack(dx, (long long)Cin * H * W);
     }
     if (bd.rc) return bd.rc;
-    bd.conv(cw, dx, Cin, (long long)Cin * H * W, nullptr, 0, H, W, dy, (long long)Cout * 4 * H * W,
-            Builder::ConvOpts(), false, PC_UP);
+    bd.conv(cw, Builder::In(dx, Cin, (long long)Cin * H * W, H, W), Builder::Out(dy, (long long)Cout * 4 * H * W), Builder::ConvOpts(), false, PC_UP);
     if (bd.rc) return bd.rc;
-    if (dev_env("CDC_OP_REQUIRE_PF")) {       // test aid, see op_conv2d_impl
-        bool on_pf = false;
-        for (const Op &q : h->ops) on_pf = on_pf || q.on_conv_pf_kernel();
-        if (!on_pf) return fail(h, CDC_ERR_UNSUPPORTED, "CDC_OP_REQUIRE_PF: the convolution was not planned on conv_pf_kernel");
-    }
+    if ((rc = require_kernel(h, false))) return rc;
     return sc.run(B, y, dy, ny);
 }
 
@@ -1614,11 +1623,13 @@ static int op_chan_layernorm_impl(cdc_handle *h, const float *x, int nparts, con
     float *dout = bd.dalloc(total);
     if (bd.rc) return bd.rc;
     float *dy = y ? dout : nullptr, *dsm = stats ? dout + ny : nullptr, *dsr = stats ? dout + ny + ns : nullptr;
+    Builder::ConvOpts o;
+    o.ln_g = dg; o.ln_b = db; o.relu = relu; o.shift = ds; o.resid = dr; o.stat_mean = dsm; o.stat_rstd = dsr;
     if (in_place) {
         bd.copy(dx, (long long)C * HW, dy, (long long)C * HW, (long long)C * HW);
-        bd.ln(dy, dy, C, HW, dg, db, relu, ds, dr, dsm, dsr);
+        bd.ln(dy, dy, C, HW, o);
     } else {
-        bd.ln(dx, dy, C, HW, dg, db, relu, ds, dr, dsm, dsr, nparts);
+        bd.ln(dx, dy, C, HW, o, nparts);
     }
     if (bd.rc) return bd.rc;
     if (!stats) return sc.run(B, y, dout, total);
@@ -1687,7 +1698,7 @@ static int op_linear_attention_impl(cdc_handle *h, const float *x, const float *
     if ((rc = sc.up(x, (size_t)B * C * H * W, &ax.p))) return rc;
     float *sm = bd.dalloc((size_t)B * H * W), *sr = bd.dalloc((size_t)B * H * W);
     if (bd.rc) return bd.rc;
-    bd.ln(ax.p, nullptr, C, H * W, nullptr, nullptr, 0, nullptr, nullptr, sm, sr);   // statistics only
+    bd.ln_stats(ax.p, C, H * W, sm, sr);
     Act ay = bd.attention(at, ax, sm, sr);
     if (bd.rc) return bd.rc;
     return sc.run(B, y, ay.p, (size_t)B * C * H * W);
