@@ -298,6 +298,58 @@ class _ContextDecoder:
                                 int(image_hw[0]), int(image_hw[1]), args[0].mem, _current_stream(args[0].mem)))
         return out
 
+    RATE_MAPS = {"latent": 0, "hyper": 1, "cell": 2, "latent_channels": 3, "hyper_channels": 4}     # name -> output slot of cdc_rate_map
+
+    @property
+    def hyper_upsampling(self):
+        """Latent positions per hyper-latent position and side (U; 4 as published): one stride-2 ConvTranspose2d per hyper_dec layer
+        but the last."""
+        return 2 ** (len(self.reversed_hyper_dims) - 2)
+
+    @property
+    def rate_map_cell(self):
+        """Image pixels per latent position and side: the cell of the maps of `rate_map` / `forward(return_rate_map=True)` (16 as
+        published)."""
+        return self.frame_multiple // self.hyper_upsampling
+
+    @classmethod
+    def _rate_map_names(cls, what):
+        """The argument rule of rate_map's `what`, checked before the library is touched -> tuple of names."""
+        names = (what,) if isinstance(what, str) else tuple(what)
+        bad = [n for n in names if n not in cls.RATE_MAPS]
+        if bad or not names:
+            raise ValueError(f"rate_map: what={what!r}: names among {tuple(cls.RATE_MAPS)}")
+        return names
+
+    def rate_map(self, q_hyper_latent, q_latent, mean, scale, what=("cell",)):
+        """Where the bits of `rate()` went (cdc_rate_map; the header states the sums): a dict of float32 maps in bits with the entries
+        of `what` among "latent" [B, U h, U w] (the Gaussian prices summed over the channels), "hyper" [B, h, w] (the prior prices
+        likewise), "cell" [B, U h, U w] (latent + hyper / U^2 of the position above: the whole rate on the latent grid, one entry per
+        `rate_map_cell` x `rate_map_cell` pixels of the padded frame), "latent_channels" [B, CL] and "hyper_channels" [B, CH] (the
+        prices summed over the positions).  NumPy arrays or torch tensors, following the inputs, as `rate()`; the same shape checks."""
+        names = self._rate_map_names(what)
+        L, h = _lib.lib(), self._hyper_handle()
+        if not (self._hyper_finalized and self._prior_loaded):
+            raise _lib.CdcError("the prior.* tensors have not been loaded (load_state_dict with the full state_dict)")
+        args = [_Arg(t, self.device_index) for t in (q_hyper_latent, q_latent, mean, scale)]
+        if len({a.mem for a in args}) != 1:
+            raise _lib.CdcError("all inputs must live in the same memory")
+        B, CH, hh, wh = args[0].shape
+        up, CL = self.hyper_upsampling, self.reversed_hyper_dims[-1] // 2
+        if CH != self.reversed_hyper_dims[0]:
+            raise _lib.CdcError(f"q_hyper_latent has {CH} channels, the prior expects {self.reversed_hyper_dims[0]}")
+        if args[1].shape != (B, CL, up * hh, up * wh) or args[2].shape != args[1].shape or args[3].shape != args[1].shape:
+            raise _lib.CdcError(f"latent shapes {args[1].shape} do not belong to a {args[0].shape} hyper latent")
+        shapes = {"latent": (B, up * hh, up * wh), "hyper": (B, hh, wh), "cell": (B, up * hh, up * wh), "latent_channels": (B, CL),
+                  "hyper_channels": (B, CH)}
+        out, ptrs = {}, [None] * 5
+        for n in names:
+            if n not in out:
+                out[n], ptrs[self.RATE_MAPS[n]], _ = _result_like(q_hyper_latent, shapes[n], self.device_index)
+        _lib.check(h, L.cdc_rate_map(h, args[0].ptr, args[1].ptr, args[2].ptr, args[3].ptr, *ptrs, B, hh, wh, args[0].mem,
+                                     _current_stream(args[0].mem)))
+        return out
+
     def bpp(self, shape, state4bpp):
         """Compressor.bpp (compress_modules.py:76-90) in eval mode: quantise with the medians / the predicted
         mean, then the rate of both latents."""
@@ -429,13 +481,15 @@ class _ContextDecoder:
         return [raw[offs[b]: offs[b + 1]] for b in range(B)]
 
     def decompress_from_bytes(self, streams, like=None, return_hyper=False, max_image_hw=None, return_bitrate_scale=False,
-                              return_image_size=False):
+                              return_image_size=False, return_rate_map=False):
         """list of B bitstreams -> q_latent [B, C, h, w] exactly as the encoder dequantised it (numpy, or a tensor on
         `like`'s device); all streams must have the same latent size.  max_image_hw=(H, W): refuse streams whose header
         describes a larger image before anything is allocated (untrusted input; default: the library's 2^22-position bound).
         return_bitrate_scale: also return the float32 [B] rates the streams of a VBR model carry (None for a fixed-rate model);
         `decode(q_latent, rates)` then gives the context pyramid.  return_image_size: also return (H, W), the size the streams
-        record (version 5 / 6) or, for version 3 / 4, the coded extent; q_latent is that of the padded frame either way."""
+        record (version 5 / 6) or, for version 3 / 4, the coded extent; q_latent is that of the padded frame either way.
+        return_rate_map: also return, last, `rate_map(...)["cell"]` of the decoded symbols, [B, U h, U w]: where the streams' bits
+        went, without the original (the decoder holds the symbols, and runs hyper_decode once more for their mean and scale)."""
         L, h = _lib.lib(), self._hyper_handle()
         # the limit is handle state in the library: set it on EVERY call (None -> the library's default bound), so that one
         # restricted call does not restrict the next; the product is clamped before it is handed over as a C int
@@ -479,6 +533,9 @@ class _ContextDecoder:
             if len(sizes) != 1:
                 raise _lib.CdcError("the streams of one call must share the image size")
             out = out + (sizes.pop(),)
+        if return_rate_map:
+            mean, scale = self.hyper_decode(qh, cond=self.bitrate_scale_of(streams) if self.vbr else None)
+            out = out + (self.rate_map(qh, q, mean, scale, ("cell",))["cell"],)
         return out if len(out) > 1 else out[0]
 
     @staticmethod
@@ -511,13 +568,19 @@ class _ContextDecoder:
             out[b] = r.value
         return out
 
-    def forward(self, input, cond=None, padded_hw=None):
+    def forward(self, input, cond=None, padded_hw=None, return_rate_map=False):
         """Compressor.forward (compress_modules.py:92-103).  Images of any size (float32 / uint8): "output" (the context pyramid the
-        U-Net consumes), "q_latent" and "q_hyper_latent" are those of the PADDED frame, "bpp" counts bits over the original H * W."""
+        U-Net consumes), "q_latent" and "q_hyper_latent" are those of the PADDED frame, "bpp" counts bits over the original H * W.
+        return_rate_map: also "rate_map", `rate_map(...)["cell"]` of the padded frame, [B, Hp / c, Wp / c] in bits with
+        c = `rate_map_cell`; its sum over an image is bpp * H * W."""
         shape = frame.image_shape(input)
         q_latent, q_hyper_latent, state4bpp = self.encode(input, cond, padded_hw)
-        return {"output": self.decode(q_latent, cond), "bpp": self.bpp(shape, state4bpp), "q_latent": q_latent,
-                "q_hyper_latent": q_hyper_latent}
+        out = {"output": self.decode(q_latent, cond), "bpp": self.bpp(shape, state4bpp), "q_latent": q_latent,
+               "q_hyper_latent": q_hyper_latent}
+        if return_rate_map:
+            dist = state4bpp["latent_distribution"]
+            out["rate_map"] = self.rate_map(q_hyper_latent, q_latent, dist.mean, dist.scale, ("cell",))["cell"]
+        return out
 
     __call__ = forward
 

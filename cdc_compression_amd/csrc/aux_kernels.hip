@@ -6,6 +6,7 @@
 #include <stdlib.h>
 
 #include "cdc_internal.h"
+#include "rate_terms.h"
 
 namespace cdc {
 
@@ -1450,22 +1451,7 @@ __global__ void __launch_bounds__(256) copy_kernel(const float *src, long long s
 //   cond_rate  = -log2 NormalDistribution(mean, scale).likelihood(q_latent)   (utils.py:147-159)
 //   bpp[b] = (sum hyper_rate + sum cond_rate) / (H * W)
 // One workgroup per image; per-thread partial sums in double, fixed-order tree reduction (deterministic).
-__device__ __forceinline__ float prior_logit(const float *p, float x) {
-    float h[3], g[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { h[k] = x * p[k] + p[3 + k]; h[k] += p[6 + k] * tanhf(h[k]); }
-    p += 9;
-#pragma unroll
-    for (int l = 0; l < 2; ++l) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) g[j] = h[0] * p[j] + h[1] * p[3 + j] + h[2] * p[6 + j] + p[9 + j];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) h[j] = g[j] + p[12 + j] * tanhf(g[j]);
-        p += 15;
-    }
-    return h[0] * p[0] + h[1] * p[1] + h[2] * p[2] + p[3];
-}
-
+// The price of one symbol is rate_terms.h (cdc_rate_map sums the same values along the other axes).
 __global__ void __launch_bounds__(256) bpp_kernel(const float *qh, long long nh, int hw_h, const float *prior,
                                                   const float *ql, const float *mean, const float *scale,
                                                   long long nl, float inv_hw, float *bpp) {
@@ -1474,21 +1460,13 @@ __global__ void __launch_bounds__(256) bpp_kernel(const float *qh, long long nh,
     double acc = 0.0;
     const float *xh = qh + (size_t)b * nh;
     for (long long i = threadIdx.x; i < nh; i += blockDim.x) {
-        const float *p = prior + (size_t)(i / hw_h) * 44;
+        const float *p = prior + (size_t)(i / hw_h) * PRIOR_FLOATS;
         const float x = xh[i];
         const float lower = prior_logit(p, x - 0.5f), upper = prior_logit(p, x + 0.5f);
-        const float t = lower + upper;
-        const float sgn = t > 0.f ? -1.f : (t < 0.f ? 1.f : 0.f);            // -torch.sign(lower + upper)
-        const float su = 1.f / (1.f + expf(-upper * sgn)), sl = 1.f / (1.f + expf(-lower * sgn));
-        acc -= (double)log2f(fmaxf(fabsf(su - sl), 1e-9f));
+        acc += (double)hyper_logits_bits(lower, upper);
     }
     const float *xl = ql + (size_t)b * nl, *mu = mean + (size_t)b * nl, *sc = scale + (size_t)b * nl;
-    for (long long i = threadIdx.x; i < nl; i += blockDim.x) {
-        const float d = fabsf(xl[i] - mu[i]), s = sc[i];
-        const float c = -0.70710678118654752440f;                            // -(2 ** -0.5)
-        const float upper = 0.5f * erfcf(c * ((0.5f - d) / s)), lower = 0.5f * erfcf(c * ((-0.5f - d) / s));
-        acc -= (double)log2f(fmaxf(upper - lower, 1e-9f));
-    }
+    for (long long i = threadIdx.x; i < nl; i += blockDim.x) acc += (double)latent_symbol_bits(xl[i], mu[i], sc[i]);
     red[threadIdx.x] = acc;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {

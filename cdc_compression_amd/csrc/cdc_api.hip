@@ -314,6 +314,7 @@ void cdc_destroy(cdc_handle *h) {
     h->d_rep_stage.release();
     h->picks.dev.release();
     if (h->metric_work) (void)hipFree(h->metric_work);
+    if (h->map_work) (void)hipFree(h->map_work);
     if (h->trace_buf) (void)hipFree(h->trace_buf);
     (void)resolve_pending(h);
     for (hipEvent_t e : h->ev_free) (void)hipEventDestroy(e);
@@ -633,6 +634,92 @@ int cdc_distortion(cdc_handle *h, const cdc_image_view *a, const cdc_image_view 
                 if (components) memcpy(components, res.data() + 2 * (size_t)B, sizeof(double) * B * METRIC_SCALES * 3);
             }
             return CDC_OK;
+        });
+    });
+}
+
+// ---- rate and error maps (map_kernels.hip) ----------------------------------------------------------------------------------------------
+namespace {
+// The handle's map work area, at least `bytes`.  A device-memory call need not have synchronised: wait before the old area goes.
+int map_work_area(cdc_handle *h, const char *what, size_t bytes) {
+    if (bytes <= h->map_cap) return CDC_OK;
+    HIP_TRY(h, hipDeviceSynchronize());
+    if (h->map_work) { (void)hipFree(h->map_work); h->map_work = nullptr; h->map_cap = 0; }
+    if (hipMalloc(&h->map_work, bytes) != hipSuccess) { h->map_work = nullptr; return fail(h, CDC_ERR_NOMEM, "%s: hipMalloc of %zu bytes failed", what, bytes); }
+    h->map_cap = bytes;
+    return CDC_OK;
+}
+inline size_t map_up16(size_t n) { return (n + 15) & ~(size_t)15; }
+}  // namespace
+
+int cdc_rate_map(cdc_handle *h, const float *q_hyper_latent, const float *q_latent, const float *mean, const float *scale,
+                 float *latent_bits, float *hyper_bits, float *cell_bits, float *latent_channel_bits, float *hyper_channel_bits,
+                 int B, int hh, int wh, int mem, void *stream) {
+    if (!h) return CDC_ERR_INVALID;
+    return no_throw(h, [&] {
+        return with_range_guard(h, [&]() -> int {
+            int rc = check_ready(h);
+            if (rc) return rc;
+            if ((rc = require_kind(h, HandleKind::HyperDecoder))) return rc;
+            if (!h->d_prior) return fail(h, CDC_ERR_STATE, "the prior.* tensors were not loaded");
+            if (!q_hyper_latent || !q_latent || !mean || !scale) return fail(h, CDC_ERR_INVALID, "rate_map: null input");
+            if (B < 1 || hh < 1 || wh < 1) return fail(h, CDC_ERR_INVALID, "rate_map: B=%d h_hyper=%d w_hyper=%d (all must be >= 1)", B, hh, wh);
+            if (mem != CDC_MEM_HOST && mem != CDC_MEM_DEVICE) return fail(h, CDC_ERR_INVALID, "rate_map: mem_kind %d", mem);
+            float *outs[5] = {latent_bits, hyper_bits, cell_bits, latent_channel_bits, hyper_channel_bits};
+            if (!outs[0] && !outs[1] && !outs[2] && !outs[3] && !outs[4]) return fail(h, CDC_ERR_INVALID, "rate_map: no output requested (all five are NULL)");
+            const int Ch = h->hyper_dims[0], Cl = h->hyper_dims.back() / 2, U = 1 << ((int)h->hyper_dims.size() - 2);   // as cdc_bpp
+            RateMapLayout L;
+            if (!rate_map_layout(B, Ch, Cl, hh, wh, U, &L)) return fail(h, CDC_ERR_INVALID, "rate_map: B=%d, a %d x %d hyper latent is beyond the launch limits", B, hh, wh);
+            const size_t nh = (size_t)hh * wh, nl = nh * U * U;
+            const size_t elems[5] = {B * nl, B * nh, B * nl, (size_t)B * Cl, (size_t)B * Ch};
+            size_t off[5], total = L.bytes;
+            for (int i = 0; i < 5; ++i) { off[i] = total; if (mem == CDC_MEM_HOST && outs[i]) total += map_up16(sizeof(float) * elems[i]); }
+            if ((rc = map_work_area(h, "rate_map", total))) return rc;
+            hipStream_t st = pick_stream(h, stream, mem);
+            Staging s(h, mem, st);
+            const float *dqh = s.in(q_hyper_latent, sizeof(float) * B * Ch * nh), *dql = s.in(q_latent, sizeof(float) * B * Cl * nl),
+                        *dm = s.in(mean, sizeof(float) * B * Cl * nl), *ds = s.in(scale, sizeof(float) * B * Cl * nl);
+            float *d[5];
+            for (int i = 0; i < 5; ++i)
+                d[i] = outs[i] ? s.out(outs[i], sizeof(float) * elems[i], mem == CDC_MEM_HOST ? (char *)h->map_work + off[i] : nullptr) : nullptr;
+            const RateMapOut o = {d[0], d[1], d[2], d[3], d[4]};
+            if (s.ok()) s.e = rate_map_launch(dqh, dql, dm, ds, h->d_prior, B, Ch, Cl, hh, wh, U, L, h->map_work, o, st);
+            return s.finish("rate_map");
+        });
+    });
+}
+
+int cdc_distortion_map(cdc_handle *h, const cdc_image_view *a, const cdc_image_view *b, int B, int H, int W, int cell, int gh, int gw,
+                       double *sse, int32_t *count, int mem, void *stream) {
+    if (!h) return CDC_ERR_INVALID;
+    return no_throw(h, [&] {
+        return with_range_guard(h, [&]() -> int {
+            int rc = ensure_device(h);
+            if (rc) return rc;
+            if (!a || !b || !a->data || !b->data) return fail(h, CDC_ERR_INVALID, "distortion_map: null operand");
+            if (!sse) return fail(h, CDC_ERR_INVALID, "distortion_map: no sse array");
+            if (B < 1 || H < 1 || W < 1) return fail(h, CDC_ERR_INVALID, "distortion_map: B=%d H=%d W=%d (all must be >= 1)", B, H, W);
+            if (cell < 1) return fail(h, CDC_ERR_INVALID, "distortion_map: cell = %d (must be >= 1)", cell);
+            if (gh < 1 || gw < 1 || (long long)gh * cell < H || (long long)gw * cell < W)
+                return fail(h, CDC_ERR_INVALID, "distortion_map: a %d x %d grid of %d-pixel cells does not cover the %d x %d window", gh, gw, cell, H, W);
+            if (mem != CDC_MEM_HOST && mem != CDC_MEM_DEVICE) return fail(h, CDC_ERR_INVALID, "distortion_map: mem_kind %d", mem);
+            MetricView mv[2];
+            size_t bytes[2];
+            if ((rc = image_operand(h, "distortion_map", *a, 'a', B, H, W, &mv[0], &bytes[0]))) return rc;
+            if ((rc = image_operand(h, "distortion_map", *b, 'b', B, H, W, &mv[1], &bytes[1]))) return rc;
+            const long long cells = (long long)B * gh * gw;
+            if (cells > (1ll << 31) || 3ll * std::min(cell, H) * std::min(cell, W) > (1ll << 30))
+                return fail(h, CDC_ERR_INVALID, "distortion_map: B=%d, a %d x %d grid of %d-pixel cells is beyond the launch limits", B, gh, gw, cell);
+            const size_t sse_bytes = map_up16(sizeof(double) * cells), cnt_bytes = map_up16(sizeof(int32_t) * cells);
+            if (mem == CDC_MEM_HOST && (rc = map_work_area(h, "distortion_map", sse_bytes + cnt_bytes))) return rc;
+            hipStream_t st = pick_stream(h, stream, mem);
+            Staging s(h, mem, st);
+            for (int i = 0; i < 2; ++i) mv[i].data = s.in(mv[i].data, bytes[i]);
+            char *stage = mem == CDC_MEM_HOST ? (char *)h->map_work : nullptr;      // (device memory: the results are written in place)
+            double *dsse = s.out(sse, sizeof(double) * cells, stage);
+            int32_t *dcnt = count ? s.out(count, sizeof(int32_t) * cells, stage ? stage + sse_bytes : nullptr) : nullptr;
+            if (s.ok()) s.e = sse_map_launch(mv[0], mv[1], B, H, W, cell, gh, gw, dsse, dcnt, st);
+            return s.finish("distortion_map");
         });
     });
 }

@@ -340,6 +340,19 @@ int metric_next_side(int s);                                       // side of th
 bool metric_layout(int B, int H, int W, bool psnr, bool msssim, MetricLayout *L);   // false: too small for five scales, or too many tiles
 hipError_t metric_psnr_launch(const MetricView &a, const MetricView &b, int B, int H, int W, const MetricLayout &L, void *work, hipStream_t st);
 hipError_t metric_msssim_launch(const MetricView &a, const MetricView &b, int B, const MetricLayout &L, void *work, hipStream_t st);
+// map_kernels.hip (cdc_rate_map, cdc_distortion_map): the prices of rate_terms.h summed per position and per channel; squared error per
+// cell of a grid over the window.  Index 0: the hyper grid [CH][hh][wh], 1: the latent grid [CL][U hh][U wh].
+struct RateMapLayout {                                             // launch shapes and the device work area (byte offsets), functions of the shapes alone
+    int P[2] = {}, logP[2] = {}, Cg[2] = {}, tiles[2] = {};        // positions per workgroup, channels per thread, workgroups per image
+    size_t bytes = 0, hyper_sum_off = 0, part_off[2] = {};         // doubles: hyper position sums [B][hh wh] | channel partials [B][C][tiles] of each grid
+};
+struct RateMapOut { float *latent, *hyper, *cell, *latent_channels, *hyper_channels; };   // device pointers, each may be null
+bool rate_map_layout(int B, int CH, int CL, int hh, int wh, int U, RateMapLayout *L);     // false: beyond the launch limits
+hipError_t rate_map_launch(const float *qh, const float *ql, const float *mean, const float *scale, const float *prior, int B, int CH,
+                           int CL, int hh, int wh, int U, const RateMapLayout &L, void *work, const RateMapOut &o, hipStream_t st);
+// sse [B][gh][gw] (double), count [B][gh][gw] (or null) over cells of `cell` pixels a side; 3 * min(cell, H) * min(cell, W) < 2^31
+hipError_t sse_map_launch(const MetricView &a, const MetricView &b, int B, int H, int W, int cell, int gh, int gw, double *sse,
+                          int32_t *count, hipStream_t st);
 // lpips_kernels.hip (cdc_lpips): what LPIPS-VGG needs beside the planner's convolutions.  Operands as MetricView (device pointers).
 constexpr int LPIPS_TAPS = 5;
 // both operands' H x W windows -> out [2 n][3][H][W]: (2 u - 1 - shift[c]) / scale[c], operand a in rows 0 .. n-1, b in rows n .. 2n-1

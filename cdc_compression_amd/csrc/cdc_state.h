@@ -322,6 +322,10 @@ struct cdc_handle {
     // CDC_ERR_NOMEM with a text of its own, and no graph or queued work holds it)
     void *metric_work = nullptr;
     size_t metric_cap = 0;
+    // cdc_rate_map / cdc_distortion_map: the work area of map_kernels.hip and, for host results, the maps on their way out; grown on
+    // demand like metric_work
+    void *map_work = nullptr;
+    size_t map_cap = 0;
     // decode trajectory (cdc_set_trace): the request, and the recording of the last traced decode.  trace_buf holds the x0 slots, then
     // the x_t slots, tr_slots of tr_slot_bytes each, in execution order (no GrowBuf: its failure is CDC_ERR_NOMEM with the sizes in the
     // text, and no graph reads it -- a traced decode runs the eager loop).
@@ -478,7 +482,7 @@ struct Staging {
     DevPool pool;
     hipError_t e = hipSuccess;    // the first HIP error: the caller stores its launches' here (`if (s.ok()) s.e = ..._launch(...)`)
     bool nomem = false;           // a scratch allocation failed
-    struct Back { void *host; const void *dev; size_t bytes; } backs[4];   // results to copy to the host in finish()
+    struct Back { void *host; const void *dev; size_t bytes; } backs[8];   // results to copy to the host in finish()
     int n_backs = 0;
     bool host_results = false;    // finish() synchronises for a device-memory call too
     Staging(cdc_handle *h_, int mem_, hipStream_t st_) : h(h_), mem(mem_), st(st_) {}

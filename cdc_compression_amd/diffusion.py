@@ -136,12 +136,17 @@ class _GaussianDiffusionBase:
                                            optr, omem, _current_stream(omem)))
         return out
 
-    def _context_of(self, images, *ctx_args):
-        """The context model on the padded frame of `images` -> (context_dict with bpp over H * W, B, H, W, Hp, Wp)."""
+    def _context_of(self, images, *ctx_args, rate_map=False):
+        """The context model on the padded frame of `images` -> (context_dict with bpp over H * W, B, H, W, Hp, Wp).  rate_map: the
+        dict also holds "rate_map" (this package's compressors only)."""
         B, _, H, W = frame.image_shape(images)
         Hp, Wp = self.padded_size(H, W)
         h, dev = self.denoise_fn._handle(), self.denoise_fn.device_index
-        if hasattr(self.context_fn, "_framed"):              # this package's compressor: pads itself, bpp over H * W
+        if rate_map and not hasattr(self.context_fn, "rate_map"):
+            raise ValueError("maps=True needs a context model with rate_map() (a compressor of this package)")
+        if rate_map:
+            context_dict = self.context_fn(images, *ctx_args, padded_hw=(Hp, Wp), return_rate_map=True)
+        elif hasattr(self.context_fn, "_framed"):            # this package's compressor: pads itself, bpp over H * W
             context_dict = self.context_fn(images, *ctx_args, padded_hw=(Hp, Wp))        # x :216, eps :205
         elif (Hp, Wp) == (H, W) and not frame.is_uint8(images):
             context_dict = self.context_fn(images, *ctx_args)
@@ -150,17 +155,20 @@ class _GaussianDiffusionBase:
             context_dict["bpp"] = context_dict["bpp"] * ((Hp * Wp) / (H * W))
         return context_dict, B, H, W, Hp, Wp
 
-    def _compress_frame(self, images, sample_steps, init, eta, loop, *ctx_args, sampler="ddim", spacing="index", trace=None):
+    def _compress_frame(self, images, sample_steps, init, eta, loop, *ctx_args, sampler="ddim", spacing="index", trace=None,
+                        rate_map=False):
         """compress() of both trees up to the crop: context model and sampler on the padded frame -> (frame, bpp [B], H, W, Trajectory
-        or None).  trace: (trajectory, trajectory_of, trajectory_dtype, seed) of the call; loop(shape, context, init, spec, window)."""
+        or None), and the context model's rate map of the frame as a sixth entry with rate_map=True.  trace: (trajectory,
+        trajectory_of, trajectory_dtype, seed) of the call; loop(shape, context, init, spec, window)."""
         self._sampler_args(sampler, eta)
         spec = None if trace is None else self._trace_spec(*trace[:3], self._steps(sample_steps, spacing), eta, trace[3])
-        context_dict, B, H, W, Hp, Wp = self._context_of(images, *ctx_args)
+        context_dict, B, H, W, Hp, Wp = self._context_of(images, *ctx_args, rate_map=rate_map)
         h, dev = self.denoise_fn._handle(), self.denoise_fn.device_index
         self.set_sample_schedule(self._steps(sample_steps, spacing), sampler=sampler, spacing=spacing)
         rec = loop((B, 3, Hp, Wp), context_dict["output"], frame.extend_init(h, init, B, H, W, Hp, Wp, dev), spec, (H, W))
         rec, traj = rec if spec is not None else (rec, None)
-        return rec, context_dict["bpp"], H, W, traj
+        res = (rec, context_dict["bpp"], H, W, traj)
+        return res + (context_dict["rate_map"],) if rate_map else res
 
     def _window(self, rec, H, W):
         """The reconstruction compress() returns: the frame's top-left H x W window (the frame itself when it is the image)."""
@@ -168,20 +176,31 @@ class _GaussianDiffusionBase:
             rec = frame.crop(self.denoise_fn._handle(), rec, H, W, self.denoise_fn.device_index)
         return rec
 
-    def evaluate(self, images, *args, as_saved=True, **kwargs):
+    def evaluate(self, images, *args, as_saved=True, maps=False, **kwargs):
         """compress() with the other axis of the rate-distortion plot: takes compress()'s arguments, runs its path once and returns
         {"reconstruction": what compress() returns, "bpp": [B], "psnr": float64 [B], "ms_ssim": float64 [B], or None when
         min(H, W) <= 160}, and "lpips": float64 [B] when the loaded state dict carried the LPIPS-VGG weights (self.loss_fn_vgg).
         The distortion is measured on the device (cdc_compression_amd.metrics), on the padded frame's H x W window
         against `images` as given (float32 or uint8); as_saved: float32 operands through the uint8 image the reference's script would
-        save (metrics.psnr(model, reconstruction, images, as_saved=True) gives the same figures)."""
+        save (metrics.psnr(model, reconstruction, images, as_saved=True) gives the same figures).
+        maps=True: where the bits went and where the error remains, on one grid of "map_cell" x "map_cell" pixels (the context model's
+        rate_map_cell) over the padded frame: "rate_map" float32 [B, gh, gw] in bits (its sum is bpp * H * W), "sse_map" float64 and
+        "sse_count" int32 of the same shape (metrics.sse_map of the reconstruction against `images` under as_saved: sum(sse) /
+        sum(count) is the MSE of "psnr"; the cells of the padding beyond the window have count 0)."""
         from . import metrics
         import inspect
         bound = dict(inspect.signature(self.compress).bind(images, *args, **kwargs).arguments)
         bound.pop("bpp_return_mean", None)                    # bpp comes per image
-        rec, bpp, H, W, traj = self._frame_of(**bound)
+        if maps:
+            rec, bpp, H, W, traj, rate_map = self._frame_of(**bound, rate_map=True)
+        else:
+            rec, bpp, H, W, traj = self._frame_of(**bound)
         ps, ms = metrics.distortion(self.denoise_fn, rec, images, size=(H, W), as_saved=as_saved)
         out = {"reconstruction": self._window(rec, H, W), "bpp": bpp, "psnr": ps, "ms_ssim": ms}
+        if maps:
+            cell = self.context_fn.rate_map_cell
+            sse, count = metrics.sse_map(self.denoise_fn, rec, images, cell, size=(H, W), as_saved=as_saved, grid=tuple(rate_map.shape[1:]))
+            out.update({"rate_map": rate_map, "sse_map": sse, "sse_count": count, "map_cell": cell})
         if self.loss_fn_vgg is not None:
             out["lpips"] = metrics.lpips(self.loss_fn_vgg, rec, images, size=(H, W), as_saved=as_saved)
         if traj is not None:
@@ -539,13 +558,14 @@ class GaussianDiffusionX(_GaussianDiffusionBase):
         return self._loop(tuple(shape), context, clip_denoised, init, eta, seed, gamma, sampler, spec, window)
 
     def _frame_of(self, images, sample_steps=None, init=None, eta=0, seed=None, gamma=None, sampler="ddim", spacing="index",
-                  trajectory=None, trajectory_of="x0", trajectory_dtype="float32"):
+                  trajectory=None, trajectory_of="x0", trajectory_dtype="float32", rate_map=False):
         self._seed_args(seed, gamma, init, frame.image_shape(images)[0])
         return self._compress_frame(images, sample_steps, init, eta,
                                     lambda shape, ctx, i, spec, win: self.p_sample_loop(shape, ctx, clip_denoised=True, init=i, eta=eta,
                                                                                         seed=seed, gamma=gamma, trajectory=spec,
                                                                                         window=win),   # :223
-                                    sampler=sampler, spacing=spacing, trace=(trajectory, trajectory_of, trajectory_dtype, seed))
+                                    sampler=sampler, spacing=spacing, trace=(trajectory, trajectory_of, trajectory_dtype, seed),
+                                    rate_map=rate_map)
 
     def compress(self, images, sample_steps=None, bpp_return_mean=True, init=None, eta=0, seed=None, gamma=None, sampler="ddim",
                  spacing="index", trajectory=None, trajectory_of="x0", trajectory_dtype="float32"):
@@ -592,13 +612,13 @@ class GaussianDiffusionEps(_GaussianDiffusionBase):
         return self._loop(tuple(shape), context, self.clip_noise, init, eta, seed, gamma, sampler, spec, window)
 
     def _frame_of(self, images, sample_steps=None, bitrate_scale=None, sample_mode="ddpm", init=None, eta=0, seed=None, gamma=None,
-                  sampler="ddim", spacing="index", trajectory=None, trajectory_of="x0", trajectory_dtype="float32"):
+                  sampler="ddim", spacing="index", trajectory=None, trajectory_of="x0", trajectory_dtype="float32", rate_map=False):
         self._seed_args(seed, gamma, init, frame.image_shape(images)[0])
         return self._compress_frame(images, sample_steps, init, eta,
                                     lambda shape, ctx, i, spec, win: self.p_sample_loop(shape, ctx, sample_mode, init=i, eta=eta, seed=seed,
                                                                                         gamma=gamma, trajectory=spec, window=win),
                                     bitrate_scale, sampler=sampler, spacing=spacing,
-                                    trace=(trajectory, trajectory_of, trajectory_dtype, seed))
+                                    trace=(trajectory, trajectory_of, trajectory_dtype, seed), rate_map=rate_map)
 
     def compress(self, images, sample_steps=None, bitrate_scale=None, sample_mode="ddpm",
                  bpp_return_mean=True, init=None, eta=0, seed=None, gamma=None, sampler="ddim", spacing="index",

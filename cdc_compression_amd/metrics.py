@@ -5,6 +5,7 @@ operands' common shape), so a padded decoder frame is measured beside the image 
 are numpy, torch-cpu or torch-cuda tensors, float32 (in [-1, 1], mapped as `clamp(-1, 1) / 2 + 0.5`) or uint8 (`v / 255`);
 `as_saved=True` measures a float32 operand through the uint8 image the reference's script would save.  The header states the
 definition (PSNR: the reference's per-image `batch_psnr`; MS-SSIM: the conventions of pytorch-msssim 0.2.1, `data_range=1`).
+`sse_map` is the squared error per cell of a grid over the window (cdc_distortion_map), the picture beside a compressor's `rate_map`.
 `lpips` is the third axis: LPIPS-VGG of lpips 0.1.4 on the same operands (cdc_lpips; the model is an `lpips.LpipsVGG`, which holds
 the network's weights).  Results are float64 NumPy arrays of `B` values."""
 import ctypes
@@ -103,6 +104,44 @@ def distortion(model, a, b, size=None, as_saved=False):
         return psnr(model, a, b, size, as_saved), None
     ps, ms, _ = _distortion(model, a, b, size, as_saved, _lib.CDC_METRIC_PSNR | _lib.CDC_METRIC_MSSSIM)
     return ps, ms
+
+
+def _check_grid(H, W, cell, grid):
+    """The argument rules of sse_map's cell and grid, checked before the library is touched -> (cell, gh, gw)."""
+    if isinstance(cell, bool) or int(cell) != cell or int(cell) < 1:
+        raise ValueError(f"cell must be an integer >= 1, got {cell!r}")
+    cell = int(cell)
+    if grid is None:
+        return cell, -(-H // cell), -(-W // cell)
+    gh, gw = (int(g) for g in grid)
+    if gh < 1 or gw < 1 or gh * cell < H or gw * cell < W:
+        raise ValueError(f"a {gh} x {gw} grid of {cell}-pixel cells does not cover the {H} x {W} window")
+    return cell, gh, gw
+
+
+def sse_map(model, a, b, cell, size=None, as_saved=False, grid=None):
+    """Where the error remains (cdc_distortion_map): (sse float64 [B, gh, gw], count int32 [B, gh, gw]) over cells of cell x cell
+    pixels anchored at the window's top-left pixel.  sse: the sum of (a - b)^2 over the three channels and the cell's pixels inside
+    the window, operands and window as for `psnr`; count: 3 x those pixels, 0 for a cell beyond the window.  grid=(gh, gw): default
+    ceil(H / cell) x ceil(W / cell); a larger one (the rate map's, of the padded frame) gets zero cells.  sse.sum() / count.sum()
+    over an image is the MSE of `psnr`; two byte operands give exact sums."""
+    B, H, W, saved = _check_args(a, b, size, as_saved)
+    cell, gh, gw = _check_grid(H, W, cell, grid)
+    h, dev = model._handle(), model.device_index
+    args, views = _views(a, b, saved, dev)
+    sse, count = np.empty((B, gh, gw), np.float64), np.empty((B, gh, gw), np.int32)
+    mem = args[0].mem
+    if mem == _lib.CDC_MEM_HOST:
+        ps, pc, keep = sse.ctypes.data, count.ctypes.data, None
+    else:
+        import torch
+        keep = (torch.empty((B, gh, gw), dtype=torch.float64, device=f"cuda:{dev}"), torch.empty((B, gh, gw), dtype=torch.int32, device=f"cuda:{dev}"))
+        ps, pc = keep[0].data_ptr(), keep[1].data_ptr()
+    _lib.check(h, _lib.lib().cdc_distortion_map(h, ctypes.byref(views[0]), ctypes.byref(views[1]), B, H, W, cell, gh, gw, ps, pc, mem,
+                                                _current_stream(mem)))
+    if keep is not None:
+        sse, count = keep[0].cpu().numpy(), keep[1].cpu().numpy()
+    return sse, count
 
 
 def lpips(model, a, b, size=None, as_saved=False, return_layers=False):

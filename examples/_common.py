@@ -28,7 +28,11 @@ def _shared_options():
       --select METRIC   the score of --samples: "psnr" (default), "ms_ssim" or "lpips".  Without the two the output is unchanged.
       --trajectory N    progressive previews: the prediction x0 of every N-th executed step (and of the last), recorded inside the
                         device loop as uint8 (compress(..., trajectory=N, trajectory_dtype="uint8")) and saved beside the image as
-                        name.stepNNNN.png, NNNN the sample index.  Not with --samples.  Without it the output is unchanged."""
+                        name.stepNNNN.png, NNNN the sample index.  Not with --samples.  Without it the output is unchanged.
+      --maps_dir DIR    where the bits went and where the error remains: evaluate(..., maps=True) instead of compress(), and per image
+                        DIR/name.rate_map.npy (float32 [gh, gw], bits per cell of the padded frame) and DIR/name.sse_map.npy (float64,
+                        squared error of the saved image per cell; np.kron(map, np.ones((c, c))) / c ** 2 with the printed cell size c
+                        lays either over the picture).  Not with --samples or --trajectory.  Without it the output is unchanged."""
     import argparse
     p = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
     p.add_argument("--device_seed", type=int, default=None)
@@ -38,11 +42,14 @@ def _shared_options():
     p.add_argument("--samples", type=int, default=None)
     p.add_argument("--select", choices=("psnr", "ms_ssim", "lpips"), default=None)
     p.add_argument("--trajectory", type=int, default=None)
+    p.add_argument("--maps_dir", type=str, default=None)
     opts, sys.argv[1:] = p.parse_known_args(sys.argv[1:])
     if opts.select is not None and opts.samples is None:
         p.error("--select METRIC scores the candidates of --samples K")
     if opts.trajectory is not None and (opts.trajectory < 1 or opts.samples is not None):
         p.error("--trajectory N needs N >= 1 and excludes --samples")
+    if opts.maps_dir is not None and (opts.samples is not None or opts.trajectory is not None):
+        p.error("--maps_dir DIR excludes --samples and --trajectory")
     return opts
 
 
@@ -145,8 +152,12 @@ def run_folder(diffusion, config, rank, compress_kwargs):
                                                      std=config.gamma)).to(to_be_compressed.device)
             else:
                 init = torch.randn(shape, device=to_be_compressed.device) * config.gamma
-            traj = None
-            if best is None and SHARED.trajectory is not None:
+            traj, maps = None, None
+            if best is None and SHARED.maps_dir is not None:
+                maps = diffusion.evaluate(to_be_compressed, sample_steps=config.n_denoise_step, init=init, maps=True, **compress_kwargs)
+                compressed = maps["reconstruction"]
+                bpp = maps["bpp"].mean() if compress_kwargs.get("bpp_return_mean", True) else maps["bpp"]
+            elif best is None and SHARED.trajectory is not None:
                 compressed, bpp, traj = diffusion.compress(to_be_compressed, sample_steps=config.n_denoise_step, init=init,
                                                            trajectory=SHARED.trajectory, trajectory_dtype="uint8", **compress_kwargs)
             elif best is None:
@@ -170,8 +181,17 @@ def run_folder(diffusion, config, rank, compress_kwargs):
                 stem = os.path.splitext(img)[0]
                 for slot, i in enumerate(traj.steps):
                     save_image(traj.x0[slot], os.path.join(config.out_dir, f"{stem}.step{i:04d}.png"))
+            if maps is not None:
+                pathlib.Path(SHARED.maps_dir).mkdir(parents=True, exist_ok=True)
+                stem = os.path.splitext(img)[0]
+                rate_map = maps["rate_map"]
+                rate_map = rate_map.detach().cpu().numpy() if hasattr(rate_map, "detach") else np.asarray(rate_map)
+                np.save(os.path.join(SHARED.maps_dir, f"{stem}.rate_map.npy"), rate_map[0])
+                np.save(os.path.join(SHARED.maps_dir, f"{stem}.sse_map.npy"), maps["sse_map"][0])
             print("image:", img)
             print("bpp:", bpp)
+            if maps is not None:
+                print("map cell:", int(maps["map_cell"]))
             if SHARED.metrics:
                 print("psnr:", float(ps[0]))
                 print("ms_ssim:", "n/a (needs min(H, W) > 160)" if ms is None else float(ms[0]))

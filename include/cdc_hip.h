@@ -579,6 +579,47 @@ int cdc_distortion(cdc_handle *h, const cdc_image_view *a, const cdc_image_view 
                    double *psnr /*[B]*/, double *msssim /*[B]*/, double *components /*[B][5][3] or NULL*/,
                    int mem_kind, void *stream);
 
+/* ---- rate and error maps: where the bits went, where the error remains (csrc/map_kernels.hip) -------------------------------------
+ * THE DEFINITION, rate side.  Inputs as for cdc_bpp: q_hyper_latent [B][CH][h][w], q_latent / mean / scale [B][CL][U h][U w], with
+ * CH = dims[0], CL = dims[n] / 2 and U = 2^(n_layers - 1) of the hyper-decoder handle (4 as published).  The price of a symbol is the
+ * float32 value cdc_bpp sums: -log2 of its FlexiblePrior likelihood (hyper latent) or of its Gaussian likelihood (latent), the
+ * likelihood floored at 1e-9.  Outputs, float32, in bits, each optional (NULL: neither computed nor written):
+ *   latent_bits          [B][U h][U w]  sum over the CL channels of the Gaussian price at the position
+ *   hyper_bits           [B][h][w]      sum over the CH channels of the prior price at the position
+ *   cell_bits            [B][U h][U w]  latent sum[y][x] + hyper sum[y / U][x / U] / U^2: the whole rate on one grid, formed from the two
+ *                                       float64 sums, the division in float64, one cast
+ *   latent_channel_bits  [B][CL]        sum over all positions of the channel
+ *   hyper_channel_bits   [B][CH]        likewise
+ * Every sum is accumulated in float64 in an order fixed by the tensor's shape alone and cast to float32 once.  Position sums: with
+ * P = the power of two >= min(positions of the grid, 16) and G = 256 / P, the channels fall into G consecutive groups of ceil(C / G);
+ * a group is summed in ascending channel order, then the groups in ascending order.  Channel sums: tiles of P consecutive positions
+ * (row-major) by an xor butterfly each, then the tiles t, t + 64, ... in ascending order for t = 0 .. 63, then an xor butterfly over
+ * the 64.  No atomics: a result depends neither on B, nor on the image's row in the batch, nor on the outputs requested, nor on the
+ * run.  The sum of cell_bits over an image is its cdc_bpp times H_img W_img up to the float32 casts of the entries.
+ * cdc_rate_map: a hyper-decoder handle with the prior.* tensors loaded (CDC_ERR_STATE without them, as cdc_bpp).  All pointers follow
+ *   mem_kind; host results are staged through handle-owned device memory grown on demand, and the call then synchronises; stream as
+ *   for cdc_unet_forward.  The same guard / error runner as every entry point.  CDC_ERR_INVALID, with a message and before any launch:
+ *   all five outputs NULL; an input pointer missing; B, h_hyper or w_hyper < 1; more than 65535 images or 2^30 latent positions.
+ *
+ * THE DEFINITION, error side.  Operands: two cdc_image_view batches over the top-left H x W window, mapped to [0, 1] exactly as for
+ * cdc_distortion (uint8, float32 clamped, float32 as_saved).  A grid of gh x gw cells of cell x cell pixels, anchored at the top-left
+ * pixel, with gh cell >= H and gw cell >= W.
+ *   sse   [B][gh][gw] float64  sum over the three channels and over the cell's pixels INSIDE the window of (a - b)^2
+ *   count [B][gh][gw] int32    3 x the number of those pixels (may be NULL)
+ * A cell wholly outside the window has sse = 0 and count = 0; nothing outside the window is read.  Two byte operands (uint8, or
+ * float32 with as_saved): the cell's sum of squared integer differences is exact and divided once by 65025.0.  Otherwise the
+ * difference is fp32 and every square is accumulated in fp64: element e = (channel, row, column) of the cell, row-major, goes to lane
+ * e mod 64 in ascending order, then an xor butterfly over the 64 lanes.  sum(sse) / sum(count) over an image is the MSE of
+ * cdc_distortion's PSNR.  One wave per cell: made for the cells of the latent grid (16 pixels a side as published), correct for any.
+ * cdc_distortion_map: any handle kind; sse, count and the images follow mem_kind (host results: handle-owned staging, the call
+ *   synchronises).  CDC_ERR_INVALID, with a message and before any launch: B, H, W or cell < 1; a grid that does not cover the
+ *   window; Hf < H or Wf < W; an unknown element kind; as_saved on a uint8 operand; sse NULL; a cell of more than 2^30 / 3 pixels. */
+int cdc_rate_map(cdc_handle *hyperdec, const float *q_hyper_latent, const float *q_latent, const float *mean, const float *scale,
+                 float *latent_bits, float *hyper_bits, float *cell_bits, float *latent_channel_bits, float *hyper_channel_bits,
+                 int B, int h_hyper, int w_hyper, int mem_kind, void *stream);
+int cdc_distortion_map(cdc_handle *h, const cdc_image_view *a, const cdc_image_view *b, int B, int H, int W, int cell, int gh, int gw,
+                       double *sse /*[B][gh][gw]*/, int32_t *count /*[B][gh][gw] or NULL*/, int mem_kind, void *stream);
+
 /* ---- LPIPS-VGG of decoded images on the device: the perceptual axis (csrc/lpips_kernels.hip, build_lpips_program) ----------------
  * THE DEFINITION.  LPIPS of the lpips package, version 0.1.4: LPIPS(net="vgg", lpips=True, spatial=False).forward(in0, in1,
  * normalize=False), per image.  The reference trains with it (xparam/modules/denoising_diffusion.py:47,331-336) and its checkpoints
