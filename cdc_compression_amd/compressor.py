@@ -24,6 +24,12 @@ multiple (`padded_size`).  Every latent and `forward()["output"]` -- the context
 that PADDED frame; `bpp` counts bits over the original `H * W`; the streams record `H x W` (container version 5 / 6) unless the
 image already is its own frame, in which case they are the version-3 / -4 streams they always were.  `analysis`, `decode`,
 `hyper_decode` mirror the reference's modules one to one and keep requiring frame sizes.
+
+Rate control in the encoder (no reference counterpart; include/cdc_hip.h: cdc_set_rdo states the decision): `rdo=mu` -- the price of a
+bit, a scalar or B values -- makes the quantiser code, per latent symbol, the neighbour towards the mean in place of the nearest integer
+where mu * (bits saved) exceeds the squared error added.  `encode`, `forward`, `latents_to_bytes` and `compress_to_bytes` take it;
+`compress_to_bytes(target_bpp= | max_bytes=)` finds mu per image from `rate_sweep`'s one-pass curve.  The streams keep their format and
+the decoder never learns mu; `rdo=None` runs what always ran.  What the moves do to decoded images of trained weights is unmeasured.
 """
 import ctypes
 
@@ -42,6 +48,53 @@ class NormalDistribution:
     @property
     def mean(self):
         return self.loc
+
+
+# ---- rate-distortion optimised quantisation: the host side of rate targeting (include/cdc_hip.h: cdc_set_rdo states the decision) ----
+RDO_MAX_LADDER = 32                                                    # cdc_entropy_rate_sweep prices at most this many mu in one pass
+RDO_LADDER = np.float32(2.0) ** np.arange(-8, 9, dtype=np.float32)      # the default ladder: mu = 2^-8 ... 2^8 in 17 steps
+RDO_REFINE_STEPS = 17
+
+
+def rdo_values(rdo, B, what="rdo"):
+    """rdo / a ladder -> float32 host vector, checked before the library is touched: finite, >= 0, and 1 or B values (B=None: a ladder
+    of 1 .. RDO_MAX_LADDER values)."""
+    r = np.ascontiguousarray(_as_host_f32(rdo).reshape(-1))
+    if B is None:
+        if not 1 <= r.size <= RDO_MAX_LADDER:
+            raise ValueError(f"{what}: a ladder of {r.size} values (1 .. {RDO_MAX_LADDER} expected)")
+    elif r.size not in (1, B):
+        raise ValueError(f"{what} has {r.size} values for a batch of {B} (1 or {B} expected)")
+    if not np.all(np.isfinite(r)) or np.any(r < 0):
+        raise ValueError(f"{what}={r.tolist()}: every mu must be finite and >= 0")
+    return r
+
+
+def rdo_exclusive(rdo=None, target_bpp=None, max_bytes=None):
+    """rdo, target_bpp and max_bytes exclude each other."""
+    given = [n for n, v in (("rdo", rdo), ("target_bpp", target_bpp), ("max_bytes", max_bytes)) if v is not None]
+    if len(given) > 1:
+        raise ValueError(f"{' and '.join(given)} exclude each other: give one of rdo, target_bpp, max_bytes")
+
+
+def rdo_select(cost, target):
+    """One row of a sweep table -> (j, met).  cost[j]: the estimated cost at ladder entry j, non-increasing along an ascending
+    ladder; j is the first entry whose cost is <= target (the smallest mu that meets it).  None does: (last entry, False)."""
+    cost = np.asarray(cost, np.float64).reshape(-1)
+    hit = np.nonzero(cost <= float(target))[0]
+    return (int(hit[0]), True) if hit.size else (cost.size - 1, False)
+
+
+def rdo_refine_ladder(lo, hi, steps=RDO_REFINE_STEPS):
+    """The refining ladder between two neighbouring entries lo < hi of a ladder: `steps` float32 values from lo to hi inclusive,
+    geometric (linear when lo = 0, the entry below the first positive mu), ascending, without repeats."""
+    lo, hi = float(np.float32(lo)), float(np.float32(hi))
+    if not (0 <= lo < hi and np.isfinite(hi)) or not 2 <= steps <= RDO_MAX_LADDER:
+        raise ValueError(f"rdo_refine_ladder: lo={lo}, hi={hi}, steps={steps}")
+    v = np.linspace(lo, hi, steps) if lo == 0 else np.geomspace(lo, hi, steps)
+    v = v.astype(np.float32)
+    v[0], v[-1] = lo, hi
+    return np.unique(v)
 
 
 def _enable_vbr(h):
@@ -358,7 +411,8 @@ class _ContextDecoder:
         mean, scale = (dist.mean, dist.scale) if hasattr(dist, "mean") else dist
         hyper = state4bpp["hyper_latent"]
         q_hyper = self.dequantize(hyper, self._medians_like(hyper))
-        q_latent = self.dequantize(state4bpp["latent"], mean)
+        # encode(..., rdo=) chose the symbols: "latent" stays the unquantised latent, the rate is that of the symbols chosen
+        q_latent = state4bpp["q_latent"] if "q_latent" in state4bpp else self.dequantize(state4bpp["latent"], mean)
         return self.rate(q_hyper, q_latent, mean, scale, (H, W))
 
     # ---- images of any size ------------------------------------------------------------------
@@ -426,18 +480,52 @@ class _ContextDecoder:
             med = torch.from_numpy(med).to(t.device)
         return med
 
-    def encode(self, input, cond=None, padded_hw=None):
+    def encode(self, input, cond=None, padded_hw=None, rdo=None):
         """Compressor.encode (compress_modules.py:43-66): (q_latent, q_hyper_latent, state4bpp); cond: VBR rate.  Images of any
-        size (float32 / uint8): the results are those of the padded frame."""
-        self._rates(cond, frame.image_shape(input)[0])
+        size (float32 / uint8): the results are those of the padded frame.  rdo: the price of a bit mu >= 0, a scalar or B values
+        (no reference counterpart): q_latent comes from `rdo_quantize` -- every symbol the nearest integer or, where mu * (bits saved)
+        exceeds the squared error it costs, its neighbour towards the mean; state4bpp keeps the unquantised latent and gains
+        "q_latent" and "rdo_moved" (int64 [B]).  None runs the reference's rounding."""
+        B = frame.image_shape(input)[0]
+        self._rates(cond, B)
+        mu = None if rdo is None else rdo_values(rdo, B)
         input, _ = self._framed(input, padded_hw)
         latent, hyper_latent = self.analysis(input, cond)
         q_hyper_latent = self.dequantize(hyper_latent, self._medians_like(hyper_latent))
         mean, scale = self.hyper_decode(q_hyper_latent, cond=cond)
-        q_latent = self.dequantize(latent, mean)
         state4bpp = {"latent": latent, "hyper_latent": hyper_latent,
                      "latent_distribution": NormalDistribution(mean, scale)}
+        if mu is None:
+            q_latent = self.dequantize(latent, mean)
+        else:
+            q_latent, moved = self.rdo_quantize(latent, mean, scale, mu)
+            state4bpp.update(q_latent=q_latent, rdo_moved=moved)
         return q_latent, q_hyper_latent, state4bpp
+
+    def rdo_quantize(self, latent, mean, scale, rdo):
+        """cdc_op_rdo_quantize: the decision of include/cdc_hip.h on caller-supplied operands of one shape [B, ...] -> (q_latent,
+        moved int64 [B] numpy).  rdo: 1 or B values.  Non-finite operands are refused (CdcError) with nothing written."""
+        args = [_Arg(t, self.device_index) for t in (latent, mean, scale)]
+        if len({a.mem for a in args}) != 1 or len({tuple(a.shape) for a in args}) != 1:
+            raise _lib.CdcError("latent, mean and scale must have the same shape and live in the same memory")
+        B = args[0].shape[0]
+        per = int(np.prod(args[0].shape[1:]))
+        mu = rdo_values(rdo, B)
+        mu = np.ascontiguousarray(np.broadcast_to(mu, (B,)), dtype=np.float32)
+        L, h = _lib.lib(), self._hyper_handle()
+        if not self._hyper_finalized:
+            raise _lib.CdcError("load_hyper_state_dict() has not been called")
+        out, po, mem = _result_like(latent, args[0].shape, self.device_index)
+        if mem == _lib.CDC_MEM_DEVICE:
+            import torch
+            mv = torch.zeros(B, dtype=torch.int64, device=out.device)
+            pm = mv.data_ptr()
+        else:
+            mv = np.zeros(B, np.int64)
+            pm = mv.ctypes.data
+        _lib.check(h, L.cdc_op_rdo_quantize(h, args[0].ptr, args[1].ptr, args[2].ptr, mu.ctypes.data, po, pm, B, per, mem,
+                                            _current_stream(mem)))
+        return out, (mv.cpu().numpy() if mem == _lib.CDC_MEM_DEVICE else mv)
 
     # ---- entropy coder (SURVEY section 8f row 4; no reference counterpart) ---------------------
     def _median_vector(self):
@@ -445,27 +533,174 @@ class _ContextDecoder:
         med = self._medians.reshape(-1) if self._medians is not None else np.zeros(C, np.float32)
         return np.ascontiguousarray(med, dtype=np.float32)
 
-    def compress_to_bytes(self, images, bitrate_scale=None):
+    def compress_to_bytes(self, images, bitrate_scale=None, rdo=None, target_bpp=None, max_bytes=None, return_info=False):
         """images [B, 3, H, W] -> list of B bitstreams (bytes): analysis transform + hyper encoder on the GPU, then the
         range-ANS coder of include/cdc_hip.h (cdc_entropy_encode) over exactly the symbols `bpp()` prices.  A VBR model
-        takes bitrate_scale (1 or B values) and records each image's rate in its stream."""
-        self._rates(bitrate_scale, frame.image_shape(images)[0])
+        takes bitrate_scale (1 or B values) and records each image's rate in its stream.
+        Rate control (one of three; the streams keep their format and the decoder never learns mu; downward only):
+          rdo=mu         the price of a bit, a scalar or B values: rate-distortion optimised quantisation of the latent (cdc_set_rdo);
+                         0 gives the bytes of rdo=None.
+          target_bpp=t   a scalar or B values: per image the smallest mu whose ESTIMATED bpp (`rate()` over H * W) is <= t, found by
+                         one sweep of the ladder 0, 2^-8 ... 2^8 and one refining sweep of 17 steps below the entry found
+                         (`rate_sweep`: no analysis transform is repeated), then one encode.  An image that meets t already gets
+                         mu = 0; one that the largest mu does not bring down to t is coded with it and reported met=False.
+          max_bytes=n    the same against 8 n bits, the stream's header counted; the coder's own overhead (its 2 x 64 lane states,
+                         escapes) is not in the estimate, so a stream that ends over n shrinks its image's bit target by the
+                         observed ratio and is chosen again: at most 3 re-encodes.  met: len(stream) <= n.
+        return_info=True: -> (streams, {"mu", "estimated_bpp", "moved", "latent_mse", "met" (each [B]), "reencodes"})."""
+        B = frame.image_shape(images)[0]
+        rdo_exclusive(rdo, target_bpp, max_bytes)
+        self._rates(bitrate_scale, B)
+        mu = None if rdo is None else rdo_values(rdo, B)
+        target = None if target_bpp is None else self._targets(target_bpp, B, "target_bpp")
+        budget = None if max_bytes is None else self._targets(max_bytes, B, "max_bytes")
         images, hw = self._framed(images)
         latent, hyper = self.analysis(images, bitrate_scale)
-        return self.latents_to_bytes(latent, hyper, bitrate_scale, image_hw=hw)
+        if target is None and budget is None:
+            streams = self.latents_to_bytes(latent, hyper, bitrate_scale, image_hw=hw, rdo=mu)
+            if not return_info:
+                return streams
+            row = self._sweep(latent, hyper, np.zeros(1, np.float32) if mu is None else mu, bitrate_scale, per_image=True)
+            return streams, self._rdo_info(row, np.zeros(B, np.float32) if mu is None else np.broadcast_to(mu, (B,)), hw, latent,
+                                           np.ones(B, bool), 0)
+        ladder = np.concatenate([np.zeros(1, np.float32), RDO_LADDER])
+        table = self._sweep(latent, hyper, ladder, bitrate_scale)
+        npix = float(hw[0] * hw[1])
+        if target is not None:
+            goal, cost0 = target, table["bits"] / npix                  # estimated bpp against the target
+        else:
+            header = self._stream_header_bytes(images, hw)
+            goal, cost0 = 8.0 * (budget - header), table["bits"]       # estimated payload bits against the budget's
+        div = npix if target is not None else 1.0
+        rows = [self._choose_mu(latent, hyper, bitrate_scale, b, ladder, cost0[b], goal[b], div)
+                for b in range(B)]
+        reencodes = 0
+        while True:
+            mus = np.asarray([r["mu"] for r in rows], np.float32)
+            streams = self.latents_to_bytes(latent, hyper, bitrate_scale, image_hw=hw, rdo=mus)
+            over = [] if budget is None else [b for b in range(B) if len(streams[b]) > budget[b]]
+            if not over or reencodes == 3:
+                break
+            reencodes += 1
+            for b in over:                                              # the estimate missed the coder's overhead: aim lower by what was seen
+                goal[b] *= budget[b] / len(streams[b])
+                rows[b] = self._choose_mu(latent, hyper, bitrate_scale, b, ladder, cost0[b], goal[b], div)
+        if not return_info:
+            return streams
+        met = np.asarray([r["met"] for r in rows], bool) if budget is None else \
+            np.asarray([len(streams[b]) <= budget[b] for b in range(B)], bool)
+        row = {k: np.stack([r[k] for r in rows]) for k in ("bits", "sse", "moved")}
+        return streams, self._rdo_info(row, mus, hw, latent, met, reencodes)
 
-    def latents_to_bytes(self, latent, hyper, bitrate_scale=None, image_hw=None):
-        """The UNquantised outputs of `analysis()` -> list of B bitstreams.  The coder's determinism contract starts here: the
-        same (latent, hyper) rows give the same bytes whatever the batch they are coded in (the analysis transform itself is
-        an ordinary batched forward: its last bits may depend on the batch size, like any other entry point's).
-        image_hw=(H, W): the size of the original image when the latents are those of its padded frame; the streams then record it
-        (container version 5 / 6) unless it equals the frame's, and are today's version 3 / 4 otherwise."""
+    @staticmethod
+    def _targets(v, B, what):
+        """target_bpp / max_bytes -> float64 [B], checked before the library is touched."""
+        t = np.asarray(_as_host_f32(v) if type(v).__module__.startswith("torch") else v, np.float64).reshape(-1)
+        if t.size not in (1, B):
+            raise ValueError(f"{what} has {t.size} values for a batch of {B} (1 or {B} expected)")
+        if not np.all(np.isfinite(t)) or np.any(t <= 0):
+            raise ValueError(f"{what}={t.tolist()}: finite values > 0 expected")
+        return np.broadcast_to(t, (B,)).copy()
+
+    def _stream_header_bytes(self, images, hw):
+        """Bytes of a stream's header (include/cdc_hip.h: 34, + 4 with a bitrate_scale, + 8 with a recorded image size)."""
+        framed = tuple(frame.image_shape(images)[2:])
+        return 34 + (4 if self.vbr else 0) + (8 if tuple(hw) != framed else 0)
+
+    def _sweep(self, latent, hyper, mus, bitrate_scale=None, per_image=False):
+        """cdc_entropy_rate_sweep on the unquantised outputs of `analysis()` -> {"bits", "sse" float64 [B, L], "moved" int64 [B, L]}.
+        per_image: `mus` holds 1 or B values, one per image, and the result is [B] (image b at its own mu; the batch = batch-1
+        contract makes the batch-1 calls this takes the rows of one batched call)."""
         L, h = _lib.lib(), self._hyper_handle()
         if not (self._hyper_finalized and self._prior_loaded):
             raise _lib.CdcError("the prior.* tensors have not been loaded (load_state_dict with the full state_dict)")
         al, ah = _Arg(latent, self.device_index), _Arg(hyper, self.device_index)
         B, _, hh, wh = ah.shape
+        if per_image:
+            mus = np.broadcast_to(rdo_values(mus, B), (B,))
+            if len(set(mus.tolist())) == 1:
+                one = self._sweep(latent, hyper, mus[:1], bitrate_scale)
+                return {k: v[:, 0] for k, v in one.items()}
+            rates = self._rates(bitrate_scale, B)
+            rows = [self._sweep(latent[b:b + 1], hyper[b:b + 1], mus[b:b + 1],
+                                None if rates is None else rates[b if rates.size > 1 else 0]) for b in range(B)]
+            return {k: np.concatenate([r[k][:, 0] for r in rows]) for k in rows[0]}
+        mus = rdo_values(mus, None, "mus")
         self._set_rate(h, bitrate_scale, B)
+        n = int(mus.size)
+        bits, sse, moved = np.empty((B, n), np.float64), np.empty((B, n), np.float64), np.empty((B, n), np.int64)
+        med = self._median_vector()
+        _lib.check(h, L.cdc_entropy_rate_sweep(h, al.ptr, ah.ptr, med.ctypes.data, B, hh, wh, mus.ctypes.data, n, bits.ctypes.data,
+                                               sse.ctypes.data, moved.ctypes.data, al.mem, _current_stream(al.mem)))
+        return {"bits": bits, "sse": sse, "moved": moved}
+
+    def _choose_mu(self, latent, hyper, bitrate_scale, b, ladder, cost, goal, div):
+        """Image b's mu for the cost goal `goal`: `cost` is its row of the first sweep over `ladder` (ascending, entry 0 = mu 0) in the
+        goal's unit (bits / div) -> {"mu", "met", "bits", "sse", "moved"} at the mu chosen.  The refining sweep runs on the image's
+        own rows: batch 1, the same values as in the batch."""
+        rates = self._rates(bitrate_scale, _Arg(hyper, self.device_index).shape[0])
+        rate_b = None if rates is None else rates[b if rates.size > 1 else 0]
+        j, met = rdo_select(cost, goal)
+        if j == 0 or not met:           # the plain symbols do, or nothing on the ladder does: no interval to refine
+            sub = ladder[j:j + 1]
+            k = 0
+            row = self._sweep(latent[b:b + 1], hyper[b:b + 1], sub, rate_b)
+        else:
+            sub = rdo_refine_ladder(ladder[j - 1], ladder[j])
+            row = self._sweep(latent[b:b + 1], hyper[b:b + 1], sub, rate_b)
+            k, _ = rdo_select(row["bits"][0] / div, goal)               # (the interval's upper end meets the goal: it did above)
+        return {"mu": np.float32(sub[k]), "met": met, "bits": row["bits"][0, k], "sse": row["sse"][0, k], "moved": row["moved"][0, k]}
+
+    @staticmethod
+    def _rdo_info(row, mus, hw, latent, met, reencodes):
+        per = float(np.prod(tuple(latent.shape)[1:]))
+        return {"mu": np.asarray(mus, np.float32).copy(), "estimated_bpp": np.asarray(row["bits"], np.float64) / float(hw[0] * hw[1]),
+                "moved": np.asarray(row["moved"], np.int64), "latent_mse": np.asarray(row["sse"], np.float64) / per,
+                "met": np.asarray(met, bool), "reencodes": int(reencodes)}
+
+    def rate_sweep(self, images, mus, bitrate_scale=None, image_hw=None):
+        """The rate-distortion curve of the quantiser itself, for plots: images [B, 3, H, W], or the unquantised (latent, hyper) of
+        `analysis()`, and a ladder `mus` of 1 .. 32 values -> {"mu" float32 [L], "bpp" [B, L] (the estimate `rate()` gives for the
+        symbols chosen at mu, over H * W -- of a (latent, hyper) pair: over image_hw, default the coded extent), "latent_mse" [B, L]
+        (mean squared error of the dequantised latent against the unquantised one), "moved" int64 [B, L]}.  One pass over the latent
+        for the whole ladder (cdc_entropy_rate_sweep); mean and scale are the coder's own.  What the moves do to decoded images of
+        trained weights is not measured by this."""
+        mus = rdo_values(mus, None, "mus")
+        if isinstance(images, (tuple, list)):
+            latent, hyper = images
+            hh, wh = tuple(hyper.shape)[2:]
+            hw = tuple(image_hw) if image_hw is not None else (hh * self.frame_multiple, wh * self.frame_multiple)
+        else:
+            self._rates(bitrate_scale, frame.image_shape(images)[0])
+            images, hw = self._framed(images)
+            latent, hyper = self.analysis(images, bitrate_scale)
+        t = self._sweep(latent, hyper, mus, bitrate_scale)
+        per = float(np.prod(tuple(latent.shape)[1:]))
+        return {"mu": mus.copy(), "bpp": t["bits"] / float(hw[0] * hw[1]), "latent_mse": t["sse"] / per, "moved": t["moved"]}
+
+    def latents_to_bytes(self, latent, hyper, bitrate_scale=None, image_hw=None, rdo=None):
+        """The UNquantised outputs of `analysis()` -> list of B bitstreams.  The coder's determinism contract starts here: the
+        same (latent, hyper) rows give the same bytes whatever the batch they are coded in (the analysis transform itself is
+        an ordinary batched forward: its last bits may depend on the batch size, like any other entry point's).
+        image_hw=(H, W): the size of the original image when the latents are those of its padded frame; the streams then record it
+        (container version 5 / 6) unless it equals the frame's, and are today's version 3 / 4 otherwise.
+        rdo: mu, 1 or B values (cdc_set_rdo for this call alone); image b's stream depends on its own mu only."""
+        L, h = _lib.lib(), self._hyper_handle()
+        al, ah = _Arg(latent, self.device_index), _Arg(hyper, self.device_index)
+        B, _, hh, wh = ah.shape
+        mu = None if rdo is None else rdo_values(rdo, B)
+        if not (self._hyper_finalized and self._prior_loaded):
+            raise _lib.CdcError("the prior.* tensors have not been loaded (load_state_dict with the full state_dict)")
+        self._set_rate(h, bitrate_scale, B)
+        if mu is not None:
+            _lib.check(h, L.cdc_set_rdo(h, mu.ctypes.data, int(mu.size)))
+            try:
+                return self._coded(L, h, al, ah, B, hh, wh, image_hw)
+            finally:
+                L.cdc_set_rdo(h, None, 0)
+        return self._coded(L, h, al, ah, B, hh, wh, image_hw)
+
+    def _coded(self, L, h, al, ah, B, hh, wh, image_hw):
         nsym = int(np.prod(al.shape[1:])) + int(np.prod(ah.shape[1:]))
         cap = B * (64 + 2 * 320 + 6 * nsym)              # <= 2 renormalisation bytes + a 4-byte escape payload per symbol
         buf = np.empty(cap, dtype=np.uint8)
@@ -568,13 +803,14 @@ class _ContextDecoder:
             out[b] = r.value
         return out
 
-    def forward(self, input, cond=None, padded_hw=None, return_rate_map=False):
+    def forward(self, input, cond=None, padded_hw=None, return_rate_map=False, rdo=None):
         """Compressor.forward (compress_modules.py:92-103).  Images of any size (float32 / uint8): "output" (the context pyramid the
         U-Net consumes), "q_latent" and "q_hyper_latent" are those of the PADDED frame, "bpp" counts bits over the original H * W.
         return_rate_map: also "rate_map", `rate_map(...)["cell"]` of the padded frame, [B, Hp / c, Wp / c] in bits with
-        c = `rate_map_cell`; its sum over an image is bpp * H * W."""
+        c = `rate_map_cell`; its sum over an image is bpp * H * W.  rdo: as `encode`; "bpp", "output" and "rate_map" are those of
+        the symbols it chose."""
         shape = frame.image_shape(input)
-        q_latent, q_hyper_latent, state4bpp = self.encode(input, cond, padded_hw)
+        q_latent, q_hyper_latent, state4bpp = self.encode(input, cond, padded_hw, rdo)
         out = {"output": self.decode(q_latent, cond), "bpp": self.bpp(shape, state4bpp), "q_latent": q_latent,
                "q_hyper_latent": q_hyper_latent}
         if return_rate_map:

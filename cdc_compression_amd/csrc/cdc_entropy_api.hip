@@ -60,6 +60,70 @@ int hyperdec_batch(cdc_handle *h, int B, hipStream_t st, bool check) {
     return CDC_OK;
 }
 
+// The encoder's front end, one copy for the coder and for cdc_entropy_rate_sweep: the operands on the device, the hyper symbols and
+// their dequantised values -> hyper_dec through the batch-1 plan -> (mean | scale) in h->dec_outs[0].  What prices a decision is
+// therefore exactly the mean and scale the coder codes with.  Everything lives until `d` goes.
+struct EncoderFront {
+    DevPool d;
+    hipStream_t st = nullptr;
+    const float *d_hl = nullptr, *d_lat = nullptr;       // hyper latent and latent on the device
+    int32_t *symh = nullptr;                             // hyper symbols [B][nh]
+    int *bad = nullptr;                                  // zero so far
+    int Ch = 0, per = 0;
+    long long nh = 0, nl = 0;
+};
+int encoder_front(cdc_handle *h, const float *latent, const float *hyper_latent, const float *medians, int B, int hh, int wh, int mem,
+                  void *stream, EncoderFront *f) {
+    int rc;
+    if ((rc = ensure_entropy(h, medians))) return rc;
+    hipStream_t st = f->st = h->own_stream;               // synchronous entry point
+    if (mem == CDC_MEM_DEVICE) HIP_TRY(h, hipStreamSynchronize((hipStream_t)stream));
+    const int Ch = f->Ch = h->hyper_dims[0], per = f->per = hh * wh;
+    const long long nh = f->nh = (long long)Ch * per;
+    if ((rc = build_hyperdec_program(h, B, hh, wh, true))) return rc;
+    const Act &o = h->dec_outs[0];
+    const long long nl = f->nl = (long long)(o.C / 2) * o.H * o.W;
+    if (nh > (1ll << 29) || nl > (1ll << 29)) return fail(h, CDC_ERR_INVALID, "image too large for one coder section");   // (section offsets are 32-bit)
+    DevPool &d = f->d;
+    f->d_hl = hyper_latent; f->d_lat = latent;
+    if (mem != CDC_MEM_DEVICE) {
+        float *a, *b;
+        HIP_TRY(h, d.get(&a, (size_t)B * nh)); HIP_TRY(h, d.get(&b, (size_t)B * nl));
+        HIP_TRY(h, hipMemcpyAsync(a, hyper_latent, (size_t)B * nh * sizeof(float), hipMemcpyHostToDevice, st));
+        HIP_TRY(h, hipMemcpyAsync(b, latent, (size_t)B * nl * sizeof(float), hipMemcpyHostToDevice, st));
+        f->d_hl = a; f->d_lat = b;
+    }
+    HIP_TRY(h, d.get(&f->symh, (size_t)B * nh)); HIP_TRY(h, d.get(&f->bad, 1));
+    HIP_TRY(h, hipMemsetAsync(f->bad, 0, sizeof(int), st));
+    // hyper symbols; their dequantised values are hyper_dec's input (quantize(.., "dequantize", medians), utils.py:72-85)
+    HIP_TRY(h, cdc::hyper_symbols_launch(f->d_hl, h->ent->d_medians, Ch, per, B, f->symh, h->in_x, f->bad, st));
+    int hbad = 0;                                         // (before hyper_dec: garbage input must not trip the range guard)
+    HIP_TRY(h, hipMemcpyAsync(&hbad, f->bad, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    if (hbad) return fail(h, CDC_ERR_INVALID, "non-finite or out-of-range hyper-latent (nothing to code)");
+    if ((rc = stage_rate(h, nullptr, B, st))) return rc;      // variable bitrate: the handle's rates, recorded in the streams below
+    // the encoder may leave CDC_ARITH_F16X2 when hyper_dec overflows its range (checked outside the repetition only): the stream
+    // header records the arithmetic that was finally used and the decoder runs what the header says
+    return hyperdec_batch(h, B, st, !h->in_retry);
+}
+
+// the per-image mu of one call on the device: the handle's cdc_set_rdo values (1, broadcast, or B), as stage_rate does for the rates
+int stage_rdo(cdc_handle *h, int B, DevPool *d, float **d_mu, hipStream_t st) {
+    const size_t n = h->rdo_mu.size();
+    if (n != 1 && n != (size_t)B) return fail(h, CDC_ERR_INVALID, "rdo has %zu values for a batch of %d (1 or %d expected)", n, B, B);
+    h->rdo_stage.resize((size_t)B);
+    for (int b = 0; b < B; ++b) h->rdo_stage[b] = h->rdo_mu[n == 1 ? 0 : b];
+    HIP_TRY(h, d->get(d_mu, (size_t)B));
+    HIP_TRY(h, hipMemcpyAsync(*d_mu, h->rdo_stage.data(), sizeof(float) * B, hipMemcpyHostToDevice, st));
+    return CDC_OK;
+}
+
+inline int check_mu(cdc_handle *h, const char *what, const float *mu, int n) {
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(mu[i]) || mu[i] < 0.f) return fail(h, CDC_ERR_INVALID, "%s: mu[%d] = %g (finite and >= 0 expected)", what, i, (double)mu[i]);
+    return CDC_OK;
+}
+
 // img_h = img_w = 0: the image is the coded extent (version 3 / 4), as is an image size equal to it
 int entropy_encode_impl(cdc_handle *h, const float *latent, const float *hyper_latent, const float *medians, int B,
                         int hh, int wh, int img_h, int img_w, unsigned char *out, size_t cap, size_t *offsets, int mem, void *stream) {
@@ -76,49 +140,34 @@ int entropy_encode_impl(cdc_handle *h, const float *latent, const float *hyper_l
                         img_h, img_w, (long long)D * hh, (long long)D * wh, hh, wh, D);
         if ((long long)D * hh == img_h && (long long)D * wh == img_w) img_h = img_w = 0;      // nothing to crop: today's stream, byte for byte
     }
-    if ((rc = ensure_entropy(h, medians))) return rc;
-    hipStream_t st = h->own_stream;                       // synchronous entry point
-    if (mem == CDC_MEM_DEVICE) HIP_TRY(h, hipStreamSynchronize((hipStream_t)stream));
-    const int Ch = h->hyper_dims[0], per = hh * wh;
-    const long long nh = (long long)Ch * per;
-    if ((rc = build_hyperdec_program(h, B, hh, wh, true))) return rc;
+    EncoderFront f;
+    if ((rc = encoder_front(h, latent, hyper_latent, medians, B, hh, wh, mem, stream, &f))) return rc;
+    DevPool &d = f.d;
+    hipStream_t st = f.st;
+    const int Ch = f.Ch, per = f.per;
+    const long long nh = f.nh, nl = f.nl;
+    const float *d_lat = f.d_lat;
+    int32_t *symh = f.symh, *syml;
+    int *bad = f.bad;
     const Act &o = h->dec_outs[0];
-    const long long nl = (long long)(o.C / 2) * o.H * o.W;
-    if (nh > (1ll << 29) || nl > (1ll << 29)) return fail(h, CDC_ERR_INVALID, "image too large for one coder section");   // (section offsets are 32-bit)
-    DevPool d;
-    const float *d_hl = hyper_latent, *d_lat = latent;
-    if (mem != CDC_MEM_DEVICE) {
-        float *a, *b;
-        HIP_TRY(h, d.get(&a, (size_t)B * nh)); HIP_TRY(h, d.get(&b, (size_t)B * nl));
-        HIP_TRY(h, hipMemcpyAsync(a, hyper_latent, (size_t)B * nh * sizeof(float), hipMemcpyHostToDevice, st));
-        HIP_TRY(h, hipMemcpyAsync(b, latent, (size_t)B * nl * sizeof(float), hipMemcpyHostToDevice, st));
-        d_hl = a; d_lat = b;
-    }
-    int32_t *symh, *syml;
     uint8_t *bin, *sec_h, *sec_l, *packed;
     uint32_t *sf, *ew, *esc_h, *esc_l;
-    int *bad;
     cdc::RansMeta *meta;
     long long *d_off;
     const long long cap_h = section_cap(nh), cap_l = section_cap(nl);
     const long long pack_cap = (long long)B * ((h->vbr ? kStreamHeaderVbr : kStreamHeader) + kStreamSizeField + cap_h + 4 * nh + cap_l + 4 * nl);
-    HIP_TRY(h, d.get(&symh, (size_t)B * nh)); HIP_TRY(h, d.get(&syml, (size_t)B * nl)); HIP_TRY(h, d.get(&bin, (size_t)B * nl));
+    HIP_TRY(h, d.get(&syml, (size_t)B * nl)); HIP_TRY(h, d.get(&bin, (size_t)B * nl));
     HIP_TRY(h, d.get(&sf, (size_t)B * std::max(nh, nl))); HIP_TRY(h, d.get(&ew, (size_t)B * std::max(nh, nl)));
     HIP_TRY(h, d.get(&sec_h, (size_t)B * cap_h)); HIP_TRY(h, d.get(&sec_l, (size_t)B * cap_l));
     HIP_TRY(h, d.get(&esc_h, (size_t)B * nh)); HIP_TRY(h, d.get(&esc_l, (size_t)B * nl));
-    HIP_TRY(h, d.get(&bad, 1)); HIP_TRY(h, d.get(&meta, 2 * (size_t)B)); HIP_TRY(h, d.get(&d_off, (size_t)B + 1));
-    HIP_TRY(h, hipMemsetAsync(bad, 0, sizeof(int), st));
-    // hyper symbols; their dequantised values are hyper_dec's input (quantize(.., "dequantize", medians), utils.py:72-85)
-    HIP_TRY(h, cdc::hyper_symbols_launch(d_hl, h->ent->d_medians, Ch, per, B, symh, h->in_x, bad, st));
-    int hbad = 0;                                         // (before hyper_dec: garbage input must not trip the range guard)
-    HIP_TRY(h, hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    if (hbad) return fail(h, CDC_ERR_INVALID, "non-finite or out-of-range hyper-latent (nothing to code)");
-    if ((rc = stage_rate(h, nullptr, B, st))) return rc;      // variable bitrate: the handle's rates, recorded in the streams below
-    // the encoder may leave CDC_ARITH_F16X2 when hyper_dec overflows its range (checked outside the repetition only): the stream
-    // header records the arithmetic that was finally used and the decoder runs what the header says
-    if ((rc = hyperdec_batch(h, B, st, !h->in_retry))) return rc;
-    HIP_TRY(h, cdc::latent_symbols_launch(d_lat, nl, o.p, o.p + nl, o.bs(), h->ent->d_edges, nl, B, syml, bin, bad, st));
+    HIP_TRY(h, d.get(&meta, 2 * (size_t)B)); HIP_TRY(h, d.get(&d_off, (size_t)B + 1));
+    if (h->rdo_mu.empty()) {
+        HIP_TRY(h, cdc::latent_symbols_launch(d_lat, nl, o.p, o.p + nl, o.bs(), h->ent->d_edges, nl, B, syml, bin, bad, st));
+    } else {                                              // cdc_set_rdo: the same symbols, moved one step towards the mean where that pays
+        float *d_mu;
+        if ((rc = stage_rdo(h, B, &d, &d_mu, st))) return rc;
+        HIP_TRY(h, cdc::latent_symbols_rdo_launch(d_lat, nl, o.p, o.p + nl, o.bs(), h->ent->d_edges, nl, B, d_mu, syml, bin, bad, st));
+    }
     const cdc::EntropyDev T = h->ent->dev();
     HIP_TRY(h, cdc::rans_encode_launch(T, symh, nh, nullptr, 0, per, 0, (int)nh, 0u, B, sf, ew, sec_h, cap_h, esc_h, nh, meta, st));
     HIP_TRY(h, cdc::rans_encode_launch(T, syml, nl, bin, nl, 0, Ch, (int)nl, 1u, B, sf, ew, sec_l, cap_l, esc_l, nl, meta + B, st));
@@ -128,6 +177,7 @@ int entropy_encode_impl(cdc_handle *h, const float *latent, const float *hyper_l
                     h->vbr ? h->d_rate : nullptr, img_h, img_w};
     HIP_TRY(h, cdc::rans_pack_launch(P, B, st));
     std::vector<long long> hoff((size_t)B + 1);
+    int hbad = 0;
     HIP_TRY(h, hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipMemcpyAsync(hoff.data(), d_off, sizeof(long long) * ((size_t)B + 1), hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipStreamSynchronize(st));
@@ -141,6 +191,53 @@ int entropy_encode_impl(cdc_handle *h, const float *latent, const float *hyper_l
         return fail(h, CDC_ERR_NOMEM, "bitstream buffer too small: %d image(s) need %lld bytes of %zu", B, hoff[B], cap);
     HIP_TRY(h, hipMemcpy(out, packed, (size_t)hoff[B], hipMemcpyDeviceToHost));
     for (int b = 0; b <= B; ++b) offsets[b] = (size_t)hoff[b];
+    return CDC_OK;
+}
+
+// cdc_entropy_rate_sweep: the front end above, then one pass of rdo_sweep_kernel over the latent for the whole ladder
+int rate_sweep_impl(cdc_handle *h, const float *latent, const float *hyper_latent, const float *medians, int B, int hh, int wh,
+                    const float *mu, int L, double *bits, double *sse, int64_t *moved, int mem, void *stream) {
+    int rc = check_ready(h);
+    if (rc) return rc;
+    if (!latent || !hyper_latent || !medians || !mu || !bits || !sse || !moved || B < 1 || hh < 1 || wh < 1 || hh > 65535 || wh > 65535 ||
+        (long long)hh * wh > kMaxHyperPositions)
+        return fail(h, CDC_ERR_INVALID, "null/invalid argument");
+    if (L < 1 || L > cdc::kRdoMaxLadder) return fail(h, CDC_ERR_INVALID, "rate_sweep: a ladder of %d values (1 .. %d expected)", L, cdc::kRdoMaxLadder);
+    if ((rc = check_mu(h, "rate_sweep", mu, L))) return rc;
+    EncoderFront f;
+    if ((rc = encoder_front(h, latent, hyper_latent, medians, B, hh, wh, mem, stream, &f))) return rc;
+    if (!h->d_prior) return fail(h, CDC_ERR_STATE, "the prior.* tensors were not loaded");
+    DevPool &d = f.d;
+    hipStream_t st = f.st;
+    const Act &o = h->dec_outs[0];
+    const long long nh = f.nh, nl = f.nl;
+    const size_t parts = (size_t)cdc::rdo_sweep_parts(nl), np = (size_t)B * parts * L, nr = (size_t)B * L;
+    float *d_mu, *qh;
+    double *hb, *pb, *ps, *rb, *rs;
+    long long *pm, *rm;
+    HIP_TRY(h, d.get(&d_mu, (size_t)L)); HIP_TRY(h, d.get(&qh, (size_t)B * nh)); const int hparts = cdc::hyper_bits_parts(nh);
+    HIP_TRY(h, d.get(&hb, (size_t)B * hparts));
+    HIP_TRY(h, d.get(&pb, np)); HIP_TRY(h, d.get(&ps, np)); HIP_TRY(h, d.get(&pm, np));
+    HIP_TRY(h, d.get(&rb, nr)); HIP_TRY(h, d.get(&rs, nr)); HIP_TRY(h, d.get(&rm, nr));
+    h->rdo_stage.assign(mu, mu + L);
+    HIP_TRY(h, hipMemcpyAsync(d_mu, h->rdo_stage.data(), sizeof(float) * L, hipMemcpyHostToDevice, st));
+    // the hyper section's price, of the dequantised symbols the coder codes (sym + median: what cdc_entropy_decode returns)
+    HIP_TRY(h, cdc::symbols_to_hyper_launch(f.symh, h->ent->d_medians, f.Ch, f.per, B, qh, st));
+    HIP_TRY(h, cdc::hyper_bits_launch(qh, nh, f.per, h->d_prior, B, hb, st));
+    HIP_TRY(h, cdc::rdo_sweep_launch(f.d_lat, nl, o.p, o.p + nl, o.bs(), nl, B, d_mu, L, hb, hparts, pb, ps, pm, rb, rs, rm, f.bad, st));
+    int hbad = 0;
+    std::vector<double> tb(nr), ts(nr);
+    std::vector<long long> tm(nr);
+    HIP_TRY(h, hipMemcpyAsync(&hbad, f.bad, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(tb.data(), rb, sizeof(double) * nr, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(ts.data(), rs, sizeof(double) * nr, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(tm.data(), rm, sizeof(long long) * nr, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    if (hbad) {
+        if (h->in_retry) h->retry_futile = true;          // (as the encoder: the range was not the cause)
+        return fail(h, CDC_ERR_INVALID, "non-finite or out-of-range latent, mean or scale (nothing to price)");
+    }
+    for (size_t i = 0; i < nr; ++i) { bits[i] = tb[i]; sse[i] = ts[i]; moved[i] = (int64_t)tm[i]; }
     return CDC_OK;
 }
 
@@ -287,6 +384,60 @@ int cdc_entropy_encode_image(cdc_handle *h, const float *latent, const float *hy
     return no_throw(h, [&]() -> int {
         if (h && (img_h < 1 || img_w < 1)) return fail(h, CDC_ERR_INVALID, "image size %d x %d", img_h, img_w);
         return with_range_guard(h, [&] { return entropy_encode_impl(h, latent, hyper_latent, medians, B, hh, wh, img_h, img_w, out, cap, offsets, mem, stream); });
+    });
+}
+
+int cdc_set_rdo(cdc_handle *h, const float *mu, int n) {
+    if (!h) return CDC_ERR_INVALID;
+    if (int rc = require_kind(h, HandleKind::HyperDecoder)) return rc;
+    if (n < 0 || (n > 0 && !mu)) return fail(h, CDC_ERR_INVALID, "null/invalid argument");
+    if (int rc = check_mu(h, "cdc_set_rdo", mu, n)) return rc;
+    return no_throw(h, [&] { h->rdo_mu.assign(mu, mu + n); return CDC_OK; });
+}
+
+int cdc_entropy_rate_sweep(cdc_handle *h, const float *latent, const float *hyper_latent, const float *medians, int B, int hh, int wh,
+                           const float *mu, int L, double *bits, double *sse, int64_t *moved, int mem, void *stream) {
+    return no_throw(h, [&] {
+        return with_range_guard(h, [&] { return rate_sweep_impl(h, latent, hyper_latent, medians, B, hh, wh, mu, L, bits, sse, moved, mem, stream); });
+    });
+}
+
+int cdc_op_rdo_quantize(cdc_handle *h, const float *latent, const float *mean, const float *scale, const float *mu, float *q_latent,
+                        int64_t *moved, int B, long long per_image, int mem, void *stream) {
+    return no_throw(h, [&]() -> int {
+        int rc = check_ready(h);
+        if (rc) return rc;
+        if ((rc = require_kind(h, HandleKind::HyperDecoder))) return rc;
+        if (!latent || !mean || !scale || !mu || !q_latent || B < 1 || per_image < 1 || per_image > (1ll << 40) / B)
+            return fail(h, CDC_ERR_INVALID, "null/invalid argument");
+        if (mem != CDC_MEM_HOST && mem != CDC_MEM_DEVICE) return fail(h, CDC_ERR_INVALID, "rdo_quantize: mem_kind %d", mem);
+        if ((rc = check_mu(h, "rdo_quantize", mu, B))) return rc;
+        hipStream_t st = pick_stream(h, stream, mem);
+        Staging s(h, mem, st);
+        const size_t n = (size_t)B * (size_t)per_image;
+        const float *dy = s.in(latent, sizeof(float) * n), *dm = s.in(mean, sizeof(float) * n), *ds = s.in(scale, sizeof(float) * n);
+        float *d_mu = (float *)s.scratch(sizeof(float) * B);
+        int *bad = (int *)s.scratch(sizeof(int));
+        int hbad = 0;
+        if (s.ok()) {
+            HIP_TRY(h, hipStreamSynchronize(st));         // an earlier call's copy out of rdo_stage may still be queued
+            h->rdo_stage.assign(mu, mu + B);
+            s.e = hipMemcpyAsync(d_mu, h->rdo_stage.data(), sizeof(float) * B, hipMemcpyHostToDevice, st);
+        }
+        // the operands the coder refuses are refused here, before anything is written
+        if (s.ok()) s.e = hipMemsetAsync(bad, 0, sizeof(int), st);
+        if (s.ok()) s.e = cdc::rdo_check_launch(dy, dm, ds, (long long)n, bad, st);
+        if (s.ok()) s.e = hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st);
+        if (s.ok()) s.e = hipStreamSynchronize(st);
+        if (s.ok() && hbad) {
+            (void)s.finish("cdc_op_rdo_quantize");
+            return fail(h, CDC_ERR_INVALID, "rdo_quantize: non-finite or out-of-range latent, mean or scale (nothing written)");
+        }
+        float *dq = s.out(q_latent, sizeof(float) * n);
+        long long *dmv = moved ? s.out(reinterpret_cast<long long *>(moved), sizeof(long long) * B) : nullptr;
+        if (s.ok() && dmv) s.e = hipMemsetAsync(dmv, 0, sizeof(long long) * B, st);
+        if (s.ok()) s.e = cdc::rdo_quantize_launch(dy, dm, ds, d_mu, dq, dmv, B, per_image, st);
+        return s.finish("cdc_op_rdo_quantize");
     });
 }
 

@@ -246,6 +246,10 @@ struct cdc_handle {
     std::vector<float> vbr_rate;  // cdc_set_bitrate_scale: 1 value (broadcast) or one per image; empty until set
     std::vector<float> vbr_stage; // host staging of the per-image rates of the current call
     float *d_rate = nullptr;
+    // HyperDecoder: rate-distortion optimised quantisation in the entropy encoder (cdc_set_rdo): the price of a bit, 1 value (broadcast)
+    // or one per image; empty: off, and the encoder launches latent_symbols_kernel as it always did
+    std::vector<float> rdo_mu;
+    std::vector<float> rdo_stage; // host staging of the per-image mu (or of a sweep's ladder) of the current call
     int device = 0;
     int arith = default_arith();  // k x k / wide 1x1 convolutions: 1 two fp16 planes (3 MFMA products), 0 three bf16 planes (6)
     std::string err;

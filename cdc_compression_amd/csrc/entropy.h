@@ -44,6 +44,37 @@ hipError_t entropy_upload(EntropyModel *m, std::vector<void *> *allocs);
 // latent symbols round(latent - mean) and the scale bin of every position; *bad: something cannot be coded (non-finite, > int32)
 hipError_t latent_symbols_launch(const float *latent, long long latent_bs, const float *mean, const float *scale, long long ms_bs,
                                  const float *edges, long long n, int B, int32_t *sym, uint8_t *bin, int *bad, hipStream_t st);
+// the scale bin of a position: smallest i with s <= edges[i] (latent_symbols_kernel and its rate-distortion optimised twin)
+__device__ __forceinline__ int scale_bin(const float *edges, float s) {
+    int lo = 0, hi = kEntropyBins - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (s <= edges[mid]) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+// ---- rate-distortion optimised quantisation (rdo_kernels.hip; the decision: rdo_terms.h) ---------------------------------------
+constexpr int kRdoMaxLadder = 32;
+// latent_symbols_launch with the decision of rdo_terms.h at mu[b] (device, B values); mu[b] = 0 gives latent_symbols_launch's symbols
+hipError_t latent_symbols_rdo_launch(const float *latent, long long latent_bs, const float *mean, const float *scale, long long ms_bs,
+                                     const float *edges, long long n, int B, const float *mu, int32_t *sym, uint8_t *bin, int *bad, hipStream_t st);
+// *bad |= 1 when any of the n (latent, mean, scale) triples is one the coder refuses (non-finite, symbol beyond int32)
+hipError_t rdo_check_launch(const float *latent, const float *mean, const float *scale, long long n, int *bad, hipStream_t st);
+// q[b][i] = (float)k + mean[b][i] with k chosen at mu[b]; moved[b] += symbols with k != k0 (null: not counted; zeroed by the caller)
+hipError_t rdo_quantize_launch(const float *latent, const float *mean, const float *scale, const float *mu, float *q, long long *moved,
+                               int B, long long per, hipStream_t st);
+// per image b and ladder entry j < L <= kRdoMaxLadder: bits[b][j] = the hparts hyper partials of image b + the latent prices at mu[j],
+// sse[b][j] = sum (y - q)^2, moved[b][j]; pbits / psse / pmoved: work areas of B * rdo_sweep_parts(n) * L entries each.  *bad as
+// rdo_check_launch.
+int rdo_sweep_parts(long long n);
+hipError_t rdo_sweep_launch(const float *latent, long long latent_bs, const float *mean, const float *scale, long long ms_bs, long long n, int B,
+                            const float *mu, int L, const double *hyper_parts, int hparts, double *pbits, double *psse, long long *pmoved,
+                            double *bits, double *sse, long long *moved, int *bad, hipStream_t st);
+// out[b][p], p < hyper_bits_parts(nh): partial sums of the prior's price of the dequantised hyper-latent symbols qh[b][0 .. nh) in bits
+// (hw_h positions per channel; the float32 prices cdc_bpp sums)
+int hyper_bits_parts(long long nh);
+hipError_t hyper_bits_launch(const float *qh, long long nh, int hw_h, const float *prior, int B, double *out, hipStream_t st);
+
 hipError_t symbols_to_latent_launch(const int32_t *sym, const float *mean, long long mean_bs, long long n, int B, float *q, hipStream_t st);
 // hyper symbols round(hyper - median[c]) and the dequantised hyper-latent sym + median[c] (per = positions per channel)
 hipError_t hyper_symbols_launch(const float *hyper, const float *medians, int C, int per, int B, int32_t *sym, float *q, int *bad, hipStream_t st);

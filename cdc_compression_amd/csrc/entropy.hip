@@ -184,15 +184,7 @@ hipError_t entropy_upload(EntropyModel *m, std::vector<void *> *allocs) {
 }
 
 // ---- device side: the per-element work ---------------------------------------------------------------------------------
-__device__ __forceinline__ int scale_bin(const float *edges, float s) {
-    int lo = 0, hi = kEntropyBins - 1;              // smallest i with s <= edges[i]
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (s <= edges[mid]) hi = mid; else lo = mid + 1;
-    }
-    return lo;
-}
-
+// (scale_bin: entropy.h)
 // *bad is set when a value cannot be coded: a non-finite latent / mean / scale, or a symbol beyond the int32 range
 __global__ void __launch_bounds__(256) latent_symbols_kernel(const float *latent, long long latent_bs, const float *mean, const float *scale,
                                                              long long ms_bs, const float *edges, long long n, int32_t *sym, uint8_t *bin, int *bad) {

@@ -136,15 +136,41 @@ class _GaussianDiffusionBase:
                                            optr, omem, _current_stream(omem)))
         return out
 
-    def _context_of(self, images, *ctx_args, rate_map=False):
+    def _rdo_of(self, images, bitrate_scale=None, rdo=None, target_bpp=None, max_bytes=None):
+        """The rate-control arguments of compress / compress_best_of / compress_to_bytes, checked before the library is touched ->
+        the context model's mu (float32, 1 or B values) or None.  target_bpp / max_bytes: the context model chooses mu as its
+        compress_to_bytes does (compressor.py), and forward(rdo=mu) then runs with it."""
+        from . import compressor
+        compressor.rdo_exclusive(rdo, target_bpp, max_bytes)
+        B, _, H, W = frame.image_shape(images)
+        if rdo is not None:
+            mu = compressor.rdo_values(rdo, B)
+        for name, v in (("target_bpp", target_bpp), ("max_bytes", max_bytes)):
+            if v is not None:
+                compressor._ContextDecoder._targets(v, B, name)
+        if rdo is None and target_bpp is None and max_bytes is None:
+            return None
+        if not hasattr(self.context_fn, "rdo_quantize"):
+            raise ValueError("rdo / target_bpp / max_bytes need a context model of this package (rate-distortion optimised quantisation)")
+        if rdo is not None:
+            return mu
+        if self.padded_size(H, W) != self.context_fn.padded_size(H, W):
+            raise NotImplementedError("target_bpp / max_bytes choose mu on the context model's own frame: a U-Net that needs a larger one "
+                                      f"({self.padded_size(H, W)} against {self.context_fn.padded_size(H, W)}) cannot share it")
+        _, info = self.context_fn.compress_to_bytes(images, bitrate_scale, target_bpp=target_bpp, max_bytes=max_bytes, return_info=True)
+        return info["mu"]
+
+    def _context_of(self, images, *ctx_args, rate_map=False, rdo=None):
         """The context model on the padded frame of `images` -> (context_dict with bpp over H * W, B, H, W, Hp, Wp).  rate_map: the
-        dict also holds "rate_map" (this package's compressors only)."""
+        dict also holds "rate_map" (this package's compressors only).  rdo: the context model's mu (`_rdo_of`)."""
         B, _, H, W = frame.image_shape(images)
         Hp, Wp = self.padded_size(H, W)
         h, dev = self.denoise_fn._handle(), self.denoise_fn.device_index
         if rate_map and not hasattr(self.context_fn, "rate_map"):
             raise ValueError("maps=True needs a context model with rate_map() (a compressor of this package)")
-        if rate_map:
+        if rdo is not None:
+            context_dict = self.context_fn(images, *ctx_args, padded_hw=(Hp, Wp), return_rate_map=rate_map, rdo=rdo)
+        elif rate_map:
             context_dict = self.context_fn(images, *ctx_args, padded_hw=(Hp, Wp), return_rate_map=True)
         elif hasattr(self.context_fn, "_framed"):            # this package's compressor: pads itself, bpp over H * W
             context_dict = self.context_fn(images, *ctx_args, padded_hw=(Hp, Wp))        # x :216, eps :205
@@ -156,13 +182,13 @@ class _GaussianDiffusionBase:
         return context_dict, B, H, W, Hp, Wp
 
     def _compress_frame(self, images, sample_steps, init, eta, loop, *ctx_args, sampler="ddim", spacing="index", trace=None,
-                        rate_map=False):
+                        rate_map=False, rdo=None):
         """compress() of both trees up to the crop: context model and sampler on the padded frame -> (frame, bpp [B], H, W, Trajectory
         or None), and the context model's rate map of the frame as a sixth entry with rate_map=True.  trace: (trajectory,
         trajectory_of, trajectory_dtype, seed) of the call; loop(shape, context, init, spec, window)."""
         self._sampler_args(sampler, eta)
         spec = None if trace is None else self._trace_spec(*trace[:3], self._steps(sample_steps, spacing), eta, trace[3])
-        context_dict, B, H, W, Hp, Wp = self._context_of(images, *ctx_args, rate_map=rate_map)
+        context_dict, B, H, W, Hp, Wp = self._context_of(images, *ctx_args, rate_map=rate_map, rdo=rdo)
         h, dev = self.denoise_fn._handle(), self.denoise_fn.device_index
         self.set_sample_schedule(self._steps(sample_steps, spacing), sampler=sampler, spacing=spacing)
         rec = loop((B, 3, Hp, Wp), context_dict["output"], frame.extend_init(h, init, B, H, W, Hp, Wp, dev), spec, (H, W))
@@ -478,7 +504,7 @@ class _GaussianDiffusionBase:
         return window(mean), window(m2)
 
     def _best_of(self, images, samples, metric, seed, gamma, eta, sample_steps, sampler, spacing, sample_chunk, as_saved, clip_denoised,
-                 *ctx_args):
+                 *ctx_args, rdo=None):
         """compress_best_of of both trees."""
         from . import metrics
         K = _samples.check_args(samples, seed, gamma, eta, sample_chunk=sample_chunk, metric=metric)
@@ -490,7 +516,7 @@ class _GaussianDiffusionBase:
             raise ValueError(f"MS-SSIM needs min(H, W) > 160, got {H} x {W}")
         higher = _samples.METRICS[metric]
         all_seeds = sample_seeds(seed, B, K)
-        context_dict, B, H, W, Hp, Wp = self._context_of(images, *ctx_args)
+        context_dict, B, H, W, Hp, Wp = self._context_of(images, *ctx_args, rdo=rdo)
         context = context_dict["output"]
         self.set_sample_schedule(self._steps(sample_steps, spacing), sampler=sampler, spacing=spacing)
         un = self.denoise_fn
@@ -519,18 +545,29 @@ class _GaussianDiffusionBase:
                 "score": scores[np.arange(B), best_k], "scores": scores}
 
 
-    def compress_to_bytes(self, images, bitrate_scale=None):
+    def compress_to_bytes(self, images, bitrate_scale=None, rdo=None, target_bpp=None, max_bytes=None, return_info=False):
         """The transmitted half of compress(): images -> one entropy-coded bitstream per image.
         `decompress(streams, shape, sample_steps, init)` reconstructs from them.  bitrate_scale: the rate of a
         variable-bitrate context model (1 or B values), recorded in each stream.  Images of any size: a stream records H x W
-        unless the image is its own padded frame."""
-        _, _, H, W = frame.image_shape(images)
+        unless the image is its own padded frame.  rdo / target_bpp / max_bytes / return_info: the context model's rate control
+        (compressor.compress_to_bytes); the decoder side needs nothing."""
+        from . import compressor
+        compressor.rdo_exclusive(rdo, target_bpp, max_bytes)
+        B, _, H, W = frame.image_shape(images)
+        if rdo is not None:
+            compressor.rdo_values(rdo, B)
+        for name, v in (("target_bpp", target_bpp), ("max_bytes", max_bytes)):
+            if v is not None:
+                compressor._ContextDecoder._targets(v, B, name)
         if self.padded_size(H, W) != self.context_fn.padded_size(H, W):
             raise NotImplementedError("the stream records the image size against the context model's own multiple: a U-Net that needs a "
                                       f"larger one ({self.padded_size(H, W)} against {self.context_fn.padded_size(H, W)}) cannot share it")
+        kw = {k: v for k, v in (("rdo", rdo), ("target_bpp", target_bpp), ("max_bytes", max_bytes)) if v is not None}
+        if return_info:
+            kw["return_info"] = True
         if bitrate_scale is None:
-            return self.context_fn.compress_to_bytes(images)
-        return self.context_fn.compress_to_bytes(images, bitrate_scale)
+            return self.context_fn.compress_to_bytes(images, **kw)
+        return self.context_fn.compress_to_bytes(images, bitrate_scale, **kw)
 
 
 class GaussianDiffusionX(_GaussianDiffusionBase):
@@ -558,32 +595,36 @@ class GaussianDiffusionX(_GaussianDiffusionBase):
         return self._loop(tuple(shape), context, clip_denoised, init, eta, seed, gamma, sampler, spec, window)
 
     def _frame_of(self, images, sample_steps=None, init=None, eta=0, seed=None, gamma=None, sampler="ddim", spacing="index",
-                  trajectory=None, trajectory_of="x0", trajectory_dtype="float32", rate_map=False):
+                  trajectory=None, trajectory_of="x0", trajectory_dtype="float32", rate_map=False, rdo=None):
         self._seed_args(seed, gamma, init, frame.image_shape(images)[0])
         return self._compress_frame(images, sample_steps, init, eta,
                                     lambda shape, ctx, i, spec, win: self.p_sample_loop(shape, ctx, clip_denoised=True, init=i, eta=eta,
                                                                                         seed=seed, gamma=gamma, trajectory=spec,
                                                                                         window=win),   # :223
                                     sampler=sampler, spacing=spacing, trace=(trajectory, trajectory_of, trajectory_dtype, seed),
-                                    rate_map=rate_map)
+                                    rate_map=rate_map, rdo=rdo)
 
     def compress(self, images, sample_steps=None, bpp_return_mean=True, init=None, eta=0, seed=None, gamma=None, sampler="ddim",
-                 spacing="index", trajectory=None, trajectory_of="x0", trajectory_dtype="float32"):
-        """trajectory=: -> (reconstruction, bpp, Trajectory) (cdc_compression_amd.trajectory)."""
+                 spacing="index", trajectory=None, trajectory_of="x0", trajectory_dtype="float32", rdo=None, target_bpp=None,
+                 max_bytes=None):
+        """trajectory=: -> (reconstruction, bpp, Trajectory) (cdc_compression_amd.trajectory).  rdo / target_bpp / max_bytes: the
+        context model's rate control (compressor.compress_to_bytes); bpp is that of the symbols it chose."""
+        mu = self._rdo_of(images, None, rdo, target_bpp, max_bytes)
         rec, bpp, H, W, traj = self._frame_of(images, sample_steps, init, eta, seed, gamma, sampler, spacing, trajectory, trajectory_of,
-                                              trajectory_dtype)
+                                              trajectory_dtype, rdo=mu)
         res = (self._window(rec, H, W), (bpp.mean() if bpp_return_mean else bpp))
         return res if traj is None else res + (traj,)
 
 
     def compress_best_of(self, images, samples, metric="psnr", seed=None, gamma=None, eta=0, sample_steps=None, sampler="ddim",
-                         spacing="index", sample_chunk=None, as_saved=True):
+                         spacing="index", sample_chunk=None, as_saved=True, rdo=None, target_bpp=None, max_bytes=None):
         """The encoder's closed loop: the context model once, then `samples` seeded decodes per image (seeds
         parallel.sample_seeds(seed, B, samples)), each scored on the device against `images` on the frame's H x W window
         (metric "psnr" / "ms_ssim": higher is better; "lpips": lower, needs self.loss_fn_vgg; ties go to the lowest k, a NaN never
         beats a number) -> {"reconstruction": the winner's window, "bpp": [B], "seed": uint64 [B], ready for decompress(..., seed=),
-        "sample": int [B], "score": [B], "scores": [B, samples]}."""
-        return self._best_of(images, samples, metric, seed, gamma, eta, sample_steps, sampler, spacing, sample_chunk, as_saved, True)
+        "sample": int [B], "score": [B], "scores": [B, samples]}.  rdo / target_bpp / max_bytes: as compress()."""
+        mu = self._rdo_of(images, None, rdo, target_bpp, max_bytes)
+        return self._best_of(images, samples, metric, seed, gamma, eta, sample_steps, sampler, spacing, sample_chunk, as_saved, True, rdo=mu)
 
 
 class GaussianDiffusionEps(_GaussianDiffusionBase):
@@ -612,25 +653,29 @@ class GaussianDiffusionEps(_GaussianDiffusionBase):
         return self._loop(tuple(shape), context, self.clip_noise, init, eta, seed, gamma, sampler, spec, window)
 
     def _frame_of(self, images, sample_steps=None, bitrate_scale=None, sample_mode="ddpm", init=None, eta=0, seed=None, gamma=None,
-                  sampler="ddim", spacing="index", trajectory=None, trajectory_of="x0", trajectory_dtype="float32", rate_map=False):
+                  sampler="ddim", spacing="index", trajectory=None, trajectory_of="x0", trajectory_dtype="float32", rate_map=False,
+                  rdo=None):
         self._seed_args(seed, gamma, init, frame.image_shape(images)[0])
         return self._compress_frame(images, sample_steps, init, eta,
                                     lambda shape, ctx, i, spec, win: self.p_sample_loop(shape, ctx, sample_mode, init=i, eta=eta, seed=seed,
                                                                                         gamma=gamma, trajectory=spec, window=win),
                                     bitrate_scale, sampler=sampler, spacing=spacing,
-                                    trace=(trajectory, trajectory_of, trajectory_dtype, seed), rate_map=rate_map)
+                                    trace=(trajectory, trajectory_of, trajectory_dtype, seed), rate_map=rate_map, rdo=rdo)
 
     def compress(self, images, sample_steps=None, bitrate_scale=None, sample_mode="ddpm",
                  bpp_return_mean=True, init=None, eta=0, seed=None, gamma=None, sampler="ddim", spacing="index",
-                 trajectory=None, trajectory_of="x0", trajectory_dtype="float32"):
-        """trajectory=: -> (reconstruction, bpp, Trajectory) (cdc_compression_amd.trajectory)."""
+                 trajectory=None, trajectory_of="x0", trajectory_dtype="float32", rdo=None, target_bpp=None, max_bytes=None):
+        """trajectory=: -> (reconstruction, bpp, Trajectory) (cdc_compression_amd.trajectory).  rdo / target_bpp / max_bytes: as
+        GaussianDiffusionX.compress."""
+        mu = self._rdo_of(images, bitrate_scale, rdo, target_bpp, max_bytes)
         rec, bpp, H, W, traj = self._frame_of(images, sample_steps, bitrate_scale, sample_mode, init, eta, seed, gamma, sampler, spacing,
-                                              trajectory, trajectory_of, trajectory_dtype)
+                                              trajectory, trajectory_of, trajectory_dtype, rdo=mu)
         res = (self._window(rec, H, W), (bpp.mean() if bpp_return_mean else bpp))
         return res if traj is None else res + (traj,)
 
     def compress_best_of(self, images, samples, metric="psnr", seed=None, gamma=None, eta=0, sample_steps=None, sampler="ddim",
-                         spacing="index", sample_chunk=None, as_saved=True, bitrate_scale=None):
+                         spacing="index", sample_chunk=None, as_saved=True, bitrate_scale=None, rdo=None, target_bpp=None, max_bytes=None):
         """GaussianDiffusionX.compress_best_of with this tree's context argument (bitrate_scale of a variable-bitrate model)."""
+        mu = self._rdo_of(images, bitrate_scale, rdo, target_bpp, max_bytes)
         return self._best_of(images, samples, metric, seed, gamma, eta, sample_steps, sampler, spacing, sample_chunk, as_saved,
-                             self.clip_noise, bitrate_scale)
+                             self.clip_noise, bitrate_scale, rdo=mu)

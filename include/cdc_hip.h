@@ -620,6 +620,50 @@ int cdc_rate_map(cdc_handle *hyperdec, const float *q_hyper_latent, const float 
 int cdc_distortion_map(cdc_handle *h, const cdc_image_view *a, const cdc_image_view *b, int B, int H, int W, int cell, int gh, int gw,
                        double *sse /*[B][gh][gw]*/, int32_t *count /*[B][gh][gw] or NULL*/, int mem_kind, void *stream);
 
+/* ---- rate-distortion optimised quantisation and the rate of a ladder of mu (csrc/rdo_terms.h, csrc/rdo_kernels.hip) -------------
+ * The hyperprior is not autoregressive: given q_hyper_latent, a latent symbol is priced by its own (mean, scale) alone.  Choosing per
+ * symbol between the nearest integer and its neighbour towards the mean by distortion + mu * bits is therefore separable: no trellis,
+ * no second pass, and the decoder never learns mu (the streams are the streams cdc_entropy_decode always read).
+ * THE DECISION, for a latent value y with (mean m, scale s) and the price of a bit mu >= 0, all float32, operation by operation:
+ *   d  = y - m                k0 = rintf(d)                         today's symbol
+ *   k1 = k0 - sign(k0)        (k0 != 0 only)                        its neighbour towards the mean
+ *   dR = bits(k0 + m, m, s) - bits(k1 + m, m, s)                    bits = the Gaussian price of cdc_bpp / cdc_rate_map:
+ *                                                                   -log2 max(Phi((.5 - |x - m|) / s) - Phi((-.5 - |x - m|) / s), 1e-9)
+ *   e  = |d| - |k0|           dD = 2 e + 1                          = (d - k1)^2 - (d - k0)^2, in [0, 2]
+ *   move (code k1 in place of k0)  <=>  k0 != 0  and  mu * dR > dD
+ * dR and dD do not depend on mu and a float32 product is monotone in mu: a symbol that moves at mu moves at every larger mu.  mu = 0
+ * never moves; where both prices sit on the 1e-9 clamp dR = 0 and nothing moves; |q - y| <= 1.5 always.  The hyper-latent symbols are
+ * never touched: one of them changes (mean, scale) of U^2 C latent symbols, so its choice is not separable.
+ * The decision uses the ESTIMATE's price (what cdc_bpp sums), not the coder's integer tables; what it does to decoded images of trained
+ * weights has not been measured.
+ *
+ * cdc_set_rdo: state of a hyper-decoder handle, like cdc_set_bitrate_scale.  n = 0 turns it off (mu may be NULL); n = 1 is one mu for
+ *   every image; n = B one per image.  mu is a HOST array, copied before the call returns.  CDC_ERR_INVALID for a negative or
+ *   non-finite value, CDC_ERR_STATE for another handle kind.  While set, cdc_entropy_encode / cdc_entropy_encode_image choose every
+ *   latent symbol by the decision at the image's mu (a call whose batch is neither 1 nor n images: CDC_ERR_INVALID); everything else,
+ *   container versions included, is unchanged.  Image b's stream depends on its own mu only (the batch = batch-1 contract holds), and a
+ *   mu of exactly 0 gives the bytes of a handle with nothing set.
+ * cdc_entropy_rate_sweep: what a ladder mu[L] (HOST array, 1 <= L <= 32, finite and >= 0) would cost, from ONE pass over the latent.  It
+ *   runs the encoder's own front end (hyper symbols -> hyper_dec through the batch-1 plan -> mean / scale), so the decisions are priced
+ *   with exactly the mean and scale the coder uses; latent / hyper_latent / medians / B / h_hyper / w_hyper / mem_kind / stream as for
+ *   cdc_entropy_encode.  bits, sse and moved are HOST arrays [B][L], and the call synchronises:
+ *     bits[b][j]   the prior's price of the hyper symbols, summed as cdc_bpp sums it, + the Gaussian prices of the latent symbols at mu[j]
+ *     sse[b][j]    sum over the latent of (y - q)^2 in float64, q = (float)k + mean the float32 value the decoder reconstructs
+ *     moved[b][j]  latent symbols with k != k0
+ *   Sums are float64 in an order fixed by the latent's size: no atomics, the same bits whatever the batch, the row or the run.  bits is
+ *   non-increasing and sse / moved non-decreasing in mu, exactly.  The range guard applies as for the encoder; a non-finite operand
+ *   is CDC_ERR_INVALID.
+ * cdc_op_rdo_quantize: the decision as an op on caller-supplied operands [B][per_image] (a hyper-decoder handle): q_latent =
+ *   (float)k + mean at mu[b] (HOST array of B values), moved[b] (may be NULL) the symbols with k != k0.  latent / mean / scale /
+ *   q_latent / moved follow mem_kind.  An operand the coder refuses (non-finite, a symbol beyond int32) is CDC_ERR_INVALID with
+ *   nothing written. */
+int cdc_set_rdo(cdc_handle *hyperdec, const float *mu, int n);
+int cdc_entropy_rate_sweep(cdc_handle *hyperdec, const float *latent, const float *hyper_latent, const float *medians, int B,
+                           int h_hyper, int w_hyper, const float *mu, int L, double *bits /*[B][L]*/, double *sse /*[B][L]*/,
+                           int64_t *moved /*[B][L]*/, int mem_kind, void *stream);
+int cdc_op_rdo_quantize(cdc_handle *hyperdec, const float *latent, const float *mean, const float *scale, const float *mu /*[B] host*/,
+                        float *q_latent, int64_t *moved /*[B] or NULL*/, int B, long long per_image, int mem_kind, void *stream);
+
 /* ---- LPIPS-VGG of decoded images on the device: the perceptual axis (csrc/lpips_kernels.hip, build_lpips_program) ----------------
  * THE DEFINITION.  LPIPS of the lpips package, version 0.1.4: LPIPS(net="vgg", lpips=True, spatial=False).forward(in0, in1,
  * normalize=False), per image.  The reference trains with it (xparam/modules/denoising_diffusion.py:47,331-336) and its checkpoints
