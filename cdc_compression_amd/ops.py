@@ -27,6 +27,20 @@ class Ops:
             return cfg
         self._lh = _lib.Handle("cdc_create", config, _lib.device_index_of(device))
         self._h = self._lh.ptr
+        self._first_op = 0
+
+    def _mark(self):
+        self._first_op = _lib.lib().cdc_prof_num_ops(self._h)
+
+    def last_labels(self):
+        """The lines of the per-op table (include/cdc_hip.h: cdc_prof_op) of the ops the last conv2d / conv_transpose2d call planned, in
+        launch order: which kernel family ran it (csrc/cdc_state.h: op_label).  A call repeated by the range guard lists them twice."""
+        L, out = _lib.lib(), []
+        for i in range(self._first_op, L.cdc_prof_num_ops(self._h)):
+            lab = ctypes.c_char_p()
+            L.cdc_prof_op(self._h, i, ctypes.byref(lab), None, None, None)
+            out.append(lab.value.decode())
+        return out
 
     def status(self):
         """{"arith", "range_faults", "nonfinite_results"} of this handle (range guard of the fp16 arithmetic)."""
@@ -68,6 +82,7 @@ class Ops:
         y = np.empty((B, Cout, Ho, Wo), np.float32)
         if ln_g is not None:
             ln_g, ln_b = ln_g.reshape(-1), ln_b.reshape(-1)
+        self._mark()
         _lib.check(self._h, _lib.lib().cdc_op_conv2d(
             self._h, _p(x), _p(w), _p(b), _p(y), B, Cin, H, W, Cout, KH, KW, stride, padding, _p(ln_g),
             _p(ln_b), int(relu), _p(shift), _p(resid)))
@@ -78,6 +93,7 @@ class Ops:
         B, Cin, H, W = x.shape
         Cout = w.shape[1]
         y = np.empty((B, Cout, 2 * H, 2 * W), np.float32)
+        self._mark()
         _lib.check(self._h, _lib.lib().cdc_op_conv_transpose2d(self._h, _p(x), _p(w), _p(b), _p(y), B,
                                                                Cin, H, W, Cout))
         return y

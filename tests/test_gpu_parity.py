@@ -16,6 +16,7 @@ from cdc_compression_amd.ops import Ops
 from oracle import model as om
 from oracle import ops as oops
 import attention_ref
+from conv_ref import family_of
 from helpers import GOLDEN, digest_idx, load_case, oracle_cfg
 
 pytestmark = pytest.mark.gpu
@@ -93,6 +94,16 @@ PF3_CASES = [
 ]
 
 
+def _ran(G, family, arith=1):
+    """The last convolution call of `G` was on the kernel `family` (tests/conv_ref.py: family_of reads the per-op labels of the call) and left
+    a clean status: the arithmetic asked for, no range fault (the entry point would have repeated the call in bf16x3 and the comparison
+    would pass on the other arithmetic), no non-finite result."""
+    labels = G.last_labels()
+    ran = [family_of(l) for l in labels if family_of(l)]
+    assert ran == [family], (family, labels)
+    assert G.status() == {"arith": arith, "range_faults": 0, "nonfinite_results": 0}, G.status()
+
+
 @pytest.mark.parametrize("case", CONV_CASES)
 def test_conv2d_matches_oracle(O, G, case):
     B, Ci, H, W, Co, k, s, p, fused = case
@@ -113,13 +124,17 @@ def test_conv2d_matches_oracle(O, G, case):
         assert relerr(g2, r2) < 1e-5, relerr(g2, r2)
 
 
-def _conv_check(O, G, case, tol_plain=1e-5, tol_fused=1e-5):
+def _conv_check(O, G, case, tol_plain=1e-5, tol_fused=1e-5, family=None, arith=1):
+    """family: the kernel family of the bias-only call, or (that, the family of the call with LayerNorm + ReLU + shift + residual)."""
+    plain_family, fused_family = family if isinstance(family, tuple) else (family, family)
     B, Ci, H, W, Co, k, s, p, fused = case
     x = synth.normal("cx", (B, Ci, H, W), 21)
     w = synth.normal("cw", (Co, Ci, k, k), 21, 1.0 / np.sqrt(Ci * k * k))
     b = synth.normal("cb", (Co,), 21, 0.1)
     ref = O.conv2d(x, w, b, s, p)
     got = G.conv2d(x, w, b, s, p)
+    if plain_family:
+        _ran(G, plain_family, arith)
     assert relerr(got, ref) < tol_plain, relerr(got, ref)
     if fused:
         g = synth.normal("cg", (Co,), 21, 0.2, 1.0)
@@ -128,6 +143,8 @@ def _conv_check(O, G, case, tol_plain=1e-5, tol_fused=1e-5):
         resid = synth.normal("cr", ref.shape, 21)
         r2 = np.maximum(O.chan_layernorm(ref, g, bb), 0) + shift[:, :, None, None] + resid
         g2 = G.conv2d(x, w, b, s, p, ln_g=g, ln_b=bb, relu=True, shift=shift, resid=resid)
+        if fused_family:
+            _ran(G, fused_family, arith)
         assert relerr(g2, r2) < tol_fused, relerr(g2, r2)
 
 
@@ -140,15 +157,32 @@ def test_conv2d_persistent_ping_pong_kernel(O, case, walk, monkeypatch):
     monkeypatch.setenv("CDC_PF_MAXPIX", "0")
     if walk == "row-major":
         monkeypatch.setenv("CDC_PF3_XMAJOR", "1")
-    _conv_check(O, Ops(0), case)
+    _conv_check(O, Ops(0), case, family="pf" if case == PF3_CASES[3] else "pf3")
 
 
 @pytest.mark.parametrize("case", PF_CASES + CONV_CASES[4:6])
 def test_conv2d_pre_split_operand_kernel(O, case, monkeypatch):
-    """conv_pf_kernel (CDC_PF=1): activations arrive as two fp16 planes by LDS-DMA; every tile shape of its planner."""
+    """CDC_PF=1 on the shapes of conv_pf_kernel's tile table.  As single launches these are few-pixel launches: the planner puts every one
+    of them on conv_ws_kernel, conv_ws1_kernel or conv_split2 (asserted per case; the tile shapes themselves run inside the network
+    programs).  test_conv2d_on_the_plane_operand_kernel below holds conv_pf_kernel itself to the oracle."""
     monkeypatch.setenv("CDC_PF", "1")
     monkeypatch.setenv("CDC_PF_MAXPIX", "0")
-    _conv_check(O, Ops(0), case)
+    _conv_check(O, Ops(0), case, family=PF_CASE_FAMILY[case])
+
+
+PF_CASE_FAMILY = {   # (bias-only call, call with LayerNorm + ReLU + shift + residual) under CDC_PF=1 CDC_PF_MAXPIX=0
+    PF_CASES[0]: "ws", PF_CASES[1]: "ws", PF_CASES[2]: "ws", PF_CASES[3]: "ws1", PF_CASES[4]: "split2h", PF_CASES[5]: "split2h", PF_CASES[6]: "split2h",
+    CONV_CASES[4]: "ws", CONV_CASES[5]: "split2h"}
+
+
+@pytest.mark.parametrize("case", PF_CASES[1:4])
+def test_conv2d_on_the_plane_operand_kernel(O, case, monkeypatch):
+    """conv_pf_kernel itself (activations arrive as two fp16 planes by LDS-DMA) on the launches tests/test_gpu_determinism.py runs on it,
+    with its switches: never the weight-stationary kernel, small launches stay on the plane kernels, and the call fails instead of
+    falling back."""
+    for k, v in {"CDC_PF": "1", "CDC_PF_MAXPIX": "0", "CDC_WS_MIN_WGS": "1000000000", "CDC_PF_MIN_WAVES": "1", "CDC_OP_REQUIRE_PF": "1"}.items():
+        monkeypatch.setenv(k, v)
+    _conv_check(O, Ops(0), case, family="pf")
 
 
 PF_S2_CASES = [
@@ -195,8 +229,11 @@ def test_conv2d_weight_stationary_kernel(O, case, npb, monkeypatch):
     r2 = np.maximum(O.chan_layernorm(ref, g, bb), 0) + shift[:, :, None, None] + resid
     G2 = Ops(0)
     g2 = G2.conv2d(x, w, b, s, p, ln_g=g, ln_b=bb, relu=True, shift=shift, resid=resid)
+    _ran(G2, "ws")
+    assert f"NPB{npb}" in G2.last_labels()[0], G2.last_labels()
     assert relerr(g2, r2) < 1e-5, relerr(g2, r2)
     assert relerr(G2.conv2d(x, w, b, s, p), ref) < 1e-5
+    _ran(G2, "ws")
 
 
 @pytest.mark.parametrize("case", [(2, 320, 16, 16, 320), (1, 256, 32, 32, 256), (1, 64, 64, 64, 64), (3, 192, 32, 64, 192), (1, 128, 64, 32, 96)])
@@ -211,7 +248,10 @@ def test_conv2d_stride2_weight_stationary_kernel(O, case, monkeypatch):
     w = synth.normal("cw", (Co, Ci, 3, 3), 41, 1.0 / np.sqrt(Ci * 9))
     b = synth.normal("cb", (Co,), 41, 0.1)
     ref = O.conv2d(x, w, b, 2, 1)
-    got = Ops(0).conv2d(x, w, b, 2, 1)
+    G2 = Ops(0)
+    got = G2.conv2d(x, w, b, 2, 1)
+    _ran(G2, "ws")
+    assert " s2 " in G2.last_labels()[0], G2.last_labels()
     assert got.shape == ref.shape and relerr(got, ref) < 1e-5, relerr(got, ref)
 
 
@@ -225,8 +265,8 @@ WS1_CASES = [
 @pytest.mark.parametrize("npb", ["2", "4"])
 @pytest.mark.parametrize("case", WS1_CASES)
 def test_conv2d_pointwise_few_pixel_kernel(O, case, npb, monkeypatch):
-    """bias-only and bias + per-image shift + residual 1x1 convolutions on conv_ws1_kernel against the oracle (64- and 128-pixel tiles;
-    a case whose batch does not divide into the forced tile stays on the round-4 kernels and is still checked)."""
+    """bias-only and bias + per-image shift + residual 1x1 convolutions on conv_ws1_kernel against the oracle (64- and 128-pixel tiles).
+    One case, 96 pixels, does not divide into the kernel's tiles: it is on conv_split2 and is still checked, under that name."""
     monkeypatch.setenv("CDC_WS1_MIN_WGS", "1")
     monkeypatch.setenv("CDC_WS1_NPB", npb)
     from cdc_compression_amd.ops import Ops
@@ -238,8 +278,12 @@ def test_conv2d_pointwise_few_pixel_kernel(O, case, npb, monkeypatch):
     ref = O.conv2d(x, w, b, 1, 0)
     resid = synth.normal("cr", ref.shape, 31)
     G2 = Ops(0)
+    family = "split2h" if case == (1, 64, 4, 24, 96) else "ws1"
     assert relerr(G2.conv2d(x, w, b, 1, 0), ref) < 1e-5
+    _ran(G2, family)
+    assert family != "ws1" or f"NPB{npb}" in G2.last_labels()[0], G2.last_labels()
     got = G2.conv2d(x, w, b, 1, 0, shift=shift, resid=resid)
+    _ran(G2, family)
     assert relerr(got, ref + shift[:, :, None, None] + resid) < 1e-5
 
 
@@ -287,12 +331,16 @@ def test_conv2d_stride2_on_plane_operands(O, case, monkeypatch):
     monkeypatch.setenv("CDC_PF_MAXPIX", "0")
     monkeypatch.setenv("CDC_PF_S2_MIN_WGS", "1")
     monkeypatch.setenv("CDC_OP_REQUIRE_PF", "1")      # fails instead of falling back to the register-staged kernel
-    _conv_check(O, Ops(0), case)
+    _conv_check(O, Ops(0), case, family="pf s2")
 
 
 PW_CASES = [  # B, Cin, H, W, Cout: every tile shape of conv_pw_kernel's planner, ragged rows, linear (narrow-map) tiles
     (2, 64, 36, 64, 64), (1, 128, 20, 32, 128), (2, 256, 32, 32, 256), (1, 96, 64, 64, 192), (1, 64, 40, 96, 384),
-    (3, 320, 16, 16, 128), (4, 384, 8, 8, 256), (1, 48, 12, 16, 64)]
+    (3, 320, 16, 16, 128), (4, 384, 8, 8, 256), (1, 48, 12, 16, 64),
+    (2, 192, 64, 64, 384)]    # (the launch tests/test_gpu_determinism.py has on conv_pw_kernel: three channel groups)
+# Of these only the first and the last are on conv_pw_kernel as single launches; the others are launches of at most 128 pixel blocks,
+# which conv_ws1_kernel takes (Builder::try_ws1 comes first).  Each is held to the family it runs.
+PW_ON_PW = {(2, 64, 36, 64, 64), (2, 192, 64, 64, 384)}
 
 
 def test_conv2d_pointwise_kernel_4_byte_activation_pieces(O, monkeypatch):
@@ -305,6 +353,7 @@ def test_conv2d_pointwise_kernel_4_byte_activation_pieces(O, monkeypatch):
         w = synth.normal("pw", (Co, Ci, 1, 1), 25, 1.0 / np.sqrt(Ci))
         b = synth.normal("pb", (Co,), 25, 0.1)
         assert relerr(G2.conv2d(x, w, b, 1, 0), O.conv2d(x, w, b, 1, 0)) < 1e-5
+        _ran(G2, "pw" if (B, Ci, H, W, Co) in PW_ON_PW else "ws1")      # (only the first is on conv_pw_kernel, where the switch acts)
 
 
 @pytest.mark.parametrize("case", PW_CASES)
@@ -318,17 +367,21 @@ def test_conv2d_pointwise_kernel(O, case, monkeypatch):
     w = synth.normal("pw", (Co, Ci, 1, 1), 27, 1.0 / np.sqrt(Ci))
     b = synth.normal("pb", (Co,), 27, 0.1)
     ref = O.conv2d(x, w, b, 1, 0)
+    family = "pw" if case in PW_ON_PW else "ws1"
     assert relerr(G2.conv2d(x, w, b, 1, 0), ref) < 1e-5
+    _ran(G2, family)
     resid = synth.normal("pr", ref.shape, 27)
     r2 = ref + resid
     assert relerr(G2.conv2d(x, w, b, 1, 0, resid=resid), r2) < 1e-5
+    _ran(G2, family)
 
 
 @pytest.mark.parametrize("case", [CONV_CASES[4], CONV_CASES[6], CONV_CASES[7], CONV_CASES[10], CONV_CASES[11]] + PF_CASES[:2])
 def test_conv2d_three_plane_bf16_arithmetic(O, case, monkeypatch):
     """CDC_ARITH=0: the exact three-way bf16 split (six MFMA products) stays available as the full-range path."""
     monkeypatch.setenv("CDC_ARITH", "0")
-    _conv_check(O, Ops(0), case)
+    # (the 128-channel fused LayerNorm form has no conv_split2 instantiation in this arithmetic: conv_split_kernel)
+    _conv_check(O, Ops(0), case, family=("split2", "split" if case == PF_CASES[0] else "split2"), arith=0)
 
 
 @pytest.mark.parametrize("case", [(2, 5, 6, 7, 4), (1, 64, 16, 16, 64), (1, 320, 8, 8, 320),
@@ -364,7 +417,9 @@ def test_conv_transpose2d_fused_phases_on_plane_operands(O, case, plan, monkeypa
     w = synth.normal("tw", (Ci, Co, 4, 4), 22, 1.0 / np.sqrt(Ci * 4))
     b = synth.normal("tb", (Co,), 22, 0.1)
     ref = O.conv_transpose2d(x, w, b, 2, 1)
-    got = Ops(0).conv_transpose2d(x, w, b)
+    G2 = Ops(0)
+    got = G2.conv_transpose2d(x, w, b)
+    _ran(G2, "pf tz4")
     assert relerr(got, ref) < 1e-5, relerr(got, ref)
 
 
