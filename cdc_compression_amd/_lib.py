@@ -143,6 +143,9 @@ def lib():
     L.cdc_set_rdo.argtypes = [H, _vp, _i]
     L.cdc_entropy_rate_sweep.argtypes = [H, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp]
     L.cdc_op_rdo_quantize.argtypes = [H, _vp, _vp, _vp, _vp, _vp, _vp, _i, ctypes.c_longlong, _i, _vp]
+    L.cdc_price_cells.argtypes = [H, _vp] + [_i] * 9 + [_vp, _i, _vp]
+    L.cdc_set_rdo_map.argtypes = [H, _vp, _i, _i, _i, _i, _vp]
+    L.cdc_op_rdo_quantize_map.argtypes = [H, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp]
     L.cdc_lpips_create.argtypes = [_i, ctypes.POINTER(H)]
     L.cdc_lpips.argtypes = [H, ctypes.POINTER(ImageView), ctypes.POINTER(ImageView), _i, _i, _i, f64p, f64p, _i, _vp]
     L.cdc_dequantize.argtypes = [H, _vp, _vp, _vp, ctypes.c_longlong, _i, _vp]
@@ -214,7 +217,8 @@ EXPORTS = ["cdc_create", "cdc_destroy", "cdc_last_error", "cdc_version", "cdc_nu
            "cdc_set_solver", "cdc_decode_solver", "cdc_solver_step", "cdc_op_solver_update", "cdc_op_ddim_update",
            "cdc_repeat_images", "cdc_decode_samples", "cdc_sample_moments", "cdc_sample_select",
            "cdc_set_trace", "cdc_trace_info", "cdc_trace_read", "cdc_op_trace_tap",
-           "cdc_rate_map", "cdc_distortion_map", "cdc_set_rdo", "cdc_entropy_rate_sweep", "cdc_op_rdo_quantize"]
+           "cdc_rate_map", "cdc_distortion_map", "cdc_set_rdo", "cdc_entropy_rate_sweep", "cdc_op_rdo_quantize",
+           "cdc_price_cells", "cdc_set_rdo_map", "cdc_op_rdo_quantize_map"]
 
 
 def handle_status(handle):

@@ -30,13 +30,18 @@ bit, a scalar or B values -- makes the quantiser code, per latent symbol, the ne
 where mu * (bits saved) exceeds the squared error added.  `encode`, `forward`, `latents_to_bytes` and `compress_to_bytes` take it;
 `compress_to_bytes(target_bpp= | max_bytes=)` finds mu per image from `rate_sweep`'s one-pass curve.  The streams keep their format and
 the decoder never learns mu; `rdo=None` runs what always ran.  What the moves do to decoded images of trained weights is unmeasured.
+
+Region-of-interest coding (include/cdc_hip.h: cdc_set_rdo_map): with any of the three, `price_map=` -- a map in pixels at the image's
+own size -- or `price_cells=` -- its cells on the latent grid, `price_cells()` -- makes the price of a bit mu * map per latent position:
+0 protects a region, values above 1 make one pay.  The decision stays separable, so the streams and the decoder are untouched, and
+`target_bpp` / `max_bytes` search the base mu under the map.  What a map does to decoded images of trained weights is unmeasured too.
 """
 import ctypes
 
 import numpy as np
 
 from . import _lib, frame
-from .unet import _Arg, _as_host_f32, _current_stream, _result_like
+from .unet import _Arg, _as_host_f32, _current_stream, _is_torch, _result_like
 
 
 class NormalDistribution:
@@ -75,6 +80,84 @@ def rdo_exclusive(rdo=None, target_bpp=None, max_bytes=None):
     given = [n for n, v in (("rdo", rdo), ("target_bpp", target_bpp), ("max_bytes", max_bytes)) if v is not None]
     if len(given) > 1:
         raise ValueError(f"{' and '.join(given)} exclude each other: give one of rdo, target_bpp, max_bytes")
+
+
+def price_map_values(price_map, B, H, W):
+    """A pixel-domain price map -> float32 [n, H, W] (NumPy, or a torch tensor on its own device), checked before the library is
+    touched.  Accepted: [H, W], [1, H, W], [B, H, W] or [B, 1, H, W] at the image's own size, float32 or bool (cast), finite and >= 0.
+    B=None: any number of rows."""
+    t = price_map
+    torch_like = _is_torch(t)
+    if torch_like:
+        import torch
+        if t.dtype == torch.bool:
+            t = t.to(torch.float32)
+        ok = t.dtype == torch.float32
+    else:
+        t = np.asarray(t)
+        if t.dtype == np.bool_:
+            t = t.astype(np.float32)
+        ok = t.dtype == np.float32
+    if not ok:
+        raise ValueError(f"price_map must be float32 or bool, got {t.dtype}")
+    shape = tuple(int(d) for d in t.shape)
+    if len(shape) == 4 and shape[1] == 1:
+        shape = (shape[0],) + shape[2:]
+    elif len(shape) == 2:
+        shape = (1,) + shape
+    if len(shape) != 3 or shape[1:] != (int(H), int(W)) or (B is not None and shape[0] not in (1, B)) or shape[0] < 1:
+        raise ValueError(f"price_map of shape {tuple(price_map.shape)}: [H, W], [1, H, W], [B, H, W] or [B, 1, H, W] with "
+                         f"H x W = {H} x {W}" + ("" if B is None else f" and B = {B}") + " expected")
+    t = t.reshape(shape)
+    if torch_like:
+        import torch
+        good = bool(torch.isfinite(t).all()) and bool((t >= 0).all())
+        t = t.contiguous()
+    else:
+        good = bool(np.all(np.isfinite(t))) and bool(np.all(t >= 0))
+        t = np.ascontiguousarray(t)
+    if not good:
+        raise ValueError("price_map: every value must be finite and >= 0")
+    return t
+
+
+def price_cells_values(price_cells, B, grid=None):
+    """Prices already on the latent grid -> float32 host array [n, gh, gw], n = 1 or B (B=None: any), checked before the library is
+    touched: [gh, gw] or [n, gh, gw], float32 or bool, finite and >= 0; grid=(gh, gw): the grid they must lie on."""
+    c = price_cells.detach().cpu().numpy() if _is_torch(price_cells) else np.asarray(price_cells)
+    if c.dtype == np.bool_:
+        c = c.astype(np.float32)
+    if c.dtype != np.float32:
+        raise ValueError(f"price_cells must be float32 or bool, got {c.dtype}")
+    if c.ndim == 2:
+        c = c[None]
+    if c.ndim != 3 or min(c.shape) < 1 or (B is not None and c.shape[0] not in (1, B)) or \
+            (grid is not None and tuple(c.shape[1:]) != tuple(grid)):
+        raise ValueError(f"price_cells of shape {tuple(price_cells.shape)}: [gh, gw] or [n, gh, gw]" +
+                         ("" if grid is None else f" on the latent grid {tuple(grid)}") + ("" if B is None else f" with n = 1 or {B}") + " expected")
+    if not np.all(np.isfinite(c)) or np.any(c < 0):
+        raise ValueError("price_cells: every value must be finite and >= 0")
+    return np.ascontiguousarray(c)
+
+
+def price_args(price_map, price_cells, B, hw, rated):
+    """The price-map arguments of an entry point, checked before the library is touched -> None, ("map", float32 [n, H, W]) or
+    ("cells", float32 host [n, gh, gw]).  hw: the image's own size; rated: one of rdo / target_bpp / max_bytes is given (a map steers
+    a price: without one there is nothing to steer)."""
+    if price_map is None and price_cells is None:
+        return None
+    if price_map is not None and price_cells is not None:
+        raise ValueError("price_map and price_cells exclude each other: the map in pixels, or its cells on the latent grid")
+    if not rated:
+        raise ValueError("price_map / price_cells need one of rdo, target_bpp, max_bytes: the map scales the price of a bit")
+    if price_map is not None:
+        return "map", price_map_values(price_map, B, hw[0], hw[1])
+    return "cells", price_cells_values(price_cells, B)
+
+
+def _cells_row(cells, b):
+    """Image b's own row of a price map on the latent grid (None stays None)."""
+    return None if cells is None else cells[b:b + 1] if cells.shape[0] > 1 else cells
 
 
 def rdo_select(cost, target):
@@ -403,6 +486,48 @@ class _ContextDecoder:
                                      _current_stream(args[0].mem)))
         return out
 
+    # ---- region-of-interest coding: a price per latent position (include/cdc_hip.h: cdc_set_rdo_map states the decision) -----------
+    def price_cells(self, price_map, size, padded_hw=None):
+        """A pixel-domain price map at the image's own size=(H, W) -> its cells, float32 NumPy [n, gh, gw], on the grid `rate_map` uses
+        for that image: the latent grid of the padded frame (of `padded_hw` when the U-Net asks for a larger one), `rate_map_cell`
+        pixels a side.  cdc_price_cells: a cell is the mean of the map over its pixels inside the image, a cell that lies wholly in
+        the padding takes the value of the nearest one that does not.  price_map: as `price_map_values` (any number of rows)."""
+        H, W = (int(d) for d in size)
+        pm = price_map_values(price_map, None, H, W)
+        Hp, Wp = self.padded_size(H, W) if padded_hw is None else (int(d) for d in padded_hw)
+        cell = self.rate_map_cell
+        if Hp % cell or Wp % cell or Hp < H or Wp < W:
+            raise _lib.CdcError(f"padded_hw {(Hp, Wp)} is no frame of a {H} x {W} image for this model")
+        gh, gw = Hp // cell, Wp // cell
+        L, h = _lib.lib(), self._hyper_handle()
+        a = _Arg(pm, self.device_index)
+        n = a.shape[0]
+        out, po, mem = _result_like(pm, (n, gh, gw), self.device_index)
+        _lib.check(h, L.cdc_price_cells(h, a.ptr, n, n, H, W, H, W, cell, gh, gw, po, mem, _current_stream(mem)))
+        return out.cpu().numpy() if _is_torch(out) else out
+
+    def _cells_of(self, priced, hw, padded_hw=None):
+        """What `price_args` returned -> the cells as a float32 host array [n, gh, gw] on the latent grid of the frame, or None."""
+        if priced is None:
+            return None
+        kind, v = priced
+        if kind == "map":
+            return self.price_cells(v, hw, padded_hw)
+        Hp, Wp = self.padded_size(*hw) if padded_hw is None else padded_hw
+        return price_cells_values(v, None, (Hp // self.rate_map_cell, Wp // self.rate_map_cell))
+
+    def _with_map(self, h, cells, call):
+        """call() while the hyper-decoder handle holds `cells` as its price map (cdc_set_rdo_map for this call alone)."""
+        if cells is None:
+            return call()
+        L = _lib.lib()
+        n, gh, gw = cells.shape
+        _lib.check(h, L.cdc_set_rdo_map(h, cells.ctypes.data, n, gh, gw, _lib.CDC_MEM_HOST, None))
+        try:
+            return call()
+        finally:
+            L.cdc_set_rdo_map(h, None, 0, 0, 0, _lib.CDC_MEM_HOST, None)
+
     def bpp(self, shape, state4bpp):
         """Compressor.bpp (compress_modules.py:76-90) in eval mode: quantise with the medians / the predicted
         mean, then the rate of both latents."""
@@ -480,16 +605,20 @@ class _ContextDecoder:
             med = torch.from_numpy(med).to(t.device)
         return med
 
-    def encode(self, input, cond=None, padded_hw=None, rdo=None):
+    def encode(self, input, cond=None, padded_hw=None, rdo=None, price_map=None, price_cells=None):
         """Compressor.encode (compress_modules.py:43-66): (q_latent, q_hyper_latent, state4bpp); cond: VBR rate.  Images of any
         size (float32 / uint8): the results are those of the padded frame.  rdo: the price of a bit mu >= 0, a scalar or B values
         (no reference counterpart): q_latent comes from `rdo_quantize` -- every symbol the nearest integer or, where mu * (bits saved)
         exceeds the squared error it costs, its neighbour towards the mean; state4bpp keeps the unquantised latent and gains
-        "q_latent" and "rdo_moved" (int64 [B]).  None runs the reference's rounding."""
-        B = frame.image_shape(input)[0]
+        "q_latent" and "rdo_moved" (int64 [B]).  None runs the reference's rounding.  price_map / price_cells (with rdo): the price of
+        a bit becomes mu * the map's value at the symbol's position -- a pixel-domain map at the image's own size ([H, W], [1, H, W],
+        [B, H, W] or [B, 1, H, W]; float32 >= 0 or bool), or its cells on the latent grid as `price_cells()` returns them."""
+        B, _, H0, W0 = frame.image_shape(input)
         self._rates(cond, B)
         mu = None if rdo is None else rdo_values(rdo, B)
+        priced = price_args(price_map, price_cells, B, (H0, W0), rdo is not None)
         input, _ = self._framed(input, padded_hw)
+        cells = self._cells_of(priced, (H0, W0), tuple(frame.image_shape(input)[2:]))
         latent, hyper_latent = self.analysis(input, cond)
         q_hyper_latent = self.dequantize(hyper_latent, self._medians_like(hyper_latent))
         mean, scale = self.hyper_decode(q_hyper_latent, cond=cond)
@@ -498,13 +627,25 @@ class _ContextDecoder:
         if mu is None:
             q_latent = self.dequantize(latent, mean)
         else:
-            q_latent, moved = self.rdo_quantize(latent, mean, scale, mu)
+            q_latent, moved = self.rdo_quantize(latent, mean, scale, mu, price_cells=cells)
             state4bpp.update(q_latent=q_latent, rdo_moved=moved)
         return q_latent, q_hyper_latent, state4bpp
 
-    def rdo_quantize(self, latent, mean, scale, rdo):
+    def rdo_quantize(self, latent, mean, scale, rdo, price_map=None, price_cells=None):
         """cdc_op_rdo_quantize: the decision of include/cdc_hip.h on caller-supplied operands of one shape [B, ...] -> (q_latent,
-        moved int64 [B] numpy).  rdo: 1 or B values.  Non-finite operands are refused (CdcError) with nothing written."""
+        moved int64 [B] numpy).  rdo: 1 or B values.  Non-finite operands are refused (CdcError) with nothing written.
+        With a price map (cdc_op_rdo_quantize_map) the operands are [B, C, ...] and a position is what follows the channel axis:
+        price_cells [n, ...] holds one value per position, n = 1 or B (a NumPy array, or a tensor in the operands' memory);
+        price_map is the same in pixels, for operands [B, C, h, w], at the size (h, w) * `rate_map_cell`."""
+        shape = tuple(int(d) for d in latent.shape)
+        if price_map is not None and price_cells is not None:
+            raise ValueError("price_map and price_cells exclude each other: the map in pixels, or its cells on the latent grid")
+        pixels = None
+        if price_map is not None:
+            if len(shape) != 4:
+                raise ValueError(f"price_map needs operands [B, C, h, w], got {shape}: give price_cells, one value per position")
+            size = tuple(d * self.rate_map_cell for d in shape[2:])
+            pixels = price_map_values(price_map, shape[0], *size)
         args = [_Arg(t, self.device_index) for t in (latent, mean, scale)]
         if len({a.mem for a in args}) != 1 or len({tuple(a.shape) for a in args}) != 1:
             raise _lib.CdcError("latent, mean and scale must have the same shape and live in the same memory")
@@ -512,6 +653,12 @@ class _ContextDecoder:
         per = int(np.prod(args[0].shape[1:]))
         mu = rdo_values(rdo, B)
         mu = np.ascontiguousarray(np.broadcast_to(mu, (B,)), dtype=np.float32)
+        C = shape[1] if len(shape) > 1 else 1
+        gmap = None
+        if pixels is not None:
+            price_cells = self.price_cells(pixels, size, size)
+        if price_cells is not None:
+            gmap = self._op_map(price_cells, B, per // C, args[0].mem)
         L, h = _lib.lib(), self._hyper_handle()
         if not self._hyper_finalized:
             raise _lib.CdcError("load_hyper_state_dict() has not been called")
@@ -523,9 +670,38 @@ class _ContextDecoder:
         else:
             mv = np.zeros(B, np.int64)
             pm = mv.ctypes.data
-        _lib.check(h, L.cdc_op_rdo_quantize(h, args[0].ptr, args[1].ptr, args[2].ptr, mu.ctypes.data, po, pm, B, per, mem,
-                                            _current_stream(mem)))
+        if gmap is None:
+            _lib.check(h, L.cdc_op_rdo_quantize(h, args[0].ptr, args[1].ptr, args[2].ptr, mu.ctypes.data, po, pm, B, per, mem,
+                                                _current_stream(mem)))
+        else:
+            _lib.check(h, L.cdc_op_rdo_quantize_map(h, args[0].ptr, args[1].ptr, args[2].ptr, mu.ctypes.data, gmap.ptr, gmap.shape[0], po, pm,
+                                                    B, C, per // C, mem, _current_stream(mem)))
         return out, (mv.cpu().numpy() if mem == _lib.CDC_MEM_DEVICE else mv)
+
+    def _op_map(self, price_cells, B, P, mem):
+        """The map operand of cdc_op_rdo_quantize_map: [n, ...] with P values a row, n = 1 or B, float32 or bool, in the memory `mem`
+        of the other operands (moved there when it lives elsewhere).  A host map is checked here (ValueError); a device map by the
+        library's check kernel (CdcError, nothing written)."""
+        t = price_cells
+        n = int(t.shape[0]) if len(t.shape) > 1 else 1
+        if n not in (1, B) or int(np.prod(tuple(t.shape))) != n * P:
+            raise ValueError(f"price_cells of shape {tuple(t.shape)}: [n, ...] with n = 1 or {B} and {P} positions a row expected")
+        on_device = _is_torch(t) and t.is_cuda
+        if not on_device:
+            t = price_cells_values(np.asarray(t.detach().numpy() if _is_torch(t) else t).reshape(n, 1, P), B).reshape(n, P)
+            if mem == _lib.CDC_MEM_DEVICE:
+                import torch
+                t = torch.from_numpy(t).to(f"cuda:{self.device_index}")
+        else:
+            import torch
+            if t.dtype not in (torch.float32, torch.bool):
+                raise ValueError(f"price_cells must be float32 or bool, got {t.dtype}")
+            t = t.to(torch.float32).reshape(n, P)
+            if mem != _lib.CDC_MEM_DEVICE:
+                t = t.cpu().numpy()
+        a = _Arg(t, self.device_index)
+        a.shape = (n, P)
+        return a
 
     # ---- entropy coder (SURVEY section 8f row 4; no reference counterpart) ---------------------
     def _median_vector(self):
@@ -533,7 +709,8 @@ class _ContextDecoder:
         med = self._medians.reshape(-1) if self._medians is not None else np.zeros(C, np.float32)
         return np.ascontiguousarray(med, dtype=np.float32)
 
-    def compress_to_bytes(self, images, bitrate_scale=None, rdo=None, target_bpp=None, max_bytes=None, return_info=False):
+    def compress_to_bytes(self, images, bitrate_scale=None, rdo=None, target_bpp=None, max_bytes=None, return_info=False,
+                          price_map=None, price_cells=None):
         """images [B, 3, H, W] -> list of B bitstreams (bytes): analysis transform + hyper encoder on the GPU, then the
         range-ANS coder of include/cdc_hip.h (cdc_entropy_encode) over exactly the symbols `bpp()` prices.  A VBR model
         takes bitrate_scale (1 or B values) and records each image's rate in its stream.
@@ -547,24 +724,31 @@ class _ContextDecoder:
           max_bytes=n    the same against 8 n bits, the stream's header counted; the coder's own overhead (its 2 x 64 lane states,
                          escapes) is not in the estimate, so a stream that ends over n shrinks its image's bit target by the
                          observed ratio and is chosen again: at most 3 re-encodes.  met: len(stream) <= n.
+        Region of interest (with one of the three; cdc_set_rdo_map): price_map -- [H, W], [1, H, W], [B, H, W] or [B, 1, H, W] at the
+        image's own size, float32 >= 0 or bool -- or price_cells, its cells on the latent grid as `price_cells()` returns them.  The
+        price of a bit becomes mu * the map at the symbol's position: 0 protects a region, 1 leaves mu as it is, larger values make
+        a region pay.  Under target_bpp / max_bytes every sweep prices the ladder under the image's own map, and the "mu" reported
+        is the base price the map multiplies.
         return_info=True: -> (streams, {"mu", "estimated_bpp", "moved", "latent_mse", "met" (each [B]), "reencodes"})."""
-        B = frame.image_shape(images)[0]
+        B, _, H0, W0 = frame.image_shape(images)
         rdo_exclusive(rdo, target_bpp, max_bytes)
         self._rates(bitrate_scale, B)
         mu = None if rdo is None else rdo_values(rdo, B)
         target = None if target_bpp is None else self._targets(target_bpp, B, "target_bpp")
         budget = None if max_bytes is None else self._targets(max_bytes, B, "max_bytes")
+        priced = price_args(price_map, price_cells, B, (H0, W0), not (rdo is None and target_bpp is None and max_bytes is None))
         images, hw = self._framed(images)
+        cells = self._cells_of(priced, hw)
         latent, hyper = self.analysis(images, bitrate_scale)
         if target is None and budget is None:
-            streams = self.latents_to_bytes(latent, hyper, bitrate_scale, image_hw=hw, rdo=mu)
+            streams = self.latents_to_bytes(latent, hyper, bitrate_scale, image_hw=hw, rdo=mu, price_cells=cells)
             if not return_info:
                 return streams
-            row = self._sweep(latent, hyper, np.zeros(1, np.float32) if mu is None else mu, bitrate_scale, per_image=True)
+            row = self._sweep(latent, hyper, np.zeros(1, np.float32) if mu is None else mu, bitrate_scale, per_image=True, cells=cells)
             return streams, self._rdo_info(row, np.zeros(B, np.float32) if mu is None else np.broadcast_to(mu, (B,)), hw, latent,
                                            np.ones(B, bool), 0)
         ladder = np.concatenate([np.zeros(1, np.float32), RDO_LADDER])
-        table = self._sweep(latent, hyper, ladder, bitrate_scale)
+        table = self._sweep(latent, hyper, ladder, bitrate_scale, cells=cells)
         npix = float(hw[0] * hw[1])
         if target is not None:
             goal, cost0 = target, table["bits"] / npix                  # estimated bpp against the target
@@ -572,19 +756,19 @@ class _ContextDecoder:
             header = self._stream_header_bytes(images, hw)
             goal, cost0 = 8.0 * (budget - header), table["bits"]       # estimated payload bits against the budget's
         div = npix if target is not None else 1.0
-        rows = [self._choose_mu(latent, hyper, bitrate_scale, b, ladder, cost0[b], goal[b], div)
+        rows = [self._choose_mu(latent, hyper, bitrate_scale, b, ladder, cost0[b], goal[b], div, cells)
                 for b in range(B)]
         reencodes = 0
         while True:
             mus = np.asarray([r["mu"] for r in rows], np.float32)
-            streams = self.latents_to_bytes(latent, hyper, bitrate_scale, image_hw=hw, rdo=mus)
+            streams = self.latents_to_bytes(latent, hyper, bitrate_scale, image_hw=hw, rdo=mus, price_cells=cells)
             over = [] if budget is None else [b for b in range(B) if len(streams[b]) > budget[b]]
             if not over or reencodes == 3:
                 break
             reencodes += 1
             for b in over:                                              # the estimate missed the coder's overhead: aim lower by what was seen
                 goal[b] *= budget[b] / len(streams[b])
-                rows[b] = self._choose_mu(latent, hyper, bitrate_scale, b, ladder, cost0[b], goal[b], div)
+                rows[b] = self._choose_mu(latent, hyper, bitrate_scale, b, ladder, cost0[b], goal[b], div, cells)
         if not return_info:
             return streams
         met = np.asarray([r["met"] for r in rows], bool) if budget is None else \
@@ -607,10 +791,11 @@ class _ContextDecoder:
         framed = tuple(frame.image_shape(images)[2:])
         return 34 + (4 if self.vbr else 0) + (8 if tuple(hw) != framed else 0)
 
-    def _sweep(self, latent, hyper, mus, bitrate_scale=None, per_image=False):
+    def _sweep(self, latent, hyper, mus, bitrate_scale=None, per_image=False, cells=None):
         """cdc_entropy_rate_sweep on the unquantised outputs of `analysis()` -> {"bits", "sse" float64 [B, L], "moved" int64 [B, L]}.
         per_image: `mus` holds 1 or B values, one per image, and the result is [B] (image b at its own mu; the batch = batch-1
-        contract makes the batch-1 calls this takes the rows of one batched call)."""
+        contract makes the batch-1 calls this takes the rows of one batched call).  cells: a price map on the latent grid, float32 host
+        [1 or B, gh, gw] (cdc_set_rdo_map for this call alone): every mu is priced under image b's own row."""
         L, h = _lib.lib(), self._hyper_handle()
         if not (self._hyper_finalized and self._prior_loaded):
             raise _lib.CdcError("the prior.* tensors have not been loaded (load_state_dict with the full state_dict)")
@@ -619,35 +804,36 @@ class _ContextDecoder:
         if per_image:
             mus = np.broadcast_to(rdo_values(mus, B), (B,))
             if len(set(mus.tolist())) == 1:
-                one = self._sweep(latent, hyper, mus[:1], bitrate_scale)
+                one = self._sweep(latent, hyper, mus[:1], bitrate_scale, cells=cells)
                 return {k: v[:, 0] for k, v in one.items()}
             rates = self._rates(bitrate_scale, B)
             rows = [self._sweep(latent[b:b + 1], hyper[b:b + 1], mus[b:b + 1],
-                                None if rates is None else rates[b if rates.size > 1 else 0]) for b in range(B)]
+                                None if rates is None else rates[b if rates.size > 1 else 0], cells=_cells_row(cells, b)) for b in range(B)]
             return {k: np.concatenate([r[k][:, 0] for r in rows]) for k in rows[0]}
         mus = rdo_values(mus, None, "mus")
         self._set_rate(h, bitrate_scale, B)
         n = int(mus.size)
         bits, sse, moved = np.empty((B, n), np.float64), np.empty((B, n), np.float64), np.empty((B, n), np.int64)
         med = self._median_vector()
-        _lib.check(h, L.cdc_entropy_rate_sweep(h, al.ptr, ah.ptr, med.ctypes.data, B, hh, wh, mus.ctypes.data, n, bits.ctypes.data,
-                                               sse.ctypes.data, moved.ctypes.data, al.mem, _current_stream(al.mem)))
+        self._with_map(h, cells, lambda: _lib.check(h, L.cdc_entropy_rate_sweep(
+            h, al.ptr, ah.ptr, med.ctypes.data, B, hh, wh, mus.ctypes.data, n, bits.ctypes.data, sse.ctypes.data, moved.ctypes.data, al.mem,
+            _current_stream(al.mem))))
         return {"bits": bits, "sse": sse, "moved": moved}
 
-    def _choose_mu(self, latent, hyper, bitrate_scale, b, ladder, cost, goal, div):
+    def _choose_mu(self, latent, hyper, bitrate_scale, b, ladder, cost, goal, div, cells=None):
         """Image b's mu for the cost goal `goal`: `cost` is its row of the first sweep over `ladder` (ascending, entry 0 = mu 0) in the
         goal's unit (bits / div) -> {"mu", "met", "bits", "sse", "moved"} at the mu chosen.  The refining sweep runs on the image's
-        own rows: batch 1, the same values as in the batch."""
+        own rows -- its own row of the price map `cells` included: batch 1, the same values as in the batch."""
         rates = self._rates(bitrate_scale, _Arg(hyper, self.device_index).shape[0])
         rate_b = None if rates is None else rates[b if rates.size > 1 else 0]
         j, met = rdo_select(cost, goal)
         if j == 0 or not met:           # the plain symbols do, or nothing on the ladder does: no interval to refine
             sub = ladder[j:j + 1]
             k = 0
-            row = self._sweep(latent[b:b + 1], hyper[b:b + 1], sub, rate_b)
+            row = self._sweep(latent[b:b + 1], hyper[b:b + 1], sub, rate_b, cells=_cells_row(cells, b))
         else:
             sub = rdo_refine_ladder(ladder[j - 1], ladder[j])
-            row = self._sweep(latent[b:b + 1], hyper[b:b + 1], sub, rate_b)
+            row = self._sweep(latent[b:b + 1], hyper[b:b + 1], sub, rate_b, cells=_cells_row(cells, b))
             k, _ = rdo_select(row["bits"][0] / div, goal)               # (the interval's upper end meets the goal: it did above)
         return {"mu": np.float32(sub[k]), "met": met, "bits": row["bits"][0, k], "sse": row["sse"][0, k], "moved": row["moved"][0, k]}
 
@@ -658,44 +844,55 @@ class _ContextDecoder:
                 "moved": np.asarray(row["moved"], np.int64), "latent_mse": np.asarray(row["sse"], np.float64) / per,
                 "met": np.asarray(met, bool), "reencodes": int(reencodes)}
 
-    def rate_sweep(self, images, mus, bitrate_scale=None, image_hw=None):
+    def rate_sweep(self, images, mus, bitrate_scale=None, image_hw=None, price_map=None, price_cells=None):
         """The rate-distortion curve of the quantiser itself, for plots: images [B, 3, H, W], or the unquantised (latent, hyper) of
         `analysis()`, and a ladder `mus` of 1 .. 32 values -> {"mu" float32 [L], "bpp" [B, L] (the estimate `rate()` gives for the
         symbols chosen at mu, over H * W -- of a (latent, hyper) pair: over image_hw, default the coded extent), "latent_mse" [B, L]
         (mean squared error of the dequantised latent against the unquantised one), "moved" int64 [B, L]}.  One pass over the latent
         for the whole ladder (cdc_entropy_rate_sweep); mean and scale are the coder's own.  What the moves do to decoded images of
-        trained weights is not measured by this."""
+        trained weights is not measured by this.  price_map / price_cells: the curve under a price map (as `compress_to_bytes`; the
+        pixel-domain map at the image's size, image_hw for a (latent, hyper) pair)."""
         mus = rdo_values(mus, None, "mus")
         if isinstance(images, (tuple, list)):
             latent, hyper = images
             hh, wh = tuple(hyper.shape)[2:]
-            hw = tuple(image_hw) if image_hw is not None else (hh * self.frame_multiple, wh * self.frame_multiple)
+            framed = (hh * self.frame_multiple, wh * self.frame_multiple)
+            hw = tuple(image_hw) if image_hw is not None else framed
+            cells = self._cells_of(price_args(price_map, price_cells, int(hyper.shape[0]), hw, True), hw, framed)
         else:
-            self._rates(bitrate_scale, frame.image_shape(images)[0])
+            B, _, H0, W0 = frame.image_shape(images)
+            self._rates(bitrate_scale, B)
+            priced = price_args(price_map, price_cells, B, (H0, W0), True)
             images, hw = self._framed(images)
+            cells = self._cells_of(priced, hw)
             latent, hyper = self.analysis(images, bitrate_scale)
-        t = self._sweep(latent, hyper, mus, bitrate_scale)
+        t = self._sweep(latent, hyper, mus, bitrate_scale, cells=cells)
         per = float(np.prod(tuple(latent.shape)[1:]))
         return {"mu": mus.copy(), "bpp": t["bits"] / float(hw[0] * hw[1]), "latent_mse": t["sse"] / per, "moved": t["moved"]}
 
-    def latents_to_bytes(self, latent, hyper, bitrate_scale=None, image_hw=None, rdo=None):
+    def latents_to_bytes(self, latent, hyper, bitrate_scale=None, image_hw=None, rdo=None, price_map=None, price_cells=None):
         """The UNquantised outputs of `analysis()` -> list of B bitstreams.  The coder's determinism contract starts here: the
         same (latent, hyper) rows give the same bytes whatever the batch they are coded in (the analysis transform itself is
         an ordinary batched forward: its last bits may depend on the batch size, like any other entry point's).
         image_hw=(H, W): the size of the original image when the latents are those of its padded frame; the streams then record it
         (container version 5 / 6) unless it equals the frame's, and are today's version 3 / 4 otherwise.
-        rdo: mu, 1 or B values (cdc_set_rdo for this call alone); image b's stream depends on its own mu only."""
+        rdo: mu, 1 or B values (cdc_set_rdo for this call alone); image b's stream depends on its own mu only.
+        price_map / price_cells (with rdo; cdc_set_rdo_map for this call alone): as `compress_to_bytes`, the pixel-domain map at
+        image_hw (default: the coded extent); image b's stream depends on its own mu and its own row of the map only."""
         L, h = _lib.lib(), self._hyper_handle()
         al, ah = _Arg(latent, self.device_index), _Arg(hyper, self.device_index)
         B, _, hh, wh = ah.shape
         mu = None if rdo is None else rdo_values(rdo, B)
+        framed = (hh * self.frame_multiple, wh * self.frame_multiple)
+        hw = framed if image_hw is None else (int(image_hw[0]), int(image_hw[1]))
+        cells = self._cells_of(price_args(price_map, price_cells, B, hw, rdo is not None), hw, framed)
         if not (self._hyper_finalized and self._prior_loaded):
             raise _lib.CdcError("the prior.* tensors have not been loaded (load_state_dict with the full state_dict)")
         self._set_rate(h, bitrate_scale, B)
         if mu is not None:
             _lib.check(h, L.cdc_set_rdo(h, mu.ctypes.data, int(mu.size)))
             try:
-                return self._coded(L, h, al, ah, B, hh, wh, image_hw)
+                return self._with_map(h, cells, lambda: self._coded(L, h, al, ah, B, hh, wh, image_hw))
             finally:
                 L.cdc_set_rdo(h, None, 0)
         return self._coded(L, h, al, ah, B, hh, wh, image_hw)
@@ -803,14 +1000,14 @@ class _ContextDecoder:
             out[b] = r.value
         return out
 
-    def forward(self, input, cond=None, padded_hw=None, return_rate_map=False, rdo=None):
+    def forward(self, input, cond=None, padded_hw=None, return_rate_map=False, rdo=None, price_map=None, price_cells=None):
         """Compressor.forward (compress_modules.py:92-103).  Images of any size (float32 / uint8): "output" (the context pyramid the
         U-Net consumes), "q_latent" and "q_hyper_latent" are those of the PADDED frame, "bpp" counts bits over the original H * W.
         return_rate_map: also "rate_map", `rate_map(...)["cell"]` of the padded frame, [B, Hp / c, Wp / c] in bits with
         c = `rate_map_cell`; its sum over an image is bpp * H * W.  rdo: as `encode`; "bpp", "output" and "rate_map" are those of
-        the symbols it chose."""
+        the symbols it chose.  price_map / price_cells: as `encode`."""
         shape = frame.image_shape(input)
-        q_latent, q_hyper_latent, state4bpp = self.encode(input, cond, padded_hw, rdo)
+        q_latent, q_hyper_latent, state4bpp = self.encode(input, cond, padded_hw, rdo, price_map, price_cells)
         out = {"output": self.decode(q_latent, cond), "bpp": self.bpp(shape, state4bpp), "q_latent": q_latent,
                "q_hyper_latent": q_hyper_latent}
         if return_rate_map:

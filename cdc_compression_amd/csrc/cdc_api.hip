@@ -313,6 +313,7 @@ void cdc_destroy(cdc_handle *h) {
     h->d_hist.release();
     h->d_rep_stage.release();
     h->picks.dev.release();
+    h->rdo_map.release();
     if (h->metric_work) (void)hipFree(h->metric_work);
     if (h->map_work) (void)hipFree(h->map_work);
     if (h->trace_buf) (void)hipFree(h->trace_buf);
@@ -720,6 +721,50 @@ int cdc_distortion_map(cdc_handle *h, const cdc_image_view *a, const cdc_image_v
             int32_t *dcnt = count ? s.out(count, sizeof(int32_t) * cells, stage ? stage + sse_bytes : nullptr) : nullptr;
             if (s.ok()) s.e = sse_map_launch(mv[0], mv[1], B, H, W, cell, gh, gw, dsse, dcnt, st);
             return s.finish("distortion_map");
+        });
+    });
+}
+
+int cdc_price_cells(cdc_handle *h, const float *pixel_map, int n, int B, int H, int W, int Hf, int Wf, int cell, int gh, int gw, float *cells,
+                    int mem, void *stream) {
+    if (!h) return CDC_ERR_INVALID;
+    return no_throw(h, [&] {
+        return with_range_guard(h, [&]() -> int {
+            int rc = ensure_device(h);
+            if (rc) return rc;
+            if (!pixel_map) return fail(h, CDC_ERR_INVALID, "price_cells: null map");
+            if (!cells) return fail(h, CDC_ERR_INVALID, "price_cells: no cells array");
+            if (B < 1 || H < 1 || W < 1) return fail(h, CDC_ERR_INVALID, "price_cells: B=%d H=%d W=%d (all must be >= 1)", B, H, W);
+            if (n != 1 && n != B) return fail(h, CDC_ERR_INVALID, "price_cells: a map of %d images for a batch of %d (1 or %d expected)", n, B, B);
+            if (Hf < H || Wf < W) return fail(h, CDC_ERR_INVALID, "price_cells: the %d x %d window is larger than the map's frame (%d x %d)", H, W, Hf, Wf);
+            if (cell < 1) return fail(h, CDC_ERR_INVALID, "price_cells: cell = %d (must be >= 1)", cell);
+            if (gh < 1 || gw < 1 || (long long)gh * cell < H || (long long)gw * cell < W)
+                return fail(h, CDC_ERR_INVALID, "price_cells: a %d x %d grid of %d-pixel cells does not cover the %d x %d window", gh, gw, cell, H, W);
+            if (mem != CDC_MEM_HOST && mem != CDC_MEM_DEVICE) return fail(h, CDC_ERR_INVALID, "price_cells: mem_kind %d", mem);
+            const long long total = (long long)n * gh * gw;
+            if (total > (1ll << 31) || (long long)std::min(cell, H) * std::min(cell, W) > (1ll << 30) || (long long)n * Hf * Wf > (1ll << 40))
+                return fail(h, CDC_ERR_INVALID, "price_cells: n=%d, a %d x %d grid of %d-pixel cells is beyond the launch limits", n, gh, gw, cell);
+            // the cells are produced in the handle's work area and released to the caller only once the kernel's flag has been read
+            const size_t cell_bytes = map_up16(sizeof(float) * total);
+            if ((rc = map_work_area(h, "price_cells", cell_bytes + 16))) return rc;
+            hipStream_t st = pick_stream(h, stream, mem);
+            Staging s(h, mem, st);
+            const float *src = s.in(pixel_map, sizeof(float) * (size_t)n * Hf * Wf);
+            float *work = (float *)h->map_work;
+            int *bad = (int *)((char *)h->map_work + cell_bytes);
+            int hbad = 0;
+            if (s.ok()) s.e = hipMemsetAsync(bad, 0, sizeof(int), st);
+            if (s.ok()) s.e = price_cells_launch(src, n, H, W, Hf, Wf, cell, gh, gw, work, bad, st);
+            if (s.ok()) s.e = hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st);
+            if (s.ok()) s.e = hipStreamSynchronize(st);
+            if (s.ok() && hbad) {
+                (void)s.finish("price_cells");
+                return fail(h, CDC_ERR_INVALID, "price_cells: a non-finite or negative value inside the window (nothing written)");
+            }
+            if (s.ok())
+                s.e = hipMemcpyAsync(cells, work, sizeof(float) * total, mem == CDC_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st);
+            if (s.ok() && mem == CDC_MEM_DEVICE) s.e = hipStreamSynchronize(st);      // (the work area is the next call's too)
+            return s.finish("price_cells");
         });
     });
 }

@@ -124,6 +124,23 @@ inline int check_mu(cdc_handle *h, const char *what, const float *mu, int n) {
     return CDC_OK;
 }
 
+// The handle's price map (cdc_set_rdo_map) for a call of B images over hh x wh hyper-latent positions; m->g = null with none set.
+// Checked before anything is launched: the map's grid is the call's latent grid, its rows are 1 or B.
+int call_rdo_map(cdc_handle *h, int B, int hh, int wh, cdc::RdoMap *m) {
+    *m = cdc::RdoMap();
+    if (!h->rdo_map_n) return CDC_OK;
+    const int U = 1 << ((int)h->hyper_dims.size() - 2);   // as cdc_bpp
+    const long long gh = (long long)U * hh, gw = (long long)U * wh;
+    if (h->rdo_map_gh != gh || h->rdo_map_gw != gw)
+        return fail(h, CDC_ERR_INVALID, "the price map is %d x %d, the call's latent grid %lld x %lld (cdc_set_rdo_map)", h->rdo_map_gh, h->rdo_map_gw, gh, gw);
+    if (h->rdo_map_n != 1 && h->rdo_map_n != B)
+        return fail(h, CDC_ERR_INVALID, "the price map has %d rows for a batch of %d (1 or %d expected)", h->rdo_map_n, B, B);
+    m->g = h->rdo_map.p;
+    m->P = (unsigned)(gh * gw);
+    m->bs = h->rdo_map_n == 1 ? 0 : gh * gw;
+    return CDC_OK;
+}
+
 // img_h = img_w = 0: the image is the coded extent (version 3 / 4), as is an image size equal to it
 int entropy_encode_impl(cdc_handle *h, const float *latent, const float *hyper_latent, const float *medians, int B,
                         int hh, int wh, int img_h, int img_w, unsigned char *out, size_t cap, size_t *offsets, int mem, void *stream) {
@@ -140,6 +157,10 @@ int entropy_encode_impl(cdc_handle *h, const float *latent, const float *hyper_l
                         img_h, img_w, (long long)D * hh, (long long)D * wh, hh, wh, D);
         if ((long long)D * hh == img_h && (long long)D * wh == img_w) img_h = img_w = 0;      // nothing to crop: today's stream, byte for byte
     }
+    if (h->rdo_map_n && h->rdo_mu.empty())                // never a silent no-op
+        return fail(h, CDC_ERR_STATE, "a price map is set (cdc_set_rdo_map) but no mu (cdc_set_rdo): nothing to multiply it with");
+    cdc::RdoMap map;
+    if ((rc = call_rdo_map(h, B, hh, wh, &map))) return rc;
     EncoderFront f;
     if ((rc = encoder_front(h, latent, hyper_latent, medians, B, hh, wh, mem, stream, &f))) return rc;
     DevPool &d = f.d;
@@ -166,7 +187,8 @@ int entropy_encode_impl(cdc_handle *h, const float *latent, const float *hyper_l
     } else {                                              // cdc_set_rdo: the same symbols, moved one step towards the mean where that pays
         float *d_mu;
         if ((rc = stage_rdo(h, B, &d, &d_mu, st))) return rc;
-        HIP_TRY(h, cdc::latent_symbols_rdo_launch(d_lat, nl, o.p, o.p + nl, o.bs(), h->ent->d_edges, nl, B, d_mu, syml, bin, bad, st));
+        if (map.g && (long long)(o.C / 2) * map.P != nl) return fail(h, CDC_ERR_INVALID, "the price map's grid is not the latent's");
+        HIP_TRY(h, cdc::latent_symbols_rdo_launch(d_lat, nl, o.p, o.p + nl, o.bs(), h->ent->d_edges, nl, B, d_mu, map, syml, bin, bad, st));
     }
     const cdc::EntropyDev T = h->ent->dev();
     HIP_TRY(h, cdc::rans_encode_launch(T, symh, nh, nullptr, 0, per, 0, (int)nh, 0u, B, sf, ew, sec_h, cap_h, esc_h, nh, meta, st));
@@ -204,6 +226,8 @@ int rate_sweep_impl(cdc_handle *h, const float *latent, const float *hyper_laten
         return fail(h, CDC_ERR_INVALID, "null/invalid argument");
     if (L < 1 || L > cdc::kRdoMaxLadder) return fail(h, CDC_ERR_INVALID, "rate_sweep: a ladder of %d values (1 .. %d expected)", L, cdc::kRdoMaxLadder);
     if ((rc = check_mu(h, "rate_sweep", mu, L))) return rc;
+    cdc::RdoMap map;                                      // cdc_set_rdo_map: the ladder is priced under image b's own row
+    if ((rc = call_rdo_map(h, B, hh, wh, &map))) return rc;
     EncoderFront f;
     if ((rc = encoder_front(h, latent, hyper_latent, medians, B, hh, wh, mem, stream, &f))) return rc;
     if (!h->d_prior) return fail(h, CDC_ERR_STATE, "the prior.* tensors were not loaded");
@@ -224,7 +248,8 @@ int rate_sweep_impl(cdc_handle *h, const float *latent, const float *hyper_laten
     // the hyper section's price, of the dequantised symbols the coder codes (sym + median: what cdc_entropy_decode returns)
     HIP_TRY(h, cdc::symbols_to_hyper_launch(f.symh, h->ent->d_medians, f.Ch, f.per, B, qh, st));
     HIP_TRY(h, cdc::hyper_bits_launch(qh, nh, f.per, h->d_prior, B, hb, st));
-    HIP_TRY(h, cdc::rdo_sweep_launch(f.d_lat, nl, o.p, o.p + nl, o.bs(), nl, B, d_mu, L, hb, hparts, pb, ps, pm, rb, rs, rm, f.bad, st));
+    if (map.g && (long long)(o.C / 2) * map.P != nl) return fail(h, CDC_ERR_INVALID, "the price map's grid is not the latent's");
+    HIP_TRY(h, cdc::rdo_sweep_launch(f.d_lat, nl, o.p, o.p + nl, o.bs(), nl, B, d_mu, L, map, hb, hparts, pb, ps, pm, rb, rs, rm, f.bad, st));
     int hbad = 0;
     std::vector<double> tb(nr), ts(nr);
     std::vector<long long> tm(nr);
@@ -402,44 +427,106 @@ int cdc_entropy_rate_sweep(cdc_handle *h, const float *latent, const float *hype
     });
 }
 
+int cdc_set_rdo_map(cdc_handle *h, const float *cells, int n, int gh, int gw, int mem, void *stream) {
+    if (!h) return CDC_ERR_INVALID;
+    return no_throw(h, [&] {
+        return with_range_guard(h, [&]() -> int {
+            int rc = require_kind(h, HandleKind::HyperDecoder);
+            if (rc) return rc;
+            if (n < 0 || (n > 0 && !cells)) return fail(h, CDC_ERR_INVALID, "set_rdo_map: null/invalid argument");
+            if (n == 0) { h->rdo_map_n = h->rdo_map_gh = h->rdo_map_gw = 0; return CDC_OK; }
+            if (gh < 1 || gw < 1 || (long long)gh * gw > (1ll << 29) || (long long)n * gh * gw > (1ll << 31))
+                return fail(h, CDC_ERR_INVALID, "set_rdo_map: n=%d, a %d x %d grid (all >= 1, at most 2^29 positions expected)", n, gh, gw);
+            if (mem != CDC_MEM_HOST && mem != CDC_MEM_DEVICE) return fail(h, CDC_ERR_INVALID, "set_rdo_map: mem_kind %d", mem);
+            if ((rc = ensure_device(h))) return rc;
+            // validated on the host, whatever memory the cells live in: a map is small (one float per latent position)
+            const size_t total = (size_t)n * gh * gw;
+            std::vector<float> host(total);
+            if (mem == CDC_MEM_DEVICE) {
+                HIP_TRY(h, hipStreamSynchronize((hipStream_t)stream));
+                HIP_TRY(h, hipMemcpy(host.data(), cells, sizeof(float) * total, hipMemcpyDeviceToHost));
+            } else {
+                memcpy(host.data(), cells, sizeof(float) * total);
+            }
+            for (size_t i = 0; i < total; ++i)
+                if (!std::isfinite(host[i]) || host[i] < 0.f)
+                    return fail(h, CDC_ERR_INVALID, "set_rdo_map: cells[%zu] = %g (finite and >= 0 expected; the handle's map is unchanged)", i, (double)host[i]);
+            HIP_TRY(h, hipStreamSynchronize(h->own_stream));      // (the encoders that read the old map have synchronised; so has this)
+            if ((rc = h->rdo_map.grow(h, total))) return rc;
+            HIP_TRY(h, hipMemcpy(h->rdo_map.p, host.data(), sizeof(float) * total, hipMemcpyHostToDevice));
+            h->rdo_map_n = n; h->rdo_map_gh = gh; h->rdo_map_gw = gw;
+            return CDC_OK;
+        });
+    });
+}
+
+// cdc_op_rdo_quantize (map = null) and cdc_op_rdo_quantize_map (map [n_map][P], per_image = C P) in one body
+static int op_rdo_quantize(cdc_handle *h, const char *what, const float *latent, const float *mean, const float *scale, const float *mu,
+                const float *map, int n_map, long long P, float *q_latent, int64_t *moved, int B, long long per_image, int mem, void *stream) {
+    int rc = check_ready(h);
+    if (rc) return rc;
+    if ((rc = require_kind(h, HandleKind::HyperDecoder))) return rc;
+    if (!latent || !mean || !scale || !mu || !q_latent || B < 1 || per_image < 1 || per_image > (1ll << 40) / B)
+        return fail(h, CDC_ERR_INVALID, "null/invalid argument");
+    if (mem != CDC_MEM_HOST && mem != CDC_MEM_DEVICE) return fail(h, CDC_ERR_INVALID, "rdo_quantize: mem_kind %d", mem);
+    if ((rc = check_mu(h, "rdo_quantize", mu, B))) return rc;
+    hipStream_t st = pick_stream(h, stream, mem);
+    Staging s(h, mem, st);
+    const size_t n = (size_t)B * (size_t)per_image;
+    const float *dy = s.in(latent, sizeof(float) * n), *dm = s.in(mean, sizeof(float) * n), *ds = s.in(scale, sizeof(float) * n);
+    cdc::RdoMap gm;
+    if (map) {
+        gm.g = s.in(map, sizeof(float) * (size_t)n_map * (size_t)P);
+        gm.P = (unsigned)P;
+        gm.bs = n_map == 1 ? 0 : P;
+    }
+    float *d_mu = (float *)s.scratch(sizeof(float) * B);
+    int *bad = (int *)s.scratch(sizeof(int));
+    int hbad = 0;
+    if (s.ok()) {
+        HIP_TRY(h, hipStreamSynchronize(st));         // an earlier call's copy out of rdo_stage may still be queued
+        h->rdo_stage.assign(mu, mu + B);
+        s.e = hipMemcpyAsync(d_mu, h->rdo_stage.data(), sizeof(float) * B, hipMemcpyHostToDevice, st);
+    }
+    // the operands the coder refuses are refused here, before anything is written
+    if (s.ok()) s.e = hipMemsetAsync(bad, 0, sizeof(int), st);
+    if (s.ok()) s.e = cdc::rdo_check_launch(dy, dm, ds, (long long)n, bad, st);
+    if (s.ok() && gm.g) s.e = cdc::rdo_map_check_launch(gm.g, (long long)n_map * P, bad, st);
+    if (s.ok()) s.e = hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st);
+    if (s.ok()) s.e = hipStreamSynchronize(st);
+    if (s.ok() && hbad) {
+        (void)s.finish(what);
+        if (hbad & 1) return fail(h, CDC_ERR_INVALID, "rdo_quantize: non-finite or out-of-range latent, mean or scale (nothing written)");
+        return fail(h, CDC_ERR_INVALID, "rdo_quantize_map: a non-finite or negative map value (nothing written)");
+    }
+    float *dq = s.out(q_latent, sizeof(float) * n);
+    long long *dmv = moved ? s.out(reinterpret_cast<long long *>(moved), sizeof(long long) * B) : nullptr;
+    if (s.ok() && dmv) s.e = hipMemsetAsync(dmv, 0, sizeof(long long) * B, st);
+    if (s.ok()) s.e = cdc::rdo_quantize_launch(dy, dm, ds, d_mu, gm, dq, dmv, B, per_image, st);
+    return s.finish(what);
+}
+
 int cdc_op_rdo_quantize(cdc_handle *h, const float *latent, const float *mean, const float *scale, const float *mu, float *q_latent,
                         int64_t *moved, int B, long long per_image, int mem, void *stream) {
     return no_throw(h, [&]() -> int {
-        int rc = check_ready(h);
-        if (rc) return rc;
-        if ((rc = require_kind(h, HandleKind::HyperDecoder))) return rc;
-        if (!latent || !mean || !scale || !mu || !q_latent || B < 1 || per_image < 1 || per_image > (1ll << 40) / B)
-            return fail(h, CDC_ERR_INVALID, "null/invalid argument");
-        if (mem != CDC_MEM_HOST && mem != CDC_MEM_DEVICE) return fail(h, CDC_ERR_INVALID, "rdo_quantize: mem_kind %d", mem);
-        if ((rc = check_mu(h, "rdo_quantize", mu, B))) return rc;
-        hipStream_t st = pick_stream(h, stream, mem);
-        Staging s(h, mem, st);
-        const size_t n = (size_t)B * (size_t)per_image;
-        const float *dy = s.in(latent, sizeof(float) * n), *dm = s.in(mean, sizeof(float) * n), *ds = s.in(scale, sizeof(float) * n);
-        float *d_mu = (float *)s.scratch(sizeof(float) * B);
-        int *bad = (int *)s.scratch(sizeof(int));
-        int hbad = 0;
-        if (s.ok()) {
-            HIP_TRY(h, hipStreamSynchronize(st));         // an earlier call's copy out of rdo_stage may still be queued
-            h->rdo_stage.assign(mu, mu + B);
-            s.e = hipMemcpyAsync(d_mu, h->rdo_stage.data(), sizeof(float) * B, hipMemcpyHostToDevice, st);
-        }
-        // the operands the coder refuses are refused here, before anything is written
-        if (s.ok()) s.e = hipMemsetAsync(bad, 0, sizeof(int), st);
-        if (s.ok()) s.e = cdc::rdo_check_launch(dy, dm, ds, (long long)n, bad, st);
-        if (s.ok()) s.e = hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st);
-        if (s.ok()) s.e = hipStreamSynchronize(st);
-        if (s.ok() && hbad) {
-            (void)s.finish("cdc_op_rdo_quantize");
-            return fail(h, CDC_ERR_INVALID, "rdo_quantize: non-finite or out-of-range latent, mean or scale (nothing written)");
-        }
-        float *dq = s.out(q_latent, sizeof(float) * n);
-        long long *dmv = moved ? s.out(reinterpret_cast<long long *>(moved), sizeof(long long) * B) : nullptr;
-        if (s.ok() && dmv) s.e = hipMemsetAsync(dmv, 0, sizeof(long long) * B, st);
-        if (s.ok()) s.e = cdc::rdo_quantize_launch(dy, dm, ds, d_mu, dq, dmv, B, per_image, st);
-        return s.finish("cdc_op_rdo_quantize");
+        return op_rdo_quantize(h, "cdc_op_rdo_quantize", latent, mean, scale, mu, nullptr, 0, 0, q_latent, moved, B, per_image, mem, stream);
     });
 }
+
+int cdc_op_rdo_quantize_map(cdc_handle *h, const float *latent, const float *mean, const float *scale, const float *mu, const float *map, int n,
+                            float *q_latent, int64_t *moved, int B, int C, int P, int mem, void *stream) {
+    if (!h) return CDC_ERR_INVALID;
+    return no_throw(h, [&] {
+        return with_range_guard(h, [&]() -> int {
+            if (!map) return fail(h, CDC_ERR_INVALID, "rdo_quantize_map: null map");
+            if (B < 1 || C < 1 || P < 1 || (long long)C * P >= (1ll << 31))
+                return fail(h, CDC_ERR_INVALID, "rdo_quantize_map: B=%d C=%d P=%d (all >= 1 and C P < 2^31 expected)", B, C, P);
+            if (n != 1 && n != B) return fail(h, CDC_ERR_INVALID, "rdo_quantize_map: the map has %d rows for a batch of %d (1 or %d expected)", n, B, B);
+            return op_rdo_quantize(h, "cdc_op_rdo_quantize_map", latent, mean, scale, mu, map, n, P, q_latent, moved, B, (long long)C * P, mem, stream);
+        });
+    });
+}
+
 
 int cdc_entropy_set_image_scale(cdc_handle *h, int pixels_per_position) {
     if (!h) return CDC_ERR_INVALID;

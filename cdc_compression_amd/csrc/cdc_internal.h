@@ -353,6 +353,11 @@ hipError_t rate_map_launch(const float *qh, const float *ql, const float *mean, 
 // sse [B][gh][gw] (double), count [B][gh][gw] (or null) over cells of `cell` pixels a side; 3 * min(cell, H) * min(cell, W) < 2^31
 hipError_t sse_map_launch(const MetricView &a, const MetricView &b, int B, int H, int W, int cell, int gh, int gw, double *sse,
                           int32_t *count, hipStream_t st);
+// cells [n][gh][gw]: the mean of src [n][Hf][Wf] over each cell's pixels inside the H x W window, a cell beyond the window the value of
+// the nearest one inside (include/cdc_hip.h: cdc_price_cells); *bad |= 1 for a non-finite or negative value read.  min(cell, H) *
+// min(cell, W) < 2^31.
+hipError_t price_cells_launch(const float *src, int n, int H, int W, int Hf, int Wf, int cell, int gh, int gw, float *cells, int *bad,
+                              hipStream_t st);
 // lpips_kernels.hip (cdc_lpips): what LPIPS-VGG needs beside the planner's convolutions.  Operands as MetricView (device pointers).
 constexpr int LPIPS_TAPS = 5;
 // both operands' H x W windows -> out [2 n][3][H][W]: (2 u - 1 - shift[c]) / scale[c], operand a in rows 0 .. n-1, b in rows n .. 2n-1

@@ -250,6 +250,10 @@ struct cdc_handle {
     // or one per image; empty: off, and the encoder launches latent_symbols_kernel as it always did
     std::vector<float> rdo_mu;
     std::vector<float> rdo_stage; // host staging of the per-image mu (or of a sweep's ladder) of the current call
+    // ... and its price map (cdc_set_rdo_map): rdo_map_n rows (0: off, 1: broadcast, or one per image) of rdo_map_gh x rdo_map_gw validated
+    // values in handle-owned device memory; while set, the encoder and the sweep launch the map forms of the kernels
+    GrowBuf<float> rdo_map;
+    int rdo_map_n = 0, rdo_map_gh = 0, rdo_map_gw = 0;
     int device = 0;
     int arith = default_arith();  // k x k / wide 1x1 convolutions: 1 two fp16 planes (3 MFMA products), 0 three bf16 planes (6)
     std::string err;

@@ -55,21 +55,28 @@ __device__ __forceinline__ int scale_bin(const float *edges, float s) {
 }
 // ---- rate-distortion optimised quantisation (rdo_kernels.hip; the decision: rdo_terms.h) ---------------------------------------
 constexpr int kRdoMaxLadder = 32;
+// A price map (include/cdc_hip.h: cdc_set_rdo_map): g[b * bs + p] >= 0 for latent position p < P of image b (bs = 0: one row for every
+// image); element i of an image [C][P] has position i mod P.  g = null: no map, and the launches below run the kernels they always ran.
+struct RdoMap { const float *g = nullptr; long long bs = 0; unsigned P = 1; };
 // latent_symbols_launch with the decision of rdo_terms.h at mu[b] (device, B values); mu[b] = 0 gives latent_symbols_launch's symbols
 hipError_t latent_symbols_rdo_launch(const float *latent, long long latent_bs, const float *mean, const float *scale, long long ms_bs,
-                                     const float *edges, long long n, int B, const float *mu, int32_t *sym, uint8_t *bin, int *bad, hipStream_t st);
+                                     const float *edges, long long n, int B, const float *mu, const RdoMap &map, int32_t *sym, uint8_t *bin, int *bad,
+                                     hipStream_t st);
 // *bad |= 1 when any of the n (latent, mean, scale) triples is one the coder refuses (non-finite, symbol beyond int32)
 hipError_t rdo_check_launch(const float *latent, const float *mean, const float *scale, long long n, int *bad, hipStream_t st);
+// *bad |= 2 when any of the n map values is non-finite or negative
+hipError_t rdo_map_check_launch(const float *g, long long n, int *bad, hipStream_t st);
 // q[b][i] = (float)k + mean[b][i] with k chosen at mu[b]; moved[b] += symbols with k != k0 (null: not counted; zeroed by the caller)
-hipError_t rdo_quantize_launch(const float *latent, const float *mean, const float *scale, const float *mu, float *q, long long *moved,
-                               int B, long long per, hipStream_t st);
+// (with a map: per = C * map.P < 2^31)
+hipError_t rdo_quantize_launch(const float *latent, const float *mean, const float *scale, const float *mu, const RdoMap &map, float *q,
+                               long long *moved, int B, long long per, hipStream_t st);
 // per image b and ladder entry j < L <= kRdoMaxLadder: bits[b][j] = the hparts hyper partials of image b + the latent prices at mu[j],
 // sse[b][j] = sum (y - q)^2, moved[b][j]; pbits / psse / pmoved: work areas of B * rdo_sweep_parts(n) * L entries each.  *bad as
-// rdo_check_launch.
+// rdo_check_launch.  With a map the walk and every sum keep their order: an all-ones map gives the bits of the call without one.
 int rdo_sweep_parts(long long n);
 hipError_t rdo_sweep_launch(const float *latent, long long latent_bs, const float *mean, const float *scale, long long ms_bs, long long n, int B,
-                            const float *mu, int L, const double *hyper_parts, int hparts, double *pbits, double *psse, long long *pmoved,
-                            double *bits, double *sse, long long *moved, int *bad, hipStream_t st);
+                            const float *mu, int L, const RdoMap &map, const double *hyper_parts, int hparts, double *pbits, double *psse,
+                            long long *pmoved, double *bits, double *sse, long long *moved, int *bad, hipStream_t st);
 // out[b][p], p < hyper_bits_parts(nh): partial sums of the prior's price of the dequantised hyper-latent symbols qh[b][0 .. nh) in bits
 // (hw_h positions per channel; the float32 prices cdc_bpp sums)
 int hyper_bits_parts(long long nh);

@@ -20,8 +20,10 @@
 //                         metric_view.h; two byte operands: integer differences and an exact integer sum, divided once by 65025.0;
 //                         otherwise the float32 difference of the [0, 1] values, its square (exact in double) accumulated in double;
 //                         then an xor butterfly over the 64 lanes.  An element outside the window is never loaded.
+//   price_cells_kernel    sse_map_kernel's structure for cdc_price_cells: a pixel-domain price map reduced to the mean per cell of the
+//                         latent grid, cells beyond the window replicated from the nearest one inside.
 //
-// Both are bound by arithmetic per element (two erfcf and a log2f, or eighteen tanhf and two expf, per symbol), not by memory.
+// The first two are bound by arithmetic per element (two erfcf and a log2f, or eighteen tanhf and two expf, per symbol), not by memory.
 // Compiled with the flags of aux_kernels.hip, so that a symbol's price has bpp_kernel's bits; the pixel arithmetic of metric_view.h
 // is made of _rn intrinsics and does not depend on the contraction flag.
 #include <hip/hip_runtime.h>
@@ -147,6 +149,35 @@ __global__ void __launch_bounds__(256) sse_map_kernel(const DView a, const DView
     }
 }
 
+// One wave per cell of the [n][gh][gw] grid, four cells per workgroup.  A cell beyond the window computes the cell its clamped row and
+// column index name, so it holds that cell's bits.  Lane l adds pixels l, l + 64, ... (row-major inside the cell's part of the window) in
+// double, then the xor butterfly, one division by the count and one cast.  A pixel outside the window is never loaded.
+__global__ void __launch_bounds__(256) price_cells_kernel(const float *src, int H, int W, int Hf, int Wf, int cell, int gh, int gw, long long cells,
+                                                          float *out, int *bad) {
+    const int lane = threadIdx.x & 63;
+    const long long id = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (id >= cells) return;                                 // (uniform in the wave)
+    const long long row = id / gw;
+    const int gx = (int)(id - row * gw), gy = (int)(row % gh);
+    const long long img = row / gh;
+    const int cy = std::min(gy, (H - 1) / cell), cx = std::min(gx, (W - 1) / cell);
+    const long long y0 = (long long)cy * cell, x0 = (long long)cx * cell;
+    const int ch = (int)std::min<long long>(cell, H - y0), cw = (int)std::min<long long>(cell, W - x0);
+    const int n = ch * cw;                                   // >= 1 (the entry point keeps it below 2^31)
+    const float *p = src + ((size_t)img * Hf + (size_t)y0) * Wf + (size_t)x0;
+    double acc = 0.0;
+    bool nok = false;
+    for (int e = lane; e < n; e += 64) {
+        const int yy = e / cw, xx = e - yy * cw;
+        const float v = p[(size_t)yy * Wf + xx];
+        nok |= !(isfinite(v) && v >= 0.f);
+        acc += (double)v;
+    }
+    for (int m = 1; m < 64; m <<= 1) acc += __shfl_xor(acc, m);
+    if (__any(nok) && lane == 0) atomicOr(bad, 1);
+    if (lane == 0) out[id] = (float)(acc / (double)n);
+}
+
 inline size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
 
 void grid_plan(int C, long long npos, int *P, int *logP, int *Cg, int *tiles) {
@@ -213,6 +244,13 @@ hipError_t sse_map_launch(const MetricView &a, const MetricView &b, int B, int H
     const dim3 grid((unsigned)((cells + 3) / 4)), blk(256);
     if (bytes) hipLaunchKernelGGL((sse_map_kernel<true>), grid, blk, 0, st, view(a), view(b), H, W, cell, gh, gw, cells, sse, count);
     else hipLaunchKernelGGL((sse_map_kernel<false>), grid, blk, 0, st, view(a), view(b), H, W, cell, gh, gw, cells, sse, count);
+    return hipGetLastError();
+}
+
+hipError_t price_cells_launch(const float *src, int n, int H, int W, int Hf, int Wf, int cell, int gh, int gw, float *cells, int *bad,
+                              hipStream_t st) {
+    const long long total = (long long)n * gh * gw;
+    hipLaunchKernelGGL(price_cells_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, st, src, H, W, Hf, Wf, cell, gh, gw, total, cells, bad);
     return hipGetLastError();
 }
 

@@ -11,6 +11,16 @@
 // |(k + m) - y| <= 1.5 always.  No expression here changes under contraction: 2 e is exact, so fma(2, e, 1) rounds as 2 e + 1 does,
 // and the comparison keeps the form mu * dR > dD (one product, no difference).  The three kernels of rdo_kernels.hip share this one
 // function, so the quantiser, the coder's symbol kernel and the sweep take the same decision for the same operands.
+//
+// With a price map (include/cdc_hip.h: cdc_set_rdo_map) mu is replaced by the float32 product mu * g of the image's mu and the value
+// g >= 0 of the symbol's latent position (all channels of a position share it):
+//   move  <=>  k0 != 0  and  (mu * g) * dR > dD                                   the two products in this order
+//   g = 1    the rule above bit for bit: mu * 1.0f is exact.
+//   g = 0    never moves (0 * dR > dD is false for dD >= 0; the region is protected).
+//   A float32 product of non-negatives is monotone in each factor, so for a fixed map a symbol that moves at mu still moves at every
+//   larger mu: the host's bisection along a ladder rests on this.
+//   mu * g = +inf (overflow) behaves as the limit: the symbol moves where dR > 0, and inf * 0 = NaN compares false where dR = 0;
+//   no overflow check is needed.
 #pragma once
 #include "rate_terms.h"
 
@@ -22,6 +32,7 @@ struct RdoTerms {
     float dR, dD;
     bool can_move;       // k0 != 0
     __device__ __forceinline__ bool move(float mu) const { return can_move && mu * dR > dD; }
+    __device__ __forceinline__ bool move(float mu, float g) const { return can_move && (mu * g) * dR > dD; }   // g: the position's price
 };
 
 __device__ __forceinline__ RdoTerms rdo_terms(float y, float m, float s) {

@@ -136,10 +136,12 @@ class _GaussianDiffusionBase:
                                            optr, omem, _current_stream(omem)))
         return out
 
-    def _rdo_of(self, images, bitrate_scale=None, rdo=None, target_bpp=None, max_bytes=None):
+    def _rdo_of(self, images, bitrate_scale=None, rdo=None, target_bpp=None, max_bytes=None, price_map=None, price_cells=None):
         """The rate-control arguments of compress / compress_best_of / compress_to_bytes, checked before the library is touched ->
-        the context model's mu (float32, 1 or B values) or None.  target_bpp / max_bytes: the context model chooses mu as its
-        compress_to_bytes does (compressor.py), and forward(rdo=mu) then runs with it."""
+        (mu, cells): the context model's mu (float32, 1 or B values) or None, and its price map on the latent grid of the frame the
+        U-Net asks for (float32 host [1 or B, gh, gw]) or None.  target_bpp / max_bytes: the context model chooses mu as its
+        compress_to_bytes does (compressor.py) -- under the map, when there is one -- and forward(rdo=mu, price_cells=cells) then
+        runs with both."""
         from . import compressor
         compressor.rdo_exclusive(rdo, target_bpp, max_bytes)
         B, _, H, W = frame.image_shape(images)
@@ -148,28 +150,34 @@ class _GaussianDiffusionBase:
         for name, v in (("target_bpp", target_bpp), ("max_bytes", max_bytes)):
             if v is not None:
                 compressor._ContextDecoder._targets(v, B, name)
-        if rdo is None and target_bpp is None and max_bytes is None:
-            return None
+        rated = not (rdo is None and target_bpp is None and max_bytes is None)
+        priced = compressor.price_args(price_map, price_cells, B, (H, W), rated)
+        if not rated:
+            return None, None
         if not hasattr(self.context_fn, "rdo_quantize"):
             raise ValueError("rdo / target_bpp / max_bytes need a context model of this package (rate-distortion optimised quantisation)")
+        cells = self.context_fn._cells_of(priced, (H, W), self.padded_size(H, W))
         if rdo is not None:
-            return mu
+            return mu, cells
         if self.padded_size(H, W) != self.context_fn.padded_size(H, W):
             raise NotImplementedError("target_bpp / max_bytes choose mu on the context model's own frame: a U-Net that needs a larger one "
                                       f"({self.padded_size(H, W)} against {self.context_fn.padded_size(H, W)}) cannot share it")
-        _, info = self.context_fn.compress_to_bytes(images, bitrate_scale, target_bpp=target_bpp, max_bytes=max_bytes, return_info=True)
-        return info["mu"]
+        _, info = self.context_fn.compress_to_bytes(images, bitrate_scale, target_bpp=target_bpp, max_bytes=max_bytes, return_info=True,
+                                                    price_cells=cells)
+        return info["mu"], cells
 
-    def _context_of(self, images, *ctx_args, rate_map=False, rdo=None):
+    def _context_of(self, images, *ctx_args, rate_map=False, rdo=None, price_cells=None):
         """The context model on the padded frame of `images` -> (context_dict with bpp over H * W, B, H, W, Hp, Wp).  rate_map: the
-        dict also holds "rate_map" (this package's compressors only).  rdo: the context model's mu (`_rdo_of`)."""
+        dict also holds "rate_map" (this package's compressors only).  rdo, price_cells: the context model's mu and price map
+        (`_rdo_of`)."""
         B, _, H, W = frame.image_shape(images)
         Hp, Wp = self.padded_size(H, W)
         h, dev = self.denoise_fn._handle(), self.denoise_fn.device_index
         if rate_map and not hasattr(self.context_fn, "rate_map"):
             raise ValueError("maps=True needs a context model with rate_map() (a compressor of this package)")
         if rdo is not None:
-            context_dict = self.context_fn(images, *ctx_args, padded_hw=(Hp, Wp), return_rate_map=rate_map, rdo=rdo)
+            kw = {} if price_cells is None else {"price_cells": price_cells}
+            context_dict = self.context_fn(images, *ctx_args, padded_hw=(Hp, Wp), return_rate_map=rate_map, rdo=rdo, **kw)
         elif rate_map:
             context_dict = self.context_fn(images, *ctx_args, padded_hw=(Hp, Wp), return_rate_map=True)
         elif hasattr(self.context_fn, "_framed"):            # this package's compressor: pads itself, bpp over H * W
@@ -182,13 +190,13 @@ class _GaussianDiffusionBase:
         return context_dict, B, H, W, Hp, Wp
 
     def _compress_frame(self, images, sample_steps, init, eta, loop, *ctx_args, sampler="ddim", spacing="index", trace=None,
-                        rate_map=False, rdo=None):
+                        rate_map=False, rdo=None, price_cells=None):
         """compress() of both trees up to the crop: context model and sampler on the padded frame -> (frame, bpp [B], H, W, Trajectory
         or None), and the context model's rate map of the frame as a sixth entry with rate_map=True.  trace: (trajectory,
         trajectory_of, trajectory_dtype, seed) of the call; loop(shape, context, init, spec, window)."""
         self._sampler_args(sampler, eta)
         spec = None if trace is None else self._trace_spec(*trace[:3], self._steps(sample_steps, spacing), eta, trace[3])
-        context_dict, B, H, W, Hp, Wp = self._context_of(images, *ctx_args, rate_map=rate_map, rdo=rdo)
+        context_dict, B, H, W, Hp, Wp = self._context_of(images, *ctx_args, rate_map=rate_map, rdo=rdo, price_cells=price_cells)
         h, dev = self.denoise_fn._handle(), self.denoise_fn.device_index
         self.set_sample_schedule(self._steps(sample_steps, spacing), sampler=sampler, spacing=spacing)
         rec = loop((B, 3, Hp, Wp), context_dict["output"], frame.extend_init(h, init, B, H, W, Hp, Wp, dev), spec, (H, W))
@@ -212,11 +220,16 @@ class _GaussianDiffusionBase:
         maps=True: where the bits went and where the error remains, on one grid of "map_cell" x "map_cell" pixels (the context model's
         rate_map_cell) over the padded frame: "rate_map" float32 [B, gh, gw] in bits (its sum is bpp * H * W), "sse_map" float64 and
         "sse_count" int32 of the same shape (metrics.sse_map of the reconstruction against `images` under as_saved: sum(sse) /
-        sum(count) is the MSE of "psnr"; the cells of the padding beyond the window have count 0)."""
+        sum(count) is the MSE of "psnr"; the cells of the padding beyond the window have count 0).  With price_map= / price_cells=
+        also "price_cells", float32 [1 or B, gh, gw]: the map the encoder used, so the three maps lie on one grid."""
         from . import metrics
         import inspect
         bound = dict(inspect.signature(self.compress).bind(images, *args, **kwargs).arguments)
         bound.pop("bpp_return_mean", None)                    # bpp comes per image
+        rate_kw = {k: bound.pop(k, None) for k in ("rdo", "target_bpp", "max_bytes", "price_map", "price_cells")}
+        mu, cells = self._rdo_of(images, bound.get("bitrate_scale"), **rate_kw)
+        if mu is not None:
+            bound.update(rdo=mu, price_cells=cells)
         if maps:
             rec, bpp, H, W, traj, rate_map = self._frame_of(**bound, rate_map=True)
         else:
@@ -227,6 +240,8 @@ class _GaussianDiffusionBase:
             cell = self.context_fn.rate_map_cell
             sse, count = metrics.sse_map(self.denoise_fn, rec, images, cell, size=(H, W), as_saved=as_saved, grid=tuple(rate_map.shape[1:]))
             out.update({"rate_map": rate_map, "sse_map": sse, "sse_count": count, "map_cell": cell})
+            if cells is not None:
+                out["price_cells"] = cells
         if self.loss_fn_vgg is not None:
             out["lpips"] = metrics.lpips(self.loss_fn_vgg, rec, images, size=(H, W), as_saved=as_saved)
         if traj is not None:
@@ -504,7 +519,7 @@ class _GaussianDiffusionBase:
         return window(mean), window(m2)
 
     def _best_of(self, images, samples, metric, seed, gamma, eta, sample_steps, sampler, spacing, sample_chunk, as_saved, clip_denoised,
-                 *ctx_args, rdo=None):
+                 *ctx_args, rdo=None, price_cells=None):
         """compress_best_of of both trees."""
         from . import metrics
         K = _samples.check_args(samples, seed, gamma, eta, sample_chunk=sample_chunk, metric=metric)
@@ -516,7 +531,7 @@ class _GaussianDiffusionBase:
             raise ValueError(f"MS-SSIM needs min(H, W) > 160, got {H} x {W}")
         higher = _samples.METRICS[metric]
         all_seeds = sample_seeds(seed, B, K)
-        context_dict, B, H, W, Hp, Wp = self._context_of(images, *ctx_args, rdo=rdo)
+        context_dict, B, H, W, Hp, Wp = self._context_of(images, *ctx_args, rdo=rdo, price_cells=price_cells)
         context = context_dict["output"]
         self.set_sample_schedule(self._steps(sample_steps, spacing), sampler=sampler, spacing=spacing)
         un = self.denoise_fn
@@ -545,12 +560,13 @@ class _GaussianDiffusionBase:
                 "score": scores[np.arange(B), best_k], "scores": scores}
 
 
-    def compress_to_bytes(self, images, bitrate_scale=None, rdo=None, target_bpp=None, max_bytes=None, return_info=False):
+    def compress_to_bytes(self, images, bitrate_scale=None, rdo=None, target_bpp=None, max_bytes=None, return_info=False,
+                          price_map=None, price_cells=None):
         """The transmitted half of compress(): images -> one entropy-coded bitstream per image.
         `decompress(streams, shape, sample_steps, init)` reconstructs from them.  bitrate_scale: the rate of a
         variable-bitrate context model (1 or B values), recorded in each stream.  Images of any size: a stream records H x W
         unless the image is its own padded frame.  rdo / target_bpp / max_bytes / return_info: the context model's rate control
-        (compressor.compress_to_bytes); the decoder side needs nothing."""
+        (compressor.compress_to_bytes), price_map / price_cells its region-of-interest map; the decoder side needs nothing."""
         from . import compressor
         compressor.rdo_exclusive(rdo, target_bpp, max_bytes)
         B, _, H, W = frame.image_shape(images)
@@ -559,12 +575,15 @@ class _GaussianDiffusionBase:
         for name, v in (("target_bpp", target_bpp), ("max_bytes", max_bytes)):
             if v is not None:
                 compressor._ContextDecoder._targets(v, B, name)
+        priced = compressor.price_args(price_map, price_cells, B, (H, W), not (rdo is None and target_bpp is None and max_bytes is None))
         if self.padded_size(H, W) != self.context_fn.padded_size(H, W):
             raise NotImplementedError("the stream records the image size against the context model's own multiple: a U-Net that needs a "
                                       f"larger one ({self.padded_size(H, W)} against {self.context_fn.padded_size(H, W)}) cannot share it")
         kw = {k: v for k, v in (("rdo", rdo), ("target_bpp", target_bpp), ("max_bytes", max_bytes)) if v is not None}
         if return_info:
             kw["return_info"] = True
+        if priced is not None:
+            kw["price_map" if priced[0] == "map" else "price_cells"] = priced[1]
         if bitrate_scale is None:
             return self.context_fn.compress_to_bytes(images, **kw)
         return self.context_fn.compress_to_bytes(images, bitrate_scale, **kw)
@@ -595,36 +614,39 @@ class GaussianDiffusionX(_GaussianDiffusionBase):
         return self._loop(tuple(shape), context, clip_denoised, init, eta, seed, gamma, sampler, spec, window)
 
     def _frame_of(self, images, sample_steps=None, init=None, eta=0, seed=None, gamma=None, sampler="ddim", spacing="index",
-                  trajectory=None, trajectory_of="x0", trajectory_dtype="float32", rate_map=False, rdo=None):
+                  trajectory=None, trajectory_of="x0", trajectory_dtype="float32", rate_map=False, rdo=None, price_cells=None):
         self._seed_args(seed, gamma, init, frame.image_shape(images)[0])
         return self._compress_frame(images, sample_steps, init, eta,
                                     lambda shape, ctx, i, spec, win: self.p_sample_loop(shape, ctx, clip_denoised=True, init=i, eta=eta,
                                                                                         seed=seed, gamma=gamma, trajectory=spec,
                                                                                         window=win),   # :223
                                     sampler=sampler, spacing=spacing, trace=(trajectory, trajectory_of, trajectory_dtype, seed),
-                                    rate_map=rate_map, rdo=rdo)
+                                    rate_map=rate_map, rdo=rdo, price_cells=price_cells)
 
     def compress(self, images, sample_steps=None, bpp_return_mean=True, init=None, eta=0, seed=None, gamma=None, sampler="ddim",
                  spacing="index", trajectory=None, trajectory_of="x0", trajectory_dtype="float32", rdo=None, target_bpp=None,
-                 max_bytes=None):
+                 max_bytes=None, price_map=None, price_cells=None):
         """trajectory=: -> (reconstruction, bpp, Trajectory) (cdc_compression_amd.trajectory).  rdo / target_bpp / max_bytes: the
-        context model's rate control (compressor.compress_to_bytes); bpp is that of the symbols it chose."""
-        mu = self._rdo_of(images, None, rdo, target_bpp, max_bytes)
+        context model's rate control (compressor.compress_to_bytes); bpp is that of the symbols it chose.  price_map / price_cells
+        (with one of them): its region-of-interest map, in pixels at the image's size or on the latent grid."""
+        mu, cells = self._rdo_of(images, None, rdo, target_bpp, max_bytes, price_map, price_cells)
         rec, bpp, H, W, traj = self._frame_of(images, sample_steps, init, eta, seed, gamma, sampler, spacing, trajectory, trajectory_of,
-                                              trajectory_dtype, rdo=mu)
+                                              trajectory_dtype, rdo=mu, price_cells=cells)
         res = (self._window(rec, H, W), (bpp.mean() if bpp_return_mean else bpp))
         return res if traj is None else res + (traj,)
 
 
     def compress_best_of(self, images, samples, metric="psnr", seed=None, gamma=None, eta=0, sample_steps=None, sampler="ddim",
-                         spacing="index", sample_chunk=None, as_saved=True, rdo=None, target_bpp=None, max_bytes=None):
+                         spacing="index", sample_chunk=None, as_saved=True, rdo=None, target_bpp=None, max_bytes=None, price_map=None,
+                         price_cells=None):
         """The encoder's closed loop: the context model once, then `samples` seeded decodes per image (seeds
         parallel.sample_seeds(seed, B, samples)), each scored on the device against `images` on the frame's H x W window
         (metric "psnr" / "ms_ssim": higher is better; "lpips": lower, needs self.loss_fn_vgg; ties go to the lowest k, a NaN never
         beats a number) -> {"reconstruction": the winner's window, "bpp": [B], "seed": uint64 [B], ready for decompress(..., seed=),
-        "sample": int [B], "score": [B], "scores": [B, samples]}.  rdo / target_bpp / max_bytes: as compress()."""
-        mu = self._rdo_of(images, None, rdo, target_bpp, max_bytes)
-        return self._best_of(images, samples, metric, seed, gamma, eta, sample_steps, sampler, spacing, sample_chunk, as_saved, True, rdo=mu)
+        "sample": int [B], "score": [B], "scores": [B, samples]}.  rdo / target_bpp / max_bytes / price_map / price_cells: as compress()."""
+        mu, cells = self._rdo_of(images, None, rdo, target_bpp, max_bytes, price_map, price_cells)
+        return self._best_of(images, samples, metric, seed, gamma, eta, sample_steps, sampler, spacing, sample_chunk, as_saved, True, rdo=mu,
+                             price_cells=cells)
 
 
 class GaussianDiffusionEps(_GaussianDiffusionBase):
@@ -654,28 +676,31 @@ class GaussianDiffusionEps(_GaussianDiffusionBase):
 
     def _frame_of(self, images, sample_steps=None, bitrate_scale=None, sample_mode="ddpm", init=None, eta=0, seed=None, gamma=None,
                   sampler="ddim", spacing="index", trajectory=None, trajectory_of="x0", trajectory_dtype="float32", rate_map=False,
-                  rdo=None):
+                  rdo=None, price_cells=None):
         self._seed_args(seed, gamma, init, frame.image_shape(images)[0])
         return self._compress_frame(images, sample_steps, init, eta,
                                     lambda shape, ctx, i, spec, win: self.p_sample_loop(shape, ctx, sample_mode, init=i, eta=eta, seed=seed,
                                                                                         gamma=gamma, trajectory=spec, window=win),
                                     bitrate_scale, sampler=sampler, spacing=spacing,
-                                    trace=(trajectory, trajectory_of, trajectory_dtype, seed), rate_map=rate_map, rdo=rdo)
+                                    trace=(trajectory, trajectory_of, trajectory_dtype, seed), rate_map=rate_map, rdo=rdo,
+                                    price_cells=price_cells)
 
     def compress(self, images, sample_steps=None, bitrate_scale=None, sample_mode="ddpm",
                  bpp_return_mean=True, init=None, eta=0, seed=None, gamma=None, sampler="ddim", spacing="index",
-                 trajectory=None, trajectory_of="x0", trajectory_dtype="float32", rdo=None, target_bpp=None, max_bytes=None):
-        """trajectory=: -> (reconstruction, bpp, Trajectory) (cdc_compression_amd.trajectory).  rdo / target_bpp / max_bytes: as
-        GaussianDiffusionX.compress."""
-        mu = self._rdo_of(images, bitrate_scale, rdo, target_bpp, max_bytes)
+                 trajectory=None, trajectory_of="x0", trajectory_dtype="float32", rdo=None, target_bpp=None, max_bytes=None,
+                 price_map=None, price_cells=None):
+        """trajectory=: -> (reconstruction, bpp, Trajectory) (cdc_compression_amd.trajectory).  rdo / target_bpp / max_bytes /
+        price_map / price_cells: as GaussianDiffusionX.compress."""
+        mu, cells = self._rdo_of(images, bitrate_scale, rdo, target_bpp, max_bytes, price_map, price_cells)
         rec, bpp, H, W, traj = self._frame_of(images, sample_steps, bitrate_scale, sample_mode, init, eta, seed, gamma, sampler, spacing,
-                                              trajectory, trajectory_of, trajectory_dtype, rdo=mu)
+                                              trajectory, trajectory_of, trajectory_dtype, rdo=mu, price_cells=cells)
         res = (self._window(rec, H, W), (bpp.mean() if bpp_return_mean else bpp))
         return res if traj is None else res + (traj,)
 
     def compress_best_of(self, images, samples, metric="psnr", seed=None, gamma=None, eta=0, sample_steps=None, sampler="ddim",
-                         spacing="index", sample_chunk=None, as_saved=True, bitrate_scale=None, rdo=None, target_bpp=None, max_bytes=None):
+                         spacing="index", sample_chunk=None, as_saved=True, bitrate_scale=None, rdo=None, target_bpp=None, max_bytes=None,
+                         price_map=None, price_cells=None):
         """GaussianDiffusionX.compress_best_of with this tree's context argument (bitrate_scale of a variable-bitrate model)."""
-        mu = self._rdo_of(images, bitrate_scale, rdo, target_bpp, max_bytes)
+        mu, cells = self._rdo_of(images, bitrate_scale, rdo, target_bpp, max_bytes, price_map, price_cells)
         return self._best_of(images, samples, metric, seed, gamma, eta, sample_steps, sampler, spacing, sample_chunk, as_saved,
-                             self.clip_noise, bitrate_scale, rdo=mu)
+                             self.clip_noise, bitrate_scale, rdo=mu, price_cells=cells)

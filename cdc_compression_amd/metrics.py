@@ -6,6 +6,7 @@ are numpy, torch-cpu or torch-cuda tensors, float32 (in [-1, 1], mapped as `clam
 `as_saved=True` measures a float32 operand through the uint8 image the reference's script would save.  The header states the
 definition (PSNR: the reference's per-image `batch_psnr`; MS-SSIM: the conventions of pytorch-msssim 0.2.1, `data_range=1`).
 `sse_map` is the squared error per cell of a grid over the window (cdc_distortion_map), the picture beside a compressor's `rate_map`.
+`psnr_weighted` composes it on the host into a PSNR with a weight per cell: the figure of region-of-interest coding (`price_map=`).
 `lpips` is the third axis: LPIPS-VGG of lpips 0.1.4 on the same operands (cdc_lpips; the model is an `lpips.LpipsVGG`, which holds
 the network's weights).  Results are float64 NumPy arrays of `B` values."""
 import ctypes
@@ -142,6 +143,38 @@ def sse_map(model, a, b, cell, size=None, as_saved=False, grid=None):
     if keep is not None:
         sse, count = keep[0].cpu().numpy(), keep[1].cpu().numpy()
     return sse, count
+
+
+def weighted_psnr_of(sse, count, cell_weights):
+    """The host composition of `psnr_weighted`: sse float64 / count int32 [B, gh, gw] of `sse_map` and weights [gh, gw], [1, gh, gw] or
+    [B, gh, gw] (finite, >= 0, a positive total over the cells inside the window) -> 10 log10(1 / (sum w sse / sum w count)) per image,
+    float64 [B]; +inf where the weighted error is 0."""
+    sse, count = np.asarray(sse, np.float64), np.asarray(count, np.float64)
+    w = np.asarray(cell_weights.detach().cpu().numpy() if _is_torch(cell_weights) else cell_weights, np.float64)
+    if w.ndim == 2:
+        w = w[None]
+    if sse.ndim != 3 or count.shape != sse.shape or w.ndim != 3 or w.shape[1:] != sse.shape[1:] or w.shape[0] not in (1, sse.shape[0]):
+        raise ValueError(f"cell_weights of shape {w.shape} for maps of shape {sse.shape}: [gh, gw], [1, gh, gw] or [B, gh, gw] expected")
+    if not np.all(np.isfinite(w)) or np.any(w < 0):
+        raise ValueError("cell_weights: every weight must be finite and >= 0")
+    num, den = (w * sse).reshape(sse.shape[0], -1).sum(1), (w * count).reshape(sse.shape[0], -1).sum(1)
+    if np.any(den <= 0):
+        raise ValueError("cell_weights: no weight on any pixel of the window")
+    with np.errstate(divide="ignore"):
+        return 10.0 * np.log10(1.0 / (num / den))
+
+
+def psnr_weighted(model, a, b, cell_weights, cell, size=None, as_saved=False):
+    """PSNR with a weight per cell of `sse_map`'s grid -- the figure a region-of-interest user reports: 10 log10(1 / (sum w sse /
+    sum w count)) per image, float64 [B], composed on the host in float64 from `sse_map(model, a, b, cell, size, as_saved, grid)`.
+    cell_weights: [gh, gw], [1, gh, gw] or [B, gh, gw], finite and >= 0; its grid may be the default one of the window or a larger one
+    (the rate map's, of the padded frame: cells beyond the window have count 0 and do not weigh).  All weights equal gives `psnr`'s MSE
+    to float64 rounding."""
+    w = cell_weights.detach().cpu().numpy() if _is_torch(cell_weights) else np.asarray(cell_weights)
+    if w.ndim not in (2, 3):
+        raise ValueError(f"cell_weights of shape {w.shape}: [gh, gw], [1, gh, gw] or [B, gh, gw] expected")
+    sse, count = sse_map(model, a, b, cell, size=size, as_saved=as_saved, grid=tuple(w.shape[-2:]))
+    return weighted_psnr_of(sse, count, w)
 
 
 def lpips(model, a, b, size=None, as_saved=False, return_layers=False):

@@ -664,6 +664,48 @@ int cdc_entropy_rate_sweep(cdc_handle *hyperdec, const float *latent, const floa
 int cdc_op_rdo_quantize(cdc_handle *hyperdec, const float *latent, const float *mean, const float *scale, const float *mu /*[B] host*/,
                         float *q_latent, int64_t *moved /*[B] or NULL*/, int B, long long per_image, int mem_kind, void *stream);
 
+/* ---- region-of-interest coding: a price per latent position steers the decision above (csrc/rdo_terms.h, rdo_kernels.hip, map_kernels.hip)
+ * THE DECISION WITH A PRICE MAP.  A price map g is float32, finite and >= 0, one value per latent position: [n][P] with P = h_lat w_lat
+ * and n = 1 (every image) or B (one row per image).  All channels of a position share its value: element i of an image's latent
+ * [C][h_lat][w_lat] has position i mod P.  The rule above stays, with mu replaced by the float32 product mu_b * g[b][p]:
+ *   move  <=>  k0 != 0  and  (mu * g) * dR > dD                     float32, the two products in this order
+ * Consequences: g = 1 is the scalar rule bit for bit (mu * 1.0f is exact); g = 0 never moves (the region is protected); a float32
+ * product of non-negatives is monotone, so for any fixed map a symbol that moves at mu moves at every larger mu (a bisection along a
+ * ladder of mu stays valid, and cdc_entropy_rate_sweep stays exactly monotone); a product that overflows to +inf behaves as the limit
+ * (it moves where dR > 0; inf * 0 = NaN compares false where dR = 0).  The decision stays separable per symbol: no trellis, no change
+ * to the streams, nothing for the decoder to learn, for every model.  What a map does to decoded images of trained weights has not
+ * been measured.
+ *
+ * cdc_price_cells: from a pixel-domain map to cells.  pixel_map is float32 [n][Hf][Wf] (n = 1 or B; B is the batch the map is meant
+ *   for and only bounds n), of which the top-left H x W window is read, with row / image strides Hf >= H, Wf >= W as for the image
+ *   views of cdc_distortion_map.  A grid of gh x gw cells of cell x cell pixels anchored at the top-left pixel, gh cell >= H and
+ *   gw cell >= W (for the encoder: cell = the pixels per latent position and side, the grid = the latent grid of the padded frame).
+ *   cells [n][gh][gw] float32: a cell's value is the mean of the map over the cell's pixels INSIDE the window: pixel e of that part
+ *   (row-major) goes to lane e mod 64 in ascending order in float64, then an xor butterfly over the 64 lanes, a float64 division by
+ *   the count and one cast to float32 (one wave per cell, as the error side of cdc_distortion_map).  A cell wholly outside the window
+ *   takes the value of the nearest cell that is not (row and column index clamped): the edge replication the frame itself uses.
+ *   Nothing outside the window is read.  pixel_map and cells follow mem_kind (host results: the call synchronises); any handle kind.
+ *   CDC_ERR_INVALID, with a message and before any launch: a null pointer; n not 1 or B; B, H, W or cell < 1; Hf < H or Wf < W; a grid
+ *   that does not cover the window; sizes beyond the launch limits.  CDC_ERR_INVALID with NOTHING WRITTEN to cells: a non-finite or
+ *   negative value inside the window (the kernel raises a flag that is read before the result is released; the call synchronises).
+ * cdc_set_rdo_map: state of a hyper-decoder handle, like cdc_set_rdo.  n = 0 turns it off (cells may be NULL); n = 1 is one map for
+ *   every image; n = B one per image.  cells [n][gh][gw] follows mem_kind; the values are validated (finite, >= 0: CDC_ERR_INVALID, the
+ *   map of the handle unchanged) and copied into handle-owned device memory before the call returns.  While a map is set,
+ *   cdc_entropy_encode, cdc_entropy_encode_image and cdc_entropy_rate_sweep take every decision with it (the map forms of the
+ *   kernels); with none set they launch exactly what they always launched.  Those calls return CDC_ERR_INVALID when gh x gw is not
+ *   their latent grid (U h_hyper x U w_hyper) or when their batch is neither 1 nor n images, and the encoders return CDC_ERR_STATE
+ *   when they find a map but no mu (cdc_set_rdo): a map is never silently ignored.  Image b's stream depends on its own mu and its
+ *   own map row only (the batch = batch-1 contract holds); cdc_entropy_rate_sweep prices its ladder mu[L] under image b's row.
+ * cdc_op_rdo_quantize_map: cdc_op_rdo_quantize on operands [B][C][P] with a map [n][P] (n = 1 or B) that follows mem_kind like the
+ *   operands; mu [B] is a HOST array.  C P < 2^31.  A non-finite operand or a non-finite / negative map value is CDC_ERR_INVALID with
+ *   nothing written (check kernels run first). */
+int cdc_price_cells(cdc_handle *h, const float *pixel_map, int n, int B, int H, int W, int Hf, int Wf, int cell, int gh, int gw,
+                    float *cells /*[n][gh][gw]*/, int mem_kind, void *stream);
+int cdc_set_rdo_map(cdc_handle *hyperdec, const float *cells /*[n][gh][gw]*/, int n, int gh, int gw, int mem_kind, void *stream);
+int cdc_op_rdo_quantize_map(cdc_handle *hyperdec, const float *latent, const float *mean, const float *scale, const float *mu /*[B] host*/,
+                            const float *map /*[n][P]*/, int n, float *q_latent, int64_t *moved /*[B] or NULL*/, int B, int C, int P,
+                            int mem_kind, void *stream);
+
 /* ---- LPIPS-VGG of decoded images on the device: the perceptual axis (csrc/lpips_kernels.hip, build_lpips_program) ----------------
  * THE DEFINITION.  LPIPS of the lpips package, version 0.1.4: LPIPS(net="vgg", lpips=True, spatial=False).forward(in0, in1,
  * normalize=False), per image.  The reference trains with it (xparam/modules/denoising_diffusion.py:47,331-336) and its checkpoints
