@@ -174,6 +174,12 @@ def lib():
     L.cdc_randn.argtypes = [H, u64p, _i, ctypes.c_int64, ctypes.c_uint32, ctypes.c_float, _vp, _i, _vp]
     L.cdc_randn_host.argtypes = [u64p, _i, ctypes.c_int64, ctypes.c_uint32, ctypes.c_float, _vp]
     L.cdc_philox4x32_10.argtypes = [ctypes.POINTER(ctypes.c_uint32)] * 3
+    i32p = ctypes.POINTER(ctypes.c_int32)
+    L.cdc_set_noise_frames.argtypes = [H, i32p, _i]
+    L.cdc_randn_framed.argtypes = [H, u64p, i32p, _i, _i, _i, _i, ctypes.c_uint32, ctypes.c_float, _vp, _i, _vp]
+    L.cdc_randn_framed_host.argtypes = [u64p, i32p, _i, _i, _i, _i, ctypes.c_uint32, ctypes.c_float, _vp]
+    L.cdc_tile_gather.argtypes = [H, _vp, _vp, i32p] + [_i] * 8 + [_vp]
+    L.cdc_tile_blend.argtypes = [H, _vp, _vp, i32p, _i, i32p, _i, _vp] + [_i] * 14 + [_vp]
     L.cdc_prof_enable.argtypes = [H, _i]
     L.cdc_prof_name.argtypes = [_i]
     L.cdc_prof_name.restype = ctypes.c_char_p
@@ -218,7 +224,8 @@ EXPORTS = ["cdc_create", "cdc_destroy", "cdc_last_error", "cdc_version", "cdc_nu
            "cdc_repeat_images", "cdc_decode_samples", "cdc_sample_moments", "cdc_sample_select",
            "cdc_set_trace", "cdc_trace_info", "cdc_trace_read", "cdc_op_trace_tap",
            "cdc_rate_map", "cdc_distortion_map", "cdc_set_rdo", "cdc_entropy_rate_sweep", "cdc_op_rdo_quantize",
-           "cdc_price_cells", "cdc_set_rdo_map", "cdc_op_rdo_quantize_map"]
+           "cdc_price_cells", "cdc_set_rdo_map", "cdc_op_rdo_quantize_map",
+           "cdc_set_noise_frames", "cdc_randn_framed", "cdc_randn_framed_host", "cdc_tile_gather", "cdc_tile_blend"]
 
 
 def handle_status(handle):

@@ -309,6 +309,8 @@ void cdc_destroy(cdc_handle *h) {
     h->d_time_steps.release();
     h->d_shift_tab.release();
     h->seeds.dev.release();
+    h->frames.dev.release();
+    h->tile_meta.dev.release();
     h->d_stab.release();
     h->d_hist.release();
     h->d_rep_stage.release();
@@ -1069,8 +1071,31 @@ static SamplerArgs sampler_args(cdc_handle *h, const float *fx, const float *x, 
     return s;
 }
 
-// The noise of a DDIM step (eta != 0): a tensor, or the per-image seeds of the generator on the device
-struct StepNoise { const float *tensor = nullptr; const unsigned long long *seeds = nullptr; };
+// The noise of a DDIM step (eta != 0): a tensor, or the per-image seeds of the generator on the device -- with `frames` (device rows
+// of cdc_set_noise_frames) the draws are indexed on each row's frame
+struct StepNoise { const float *tensor = nullptr; const unsigned long long *seeds = nullptr; const NoiseFrame *frames = nullptr;
+                   bool frames_quad = false; };
+
+// The frames of a seeded call of B rows of C x H x W (cdc_set_noise_frames): none set -> *dframes = null and the call launches what it
+// always did; else the rows checked against the call and staged on the device.
+static int stage_noise_frames(cdc_handle *h, const char *what, int B, int C, int H, int W, hipStream_t st, const NoiseFrame **dframes, bool *quad) {
+    *dframes = nullptr; *quad = false;
+    if (h->noise_frames.empty()) return CDC_OK;
+    if ((int)h->noise_frames.size() != B)
+        return fail(h, CDC_ERR_INVALID, "%s: %zu noise frames are set (cdc_set_noise_frames), the call has %d rows", what, h->noise_frames.size(), B);
+    for (int b = 0; b < B; ++b) {
+        const NoiseFrame &f = h->noise_frames[b];
+        if (f.y0 > f.frame_h - H || f.x0 > f.frame_w - W)
+            return fail(h, CDC_ERR_INVALID, "%s: row %d is a %d x %d window at (%d, %d), outside its %d x %d noise frame", what, b, H, W, f.y0, f.x0, f.frame_h, f.frame_w);
+        if ((long long)C * f.frame_h * f.frame_w > (1ll << 34))
+            return fail(h, CDC_ERR_INVALID, "%s: row %d: %d x %d x %d frame elements, beyond the generator's 2^34", what, b, C, f.frame_h, f.frame_w);
+    }
+    int rc = h->frames.stage(h, h->noise_frames.data(), (size_t)B, st);
+    if (rc) return rc;
+    *dframes = h->frames.dev.p;
+    *quad = h->noise_frames_quad && (W & 3) == 0;
+    return CDC_OK;
+}
 
 // One iteration: the U-Net on h->in_x, then the update h->in_x -> x_out.  solver: x_out = a x + b x0 + c hist, hist <- x0 (h->d_hist, in
 // place); else the DDIM update with `noise`.  The 7-row combine of the final convolution rides in the sampler kernel (one launch and a
@@ -1098,7 +1123,7 @@ static int sampler_on_device(cdc_handle *h, bool solver, int i, StepNoise noise,
     else {
         DdimArgs d = {s};
         d.eta = eta;
-        if (eta != 0.f && noise.seeds) { d.seeds = noise.seeds; d.per_image = s.n / B; }
+        if (eta != 0.f && noise.seeds) { d.seeds = noise.seeds; d.per_image = s.n / B; d.frames = noise.frames; d.frames_quad = noise.frames_quad; }
         else if (eta != 0.f) d.noise = noise.tensor;
         rc = run_op(h, Op(PC_SMALL, d, 0, 16.0 * s.n), B, st);
     }
@@ -1231,21 +1256,27 @@ static int decode_impl(cdc_handle *h, const float *init, float gamma, const uint
         // a range fault comes through here again and regenerates both from the seeds
         const bool gen_init = seeds && !init && gamma != 0.f;
         const unsigned long long *dseeds = nullptr;
+        const NoiseFrame *dframes = nullptr;
+        bool fquad = false;
         if (seeds && (gen_init || eta != 0.f)) {
             if ((rc = h->seeds.stage(h, seeds, (size_t)B, st))) return rc;
             dseeds = h->seeds.dev.p;
+            if (rep && !h->noise_frames.empty())
+                return fail(h, CDC_ERR_INVALID, "cdc_decode_samples: noise frames are set (cdc_set_noise_frames); a tiled decode is a single decode");
+            if ((rc = stage_noise_frames(h, "decode", B, h->cfg.channels, H, W, st, &dframes, &fquad))) return rc;
         }
         // one iteration, in place on h->in_x; i = -2: the step index comes from h->d_step (graph capture)
         const bool tr_u8 = traced && (h->tr_what & CDC_TRACE_U8);
         uint8_t *const tr_x0 = traced && (h->tr_what & CDC_TRACE_X0) ? (uint8_t *)h->trace_buf : nullptr;
         uint8_t *const tr_xt = !traced || !(h->tr_what & CDC_TRACE_XT) ? nullptr : (uint8_t *)h->trace_buf + (tr_x0 ? (size_t)n_slots * h->tr_slot_bytes : 0);
         auto iterate = [&](int i, hipStream_t s) {
-            if (!traced || i < 0 || slot_of[i] < 0) return sampler_on_device(h, solver, i, {nullptr, dseeds}, eta, h->in_x, B, H, W, pred_mode, clip, s);
+            if (!traced || i < 0 || slot_of[i] < 0) return sampler_on_device(h, solver, i, {nullptr, dseeds, dframes, fquad}, eta, h->in_x, B, H, W, pred_mode, clip, s);
             const size_t off = (size_t)slot_of[i] * h->tr_slot_bytes;
             const TraceStep t = {tr_x0 ? tr_x0 + off : nullptr, tr_xt ? tr_xt + off : nullptr, tr_u8 ? 1 : 0, h->tr_H, h->tr_W};
-            return sampler_on_device(h, solver, i, {nullptr, dseeds}, eta, h->in_x, B, H, W, pred_mode, clip, s, &t);
+            return sampler_on_device(h, solver, i, {nullptr, dseeds, dframes, fquad}, eta, h->in_x, B, H, W, pred_mode, clip, s, &t);
         };
         if (init) { if ((rc = copy_in(h, h->in_x, init, n, mem, st))) return rc; }
+        else if (gen_init && dframes) HIP_TRY(h, randn_framed_launch(dseeds, dframes, fquad, B, h->cfg.channels, H, W, 0u, gamma, h->in_x, st));
         else if (gen_init) HIP_TRY(h, randn_fill_launch(dseeds, B, (long long)(n / B), 0u, gamma, h->in_x, st));
         else HIP_TRY(h, hipMemsetAsync(h->in_x, 0, n * sizeof(float), st));
         if ((rc = rep ? stage_ctx_repeated(h, ctx, n_ctx, B / rep, rep, mem, st) : stage_ctx(h, ctx, n_ctx, B, mem, st))) return rc;
@@ -1275,7 +1306,7 @@ static int decode_impl(cdc_handle *h, const float *init, float gamma, const uint
             --i;
             int eta_bits;
             memcpy(&eta_bits, &eta, sizeof eta_bits);
-            const int key[8] = {h->steps, pred_mode, clip, h->sched_gen, eta_bits, dseeds != nullptr, solver ? 1 : 0, solver ? h->solver_gen : 0};
+            const int key[8] = {h->steps, pred_mode, clip, h->sched_gen, eta_bits, dseeds ? (dframes ? (fquad ? 3 : 2) : 1) : 0, solver ? 1 : 0, solver ? h->solver_gen : 0};
             if (!h->graph_exec || memcmp(key, h->graph_key, sizeof key)) {
                 if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
                 hipGraph_t g = nullptr;
@@ -1487,6 +1518,9 @@ int cdc_op_ddim_update(cdc_handle *h, const float *fx, const float *x, const flo
             hipStream_t st = pick_stream(h, stream, mem);
             const size_t n = (size_t)B * C * H * W, bytes = n * sizeof(float);
             if (eta != 0.f && seeds && (rc = h->seeds.stage(h, seeds, (size_t)B, st))) return rc;
+            const NoiseFrame *dframes = nullptr;
+            bool fquad = false;
+            if (eta != 0.f && seeds && (rc = stage_noise_frames(h, "ddim_update", B, C, H, W, st, &dframes, &fquad))) return rc;
             Staging s(h, mem, st);
             const float *dfx = fx ? s.in(fx, bytes) : nullptr, *dx = s.in(x, bytes);
             const float *dP = planes ? s.in(planes, bytes * KH) : nullptr;
@@ -1497,7 +1531,7 @@ int cdc_op_ddim_update(cdc_handle *h, const float *fx, const float *x, const flo
                 DdimArgs d = {sampler_args(h, dfx, dx, dn, i, B, C, H, W, pred_mode, clip, nullptr)};
                 if (dP) { d.s.P = dP; d.s.P_bias = dPb; d.s.pKH = KH; d.s.pPad = pad; }
                 d.eta = eta;
-                if (eta != 0.f && seeds) { d.seeds = h->seeds.dev.p; d.per_image = (long long)(n / B); }
+                if (eta != 0.f && seeds) { d.seeds = h->seeds.dev.p; d.per_image = (long long)(n / B); d.frames = dframes; d.frames_quad = fquad; }
                 else d.noise = dz;
                 s.e = ddim_launch(d, st);
             }
@@ -1653,6 +1687,196 @@ int cdc_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out
     if (!ctr || !key || !out) return CDC_ERR_INVALID;
     cdcrng::philox4x32_10(ctr[0], ctr[1], ctr[2], ctr[3], key[0], key[1], out);
     return CDC_OK;
+}
+
+// ---- frame-indexed draws and the tiles of a tiled decode (rng.h, sampler_kernels.hip, tile_kernels.hip) -----------------------------
+// rows [n][4] = {frame_h, frame_w, y0, x0}: each a non-empty frame and an origin inside it; -> null, or what is wrong.  *quad: every
+// frame_w and x0 is a multiple of 4.
+static const char *noise_rows_check(const int32_t *rows, int n, bool *quad) {
+    *quad = true;
+    for (int b = 0; b < n; ++b) {
+        const int32_t *r = rows + 4 * b;
+        if (r[0] < 1 || r[1] < 1) return "a frame of less than 1 x 1";
+        if (r[2] < 0 || r[3] < 0 || r[2] >= r[0] || r[3] >= r[1]) return "an origin outside its frame";
+        if ((r[1] & 3) || (r[3] & 3)) *quad = false;
+    }
+    return nullptr;
+}
+
+int cdc_set_noise_frames(cdc_handle *h, const int32_t *rows, int n) {
+    if (!h) return CDC_ERR_INVALID;
+    return no_throw(h, [&]() -> int {
+        int rc = require_kind(h, HandleKind::Unet);
+        if (rc) return rc;
+        if (n < 0 || n > 65535 || (n > 0 && !rows)) return fail(h, CDC_ERR_INVALID, "set_noise_frames: n = %d%s", n, n > 0 && !rows ? " with null rows" : "");
+        if (n == 0) { h->noise_frames.clear(); h->noise_frames_quad = false; return CDC_OK; }
+        bool quad;
+        if (const char *bad = noise_rows_check(rows, n, &quad)) return fail(h, CDC_ERR_INVALID, "set_noise_frames: %s", bad);
+        h->noise_frames.resize((size_t)n);
+        for (int b = 0; b < n; ++b) h->noise_frames[b] = {rows[4 * b], rows[4 * b + 1], rows[4 * b + 2], rows[4 * b + 3]};
+        h->noise_frames_quad = quad;
+        return CDC_OK;
+    });
+}
+
+// what cdc_randn_framed and its host twin check: -> null, or what is wrong
+static const char *randn_framed_args(const uint64_t *seeds, const int32_t *rows, int B, int C, int th, int tw, const float *out, bool *quad) {
+    if (!seeds || !rows || !out) return "null argument";
+    if (B < 1 || B > 65535) return "batch outside [1, 65535]";
+    if (C < 1 || th < 1 || tw < 1) return "C, th, tw must be >= 1";
+    if (const char *bad = noise_rows_check(rows, B, quad)) return bad;
+    for (int b = 0; b < B; ++b) {
+        const int32_t *r = rows + 4 * b;
+        if (r[2] > r[0] - th || r[3] > r[1] - tw) return "a window outside its frame";
+        if ((long long)C * r[0] * r[1] > (1ll << 34)) return "C * frame_h * frame_w beyond 2^34";
+    }
+    return nullptr;
+}
+
+int cdc_randn_framed(cdc_handle *h, const uint64_t *seeds, const int32_t *rows, int B, int C, int th, int tw, uint32_t draw, float scale,
+                     float *out, int mem, void *stream) {
+    if (!h) return CDC_ERR_INVALID;
+    return no_throw(h, [&] {
+        return with_range_guard(h, [&]() -> int {
+            int rc = ensure_device(h);
+            if (rc) return rc;
+            bool quad;
+            if (const char *bad = randn_framed_args(seeds, rows, B, C, th, tw, out, &quad)) return fail(h, CDC_ERR_INVALID, "randn_framed: %s", bad);
+            if (mem != CDC_MEM_HOST && mem != CDC_MEM_DEVICE) return fail(h, CDC_ERR_INVALID, "randn_framed: mem_kind %d", mem);
+            hipStream_t st = pick_stream(h, stream, mem);
+            if ((rc = h->seeds.stage(h, seeds, (size_t)B, st))) return rc;
+            if ((rc = h->frames.stage(h, reinterpret_cast<const NoiseFrame *>(rows), (size_t)B, st))) return rc;
+            Staging s(h, mem, st);
+            float *dd = s.out(out, (size_t)B * C * th * tw * sizeof(float));
+            if (s.ok()) s.e = randn_framed_launch(h->seeds.dev.p, h->frames.dev.p, quad, B, C, th, tw, draw, scale, dd, st);
+            return s.finish("randn_framed");
+        });
+    });
+}
+
+int cdc_randn_framed_host(const uint64_t *seeds, const int32_t *rows, int B, int C, int th, int tw, uint32_t draw, float scale, float *out) {
+    bool quad;
+    if (randn_framed_args(seeds, rows, B, C, th, tw, out, &quad)) return CDC_ERR_INVALID;
+    for (int b = 0; b < B; ++b) {
+        const int32_t *r = rows + 4 * b;
+        float *o = out + (size_t)b * C * th * tw;
+        for (int c = 0; c < C; ++c)
+            for (int y = 0; y < th; ++y) {
+                long long have = -1;
+                float z[4];
+                for (int x = 0; x < tw; ++x) {
+                    const long long e = ((long long)c * r[0] + r[2] + y) * r[1] + r[3] + x;
+                    if ((e >> 2) != have) { have = e >> 2; cdcrng::normal4(seeds[b], (uint32_t)have, draw, z); }
+                    o[((size_t)c * th + y) * tw + x] = scale * z[e & 3];
+                }
+            }
+    }
+    return CDC_OK;
+}
+
+int cdc_tile_gather(cdc_handle *h, const float *src, float *dst, const int32_t *origins, int B, int C, int Hs, int Ws, int T, int th, int tw,
+                    int mem, void *stream) {
+    if (!h) return CDC_ERR_INVALID;
+    return no_throw(h, [&] {
+        return with_range_guard(h, [&]() -> int {
+            int rc = ensure_device(h);
+            if (rc) return rc;
+            if (!src || !dst || !origins) return fail(h, CDC_ERR_INVALID, "tile_gather: null pointer");
+            if (B < 1 || C < 1 || T < 1 || th < 1 || tw < 1 || th > Hs || tw > Ws)
+                return fail(h, CDC_ERR_INVALID, "tile_gather: B=%d C=%d T=%d, %d x %d tiles of a %d x %d source", B, C, T, th, tw, Hs, Ws);
+            if ((double)B * C * Hs * Ws > (double)(1ll << 40) || (double)B * T * C * th * tw > (double)(1ll << 40))
+                return fail(h, CDC_ERR_INVALID, "tile_gather: %d x %d x %d x %d source, %d tiles of %d x %d: beyond 2^40 elements", B, C, Hs, Ws, T, th, tw);
+            if (mem != CDC_MEM_HOST && mem != CDC_MEM_DEVICE) return fail(h, CDC_ERR_INVALID, "tile_gather: mem_kind %d", mem);
+            bool vec = (tw & 3) == 0 && (Ws & 3) == 0;
+            for (int t = 0; t < T; ++t) {
+                const int y = origins[2 * t], x = origins[2 * t + 1];
+                if (y < 0 || x < 0 || y > Hs - th || x > Ws - tw)
+                    return fail(h, CDC_ERR_INVALID, "tile_gather: tile %d at (%d, %d) reaches outside the %d x %d source", t, y, x, Hs, Ws);
+                vec = vec && (x & 3) == 0;
+            }
+            hipStream_t st = pick_stream(h, stream, mem);
+            if ((rc = h->tile_meta.stage(h, origins, (size_t)2 * T, st))) return rc;
+            Staging s(h, mem, st);
+            const float *ds = s.in(src, (size_t)B * C * Hs * Ws * sizeof(float));
+            float *dd = s.out(dst, (size_t)B * T * C * th * tw * sizeof(float));
+            vec = vec && (((uintptr_t)ds | (uintptr_t)dd) & 15) == 0;
+            if (s.ok()) s.e = tile_gather_launch({ds, dd, h->tile_meta.dev.p, C, Hs, Ws, T, th, tw, vec}, B, st);
+            return s.finish("tile_gather");
+        });
+    });
+}
+
+// One axis of a blend: n tiles of `size` at origins o[] (strictly ascending, inside [0, L]), the window [w0, w0 + wn): the cover table
+// (first covering tile, count) per window coordinate -> null, or what is wrong.  [*t0, *t1): the tiles that cover some coordinate.
+static const char *blend_axis(const int32_t *o, int n, int size, int L, int ov, int w0, int wn, std::vector<int> *cov, int *t0, int *t1) {
+    if (n < 1 || size < 1 || size > L) return "no tiles, or tiles larger than the frame";
+    if (n > 1 && ov < 1) return "overlap must be >= 1 where an axis has more than one tile";
+    for (int k = 0; k < n; ++k)
+        if (o[k] < 0 || o[k] > L - size || (k > 0 && o[k] <= o[k - 1])) return "origins must ascend strictly and keep every tile inside the frame";
+    if (w0 < 0 || wn < 1 || w0 > L - wn) return "the window reaches outside the frame";
+    cov->resize((size_t)2 * wn);
+    *t0 = n; *t1 = 0;
+    int first = 0;
+    for (int i = 0; i < wn; ++i) {
+        const int p = w0 + i;
+        while (first < n && o[first] + size <= p) ++first;
+        int cnt = 0;
+        while (first + cnt < n && o[first + cnt] <= p) ++cnt;
+        if (cnt < 1) return "a coordinate of the window that no tile covers";
+        (*cov)[2 * i] = first; (*cov)[2 * i + 1] = cnt;
+        *t0 = std::min(*t0, first); *t1 = std::max(*t1, first + cnt);
+    }
+    return nullptr;
+}
+
+int cdc_tile_blend(cdc_handle *h, const float *tiles, void *out, const int32_t *ys, int ny, const int32_t *xs, int nx, const uint8_t *present,
+                   int B, int C, int Th, int Tw, int Hf, int Wf, int overlap_y, int overlap_x, int wy0, int wx0, int wh, int ww, int elem,
+                   int mem, void *stream) {
+    if (!h) return CDC_ERR_INVALID;
+    return no_throw(h, [&] {
+        return with_range_guard(h, [&]() -> int {
+            int rc = ensure_device(h);
+            if (rc) return rc;
+            if (!tiles || !out || !ys || !xs) return fail(h, CDC_ERR_INVALID, "tile_blend: null pointer");
+            if (B < 1 || C < 1 || (long long)B * C > 65535 || Hf < 1 || Wf < 1 || ny < 1 || nx < 1 || (long long)ny * nx > (1 << 24))
+                return fail(h, CDC_ERR_INVALID, "tile_blend: B=%d C=%d (B * C <= 65535), %d x %d tiles of a %d x %d frame", B, C, ny, nx, Hf, Wf);
+            if (elem != CDC_ELEM_F32 && elem != CDC_ELEM_U8) return fail(h, CDC_ERR_INVALID, "tile_blend: element kind %d", elem);
+            if (mem != CDC_MEM_HOST && mem != CDC_MEM_DEVICE) return fail(h, CDC_ERR_INVALID, "tile_blend: mem_kind %d", mem);
+            std::vector<int> ycov, xcov;
+            int ty0, ty1, tx0, tx1;
+            if (const char *bad = blend_axis(ys, ny, Th, Hf, overlap_y, wy0, wh, &ycov, &ty0, &ty1)) return fail(h, CDC_ERR_INVALID, "tile_blend: rows: %s", bad);
+            if (const char *bad = blend_axis(xs, nx, Tw, Wf, overlap_x, wx0, ww, &xcov, &tx0, &tx1)) return fail(h, CDC_ERR_INVALID, "tile_blend: columns: %s", bad);
+            // the present tiles are stored one after the other in ascending t; a tile covers a pixel of the window exactly when its row
+            // of tiles covers one of the window's rows and its column one of the window's columns
+            const int T = ny * nx;
+            std::vector<int> meta((size_t)ny + nx + T);
+            std::copy(ys, ys + ny, meta.begin());
+            std::copy(xs, xs + nx, meta.begin() + ny);
+            int Tp = 0;
+            bool vec = (Tw & 3) == 0 && (ww & 3) == 0 && (wx0 & 3) == 0;
+            for (int t = 0; t < T; ++t) meta[(size_t)ny + nx + t] = (!present || present[t]) ? Tp++ : -1;
+            for (int tx = 0; tx < nx; ++tx) vec = vec && (xs[tx] & 3) == 0;
+            for (int ty = ty0; ty < ty1; ++ty)
+                for (int tx = tx0; tx < tx1; ++tx)
+                    if (meta[(size_t)ny + nx + ty * nx + tx] < 0)
+                        return fail(h, CDC_ERR_INVALID, "tile_blend: tile %d (row %d, column %d) covers the window and is absent", ty * nx + tx, ty, tx);
+            if (Tp < 1 || (double)B * Tp * C * Th * Tw > (double)(1ll << 40)) return fail(h, CDC_ERR_INVALID, "tile_blend: %d present tiles", Tp);
+            meta.insert(meta.end(), ycov.begin(), ycov.end());
+            meta.insert(meta.end(), xcov.begin(), xcov.end());
+            hipStream_t st = pick_stream(h, stream, mem);
+            if ((rc = h->tile_meta.stage(h, meta.data(), meta.size(), st))) return rc;
+            const int u8 = elem == CDC_ELEM_U8;
+            Staging s(h, mem, st);
+            const float *dt = s.in(tiles, (size_t)B * Tp * C * Th * Tw * sizeof(float));
+            void *dd = s.out((uint8_t *)out, (size_t)B * C * wh * ww * (u8 ? 1 : 4));
+            vec = vec && ((uintptr_t)dt & 15) == 0 && ((uintptr_t)dd & (u8 ? 3 : 15)) == 0;
+            const int *m = h->tile_meta.dev.p;
+            if (s.ok())
+                s.e = tile_blend_launch({dt, dd, u8, C, Th, Tw, Tp, nx, m, m + ny, m + ny + nx, m + ny + nx + T, m + ny + nx + T + 2 * wh, Hf, Wf,
+                                         overlap_y, overlap_x, wy0, wx0, wh, ww, vec}, B, st);
+            return s.finish("tile_blend");
+        });
+    });
 }
 
 int cdc_prof_enable(cdc_handle *h, int on) {

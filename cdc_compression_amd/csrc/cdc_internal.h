@@ -264,13 +264,19 @@ struct SamplerArgs {
 };
 // DDIM: the noise of the step is none (noise and seeds null: eta = 0), a tensor (`noise`: cdc_ddim_step),
 // or generated in the kernel (`seeds` non-null, rng.h): image b draws z(seeds[b], draw = step index + 1, element index inside its own
-// per_image elements); `noise` is then neither read nor written.
+// per_image elements); `noise` is then neither read nor written.  `frames` non-null (with seeds; cdc_set_noise_frames): row b is the
+// window (y0, x0) of a frame_h x frame_w frame and draws what the frame's own tensor draws there: element (c, y, x) of the row is
+// element ((c frame_h + y0 + y) frame_w + x0 + x) of the generator.  frames_quad: frame_w, x0 of every row and the row's width are
+// multiples of 4, so four pixels are one quad (the four-pixel traversal); else the element traversal.
+struct NoiseFrame { int frame_h, frame_w, y0, x0; };
 struct DdimArgs {
     SamplerArgs s;
     const float *noise = nullptr;
     float eta = 0.f;
     const unsigned long long *seeds = nullptr;
     long long per_image = 0;
+    const NoiseFrame *frames = nullptr;
+    bool frames_quad = false;
 };
 hipError_t ddim_launch(const DdimArgs &a, hipStream_t st);
 // Second-order multistep update in data-prediction form (DPM-Solver++ 2M; include/cdc_hip.h states it):
@@ -295,6 +301,21 @@ hipError_t trace_tap_launch(const TraceArgs &a, hipStream_t st);
 // out[b][e] = scale * z(seeds[b], draw, e) for e < per_image (rng.h; seeds on the device); 16-byte stores when the layout allows
 hipError_t randn_fill_launch(const unsigned long long *seeds, int B, long long per_image, unsigned draw, float scale, float *out,
                              hipStream_t st);
+// out[b][c][y][x] = scale * z(seeds[b], draw, ((c frame_h + y0 + y) frame_w + x0 + x)) of frames[b] (device arrays), out [B][C][th][tw];
+// quad: frames_quad of DdimArgs (one generator call and one 16-byte store per four pixels where `out` allows it)
+hipError_t randn_framed_launch(const unsigned long long *seeds, const NoiseFrame *frames, bool quad, int B, int C, int th, int tw,
+                               unsigned draw, float scale, float *out, hipStream_t st);
+// tile_kernels.hip (tiled decode: cdc_tile_gather / cdc_tile_blend; include/cdc_hip.h states both)
+// dst[(b T + t)][c][y][x] = src[b][c][oy[t] + y][ox[t] + x]; origins: device [T][2] (y, x); vec: tw, Ws and every x are multiples of 4
+struct TileGatherArgs { const float *src; float *dst; const int *origins; int C, Hs, Ws, T, th, tw; bool vec; };
+hipError_t tile_gather_launch(const TileGatherArgs &a, int B, hipStream_t st);
+// The feathered blend of the ny x nx tiles of each image into the window (wy0, wx0, wh, ww) of its frame [C][Hf][Wf].  Device tables:
+// ys [ny], xs [nx] the tile origins per axis; slot [ny nx] the index of tile t among the Tp present ones (-1: absent); ycov [wh][2],
+// xcov [ww][2] (first covering tile index of the axis, count) per window coordinate.  tiles [B][Tp][C][Th][Tw]; out [B][C][wh][ww]
+// float32 or uint8 (frame_pixel.h).  vec: Tw, ww, wx0 and every x origin are multiples of 4 and both pointers aligned.
+struct TileBlendArgs { const float *tiles; void *out; int u8, C, Th, Tw, Tp, nx; const int *ys, *xs, *slot, *ycov, *xcov;
+                       int Hf, Wf, ov_y, ov_x, wy0, wx0, wh, ww; bool vec; };
+hipError_t tile_blend_launch(const TileBlendArgs &a, int B, hipStream_t st);
 // dst[b] = sum of `parts` planes of src[b] (plane p at + p * part_stride); step != null: the source row is selected by a device step index
 struct CopyArgs { const float *src; long long src_bs; float *dst; long long dst_bs, n; int parts = 1; long long part_stride = 0;
                   const int *step = nullptr; long long step_stride = 0; };

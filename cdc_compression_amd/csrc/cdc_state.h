@@ -315,6 +315,13 @@ struct cdc_handle {
     GrowBuf<float> d_hist;
     // seeded stochastic decode (cdc_decode_seeded / cdc_randn): the per-image seeds of the running call on the device
     StagedBuf<unsigned long long> seeds;
+    // frame-indexed draws (cdc_set_noise_frames): one row per batch row of the next seeded calls, empty: off; quad: every row allows the
+    // four-pixel traversal in a row width that is a multiple of 4.  frames: the rows of the running call on the device.
+    std::vector<cdc::NoiseFrame> noise_frames;
+    bool noise_frames_quad = false;
+    StagedBuf<cdc::NoiseFrame> frames;
+    // cdc_tile_gather / cdc_tile_blend: origins, slots and cover tables of the running call on the device
+    StagedBuf<int> tile_meta;
     int time_steps_B = 0;
     // K samples per image (cdc_decode_samples / cdc_sample_select): the B host images of one context level on their way to the repeat
     // kernel, and the picks of the running call.

@@ -81,8 +81,12 @@ __device__ __forceinline__ float predict_x0(const StepConsts &k, float fx, float
 // the four elements from idx on (pixels pix .. pix + 3 of plane img_co), given their model outputs and x. --------------------------
 // DDIM (denoising_diffusion.py ddim(), both trees).  The noise of the step: none (eta = 0), a tensor (`noise`), or -- SEEDED, an instance
 // of its own so that the others carry no generator code -- made here: image b draws z(seeds[b], step index + 1, element inside the image).
-template <bool SEEDED>
+// FRAMED, a third instance: the row is a window of a larger frame (NoiseFrame) and draws the frame's elements, so that two windows
+// that overlap see the same noise where they do; the element index is formed in 64 bits (C frame_h frame_w <= 2^34).
+enum { NOISE_TENSOR = 0, NOISE_SEEDED = 1, NOISE_FRAMED = 2 };
+template <int NOISE>
 struct DdimRule {
+    static constexpr bool SEEDED = NOISE == NOISE_SEEDED, FRAMED = NOISE == NOISE_FRAMED;
     using Args = DdimArgs;
     const DdimArgs &a;
     const StepConsts &k;
@@ -113,6 +117,15 @@ struct DdimRule {
             cdcrng::normal4(a.seeds[b], (uint32_t)(e >> 2), (uint32_t)k.si + 1u, z);
             const int lane = (int)(e & 3);
             a.s.x_next[idx] = next(fx, x, lane == 0 ? z[0] : lane == 1 ? z[1] : lane == 2 ? z[2] : z[3], clip, true);
+        } else if constexpr (FRAMED) {
+            const long long b = idx / a.per_image, r = idx - b * a.per_image, plane = (long long)a.s.pH * a.s.pW;
+            const int c = (int)(r / plane), pix = (int)(r - c * plane), y = pix / a.s.pW, xx = pix - y * a.s.pW;
+            const NoiseFrame f = a.frames[b];
+            const long long e = ((long long)c * f.frame_h + f.y0 + y) * f.frame_w + f.x0 + xx;
+            float z[4];
+            cdcrng::normal4(a.seeds[b], (uint32_t)(e >> 2), (uint32_t)k.si + 1u, z);
+            const int lane = (int)(e & 3);
+            a.s.x_next[idx] = next(fx, x, lane == 0 ? z[0] : lane == 1 ? z[1] : lane == 2 ? z[2] : z[3], clip, true);
         } else {
             a.s.x_next[idx] = next(fx, x, a.noise ? a.noise[idx] : 0.f, clip, a.noise != nullptr);
         }
@@ -124,13 +137,19 @@ struct DdimRule {
             const int b = img_co / a.s.pC;
             const long long e = (long long)(img_co - b * a.s.pC) * plane + pix;
             cdcrng::normal4(a.seeds[b], (uint32_t)(e >> 2), (uint32_t)k.si + 1u, nz);
+        } else if constexpr (FRAMED) {
+            // frames_quad: frame_w, x0 and pW are multiples of 4, so these four pixels are one quad of the frame's tensor
+            const int b = img_co / a.s.pC, y = pix / a.s.pW, xx = pix - y * a.s.pW;
+            const NoiseFrame f = a.frames[b];
+            const long long e = ((long long)(img_co - b * a.s.pC) * f.frame_h + f.y0 + y) * f.frame_w + f.x0 + xx;
+            cdcrng::normal4(a.seeds[b], (uint32_t)(e >> 2), (uint32_t)k.si + 1u, nz);
         } else if (a.noise) {
             const float4 n4 = *reinterpret_cast<const float4 *>(a.noise + idx);
             nz[0] = n4.x; nz[1] = n4.y; nz[2] = n4.z; nz[3] = n4.w;
         }
         float out[4];
 #pragma unroll
-        for (int c = 0; c < 4; ++c) out[c] = next(fx[c], x[c], nz[c], clip, SEEDED || a.noise != nullptr);
+        for (int c = 0; c < 4; ++c) out[c] = next(fx[c], x[c], nz[c], clip, SEEDED || FRAMED || a.noise != nullptr);
         *reinterpret_cast<float4 *>(a.s.x_next + idx) = make_float4(out[0], out[1], out[2], out[3]);
     }
 };
@@ -207,13 +226,14 @@ __global__ void __launch_bounds__(256) sampler_rows4_kernel(const typename Rule:
     if (bad && s.fault) *s.fault = 1;
 }
 
-// The four-pixel form where the frame and every pointer the instance dereferences allow it (`rule_ptrs`: the rule's own, or-ed).
+// The four-pixel form where the frame and every pointer the instance dereferences allow it (`rule_ptrs`: the rule's own, or-ed) and
+// the rule itself does (`quads`: the framed draws of four pixels are one quad).
 template <class Rule>
-static hipError_t sampler_launch(const typename Rule::Args &a, uintptr_t rule_ptrs, hipStream_t st) {
+static hipError_t sampler_launch(const typename Rule::Args &a, uintptr_t rule_ptrs, hipStream_t st, bool quads = true) {
     const SamplerArgs &s = a.s;
     const long long plane = (long long)s.pH * s.pW;
     if (s.n <= 0) return hipErrorInvalidValue;
-    if (plane > 0 && (s.pW & 3) == 0 && plane < (1ll << 30) && s.n % plane == 0 && s.n / plane <= 65535 &&
+    if (quads && plane > 0 && (s.pW & 3) == 0 && plane < (1ll << 30) && s.n % plane == 0 && s.n / plane <= 65535 &&
         (((uintptr_t)s.P | (uintptr_t)s.fx | (uintptr_t)s.x | (uintptr_t)s.x_next | rule_ptrs) & 15) == 0) {
         const dim3 g((unsigned)ceil_div((int)(plane / 4), 256), (unsigned)(s.n / plane));
         hipLaunchKernelGGL(sampler_rows4_kernel<Rule>, g, dim3(256), 0, st, a);
@@ -225,7 +245,8 @@ static hipError_t sampler_launch(const typename Rule::Args &a, uintptr_t rule_pt
 }
 
 hipError_t ddim_launch(const DdimArgs &a, hipStream_t st) {
-    return a.seeds ? sampler_launch<DdimRule<true>>(a, 0, st) : sampler_launch<DdimRule<false>>(a, (uintptr_t)a.noise, st);
+    if (a.seeds && a.frames) return sampler_launch<DdimRule<NOISE_FRAMED>>(a, 0, st, a.frames_quad);
+    return a.seeds ? sampler_launch<DdimRule<NOISE_SEEDED>>(a, 0, st) : sampler_launch<DdimRule<NOISE_TENSOR>>(a, (uintptr_t)a.noise, st);
 }
 hipError_t solver_launch(const SolverArgs &a, hipStream_t st) { return sampler_launch<SolverRule>(a, (uintptr_t)a.hist, st); }
 
@@ -347,6 +368,53 @@ hipError_t randn_fill_launch(const unsigned long long *seeds, int B, long long p
         hipLaunchKernelGGL(randn_fill_kernel<true>, g, dim3(256), 0, st, seeds, per_image, draw, scale, out);
     else
         hipLaunchKernelGGL(randn_fill_kernel<false>, g, dim3(256), 0, st, seeds, per_image, draw, scale, out);
+    return hipGetLastError();
+}
+
+// The framed fill (cdc_randn_framed; the start image of a framed decode): row b is the window (y0, x0) of frames[b], [C][th][tw].
+// QUAD: one quad of the frame per thread (frame_w, x0, tw multiples of 4), a 16-byte store where OUT_VEC says `out` is aligned; else one
+// element per thread, which evaluates the quad of its element and picks its lane, as DdimRule<NOISE_FRAMED>::one does.
+template <bool QUAD, bool OUT_VEC>
+__global__ void __launch_bounds__(256) randn_framed_kernel(const unsigned long long *seeds, const NoiseFrame *frames, int C, int th, int tw,
+                                                           unsigned draw, float scale, float *out) {
+    constexpr int V = QUAD ? 4 : 1;
+    const int upr = tw / V;                                                     // threads per row
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x, units = (long long)C * th * upr;
+    if (i >= units) return;
+    const int b = blockIdx.y;
+    const long long row = i / upr;                                              // = c * th + y
+    const int xx = (int)(i - row * upr) * V, c = (int)(row / th), y = (int)(row - (long long)c * th);
+    const NoiseFrame f = frames[b];
+    const long long e = ((long long)c * f.frame_h + f.y0 + y) * f.frame_w + f.x0 + xx;
+    float z[4];
+    cdcrng::normal4(seeds[b], (uint32_t)(e >> 2), draw, z);
+    float *o = out + ((size_t)b * C * th + row) * tw + xx;
+    if constexpr (QUAD) {
+        if constexpr (OUT_VEC) {
+            *reinterpret_cast<float4 *>(o) = make_float4(scale * z[0], scale * z[1], scale * z[2], scale * z[3]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o[k] = scale * z[k];
+        }
+    } else {
+        const int lane = (int)(e & 3);
+        *o = scale * (lane == 0 ? z[0] : lane == 1 ? z[1] : lane == 2 ? z[2] : z[3]);
+    }
+}
+
+hipError_t randn_framed_launch(const unsigned long long *seeds, const NoiseFrame *frames, bool quad, int B, int C, int th, int tw,
+                               unsigned draw, float scale, float *out, hipStream_t st) {
+    if (B < 1 || B > 65535 || C < 1 || th < 1 || tw < 1) return hipErrorInvalidValue;
+    quad = quad && (tw & 3) == 0;
+    const long long units = (long long)C * th * (quad ? tw / 4 : tw);
+    if (units > (long long)INT32_MAX * 256) return hipErrorInvalidValue;
+    const dim3 g((unsigned)((units + 255) / 256), (unsigned)B);
+    if (quad && ((uintptr_t)out & 15) == 0)
+        hipLaunchKernelGGL((randn_framed_kernel<true, true>), g, dim3(256), 0, st, seeds, frames, C, th, tw, draw, scale, out);
+    else if (quad)
+        hipLaunchKernelGGL((randn_framed_kernel<true, false>), g, dim3(256), 0, st, seeds, frames, C, th, tw, draw, scale, out);
+    else
+        hipLaunchKernelGGL((randn_framed_kernel<false, false>), g, dim3(256), 0, st, seeds, frames, C, th, tw, draw, scale, out);
     return hipGetLastError();
 }
 

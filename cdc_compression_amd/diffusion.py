@@ -35,12 +35,20 @@ cleared again, also on error.
 Images of any size (cdc_compression_amd.frame states the rule): `compress`, `compress_to_bytes` and `decompress` pad on the device to
 the model's multiple, run on the padded frame and return the top-left `[B, 3, H, W]` window, bpp over `H * W`.  `p_sample_loop`
 mirrors the reference's method and keeps requiring frame sizes (`padded_size(H, W)` tells them).
+
+Tiled decode (no reference counterpart; cdc_compression_amd.tiles states the plan, the noise and the weights): `decompress(..., tile=,
+tile_overlap=, tile_chunk=, region=)` keeps the full-frame entropy and hyper decode and runs what follows the latent on overlapping
+tiles as batch rows -- `context_fn.decode` and the sampler on `tile_chunk` rows per call, all tiles of an image on the image's seed with
+frame-indexed draws -- and feather-blends the decoded tiles, crop and `as_uint8` fused into the blend.  `region=(y0, x0, h, w)` decodes
+only the tiles that intersect it and returns (window, info).  One tile that covers the frame is the plain path.  `compress`, `evaluate`
+and `compress_best_of` pass the arguments through.  `tile=None` runs the code it ran.  What tiling does to decoded images of trained
+weights is not measured.
 """
 import ctypes
 
 import numpy as np
 
-from . import _lib, frame, lpips, samples as _samples, trajectory as _trajectory
+from . import _lib, frame, lpips, samples as _samples, tiles as _tiles, trajectory as _trajectory
 from .parallel import expand_seeds, sample_seeds
 from .schedule import SAMPLERS, SampleSchedule
 from .unet import _Arg, _current_stream, _is_torch, _result_like
@@ -226,6 +234,9 @@ class _GaussianDiffusionBase:
         import inspect
         bound = dict(inspect.signature(self.compress).bind(images, *args, **kwargs).arguments)
         bound.pop("bpp_return_mean", None)                    # bpp comes per image
+        tile_kw = {k: bound.pop(k, None) for k in ("tile", "tile_overlap", "tile_chunk", "region")}
+        if any(v is not None for v in tile_kw.values()):
+            return self._evaluate_tiled(images, bound, tile_kw, as_saved, maps)
         rate_kw = {k: bound.pop(k, None) for k in ("rdo", "target_bpp", "max_bytes", "price_map", "price_cells")}
         mu, cells = self._rdo_of(images, bound.get("bitrate_scale"), **rate_kw)
         if mu is not None:
@@ -246,6 +257,19 @@ class _GaussianDiffusionBase:
             out["lpips"] = metrics.lpips(self.loss_fn_vgg, rec, images, size=(H, W), as_saved=as_saved)
         if traj is not None:
             out["trajectory"] = self._score_trajectory(traj, images, as_saved)
+        return out
+
+    def _evaluate_tiled(self, images, bound, tile_kw, as_saved, maps):
+        """evaluate(tile=...): compress()'s tiled path once, the figures on its H x W window (the tiles never form the padded frame)."""
+        from . import metrics
+        _tiles.check_args(tile_kw["tile"], tile_kw["tile_overlap"], tile_kw["tile_chunk"], tile_kw["region"], None, bound.get("trajectory"), maps)
+        if tile_kw["region"] is not None:
+            raise ValueError("evaluate() measures the whole image: region belongs to compress() / decompress()")
+        rec, bpp = self.compress(**bound, bpp_return_mean=False, **tile_kw)
+        ps, ms = metrics.distortion(self.denoise_fn, rec, images, as_saved=as_saved)
+        out = {"reconstruction": rec, "bpp": bpp, "psnr": ps, "ms_ssim": ms}
+        if self.loss_fn_vgg is not None:
+            out["lpips"] = metrics.lpips(self.loss_fn_vgg, rec, images, as_saved=as_saved)
         return out
 
     def _score_trajectory(self, traj, images, as_saved):
@@ -421,7 +445,7 @@ class _GaussianDiffusionBase:
 
     def decompress(self, context, shape=None, sample_steps=None, init=None, eta=0, clip_denoised=None, bitrate_scale=None,
                    as_uint8=False, seed=None, gamma=None, sampler="ddim", spacing="index", samples=None, reduce=None, sample_chunk=None,
-                   trajectory=None, trajectory_of="x0", trajectory_dtype="float32"):
+                   trajectory=None, trajectory_of="x0", trajectory_dtype="float32", tile=None, tile_overlap=None, tile_chunk=None, region=None):
         """Decode half of compress(): context pyramid (= context_fn(...)["output"]) -> image.  `context`
         may also be the transmitted q_latent tensor [B, C, H/16, W/16]: it then goes through
         `context_fn.decode` first (compress_modules.py:68-74; cdc_compression_amd.compressor on the GPU) -- with
@@ -440,7 +464,21 @@ class _GaussianDiffusionBase:
         cropped once.  sample_chunk: samples per image per library call (default: the largest divisor of K with B * Kc <= 32).
         trajectory / trajectory_of / trajectory_dtype (cdc_compression_amd.trajectory): x0 and / or x_t of chosen steps, recorded in the
         device loop -> (reconstruction, Trajectory), the slots [S, B, 3, H, W] cropped to the window as the reconstruction is; excludes
-        samples=, and eta != 0 needs a seed."""
+        samples=, and eta != 0 needs a seed.
+        tile / tile_overlap / tile_chunk / region (cdc_compression_amd.tiles): the tiled decode of a q_latent or of streams.  tile,
+        tile_overlap: multiples of the frame multiple `padded_size(1, 1)[0]`, ints or (h, w) pairs, 0 < overlap <= tile / 2 (default: the
+        multiple); tile_chunk: rows (tiles of all images) per sampler call (default: the fewest calls of at most 32 rows);
+        region=(y0, x0, h, w) in image pixels: decodes the tiles that intersect it -> (that window, {"tiles", "tiles_decoded", "region"}).
+        Excludes samples=, trajectory= and a context pyramid; eta != 0 needs a seed."""
+        tile_hw, overlap_hw = _tiles.check_args(tile, tile_overlap, tile_chunk, region, samples, trajectory)
+        if tile_hw is not None:
+            if eta != 0 and seed is None:
+                raise ValueError("tile with eta != 0 needs a seed: the tiles of an image draw the noise of the frame positions they cover")
+            if isinstance(context, (list, tuple)) and context and not isinstance(context[0], (bytes, bytearray)):
+                raise ValueError("tile needs the latent (a q_latent tensor or streams): a context pyramid of the whole frame is not cut into tiles")
+            tile_hw, overlap_hw = _tiles.check_multiples(tile_hw, overlap_hw, self.padded_size(1, 1)[0])
+            if region is not None and shape is not None:
+                _tiles.check_region(region, int(shape[2]), int(shape[3]))
         self._seed_args(seed, gamma, init)
         self._sampler_args(sampler, eta)
         spec = self._trace_spec(trajectory, trajectory_of, trajectory_dtype, self._steps(sample_steps, spacing), eta, seed, samples)
@@ -459,6 +497,11 @@ class _GaussianDiffusionBase:
         if not isinstance(context, (list, tuple)):
             if self.context_fn is None or not hasattr(self.context_fn, "decode"):
                 raise RuntimeError("decompress(q_latent, ...) needs a context_fn with decode()")
+            if tile_hw is not None:
+                res = self._decompress_tiled(context, bitrate_scale, recorded, shape, tile_hw, overlap_hw, tile_chunk, region, sample_steps, init,
+                                             eta, clip_denoised, as_uint8, seed, gamma, sampler, spacing)
+                if res is not None:
+                    return res
             context = self.context_fn.decode(context) if bitrate_scale is None else self.context_fn.decode(context, bitrate_scale)
         if K is None:
             self._seed_args(seed, gamma, init, int(context[0].shape[0]))
@@ -483,6 +526,81 @@ class _GaussianDiffusionBase:
         if (Hp, Wp) != (H, W) or as_uint8:
             rec = frame.crop(h, rec, H, W, dev, as_uint8=as_uint8)
         return rec if traj is None else (rec, traj)
+
+    # ---- tiled decode (cdc_compression_amd.tiles) --------------------------------------------------------------------------
+    def _decompress_tiled(self, q_latent, bitrate_scale, recorded, shape, tile, overlap, tile_chunk, region, sample_steps, init, eta,
+                          clip_denoised, as_uint8, seed, gamma, sampler, spacing):
+        """decompress(q_latent, tile=...): -> the result, or None when one tile covers the frame and no region is asked for (the caller
+        goes on with the plain path: the same launches, the same bits)."""
+        cf, un = self.context_fn, self.denoise_fn
+        h, dev = un._handle(), un.device_index
+        M = self.padded_size(1, 1)[0]
+        B, _, hl, wl = (int(d) for d in q_latent.shape)
+        cell = 1 << len(cf.rev_mults)                               # image pixels per latent position and side (compressor.decode)
+        Hp, Wp = hl * cell, wl * cell
+        if M % cell:
+            raise _lib.CdcError(f"the frame multiple {M} is no multiple of the {cell} pixels of a latent position")
+        H, W = recorded if recorded is not None else ((Hp, Wp) if shape is None else (int(shape[2]), int(shape[3])))
+        if shape is not None and tuple(int(d) for d in shape) != (B, 3, H, W):
+            raise _lib.CdcError(f"shape {tuple(shape)} contradicts the context, which holds {B} image(s) of {H} x {W}")
+        if not (0 <= Hp - H < M and 0 <= Wp - W < M):
+            raise _lib.CdcError(f"a {H} x {W} image does not pad to the {Hp} x {Wp} frame of the context (multiple {M})")
+        window = None if region is None else _tiles.check_region(region, H, W)
+        plan = _tiles.Plan(Hp, Wp, tile, overlap)
+        if plan.T == 1:
+            if window is None:
+                return None
+            rec = self.decompress(q_latent, (B, 3, H, W), sample_steps, init, eta, clip_denoised, bitrate_scale, False, seed, gamma, sampler, spacing)
+            one = _tiles.Plan(H, W, (H, W), (1, 1))                 # the image as its own single tile: the blend is a copy of the window
+            return _tiles.blend(h, rec, one, B, dev, window=window, as_uint8=as_uint8), {"tiles": 1, "tiles_decoded": 1, "region": window}
+        seeds = self._seed_args(seed, gamma, init, B)
+        self.set_sample_schedule(self._steps(sample_steps, spacing), sampler=sampler, spacing=spacing)
+        if clip_denoised is None:
+            clip_denoised = True if self._param == "x" else getattr(self, "clip_noise", "none")
+        sel = plan.intersecting(window)
+        Ts, th, tw = len(sel), plan.th, plan.tw
+        origins = plan.origins(sel)
+        lat = _tiles.gather(cf._handle(), q_latent, [(y // cell, x // cell) for y, x in origins], th // cell, tw // cell, cf.device_index)
+        init_rows = None
+        if init is not None:
+            init_rows = _tiles.gather(h, frame.extend_init(h, init, B, H, W, Hp, Wp, dev), origins, th, tw, dev)
+        rates = None if bitrate_scale is None else np.broadcast_to(np.asarray(bitrate_scale, np.float32).reshape(-1), (B,))
+        rows = B * Ts
+        chunk = _tiles.default_chunk(rows) if tile_chunk is None else min(int(tile_chunk), rows)
+        decoded = None
+        for r0 in range(0, rows, chunk):
+            r1 = min(rows, r0 + chunk)
+            bs = [r // Ts for r in range(r0, r1)]
+            ctx = cf.decode(lat[r0:r1]) if rates is None else cf.decode(lat[r0:r1], np.ascontiguousarray(rates[bs]))
+            frames = None if seeds is None else [(Hp, Wp) + tuple(origins[r % Ts]) for r in range(r0, r1)]
+            with _tiles.noise_frames(h, frames):
+                part = self._loop((r1 - r0, 3, th, tw), ctx, clip_denoised, None if init_rows is None else init_rows[r0:r1], eta,
+                                  None if seeds is None else [seeds[b] for b in bs], gamma, sampler)
+            if r1 - r0 == rows:
+                decoded = part
+            else:
+                if decoded is None:
+                    decoded = frame._empty_like(part, (rows, 3, th, tw), False)[0]
+                decoded[r0:r1] = part
+        rec = _tiles.blend(h, decoded, plan, B, dev, window=(0, 0, H, W) if window is None else window,
+                           present=None if Ts == plan.T else sel, as_uint8=as_uint8)
+        return rec if window is None else (rec, {"tiles": plan.T, "tiles_decoded": Ts, "region": window})
+
+    def _compress_tiled(self, images, ctx_args, rate_kw, bpp_return_mean, tile_kw, **dec_kw):
+        """compress(tile=...) of both trees: the encoder on the whole frame (no full-frame context pyramid is made), then the tiled
+        decode of its q_latent -> (reconstruction, bpp), with a region (window, bpp, info)."""
+        cf = self.context_fn
+        if not hasattr(cf, "encode") or not hasattr(cf, "rev_mults"):
+            raise ValueError("tile needs a context model of this package (its q_latent is what is cut into tiles)")
+        _tiles.check_args(tile_kw["tile"], tile_kw["tile_overlap"], tile_kw["tile_chunk"], tile_kw["region"], None, dec_kw.pop("trajectory", None))
+        mu, cells = self._rdo_of(images, ctx_args[0] if ctx_args else None, **rate_kw)
+        B, _, H, W = frame.image_shape(images)
+        kw = {} if mu is None else ({"rdo": mu} if cells is None else {"rdo": mu, "price_cells": cells})
+        q_latent, _, state = cf.encode(images, *ctx_args, padded_hw=self.padded_size(H, W), **kw)
+        bpp = cf.bpp((B, 3, H, W), state)
+        rec = self.decompress(q_latent, (B, 3, H, W), bitrate_scale=ctx_args[0] if ctx_args else None, **dec_kw, **tile_kw)
+        bpp = bpp.mean() if bpp_return_mean else bpp
+        return (rec[0], bpp, rec[1]) if tile_kw["region"] is not None else (rec, bpp)
 
     # ---- K samples per image (cdc_compression_amd.samples) --------------------------------------------------------------
     def _sample_chunk(self, context, seeds, k0, Kc, clip_denoised, eta, gamma, sampler):
@@ -519,8 +637,9 @@ class _GaussianDiffusionBase:
         return window(mean), window(m2)
 
     def _best_of(self, images, samples, metric, seed, gamma, eta, sample_steps, sampler, spacing, sample_chunk, as_saved, clip_denoised,
-                 *ctx_args, rdo=None, price_cells=None):
-        """compress_best_of of both trees."""
+                 *ctx_args, rdo=None, price_cells=None, tile_kw=None):
+        """compress_best_of of both trees.  tile_kw (tile / tile_overlap / tile_chunk): every candidate is a tiled decode of the
+        encoder's q_latent, scored and kept on the H x W window, one candidate per pass."""
         from . import metrics
         K = _samples.check_args(samples, seed, gamma, eta, sample_chunk=sample_chunk, metric=metric)
         self._sampler_args(sampler, eta)
@@ -531,6 +650,33 @@ class _GaussianDiffusionBase:
             raise ValueError(f"MS-SSIM needs min(H, W) > 160, got {H} x {W}")
         higher = _samples.METRICS[metric]
         all_seeds = sample_seeds(seed, B, K)
+        if tile_kw is not None and any(v is not None for v in tile_kw.values()):
+            _tiles.check_args(tile_kw["tile"], tile_kw["tile_overlap"], tile_kw["tile_chunk"])
+            cf = self.context_fn
+            if not hasattr(cf, "encode") or not hasattr(cf, "rev_mults"):
+                raise ValueError("tile needs a context model of this package (its q_latent is what is cut into tiles)")
+            kw = {} if rdo is None else ({"rdo": rdo} if price_cells is None else {"rdo": rdo, "price_cells": price_cells})
+            q_latent, _, state = cf.encode(images, *ctx_args, padded_hw=self.padded_size(H, W), **kw)
+            scores = np.full((B, K), np.nan, np.float64)
+            best_k, best = [0] * B, None
+            for k in range(K):
+                rec = self.decompress(q_latent, (B, 3, H, W), sample_steps, None, eta, clip_denoised, ctx_args[0] if ctx_args else None, False,
+                                      [all_seeds[b][k] for b in range(B)], gamma, sampler, spacing, **tile_kw)
+                if metric == "lpips":
+                    row = metrics.lpips(self.loss_fn_vgg, rec, images, as_saved=as_saved)
+                else:
+                    row = getattr(metrics, metric)(self.denoise_fn, rec, images, as_saved=as_saved)
+                scores[:, k] = np.asarray(row, np.float64)
+                if best is None:
+                    best = rec
+                    continue
+                for b in range(B):
+                    if _samples.better(float(scores[b, k]), float(scores[b, best_k[b]]), higher):
+                        best_k[b] = k
+                        best[b] = rec[b]
+            return {"reconstruction": best, "bpp": cf.bpp((B, 3, H, W), state),
+                    "seed": np.asarray([all_seeds[b][best_k[b]] for b in range(B)], dtype=np.uint64), "sample": np.asarray(best_k, dtype=np.int64),
+                    "score": scores[np.arange(B), best_k], "scores": scores}
         context_dict, B, H, W, Hp, Wp = self._context_of(images, *ctx_args, rdo=rdo, price_cells=price_cells)
         context = context_dict["output"]
         self.set_sample_schedule(self._steps(sample_steps, spacing), sampler=sampler, spacing=spacing)
@@ -625,10 +771,17 @@ class GaussianDiffusionX(_GaussianDiffusionBase):
 
     def compress(self, images, sample_steps=None, bpp_return_mean=True, init=None, eta=0, seed=None, gamma=None, sampler="ddim",
                  spacing="index", trajectory=None, trajectory_of="x0", trajectory_dtype="float32", rdo=None, target_bpp=None,
-                 max_bytes=None, price_map=None, price_cells=None):
+                 max_bytes=None, price_map=None, price_cells=None, tile=None, tile_overlap=None, tile_chunk=None, region=None):
         """trajectory=: -> (reconstruction, bpp, Trajectory) (cdc_compression_amd.trajectory).  rdo / target_bpp / max_bytes: the
         context model's rate control (compressor.compress_to_bytes); bpp is that of the symbols it chose.  price_map / price_cells
-        (with one of them): its region-of-interest map, in pixels at the image's size or on the latent grid."""
+        (with one of them): its region-of-interest map, in pixels at the image's size or on the latent grid.
+        tile / tile_overlap / tile_chunk / region: the decode half runs tiled (decompress states them); with a region
+        -> (window, bpp, info)."""
+        if not (tile is None and tile_overlap is None and tile_chunk is None and region is None):
+            return self._compress_tiled(images, (), dict(rdo=rdo, target_bpp=target_bpp, max_bytes=max_bytes, price_map=price_map, price_cells=price_cells),
+                                        bpp_return_mean, dict(tile=tile, tile_overlap=tile_overlap, tile_chunk=tile_chunk, region=region),
+                                        sample_steps=sample_steps, init=init, eta=eta, seed=seed, gamma=gamma, sampler=sampler, spacing=spacing,
+                                        trajectory=trajectory)
         mu, cells = self._rdo_of(images, None, rdo, target_bpp, max_bytes, price_map, price_cells)
         rec, bpp, H, W, traj = self._frame_of(images, sample_steps, init, eta, seed, gamma, sampler, spacing, trajectory, trajectory_of,
                                               trajectory_dtype, rdo=mu, price_cells=cells)
@@ -638,15 +791,16 @@ class GaussianDiffusionX(_GaussianDiffusionBase):
 
     def compress_best_of(self, images, samples, metric="psnr", seed=None, gamma=None, eta=0, sample_steps=None, sampler="ddim",
                          spacing="index", sample_chunk=None, as_saved=True, rdo=None, target_bpp=None, max_bytes=None, price_map=None,
-                         price_cells=None):
+                         price_cells=None, tile=None, tile_overlap=None, tile_chunk=None):
         """The encoder's closed loop: the context model once, then `samples` seeded decodes per image (seeds
         parallel.sample_seeds(seed, B, samples)), each scored on the device against `images` on the frame's H x W window
         (metric "psnr" / "ms_ssim": higher is better; "lpips": lower, needs self.loss_fn_vgg; ties go to the lowest k, a NaN never
         beats a number) -> {"reconstruction": the winner's window, "bpp": [B], "seed": uint64 [B], ready for decompress(..., seed=),
-        "sample": int [B], "score": [B], "scores": [B, samples]}.  rdo / target_bpp / max_bytes / price_map / price_cells: as compress()."""
+        "sample": int [B], "score": [B], "scores": [B, samples]}.  rdo / target_bpp / max_bytes / price_map / price_cells: as compress().
+        tile / tile_overlap / tile_chunk: every candidate is a tiled decode (decompress states them)."""
         mu, cells = self._rdo_of(images, None, rdo, target_bpp, max_bytes, price_map, price_cells)
         return self._best_of(images, samples, metric, seed, gamma, eta, sample_steps, sampler, spacing, sample_chunk, as_saved, True, rdo=mu,
-                             price_cells=cells)
+                             price_cells=cells, tile_kw=dict(tile=tile, tile_overlap=tile_overlap, tile_chunk=tile_chunk))
 
 
 class GaussianDiffusionEps(_GaussianDiffusionBase):
@@ -688,9 +842,17 @@ class GaussianDiffusionEps(_GaussianDiffusionBase):
     def compress(self, images, sample_steps=None, bitrate_scale=None, sample_mode="ddpm",
                  bpp_return_mean=True, init=None, eta=0, seed=None, gamma=None, sampler="ddim", spacing="index",
                  trajectory=None, trajectory_of="x0", trajectory_dtype="float32", rdo=None, target_bpp=None, max_bytes=None,
-                 price_map=None, price_cells=None):
+                 price_map=None, price_cells=None, tile=None, tile_overlap=None, tile_chunk=None, region=None):
         """trajectory=: -> (reconstruction, bpp, Trajectory) (cdc_compression_amd.trajectory).  rdo / target_bpp / max_bytes /
-        price_map / price_cells: as GaussianDiffusionX.compress."""
+        price_map / price_cells / tile / tile_overlap / tile_chunk / region: as GaussianDiffusionX.compress."""
+        if not (tile is None and tile_overlap is None and tile_chunk is None and region is None):
+            if sample_mode != "ddim":
+                raise NotImplementedError('sample_mode "ddpm" raises AttributeError in the reference; only "ddim" is implemented')
+            return self._compress_tiled(images, (bitrate_scale,), dict(rdo=rdo, target_bpp=target_bpp, max_bytes=max_bytes, price_map=price_map,
+                                                                      price_cells=price_cells),
+                                        bpp_return_mean, dict(tile=tile, tile_overlap=tile_overlap, tile_chunk=tile_chunk, region=region),
+                                        sample_steps=sample_steps, init=init, eta=eta, seed=seed, gamma=gamma, sampler=sampler, spacing=spacing,
+                                        trajectory=trajectory)
         mu, cells = self._rdo_of(images, bitrate_scale, rdo, target_bpp, max_bytes, price_map, price_cells)
         rec, bpp, H, W, traj = self._frame_of(images, sample_steps, bitrate_scale, sample_mode, init, eta, seed, gamma, sampler, spacing,
                                               trajectory, trajectory_of, trajectory_dtype, rdo=mu, price_cells=cells)
@@ -699,8 +861,9 @@ class GaussianDiffusionEps(_GaussianDiffusionBase):
 
     def compress_best_of(self, images, samples, metric="psnr", seed=None, gamma=None, eta=0, sample_steps=None, sampler="ddim",
                          spacing="index", sample_chunk=None, as_saved=True, bitrate_scale=None, rdo=None, target_bpp=None, max_bytes=None,
-                         price_map=None, price_cells=None):
+                         price_map=None, price_cells=None, tile=None, tile_overlap=None, tile_chunk=None):
         """GaussianDiffusionX.compress_best_of with this tree's context argument (bitrate_scale of a variable-bitrate model)."""
         mu, cells = self._rdo_of(images, bitrate_scale, rdo, target_bpp, max_bytes, price_map, price_cells)
         return self._best_of(images, samples, metric, seed, gamma, eta, sample_steps, sampler, spacing, sample_chunk, as_saved,
-                             self.clip_noise, bitrate_scale, rdo=mu, price_cells=cells)
+                             self.clip_noise, bitrate_scale, rdo=mu, price_cells=cells,
+                             tile_kw=dict(tile=tile, tile_overlap=tile_overlap, tile_chunk=tile_chunk))

@@ -824,6 +824,54 @@ int cdc_op_linear_attention(cdc_handle *h, const float *x, const float *norm_g,
                             const float *norm_b, const float *w_qkv, const float *w_out,
                             const float *b_out, float *y, int B, int C, int H, int W);
 
+/* ---- tiled decode (no reference counterpart: the reference decodes the whole frame as one U-Net problem) ---------------------------
+ * The stream, the entropy decode and the hyper decode stay on the full frame.  What follows the dequantised latent may run on overlapping
+ * tiles as batch rows: the latent is cut into windows (cdc_tile_gather), each window goes through the context decoder and the sampler,
+ * and the decoded tiles are blended back into the frame (cdc_tile_blend).  Rows of image b are b * T + t, tiles numbered row-major,
+ * t = ty * nx + tx.  What tiling does to decoded images of trained weights is not measured: these entry points define the operation.
+ *
+ * FRAME-INDEXED DRAWS.  The generator of the seeded decode indexes its draws on the row's own tensor; two tiles that overlap would
+ * draw different noise for one pixel.  A framed row carries {frame_h, frame_w, y0, x0} (four int32) beside its seed and draws what the
+ * frame's tensor draws at the positions it covers: element (c, y, x) of the row [C][th][tw] is lane (e & 3) of quad (e >> 2),
+ *   e = (c * frame_h + y0 + y) * frame_w + x0 + x        (formed in 64 bits; C * frame_h * frame_w <= 2^34),
+ * generator, key, draw numbering, uniform and Box-Muller as stated for cdc_decode_seeded, counter words 2 and 3 still 0.  A row that is
+ * its whole frame (y0 = x0 = 0, th = frame_h, tw = frame_w) draws exactly the plain draws.  Where frame_w, x0 and tw are multiples of 4
+ * the kernels evaluate one quad per four pixels, otherwise the quad of each element; both give the same bits.
+ * cdc_set_noise_frames: rows [n][4] (host, copied) for the next seeded calls of n batch rows, kept on the handle until changed; n = 0
+ *   (rows may be NULL) clears them.  While set, cdc_decode_seeded, cdc_decode_solver (the start image gamma * z) and cdc_op_ddim_update
+ *   with seeds draw framed -- a third instantiation of the DDIM kernels beside the tensor and the seeded one -- and check at the call:
+ *   n == B, every window inside its frame, the element bound; cdc_decode_samples is refused.  The BF16X3 repetition of a range fault
+ *   regenerates framed draws as it regenerates plain ones.  With no frames set every entry point launches exactly what it launched
+ *   before.  Needs a U-Net handle.
+ * cdc_randn_framed: out [B][C][th][tw] = scale * z of the rows' frames, made on the device; any handle kind.  cdc_randn_framed_host: the
+ *   same header evaluated on the host (libm differences as for cdc_randn_host); no handle, no GPU.
+ *
+ * cdc_tile_gather: dst [B * T][C][th][tw] <- src [B][C][Hs][Ws], row b * T + t the window at origins[t] = (y, x) (host array [T][2]),
+ *   bit for bit; every window must lie inside the source.  16-byte accesses when tw, Ws and every x are multiples of 4 and the pointers
+ *   are aligned, element accesses otherwise.  Serves the latent grid (origins divided by the pixels per latent position) and the pixel
+ *   grid (a caller's full-frame start image).
+ * cdc_tile_blend: the ny x nx tiles [Th][Tw] of each of B images, at the per-axis origins ys [ny], xs [nx] (host, strictly ascending,
+ *   every tile inside the frame Hf x Wf), blended into the window (wy0, wx0, wh, ww) of the frame: out [B][C][wh][ww], CDC_ELEM_F32 or
+ *   CDC_ELEM_U8 (the byte cdc_frame_crop writes).  THE WEIGHTS: along an axis of length L a tile [o, o + size) has at coordinate p
+ *     lo = 1 if o == 0, else min(1, (p - o + 0.5) / overlap);   hi = 1 if o + size == L, else min(1, (o + size - p - 0.5) / overlap);
+ *     w_axis = min(lo, hi);   w = w_y * w_x;   out = (sum_t w_t v_t) / (sum_t w_t)
+ *   over the tiles that cover the pixel in ascending t, every operation rounded to float32 on its own (the first term starts both
+ *   sums), the divisions IEEE-rounded.  A gather: every output element is written once by its own thread, no atomics.  One covering
+ *   tile returns its value bit for bit; a window is the crop of the full blend bit for bit.  `present` (host [ny * nx] bytes, NULL: all):
+ *   tiles holds only the present tiles of each image, [B][Tp][C][Th][Tw] in ascending t; a tile that covers a pixel of the window and is
+ *   absent is CDC_ERR_INVALID, as is a window coordinate no tile covers.  B * C <= 65535.  16-byte accesses when Tw, ww, wx0 and
+ *   every xs are multiples of 4 and the pointers are aligned.
+ * Both follow `mem` / `stream` as cdc_frame_crop does and take any handle kind. */
+int cdc_set_noise_frames(cdc_handle *h, const int32_t *rows /* [n][4]: frame_h, frame_w, y0, x0; nullable when n == 0 */, int n);
+int cdc_randn_framed(cdc_handle *h, const uint64_t *seeds, const int32_t *rows, int B, int C, int th, int tw, uint32_t draw, float scale,
+                     float *out, int mem, void *stream);
+int cdc_randn_framed_host(const uint64_t *seeds, const int32_t *rows, int B, int C, int th, int tw, uint32_t draw, float scale, float *out);
+int cdc_tile_gather(cdc_handle *h, const float *src, float *dst, const int32_t *origins /* host [T][2] */, int B, int C, int Hs, int Ws,
+                    int T, int th, int tw, int mem, void *stream);
+int cdc_tile_blend(cdc_handle *h, const float *tiles, void *out, const int32_t *ys, int ny, const int32_t *xs, int nx,
+                   const uint8_t *present /* nullable */, int B, int C, int Th, int Tw, int Hf, int Wf, int overlap_y, int overlap_x,
+                   int wy0, int wx0, int wh, int ww, int elem_kind, int mem, void *stream);
+
 /* Determinism stress of the single-operator entry points (test infrastructure of the model path: it has no atomics and every
  * summation order is fixed by the launch geometry, so a launch program must reproduce its own bits).  After
  * cdc_op_stress(h, n), every cdc_op_* call launches its program n more times behind the first execution and counts the
