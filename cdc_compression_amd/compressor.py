@@ -75,6 +75,22 @@ def rdo_values(rdo, B, what="rdo"):
     return r
 
 
+def segment_positions(segment, cell):
+    """segment= -> the side of a stream segment in latent positions (cdc_entropy_set_segments), checked before the library is touched.
+    segment is in image pixels, like tile=: an int > 0 that is a multiple of `cell`, the pixels of a latent position; None -> 0, the
+    unsegmented streams."""
+    if segment is None:
+        return 0
+    if isinstance(segment, bool) or not isinstance(segment, (int, np.integer)):
+        raise ValueError(f"segment={segment!r}: an int in image pixels expected")
+    seg = int(segment)
+    if seg <= 0 or seg % cell:
+        raise ValueError(f"segment={seg}: a positive multiple of the {cell} pixels of a latent position expected")
+    if seg // cell > 65535:
+        raise ValueError(f"segment={seg}: at most {65535 * cell} pixels ({65535} latent positions)")
+    return seg // cell
+
+
 def rdo_exclusive(rdo=None, target_bpp=None, max_bytes=None):
     """rdo, target_bpp and max_bytes exclude each other."""
     given = [n for n, v in (("rdo", rdo), ("target_bpp", target_bpp), ("max_bytes", max_bytes)) if v is not None]
@@ -605,15 +621,17 @@ class _ContextDecoder:
             med = torch.from_numpy(med).to(t.device)
         return med
 
-    def encode(self, input, cond=None, padded_hw=None, rdo=None, price_map=None, price_cells=None):
+    def encode(self, input, cond=None, padded_hw=None, rdo=None, price_map=None, price_cells=None, segment=None):
         """Compressor.encode (compress_modules.py:43-66): (q_latent, q_hyper_latent, state4bpp); cond: VBR rate.  Images of any
         size (float32 / uint8): the results are those of the padded frame.  rdo: the price of a bit mu >= 0, a scalar or B values
         (no reference counterpart): q_latent comes from `rdo_quantize` -- every symbol the nearest integer or, where mu * (bits saved)
         exceeds the squared error it costs, its neighbour towards the mean; state4bpp keeps the unquantised latent and gains
         "q_latent" and "rdo_moved" (int64 [B]).  None runs the reference's rounding.  price_map / price_cells (with rdo): the price of
         a bit becomes mu * the map's value at the symbol's position -- a pixel-domain map at the image's own size ([H, W], [1, H, W],
-        [B, H, W] or [B, 1, H, W]; float32 >= 0 or bool), or its cells on the latent grid as `price_cells()` returns them."""
+        [B, H, W] or [B, 1, H, W]; float32 >= 0 or bool), or its cells on the latent grid as `price_cells()` returns them.
+        segment: the segment size of `compress_to_bytes`, checked as there; the symbols do not depend on how a stream is cut."""
         B, _, H0, W0 = frame.image_shape(input)
+        segment_positions(segment, self.rate_map_cell)
         self._rates(cond, B)
         mu = None if rdo is None else rdo_values(rdo, B)
         priced = price_args(price_map, price_cells, B, (H0, W0), rdo is not None)
@@ -710,7 +728,7 @@ class _ContextDecoder:
         return np.ascontiguousarray(med, dtype=np.float32)
 
     def compress_to_bytes(self, images, bitrate_scale=None, rdo=None, target_bpp=None, max_bytes=None, return_info=False,
-                          price_map=None, price_cells=None):
+                          price_map=None, price_cells=None, segment=None):
         """images [B, 3, H, W] -> list of B bitstreams (bytes): analysis transform + hyper encoder on the GPU, then the
         range-ANS coder of include/cdc_hip.h (cdc_entropy_encode) over exactly the symbols `bpp()` prices.  A VBR model
         takes bitrate_scale (1 or B values) and records each image's rate in its stream.
@@ -729,9 +747,14 @@ class _ContextDecoder:
         price of a bit becomes mu * the map at the symbol's position: 0 protects a region, 1 leaves mu as it is, larger values make
         a region pay.  Under target_bpp / max_bytes every sweep prices the ladder under the image's own map, and the "mu" reported
         is the base price the map multiplies.
+        segment=s (image pixels, a multiple of `rate_map_cell`, like tile=): segmented streams (container versions 11 - 14,
+        cdc_entropy_set_segments): the latent section is cut into independent sections, one per s x s window of the image, behind an
+        index -- n segments code and decode on n waves, and `decompress_from_bytes(window=)` decodes only those it needs.  The symbols
+        are the same; a stream grows by 8 + 12 n bytes and its segments' lane states (max_bytes counts them).  None: today's streams.
         return_info=True: -> (streams, {"mu", "estimated_bpp", "moved", "latent_mse", "met" (each [B]), "reencodes"})."""
         B, _, H0, W0 = frame.image_shape(images)
         rdo_exclusive(rdo, target_bpp, max_bytes)
+        segment_positions(segment, self.rate_map_cell)
         self._rates(bitrate_scale, B)
         mu = None if rdo is None else rdo_values(rdo, B)
         target = None if target_bpp is None else self._targets(target_bpp, B, "target_bpp")
@@ -741,7 +764,7 @@ class _ContextDecoder:
         cells = self._cells_of(priced, hw)
         latent, hyper = self.analysis(images, bitrate_scale)
         if target is None and budget is None:
-            streams = self.latents_to_bytes(latent, hyper, bitrate_scale, image_hw=hw, rdo=mu, price_cells=cells)
+            streams = self.latents_to_bytes(latent, hyper, bitrate_scale, image_hw=hw, rdo=mu, price_cells=cells, segment=segment)
             if not return_info:
                 return streams
             row = self._sweep(latent, hyper, np.zeros(1, np.float32) if mu is None else mu, bitrate_scale, per_image=True, cells=cells)
@@ -753,7 +776,7 @@ class _ContextDecoder:
         if target is not None:
             goal, cost0 = target, table["bits"] / npix                  # estimated bpp against the target
         else:
-            header = self._stream_header_bytes(images, hw)
+            header = self._stream_header_bytes(images, hw, segment)
             goal, cost0 = 8.0 * (budget - header), table["bits"]       # estimated payload bits against the budget's
         div = npix if target is not None else 1.0
         rows = [self._choose_mu(latent, hyper, bitrate_scale, b, ladder, cost0[b], goal[b], div, cells)
@@ -761,7 +784,7 @@ class _ContextDecoder:
         reencodes = 0
         while True:
             mus = np.asarray([r["mu"] for r in rows], np.float32)
-            streams = self.latents_to_bytes(latent, hyper, bitrate_scale, image_hw=hw, rdo=mus, price_cells=cells)
+            streams = self.latents_to_bytes(latent, hyper, bitrate_scale, image_hw=hw, rdo=mus, price_cells=cells, segment=segment)
             over = [] if budget is None else [b for b in range(B) if len(streams[b]) > budget[b]]
             if not over or reencodes == 3:
                 break
@@ -786,10 +809,16 @@ class _ContextDecoder:
             raise ValueError(f"{what}={t.tolist()}: finite values > 0 expected")
         return np.broadcast_to(t, (B,)).copy()
 
-    def _stream_header_bytes(self, images, hw):
-        """Bytes of a stream's header (include/cdc_hip.h: 34, + 4 with a bitrate_scale, + 8 with a recorded image size)."""
+    def _stream_header_bytes(self, images, hw, segment=None):
+        """Bytes of a stream that code no symbol (include/cdc_hip.h: the header's 34, + 4 with a bitrate_scale, + 8 with a recorded image
+        size; of a segmented stream also the 8 bytes and the 12 of every index entry in front of its segments)."""
         framed = tuple(frame.image_shape(images)[2:])
-        return 34 + (4 if self.vbr else 0) + (8 if tuple(hw) != framed else 0)
+        seg = segment_positions(segment, self.rate_map_cell)
+        index = 0
+        if seg:
+            c = self.rate_map_cell
+            index = 8 + 12 * (-(-(framed[0] // c) // seg)) * (-(-(framed[1] // c) // seg))
+        return 34 + (4 if self.vbr else 0) + (8 if tuple(hw) != framed else 0) + index
 
     def _sweep(self, latent, hyper, mus, bitrate_scale=None, per_image=False, cells=None):
         """cdc_entropy_rate_sweep on the unquantised outputs of `analysis()` -> {"bits", "sse" float64 [B, L], "moved" int64 [B, L]}.
@@ -870,7 +899,7 @@ class _ContextDecoder:
         per = float(np.prod(tuple(latent.shape)[1:]))
         return {"mu": mus.copy(), "bpp": t["bits"] / float(hw[0] * hw[1]), "latent_mse": t["sse"] / per, "moved": t["moved"]}
 
-    def latents_to_bytes(self, latent, hyper, bitrate_scale=None, image_hw=None, rdo=None, price_map=None, price_cells=None):
+    def latents_to_bytes(self, latent, hyper, bitrate_scale=None, image_hw=None, rdo=None, price_map=None, price_cells=None, segment=None):
         """The UNquantised outputs of `analysis()` -> list of B bitstreams.  The coder's determinism contract starts here: the
         same (latent, hyper) rows give the same bytes whatever the batch they are coded in (the analysis transform itself is
         an ordinary batched forward: its last bits may depend on the batch size, like any other entry point's).
@@ -878,7 +907,9 @@ class _ContextDecoder:
         (container version 5 / 6) unless it equals the frame's, and are today's version 3 / 4 otherwise.
         rdo: mu, 1 or B values (cdc_set_rdo for this call alone); image b's stream depends on its own mu only.
         price_map / price_cells (with rdo; cdc_set_rdo_map for this call alone): as `compress_to_bytes`, the pixel-domain map at
-        image_hw (default: the coded extent); image b's stream depends on its own mu and its own row of the map only."""
+        image_hw (default: the coded extent); image b's stream depends on its own mu and its own row of the map only.
+        segment: as `compress_to_bytes` (cdc_entropy_set_segments for this call alone)."""
+        seg = segment_positions(segment, self.rate_map_cell)
         L, h = _lib.lib(), self._hyper_handle()
         al, ah = _Arg(latent, self.device_index), _Arg(hyper, self.device_index)
         B, _, hh, wh = ah.shape
@@ -889,17 +920,25 @@ class _ContextDecoder:
         if not (self._hyper_finalized and self._prior_loaded):
             raise _lib.CdcError("the prior.* tensors have not been loaded (load_state_dict with the full state_dict)")
         self._set_rate(h, bitrate_scale, B)
-        if mu is not None:
-            _lib.check(h, L.cdc_set_rdo(h, mu.ctypes.data, int(mu.size)))
-            try:
-                return self._with_map(h, cells, lambda: self._coded(L, h, al, ah, B, hh, wh, image_hw))
-            finally:
-                L.cdc_set_rdo(h, None, 0)
-        return self._coded(L, h, al, ah, B, hh, wh, image_hw)
+        if seg:
+            _lib.check(h, L.cdc_entropy_set_segments(h, seg))
+        try:
+            if mu is not None:
+                _lib.check(h, L.cdc_set_rdo(h, mu.ctypes.data, int(mu.size)))
+                try:
+                    return self._with_map(h, cells, lambda: self._coded(L, h, al, ah, B, hh, wh, image_hw, seg))
+                finally:
+                    L.cdc_set_rdo(h, None, 0)
+            return self._coded(L, h, al, ah, B, hh, wh, image_hw, seg)
+        finally:
+            if seg:
+                L.cdc_entropy_set_segments(h, 0)
 
-    def _coded(self, L, h, al, ah, B, hh, wh, image_hw):
+    def _coded(self, L, h, al, ah, B, hh, wh, image_hw, seg=0):
         nsym = int(np.prod(al.shape[1:])) + int(np.prod(ah.shape[1:]))
         cap = B * (64 + 2 * 320 + 6 * nsym)              # <= 2 renormalisation bytes + a 4-byte escape payload per symbol
+        if seg:                                          # the index and every segment's own 64 lane states
+            cap += B * (8 + (12 + 256) * (-(-int(al.shape[2]) // seg)) * (-(-int(al.shape[3]) // seg)))
         buf = np.empty(cap, dtype=np.uint8)
         offs = (ctypes.c_size_t * (B + 1))()
         med = self._median_vector()
@@ -913,7 +952,7 @@ class _ContextDecoder:
         return [raw[offs[b]: offs[b + 1]] for b in range(B)]
 
     def decompress_from_bytes(self, streams, like=None, return_hyper=False, max_image_hw=None, return_bitrate_scale=False,
-                              return_image_size=False, return_rate_map=False):
+                              return_image_size=False, return_rate_map=False, window=None, return_segments=False):
         """list of B bitstreams -> q_latent [B, C, h, w] exactly as the encoder dequantised it (numpy, or a tensor on
         `like`'s device); all streams must have the same latent size.  max_image_hw=(H, W): refuse streams whose header
         describes a larger image before anything is allocated (untrusted input; default: the library's 2^22-position bound).
@@ -921,7 +960,15 @@ class _ContextDecoder:
         `decode(q_latent, rates)` then gives the context pyramid.  return_image_size: also return (H, W), the size the streams
         record (version 5 / 6) or, for version 3 / 4, the coded extent; q_latent is that of the padded frame either way.
         return_rate_map: also return, last, `rate_map(...)["cell"]` of the decoded symbols, [B, U h, U w]: where the streams' bits
-        went, without the original (the decoder holds the symbols, and runs hyper_decode once more for their mean and scale)."""
+        went, without the original (the decoder holds the symbols, and runs hyper_decode once more for their mean and scale).
+        window=(y0, x0, h, w) in LATENT positions (cdc_entropy_decode_window): of segmented streams only the segments that intersect
+        it are decoded and verified; q_latent is full-size, equal to the full decode inside them and to hyper_decode's mean elsewhere.
+        The header's checksum over all symbols is then not checked, and a corrupt segment outside the window is not noticed.
+        Unsegmented streams decode whole.  return_segments: also return (segments per image, segments decoded per image)."""
+        if window is not None:
+            window = tuple(int(v) for v in window)
+            if len(window) != 4 or window[0] < 0 or window[1] < 0 or window[2] < 1 or window[3] < 1:
+                raise ValueError(f"window={window}: (y0, x0, h, w) in latent positions with y0, x0 >= 0 and h, w >= 1 expected")
         L, h = _lib.lib(), self._hyper_handle()
         # the limit is handle state in the library: set it on EVERY call (None -> the library's default bound), so that one
         # restricted call does not restrict the next; the product is clamped before it is handed over as a C int
@@ -956,7 +1003,12 @@ class _ContextDecoder:
             pos += len(s)
         offs[B] = pos
         med = self._median_vector()
-        _lib.check(h, L.cdc_entropy_decode(h, blob, offs, med.ctypes.data, B, pq, ph, mem, _current_stream(mem)))
+        if window is None:
+            _lib.check(h, L.cdc_entropy_decode(h, blob, offs, med.ctypes.data, B, pq, ph, mem, _current_stream(mem)))
+        else:
+            n_dec = ctypes.c_int(0)
+            _lib.check(h, L.cdc_entropy_decode_window(h, blob, offs, med.ctypes.data, B, (ctypes.c_int32 * 4)(*window), pq, ph,
+                                                      ctypes.byref(n_dec), mem, _current_stream(mem)))
         out = (q, qh) if return_hyper else (q,)
         if return_bitrate_scale:
             out = out + (self.bitrate_scale_of(streams) if self.vbr else None,)
@@ -968,7 +1020,24 @@ class _ContextDecoder:
         if return_rate_map:
             mean, scale = self.hyper_decode(qh, cond=self.bitrate_scale_of(streams) if self.vbr else None)
             out = out + (self.rate_map(qh, q, mean, scale, ("cell",))["cell"],)
+        if return_segments:
+            _, ny, nx = self.segments_of(streams[:1])[0]
+            out = out + ((ny * nx, ny * nx if window is None else int(n_dec.value)),)
         return out if len(out) > 1 else out[0]
+
+    @staticmethod
+    def segments_of(streams):
+        """[(segment side in latent positions, ny, nx)] of the streams (cdc_entropy_peek_segments, no handle needed): (0, 1, 1) for an
+        unsegmented stream (version 3 - 6), the segment size and the grid of segments of a segmented one (version 11 - 14)."""
+        L = _lib.lib()
+        seg, ny, nx = (ctypes.c_int() for _ in range(3))
+        out = []
+        for s in streams:
+            s = bytes(s)
+            if L.cdc_entropy_peek_segments(s, len(s), ctypes.byref(seg), ctypes.byref(ny), ctypes.byref(nx)) != 0:
+                raise _lib.CdcError("not a CDC bitstream")
+            out.append((seg.value, ny.value, nx.value))
+        return out
 
     @staticmethod
     def image_size_of(streams, frame_multiple=64):

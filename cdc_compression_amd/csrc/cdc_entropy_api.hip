@@ -12,9 +12,15 @@ constexpr int kStreamHeaderVbr = 38;
 // version 6 -- img_h u32 | img_w u32: the size the decoder crops to (the coded extent is the image padded at the bottom / right)
 constexpr int kStreamVersionSized = 5, kStreamVersionVbrSized = 6;
 constexpr int kStreamSizeField = 8;
-inline bool version_known(int v) { return v == kStreamVersion || v == kStreamVersionVbr || v == kStreamVersionSized || v == kStreamVersionVbrSized; }
-inline bool version_vbr(int v) { return v == kStreamVersionVbr || v == kStreamVersionVbrSized; }
-inline bool version_sized(int v) { return v == kStreamVersionSized || v == kStreamVersionVbrSized; }
+// segmented streams (include/cdc_hip.h): the header of version 3 .. 6 byte for byte with version byte + 8 = 11 .. 14 (7 and 8 stay
+// no stream), and a latent part cut into independent sections behind an index
+constexpr int kStreamSegmentedBy = 8;
+constexpr int kSegHeader = 8, kSegIndexEntry = 12, kMaxSegments = 65535;
+inline bool version_segmented(int v) { return v >= kStreamVersion + kStreamSegmentedBy && v <= kStreamVersionVbrSized + kStreamSegmentedBy; }
+inline int version_base(int v) { return version_segmented(v) ? v - kStreamSegmentedBy : v; }
+inline bool version_known(int v) { v = version_base(v); return v == kStreamVersion || v == kStreamVersionVbr || v == kStreamVersionSized || v == kStreamVersionVbrSized; }
+inline bool version_vbr(int v) { v = version_base(v); return v == kStreamVersionVbr || v == kStreamVersionVbrSized; }
+inline bool version_sized(int v) { v = version_base(v); return v == kStreamVersionSized || v == kStreamVersionVbrSized; }
 inline int stream_header(const unsigned char *s) { return (version_vbr(s[3]) ? kStreamHeaderVbr : kStreamHeader) + (version_sized(s[3]) ? kStreamSizeField : 0); }
 // the recorded size must pad to exactly the coded extent: D (n - 1) < size <= D n, D image pixels per hyper-latent position
 inline bool size_fits(long long size, int n, int D) { return size > (long long)D * (n - 1) && size <= (long long)D * n; }
@@ -43,8 +49,54 @@ int ensure_entropy(cdc_handle *h, const float *medians) {
 }
 
 inline uint32_t get_u32(const unsigned char *s) { uint32_t v = 0; for (int i = 0; i < 4; ++i) v |= (uint32_t)s[i] << (8 * i); return v; }
+inline uint32_t get_u16(const unsigned char *s) { return (uint32_t)s[0] | ((uint32_t)s[1] << 8); }
+// The segmented latent part of a version-11 .. -14 stream s[0 .. n) whose fixed header is complete: everything a reader without a
+// handle can check (include/cdc_hip.h lists it).  -> false: no stream.  index: the first index entry; first: where segment 0 starts.
+struct SegLayout { int seg = 0, ny = 1, nx = 1; const unsigned char *index = nullptr; size_t first = 0; };
+bool parse_segments(const unsigned char *s, size_t n, SegLayout *out) {
+    const unsigned long long hdr = (unsigned long long)stream_header(s), nbh = get_u32(s + 10), nbl = get_u32(s + 14), el = get_u32(s + 30);
+    if (hdr + nbh + nbl != (unsigned long long)n || nbl < (unsigned long long)kSegHeader) return false;
+    const unsigned char *p = s + hdr + nbh;
+    const uint32_t seg = get_u16(p), ny = get_u16(p + 2), nx = get_u16(p + 4), zero = get_u16(p + 6);
+    const unsigned long long S = (unsigned long long)ny * nx;
+    if (seg < 1 || S < 1 || S > (unsigned long long)kMaxSegments || zero != 0) return false;
+    const unsigned long long fixed = kSegHeader + kSegIndexEntry * S;
+    if (nbl < fixed) return false;
+    unsigned long long bytes = 0, esc = 0;
+    for (unsigned long long i = 0; i < S; ++i) {
+        const unsigned char *e = p + kSegHeader + kSegIndexEntry * i;
+        const unsigned long long b = get_u32(e), x = get_u32(e + 4);
+        if (b < 256 + 4 * x) return false;
+        bytes += b; esc += x;
+    }
+    if (fixed + bytes != nbl || esc != el) return false;
+    out->seg = (int)seg; out->ny = (int)ny; out->nx = (int)nx;
+    out->index = p + kSegHeader;
+    out->first = (size_t)(hdr + nbh + fixed);
+    return true;
+}
+
 constexpr int kMaxHyperPositions = 1 << 22;       // hh * wh of a 131072 x 131072 image; bounds every allocation of the decoder
 inline long long section_cap(long long n) { return (2 * n + 256 + 15) & ~15ll; }   // <= 2 renormalisation bytes per symbol + 64 states
+
+// The segment table of a latent grid [C][Hl][Wl] cut into seg x seg windows (raster order; edge segments are smaller)
+struct SegTable { std::vector<cdc::SegEntry> e; int ny = 0, nx = 0, max_n = 0; };
+void make_seg_table(int C, int Hl, int Wl, int seg, SegTable *t) {
+    t->ny = (Hl + seg - 1) / seg; t->nx = (Wl + seg - 1) / seg;
+    t->e.clear();
+    t->max_n = 0;
+    int off = 0;
+    for (int sy = 0; sy < t->ny; ++sy)
+        for (int sx = 0; sx < t->nx; ++sx) {
+            cdc::SegEntry q;
+            q.y0 = sy * seg; q.x0 = sx * seg;
+            q.h = std::min(seg, Hl - q.y0); q.w = std::min(seg, Wl - q.x0);
+            q.off = off; q.n = C * q.h * q.w;             // (the caller has bounded C Hl Wl by 2^29)
+            off += q.n;
+            t->max_n = std::max(t->max_n, q.n);
+            t->e.push_back(q);
+        }
+}
 
 // hyper_dec over the batch through the batch-1 launch plan: h->in_x (filled by the caller) -> dec_outs[0] = (mean | scale).
 // `check`: the results are range-checked (kRangeRetry when they left the F16X2 range).
@@ -175,8 +227,21 @@ int entropy_encode_impl(cdc_handle *h, const float *latent, const float *hyper_l
     uint32_t *sf, *ew, *esc_h, *esc_l;
     cdc::RansMeta *meta;
     long long *d_off;
-    const long long cap_h = section_cap(nh), cap_l = section_cap(nl);
-    const long long pack_cap = (long long)B * ((h->vbr ? kStreamHeaderVbr : kStreamHeader) + kStreamSizeField + cap_h + 4 * nh + cap_l + 4 * nl);
+    // cdc_entropy_set_segments: the latent part as S independent sections; 0 leaves every size and launch below as it was
+    const int seg = h->ent_seg, Cl = o.C / 2;
+    SegTable segs;
+    int S = 0;
+    if (seg > 0) {
+        const long long ny = ((long long)o.H + seg - 1) / seg, nx = ((long long)o.W + seg - 1) / seg;
+        if (ny * nx > kMaxSegments)
+            return fail(h, CDC_ERR_INVALID, "segments of %d positions cut the %d x %d latent grid into %lld x %lld: more than %d segments", seg, o.H, o.W, ny, nx, kMaxSegments);
+        if (B > 65535) return fail(h, CDC_ERR_INVALID, "segmented streams: a batch of %d (at most 65535 images a call)", B);
+        make_seg_table(Cl, o.H, o.W, seg, &segs);
+        S = segs.ny * segs.nx;
+    }
+    const long long cap_h = section_cap(nh), cap_l = S ? ((2 * nl + 256ll * S + 15) & ~15ll) : section_cap(nl);
+    const long long pack_cap = (long long)B * ((h->vbr ? kStreamHeaderVbr : kStreamHeader) + kStreamSizeField + cap_h + 4 * nh + cap_l + 4 * nl +
+                                               (S ? kSegHeader + (long long)kSegIndexEntry * S : 0));
     HIP_TRY(h, d.get(&syml, (size_t)B * nl)); HIP_TRY(h, d.get(&bin, (size_t)B * nl));
     HIP_TRY(h, d.get(&sf, (size_t)B * std::max(nh, nl))); HIP_TRY(h, d.get(&ew, (size_t)B * std::max(nh, nl)));
     HIP_TRY(h, d.get(&sec_h, (size_t)B * cap_h)); HIP_TRY(h, d.get(&sec_l, (size_t)B * cap_l));
@@ -192,12 +257,26 @@ int entropy_encode_impl(cdc_handle *h, const float *latent, const float *hyper_l
     }
     const cdc::EntropyDev T = h->ent->dev();
     HIP_TRY(h, cdc::rans_encode_launch(T, symh, nh, nullptr, 0, per, 0, (int)nh, 0u, B, sf, ew, sec_h, cap_h, esc_h, nh, meta, st));
-    HIP_TRY(h, cdc::rans_encode_launch(T, syml, nl, bin, nl, 0, Ch, (int)nl, 1u, B, sf, ew, sec_l, cap_l, esc_l, nl, meta + B, st));
+    if (!S) HIP_TRY(h, cdc::rans_encode_launch(T, syml, nl, bin, nl, 0, Ch, (int)nl, 1u, B, sf, ew, sec_l, cap_l, esc_l, nl, meta + B, st));
     const long long dev_cap = (long long)std::min<unsigned long long>((unsigned long long)cap, (unsigned long long)pack_cap);
     HIP_TRY(h, d.get(&packed, (size_t)dev_cap));
     cdc::RansPack P{sec_h, sec_l, esc_h, esc_l, meta, meta + B, cap_h, cap_l, nh, nl, dev_cap, packed, d_off, h->ent_model_hash, h->arith, hh, wh,
                     h->vbr ? h->d_rate : nullptr, img_h, img_w};
-    HIP_TRY(h, cdc::rans_pack_launch(P, B, st));
+    if (!S) {
+        HIP_TRY(h, cdc::rans_pack_launch(P, B, st));
+    } else {
+        cdc::SegEntry *d_tab;
+        cdc::RansMeta *smeta;
+        cdc::SegTotal *tot;
+        long long *seg_at;
+        HIP_TRY(h, d.get(&d_tab, (size_t)S)); HIP_TRY(h, d.get(&smeta, (size_t)B * S)); HIP_TRY(h, d.get(&tot, (size_t)B));
+        HIP_TRY(h, d.get(&seg_at, (size_t)B * S));
+        HIP_TRY(h, hipMemcpyAsync(d_tab, segs.e.data(), sizeof(cdc::SegEntry) * S, hipMemcpyHostToDevice, st));
+        HIP_TRY(h, cdc::seg_encode_launch(T, d_tab, S, segs.max_n, syml, bin, nl, o.H, o.W, Ch, B, sf, ew, sec_l, cap_l, esc_l, smeta, tot, st));
+        P.meta_l = nullptr;
+        cdc::SegPack SP{P, d_tab, smeta, tot, seg_at, seg, segs.ny, segs.nx};
+        HIP_TRY(h, cdc::seg_pack_launch(SP, B, st));
+    }
     std::vector<long long> hoff((size_t)B + 1);
     int hbad = 0;
     HIP_TRY(h, hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -266,8 +345,9 @@ int rate_sweep_impl(cdc_handle *h, const float *latent, const float *hyper_laten
     return CDC_OK;
 }
 
-int entropy_decode_impl(cdc_handle *h, const unsigned char *in, const size_t *offsets, const float *medians, int B,
-                        float *q_latent, float *q_hyper_latent, int mem, void *stream) {
+// window = null: cdc_entropy_decode; else cdc_entropy_decode_window (y0, x0, h, w in latent positions; *segments_decoded per image)
+int entropy_decode_impl(cdc_handle *h, const unsigned char *in, const size_t *offsets, const float *medians, int B, const int32_t *window,
+                        float *q_latent, float *q_hyper_latent, int *segments_decoded, int mem, void *stream) {
     int rc = check_ready(h);
     if (rc) return rc;
     if (!in || !offsets || !medians || !q_latent || B < 1) return fail(h, CDC_ERR_INVALID, "null/invalid argument");
@@ -279,7 +359,8 @@ int entropy_decode_impl(cdc_handle *h, const unsigned char *in, const size_t *of
     // the decoder runs hyper_dec in the encoder's arithmetic (see the contract in entropy.hip); the handle's own mode comes back
     struct Restore { cdc_handle *h; int a; ~Restore() { if (h->arith != a) (void)cdc_set_arith(h, a); } } restore{h, h->arith};
     // ---- headers: everything that sizes an allocation is validated here ----
-    struct Hdr { int hh, wh, ar, hdr; uint32_t nbh, nbl, sum, eh, el; float rate; };
+    struct Hdr { int hh, wh, ar, hdr; uint32_t nbh, nbl, sum, eh, el; float rate; SegLayout lay; };
+    const int U = 1 << ((int)h->hyper_dims.size() - 2);    // latent positions per hyper-latent position and side (as cdc_bpp)
     int img0_h = -1, img0_w = -1;                        // the size every image of the call shares (0: the coded extent)
     std::vector<Hdr> hd((size_t)B);
     for (int b = 0; b < B; ++b) {
@@ -318,9 +399,28 @@ int entropy_decode_impl(cdc_handle *h, const unsigned char *in, const size_t *of
         if (4ull * q.eh + 256 > q.nbh || 4ull * q.el + 256 > q.nbl) return fail(h, CDC_ERR_INVALID, "image %d: corrupt section sizes", b);
         if (q.hh != hd[0].hh || q.wh != hd[0].wh)
             return fail(h, CDC_ERR_INVALID, "image %d: %d x %d hyper-latent in a batch of %d x %d (one call decodes one image size)", b, q.hh, q.wh, hd[0].hh, hd[0].wh);
+        if (version_segmented(s[3])) {                     // (cdc_entropy_peek has validated the index against the header)
+            if (!parse_segments(s, n, &q.lay)) return fail(h, CDC_ERR_INVALID, "image %d: corrupt segment index", b);
+            const long long Hl = (long long)U * q.hh, Wl = (long long)U * q.wh;
+            if (q.lay.ny != (Hl + q.lay.seg - 1) / q.lay.seg || q.lay.nx != (Wl + q.lay.seg - 1) / q.lay.seg)
+                return fail(h, CDC_ERR_INVALID, "image %d: %d x %d segments of %d positions do not tile this model's %lld x %lld latent grid", b, q.lay.ny,
+                            q.lay.nx, q.lay.seg, Hl, Wl);
+        }
+        if (q.lay.seg != hd[0].lay.seg)
+            return fail(h, CDC_ERR_INVALID, "image %d: %s stream in a call whose image 0 is %s (one call decodes one form and one segment size)", b,
+                        q.lay.seg ? "a segmented" : "an unsegmented", hd[0].lay.seg ? "segmented" : "not, or is cut otherwise");
     }
     const int hh = hd[0].hh, wh = hd[0].wh, per = hh * wh;
     const long long nh = (long long)Ch * per;
+    const int seg = hd[0].lay.seg, S = hd[0].lay.ny * hd[0].lay.nx;
+    cdc::SegWindow win{0, 0, U * hh, U * wh};
+    if (window) {
+        win = cdc::SegWindow{window[0], window[1], window[2], window[3]};
+        if (win.y0 < 0 || win.x0 < 0 || win.h < 1 || win.w < 1 || (long long)win.y0 + win.h > (long long)U * hh || (long long)win.x0 + win.w > (long long)U * wh)
+            return fail(h, CDC_ERR_INVALID, "window (%d, %d, %d, %d) is not inside the %d x %d latent grid", win.y0, win.x0, win.h, win.w, U * hh, U * wh);
+    }
+    if (seg && B > 65535) return fail(h, CDC_ERR_INVALID, "segmented streams: a batch of %d (at most 65535 images a call)", B);
+    int n_sel = 1;                                         // segments a window selects (an unsegmented stream decodes whole)
     // the whole input goes to the device once (+ slack: nothing reads past the end, but sections are addressed by offset)
     const size_t total = offsets[B] - offsets[0];
     DevPool d;
@@ -367,11 +467,70 @@ int entropy_decode_impl(cdc_handle *h, const unsigned char *in, const size_t *of
         }
         if ((rc = hyperdec_batch(h, nb, st, false))) return rc;
         HIP_TRY(h, cdc::latent_symbols_launch(nullptr, 0, o.p, o.p + nl, o.bs(), h->ent->d_edges, nl, nb, nullptr, bin, nullptr, st));
-        HIP_TRY(h, cdc::rans_decode_launch(T, d_in, d_off + nb, d_len + nb, d_esc + nb, bin, nl, 0, Ch, (int)nl, 1u, nb, syml, nl, meta + nb, st));
         std::vector<cdc::RansMeta> hm(2 * (size_t)nb);
-        HIP_TRY(h, hipMemcpyAsync(hm.data(), meta, sizeof(cdc::RansMeta) * hm.size(), hipMemcpyDeviceToHost, st));
-        HIP_TRY(h, hipStreamSynchronize(st));
-        for (int b = b0; b < b1; ++b) {
+        if (seg) {
+            // the selected segments, one wave each: their bins gathered into segment order, decoded, scattered back to the frame
+            if (o.H != U * hh || o.W != U * wh) return fail(h, CDC_ERR_STATE, "the hyper decoder's output is not the %d x %d latent grid", U * hh, U * wh);
+            SegTable segs;
+            make_seg_table(o.C / 2, o.H, o.W, seg, &segs);
+            std::vector<cdc::SegJob> jobs;
+            std::vector<uint32_t> want;                    // the index's checksum of every job's segment
+            for (int b = b0; b < b1; ++b) {
+                long long at = (long long)(offsets[b] - offsets[0]) + (long long)hd[b].lay.first;
+                for (int s = 0; s < S; ++s) {
+                    const unsigned char *ix = hd[b].lay.index + (size_t)kSegIndexEntry * s;
+                    const cdc::SegEntry &e = segs.e[s];
+                    if (e.y0 < win.y0 + win.h && win.y0 < e.y0 + e.h && e.x0 < win.x0 + win.w && win.x0 < e.x0 + e.w) {
+                        jobs.push_back(cdc::SegJob{at, (int)get_u32(ix), (int)get_u32(ix + 4), b - b0, s});
+                        want.push_back(get_u32(ix + 8));
+                    }
+                    at += get_u32(ix);
+                }
+            }
+            n_sel = (int)(jobs.size() / (size_t)nb);
+            cdc::SegEntry *d_tab;
+            cdc::SegJob *d_jobs;
+            cdc::RansMeta *jmeta;
+            uint8_t *bin_seg;
+            int32_t *sym_seg;
+            uint32_t *sums;
+            HIP_TRY(h, d.get(&d_tab, (size_t)S)); HIP_TRY(h, d.get(&d_jobs, jobs.size())); HIP_TRY(h, d.get(&jmeta, jobs.size()));
+            HIP_TRY(h, d.get(&bin_seg, (size_t)nb * nl)); HIP_TRY(h, d.get(&sym_seg, (size_t)nb * nl)); HIP_TRY(h, d.get(&sums, (size_t)nb * S));
+            HIP_TRY(h, hipMemcpyAsync(d_tab, segs.e.data(), sizeof(cdc::SegEntry) * S, hipMemcpyHostToDevice, st));
+            HIP_TRY(h, hipMemcpyAsync(d_jobs, jobs.data(), sizeof(cdc::SegJob) * jobs.size(), hipMemcpyHostToDevice, st));
+            HIP_TRY(h, cdc::seg_gather_bins_launch(d_tab, S, segs.max_n, win, bin, nl, o.H, o.W, nb, bin_seg, st));
+            HIP_TRY(h, cdc::seg_decode_launch(T, d_tab, d_jobs, (int)jobs.size(), d_in, bin_seg, nl, Ch, sym_seg, jmeta, st));
+            HIP_TRY(h, cdc::seg_scatter_launch(d_tab, S, segs.max_n, win, sym_seg, nl, o.H, o.W, nb, syml, sums, st));
+            std::vector<cdc::RansMeta> jm(jobs.size());
+            std::vector<uint32_t> hs((size_t)nb * S);
+            HIP_TRY(h, hipMemcpyAsync(hm.data(), meta, sizeof(cdc::RansMeta) * nb, hipMemcpyDeviceToHost, st));
+            HIP_TRY(h, hipMemcpyAsync(jm.data(), jmeta, sizeof(cdc::RansMeta) * jm.size(), hipMemcpyDeviceToHost, st));
+            HIP_TRY(h, hipMemcpyAsync(hs.data(), sums, sizeof(uint32_t) * hs.size(), hipMemcpyDeviceToHost, st));
+            HIP_TRY(h, hipStreamSynchronize(st));
+            for (int b = b0; b < b1; ++b)
+                if (hm[b - b0].bad) return fail(h, CDC_ERR_INVALID, "image %d: corrupt hyper stream", b);
+            std::vector<uint32_t> total((size_t)nb, 0u);
+            for (size_t j = 0; j < jobs.size(); ++j) {
+                const int b = b0 + jobs[j].b, s = jobs[j].s;
+                if (jm[j].bad)
+                    return fail(h, CDC_ERR_INVALID, "image %d, segment %d (row %d, column %d): corrupt latent segment (or this decoder's hyper-decoder "
+                                "output differs from the encoder's)", b, s, s / hd[b].lay.nx, s % hd[b].lay.nx);
+                if (hs[(size_t)jobs[j].b * S + s] != want[j])
+                    return fail(h, CDC_ERR_INVALID, "image %d, segment %d (row %d, column %d): symbol checksum mismatch -- this decoder's hyper-decoder "
+                                "output differs from the encoder's, or the segment or its index entry is corrupt", b, s, s / hd[b].lay.nx, s % hd[b].lay.nx);
+                total[jobs[j].b] += want[j];
+            }
+            // the header's checksum covers every symbol: checked when every segment was decoded (never by a window: include/cdc_hip.h)
+            for (int b = b0; b < b1 && !window; ++b)
+                if (hm[b - b0].checksum + total[b - b0] != hd[b].sum)
+                    return fail(h, CDC_ERR_INVALID, "image %d: symbol checksum mismatch -- this decoder's hyper-decoder output differs from the encoder's "
+                                                   "(other library build, development switches or GPU), or the payload is corrupt", b);
+        } else {
+            HIP_TRY(h, cdc::rans_decode_launch(T, d_in, d_off + nb, d_len + nb, d_esc + nb, bin, nl, 0, Ch, (int)nl, 1u, nb, syml, nl, meta + nb, st));
+            HIP_TRY(h, hipMemcpyAsync(hm.data(), meta, sizeof(cdc::RansMeta) * hm.size(), hipMemcpyDeviceToHost, st));
+            HIP_TRY(h, hipStreamSynchronize(st));
+        }
+        for (int b = b0; b < b1 && !seg; ++b) {
             if (hm[b - b0].bad) return fail(h, CDC_ERR_INVALID, "image %d: corrupt hyper stream", b);
             if (hm[nb + b - b0].bad)
                 return fail(h, CDC_ERR_INVALID, "image %d: corrupt latent stream (or this decoder's hyper-decoder output differs from the encoder's)", b);
@@ -390,6 +549,7 @@ int entropy_decode_impl(cdc_handle *h, const unsigned char *in, const size_t *of
         HIP_TRY(h, hipStreamSynchronize(st));
         b0 = b1;
     }
+    if (segments_decoded) *segments_decoded = n_sel;
     return CDC_OK;
 }
 
@@ -552,6 +712,10 @@ int cdc_entropy_peek(const unsigned char *in, size_t n, int *hh, int *wh, int *a
         const uint32_t uh = get_u32(f), uw = get_u32(f + 4);
         if (uh < 1 || uw < 1 || uh > (uint32_t)INT32_MAX || uw > (uint32_t)INT32_MAX) return CDC_ERR_INVALID;
     }
+    if (version_segmented(in[3])) {                       // a segmented stream is one whose index is sound: for every peek
+        SegLayout lay;
+        if (!parse_segments(in, n, &lay)) return CDC_ERR_INVALID;
+    }
     if (arith) *arith = in[4];
     if (hh) *hh = in[6] | (in[7] << 8);
     if (wh) *wh = in[8] | (in[9] << 8);
@@ -576,9 +740,35 @@ int cdc_entropy_peek_image_size(const unsigned char *in, size_t n, int *has_size
     return CDC_OK;
 }
 
+int cdc_entropy_peek_segments(const unsigned char *in, size_t n, int *seg, int *ny, int *nx) {
+    if (cdc_entropy_peek(in, n, nullptr, nullptr, nullptr)) return CDC_ERR_INVALID;
+    SegLayout lay;                                        // versions 3 - 6: one unsegmented section
+    if (version_segmented(in[3]) && !parse_segments(in, n, &lay)) return CDC_ERR_INVALID;
+    if (seg) *seg = lay.seg;
+    if (ny) *ny = lay.ny;
+    if (nx) *nx = lay.nx;
+    return CDC_OK;
+}
+
+int cdc_entropy_set_segments(cdc_handle *h, int seg) {
+    if (!h) return CDC_ERR_INVALID;
+    if (int rc = require_kind(h, HandleKind::HyperDecoder)) return rc;
+    if (seg < 0 || seg > 65535) return fail(h, CDC_ERR_INVALID, "segment side %d (0: unsegmented streams, or 1 .. 65535 latent positions)", seg);
+    h->ent_seg = seg;
+    return CDC_OK;
+}
+
 int cdc_entropy_decode(cdc_handle *h, const unsigned char *in, const size_t *offsets, const float *medians, int B,
                        float *q_latent, float *q_hyper_latent, int mem, void *stream) {
-    return no_throw(h, [&] { return entropy_decode_impl(h, in, offsets, medians, B, q_latent, q_hyper_latent, mem, stream); });
+    return no_throw(h, [&] { return entropy_decode_impl(h, in, offsets, medians, B, nullptr, q_latent, q_hyper_latent, nullptr, mem, stream); });
+}
+
+int cdc_entropy_decode_window(cdc_handle *h, const unsigned char *in, const size_t *offsets, const float *medians, int B, const int32_t window[4],
+                              float *q_latent, float *q_hyper_latent, int *segments_decoded, int mem, void *stream) {
+    return no_throw(h, [&]() -> int {
+        if (h && !window) return fail(h, CDC_ERR_INVALID, "null/invalid argument");
+        return entropy_decode_impl(h, in, offsets, medians, B, window, q_latent, q_hyper_latent, segments_decoded, mem, stream);
+    });
 }
 
 }  // extern "C"

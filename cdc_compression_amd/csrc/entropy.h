@@ -116,4 +116,37 @@ struct RansPack {
 };
 hipError_t rans_pack_launch(const RansPack &P, int B, hipStream_t st);
 
+// ---- segmented latent part (container versions 11 - 14; see entropy.hip) -----------------------------------------------------
+// One table serves every image of a call (they share the latent grid [C][Hl][Wl]): segment s = window [y0, y0 + h) x [x0, x0 + w),
+// all channels, n = C h w symbols in order (c, y, x), which start at `off` in segment order (raster order of segments).
+struct SegEntry { int y0, x0, h, w, off, n; };
+struct SegWindow { int y0, x0, h, w; };             // latent positions; a segment is selected when it intersects the window
+struct SegTotal { unsigned long long bytes; uint32_t esc, checksum; };      // per image, over its segments' sections
+struct SegJob { long long off; int len, esc, b, s; };                       // decoder: section of segment s of image b in the input
+// Encoder: sym / bin in frame order [B][nl] -> sf, ew in segment order; segment s of image b is coded into its own 2 n + 256 bytes at
+// out[b * out_bs + 2 off + 256 s ..] (out_bs >= 2 nl + 256 S), its payloads into esc[b * nl + off .. + n); meta[b * S + s] =
+// {start, esc_start (both within the segment's own area), checksum over the indices in the full section}; tot[b]: the sums.
+hipError_t seg_encode_launch(EntropyDev T, const SegEntry *tab, int S, int max_n, const int32_t *sym, const uint8_t *bin, long long nl, int Hl,
+                             int Wl, int tab0, int B, uint32_t *sf, uint32_t *ew, uint8_t *out, long long out_bs, uint32_t *esc, RansMeta *meta,
+                             SegTotal *tot, hipStream_t st);
+// rans_pack_launch of segmented streams: base.sec_l / esc_l / out_bs_l / esc_bs_l are seg_encode_launch's out / esc / out_bs / nl,
+// base.meta_l is unused; seg_at: scratch, B * ny * nx entries.
+struct SegPack {
+    RansPack base;
+    const SegEntry *tab;
+    const RansMeta *meta;
+    const SegTotal *tot;
+    long long *seg_at;
+    int seg, ny, nx;
+};
+hipError_t seg_pack_launch(const SegPack &P, int B, hipStream_t st);
+// Decoder: bins of the selected segments into segment order; one wave per job -> sym_seg (segment order), meta[job].bad;
+// then every frame position gets its symbol (0 in a segment that was not selected) and sums[b * S + s] the segment's checksum.
+hipError_t seg_gather_bins_launch(const SegEntry *tab, int S, int max_n, SegWindow win, const uint8_t *bin, long long nl, int Hl, int Wl, int B,
+                                  uint8_t *bin_seg, hipStream_t st);
+hipError_t seg_decode_launch(EntropyDev T, const SegEntry *tab, const SegJob *jobs, int n_jobs, const uint8_t *in, const uint8_t *bin_seg, long long nl,
+                             int tab0, int32_t *sym_seg, RansMeta *meta, hipStream_t st);
+hipError_t seg_scatter_launch(const SegEntry *tab, int S, int max_n, SegWindow win, const int32_t *sym_seg, long long nl, int Hl, int Wl, int B,
+                              int32_t *sym, uint32_t *sums, hipStream_t st);
+
 }  // namespace cdc

@@ -271,7 +271,19 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
     return v;
 }
 
-// (start | freq << 16) and the escape payload of every symbol, plus the section's checksum (atomicAdd: commutative)
+// (start | freq << 16) and the escape payload of symbol k under table t
+__device__ __forceinline__ void rans_lookup(EntropyDev T, int t, int k, uint32_t *sf, uint32_t *ew) {
+    const int K = T.K[t];
+    const uint32_t *c = T.cum + T.off[t];
+    const bool in = k >= -K && k <= K;
+    const int en = in ? k + K : 2 * K + 1;
+    const uint32_t st = c[en], f = c[en + 1] - st;
+    *sf = st | (f << 16);                                     // f <= 65535: every table has >= 2 entries of frequency >= 1
+    const long long mag = k < 0 ? -(long long)k : (long long)k;
+    *ew = in ? 0u : ((uint32_t)(mag - K - 1) << 1) | (k < 0 ? 1u : 0u);
+}
+
+// ... of every symbol, plus the section's checksum (atomicAdd: commutative)
 __global__ void __launch_bounds__(256) rans_prepare_kernel(EntropyDev T, const int32_t *sym, long long sym_bs, const uint8_t *bin, long long bin_bs,
                                                            int per, int tab0, int N, uint32_t sect, uint32_t *sf, uint32_t *ew, RansMeta *meta) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -279,28 +291,18 @@ __global__ void __launch_bounds__(256) rans_prepare_kernel(EntropyDev T, const i
     uint32_t mix = 0;
     if (i < N) {
         const int k = sym[b * sym_bs + i];
-        const int t = tab0 + (per ? i / per : (int)bin[b * bin_bs + i]);
-        const int K = T.K[t];
-        const uint32_t *c = T.cum + T.off[t];
-        const bool in = k >= -K && k <= K;
-        const int en = in ? k + K : 2 * K + 1;
-        const uint32_t st = c[en], f = c[en + 1] - st;
-        sf[b * N + i] = st | (f << 16);                       // f <= 65535: every table has >= 2 entries of frequency >= 1
-        const long long mag = k < 0 ? -(long long)k : (long long)k;
-        ew[b * N + i] = in ? 0u : ((uint32_t)(mag - K - 1) << 1) | (k < 0 ? 1u : 0u);
+        rans_lookup(T, tab0 + (per ? i / per : (int)bin[b * bin_bs + i]), k, &sf[b * N + i], &ew[b * N + i]);
         mix = sym_mix(sect, (uint32_t)i, k);
     }
     mix = wave_sum(mix);
     if ((threadIdx.x & 63) == 0 && mix) atomicAdd(&meta[b].checksum, mix);
 }
 
-__global__ void __launch_bounds__(64) rans_encode_kernel(const uint32_t *sf, const uint32_t *ew, int N, uint8_t *out, long long out_bs,
-                                                         uint32_t *esc, long long esc_bs, RansMeta *meta) {
+// one section by one wave: N symbols' (start | freq << 16) words sf and escape words ew -> o[0 .. out_bs) filled from the end,
+// payloads eo[0 .. esc_bs) likewise; m = {start, esc_start}
+__device__ __forceinline__ void rans_encode_section(const uint32_t *sf, const uint32_t *ew, int N, uint8_t *o, long long out_bs, uint32_t *eo,
+                                                    long long esc_bs, RansMeta *m) {
     const int lane = threadIdx.x;
-    const long long b = blockIdx.x;
-    sf += b * N; ew += b * N;
-    uint8_t *o = out + b * out_bs;
-    uint32_t *eo = esc + b * esc_bs;
     const uint64_t above = lane == 63 ? 0ull : ~((2ull << lane) - 1ull), below = (1ull << lane) - 1ull;
     uint32_t x = 1u << 23;
     long long pos = out_bs, epos = esc_bs;
@@ -342,23 +344,28 @@ __global__ void __launch_bounds__(64) rans_encode_kernel(const uint32_t *sf, con
     }
     pos -= 256;
     for (int k = 0; k < 4; ++k) o[pos + 4 * lane + k] = (uint8_t)(x >> (8 * k));
-    if (lane == 0) { meta[b].start = (int)pos; meta[b].esc_start = (int)epos; }
+    if (lane == 0) { m->start = (int)pos; m->esc_start = (int)epos; }
 }
 
-__global__ void __launch_bounds__(64) rans_decode_kernel(EntropyDev T, const uint8_t *in, const long long *in_off, const int *in_len, const int *in_esc,
-                                                         const uint8_t *bin, long long bin_bs, int per, int tab0, int N, uint32_t sect,
-                                                         int32_t *sym, long long sym_bs, RansMeta *meta) {
-    const int lane = threadIdx.x;
+__global__ void __launch_bounds__(64) rans_encode_kernel(const uint32_t *sf, const uint32_t *ew, int N, uint8_t *out, long long out_bs,
+                                                         uint32_t *esc, long long esc_bs, RansMeta *meta) {
     const long long b = blockIdx.x;
-    const uint8_t *s = in + in_off[b];
-    const long long nbytes = in_len[b], ne = (uint32_t)in_esc[b];
-    if (nbytes < 256 + 4 * ne) { if (lane == 0) { meta[b].bad = 1; meta[b].checksum = 0; } return; }
+    rans_encode_section(sf + b * N, ew + b * N, N, out + b * out_bs, out_bs, esc + b * esc_bs, esc_bs, meta + b);
+}
+
+// one section s[0 .. nbytes) with ne escape payloads by one wave -> sym[0 .. N); the table of symbol i is tab0 + (per ? i / per : bin[i]).
+// kSum: the section's checksum over (sect, i, symbol) is accumulated on the way (a segment's is taken where its symbols get their
+// index in the full section: seg_scatter_kernel).  m = {checksum, bad}
+template <bool kSum>
+__device__ __forceinline__ void rans_decode_section(EntropyDev T, const uint8_t *s, long long nbytes, long long ne, const uint8_t *bin, int per,
+                                                    int tab0, int N, uint32_t sect, int32_t *sym, RansMeta *m) {
+    const int lane = threadIdx.x;
+    if (nbytes < 256 + 4 * ne) { if (lane == 0) { m->bad = 1; m->checksum = 0; } return; }
     const uint64_t below = (1ull << lane) - 1ull;
     uint32_t x = (uint32_t)s[4 * lane] | ((uint32_t)s[4 * lane + 1] << 8) | ((uint32_t)s[4 * lane + 2] << 16) | ((uint32_t)s[4 * lane + 3] << 24);
     long long p = 256, eidx = 0;
     const long long end = nbytes - 4 * ne;
     const uint8_t *ep = s + end;
-    bin += b * bin_bs; sym += b * sym_bs;
     bool bad = false;
     uint32_t csum = 0;
     const int nit = (N + 63) / 64;
@@ -413,13 +420,20 @@ __global__ void __launch_bounds__(64) rans_decode_kernel(EntropyDev T, const uin
                 }
                 eidx += __popcll(me);
             }
-            if (act && !lb) { sym[i] = k; csum += sym_mix(sect, (uint32_t)i, k); }
+            if (act && !lb) { sym[i] = k; if (kSum) csum += sym_mix(sect, (uint32_t)i, k); }
             if (__ballot(lb)) { bad = true; break; }
         }
     }
     if (!bad) bad = p != end || eidx != ne || __ballot(x != (1u << 23)) != 0;
-    csum = wave_sum(csum);
-    if (lane == 0) { meta[b].bad = bad ? 1 : 0; meta[b].checksum = csum; }
+    if (kSum) csum = wave_sum(csum);
+    if (lane == 0) { m->bad = bad ? 1 : 0; m->checksum = csum; }
+}
+
+__global__ void __launch_bounds__(64) rans_decode_kernel(EntropyDev T, const uint8_t *in, const long long *in_off, const int *in_len, const int *in_esc,
+                                                         const uint8_t *bin, long long bin_bs, int per, int tab0, int N, uint32_t sect,
+                                                         int32_t *sym, long long sym_bs, RansMeta *meta) {
+    const long long b = blockIdx.x;
+    rans_decode_section<true>(T, in + in_off[b], in_len[b], (uint32_t)in_esc[b], bin + b * bin_bs, per, tab0, N, sect, sym + b * sym_bs, meta + b);
 }
 
 hipError_t rans_encode_launch(EntropyDev T, const int32_t *sym, long long sym_bs, const uint8_t *bin, long long bin_bs, int per, int tab0,
@@ -483,6 +497,225 @@ __global__ void __launch_bounds__(256) rans_pack_kernel(RansPack P) {
 
 hipError_t rans_pack_launch(const RansPack &P, int B, hipStream_t st) {
     hipLaunchKernelGGL(rans_pack_kernel, dim3((unsigned)B), dim3(256), 0, st, P);
+    return hipGetLastError();
+}
+
+// ---- segmented latent part (include/cdc_hip.h: container versions 11 - 14) ---------------------------------------------------------
+// The latent section is cut into n_seg independent sections, one per seg x seg window of the latent grid (all channels, order
+// (c, y, x) inside the window): one wave per (segment, image) instead of one wave per image.  Everything per symbol that needs the
+// symbol's place in the frame -- the gather into segment order, the scatter back, the checksum over the index IN THE FULL SECTION --
+// runs in parallel kernels over (position in segment, segment, image); the serial waves see plain sections.
+// Symbol j of segment e -> its index in the full latent section [C][Hl][Wl]
+__device__ __forceinline__ long long seg_frame_index(const SegEntry &e, int j, int Hl, int Wl) {
+    const int hw = e.h * e.w, c = j / hw, r = j - c * hw, y = r / e.w, x = r - y * e.w;
+    return ((long long)c * Hl + (e.y0 + y)) * Wl + e.x0 + x;
+}
+__device__ __forceinline__ bool seg_selected(const SegEntry &e, SegWindow w) {
+    return e.y0 < w.y0 + w.h && w.y0 < e.y0 + e.h && e.x0 < w.x0 + w.w && w.x0 < e.x0 + e.w;
+}
+
+// rans_prepare_kernel of the latent section in segment order: grid (blocks of the largest segment, n_seg, B)
+__global__ void __launch_bounds__(256) seg_prepare_kernel(EntropyDev T, const SegEntry *tab, const int32_t *sym, const uint8_t *bin, long long nl,
+                                                          int Hl, int Wl, int tab0, uint32_t *sf, uint32_t *ew, RansMeta *meta, SegTotal *tot) {
+    const SegEntry e = tab[blockIdx.y];
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (blockIdx.x * 256 >= e.n) return;                       // (whole workgroups only: the waves below sum over all their lanes)
+    const long long b = blockIdx.z;
+    uint32_t mix = 0;
+    if (j < e.n) {
+        const long long i = seg_frame_index(e, j, Hl, Wl), d = b * nl + e.off + j;
+        const int k = sym[b * nl + i];
+        rans_lookup(T, tab0 + (int)bin[b * nl + i], k, &sf[d], &ew[d]);
+        mix = sym_mix(1u, (uint32_t)i, k);
+    }
+    mix = wave_sum(mix);
+    if ((threadIdx.x & 63) == 0 && mix) {
+        atomicAdd(&meta[b * gridDim.y + blockIdx.y].checksum, mix);
+        atomicAdd(&tot[b].checksum, mix);
+    }
+}
+
+// one wave per (segment, image): segment s of image b is written back to front into its own 2 n + 256 bytes of out
+__global__ void __launch_bounds__(64) seg_encode_kernel(const SegEntry *tab, const uint32_t *sf, const uint32_t *ew, long long nl, uint8_t *out,
+                                                        long long out_bs, uint32_t *esc, RansMeta *meta, SegTotal *tot) {
+    const int s = blockIdx.x, S = gridDim.x;
+    const long long b = blockIdx.y;
+    const SegEntry e = tab[s];
+    const long long cap = 2ll * e.n + 256;
+    RansMeta *m = meta + b * S + s;
+    rans_encode_section(sf + b * nl + e.off, ew + b * nl + e.off, e.n, out + b * out_bs + 2ll * e.off + 256ll * s, cap, esc + b * nl + e.off, e.n, m);
+    if (threadIdx.x == 0) {                                    // (the values this lane has just stored)
+        const uint32_t ne = (uint32_t)(e.n - m->esc_start);
+        atomicAdd(&tot[b].bytes, (unsigned long long)(cap - m->start) + 4ull * ne);
+        atomicAdd(&tot[b].esc, ne);
+    }
+}
+
+// rans_pack_kernel of a segmented stream, first half: one workgroup per image writes the header, the hyper section, the 8-byte
+// segment header and the index, and leaves every segment's place in the stream in P.seg_at (a workgroup scan over the sizes)
+__global__ void __launch_bounds__(256) seg_pack_index_kernel(SegPack P) {
+    __shared__ unsigned long long wave_tot[4];
+    const RansPack &Q = P.base;
+    const int b = blockIdx.x, S = P.ny * P.nx;
+    const bool sized = Q.img_h > 0;
+    const int hdr = (Q.rates ? 38 : 34) + (sized ? 8 : 0);
+    const unsigned long long fixed = 8ull + 12ull * S;
+    auto hyper = [&](int i, uint32_t *nh, uint32_t *eh) {
+        *eh = (uint32_t)(Q.esc_bs_h - Q.meta_h[i].esc_start);
+        *nh = (uint32_t)(Q.out_bs_h - Q.meta_h[i].start) + 4u * *eh;
+    };
+    uint32_t nh, eh;
+    long long off = 0;
+    for (int i = 0; i < b; ++i) { hyper(i, &nh, &eh); off += hdr + (long long)nh + (long long)(fixed + P.tot[i].bytes); }
+    hyper(b, &nh, &eh);
+    const unsigned long long nl = fixed + P.tot[b].bytes;
+    const long long end = off + hdr + (long long)nh + (long long)nl;
+    if (threadIdx.x == 0) {
+        Q.offsets[b] = off;
+        if (b == (int)gridDim.x - 1) Q.offsets[b + 1] = end;
+    }
+    if (end > Q.cap) return;                                   // the host sees the total in offsets[B] and reports it
+    // (nl fits 32 bits: at most 2^29 symbols of <= 6 bytes and 65535 segments of 268 bytes more)
+    uint8_t *o = Q.out + off;
+    if (threadIdx.x == 0) {
+        const uint32_t w[6] = {nh, (uint32_t)nl, Q.model, Q.meta_h[b].checksum + P.tot[b].checksum, eh, P.tot[b].esc};
+        o[0] = 'C'; o[1] = 'D'; o[2] = 'C'; o[3] = 8 + (Q.rates ? 4 : 3) + (sized ? 2 : 0); o[4] = (uint8_t)Q.arith; o[5] = 0;
+        o[6] = (uint8_t)(Q.hh & 255); o[7] = (uint8_t)(Q.hh >> 8); o[8] = (uint8_t)(Q.wh & 255); o[9] = (uint8_t)(Q.wh >> 8);
+        for (int k = 0; k < 6; ++k) for (int q = 0; q < 4; ++q) o[10 + 4 * k + q] = (uint8_t)(w[k] >> (8 * q));
+        if (Q.rates) { const uint32_t r = __float_as_uint(Q.rates[b]); for (int q = 0; q < 4; ++q) o[34 + q] = (uint8_t)(r >> (8 * q)); }
+        if (sized) for (int q = 0; q < 4; ++q) { o[hdr - 8 + q] = (uint8_t)((uint32_t)Q.img_h >> (8 * q)); o[hdr - 4 + q] = (uint8_t)((uint32_t)Q.img_w >> (8 * q)); }
+    }
+    o += hdr;
+    const uint8_t *sh = Q.sec_h + (long long)b * Q.out_bs_h + Q.meta_h[b].start;
+    const uint32_t *xh = Q.esc_h + (long long)b * Q.esc_bs_h + Q.meta_h[b].esc_start;
+    const uint32_t bh = nh - 4u * eh;
+    for (uint32_t i = threadIdx.x; i < bh; i += 256) o[i] = sh[i];
+    for (uint32_t i = threadIdx.x; i < 4u * eh; i += 256) o[bh + i] = (uint8_t)(xh[i >> 2] >> (8 * (i & 3)));
+    o += nh;
+    if (threadIdx.x == 0) {
+        const uint16_t w[4] = {(uint16_t)P.seg, (uint16_t)P.ny, (uint16_t)P.nx, 0};
+        for (int k = 0; k < 4; ++k) { o[2 * k] = (uint8_t)(w[k] & 255); o[2 * k + 1] = (uint8_t)(w[k] >> 8); }
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long carry = (unsigned long long)(off + hdr + nh) + fixed;      // where segment 0 starts in P.out
+    for (int s0 = 0; s0 < S; s0 += 256) {
+        const int s = s0 + threadIdx.x;
+        uint32_t bytes = 0, ne = 0, sum = 0;
+        if (s < S) {
+            const RansMeta m = P.meta[(long long)b * S + s];
+            const int n = P.tab[s].n;
+            ne = (uint32_t)(n - m.esc_start);
+            bytes = (uint32_t)(2ll * n + 256 - m.start) + 4u * ne;
+            sum = m.checksum;
+        }
+        unsigned long long inc = bytes;                        // inclusive scan: the wave, then the four wave totals
+        for (int d = 1; d < 64; d <<= 1) { const unsigned long long v = __shfl_up(inc, d, 64); if (lane >= d) inc += v; }
+        if (lane == 63) wave_tot[wave] = inc;
+        __syncthreads();
+        unsigned long long before = carry, all = 0;
+        for (int w = 0; w < 4; ++w) { if (w < wave) before += wave_tot[w]; all += wave_tot[w]; }
+        __syncthreads();
+        if (s < S) {
+            P.seg_at[(long long)b * S + s] = (long long)(before + inc - bytes);
+            uint8_t *ix = o + 8 + 12ll * s;
+            const uint32_t w[3] = {bytes, ne, sum};
+            for (int k = 0; k < 3; ++k) for (int q = 0; q < 4; ++q) ix[4 * k + q] = (uint8_t)(w[k] >> (8 * q));
+        }
+        carry += all;
+    }
+}
+
+// second half: one workgroup per (segment, image) copies the segment's section to its place
+__global__ void __launch_bounds__(256) seg_pack_copy_kernel(SegPack P) {
+    const RansPack &Q = P.base;
+    const int s = blockIdx.x, S = gridDim.x;
+    const long long b = blockIdx.y;
+    if (Q.offsets[b + 1] > Q.cap) return;                      // image b's end: seg_pack_index_kernel wrote nothing for it either
+    const RansMeta m = P.meta[b * S + s];
+    const SegEntry e = P.tab[s];
+    const uint32_t ne = (uint32_t)(e.n - m.esc_start), nb = (uint32_t)(2ll * e.n + 256 - m.start);
+    const uint8_t *src = Q.sec_l + b * Q.out_bs_l + 2ll * e.off + 256ll * s + m.start;
+    const uint32_t *xs = Q.esc_l + b * Q.esc_bs_l + e.off + m.esc_start;
+    uint8_t *o = Q.out + P.seg_at[b * S + s];
+    for (uint32_t i = threadIdx.x; i < nb; i += 256) o[i] = src[i];
+    for (uint32_t i = threadIdx.x; i < 4u * ne; i += 256) o[nb + i] = (uint8_t)(xs[i >> 2] >> (8 * (i & 3)));
+}
+
+hipError_t seg_encode_launch(EntropyDev T, const SegEntry *tab, int S, int max_n, const int32_t *sym, const uint8_t *bin, long long nl, int Hl,
+                             int Wl, int tab0, int B, uint32_t *sf, uint32_t *ew, uint8_t *out, long long out_bs, uint32_t *esc, RansMeta *meta,
+                             SegTotal *tot, hipStream_t st) {
+    hipError_t e = hipMemsetAsync(meta, 0, sizeof(RansMeta) * (size_t)B * S, st);
+    if (e != hipSuccess) return e;
+    if ((e = hipMemsetAsync(tot, 0, sizeof(SegTotal) * (size_t)B, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(seg_prepare_kernel, dim3((unsigned)((max_n + 255) / 256), (unsigned)S, (unsigned)B), dim3(256), 0, st, T, tab, sym, bin, nl,
+                       Hl, Wl, tab0, sf, ew, meta, tot);
+    hipLaunchKernelGGL(seg_encode_kernel, dim3((unsigned)S, (unsigned)B), dim3(64), 0, st, tab, sf, ew, nl, out, out_bs, esc, meta, tot);
+    return hipGetLastError();
+}
+
+hipError_t seg_pack_launch(const SegPack &P, int B, hipStream_t st) {
+    hipLaunchKernelGGL(seg_pack_index_kernel, dim3((unsigned)B), dim3(256), 0, st, P);
+    hipLaunchKernelGGL(seg_pack_copy_kernel, dim3((unsigned)(P.ny * P.nx), (unsigned)B), dim3(256), 0, st, P);
+    return hipGetLastError();
+}
+
+// the scale bins of the selected segments in segment order (the decoder's waves then read bin[j] as a plain section does)
+__global__ void __launch_bounds__(256) seg_gather_bins_kernel(const SegEntry *tab, SegWindow win, const uint8_t *bin, long long nl, int Hl, int Wl,
+                                                              uint8_t *bin_seg) {
+    const SegEntry e = tab[blockIdx.y];
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= e.n || !seg_selected(e, win)) return;
+    const long long b = blockIdx.z;
+    bin_seg[b * nl + e.off + j] = bin[b * nl + seg_frame_index(e, j, Hl, Wl)];
+}
+
+// one wave per selected (segment, image)
+__global__ void __launch_bounds__(64) seg_decode_kernel(EntropyDev T, const SegEntry *tab, const SegJob *jobs, const uint8_t *in, const uint8_t *bin_seg,
+                                                        long long nl, int tab0, int32_t *sym_seg, RansMeta *meta) {
+    const SegJob q = jobs[blockIdx.x];
+    const SegEntry e = tab[q.s];
+    const long long base = (long long)q.b * nl + e.off;
+    rans_decode_section<false>(T, in + q.off, q.len, (uint32_t)q.esc, bin_seg + base, 0, tab0, e.n, 1u, sym_seg + base, meta + blockIdx.x);
+}
+
+// segment order -> frame order, 0 where the segment was not selected; sums[b][s] += the checksum of a selected segment's symbols
+__global__ void __launch_bounds__(256) seg_scatter_kernel(const SegEntry *tab, SegWindow win, const int32_t *sym_seg, long long nl, int Hl, int Wl,
+                                                          int32_t *sym, uint32_t *sums) {
+    const SegEntry e = tab[blockIdx.y];
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (blockIdx.x * 256 >= e.n) return;
+    const long long b = blockIdx.z;
+    const bool sel = seg_selected(e, win);
+    uint32_t mix = 0;
+    if (j < e.n) {
+        const long long i = seg_frame_index(e, j, Hl, Wl);
+        const int k = sel ? sym_seg[b * nl + e.off + j] : 0;
+        sym[b * nl + i] = k;
+        if (sel) mix = sym_mix(1u, (uint32_t)i, k);
+    }
+    mix = wave_sum(mix);
+    if ((threadIdx.x & 63) == 0 && mix) atomicAdd(&sums[b * gridDim.y + blockIdx.y], mix);
+}
+
+hipError_t seg_gather_bins_launch(const SegEntry *tab, int S, int max_n, SegWindow win, const uint8_t *bin, long long nl, int Hl, int Wl, int B,
+                                  uint8_t *bin_seg, hipStream_t st) {
+    hipLaunchKernelGGL(seg_gather_bins_kernel, dim3((unsigned)((max_n + 255) / 256), (unsigned)S, (unsigned)B), dim3(256), 0, st, tab, win, bin, nl, Hl,
+                       Wl, bin_seg);
+    return hipGetLastError();
+}
+
+hipError_t seg_decode_launch(EntropyDev T, const SegEntry *tab, const SegJob *jobs, int n_jobs, const uint8_t *in, const uint8_t *bin_seg, long long nl,
+                             int tab0, int32_t *sym_seg, RansMeta *meta, hipStream_t st) {
+    hipLaunchKernelGGL(seg_decode_kernel, dim3((unsigned)n_jobs), dim3(64), 0, st, T, tab, jobs, in, bin_seg, nl, tab0, sym_seg, meta);
+    return hipGetLastError();
+}
+
+hipError_t seg_scatter_launch(const SegEntry *tab, int S, int max_n, SegWindow win, const int32_t *sym_seg, long long nl, int Hl, int Wl, int B,
+                              int32_t *sym, uint32_t *sums, hipStream_t st) {
+    hipError_t e = hipMemsetAsync(sums, 0, sizeof(uint32_t) * (size_t)B * S, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(seg_scatter_kernel, dim3((unsigned)((max_n + 255) / 256), (unsigned)S, (unsigned)B), dim3(256), 0, st, tab, win, sym_seg, nl, Hl,
+                       Wl, sym, sums);
     return hipGetLastError();
 }
 

@@ -144,14 +144,16 @@ class _GaussianDiffusionBase:
                                            optr, omem, _current_stream(omem)))
         return out
 
-    def _rdo_of(self, images, bitrate_scale=None, rdo=None, target_bpp=None, max_bytes=None, price_map=None, price_cells=None):
+    def _rdo_of(self, images, bitrate_scale=None, rdo=None, target_bpp=None, max_bytes=None, price_map=None, price_cells=None, segment=None):
         """The rate-control arguments of compress / compress_best_of / compress_to_bytes, checked before the library is touched ->
         (mu, cells): the context model's mu (float32, 1 or B values) or None, and its price map on the latent grid of the frame the
         U-Net asks for (float32 host [1 or B, gh, gw]) or None.  target_bpp / max_bytes: the context model chooses mu as its
         compress_to_bytes does (compressor.py) -- under the map, when there is one -- and forward(rdo=mu, price_cells=cells) then
-        runs with both."""
+        runs with both.  segment: the segment size of the streams `compress_to_bytes(segment=)` would write (image pixels): max_bytes
+        counts their larger container; it changes no symbol otherwise."""
         from . import compressor
         compressor.rdo_exclusive(rdo, target_bpp, max_bytes)
+        self._segment_arg(segment)
         B, _, H, W = frame.image_shape(images)
         if rdo is not None:
             mu = compressor.rdo_values(rdo, B)
@@ -170,9 +172,21 @@ class _GaussianDiffusionBase:
         if self.padded_size(H, W) != self.context_fn.padded_size(H, W):
             raise NotImplementedError("target_bpp / max_bytes choose mu on the context model's own frame: a U-Net that needs a larger one "
                                       f"({self.padded_size(H, W)} against {self.context_fn.padded_size(H, W)}) cannot share it")
+        kw = {} if segment is None else {"segment": segment}
         _, info = self.context_fn.compress_to_bytes(images, bitrate_scale, target_bpp=target_bpp, max_bytes=max_bytes, return_info=True,
-                                                    price_cells=cells)
+                                                    price_cells=cells, **kw)
         return info["mu"], cells
+
+    def _segment_arg(self, segment):
+        """The argument rule of segment= (compressor.segment_positions), checked before the library is touched: a stream is cut by a
+        context model of this package, never by a callable that only returns a context pyramid."""
+        from . import compressor
+        if segment is None:
+            return
+        if not hasattr(self.context_fn, "segments_of"):
+            raise ValueError("segment needs a context model of this package (its entropy coder writes the streams): a context_fn that only "
+                             "returns a context pyramid has no stream to cut")
+        compressor.segment_positions(segment, self.context_fn.rate_map_cell)
 
     def _context_of(self, images, *ctx_args, rate_map=False, rdo=None, price_cells=None):
         """The context model on the padded frame of `images` -> (context_dict with bpp over H * W, B, H, W, Hp, Wp).  rate_map: the
@@ -469,6 +483,8 @@ class _GaussianDiffusionBase:
         tile_overlap: multiples of the frame multiple `padded_size(1, 1)[0]`, ints or (h, w) pairs, 0 < overlap <= tile / 2 (default: the
         multiple); tile_chunk: rows (tiles of all images) per sampler call (default: the fewest calls of at most 32 rows);
         region=(y0, x0, h, w) in image pixels: decodes the tiles that intersect it -> (that window, {"tiles", "tiles_decoded", "region"}).
+        Of segmented streams (compress_to_bytes(segment=)) only the segments under those tiles are entropy-decoded, and the dict also
+        holds "segments" and "segments_decoded" (per image).
         Excludes samples=, trajectory= and a context pyramid; eta != 0 needs a seed."""
         tile_hw, overlap_hw = _tiles.check_args(tile, tile_overlap, tile_chunk, region, samples, trajectory)
         if tile_hw is not None:
@@ -485,15 +501,24 @@ class _GaussianDiffusionBase:
         if samples is None and (reduce is not None or sample_chunk is not None):
             raise ValueError("reduce / sample_chunk belong to samples=K")
         K = None if samples is None else _samples.check_args(samples, seed, gamma, eta, init, reduce, as_uint8, sample_chunk)
-        recorded = None
+        recorded = seg_info = None
         if isinstance(context, (bytes, bytearray)):
             context = [context]
         if isinstance(context, (list, tuple)) and context and isinstance(context[0], (bytes, bytearray)):
             # entropy-coded bitstreams (compress_to_bytes): range-ANS decode -> q_latent (+ the rates of a VBR model)
             if bitrate_scale is not None:
                 raise ValueError("the streams carry their own bitrate_scale")
-            context, bitrate_scale, recorded = self.context_fn.decompress_from_bytes(context, like=init, return_bitrate_scale=True,
-                                                                                     return_image_size=True)
+            # a region of segmented streams: the tiles are planned from the peeked sizes first, and only the segments under the
+            # selected tiles' latent windows are entropy-decoded (unsegmented streams: the call and the info dict of always)
+            cut = tile_hw is not None and region is not None and hasattr(self.context_fn, "segments_of") and \
+                self.context_fn.segments_of(context[:1])[0][0] > 0
+            if cut:
+                win = self._stream_window(context[0], tile_hw, overlap_hw, region)
+                context, bitrate_scale, recorded, seg_info = self.context_fn.decompress_from_bytes(
+                    context, like=init, return_bitrate_scale=True, return_image_size=True, window=win, return_segments=True)
+            else:
+                context, bitrate_scale, recorded = self.context_fn.decompress_from_bytes(context, like=init, return_bitrate_scale=True,
+                                                                                         return_image_size=True)
         if not isinstance(context, (list, tuple)):
             if self.context_fn is None or not hasattr(self.context_fn, "decode"):
                 raise RuntimeError("decompress(q_latent, ...) needs a context_fn with decode()")
@@ -501,6 +526,8 @@ class _GaussianDiffusionBase:
                 res = self._decompress_tiled(context, bitrate_scale, recorded, shape, tile_hw, overlap_hw, tile_chunk, region, sample_steps, init,
                                              eta, clip_denoised, as_uint8, seed, gamma, sampler, spacing)
                 if res is not None:
+                    if seg_info is not None:
+                        res[1].update(segments=seg_info[0], segments_decoded=seg_info[1])
                     return res
             context = self.context_fn.decode(context) if bitrate_scale is None else self.context_fn.decode(context, bitrate_scale)
         if K is None:
@@ -528,6 +555,26 @@ class _GaussianDiffusionBase:
         return rec if traj is None else (rec, traj)
 
     # ---- tiled decode (cdc_compression_amd.tiles) --------------------------------------------------------------------------
+    def _stream_window(self, stream, tile, overlap, region):
+        """The latent window decompress(streams, tile=, region=) needs of the streams' q_latent: the bounding box of the selected
+        tiles' latent windows (y0, x0, h, w in latent positions), planned from the sizes the stream's header holds as
+        `_decompress_tiled` plans them from the q_latent; None when one tile covers the frame (the plain path decodes it whole)."""
+        cf = self.context_fn
+        cell = 1 << len(cf.rev_mults)
+        H, W = cf.image_size_of([stream], cf.frame_multiple)[0]
+        hh, wh = ctypes.c_int(), ctypes.c_int()
+        if _lib.lib().cdc_entropy_peek(bytes(stream), len(stream), ctypes.byref(hh), ctypes.byref(wh), None) != 0:
+            raise _lib.CdcError("not a CDC bitstream")
+        Hp, Wp = hh.value * cf.frame_multiple, wh.value * cf.frame_multiple
+        window = _tiles.check_region(region, H, W)
+        plan = _tiles.Plan(Hp, Wp, tile, overlap)
+        if plan.T == 1:
+            return None
+        origins = plan.origins(plan.intersecting(window))
+        y0, x0 = min(y for y, _ in origins) // cell, min(x for _, x in origins) // cell
+        y1, x1 = (max(y for y, _ in origins) + plan.th) // cell, (max(x for _, x in origins) + plan.tw) // cell
+        return (y0, x0, y1 - y0, x1 - x0)
+
     def _decompress_tiled(self, q_latent, bitrate_scale, recorded, shape, tile, overlap, tile_chunk, region, sample_steps, init, eta,
                           clip_denoised, as_uint8, seed, gamma, sampler, spacing):
         """decompress(q_latent, tile=...): -> the result, or None when one tile covers the frame and no region is asked for (the caller
@@ -707,14 +754,17 @@ class _GaussianDiffusionBase:
 
 
     def compress_to_bytes(self, images, bitrate_scale=None, rdo=None, target_bpp=None, max_bytes=None, return_info=False,
-                          price_map=None, price_cells=None):
+                          price_map=None, price_cells=None, segment=None):
         """The transmitted half of compress(): images -> one entropy-coded bitstream per image.
         `decompress(streams, shape, sample_steps, init)` reconstructs from them.  bitrate_scale: the rate of a
         variable-bitrate context model (1 or B values), recorded in each stream.  Images of any size: a stream records H x W
         unless the image is its own padded frame.  rdo / target_bpp / max_bytes / return_info: the context model's rate control
-        (compressor.compress_to_bytes), price_map / price_cells its region-of-interest map; the decoder side needs nothing."""
+        (compressor.compress_to_bytes), price_map / price_cells its region-of-interest map; the decoder side needs nothing.
+        segment (image pixels, a multiple of the pixels of a latent position): segmented streams, whose segments code and decode in
+        parallel and of which `decompress(streams, tile=, region=)` entropy-decodes only what the region's tiles need."""
         from . import compressor
         compressor.rdo_exclusive(rdo, target_bpp, max_bytes)
+        self._segment_arg(segment)
         B, _, H, W = frame.image_shape(images)
         if rdo is not None:
             compressor.rdo_values(rdo, B)
@@ -728,6 +778,8 @@ class _GaussianDiffusionBase:
         kw = {k: v for k, v in (("rdo", rdo), ("target_bpp", target_bpp), ("max_bytes", max_bytes)) if v is not None}
         if return_info:
             kw["return_info"] = True
+        if segment is not None:
+            kw["segment"] = segment
         if priced is not None:
             kw["price_map" if priced[0] == "map" else "price_cells"] = priced[1]
         if bitrate_scale is None:
@@ -771,18 +823,19 @@ class GaussianDiffusionX(_GaussianDiffusionBase):
 
     def compress(self, images, sample_steps=None, bpp_return_mean=True, init=None, eta=0, seed=None, gamma=None, sampler="ddim",
                  spacing="index", trajectory=None, trajectory_of="x0", trajectory_dtype="float32", rdo=None, target_bpp=None,
-                 max_bytes=None, price_map=None, price_cells=None, tile=None, tile_overlap=None, tile_chunk=None, region=None):
+                 max_bytes=None, price_map=None, price_cells=None, tile=None, tile_overlap=None, tile_chunk=None, region=None, segment=None):
         """trajectory=: -> (reconstruction, bpp, Trajectory) (cdc_compression_amd.trajectory).  rdo / target_bpp / max_bytes: the
         context model's rate control (compressor.compress_to_bytes); bpp is that of the symbols it chose.  price_map / price_cells
         (with one of them): its region-of-interest map, in pixels at the image's size or on the latent grid.
         tile / tile_overlap / tile_chunk / region: the decode half runs tiled (decompress states them); with a region
-        -> (window, bpp, info)."""
+        -> (window, bpp, info).  segment: the segment size of the streams to be written (compress_to_bytes): max_bytes counts it."""
         if not (tile is None and tile_overlap is None and tile_chunk is None and region is None):
-            return self._compress_tiled(images, (), dict(rdo=rdo, target_bpp=target_bpp, max_bytes=max_bytes, price_map=price_map, price_cells=price_cells),
+            return self._compress_tiled(images, (), dict(rdo=rdo, target_bpp=target_bpp, max_bytes=max_bytes, price_map=price_map, price_cells=price_cells,
+                                                         segment=segment),
                                         bpp_return_mean, dict(tile=tile, tile_overlap=tile_overlap, tile_chunk=tile_chunk, region=region),
                                         sample_steps=sample_steps, init=init, eta=eta, seed=seed, gamma=gamma, sampler=sampler, spacing=spacing,
                                         trajectory=trajectory)
-        mu, cells = self._rdo_of(images, None, rdo, target_bpp, max_bytes, price_map, price_cells)
+        mu, cells = self._rdo_of(images, None, rdo, target_bpp, max_bytes, price_map, price_cells, segment)
         rec, bpp, H, W, traj = self._frame_of(images, sample_steps, init, eta, seed, gamma, sampler, spacing, trajectory, trajectory_of,
                                               trajectory_dtype, rdo=mu, price_cells=cells)
         res = (self._window(rec, H, W), (bpp.mean() if bpp_return_mean else bpp))
@@ -791,14 +844,14 @@ class GaussianDiffusionX(_GaussianDiffusionBase):
 
     def compress_best_of(self, images, samples, metric="psnr", seed=None, gamma=None, eta=0, sample_steps=None, sampler="ddim",
                          spacing="index", sample_chunk=None, as_saved=True, rdo=None, target_bpp=None, max_bytes=None, price_map=None,
-                         price_cells=None, tile=None, tile_overlap=None, tile_chunk=None):
+                         price_cells=None, tile=None, tile_overlap=None, tile_chunk=None, segment=None):
         """The encoder's closed loop: the context model once, then `samples` seeded decodes per image (seeds
         parallel.sample_seeds(seed, B, samples)), each scored on the device against `images` on the frame's H x W window
         (metric "psnr" / "ms_ssim": higher is better; "lpips": lower, needs self.loss_fn_vgg; ties go to the lowest k, a NaN never
         beats a number) -> {"reconstruction": the winner's window, "bpp": [B], "seed": uint64 [B], ready for decompress(..., seed=),
         "sample": int [B], "score": [B], "scores": [B, samples]}.  rdo / target_bpp / max_bytes / price_map / price_cells: as compress().
-        tile / tile_overlap / tile_chunk: every candidate is a tiled decode (decompress states them)."""
-        mu, cells = self._rdo_of(images, None, rdo, target_bpp, max_bytes, price_map, price_cells)
+        tile / tile_overlap / tile_chunk: every candidate is a tiled decode (decompress states them).  segment: as compress()."""
+        mu, cells = self._rdo_of(images, None, rdo, target_bpp, max_bytes, price_map, price_cells, segment)
         return self._best_of(images, samples, metric, seed, gamma, eta, sample_steps, sampler, spacing, sample_chunk, as_saved, True, rdo=mu,
                              price_cells=cells, tile_kw=dict(tile=tile, tile_overlap=tile_overlap, tile_chunk=tile_chunk))
 
@@ -842,18 +895,18 @@ class GaussianDiffusionEps(_GaussianDiffusionBase):
     def compress(self, images, sample_steps=None, bitrate_scale=None, sample_mode="ddpm",
                  bpp_return_mean=True, init=None, eta=0, seed=None, gamma=None, sampler="ddim", spacing="index",
                  trajectory=None, trajectory_of="x0", trajectory_dtype="float32", rdo=None, target_bpp=None, max_bytes=None,
-                 price_map=None, price_cells=None, tile=None, tile_overlap=None, tile_chunk=None, region=None):
+                 price_map=None, price_cells=None, tile=None, tile_overlap=None, tile_chunk=None, region=None, segment=None):
         """trajectory=: -> (reconstruction, bpp, Trajectory) (cdc_compression_amd.trajectory).  rdo / target_bpp / max_bytes /
-        price_map / price_cells / tile / tile_overlap / tile_chunk / region: as GaussianDiffusionX.compress."""
+        price_map / price_cells / tile / tile_overlap / tile_chunk / region / segment: as GaussianDiffusionX.compress."""
         if not (tile is None and tile_overlap is None and tile_chunk is None and region is None):
             if sample_mode != "ddim":
                 raise NotImplementedError('sample_mode "ddpm" raises AttributeError in the reference; only "ddim" is implemented')
             return self._compress_tiled(images, (bitrate_scale,), dict(rdo=rdo, target_bpp=target_bpp, max_bytes=max_bytes, price_map=price_map,
-                                                                      price_cells=price_cells),
+                                                                      price_cells=price_cells, segment=segment),
                                         bpp_return_mean, dict(tile=tile, tile_overlap=tile_overlap, tile_chunk=tile_chunk, region=region),
                                         sample_steps=sample_steps, init=init, eta=eta, seed=seed, gamma=gamma, sampler=sampler, spacing=spacing,
                                         trajectory=trajectory)
-        mu, cells = self._rdo_of(images, bitrate_scale, rdo, target_bpp, max_bytes, price_map, price_cells)
+        mu, cells = self._rdo_of(images, bitrate_scale, rdo, target_bpp, max_bytes, price_map, price_cells, segment)
         rec, bpp, H, W, traj = self._frame_of(images, sample_steps, bitrate_scale, sample_mode, init, eta, seed, gamma, sampler, spacing,
                                               trajectory, trajectory_of, trajectory_dtype, rdo=mu, price_cells=cells)
         res = (self._window(rec, H, W), (bpp.mean() if bpp_return_mean else bpp))
@@ -861,9 +914,9 @@ class GaussianDiffusionEps(_GaussianDiffusionBase):
 
     def compress_best_of(self, images, samples, metric="psnr", seed=None, gamma=None, eta=0, sample_steps=None, sampler="ddim",
                          spacing="index", sample_chunk=None, as_saved=True, bitrate_scale=None, rdo=None, target_bpp=None, max_bytes=None,
-                         price_map=None, price_cells=None, tile=None, tile_overlap=None, tile_chunk=None):
+                         price_map=None, price_cells=None, tile=None, tile_overlap=None, tile_chunk=None, segment=None):
         """GaussianDiffusionX.compress_best_of with this tree's context argument (bitrate_scale of a variable-bitrate model)."""
-        mu, cells = self._rdo_of(images, bitrate_scale, rdo, target_bpp, max_bytes, price_map, price_cells)
+        mu, cells = self._rdo_of(images, bitrate_scale, rdo, target_bpp, max_bytes, price_map, price_cells, segment)
         return self._best_of(images, samples, metric, seed, gamma, eta, sample_steps, sampler, spacing, sample_chunk, as_saved,
                              self.clip_noise, bitrate_scale, rdo=mu, price_cells=cells,
                              tile_kw=dict(tile=tile, tile_overlap=tile_overlap, tile_chunk=tile_chunk))

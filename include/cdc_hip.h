@@ -455,8 +455,9 @@ int cdc_bpp(cdc_handle *h, const float *q_hyper_latent, const float *q_latent, c
  * Synchronous; latent / hyper_latent / q_latent / q_hyper_latent follow `mem`, in / out / offsets / medians are host. */
 int cdc_entropy_encode(cdc_handle *h, const float *latent, const float *hyper_latent, const float *medians, int B,
                        int h_hyper, int w_hyper, unsigned char *out, size_t cap, size_t *offsets, int mem_kind, void *stream);
-/* Header fields of a version-3, -4, -5 or -6 stream (CDC_ERR_INVALID for anything else, a version-5 / -6 header whose recorded
- * image size is 0 or beyond 2^31 - 1 on either side included: every peek below refuses what this one refuses). */
+/* Header fields of a version-3, -4, -5 or -6 stream, or of its segmented form 11 - 14 (below) (CDC_ERR_INVALID for anything else,
+ * a version-5 / -6 header whose recorded image size is 0 or beyond 2^31 - 1 on either side and a segmented stream whose index is
+ * unsound included: every peek below refuses what this one refuses). */
 int cdc_entropy_peek(const unsigned char *in, size_t n, int *h_hyper, int *w_hyper, int *arith);
 /* A stream header sizes the decoder's allocations and its hyper_dec launch program (up to 2^22 positions = a 131072 x 131072
  * image: tens of GB on a 288 GB part).  A caller that knows what it expects bounds that BEFORE decoding untrusted bytes: streams whose
@@ -543,6 +544,46 @@ int cdc_entropy_encode_image(cdc_handle *h, const float *latent, const float *hy
                              int h_hyper, int w_hyper, int img_h, int img_w, unsigned char *out, size_t cap, size_t *offsets,
                              int mem_kind, void *stream);
 int cdc_entropy_peek_image_size(const unsigned char *in, size_t n, int *has_size, int *img_h, int *img_w);
+
+/* ---- segmented streams: container versions 11 - 14 (csrc/entropy.hip: the seg_* kernels) -----------------------------------------
+ * THE FORMAT.  Version 11 / 12 / 13 / 14 = version 3 / 4 / 5 / 6 + 8 (7 and 8 are no stream and stay refused).  The header is that
+ * of the base version byte for byte but for the version byte; the hyper section is unchanged.  n_latent is the size of the whole
+ * latent part (header + n_hyper + n_latent is still the stream's length), esc_latent the sum over the segments, and `symbols` is
+ * the number the unsegmented stream of the same symbols carries.  The latent part:
+ *   seg u16 | ny u16 | nx u16 | 0 u16                          8 bytes (little endian)
+ *   ny nx x ( bytes u32 | esc u32 | checksum u32 )             the index, raster order of segments
+ *   segment 0 | segment 1 | ...                                back to back, raster order
+ * seg = side of a segment in latent positions, 1 .. 65535; ny = ceil(Hl / seg), nx = ceil(Wl / seg) over the Hl x Wl latent grid
+ * (edge segments are smaller), ny nx <= 65535.  Segment (sy, sx) holds the symbols of the window [sy seg, min(Hl, (sy + 1) seg)) x
+ * [sx seg, min(Wl, (sx + 1) seg)), all C channels, in order (c, y, x), c slowest; its bytes are exactly a section (64 lane states,
+ * renormalisation bytes, escape payloads) over those symbols in that order -- symbol j of the segment belongs to lane j % 64.
+ * bytes / esc = its section size and escape count; checksum = sum of mix(1, i, symbol) over its symbols with i the symbol's index
+ * IN THE FULL LATENT SECTION, so that the segment checksums add up to the latent share of `symbols`.
+ * The probability tables, the model fingerprint, hyper_dec over the full frame and the batch = batch-1 contract are unchanged.
+ * cdc_entropy_set_segments: seg = 0 (the default): cdc_entropy_encode / cdc_entropy_encode_image write versions 3 - 6 through the
+ *   launches they always ran; seg = 1 .. 65535 latent positions: versions 11 - 14, n segments coded by n waves (one segment is
+ *   allowed).  CDC_ERR_INVALID when the call's latent grid would be cut into more than 65535 segments.  cdc_set_rdo, cdc_set_rdo_map and the
+ *   rates of a VBR model compose: they change symbols or header fields only.
+ * cdc_entropy_peek, _peek_bitrate_scale and _peek_image_size read versions 11 - 14 as their base versions.
+ * cdc_entropy_peek_segments: handle-free; seg = 0, ny = nx = 1 for versions 3 - 6.  For 11 - 14 everything a reader without a
+ *   handle can check is checked, BY EVERY PEEK: header + n_hyper + n_latent = n; the 8 bytes with 1 <= seg, 1 <= ny nx <= 65535
+ *   and the reserved zero; every index entry has bytes >= 256 + 4 esc; 8 + 12 ny nx + sum bytes = n_latent; sum esc = esc_latent.
+ *   CDC_ERR_INVALID for anything else.
+ * cdc_entropy_decode decodes versions 11 - 14 whole, one wave per (segment, image).  Before anything is allocated ny and nx must be
+ *   ceil(Hl / seg), ceil(Wl / seg) of the handle's own latent grid.  Every segment's end conditions and checksum are checked --
+ *   errors name the image and the segment -- and then the header's `symbols` against hyper sum + the segments' sums.  The
+ *   streams of one call are all unsegmented or all segmented with one seg (CDC_ERR_INVALID otherwise).
+ * cdc_entropy_decode_window: window = (y0, x0, h, w) in latent positions, inside the grid (CDC_ERR_INVALID otherwise).  The hyper
+ *   section and hyper_dec run on the full frame as always; only the segments that intersect the window are decoded and verified
+ *   (*segments_decoded, per image).  q_latent is full-size: equal to the full decode inside those segments, equal to hyper_dec's
+ *   mean elsewhere (symbol 0), bit for bit.  The header's `symbols` is NOT checked -- it cannot be without the rest -- and a corrupt
+ *   segment outside the window is by design not noticed.  An unsegmented stream decodes whole (*segments_decoded = 1), checked
+ *   as cdc_entropy_decode checks it. */
+int cdc_entropy_set_segments(cdc_handle *hyperdec, int seg);
+int cdc_entropy_peek_segments(const unsigned char *in, size_t n, int *seg, int *ny, int *nx);
+int cdc_entropy_decode_window(cdc_handle *h, const unsigned char *in, const size_t *offsets, const float *medians, int B,
+                              const int32_t window[4] /* y0, x0, h, w in latent positions */, float *q_latent, float *q_hyper_latent,
+                              int *segments_decoded, int mem_kind, void *stream);
 
 /* ---- distortion of decoded images: PSNR and MS-SSIM on the device (csrc/metric_kernels.hip) --------------------------------------
  * THE DEFINITION.  Operands: two image batches a, b, each [B][3][Hf][Wf] with Hf >= H, Wf >= W and its own element kind, frame size
