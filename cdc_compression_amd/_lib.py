@@ -140,6 +140,8 @@ def lib():
     L.cdc_entropy_peek_segments.argtypes = [_vp, ctypes.c_size_t, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]
     L.cdc_entropy_decode_window.argtypes = [H, _vp, ctypes.POINTER(ctypes.c_size_t), _vp, _i, ctypes.POINTER(ctypes.c_int32), _vp, _vp,
                                             ctypes.POINTER(_i), _i, _vp]
+    L.cdc_entropy_set_hyper_groups.argtypes = [H, _i]
+    L.cdc_entropy_peek_hyper_groups.argtypes = [_vp, ctypes.c_size_t, ctypes.POINTER(_i), ctypes.POINTER(_i)]
     f64p = ctypes.POINTER(ctypes.c_double)
     L.cdc_distortion.argtypes = [H, ctypes.POINTER(ImageView), ctypes.POINTER(ImageView), _i, _i, _i, _i, f64p, f64p, f64p, _i, _vp]
     L.cdc_rate_map.argtypes = [H] + [_vp] * 9 + [_i, _i, _i, _i, _vp]
@@ -230,7 +232,8 @@ EXPORTS = ["cdc_create", "cdc_destroy", "cdc_last_error", "cdc_version", "cdc_nu
            "cdc_rate_map", "cdc_distortion_map", "cdc_set_rdo", "cdc_entropy_rate_sweep", "cdc_op_rdo_quantize",
            "cdc_price_cells", "cdc_set_rdo_map", "cdc_op_rdo_quantize_map",
            "cdc_set_noise_frames", "cdc_randn_framed", "cdc_randn_framed_host", "cdc_tile_gather", "cdc_tile_blend",
-           "cdc_entropy_set_segments", "cdc_entropy_peek_segments", "cdc_entropy_decode_window"]
+           "cdc_entropy_set_segments", "cdc_entropy_peek_segments", "cdc_entropy_decode_window",
+           "cdc_entropy_set_hyper_groups", "cdc_entropy_peek_hyper_groups"]
 
 
 def handle_status(handle):

@@ -91,6 +91,22 @@ def segment_positions(segment, cell):
     return seg // cell
 
 
+def hyper_group_channels(hyper_groups, channels, segment):
+    """hyper_groups=G -> cg, the hyper channels per group (cdc_entropy_set_hyper_groups), checked before the library is touched.  G is
+    the number of groups asked for, an int in 1 .. `channels`; cg = ceil(channels / G), and the stream then holds ceil(channels / cg)
+    groups, which can be fewer than G (40 channels, G = 16: cg = 3, 14 groups).  Only with segment=; None -> 0, one hyper section."""
+    if hyper_groups is None:
+        return 0
+    if isinstance(hyper_groups, bool) or not isinstance(hyper_groups, (int, np.integer)):
+        raise ValueError(f"hyper_groups={hyper_groups!r}: an int expected, the number of groups")
+    G = int(hyper_groups)
+    if G < 1 or G > channels:
+        raise ValueError(f"hyper_groups={G}: 1 .. {channels} expected (the model has {channels} hyper channels)")
+    if segment is None:
+        raise ValueError("hyper_groups needs segment=: grouped streams are segmented streams (container versions 19 - 22)")
+    return -(-channels // G)
+
+
 def rdo_exclusive(rdo=None, target_bpp=None, max_bytes=None):
     """rdo, target_bpp and max_bytes exclude each other."""
     given = [n for n, v in (("rdo", rdo), ("target_bpp", target_bpp), ("max_bytes", max_bytes)) if v is not None]
@@ -621,7 +637,7 @@ class _ContextDecoder:
             med = torch.from_numpy(med).to(t.device)
         return med
 
-    def encode(self, input, cond=None, padded_hw=None, rdo=None, price_map=None, price_cells=None, segment=None):
+    def encode(self, input, cond=None, padded_hw=None, rdo=None, price_map=None, price_cells=None, segment=None, hyper_groups=None):
         """Compressor.encode (compress_modules.py:43-66): (q_latent, q_hyper_latent, state4bpp); cond: VBR rate.  Images of any
         size (float32 / uint8): the results are those of the padded frame.  rdo: the price of a bit mu >= 0, a scalar or B values
         (no reference counterpart): q_latent comes from `rdo_quantize` -- every symbol the nearest integer or, where mu * (bits saved)
@@ -629,9 +645,10 @@ class _ContextDecoder:
         "q_latent" and "rdo_moved" (int64 [B]).  None runs the reference's rounding.  price_map / price_cells (with rdo): the price of
         a bit becomes mu * the map's value at the symbol's position -- a pixel-domain map at the image's own size ([H, W], [1, H, W],
         [B, H, W] or [B, 1, H, W]; float32 >= 0 or bool), or its cells on the latent grid as `price_cells()` returns them.
-        segment: the segment size of `compress_to_bytes`, checked as there; the symbols do not depend on how a stream is cut."""
+        segment / hyper_groups: those of `compress_to_bytes`, checked as there; the symbols do not depend on how a stream is cut."""
         B, _, H0, W0 = frame.image_shape(input)
         segment_positions(segment, self.rate_map_cell)
+        hyper_group_channels(hyper_groups, self.reversed_hyper_dims[0], segment)
         self._rates(cond, B)
         mu = None if rdo is None else rdo_values(rdo, B)
         priced = price_args(price_map, price_cells, B, (H0, W0), rdo is not None)
@@ -728,7 +745,7 @@ class _ContextDecoder:
         return np.ascontiguousarray(med, dtype=np.float32)
 
     def compress_to_bytes(self, images, bitrate_scale=None, rdo=None, target_bpp=None, max_bytes=None, return_info=False,
-                          price_map=None, price_cells=None, segment=None):
+                          price_map=None, price_cells=None, segment=None, hyper_groups=None):
         """images [B, 3, H, W] -> list of B bitstreams (bytes): analysis transform + hyper encoder on the GPU, then the
         range-ANS coder of include/cdc_hip.h (cdc_entropy_encode) over exactly the symbols `bpp()` prices.  A VBR model
         takes bitrate_scale (1 or B values) and records each image's rate in its stream.
@@ -751,10 +768,15 @@ class _ContextDecoder:
         cdc_entropy_set_segments): the latent section is cut into independent sections, one per s x s window of the image, behind an
         index -- n segments code and decode on n waves, and `decompress_from_bytes(window=)` decodes only those it needs.  The symbols
         are the same; a stream grows by 8 + 12 n bytes and its segments' lane states (max_bytes counts them).  None: today's streams.
+        hyper_groups=G (with segment=; container versions 19 - 22, cdc_entropy_set_hyper_groups): the hyper section as well is cut into
+        independent sections, one per group of cg = ceil(Ch / G) consecutive hyper channels -- the stream holds ceil(Ch / cg) groups,
+        which can be fewer than G -- coded and decoded on as many waves.  Every decode reads the form from the stream.  A stream grows
+        by 8 + 12 per group and the groups' lane states, about 235 bytes a group (max_bytes counts the index).  None: one hyper section.
         return_info=True: -> (streams, {"mu", "estimated_bpp", "moved", "latent_mse", "met" (each [B]), "reencodes"})."""
         B, _, H0, W0 = frame.image_shape(images)
         rdo_exclusive(rdo, target_bpp, max_bytes)
         segment_positions(segment, self.rate_map_cell)
+        hyper_group_channels(hyper_groups, self.reversed_hyper_dims[0], segment)
         self._rates(bitrate_scale, B)
         mu = None if rdo is None else rdo_values(rdo, B)
         target = None if target_bpp is None else self._targets(target_bpp, B, "target_bpp")
@@ -764,7 +786,8 @@ class _ContextDecoder:
         cells = self._cells_of(priced, hw)
         latent, hyper = self.analysis(images, bitrate_scale)
         if target is None and budget is None:
-            streams = self.latents_to_bytes(latent, hyper, bitrate_scale, image_hw=hw, rdo=mu, price_cells=cells, segment=segment)
+            streams = self.latents_to_bytes(latent, hyper, bitrate_scale, image_hw=hw, rdo=mu, price_cells=cells, segment=segment,
+                                            hyper_groups=hyper_groups)
             if not return_info:
                 return streams
             row = self._sweep(latent, hyper, np.zeros(1, np.float32) if mu is None else mu, bitrate_scale, per_image=True, cells=cells)
@@ -776,7 +799,7 @@ class _ContextDecoder:
         if target is not None:
             goal, cost0 = target, table["bits"] / npix                  # estimated bpp against the target
         else:
-            header = self._stream_header_bytes(images, hw, segment)
+            header = self._stream_header_bytes(images, hw, segment, hyper_groups)
             goal, cost0 = 8.0 * (budget - header), table["bits"]       # estimated payload bits against the budget's
         div = npix if target is not None else 1.0
         rows = [self._choose_mu(latent, hyper, bitrate_scale, b, ladder, cost0[b], goal[b], div, cells)
@@ -784,7 +807,8 @@ class _ContextDecoder:
         reencodes = 0
         while True:
             mus = np.asarray([r["mu"] for r in rows], np.float32)
-            streams = self.latents_to_bytes(latent, hyper, bitrate_scale, image_hw=hw, rdo=mus, price_cells=cells, segment=segment)
+            streams = self.latents_to_bytes(latent, hyper, bitrate_scale, image_hw=hw, rdo=mus, price_cells=cells, segment=segment,
+                                            hyper_groups=hyper_groups)
             over = [] if budget is None else [b for b in range(B) if len(streams[b]) > budget[b]]
             if not over or reencodes == 3:
                 break
@@ -809,15 +833,20 @@ class _ContextDecoder:
             raise ValueError(f"{what}={t.tolist()}: finite values > 0 expected")
         return np.broadcast_to(t, (B,)).copy()
 
-    def _stream_header_bytes(self, images, hw, segment=None):
+    def _stream_header_bytes(self, images, hw, segment=None, hyper_groups=None):
         """Bytes of a stream that code no symbol (include/cdc_hip.h: the header's 34, + 4 with a bitrate_scale, + 8 with a recorded image
-        size; of a segmented stream also the 8 bytes and the 12 of every index entry in front of its segments)."""
+        size; of a segmented stream also the 8 bytes and the 12 of every index entry in front of its segments, and of a grouped hyper
+        part the same in front of its groups)."""
         framed = tuple(frame.image_shape(images)[2:])
         seg = segment_positions(segment, self.rate_map_cell)
         index = 0
         if seg:
             c = self.rate_map_cell
             index = 8 + 12 * (-(-(framed[0] // c) // seg)) * (-(-(framed[1] // c) // seg))
+        Ch = self.reversed_hyper_dims[0]
+        cg = hyper_group_channels(hyper_groups, Ch, segment)
+        if cg:
+            index += 8 + 12 * (-(-Ch // cg))
         return 34 + (4 if self.vbr else 0) + (8 if tuple(hw) != framed else 0) + index
 
     def _sweep(self, latent, hyper, mus, bitrate_scale=None, per_image=False, cells=None):
@@ -899,7 +928,8 @@ class _ContextDecoder:
         per = float(np.prod(tuple(latent.shape)[1:]))
         return {"mu": mus.copy(), "bpp": t["bits"] / float(hw[0] * hw[1]), "latent_mse": t["sse"] / per, "moved": t["moved"]}
 
-    def latents_to_bytes(self, latent, hyper, bitrate_scale=None, image_hw=None, rdo=None, price_map=None, price_cells=None, segment=None):
+    def latents_to_bytes(self, latent, hyper, bitrate_scale=None, image_hw=None, rdo=None, price_map=None, price_cells=None, segment=None,
+                         hyper_groups=None):
         """The UNquantised outputs of `analysis()` -> list of B bitstreams.  The coder's determinism contract starts here: the
         same (latent, hyper) rows give the same bytes whatever the batch they are coded in (the analysis transform itself is
         an ordinary batched forward: its last bits may depend on the batch size, like any other entry point's).
@@ -908,8 +938,9 @@ class _ContextDecoder:
         rdo: mu, 1 or B values (cdc_set_rdo for this call alone); image b's stream depends on its own mu only.
         price_map / price_cells (with rdo; cdc_set_rdo_map for this call alone): as `compress_to_bytes`, the pixel-domain map at
         image_hw (default: the coded extent); image b's stream depends on its own mu and its own row of the map only.
-        segment: as `compress_to_bytes` (cdc_entropy_set_segments for this call alone)."""
+        segment / hyper_groups: as `compress_to_bytes` (cdc_entropy_set_segments / cdc_entropy_set_hyper_groups for this call alone)."""
         seg = segment_positions(segment, self.rate_map_cell)
+        cg = hyper_group_channels(hyper_groups, self.reversed_hyper_dims[0], segment)
         L, h = _lib.lib(), self._hyper_handle()
         al, ah = _Arg(latent, self.device_index), _Arg(hyper, self.device_index)
         B, _, hh, wh = ah.shape
@@ -923,22 +954,28 @@ class _ContextDecoder:
         if seg:
             _lib.check(h, L.cdc_entropy_set_segments(h, seg))
         try:
+            if cg:
+                _lib.check(h, L.cdc_entropy_set_hyper_groups(h, cg))
             if mu is not None:
                 _lib.check(h, L.cdc_set_rdo(h, mu.ctypes.data, int(mu.size)))
                 try:
-                    return self._with_map(h, cells, lambda: self._coded(L, h, al, ah, B, hh, wh, image_hw, seg))
+                    return self._with_map(h, cells, lambda: self._coded(L, h, al, ah, B, hh, wh, image_hw, seg, cg))
                 finally:
                     L.cdc_set_rdo(h, None, 0)
-            return self._coded(L, h, al, ah, B, hh, wh, image_hw, seg)
+            return self._coded(L, h, al, ah, B, hh, wh, image_hw, seg, cg)
         finally:
+            if cg:
+                L.cdc_entropy_set_hyper_groups(h, 0)
             if seg:
                 L.cdc_entropy_set_segments(h, 0)
 
-    def _coded(self, L, h, al, ah, B, hh, wh, image_hw, seg=0):
+    def _coded(self, L, h, al, ah, B, hh, wh, image_hw, seg=0, cg=0):
         nsym = int(np.prod(al.shape[1:])) + int(np.prod(ah.shape[1:]))
         cap = B * (64 + 2 * 320 + 6 * nsym)              # <= 2 renormalisation bytes + a 4-byte escape payload per symbol
         if seg:                                          # the index and every segment's own 64 lane states
             cap += B * (8 + (12 + 256) * (-(-int(al.shape[2]) // seg)) * (-(-int(al.shape[3]) // seg)))
+        if cg:                                           # likewise the hyper part's groups
+            cap += B * (8 + (12 + 256) * (-(-int(ah.shape[1]) // cg)))
         buf = np.empty(cap, dtype=np.uint8)
         offs = (ctypes.c_size_t * (B + 1))()
         med = self._median_vector()
@@ -1037,6 +1074,20 @@ class _ContextDecoder:
             if L.cdc_entropy_peek_segments(s, len(s), ctypes.byref(seg), ctypes.byref(ny), ctypes.byref(nx)) != 0:
                 raise _lib.CdcError("not a CDC bitstream")
             out.append((seg.value, ny.value, nx.value))
+        return out
+
+    @staticmethod
+    def hyper_groups_of(streams):
+        """[(hyper channels per group, groups)] of the streams (cdc_entropy_peek_hyper_groups, no handle needed): (0, 1) for a stream
+        with one hyper section (version 3 - 6, 11 - 14), cg and ng of a grouped one (version 19 - 22)."""
+        L = _lib.lib()
+        cg, ng = ctypes.c_int(), ctypes.c_int()
+        out = []
+        for s in streams:
+            s = bytes(s)
+            if L.cdc_entropy_peek_hyper_groups(s, len(s), ctypes.byref(cg), ctypes.byref(ng)) != 0:
+                raise _lib.CdcError("not a CDC bitstream")
+            out.append((cg.value, ng.value))
         return out
 
     @staticmethod

@@ -16,8 +16,14 @@ constexpr int kStreamSizeField = 8;
 // no stream), and a latent part cut into independent sections behind an index
 constexpr int kStreamSegmentedBy = 8;
 constexpr int kSegHeader = 8, kSegIndexEntry = 12, kMaxSegments = 65535;
-inline bool version_segmented(int v) { return v >= kStreamVersion + kStreamSegmentedBy && v <= kStreamVersionVbrSized + kStreamSegmentedBy; }
-inline int version_base(int v) { return version_segmented(v) ? v - kStreamSegmentedBy : v; }
+// ... and with the hyper part cut into channel groups as well: version byte + 16 = 19 .. 22 (15 .. 18 and 23 upwards stay no stream)
+constexpr int kStreamGroupedBy = 16;
+constexpr int kGrpHeader = 8, kGrpIndexEntry = 12;
+inline bool version_grouped(int v) { return v >= kStreamVersion + kStreamGroupedBy && v <= kStreamVersionVbrSized + kStreamGroupedBy; }
+inline bool version_segmented(int v) {
+    return (v >= kStreamVersion + kStreamSegmentedBy && v <= kStreamVersionVbrSized + kStreamSegmentedBy) || version_grouped(v);
+}
+inline int version_base(int v) { return version_grouped(v) ? v - kStreamGroupedBy : version_segmented(v) ? v - kStreamSegmentedBy : v; }
 inline bool version_known(int v) { v = version_base(v); return v == kStreamVersion || v == kStreamVersionVbr || v == kStreamVersionSized || v == kStreamVersionVbrSized; }
 inline bool version_vbr(int v) { v = version_base(v); return v == kStreamVersionVbr || v == kStreamVersionVbrSized; }
 inline bool version_sized(int v) { v = version_base(v); return v == kStreamVersionSized || v == kStreamVersionVbrSized; }
@@ -73,6 +79,31 @@ bool parse_segments(const unsigned char *s, size_t n, SegLayout *out) {
     out->seg = (int)seg; out->ny = (int)ny; out->nx = (int)nx;
     out->index = p + kSegHeader;
     out->first = (size_t)(hdr + nbh + fixed);
+    return true;
+}
+
+// The grouped hyper part of a version-19 .. -22 stream s[0 .. n) whose fixed header is complete, checked as parse_segments checks the
+// latent part.  index: the first index entry; first: where group 0 starts.
+struct GroupLayout { int cg = 0, ng = 1; const unsigned char *index = nullptr; size_t first = 0; };
+bool parse_hyper_groups(const unsigned char *s, size_t n, GroupLayout *out) {
+    const unsigned long long hdr = (unsigned long long)stream_header(s), nbh = get_u32(s + 10), nbl = get_u32(s + 14), eh = get_u32(s + 26);
+    if (hdr + nbh + nbl != (unsigned long long)n || nbh < (unsigned long long)kGrpHeader) return false;
+    const unsigned char *p = s + hdr;
+    const uint32_t cg = get_u16(p), ng = get_u16(p + 2), zero = get_u32(p + 4);
+    if (cg < 1 || ng < 1 || zero != 0) return false;
+    const unsigned long long fixed = kGrpHeader + (unsigned long long)kGrpIndexEntry * ng;
+    if (nbh < fixed) return false;
+    unsigned long long bytes = 0, esc = 0;
+    for (uint32_t i = 0; i < ng; ++i) {
+        const unsigned char *e = p + kGrpHeader + (size_t)kGrpIndexEntry * i;
+        const unsigned long long b = get_u32(e), x = get_u32(e + 4);
+        if (b < 256 + 4 * x) return false;
+        bytes += b; esc += x;
+    }
+    if (fixed + bytes != nbh || esc != eh) return false;
+    out->cg = (int)cg; out->ng = (int)ng;
+    out->index = p + kGrpHeader;
+    out->first = (size_t)(hdr + fixed);
     return true;
 }
 
@@ -229,6 +260,12 @@ int entropy_encode_impl(cdc_handle *h, const float *latent, const float *hyper_l
     long long *d_off;
     // cdc_entropy_set_segments: the latent part as S independent sections; 0 leaves every size and launch below as it was
     const int seg = h->ent_seg, Cl = o.C / 2;
+    // cdc_entropy_set_hyper_groups: the hyper part as ng independent sections (versions 19 - 22), only of segmented streams
+    const int cg = h->ent_hgroups, ng = cg > 0 ? (Ch + cg - 1) / cg : 0;
+    if (cg > 0 && seg == 0)
+        return fail(h, CDC_ERR_INVALID, "hyper groups are set (cdc_entropy_set_hyper_groups) but no segments (cdc_entropy_set_segments): grouped "
+                                        "streams are segmented streams");
+    if (cg > Ch || ng > 65535) return fail(h, CDC_ERR_INVALID, "%d hyper channels per group of %d channels", cg, Ch);
     SegTable segs;
     int S = 0;
     if (seg > 0) {
@@ -239,9 +276,9 @@ int entropy_encode_impl(cdc_handle *h, const float *latent, const float *hyper_l
         make_seg_table(Cl, o.H, o.W, seg, &segs);
         S = segs.ny * segs.nx;
     }
-    const long long cap_h = section_cap(nh), cap_l = S ? ((2 * nl + 256ll * S + 15) & ~15ll) : section_cap(nl);
+    const long long cap_h = ng ? ((2 * nh + 256ll * ng + 15) & ~15ll) : section_cap(nh), cap_l = S ? ((2 * nl + 256ll * S + 15) & ~15ll) : section_cap(nl);
     const long long pack_cap = (long long)B * ((h->vbr ? kStreamHeaderVbr : kStreamHeader) + kStreamSizeField + cap_h + 4 * nh + cap_l + 4 * nl +
-                                               (S ? kSegHeader + (long long)kSegIndexEntry * S : 0));
+                                               (S ? kSegHeader + (long long)kSegIndexEntry * S : 0) + (ng ? kGrpHeader + (long long)kGrpIndexEntry * ng : 0));
     HIP_TRY(h, d.get(&syml, (size_t)B * nl)); HIP_TRY(h, d.get(&bin, (size_t)B * nl));
     HIP_TRY(h, d.get(&sf, (size_t)B * std::max(nh, nl))); HIP_TRY(h, d.get(&ew, (size_t)B * std::max(nh, nl)));
     HIP_TRY(h, d.get(&sec_h, (size_t)B * cap_h)); HIP_TRY(h, d.get(&sec_l, (size_t)B * cap_l));
@@ -256,7 +293,15 @@ int entropy_encode_impl(cdc_handle *h, const float *latent, const float *hyper_l
         HIP_TRY(h, cdc::latent_symbols_rdo_launch(d_lat, nl, o.p, o.p + nl, o.bs(), h->ent->d_edges, nl, B, d_mu, map, syml, bin, bad, st));
     }
     const cdc::EntropyDev T = h->ent->dev();
-    HIP_TRY(h, cdc::rans_encode_launch(T, symh, nh, nullptr, 0, per, 0, (int)nh, 0u, B, sf, ew, sec_h, cap_h, esc_h, nh, meta, st));
+    cdc::RansMeta *hmeta = nullptr;
+    cdc::SegTotal *htot = nullptr;
+    long long *grp_at = nullptr;
+    if (!ng) {
+        HIP_TRY(h, cdc::rans_encode_launch(T, symh, nh, nullptr, 0, per, 0, (int)nh, 0u, B, sf, ew, sec_h, cap_h, esc_h, nh, meta, st));
+    } else {
+        HIP_TRY(h, d.get(&hmeta, (size_t)B * ng)); HIP_TRY(h, d.get(&htot, (size_t)B)); HIP_TRY(h, d.get(&grp_at, (size_t)B * ng));
+        HIP_TRY(h, cdc::hgrp_encode_launch(T, symh, Ch, per, cg, 0, B, sf, ew, sec_h, cap_h, esc_h, hmeta, htot, st));
+    }
     if (!S) HIP_TRY(h, cdc::rans_encode_launch(T, syml, nl, bin, nl, 0, Ch, (int)nl, 1u, B, sf, ew, sec_l, cap_l, esc_l, nl, meta + B, st));
     const long long dev_cap = (long long)std::min<unsigned long long>((unsigned long long)cap, (unsigned long long)pack_cap);
     HIP_TRY(h, d.get(&packed, (size_t)dev_cap));
@@ -275,6 +320,7 @@ int entropy_encode_impl(cdc_handle *h, const float *latent, const float *hyper_l
         HIP_TRY(h, cdc::seg_encode_launch(T, d_tab, S, segs.max_n, syml, bin, nl, o.H, o.W, Ch, B, sf, ew, sec_l, cap_l, esc_l, smeta, tot, st));
         P.meta_l = nullptr;
         cdc::SegPack SP{P, d_tab, smeta, tot, seg_at, seg, segs.ny, segs.nx};
+        if (ng) { SP.base.meta_h = nullptr; SP.hmeta = hmeta; SP.htot = htot; SP.grp_at = grp_at; SP.cg = cg; SP.ng = ng; SP.Ch = Ch; SP.per = per; }
         HIP_TRY(h, cdc::seg_pack_launch(SP, B, st));
     }
     std::vector<long long> hoff((size_t)B + 1);
@@ -359,7 +405,7 @@ int entropy_decode_impl(cdc_handle *h, const unsigned char *in, const size_t *of
     // the decoder runs hyper_dec in the encoder's arithmetic (see the contract in entropy.hip); the handle's own mode comes back
     struct Restore { cdc_handle *h; int a; ~Restore() { if (h->arith != a) (void)cdc_set_arith(h, a); } } restore{h, h->arith};
     // ---- headers: everything that sizes an allocation is validated here ----
-    struct Hdr { int hh, wh, ar, hdr; uint32_t nbh, nbl, sum, eh, el; float rate; SegLayout lay; };
+    struct Hdr { int hh, wh, ar, hdr; uint32_t nbh, nbl, sum, eh, el; float rate; SegLayout lay; GroupLayout grp; };
     const int U = 1 << ((int)h->hyper_dims.size() - 2);    // latent positions per hyper-latent position and side (as cdc_bpp)
     int img0_h = -1, img0_w = -1;                        // the size every image of the call shares (0: the coded extent)
     std::vector<Hdr> hd((size_t)B);
@@ -406,6 +452,15 @@ int entropy_decode_impl(cdc_handle *h, const unsigned char *in, const size_t *of
                 return fail(h, CDC_ERR_INVALID, "image %d: %d x %d segments of %d positions do not tile this model's %lld x %lld latent grid", b, q.lay.ny,
                             q.lay.nx, q.lay.seg, Hl, Wl);
         }
+        if (version_grouped(s[3])) {                       // (likewise validated by cdc_entropy_peek)
+            if (!parse_hyper_groups(s, n, &q.grp)) return fail(h, CDC_ERR_INVALID, "image %d: corrupt hyper group index", b);
+            if (q.grp.cg > Ch || q.grp.ng != (Ch + q.grp.cg - 1) / q.grp.cg)
+                return fail(h, CDC_ERR_INVALID, "image %d: %d hyper groups of %d channels do not cover this model's %d hyper channels", b, q.grp.ng,
+                            q.grp.cg, Ch);
+        }
+        if (q.grp.cg != hd[0].grp.cg)
+            return fail(h, CDC_ERR_INVALID, "image %d: %s hyper part in a call whose image 0's is %s (one call decodes one form and one group size)", b,
+                        q.grp.cg ? "a grouped" : "an ungrouped", hd[0].grp.cg ? "grouped" : "not, or is cut otherwise");
         if (q.lay.seg != hd[0].lay.seg)
             return fail(h, CDC_ERR_INVALID, "image %d: %s stream in a call whose image 0 is %s (one call decodes one form and one segment size)", b,
                         q.lay.seg ? "a segmented" : "an unsegmented", hd[0].lay.seg ? "segmented" : "not, or is cut otherwise");
@@ -413,6 +468,7 @@ int entropy_decode_impl(cdc_handle *h, const unsigned char *in, const size_t *of
     const int hh = hd[0].hh, wh = hd[0].wh, per = hh * wh;
     const long long nh = (long long)Ch * per;
     const int seg = hd[0].lay.seg, S = hd[0].lay.ny * hd[0].lay.nx;
+    const int cg = hd[0].grp.cg, ng = cg ? hd[0].grp.ng : 0;
     cdc::SegWindow win{0, 0, U * hh, U * wh};
     if (window) {
         win = cdc::SegWindow{window[0], window[1], window[2], window[3]};
@@ -458,7 +514,26 @@ int entropy_decode_impl(cdc_handle *h, const unsigned char *in, const size_t *of
         HIP_TRY(h, hipMemcpyAsync(d_esc, esc.data(), sizeof(int) * esc.size(), hipMemcpyHostToDevice, st));
         HIP_TRY(h, hipMemsetAsync(meta, 0, sizeof(cdc::RansMeta) * 2 * nb, st));
         const cdc::EntropyDev T = h->ent->dev();
-        HIP_TRY(h, cdc::rans_decode_launch(T, d_in, d_off, d_len, d_esc, nullptr, 0, per, 0, (int)nh, 0u, nb, symh, nh, meta, st));
+        std::vector<cdc::SegJob> gjobs;                    // grouped hyper part: one wave per (group, image), always all of them
+        std::vector<uint32_t> gwant;                       // the index's checksum of every job's group
+        cdc::RansMeta *gmeta = nullptr;
+        if (!ng) {
+            HIP_TRY(h, cdc::rans_decode_launch(T, d_in, d_off, d_len, d_esc, nullptr, 0, per, 0, (int)nh, 0u, nb, symh, nh, meta, st));
+        } else {
+            for (int b = b0; b < b1; ++b) {
+                long long at = (long long)(offsets[b] - offsets[0]) + (long long)hd[b].grp.first;
+                for (int g = 0; g < ng; ++g) {
+                    const unsigned char *ix = hd[b].grp.index + (size_t)kGrpIndexEntry * g;
+                    gjobs.push_back(cdc::SegJob{at, (int)get_u32(ix), (int)get_u32(ix + 4), b - b0, g});
+                    gwant.push_back(get_u32(ix + 8));
+                    at += get_u32(ix);
+                }
+            }
+            cdc::SegJob *d_gjobs;
+            HIP_TRY(h, d.get(&d_gjobs, gjobs.size())); HIP_TRY(h, d.get(&gmeta, gjobs.size()));
+            HIP_TRY(h, hipMemcpyAsync(d_gjobs, gjobs.data(), sizeof(cdc::SegJob) * gjobs.size(), hipMemcpyHostToDevice, st));
+            HIP_TRY(h, cdc::hgrp_decode_launch(T, d_gjobs, (int)gjobs.size(), d_in, Ch, per, cg, 0, symh, gmeta, st));
+        }
         HIP_TRY(h, cdc::symbols_to_hyper_launch(symh, h->ent->d_medians, Ch, per, nb, h->in_x, st));
         if (h->vbr) {                     // each image's own rate; the handle's cdc_set_bitrate_scale values stay as they are
             std::vector<float> rates((size_t)nb);
@@ -506,7 +581,19 @@ int entropy_decode_impl(cdc_handle *h, const unsigned char *in, const size_t *of
             HIP_TRY(h, hipMemcpyAsync(hm.data(), meta, sizeof(cdc::RansMeta) * nb, hipMemcpyDeviceToHost, st));
             HIP_TRY(h, hipMemcpyAsync(jm.data(), jmeta, sizeof(cdc::RansMeta) * jm.size(), hipMemcpyDeviceToHost, st));
             HIP_TRY(h, hipMemcpyAsync(hs.data(), sums, sizeof(uint32_t) * hs.size(), hipMemcpyDeviceToHost, st));
+            std::vector<cdc::RansMeta> gm(gjobs.size());
+            if (ng) HIP_TRY(h, hipMemcpyAsync(gm.data(), gmeta, sizeof(cdc::RansMeta) * gm.size(), hipMemcpyDeviceToHost, st));
             HIP_TRY(h, hipStreamSynchronize(st));
+            for (size_t j = 0; j < gjobs.size(); ++j) {        // every group's end conditions and checksum; hm[b] then stands for their sum
+                const int b = b0 + gjobs[j].b, g = gjobs[j].s;
+                if (j % (size_t)ng == 0) hm[b - b0] = cdc::RansMeta{0, 0, 0u, 0};
+                if (gm[j].bad) return fail(h, CDC_ERR_INVALID, "image %d, hyper group %d (channels %d - %d): corrupt hyper group", b, g, g * cg,
+                                           std::min(Ch, (g + 1) * cg) - 1);
+                if (gm[j].checksum != gwant[j])
+                    return fail(h, CDC_ERR_INVALID, "image %d, hyper group %d (channels %d - %d): symbol checksum mismatch -- the group or its index "
+                                "entry is corrupt", b, g, g * cg, std::min(Ch, (g + 1) * cg) - 1);
+                hm[b - b0].checksum += gwant[j];
+            }
             for (int b = b0; b < b1; ++b)
                 if (hm[b - b0].bad) return fail(h, CDC_ERR_INVALID, "image %d: corrupt hyper stream", b);
             std::vector<uint32_t> total((size_t)nb, 0u);
@@ -716,6 +803,10 @@ int cdc_entropy_peek(const unsigned char *in, size_t n, int *hh, int *wh, int *a
         SegLayout lay;
         if (!parse_segments(in, n, &lay)) return CDC_ERR_INVALID;
     }
+    if (version_grouped(in[3])) {                         // ... and so is its hyper index
+        GroupLayout lay;
+        if (!parse_hyper_groups(in, n, &lay)) return CDC_ERR_INVALID;
+    }
     if (arith) *arith = in[4];
     if (hh) *hh = in[6] | (in[7] << 8);
     if (wh) *wh = in[8] | (in[9] << 8);
@@ -747,6 +838,25 @@ int cdc_entropy_peek_segments(const unsigned char *in, size_t n, int *seg, int *
     if (seg) *seg = lay.seg;
     if (ny) *ny = lay.ny;
     if (nx) *nx = lay.nx;
+    return CDC_OK;
+}
+
+int cdc_entropy_peek_hyper_groups(const unsigned char *in, size_t n, int *channels_per_group, int *groups) {
+    if (cdc_entropy_peek(in, n, nullptr, nullptr, nullptr)) return CDC_ERR_INVALID;
+    GroupLayout lay;                                      // versions 3 - 6 and 11 - 14: one hyper section
+    if (version_grouped(in[3]) && !parse_hyper_groups(in, n, &lay)) return CDC_ERR_INVALID;
+    if (channels_per_group) *channels_per_group = lay.cg;
+    if (groups) *groups = lay.ng;
+    return CDC_OK;
+}
+
+int cdc_entropy_set_hyper_groups(cdc_handle *h, int channels_per_group) {
+    if (!h) return CDC_ERR_INVALID;
+    if (int rc = require_kind(h, HandleKind::HyperDecoder)) return rc;
+    const int Ch = h->hyper_dims.empty() ? 0 : h->hyper_dims[0];
+    if (channels_per_group < 0 || channels_per_group > Ch)
+        return fail(h, CDC_ERR_INVALID, "%d hyper channels per group (0: one hyper section, or 1 .. %d, the model's hyper channels)", channels_per_group, Ch);
+    h->ent_hgroups = channels_per_group;
     return CDC_OK;
 }
 

@@ -235,6 +235,7 @@ struct cdc_handle {
     std::unique_ptr<cdc::EntropyModel> ent;   // HyperDecoder: entropy coder tables (built on first use)
     uint32_t ent_model_hash = 0;
     int ent_pixels = 0;                       // HyperDecoder: image pixels per hyper-latent position and side (cdc_entropy_set_image_scale; 0: not told)
+    int ent_hgroups = 0;                      // HyperDecoder: hyper channels per group (cdc_entropy_set_hyper_groups; 0: one hyper section)
     int ent_seg = 0;                          // HyperDecoder: side of a stream segment in latent positions (cdc_entropy_set_segments; 0: unsegmented streams)
     int ent_max_positions = 1 << 22;          // HyperDecoder: largest hh * wh cdc_entropy_decode accepts from a stream header (cdc_entropy_set_limit)
     std::vector<int> rev_dims;    // ContextDecoder: [dim*m for m in rev_mults] + [out_channels]

@@ -138,6 +138,12 @@ struct SegPack {
     const SegTotal *tot;
     long long *seg_at;
     int seg, ny, nx;
+    // grouped hyper part (versions 19 - 22; ng = 0: the one hyper section of base): base.sec_h / esc_h / out_bs_h / esc_bs_h are
+    // hgrp_encode_launch's out / esc / out_bs / Ch per, base.meta_h is unused; grp_at: scratch, B * ng entries
+    const RansMeta *hmeta = nullptr;
+    const SegTotal *htot = nullptr;
+    long long *grp_at = nullptr;
+    int cg = 0, ng = 0, Ch = 0, per = 0;
 };
 hipError_t seg_pack_launch(const SegPack &P, int B, hipStream_t st);
 // Decoder: bins of the selected segments into segment order; one wave per job -> sym_seg (segment order), meta[job].bad;
@@ -148,5 +154,19 @@ hipError_t seg_decode_launch(EntropyDev T, const SegEntry *tab, const SegJob *jo
                              int tab0, int32_t *sym_seg, RansMeta *meta, hipStream_t st);
 hipError_t seg_scatter_launch(const SegEntry *tab, int S, int max_n, SegWindow win, const int32_t *sym_seg, long long nl, int Hl, int Wl, int B,
                               int32_t *sym, uint32_t *sums, hipStream_t st);
+
+
+// ---- grouped hyper part (container versions 19 - 22; see entropy.hip) --------------------------------------------------------
+// Group g = channels [g cg, min(Ch, (g + 1) cg)) of the hyper section [Ch][per], ng = ceil(Ch / cg) groups: a contiguous range of the
+// section, coded as a section of its own with the tables tab0 + channel.
+// Encoder: sym [B][Ch per] -> sf, ew in section order; group g of image b is coded into its own 2 n + 256 bytes at
+// out[b * out_bs + 2 g cg per + 256 g ..] (out_bs >= 2 Ch per + 256 ng), its payloads into esc[b * Ch per + g cg per .. + n);
+// meta[b * ng + g] = {start, esc_start (both within the group's own area), checksum over the indices in the full section}; tot[b]: sums.
+hipError_t hgrp_encode_launch(EntropyDev T, const int32_t *sym, int Ch, int per, int cg, int tab0, int B, uint32_t *sf, uint32_t *ew, uint8_t *out,
+                              long long out_bs, uint32_t *esc, RansMeta *meta, SegTotal *tot, hipStream_t st);
+// Decoder: one wave per job (job.s = the group, job.b = the image) -> sym[b][Ch per] in frame order; meta[job] = {checksum over the
+// indices in the full section, bad}
+hipError_t hgrp_decode_launch(EntropyDev T, const SegJob *jobs, int n_jobs, const uint8_t *in, int Ch, int per, int cg, int tab0, int32_t *sym,
+                              RansMeta *meta, hipStream_t st);
 
 }  // namespace cdc

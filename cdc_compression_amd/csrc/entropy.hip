@@ -354,11 +354,12 @@ __global__ void __launch_bounds__(64) rans_encode_kernel(const uint32_t *sf, con
 }
 
 // one section s[0 .. nbytes) with ne escape payloads by one wave -> sym[0 .. N); the table of symbol i is tab0 + (per ? i / per : bin[i]).
-// kSum: the section's checksum over (sect, i, symbol) is accumulated on the way (a segment's is taken where its symbols get their
-// index in the full section: seg_scatter_kernel).  m = {checksum, bad}
+// kSum: the section's checksum over (sect, ibase + i, symbol) is accumulated on the way -- ibase = where symbol 0 stands in the full
+// section, 0 for a whole section (a latent segment's is taken where its symbols get their index in the full section:
+// seg_scatter_kernel).  m = {checksum, bad}
 template <bool kSum>
 __device__ __forceinline__ void rans_decode_section(EntropyDev T, const uint8_t *s, long long nbytes, long long ne, const uint8_t *bin, int per,
-                                                    int tab0, int N, uint32_t sect, int32_t *sym, RansMeta *m) {
+                                                    int tab0, int N, uint32_t sect, uint32_t ibase, int32_t *sym, RansMeta *m) {
     const int lane = threadIdx.x;
     if (nbytes < 256 + 4 * ne) { if (lane == 0) { m->bad = 1; m->checksum = 0; } return; }
     const uint64_t below = (1ull << lane) - 1ull;
@@ -420,7 +421,7 @@ __device__ __forceinline__ void rans_decode_section(EntropyDev T, const uint8_t 
                 }
                 eidx += __popcll(me);
             }
-            if (act && !lb) { sym[i] = k; if (kSum) csum += sym_mix(sect, (uint32_t)i, k); }
+            if (act && !lb) { sym[i] = k; if (kSum) csum += sym_mix(sect, ibase + (uint32_t)i, k); }
             if (__ballot(lb)) { bad = true; break; }
         }
     }
@@ -433,7 +434,7 @@ __global__ void __launch_bounds__(64) rans_decode_kernel(EntropyDev T, const uin
                                                          const uint8_t *bin, long long bin_bs, int per, int tab0, int N, uint32_t sect,
                                                          int32_t *sym, long long sym_bs, RansMeta *meta) {
     const long long b = blockIdx.x;
-    rans_decode_section<true>(T, in + in_off[b], in_len[b], (uint32_t)in_esc[b], bin + b * bin_bs, per, tab0, N, sect, sym + b * sym_bs, meta + b);
+    rans_decode_section<true>(T, in + in_off[b], in_len[b], (uint32_t)in_esc[b], bin + b * bin_bs, per, tab0, N, sect, 0u, sym + b * sym_bs, meta + b);
 }
 
 hipError_t rans_encode_launch(EntropyDev T, const int32_t *sym, long long sym_bs, const uint8_t *bin, long long bin_bs, int per, int tab0,
@@ -551,23 +552,61 @@ __global__ void __launch_bounds__(64) seg_encode_kernel(const SegEntry *tab, con
     }
 }
 
-// rans_pack_kernel of a segmented stream, first half: one workgroup per image writes the header, the hyper section, the 8-byte
-// segment header and the index, and leaves every segment's place in the stream in P.seg_at (a workgroup scan over the sizes)
+// One workgroup places n sections behind an index: entry(e, &bytes, &esc, &sum) gives section e's size, escape count and checksum;
+// its 12 index bytes go to ix + 12 e and its place in the output, first + (the sizes before it), to at[e] (a workgroup scan)
+template <class F>
+__device__ __forceinline__ void pack_index_scan(int n, unsigned long long first, uint8_t *ix0, long long *at, unsigned long long *wave_tot, F entry) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long carry = first;
+    for (int s0 = 0; s0 < n; s0 += 256) {
+        const int s = s0 + threadIdx.x;
+        uint32_t bytes = 0, ne = 0, sum = 0;
+        if (s < n) entry(s, &bytes, &ne, &sum);
+        unsigned long long inc = bytes;                        // inclusive scan: the wave, then the four wave totals
+        for (int d = 1; d < 64; d <<= 1) { const unsigned long long v = __shfl_up(inc, d, 64); if (lane >= d) inc += v; }
+        if (lane == 63) wave_tot[wave] = inc;
+        __syncthreads();
+        unsigned long long before = carry, all = 0;
+        for (int w = 0; w < 4; ++w) { if (w < wave) before += wave_tot[w]; all += wave_tot[w]; }
+        __syncthreads();
+        if (s < n) {
+            at[s] = (long long)(before + inc - bytes);
+            uint8_t *ix = ix0 + 12ll * s;
+            const uint32_t w[3] = {bytes, ne, sum};
+            for (int k = 0; k < 3; ++k) for (int q = 0; q < 4; ++q) ix[4 * k + q] = (uint8_t)(w[k] >> (8 * q));
+        }
+        carry += all;
+    }
+}
+
+// channels [g cg, min(Ch, (g + 1) cg)) of the hyper section [Ch][per]: where group g starts in the section, and its symbols
+__device__ __forceinline__ int hgrp_off(int g, int cg, int per) { return g * cg * per; }
+__device__ __forceinline__ int hgrp_n(int g, int cg, int Ch, int per) { return (min(Ch, (g + 1) * cg) - g * cg) * per; }
+
+// rans_pack_kernel of a segmented stream, first half: one workgroup per image writes the header, the hyper part -- the one section, or
+// (P.ng > 0: versions 19 - 22) its 8 bytes and the index of its groups --, the 8-byte segment header and the index, and leaves every
+// segment's and every group's place in the stream in P.seg_at / P.grp_at (a workgroup scan over the sizes)
 __global__ void __launch_bounds__(256) seg_pack_index_kernel(SegPack P) {
     __shared__ unsigned long long wave_tot[4];
     const RansPack &Q = P.base;
-    const int b = blockIdx.x, S = P.ny * P.nx;
+    const int b = blockIdx.x, S = P.ny * P.nx, G = P.ng;
     const bool sized = Q.img_h > 0;
     const int hdr = (Q.rates ? 38 : 34) + (sized ? 8 : 0);
-    const unsigned long long fixed = 8ull + 12ull * S;
+    const unsigned long long fixed = 8ull + 12ull * S, hfixed = 8ull + 12ull * G;
     auto hyper = [&](int i, uint32_t *nh, uint32_t *eh) {
         *eh = (uint32_t)(Q.esc_bs_h - Q.meta_h[i].esc_start);
         *nh = (uint32_t)(Q.out_bs_h - Q.meta_h[i].start) + 4u * *eh;
     };
+    auto grouped = [&](int i, uint32_t *nh, uint32_t *eh) {     // (<= 2^29 symbols of <= 6 bytes: 32 bits do)
+        *eh = P.htot[i].esc;
+        *nh = (uint32_t)(hfixed + P.htot[i].bytes);
+    };
     uint32_t nh, eh;
     long long off = 0;
-    for (int i = 0; i < b; ++i) { hyper(i, &nh, &eh); off += hdr + (long long)nh + (long long)(fixed + P.tot[i].bytes); }
-    hyper(b, &nh, &eh);
+    // (one loop per form: with the choice inside, the two loads of an iteration would wait for each other)
+    if (G) for (int i = 0; i < b; ++i) { grouped(i, &nh, &eh); off += hdr + (long long)nh + (long long)(fixed + P.tot[i].bytes); }
+    else for (int i = 0; i < b; ++i) { hyper(i, &nh, &eh); off += hdr + (long long)nh + (long long)(fixed + P.tot[i].bytes); }
+    if (G) grouped(b, &nh, &eh); else hyper(b, &nh, &eh);
     const unsigned long long nl = fixed + P.tot[b].bytes;
     const long long end = off + hdr + (long long)nh + (long long)nl;
     if (threadIdx.x == 0) {
@@ -578,51 +617,47 @@ __global__ void __launch_bounds__(256) seg_pack_index_kernel(SegPack P) {
     // (nl fits 32 bits: at most 2^29 symbols of <= 6 bytes and 65535 segments of 268 bytes more)
     uint8_t *o = Q.out + off;
     if (threadIdx.x == 0) {
-        const uint32_t w[6] = {nh, (uint32_t)nl, Q.model, Q.meta_h[b].checksum + P.tot[b].checksum, eh, P.tot[b].esc};
-        o[0] = 'C'; o[1] = 'D'; o[2] = 'C'; o[3] = 8 + (Q.rates ? 4 : 3) + (sized ? 2 : 0); o[4] = (uint8_t)Q.arith; o[5] = 0;
+        const uint32_t w[6] = {nh, (uint32_t)nl, Q.model, (G ? P.htot[b].checksum : Q.meta_h[b].checksum) + P.tot[b].checksum, eh, P.tot[b].esc};
+        o[0] = 'C'; o[1] = 'D'; o[2] = 'C'; o[3] = (G ? 16 : 8) + (Q.rates ? 4 : 3) + (sized ? 2 : 0); o[4] = (uint8_t)Q.arith; o[5] = 0;
         o[6] = (uint8_t)(Q.hh & 255); o[7] = (uint8_t)(Q.hh >> 8); o[8] = (uint8_t)(Q.wh & 255); o[9] = (uint8_t)(Q.wh >> 8);
         for (int k = 0; k < 6; ++k) for (int q = 0; q < 4; ++q) o[10 + 4 * k + q] = (uint8_t)(w[k] >> (8 * q));
         if (Q.rates) { const uint32_t r = __float_as_uint(Q.rates[b]); for (int q = 0; q < 4; ++q) o[34 + q] = (uint8_t)(r >> (8 * q)); }
         if (sized) for (int q = 0; q < 4; ++q) { o[hdr - 8 + q] = (uint8_t)((uint32_t)Q.img_h >> (8 * q)); o[hdr - 4 + q] = (uint8_t)((uint32_t)Q.img_w >> (8 * q)); }
     }
     o += hdr;
-    const uint8_t *sh = Q.sec_h + (long long)b * Q.out_bs_h + Q.meta_h[b].start;
-    const uint32_t *xh = Q.esc_h + (long long)b * Q.esc_bs_h + Q.meta_h[b].esc_start;
-    const uint32_t bh = nh - 4u * eh;
-    for (uint32_t i = threadIdx.x; i < bh; i += 256) o[i] = sh[i];
-    for (uint32_t i = threadIdx.x; i < 4u * eh; i += 256) o[bh + i] = (uint8_t)(xh[i >> 2] >> (8 * (i & 3)));
+    if (G) {
+        if (threadIdx.x == 0) {
+            const uint16_t w[4] = {(uint16_t)P.cg, (uint16_t)G, 0, 0};
+            for (int k = 0; k < 4; ++k) { o[2 * k] = (uint8_t)(w[k] & 255); o[2 * k + 1] = (uint8_t)(w[k] >> 8); }
+        }
+        pack_index_scan(G, (unsigned long long)(off + hdr) + hfixed, o + 8, P.grp_at + (long long)b * G, wave_tot,
+                        [&](int g, uint32_t *bytes, uint32_t *ne, uint32_t *sum) {
+                            const RansMeta m = P.hmeta[(long long)b * G + g];
+                            const int n = hgrp_n(g, P.cg, P.Ch, P.per);
+                            *ne = (uint32_t)(n - m.esc_start);
+                            *bytes = (uint32_t)(2ll * n + 256 - m.start) + 4u * *ne;
+                            *sum = m.checksum;
+                        });
+    } else {
+        const uint8_t *sh = Q.sec_h + (long long)b * Q.out_bs_h + Q.meta_h[b].start;
+        const uint32_t *xh = Q.esc_h + (long long)b * Q.esc_bs_h + Q.meta_h[b].esc_start;
+        const uint32_t bh = nh - 4u * eh;
+        for (uint32_t i = threadIdx.x; i < bh; i += 256) o[i] = sh[i];
+        for (uint32_t i = threadIdx.x; i < 4u * eh; i += 256) o[bh + i] = (uint8_t)(xh[i >> 2] >> (8 * (i & 3)));
+    }
     o += nh;
     if (threadIdx.x == 0) {
         const uint16_t w[4] = {(uint16_t)P.seg, (uint16_t)P.ny, (uint16_t)P.nx, 0};
         for (int k = 0; k < 4; ++k) { o[2 * k] = (uint8_t)(w[k] & 255); o[2 * k + 1] = (uint8_t)(w[k] >> 8); }
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long carry = (unsigned long long)(off + hdr + nh) + fixed;      // where segment 0 starts in P.out
-    for (int s0 = 0; s0 < S; s0 += 256) {
-        const int s = s0 + threadIdx.x;
-        uint32_t bytes = 0, ne = 0, sum = 0;
-        if (s < S) {
-            const RansMeta m = P.meta[(long long)b * S + s];
-            const int n = P.tab[s].n;
-            ne = (uint32_t)(n - m.esc_start);
-            bytes = (uint32_t)(2ll * n + 256 - m.start) + 4u * ne;
-            sum = m.checksum;
-        }
-        unsigned long long inc = bytes;                        // inclusive scan: the wave, then the four wave totals
-        for (int d = 1; d < 64; d <<= 1) { const unsigned long long v = __shfl_up(inc, d, 64); if (lane >= d) inc += v; }
-        if (lane == 63) wave_tot[wave] = inc;
-        __syncthreads();
-        unsigned long long before = carry, all = 0;
-        for (int w = 0; w < 4; ++w) { if (w < wave) before += wave_tot[w]; all += wave_tot[w]; }
-        __syncthreads();
-        if (s < S) {
-            P.seg_at[(long long)b * S + s] = (long long)(before + inc - bytes);
-            uint8_t *ix = o + 8 + 12ll * s;
-            const uint32_t w[3] = {bytes, ne, sum};
-            for (int k = 0; k < 3; ++k) for (int q = 0; q < 4; ++q) ix[4 * k + q] = (uint8_t)(w[k] >> (8 * q));
-        }
-        carry += all;
-    }
+    pack_index_scan(S, (unsigned long long)(off + hdr + nh) + fixed, o + 8, P.seg_at + (long long)b * S, wave_tot,
+                    [&](int s, uint32_t *bytes, uint32_t *ne, uint32_t *sum) {
+                        const RansMeta m = P.meta[(long long)b * S + s];
+                        const int n = P.tab[s].n;
+                        *ne = (uint32_t)(n - m.esc_start);
+                        *bytes = (uint32_t)(2ll * n + 256 - m.start) + 4u * *ne;
+                        *sum = m.checksum;
+                    });
 }
 
 // second half: one workgroup per (segment, image) copies the segment's section to its place
@@ -641,6 +676,73 @@ __global__ void __launch_bounds__(256) seg_pack_copy_kernel(SegPack P) {
     for (uint32_t i = threadIdx.x; i < 4u * ne; i += 256) o[nb + i] = (uint8_t)(xs[i >> 2] >> (8 * (i & 3)));
 }
 
+// ---- grouped hyper part (include/cdc_hip.h: container versions 19 - 22) ---------------------------------------------------------
+// The hyper section's symbols stand in order (c, y, x) and its tables are per channel, so a group of cg consecutive channels is a
+// contiguous range of the section: no gather, no scatter, no bins.  Group g is a plain section over symbols [g cg per, ...) with
+// tables tab0 + g cg + j / per; only its checksum needs the index in the full section.  One wave per (group, image).
+// rans_prepare_kernel of the hyper section per group: grid (blocks of the largest group, ng, B).  A wave lies inside one group
+// (groups are no multiples of 64 and may be smaller than a wave), so sf / ew keep section order and the sums are per group.
+__global__ void __launch_bounds__(256) hgrp_prepare_kernel(EntropyDev T, const int32_t *sym, int Ch, int per, int cg, int tab0, uint32_t *sf,
+                                                           uint32_t *ew, RansMeta *meta, SegTotal *tot) {
+    const int g = blockIdx.y, n = hgrp_n(g, cg, Ch, per);
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (blockIdx.x * 256 >= n) return;                         // (whole workgroups only: the waves below sum over all their lanes)
+    const long long b = blockIdx.z, nh = (long long)Ch * per;
+    uint32_t mix = 0;
+    if (j < n) {
+        const int i = hgrp_off(g, cg, per) + j;
+        const int k = sym[b * nh + i];
+        rans_lookup(T, tab0 + i / per, k, &sf[b * nh + i], &ew[b * nh + i]);
+        mix = sym_mix(0u, (uint32_t)i, k);
+    }
+    mix = wave_sum(mix);
+    if ((threadIdx.x & 63) == 0 && mix) {
+        atomicAdd(&meta[b * gridDim.y + g].checksum, mix);
+        atomicAdd(&tot[b].checksum, mix);
+    }
+}
+
+// one wave per (group, image): group g of image b is written back to front into its own 2 n + 256 bytes of out
+__global__ void __launch_bounds__(64) hgrp_encode_kernel(const uint32_t *sf, const uint32_t *ew, int Ch, int per, int cg, uint8_t *out, long long out_bs,
+                                                         uint32_t *esc, RansMeta *meta, SegTotal *tot) {
+    const int g = blockIdx.x, G = gridDim.x;
+    const long long b = blockIdx.y, nh = (long long)Ch * per;
+    const int off = hgrp_off(g, cg, per), n = hgrp_n(g, cg, Ch, per);
+    const long long cap = 2ll * n + 256;
+    RansMeta *m = meta + b * G + g;
+    rans_encode_section(sf + b * nh + off, ew + b * nh + off, n, out + b * out_bs + 2ll * off + 256ll * g, cap, esc + b * nh + off, n, m);
+    if (threadIdx.x == 0) {                                    // (the values this lane has just stored)
+        const uint32_t ne = (uint32_t)(n - m->esc_start);
+        atomicAdd(&tot[b].bytes, (unsigned long long)(cap - m->start) + 4ull * ne);
+        atomicAdd(&tot[b].esc, ne);
+    }
+}
+
+// one workgroup per (group, image) copies the group's section to its place
+__global__ void __launch_bounds__(256) hgrp_pack_copy_kernel(SegPack P) {
+    const RansPack &Q = P.base;
+    const int g = blockIdx.x, G = gridDim.x;
+    const long long b = blockIdx.y;
+    if (Q.offsets[b + 1] > Q.cap) return;                      // image b's end: seg_pack_index_kernel wrote nothing for it either
+    const RansMeta m = P.hmeta[b * G + g];
+    const int off = hgrp_off(g, P.cg, P.per), n = hgrp_n(g, P.cg, P.Ch, P.per);
+    const uint32_t ne = (uint32_t)(n - m.esc_start), nb = (uint32_t)(2ll * n + 256 - m.start);
+    const uint8_t *src = Q.sec_h + b * Q.out_bs_h + 2ll * off + 256ll * g + m.start;
+    const uint32_t *xs = Q.esc_h + b * Q.esc_bs_h + off + m.esc_start;
+    uint8_t *o = Q.out + P.grp_at[b * G + g];
+    for (uint32_t i = threadIdx.x; i < nb; i += 256) o[i] = src[i];
+    for (uint32_t i = threadIdx.x; i < 4u * ne; i += 256) o[nb + i] = (uint8_t)(xs[i >> 2] >> (8 * (i & 3)));
+}
+
+// one wave per (group, image): job.s = the group, straight into the frame-ordered symbol buffer sym[b][Ch per]
+__global__ void __launch_bounds__(64) hgrp_decode_kernel(EntropyDev T, const SegJob *jobs, const uint8_t *in, int Ch, int per, int cg, int tab0,
+                                                         int32_t *sym, RansMeta *meta) {
+    const SegJob q = jobs[blockIdx.x];
+    const int off = hgrp_off(q.s, cg, per), n = hgrp_n(q.s, cg, Ch, per);
+    rans_decode_section<true>(T, in + q.off, q.len, (uint32_t)q.esc, nullptr, per, tab0 + q.s * cg, n, 0u, (uint32_t)off,
+                              sym + (long long)q.b * Ch * per + off, meta + blockIdx.x);
+}
+
 hipError_t seg_encode_launch(EntropyDev T, const SegEntry *tab, int S, int max_n, const int32_t *sym, const uint8_t *bin, long long nl, int Hl,
                              int Wl, int tab0, int B, uint32_t *sf, uint32_t *ew, uint8_t *out, long long out_bs, uint32_t *esc, RansMeta *meta,
                              SegTotal *tot, hipStream_t st) {
@@ -655,7 +757,26 @@ hipError_t seg_encode_launch(EntropyDev T, const SegEntry *tab, int S, int max_n
 
 hipError_t seg_pack_launch(const SegPack &P, int B, hipStream_t st) {
     hipLaunchKernelGGL(seg_pack_index_kernel, dim3((unsigned)B), dim3(256), 0, st, P);
+    if (P.ng) hipLaunchKernelGGL(hgrp_pack_copy_kernel, dim3((unsigned)P.ng, (unsigned)B), dim3(256), 0, st, P);
     hipLaunchKernelGGL(seg_pack_copy_kernel, dim3((unsigned)(P.ny * P.nx), (unsigned)B), dim3(256), 0, st, P);
+    return hipGetLastError();
+}
+
+hipError_t hgrp_encode_launch(EntropyDev T, const int32_t *sym, int Ch, int per, int cg, int tab0, int B, uint32_t *sf, uint32_t *ew, uint8_t *out,
+                              long long out_bs, uint32_t *esc, RansMeta *meta, SegTotal *tot, hipStream_t st) {
+    const int ng = (Ch + cg - 1) / cg;
+    hipError_t e = hipMemsetAsync(meta, 0, sizeof(RansMeta) * (size_t)B * ng, st);
+    if (e != hipSuccess) return e;
+    if ((e = hipMemsetAsync(tot, 0, sizeof(SegTotal) * (size_t)B, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(hgrp_prepare_kernel, dim3((unsigned)((cg * per + 255) / 256), (unsigned)ng, (unsigned)B), dim3(256), 0, st, T, sym, Ch, per, cg,
+                       tab0, sf, ew, meta, tot);
+    hipLaunchKernelGGL(hgrp_encode_kernel, dim3((unsigned)ng, (unsigned)B), dim3(64), 0, st, sf, ew, Ch, per, cg, out, out_bs, esc, meta, tot);
+    return hipGetLastError();
+}
+
+hipError_t hgrp_decode_launch(EntropyDev T, const SegJob *jobs, int n_jobs, const uint8_t *in, int Ch, int per, int cg, int tab0, int32_t *sym,
+                              RansMeta *meta, hipStream_t st) {
+    hipLaunchKernelGGL(hgrp_decode_kernel, dim3((unsigned)n_jobs), dim3(64), 0, st, T, jobs, in, Ch, per, cg, tab0, sym, meta);
     return hipGetLastError();
 }
 
@@ -675,7 +796,7 @@ __global__ void __launch_bounds__(64) seg_decode_kernel(EntropyDev T, const SegE
     const SegJob q = jobs[blockIdx.x];
     const SegEntry e = tab[q.s];
     const long long base = (long long)q.b * nl + e.off;
-    rans_decode_section<false>(T, in + q.off, q.len, (uint32_t)q.esc, bin_seg + base, 0, tab0, e.n, 1u, sym_seg + base, meta + blockIdx.x);
+    rans_decode_section<false>(T, in + q.off, q.len, (uint32_t)q.esc, bin_seg + base, 0, tab0, e.n, 1u, 0u, sym_seg + base, meta + blockIdx.x);
 }
 
 // segment order -> frame order, 0 where the segment was not selected; sums[b][s] += the checksum of a selected segment's symbols

@@ -144,16 +144,17 @@ class _GaussianDiffusionBase:
                                            optr, omem, _current_stream(omem)))
         return out
 
-    def _rdo_of(self, images, bitrate_scale=None, rdo=None, target_bpp=None, max_bytes=None, price_map=None, price_cells=None, segment=None):
+    def _rdo_of(self, images, bitrate_scale=None, rdo=None, target_bpp=None, max_bytes=None, price_map=None, price_cells=None, segment=None,
+                hyper_groups=None):
         """The rate-control arguments of compress / compress_best_of / compress_to_bytes, checked before the library is touched ->
         (mu, cells): the context model's mu (float32, 1 or B values) or None, and its price map on the latent grid of the frame the
         U-Net asks for (float32 host [1 or B, gh, gw]) or None.  target_bpp / max_bytes: the context model chooses mu as its
         compress_to_bytes does (compressor.py) -- under the map, when there is one -- and forward(rdo=mu, price_cells=cells) then
         runs with both.  segment: the segment size of the streams `compress_to_bytes(segment=)` would write (image pixels): max_bytes
-        counts their larger container; it changes no symbol otherwise."""
+        counts their larger container; it changes no symbol otherwise.  hyper_groups: likewise the groups of their hyper part."""
         from . import compressor
         compressor.rdo_exclusive(rdo, target_bpp, max_bytes)
-        self._segment_arg(segment)
+        self._segment_arg(segment, hyper_groups)
         B, _, H, W = frame.image_shape(images)
         if rdo is not None:
             mu = compressor.rdo_values(rdo, B)
@@ -173,14 +174,22 @@ class _GaussianDiffusionBase:
             raise NotImplementedError("target_bpp / max_bytes choose mu on the context model's own frame: a U-Net that needs a larger one "
                                       f"({self.padded_size(H, W)} against {self.context_fn.padded_size(H, W)}) cannot share it")
         kw = {} if segment is None else {"segment": segment}
+        if hyper_groups is not None:
+            kw["hyper_groups"] = hyper_groups
         _, info = self.context_fn.compress_to_bytes(images, bitrate_scale, target_bpp=target_bpp, max_bytes=max_bytes, return_info=True,
                                                     price_cells=cells, **kw)
         return info["mu"], cells
 
-    def _segment_arg(self, segment):
-        """The argument rule of segment= (compressor.segment_positions), checked before the library is touched: a stream is cut by a
-        context model of this package, never by a callable that only returns a context pyramid."""
+    def _segment_arg(self, segment, hyper_groups=None):
+        """The argument rules of segment= and hyper_groups= (compressor.segment_positions, compressor.hyper_group_channels), checked
+        before the library is touched: a stream is cut by a context model of this package, never by a callable that only returns a
+        context pyramid."""
         from . import compressor
+        if hyper_groups is not None:
+            if not hasattr(self.context_fn, "hyper_groups_of"):
+                raise ValueError("hyper_groups needs a context model of this package (its entropy coder writes the streams): a context_fn "
+                                 "that only returns a context pyramid has no stream to cut")
+            compressor.hyper_group_channels(hyper_groups, self.context_fn.reversed_hyper_dims[0], segment)
         if segment is None:
             return
         if not hasattr(self.context_fn, "segments_of"):
@@ -484,7 +493,8 @@ class _GaussianDiffusionBase:
         multiple); tile_chunk: rows (tiles of all images) per sampler call (default: the fewest calls of at most 32 rows);
         region=(y0, x0, h, w) in image pixels: decodes the tiles that intersect it -> (that window, {"tiles", "tiles_decoded", "region"}).
         Of segmented streams (compress_to_bytes(segment=)) only the segments under those tiles are entropy-decoded, and the dict also
-        holds "segments" and "segments_decoded" (per image).
+        holds "segments" and "segments_decoded" (per image); of streams with a grouped hyper section (hyper_groups=) also
+        "hyper_groups", the groups a stream holds -- all of them are always decoded.
         Excludes samples=, trajectory= and a context pyramid; eta != 0 needs a seed."""
         tile_hw, overlap_hw = _tiles.check_args(tile, tile_overlap, tile_chunk, region, samples, trajectory)
         if tile_hw is not None:
@@ -501,7 +511,7 @@ class _GaussianDiffusionBase:
         if samples is None and (reduce is not None or sample_chunk is not None):
             raise ValueError("reduce / sample_chunk belong to samples=K")
         K = None if samples is None else _samples.check_args(samples, seed, gamma, eta, init, reduce, as_uint8, sample_chunk)
-        recorded = seg_info = None
+        recorded = seg_info = hyper_groups = None
         if isinstance(context, (bytes, bytearray)):
             context = [context]
         if isinstance(context, (list, tuple)) and context and isinstance(context[0], (bytes, bytearray)):
@@ -512,6 +522,8 @@ class _GaussianDiffusionBase:
             # selected tiles' latent windows are entropy-decoded (unsegmented streams: the call and the info dict of always)
             cut = tile_hw is not None and region is not None and hasattr(self.context_fn, "segments_of") and \
                 self.context_fn.segments_of(context[:1])[0][0] > 0
+            if hasattr(self.context_fn, "hyper_groups_of") and self.context_fn.hyper_groups_of(context[:1])[0][0] > 0:
+                hyper_groups = self.context_fn.hyper_groups_of(context[:1])[0][1]
             if cut:
                 win = self._stream_window(context[0], tile_hw, overlap_hw, region)
                 context, bitrate_scale, recorded, seg_info = self.context_fn.decompress_from_bytes(
@@ -528,6 +540,8 @@ class _GaussianDiffusionBase:
                 if res is not None:
                     if seg_info is not None:
                         res[1].update(segments=seg_info[0], segments_decoded=seg_info[1])
+                    if hyper_groups is not None and region is not None:
+                        res[1].update(hyper_groups=hyper_groups)
                     return res
             context = self.context_fn.decode(context) if bitrate_scale is None else self.context_fn.decode(context, bitrate_scale)
         if K is None:
@@ -754,17 +768,19 @@ class _GaussianDiffusionBase:
 
 
     def compress_to_bytes(self, images, bitrate_scale=None, rdo=None, target_bpp=None, max_bytes=None, return_info=False,
-                          price_map=None, price_cells=None, segment=None):
+                          price_map=None, price_cells=None, segment=None, hyper_groups=None):
         """The transmitted half of compress(): images -> one entropy-coded bitstream per image.
         `decompress(streams, shape, sample_steps, init)` reconstructs from them.  bitrate_scale: the rate of a
         variable-bitrate context model (1 or B values), recorded in each stream.  Images of any size: a stream records H x W
         unless the image is its own padded frame.  rdo / target_bpp / max_bytes / return_info: the context model's rate control
         (compressor.compress_to_bytes), price_map / price_cells its region-of-interest map; the decoder side needs nothing.
         segment (image pixels, a multiple of the pixels of a latent position): segmented streams, whose segments code and decode in
-        parallel and of which `decompress(streams, tile=, region=)` entropy-decodes only what the region's tiles need."""
+        parallel and of which `decompress(streams, tile=, region=)` entropy-decodes only what the region's tiles need.
+        hyper_groups (with segment; compressor.compress_to_bytes): the hyper section too in that many groups of channels at the most,
+        one wave each; every decode reads the form from the stream."""
         from . import compressor
         compressor.rdo_exclusive(rdo, target_bpp, max_bytes)
-        self._segment_arg(segment)
+        self._segment_arg(segment, hyper_groups)
         B, _, H, W = frame.image_shape(images)
         if rdo is not None:
             compressor.rdo_values(rdo, B)
@@ -780,6 +796,8 @@ class _GaussianDiffusionBase:
             kw["return_info"] = True
         if segment is not None:
             kw["segment"] = segment
+        if hyper_groups is not None:
+            kw["hyper_groups"] = hyper_groups
         if priced is not None:
             kw["price_map" if priced[0] == "map" else "price_cells"] = priced[1]
         if bitrate_scale is None:
@@ -823,19 +841,21 @@ class GaussianDiffusionX(_GaussianDiffusionBase):
 
     def compress(self, images, sample_steps=None, bpp_return_mean=True, init=None, eta=0, seed=None, gamma=None, sampler="ddim",
                  spacing="index", trajectory=None, trajectory_of="x0", trajectory_dtype="float32", rdo=None, target_bpp=None,
-                 max_bytes=None, price_map=None, price_cells=None, tile=None, tile_overlap=None, tile_chunk=None, region=None, segment=None):
+                 max_bytes=None, price_map=None, price_cells=None, tile=None, tile_overlap=None, tile_chunk=None, region=None, segment=None,
+                 hyper_groups=None):
         """trajectory=: -> (reconstruction, bpp, Trajectory) (cdc_compression_amd.trajectory).  rdo / target_bpp / max_bytes: the
         context model's rate control (compressor.compress_to_bytes); bpp is that of the symbols it chose.  price_map / price_cells
         (with one of them): its region-of-interest map, in pixels at the image's size or on the latent grid.
         tile / tile_overlap / tile_chunk / region: the decode half runs tiled (decompress states them); with a region
-        -> (window, bpp, info).  segment: the segment size of the streams to be written (compress_to_bytes): max_bytes counts it."""
+        -> (window, bpp, info).  segment / hyper_groups: the segment size and the hyper groups of the streams to be written
+        (compress_to_bytes): max_bytes counts them."""
         if not (tile is None and tile_overlap is None and tile_chunk is None and region is None):
             return self._compress_tiled(images, (), dict(rdo=rdo, target_bpp=target_bpp, max_bytes=max_bytes, price_map=price_map, price_cells=price_cells,
-                                                         segment=segment),
+                                                         segment=segment, hyper_groups=hyper_groups),
                                         bpp_return_mean, dict(tile=tile, tile_overlap=tile_overlap, tile_chunk=tile_chunk, region=region),
                                         sample_steps=sample_steps, init=init, eta=eta, seed=seed, gamma=gamma, sampler=sampler, spacing=spacing,
                                         trajectory=trajectory)
-        mu, cells = self._rdo_of(images, None, rdo, target_bpp, max_bytes, price_map, price_cells, segment)
+        mu, cells = self._rdo_of(images, None, rdo, target_bpp, max_bytes, price_map, price_cells, segment, hyper_groups)
         rec, bpp, H, W, traj = self._frame_of(images, sample_steps, init, eta, seed, gamma, sampler, spacing, trajectory, trajectory_of,
                                               trajectory_dtype, rdo=mu, price_cells=cells)
         res = (self._window(rec, H, W), (bpp.mean() if bpp_return_mean else bpp))
@@ -844,14 +864,14 @@ class GaussianDiffusionX(_GaussianDiffusionBase):
 
     def compress_best_of(self, images, samples, metric="psnr", seed=None, gamma=None, eta=0, sample_steps=None, sampler="ddim",
                          spacing="index", sample_chunk=None, as_saved=True, rdo=None, target_bpp=None, max_bytes=None, price_map=None,
-                         price_cells=None, tile=None, tile_overlap=None, tile_chunk=None, segment=None):
+                         price_cells=None, tile=None, tile_overlap=None, tile_chunk=None, segment=None, hyper_groups=None):
         """The encoder's closed loop: the context model once, then `samples` seeded decodes per image (seeds
         parallel.sample_seeds(seed, B, samples)), each scored on the device against `images` on the frame's H x W window
         (metric "psnr" / "ms_ssim": higher is better; "lpips": lower, needs self.loss_fn_vgg; ties go to the lowest k, a NaN never
         beats a number) -> {"reconstruction": the winner's window, "bpp": [B], "seed": uint64 [B], ready for decompress(..., seed=),
         "sample": int [B], "score": [B], "scores": [B, samples]}.  rdo / target_bpp / max_bytes / price_map / price_cells: as compress().
-        tile / tile_overlap / tile_chunk: every candidate is a tiled decode (decompress states them).  segment: as compress()."""
-        mu, cells = self._rdo_of(images, None, rdo, target_bpp, max_bytes, price_map, price_cells, segment)
+        tile / tile_overlap / tile_chunk: every candidate is a tiled decode (decompress states them).  segment / hyper_groups: as compress()."""
+        mu, cells = self._rdo_of(images, None, rdo, target_bpp, max_bytes, price_map, price_cells, segment, hyper_groups)
         return self._best_of(images, samples, metric, seed, gamma, eta, sample_steps, sampler, spacing, sample_chunk, as_saved, True, rdo=mu,
                              price_cells=cells, tile_kw=dict(tile=tile, tile_overlap=tile_overlap, tile_chunk=tile_chunk))
 
@@ -895,18 +915,19 @@ class GaussianDiffusionEps(_GaussianDiffusionBase):
     def compress(self, images, sample_steps=None, bitrate_scale=None, sample_mode="ddpm",
                  bpp_return_mean=True, init=None, eta=0, seed=None, gamma=None, sampler="ddim", spacing="index",
                  trajectory=None, trajectory_of="x0", trajectory_dtype="float32", rdo=None, target_bpp=None, max_bytes=None,
-                 price_map=None, price_cells=None, tile=None, tile_overlap=None, tile_chunk=None, region=None, segment=None):
+                 price_map=None, price_cells=None, tile=None, tile_overlap=None, tile_chunk=None, region=None, segment=None,
+                 hyper_groups=None):
         """trajectory=: -> (reconstruction, bpp, Trajectory) (cdc_compression_amd.trajectory).  rdo / target_bpp / max_bytes /
-        price_map / price_cells / tile / tile_overlap / tile_chunk / region / segment: as GaussianDiffusionX.compress."""
+        price_map / price_cells / tile / tile_overlap / tile_chunk / region / segment / hyper_groups: as GaussianDiffusionX.compress."""
         if not (tile is None and tile_overlap is None and tile_chunk is None and region is None):
             if sample_mode != "ddim":
                 raise NotImplementedError('sample_mode "ddpm" raises AttributeError in the reference; only "ddim" is implemented')
             return self._compress_tiled(images, (bitrate_scale,), dict(rdo=rdo, target_bpp=target_bpp, max_bytes=max_bytes, price_map=price_map,
-                                                                      price_cells=price_cells, segment=segment),
+                                                                      price_cells=price_cells, segment=segment, hyper_groups=hyper_groups),
                                         bpp_return_mean, dict(tile=tile, tile_overlap=tile_overlap, tile_chunk=tile_chunk, region=region),
                                         sample_steps=sample_steps, init=init, eta=eta, seed=seed, gamma=gamma, sampler=sampler, spacing=spacing,
                                         trajectory=trajectory)
-        mu, cells = self._rdo_of(images, bitrate_scale, rdo, target_bpp, max_bytes, price_map, price_cells, segment)
+        mu, cells = self._rdo_of(images, bitrate_scale, rdo, target_bpp, max_bytes, price_map, price_cells, segment, hyper_groups)
         rec, bpp, H, W, traj = self._frame_of(images, sample_steps, bitrate_scale, sample_mode, init, eta, seed, gamma, sampler, spacing,
                                               trajectory, trajectory_of, trajectory_dtype, rdo=mu, price_cells=cells)
         res = (self._window(rec, H, W), (bpp.mean() if bpp_return_mean else bpp))
@@ -914,9 +935,9 @@ class GaussianDiffusionEps(_GaussianDiffusionBase):
 
     def compress_best_of(self, images, samples, metric="psnr", seed=None, gamma=None, eta=0, sample_steps=None, sampler="ddim",
                          spacing="index", sample_chunk=None, as_saved=True, bitrate_scale=None, rdo=None, target_bpp=None, max_bytes=None,
-                         price_map=None, price_cells=None, tile=None, tile_overlap=None, tile_chunk=None, segment=None):
+                         price_map=None, price_cells=None, tile=None, tile_overlap=None, tile_chunk=None, segment=None, hyper_groups=None):
         """GaussianDiffusionX.compress_best_of with this tree's context argument (bitrate_scale of a variable-bitrate model)."""
-        mu, cells = self._rdo_of(images, bitrate_scale, rdo, target_bpp, max_bytes, price_map, price_cells, segment)
+        mu, cells = self._rdo_of(images, bitrate_scale, rdo, target_bpp, max_bytes, price_map, price_cells, segment, hyper_groups)
         return self._best_of(images, samples, metric, seed, gamma, eta, sample_steps, sampler, spacing, sample_chunk, as_saved,
                              self.clip_noise, bitrate_scale, rdo=mu, price_cells=cells,
                              tile_kw=dict(tile=tile, tile_overlap=tile_overlap, tile_chunk=tile_chunk))

@@ -455,7 +455,7 @@ int cdc_bpp(cdc_handle *h, const float *q_hyper_latent, const float *q_latent, c
  * Synchronous; latent / hyper_latent / q_latent / q_hyper_latent follow `mem`, in / out / offsets / medians are host. */
 int cdc_entropy_encode(cdc_handle *h, const float *latent, const float *hyper_latent, const float *medians, int B,
                        int h_hyper, int w_hyper, unsigned char *out, size_t cap, size_t *offsets, int mem_kind, void *stream);
-/* Header fields of a version-3, -4, -5 or -6 stream, or of its segmented form 11 - 14 (below) (CDC_ERR_INVALID for anything else,
+/* Header fields of a version-3, -4, -5 or -6 stream, or of its segmented forms 11 - 14 and 19 - 22 (below) (CDC_ERR_INVALID for anything else,
  * a version-5 / -6 header whose recorded image size is 0 or beyond 2^31 - 1 on either side and a segmented stream whose index is
  * unsound included: every peek below refuses what this one refuses). */
 int cdc_entropy_peek(const unsigned char *in, size_t n, int *h_hyper, int *w_hyper, int *arith);
@@ -584,6 +584,37 @@ int cdc_entropy_peek_segments(const unsigned char *in, size_t n, int *seg, int *
 int cdc_entropy_decode_window(cdc_handle *h, const unsigned char *in, const size_t *offsets, const float *medians, int B,
                               const int32_t window[4] /* y0, x0, h, w in latent positions */, float *q_latent, float *q_hyper_latent,
                               int *segments_decoded, int mem_kind, void *stream);
+
+/* ---- grouped hyper part: container versions 19 - 22 (csrc/entropy.hip: the hgrp_* kernels) -----------------------------------------
+ * THE FORMAT.  Version 19 / 20 / 21 / 22 = version 11 / 12 / 13 / 14 + 8 (15 - 18 and 23 upwards are no stream and stay refused).  The
+ * fixed header is that of the base version 3 - 6 byte for byte but for the version byte, and the latent part is exactly that of
+ * versions 11 - 14.  n_hyper is the size of the whole hyper part (header + n_hyper + n_latent is still the stream's length),
+ * esc_hyper the sum over the groups, and `symbols` is the number the ungrouped stream of the same symbols carries.  The hyper part:
+ *   cg u16 | ng u16 | 0 u32                                    8 bytes (little endian)
+ *   ng x ( bytes u32 | esc u32 | checksum u32 )                the index, channel order of groups
+ *   group 0 | group 1 | ...                                    back to back, channel order
+ * cg = hyper channels per group, 1 .. Ch; ng = ceil(Ch / cg) groups, the last may be smaller; one group is allowed.  Group g holds the
+ * symbols of channels [g cg, min(Ch, (g + 1) cg)) in order (c, y, x), c slowest -- a contiguous range of the ungrouped hyper section;
+ * its bytes are exactly a section (64 lane states, renormalisation bytes, escape payloads) over those symbols in that order under
+ * their channels' tables -- symbol j of the group belongs to lane j % 64.  bytes / esc = its section size and escape count;
+ * checksum = sum of mix(0, i, symbol) over its symbols with i the symbol's index IN THE FULL HYPER SECTION, so that the group
+ * checksums add up to the hyper share of `symbols`.  Tables, model fingerprint, hyper_dec over the full frame and the batch = batch-1
+ * contract are unchanged.  A stream grows by 8 + 12 ng bytes and its groups' lane states: between 8 + 12 ng - 264 and 8 + 276 ng bytes
+ * over the one section (every section ends within 264 bytes of its symbols' ideal code length).
+ * cdc_entropy_set_hyper_groups: channels_per_group = 0 (the default): the streams and launches of cdc_entropy_set_segments alone;
+ *   1 .. Ch (the handle's hyper channels; CDC_ERR_INVALID beyond): versions 19 - 22, ng groups coded by ng waves per image.  Grouped
+ *   streams are segmented streams: an encode with groups set and cdc_entropy_set_segments at 0 returns CDC_ERR_INVALID.
+ * cdc_entropy_peek, _peek_bitrate_scale and _peek_image_size read versions 19 - 22 as their base versions 3 - 6,
+ *   cdc_entropy_peek_segments as 11 - 14.
+ * cdc_entropy_peek_hyper_groups: handle-free; cg = 0, ng = 1 for versions 3 - 6 and 11 - 14.  For 19 - 22 the hyper index is checked as
+ *   the segment index is, BY EVERY PEEK: header + n_hyper + n_latent = n; the 8 bytes with cg >= 1, ng >= 1 and the reserved zero;
+ *   every index entry has bytes >= 256 + 4 esc; 8 + 12 ng + sum bytes = n_hyper; sum esc = esc_hyper.  CDC_ERR_INVALID for anything else.
+ * cdc_entropy_decode and cdc_entropy_decode_window accept versions 19 - 22 and decode every group, always (hyper_dec needs the full
+ *   hyper frame), one wave per (group, image), straight into the frame.  Before anything is allocated cg <= Ch and ng = ceil(Ch / cg)
+ *   are checked against the handle's own channel count.  Every group's end conditions and checksum are checked -- errors name the image
+ *   and the group.  The streams of one call share one form, one seg and one cg (CDC_ERR_INVALID otherwise). */
+int cdc_entropy_set_hyper_groups(cdc_handle *hyperdec, int channels_per_group);
+int cdc_entropy_peek_hyper_groups(const unsigned char *in, size_t n, int *channels_per_group, int *groups);
 
 /* ---- distortion of decoded images: PSNR and MS-SSIM on the device (csrc/metric_kernels.hip) --------------------------------------
  * THE DEFINITION.  Operands: two image batches a, b, each [B][3][Hf][Wf] with Hf >= H, Wf >= W and its own element kind, frame size
