@@ -1068,6 +1068,7 @@ int build_program(cdc_handle *h, int B, int H, int W) {
 
     bd.emit(Op(PC_SMALL, TembArgs{h->in_time, h->tm_w0, h->tm_b0, h->tm_w2, h->tm_b2, h->cfg.dim, h->d_temb_layers, (int)h->rbs.size(),
                                   h->shift, h->shift_bs}));
+    bd.tap("temb", h->shift, 1, 1, h->shift_bs);          // (the shift table: row b holds mlp.1(LeakyReLU(time_mlp(t_b))) of every ResnetBlock at its shift_off)
 
     std::vector<Act> skips;
     size_t rbi = 0, ati = 0;
@@ -1134,11 +1135,15 @@ int build_program(cdc_handle *h, int B, int H, int W) {
         x = bd.resblock(h->rbs[rbi], x, &skip, nullptr, nullptr, Builder::SITE_RB_CHAIN,
                         bd.rb_reads_planes_only(h->rbs[rbi + 1], h->rbs[rbi].cout, x.H, x.W));
         ++rbi;
+        const std::string un = "ups." + std::to_string(i);
+        h->taps[un + ".0"] = x;
         x = bd.resblock(h->rbs[rbi++], x, nullptr, sm, sr);
+        h->taps[un + ".1"] = x;
         // (an Upsample reads fp32: planes of its input only with the development switch that runs it on conv_pf_kernel)
         // ... or, where the fused-phase plane-operand kernel takes it, planes INSTEAD of fp32 (the Upsample is the only reader)
         const bool up_planes = bd.pf_tz_would_plan(h->ups[i], x.H, x.W);
         x = bd.attention(h->attns[ati++], x, sm, sr, up_planes ? Builder::SITE_ALWAYS_PLANES : Builder::SITE_NONE, up_planes);
+        h->taps[un + ".2"] = x;
         const size_t first = h->ops.size();
         const ConvW &uw = h->ups[i];
         // the last Upsample feeds the final convolution only: planes INSTEAD of fp32 when that runs on the plane-operand kernel
@@ -1178,7 +1183,8 @@ int build_program(cdc_handle *h, int B, int H, int W) {
         bd.mark_planes_only(y, done);
         bd.require_planes_reader(x, first, "Upsample");
         x = y;
-        if (!final_ln_done) h->taps["ups." + std::to_string(i)] = x;   // (the last one may hold LN(up(x)) instead; a planes-only tensor is unpacked on demand: Act::pf)
+        if (!final_ln_done) h->taps[un] = x;   // (the last one may hold LN(up(x)) instead; a planes-only tensor is unpacked on demand: Act::pf)
+        else h->taps["final_conv.0"] = x;      // ... and is then tapped as what it holds: the final LayerNorm's output
         if (bd.rc) return bd.rc;
     }
     if (n == 1) {       // no Upsample stage: statistics of the last attention output

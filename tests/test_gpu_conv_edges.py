@@ -10,9 +10,9 @@ epilogue; every shape and switch set is one that tests/test_gpu_parity.py or tes
 any other way.  Where a shape the forms were listed for runs another family than expected (conv_ref.FORMS says which), it stays, under
 the family it runs, and the nearest shape of the suite that does run the named family is added.
 
-Out of scope: the forms that exist only inside a network program -- folded PreNorm (`pre`), per-image weights (`perimg`), hoisted
-partial sums (`pre_add` / HOIST), planes-only outputs, the unfolded first layer and the row-folded 1 x 7 final convolution; the network
-goldens keep covering them.
+The forms that exist only inside a network program -- folded PreNorm (`pre`), per-image weights (`perimg`), hoisted partial sums
+(`pre_add` / HOIST), planes-only outputs, the unfolded first layer and the row-folded 1 x 7 final convolution -- are checked stage by
+stage against float64 in tests/test_gpu_unet_edges.py.
 
 Every figure is printed before it is asserted (run with -s): per call the worst element with its error, bound, S and binade, and
 r = rms(err / S) against its limit; per family, at the end, the worst fraction of the bound and of the rms limit, whether every exact
