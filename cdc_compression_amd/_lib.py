@@ -53,6 +53,17 @@ class ImageView(ctypes.Structure):
                 ("as_saved", ctypes.c_int)]
 
 
+class StreamInfo(ctypes.Structure):
+    """cdc_stream_info of include/cdc_hip.h (cdc_entropy_peek_partial)."""
+    _fields_ = [("hh", ctypes.c_int), ("wh", ctypes.c_int), ("arith", ctypes.c_int), ("has_rate", ctypes.c_int), ("rate", ctypes.c_float),
+                ("has_size", ctypes.c_int), ("img_h", ctypes.c_int), ("img_w", ctypes.c_int), ("seg", ctypes.c_int), ("ny", ctypes.c_int),
+                ("nx", ctypes.c_int), ("cg", ctypes.c_int), ("ng", ctypes.c_int), ("complete", ctypes.c_int),
+                ("declared", ctypes.c_ulonglong), ("floor", ctypes.c_ulonglong)]
+
+
+SEG_OK, SEG_ABSENT, SEG_DAMAGED = 0, 1, 2                        # CDC_SEG_* of include/cdc_hip.h
+
+
 class CdcError(RuntimeError):
     pass
 
@@ -142,6 +153,9 @@ def lib():
                                             ctypes.POINTER(_i), _i, _vp]
     L.cdc_entropy_set_hyper_groups.argtypes = [H, _i]
     L.cdc_entropy_peek_hyper_groups.argtypes = [_vp, ctypes.c_size_t, ctypes.POINTER(_i), ctypes.POINTER(_i)]
+    L.cdc_entropy_peek_partial.argtypes = [_vp, ctypes.c_size_t, ctypes.POINTER(StreamInfo)]
+    L.cdc_entropy_decode_partial.argtypes = [H, _vp, ctypes.POINTER(ctypes.c_size_t), _vp, _i, ctypes.POINTER(ctypes.c_int32), _vp, _vp, _vp, _i, _vp]
+    L.cdc_segment_mask.argtypes = [H, _vp] + [_i] * 7 + [_vp, _i, _i, _vp]
     f64p = ctypes.POINTER(ctypes.c_double)
     L.cdc_distortion.argtypes = [H, ctypes.POINTER(ImageView), ctypes.POINTER(ImageView), _i, _i, _i, _i, f64p, f64p, f64p, _i, _vp]
     L.cdc_rate_map.argtypes = [H] + [_vp] * 9 + [_i, _i, _i, _i, _vp]
@@ -233,7 +247,8 @@ EXPORTS = ["cdc_create", "cdc_destroy", "cdc_last_error", "cdc_version", "cdc_nu
            "cdc_price_cells", "cdc_set_rdo_map", "cdc_op_rdo_quantize_map",
            "cdc_set_noise_frames", "cdc_randn_framed", "cdc_randn_framed_host", "cdc_tile_gather", "cdc_tile_blend",
            "cdc_entropy_set_segments", "cdc_entropy_peek_segments", "cdc_entropy_decode_window",
-           "cdc_entropy_set_hyper_groups", "cdc_entropy_peek_hyper_groups"]
+           "cdc_entropy_set_hyper_groups", "cdc_entropy_peek_hyper_groups",
+           "cdc_entropy_peek_partial", "cdc_entropy_decode_partial", "cdc_segment_mask"]
 
 
 def handle_status(handle):

@@ -989,7 +989,8 @@ class _ContextDecoder:
         return [raw[offs[b]: offs[b + 1]] for b in range(B)]
 
     def decompress_from_bytes(self, streams, like=None, return_hyper=False, max_image_hw=None, return_bitrate_scale=False,
-                              return_image_size=False, return_rate_map=False, window=None, return_segments=False):
+                              return_image_size=False, return_rate_map=False, window=None, return_segments=False, partial=False,
+                              return_status=False):
         """list of B bitstreams -> q_latent [B, C, h, w] exactly as the encoder dequantised it (numpy, or a tensor on
         `like`'s device); all streams must have the same latent size.  max_image_hw=(H, W): refuse streams whose header
         describes a larger image before anything is allocated (untrusted input; default: the library's 2^22-position bound).
@@ -1001,7 +1002,18 @@ class _ContextDecoder:
         window=(y0, x0, h, w) in LATENT positions (cdc_entropy_decode_window): of segmented streams only the segments that intersect
         it are decoded and verified; q_latent is full-size, equal to the full decode inside them and to hyper_decode's mean elsewhere.
         The header's checksum over all symbols is then not checked, and a corrupt segment outside the window is not noticed.
-        Unsegmented streams decode whole.  return_segments: also return (segments per image, segments decoded per image)."""
+        Unsegmented streams decode whole.  return_segments: also return (segments per image, segments decoded per image).
+        partial=True (cdc_entropy_decode_partial): every stream may be a prefix of a segmented stream (at least `stream_info(s)["floor"]`
+        bytes; each cut where it is) and may hold damaged segments.  The segments that are wholly there and pass their checks decode as
+        always; q_latent is hyper_decode's mean at every other position, and nothing is refused for them.  Sizes, rates and segments
+        come from `stream_info`.  return_status: also return, last, uint8 [B, ny, nx]: 0 decoded, 1 absent (not wholly there, or outside
+        window=), 2 damaged.  With partial the second number of return_segments counts the decoded (status 0) segments of IMAGE 0 only;
+        the status array is the full answer.  Excludes return_rate_map; unsegmented streams are refused (segment= at the encoder is
+        what makes a stream partial-decodable)."""
+        if return_status and not partial:
+            raise ValueError("return_status belongs to partial=True")
+        if partial and return_rate_map:
+            raise ValueError("partial=True excludes return_rate_map: the concealed symbols have no price")
         if window is not None:
             window = tuple(int(v) for v in window)
             if len(window) != 4 or window[0] < 0 or window[1] < 0 or window[2] < 1 or window[3] < 1:
@@ -1020,7 +1032,11 @@ class _ContextDecoder:
         B = len(streams)
         hh, wh, ar = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         dims = set()
-        for s in streams:
+        infos = [self.stream_info(s) for s in streams] if partial else None
+        for b, s in enumerate(streams):
+            if partial:
+                dims.add((infos[b]["hh"], infos[b]["wh"]))
+                continue
             if L.cdc_entropy_peek(s, len(s), ctypes.byref(hh), ctypes.byref(wh), ctypes.byref(ar)) != 0:
                 raise _lib.CdcError("not a CDC bitstream")
             dims.add((hh.value, wh.value))
@@ -1040,6 +1056,29 @@ class _ContextDecoder:
             pos += len(s)
         offs[B] = pos
         med = self._median_vector()
+        if partial:
+            grids = {(i["seg"], i["ny"], i["nx"]) for i in infos}
+            if len(grids) != 1:
+                raise _lib.CdcError("the streams of one call must share the segment size")
+            _, ny, nx = grids.pop()
+            status = np.full((B, ny, nx), _lib.SEG_ABSENT, np.uint8)
+            _lib.check(h, L.cdc_entropy_decode_partial(h, blob, offs, med.ctypes.data, B, None if window is None else (ctypes.c_int32 * 4)(*window),
+                                                       pq, ph, status.ctypes.data, mem, _current_stream(mem)))
+            out = (q, qh) if return_hyper else (q,)
+            if return_bitrate_scale:
+                if self.vbr and not all(i["has_rate"] for i in infos):
+                    raise _lib.CdcError("a fixed-rate (version 3) stream carries no bitrate_scale")
+                out = out + (np.float32([i["rate"] for i in infos]) if self.vbr else None,)
+            if return_image_size:
+                sizes = {(i["img_h"], i["img_w"]) if i["has_size"] else (i["hh"] * self.frame_multiple, i["wh"] * self.frame_multiple) for i in infos}
+                if len(sizes) != 1:
+                    raise _lib.CdcError("the streams of one call must share the image size")
+                out = out + (sizes.pop(),)
+            if return_segments:
+                out = out + ((ny * nx, int((status[0] == _lib.SEG_OK).sum())),)
+            if return_status:
+                out = out + (status,)
+            return out if len(out) > 1 else out[0]
         if window is None:
             _lib.check(h, L.cdc_entropy_decode(h, blob, offs, med.ctypes.data, B, pq, ph, mem, _current_stream(mem)))
         else:
@@ -1074,6 +1113,52 @@ class _ContextDecoder:
             if L.cdc_entropy_peek_segments(s, len(s), ctypes.byref(seg), ctypes.byref(ny), ctypes.byref(nx)) != 0:
                 raise _lib.CdcError("not a CDC bitstream")
             out.append((seg.value, ny.value, nx.value))
+        return out
+
+    @staticmethod
+    def stream_info(stream):
+        """cdc_entropy_peek_partial (no handle needed) of a segmented stream or a prefix of one, as a dict: hh, wh, arith, has_rate, rate,
+        has_size, img_h, img_w, seg, ny, nx, cg, ng; "declared", the length of the whole stream as its header states it; "floor", the
+        bytes up to the end of the segment index (less than that decodes nothing and is refused); "complete", the leading segments, in
+        raster order, that lie wholly inside the bytes given.  The `*_of` helpers refuse prefixes; this one refuses unsegmented streams."""
+        s = bytes(stream)
+        info = _lib.StreamInfo()
+        if _lib.lib().cdc_entropy_peek_partial(s, len(s), ctypes.byref(info)) != 0:
+            if len(s) >= 4 and s[:3] == b"CDC" and s[3] in (3, 4, 5, 6):
+                raise _lib.CdcError(f"an unsegmented stream (version {s[3]}) is one section with nothing independent in it: segment= at the "
+                                    "encoder is what makes a stream partial-decodable")
+            raise _lib.CdcError("not a segmented CDC bitstream, or a prefix that ends before its segment index does (or is longer than the "
+                                "stream its header declares)")
+        out = {k: getattr(info, k) for k, _ in _lib.StreamInfo._fields_}
+        for k in ("has_rate", "has_size"):
+            out[k] = bool(out[k])
+        return out
+
+    @staticmethod
+    def segment_ends(stream):
+        """The byte lengths at which segments 0 .. n - 1 of a segmented stream (or of a prefix of at least `floor` bytes) complete, in
+        raster order: a prefix of segment_ends(s)[k] bytes holds segments 0 .. k whole.  The last one is the declared length."""
+        s = bytes(stream)
+        info = _ContextDecoder.stream_info(s)
+        n, floor = info["ny"] * info["nx"], info["floor"]
+        sizes = np.frombuffer(s[floor - 12 * n: floor], dtype="<u4").reshape(n, 3)[:, 0].astype(np.int64)
+        return [int(v) for v in floor + np.cumsum(sizes)]
+
+    def segment_mask(self, status, seg, image_hw, as_uint8=False, like=None):
+        """cdc_segment_mask: the status array [B, ny, nx] of `decompress_from_bytes(partial=True, return_status=True)` as a per-pixel mask
+        [B, 1, H, W] of the H x W image: 1.0 (255 with as_uint8) where the pixel's latent position lies in a decoded segment, else 0.
+        seg: the streams' segment side in latent positions (`stream_info(s)["seg"]`); like: a tensor whose device the mask goes to."""
+        status = np.ascontiguousarray(status, np.uint8)
+        if status.ndim != 3:
+            raise ValueError(f"status must be [B, ny, nx], got {status.shape}")
+        B, ny, nx = status.shape
+        H, W = int(image_hw[0]), int(image_hw[1])
+        proto = like if like is not None else np.empty(0, np.float32)
+        out, ptr = frame._empty_like(proto, (B, 1, H, W), bool(as_uint8))
+        mem = _lib.CDC_MEM_DEVICE if _is_torch(out) and out.is_cuda else _lib.CDC_MEM_HOST
+        h = self._hyper_handle()
+        _lib.check(h, _lib.lib().cdc_segment_mask(h, status.ctypes.data, B, ny, nx, int(seg), int(self.rate_map_cell), H, W, ptr,
+                                                  _lib.CDC_ELEM_U8 if as_uint8 else _lib.CDC_ELEM_F32, mem, _current_stream(mem)))
         return out
 
     @staticmethod

@@ -58,16 +58,19 @@ inline uint32_t get_u32(const unsigned char *s) { uint32_t v = 0; for (int i = 0
 inline uint32_t get_u16(const unsigned char *s) { return (uint32_t)s[0] | ((uint32_t)s[1] << 8); }
 // The segmented latent part of a version-11 .. -14 stream s[0 .. n) whose fixed header is complete: everything a reader without a
 // handle can check (include/cdc_hip.h lists it).  -> false: no stream.  index: the first index entry; first: where segment 0 starts.
+// whole = false (cdc_entropy_peek_partial): s[0 .. n) is a prefix -- header + n_hyper + n_latent = n is replaced by first <= n <= that
+// sum (the index is required whole), and every other rule stays.
 struct SegLayout { int seg = 0, ny = 1, nx = 1; const unsigned char *index = nullptr; size_t first = 0; };
-bool parse_segments(const unsigned char *s, size_t n, SegLayout *out) {
+bool parse_segments(const unsigned char *s, size_t n, SegLayout *out, bool whole = true) {
     const unsigned long long hdr = (unsigned long long)stream_header(s), nbh = get_u32(s + 10), nbl = get_u32(s + 14), el = get_u32(s + 30);
-    if (hdr + nbh + nbl != (unsigned long long)n || nbl < (unsigned long long)kSegHeader) return false;
+    if (nbl < (unsigned long long)kSegHeader) return false;
+    if (whole ? hdr + nbh + nbl != (unsigned long long)n : (hdr + nbh + kSegHeader > (unsigned long long)n || hdr + nbh + nbl < (unsigned long long)n)) return false;
     const unsigned char *p = s + hdr + nbh;
     const uint32_t seg = get_u16(p), ny = get_u16(p + 2), nx = get_u16(p + 4), zero = get_u16(p + 6);
     const unsigned long long S = (unsigned long long)ny * nx;
     if (seg < 1 || S < 1 || S > (unsigned long long)kMaxSegments || zero != 0) return false;
     const unsigned long long fixed = kSegHeader + kSegIndexEntry * S;
-    if (nbl < fixed) return false;
+    if (nbl < fixed || hdr + nbh + fixed > (unsigned long long)n) return false;
     unsigned long long bytes = 0, esc = 0;
     for (unsigned long long i = 0; i < S; ++i) {
         const unsigned char *e = p + kSegHeader + kSegIndexEntry * i;
@@ -85,14 +88,15 @@ bool parse_segments(const unsigned char *s, size_t n, SegLayout *out) {
 // The grouped hyper part of a version-19 .. -22 stream s[0 .. n) whose fixed header is complete, checked as parse_segments checks the
 // latent part.  index: the first index entry; first: where group 0 starts.
 struct GroupLayout { int cg = 0, ng = 1; const unsigned char *index = nullptr; size_t first = 0; };
-bool parse_hyper_groups(const unsigned char *s, size_t n, GroupLayout *out) {
+bool parse_hyper_groups(const unsigned char *s, size_t n, GroupLayout *out, bool whole = true) {
     const unsigned long long hdr = (unsigned long long)stream_header(s), nbh = get_u32(s + 10), nbl = get_u32(s + 14), eh = get_u32(s + 26);
-    if (hdr + nbh + nbl != (unsigned long long)n || nbh < (unsigned long long)kGrpHeader) return false;
+    if (nbh < (unsigned long long)kGrpHeader) return false;
+    if (whole ? hdr + nbh + nbl != (unsigned long long)n : (hdr + kGrpHeader > (unsigned long long)n || hdr + nbh + nbl < (unsigned long long)n)) return false;
     const unsigned char *p = s + hdr;
     const uint32_t cg = get_u16(p), ng = get_u16(p + 2), zero = get_u32(p + 4);
     if (cg < 1 || ng < 1 || zero != 0) return false;
     const unsigned long long fixed = kGrpHeader + (unsigned long long)kGrpIndexEntry * ng;
-    if (nbh < fixed) return false;
+    if (nbh < fixed || hdr + fixed > (unsigned long long)n) return false;
     unsigned long long bytes = 0, esc = 0;
     for (uint32_t i = 0; i < ng; ++i) {
         const unsigned char *e = p + kGrpHeader + (size_t)kGrpIndexEntry * i;
@@ -391,12 +395,15 @@ int rate_sweep_impl(cdc_handle *h, const float *latent, const float *hyper_laten
     return CDC_OK;
 }
 
-// window = null: cdc_entropy_decode; else cdc_entropy_decode_window (y0, x0, h, w in latent positions; *segments_decoded per image)
+// window = null: cdc_entropy_decode; else cdc_entropy_decode_window (y0, x0, h, w in latent positions; *segments_decoded per image).
+// status != null: cdc_entropy_decode_partial -- every stream may be a prefix (its length is what offsets say), a segment that is not
+// wholly there is no job, a segment that fails its checks is concealed instead of refused; status [B][S] (host) says which is which.
 int entropy_decode_impl(cdc_handle *h, const unsigned char *in, const size_t *offsets, const float *medians, int B, const int32_t *window,
-                        float *q_latent, float *q_hyper_latent, int *segments_decoded, int mem, void *stream) {
+                        float *q_latent, float *q_hyper_latent, int *segments_decoded, unsigned char *status, int mem, void *stream) {
     int rc = check_ready(h);
     if (rc) return rc;
     if (!in || !offsets || !medians || !q_latent || B < 1) return fail(h, CDC_ERR_INVALID, "null/invalid argument");
+    const bool partial = status != nullptr;
     if ((rc = ensure_entropy(h, medians))) return rc;
     hipStream_t st = h->own_stream;
     // the outputs may be device buffers that queued work of the caller's stream still uses
@@ -414,10 +421,19 @@ int entropy_decode_impl(cdc_handle *h, const unsigned char *in, const size_t *of
         const unsigned char *s = in + offsets[b];
         const size_t n = offsets[b + 1] - offsets[b];
         Hdr &q = hd[b];
-        if (cdc_entropy_peek(s, n, &q.hh, &q.wh, &q.ar)) return fail(h, CDC_ERR_INVALID, "image %d: not a CDC bitstream (version %d / %d / %d / %d container)", b, kStreamVersion, kStreamVersionVbr, kStreamVersionSized, kStreamVersionVbrSized);
+        if (partial && n >= 4 && s[0] == 'C' && s[1] == 'D' && s[2] == 'C' && version_known(s[3]) && !version_segmented(s[3]))
+            return fail(h, CDC_ERR_INVALID, "image %d: an unsegmented stream (version %d) is one section with nothing independent in it: segment= at the "
+                        "encoder is what makes a stream partial-decodable", b, (int)s[3]);
+        cdc_stream_info pi;
+        if (partial && cdc_entropy_peek_partial(s, n, &pi))
+            return fail(h, CDC_ERR_INVALID, "image %d: not a segmented CDC bitstream, or a prefix that ends before its segment index does (or is longer "
+                        "than the stream its header declares)", b);
+        if (!partial && cdc_entropy_peek(s, n, &q.hh, &q.wh, &q.ar)) return fail(h, CDC_ERR_INVALID, "image %d: not a CDC bitstream (version %d / %d / %d / %d container)", b, kStreamVersion, kStreamVersionVbr, kStreamVersionSized, kStreamVersionVbrSized);
+        if (partial) { q.hh = pi.hh; q.wh = pi.wh; q.ar = pi.arith; }
         int has_rate = 0;
         q.rate = 0.f;
-        (void)cdc_entropy_peek_bitrate_scale(s, n, &has_rate, &q.rate);
+        if (partial) { has_rate = pi.has_rate; q.rate = pi.rate; }
+        else (void)cdc_entropy_peek_bitrate_scale(s, n, &has_rate, &q.rate);
         if (has_rate != (h->vbr ? 1 : 0))
             return fail(h, CDC_ERR_INVALID, h->vbr ? "image %d: a fixed-rate stream (version 3 / 5) given to a variable-bitrate model"
                                                    : "image %d: a variable-bitrate stream (version 4 / 6) given to a fixed-rate model", b);
@@ -427,7 +443,8 @@ int entropy_decode_impl(cdc_handle *h, const unsigned char *in, const size_t *of
             return fail(h, CDC_ERR_INVALID, "image %d: hyper-latent size %d x %d in the stream header exceeds the decoder's limit of %d positions "
                         "(cdc_entropy_set_limit)", b, q.hh, q.wh, std::min(kMaxHyperPositions, h->ent_max_positions));
         int has_size = 0, ih = 0, iw = 0;
-        (void)cdc_entropy_peek_image_size(s, n, &has_size, &ih, &iw);
+        if (partial) { has_size = pi.has_size; ih = pi.img_h; iw = pi.img_w; }
+        else (void)cdc_entropy_peek_image_size(s, n, &has_size, &ih, &iw);
         if (has_size) {
             const int D = h->ent_pixels;
             if (D < 1) return fail(h, CDC_ERR_STATE, "image %d: the stream records an image size; cdc_entropy_set_image_scale has not been called on this handle", b);
@@ -439,21 +456,22 @@ int entropy_decode_impl(cdc_handle *h, const unsigned char *in, const size_t *of
         else if (ih != img0_h || iw != img0_w) return fail(h, CDC_ERR_INVALID, "image %d: its recorded size differs from image 0's (one call decodes one image size)", b);
         if (q.ar != CDC_ARITH_BF16X3 && q.ar != CDC_ARITH_F16X2) return fail(h, CDC_ERR_INVALID, "image %d: unknown arithmetic %d", b, q.ar);
         q.nbh = get_u32(s + 10); q.nbl = get_u32(s + 14); q.sum = get_u32(s + 22); q.eh = get_u32(s + 26); q.el = get_u32(s + 30);
-        if ((unsigned long long)q.hdr + q.nbh + q.nbl != n) return fail(h, CDC_ERR_INVALID, "image %d: truncated bitstream", b);
+        // (a partial stream: cdc_entropy_peek_partial has bounded n by the index's end and the declared length)
+        if (!partial && (unsigned long long)q.hdr + q.nbh + q.nbl != n) return fail(h, CDC_ERR_INVALID, "image %d: truncated bitstream", b);
         if (get_u32(s + 18) != h->ent_model_hash)
             return fail(h, CDC_ERR_INVALID, "image %d: the stream was coded with other probability tables (prior parameters, medians, library build or libm differ)", b);
         if (4ull * q.eh + 256 > q.nbh || 4ull * q.el + 256 > q.nbl) return fail(h, CDC_ERR_INVALID, "image %d: corrupt section sizes", b);
         if (q.hh != hd[0].hh || q.wh != hd[0].wh)
             return fail(h, CDC_ERR_INVALID, "image %d: %d x %d hyper-latent in a batch of %d x %d (one call decodes one image size)", b, q.hh, q.wh, hd[0].hh, hd[0].wh);
         if (version_segmented(s[3])) {                     // (cdc_entropy_peek has validated the index against the header)
-            if (!parse_segments(s, n, &q.lay)) return fail(h, CDC_ERR_INVALID, "image %d: corrupt segment index", b);
+            if (!parse_segments(s, n, &q.lay, !partial)) return fail(h, CDC_ERR_INVALID, "image %d: corrupt segment index", b);
             const long long Hl = (long long)U * q.hh, Wl = (long long)U * q.wh;
             if (q.lay.ny != (Hl + q.lay.seg - 1) / q.lay.seg || q.lay.nx != (Wl + q.lay.seg - 1) / q.lay.seg)
                 return fail(h, CDC_ERR_INVALID, "image %d: %d x %d segments of %d positions do not tile this model's %lld x %lld latent grid", b, q.lay.ny,
                             q.lay.nx, q.lay.seg, Hl, Wl);
         }
         if (version_grouped(s[3])) {                       // (likewise validated by cdc_entropy_peek)
-            if (!parse_hyper_groups(s, n, &q.grp)) return fail(h, CDC_ERR_INVALID, "image %d: corrupt hyper group index", b);
+            if (!parse_hyper_groups(s, n, &q.grp, !partial)) return fail(h, CDC_ERR_INVALID, "image %d: corrupt hyper group index", b);
             if (q.grp.cg > Ch || q.grp.ng != (Ch + q.grp.cg - 1) / q.grp.cg)
                 return fail(h, CDC_ERR_INVALID, "image %d: %d hyper groups of %d channels do not cover this model's %d hyper channels", b, q.grp.ng,
                             q.grp.cg, Ch);
@@ -550,14 +568,20 @@ int entropy_decode_impl(cdc_handle *h, const unsigned char *in, const size_t *of
             make_seg_table(o.C / 2, o.H, o.W, seg, &segs);
             std::vector<cdc::SegJob> jobs;
             std::vector<uint32_t> want;                    // the index's checksum of every job's segment
+            size_t in_window = 0;                          // (image, segment) pairs the window selects, there or not
             for (int b = b0; b < b1; ++b) {
                 long long at = (long long)(offsets[b] - offsets[0]) + (long long)hd[b].lay.first;
+                const long long stop = (long long)(offsets[b + 1] - offsets[0]);      // where the bytes given of image b end
                 for (int s = 0; s < S; ++s) {
                     const unsigned char *ix = hd[b].lay.index + (size_t)kSegIndexEntry * s;
                     const cdc::SegEntry &e = segs.e[s];
+                    if (partial) status[(size_t)b * S + s] = CDC_SEG_ABSENT;
                     if (e.y0 < win.y0 + win.h && win.y0 < e.y0 + e.h && e.x0 < win.x0 + win.w && win.x0 < e.x0 + e.w) {
-                        jobs.push_back(cdc::SegJob{at, (int)get_u32(ix), (int)get_u32(ix + 4), b - b0, s});
-                        want.push_back(get_u32(ix + 8));
+                        ++in_window;
+                        if (!partial || at + (long long)get_u32(ix) <= stop) {       // a partial stream: no job reaches past the bytes given
+                            jobs.push_back(cdc::SegJob{at, (int)get_u32(ix), (int)get_u32(ix + 4), b - b0, s});
+                            want.push_back(get_u32(ix + 8));
+                        }
                     }
                     at += get_u32(ix);
                 }
@@ -572,14 +596,16 @@ int entropy_decode_impl(cdc_handle *h, const unsigned char *in, const size_t *of
             HIP_TRY(h, d.get(&d_tab, (size_t)S)); HIP_TRY(h, d.get(&d_jobs, jobs.size())); HIP_TRY(h, d.get(&jmeta, jobs.size()));
             HIP_TRY(h, d.get(&bin_seg, (size_t)nb * nl)); HIP_TRY(h, d.get(&sym_seg, (size_t)nb * nl)); HIP_TRY(h, d.get(&sums, (size_t)nb * S));
             HIP_TRY(h, hipMemcpyAsync(d_tab, segs.e.data(), sizeof(cdc::SegEntry) * S, hipMemcpyHostToDevice, st));
-            HIP_TRY(h, hipMemcpyAsync(d_jobs, jobs.data(), sizeof(cdc::SegJob) * jobs.size(), hipMemcpyHostToDevice, st));
+            if (!jobs.empty()) HIP_TRY(h, hipMemcpyAsync(d_jobs, jobs.data(), sizeof(cdc::SegJob) * jobs.size(), hipMemcpyHostToDevice, st));
+            // a selected segment that is not there has no wave to write its symbols: they are 0 (q_latent = mean) before the scatter reads them
+            if (jobs.size() < in_window) HIP_TRY(h, hipMemsetAsync(sym_seg, 0, sizeof(int32_t) * (size_t)nb * nl, st));
             HIP_TRY(h, cdc::seg_gather_bins_launch(d_tab, S, segs.max_n, win, bin, nl, o.H, o.W, nb, bin_seg, st));
-            HIP_TRY(h, cdc::seg_decode_launch(T, d_tab, d_jobs, (int)jobs.size(), d_in, bin_seg, nl, Ch, sym_seg, jmeta, st));
+            if (!jobs.empty()) HIP_TRY(h, cdc::seg_decode_launch(T, d_tab, d_jobs, (int)jobs.size(), d_in, bin_seg, nl, Ch, sym_seg, jmeta, st));
             HIP_TRY(h, cdc::seg_scatter_launch(d_tab, S, segs.max_n, win, sym_seg, nl, o.H, o.W, nb, syml, sums, st));
             std::vector<cdc::RansMeta> jm(jobs.size());
             std::vector<uint32_t> hs((size_t)nb * S);
             HIP_TRY(h, hipMemcpyAsync(hm.data(), meta, sizeof(cdc::RansMeta) * nb, hipMemcpyDeviceToHost, st));
-            HIP_TRY(h, hipMemcpyAsync(jm.data(), jmeta, sizeof(cdc::RansMeta) * jm.size(), hipMemcpyDeviceToHost, st));
+            if (!jobs.empty()) HIP_TRY(h, hipMemcpyAsync(jm.data(), jmeta, sizeof(cdc::RansMeta) * jm.size(), hipMemcpyDeviceToHost, st));
             HIP_TRY(h, hipMemcpyAsync(hs.data(), sums, sizeof(uint32_t) * hs.size(), hipMemcpyDeviceToHost, st));
             std::vector<cdc::RansMeta> gm(gjobs.size());
             if (ng) HIP_TRY(h, hipMemcpyAsync(gm.data(), gmeta, sizeof(cdc::RansMeta) * gm.size(), hipMemcpyDeviceToHost, st));
@@ -597,8 +623,17 @@ int entropy_decode_impl(cdc_handle *h, const unsigned char *in, const size_t *of
             for (int b = b0; b < b1; ++b)
                 if (hm[b - b0].bad) return fail(h, CDC_ERR_INVALID, "image %d: corrupt hyper stream", b);
             std::vector<uint32_t> total((size_t)nb, 0u);
+            std::vector<int> n_ok((size_t)nb, 0);           // partial: segments of the image that hold
+            std::vector<cdc::SegPair> damaged;
             for (size_t j = 0; j < jobs.size(); ++j) {
                 const int b = b0 + jobs[j].b, s = jobs[j].s;
+                if (partial) {                             // the same two checks: a verdict per segment instead of a refusal
+                    const bool ok = !jm[j].bad && hs[(size_t)jobs[j].b * S + s] == want[j];
+                    status[(size_t)b * S + s] = ok ? CDC_SEG_OK : CDC_SEG_DAMAGED;
+                    if (ok) { total[jobs[j].b] += want[j]; ++n_ok[jobs[j].b]; }
+                    else damaged.push_back(cdc::SegPair{jobs[j].b, s});
+                    continue;
+                }
                 if (jm[j].bad)
                     return fail(h, CDC_ERR_INVALID, "image %d, segment %d (row %d, column %d): corrupt latent segment (or this decoder's hyper-decoder "
                                 "output differs from the encoder's)", b, s, s / hd[b].lay.nx, s % hd[b].lay.nx);
@@ -608,10 +643,18 @@ int entropy_decode_impl(cdc_handle *h, const unsigned char *in, const size_t *of
                 total[jobs[j].b] += want[j];
             }
             // the header's checksum covers every symbol: checked when every segment was decoded (never by a window: include/cdc_hip.h)
+            // (a partial stream: for an image exactly when all its segments hold -- the result is then cdc_entropy_decode's)
             for (int b = b0; b < b1 && !window; ++b)
-                if (hm[b - b0].checksum + total[b - b0] != hd[b].sum)
+                if ((!partial || n_ok[b - b0] == S) && hm[b - b0].checksum + total[b - b0] != hd[b].sum)
                     return fail(h, CDC_ERR_INVALID, "image %d: symbol checksum mismatch -- this decoder's hyper-decoder output differs from the encoder's "
                                                    "(other library build, development switches or GPU), or the payload is corrupt", b);
+            if (!damaged.empty()) {                        // their symbols are in the frame already: back to 0, in one launch
+                cdc::SegPair *d_pairs;
+                HIP_TRY(h, d.get(&d_pairs, damaged.size()));
+                HIP_TRY(h, hipMemcpyAsync(d_pairs, damaged.data(), sizeof(cdc::SegPair) * damaged.size(), hipMemcpyHostToDevice, st));
+                HIP_TRY(h, cdc::seg_conceal_launch(d_tab, segs.max_n, d_pairs, (int)damaged.size(), nl, o.H, o.W, syml, st));
+                HIP_TRY(h, hipStreamSynchronize(st));      // (`damaged` is pageable host memory that goes with this scope)
+            }
         } else {
             HIP_TRY(h, cdc::rans_decode_launch(T, d_in, d_off + nb, d_len + nb, d_esc + nb, bin, nl, 0, Ch, (int)nl, 1u, nb, syml, nl, meta + nb, st));
             HIP_TRY(h, hipMemcpyAsync(hm.data(), meta, sizeof(cdc::RansMeta) * hm.size(), hipMemcpyDeviceToHost, st));
@@ -791,14 +834,50 @@ int cdc_entropy_set_limit(cdc_handle *h, int max_hyper_positions) {
     return CDC_OK;
 }
 
-int cdc_entropy_peek(const unsigned char *in, size_t n, int *hh, int *wh, int *arith) {
+// the fixed header of in[0 .. n), whole or a prefix: magic, version, the header's own length, a recorded size in range
+static bool fixed_header_ok(const unsigned char *in, size_t n) {
     if (!in || n < (size_t)kStreamHeader || in[0] != 'C' || in[1] != 'D' || in[2] != 'C' ||
-        !version_known(in[3]) || n < (size_t)stream_header(in)) return CDC_ERR_INVALID;
+        !version_known(in[3]) || n < (size_t)stream_header(in)) return false;
     if (version_sized(in[3])) {                           // a recorded size is 1 .. 2^31 - 1 on both sides: anything else is no stream
         const unsigned char *f = in + stream_header(in) - kStreamSizeField;
         const uint32_t uh = get_u32(f), uw = get_u32(f + 4);
-        if (uh < 1 || uw < 1 || uh > (uint32_t)INT32_MAX || uw > (uint32_t)INT32_MAX) return CDC_ERR_INVALID;
+        if (uh < 1 || uw < 1 || uh > (uint32_t)INT32_MAX || uw > (uint32_t)INT32_MAX) return false;
     }
+    return true;
+}
+
+int cdc_entropy_peek_partial(const unsigned char *in, size_t n, cdc_stream_info *info) {
+    if (!info || !fixed_header_ok(in, n) || !version_segmented(in[3])) return CDC_ERR_INVALID;
+    SegLayout lay;
+    GroupLayout grp;
+    if (version_grouped(in[3]) && !parse_hyper_groups(in, n, &grp, false)) return CDC_ERR_INVALID;
+    if (!parse_segments(in, n, &lay, false)) return CDC_ERR_INVALID;      // (floor <= n <= declared among its rules)
+    cdc_stream_info q;
+    memset(&q, 0, sizeof q);
+    q.arith = in[4]; q.hh = in[6] | (in[7] << 8); q.wh = in[8] | (in[9] << 8);
+    q.has_rate = version_vbr(in[3]) ? 1 : 0;
+    if (q.has_rate) { const uint32_t u = get_u32(in + kStreamHeader); memcpy(&q.rate, &u, 4); }
+    q.has_size = version_sized(in[3]) ? 1 : 0;
+    if (q.has_size) {
+        const unsigned char *f = in + stream_header(in) - kStreamSizeField;
+        q.img_h = (int)get_u32(f); q.img_w = (int)get_u32(f + 4);
+    }
+    q.seg = lay.seg; q.ny = lay.ny; q.nx = lay.nx;
+    q.cg = grp.cg; q.ng = grp.ng;
+    q.declared = (unsigned long long)stream_header(in) + get_u32(in + 10) + get_u32(in + 14);
+    q.floor = (unsigned long long)lay.first;
+    unsigned long long at = q.floor;
+    for (int s = 0; s < lay.ny * lay.nx; ++s) {
+        at += get_u32(lay.index + (size_t)kSegIndexEntry * s);
+        if (at > (unsigned long long)n) break;
+        ++q.complete;
+    }
+    *info = q;
+    return CDC_OK;
+}
+
+int cdc_entropy_peek(const unsigned char *in, size_t n, int *hh, int *wh, int *arith) {
+    if (!fixed_header_ok(in, n)) return CDC_ERR_INVALID;
     if (version_segmented(in[3])) {                       // a segmented stream is one whose index is sound: for every peek
         SegLayout lay;
         if (!parse_segments(in, n, &lay)) return CDC_ERR_INVALID;
@@ -870,14 +949,53 @@ int cdc_entropy_set_segments(cdc_handle *h, int seg) {
 
 int cdc_entropy_decode(cdc_handle *h, const unsigned char *in, const size_t *offsets, const float *medians, int B,
                        float *q_latent, float *q_hyper_latent, int mem, void *stream) {
-    return no_throw(h, [&] { return entropy_decode_impl(h, in, offsets, medians, B, nullptr, q_latent, q_hyper_latent, nullptr, mem, stream); });
+    return no_throw(h, [&] { return entropy_decode_impl(h, in, offsets, medians, B, nullptr, q_latent, q_hyper_latent, nullptr, nullptr, mem, stream); });
+}
+
+int cdc_entropy_decode_partial(cdc_handle *h, const unsigned char *in, const size_t *offsets, const float *medians, int B, const int32_t *window,
+                               float *q_latent, float *q_hyper_latent, unsigned char *status, int mem, void *stream) {
+    return no_throw(h, [&]() -> int {
+        if (h && !status) return fail(h, CDC_ERR_INVALID, "null/invalid argument");
+        return entropy_decode_impl(h, in, offsets, medians, B, window, q_latent, q_hyper_latent, nullptr, status, mem, stream);
+    });
+}
+
+int cdc_segment_mask(cdc_handle *h, const unsigned char *status, int B, int ny, int nx, int seg, int cell, int img_h, int img_w, void *out,
+                     int elem, int mem, void *stream) {
+    if (!h) return CDC_ERR_INVALID;
+    return no_throw(h, [&] {
+        return with_range_guard(h, [&]() -> int {
+            if (!status || !out || B < 1 || ny < 1 || nx < 1 || (long long)ny * nx > kMaxSegments || seg < 1 || cell < 1 || img_h < 1 || img_w < 1)
+                return fail(h, CDC_ERR_INVALID, "segment_mask: null/invalid argument");
+            if (elem != CDC_ELEM_F32 && elem != CDC_ELEM_U8) return fail(h, CDC_ERR_INVALID, "segment_mask: element kind %d", elem);
+            if (mem != CDC_MEM_HOST && mem != CDC_MEM_DEVICE) return fail(h, CDC_ERR_INVALID, "segment_mask: mem_kind %d", mem);
+            const long long span = (long long)seg * cell;      // pixels per segment and side
+            if (img_h > span * ny || img_w > span * nx)
+                return fail(h, CDC_ERR_INVALID, "segment_mask: a %d x %d image is larger than %d x %d segments of %d positions of %d pixels", img_h, img_w,
+                            ny, nx, seg, cell);
+            if ((long long)B * img_h * img_w > (1ll << 40)) return fail(h, CDC_ERR_INVALID, "segment_mask: %d x %d x %d pixels", B, img_h, img_w);
+            const size_t S = (size_t)ny * nx;
+            for (size_t i = 0; i < (size_t)B * S; ++i)
+                if (status[i] > CDC_SEG_DAMAGED) return fail(h, CDC_ERR_INVALID, "segment_mask: status[%zu] = %d (0, 1 or 2 expected)", i, (int)status[i]);
+            const int u8 = elem == CDC_ELEM_U8;
+            if (int rc = ensure_device(h)) return rc;          // (the argument rules above need no device)
+            hipStream_t st = pick_stream(h, stream, mem);
+            Staging s(h, mem, st);
+            uint8_t *d_status = (uint8_t *)s.scratch((size_t)B * S);
+            if (s.ok()) s.e = hipMemcpyAsync(d_status, status, (size_t)B * S, hipMemcpyHostToDevice, st);
+            void *dd = s.out(out, (size_t)B * img_h * img_w * (u8 ? 1 : 4));
+            if (s.ok()) s.e = cdc::seg_mask_launch(d_status, B, ny, nx, (int)std::min<long long>(span, INT32_MAX), img_h, img_w, dd, u8 != 0, st);
+            s.host_results = true;                             // (the status came from pageable host memory: the call ends synchronised)
+            return s.finish("segment_mask");
+        });
+    });
 }
 
 int cdc_entropy_decode_window(cdc_handle *h, const unsigned char *in, const size_t *offsets, const float *medians, int B, const int32_t window[4],
                               float *q_latent, float *q_hyper_latent, int *segments_decoded, int mem, void *stream) {
     return no_throw(h, [&]() -> int {
         if (h && !window) return fail(h, CDC_ERR_INVALID, "null/invalid argument");
-        return entropy_decode_impl(h, in, offsets, medians, B, window, q_latent, q_hyper_latent, segments_decoded, mem, stream);
+        return entropy_decode_impl(h, in, offsets, medians, B, window, q_latent, q_hyper_latent, segments_decoded, nullptr, mem, stream);
     });
 }
 

@@ -154,7 +154,13 @@ hipError_t seg_decode_launch(EntropyDev T, const SegEntry *tab, const SegJob *jo
                              int tab0, int32_t *sym_seg, RansMeta *meta, hipStream_t st);
 hipError_t seg_scatter_launch(const SegEntry *tab, int S, int max_n, SegWindow win, const int32_t *sym_seg, long long nl, int Hl, int Wl, int B,
                               int32_t *sym, uint32_t *sums, hipStream_t st);
-
+// Partial streams (include/cdc_hip.h): the frame positions of the n_pairs listed (image, segment) pairs -> symbol 0 (n_pairs >= 1) ...
+struct SegPair { int b, s; };
+hipError_t seg_conceal_launch(const SegEntry *tab, int max_n, const SegPair *pairs, int n_pairs, long long nl, int Hl, int Wl, int32_t *sym,
+                              hipStream_t st);
+// ... and status [B][ny nx] (device) -> out [B][H][W]: 1 (float32) / 255 (uint8) where status[b][(y / span) nx + x / span] is 0, else
+// 0; span = pixels per segment and side, H <= ny span, W <= nx span.  16-byte / 4-byte stores when W % 4 == 0 and out is 16-byte aligned.
+hipError_t seg_mask_launch(const uint8_t *status, int B, int ny, int nx, int span, int H, int W, void *out, bool u8, hipStream_t st);
 
 // ---- grouped hyper part (container versions 19 - 22; see entropy.hip) --------------------------------------------------------
 // Group g = channels [g cg, min(Ch, (g + 1) cg)) of the hyper section [Ch][per], ng = ceil(Ch / cg) groups: a contiguous range of the

@@ -840,4 +840,75 @@ hipError_t seg_scatter_launch(const SegEntry *tab, int S, int max_n, SegWindow w
     return hipGetLastError();
 }
 
+// ---- partial streams (include/cdc_hip.h: cdc_entropy_decode_partial, cdc_segment_mask) ------------------------------------------------
+// A damaged segment's verdict exists only after seg_scatter_kernel has put its symbols into the frame (the checksum is summed there):
+// the frame positions of the listed (image, segment) pairs go back to symbol 0, i.e. q_latent = mean.  Block blockIdx.x of nblk per
+// pair; consecutive j of one (c, y) run are consecutive frame positions, so a wave's stores are runs of e.w int32.
+__global__ void __launch_bounds__(256) seg_conceal_kernel(const SegEntry *tab, const SegPair *pairs, int nblk, long long nl, int Hl, int Wl, int32_t *sym) {
+    const SegPair q = pairs[blockIdx.x / nblk];
+    const SegEntry e = tab[q.s];
+    const long long j = (long long)(blockIdx.x % nblk) * 256 + threadIdx.x;
+    if (j >= e.n) return;
+    sym[(long long)q.b * nl + seg_frame_index(e, (int)j, Hl, Wl)] = 0;
+}
+
+hipError_t seg_conceal_launch(const SegEntry *tab, int max_n, const SegPair *pairs, int n_pairs, long long nl, int Hl, int Wl, int32_t *sym, hipStream_t st) {
+    const int nblk = (max_n + 255) / 256;                      // (max_n <= 2^29: nblk <= 2^21)
+    const int chunk = std::max(1, (1 << 30) / nblk);           // pairs per launch: the grid stays below 2^31 blocks
+    for (int p0 = 0; p0 < n_pairs; p0 += chunk) {
+        const int np = std::min(chunk, n_pairs - p0);
+        hipLaunchKernelGGL(seg_conceal_kernel, dim3((unsigned)np * (unsigned)nblk), dim3(256), 0, st, tab, pairs + p0, nblk, nl, Hl, Wl, sym);
+    }
+    return hipGetLastError();
+}
+
+// The per-pixel mask of a status table: thread t owns the four pixels 4 t .. 4 t + 3 of out [B][H][W] (flat).  kVec (W % 4 == 0 and an
+// aligned out: the four share a row): one 16-byte store of float32, one 4-byte store of uint8; else element stores.
+template <bool kVec, bool kU8>
+__global__ void __launch_bounds__(256) seg_mask_kernel(const uint8_t *status, int S, int nx, int span, int H, int W, long long total, void *out) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x, i0 = 4 * t;
+    if (i0 >= total) return;
+    const long long hw = (long long)H * W;
+    bool on[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const long long i = i0 + k;
+        on[k] = false;
+        if (i < total) {
+            const long long b = i / hw, r = i - b * hw;
+            const int y = (int)(r / W), x = (int)(r - (long long)y * W);
+            on[k] = status[b * S + (long long)(y / span) * nx + x / span] == 0;
+        }
+    }
+    if (kVec) {
+        if (kU8) {
+            uint32_t v = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v |= on[k] ? 0xffu << (8 * k) : 0u;
+            reinterpret_cast<uint32_t *>(out)[t] = v;
+        } else {
+            reinterpret_cast<float4 *>(out)[t] = make_float4(on[0] ? 1.f : 0.f, on[1] ? 1.f : 0.f, on[2] ? 1.f : 0.f, on[3] ? 1.f : 0.f);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (i0 + k >= total) break;
+            if (kU8) reinterpret_cast<uint8_t *>(out)[i0 + k] = on[k] ? 255 : 0;
+            else reinterpret_cast<float *>(out)[i0 + k] = on[k] ? 1.f : 0.f;
+        }
+    }
+}
+
+hipError_t seg_mask_launch(const uint8_t *status, int B, int ny, int nx, int span, int H, int W, void *out, bool u8, hipStream_t st) {
+    const long long total = (long long)B * H * W;
+    const bool vec = W % 4 == 0 && (uintptr_t)out % 16 == 0;
+    const dim3 grid((unsigned)(((total + 3) / 4 + 255) / 256)), block(256);
+    const int S = ny * nx;
+    if (vec && u8) hipLaunchKernelGGL((seg_mask_kernel<true, true>), grid, block, 0, st, status, S, nx, span, H, W, total, out);
+    else if (vec) hipLaunchKernelGGL((seg_mask_kernel<true, false>), grid, block, 0, st, status, S, nx, span, H, W, total, out);
+    else if (u8) hipLaunchKernelGGL((seg_mask_kernel<false, true>), grid, block, 0, st, status, S, nx, span, H, W, total, out);
+    else hipLaunchKernelGGL((seg_mask_kernel<false, false>), grid, block, 0, st, status, S, nx, span, H, W, total, out);
+    return hipGetLastError();
+}
+
 }  // namespace cdc

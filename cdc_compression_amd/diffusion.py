@@ -468,7 +468,8 @@ class _GaussianDiffusionBase:
 
     def decompress(self, context, shape=None, sample_steps=None, init=None, eta=0, clip_denoised=None, bitrate_scale=None,
                    as_uint8=False, seed=None, gamma=None, sampler="ddim", spacing="index", samples=None, reduce=None, sample_chunk=None,
-                   trajectory=None, trajectory_of="x0", trajectory_dtype="float32", tile=None, tile_overlap=None, tile_chunk=None, region=None):
+                   trajectory=None, trajectory_of="x0", trajectory_dtype="float32", tile=None, tile_overlap=None, tile_chunk=None, region=None,
+                   partial=False):
         """Decode half of compress(): context pyramid (= context_fn(...)["output"]) -> image.  `context`
         may also be the transmitted q_latent tensor [B, C, H/16, W/16]: it then goes through
         `context_fn.decode` first (compress_modules.py:68-74; cdc_compression_amd.compressor on the GPU) -- with
@@ -495,7 +496,20 @@ class _GaussianDiffusionBase:
         Of segmented streams (compress_to_bytes(segment=)) only the segments under those tiles are entropy-decoded, and the dict also
         holds "segments" and "segments_decoded" (per image); of streams with a grouped hyper section (hyper_groups=) also
         "hyper_groups", the groups a stream holds -- all of them are always decoded.
-        Excludes samples=, trajectory= and a context pyramid; eta != 0 needs a seed."""
+        Excludes samples=, trajectory= and a context pyramid; eta != 0 needs a seed.
+        partial=True (streams only; excludes samples= and trajectory=): the streams may be prefixes of segmented streams and may hold
+        damaged segments (context_fn.decompress_from_bytes(partial=True)) -> (reconstruction, info): the decode, launch for launch, of the
+        q_latent that holds hyper_decode's mean wherever a segment is absent or damaged.  info: "segment_status" uint8 [B, ny, nx] (0
+        decoded, 1 absent, 2 damaged); "present_mask" [B, 1, H, W], 1.0 (uint8 255 with as_uint8) where a pixel's latent position lies
+        in a decoded segment; "present_region" (y0, x0, h, w), the bounding box in image pixels of the leading segments that are wholly
+        there, over all images of the call, or None.  With tile=, region="present" decodes only the tiles that intersect that box --
+        planned before the entropy decode, so a 30 % prefix costs 30 % of the sampler's time -- and returns that window, the tile
+        info merged into info (a CdcError when no segment is complete); a region tuple works as always."""
+        if partial:
+            return self._decompress_partial(context, shape, sample_steps, init, eta, clip_denoised, bitrate_scale, as_uint8, seed, gamma, sampler,
+                                            spacing, samples, reduce, sample_chunk, trajectory, tile, tile_overlap, tile_chunk, region)
+        if isinstance(region, str):
+            raise ValueError(f"region={region!r} belongs to partial=True")
         tile_hw, overlap_hw = _tiles.check_args(tile, tile_overlap, tile_chunk, region, samples, trajectory)
         if tile_hw is not None:
             if eta != 0 and seed is None:
@@ -574,12 +588,17 @@ class _GaussianDiffusionBase:
         tiles' latent windows (y0, x0, h, w in latent positions), planned from the sizes the stream's header holds as
         `_decompress_tiled` plans them from the q_latent; None when one tile covers the frame (the plain path decodes it whole)."""
         cf = self.context_fn
-        cell = 1 << len(cf.rev_mults)
         H, W = cf.image_size_of([stream], cf.frame_multiple)[0]
         hh, wh = ctypes.c_int(), ctypes.c_int()
         if _lib.lib().cdc_entropy_peek(bytes(stream), len(stream), ctypes.byref(hh), ctypes.byref(wh), None) != 0:
             raise _lib.CdcError("not a CDC bitstream")
-        Hp, Wp = hh.value * cf.frame_multiple, wh.value * cf.frame_multiple
+        return self._latent_window(H, W, hh.value, wh.value, tile, overlap, region)
+
+    def _latent_window(self, H, W, hh, wh, tile, overlap, region):
+        """`_stream_window` from the sizes a peek gave: the H x W image, hh x wh hyper-latent positions."""
+        cf = self.context_fn
+        cell = 1 << len(cf.rev_mults)
+        Hp, Wp = hh * cf.frame_multiple, wh * cf.frame_multiple
         window = _tiles.check_region(region, H, W)
         plan = _tiles.Plan(Hp, Wp, tile, overlap)
         if plan.T == 1:
@@ -588,6 +607,64 @@ class _GaussianDiffusionBase:
         y0, x0 = min(y for y, _ in origins) // cell, min(x for _, x in origins) // cell
         y1, x1 = (max(y for y, _ in origins) + plan.th) // cell, (max(x for _, x in origins) + plan.tw) // cell
         return (y0, x0, y1 - y0, x1 - x0)
+
+    # ---- partial streams (include/cdc_hip.h: cdc_entropy_decode_partial) ---------------------------------------------------------
+    def _decompress_partial(self, streams, shape, sample_steps, init, eta, clip_denoised, bitrate_scale, as_uint8, seed, gamma, sampler, spacing,
+                            samples, reduce, sample_chunk, trajectory, tile, tile_overlap, tile_chunk, region):
+        """decompress(streams, partial=True): -> (reconstruction, info).  Everything the sampler needs to plan comes from the peek of
+        the prefixes, before the entropy decode."""
+        if samples is not None or reduce is not None or sample_chunk is not None or trajectory is not None:
+            raise ValueError("partial=True excludes samples= and trajectory=")
+        if isinstance(streams, (bytes, bytearray)):
+            streams = [streams]
+        if not (isinstance(streams, (list, tuple)) and streams and all(isinstance(s, (bytes, bytearray)) for s in streams)):
+            raise ValueError("partial=True decodes streams (bytes): a q_latent or a context pyramid is whole already")
+        if bitrate_scale is not None:
+            raise ValueError("the streams carry their own bitrate_scale")
+        if isinstance(region, str) and region != "present":
+            raise ValueError(f"region={region!r}: a (y0, x0, h, w) tuple or \"present\"")
+        if region is not None and tile is None:
+            raise ValueError("region belongs to tile=")
+        cf = self.context_fn
+        if cf is None or not hasattr(cf, "stream_info"):
+            raise RuntimeError("decompress(streams, partial=True) needs a context_fn of this package")
+        infos = [cf.stream_info(s) for s in streams]
+        i0 = infos[0]
+        sizes = {(i["img_h"], i["img_w"]) if i["has_size"] else (i["hh"] * cf.frame_multiple, i["wh"] * cf.frame_multiple) for i in infos}
+        if len(sizes) != 1 or len({(i["seg"], i["ny"], i["nx"]) for i in infos}) != 1:
+            raise _lib.CdcError("the streams of one call must share the image size and the segment size")
+        H, W = sizes.pop()
+        B = len(streams)
+        if shape is not None and tuple(int(d) for d in shape) != (B, 3, H, W):
+            raise _lib.CdcError(f"shape {tuple(shape)} contradicts the streams, which hold {B} image(s) of {H} x {W}")
+        # the bounding box of the segments that are wholly there, in image pixels
+        span, box = i0["seg"] * int(cf.rate_map_cell), None
+        for i in infos:
+            for s in range(i["complete"]):
+                sy, sx = divmod(s, i["nx"])
+                y0, x0, y1, x1 = sy * span, sx * span, min(H, (sy + 1) * span), min(W, (sx + 1) * span)
+                if y0 < H and x0 < W:
+                    box = (y0, x0, y1, x1) if box is None else (min(box[0], y0), min(box[1], x0), max(box[2], y1), max(box[3], x1))
+        present = None if box is None else (box[0], box[1], box[2] - box[0], box[3] - box[1])
+        if region == "present":
+            if present is None:
+                raise _lib.CdcError("region=\"present\": no segment of these streams is complete yet (nothing to decode)")
+            region = present
+        tile_hw, overlap_hw = _tiles.check_args(tile, tile_overlap, tile_chunk, region, None, None)
+        win = None
+        if tile_hw is not None and region is not None:
+            tile_hw, overlap_hw = _tiles.check_multiples(tile_hw, overlap_hw, self.padded_size(1, 1)[0])
+            win = self._latent_window(H, W, i0["hh"], i0["wh"], tile_hw, overlap_hw, region)
+        q, rates, _, seg_info, status = cf.decompress_from_bytes(streams, like=init, return_bitrate_scale=True, return_image_size=True, window=win,
+                                                                 return_segments=True, partial=True, return_status=True)
+        rec = self.decompress(q, (B, 3, H, W), sample_steps, init, eta, clip_denoised, rates, as_uint8, seed, gamma, sampler, spacing,
+                              tile=tile, tile_overlap=tile_overlap, tile_chunk=tile_chunk, region=region)
+        info = {"segment_status": status, "present_mask": cf.segment_mask(status, i0["seg"], (H, W), as_uint8=as_uint8, like=init),
+                "present_region": present}
+        if isinstance(rec, tuple):
+            rec, tile_info = rec
+            info.update(tile_info, segments=seg_info[0], segments_decoded=seg_info[1])
+        return rec, info
 
     def _decompress_tiled(self, q_latent, bitrate_scale, recorded, shape, tile, overlap, tile_chunk, region, sample_steps, init, eta,
                           clip_denoised, as_uint8, seed, gamma, sampler, spacing):

@@ -616,6 +616,63 @@ int cdc_entropy_decode_window(cdc_handle *h, const unsigned char *in, const size
 int cdc_entropy_set_hyper_groups(cdc_handle *hyperdec, int channels_per_group);
 int cdc_entropy_peek_hyper_groups(const unsigned char *in, size_t n, int *channels_per_group, int *groups);
 
+/* ---- partial streams: decode the segments that arrived, conceal the rest (csrc/entropy.hip: seg_conceal_kernel, seg_mask_kernel) ----
+ * No stream format changes.  A segmented stream (versions 11 - 14, 19 - 22) is a header, a hyper part, a segment index and segments
+ * in raster order, each segment with its own lane states, end conditions and checksum: a prefix that holds the index is the top of
+ * the image, and a damaged segment costs its own window.  Unsegmented streams (3 - 6) are one section with nothing independent in
+ * it and stay refused: segment= at the encoder is what makes a stream partial-decodable.
+ * cdc_entropy_peek_partial: handle-free.  Reads the first n bytes of a stream of versions 11 - 14 or 19 - 22:
+ *   hh, wh, arith | has_rate, rate | has_size, img_h, img_w | seg, ny, nx | cg, ng (0, 1 for 11 - 14)     as the other peeks give them
+ *   declared = header + n_hyper + n_latent as the header states them (the length of the whole stream)
+ *   floor    = the bytes up to and including the last entry of the segment index: header, whole hyper part (with its group index
+ *              if any), the 8 bytes, 12 ny nx
+ *   complete = the number of LEADING segments, in raster order, that lie wholly inside [0, n)
+ *   It validates exactly what the other peeks validate -- magic, version, a recorded size of 1 .. 2^31 - 1, the 8 bytes of either
+ *   index, every entry's bytes >= 256 + 4 esc, 8 + 12 ny nx + sum bytes = n_latent, sum esc = esc_latent, and the same of the
+ *   hyper groups -- with ONE exception: n = declared is replaced by floor <= n <= declared.  The index is required whole.
+ *   CDC_ERR_INVALID when n < floor (header, hyper part or index incomplete: nothing can be decoded), when n > declared, for
+ *   versions 3 - 6 and for anything that is no stream.  With n = declared it agrees field by field with the other peeks.
+ * cdc_entropy_decode_partial: cdc_entropy_decode / _decode_window (window may be null) of streams given in part.  Per image the
+ *   stream's ACTUAL length is offsets[b + 1] - offsets[b]; the images of one call may be cut at different places.
+ *   status: uint8 [B][ny nx], HOST memory whatever mem_kind says, per (image, segment):
+ *     CDC_SEG_OK = 0       decoded; its end conditions and its index checksum hold
+ *     CDC_SEG_ABSENT = 1   not wholly inside the bytes given, or outside `window`; it is not made a job
+ *     CDC_SEG_DAMAGED = 2  its end conditions failed, or its symbols do not sum to the index's checksum
+ *   (what the table and the outputs hold after a call that returned an error is unspecified)
+ *   q_latent is the full decode's value, bit for bit, at the positions of OK segments, and hyper_dec's mean, bit for bit (symbol 0:
+ *   the value cdc_entropy_decode_window defines for unselected segments), at every other position.  q_hyper_latent is always whole.
+ *   Everything that is refused before the latent part is refused as cdc_entropy_decode refuses it and by the same messages (header
+ *   checks, table fingerprint, limits, the grid against the handle, a corrupt hyper section or hyper group, mixed forms in one
+ *   call); an unsegmented stream is CDC_ERR_INVALID with a message that names segment=.  The header's `symbols` checksum is checked
+ *   for an image exactly when all its segments are OK and no window was given: then the result equals cdc_entropy_decode's.
+ *   Only the bytes given are copied to the device and no job's [off, off + len) reaches past them; a damaged section reports its
+ *   end conditions and reads nothing outside its own bytes (every byte pull is bounded by the section's end, every escape by its
+ *   escape count).  A DAMAGED SEGMENT THAT PASSES BOTH ITS END CONDITIONS AND ITS 32-BIT CHECKSUM BY CHANCE IS ACCEPTED.
+ *   A damaged segment's symbols are in the frame before its verdict exists (the checksum is summed where the symbols are scattered),
+ *   so one further launch (seg_conceal_kernel) rewrites the positions of the DAMAGED pairs to symbol 0 -- only when there are any.
+ * cdc_segment_mask: status [B][ny nx] (host memory, as cdc_entropy_decode_partial wrote it) -> out [B][1][img_h][img_w], the image
+ *   window (cropped as the reconstruction is): CDC_ELEM_U8 0 / 255 or CDC_ELEM_F32 0 / 1, set where the pixel's latent position
+ *   (y / cell_pixels, x / cell_pixels) lies in an OK segment, i.e. segment (y / cell_pixels / seg, x / cell_pixels / seg).
+ *   1 <= img_h <= ny seg cell_pixels and 1 <= img_w <= nx seg cell_pixels (CDC_ERR_INVALID otherwise).  Any handle kind; `out`
+ *   follows mem_kind / stream as cdc_frame_crop's does. */
+enum { CDC_SEG_OK = 0, CDC_SEG_ABSENT = 1, CDC_SEG_DAMAGED = 2 };
+typedef struct cdc_stream_info {
+    int hh, wh, arith;
+    int has_rate;
+    float rate;
+    int has_size, img_h, img_w;
+    int seg, ny, nx;
+    int cg, ng;
+    int complete;
+    unsigned long long declared, floor;
+} cdc_stream_info;
+int cdc_entropy_peek_partial(const unsigned char *in, size_t n, cdc_stream_info *info);
+int cdc_entropy_decode_partial(cdc_handle *h, const unsigned char *in, const size_t *offsets, const float *medians, int B,
+                               const int32_t *window /* null, or y0, x0, h, w in latent positions */, float *q_latent,
+                               float *q_hyper_latent /* nullable */, unsigned char *status /* [B][ny nx], host */, int mem_kind, void *stream);
+int cdc_segment_mask(cdc_handle *h, const unsigned char *status, int B, int ny, int nx, int seg, int cell_pixels, int img_h, int img_w,
+                     void *out, int elem_kind, int mem_kind, void *stream);
+
 /* ---- distortion of decoded images: PSNR and MS-SSIM on the device (csrc/metric_kernels.hip) --------------------------------------
  * THE DEFINITION.  Operands: two image batches a, b, each [B][3][Hf][Wf] with Hf >= H, Wf >= W and its own element kind, frame size
  * and as_saved flag (a cdc_image_view each).  Only the top-left H x W window is evaluated -- a padded decoder frame is measured
