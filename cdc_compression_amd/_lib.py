@@ -207,6 +207,8 @@ def lib():
                                ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double),
                                ctypes.POINTER(ctypes.c_double)]
     L.cdc_prof_reset.argtypes = [H]
+    L.cdc_set_decode_chains.argtypes = [H, _i]
+    L.cdc_decode_chains.argtypes = [H, _i, _i, _i]
     L.cdc_prof_num_ops.argtypes = [H]
     L.cdc_prof_op.argtypes = [H, _i, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_double),
                               ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double)]
@@ -248,7 +250,8 @@ EXPORTS = ["cdc_create", "cdc_destroy", "cdc_last_error", "cdc_version", "cdc_nu
            "cdc_set_noise_frames", "cdc_randn_framed", "cdc_randn_framed_host", "cdc_tile_gather", "cdc_tile_blend",
            "cdc_entropy_set_segments", "cdc_entropy_peek_segments", "cdc_entropy_decode_window",
            "cdc_entropy_set_hyper_groups", "cdc_entropy_peek_hyper_groups",
-           "cdc_entropy_peek_partial", "cdc_entropy_decode_partial", "cdc_segment_mask"]
+           "cdc_entropy_peek_partial", "cdc_entropy_decode_partial", "cdc_segment_mask",
+           "cdc_set_decode_chains", "cdc_decode_chains"]
 
 
 def handle_status(handle):

@@ -86,6 +86,7 @@ int run_pre(cdc_handle *h, hipStream_t st) {
 // step < 0: plain Unet.forward with the caller's per-image time values.
 int run_unet(cdc_handle *h, hipStream_t st, int step, bool skip_combine) {
     for (const Op &op : h->ops) {
+        if (h->mark_ev && &op - h->ops.data() == h->trunk_op) HIP_TRY(h, hipEventRecord(h->mark_ev, st));   // (split decode: initial skew)
         if (skip_combine && op.get<CombineArgs>()) continue;      // (the sampler kernel evaluates it: sampler_on_device)
         int rc;
         if (op.get<TembArgs>() && (step >= 0 || step == -2)) {      // the shifts of the step: a row of the per-decode table, under TEMB's id
@@ -231,6 +232,10 @@ int range_check(cdc_handle *h, const std::vector<GuardBuf> &bufs, int B, hipStre
     int fault = 0;
     HIP_TRY(h, hipMemcpyAsync(&fault, h->d_fault, sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipStreamSynchronize(st));
+    return range_verdict(h, fault);
+}
+// What a fault flag read back from the device means for the call (range_check; a split decode reads the flags of both chains)
+int range_verdict(cdc_handle *h, int fault) {
     if (!fault) return CDC_OK;
     if (h->in_retry || h->arith != CDC_ARITH_F16X2) {
         ++h->nonfinite_results;
@@ -261,6 +266,47 @@ static int run_compressor(cdc_handle *h, const float *x, size_t n, int B, int me
     std::vector<GuardBuf> outs;
     for (const Act &a : h->dec_outs) outs.push_back({a.p, a.bs(), (long long)a.C * a.H * a.W});
     return range_check(h, outs, B, st);
+}
+
+// ---- split decode: the twin handle ---------------------------------------------------------------------------------
+void drop_twin(cdc_handle *h) {
+    if (!h || !h->twin) return;
+    cdc_handle *t = h->twin;
+    h->twin = nullptr;
+    cdc_destroy(t);               // (synchronises the device first; frees what the twin owns, nothing it borrows)
+}
+
+// The packed weight descriptors, by value: every pointer in them is the parent's (the twin's weight_allocs holds only what the twin
+// allocates itself, its fault flag).  Valid until the parent repacks (cdc_finalize_weights) or changes its arithmetic: both drop the twin.
+static void bind_twin_weights(cdc_handle *h, cdc_handle *t) {
+    t->cfg = h->cfg; t->arith = h->arith; t->dims = h->dims; t->context_dims = h->context_dims; t->n_res = h->n_res; t->out_dim = h->out_dim;
+    t->tm_w0 = h->tm_w0; t->tm_b0 = h->tm_b0; t->tm_w2 = h->tm_w2; t->tm_b2 = h->tm_b2;
+    t->rbs = h->rbs; t->attns = h->attns; t->downs = h->downs; t->ups = h->ups;
+    t->fin_g = h->fin_g; t->fin_b = h->fin_b; t->fin_conv = h->fin_conv; t->fin_bias = h->fin_bias; t->fin_P = h->fin_P;
+    t->d_temb_layers = h->d_temb_layers; t->shift_bs = h->shift_bs;
+    t->finalized = true;
+}
+// The schedule, solver and time-shift tables and the per-call switches, at every split decode (a cdc_set_schedule* / cdc_set_solver
+// in between may have moved them; they synchronise the device before they do).
+static void bind_twin_tables(cdc_handle *h, cdc_handle *t) {
+    t->steps = h->steps; t->sched_gen = h->sched_gen; t->tab_v_gen = h->tab_v_gen; t->stab_sched_gen = h->stab_sched_gen; t->solver_gen = h->solver_gen;
+    t->d_tab = h->d_tab; t->d_tab_v = h->d_tab_v; t->d_time_steps = h->d_time_steps; t->d_shift_tab = h->d_shift_tab; t->d_stab = h->d_stab;
+    t->prof = h->prof; t->prof_every = h->prof_every; t->in_retry = h->in_retry;
+}
+
+// The twin of `h`, created on first use; null when it could not be (h->err says why; not an error of the call)
+static cdc_handle *twin_of(cdc_handle *h) {
+    if (h->twin) return h->twin;
+    cdc_handle *t = new cdc_handle;
+    t->is_twin = true;
+    t->device = h->device;
+    h->twin = t;
+    bool ok = ensure_device(t) == CDC_OK;
+    for (hipEvent_t *e : {&h->sp_fence, &h->sp_iter, &h->sp_mark, &t->sp_fence, &t->sp_iter})
+        if (ok && !*e) ok = hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
+    if (!ok) { (void)hipGetLastError(); h->err = "split decode: the twin's stream or events could not be created"; drop_twin(h); return nullptr; }
+    bind_twin_weights(h, t);
+    return t;
 }
 
 }  // namespace cdcapi
@@ -299,6 +345,11 @@ int cdc_create(const cdc_unet_config *cfg, int device, cdc_handle **out) {
 
 void cdc_destroy(cdc_handle *h) {
     if (!h) return;
+    drop_twin(h);
+    if (h->is_twin) {        // borrowed from the parent (bind_twin_tables): the parent frees them
+        h->d_tab = {}; h->d_tab_v = {}; h->d_time_steps = {}; h->d_shift_tab = {}; h->d_stab = {};
+    }
+    for (hipEvent_t e : {h->sp_fence, h->sp_iter, h->sp_mark}) if (e) (void)hipEventDestroy(e);
     if (!h->own_stream) { delete h; return; }
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
@@ -335,6 +386,7 @@ int cdc_set_arith(cdc_handle *h, int mode) {
     if (mode != CDC_ARITH_BF16X3 && mode != CDC_ARITH_F16X2) return fail(h, CDC_ERR_INVALID, "arith mode %d", mode);
     if (mode != h->arith) {
         if (h->own_stream) { (void)hipSetDevice(h->device); (void)hipDeviceSynchronize(); }
+        drop_twin(h);             // (its program was planned for the other format)
         free_program(h);          // launch plans and LDS carve-up depend on the operand format
         h->arith = mode;
     }
@@ -1224,6 +1276,100 @@ int cdc_solver_step(cdc_handle *h, const float *x_in, const float *x0_prev_in, i
     return no_throw(h, [&] { return sampler_step(h, true, x_in, x0_prev_in, 0.f, i, ctx, n_ctx, x_out, x0_out, B, H, W, pred_mode, clip, mem, stream); });
 }
 
+// Split decode: rows [0, B0) on the handle's program and the call's stream, rows [B0, B) on the twin's program and
+// stream, B0 = ceil(B / 2); both programs are built (decode_impl).  One host thread enqueues: the pre-ops of both, then per iteration
+// the parent's ops and the twin's.  Fences: the twin's stream waits for the call's stream before anything is enqueued, the call's
+// stream waits for the end of the twin's chain before the range check and the copies out.  A profiled iteration runs alone on the
+// device (the event pairs of cdc_prof_* would time two kernels sharing the CUs otherwise).  skew: the twin's first iteration starts
+// when the parent's reaches the 32 x 32 level, so that one chain's few-pixel levels run under the other's wide ones.
+static int decode_split(cdc_handle *h, const float *init, float gamma, const uint64_t *seeds, float eta, const float *const *ctx, int n_ctx,
+                        float *out, int B, int H, int W, int pred_mode, int clip, int mem, void *stream, bool solver) {
+    cdc_handle *const t = h->twin, *const hc[2] = {h, t};
+    const int Bc[2] = {(B + 1) / 2, B / 2}, row0[2] = {0, Bc[0]};
+    const size_t per = (size_t)h->cfg.channels * H * W, nc[2] = {Bc[0] * per, Bc[1] * per};
+    int rc;
+    if ((rc = ensure_time_rows(h, Bc[0]))) return rc;
+    bind_twin_tables(h, t);
+    if (n_ctx != (int)h->in_ctx.size()) return fail(h, CDC_ERR_INVALID, "expected %d context tensors, got %d", (int)h->in_ctx.size(), n_ctx);
+    const bool gen_init = seeds && !init && gamma != 0.f, use_seeds = seeds && (gen_init || eta != 0.f);
+    // whatever may synchronise the device (a buffer that grows) comes before the chains fork
+    for (int k = 0; k < 2; ++k) {
+        if (solver && (rc = hc[k]->d_hist.grow(hc[k], nc[k]))) { h->err = hc[k]->err; return rc; }
+        if (use_seeds && (rc = hc[k]->seeds.dev.grow(hc[k], (size_t)Bc[k]))) { h->err = hc[k]->err; return rc; }
+    }
+    const hipStream_t st[2] = {pick_stream(h, stream, mem), t->own_stream};
+    HIP_TRY(h, hipEventRecord(h->sp_fence, st[0]));
+    HIP_TRY(h, hipStreamWaitEvent(st[1], h->sp_fence, 0));
+    const unsigned long long *dseeds[2] = {nullptr, nullptr};
+    auto chains = [&]() -> int {
+        int rc;
+        for (int k = 0; k < 2; ++k) {
+            cdc_handle *c = hc[k];
+            if ((rc = arm_range_guard(c, st[k], true))) return rc;
+            if (solver) HIP_TRY(c, hipMemsetAsync(c->d_hist.p, 0, nc[k] * sizeof(float), st[k]));
+            if (use_seeds) {
+                if ((rc = c->seeds.stage(c, seeds + row0[k], (size_t)Bc[k], st[k]))) return rc;
+                dseeds[k] = c->seeds.dev.p;
+            }
+            if (init) { if ((rc = copy_in(c, c->in_x, init + row0[k] * per, nc[k], mem, st[k]))) return rc; }
+            else if (gen_init) HIP_TRY(c, randn_fill_launch(dseeds[k], Bc[k], (long long)per, 0u, gamma, c->in_x, st[k]));
+            else HIP_TRY(c, hipMemsetAsync(c->in_x, 0, nc[k] * sizeof(float), st[k]));
+            std::vector<const float *> cx((size_t)n_ctx);
+            for (int l = 0; l < n_ctx; ++l) {
+                if (!ctx[l]) return fail(c, CDC_ERR_INVALID, "null context tensor %d", l);
+                cx[l] = ctx[l] + (size_t)row0[k] * (size_t)c->in_ctx[l].bs();
+            }
+            if ((rc = stage_ctx(c, cx.data(), n_ctx, Bc[k], mem, st[k]))) return rc;
+            c->prof_now = false;
+            if ((rc = run_pre(c, st[k]))) return rc;       // hoisted context halves: once per decode
+        }
+        const bool skew = decode_chains_skew() && h->trunk_op >= 0;
+        // clip "half" (the first B / 2 images of the batch; B is even here, decode_chains_rule): all of the parent's rows, none of the twin's
+        const int clip_c[2] = {clip == CDC_CLIP_HALF ? CDC_CLIP_ALL : clip, clip == CDC_CLIP_HALF ? CDC_CLIP_NONE : clip};
+        for (int i = h->steps - 1; i >= 0; --i) {
+            const bool first = i == h->steps - 1, prof_now = (i % h->prof_every) == 0, alone = h->prof && prof_now;
+            h->prof_now = t->prof_now = prof_now;
+            if (alone && !first) HIP_TRY(h, hipStreamWaitEvent(st[0], t->sp_iter, 0));        // (the twin's previous iteration)
+            if (first && skew) h->mark_ev = h->sp_mark;
+            rc = sampler_on_device(h, solver, i, {nullptr, dseeds[0], nullptr, false}, eta, h->in_x, Bc[0], H, W, pred_mode, clip_c[0], st[0]);
+            h->mark_ev = nullptr;
+            if (rc) return rc;
+            if (alone) {
+                HIP_TRY(h, hipEventRecord(h->sp_iter, st[0]));
+                HIP_TRY(h, hipStreamWaitEvent(st[1], h->sp_iter, 0));
+            } else if (first && skew) HIP_TRY(h, hipStreamWaitEvent(st[1], h->sp_mark, 0));
+            if ((rc = sampler_on_device(t, solver, i, {nullptr, dseeds[1], nullptr, false}, eta, t->in_x, Bc[1], H, W, pred_mode, clip_c[1], st[1]))) return rc;
+            if (h->prof) HIP_TRY(t, hipEventRecord(t->sp_iter, st[1]));
+            if (alone) HIP_TRY(h, hipStreamWaitEvent(st[0], t->sp_iter, 0));
+        }
+        h->prof_now = t->prof_now = true;
+        return CDC_OK;
+    };
+    rc = chains();
+    // the join, after an error too: nothing of the call may still run on the twin's stream when control goes back
+    hipError_t e = hipEventRecord(t->sp_fence, st[1]);
+    if (e == hipSuccess) e = hipStreamWaitEvent(st[0], t->sp_fence, 0);
+    if (rc) {
+        (void)hipStreamSynchronize(st[1]);
+        if (!t->err.empty()) { h->err = t->err; t->err.clear(); }
+        return rc;
+    }
+    HIP_TRY(h, e);
+    // Range guard: the sampler kernels flag a non-finite U-Net output in their own chain's flag; the final image of both halves is
+    // checked into the parent's.  One read-back of the two flags, one verdict: a fault in either chain repeats the whole call.
+    if (guard_enabled(h)) {
+        HIP_TRY(h, cdc::nonfinite_launch(h->in_x, 0, (long long)nc[0], 1, h->d_fault, st[0]));
+        HIP_TRY(h, cdc::nonfinite_launch(t->in_x, 0, (long long)nc[1], 1, h->d_fault, st[0]));
+        int fault[2] = {0, 0};
+        HIP_TRY(h, hipMemcpyAsync(&fault[0], h->d_fault, sizeof(int), hipMemcpyDeviceToHost, st[0]));
+        HIP_TRY(h, hipMemcpyAsync(&fault[1], t->d_fault, sizeof(int), hipMemcpyDeviceToHost, st[0]));
+        HIP_TRY(h, hipStreamSynchronize(st[0]));
+        if ((rc = range_verdict(h, fault[0] | fault[1]))) return rc;      // (kRangeRetry: the twin went with the arithmetic)
+    }
+    if ((rc = copy_out(h, out, h->in_x, nc[0], mem, st[0]))) return rc;
+    return copy_out(h, out + nc[0], t->in_x, nc[1], mem, st[0]);
+}
+
 // cdc_decode (seeds null: eta = 0, no generator), cdc_decode_seeded and cdc_decode_solver (solver: the multistep update in place of
 // the DDIM one, eta = 0): one loop.  rep > 0 (cdc_decode_samples): ctx holds B / rep images, each staged rep times in a row.
 static int decode_impl(cdc_handle *h, const float *init, float gamma, const uint64_t *seeds, float eta, const float *const *ctx,
@@ -1244,6 +1390,21 @@ static int decode_impl(cdc_handle *h, const float *init, float gamma, const uint
             if (rep) return fail(h, CDC_ERR_INVALID, "cdc_decode_samples: a trace is set (cdc_set_trace); a trajectory belongs to a single decode");
             if ((n_slots = trace_plan(h, B, H, W, &slot_of)) < 0) return n_slots;
         }
+        // Two chains (decode_chains_rule): the half-batch programs of the handle and its twin.  The B-row program and the two half
+        // programs never stay resident together: the stale one goes before the other is built.  A twin that cannot be had -- no
+        // stream, out of memory for its program -- is not an error of the call: one chain, as ever.
+        if (decode_chains_rule(h, B, H, W, traced, !h->noise_frames.empty(), rep > 0, clip == CDC_CLIP_HALF) == 2) {
+            const int B0 = (B + 1) / 2;
+            cdc_handle *t = twin_of(h);
+            if (t && !(h->pB == B0 && h->pH == H && h->pW == W && !h->p_batch1_plan)) free_program(h);
+            if (t && (build_program(t, B - B0, H, W) != CDC_OK || build_program(h, B0, H, W) != CDC_OK)) {
+                (void)hipGetLastError();
+                free_program(t);
+                t = nullptr;
+            }
+            if (t) return decode_split(h, init, gamma, seeds, eta, ctx, n_ctx, out, B, H, W, pred_mode, clip, mem, stream, solver);
+        }
+        if (h->twin && h->twin->pB) free_program(h->twin);       // (a changed decision: the twin's program is stale)
         if ((rc = build_program(h, B, H, W))) return rc;
         if ((rc = ensure_time_rows(h, B))) return rc;
         hipStream_t st = pick_stream(h, stream, mem);
@@ -1899,10 +2060,13 @@ int cdc_prof_get(cdc_handle *h, int cls, double *ms, int64_t *launches, double *
                         h->op_flops[i] / (h->op_ms[i] / h->op_n[i] * 1e-3) / 1e12, h->op_n[i],
                         h->op_label[i].c_str());
     }
-    if (ms) *ms = h->prof_ms[cls];
-    if (launches) *launches = h->prof_launches[cls];
-    if (flops) *flops = h->prof_flops[cls];
-    if (bytes) *bytes = h->prof_bytes[cls];
+    // a split decode: the two chains' tables, summed
+    const cdc_handle *t = h->twin;
+    if (t && (rc = resolve_pending(h->twin))) { h->err = t->err; return rc; }
+    if (ms) *ms = h->prof_ms[cls] + (t ? t->prof_ms[cls] : 0.0);
+    if (launches) *launches = h->prof_launches[cls] + (t ? t->prof_launches[cls] : 0);
+    if (flops) *flops = h->prof_flops[cls] + (t ? t->prof_flops[cls] : 0.0);
+    if (bytes) *bytes = h->prof_bytes[cls] + (t ? t->prof_bytes[cls] : 0.0);
     return CDC_OK;
 }
 int cdc_prof_num_ops(cdc_handle *h) { return h ? (int)h->op_ms.size() : CDC_ERR_INVALID; }
@@ -1910,10 +2074,14 @@ int cdc_prof_op(cdc_handle *h, int idx, const char **label, double *ms, int64_t 
     if (!h || idx < 0 || idx >= (int)h->op_ms.size()) return CDC_ERR_INVALID;
     int rc = resolve_pending(h);
     if (rc) return rc;
+    // a split decode: the half-batch program's ops once each, time and flops summed over the two chains (the same network: the same
+    // op sequence), launches = the sampled executions of one chain
+    const cdc_handle *t = h->twin && h->twin->op_ms.size() == h->op_ms.size() ? h->twin : nullptr;
+    if (t && (rc = resolve_pending(h->twin))) { h->err = t->err; return rc; }
     if (label) *label = h->op_label[idx].c_str();
-    if (ms) *ms = h->op_ms[idx];
+    if (ms) *ms = h->op_ms[idx] + (t ? t->op_ms[idx] : 0.0);
     if (launches) *launches = h->op_n[idx];
-    if (flops) *flops = h->op_flops[idx];
+    if (flops) *flops = h->op_flops[idx] + (t ? t->op_flops[idx] : 0.0);
     return CDC_OK;
 }
 int cdc_prof_reset(cdc_handle *h) {
@@ -1925,7 +2093,20 @@ int cdc_prof_reset(cdc_handle *h) {
         h->prof_ms[i] = h->prof_flops[i] = h->prof_bytes[i] = 0;
         h->prof_launches[i] = 0;
     }
+    return h->twin ? cdc_prof_reset(h->twin) : CDC_OK;
+}
+
+int cdc_set_decode_chains(cdc_handle *h, int n) {
+    if (!h) return CDC_ERR_INVALID;
+    int rc = require_kind(h, HandleKind::Unet);
+    if (rc) return rc;
+    if (n < 0 || n > 2) return fail(h, CDC_ERR_INVALID, "cdc_set_decode_chains: %d (0 the library's rule, 1 one chain, 2 two chains)", n);
+    h->decode_chains = n;
     return CDC_OK;
+}
+int cdc_decode_chains(const cdc_handle *h, int B, int H, int W) {
+    if (!h) return CDC_ERR_INVALID;
+    return decode_chains_rule(h, B, H, W, !h->trace_steps.empty(), !h->noise_frames.empty(), false, false);
 }
 
 }  // extern "C"

@@ -1029,6 +1029,7 @@ void free_program(cdc_handle *h) {
     h->act_bytes = 0;
     h->pB = h->pH = h->pW = 0;
     h->p_batch1_plan = false;
+    h->trunk_op = -1;
     h->time_steps_B = 0;
     h->d_rate = nullptr;           // (it lived in act_allocs)
     h->lp_res = nullptr;
@@ -1044,6 +1045,39 @@ static int commit_program(cdc_handle *h, const Builder &bd, int H, int W, bool b
     h->pB = bd.B; h->pH = H; h->pW = W;
     h->p_batch1_plan = batch1_plan;
     return CDC_OK;
+}
+
+// Split decode: how many chains a decode of B images of H x W runs.  One chain, as ever, for everything but a plain
+// decode of a U-Net handle: a traced decode, frame-indexed noise, K samples per image, hipGraph replay (CDC_GRAPH), B < 2, clip "half" of an odd batch.  Then the
+// caller's word (cdc_set_decode_chains: 1 / 2), then -- development, A/B runs -- CDC_DECODE_CHAINS=1|2 (a trailing 's' / 'n' switches
+// the initial skew on / off), then the library's rule: split exactly where profiles/split_decode.md measured a win.
+static int chains_env(bool *skew) {
+    const char *e = dev_env("CDC_DECODE_CHAINS");
+    if (!e) return 0;
+    if (skew && strchr(e, 's')) *skew = true;
+    if (skew && strchr(e, 'n')) *skew = false;
+    const int v = atoi(e);
+    return v == 1 || v == 2 ? v : 0;
+}
+constexpr bool kChainsSkewDefault = false;
+constexpr int kChainsMinBatch = 8;
+constexpr long long kChainsMinPixels = 1LL << 21;      // 32 x 256 x 256 = 8 x 512 x 512 pixels
+bool decode_chains_skew() {
+    bool skew = kChainsSkewDefault;
+    (void)chains_env(&skew);
+    return skew;
+}
+int decode_chains_rule(const cdc_handle *h, int B, int H, int W, bool traced, bool frames, bool samples, bool clip_half) {
+    if (!h || h->kind != HandleKind::Unet || h->is_twin || B < 2 || H < 1 || W < 1 || traced || frames || samples) return 1;
+    if (clip_half && (B & 1)) return 1;
+    const char *genv = getenv("CDC_GRAPH");
+    if (genv && atoi(genv) != 0) return 1;
+    int want = h->decode_chains;
+    if (want == 0) want = chains_env(nullptr);
+    if (want == 1 || want == 2) return want;
+    // the library's rule: the shapes profiles/split_decode.md measured faster as two chains (32 and 48 x 256^2, 8 and 16 x 512^2: 2 - 5 %),
+    // and nothing with fewer images or fewer pixels than they have
+    return B >= kChainsMinBatch && (long long)B * H * W >= kChainsMinPixels ? 2 : 1;
 }
 
 // Builds the launch program of Unet.forward for batch B at H x W (unet.py:106-135).
@@ -1074,6 +1108,7 @@ int build_program(cdc_handle *h, int B, int H, int W) {
     size_t rbi = 0, ati = 0;
     for (int i = 0; i < n; ++i) {
         const int HWl = x.H * x.W;
+        if (h->trunk_op < 0 && HWl <= 32 * 32) h->trunk_op = (int)h->ops.size();     // (split decode: where the initial skew lets the twin start)
         float *sm = bd.dalloc((size_t)B * HWl), *sr = bd.dalloc((size_t)B * HWl);
         const bool has_ctx = i < n_ctx;
         const std::string dn = "downs." + std::to_string(i);

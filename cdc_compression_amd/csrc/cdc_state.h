@@ -369,6 +369,19 @@ struct cdc_handle {
     std::vector<hipEvent_t> ev_free;
     int prof_every = 1;
     bool prof_now = false;
+    // split decode: a batch as two half-batch chains on two streams.  `twin` (a Unet handle only) is the second chain,
+    // created on the first split decode and destroyed with this handle.  It OWNS its launch program, stream, events, fault flag,
+    // staged seeds, solver history and profiling tables; it BORROWS, read-only, every packed weight descriptor and the schedule /
+    // solver / time-shift tables (bind_twin_*), and never frees one.  Whatever repacks the weights or changes the arithmetic drops
+    // the twin (drop_twin); the tables are bound again at every split decode.
+    cdc_handle *twin = nullptr;
+    bool is_twin = false;
+    int decode_chains = 0;               // cdc_set_decode_chains: 0 the library's rule, 1 never split, 2 split whenever the fall-backs allow
+    hipEvent_t sp_fence = nullptr;       // parent: the caller's stream at the start of the call; twin: the end of its chain
+    hipEvent_t sp_iter = nullptr;        // the end of this chain's last iteration (profiled iterations run alone)
+    hipEvent_t sp_mark = nullptr;        // parent: its first iteration has reached the few-pixel trunk (initial skew)
+    int trunk_op = -1;                   // index in `ops` of the first op of the 32 x 32-and-below levels (build_program)
+    hipEvent_t mark_ev = nullptr;        // run_unet records it in front of op `trunk_op` (set for one iteration)
 };
 
 namespace cdcapi {
@@ -411,6 +424,11 @@ void free_pool(std::vector<void *> *pool);
 // ---- cdc_planner.hip
 void free_program(cdc_handle *h);
 int build_program(cdc_handle *h, int B, int H, int W);
+// How many chains (1 or 2) a decode of B images of H x W runs on this handle (split decode): the one place that decides.
+// traced / frames / samples: the call records a trajectory, draws frame-indexed noise, decodes K samples per image (rep > 0);
+// clip_half: it clips the first B / 2 images only (CDC_CLIP_HALF), which the halves of an odd batch cannot express.
+int decode_chains_rule(const cdc_handle *h, int B, int H, int W, bool traced, bool frames, bool samples, bool clip_half);
+bool decode_chains_skew();               // the twin's first iteration starts when the parent's reaches the few-pixel trunk
 int build_encoder_program(cdc_handle *h, int B, int H, int W);          // (a SimpleCompressor handle: build_simple_encoder_program)
 int build_simple_encoder_program(cdc_handle *h, int B, int H, int W);
 int build_hyperdec_program(cdc_handle *h, int B, int hh, int wh, bool batch1_plan = false);
@@ -439,6 +457,7 @@ int ensure_device(cdc_handle *h);
 hipStream_t pick_stream(cdc_handle *h, void *stream, int mem);
 int check_ready(cdc_handle *h);
 int require_kind(cdc_handle *h, HandleKind kind);
+void drop_twin(cdc_handle *h);           // destroys the twin of a split decode, if any (it borrows what the caller is about to replace)
 
 // ---- range guard of the two-plane fp16 arithmetic ------------------------------------------------------------------
 // |activation| >= 65504 becomes inf / NaN in CDC_ARITH_F16X2 and propagates to the results of the call.  Every entry point
@@ -455,6 +474,7 @@ constexpr int kRangeRetry = -10000;   // internal: the handle is now in BF16X3, 
 // With the guard on: "not finite" over `bufs` (and whatever a kernel of the call left in the flag).  CDC_OK: no fault, or a
 // fault in the repetition, counted and returned as it is; kRangeRetry: a fault in F16X2; or an error.
 int range_check(cdc_handle *h, const std::vector<GuardBuf> &bufs, int B, hipStream_t st);
+int range_verdict(cdc_handle *h, int fault);      // ... its verdict on a flag that was read back
 // The repetition of a call in BF16X3.  When that result is non-finite as well (a NaN / inf in the inputs or the parameters), the
 // range was not the cause: the handle goes back to F16X2 and the fault is counted in nonfinite_results only.
 struct RetryScope {

@@ -583,6 +583,7 @@ int cdc_finalize_weights(cdc_handle *h) {
     int rc = ensure_device(h);
     if (rc) return rc;
     HIP_TRY(h, hipDeviceSynchronize());
+    drop_twin(h);                 // (it borrows the descriptors that go now)
     free_program(h);
     free_pool(&h->weight_allocs);
     h->d_fault = nullptr; h->d_step = nullptr;          // (they lived in that pool)

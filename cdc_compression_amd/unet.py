@@ -93,7 +93,12 @@ class Unet:
             for i, m in enumerate(context_dim_mults):
                 cfg.context_dim_mults[i] = m
             return cfg
-        self._lh = _lib.Handle("cdc_create", config, _lib.device_index_of(device))
+        self._chains = 0
+
+        def setup(h):        # (a handle created anew on another device keeps the setting)
+            if self._chains:
+                _lib.check(h, _lib.lib().cdc_set_decode_chains(h, self._chains))
+        self._lh = _lib.Handle("cdc_create", config, _lib.device_index_of(device), setup)
 
     # ---- handle management (_lib.Handle) --------------------------------------------------
     def _handle(self):
@@ -116,6 +121,17 @@ class Unet:
     @property
     def range_faults(self):
         return self.status()["range_faults"]
+
+    def set_decode_chains(self, n):
+        """cdc_set_decode_chains: 0 the library's rule, 1 a batch is always one chain (the one-chain bits), 2 two half-batch chains
+        on two streams whenever the call allows it."""
+        _lib.check(self._handle(), _lib.lib().cdc_set_decode_chains(self._handle(), int(n)))
+        self._chains = int(n)
+        return self
+
+    def decode_chains(self, B, H, W):
+        """cdc_decode_chains: how many chains (1 or 2) a plain decode of B images of H x W runs on this model as it is set."""
+        return int(_lib.lib().cdc_decode_chains(self._handle(), int(B), int(H), int(W)))
 
     def to(self, device):
         """Another device: the handle goes now; the next use creates it there, with the parameters loaded and final as they were."""

@@ -895,6 +895,23 @@ const char *cdc_prof_name(int cls);
 int cdc_prof_get(cdc_handle *h, int cls, double *ms, int64_t *launches, double *flops,
                  double *bytes);
 int cdc_prof_reset(cdc_handle *h);
+
+/* Split decode: cdc_decode / cdc_decode_seeded / cdc_decode_solver may run a batch as two interleaved half-batch chains -- rows
+ * [0, ceil(B / 2)) on the call's stream, the rest on a second stream the handle owns -- so that the few-pixel levels of one chain
+ * run under the wide levels of the other.  Images never interact; each half runs the launch program of its own batch size, so a
+ * row agrees with the unsplit decode within the row-versus-batch-1 bound, not bit for bit.  The call's stream ordering is kept:
+ * nothing of the call starts before the work queued on its stream, and the stream waits for both chains.
+ *   n = 0  the library's rule, the default: two chains for B >= 8 and B * H * W >= 2^21 pixels (32 x 256^2, 8 x 512^2), where
+ *          it measured 2 - 5 % faster (profiles/split_decode.md)
+ *   n = 1  never split: the bits of the one-chain decode
+ *   n = 2  split whenever possible
+ * Always one chain: a traced decode (cdc_set_trace), noise frames (cdc_set_noise_frames), cdc_decode_samples, CDC_GRAPH, B < 2,
+ * CDC_CLIP_HALF of an odd batch, and a handle whose second chain cannot be had (out of memory: not an error of the call).
+ * With profiling on (cdc_prof_enable) a sampled iteration runs one chain after the other; cdc_prof_get / cdc_prof_op report the
+ * half-batch program's ops once each, with time and flops summed over the two chains.
+ * cdc_decode_chains: the decision (1 or 2) for a plain decode of B images of H x W on this handle as it is set; touches no device. */
+int cdc_set_decode_chains(cdc_handle *h, int n);
+int cdc_decode_chains(const cdc_handle *h, int B, int H, int W);
 /* Per-launch view of the same events: one entry per kernel launch of the current program (label = kernel kind,
  * shape and launch plan; ms = accumulated GPU time over `launches` instrumented executions; flops per execution). */
 int cdc_prof_num_ops(cdc_handle *h);

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Development aid: does running two half-batches on two streams (two handles, two host threads) beat one
-full batch?  The few-pixel levels leave most CUs idle; another stream's high-resolution kernels can fill them."""
+full batch?  The few-pixel levels leave most CUs idle; another stream's high-resolution kernels can fill them.
+The library does this natively now -- one handle, one host thread, shared weights: cdc_set_decode_chains(h, 2) / Unet.set_decode_chains(2)
+(tools/split_time.py measures it).  This script stays as the two-handle baseline."""
 import os, sys, threading, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
