@@ -61,7 +61,12 @@ class StreamInfo(ctypes.Structure):
                 ("declared", ctypes.c_ulonglong), ("floor", ctypes.c_ulonglong)]
 
 
-SEG_OK, SEG_ABSENT, SEG_DAMAGED = 0, 1, 2                        # CDC_SEG_* of include/cdc_hip.h
+class ParallelInfo(ctypes.Structure):
+    """cdc_parallel_info of include/cdc_hip.h (cdc_decode_parallel)."""
+    _fields_ = [("sweeps", ctypes.c_int), ("rows_evaluated", ctypes.c_int), ("max_stride", ctypes.c_int), ("max_residual", ctypes.c_double)]
+
+
+SEG_OK, SEG_ABSENT, SEG_DAMAGED = 0, 1, 2                       # CDC_SEG_* of include/cdc_hip.h
 
 
 class CdcError(RuntimeError):
@@ -189,6 +194,11 @@ def lib():
     L.cdc_op_trace_tap.argtypes = [H, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp]
     L.cdc_repeat_images.argtypes =[H, _vp, _vp, _i, _i, ctypes.c_int64, _i, _i, _vp]
     L.cdc_decode_samples.argtypes = [H, ctypes.c_float, u64p, ctypes.c_float, pp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]
+    L.cdc_decode_parallel.argtypes = [H, _vp, ctypes.c_float, u64p, ctypes.c_float, pp, _i, _vp, _i, _i, _i, _i, _i, _i, ctypes.c_float,
+                                      ctypes.POINTER(_i), ctypes.POINTER(ParallelInfo), _i, _vp]
+    L.cdc_parallel_stride.argtypes = [ctypes.POINTER(ctypes.c_double), _i, _i, _i, ctypes.c_double, ctypes.c_double]
+    L.cdc_parallel_row_steps.argtypes = [_i, _i, _i, ctypes.POINTER(_i)]
+    L.cdc_op_window_update.argtypes = [H, _vp, _vp, u64p, ctypes.c_float, _i, _i, ctypes.POINTER(ctypes.c_double)] + [_i] * 7 + [_vp]
     L.cdc_sample_moments.argtypes = [H, _vp, _i, _i, ctypes.c_int64, _i, _vp, _vp, _i, _i, _vp]
     L.cdc_sample_select.argtypes = [H, _vp, ctypes.POINTER(_i), _vp, _i, _i, ctypes.c_int64, _i, _vp]
     L.cdc_randn.argtypes = [H, u64p, _i, ctypes.c_int64, ctypes.c_uint32, ctypes.c_float, _vp, _i, _vp]
@@ -251,7 +261,8 @@ EXPORTS = ["cdc_create", "cdc_destroy", "cdc_last_error", "cdc_version", "cdc_nu
            "cdc_entropy_set_segments", "cdc_entropy_peek_segments", "cdc_entropy_decode_window",
            "cdc_entropy_set_hyper_groups", "cdc_entropy_peek_hyper_groups",
            "cdc_entropy_peek_partial", "cdc_entropy_decode_partial", "cdc_segment_mask",
-           "cdc_set_decode_chains", "cdc_decode_chains"]
+           "cdc_set_decode_chains", "cdc_decode_chains", "cdc_decode_parallel", "cdc_op_window_update", "cdc_parallel_stride",
+           "cdc_parallel_row_steps"]
 
 
 def handle_status(handle):

@@ -82,14 +82,19 @@ int run_pre(cdc_handle *h, hipStream_t st) {
     return CDC_OK;
 }
 
-// step >= 0: sampler iteration `step` (time-embedding shifts come from the per-decode table);
-// step < 0: plain Unet.forward with the caller's per-image time values.
+// step >= 0: sampler iteration `step` (time-embedding shifts come from the per-decode table); step == -2: the same with the step
+// index in device memory (graph replay); step == -3: row r at sample index h->win_steps[r] (cdc_decode_parallel);
+// step == -1: plain Unet.forward with the caller's per-image time values.
 int run_unet(cdc_handle *h, hipStream_t st, int step, bool skip_combine) {
     for (const Op &op : h->ops) {
         if (h->mark_ev && &op - h->ops.data() == h->trunk_op) HIP_TRY(h, hipEventRecord(h->mark_ev, st));   // (split decode: initial skew)
         if (skip_combine && op.get<CombineArgs>()) continue;      // (the sampler kernel evaluates it: sampler_on_device)
         int rc;
-        if (op.get<TembArgs>() && (step >= 0 || step == -2)) {      // the shifts of the step: a row of the per-decode table, under TEMB's id
+        if (op.get<TembArgs>() && step == -3) {      // a window of steps: every row its own row of the table (h->win_steps), under TEMB's id
+            Op sop(op.prof, ShiftRowsArgs{h->d_shift_tab.p, h->win_steps.p, h->shift, h->shift_bs}, op.flops, op.bytes);
+            sop.id = op.id;
+            rc = run_op(h, sop, h->pB, st);
+        } else if (op.get<TembArgs>() && (step >= 0 || step == -2)) {      // the shifts of the step: a row of the per-decode table, under TEMB's id
             CopyArgs c = {h->d_shift_tab.p + (step >= 0 ? (size_t)step * h->shift_bs : 0), 0, h->shift, h->shift_bs, h->shift_bs};
             if (step == -2) { c.step = h->d_step; c.step_stride = h->shift_bs; }
             Op cop(op.prof, c, op.flops, op.bytes);
@@ -366,6 +371,10 @@ void cdc_destroy(cdc_handle *h) {
     h->d_hist.release();
     h->d_rep_stage.release();
     h->picks.dev.release();
+    h->win_last.release();
+    h->win_partial.release();
+    h->win_res.release();
+    h->win_steps.release();
     h->rdo_map.release();
     if (h->metric_work) (void)hipFree(h->metric_work);
     if (h->map_work) (void)hipFree(h->map_work);
@@ -1540,6 +1549,219 @@ int cdc_decode_samples(cdc_handle *h, float gamma, const uint64_t *seeds, float 
     if (solver && eta != 0.f) return fail(h, CDC_ERR_INVALID, "cdc_decode_samples: the multistep update is deterministic, eta must be 0");
     if (mem != CDC_MEM_HOST && mem != CDC_MEM_DEVICE) return fail(h, CDC_ERR_INVALID, "cdc_decode_samples: mem_kind %d", mem);
     return no_throw(h, [&] { return decode_impl(h, nullptr, gamma, seeds, eta, ctx, n_ctx, out, B * K, H, W, pred_mode, clip, mem, stream, solver != 0, K); });
+}
+
+// ---- parallel-in-time decode: Picard sweeps over a window of sampler steps (the kernels: sampler_kernels.hip) -----------------
+namespace {
+// The stride of a sweep from its residual table res [B][p] (sums of squared changes over an image of `numel` elements): the number of
+// leading live rows that every image accepts, sqrt(res / numel) <= tol, and at least 1 -- row 0 is computed from the exact y_w.
+// *accepted_max: the largest RMS change among the rows 1 .. stride-1, which the tolerance let pass.  cdc_parallel_stride exposes this
+// function to the CPU tests; picard.stride restates it.
+int window_stride(const double *res, int B, int p, int live, double numel, double tol, double *accepted_max) {
+    int s = 0;
+    for (; s < live; ++s) {
+        bool ok = true;
+        for (int b = 0; b < B; ++b) ok = ok && sqrt(res[(size_t)b * p + s] / numel) <= tol;
+        if (!ok) break;
+    }
+    s = std::max(1, s);
+    for (int m = 1; m < s; ++m)
+        for (int b = 0; b < B; ++b) *accepted_max = std::max(*accepted_max, sqrt(res[(size_t)b * p + m] / numel));
+    return s;
+}
+
+// steps [p]: the sample index of the state in every slot of an image's ring at window base w.  Slot (j mod p) holds state y_j,
+// j = w .. w + p - 1, and is evaluated at sample index N - 1 - j; a row past the end of the schedule is dead: a valid index (clamped
+// to 0), a result nobody reads.  cdc_parallel_row_steps exposes this function; picard.row_steps restates it.
+void window_row_steps(int w, int p, int N, int *steps) {
+    for (int k = 0; k < p; ++k) steps[(w + k) % p] = std::max(0, N - 1 - (w + k));
+}
+
+constexpr int kMaxWindow = 256;                       // rows of a window: 4 * 256 doubles of LDS in the update kernel
+constexpr size_t kMaxWindowPartials = (size_t)1 << 25;   // doubles of the residual partial table: 256 MiB
+
+// The line in the per-op table (cdc_prof_op) of an op that the launch program does not hold, added on first use
+int extra_op_id(cdc_handle *h, const char *label) {
+    for (size_t i = h->op_label.size(); i-- > 0;)
+        if (h->op_label[i] == label) return (int)i;
+    h->op_ms.push_back(0); h->op_n.push_back(0); h->op_flops.push_back(0); h->op_label.push_back(label);
+    return (int)h->op_ms.size() - 1;
+}
+
+WindowArgs window_args(cdc_handle *h, const float *fx, float *ring, float *last, const unsigned long long *dseeds, float eta, int w, int p, int B,
+                       int C, int H, int W, int pred_mode, int clip, double *partial, double *res, int *fault) {
+    WindowArgs a = {};
+    a.d.s = sampler_args(h, fx, ring, ring, 0, B, C, H, W, pred_mode, clip, fault);
+    a.d.eta = eta;
+    if (eta != 0.f) { a.d.seeds = dseeds; a.d.per_image = (long long)C * H * W; }
+    a.ring = ring; a.last = last; a.w = w; a.p = p; a.live = std::min(p, h->steps - w); a.B = B; a.per = (long long)C * H * W;
+    a.vec = ((long long)H * W) % 4 == 0 && (((uintptr_t)fx | (uintptr_t)ring | (uintptr_t)last) & 15) == 0;
+    a.partial = partial; a.res = res;
+    return a;
+}
+}  // namespace
+
+int cdc_decode_parallel(cdc_handle *h, const float *init, float gamma, const uint64_t *seeds, float eta, const float *const *ctx, int n_ctx,
+                        float *out, int B, int H, int W, int pred_mode, int clip, int window, float tol, int *strides, cdc_parallel_info *info,
+                        int mem, void *stream) {
+    if (!h) return CDC_ERR_INVALID;
+    if (!(fabsf(eta) <= 3.0e38f) || !(fabsf(gamma) <= 3.0e38f)) return fail(h, CDC_ERR_INVALID, "cdc_decode_parallel: eta / gamma not finite");
+    if (eta != 0.f && !seeds) return fail(h, CDC_ERR_INVALID, "cdc_decode_parallel: eta != 0 needs seeds (a noise tensor is not supported)");
+    if (!(tol >= 0.f)) return fail(h, CDC_ERR_INVALID, "cdc_decode_parallel: tol %g (must be >= 0)", (double)tol);
+    if (B < 1) return fail(h, CDC_ERR_INVALID, "cdc_decode_parallel: B=%d (must be >= 1)", B);
+    if (window < 2) return fail(h, CDC_ERR_INVALID, "cdc_decode_parallel: window %d (must lie in [2, steps])", window);
+    if (window > kMaxWindow) return fail(h, CDC_ERR_INVALID, "cdc_decode_parallel: window %d, beyond the update kernel's %d rows", window, kMaxWindow);
+    if ((long long)B * window > 65535)
+        return fail(h, CDC_ERR_INVALID, "cdc_decode_parallel: B * window = %lld rows, beyond the generator's 65535", (long long)B * window);
+    if (mem != CDC_MEM_HOST && mem != CDC_MEM_DEVICE) return fail(h, CDC_ERR_INVALID, "cdc_decode_parallel: mem_kind %d", mem);
+    return no_throw(h, [&] {
+        return with_range_guard(h, [&]() -> int {
+            int rc = require_kind(h, HandleKind::Unet);
+            if (rc) return rc;
+            if ((rc = check_ready(h))) return rc;
+            if ((rc = sampler_ready(h, pred_mode, clip, false))) return rc;
+            if (!out || !ctx) return fail(h, CDC_ERR_INVALID, "null argument");
+            const int N = h->steps, p = window, rows = B * p, C = h->cfg.channels;
+            if (p > N) return fail(h, CDC_ERR_INVALID, "cdc_decode_parallel: window %d (must lie in [2, steps = %d])", p, N);
+            if (!h->trace_steps.empty())
+                return fail(h, CDC_ERR_INVALID, "cdc_decode_parallel: a trace is set (cdc_set_trace); a trajectory belongs to a sequential decode");
+            if (!h->noise_frames.empty())
+                return fail(h, CDC_ERR_INVALID, "cdc_decode_parallel: noise frames are set (cdc_set_noise_frames); a tiled decode is a sequential decode");
+            if (h->twin && h->twin->pB) free_program(h->twin);       // (one chain: a twin's program would only hold memory)
+            if ((rc = build_program(h, rows, H, W))) return rc;
+            if ((rc = ensure_time_rows(h, rows))) return rc;
+            hipStream_t st = pick_stream(h, stream, mem);
+            const size_t per = (size_t)C * H * W;
+            const int G = window_groups((long long)per);
+            if ((size_t)G * rows > kMaxWindowPartials)
+                return fail(h, CDC_ERR_INVALID, "cdc_decode_parallel: B * window = %d rows of %d x %d need %zu residual partials, beyond %zu: "
+                            "a smaller window or fewer images per call", rows, H, W, (size_t)G * rows, kMaxWindowPartials);
+            // a profiled call: the two ops of a sweep that the launch program does not hold get their lines in the per-op table now
+            const int id_update = h->prof ? extra_op_id(h, "window update") : -1, id_fill = h->prof ? extra_op_id(h, "window fill") : -1;
+            if ((rc = h->win_last.grow(h, (size_t)B * per)) || (rc = h->win_partial.grow(h, (size_t)G * rows)) ||
+                (rc = h->win_res.grow(h, (size_t)rows)) || (rc = h->win_steps.grow(h, (size_t)rows)))
+                return rc;
+            h->win_steps_host.assign((size_t)rows, 0);
+            h->win_res_host.assign((size_t)rows, 0.0);
+            if ((rc = arm_range_guard(h, st, true))) return rc;
+            // the generator serves the start image (no init, gamma != 0) and the steps (eta != 0); the BF16X3 repetition stages again
+            const bool gen_init = seeds && !init && gamma != 0.f;
+            const unsigned long long *dseeds = nullptr;
+            if (seeds && (gen_init || eta != 0.f)) {
+                if ((rc = h->seeds.stage(h, seeds, (size_t)B, st))) return rc;
+                dseeds = h->seeds.dev.p;
+            }
+            // y_0 of every image, then the constant guess: every slot of the ring and the state after the window start as y_0
+            if (init) { if ((rc = copy_in(h, h->win_last.p, init, (size_t)B * per, mem, st))) return rc; }
+            else if (gen_init) HIP_TRY(h, randn_fill_launch(dseeds, B, (long long)per, 0u, gamma, h->win_last.p, st));
+            else HIP_TRY(h, hipMemsetAsync(h->win_last.p, 0, (size_t)B * per * sizeof(float), st));
+            HIP_TRY(h, repeat_images_launch({h->win_last.p, h->in_x, (long long)per, p, 4}, B, st));
+            if ((rc = stage_ctx_repeated(h, ctx, n_ctx, B, p, mem, st))) return rc;
+            h->prof_now = false;
+            if ((rc = run_pre(h, st))) return rc;       // hoisted context halves: once per decode
+            cdc_parallel_info pi = {0, 0, 0, 0.0};
+            if (strides) std::fill(strides, strides + N, 0);
+            for (int w = 0; w < N;) {
+                for (int b = 0; b < B; ++b) window_row_steps(w, p, N, &h->win_steps_host[(size_t)b * p]);
+                HIP_TRY(h, hipMemcpyAsync(h->win_steps.p, h->win_steps_host.data(), (size_t)rows * sizeof(int), hipMemcpyHostToDevice, st));
+                h->prof_now = (pi.sweeps % h->prof_every) == 0;
+                if ((rc = run_unet(h, st, -3))) return rc;
+                const WindowArgs a = window_args(h, h->out_fx, h->in_x, h->win_last.p, dseeds, eta, w, p, B, C, H, W, pred_mode, clip,
+                                                 h->win_partial.p, h->win_res.p, h->d_fault);
+                Op uop(PC_SMALL, a, 0, 12.0 * a.live * B * per + 12.0 * B * per);
+                uop.id = id_update;
+                if ((rc = run_op(h, uop, B, st))) return rc;
+                // the stride depends on the residuals: one small read-back and a synchronisation per sweep (it also frees win_steps_host)
+                HIP_TRY(h, hipMemcpyAsync(h->win_res_host.data(), h->win_res.p, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, st));
+                HIP_TRY(h, hipStreamSynchronize(st));
+                const int s = window_stride(h->win_res_host.data(), B, p, a.live, (double)per, (double)tol, &pi.max_residual);
+                if (strides) strides[pi.sweeps] = s;
+                ++pi.sweeps;
+                pi.rows_evaluated += rows;
+                pi.max_stride = std::max(pi.max_stride, s);
+                // the new positions y_{w+p+1} .. y_{w+p+s-1} (those inside the schedule) start as y'_{w+p}, which the update left in
+                // `last` and in the slot of y_w; y_{w+p+s} is the next window's `last`, unchanged.  Each is written once.
+                const int n_new = std::min(s - 1, N - (w + p));
+                if (n_new > 0) {
+                    Op fop(PC_SMALL, WindowFillArgs{h->win_last.p, h->in_x, w, p, 1, n_new, (long long)per, a.vec}, 0, 8.0 * n_new * B * per);
+                    fop.id = id_fill;
+                    if ((rc = run_op(h, fop, B, st))) return rc;
+                }
+                w += s;
+            }
+            h->prof_now = true;
+            // y_N lies in slot (N mod p) of every image.  Range guard: the update kernel flags a non-finite U-Net output in the sweep it
+            // occurs in; the final images are checked as well.
+            const float *fin = h->in_x + (size_t)(N % p) * per;
+            if ((rc = range_check(h, {{fin, (long long)p * (long long)per, (long long)per}}, B, st))) return rc;
+            for (int b = 0; b < B; ++b)
+                HIP_TRY(h, hipMemcpyAsync(out + (size_t)b * per, fin + (size_t)b * p * per, per * sizeof(float),
+                                          mem == CDC_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+            if (mem == CDC_MEM_HOST) HIP_TRY(h, hipStreamSynchronize(st));
+            if (info) *info = pi;
+            return CDC_OK;
+        });
+    });
+}
+
+int cdc_parallel_stride(const double *residuals, int B, int window, int live, double numel, double tol) {
+    if (!residuals || B < 1 || window < 1 || live < 0 || live > window || !(numel > 0)) return CDC_ERR_INVALID;
+    double unused = 0.0;
+    return window_stride(residuals, B, window, live, numel, tol, &unused);
+}
+
+int cdc_parallel_row_steps(int w, int window, int steps, int *out) {
+    if (!out || w < 0 || window < 1 || steps < 1) return CDC_ERR_INVALID;
+    window_row_steps(w, window, steps, out);
+    return CDC_OK;
+}
+
+int cdc_op_window_update(cdc_handle *h, const float *fx, float *y, const uint64_t *seeds, float eta, int w, int window, double *residuals,
+                         int B, int C, int H, int W, int pred_mode, int clip, int mem, void *stream) {
+    if (!h) return CDC_ERR_INVALID;
+    return no_throw(h, [&] {
+        return with_range_guard(h, [&]() -> int {
+            int rc = require_kind(h, HandleKind::Unet);
+            if (rc) return rc;
+            if ((rc = ensure_device(h))) return rc;
+            if ((rc = sampler_ready(h, pred_mode, clip, false))) return rc;
+            if (!fx || !y || !residuals) return fail(h, CDC_ERR_INVALID, "null argument");
+            if (B < 1 || B > 65535 || C < 1 || H < 1 || W < 1 || (long long)C * H * W > (1ll << 30))
+                return fail(h, CDC_ERR_INVALID, "window_update: %d x %d x %d x %d elements", B, C, H, W);
+            if (window < 2 || window > kMaxWindow || window > h->steps)
+                return fail(h, CDC_ERR_INVALID, "window_update: window %d (must lie in [2, min(steps, %d)])", window, kMaxWindow);
+            if (w < 0 || w >= h->steps) return fail(h, CDC_ERR_INVALID, "window_update: window base %d out of [0,%d)", w, h->steps);
+            if (mem != CDC_MEM_HOST && mem != CDC_MEM_DEVICE) return fail(h, CDC_ERR_INVALID, "window_update: mem_kind %d", mem);
+            if (!(fabsf(eta) <= 3.0e38f)) return fail(h, CDC_ERR_INVALID, "window_update: eta is not finite");
+            if (eta != 0.f && !seeds) return fail(h, CDC_ERR_INVALID, "window_update: eta != 0 needs seeds (a noise tensor is not supported)");
+            hipStream_t st = pick_stream(h, stream, mem);
+            const int p = window, live = std::min(p, h->steps - w), G = window_groups((long long)C * H * W);
+            const size_t per = (size_t)C * H * W, pb = per * sizeof(float);
+            if (eta != 0.f && (rc = h->seeds.stage(h, seeds, (size_t)B, st))) return rc;
+            Staging s(h, mem, st);
+            const float *dfx = s.in(fx, (size_t)B * p * pb);
+            float *dy = mem == CDC_MEM_DEVICE ? y : s.out(y, (size_t)B * (p + 1) * pb, (void *)s.in(y, (size_t)B * (p + 1) * pb));
+            // the ring as the decode lays it out: window row m in slot (w + m) mod p; the state after the window in `last`
+            float *ring = (float *)s.scratch((size_t)B * p * pb), *fxr = (float *)s.scratch((size_t)B * p * pb), *last = (float *)s.scratch((size_t)B * pb);
+            double *partial = (double *)s.scratch((size_t)G * B * p * sizeof(double)), *res = (double *)s.scratch((size_t)B * p * sizeof(double));
+            for (int b = 0; b < B && s.ok(); ++b) {
+                for (int m = 0; m < p && s.ok(); ++m) {
+                    const size_t slot = (size_t)b * p + (w + m) % p;
+                    s.e = hipMemcpyAsync(ring + slot * per, dy + ((size_t)b * (p + 1) + m) * per, pb, hipMemcpyDeviceToDevice, st);
+                    if (s.ok()) s.e = hipMemcpyAsync(fxr + slot * per, dfx + ((size_t)b * p + m) * per, pb, hipMemcpyDeviceToDevice, st);
+                }
+                if (s.ok()) s.e = hipMemcpyAsync(last + (size_t)b * per, dy + ((size_t)b * (p + 1) + p) * per, pb, hipMemcpyDeviceToDevice, st);
+            }
+            if (s.ok()) s.e = window_update_launch(window_args(h, fxr, ring, last, h->seeds.dev.p, eta, w, p, B, C, H, W, pred_mode, clip, partial, res, nullptr), st);
+            for (int b = 0; b < B; ++b)
+                for (int m = 0; m < live && s.ok(); ++m) {
+                    const float *src = m + 1 == p ? last + (size_t)b * per : ring + ((size_t)b * p + (w + m + 1) % p) * per;
+                    s.e = hipMemcpyAsync(dy + ((size_t)b * (p + 1) + m + 1) * per, src, pb, hipMemcpyDeviceToDevice, st);
+                }
+            s.fetch(residuals, res, (size_t)B * p * sizeof(double));
+            return s.finish("window_update");
+        });
+    });
 }
 
 namespace {

@@ -298,6 +298,32 @@ struct TraceArgs {
     int u8, win_h, win_w;
 };
 hipError_t trace_tap_launch(const TraceArgs &a, hipStream_t st);
+// sampler_kernels.hip: one Picard sweep over a window of p sampler steps (cdc_decode_parallel; include/cdc_hip.h states the recurrence).
+// The states of B images live in a ring of p slots per image, d.s.x [B][p][per]: slot (j mod p) holds the guess of state y_j, sampling
+// order j = 0 .. steps (sample index i = steps - 1 - j).  fx [B][p][per] holds the model output of every slot.  Rows m = 0 .. live-1 of
+// the window at base w: x = y_{w+m} (slot (w+m) mod p), the DDIM update of sample index steps - 1 - (w+m) with that row's constants and
+// draws, plus the carry; the new guess of y_{w+m+1} goes to slot (w+m+1) mod p, over the old one.  Row p - 1 wraps onto the slot of
+// y_w, which that thread has read by then: the old guess of y_{w+p} is read from `last` [B][per], the new one goes to `last` and to
+// the slot.  d.s.fx, d.s.x, d.s.tab, d.s.tab_v, d.s.steps, d.s.pred_mode, d.s.clip, d.s.fault, d.eta, d.seeds are read; d.noise and
+// the fused combine (d.s.P) are not supported.  partial: [workgroups per image][B][p] doubles (window_groups); res: [B][p] doubles, the
+// squared change of every live row summed over the image (0 for a dead row).
+struct WindowArgs {
+    DdimArgs d;
+    float *ring;           // = d.s.x, written
+    float *last;
+    int w, p, live, B;
+    long long per;         // elements of one image: C H W
+    bool vec;              // H W % 4 == 0 and every pointer 16-byte aligned: 16-byte accesses
+    double *partial, *res;
+};
+int window_groups(long long per);
+hipError_t window_update_launch(const WindowArgs &a, hipStream_t st);
+// ring slot (w + k) mod p of every image <- last, k = k0 .. k0 + n - 1: the constant guess of the window's new positions
+struct WindowFillArgs { const float *last; float *ring; int w, p, k0, n; long long per; bool vec; };
+hipError_t window_fill_launch(const WindowFillArgs &a, int B, hipStream_t st);
+// shift[r] = tab[step_of_row[r]], r < rows: the time-embedding shifts of a batch whose rows stand at different steps
+struct ShiftRowsArgs { const float *tab; const int *step_of_row; float *shift; int shift_bs; };
+hipError_t shift_rows_launch(const ShiftRowsArgs &a, int rows, hipStream_t st);
 // out[b][e] = scale * z(seeds[b], draw, e) for e < per_image (rng.h; seeds on the device); 16-byte stores when the layout allows
 hipError_t randn_fill_launch(const unsigned long long *seeds, int B, long long per_image, unsigned draw, float scale, float *out,
                              hipStream_t st);

@@ -94,7 +94,8 @@ struct CtxFoldOp { AttnCtxArgs a; };
 struct FrameOutOp { const float *src; void *dst; int u8, P, H, W, Hp, Wp; };    // the crop kernel (frame_kernels.hip): a trajectory's x_t bytes
 using OpPayload = std::variant<ConvOp, PfConvOp, PwConvOp, WsConvOp, Ws1ConvOp, PfPackOp, C4PackOp, PfUnpackOp, LnArgs, TembArgs, KstatsOp,
                                CtxPartialOp, CtxOneOp, CtxReduceOp, CtxFoldOp, KvCtxArgs, LnConvArgs, CombineArgs, DdimArgs, SolverArgs, CopyArgs,
-                               UnfoldArgs, VbrArgs, MaxpoolArgs, LpipsHeadArgs, GdnArgs, TraceArgs, FrameOutOp>;
+                               UnfoldArgs, VbrArgs, MaxpoolArgs, LpipsHeadArgs, GdnArgs, TraceArgs, FrameOutOp, WindowArgs, WindowFillArgs,
+                               ShiftRowsArgs>;
 
 struct Op {
     int prof;
@@ -135,6 +136,9 @@ inline hipError_t op_launch(const LpipsHeadArgs &a, int B, hipStream_t st) { ret
 inline hipError_t op_launch(const GdnArgs &a, int B, hipStream_t st) { return gdn_launch(a, B, st); }
 inline hipError_t op_launch(const TraceArgs &a, int, hipStream_t st) { return trace_tap_launch(a, st); }
 inline hipError_t op_launch(const FrameOutOp &o, int, hipStream_t st) { return frame_out_launch(o.src, o.dst, o.u8, o.P, o.H, o.W, o.Hp, o.Wp, st); }
+inline hipError_t op_launch(const WindowArgs &a, int, hipStream_t st) { return window_update_launch(a, st); }
+inline hipError_t op_launch(const WindowFillArgs &a, int B, hipStream_t st) { return window_fill_launch(a, B, st); }
+inline hipError_t op_launch(const ShiftRowsArgs &a, int B, hipStream_t st) { return shift_rows_launch(a, B, st); }     // (B: the rows of the program)
 
 // The op's line of the per-op profile table (cdc_prof_op).  hoisted: the op belongs to the context-only part of the program; the
 // convolutions say so in the middle of their line, Builder::emit appends " HOIST" to every other hoisted op.
@@ -186,6 +190,9 @@ inline void op_label(const LpipsHeadArgs &a, char *buf, size_t n, bool) { snprin
 inline void op_label(const GdnArgs &a, char *buf, size_t n, bool) { snprintf(buf, n, "gdn C=%d HW=%d%s", a.C, a.HW, a.inverse ? " inv" : ""); }
 inline void op_label(const TraceArgs &a, char *buf, size_t n, bool) { snprintf(buf, n, "trace x0%s", a.u8 ? " u8" : ""); }
 inline void op_label(const FrameOutOp &o, char *buf, size_t n, bool) { snprintf(buf, n, "trace x_t%s", o.u8 ? " u8" : ""); }
+inline void op_label(const WindowArgs &, char *buf, size_t n, bool) { snprintf(buf, n, "window update"); }
+inline void op_label(const WindowFillArgs &, char *buf, size_t n, bool) { snprintf(buf, n, "window fill"); }
+inline void op_label(const ShiftRowsArgs &, char *buf, size_t n, bool) { snprintf(buf, n, "shift rows"); }
 
 struct GdnW { int C = 0; bool inverse = false; float *beta = nullptr, *gamma = nullptr; };   // one GDN1 layer: reparametrised beta' [C], gamma' [C][C] (device)
 struct VbrW { int C = 0; float *p = nullptr; };   // one VBRCondition site: [scale.weight | scale.bias | shift.weight | shift.bias], C each
@@ -351,6 +358,13 @@ struct cdc_handle {
     void *trace_buf = nullptr;
     size_t trace_cap = 0, tr_slot_bytes = 0;
     int tr_slots = 0, tr_what = 0, tr_B = 0, tr_C = 0, tr_H = 0, tr_W = 0;
+    // parallel-in-time decode (cdc_decode_parallel): the guess of the state after the window [B][per], the residual partials
+    // and sums of a sweep, and the sample index of every row of the program (written once per sweep)
+    GrowBuf<float> win_last;
+    GrowBuf<double> win_partial, win_res;
+    GrowBuf<int> win_steps;
+    std::vector<int> win_steps_host;
+    std::vector<double> win_res_host;
     int op_stress_n = 0;                 // cdc_op_stress: extra executions of every cdc_op_* program, results compared on the device
     long long op_stress_launches = 0, op_stress_differing = 0;
     // profiling

@@ -1,8 +1,9 @@
 // sampler_kernels.hip -- one sampler step: the model output (a tensor, or the 7-row combine of the final convolution's partial planes),
 // the prediction x0, and one of two update rules -- DDIM (xparam/modules/denoising_diffusion.py:152-174, epsilonparam :137-152; same
 // operation order as the reference) or the second-order multistep update (SolverArgs) -- in one of two traversals.  Beside them the
-// tap of a decode trajectory (the x0 of a step, written to a slot), the step counter of a graph-replayed iteration and the fill kernel
-// of the generator (rng.h).
+// tap of a decode trajectory (the x0 of a step, written to a slot), the update of one Picard sweep over a window of steps (the DDIM rule
+// row by row with a carry, the residuals, the fill of new window positions, the per-row time shifts), the step counter of a
+// graph-replayed iteration and the fill kernel of the generator (rng.h).
 #include <math.h>
 #include <stdint.h>
 
@@ -328,6 +329,151 @@ hipError_t trace_tap_launch(const TraceArgs &a, hipStream_t st) {
         if (a.u8) hipLaunchKernelGGL(trace_tap_kernel<true>, dim3(grid), dim3(256), 0, st, a);
         else hipLaunchKernelGGL(trace_tap_kernel<false>, dim3(grid), dim3(256), 0, st, a);
     }
+    return hipGetLastError();
+}
+
+// ---- one Picard sweep over a window of sampler steps (WindowArgs; cdc_internal.h states the ring, include/cdc_hip.h the recurrence) -----
+// The constants of sample index si, as step_consts makes them of the launch's own step (the clip comes per image: clip_n is not used)
+__device__ __forceinline__ StepConsts step_consts_at(const SamplerArgs &s, int si) {
+    return {si, s.pred_mode, s.tab[0 * s.steps + si], s.tab[1 * s.steps + si], s.tab_v ? s.tab_v[si] : 0.f, s.tab_v ? s.tab_v[s.steps + si] : 0.f, 0};
+}
+// four consecutive elements of which the first nv exist: one 16-byte access (VEC: nv is 0 or 4), or element by element
+template <bool VEC>
+__device__ __forceinline__ void load4(const float *p, int nv, float v[4]) {
+    if constexpr (VEC) {
+        if (nv) { const float4 q = *reinterpret_cast<const float4 *>(p); v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w; }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (c < nv) v[c] = p[c];
+    }
+}
+template <bool VEC>
+__device__ __forceinline__ void store4(float *p, int nv, const float v[4]) {
+    if constexpr (VEC) {
+        if (nv) *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (c < nv) p[c] = v[c];
+    }
+}
+// the sum over the 64 lanes in a fixed tree, valid in lane 0
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;
+}
+
+// One thread owns four consecutive elements of image blockIdx.y and walks the live rows in window order: the row's input state and the
+// carry stay in registers (the input of row m + 1 is the old guess that row m read), so a row costs two reads (model output, old guess
+// of the next state) and one write, in place: every element is read by its owner before it is overwritten and by nobody else.
+// Residuals: (new - old)^2 formed in float32 from the stored values, summed in float64 over the wave, then over the workgroup's four
+// waves in wave order, into partial[blockIdx.x][image][row]; window_residual_kernel finishes them in workgroup order.  No atomics.
+template <int NOISE, bool VEC>
+__global__ void __launch_bounds__(256) window_update_kernel(const WindowArgs a) {
+    extern __shared__ double wsum[];                      // [4 waves][p]
+    const SamplerArgs &s = a.d.s;
+    const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long q = (long long)blockIdx.x * 256 + threadIdx.x, e0 = 4 * q;
+    const int nv = e0 >= a.per ? 0 : (int)(a.per - e0 < 4 ? a.per - e0 : 4);
+    const bool clip = s.clip == 1 || (s.clip == 2 && b < a.B / 2);
+    const size_t img = (size_t)b * a.p;
+    float x[4] = {0.f, 0.f, 0.f, 0.f}, carry[4] = {0.f, 0.f, 0.f, 0.f};
+    bool bad = false;
+    load4<VEC>(a.ring + (img + a.w % a.p) * a.per + e0, nv, x);
+    for (int m = 0; m < a.live; ++m) {
+        const int j = a.w + m;
+        const StepConsts k = step_consts_at(s, s.steps - 1 - j);
+        const DdimRule<NOISE> rule(a.d, k);
+        const bool wrap = m == a.p - 1;                   // the slot of y_{w+p} is the slot of y_w, read above
+        float *const dst = a.ring + (img + (j + 1) % a.p) * a.per + e0, *const lst = a.last + (size_t)b * a.per + e0;
+        float fx[4] = {0.f, 0.f, 0.f, 0.f}, old[4] = {0.f, 0.f, 0.f, 0.f}, nz[4] = {0.f, 0.f, 0.f, 0.f}, y[4];
+        load4<VEC>(s.fx + (img + j % a.p) * a.per + e0, nv, fx);
+        load4<VEC>(wrap ? lst : dst, nv, old);
+        if constexpr (NOISE == NOISE_SEEDED) {
+            if (nv) cdcrng::normal4(a.d.seeds[b], (uint32_t)q, (uint32_t)k.si + 1u, nz);     // the quad of the sequential kernels
+        }
+        double sq = 0.0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+#pragma clang fp contract(off)
+            bad |= c < nv && nonfinite(fx[c]);
+            y[c] = rule.next(fx[c], x[c], nz[c], clip, NOISE == NOISE_SEEDED) + carry[c];
+            carry[c] = y[c] - old[c];
+            const float d2 = carry[c] * carry[c];
+            if (c < nv) sq += (double)d2;
+            x[c] = old[c];
+        }
+        store4<VEC>(dst, nv, y);
+        if (wrap) store4<VEC>(lst, nv, y);
+        sq = wave_sum(sq);
+        if (lane == 0) wsum[wave * a.p + m] = sq;
+    }
+    __syncthreads();
+    for (int m = threadIdx.x; m < a.live; m += 256)
+        a.partial[((size_t)blockIdx.x * a.B + b) * a.p + m] = ((wsum[m] + wsum[a.p + m]) + wsum[2 * a.p + m]) + wsum[3 * a.p + m];
+    if (bad && s.fault) *s.fault = 1;
+}
+
+// res[b][m] = the sum over the G workgroups of an image, in workgroup order; 0 for a dead row (its partials are not written)
+__global__ void __launch_bounds__(256) window_residual_kernel(const double *partial, double *res, int G, int B, int p, int live) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;          // = b * p + m
+    if (t >= B * p) return;
+    double sum = 0.0;
+    if (t % p < live)
+        for (int g = 0; g < G; ++g) sum += partial[(size_t)g * B * p + t];
+    res[t] = sum;
+}
+
+int window_groups(long long per) { return (int)(((per + 3) / 4 + 255) / 256); }
+
+hipError_t window_update_launch(const WindowArgs &a, hipStream_t st) {
+    const SamplerArgs &s = a.d.s;
+    if (a.p < 2 || a.p > 256 || a.live < 1 || a.live > a.p || a.w < 0 || a.w + a.live > s.steps || a.B < 1 || a.B > 65535 || a.per < 1 ||
+        a.per > (1ll << 40) || s.P || a.d.noise || a.d.frames || a.ring != s.x || (a.d.eta != 0.f && !a.d.seeds))
+        return hipErrorInvalidValue;
+    const int G = window_groups(a.per);
+    const dim3 g((unsigned)G, (unsigned)a.B);
+    const size_t lds = (size_t)4 * a.p * sizeof(double);
+    const bool seeded = a.d.eta != 0.f && a.d.seeds;
+    if (seeded && a.vec) hipLaunchKernelGGL((window_update_kernel<NOISE_SEEDED, true>), g, dim3(256), lds, st, a);
+    else if (seeded) hipLaunchKernelGGL((window_update_kernel<NOISE_SEEDED, false>), g, dim3(256), lds, st, a);
+    else if (a.vec) hipLaunchKernelGGL((window_update_kernel<NOISE_TENSOR, true>), g, dim3(256), lds, st, a);
+    else hipLaunchKernelGGL((window_update_kernel<NOISE_TENSOR, false>), g, dim3(256), lds, st, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(window_residual_kernel, dim3((unsigned)ceil_div(a.B * a.p, 256)), dim3(256), 0, st, a.partial, a.res, G, a.B, a.p, a.live);
+    return hipGetLastError();
+}
+
+// grid (quads of an image, new positions, images)
+template <bool VEC>
+__global__ void __launch_bounds__(256) window_fill_kernel(const WindowFillArgs a) {
+    const long long e0 = 4 * ((long long)blockIdx.x * 256 + threadIdx.x);
+    const int nv = e0 >= a.per ? 0 : (int)(a.per - e0 < 4 ? a.per - e0 : 4), b = blockIdx.z;
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    load4<VEC>(a.last + (size_t)b * a.per + e0, nv, v);
+    store4<VEC>(a.ring + ((size_t)b * a.p + (a.w + a.k0 + (int)blockIdx.y) % a.p) * a.per + e0, nv, v);
+}
+
+hipError_t window_fill_launch(const WindowFillArgs &a, int B, hipStream_t st) {
+    if (a.n < 1 || a.n > a.p || a.n > 65535 || B < 1 || B > 65535 || a.per < 1 || a.w < 0 || a.k0 < 0) return hipErrorInvalidValue;
+    const dim3 g((unsigned)window_groups(a.per), (unsigned)a.n, (unsigned)B);
+    if (a.vec) hipLaunchKernelGGL(window_fill_kernel<true>, g, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(window_fill_kernel<false>, g, dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+// grid (pieces of a row, rows)
+__global__ void __launch_bounds__(256) shift_rows_kernel(const ShiftRowsArgs a) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
+    if (t < a.shift_bs) a.shift[(size_t)r * a.shift_bs + t] = a.tab[(size_t)a.step_of_row[r] * a.shift_bs + t];
+}
+
+hipError_t shift_rows_launch(const ShiftRowsArgs &a, int rows, hipStream_t st) {
+    if (rows < 1 || rows > 65535 || a.shift_bs < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(shift_rows_kernel, dim3((unsigned)ceil_div(a.shift_bs, 256), (unsigned)rows), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 

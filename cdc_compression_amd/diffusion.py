@@ -48,7 +48,7 @@ import ctypes
 
 import numpy as np
 
-from . import _lib, frame, lpips, samples as _samples, tiles as _tiles, trajectory as _trajectory
+from . import _lib, frame, lpips, picard as _picard, samples as _samples, tiles as _tiles, trajectory as _trajectory
 from .parallel import expand_seeds, sample_seeds
 from .schedule import SAMPLERS, SampleSchedule
 from .unet import _Arg, _current_stream, _is_torch, _result_like
@@ -245,6 +245,7 @@ class _GaussianDiffusionBase:
         """compress() with the other axis of the rate-distortion plot: takes compress()'s arguments, runs its path once and returns
         {"reconstruction": what compress() returns, "bpp": [B], "psnr": float64 [B], "ms_ssim": float64 [B], or None when
         min(H, W) <= 160}, and "lpips": float64 [B] when the loaded state dict carried the LPIPS-VGG weights (self.loss_fn_vgg).
+        With parallel= also "parallel": the sweep dict of decompress(return_info=True).
         The distortion is measured on the device (cdc_compression_amd.metrics), on the padded frame's H x W window
         against `images` as given (float32 or uint8); as_saved: float32 operands through the uint8 image the reference's script would
         save (metrics.psnr(model, reconstruction, images, as_saved=True) gives the same figures).
@@ -257,7 +258,11 @@ class _GaussianDiffusionBase:
         import inspect
         bound = dict(inspect.signature(self.compress).bind(images, *args, **kwargs).arguments)
         bound.pop("bpp_return_mean", None)                    # bpp comes per image
+        par = self._parallel_arg(bound.get("parallel"), bound.get("parallel_tol"), bound.pop("return_info", False))
         tile_kw = {k: bound.pop(k, None) for k in ("tile", "tile_overlap", "tile_chunk", "region")}
+        if par is not None:
+            self._parallel_check(*par, False, bound.get("sample_steps"), bound.get("spacing", "index"), bound.get("sampler", "ddim"),
+                                 bound.get("eta", 0), bound.get("seed"), *tile_kw.values(), bound.get("trajectory"))
         if any(v is not None for v in tile_kw.values()):
             return self._evaluate_tiled(images, bound, tile_kw, as_saved, maps)
         rate_kw = {k: bound.pop(k, None) for k in ("rdo", "target_bpp", "max_bytes", "price_map", "price_cells")}
@@ -280,6 +285,8 @@ class _GaussianDiffusionBase:
             out["lpips"] = metrics.lpips(self.loss_fn_vgg, rec, images, size=(H, W), as_saved=as_saved)
         if traj is not None:
             out["trajectory"] = self._score_trajectory(traj, images, as_saved)
+        if par is not None:
+            out["parallel"] = dict(self.parallel_info)
         return out
 
     def _evaluate_tiled(self, images, bound, tile_kw, as_saved, maps):
@@ -390,15 +397,42 @@ class _GaussianDiffusionBase:
             kinds[name] = t
         return _trajectory.Trajectory(spec.indices, np.asarray(self.index)[spec.indices], kinds["x0"], kinds["x_t"])
 
-    def _loop(self, shape, context, clip_denoised, init, eta, seed=None, gamma=None, sampler=None, trace=None, window=None):
+    @staticmethod
+    def _parallel_arg(parallel, parallel_tol, return_info=False):
+        """parallel= / parallel_tol= of a call -> what _loop takes: None for the sequential loop, else the pair."""
+        if parallel is None or parallel is False:
+            if parallel_tol is not None:
+                raise ValueError("parallel_tol belongs to parallel=")
+            if return_info:
+                raise ValueError("return_info belongs to parallel=")
+            return None
+        return (parallel, parallel_tol)
+
+    def _parallel_check(self, parallel, parallel_tol, return_info, sample_steps, spacing, sampler, eta, seed, tile, tile_overlap, tile_chunk,
+                        region, trajectory):
+        """compress()'s parallel keywords, checked before the context model runs -> the pair of _parallel_arg or None."""
+        par = self._parallel_arg(parallel, parallel_tol, return_info)
+        if par is not None:
+            tiled = next((v for v in (tile, tile_overlap, tile_chunk, region) if v is not None), None)
+            _picard.check_args(parallel, parallel_tol, self._steps(sample_steps, spacing), None, sampler, eta, seed, tiled, None, trajectory)
+        return par
+
+    def _with_info(self, res, return_info):
+        """(result, parallel_info) when the call asked for it."""
+        return (res, dict(self.parallel_info)) if return_info else res
+
+    def _loop(self, shape, context, clip_denoised, init, eta, seed=None, gamma=None, sampler=None, trace=None, window=None, parallel=None):
         """sampler: None runs what set_sample_schedule was given.  trace: a trajectory.Spec -> (result, Trajectory) cropped to `window`
-        ((H, W) inside the frame; None: the frame)."""
+        ((H, W) inside the frame; None: the frame).  parallel: (window, tol) of picard.check_args -> the decode by Picard sweeps
+        (cdc_decode_parallel); its {"sweeps", "strides", "max_residual", ...} is left in self.parallel_info."""
         B, C, H, W = shape
         sampler = self.sampler if sampler is None else sampler
         self._sampler_args(sampler, eta)
         if sampler != self.sampler:
             raise ValueError(f'the schedule in force was set for sampler "{self.sampler}": set_sample_schedule(..., sampler="{sampler}") first')
         seeds = self._seed_args(seed, gamma, init, B)
+        if parallel is not None:
+            parallel = _picard.check_args(parallel[0], parallel[1], self.sample_steps, B, sampler, eta, seed, trajectory=trace)
         L, un = _lib.lib(), self.denoise_fn
         h = un._handle()
         proto = init if init is not None else context[0]
@@ -420,7 +454,18 @@ class _GaussianDiffusionBase:
                 raise _lib.CdcError("init and context must live in the same memory space")
 
             def device_loop():
-                if sampler == "dpmpp_2m":      # the multistep update in the device loop; the seeds serve the start image only
+                if parallel is not None:
+                    sd = None if seeds is None else np.asarray(seeds, dtype=np.uint64)
+                    strides = (ctypes.c_int * self.sample_steps)()
+                    pinfo = _lib.ParallelInfo()
+                    _lib.check(h, L.cdc_decode_parallel(h, ai.ptr if ai else None, 0.0 if gamma is None else float(gamma),
+                                                        None if sd is None else sd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), float(eta),
+                                                        ptrs, len(actx), optr, B, H, W, pred, clip, parallel[0], parallel[1], strides,
+                                                        ctypes.byref(pinfo), mem, stream))
+                    self.parallel_info = {"window": parallel[0], "tol": parallel[1], "sweeps": int(pinfo.sweeps),
+                                          "strides": [int(v) for v in strides[:pinfo.sweeps]], "max_stride": int(pinfo.max_stride),
+                                          "rows_evaluated": int(pinfo.rows_evaluated), "max_residual": float(pinfo.max_residual)}
+                elif sampler == "dpmpp_2m":      # the multistep update in the device loop; the seeds serve the start image only
                     sd = None if seeds is None else np.asarray(seeds, dtype=np.uint64)
                     _lib.check(h, L.cdc_decode_solver(h, ai.ptr if ai else None, 0.0 if gamma is None else float(gamma),
                                                       None if sd is None else sd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ptrs,
@@ -469,7 +514,7 @@ class _GaussianDiffusionBase:
     def decompress(self, context, shape=None, sample_steps=None, init=None, eta=0, clip_denoised=None, bitrate_scale=None,
                    as_uint8=False, seed=None, gamma=None, sampler="ddim", spacing="index", samples=None, reduce=None, sample_chunk=None,
                    trajectory=None, trajectory_of="x0", trajectory_dtype="float32", tile=None, tile_overlap=None, tile_chunk=None, region=None,
-                   partial=False):
+                   partial=False, parallel=None, parallel_tol=None, return_info=False):
         """Decode half of compress(): context pyramid (= context_fn(...)["output"]) -> image.  `context`
         may also be the transmitted q_latent tensor [B, C, H/16, W/16]: it then goes through
         `context_fn.decode` first (compress_modules.py:68-74; cdc_compression_amd.compressor on the GPU) -- with
@@ -504,7 +549,20 @@ class _GaussianDiffusionBase:
         in a decoded segment; "present_region" (y0, x0, h, w), the bounding box in image pixels of the leading segments that are wholly
         there, over all images of the call, or None.  With tile=, region="present" decodes only the tiles that intersect that box --
         planned before the entropy decode, so a 30 % prefix costs 30 % of the sampler's time -- and returns that window, the tile
-        info merged into info (a CdcError when no segment is complete); a region tuple works as always."""
+        info merged into info (a CdcError when no segment is complete); a region tuple works as always.
+        parallel / parallel_tol (cdc_compression_amd.picard; cdc_decode_parallel): the decode by Picard sweeps over a window of
+        `parallel` sampler steps (True: 16; a window above sample_steps is the whole schedule) evaluated as rows of one batch program --
+        for the latency of a single image.  parallel_tol: the RMS change, in the image's [-1, 1] units, below which a row counts as
+        converged; default 1e-3, a quarter of the half-step of as_uint8's rounding -- a starting value, not a measured optimum.  0
+        reproduces the sequential chain of the B * window-row program in `sample_steps` sweeps.  sampler "ddim" only; eta != 0 needs a
+        seed; excludes tile=, samples=, trajectory= and partial=.  return_info=True -> (reconstruction, {"sweeps", "strides",
+        "max_residual", "max_stride", "rows_evaluated", "window", "tol"})."""
+        par = self._parallel_arg(parallel, parallel_tol, return_info)
+        if par is not None:
+            if partial:
+                raise ValueError("parallel excludes partial=")
+            tiled = next((v for v in (tile, tile_overlap, tile_chunk, region) if v is not None), None)
+            _picard.check_args(parallel, parallel_tol, self._steps(sample_steps, spacing), None, sampler, eta, seed, tiled, samples, trajectory)
         if partial:
             return self._decompress_partial(context, shape, sample_steps, init, eta, clip_denoised, bitrate_scale, as_uint8, seed, gamma, sampler,
                                             spacing, samples, reduce, sample_chunk, trajectory, tile, tile_overlap, tile_chunk, region)
@@ -576,10 +634,12 @@ class _GaussianDiffusionBase:
         if K is not None:
             return self._decompress_samples(context, all_seeds, K, (H, W), clip_denoised, eta, gamma, sampler, reduce, sample_chunk, as_uint8)
         rec = self._loop((B, 3, Hp, Wp), context, clip_denoised, frame.extend_init(h, init, B, H, W, Hp, Wp, dev), eta,
-                         seed, gamma, sampler, spec, (H, W))
+                         seed, gamma, sampler, spec, (H, W), par)
         rec, traj = rec if spec is not None else (rec, None)
         if (Hp, Wp) != (H, W) or as_uint8:
             rec = frame.crop(h, rec, H, W, dev, as_uint8=as_uint8)
+        if par is not None:
+            return self._with_info(rec, return_info)
         return rec if traj is None else (rec, traj)
 
     # ---- tiled decode (cdc_compression_amd.tiles) --------------------------------------------------------------------------
@@ -899,33 +959,42 @@ class GaussianDiffusionX(_GaussianDiffusionBase):
         self.lagrangian_beta = lagrangian
 
     def p_sample_loop(self, shape, context, clip_denoised=False, init=None, eta=0, seed=None, gamma=None, sampler=None, spacing=None,
-                      trajectory=None, trajectory_of="x0", trajectory_dtype="float32", window=None):
+                      trajectory=None, trajectory_of="x0", trajectory_dtype="float32", window=None, parallel=None, parallel_tol=None,
+                      return_info=False):
         """trajectory / trajectory_of / trajectory_dtype (cdc_compression_amd.trajectory): -> (image, Trajectory), the slots cropped
-        to `window` ((H, W) of the image inside the frame `shape`; None: the frame)."""
+        to `window` ((H, W) of the image inside the frame `shape`; None: the frame).
+        parallel / parallel_tol (cdc_compression_amd.picard; decompress states them): the decode by Picard sweeps over a window of
+        `parallel` steps; return_info=True -> (image, {"sweeps", "strides", "max_residual", ...})."""
         spec = self._trace_spec(trajectory, trajectory_of, trajectory_dtype, self.sample_steps, eta, seed)
         self._reschedule(sampler, spacing)
-        return self._loop(tuple(shape), context, clip_denoised, init, eta, seed, gamma, sampler, spec, window)
+        return self._with_info(self._loop(tuple(shape), context, clip_denoised, init, eta, seed, gamma, sampler, spec, window,
+                                          self._parallel_arg(parallel, parallel_tol, return_info)), return_info)
 
     def _frame_of(self, images, sample_steps=None, init=None, eta=0, seed=None, gamma=None, sampler="ddim", spacing="index",
-                  trajectory=None, trajectory_of="x0", trajectory_dtype="float32", rate_map=False, rdo=None, price_cells=None):
+                  trajectory=None, trajectory_of="x0", trajectory_dtype="float32", rate_map=False, rdo=None, price_cells=None,
+                  parallel=None, parallel_tol=None):
         self._seed_args(seed, gamma, init, frame.image_shape(images)[0])
         return self._compress_frame(images, sample_steps, init, eta,
                                     lambda shape, ctx, i, spec, win: self.p_sample_loop(shape, ctx, clip_denoised=True, init=i, eta=eta,
                                                                                         seed=seed, gamma=gamma, trajectory=spec,
-                                                                                        window=win),   # :223
+                                                                                        window=win, parallel=parallel,
+                                                                                        parallel_tol=parallel_tol),   # :223
                                     sampler=sampler, spacing=spacing, trace=(trajectory, trajectory_of, trajectory_dtype, seed),
                                     rate_map=rate_map, rdo=rdo, price_cells=price_cells)
 
     def compress(self, images, sample_steps=None, bpp_return_mean=True, init=None, eta=0, seed=None, gamma=None, sampler="ddim",
                  spacing="index", trajectory=None, trajectory_of="x0", trajectory_dtype="float32", rdo=None, target_bpp=None,
                  max_bytes=None, price_map=None, price_cells=None, tile=None, tile_overlap=None, tile_chunk=None, region=None, segment=None,
-                 hyper_groups=None):
+                 hyper_groups=None, parallel=None, parallel_tol=None, return_info=False):
         """trajectory=: -> (reconstruction, bpp, Trajectory) (cdc_compression_amd.trajectory).  rdo / target_bpp / max_bytes: the
         context model's rate control (compressor.compress_to_bytes); bpp is that of the symbols it chose.  price_map / price_cells
         (with one of them): its region-of-interest map, in pixels at the image's size or on the latent grid.
         tile / tile_overlap / tile_chunk / region: the decode half runs tiled (decompress states them); with a region
         -> (window, bpp, info).  segment / hyper_groups: the segment size and the hyper groups of the streams to be written
-        (compress_to_bytes): max_bytes counts them."""
+        (compress_to_bytes): max_bytes counts them.  parallel / parallel_tol / return_info: the decode half by Picard sweeps
+        (decompress states them); return_info=True appends the sweep dict to the result."""
+        par = self._parallel_check(parallel, parallel_tol, return_info, sample_steps, spacing, sampler, eta, seed, tile, tile_overlap,
+                                   tile_chunk, region, trajectory)
         if not (tile is None and tile_overlap is None and tile_chunk is None and region is None):
             return self._compress_tiled(images, (), dict(rdo=rdo, target_bpp=target_bpp, max_bytes=max_bytes, price_map=price_map, price_cells=price_cells,
                                                          segment=segment, hyper_groups=hyper_groups),
@@ -934,8 +1003,10 @@ class GaussianDiffusionX(_GaussianDiffusionBase):
                                         trajectory=trajectory)
         mu, cells = self._rdo_of(images, None, rdo, target_bpp, max_bytes, price_map, price_cells, segment, hyper_groups)
         rec, bpp, H, W, traj = self._frame_of(images, sample_steps, init, eta, seed, gamma, sampler, spacing, trajectory, trajectory_of,
-                                              trajectory_dtype, rdo=mu, price_cells=cells)
+                                              trajectory_dtype, rdo=mu, price_cells=cells, parallel=parallel, parallel_tol=parallel_tol)
         res = (self._window(rec, H, W), (bpp.mean() if bpp_return_mean else bpp))
+        if par is not None and return_info:
+            return res + (dict(self.parallel_info),)
         return res if traj is None else res + (traj,)
 
 
@@ -969,22 +1040,26 @@ class GaussianDiffusionEps(_GaussianDiffusionBase):
         self.vbr = vbr
 
     def p_sample_loop(self, shape, context, sample_mode, init=None, eta=0, seed=None, gamma=None, sampler=None, spacing=None,
-                      trajectory=None, trajectory_of="x0", trajectory_dtype="float32", window=None):
-        """trajectory / trajectory_of / trajectory_dtype / window: as GaussianDiffusionX.p_sample_loop."""
+                      trajectory=None, trajectory_of="x0", trajectory_dtype="float32", window=None, parallel=None, parallel_tol=None,
+                      return_info=False):
+        """trajectory / trajectory_of / trajectory_dtype / window / parallel / parallel_tol / return_info: as
+        GaussianDiffusionX.p_sample_loop."""
         spec = self._trace_spec(trajectory, trajectory_of, trajectory_dtype, self.sample_steps, eta, seed)
         if sample_mode != "ddim":
             raise NotImplementedError('sample_mode "ddpm" raises AttributeError in the reference '
                                       "(posterior_mean_coef1 undefined); only \"ddim\" is implemented")
         self._reschedule(sampler, spacing)
-        return self._loop(tuple(shape), context, self.clip_noise, init, eta, seed, gamma, sampler, spec, window)
+        return self._with_info(self._loop(tuple(shape), context, self.clip_noise, init, eta, seed, gamma, sampler, spec, window,
+                                          self._parallel_arg(parallel, parallel_tol, return_info)), return_info)
 
     def _frame_of(self, images, sample_steps=None, bitrate_scale=None, sample_mode="ddpm", init=None, eta=0, seed=None, gamma=None,
                   sampler="ddim", spacing="index", trajectory=None, trajectory_of="x0", trajectory_dtype="float32", rate_map=False,
-                  rdo=None, price_cells=None):
+                  rdo=None, price_cells=None, parallel=None, parallel_tol=None):
         self._seed_args(seed, gamma, init, frame.image_shape(images)[0])
         return self._compress_frame(images, sample_steps, init, eta,
                                     lambda shape, ctx, i, spec, win: self.p_sample_loop(shape, ctx, sample_mode, init=i, eta=eta, seed=seed,
-                                                                                        gamma=gamma, trajectory=spec, window=win),
+                                                                                        gamma=gamma, trajectory=spec, window=win,
+                                                                                        parallel=parallel, parallel_tol=parallel_tol),
                                     bitrate_scale, sampler=sampler, spacing=spacing,
                                     trace=(trajectory, trajectory_of, trajectory_dtype, seed), rate_map=rate_map, rdo=rdo,
                                     price_cells=price_cells)
@@ -993,9 +1068,12 @@ class GaussianDiffusionEps(_GaussianDiffusionBase):
                  bpp_return_mean=True, init=None, eta=0, seed=None, gamma=None, sampler="ddim", spacing="index",
                  trajectory=None, trajectory_of="x0", trajectory_dtype="float32", rdo=None, target_bpp=None, max_bytes=None,
                  price_map=None, price_cells=None, tile=None, tile_overlap=None, tile_chunk=None, region=None, segment=None,
-                 hyper_groups=None):
+                 hyper_groups=None, parallel=None, parallel_tol=None, return_info=False):
         """trajectory=: -> (reconstruction, bpp, Trajectory) (cdc_compression_amd.trajectory).  rdo / target_bpp / max_bytes /
-        price_map / price_cells / tile / tile_overlap / tile_chunk / region / segment / hyper_groups: as GaussianDiffusionX.compress."""
+        price_map / price_cells / tile / tile_overlap / tile_chunk / region / segment / hyper_groups / parallel / parallel_tol /
+        return_info: as GaussianDiffusionX.compress."""
+        par = self._parallel_check(parallel, parallel_tol, return_info, sample_steps, spacing, sampler, eta, seed, tile, tile_overlap,
+                                   tile_chunk, region, trajectory)
         if not (tile is None and tile_overlap is None and tile_chunk is None and region is None):
             if sample_mode != "ddim":
                 raise NotImplementedError('sample_mode "ddpm" raises AttributeError in the reference; only "ddim" is implemented')
@@ -1006,8 +1084,11 @@ class GaussianDiffusionEps(_GaussianDiffusionBase):
                                         trajectory=trajectory)
         mu, cells = self._rdo_of(images, bitrate_scale, rdo, target_bpp, max_bytes, price_map, price_cells, segment, hyper_groups)
         rec, bpp, H, W, traj = self._frame_of(images, sample_steps, bitrate_scale, sample_mode, init, eta, seed, gamma, sampler, spacing,
-                                              trajectory, trajectory_of, trajectory_dtype, rdo=mu, price_cells=cells)
+                                              trajectory, trajectory_of, trajectory_dtype, rdo=mu, price_cells=cells, parallel=parallel,
+                                              parallel_tol=parallel_tol)
         res = (self._window(rec, H, W), (bpp.mean() if bpp_return_mean else bpp))
+        if par is not None and return_info:
+            return res + (dict(self.parallel_info),)
         return res if traj is None else res + (traj,)
 
     def compress_best_of(self, images, samples, metric="psnr", seed=None, gamma=None, eta=0, sample_steps=None, sampler="ddim",

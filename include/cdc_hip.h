@@ -325,6 +325,65 @@ int cdc_sample_moments(cdc_handle *h, const float *samples, int B, int Kc, int64
 int cdc_sample_select(cdc_handle *h, const float *samples, const int *pick /* [B], host */, float *best, int B, int Kc, int64_t per_image,
                       int mem, void *stream);
 
+/* ---- parallel-in-time decode: Picard sweeps over a window of sampler steps (no reference counterpart: the reference's p_sample_loop
+ * walks the steps one by one; Shih et al., "Parallel Sampling of Diffusion Models", 2023; csrc/sampler_kernels.hip: window_update_kernel)
+ * One image per call is latency-bound: a batch program evaluates the U-Net on p rows in far less than p times the time of one row.  The
+ * sampler chain y_{j+1} = Phi_j(y_j) -- sampling order j = 0 .. steps-1, sample index i = steps-1-j, Phi_j the DDIM update of
+ * cdc_ddim_step at index i with the draws z(seed_b, draw i + 1) of the seeded decode -- is therefore solved by sweeps over a window of
+ * `window` = p steps: one sweep evaluates the U-Net on the p current guesses y_w .. y_{w+p-1}, each at its own step, as p rows of
+ * one batch program, and corrects all of them.
+ *
+ * THE SWEEP at window base w, rows m = 0 .. live-1, live = min(p, steps - w), y_w fixed, float32, every operation rounded on its own:
+ *       c_0 = 0
+ *       y'_{w+m+1} = Phi_{w+m}(y_{w+m}) + c_m           (y_{w+m}: the OLD guess, the one the U-Net was evaluated on)
+ *       c_{m+1}    = y'_{w+m+1} - y_{w+m+1}             (new minus old guess of the same state)
+ *       r_m        = sum over the image of (y'_{w+m+1} - y_{w+m+1})^2, squares in float32, sums in float64 in a fixed order
+ *   In exact arithmetic this is the Picard prefix sum y'_{w+m+1} = y_w + sum_{l <= m} (Phi_{w+l}(y_{w+l}) - y_{w+l}); written this way a
+ *   row whose predecessors have converged is Phi(y) + 0, the bits of the sequential update.  Row 0 is always final.
+ * THE STRIDE: s = max(1, the number of leading live rows with sqrt(r_m / (C H W)) <= tol in EVERY image): the window is shared by the
+ *   images of the call.  The window then slides by s; the positions it newly covers start as the last state computed, y'_{w+p} (the
+ *   constant guess); before the first sweep every state is y_0.  Rows past the end of the schedule are dead: their step index is
+ *   clamped, their results are ignored, and the program is not planned again for a short last window.
+ * tol = 0 accepts a row only when it did not change at all: `steps` sweeps (fewer only where leading rows repeat bitwise), and the
+ *   result is the sequential chain of the same program -- the decode of cdc_decode / cdc_decode_seeded at batch B * window, which
+ *   differs from their decode at batch B as two batch sizes differ.  CDC_CLIP_HALF clips the first B / 2 IMAGES of the call (all rows
+ *   of an image alike), where the sequential B * window-row program clips its first B * window / 2 rows: under that clip mode the two
+ *   are the same chain only for an even B.  A larger tol trades sweeps for a deviation from that chain of the
+ *   order of tol per accepted row; nothing bounds the accumulated deviation but the caller's own comparison.
+ *
+ * cdc_decode_parallel: init, gamma, seeds, eta, ctx, out, pred_mode, clip, mem and stream as cdc_decode_seeded (seeds may be NULL: eta
+ *   must then be 0, init given or the start image zeros).  eta != 0 needs seeds: a noise tensor is not supported.  The rows are laid
+ *   out [B][window], as cdc_decode_samples lays out [B][K]; ctx[l] holds B images and is staged by repetition.  2 <= window <= steps,
+ *   window <= 256, B * window <= 65535, B * window * ceil(C H W / 1024) <= 2^25 (the residual partial table), tol >= 0.  strides (nullable, host, `steps` ints): the stride of every sweep in order, then
+ *   zeros.  info (nullable): sweeps; rows_evaluated = sweeps * B * window, dead rows included; max_stride; max_residual, the largest
+ *   sqrt(r_m / (C H W)) among the rows 1 .. s-1 that the tolerance let pass (0 when there was none).
+ *   Every sweep ends with the read-back of its B * window residuals and a synchronisation of the stream: the stride is decided on the
+ *   host.  The call runs eagerly on one chain: cdc_set_decode_chains and CDC_GRAPH have no effect on it.  A trace (cdc_set_trace) or
+ *   noise frames (cdc_set_noise_frames) set on the handle are refused; the multistep update is not supported (its history makes Phi a
+ *   map of two states).  A range fault repeats the whole call in CDC_ARITH_BF16X3 like every other entry point.
+ * cdc_op_window_update: one sweep's update alone on given tensors, as cdc_op_ddim_update exposes the DDIM update.  fx [B][window][C][H][W]:
+ *   the model output of row m; y [B][window + 1][C][H][W]: the states y_w .. y_{w+window}, of which the entries 1 .. live are replaced by
+ *   the new guesses and the others kept; residuals (host, always): float64 [B][window], r_m of the live rows, 0 for a dead row.  w: the
+ *   window base in sampling order, 0 <= w < steps.  The kernel runs on the ring the decode uses: row m in slot (w + m) mod window.
+ * cdc_parallel_stride, cdc_parallel_row_steps: the two host functions of the sweep loop, without a handle or a device, for tests.
+ *   stride: THE STRIDE above from residuals [B][window] (sums of squares), the live rows and numel = C H W; a negative value for bad
+ *   arguments.  row_steps: out [window], the sample index of the state in every slot of an image's ring at window base w -- slot
+ *   (j mod window) holds y_j, j = w .. w + window - 1, index steps - 1 - j, clamped to 0 for a dead row.
+ * Profiling (cdc_prof_enable): a profiled cdc_decode_parallel adds two lines, "window update" and "window fill", at the end of the
+ *   per-op table (cdc_prof_op) of the program it runs on; they stay, with n = 0, for later calls on that program, so that table is
+ *   then two lines longer than a plain decode's.  The shifts of a sweep are timed under the program's "temb" line.
+ * CDC_ERR_INVALID, with a message naming the argument: window outside [2, steps] or above 256; B * window > 65535 or too many residual partials; tol < 0 or NaN;
+ *   eta != 0 without seeds; eta / gamma not finite; w outside the schedule; a trace or noise frames set; null pointers. */
+typedef struct { int sweeps; int rows_evaluated; int max_stride; double max_residual; } cdc_parallel_info;
+int cdc_decode_parallel(cdc_handle *h, const float *init /* nullable */, float gamma, const uint64_t *seeds /* nullable, [B], host */, float eta,
+                        const float *const *ctx /* B images */, int n_ctx, float *out /* [B][C][H][W] */, int B, int H, int W, int pred_mode,
+                        int clip, int window, float tol, int *strides /* nullable, [steps], host */, cdc_parallel_info *info /* nullable */,
+                        int mem, void *stream);
+int cdc_parallel_stride(const double *residuals /* [B][window] */, int B, int window, int live, double numel, double tol);
+int cdc_parallel_row_steps(int w, int window, int steps, int *out /* [window] */);
+int cdc_op_window_update(cdc_handle *h, const float *fx, float *y, const uint64_t *seeds /* nullable, [B], host */, float eta, int w, int window,
+                         double *residuals /* [B][window], host */, int B, int C, int H, int W, int pred_mode, int clip, int mem, void *stream);
+
 /* ---- measurement --------------------------------------------------------------------------- */
 
 /* ---- context decoder: Compressor.decode ---------------------------- */
