@@ -2,7 +2,8 @@
 // launch-program types, the handle, error plumbing, the range guard, and the functions that cross the files:
 //   cdc_weights.hip      manifest + parameter repacking (cdc_finalize_weights)
 //   cdc_planner.hip      the launch-program builder (Builder), the programs of the four handle kinds, the single-operator entry points
-//   cdc_api.hip          running a program, handle life cycle, U-Net / sampler / compressor entry points, profiling
+//   cdc_api.hip          running a program, handle life cycle, U-Net / compressor / metric / generator / tile entry points, profiling
+//   cdc_decode.hip       schedule and solver tables, the sampler step, the decode drivers (one chain, two chains, Picard windows)
 //   cdc_entropy_api.hip  entropy-coder entry points and the stream container
 #pragma once
 #include <math.h>
@@ -465,12 +466,14 @@ int run_pre(cdc_handle *h, hipStream_t st);
 int run_unet(cdc_handle *h, hipStream_t st, int step, bool skip_combine = false);
 int copy_in(cdc_handle *h, float *dst, const float *src, size_t n, int mem, hipStream_t st);
 int copy_out(cdc_handle *h, float *dst, const float *src, size_t n, int mem, hipStream_t st);
-int stage_ctx(cdc_handle *h, const float *const *ctx, int n_ctx, int B, int mem, hipStream_t st);
+int check_ctx(cdc_handle *h, const float *const *ctx, int n_ctx);      // n_ctx tensors, none null, for the program's context levels
+int stage_ctx(cdc_handle *h, const float *const *ctx, int n_ctx, int B, int mem, hipStream_t st, int row0 = 0);
 int stage_ctx_repeated(cdc_handle *h, const float *const *ctx, int n_ctx, int B, int K, int mem, hipStream_t st);
 int ensure_device(cdc_handle *h);
 hipStream_t pick_stream(cdc_handle *h, void *stream, int mem);
 int check_ready(cdc_handle *h);
 int require_kind(cdc_handle *h, HandleKind kind);
+// ---- cdc_decode.hip: the sampler and the decode drivers
 void drop_twin(cdc_handle *h);           // destroys the twin of a split decode, if any (it borrows what the caller is about to replace)
 
 // ---- range guard of the two-plane fp16 arithmetic ------------------------------------------------------------------

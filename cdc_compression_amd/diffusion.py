@@ -453,31 +453,26 @@ class _GaussianDiffusionBase:
             if ai is not None and ai.mem != mem:
                 raise _lib.CdcError("init and context must live in the same memory space")
 
+            sd = None if seeds is None else np.asarray(seeds, dtype=np.uint64)      # (kept alive until device_loop has run)
+            sptr = None if sd is None else sd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+            iptr = ai.ptr if ai else None
+            g = 0.0 if gamma is None else float(gamma)
+
             def device_loop():
                 if parallel is not None:
-                    sd = None if seeds is None else np.asarray(seeds, dtype=np.uint64)
                     strides = (ctypes.c_int * self.sample_steps)()
                     pinfo = _lib.ParallelInfo()
-                    _lib.check(h, L.cdc_decode_parallel(h, ai.ptr if ai else None, 0.0 if gamma is None else float(gamma),
-                                                        None if sd is None else sd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), float(eta),
-                                                        ptrs, len(actx), optr, B, H, W, pred, clip, parallel[0], parallel[1], strides,
-                                                        ctypes.byref(pinfo), mem, stream))
+                    _lib.check(h, L.cdc_decode_parallel(h, iptr, g, sptr, float(eta), ptrs, len(actx), optr, B, H, W, pred, clip, parallel[0],
+                                                        parallel[1], strides, ctypes.byref(pinfo), mem, stream))
                     self.parallel_info = {"window": parallel[0], "tol": parallel[1], "sweeps": int(pinfo.sweeps),
                                           "strides": [int(v) for v in strides[:pinfo.sweeps]], "max_stride": int(pinfo.max_stride),
                                           "rows_evaluated": int(pinfo.rows_evaluated), "max_residual": float(pinfo.max_residual)}
                 elif sampler == "dpmpp_2m":      # the multistep update in the device loop; the seeds serve the start image only
-                    sd = None if seeds is None else np.asarray(seeds, dtype=np.uint64)
-                    _lib.check(h, L.cdc_decode_solver(h, ai.ptr if ai else None, 0.0 if gamma is None else float(gamma),
-                                                      None if sd is None else sd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ptrs,
-                                                      len(actx), optr, B, H, W, pred, clip, mem, stream))
+                    _lib.check(h, L.cdc_decode_solver(h, iptr, g, sptr, ptrs, len(actx), optr, B, H, W, pred, clip, mem, stream))
                 elif seeds is not None:      # every draw from the generator in the sampler kernels: any eta stays in the device loop
-                    sd = np.asarray(seeds, dtype=np.uint64)
-                    _lib.check(h, L.cdc_decode_seeded(h, ai.ptr if ai else None, 0.0 if gamma is None else float(gamma),
-                                                      sd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), float(eta), ptrs, len(actx), optr,
-                                                      B, H, W, pred, clip, mem, stream))
+                    _lib.check(h, L.cdc_decode_seeded(h, iptr, g, sptr, float(eta), ptrs, len(actx), optr, B, H, W, pred, clip, mem, stream))
                 else:
-                    _lib.check(h, L.cdc_decode(h, ai.ptr if ai else None, ptrs, len(actx), optr, B, H, W, pred,
-                                               clip, mem, stream))
+                    _lib.check(h, L.cdc_decode(h, iptr, ptrs, len(actx), optr, B, H, W, pred, clip, mem, stream))
             if trace is None:
                 device_loop()
                 return out

@@ -1,7 +1,7 @@
 """Parallel-in-time decode (include/cdc_hip.h: cdc_decode_parallel): the stride rule, the window bookkeeping and the
 argument rules, in plain Python so that they can be read and tested without a device.
 
-The library's host loop (csrc/cdc_api.hip: window_stride, window_row_steps) is the code that decides; `stride` and `row_steps` here
+The library's host loop (csrc/cdc_decode.hip: window_stride, window_row_steps) is the code that decides; `stride` and `row_steps` here
 restate it, and tests/test_picard_host.py runs the same hand-made tables through both (cdc_parallel_stride, cdc_parallel_row_steps), so
 the two cannot drift apart unnoticed.  `solve` is the sweep loop over any chain of maps, which the tests run on a float64 toy chain.
 A sampler chain y_{j+1} = Phi_j(y_j), j = 0 .. N-1, is solved by sweeps over a window of p steps at base w (Shih et al., "Parallel Sampling of Diffusion Models", 2023):
